@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- solver substeps/s of the HNanoSolver hot path on MI355X, with the pressure stencil's HBM roofline.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 256|128|64|plume] [--iterations 50]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 256|128|64|plume] [--iterations 50] [--full] [--dump-outputs DIR]
     (N > 1 without a launcher: bench.py starts `python -m torch.distributed.run --nproc-per-node N bench.py ...` itself,
     as a child process, before it touches the GPU; under a launcher -- WORLD_SIZE set -- it is a rank, as before)
 
@@ -15,18 +15,26 @@ e.g. plume1024 = BASELINE.json's 1024^3-extent sparse grid, split across the ran
 voxels of u / div / p / phi over RCCL where the single-GPU code has a kernel boundary that a stencil crosses, under the
 interior kernels (csrc/hns_dist_*.hip; hnanosolver_amd/dist.py is the host mirror). `value` = slab-substeps/s summed over ranks = N x (global substeps/s).
 
+A plain run sets up, warms up, times the K steps, writes its outputs if --dump-outputs is given and prints the line: the
+headline and the pressure loop's roofline (hipEvents inside the timed steps). Everything that takes work of its own --
+`roofline.kernels`, `cpu_baseline`, the `strong_scaling` records and, for N > 1, the check against the single-GPU run and of
+the ghost voxels -- runs only with --full (each can still be left out there with its --no-* option).
+
+--dump-outputs DIR: after the timed steps, what the last one computed -- the fields a caller of the step receives (`vel`,
+`density`) -- as DIR/<name>.npy in float32; above 64 MB in all, the same fixed, seeded sample of voxels from every field.
+
 Rank 0 prints ONE JSON line. `roofline`: the SOR kernel (`kernel` names the form the library picked for this grid size).
 Algorithmic bytes are 12 B/voxel per red+black iteration (read p, read div, write p once each); a launch of the temporally
 blocked form holds `iterations_per_launch` iterations, so per KERNEL LAUNCH -- the unit of `algorithmic_bytes_per_launch`,
 `ms_per_launch` and `traffic`, and what rocprofv3 --stats lists -- they are 12 B/voxel x iterations per launch; `achieved` is
-their ratio either way. Times come from hipEvents recorded on the launch stream around the pressure loop of every timed step. `roofline.kernels` carries the same figures for all five kernels of the substep (each bracketed by hipEvents
+their ratio either way. Times come from hipEvents recorded on the launch stream around the pressure loop of every timed step. `roofline.kernels` (--full) carries the same figures for all five kernels of the substep (each bracketed by hipEvents
 on the launch stream, in a short pass of its own after the timed region) and `roofline.substep` the whole substep
 against 688 B/voxel. `traffic` is NOT measured by this
 run (bench.py cannot run rocprofv3 on itself): it is the PMC-derived HBM bytes per launch from the builder's committed
 rocprofv3 passes of this same command (profiles/pmc_latest.json: per configuration and kernel), reported only while they
 were taken from the kernel source this library was built from, and labelled with `traffic_source`. Three fractions of the
 8 TB/s peak: `frac` (contractual: 12 B/voxel per ITERATION), `frac_compulsory` (12 B/voxel per LAUNCH: what the kernel must
-move) and `frac_moved` (what it did move, PMC); `roofline.kernels` carries `traffic` / `frac_moved` for all five kernels. `cpu_baseline`: the oracle (C restatement
+move) and `frac_moved` (what it did move, PMC); `roofline.kernels` carries `traffic` / `frac_moved` for all five kernels. `cpu_baseline` (--full): the oracle (C restatement
 of the reference kernels, OpenMP over leaves) on the host cores, rank 0 at N=1 only, on a bounded sample.
 """
 from __future__ import annotations
@@ -68,26 +76,56 @@ def parse():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", default="256", help="256 (default, roofline config) | 128 | 64 | plume")
     ap.add_argument("--iterations", type=int, default=50)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline: per-kernel figures (roofline.kernels), the CPU baseline, the strong_scaling "
+                         "records of the default workload and, for N > 1, the start-up check against the single-GPU run and the ghost-voxel check")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32; a fixed, seeded sample of voxels above 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--partition", action="store_true", help="N > 1: split ONE --config domain across the ranks (strong scaling) instead of one slab per rank")
     ap.add_argument("--sweeps-per-exchange", type=int, default=0, help="N > 1: fused SOR sweeps between two halo refreshes of p (1..4, 0 = library default)")
     ap.add_argument("--transport", choices=["auto", "rccl", "ipc"], default="rccl",
                     help="N > 1 halo transport: rccl (default) = RCCL send/recv groups on a communication stream under the interior kernels; ipc = one-sided "
                          "stores into hipIpc-mapped peer memory, every kernel delivering its own halo (has only run between processes sharing ONE GPU so "
-                         "far: opt-in); auto = ipc if it connects and reproduces three RCCL substeps bit for bit on this machine, else rccl. Whatever "
-                         "runs is first checked against the single-GPU result of the whole domain (config.verified)")
-    ap.add_argument("--no-verify", action="store_true", help="N > 1: skip the start-up comparison of the partitioned run with the single-GPU run of the whole domain")
+                         "far: opt-in); auto = ipc if it connects and reproduces three RCCL substeps bit for bit on this machine, else rccl. With --full, "
+                         "whatever runs is first checked against the single-GPU result of the whole domain (config.verified)")
+    ap.add_argument("--no-verify", action="store_true", help="N > 1, --full: skip the start-up comparison of the partitioned run with the single-GPU run of the whole domain")
     ap.add_argument("--share-one-gpu", action="store_true",
                     help="builder's check on a 1-GPU box: all N ranks on cuda:0, host rendezvous over gloo, --transport ipc (RCCL refuses two ranks on one device)")
     ap.add_argument("--cook", action="store_true", help="time the cook-equivalent hns_compute_sim call (upload + grid build + substep + download) instead")
-    ap.add_argument("--full", action="store_true", help="time the FULL Compute_Sim substep instead (HNanoSolver.cu:150-356 on device-resident fields: five advected scalars, "
+    ap.add_argument("--full-substep", action="store_true", help="time the FULL Compute_Sim substep instead (HNanoSolver.cu:150-356 on device-resident fields: five advected scalars, "
                                                         "combustion, buoyancy; SURVEY 8d's 812 B/voxel row) and print its own JSON line; single GPU")
     ap.add_argument("--strong-timeout", type=int, default=600, help="seconds EACH of the strong_scaling records may take before a watchdog thread abandons it and prints the line without it (0 = no limit)")
-    ap.add_argument("--no-one-sided", action="store_true", help="N > 1, default workload: skip the third record `strong_scaling_one_sided` (config 5 again over the one-sided transport "
+    ap.add_argument("--no-one-sided", action="store_true", help="N > 1, default workload, --full: skip the third record `strong_scaling_one_sided` (config 5 again over the one-sided transport "
                                                                  "where it connects and reproduces RCCL bit for bit)")
-    ap.add_argument("--no-strong", action="store_true", help="default workload only: skip the second record `strong_scaling` (BASELINE config 5, the 1024^3-extent plume "
+    ap.add_argument("--no-strong", action="store_true", help="default workload, --full: skip the second record `strong_scaling` (BASELINE config 5, the 1024^3-extent plume "
                                                               "as ONE domain over the N ranks)")
     return ap.parse_args()
+
+
+DUMP_MAX_BYTES = 64 * 2**20
+DUMP_SEED = 688
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: `arrays` (name -> float32 array, one row per voxel) as out_dir/<name>.npy. Above DUMP_MAX_BYTES in all,
+    every array keeps the same rows: a sample drawn with a fixed seed and sorted, so that it depends only on the voxel count."""
+    os.makedirs(out_dir, exist_ok=True)
+    n = len(next(iter(arrays.values())))
+    per_voxel = sum(a.nbytes // n for a in arrays.values())
+    rows = None
+    if n * per_voxel > DUMP_MAX_BYTES - 4096 * len(arrays):  # (room for the .npy headers)
+        k = (DUMP_MAX_BYTES - 4096 * len(arrays)) // per_voxel
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=k, replace=False))
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a if rows is None else a[rows], dtype=np.float32))
+
+
+def sim_outputs(sim, names, n_vox):
+    """what a caller of the device-resident substep receives: the velocity and the float fields, downloaded"""
+    out = {"vel": np.empty((n_vox, 3), dtype=np.float32), **{n: np.empty(n_vox, dtype=np.float32) for n in names}}
+    sim.download(out)
+    return out
 
 
 def cook_equivalent(args):
@@ -381,6 +419,8 @@ def full_substep(args):
 
     sim.timing(args.steps)
     elapsed = timed_steps(step, args.steps, args.warmup, 1, False)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, sim_outputs(sim, names, n_vox))
     p_ms, p_iters = sim.pressure_time()
     ms = 1e3 * elapsed / args.steps
     sor_form, sor_launches, _ = D.rbgs_plan(grid, args.iterations)
@@ -425,6 +465,8 @@ def full_substep(args):
 
 def main():
     args = parse()
+    if args.dump_outputs and (args.gpus > 1 or args.cook):
+        raise SystemExit("bench.py --dump-outputs: single-GPU substep only (not with --gpus N > 1 or --cook)")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args))
     import torch
@@ -456,9 +498,9 @@ def main():
     if args.cook:
         cook_equivalent(args)
         return
-    if args.full:
+    if args.full_substep:
         if world != 1:
-            raise SystemExit("bench.py --full is the single-GPU Compute_Sim substep")
+            raise SystemExit("bench.py --full-substep is the single-GPU Compute_Sim substep")
         full_substep(args)
         return
     origins, R = fields.config_leaves(args.config)
@@ -497,7 +539,9 @@ def main():
                               transport=args.transport, reference_transport="ipc" if args.share_one_gpu else "rccl")
         n_vox_rank = runner.n_owned * 512
         step, pressure_time, stage_times = runner.step, runner.pressure_time, None
-        if not args.no_verify:
+        if not args.full:
+            runner.verified_note = "not checked (bench.py --full compares it with the single-GPU run of the whole domain)"
+        elif not args.no_verify:
             try:
                 runner.verify_against_single_gpu()
             except Exception as e:  # noqa: BLE001 -- the check must not cost the measurement; it says that it did not run
@@ -508,10 +552,12 @@ def main():
             runner.timing_on(args.steps)
 
     elapsed = timed_steps(step, args.steps, args.warmup, world, args.share_one_gpu, before_timed=timing_on)
-    ghosts_note = ghost_note_of(runner) if world > 1 else None
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, sim_outputs(sim, ["density"], n_vox_rank))
+    ghosts_note = ghost_note_of(runner) if world > 1 and args.full else None
     p_ms, launches = pressure_time()  # (launches: red+black iterations inside the bracketed pressure loops)
     sor_form, sor_launches, sor_k = D.rbgs_plan(grid, args.iterations) if world == 1 else ("", args.iterations, 1)
-    stages, n_sub = stage_times() if stage_times else ({}, 0)
+    stages, n_sub = stage_times() if stage_times and args.full else ({}, 0)
     if rank == 0:
         ms_per_step = 1e3 * elapsed / args.steps
         value = (1 if args.partition and world > 1 else world) * args.steps / elapsed  # slab-substeps/s over all ranks (partitioned: substeps/s of the one domain)
@@ -624,7 +670,7 @@ def main():
                 "substep": {"algorithmic_bytes": sub_bytes, "ms": ms_per_step, "achieved": sub_gbs, "frac": sub_gbs / HBM_PEAK_GBS},
             },
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(origins, R, args.iterations)
     # One driver command, all curves: the default workload also runs BASELINE config 5 as one domain over the same ranks (collective: every rank takes part) -- `strong_scaling`
     # over the transport of the headline (RCCL by default) and, for N > 1, `strong_scaling_one_sided`: --transport auto semantics, i.e. the one-sided transport (every kernel
@@ -635,7 +681,7 @@ def main():
     # the record that hung, and every rank leaves the process at once without touching the GPU again (a hung collective cannot be unwound; nothing re-execs). All ranks exit 0:
     # the headline in the line is complete and valid, the abandoned record says so itself, and a non-zero exit would make the launcher discard the line.
     records = []
-    if args.config == "256" and not args.partition and not args.no_strong:
+    if args.full and args.config == "256" and not args.partition and not args.no_strong:
         records.append(("strong_scaling", None))
         if world > 1 and not args.no_one_sided:
             records.append(("strong_scaling_one_sided", "auto"))

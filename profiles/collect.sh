@@ -1,6 +1,6 @@
 #!/bin/bash
 # profiles/collect.sh <tag> -- run on the GPU box (via gpurun) from the repo root; writes everything under gpurun_out/<tag>/:
-#   bench_<config>.json             python bench.py [--config c]   (default config with the CPU baseline)
+#   bench_<config>.json             python bench.py --full [--config c]   (default config with the CPU baseline)
 #   kernel_stats.csv                rocprofv3 --kernel-trace --stats of the default bench command
 #   pmc.json                        per-kernel PMC means, one counter group per pass (never combined with other tracing)
 # Copy what should be judged into profiles/ afterwards (gpurun_out/ is scratch).
@@ -10,9 +10,9 @@ root=$GRAFT_REPO_ROOT
 out=$root/gpurun_out/$tag
 rm -rf $out && mkdir -p $out
 cd $root
-python3 bench.py > $out/bench_256.json 2> $out/bench_256.err
-for c in 128 64 plume plume1024; do python3 bench.py --config $c --no-cpu-baseline > $out/bench_$c.json 2>> $out/bench_other.err; done
-python3 bench.py --config 512 --steps 5 --no-cpu-baseline > $out/bench_512.json 2>> $out/bench_other.err
+python3 bench.py --full > $out/bench_256.json 2> $out/bench_256.err
+for c in 128 64 plume plume1024; do python3 bench.py --full --config $c --no-cpu-baseline > $out/bench_$c.json 2>> $out/bench_other.err; done
+python3 bench.py --full --config 512 --steps 5 --no-cpu-baseline > $out/bench_512.json 2>> $out/bench_other.err
 # one rank of a multi-GPU run before any wire time (local / loopback transports of hns_dist), and against emulated wire time
 for a in "256 2 4" "256 2 2" "256 2 1" "128 2 4" "128 2 1" "plume1024 8 4 --partition" "plume1024 8 1 --partition"; do python3 profiles/micro/dist_overhead.py $a >> $out/dist_overhead.jsonl 2>> $out/bench_other.err; done
 for w in 0 10 20 40; do python3 profiles/micro/dist_profile.py rank 4 $w 2>> $out/bench_other.err | grep "ms per substep" >> $out/dist_wire_sweep.txt; done
@@ -24,12 +24,12 @@ for c in 512 plume1024; do bash profiles/micro/pmc_sor.sh ${tag}_$c $c > $out/pm
 python3 bench.py --cook > $out/cook_256.json 2>> $out/bench_other.err
 python3 bench.py --cook --config 128 > $out/cook_128.json 2>> $out/bench_other.err
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -- python3 $root/bench.py --no-cpu-baseline > $out/stats.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -- python3 $root/bench.py --full --no-cpu-baseline > $out/stats.log 2>&1
 cp $(find $out/stats -name "*kernel_stats.csv" | head -1) $out/kernel_stats.csv
 dirs=""
 for grp in "FETCH_SIZE" "WRITE_SIZE" "TCC_HIT_sum TCC_MISS_sum" "TA_TA_BUSY_sum GRBM_GUI_ACTIVE" "SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAVE_CYCLES" "SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_WAIT_ANY" "TCP_TOTAL_CACHE_ACCESSES_sum TCP_TCC_READ_REQ_sum" "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE"; do
 	d=$out/pmc_$(echo $grp | tr ' ' '_' | cut -c1-40)
-	rocprofv3 --pmc $grp --output-format csv -d $d -- python3 $root/bench.py --steps 3 --warmup 1 --no-cpu-baseline > $d.log 2>&1
+	rocprofv3 --pmc $grp --output-format csv -d $d -- python3 $root/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline > $d.log 2>&1
 	dirs="$dirs $d"
 done
 python3 $root/profiles/summarize_pmc.py $out/pmc.json $dirs > $out/pmc_summary.txt

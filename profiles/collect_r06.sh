@@ -3,9 +3,9 @@
 #   pmc_latest.json            HBM-side bytes per kernel launch (2 x FETCH_SIZE + WRITE_SIZE; separate --pmc passes, counters only) of every
 #                              kernel of the substep at 256 / 512 / plume1024 / 128, stamped with the kernel-source hash bench.py checks
 #   pmc_<config>.json          the raw per-kernel PMC means of those passes (256: plus the TA / SQ / LDS groups)
-#   bench_<config>.json        python bench.py [--config c] run AFTER pmc_latest.json is in place (256 with the CPU baseline)
+#   bench_<config>.json        python bench.py --full [--config c] run AFTER pmc_latest.json is in place (256 with the CPU baseline)
 #   kernel_stats_<config>.csv  rocprofv3 --kernel-trace --stats of bench.py at 256 / 128 / 512 / plume1024
-#   full_256.json / kernel_stats_full256.csv   python bench.py --full (the whole Compute_Sim substep, SURVEY 8d's last row) and its rocprofv3 kernel statistics
+#   full_256.json / kernel_stats_full256.csv   python bench.py --full-substep (the whole Compute_Sim substep, SURVEY 8d's last row) and its rocprofv3 kernel statistics
 #   `quick`: the memory-side passes and bench lines only
 set -u
 tag=${1:-r06}; quick=${2:-}
@@ -36,7 +36,7 @@ if [ -z "$quick" ]; then
 	dirs=""
 	for grp in "FETCH_SIZE" "WRITE_SIZE" "TCC_HIT_sum TCC_MISS_sum" "TA_TA_BUSY_sum GRBM_GUI_ACTIVE" "TCP_TOTAL_CACHE_ACCESSES_sum TCP_TCC_READ_REQ_sum" "SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAVE_CYCLES SQ_WAVES SQ_INSTS_VMEM_RD SQ_INSTS_LDS"; do
 		d=$out/pmc_full256_$(echo $grp | tr ' ' '_' | cut -c1-40)
-		rocprofv3 --pmc $grp --output-format csv -d $d -- python3 $root/bench.py --full --steps 3 --warmup 1 > $d.log 2>&1
+		rocprofv3 --pmc $grp --output-format csv -d $d -- python3 $root/bench.py --full-substep --steps 3 --warmup 1 > $d.log 2>&1
 		dirs="$dirs $d"
 	done
 	python3 $root/profiles/summarize_pmc.py $out/pmc_full256.json $dirs > $out/pmc_full256_summary.txt
@@ -70,22 +70,22 @@ print(json.dumps({c: {k: round(v["hbm_bytes_per_kernel_launch"] / 1e6, 1) for k,
 PY
 cp $out/pmc_latest.json $root/profiles/pmc_latest.json
 cd $root
-python3 bench.py > $out/bench_256.json 2> $out/bench_256.err   # (the default line: with cpu_baseline and, as strong_scaling, config 5 on the one GPU)
-for c in 128 64 plume plume1024; do python3 bench.py --config $c --no-cpu-baseline > $out/bench_$c.json 2>> $out/bench_other.err; done
-python3 bench.py --config 512 --steps 5 --no-cpu-baseline > $out/bench_512.json 2>> $out/bench_other.err
+python3 bench.py --full > $out/bench_256.json 2> $out/bench_256.err   # (the default line: with cpu_baseline and, as strong_scaling, config 5 on the one GPU)
+for c in 128 64 plume plume1024; do python3 bench.py --full --config $c --no-cpu-baseline > $out/bench_$c.json 2>> $out/bench_other.err; done
+python3 bench.py --full --config 512 --steps 5 --no-cpu-baseline > $out/bench_512.json 2>> $out/bench_other.err
 if [ -z "$quick" ]; then
-	python3 bench.py --full > $out/full_256.json 2>> $out/bench_other.err
-	python3 bench.py --full --config 512 --steps 5 > $out/full_512.json 2>> $out/bench_other.err
-	python3 bench.py --full --config 128 > $out/full_128.json 2>> $out/bench_other.err
+	python3 bench.py --full-substep > $out/full_256.json 2>> $out/bench_other.err
+	python3 bench.py --full-substep --config 512 --steps 5 > $out/full_512.json 2>> $out/bench_other.err
+	python3 bench.py --full-substep --config 128 > $out/full_128.json 2>> $out/bench_other.err
 	python3 bench.py --cook > $out/cook_256.json 2>> $out/bench_other.err
 	python3 bench.py --cook --config 128 > $out/cook_128.json 2>> $out/bench_other.err
 	cd /tmp
 	for c in 256 128 512 plume1024; do
-		rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats_$c -- python3 $root/bench.py --config $c --no-cpu-baseline --no-strong > $out/stats_$c.log 2>&1
+		rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats_$c -- python3 $root/bench.py --full --config $c --no-cpu-baseline --no-strong > $out/stats_$c.log 2>&1
 		cp $(find $out/stats_$c -name "*kernel_stats.csv" | head -1) $out/kernel_stats_$c.csv
 		rm -rf $out/stats_$c
 	done
-	rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats_full -- python3 $root/bench.py --full --steps 10 > $out/stats_full.log 2>&1
+	rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats_full -- python3 $root/bench.py --full-substep --steps 10 > $out/stats_full.log 2>&1
 	cp $(find $out/stats_full -name "*kernel_stats.csv" | head -1) $out/kernel_stats_full256.csv
 	rm -rf $out/stats_full
 fi

@@ -7,7 +7,7 @@ cd /tmp && export TMPDIR=/tmp
 dirs=""
 for grp in "FETCH_SIZE" "WRITE_SIZE" "TCC_HIT_sum TCC_MISS_sum" "TCP_TCC_READ_REQ_sum TCP_TOTAL_CACHE_ACCESSES_sum"; do
 	d=$out/$(echo $grp | tr ' ' '_' | cut -c1-30)
-	rocprofv3 --pmc $grp --output-format csv -d $d -- python3 $root/bench.py --steps 2 --warmup 1 --no-cpu-baseline --config $cfg > $d.log 2>&1
+	rocprofv3 --pmc $grp --output-format csv -d $d -- python3 $root/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --config $cfg > $d.log 2>&1
 	dirs="$dirs $d"
 done
 python3 $root/profiles/summarize_pmc.py $out/pmc.json $dirs | grep -A9 "k_rbgs_pair<false>"

@@ -11,7 +11,7 @@ cd /tmp && export TMPDIR=/tmp
 dirs=""
 for grp in "FETCH_SIZE" "WRITE_SIZE"; do
 	d=$out/pmc_$grp
-	rocprofv3 --pmc $grp --output-format csv -d $d -- python3 $root/bench.py --steps 3 --warmup 1 --no-cpu-baseline > $d.log 2>&1
+	rocprofv3 --pmc $grp --output-format csv -d $d -- python3 $root/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline > $d.log 2>&1
 	dirs="$dirs $d"
 done
 python3 $root/profiles/summarize_pmc.py $out/pmc.json $dirs > $out/pmc_summary.txt

@@ -337,7 +337,7 @@ def test_bench_py_as_two_processes_sharing_the_gpu(extra, tmp_path):
         so.bind(("127.0.0.1", 0))
         port = so.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
-           os.path.join(root, "bench.py"), "--gpus", "2", "--share-one-gpu", "--transport", "auto", "--steps", "3", "--warmup", "1", "--iterations", "10"] + (extra or ["--config", "64"])
+           os.path.join(root, "bench.py"), "--gpus", "2", "--share-one-gpu", "--transport", "auto", "--steps", "3", "--warmup", "1", "--iterations", "10", "--full"] + (extra or ["--config", "64"])
     p = subprocess.run(cmd, cwd=root, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
@@ -365,7 +365,7 @@ def test_bench_py_launches_its_own_ranks():
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--share-one-gpu", "--steps", "3", "--warmup", "1", "--iterations", "10", "--config", "64"]
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--share-one-gpu", "--steps", "3", "--warmup", "1", "--iterations", "10", "--config", "64", "--full"]
     p = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
@@ -387,7 +387,7 @@ def test_bench_py_default_line_carries_the_strong_scaling_record():
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--share-one-gpu", "--steps", "2", "--warmup", "1", "--iterations", "6"]
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--share-one-gpu", "--steps", "2", "--warmup", "1", "--iterations", "6", "--full"]
     p = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
@@ -408,6 +408,32 @@ def test_bench_py_default_line_carries_the_strong_scaling_record():
     assert "verified bit for bit" in o["config"]["parallelism"], o["config"]["parallelism"]
     assert "bit-identical to the single-GPU run of the whole domain" in o["config"]["verified"], o["config"]["verified"]
     assert o["config"]["halo"]["sweeps_per_exchange"] == 2 and o["config"]["halo"]["exchanges"] == 0
+
+
+def test_bench_py_plain_line_and_dumped_outputs(tmp_path):
+    """`python bench.py --gpus 1` without --full: the headline line alone, exactly --steps timed steps; --dump-outputs writes what the
+    last timed step computed -- after warmup + steps substeps, equal to the same substeps run here."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    out = tmp_path / "dump"
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2", "--iterations", "6", "--config", "64", "--dump-outputs", str(out)]
+    p = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-3000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, p.stdout[-2000:]
+    j = json.loads(lines[0])
+    assert j["steps"] == 3 and j["ms_per_step"] > 0 and j["unit"] == "substeps/s" and j["dtype"] == "f32"
+    assert "cpu_baseline" not in j and "strong_scaling" not in j and j["roofline"]["kernels"] == {}
+    origins, R = fields.config_leaves("64")
+    _, want = single_grid(origins, R, ["density"], 6, 5)
+    for name in ("vel", "density"):
+        got = np.load(out / f"{name}.npy")
+        assert got.dtype == np.float32 and np.array_equal(got, want[name]), name
 
 
 def test_unconnected_ranks_refuse_to_step():
