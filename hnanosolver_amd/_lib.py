@@ -81,6 +81,7 @@ SIGNATURES = {
     "hns_gather_leaves": (_i, [_vp, _u64, _vp, _u64, _vp, _i, _i, _vp]),
     "hns_scatter_leaves": (_i, [_vp, _u64, _i, C.POINTER(C.c_void_p)]),
     "hns_dilate_leaves": (_i, [_vp, _u64, _vp, _i, _vp, _u64, C.POINTER(C.c_uint64)]),
+    "hns_dilate_leaf_masks": (_i, [_vp, _u64, _vp, _i, _vp, _vp, _u64, C.POINTER(C.c_uint64)]),
     "hns_union_leaves": (_i, [_vp, _u64, _vp, _u64, _vp, _u64, C.POINTER(C.c_uint64)]),
     "hns_compute_sim": (_i, [_vp, C.POINTER(hns_field), _i, _i, _f, _f, C.POINTER(hns_combustion_params), _i, _vp]),
     "hns_compute_sim_resident": (_i, [_vp, C.POINTER(hns_field), _i, C.c_char_p, C.POINTER(C.c_int), _i, _f, _f, C.POINTER(hns_combustion_params), _i, _vp]),
@@ -103,6 +104,10 @@ SIGNATURES = {
     "hns_sim_field_ptr": (_vp, [_vp, C.c_char_p]),
     "hns_sim_divergence_ptr": (_vp, [_vp]),
     "hns_sim_pressure_ptr": (_vp, [_vp]),
+    "hns_sim_set_active_masks": (_i, [_vp, _vp, _vp]),
+    "hns_sim_active_masks": (_i, [_vp, _vp, _vp]),
+    "hns_sim_regrid": (_vp, [_vp, _i, _vp, _u64, _vp, _vp, _vp, _ip]),
+    "hns_sim_regrid_times": (_i, [_vp, C.POINTER(C.c_float)]),
     "hns_dev_advect_vector": (_i, [_vp, _fp, _fp, _fp, _i, _f, _f, _vp]),
     "hns_dev_advect_scalar": (_i, [_vp, _fp, _fp, _fp, _fp, _i, _f, _f, _vp]),
     "hns_dev_advect_scalars": (_i, [_vp, _fp, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _i, _fp, _i, _f, _f, _vp]),

@@ -61,46 +61,7 @@ extern "C" int hns_device_count(void) {
 // device-resident simulation state
 // ---------------------------------------------------------------------------------------------------------------
 
-struct hns_sim {
-	hns_grid* grid = nullptr;
-	uint64_t n = 0;  // voxels
-	std::vector<std::string> names;
-	std::vector<float*> cur;  // current value of each float field (the reference's d_inputs)
-	std::vector<float*> nxt;  // scratch / next value        (the reference's d_outputs)
-	float* vel = nullptr;  // d_velocity      (Vec3f AoS, 3n floats: the host/reference layout, so H2D/D2H are plain copies)
-	float* adv = nullptr;  // d_advectedVel
-	float* tmp = nullptr;  // out-of-place vorticity target; the buoyed u* of the fused divergence / combustion / buoyancy launch
-	float* q4 = nullptr;   // {fuel, waste, temperature, flame} as one 16-byte element per voxel between that launch and advect_scalars (sims that hold those four fields)
-	float* div = nullptr;
-	float* p_a = nullptr;
-	float* p_b = nullptr;
-	float* p_result = nullptr;  // whichever of p_a/p_b holds the last solve
-	// optional hipEvent bracketing of the pressure hot loop (hns_sim_timing), on the stream the kernels run on
-	bool timing = false;
-	std::vector<hipEvent_t> ev;  // start/stop pairs
-	size_t ev_used = 0;
-	long long timed_launches = 0;
-	bool stage_timing = false;    // hns_sim_stage_timing: also bracket the five stages of hns_sim_core_substep
-	std::vector<hipEvent_t> sev;  // stage boundaries: six per substep
-	size_t sev_used = 0;
-	hipStream_t xfer = nullptr;  // transfer stream + hand-off events of the pipelined operator path (compute_sim_pipelined)
-	hipEvent_t xev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-	bool cached = false, in_use = false;  // owned by the grid's cook cache / currently lent to an operator call
-	// Device-resident feedback across cooks (hns_compute_sim_resident): a signature of what the last hns_compute_sim on this state handed
-	// back for the velocity and for float field i -- those bytes are still in `vel` / cur[i]. 0 = nothing to vouch for (any upload clears it).
-	uint64_t sig_vel = 0, dig_vel = 0;  // (sig: sample signature; dig: full digest, 0 = not taken)
-	unsigned long long* d_dig = nullptr;  // 16 accumulators of the digest kernels (hns_digest.hpp): a slice of the arena
-	unsigned long long* h_dig = nullptr;  // pinned host copy of them (read asynchronously on the cook's own stream)
-	std::vector<uint64_t> sig_cur, dig_cur;
-	void* arena = nullptr;  // every field above is a slice of this one allocation (see the arena pool below)
-	size_t arena_bytes = 0;
-	int device = -1;
-	int find(const char* name) const {
-		for (size_t i = 0; i < names.size(); ++i)
-			if (names[i] == name) return (int)i;
-		return -1;
-	}
-};
+// (struct hns_sim: hns_internal.hpp -- hns_regrid.hip moves a sim onto a new grid)
 
 // ---- arena pool ------------------------------------------------------------------------------------------------
 // A sim's fields are slices of ONE device allocation, and allocations that are no longer needed go to a small
@@ -210,8 +171,11 @@ extern "C" void hns_sim_destroy(hns_sim* s) {
 	for (hipEvent_t e : s->sev) (void)hipEventDestroy(e);
 	for (hipEvent_t e : s->xev)
 		if (e) (void)hipEventDestroy(e);
+	for (hipEvent_t e : s->rev)
+		if (e) (void)hipEventDestroy(e);
 	if (s->xfer) (void)hipStreamDestroy(s->xfer);
 	if (s->h_dig) (void)hipHostFree(s->h_dig);
+	if (s->d_masks) arena_put(Arena{s->d_masks, s->masks_bytes, s->device});
 	arena_put(Arena{s->arena, s->arena_bytes, s->device});
 	delete s;
 }
@@ -238,6 +202,33 @@ extern "C" int hns_grid_release_cache(hns_grid* g) {
 	return HNS_OK;
 }
 
+static size_t sim_unit(uint64_t n) { return (sizeof(float) * (size_t)(n ? n : 1) + 255) & ~(size_t)255; }  // one float field, 256-byte aligned
+static bool sim_combust(const hns_sim* s) { return s->find("fuel") >= 0 && s->find("waste") >= 0 && s->find("temperature") >= 0 && s->find("flame") >= 0; }
+static size_t sim_units(const hns_sim* s) { return 3 * 3 + 3 + 2 * s->names.size() + (sim_combust(s) ? 4 : 0); }  // vel, adv, tmp | div, p_a, p_b | cur, nxt per field | q4
+
+size_t hns_sim_arena_need(const hns_sim* s, uint64_t n) { return sim_unit(n) * sim_units(s) + 256; }  // (+ the 16 digest accumulators of hns_compute_sim_resident, CHECKED fields)
+
+void hns_sim_layout(hns_sim* s, void* arena, uint64_t n) {
+	const size_t unit = sim_unit(n);
+	char* q = (char*)arena;
+	auto take = [&](size_t k) {
+		float* r = (float*)q;
+		q += k * unit;
+		return r;
+	};
+	s->n = n;
+	s->vel = take(3), s->adv = take(3), s->tmp = take(3);
+	s->div = take(1), s->p_a = take(1), s->p_b = take(1);
+	s->cur.clear(), s->nxt.clear();
+	for (size_t i = 0; i < s->names.size(); ++i) {
+		s->cur.push_back(take(1));
+		s->nxt.push_back(take(1));
+	}
+	s->q4 = sim_combust(s) ? take(4) : nullptr;
+	s->d_dig = (unsigned long long*)q;
+	s->p_result = s->p_a;
+}
+
 // zero: clear the arena (what hns_sim_create promises); the operator path skips it when every buffer is written before it is read
 static hns_sim* sim_create(hns_grid* g, const char* const* float_names, int n_float, bool zero, void* stream, int* rc_out) {
 	hns_sim* s = new hns_sim;
@@ -256,29 +247,12 @@ static hns_sim* sim_create(hns_grid* g, const char* const* float_names, int n_fl
 		}
 	}
 	if (rc == HNS_OK) {
-		const size_t unit = (sizeof(float) * (size_t)(s->n ? s->n : 1) + 255) & ~(size_t)255;  // one float field, 256-byte aligned
-		const bool combust = s->find("fuel") >= 0 && s->find("waste") >= 0 && s->find("temperature") >= 0 && s->find("flame") >= 0;
-		const size_t units = 3 * 3 + 3 + 2 * s->names.size() + (combust ? 4 : 0);               // vel, adv, tmp | div, p_a, p_b | cur, nxt per field | q4
 		Arena a{nullptr, 0, -1};
-		rc = arena_get(unit * units + 256, s->device, a);  // (+ the 16 digest accumulators of hns_compute_sim_resident, CHECKED fields)
+		rc = arena_get(hns_sim_arena_need(s, s->n), s->device, a);
 		if (rc == HNS_OK) {
 			s->arena = a.p, s->arena_bytes = a.bytes;
-			char* q = (char*)a.p;
-			auto take = [&](size_t k) {
-				float* r = (float*)q;
-				q += k * unit;
-				return r;
-			};
-			s->vel = take(3), s->adv = take(3), s->tmp = take(3);
-			s->div = take(1), s->p_a = take(1), s->p_b = take(1);
-			for (size_t i = 0; i < s->names.size(); ++i) {
-				s->cur.push_back(take(1));
-				s->nxt.push_back(take(1));
-			}
-			if (combust) s->q4 = take(4);
-			s->d_dig = (unsigned long long*)q;
-			s->p_result = s->p_a;
-			if (zero && hipMemsetAsync(a.p, 0, unit * units, (hipStream_t)stream) != hipSuccess) rc = fail(HNS_ERR_HIP, "hns_sim_create: clearing the field memory failed");
+			hns_sim_layout(s, a.p, s->n);
+			if (zero && hipMemsetAsync(a.p, 0, (char*)s->d_dig - (char*)a.p, (hipStream_t)stream) != hipSuccess) rc = fail(HNS_ERR_HIP, "hns_sim_create: clearing the field memory failed");
 		}
 	}
 	if (rc != HNS_OK) {

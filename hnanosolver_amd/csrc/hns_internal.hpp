@@ -64,6 +64,7 @@ struct Topology {
 };
 
 uint32_t hash_origin(int32_t x, int32_t y, int32_t z);
+void sort_leaf_origins(int32_t* xyz, size_t n);  // OpenVDB leaf order, in place (hns_leafio.cpp)
 
 // Device view handed to every kernel by value.
 struct GridDev {
@@ -144,6 +145,59 @@ struct hns_grid {
 	std::vector<hns_sim*> sim_cache;     // device-resident state kept between operator calls (hns_api.hip: make_sim)
 	hns::GridDev dev() const;
 };
+
+// Device-resident simulation state (include/hns.h: hns_sim_*). Lives in hns_api.hip; hns_regrid.hip moves one onto a new grid.
+struct hns_sim {
+	hns_grid* grid = nullptr;
+	uint64_t n = 0;  // voxels
+	std::vector<std::string> names;
+	std::vector<float*> cur;  // current value of each float field (the reference's d_inputs)
+	std::vector<float*> nxt;  // scratch / next value        (the reference's d_outputs)
+	float* vel = nullptr;  // d_velocity      (Vec3f AoS, 3n floats: the host/reference layout, so H2D/D2H are plain copies)
+	float* adv = nullptr;  // d_advectedVel
+	float* tmp = nullptr;  // out-of-place vorticity target; the buoyed u* of the fused divergence / combustion / buoyancy launch
+	float* q4 = nullptr;   // {fuel, waste, temperature, flame} as one 16-byte element per voxel between that launch and advect_scalars (sims that hold those four fields)
+	float* div = nullptr;
+	float* p_a = nullptr;
+	float* p_b = nullptr;
+	float* p_result = nullptr;  // whichever of p_a/p_b holds the last solve
+	// optional hipEvent bracketing of the pressure hot loop (hns_sim_timing), on the stream the kernels run on
+	bool timing = false;
+	std::vector<hipEvent_t> ev;  // start/stop pairs
+	size_t ev_used = 0;
+	long long timed_launches = 0;
+	bool stage_timing = false;    // hns_sim_stage_timing: also bracket the five stages of hns_sim_core_substep
+	std::vector<hipEvent_t> sev;  // stage boundaries: six per substep
+	size_t sev_used = 0;
+	hipStream_t xfer = nullptr;  // transfer stream + hand-off events of the pipelined operator path (compute_sim_pipelined)
+	hipEvent_t xev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+	bool cached = false, in_use = false;  // owned by the grid's cook cache / currently lent to an operator call
+	// Device-resident feedback across cooks (hns_compute_sim_resident): a signature of what the last hns_compute_sim on this state handed
+	// back for the velocity and for float field i -- those bytes are still in `vel` / cur[i]. 0 = nothing to vouch for (any upload clears it).
+	uint64_t sig_vel = 0, dig_vel = 0;  // (sig: sample signature; dig: full digest, 0 = not taken)
+	unsigned long long* d_dig = nullptr;  // 16 accumulators of the digest kernels (hns_digest.hpp): a slice of the arena
+	unsigned long long* h_dig = nullptr;  // pinned host copy of them (read asynchronously on the cook's own stream)
+	std::vector<uint64_t> sig_cur, dig_cur;
+	void* arena = nullptr;  // every field above is a slice of this one allocation (see the arena pool, hns_api.hip)
+	size_t arena_bytes = 0;
+	// active voxel masks of the leaves (hns_sim_set_active_masks / hns_sim_regrid): leaf_count x 64 bytes, byte x*8+y, bit z; null = every voxel active.
+	// An allocation of their own from the arena pool, made on first use: nothing else reads them.
+	unsigned char* d_masks = nullptr;
+	size_t masks_bytes = 0;
+	hipEvent_t rev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // phase boundaries of the last hns_sim_regrid (hns_sim_regrid_times)
+	bool regrid_timed = false;
+	int device = -1;
+	int find(const char* name) const {
+		for (size_t i = 0; i < names.size(); ++i)
+			if (names[i] == name) return (int)i;
+		return -1;
+	}
+};
+
+
+// the sim's buffers over one arena (hns_api.hip): bytes an arena needs for n voxels, and the slices of `arena` for them (sets n, every buffer pointer, d_dig, p_result)
+size_t hns_sim_arena_need(const hns_sim* s, uint64_t n);
+void hns_sim_layout(hns_sim* s, void* arena, uint64_t n);
 
 // implemented in hns_pressure.hip: hns_dev_rbgs_iterate with the option of starting from p = 0 without reading (or clearing) p_a
 extern "C" __attribute__((visibility("hidden"))) int hns_rbgs_iterate(hns_grid* g, const float* div, float* p_a, float* p_b, float dx, float omega, int iterations, int* result_in_b,

@@ -14,6 +14,7 @@
 #include <unordered_map>
 #include <unordered_set>
 
+#include "hns_dilate.hpp"
 #include "hns_internal.hpp"
 
 using namespace hns;
@@ -64,6 +65,26 @@ int check_aligned(const int32_t* o, uint64_t n, const char* who) {
 }
 
 }  // namespace
+
+// OpenVDB leaf order of an origin list in place (hns_regrid.hip): the same order as leaf_less, by one precomputed key per leaf -- root tile (20 bits per
+// axis, biased), then the 15-bit child offset in the 4096^3 node and the 12-bit one in the 128^3 node.
+void hns::sort_leaf_origins(int32_t* xyz, size_t n) {
+	struct Item {
+		uint64_t tile;
+		uint32_t node;
+		int32_t x, y, z;
+	};
+	std::vector<Item> v(n);
+	for (size_t i = 0; i < n; ++i) {
+		const int32_t x = xyz[3 * i], y = xyz[3 * i + 1], z = xyz[3 * i + 2];
+		const uint64_t tile = ((uint64_t)((x >> 12) + (1 << 19)) << 40) | ((uint64_t)((y >> 12) + (1 << 19)) << 20) | (uint64_t)((z >> 12) + (1 << 19));
+		const uint32_t node = ((uint32_t)(((x & 4095) >> 7) << 10 | ((y & 4095) >> 7) << 5 | ((z & 4095) >> 7)) << 12) |
+		                      (uint32_t)(((x & 127) >> 3) << 8 | ((y & 127) >> 3) << 4 | ((z & 127) >> 3));
+		v[i] = Item{tile, node, x, y, z};
+	}
+	std::sort(v.begin(), v.end(), [](const Item& a, const Item& b) { return a.tile != b.tile ? a.tile < b.tile : a.node < b.node; });
+	for (size_t i = 0; i < n; ++i) xyz[3 * i] = v[i].x, xyz[3 * i + 1] = v[i].y, xyz[3 * i + 2] = v[i].z;
+}
 
 extern "C" {
 
@@ -143,6 +164,55 @@ int hns_dilate_leaves(const int32_t* origins, uint64_t n, const unsigned char* a
 	}
 	std::vector<Key> keys(have.begin(), have.end());
 	return emit_sorted(keys, out_origins, capacity, n_out, "hns_dilate_leaves");
+}
+
+// hns_dilate_leaves plus the dilated ACTIVE MASKS themselves: frame n+1's domain depends on them (SOP_HNanoSolver.cpp:186-199 dilates the velocity's
+// active topology, and the output grids keep that topology, GridBuilder.hpp:198-214). Every leaf of the result receives the OR of what each leaf within
+// reach contributes (hns_dilate.hpp: the separable box dilation); a leaf is in the result iff that OR is not empty, which is hns_dilate_leaves' test.
+// Leaf set and order are hns_dilate_leaves'. out_origins / out_masks may be NULL to query *n_out.
+int hns_dilate_leaf_masks(const int32_t* origins, uint64_t n, const unsigned char* active_masks, int padding_voxels, int32_t* out_origins,
+                          unsigned char* out_masks, uint64_t capacity, uint64_t* n_out) {
+	if ((n && !origins) || padding_voxels < 0 || padding_voxels > 1024) return fail(HNS_ERR_INVALID_ARGUMENT, "hns_dilate_leaf_masks: bad arguments");
+	if (int rc = check_aligned(origins, n, "hns_dilate_leaf_masks")) return rc;
+	const int p = padding_voxels, D = (p + 7) / 8;
+	struct Mask {
+		uint64_t w[8];
+	};
+	std::unordered_map<Key, Mask, KeyHash> have;
+	have.reserve((size_t)n * 4);
+	for (uint64_t i = 0; i < n; ++i) {
+		const Key o{origins[3 * i], origins[3 * i + 1], origins[3 * i + 2]};
+		uint64_t m[8], any = 0;
+		for (int x = 0; x < 8; ++x) {
+			if (active_masks)
+				memcpy(&m[x], active_masks + 64 * i + 8 * x, 8);
+			else
+				m[x] = ~0ull;
+			any |= m[x];
+		}
+		if (!any) continue;
+		for (int dx = -D; dx <= D; ++dx)
+			for (int dy = -D; dy <= D; ++dy)
+				for (int dz = -D; dz <= D; ++dz) {
+					uint64_t c[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+					if (!dilate_into(m, -8 * dx, -8 * dy, -8 * dz, p, c)) continue;
+					const int64_t nx = (int64_t)o.x + 8 * dx, ny = (int64_t)o.y + 8 * dy, nz = (int64_t)o.z + 8 * dz;
+					if (nx < INT32_MIN || nx > INT32_MAX - 7 || ny < INT32_MIN || ny > INT32_MAX - 7 || nz < INT32_MIN || nz > INT32_MAX - 7) continue;
+					Mask& t = have.try_emplace(Key{(int32_t)nx, (int32_t)ny, (int32_t)nz}, Mask{{0, 0, 0, 0, 0, 0, 0, 0}}).first->second;
+					for (int x = 0; x < 8; ++x) t.w[x] |= c[x];
+				}
+	}
+	std::vector<Key> keys;
+	keys.reserve(have.size());
+	for (const auto& kv : have) keys.push_back(kv.first);
+	if (out_masks && keys.size() > capacity) {
+		set_error("hns_dilate_leaf_masks: %zu leaves do not fit the output capacity %llu", keys.size(), (unsigned long long)capacity);
+		return HNS_ERR_INVALID_ARGUMENT;
+	}
+	if (int rc = emit_sorted(keys, out_origins, capacity, n_out, "hns_dilate_leaf_masks")) return rc;
+	if (out_masks)
+		for (size_t i = 0; i < keys.size(); ++i) memcpy(out_masks + 64 * i, have[keys[i]].w, 64);
+	return HNS_OK;
 }
 
 // topologyUnion of two leaf sets (SOP_HNanoSolver.cpp:189,195-197), in OpenVDB leaf order, duplicates removed.

@@ -184,6 +184,52 @@ class Sim:
         _raise(lib.hns_sim_stage_times(self._ptr, ms, C.byref(n)))
         return dict(zip(("advect_vector", "divergence", "pressure", "gradient", "advect_scalars"), [float(x) for x in ms])), int(n.value)
 
+    def set_active_masks(self, masks: Optional[np.ndarray], stream: int = 0) -> None:
+        """Active voxel masks of the grid's leaves (leaf_count x 64 uint8, byte x*8+y, bit z); None = every voxel active (a new sim's state)."""
+        if masks is None:
+            _raise(lib.hns_sim_set_active_masks(self._ptr, None, stream))
+            return
+        m = np.ascontiguousarray(masks, dtype=np.uint8)
+        if m.size != self.grid.leaf_count() * 64:
+            raise ValueError(f"masks: need {self.grid.leaf_count()} x 64 bytes, got {m.size}")
+        _raise(lib.hns_sim_set_active_masks(self._ptr, m.ctypes.data, stream))
+
+    def active_masks(self, stream: int = 0) -> np.ndarray:
+        out = np.empty((self.grid.leaf_count(), 64), dtype=np.uint8)
+        _raise(lib.hns_sim_active_masks(self._ptr, out.ctypes.data, stream))
+        return out
+
+    def regrid(self, padding: int, sdf=None, stream: int = 0) -> IndexGridHandle:
+        """The domain change between two cooks (``hns_sim_regrid``): dilate the active masks by `padding` voxels, unite with the collision SDF's
+        leaves and carry every field into the new leaf set, on the device. sdf = (origins, masks or None, values: 512 floats per leaf) or None.
+        Returns the new grid and makes it ``self.grid``; the old handle is untouched and still the caller's."""
+        o = m = v = None
+        n_sdf = 0
+        if sdf is not None:
+            so, sm, sv = sdf
+            o = np.ascontiguousarray(so, dtype=np.int32).reshape(-1, 3)
+            n_sdf = len(o)
+            v = np.ascontiguousarray(sv, dtype=np.float32).reshape(-1)
+            if v.size != n_sdf * 512:
+                raise ValueError(f"sdf values: need {n_sdf} x 512 floats, got {v.size}")
+            if sm is not None:
+                m = np.ascontiguousarray(sm, dtype=np.uint8).reshape(-1)
+                if m.size != n_sdf * 64:
+                    raise ValueError(f"sdf masks: need {n_sdf} x 64 bytes, got {m.size}")
+        err = C.c_int(0)
+        ptr = lib.hns_sim_regrid(self._ptr, int(padding), None if o is None else o.ctypes.data, n_sdf, None if m is None else m.ctypes.data,
+                                 None if v is None else v.ctypes.data, stream, C.byref(err))
+        if not ptr:
+            _raise(err.value if err.value < 0 else _lib.HNS_ERR_RUNTIME)
+        self.grid = IndexGridHandle(ptr)
+        return self.grid
+
+    def regrid_times(self):
+        """hipEvent split of the last regrid in ms: {candidates, host (origins, sort, grid tables), masks, fields}"""
+        ms = (C.c_float * 4)()
+        _raise(lib.hns_sim_regrid_times(self._ptr, ms))
+        return dict(zip(("candidates", "host", "masks", "fields"), [float(x) for x in ms]))
+
     def close(self) -> None:
         if self._ptr:
             lib.hns_sim_destroy(self._ptr)

@@ -47,6 +47,20 @@ def dilate_leaves(origins, padding_voxels: int, active_masks: Optional[np.ndarra
     return out
 
 
+def dilate_leaf_masks(origins, padding_voxels: int, masks: Optional[np.ndarray] = None):
+    """-> (origins, masks): ``dilate_leaves`` plus the dilated active masks (n x 64 uint8, byte x*8+y, bit z) that the next frame's dilation starts
+    from (``hns_dilate_leaf_masks``). masks None = every voxel active."""
+    o = _o(origins)
+    m = None if masks is None else np.ascontiguousarray(masks, dtype=np.uint8).reshape(len(o), 64)
+    mp = m.ctypes.data if m is not None else None
+    n = C.c_uint64(0)
+    _lib.check(lib.hns_dilate_leaf_masks(o.ctypes.data, len(o), mp, int(padding_voxels), None, None, 0, C.byref(n)))
+    out = np.zeros((n.value, 3), dtype=np.int32)
+    out_m = np.zeros((n.value, 64), dtype=np.uint8)
+    _lib.check(lib.hns_dilate_leaf_masks(o.ctypes.data, len(o), mp, int(padding_voxels), out.ctypes.data, out_m.ctypes.data, n.value, C.byref(n)))
+    return out, out_m
+
+
 def union_leaves(a, b) -> np.ndarray:
     a, b = _o(a), _o(b)
     n = C.c_uint64(0)

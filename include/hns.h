@@ -159,6 +159,13 @@ int hns_scatter_leaves(const float* flat, uint64_t n_domain, int ncomp, float* c
  * be NULL to query *n_out. */
 int hns_dilate_leaves(const int32_t* origins, uint64_t n, const unsigned char* active_masks, int padding_voxels, int32_t* out_origins, uint64_t capacity,
                       uint64_t* n_out);
+/* hns_dilate_leaves plus the dilated ACTIVE MASKS (n_out x 64 bytes, same layout): what a host caller needs to chain frames, since frame n+1's
+ * domain depends on them (with padding 1, seven frames in eight keep the same leaves only because the masks carry the partial ring). Every
+ * leaf of the result holds the active voxels of the input dilated by the Chebyshev ball of radius padding_voxels (padding_voxels iterations of
+ * 26-neighbour dilation, SOP_HNanoSolver.cpp:190-193), cropped to the leaf. Leaf set and order equal hns_dilate_leaves'. out_origins and
+ * out_masks may be NULL to query *n_out. */
+int hns_dilate_leaf_masks(const int32_t* origins, uint64_t n, const unsigned char* active_masks, int padding_voxels, int32_t* out_origins,
+                          unsigned char* out_masks, uint64_t capacity, uint64_t* n_out);
 /* topologyUnion of two leaf sets, in OpenVDB leaf order, duplicates removed. */
 int hns_union_leaves(const int32_t* a, uint64_t na, const int32_t* b, uint64_t nb, int32_t* out_origins, uint64_t capacity, uint64_t* n_out);
 
@@ -246,6 +253,38 @@ float* hns_sim_velocity_ptr(hns_sim*);
 float* hns_sim_field_ptr(hns_sim*, const char* name);
 float* hns_sim_divergence_ptr(hns_sim*);
 float* hns_sim_pressure_ptr(hns_sim*);
+
+/* ------------------------------------------------------------------------------------------------------------ */
+/* Regrid of a device-resident sim: the domain change between two cooks, on the device                         */
+/* ------------------------------------------------------------------------------------------------------------ */
+
+/* Each cook the reference rebuilds the domain (SOP_HNanoSolver.cpp:186-199): the velocity's active topology, dilateVoxels(padding,
+ * NN_FACE_EDGE_VERTEX), united with the collision SDF's topology; padding has a hard minimum of 1 (:32-36) and the output grids keep the
+ * dilated topology (GridBuilder.hpp:198-214 clones the domain's masks, prune commented out), so the domain grows by `padding` voxels a frame.
+ *
+ * Active masks are sim state: leaf_count x 64 bytes, byte x*8+y, bit z (the hns_dilate_leaves layout). A new sim has every voxel active (NULL masks);
+ * hns_sim_set_active_masks(sim, NULL, ...) returns to that. hns_sim_active_masks is synchronous. */
+int hns_sim_set_active_masks(hns_sim*, const unsigned char* masks, void* stream);
+int hns_sim_active_masks(hns_sim*, unsigned char* out, void* stream);
+/* Moves the sim onto the next frame's domain D and returns it as a NEW grid the caller owns (same voxel size; device tables built by the usual
+ * path). Synchronous. Only leaf origins and masks cross PCIe, plus the SDF source when one is given.
+ *   D       = the leaves holding an active voxel of the masks dilated by the Chebyshev ball of radius padding_voxels (0..1024), united with the SDF
+ *             source's leaves; OpenVDB leaf order. Equals hns_union_leaves(hns_dilate_leaves(L, M, p), S).
+ *   masks   = the dilated masks, ORed with sdf_masks (NULL = all active) on the SDF's leaves: hns_dilate_leaf_masks, then the union.
+ *   fields  = velocity and every float field: the old leaf's values where the leaf existed, zeros elsewhere (HNS_FILL_ZERO).
+ *   collision_sdf  with a source (sdf_values != NULL: n_sdf leaves at sdf_origins, 512 floats each, host memory): gathered from it, bytes 0x01
+ *             where it has no leaf (HNS_FILL_SDF); without one: carried like any other field, bytes 0x01 on new leaves. A source for a sim without
+ *             that field is HNS_ERR_INVALID_ARGUMENT.
+ * Afterwards the sim runs on the new grid; the old grid is untouched and still the caller's to destroy. Pointers from hns_sim_*_ptr are
+ * invalidated, the divergence / pressure scratch holds no defined values and the feedback signatures of hns_compute_sim_resident are cleared.
+ * Results are independent of atomic ordering: two runs, and the host chain, give the same bytes.
+ * Refused, with the sim and its grid left exactly as they were: a sim lent to a grid's cook cache and a grid whose launch range is not the whole
+ * grid (HNS_ERR_INVALID_ARGUMENT); SDF origins not 8-aligned or duplicated (HNS_ERR_TOPOLOGY); an empty result (HNS_ERR_RUNTIME, the SOP's "No
+ * active voxels"). */
+hns_grid* hns_sim_regrid(hns_sim*, int padding_voxels, const int32_t* sdf_origins, uint64_t n_sdf, const unsigned char* sdf_masks,
+                         const float* sdf_values, void* stream, int* err);
+/* hipEvent split of the sim's last regrid, milliseconds: {candidate leaves, origins to the host + sort + grid tables, masks, field copy}. */
+int hns_sim_regrid_times(hns_sim*, float* ms4);
 
 /* ------------------------------------------------------------------------------------------------------------ */
 /* Kernel-level entry points on caller-owned DEVICE memory (asynchronous on `stream`).                           */
