@@ -367,7 +367,9 @@ static int sim_pressure(hns_sim* s, int iterations, float voxel_size, float omeg
 	return HNS_OK;
 }
 
-static float omega_compute(float vs) { return 2.0f / (1.0f + sinf(static_cast<float>(3.14159) * vs)); }          // HNanoSolver.cu:257
+namespace hns {  // (declared in hns_dist.hpp: the partitioned substep uses the same omega)
+float omega_compute(float vs) { return 2.0f / (1.0f + sinf(static_cast<float>(3.14159) * vs)); }          // HNanoSolver.cu:257
+}  // namespace hns
 static float omega_project(float vs) { return (float)(2.0f / (1.0f + sin(3.14159 * (double)vs))); }             // PressureProjection.cu:53
 
 extern "C" int hns_sim_pressure_solve(hns_sim* s, int iterations, float voxel_size, void* stream) {

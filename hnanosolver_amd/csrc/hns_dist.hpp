@@ -82,6 +82,11 @@ int need_rccl(const char* who);
 		}                                                                                                      \
 	} while (0)
 
+namespace hns {
+// the SOR factor of the Compute_Sim pressure loop, defined once in hns_api.hip: the partitioned substep is bit-equal to the single grid only with the same omega
+float omega_compute(float vs);
+}  // namespace hns
+
 namespace hnsd {
 
 constexpr int kMaxBatchPeers = 16;  // peers whose regions one pack / unpack launch serves (k_halo_copy_all)

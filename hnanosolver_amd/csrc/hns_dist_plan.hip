@@ -218,6 +218,14 @@ int build_plan(hns_dist* d, const int32_t* origins, int64_t n, int world, int ra
 		d->peers.push_back(std::move(p));
 	}
 	d->nG = (int)d->local_global.size() - n_owned;
+	// What lets the interior launch overlap the previous exchange's unpack (complete_boundary_only, hns_dist_substep.hip): no interior leaf has a foreign
+	// leaf among its 26 neighbours, and the blocked sweep's dependency cone (2k voxels) stays inside one leaf
+	if (d->k > 4) return fail(HNS_ERR_RUNTIME, "hns_dist: plan invariant broken: sweeps_per_exchange above 4 reaches beyond one leaf");
+	for (int l = d->nB; l < n_owned; ++l)
+		for (int j = 0; j < 27; ++j) {
+			const int64_t nb = topo.nbr27[(size_t)d->local_global[(size_t)l] * 27 + (size_t)j];
+			if (nb >= 0 && (nb < o0 || nb >= o1)) return fail(HNS_ERR_RUNTIME, "hns_dist: plan invariant broken: an interior leaf has a neighbour owned by another rank");
+		}
 	return HNS_OK;
 }
 

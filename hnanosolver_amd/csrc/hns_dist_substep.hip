@@ -281,12 +281,41 @@ size_t message_floats(const Pending& x, const Region& r) {
 	return c * (size_t)r.voxels;
 }
 
+// All messages of exchange `x` as k_ipc_put launches of up to kIpcMaxSegs segments, one segment per peer and field: `voxels(i)` voxels of peer i's send region travel,
+// and field `f` of that message lands at `dst(i, f, before)` (`before`: the components of the fields ahead of it in the message).
+template <bool FENCE, class VoxelsFn, class DstFn>
+void put_messages(hns_dist* d, const Pending& x, hipStream_t cs, VoxelsFn voxels, DstFn dst) {
+	IpcSegs sg;
+	sg.n = 0, sg.wg0[0] = 0;
+	auto flush = [&]() {
+		if (sg.n) hipLaunchKernelGGL(k_ipc_put<FENCE>, dim3(sg.wg0[sg.n]), dim3(256), 0, cs, sg);
+		sg.n = 0;
+	};
+	for (size_t i = 0; i < d->peers.size(); ++i) {
+		const Peer& p = d->peers[i];
+		int before = 0;
+		for (auto& f : x.fields) {
+			const size_t fl = voxels(i) * (size_t)f.second;
+			if (fl) {
+				if (sg.n == kIpcMaxSegs) flush();
+				sg.dst[sg.n] = dst(i, f, before), sg.src[sg.n] = segment(p.send[x.type], f.first, f.second, p.sbuf[x.parity], before), sg.floats[sg.n] = (unsigned)fl;
+				sg.wg0[sg.n + 1] = sg.wg0[sg.n] + (unsigned)((fl + 4095) / 4096);
+				++sg.n;
+			}
+			before += f.second;
+		}
+	}
+	flush();
+}
+
 // received regions -> ghost voxels, on the communication stream; ev_done marks the end of the exchange
 int unpack(hns_dist* d, Pending& x) {
 	HNS_TRY(halo_copy_exchange(d, false, x, x.stream));
 	if (!d->single_stream) HNS_HIP(hipEventRecord(d->ev_done[x.parity], x.stream));
 	return HNS_OK;
 }
+
+const auto nothing = [](hipStream_t) { return (int)HNS_OK; };  // a boundary or interior launch that has nothing to launch
 
 // One exchange. post(): the compute stream `st` marks "everything the boundary kernel reads is ready", and the rank's
 // communication stream takes over the whole boundary side of the step: `boundary(cs)` runs the kernel on the boundary leaves,
@@ -339,33 +368,13 @@ int post(hns_dist* d, int type, std::vector<std::pair<float*, int>> fields, hipS
 			ip.rank[i] = d->peers[(size_t)i].rank;
 		}
 		hipLaunchKernelGGL(k_ipc_ready, dim3(1), dim3(64), 0, cs, ip, (const uint32_t*)d->ipc_flags, seq, d->ipc_status);
-		IpcSegs sg;
-		sg.n = 0, sg.wg0[0] = 0;
-		auto flush = [&]() {
-			if (sg.n) hipLaunchKernelGGL(k_ipc_put<true>, dim3(sg.wg0[sg.n]), dim3(256), 0, cs, sg);
-			sg.n = 0;
-		};
-		for (size_t i = 0; i < d->peers.size(); ++i) {
-			Peer& p = d->peers[i];
+		put_messages<true>(d, x, cs, [&](size_t i) { return (size_t)d->peers[i].send[type].voxels; }, [&](size_t i, const std::pair<float*, int>& f, int before) {
+			// the same field in the peer's memory: fields sit at the same multiples of the (peer's) unit
 			const hns_dist::IpcPeer& q = d->ipc_peers[i];
-			const Region& rs = p.send[type];
-			int before = 0;
-			for (auto& f : x.fields) {
-				const size_t fl = (size_t)rs.voxels * (size_t)f.second;
-				if (fl) {
-					if (sg.n == kIpcMaxSegs) flush();
-					// the same field in the peer's memory: fields sit at the same multiples of the (peer's) unit
-					const size_t unit_index = (size_t)((char*)f.first - (char*)d->arena) / d->unit_bytes;
-					char* dst = q.recv_direct[type] >= 0 ? q.arena + unit_index * q.unit_bytes + sizeof(float) * 512 * (size_t)q.recv_direct[type] * (size_t)f.second
-					                                     : q.tables + q.rbuf_off[x.parity] + sizeof(float) * (size_t)before * (size_t)q.recv_voxels[type];
-					sg.dst[sg.n] = (float*)dst, sg.src[sg.n] = segment(rs, f.first, f.second, p.sbuf[x.parity], before), sg.floats[sg.n] = (unsigned)fl;
-					sg.wg0[sg.n + 1] = sg.wg0[sg.n] + (unsigned)((fl + 4095) / 4096);
-					++sg.n;
-				}
-				before += f.second;
-			}
-		}
-		flush();
+			const size_t unit_index = (size_t)((char*)f.first - (char*)d->arena) / d->unit_bytes;
+			return (float*)(q.recv_direct[type] >= 0 ? q.arena + unit_index * q.unit_bytes + sizeof(float) * 512 * (size_t)q.recv_direct[type] * (size_t)f.second
+			                                         : q.tables + q.rbuf_off[x.parity] + sizeof(float) * (size_t)before * (size_t)q.recv_voxels[type]);
+		});
 		hipLaunchKernelGGL(k_ipc_landed, dim3(1), dim3(64), 0, cs, ip, (const uint32_t*)d->ipc_flags, seq, d->ipc_status);
 		HNS_TRY(launch_status("hns_dist: one-sided exchange"));
 	} else if (d->comm) {
@@ -387,27 +396,8 @@ int post(hns_dist* d, int type, std::vector<std::pair<float*, int>> fields, hipS
 		if (const int us = options().dist_wire_us.load()) hipLaunchKernelGGL(k_wire_delay, dim3(1), dim3(1), 0, cs, (long long)us * 100);
 		// all messages of the exchange as ONE copy launch (round 6; a hipMemcpyAsync per peer and field cost the host 5-8 us each, two to fourteen of them per exchange):
 		// what stands in for the one send / receive group of the RCCL path
-		IpcSegs sg;
-		sg.n = 0, sg.wg0[0] = 0;
-		auto flush = [&]() {
-			if (sg.n) hipLaunchKernelGGL(k_ipc_put<false>, dim3(sg.wg0[sg.n]), dim3(256), 0, cs, sg);
-			sg.n = 0;
-		};
-		for (Peer& p : d->peers) {
-			const Region &rs = p.send[type], &rr = p.recv[type];
-			int before = 0;
-			for (auto& f : x.fields) {
-				const size_t nr = (size_t)std::min(rs.voxels, rr.voxels) * (size_t)f.second;
-				if (nr) {
-					if (sg.n == kIpcMaxSegs) flush();
-					sg.dst[sg.n] = segment(rr, f.first, f.second, p.rbuf[x.parity], before), sg.src[sg.n] = segment(rs, f.first, f.second, p.sbuf[x.parity], before), sg.floats[sg.n] = (unsigned)nr;
-					sg.wg0[sg.n + 1] = sg.wg0[sg.n] + (unsigned)((nr + 4095) / 4096);
-					++sg.n;
-				}
-				before += f.second;
-			}
-		}
-		flush();
+		put_messages<false>(d, x, cs, [&](size_t i) { return (size_t)std::min(d->peers[i].send[type].voxels, d->peers[i].recv[type].voxels); },
+		                    [&](size_t i, const std::pair<float*, int>& f, int before) { return segment(d->peers[i].recv[type], f.first, f.second, d->peers[i].rbuf[x.parity], before); });
 		HNS_TRY(launch_status("hns_dist: loopback exchange"));
 	} else {
 		if (!d->single_stream) HNS_HIP(hipEventRecord(d->ev_post[x.parity], cs));  // packed: the peers may pull
@@ -419,11 +409,6 @@ int post(hns_dist* d, int type, std::vector<std::pair<float*, int>> fields, hipS
 		return HNS_OK;
 	}
 	return unpack(d, x);
-}
-
-template <class BoundaryFn>
-int post(hns_dist* d, int type, std::vector<std::pair<float*, int>> fields, hipStream_t st, BoundaryFn boundary) {
-	return post(d, type, std::move(fields), st, boundary, [](hipStream_t) { return (int)HNS_OK; });
 }
 
 // Make the posted exchange's data visible in the ghost voxels before anything else runs on the compute stream.
@@ -464,6 +449,9 @@ int complete(hns_dist* d, hipStream_t st) {
 // boundary leaves' new p), not its messages -- the ghost voxels are read by the next boundary kernel alone, which follows the unpack in stream order on the communication
 // stream. So the compute stream waits for ev_bdone, the exchange is forgotten, and no cross-stream edge is left on the chain boundary sweep -> transfer -> unpack -> next
 // boundary sweep. (The last exchange of a solve is completed in full by the phase behind it.) Two-stream transports only; false = the caller must complete() in full.
+// Invariant (checked by build_plan): every interior leaf has all 26 neighbours absent or owned, and sweeps_per_exchange k <= 4. The interior launch may then run while the
+// previous exchange's unpack is still writing ghost leaves: no interior voxel reads a ghost voxel, and the blocked sweep's dependency cone (2k <= 8 voxels) stays inside one leaf,
+// so what an interior launch reads within a block is owned.
 bool complete_boundary_only(hns_dist* d, hipStream_t st) {
 	Pending& x = d->pending;
 	if (!x.active) return true;
@@ -474,10 +462,18 @@ bool complete_boundary_only(hns_dist* d, hipStream_t st) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// the core substep as a sequence of phases; a phase ends where an exchange has been posted
+// the core / full substep as a list of phases; a phase ends where an exchange has been posted
 // ---------------------------------------------------------------------------------------------------------------
 
-float omega_compute(float vs) { return 2.0f / (1.0f + sinf(static_cast<float>(3.14159) * vs)); }  // reference HNanoSolver.cu:257
+enum class PhaseKind { Open, Collision, AdvectVector, Vorticity, Divergence, Combustion, SorBlock, Gradient, AdvectScalars };
+struct Phase {
+	PhaseKind kind;
+	int block;  // SorBlock: which block of up to k sweeps of the pressure loop (0 otherwise)
+	bool operator==(const Phase& o) const { return kind == o.kind && block == o.block; }
+};
+
+typedef std::vector<std::pair<float*, int>> Fields;
+typedef std::vector<std::pair<const float*, int>> Outs;
 
 struct Step {
 	hns_dist* d;
@@ -494,12 +490,43 @@ struct Step {
 	bool coll = false, vort = false;
 
 	bool full() const { return prm != nullptr; }
-	int n_phases() const {
-		const int blocks = (iterations + d->k - 1) / d->k;
-		if (full()) return 1 + (coll ? 1 : 0) + 1 + (vort ? 1 : 0) + 1 + 1 + blocks + 1 + 1;  // open | [collision] | advect_vector | [vorticity] | divergence | combustion | blocks | gradient | advect_scalars
-		return 1 + 1 + 1 + blocks + 1 + 1;  // open | advect_vector | divergence | pressure blocks | gradient | advect_scalars
-	}
 	const float* sdf() const { return coll ? d->phi[(size_t)fi[4]] : nullptr; }
+	float inv_dx() const { return 1.0f / d->voxel_size; }
+	// Only the core substep takes the chained form (and the mirror pressure loop): the full one exchanges at every kernel boundary a stencil crosses, whatever the transport.
+	bool chained_form() const { return !full() && d->chain; }
+	bool exchanged_blocks() const { return full() || !d->mirror; }  // the pressure loop's blocks are sor_block_exchanged's (else mirror_block's)
+
+	// open | [collision] | advect_vector | [vorticity] | divergence | [combustion] | blocks of up to k sweeps | gradient | advect_scalars (the core: none of [...])
+	std::vector<Phase> phases() const {
+		std::vector<Phase> p{{PhaseKind::Open, 0}};
+		if (coll) p.push_back({PhaseKind::Collision, 0});
+		p.push_back({PhaseKind::AdvectVector, 0});
+		if (vort) p.push_back({PhaseKind::Vorticity, 0});
+		p.push_back({PhaseKind::Divergence, 0});
+		if (full()) p.push_back({PhaseKind::Combustion, 0});
+		for (int b = 0, blocks = (iterations + d->k - 1) / d->k; b < blocks; ++b) p.push_back({PhaseKind::SorBlock, b});
+		p.push_back({PhaseKind::Gradient, 0});
+		p.push_back({PhaseKind::AdvectScalars, 0});
+		return p;
+	}
+
+	// The one completion rule: a phase first makes the exchange in flight visible (complete), except Open -- it posts the first exchange of the substep -- and a
+	// block of the exchanged pressure loop, which completes for itself (sor_block_exchanged: in full, or the boundary kernel alone). The mirror loop's blocks do complete first.
+	int run(const Phase& p) {
+		if (p.kind != PhaseKind::Open && !(p.kind == PhaseKind::SorBlock && exchanged_blocks())) HNS_TRY(complete(d, st));
+		switch (p.kind) {
+			case PhaseKind::Open: return open();
+			case PhaseKind::Collision: return collision();
+			case PhaseKind::AdvectVector: return advect_vector();
+			case PhaseKind::Vorticity: return vorticity();
+			case PhaseKind::Divergence: return divergence();
+			case PhaseKind::Combustion: return combustion();
+			case PhaseKind::SorBlock: return exchanged_blocks() ? sor_block_exchanged(p.block) : mirror_block(p.block);
+			case PhaseKind::Gradient: return gradient();
+			case PhaseKind::AdvectScalars: return advect_scalars();
+		}
+		return fail(HNS_ERR_RUNTIME, "hns_dist: unknown phase");
+	}
 
 	// Do both launch ranges of the split sweep take two iterations in ONE launch each (result in dst for both)? Asked of the library's own
 	// plan, so that whatever hns_rbgs_iterate does with `2` is what this loop assumes.
@@ -520,12 +547,6 @@ struct Step {
 			if (hns_grid_rbgs_plan(g, 2, nullptr, 0, &launches, &per) != HNS_OK || launches != 1) return false;
 		}
 		return true;
-	}
-
-	int advect_scalars(hns_grid* g, float inv_dx, hipStream_t s) const {
-		if (!d->n_scalars || !g->n_active) return HNS_OK;
-		std::vector<const float*> in(d->phi.begin(), d->phi.end());
-		return hns_dev_advect_scalars(g, d->u, in.data(), d->phi_next.data(), d->n_scalars, nullptr, 0, dt, inv_dx, s);
 	}
 
 	// One chained launch (hns_flags.hpp: PhaseMirror): `launch` runs the kernel over the owned leaves with the arguments `m`.
@@ -551,10 +572,105 @@ struct Step {
 		return launch_status("hns_dist: chained launch");
 	}
 
+	// the advection inputs: phi unless the previous substep already posted it, and u
+	int open() {
+		Fields f;
+		if (full()) {  // (u may still need posting behind a phi in flight -- unless collision is about to rewrite u and post it again)
+			if (!coll && !d->u_ghosts_fresh) {
+				if (d->phi_in_flight) HNS_TRY(complete(d, st));
+				f.emplace_back(d->u, 3);
+			}
+			if (!d->phi_in_flight)
+				for (float* p : d->phi) f.emplace_back(p, 1);
+			d->phi_in_flight = false;
+		} else {  // (the core substep's last phase leaves u's ghosts fresh whenever it posts phi: nothing to add then)
+			if (d->phi_in_flight) return HNS_OK;
+			if (!d->u_ghosts_fresh) f.emplace_back(d->u, 3);
+			for (float* p : d->phi) f.emplace_back(p, 1);
+		}
+		return f.empty() ? (int)HNS_OK : post(d, X_ADV, f, st, nothing, nothing);
+	}
+
+	// enforceCollisionBoundaries (HNanoSolver.cu:153-157) reads the ghost voxels of the SDF (its normal): they have arrived now
+	int collision() {
+		HNS_TRY(hns_dev_enforce_collision_boundaries(d->gO, d->u, sdf(), d->voxel_size, st));
+		return post(d, X_ADV, Fields{{d->u, 3}}, st, nothing, nothing);
+	}
+
+	// advect_vector (:162-170); vorticity confinement reads it up to factor_scale + 1 voxels away: whole leaves travel then
+	int advect_vector() {
+		const float ix = inv_dx(), dtv = dt;
+		if (chained_form()) {
+			const PhaseMirror m = phase_args(d, X_D1, Outs{{d->adv, 3}});
+			return chained(m, [&] {  // gate | the kernel as it is | copy of the boundary leaves' reach-1 voxels into the peers' ghosts
+				HNS_TRY(hns_dev_advect_vector(d->gO, d->u, d->adv, nullptr, 0, dt, ix, st));
+				if (d->nB && m.n_peers)
+					hipLaunchKernelGGL(k_chain_mirror<3>, dim3((unsigned)d->nB), dim3(64), 0, st, m, 1, (const float*)d->adv, (const float*)nullptr, (const float*)nullptr,
+					                   (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr);
+				return HNS_OK;
+			}, true);
+		}
+		hns_dist* D = d;
+		const float* sd = sdf();
+		const int c = coll ? 1 : 0;
+		return post(d, vort ? X_ADV : X_D1, Fields{{d->adv, 3}}, st, [=](hipStream_t s) { return hns_dev_advect_vector(D->gB, D->u, D->adv, sd, c, dtv, ix, s); },
+		            [=](hipStream_t s) { return hns_dev_advect_vector(D->gI, D->u, D->adv, sd, c, dtv, ix, s); });
+	}
+
+	// :172-176, out of place (the reference's in-place launch races)
+	int vorticity() {
+		hns_dist* D = d;
+		const float ix = inv_dx(), dtv = dt, scale = prm->vorticityScale, fs = prm->factorScale;
+		HNS_TRY(post(d, X_D1, Fields{{d->tmp, 3}}, st, [=](hipStream_t s) { return hns_dev_vorticity_confinement(D->gB, D->adv, D->tmp, dtv, ix, scale, fs, s); },
+		             [=](hipStream_t s) { return hns_dev_vorticity_confinement(D->gI, D->adv, D->tmp, dtv, ix, scale, fs, s); }));
+		std::swap(d->adv, d->tmp);
+		return HNS_OK;
+	}
+
+	// divergence (:181-188)
+	int divergence() {
+		hns_dist* D = d;
+		const float ix = inv_dx();
+		if (!full()) {
+			if (d->chain) {
+				const PhaseMirror m = phase_args(d, X_DIV, Outs{{d->div, 1}});
+				return chained(m, [&] { return hns_chain_divergence(d->gO, d->adv, d->div, ix, &m, st); });
+			}
+			if (in_line_rank()) return post(d, X_DIV, Fields{{d->div, 1}}, st, [=](hipStream_t s) { return hns_dev_divergence(D->gO, D->adv, D->div, ix, s); }, nothing, true);
+			return post(d, X_DIV, Fields{{d->div, 1}}, st, [=](hipStream_t s) { return hns_dev_divergence(D->gB, D->adv, D->div, ix, s); },
+			            [=](hipStream_t s) { return hns_dev_divergence(D->gI, D->adv, D->div, ix, s); });
+		}
+		// full: + what combustion adds to it (:211-221, k_combustion_div: fuel and waste only); its interior launches follow post() instead of being handed to it
+		const float ex = prm->expansionRate;
+		const float *fuel = d->phi[(size_t)fi[0]], *waste = d->phi[(size_t)fi[1]];
+		const uint64_t nb = (uint64_t)d->nB * 512u, ni = (uint64_t)d->nI * 512u;
+		HNS_TRY(post(d, X_DIV, Fields{{d->div, 1}}, st, [=](hipStream_t s) {
+			HNS_TRY(hns_dev_divergence(D->gB, D->adv, D->div, ix, s));
+			return nb ? hns_combustion_div(fuel, waste, D->div, ex, nb, s) : HNS_OK;
+		}, nothing));
+		HNS_TRY(hns_dev_divergence(d->gI, d->adv, d->div, ix, st));
+		return ni ? hns_combustion_div(fuel + nb, waste + nb, d->div + nb, ex, ni, st) : HNS_OK;
+	}
+
+	// the rest of combustion, buoyancy with the NEW temperature (:226-234), outputs become inputs (:239-246): pointwise, owned voxels
+	int combustion() {
+		const uint64_t n_owned = (uint64_t)(d->nB + d->nI) * 512u;
+		if (n_owned) {
+			HNS_TRY(hns_combustion_fields(d->phi[(size_t)fi[0]], d->phi[(size_t)fi[1]], d->phi[(size_t)fi[2]], d->phi[(size_t)fi[3]], d->phi_next[(size_t)fi[0]],
+			                              d->phi_next[(size_t)fi[1]], d->phi_next[(size_t)fi[2]], d->phi_next[(size_t)fi[3]], prm->temperatureRelease, n_owned, st));
+			HNS_TRY(hns_dev_temperature_buoyancy(d->adv, d->phi_next[(size_t)fi[2]], d->adv, dt, prm->ambientTemp, prm->buoyancyStrength, n_owned, st));
+		}
+		Fields f;
+		for (int c = 0; c < 4; ++c) {
+			std::swap(d->phi[(size_t)fi[c]], d->phi_next[(size_t)fi[c]]);
+			f.emplace_back(d->phi[(size_t)fi[c]], 1);
+		}
+		return post(d, X_ADV, f, st, nothing, nothing);  // advect_scalars reads their ghosts; hidden under the pressure solve
+	}
+
 	// one block of up to k sweeps with the halo of p exchanged behind it; all but the last sweep the ghost leaves too
 	int sor_block_exchanged(int b) {
 		hns_dist* D = d;
-		typedef std::vector<std::pair<float*, int>> Fields;
 		if (b == 0) it = 0, src = d->p_a, dst = d->p_b;  // never warm-started (reference HNanoSolver.cu:113): the first sweep reads no p
 		const int n = std::min(d->k, iterations - it);
 		// what the previous phase posted: in full in front of the first block (the divergence's ghosts) and wherever this block starts with sweeps over the ghost leaves;
@@ -581,243 +697,109 @@ struct Step {
 			return g->n_active ? hns_rbgs_iterate(g, D->div, s0, d0, vs, omega_compute(vs), tail, nullptr, s, zero) : (int)HNS_OK;
 		};
 		const int xt = last ? X_D1 : X_P;
+		auto pack_launch = [=](hns_grid* g, int its, hipStream_t s, bool* done) {  // the blocked sweep that writes the peers' messages as it stores (PackMirror)
+			PackMirror m = D->pack_type[xt];
+			for (size_t pi = 0; pi < D->peers.size(); ++pi) m.msg[pi] = D->peers[pi].sbuf[D->pending.parity];
+			return hns_rbgs_block_pack_launch(g, D->div, s0, d0, vs, omega_compute(vs), zero, &m, s, done, its);
+		};
 		// Round 6: ONE launch over all owned leaves that packs the peers' messages as it stores (PackMirror), then the transfer and the unpack behind it on the compute stream.
 		// The boundary / interior split (below) buys overlap of the transfer with the interior sweep, and pays for it: a 16^3 block that straddles the boundary layer is swept by
 		// both launches (config 5, rank 4 of 8: 14 + 14 us against 19 for the one launch), two cross-stream event edges per exchange, and twice the runtime calls -- traced, the
 		// split loop's chain boundary sweep -> transfer -> unpack -> next boundary sweep alone took longer than this whole sequence (profiles/r06_dist_exchanged_notes.txt).
 		if (unsplit) {
 			HNS_TRY(post(d, xt, Fields{{dst, 1}}, st, [=](hipStream_t s) -> int {
-				PackMirror m = D->pack_type[xt];
-				for (size_t pi = 0; pi < D->peers.size(); ++pi) m.msg[pi] = D->peers[pi].sbuf[D->pending.parity];
 				bool done = false;
-				HNS_TRY(hns_rbgs_block_pack_launch(D->gO, D->div, s0, d0, vs, omega_compute(vs), zero, &m, s, &done, tail));
+				HNS_TRY(pack_launch(D->gO, tail, s, &done));
 				if (!done) return fail(HNS_ERR_RUNTIME, "hns_dist: the owned range is not swept in 16^3 blocks after all");
 				D->pending.prepacked = true;
 				return HNS_OK;
-			}, [](hipStream_t) { return (int)HNS_OK; }, true));
-			std::swap(src, dst);
-			it += tail;
-			if (last) d->p_result = src;
-			return HNS_OK;
-		}
-		HNS_TRY(post(d, xt, Fields{{dst, 1}}, st, [=](hipStream_t s) -> int {
-			// two iterations in one blocked launch: the boundary sweep writes the peers' messages as it stores (PackMirror)
-			if (tail == 2 && D->pack_ok[xt]) {
-				PackMirror m = D->pack_type[xt];
-				for (size_t pi = 0; pi < D->peers.size(); ++pi) m.msg[pi] = D->peers[pi].sbuf[D->pending.parity];
-				bool done = false;
-				HNS_TRY(hns_rbgs_block_pack_launch(D->gB, D->div, s0, d0, vs, omega_compute(vs), zero, &m, s, &done, 2));
-				if (done) {
-					D->pending.prepacked = true;
-					return HNS_OK;
+			}, nothing, true));
+		} else {
+			HNS_TRY(post(d, xt, Fields{{dst, 1}}, st, [=](hipStream_t s) -> int {
+				// two iterations in one blocked launch: the boundary sweep packs the messages itself
+				if (tail == 2 && D->pack_ok[xt]) {
+					bool done = false;
+					HNS_TRY(pack_launch(D->gB, 2, s, &done));
+					if (done) {
+						D->pending.prepacked = true;
+						return HNS_OK;
+					}
 				}
-			}
-			return part(D->gB, s);
-		}, [=](hipStream_t s) { return part(D->gI, s); }));
+				return part(D->gB, s);
+			}, [=](hipStream_t s) { return part(D->gI, s); }));
+		}
 		std::swap(src, dst);
 		it += tail;
 		if (last) d->p_result = src;
 		return HNS_OK;
 	}
 
-	// The full substep. Every kernel boundary a stencil crosses is an exchange (post / complete), whatever the transport: the chained
-	// and mirroring forms of the core substep are not used here. Pointwise kernels run over the owned leaves, local [0, nB + nI).
-	int run_full(int ph) {
-		const float inv_dx = 1.0f / d->voxel_size;
-		const int blocks = (iterations + d->k - 1) / d->k;
-		typedef std::vector<std::pair<float*, int>> Fields;
-		hns_dist* D = d;
-		const float* sd = sdf();
-		const int cl = coll ? 1 : 0;
-		const uint64_t n_owned = (uint64_t)(d->nB + d->nI) * 512u;
-		auto nothing = [](hipStream_t) { return HNS_OK; };
-		const float dtv = dt;
-		if (ph == 0) {  // the advection inputs: phi unless the previous substep already posted it, and u -- which collision rewrites first
-			Fields f;
-			if (!coll && !d->u_ghosts_fresh) {
-				if (d->phi_in_flight) HNS_TRY(complete(d, st));
-				f.emplace_back(d->u, 3);
-			}
-			if (!d->phi_in_flight)
-				for (float* p : d->phi) f.emplace_back(p, 1);
-			d->phi_in_flight = false;
-			if (f.empty()) return HNS_OK;
-			return post(d, X_ADV, f, st, nothing);
+	// one block of the mirror pressure loop: ONE chained launch of the temporally blocked form, two iterations or the odd one left over (every rank alike: blocked_mirror)
+	int mirror_block(int b) {
+		if (b == 0) {
+			it = 0, src = d->p_a, dst = d->p_b;  // never warm-started (reference HNanoSolver.cu:113): the first sweep reads no p
+			if (d->timing && d->tev_used + 2 <= d->tev.size()) HNS_HIP(hipEventRecord(d->tev[d->tev_used], st));
 		}
-		{  // (the blocks of the exchanged pressure loop complete what is in flight themselves: sor_block_exchanged)
-			const int qb = ph - 1 - (coll ? 1 : 0) - (vort ? 2 : 1) - 2;
-			if (!(qb >= 0 && qb < blocks)) HNS_TRY(complete(d, st));
-		}
-		if (coll && ph == 1) {  // enforceCollisionBoundaries (HNanoSolver.cu:153-157) reads the ghost voxels of the SDF (its normal): they have arrived now
-			HNS_TRY(hns_dev_enforce_collision_boundaries(d->gO, d->u, sd, d->voxel_size, st));
-			return post(d, X_ADV, Fields{{d->u, 3}}, st, nothing);
-		}
-		int q = ph - 1 - (coll ? 1 : 0);
-		if (q == 0) {  // advect_vector (:162-170); vorticity confinement reads it up to factor_scale + 1 voxels away: whole leaves travel then
-			return post(d, vort ? X_ADV : X_D1, Fields{{d->adv, 3}}, st, [=](hipStream_t s) { return hns_dev_advect_vector(D->gB, D->u, D->adv, sd, cl, dtv, inv_dx, s); },
-			            [=](hipStream_t s) { return hns_dev_advect_vector(D->gI, D->u, D->adv, sd, cl, dtv, inv_dx, s); });
-		}
-		if (vort && q == 1) {  // :172-176, out of place (the reference's in-place launch races)
-			const float scale = prm->vorticityScale, fs = prm->factorScale;
-			HNS_TRY(post(d, X_D1, Fields{{d->tmp, 3}}, st, [=](hipStream_t s) { return hns_dev_vorticity_confinement(D->gB, D->adv, D->tmp, dtv, inv_dx, scale, fs, s); },
-			             [=](hipStream_t s) { return hns_dev_vorticity_confinement(D->gI, D->adv, D->tmp, dtv, inv_dx, scale, fs, s); }));
-			std::swap(d->adv, d->tmp);
-			return HNS_OK;
-		}
-		q -= vort ? 2 : 1;
-		if (q == 0) {  // divergence (:181-188) + what combustion adds to it (:211-221, k_combustion_div: fuel and waste only)
-			const float ex = prm->expansionRate;
-			const float *fuel = d->phi[(size_t)fi[0]], *waste = d->phi[(size_t)fi[1]];
-			const uint64_t nb = (uint64_t)d->nB * 512u, ni = (uint64_t)d->nI * 512u;
-			HNS_TRY(post(d, X_DIV, Fields{{d->div, 1}}, st, [=](hipStream_t s) {
-				HNS_TRY(hns_dev_divergence(D->gB, D->adv, D->div, inv_dx, s));
-				return nb ? hns_combustion_div(fuel, waste, D->div, ex, nb, s) : HNS_OK;
-			}));
-			HNS_TRY(hns_dev_divergence(d->gI, d->adv, d->div, inv_dx, st));
-			return ni ? hns_combustion_div(fuel + nb, waste + nb, d->div + nb, ex, ni, st) : HNS_OK;
-		}
-		if (q == 1) {  // the rest of combustion, buoyancy with the NEW temperature (:226-234), outputs become inputs (:239-246): pointwise, owned voxels
-			if (n_owned) {
-				HNS_TRY(hns_combustion_fields(d->phi[(size_t)fi[0]], d->phi[(size_t)fi[1]], d->phi[(size_t)fi[2]], d->phi[(size_t)fi[3]], d->phi_next[(size_t)fi[0]],
-				                              d->phi_next[(size_t)fi[1]], d->phi_next[(size_t)fi[2]], d->phi_next[(size_t)fi[3]], prm->temperatureRelease, n_owned, st));
-				HNS_TRY(hns_dev_temperature_buoyancy(d->adv, d->phi_next[(size_t)fi[2]], d->adv, dt, prm->ambientTemp, prm->buoyancyStrength, n_owned, st));
-			}
-			Fields f;
-			for (int c = 0; c < 4; ++c) {
-				std::swap(d->phi[(size_t)fi[c]], d->phi_next[(size_t)fi[c]]);
-				f.emplace_back(d->phi[(size_t)fi[c]], 1);
-			}
-			return post(d, X_ADV, f, st, nothing);  // advect_scalars reads their ghosts; hidden under the pressure solve
-		}
-		q -= 2;
-		if (q < blocks) return sor_block_exchanged(q);
-		q -= blocks;
-		if (q == 0) {  // gradient subtraction (:278-289) [and collision, :292-296] -> u, whose ghosts the scalar advection reads
-			if (d->timing && d->tev_used + 2 <= d->tev.size()) {
-				HNS_HIP(hipEventRecord(d->tev[d->tev_used + 1], st));
-				d->tev_used += 2;
-				d->timed_sweeps += iterations;
-			}
-			const float vs = d->voxel_size;
-			HNS_TRY(post(d, X_ADV, Fields{{d->u, 3}}, st, [=](hipStream_t s) {
-				HNS_TRY(hns_dev_subtract_pressure_gradient(D->gB, D->adv, D->p_result, D->u, sd, cl, inv_dx, s));
-				return cl ? hns_dev_enforce_collision_boundaries(D->gB, D->u, sd, vs, s) : HNS_OK;
-			}));
-			HNS_TRY(hns_dev_subtract_pressure_gradient(d->gI, d->adv, d->p_result, d->u, sd, cl, inv_dx, st));
-			return cl ? hns_dev_enforce_collision_boundaries(d->gI, d->u, sd, vs, st) : HNS_OK;
-		}
-		// advect every float field except collision_sdf with the projected velocity (:321-356), and post them for the next substep
-		d->u_ghosts_fresh = !coll;  // (with collision the next substep rewrites u before it advects)
-		std::vector<const float*> in;
-		std::vector<float*> out;
-		std::vector<int> which;
-		for (int sidx = 0; sidx < d->n_scalars; ++sidx)
-			if (sidx != fi[4]) in.push_back(d->phi[(size_t)sidx]), out.push_back(d->phi_next[(size_t)sidx]), which.push_back(sidx);
-		Fields f;
-		for (float* p : out) f.emplace_back(p, 1);
-		const int ns = (int)in.size();
-		if (ns) {
-			HNS_TRY(post(d, X_ADV, f, st, [=](hipStream_t s) {
-				return D->gB->n_active ? hns_dev_advect_scalars(D->gB, D->u, in.data(), const_cast<float* const*>(out.data()), ns, sd, cl, dtv, inv_dx, s) : HNS_OK;
-			}));
-			if (d->gI->n_active) HNS_TRY(hns_dev_advect_scalars(d->gI, d->u, in.data(), out.data(), ns, sd, cl, dt, inv_dx, st));
-		}
-		for (int sidx : which) std::swap(d->phi[(size_t)sidx], d->phi_next[(size_t)sidx]);
-		d->phi_in_flight = ns > 0 && d->world > 1;
-		return HNS_OK;
+		const int its = std::min(2, iterations - it);
+		const PhaseMirror m = phase_args(d, X_P, Outs{{dst, 1}});
+		const bool zero = it == 0;
+		HNS_TRY(chained(m, [&] { return hns_rbgs_block_mirror_launch(d->gO, d->div, src, dst, d->voxel_size, omega_compute(d->voxel_size), zero, &m, st, its); }));
+		std::swap(src, dst);
+		it += its;
+		if (it == iterations) d->p_result = src;
+		return launch_status("hns_dist: blocked mirror sweep");
 	}
 
-	int run(int ph) {
-		if (full()) return run_full(ph);
-		const float inv_dx = 1.0f / d->voxel_size;
-		const int blocks = (iterations + d->k - 1) / d->k;
-		typedef std::vector<std::pair<float*, int>> Fields;
-		typedef std::vector<std::pair<const float*, int>> Outs;
+	// gradient subtraction (:278-289) [and collision, :292-296] -> u, whose ghosts the scalar advection reads
+	int gradient() {
+		if (!full() && d->mirror && !d->chain && d->mir.n_peers) {  // the gradient reads what the peers' last sweep wrote into the ghost voxels
+			// (here and not behind the last sweep: locally connected ranks share one stream, and a rank's wait must not sit in
+			// front of the sweeps it waits for)
+			PhaseMirror m = d->mir;
+			m.seq = d->sweep_seq;
+			hipLaunchKernelGGL(k_sweep_wait, dim3(1), dim3(64), 0, st, m);
+		}
+		if (d->timing && d->tev_used + 2 <= d->tev.size()) {  // the timed region ends when the last refresh of p has landed (complete() in front of the phase)
+			HNS_HIP(hipEventRecord(d->tev[d->tev_used + 1], st));
+			d->tev_used += 2;
+			d->timed_sweeps += iterations;
+		}
 		hns_dist* D = d;
-		auto nothing = [](hipStream_t) { return HNS_OK; };
-		if (ph == 0) {  // the advection inputs: phi was posted by the previous substep unless new fields were uploaded
-			if (d->phi_in_flight) return HNS_OK;
-			Fields f;
-			if (!d->u_ghosts_fresh) f.emplace_back(d->u, 3);
-			for (float* p : d->phi) f.emplace_back(p, 1);
-			if (f.empty()) return HNS_OK;
-			return post(d, X_ADV, f, st, nothing);
-		}
-		if (!(ph >= 3 && ph < 3 + blocks && !d->mirror)) HNS_TRY(complete(d, st));  // (the blocks of the exchanged pressure loop do it themselves: sor_block_exchanged)
-		if (ph == 1) {
-			if (d->chain) {
-				const PhaseMirror m = phase_args(d, X_D1, Outs{{d->adv, 3}});
-				return chained(m, [&] {  // gate | the kernel as it is | copy of the boundary leaves' reach-1 voxels into the peers' ghosts
-					HNS_TRY(hns_dev_advect_vector(d->gO, d->u, d->adv, nullptr, 0, dt, inv_dx, st));
-					if (d->nB && m.n_peers)
-						hipLaunchKernelGGL(k_chain_mirror<3>, dim3((unsigned)d->nB), dim3(64), 0, st, m, 1, (const float*)d->adv, (const float*)nullptr, (const float*)nullptr,
-						                   (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr);
-					return HNS_OK;
-				}, true);
-			}
-			const float dtv = dt;
-			return post(d, X_D1, Fields{{d->adv, 3}}, st, [=](hipStream_t s) { return hns_dev_advect_vector(D->gB, D->u, D->adv, nullptr, 0, dtv, inv_dx, s); },
-			            [=](hipStream_t s) { return hns_dev_advect_vector(D->gI, D->u, D->adv, nullptr, 0, dtv, inv_dx, s); });
-		}
-		if (ph == 2) {
-			if (d->chain) {
-				const PhaseMirror m = phase_args(d, X_DIV, Outs{{d->div, 1}});
-				return chained(m, [&] { return hns_chain_divergence(d->gO, d->adv, d->div, inv_dx, &m, st); });
-			}
-			if (in_line_rank()) return post(d, X_DIV, Fields{{d->div, 1}}, st, [=](hipStream_t s) { return hns_dev_divergence(D->gO, D->adv, D->div, inv_dx, s); }, nothing, true);
-			return post(d, X_DIV, Fields{{d->div, 1}}, st, [=](hipStream_t s) { return hns_dev_divergence(D->gB, D->adv, D->div, inv_dx, s); },
-			            [=](hipStream_t s) { return hns_dev_divergence(D->gI, D->adv, D->div, inv_dx, s); });
-		}
-		if (ph < 3 + blocks) {  // one block of up to k sweeps; all but the last sweep the ghost leaves too
-			const int b = ph - 3;
-			if (!d->mirror) return sor_block_exchanged(b);
-			if (b == 0) {
-				it = 0, src = d->p_a, dst = d->p_b;  // never warm-started (reference HNanoSolver.cu:113): the first sweep reads no p
-				if (d->timing && d->tev_used + 2 <= d->tev.size()) HNS_HIP(hipEventRecord(d->tev[d->tev_used], st));
-			}
-			{  // ONE chained launch of the temporally blocked form: two iterations, or the odd one left over (every rank alike: blocked_mirror)
-				const int its = std::min(2, iterations - it);
-				const PhaseMirror m = phase_args(d, X_P, Outs{{dst, 1}});
-				const bool zero = it == 0;
-				HNS_TRY(chained(m, [&] { return hns_rbgs_block_mirror_launch(d->gO, d->div, src, dst, d->voxel_size, omega_compute(d->voxel_size), zero, &m, st, its); }));
-				std::swap(src, dst);
-				it += its;
-				if (it == iterations) d->p_result = src;
-				return launch_status("hns_dist: blocked mirror sweep");
-			}
-		}
-		if (ph == 3 + blocks) {
-			if (d->mirror && !d->chain && d->mir.n_peers) {  // the gradient reads what the peers' last sweep wrote into the ghost voxels
-				// (here and not behind the last sweep: locally connected ranks share one stream, and a rank's wait must not sit in
-				// front of the sweeps it waits for)
-				PhaseMirror m = d->mir;
-				m.seq = d->sweep_seq;
-				hipLaunchKernelGGL(k_sweep_wait, dim3(1), dim3(64), 0, st, m);
-			}
-			if (d->timing && d->tev_used + 2 <= d->tev.size()) {  // the timed region ends when the last refresh of p has landed (complete() above)
-				HNS_HIP(hipEventRecord(d->tev[d->tev_used + 1], st));
-				d->tev_used += 2;
-				d->timed_sweeps += iterations;
-			}
+		const float ix = inv_dx();
+		if (!full()) {
 			if (d->chain) {  // (its boundary workgroups wait for the peers' last sweep themselves)
 				const PhaseMirror m = phase_args(d, X_ADV, Outs{{d->u, 3}});
-				return chained(m, [&] { return hns_chain_subtract_pressure_gradient(d->gO, d->adv, d->p_result, d->u, inv_dx, &m, st); });
+				return chained(m, [&] { return hns_chain_subtract_pressure_gradient(d->gO, d->adv, d->p_result, d->u, ix, &m, st); });
 			}
 			if (in_line_rank())
-				return post(d, X_ADV, Fields{{d->u, 3}}, st, [=](hipStream_t s) { return hns_dev_subtract_pressure_gradient(D->gO, D->adv, D->p_result, D->u, nullptr, 0, inv_dx, s); }, nothing, true);
-			return post(d, X_ADV, Fields{{d->u, 3}}, st, [=](hipStream_t s) { return hns_dev_subtract_pressure_gradient(D->gB, D->adv, D->p_result, D->u, nullptr, 0, inv_dx, s); },
-			            [=](hipStream_t s) { return hns_dev_subtract_pressure_gradient(D->gI, D->adv, D->p_result, D->u, nullptr, 0, inv_dx, s); });
+				return post(d, X_ADV, Fields{{d->u, 3}}, st, [=](hipStream_t s) { return hns_dev_subtract_pressure_gradient(D->gO, D->adv, D->p_result, D->u, nullptr, 0, ix, s); }, nothing, true);
+			return post(d, X_ADV, Fields{{d->u, 3}}, st, [=](hipStream_t s) { return hns_dev_subtract_pressure_gradient(D->gB, D->adv, D->p_result, D->u, nullptr, 0, ix, s); },
+			            [=](hipStream_t s) { return hns_dev_subtract_pressure_gradient(D->gI, D->adv, D->p_result, D->u, nullptr, 0, ix, s); });
 		}
-		// last phase: advect the scalars, and already post them for the advection that opens the next substep
-		d->u_ghosts_fresh = true;
-		if (d->chain) {
+		// full: with collision; its interior launches follow post() instead of being handed to it
+		const float* sd = sdf();
+		const int c = coll ? 1 : 0;
+		const float vs = d->voxel_size;
+		HNS_TRY(post(d, X_ADV, Fields{{d->u, 3}}, st, [=](hipStream_t s) {
+			HNS_TRY(hns_dev_subtract_pressure_gradient(D->gB, D->adv, D->p_result, D->u, sd, c, ix, s));
+			return c ? hns_dev_enforce_collision_boundaries(D->gB, D->u, sd, vs, s) : HNS_OK;
+		}, nothing));
+		HNS_TRY(hns_dev_subtract_pressure_gradient(d->gI, d->adv, d->p_result, d->u, sd, c, ix, st));
+		return c ? hns_dev_enforce_collision_boundaries(d->gI, d->u, sd, vs, st) : HNS_OK;
+	}
+
+	// advect every float field except collision_sdf with the projected velocity (:321-356), and already post them for the advection that opens the next substep
+	int advect_scalars() {
+		d->u_ghosts_fresh = !coll;  // (with collision the next substep rewrites u before it advects)
+		const float ix = inv_dx();
+		if (chained_form()) {
 			if (d->n_scalars) {
 				Outs outs;
 				for (float* p : d->phi_next) outs.emplace_back(p, 1);
 				const PhaseMirror m = phase_args(d, X_ADV, outs);
 				std::vector<const float*> in(d->phi.begin(), d->phi.end());
 				HNS_TRY(chained(m, [&] {
-					HNS_TRY(hns_dev_advect_scalars(d->gO, d->u, in.data(), d->phi_next.data(), d->n_scalars, nullptr, 0, dt, inv_dx, st));
+					HNS_TRY(hns_dev_advect_scalars(d->gO, d->u, in.data(), d->phi_next.data(), d->n_scalars, nullptr, 0, dt, ix, st));
 					const float* f[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
 					for (int s = 0; s < d->n_scalars && s < 8; ++s) f[s] = d->phi_next[(size_t)s];
 					if (d->nB && m.n_peers)
@@ -829,67 +811,39 @@ struct Step {
 			d->phi_in_flight = true;  // (here: the peers' ghost copies of phi are already being written, nothing to open the next substep with)
 			return HNS_OK;
 		}
-		Fields f;
-		for (float* p : d->phi_next) f.emplace_back(p, 1);  // the boundary leaves' new values travel while the interior is advected
-		const Step self = *this;  // (the scalars' arrays as they are now: they are swapped below)
-		if (d->n_scalars) HNS_TRY(post(d, X_ADV, f, st, [=](hipStream_t s) { return self.advect_scalars(D->gB, inv_dx, s); }, [=](hipStream_t s) { return self.advect_scalars(D->gI, inv_dx, s); }));
-		std::swap(d->phi, d->phi_next);
-		d->phi_in_flight = d->n_scalars > 0 && d->world > 1;
+		std::vector<const float*> in;
+		std::vector<float*> out;
+		std::vector<int> which;
+		for (int s = 0; s < d->n_scalars; ++s)
+			if (s != fi[4]) in.push_back(d->phi[(size_t)s]), out.push_back(d->phi_next[(size_t)s]), which.push_back(s);
+		const int ns = (int)in.size();
+		if (ns) {
+			Fields f;
+			for (float* p : out) f.emplace_back(p, 1);  // the boundary leaves' new values travel while the interior is advected
+			const float* sd = sdf();
+			const int c = coll ? 1 : 0;
+			auto part = [&](hns_grid* g, hipStream_t s) { return g->n_active ? hns_dev_advect_scalars(g, d->u, in.data(), out.data(), ns, sd, c, dt, ix, s) : (int)HNS_OK; };
+			if (full()) {  // (its interior launch follows post() instead of being handed to it)
+				HNS_TRY(post(d, X_ADV, f, st, [&](hipStream_t s) { return part(d->gB, s); }, nothing));
+				HNS_TRY(part(d->gI, st));
+			} else {
+				HNS_TRY(post(d, X_ADV, f, st, [&](hipStream_t s) { return part(d->gB, s); }, [&](hipStream_t s) { return part(d->gI, s); }));
+			}
+		}
+		for (int s : which) std::swap(d->phi[(size_t)s], d->phi_next[(size_t)s]);
+		d->phi_in_flight = ns > 0 && d->world > 1;
 		return HNS_OK;
 	}
 };
 
-int check_step(const hns_dist* d, int iterations, float dt) {
-	if (!d) return fail(HNS_ERR_INVALID_ARGUMENT, "hns_dist_core_substep: null handle");
-	if (dt < 0.0f) return fail(HNS_ERR_INVALID_ARGUMENT, "dt (time step) cannot be negative.");
-	if (iterations <= 0) return fail(HNS_ERR_INVALID_ARGUMENT, "Number of pressure iterations must be positive.");
-	return far_check(d);  // (raised by an earlier substep: kernels are asynchronous; hns_dist_synchronize / hns_dist_download report it too)
-}
-
-}  // namespace
-
-extern "C" {
-
-// One core substep (advect_vector -> divergence -> iterations x RB-SOR -> gradient subtraction -> advect_scalars) of this
-// rank, asynchronous on `stream` (plus the rank's communication stream). RCCL transport, or world == 1.
-int hns_dist_core_substep(hns_dist* d, int iterations, float dt, void* stream) {
-	HNS_TRY(check_step(d, iterations, dt));
-	if (!d->gA) return fail(HNS_ERR_NO_DEVICE, "hns_dist_core_substep: plan-only handle (there is no CPU fallback)");
-	if (!d->local_ranks.empty() && d->world > 1) return fail(HNS_ERR_INVALID_ARGUMENT, "hns_dist_core_substep: locally connected ranks step together (hns_dist_local_core_substep)");
-	if (d->ipc_status && *(volatile int*)d->ipc_status) return fail(HNS_ERR_RUNTIME, "hns_dist: a peer did not answer within 20 s (one-sided transport); results are invalid");
-	memset(d->bytes_sent, 0, sizeof(d->bytes_sent));
-	d->messages_sent = d->exchanges = d->packed_exchanges = 0;
-	Step s{d, iterations, dt, (hipStream_t)stream};
-	for (int ph = 0, n = s.n_phases(); ph < n; ++ph) HNS_TRY(s.run(ph));
-	return HNS_OK;
-}
-
-// The same for ranks connected with hns_dist_connect_local: all ranks advance phase by phase on `stream`.
-int hns_dist_local_core_substep(hns_dist* const* ranks, int world, int iterations, float dt, void* stream) {
-	if (!ranks || world < 1) return fail(HNS_ERR_INVALID_ARGUMENT, "hns_dist_local_core_substep: bad arguments");
-	std::vector<Step> steps;
-	for (int r = 0; r < world; ++r) {
-		HNS_TRY(check_step(ranks[r], iterations, dt));
-		if ((int)ranks[r]->local_ranks.size() != world) return fail(HNS_ERR_INVALID_ARGUMENT, "hns_dist_local_core_substep: ranks are not locally connected");
-		memset(ranks[r]->bytes_sent, 0, sizeof(ranks[r]->bytes_sent));
-		ranks[r]->messages_sent = ranks[r]->exchanges = ranks[r]->packed_exchanges = 0;
-		steps.push_back(Step{ranks[r], iterations, dt, (hipStream_t)stream});
-	}
-	// a message may be the sender's field itself (whole-leaf regions are not packed): every rank takes delivery of the previous
-	// phase's exchange before any rank's next kernel overwrites what was sent
-	for (int ph = 0, n = steps[0].n_phases(); ph < n; ++ph) {
-		if (ph > 0)
-			for (Step& s : steps) HNS_TRY(complete(s.d, s.st));
-		for (Step& s : steps) HNS_TRY(s.run(ph));
-	}
-	return HNS_OK;
-}
-
 // ---- the whole Compute_Sim substep, partitioned (reference HNanoSolver.cu:150-356; single GPU: hns_sim_substep) ----
 // field_index: positions of fuel, waste, temperature, flame and collision_sdf (-1: none) among the rank's scalars (hns_dist_upload
 // order). Every float field except collision_sdf is advected. Owned results equal hns_sim_substep's on the whole domain bit for bit.
-static int sim_step_args(const hns_dist* d, const hns_combustion_params* params, const int* field_index, int has_collision, Step& s) {
-	if (!params || !field_index) return fail(HNS_ERR_INVALID_ARGUMENT, "hns_dist_sim_substep: null argument");
+struct SimArgs { const hns_combustion_params* params; const int* field_index; int has_collision; };
+
+int sim_step_args(const hns_dist* d, const SimArgs& a, Step& s) {
+	const int* field_index = a.field_index;
+	if (!a.params || !field_index) return fail(HNS_ERR_INVALID_ARGUMENT, "hns_dist_sim_substep: null argument");
 	const char* required[4] = {"fuel", "waste", "temperature", "flame"};
 	for (int c = 0; c < 4; ++c) {
 		if (field_index[c] < 0 || field_index[c] >= d->n_scalars) {
@@ -903,46 +857,90 @@ static int sim_step_args(const hns_dist* d, const hns_combustion_params* params,
 	for (int c = 0; c < 4; ++c)
 		if (field_index[4] >= 0 && field_index[4] == field_index[c]) return fail(HNS_ERR_INVALID_ARGUMENT, "hns_dist_sim_substep: collision_sdf shares a scalar with a combustion field");
 	// vorticity confinement reads u* up to (int)factor_scale + 1 voxels from a voxel: it must stay inside the one-leaf ghost layer
-	if ((int)params->factorScale > 6 || (int)params->factorScale < 0) return fail(HNS_ERR_INVALID_ARGUMENT, "hns_dist_sim_substep: factor_scale must be within 0..6 on a partitioned domain");
-	s.prm = params;
+	if ((int)a.params->factorScale > 6 || (int)a.params->factorScale < 0) return fail(HNS_ERR_INVALID_ARGUMENT, "hns_dist_sim_substep: factor_scale must be within 0..6 on a partitioned domain");
+	s.prm = a.params;
 	for (int c = 0; c < 5; ++c) s.fi[c] = field_index[c];
-	s.coll = has_collision && field_index[4] >= 0;  // HNanoSolver.cu:66-75 (collision_sdf itself is never advected, used or not: :327)
-	s.vort = (int)params->factorScale != 0;  // (int)factor_scale == 0: the kernel is a bit-exact copy (hns_api.hip: Substep::part_a)
+	s.coll = a.has_collision && field_index[4] >= 0;  // HNanoSolver.cu:66-75 (collision_sdf itself is never advected, used or not: :327)
+	s.vort = (int)a.params->factorScale != 0;  // (int)factor_scale == 0: the kernel is a bit-exact copy (hns_api.hip: Substep::part_a)
 	return HNS_OK;
 }
 
-int hns_dist_sim_substep(hns_dist* d, int iterations, float dt, const hns_combustion_params* params, const int* field_index, int has_collision, void* stream) {
-	HNS_TRY(check_step(d, iterations, dt));
-	if (!d->gA) return fail(HNS_ERR_NO_DEVICE, "hns_dist_sim_substep: plan-only handle (there is no CPU fallback)");
-	if (!d->local_ranks.empty() && d->world > 1) return fail(HNS_ERR_INVALID_ARGUMENT, "hns_dist_sim_substep: locally connected ranks step together (hns_dist_local_sim_substep)");
-	if (d->ipc_status && *(volatile int*)d->ipc_status) return fail(HNS_ERR_RUNTIME, "hns_dist: a peer did not answer within 20 s (one-sided transport); results are invalid");
+// The names of an entry point pair: a rank stepped on its own, and ranks connected with hns_dist_connect_local stepped together.
+struct EntryPoint { const char *single, *local; };
+constexpr EntryPoint kCore{"hns_dist_core_substep", "hns_dist_local_core_substep"}, kSim{"hns_dist_sim_substep", "hns_dist_local_sim_substep"};
+
+// The preamble of every entry point, for one rank: its checks (`local_world` > 0: one of that many locally connected ranks; 0: a rank on its own), then
+// the statistics of the last substep are cleared and the rank's Step is set up (`sim`: the full substep; null: the core).
+int begin_rank(hns_dist* d, int iterations, float dt, void* stream, const EntryPoint& e, int local_world, const SimArgs* sim, std::vector<Step>& steps) {
+	if (!d) return fail(HNS_ERR_INVALID_ARGUMENT, "hns_dist_core_substep: null handle");
+	if (dt < 0.0f) return fail(HNS_ERR_INVALID_ARGUMENT, "dt (time step) cannot be negative.");
+	if (iterations <= 0) return fail(HNS_ERR_INVALID_ARGUMENT, "Number of pressure iterations must be positive.");
+	HNS_TRY(far_check(d));  // (raised by an earlier substep: kernels are asynchronous; hns_dist_synchronize / hns_dist_download report it too)
+	if (local_world) {
+		if ((int)d->local_ranks.size() != local_world) return fail(HNS_ERR_INVALID_ARGUMENT, (std::string(e.local) + ": ranks are not locally connected").c_str());
+	} else {
+		if (!d->gA) return fail(HNS_ERR_NO_DEVICE, (std::string(e.single) + ": plan-only handle (there is no CPU fallback)").c_str());
+		if (!d->local_ranks.empty() && d->world > 1) return fail(HNS_ERR_INVALID_ARGUMENT, (std::string(e.single) + ": locally connected ranks step together (" + e.local + ")").c_str());
+		if (d->ipc_status && *(volatile int*)d->ipc_status) return fail(HNS_ERR_RUNTIME, "hns_dist: a peer did not answer within 20 s (one-sided transport); results are invalid");
+	}
 	memset(d->bytes_sent, 0, sizeof(d->bytes_sent));
 	d->messages_sent = d->exchanges = d->packed_exchanges = 0;
-	Step s{d, iterations, dt, (hipStream_t)stream};
-	HNS_TRY(sim_step_args(d, params, field_index, has_collision, s));
-	for (int ph = 0, n = s.n_phases(); ph < n; ++ph) HNS_TRY(s.run(ph));
+	steps.push_back(Step{d, iterations, dt, (hipStream_t)stream});
+	return sim ? sim_step_args(d, *sim, steps.back()) : (int)HNS_OK;
+}
+
+// One rank on its own (RCCL, ipc or loopback transport, or world == 1), asynchronous on `stream` (plus the rank's communication stream).
+int substep(hns_dist* d, int iterations, float dt, void* stream, const EntryPoint& e, const SimArgs* sim) {
+	std::vector<Step> steps;
+	HNS_TRY(begin_rank(d, iterations, dt, stream, e, 0, sim, steps));
+	for (const Phase& p : steps[0].phases()) HNS_TRY(steps[0].run(p));
 	return HNS_OK;
 }
 
-int hns_dist_local_sim_substep(hns_dist* const* ranks, int world, int iterations, float dt, const hns_combustion_params* params, const int* field_index, int has_collision,
-                               void* stream) {
-	if (!ranks || world < 1) return fail(HNS_ERR_INVALID_ARGUMENT, "hns_dist_local_sim_substep: bad arguments");
+// Ranks connected with hns_dist_connect_local advance in lock step, phase by phase on `stream`: a message may be the sender's field itself (whole-leaf
+// regions are not packed), so every rank takes delivery of the previous phase's exchange before any rank's next kernel overwrites what was sent.
+// `complete_before_open`: the same in front of phase 0 (the full substep; see hns_dist_local_sim_substep).
+int local_substep(hns_dist* const* ranks, int world, int iterations, float dt, void* stream, const EntryPoint& e, const SimArgs* sim, bool complete_before_open) {
+	if (!ranks || world < 1) return fail(HNS_ERR_INVALID_ARGUMENT, (std::string(e.local) + ": bad arguments").c_str());
 	std::vector<Step> steps;
-	for (int r = 0; r < world; ++r) {
-		HNS_TRY(check_step(ranks[r], iterations, dt));
-		if ((int)ranks[r]->local_ranks.size() != world) return fail(HNS_ERR_INVALID_ARGUMENT, "hns_dist_local_sim_substep: ranks are not locally connected");
-		memset(ranks[r]->bytes_sent, 0, sizeof(ranks[r]->bytes_sent));
-		ranks[r]->messages_sent = ranks[r]->exchanges = ranks[r]->packed_exchanges = 0;
-		steps.push_back(Step{ranks[r], iterations, dt, (hipStream_t)stream});
-		HNS_TRY(sim_step_args(ranks[r], params, field_index, has_collision, steps.back()));
-	}
-	for (int ph = 0, n = steps[0].n_phases(); ph < n; ++ph) {
-		// (before phase 0 too: with collision the phase rewrites u and posts it again, and a rank must have taken delivery of the
-		// exchange the previous substep left in flight before a peer posts the next one)
-		for (Step& s : steps) HNS_TRY(complete(s.d, s.st));
-		for (Step& s : steps) HNS_TRY(s.run(ph));
+	for (int r = 0; r < world; ++r) HNS_TRY(begin_rank(ranks[r], iterations, dt, stream, e, world, sim, steps));
+	// every rank runs rank 0's list: ranks whose lists differ (created with different sweeps_per_exchange: hns_dist_connect_local does not compare it) are refused here
+	const std::vector<Phase> phases = steps[0].phases();
+	for (const Step& s : steps)
+		if (s.phases() != phases) return fail(HNS_ERR_INVALID_ARGUMENT, (std::string(e.local) + ": ranks with different phases (created with different sweeps_per_exchange?)").c_str());
+	for (size_t i = 0; i < phases.size(); ++i) {
+		if (i > 0 || complete_before_open)
+			for (Step& s : steps) HNS_TRY(complete(s.d, s.st));
+		for (Step& s : steps) HNS_TRY(s.run(phases[i]));
 	}
 	return HNS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+// One core substep (advect_vector -> divergence -> iterations x RB-SOR -> gradient subtraction -> advect_scalars) of this
+// rank, asynchronous on `stream` (plus the rank's communication stream). RCCL transport, or world == 1.
+int hns_dist_core_substep(hns_dist* d, int iterations, float dt, void* stream) { return substep(d, iterations, dt, stream, kCore, nullptr); }
+
+// The same for ranks connected with hns_dist_connect_local: all ranks advance phase by phase on `stream`.
+int hns_dist_local_core_substep(hns_dist* const* ranks, int world, int iterations, float dt, void* stream) {
+	return local_substep(ranks, world, iterations, dt, stream, kCore, nullptr, false);
+}
+
+// the whole Compute_Sim substep, partitioned (see SimArgs)
+int hns_dist_sim_substep(hns_dist* d, int iterations, float dt, const hns_combustion_params* params, const int* field_index, int has_collision, void* stream) {
+	const SimArgs a{params, field_index, has_collision};
+	return substep(d, iterations, dt, stream, kSim, &a);
+}
+
+// (complete before phase 0 too: with collision that phase rewrites u and posts it again, and a rank must have taken delivery of the exchange the
+// previous substep left in flight before a peer posts the next one)
+int hns_dist_local_sim_substep(hns_dist* const* ranks, int world, int iterations, float dt, const hns_combustion_params* params, const int* field_index, int has_collision,
+                               void* stream) {
+	const SimArgs a{params, field_index, has_collision};
+	return local_substep(ranks, world, iterations, dt, stream, kSim, &a, true);
 }
 
 int hns_dist_timing(hns_dist* d, int max_solves) {

@@ -159,7 +159,7 @@ class ReferenceRank:
             self.phi, self.phi_next = self.phi_next, self.phi
             self.phi_in_flight = self.world > 1
 
-    # ---- the whole Compute_Sim substep (hns_dist_substep.hip: Step::run_full; reference HNanoSolver.cu:150-356) ----
+    # ---- the whole Compute_Sim substep (hns_dist_substep.hip: Step::phases() of the full substep; reference HNanoSolver.cu:150-356) ----
     def sim_substep(self, names, iterations, dt, params, has_collision):
         """`names`: the scalars in load order. Same phases, exchange types and launch ranges as hns_dist_sim_substep."""
         G, k = self.G, self.k

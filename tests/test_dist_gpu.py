@@ -447,6 +447,28 @@ def test_unconnected_ranks_refuse_to_step():
         d.core_substep(3, 1.0 / 24.0)
 
 
+@pytest.mark.parametrize("sim", [False, True])
+def test_local_ranks_with_different_sweeps_per_exchange_refuse_to_step(sim):
+    """hns_dist_connect_local does not compare sweeps_per_exchange (1 and 3: neither takes the chained form, so it connects), but the two ranks' substeps
+    then have different phase lists. The local driver steps every rank through rank 0's list, so it refuses before any launch."""
+    import hnanosolver_amd as H
+    import torch
+    from hnanosolver_amd import _lib, api
+
+    origins = fields.dense_leaves(16)
+    names = SIM_NAMES if sim else ["density"]
+    ranks = [HD.DistRank(origins, 2, r, 1.0 / 16, n_scalars=len(names), sweeps_per_exchange=k) for r, k in enumerate((1, 3))]
+    HD.DistRank.connect_local(ranks)
+    stream = int(torch.cuda.current_stream().cuda_stream)
+    with pytest.raises(H.HNSError, match="different phases") as e:
+        if sim:
+            HD.DistRank.local_sim_substep(ranks, names, 6, 1.0 / 24.0, api.CombustionParams(), True, stream)
+        else:
+            HD.DistRank.local_core_substep(ranks, 6, 1.0 / 24.0, stream)
+    assert e.value.code == _lib.HNS_ERR_INVALID_ARGUMENT
+    assert all(d.info()["exchanges"] == 0 for d in ranks)
+
+
 @pytest.mark.parametrize("partition", [False, True])
 def test_bench_driver_single_rank(partition):
     """bench.py's multi-GPU driver with world = 1 (no peers): runs, times its pressure loop, equals the single grid."""
