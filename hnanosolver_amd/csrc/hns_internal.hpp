@@ -184,7 +184,7 @@ struct hns_sim {
 	// An allocation of their own from the arena pool, made on first use: nothing else reads them.
 	unsigned char* d_masks = nullptr;
 	size_t masks_bytes = 0;
-	hipEvent_t rev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // phase boundaries of the last hns_sim_regrid (hns_sim_regrid_times)
+	hipEvent_t rev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // phase boundaries of the last hns_sim_regrid (hns_sim_regrid_times: 0-4); 5: the origins' read-back
 	bool regrid_timed = false;
 	int device = -1;
 	int find(const char* name) const {

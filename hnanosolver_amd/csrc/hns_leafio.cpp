@@ -215,6 +215,57 @@ int hns_dilate_leaf_masks(const int32_t* origins, uint64_t n, const unsigned cha
 	return HNS_OK;
 }
 
+// openvdb::tools::compSum(a, b) over two leaf sets (SOP_HNanoSolver.cpp:159-179): every leaf of either side, masks ORed, values fl(a + b) per component
+// where the side without the leaf contributes +0.0f (so a -0.0f on one side alone becomes +0.0f). Leaf order is hns_union_leaves'.
+int hns_add_leaves(const int32_t* a_origins, uint64_t na, const unsigned char* a_masks, const float* a_values, const int32_t* b_origins, uint64_t nb,
+                   const unsigned char* b_masks, const float* b_values, int ncomp, int32_t* out_origins, unsigned char* out_masks, float* out_values,
+                   uint64_t capacity, uint64_t* n_out) {
+	if ((na && (!a_origins || !a_values)) || (nb && (!b_origins || !b_values)) || (ncomp != 1 && ncomp != 3))
+		return fail(HNS_ERR_INVALID_ARGUMENT, "hns_add_leaves: bad arguments");
+	if (int rc = check_aligned(a_origins, na, "hns_add_leaves")) return rc;
+	if (int rc = check_aligned(b_origins, nb, "hns_add_leaves")) return rc;
+	std::unordered_map<Key, std::pair<int64_t, int64_t>, KeyHash> at;  // origin -> (leaf of a, leaf of b), -1 = absent
+	at.reserve((size_t)(na + nb) * 2);
+	for (int side = 0; side < 2; ++side) {
+		const int32_t* o = side ? b_origins : a_origins;
+		const uint64_t n = side ? nb : na;
+		for (uint64_t i = 0; i < n; ++i) {
+			auto& e = at.try_emplace(Key{o[3 * i], o[3 * i + 1], o[3 * i + 2]}, std::pair<int64_t, int64_t>{-1, -1}).first->second;
+			int64_t& slot = side ? e.second : e.first;
+			if (slot >= 0) {
+				set_error("hns_add_leaves: duplicate leaf origin (%d, %d, %d) in input %c", o[3 * i], o[3 * i + 1], o[3 * i + 2], side ? 'b' : 'a');
+				return HNS_ERR_TOPOLOGY;
+			}
+			slot = (int64_t)i;
+		}
+	}
+	std::vector<Key> keys;
+	keys.reserve(at.size());
+	for (const auto& kv : at) keys.push_back(kv.first);
+	if ((out_masks || out_values) && keys.size() > capacity) {
+		set_error("hns_add_leaves: %zu leaves do not fit the output capacity %llu", keys.size(), (unsigned long long)capacity);
+		return HNS_ERR_INVALID_ARGUMENT;
+	}
+	if (int rc = emit_sorted(keys, out_origins, capacity, n_out, "hns_add_leaves")) return rc;
+	const size_t leaf_floats = 512u * (size_t)ncomp;
+	for (size_t i = 0; i < keys.size() && (out_masks || out_values); ++i) {
+		const auto ab = at[keys[i]];
+		if (out_masks)
+			for (int w = 0; w < 64; ++w) {
+				const unsigned char ma = ab.first < 0 ? 0 : a_masks ? a_masks[64 * ab.first + w] : 0xFF;
+				const unsigned char mb = ab.second < 0 ? 0 : b_masks ? b_masks[64 * ab.second + w] : 0xFF;
+				out_masks[64 * i + w] = ma | mb;
+			}
+		if (out_values) {
+			const float* va = ab.first < 0 ? nullptr : a_values + (size_t)ab.first * leaf_floats;
+			const float* vb = ab.second < 0 ? nullptr : b_values + (size_t)ab.second * leaf_floats;
+			float* dst = out_values + i * leaf_floats;
+			for (size_t k = 0; k < leaf_floats; ++k) dst[k] = (va ? va[k] : 0.0f) + (vb ? vb[k] : 0.0f);
+		}
+	}
+	return HNS_OK;
+}
+
 // topologyUnion of two leaf sets (SOP_HNanoSolver.cpp:189,195-197), in OpenVDB leaf order, duplicates removed.
 int hns_union_leaves(const int32_t* a, uint64_t na, const int32_t* b, uint64_t nb, int32_t* out_origins, uint64_t capacity, uint64_t* n_out) {
 	if ((na && !a) || (nb && !b)) return fail(HNS_ERR_INVALID_ARGUMENT, "hns_union_leaves: bad arguments");

@@ -4,17 +4,24 @@
 // (hns_sim_download -> hns_dilate_leaf_masks -> hns_union_leaves -> hns_gather_leaves -> new grid -> hns_sim_upload) moves every field over PCIe
 // twice; here only leaf origins cross (12 bytes per leaf each way) plus, when a collision SDF source is given, that source.
 //
-//   1. candidates  one thread per (old leaf, offset in the (2R+1)^3 leaf neighbourhood), R = ceil(p / 8), and one per SDF leaf: a hit (the old leaf's
-//                  active voxels reach the candidate's box, hns_dilate.hpp) goes into a fresh origin hash with compare-and-swap, then the hash is compacted
+// hns_sim_regrid_sourced first adds a frame's SOURCES into the fields (SOP_HNanoSolver.cpp:159-179: compSum of the emitter into the feedback grids,
+// before the domain is built from the summed velocity). Only the source leaves cross PCIe; the sum is formed in the field phase, the velocity
+// source's leaves and masks join the domain through the candidate and mask phases (dilation distributes over the union, so nothing is pre-merged).
+//
+//   1. candidates  one thread per (old leaf, offset in the (2R+1)^3 leaf neighbourhood), R = ceil(p / 8), one per SDF leaf and one per (velocity source
+//                  leaf, offset): a hit (the leaf's active voxels reach the candidate's box, hns_dilate.hpp) goes into a fresh origin hash with
+//                  compare-and-swap, then the hash is compacted. Each source's leaves go into an origin hash of their own (duplicates are refused)
 //   2. order       the origins come to the host, are sorted into OpenVDB leaf order and become a new hns_grid through the usual path (Topology::prepare,
-//                  hns_grid_upload: hash, nbr27, launch order)
-//   3. masks       one wave per new leaf gathers the masks of the old leaves within reach (old grid's origin hash), dilates each separably into its own
-//                  box, ORs them across the wave and ORs in the SDF leaf's mask; the same wave records which old leaf (if any) has this origin
+//                  hns_grid_upload: hash, nbr27, launch order); the source values are uploaded meanwhile
+//   3. masks       one wave per new leaf gathers the masks of the old leaves and velocity source leaves within reach (their origin hashes), dilates
+//                  each separably into its own box, ORs them across the wave and ORs in the SDF leaf's mask; the same wave records which old leaf and
+//                  which velocity source leaf (if any) has this origin. Each float source's leaves are indexed into the new grid
 //   4. fields      velocity and every float field, 16 bytes per load and store, from the old leaf or the fill (zeros; bytes 0x01 for collision_sdf),
-//                  into a fresh arena from the pool; the old arena goes back to the pool
+//                  into a fresh arena from the pool; a sourced field gets (old or +0) + (source or +0) instead. The old arena goes back to the pool
 //
 // Everything that decides a result is order-free: hash slots hold the smallest thing that identifies a candidate (its thread id), the compacted
-// order is discarded by the sort, and the mask OR is commutative. Two runs give the same bytes.
+// order is discarded by the sort, the mask OR is commutative and a source hash is only ever asked for an origin it holds once. Two runs give the
+// same bytes.
 #include <algorithm>
 #include <cstring>
 #include <vector>
@@ -41,12 +48,15 @@ __device__ __forceinline__ void load_mask(const unsigned char* masks, int l, uin
 	for (int x = 0; x < 8; ++x) m[x] = w ? w[x] : ~0ull;
 }
 
-// The candidate a thread id stands for: ids [0, n_dil) are (old leaf, offset) pairs, ids [n_dil, n_dil + n_sdf) the SDF leaves.
+// The candidate a thread id stands for: ids [0, n_dil) are (old leaf, offset) pairs, ids [n_dil, n_dil + n_sdf) the SDF leaves, ids
+// [n_dil + n_sdf, n_dil + n_sdf + n_vdil) (velocity source leaf, offset) pairs.
 struct Candidates {
 	const int4* old_origins;
 	const unsigned char* old_masks;  // null: every voxel active
 	const int4* sdf;
-	uint64_t n_dil, n_sdf;
+	const int4* vsrc;                 // the velocity source's leaves
+	const unsigned char* vsrc_masks;  // null: every voxel active
+	uint64_t n_dil, n_sdf, n_vdil;
 	int side, R, p;
 	unsigned long long* table;
 	uint32_t mask;
@@ -54,17 +64,24 @@ struct Candidates {
 	unsigned long long* count;  // [0] slots reserved, [1] overflow, [2] compacted leaves
 };
 
-__device__ __forceinline__ bool cand_origin(const Candidates& c, uint64_t t, int& x, int& y, int& z, int& l, int (&d)[3]) {
+// l: the old or velocity source leaf whose active voxels (`masks`) must reach the candidate, -1 for an SDF leaf
+__device__ __forceinline__ bool cand_origin(const Candidates& c, uint64_t t, int& x, int& y, int& z, int& l, int (&d)[3], const unsigned char*& masks) {
+	const int4* origins = c.old_origins;
+	masks = c.old_masks;
 	if (t >= c.n_dil) {
-		const int4 o = c.sdf[t - c.n_dil];
-		x = o.x, y = o.y, z = o.z, l = -1;
-		return true;
+		if (t < c.n_dil + c.n_sdf) {
+			const int4 o = c.sdf[t - c.n_dil];
+			x = o.x, y = o.y, z = o.z, l = -1;
+			return true;
+		}
+		t -= c.n_dil + c.n_sdf;
+		origins = c.vsrc, masks = c.vsrc_masks;
 	}
 	const uint64_t K = (uint64_t)c.side * c.side * c.side;
 	l = (int)(t / K);
 	const int k = (int)(t - (uint64_t)l * K);
 	d[0] = k / (c.side * c.side) - c.R, d[1] = (k / c.side) % c.side - c.R, d[2] = k % c.side - c.R;
-	const int4 o = c.old_origins[l];
+	const int4 o = origins[l];
 	const int64_t nx = (int64_t)o.x + 8 * d[0], ny = (int64_t)o.y + 8 * d[1], nz = (int64_t)o.z + 8 * d[2];
 	if (nx < INT32_MIN || nx > INT32_MAX - 7 || ny < INT32_MIN || ny > INT32_MAX - 7 || nz < INT32_MIN || nz > INT32_MAX - 7) return false;
 	x = (int)nx, y = (int)ny, z = (int)nz;
@@ -72,13 +89,14 @@ __device__ __forceinline__ bool cand_origin(const Candidates& c, uint64_t t, int
 }
 
 __global__ __launch_bounds__(256) void k_regrid_candidates(Candidates c) {
-	const uint64_t total = c.n_dil + c.n_sdf;
+	const uint64_t total = c.n_dil + c.n_sdf + c.n_vdil;
 	for (uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (uint64_t)gridDim.x * 256) {
 		int x, y, z, l, d[3] = {0, 0, 0};
-		if (!cand_origin(c, t, x, y, z, l, d)) continue;
-		if (l >= 0) {  // a hit iff the old leaf's active voxels, dilated by p, reach the candidate's box (hns_dilate_leaves' slab test)
+		const unsigned char* ms;
+		if (!cand_origin(c, t, x, y, z, l, d, ms)) continue;
+		if (l >= 0) {  // a hit iff the leaf's active voxels, dilated by p, reach the candidate's box (hns_dilate_leaves' slab test)
 			uint64_t m[8], out[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-			load_mask(c.old_masks, l, m);
+			load_mask(ms, l, m);
 			if (!dilate_into(m, -8 * d[0], -8 * d[1], -8 * d[2], c.p, out)) continue;
 		}
 		uint32_t s = d_hash_origin(x, y, z) & c.mask;
@@ -97,7 +115,8 @@ __global__ __launch_bounds__(256) void k_regrid_candidates(Candidates c) {
 				if (cur == kEmptySlot) break;
 			}
 			int qx, qy, qz, ql, qd[3];
-			cand_origin(c, cur, qx, qy, qz, ql, qd);  // (an id in the table always stands for a valid origin)
+			const unsigned char* qm;
+			cand_origin(c, cur, qx, qy, qz, ql, qd, qm);  // (an id in the table always stands for a valid origin)
 			if (qx == x && qy == y && qz == z) break;
 			s = (s + 1) & c.mask;
 		}
@@ -110,23 +129,57 @@ __global__ __launch_bounds__(256) void k_regrid_compact(Candidates c, int4* __re
 	const unsigned long long t = c.table[s];
 	if (t == kEmptySlot) return;
 	int x, y, z, l, d[3];
-	cand_origin(c, t, x, y, z, l, d);
+	const unsigned char* m;
+	cand_origin(c, t, x, y, z, l, d, m);
 	out[atomicAdd(&c.count[2], 1ull)] = make_int4(x, y, z, 0);
 }
 
-// sdf_idx[new leaf] = the SDF leaf with its origin; two SDF leaves on one origin raise *dup
+// A source's leaves by origin: open addressing over `mask + 1` (>= 2 n) slots holding the leaf index, -1 = empty. Two leaves on one origin raise *dup.
+struct SrcHash {
+	const int4* origins;
+	const int* table;
+	uint32_t mask;
+};
+
+__global__ __launch_bounds__(256) void k_regrid_src_hash(const int4* __restrict__ origins, int n, int* __restrict__ table, uint32_t mask, int* __restrict__ dup) {
+	const int i = blockIdx.x * 256 + threadIdx.x;
+	if (i >= n) return;
+	const int4 o = origins[i];
+	for (uint32_t s = d_hash_origin(o.x, o.y, o.z) & mask;; s = (s + 1) & mask) {
+		const int cur = atomicCAS(&table[s], -1, i);
+		if (cur == -1) return;
+		const int4 q = origins[cur];
+		if (q.x == o.x && q.y == o.y && q.z == o.z) {
+			*dup = 1;
+			return;
+		}
+	}
+}
+
+__device__ __forceinline__ int d_find_src(const SrcHash& h, int x, int y, int z) {
+	for (uint32_t s = d_hash_origin(x, y, z) & h.mask;; s = (s + 1) & h.mask) {
+		const int i = h.table[s];
+		if (i < 0) return -1;
+		const int4 q = h.origins[i];
+		if (q.x == x && q.y == y && q.z == z) return i;
+	}
+}
+
+// sdf_idx[new leaf] = the SDF (or float source) leaf with its origin; two such leaves on one origin raise *dup. Leaves outside the new grid are skipped.
 __global__ __launch_bounds__(256) void k_regrid_sdf_index(GridDev ng, const int4* __restrict__ sdf, int n_sdf, int* __restrict__ sdf_idx, int* __restrict__ dup) {
 	const int i = blockIdx.x * 256 + threadIdx.x;
 	if (i >= n_sdf) return;
 	const int4 o = sdf[i];
-	const int b = d_find_leaf(ng, o.x, o.y, o.z);  // (present: every SDF leaf is a leaf of the new grid)
+	const int b = d_find_leaf(ng, o.x, o.y, o.z);  // (every SDF leaf is a leaf of the new grid; a float source's may not be)
 	if (b >= 0 && atomicCAS(&sdf_idx[b], -1, i) != -1) *dup = 1;
 }
 
-// One wave per new leaf: its dilated mask (OR over the old leaves within reach, then the SDF leaf's mask) and the old leaf with its origin (map, -1 = new).
+// One wave per new leaf: its dilated mask (OR over the old leaves and velocity source leaves within reach, then the SDF leaf's mask), the old leaf with
+// its origin (map, -1 = new) and, with a velocity source (vh.table != null), its leaf with that origin (vmap, -1 = none).
 __global__ __launch_bounds__(256) void k_regrid_masks(GridDev og, const unsigned char* __restrict__ old_masks, const int4* __restrict__ new_origins, int n_new, int p, int R,
-                                                      const int* __restrict__ sdf_idx, const unsigned char* __restrict__ sdf_masks, uint64_t* __restrict__ new_masks,
-                                                      int* __restrict__ map) {
+                                                      const int* __restrict__ sdf_idx, const unsigned char* __restrict__ sdf_masks, SrcHash vh,
+                                                      const unsigned char* __restrict__ vsrc_masks, uint64_t* __restrict__ new_masks, int* __restrict__ map,
+                                                      int* __restrict__ vmap) {
 	const int b = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
 	if (b >= n_new) return;
 	const int4 o = new_origins[b];
@@ -138,11 +191,22 @@ __global__ __launch_bounds__(256) void k_regrid_masks(GridDev og, const unsigned
 		int l = -1;
 		if (og.n_leaves > 0 && nx >= INT32_MIN && nx <= INT32_MAX && ny >= INT32_MIN && ny <= INT32_MAX && nz >= INT32_MIN && nz <= INT32_MAX)
 			l = d_find_leaf(og, (int)nx, (int)ny, (int)nz);
-		if (k == centre) map[b] = l;
-		if (l < 0) continue;
+		int vl = -1;
+		if (vh.table && nx >= INT32_MIN && nx <= INT32_MAX && ny >= INT32_MIN && ny <= INT32_MAX && nz >= INT32_MIN && nz <= INT32_MAX)
+			vl = d_find_src(vh, (int)nx, (int)ny, (int)nz);
+		if (k == centre) {
+			map[b] = l;
+			if (vh.table) vmap[b] = vl;
+		}
 		uint64_t m[8];
-		load_mask(old_masks, l, m);
-		dilate_into(m, 8 * d[0], 8 * d[1], 8 * d[2], p, acc);
+		if (l >= 0) {
+			load_mask(old_masks, l, m);
+			dilate_into(m, 8 * d[0], 8 * d[1], 8 * d[2], p, acc);
+		}
+		if (vl >= 0) {
+			load_mask(vsrc_masks, vl, m);
+			dilate_into(m, 8 * d[0], 8 * d[1], 8 * d[2], p, acc);
+		}
 	}
 #pragma unroll
 	for (int x = 0; x < 8; ++x) {
@@ -199,6 +263,44 @@ __global__ __launch_bounds__(256) void k_regrid_copy(CopySet cs, uint32_t n_f4) 
 	}
 }
 
+struct AddSet {
+	const float4* a[kCopyFields];  // the old field
+	const float4* b[kCopyFields];  // the source's leaves
+	float4* dst[kCopyFields];
+	const int* map_a[kCopyFields];  // new leaf -> old leaf, -1 = none
+	const int* map_b[kCopyFields];  // new leaf -> source leaf, -1 = none
+};
+
+// A sourced field (compSum, then the gather): (old or +0) + (source or +0) in f32, the k_regrid_copy layout. All eight loads in flight before the adds.
+template <int NC>
+__global__ __launch_bounds__(256) void k_regrid_add(AddSet as, uint32_t n_f4) {
+	constexpr uint32_t per_leaf = 128u * NC;
+	const int f = blockIdx.y;
+	const float4* __restrict__ a = as.a[f];
+	const float4* __restrict__ b = as.b[f];
+	float4* __restrict__ dst = as.dst[f];
+	const int* __restrict__ map_a = as.map_a[f];
+	const int* __restrict__ map_b = as.map_b[f];
+	const uint32_t base = blockIdx.x * 1024u + threadIdx.x;
+	float4 va[4], vb[4];
+#pragma unroll
+	for (int j = 0; j < 4; ++j) {
+		const uint32_t e = base + 256u * j;
+		va[j] = vb[j] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+		if (e < n_f4) {
+			const uint32_t leaf = e / per_leaf, r = e - leaf * per_leaf;
+			const int la = map_a[leaf], lb = map_b[leaf];
+			if (la >= 0) va[j] = a[(size_t)la * per_leaf + r];
+			if (lb >= 0) vb[j] = b[(size_t)lb * per_leaf + r];
+		}
+	}
+#pragma unroll
+	for (int j = 0; j < 4; ++j) {
+		const uint32_t e = base + 256u * j;
+		if (e < n_f4) dst[e] = make_float4(va[j].x + vb[j].x, va[j].y + vb[j].y, va[j].z + vb[j].z, va[j].w + vb[j].w);
+	}
+}
+
 // device allocations of one regrid, returned to the pool however it ends (hns_arena_put waits for the device first)
 struct Scratch {
 	std::vector<std::pair<void*, size_t>> held;
@@ -243,19 +345,110 @@ int copy_fields(const CopySet& cs, int nf, int nc, uint64_t n_new, hipStream_t s
 	return HNS_OK;
 }
 
-// The regrid proper; the sim is only touched at the very end, when everything has succeeded.
-int regrid(hns_sim* s, int p, const int32_t* sdf_origins, uint64_t n_sdf, const unsigned char* sdf_masks, const float* sdf_values, hipStream_t st, hns_grid** out) {
+int add_fields(const AddSet& as, int nf, int nc, uint64_t n_new, hipStream_t st) {
+	if (!nf || !n_new) return HNS_OK;
+	const uint32_t n_f4 = (uint32_t)(n_new * 128u * (uint64_t)nc);
+	const dim3 grid((n_f4 + 1023u) / 1024u, (unsigned)nf);
+	if (nc == 3)
+		k_regrid_add<3><<<grid, 256, 0, st>>>(as, n_f4);
+	else
+		k_regrid_add<1><<<grid, 256, 0, st>>>(as, n_f4);
+	HNS_HIP(hipGetLastError());
+	return HNS_OK;
+}
+
+// One source of hns_sim_regrid_sourced, validated, and where its leaves live on the device.
+struct Source {
+	const hns_leaf_source* s = nullptr;
+	int field = -1;  // float field index, -1 = the velocity
+	std::vector<int32_t> o4;  // the origins as int4 (host staging of the upload)
+	int4* origins = nullptr;
+	int* table = nullptr;  // origin hash (SrcHash)
+	uint32_t mask = 0;
+	unsigned char* masks = nullptr;  // velocity only; null = every voxel active
+	float* values = nullptr;
+	int* idx = nullptr;  // new leaf -> source leaf, -1 = none (phase 3)
+};
+
+int check_sources(const hns_sim* s, const hns_leaf_source* src, int n_src, const char* who, std::vector<Source>& out) {
+	if (n_src < 0 || (n_src > 0 && !src)) {
+		set_error("%s: bad source list", who);
+		return HNS_ERR_INVALID_ARGUMENT;
+	}
+	std::vector<char> taken(s->names.size() + 1, 0);  // [names.size()]: the velocity
+	out.resize((size_t)n_src);
+	for (int i = 0; i < n_src; ++i) {
+		const hns_leaf_source& q = src[i];
+		const char* nm = q.name ? q.name : "(null)";
+		if (q.ncomp != 1 && q.ncomp != 3) {
+			set_error("%s: source %d ('%s'): ncomp %d (1 or 3)", who, i, nm, q.ncomp);
+			return HNS_ERR_INVALID_ARGUMENT;
+		}
+		const int f = q.name ? s->find(q.name) : -1;
+		if (q.name && !strcmp(q.name, "collision_sdf")) {
+			set_error("%s: source %d: 'collision_sdf' cannot be a source (the SDF comes from the collision input, never from the feedback)", who, i);
+			return HNS_ERR_INVALID_ARGUMENT;
+		}
+		if (q.ncomp == 1 && f < 0) {
+			set_error("%s: source %d: the sim has no float field '%s'", who, i, nm);
+			return HNS_ERR_INVALID_ARGUMENT;
+		}
+		if (q.ncomp == 3 && f >= 0) {
+			set_error("%s: source %d: ncomp 3 under the float field name '%s'", who, i, nm);
+			return HNS_ERR_INVALID_ARGUMENT;
+		}
+		const size_t slot = q.ncomp == 3 ? s->names.size() : (size_t)f;
+		if (taken[slot]) {
+			if (q.ncomp == 3)
+				set_error("%s: source %d: a second velocity source", who, i);
+			else
+				set_error("%s: source %d: a second source for '%s'", who, i, nm);
+			return HNS_ERR_INVALID_ARGUMENT;
+		}
+		taken[slot] = 1;
+		if (q.n_leaves && (!q.origins || !q.values)) {
+			set_error("%s: source %d ('%s'): origins or values NULL with %llu leaves", who, i, nm, (unsigned long long)q.n_leaves);
+			return HNS_ERR_INVALID_ARGUMENT;
+		}
+		if (q.n_leaves > (uint64_t(1) << 22)) {
+			set_error("%s: source %d ('%s'): %llu leaves exceed the 2^22-leaf limit", who, i, nm, (unsigned long long)q.n_leaves);
+			return HNS_ERR_INVALID_ARGUMENT;
+		}
+		for (uint64_t k = 0; k < 3 * q.n_leaves; ++k)
+			if (q.origins[k] & 7) {
+				set_error("%s: source %d ('%s'): leaf origin %llu is not 8-aligned", who, i, nm, (unsigned long long)(k / 3));
+				return HNS_ERR_TOPOLOGY;
+			}
+		out[i].s = &q;
+		out[i].field = q.ncomp == 3 ? -1 : f;
+	}
+	return HNS_OK;
+}
+
+// The regrid proper; the sim is only touched at the very end, when everything has succeeded. `who` names the entry point in messages.
+int regrid(hns_sim* s, int p, const hns_leaf_source* src, int n_src, const int32_t* sdf_origins, uint64_t n_sdf, const unsigned char* sdf_masks, const float* sdf_values,
+           hipStream_t st, hns_grid** out, const char* who) {
 	hns_grid* og = s->grid;
 	const bool have_src = sdf_values != nullptr;
 	const int i_sdf = s->find("collision_sdf");
-	if (og->first_active != 0 || og->n_active != (uint64_t)og->topo.n_leaves)
-		return fail(HNS_ERR_INVALID_ARGUMENT, "hns_sim_regrid: the grid's launch range is not the whole grid (a multi-GPU rank's grid cannot be regridded)");
-	if (have_src && i_sdf < 0) return fail(HNS_ERR_INVALID_ARGUMENT, "hns_sim_regrid: a collision SDF source was given but the sim has no field 'collision_sdf'");
+	if (og->first_active != 0 || og->n_active != (uint64_t)og->topo.n_leaves) {
+		set_error("%s: the grid's launch range is not the whole grid (a multi-GPU rank's grid cannot be regridded)", who);
+		return HNS_ERR_INVALID_ARGUMENT;
+	}
+	if (have_src && i_sdf < 0) {
+		set_error("%s: a collision SDF source was given but the sim has no field 'collision_sdf'", who);
+		return HNS_ERR_INVALID_ARGUMENT;
+	}
 	for (uint64_t i = 0; i < 3 * n_sdf; ++i)
 		if (sdf_origins[i] & 7) {
-			set_error("hns_sim_regrid: SDF leaf origin %llu is not 8-aligned", (unsigned long long)(i / 3));
+			set_error("%s: SDF leaf origin %llu is not 8-aligned", who, (unsigned long long)(i / 3));
 			return HNS_ERR_TOPOLOGY;
 		}
+	std::vector<Source> srcs;  // (before the scratch: its staging outlives the device work)
+	HNS_TRY_RC(check_sources(s, src, n_src, who, srcs));
+	Source* vsrc = nullptr;
+	for (Source& q : srcs)
+		if (q.field < 0) vsrc = &q;
 	CurrentDevice on(s->device);
 	if (!s->rev[0])
 		for (hipEvent_t& e : s->rev) HNS_HIP(hipEventCreate(&e));
@@ -266,7 +459,8 @@ int regrid(hns_sim* s, int p, const int32_t* sdf_origins, uint64_t n_sdf, const 
 	const uint64_t n_old = (uint64_t)og->topo.n_leaves;
 	const int R = (p + 7) / 8, side = 2 * R + 1;
 	const uint64_t n_dil = n_old * (uint64_t)side * side * side;
-	const uint64_t cap = std::min<uint64_t>(n_dil + n_sdf, kMaxCandidates);
+	const uint64_t n_vdil = vsrc ? vsrc->s->n_leaves * (uint64_t)side * side * side : 0;
+	const uint64_t cap = std::min<uint64_t>(n_dil + n_sdf + n_vdil, kMaxCandidates);
 	uint64_t T = 16;
 	while (T < 2 * cap) T <<= 1;
 	std::vector<int32_t> sdf4((size_t)n_sdf * 4, 0);
@@ -283,15 +477,54 @@ int regrid(hns_sim* s, int p, const int32_t* sdf_origins, uint64_t n_sdf, const 
 	int4* d_sdf = (int4*)q;
 	q += sz1[2];
 	c.count = (unsigned long long*)q;
+	// the sources: per source its origins, origin hash, masks (velocity) and values, and one duplicate flag each
+	int* src_dup = nullptr;
+	if (!srcs.empty()) {
+		size_t bytes = pad256(4 * srcs.size());
+		for (Source& sr : srcs) {
+			const uint64_t n = sr.s->n_leaves, n1 = n ? n : 1;
+			uint64_t Ts = 16;
+			while (Ts < 2 * n) Ts <<= 1;
+			sr.mask = (uint32_t)(Ts - 1);
+			bytes += pad256(16 * n1) + pad256(4 * Ts) + (sr.field < 0 && sr.s->masks ? pad256(64 * n1) : 0) + pad256(2048 * (uint64_t)sr.s->ncomp * n1);
+		}
+		void* ps = nullptr;
+		HNS_TRY_RC(scratch.get(bytes, &ps));
+		q = (char*)ps;
+		src_dup = (int*)q;
+		q += pad256(4 * srcs.size());
+		for (Source& sr : srcs) {
+			const uint64_t n = sr.s->n_leaves, n1 = n ? n : 1;
+			sr.origins = (int4*)q, q += pad256(16 * n1);
+			sr.table = (int*)q, q += pad256(4 * ((uint64_t)sr.mask + 1));
+			if (sr.field < 0 && sr.s->masks) sr.masks = (unsigned char*)q, q += pad256(64 * n1);
+			sr.values = (float*)q, q += pad256(2048 * (uint64_t)sr.s->ncomp * n1);
+			sr.o4.assign((size_t)n * 4, 0);
+			for (uint64_t i = 0; i < n; ++i)
+				for (int a = 0; a < 3; ++a) sr.o4[4 * i + a] = sr.s->origins[3 * i + a];
+		}
+	}
 	c.old_origins = (const int4*)og->d_origins, c.old_masks = s->d_masks, c.sdf = d_sdf;
-	c.n_dil = n_dil, c.n_sdf = n_sdf, c.side = side, c.R = R, c.p = p;
+	c.vsrc = vsrc ? vsrc->origins : nullptr, c.vsrc_masks = vsrc ? vsrc->masks : nullptr;
+	c.n_dil = n_dil, c.n_sdf = n_sdf, c.n_vdil = n_vdil, c.side = side, c.R = R, c.p = p;
 	c.mask = (uint32_t)(T - 1), c.cap = cap;
 	HNS_HIP(hipEventRecord(s->rev[0], st));
 	HNS_HIP(hipMemsetAsync(c.table, 0xFF, 8 * T, st));
 	HNS_HIP(hipMemsetAsync(c.count, 0, 256, st));
 	if (n_sdf) HNS_HIP(hipMemcpyAsync(d_sdf, sdf4.data(), 16 * n_sdf, hipMemcpyHostToDevice, st));
-	if (n_dil + n_sdf) {
-		const uint64_t blocks = std::min<uint64_t>((n_dil + n_sdf + 255) / 256, 1u << 20);
+	if (!srcs.empty()) HNS_HIP(hipMemsetAsync(src_dup, 0, 4 * srcs.size(), st));
+	for (size_t i = 0; i < srcs.size(); ++i) {
+		Source& sr = srcs[i];
+		const uint64_t n = sr.s->n_leaves;
+		HNS_HIP(hipMemsetAsync(sr.table, 0xFF, 4 * ((size_t)sr.mask + 1), st));
+		if (!n) continue;
+		HNS_HIP(hipMemcpyAsync(sr.origins, sr.o4.data(), 16 * n, hipMemcpyHostToDevice, st));
+		if (sr.masks) HNS_HIP(hipMemcpyAsync(sr.masks, sr.s->masks, 64 * n, hipMemcpyHostToDevice, st));
+		k_regrid_src_hash<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(sr.origins, (int)n, sr.table, sr.mask, src_dup + i);
+		HNS_HIP(hipGetLastError());
+	}
+	if (n_dil + n_sdf + n_vdil) {
+		const uint64_t blocks = std::min<uint64_t>((n_dil + n_sdf + n_vdil + 255) / 256, 1u << 20);
 		k_regrid_candidates<<<(unsigned)blocks, 256, 0, st>>>(c);
 		HNS_HIP(hipGetLastError());
 		k_regrid_compact<<<(unsigned)(T / 256 ? T / 256 : 1), 256, 0, st>>>(c, compact);
@@ -301,14 +534,24 @@ int regrid(hns_sim* s, int p, const int32_t* sdf_origins, uint64_t n_sdf, const 
 	unsigned long long counts[3] = {0, 0, 0};
 	HNS_HIP(hipMemcpyAsync(counts, c.count, sizeof(counts), hipMemcpyDeviceToHost, st));
 	HNS_HIP(hipStreamSynchronize(st));
-	if (counts[1] || counts[2] > (uint64_t(1) << 22)) return fail(HNS_ERR_TOPOLOGY, "hns_sim_regrid: the new domain exceeds the 2^22-leaf (2^31-voxel) limit of 32-bit voxel indices");
+	if (counts[1] || counts[2] > (uint64_t(1) << 22)) {
+		set_error("%s: the new domain exceeds the 2^22-leaf (2^31-voxel) limit of 32-bit voxel indices", who);
+		return HNS_ERR_TOPOLOGY;
+	}
 	const uint64_t n_new = counts[2];
-	if (n_new == 0) return fail(HNS_ERR_RUNTIME, "hns_sim_regrid: No active voxels in the new domain");  // SOP_HNanoSolver.cpp: "No active voxels"
+	if (n_new == 0) {  // SOP_HNanoSolver.cpp: "No active voxels"
+		set_error("%s: No active voxels in the new domain", who);
+		return HNS_ERR_RUNTIME;
+	}
 
 	// ---- 2. order + grid ----
 	std::vector<int32_t> c4((size_t)n_new * 4);
 	HNS_HIP(hipMemcpyAsync(c4.data(), compact, 16 * n_new, hipMemcpyDeviceToHost, st));
-	HNS_HIP(hipStreamSynchronize(st));
+	HNS_HIP(hipEventRecord(s->rev[5], st));
+	for (Source& sr : srcs)  // issued before the sort, so that they can overlap it
+		if (sr.s->n_leaves)
+			HNS_HIP(hipMemcpyAsync(sr.values, sr.s->values, 2048 * (size_t)sr.s->ncomp * sr.s->n_leaves, hipMemcpyHostToDevice, st));
+	HNS_HIP(hipEventSynchronize(s->rev[5]));
 	std::vector<int32_t> xyz((size_t)n_new * 3);
 	for (uint64_t i = 0; i < n_new; ++i)
 		for (int a = 0; a < 3; ++a) xyz[3 * i + a] = c4[4 * i + a];
@@ -348,8 +591,23 @@ int regrid(hns_sim* s, int p, const int32_t* sdf_origins, uint64_t n_sdf, const 
 		k_regrid_sdf_index<<<(unsigned)((n_sdf + 255) / 256), 256, 0, st>>>(ng.g->dev(), d_sdf, (int)n_sdf, sdf_idx, dup);
 		HNS_HIP(hipGetLastError());
 	}
+	if (!srcs.empty()) {  // new leaf -> source leaf: the velocity's from the mask waves, each float source's by its own leaves
+		void* pi = nullptr;
+		HNS_TRY_RC(scratch.get(pad256(4 * n_new) * srcs.size(), &pi));
+		for (size_t i = 0; i < srcs.size(); ++i) {
+			Source& sr = srcs[i];
+			sr.idx = (int*)((char*)pi + pad256(4 * n_new) * i);
+			if (sr.field < 0) continue;
+			HNS_HIP(hipMemsetAsync(sr.idx, 0xFF, 4 * n_new, st));
+			if (!sr.s->n_leaves) continue;
+			k_regrid_sdf_index<<<(unsigned)((sr.s->n_leaves + 255) / 256), 256, 0, st>>>(ng.g->dev(), sr.origins, (int)sr.s->n_leaves, sr.idx, src_dup + i);
+			HNS_HIP(hipGetLastError());
+		}
+	}
+	const SrcHash vh{vsrc ? vsrc->origins : nullptr, vsrc ? vsrc->table : nullptr, vsrc ? vsrc->mask : 0u};
 	k_regrid_masks<<<(unsigned)((n_new + 3) / 4), 256, 0, st>>>(og->dev(), s->d_masks, (const int4*)ng.g->d_origins, (int)n_new, p, R, n_sdf ? sdf_idx : nullptr,
-	                                                           sdf_masks ? d_sdf_masks : nullptr, (uint64_t*)p_masks, map);
+	                                                           sdf_masks ? d_sdf_masks : nullptr, vh, vsrc ? vsrc->masks : nullptr, (uint64_t*)p_masks, map,
+	                                                           vsrc ? vsrc->idx : nullptr);
 	HNS_HIP(hipGetLastError());
 	HNS_HIP(hipEventRecord(s->rev[3], st));
 
@@ -360,13 +618,27 @@ int regrid(hns_sim* s, int p, const int32_t* sdf_origins, uint64_t n_sdf, const 
 	HNS_TRY_RC(scratch.get(hns_sim_arena_need(s, n_new * 512u), &p_fields));
 	hns_sim_layout(&shell, p_fields, n_new * 512u);
 	const uint32_t sdf_fill = 0x01010101u;  // memset(..., 1, ...) (GridBuilder.hpp:108)
-	CopySet vs{};
-	vs.src[0] = (const float4*)s->vel, vs.dst[0] = (float4*)shell.vel, vs.map[0] = map, vs.fill[0] = 0;
-	HNS_TRY_RC(copy_fields(vs, 1, 3, n_new, st));
-	for (size_t f0 = 0; f0 < s->names.size(); f0 += kCopyFields) {
+	if (vsrc) {
+		AddSet as{};
+		as.a[0] = (const float4*)s->vel, as.map_a[0] = map;
+		as.b[0] = (const float4*)vsrc->values, as.map_b[0] = vsrc->idx;
+		as.dst[0] = (float4*)shell.vel;
+		HNS_TRY_RC(add_fields(as, 1, 3, n_new, st));
+	} else {
+		CopySet vs{};
+		vs.src[0] = (const float4*)s->vel, vs.dst[0] = (float4*)shell.vel, vs.map[0] = map, vs.fill[0] = 0;
+		HNS_TRY_RC(copy_fields(vs, 1, 3, n_new, st));
+	}
+	std::vector<const Source*> src_of(s->names.size(), nullptr);
+	for (const Source& sr : srcs)
+		if (sr.field >= 0) src_of[(size_t)sr.field] = &sr;
+	std::vector<size_t> plain, summed;  // fields carried as they are / with a source added
+	for (size_t f = 0; f < s->names.size(); ++f) (src_of[f] ? summed : plain).push_back(f);
+	for (size_t f0 = 0; f0 < plain.size(); f0 += kCopyFields) {
 		CopySet cs{};
 		int nf = 0;
-		for (size_t f = f0; f < s->names.size() && nf < kCopyFields; ++f, ++nf) {
+		for (size_t j = f0; j < plain.size() && nf < kCopyFields; ++j, ++nf) {
+			const size_t f = plain[j];
 			const bool sdf = (int)f == i_sdf;
 			const bool from_src = sdf && have_src;
 			cs.src[nf] = from_src ? (const float4*)d_sdf_values : (const float4*)s->cur[f];
@@ -376,11 +648,32 @@ int regrid(hns_sim* s, int p, const int32_t* sdf_origins, uint64_t n_sdf, const 
 		}
 		HNS_TRY_RC(copy_fields(cs, nf, 1, n_new, st));
 	}
+	for (size_t f0 = 0; f0 < summed.size(); f0 += kCopyFields) {
+		AddSet as{};
+		int nf = 0;
+		for (size_t j = f0; j < summed.size() && nf < kCopyFields; ++j, ++nf) {
+			const size_t f = summed[j];
+			as.a[nf] = (const float4*)s->cur[f], as.map_a[nf] = map;
+			as.b[nf] = (const float4*)src_of[f]->values, as.map_b[nf] = src_of[f]->idx;
+			as.dst[nf] = (float4*)shell.cur[f];
+		}
+		HNS_TRY_RC(add_fields(as, nf, 1, n_new, st));
+	}
 	HNS_HIP(hipEventRecord(s->rev[4], st));
 	int dup_h = 0;
+	std::vector<int> src_dup_h(srcs.size(), 0);
 	HNS_HIP(hipMemcpyAsync(&dup_h, dup, 4, hipMemcpyDeviceToHost, st));
+	if (!srcs.empty()) HNS_HIP(hipMemcpyAsync(src_dup_h.data(), src_dup, 4 * srcs.size(), hipMemcpyDeviceToHost, st));
 	HNS_HIP(hipStreamSynchronize(st));
-	if (dup_h) return fail(HNS_ERR_TOPOLOGY, "hns_sim_regrid: duplicate SDF leaf origin");
+	if (dup_h) {
+		set_error("%s: duplicate SDF leaf origin", who);
+		return HNS_ERR_TOPOLOGY;
+	}
+	for (size_t i = 0; i < srcs.size(); ++i)
+		if (src_dup_h[i]) {
+			set_error("%s: source %zu ('%s'): duplicate leaf origin", who, i, srcs[i].s->name ? srcs[i].s->name : "(null)");
+			return HNS_ERR_TOPOLOGY;
+		}
 
 	// ---- the sim moves onto the new grid ----
 	size_t fields_bytes = 0, masks_bytes = 0;
@@ -441,18 +734,34 @@ extern "C" int hns_sim_active_masks(hns_sim* s, unsigned char* out, void* stream
 	return HNS_OK;
 }
 
-extern "C" hns_grid* hns_sim_regrid(hns_sim* s, int padding_voxels, const int32_t* sdf_origins, uint64_t n_sdf, const unsigned char* sdf_masks, const float* sdf_values,
-                                    void* stream, int* err) {
+namespace {
+hns_grid* regrid_entry(hns_sim* s, int padding_voxels, const hns_leaf_source* sources, int n_sources, const int32_t* sdf_origins, uint64_t n_sdf,
+                       const unsigned char* sdf_masks, const float* sdf_values, void* stream, int* err, const char* who) {
 	int rc = HNS_OK;
 	hns_grid* g = nullptr;
-	if (!s || !s->grid || padding_voxels < 0 || padding_voxels > 1024 || (n_sdf && (!sdf_origins || !sdf_values)))
-		rc = fail(HNS_ERR_INVALID_ARGUMENT, "hns_sim_regrid: bad arguments");
-	else if (s->cached)
-		rc = fail(HNS_ERR_INVALID_ARGUMENT, "hns_sim_regrid: the sim belongs to a grid's cook cache");
-	else
-		rc = regrid(s, padding_voxels, sdf_origins, n_sdf, sdf_masks, sdf_values, (hipStream_t)stream, &g);
+	if (!s || !s->grid || padding_voxels < 0 || padding_voxels > 1024 || (n_sdf && (!sdf_origins || !sdf_values))) {
+		set_error("%s: bad arguments", who);
+		rc = HNS_ERR_INVALID_ARGUMENT;
+	} else if (s->cached) {
+		set_error("%s: the sim belongs to a grid's cook cache", who);
+		rc = HNS_ERR_INVALID_ARGUMENT;
+	} else {
+		rc = regrid(s, padding_voxels, sources, n_sources, sdf_origins, n_sdf, sdf_masks, sdf_values, (hipStream_t)stream, &g, who);
+	}
 	if (err) *err = rc;
 	return rc == HNS_OK ? g : nullptr;
+}
+}  // namespace
+
+extern "C" hns_grid* hns_sim_regrid(hns_sim* s, int padding_voxels, const int32_t* sdf_origins, uint64_t n_sdf, const unsigned char* sdf_masks, const float* sdf_values,
+                                    void* stream, int* err) {
+	return regrid_entry(s, padding_voxels, nullptr, 0, sdf_origins, n_sdf, sdf_masks, sdf_values, stream, err, "hns_sim_regrid");
+}
+
+// hns_sim_regrid after adding a frame's sources into the fields (include/hns.h): the same four phases, the sources folded into them.
+extern "C" hns_grid* hns_sim_regrid_sourced(hns_sim* s, int padding_voxels, const hns_leaf_source* sources, int n_sources, const int32_t* sdf_origins, uint64_t n_sdf,
+                                            const unsigned char* sdf_masks, const float* sdf_values, void* stream, int* err) {
+	return regrid_entry(s, padding_voxels, sources, n_sources, sdf_origins, n_sdf, sdf_masks, sdf_values, stream, err, "hns_sim_regrid_sourced");
 }
 
 // hipEvent split of the last hns_sim_regrid: {candidates, origins to the host + sort + grid tables, masks, field copy} in milliseconds

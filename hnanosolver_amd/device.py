@@ -199,9 +199,11 @@ class Sim:
         _raise(lib.hns_sim_active_masks(self._ptr, out.ctypes.data, stream))
         return out
 
-    def regrid(self, padding: int, sdf=None, stream: int = 0) -> IndexGridHandle:
+    def regrid(self, padding: int, sdf=None, sources=None, stream: int = 0) -> IndexGridHandle:
         """The domain change between two cooks (``hns_sim_regrid``): dilate the active masks by `padding` voxels, unite with the collision SDF's
         leaves and carry every field into the new leaf set, on the device. sdf = (origins, masks or None, values: 512 floats per leaf) or None.
+        sources = {name: (origins, masks or None, values)}: this frame's sources, added into the fields first (``hns_sim_regrid_sourced``); values
+        of shape (n * 512, 3) make the source the velocity's, anything else holds 512 floats per leaf of a float field.
         Returns the new grid and makes it ``self.grid``; the old handle is untouched and still the caller's."""
         o = m = v = None
         n_sdf = 0
@@ -217,8 +219,28 @@ class Sim:
                 if m.size != n_sdf * 64:
                     raise ValueError(f"sdf masks: need {n_sdf} x 64 bytes, got {m.size}")
         err = C.c_int(0)
-        ptr = lib.hns_sim_regrid(self._ptr, int(padding), None if o is None else o.ctypes.data, n_sdf, None if m is None else m.ctypes.data,
-                                 None if v is None else v.ctypes.data, stream, C.byref(err))
+        sdf_args = (None if o is None else o.ctypes.data, n_sdf, None if m is None else m.ctypes.data, None if v is None else v.ctypes.data)
+        if sources is None:
+            ptr = lib.hns_sim_regrid(self._ptr, int(padding), *sdf_args, stream, C.byref(err))
+        else:
+            arr = (_lib.hns_leaf_source * max(1, len(sources)))()
+            keep = []
+            for i, (name, (so, sm, sv)) in enumerate(sources.items()):
+                so = np.ascontiguousarray(so, dtype=np.int32).reshape(-1, 3)
+                sv = np.ascontiguousarray(sv, dtype=np.float32)
+                nc = 3 if (sv.ndim == 2 and sv.shape[1] == 3) else 1
+                if sv.size != len(so) * 512 * nc:
+                    raise ValueError(f"source {name}: need {len(so)} x 512 x {nc} floats, got {sv.size}")
+                if sm is not None:
+                    sm = np.ascontiguousarray(sm, dtype=np.uint8).reshape(-1)
+                    if sm.size != len(so) * 64:
+                        raise ValueError(f"source {name}: masks need {len(so)} x 64 bytes, got {sm.size}")
+                b = name.encode()
+                keep += [b, so, sm, sv]
+                arr[i].name, arr[i].ncomp, arr[i].n_leaves = b, nc, len(so)
+                arr[i].origins, arr[i].values = so.ctypes.data, sv.ctypes.data
+                arr[i].masks = None if sm is None else sm.ctypes.data
+            ptr = lib.hns_sim_regrid_sourced(self._ptr, int(padding), arr, len(sources), *sdf_args, stream, C.byref(err))
         if not ptr:
             _raise(err.value if err.value < 0 else _lib.HNS_ERR_RUNTIME)
         self.grid = IndexGridHandle(ptr)

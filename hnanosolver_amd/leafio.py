@@ -61,6 +61,30 @@ def dilate_leaf_masks(origins, padding_voxels: int, masks: Optional[np.ndarray] 
     return out, out_m
 
 
+def add_leaves(a, b, ncomp: int = 1):
+    """openvdb::tools::compSum over leaf sets (``hns_add_leaves``): a, b = (origins, masks or None, values: 512 x ncomp floats per leaf) ->
+    (origins, masks, values) on the union of the two leaf sets in OpenVDB leaf order; masks ORed (None = all active), values a + b where a side
+    without the leaf contributes +0.0f."""
+    sides = []
+    for o, m, v in (a, b):
+        o = _o(o)
+        m = None if m is None else np.ascontiguousarray(m, dtype=np.uint8).reshape(len(o), 64)
+        v = np.ascontiguousarray(v, dtype=np.float32)
+        if v.size != len(o) * 512 * ncomp:
+            raise ValueError(f"add_leaves: need {len(o)} x 512 x {ncomp} floats, got {v.size}")
+        sides.append((o, m, v))
+    args = []
+    for o, m, v in sides:
+        args += [o.ctypes.data, len(o), None if m is None else m.ctypes.data, v.ctypes.data]
+    n = C.c_uint64(0)
+    _lib.check(lib.hns_add_leaves(*args, int(ncomp), None, None, None, 0, C.byref(n)))
+    out = np.zeros((n.value, 3), dtype=np.int32)
+    out_m = np.zeros((n.value, 64), dtype=np.uint8)
+    out_v = np.zeros((n.value * 512, ncomp) if ncomp == 3 else (n.value * 512,), dtype=np.float32)
+    _lib.check(lib.hns_add_leaves(*args, int(ncomp), out.ctypes.data, out_m.ctypes.data, out_v.ctypes.data, n.value, C.byref(n)))
+    return out, out_m, out_v
+
+
 def union_leaves(a, b) -> np.ndarray:
     a, b = _o(a), _o(b)
     n = C.c_uint64(0)

@@ -168,6 +168,13 @@ int hns_dilate_leaf_masks(const int32_t* origins, uint64_t n, const unsigned cha
                           unsigned char* out_masks, uint64_t capacity, uint64_t* n_out);
 /* topologyUnion of two leaf sets, in OpenVDB leaf order, duplicates removed. */
 int hns_union_leaves(const int32_t* a, uint64_t na, const int32_t* b, uint64_t nb, int32_t* out_origins, uint64_t capacity, uint64_t* n_out);
+/* openvdb::tools::compSum(a, b) over leaf sets (SOP_HNanoSolver.cpp:159-179): the union of the two leaf sets in OpenVDB leaf order (as
+ * hns_union_leaves), masks ORed (NULL = all active), values fl(a + b) per component, where a side without the leaf contributes +0.0f -- so a -0.0f
+ * on one side alone becomes +0.0f (compSum applies the sum to every voxel of both trees). ncomp 1 or 3. out_* may be NULL to query *n_out.
+ * Unaligned or duplicated origins in either input: HNS_ERR_TOPOLOGY. */
+int hns_add_leaves(const int32_t* a_origins, uint64_t na, const unsigned char* a_masks, const float* a_values, const int32_t* b_origins, uint64_t nb,
+                   const unsigned char* b_masks, const float* b_values, int ncomp, int32_t* out_origins, unsigned char* out_masks, float* out_values,
+                   uint64_t capacity, uint64_t* n_out);
 
 /* ------------------------------------------------------------------------------------------------------------ */
 /* Drop-in operators (host pointers in, results in place, synchronous)                                           */
@@ -285,6 +292,34 @@ hns_grid* hns_sim_regrid(hns_sim*, int padding_voxels, const int32_t* sdf_origin
                          const float* sdf_values, void* stream, int* err);
 /* hipEvent split of the sim's last regrid, milliseconds: {candidate leaves, origins to the host + sort + grid tables, masks, field copy}. */
 int hns_sim_regrid_times(hns_sim*, float* ms4);
+/* One source of hns_sim_regrid_sourced: the leaves a frame's emitter adds into a field (the SOP's second input). */
+typedef struct {
+	const char* name;            /* a float field of the sim; with ncomp 3: the velocity (any name that is not a float field's) */
+	int ncomp;                   /* 1 or 3 */
+	const int32_t* origins;      /* n_leaves x 3, 8-aligned, no duplicates, any order */
+	uint64_t n_leaves;           /* at most 2^22 */
+	const unsigned char* masks;  /* n_leaves x 64 bytes or NULL = all active; they enter the domain only for the velocity (as in the reference) */
+	const float* values;         /* n_leaves x 512 x ncomp floats, host memory */
+} hns_leaf_source;
+/* hns_sim_regrid after adding this frame's sources into the sim's fields (SOP_HNanoSolver.cpp:159-179, then :186-199). The result is
+ * byte-identical to this host chain:
+ *   1. hns_sim_download and hns_sim_active_masks;
+ *   2. per source, hns_add_leaves(sim field, source); for the velocity the masks are added too;
+ *   3. hns_dilate_leaf_masks of the summed velocity's leaves and masks;
+ *   4. the union with the SDF leaves and their masks, as hns_sim_regrid does;
+ *   5. hns_gather_leaves of every field onto the new domain, fill 0 (HNS_FILL_SDF for collision_sdf).
+ * So: a velocity source leaf outside the current domain is a dilation seed like an old leaf; a float source leaf outside the final domain is
+ * dropped, as in the reference (the gather only visits domain leaves); a sourced field is a sum on every leaf (a -0.0f there becomes +0.0f, also
+ * on leaves the source lacks); fields without a source are carried exactly as hns_sim_regrid carries them. With n_sources 0 this IS
+ * hns_sim_regrid. Only the source leaves cross PCIe, never the sim's fields.
+ * The reference pairs sources with feedback grids by POSITION (i-th float source into the i-th float feedback grid); a shim passes
+ * feedback_float_grids[i]->getName() as the name of source i.
+ * Refused, with the sim and its grid left exactly as they were (besides hns_sim_regrid's refusals): a name the sim lacks, collision_sdf as a
+ * source (the SDF comes from the collision input, never from the feedback), a second velocity source or two sources of one name, ncomp other
+ * than 1 or 3 or ncomp 3 under a float field's name, values (or origins) NULL with n_leaves > 0, more than 2^22 leaves (HNS_ERR_INVALID_ARGUMENT);
+ * unaligned or duplicated origins in a source (HNS_ERR_TOPOLOGY). hns_sim_regrid_times counts the source work in the phase it runs in. */
+hns_grid* hns_sim_regrid_sourced(hns_sim*, int padding_voxels, const hns_leaf_source* sources, int n_sources, const int32_t* sdf_origins, uint64_t n_sdf,
+                                 const unsigned char* sdf_masks, const float* sdf_values, void* stream, int* err);
 
 /* ------------------------------------------------------------------------------------------------------------ */
 /* Kernel-level entry points on caller-owned DEVICE memory (asynchronous on `stream`).                           */
