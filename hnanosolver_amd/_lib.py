@@ -49,6 +49,10 @@ class hns_leaf_source(C.Structure):
     _fields_ = [("name", C.c_char_p), ("ncomp", C.c_int), ("origins", C.c_void_p), ("n_leaves", C.c_uint64), ("masks", C.c_void_p), ("values", C.c_void_p)]
 
 
+class hns_activity_field(C.Structure):
+    _fields_ = [("name", C.c_char_p), ("ncomp", C.c_int), ("tolerance", C.c_float)]
+
+
 class hns_combustion_params(C.Structure):
     _fields_ = [(n, C.c_float) for n in ("expansionRate", "temperatureRelease", "buoyancyStrength", "ambientTemp", "vorticityScale", "factorScale")]
 
@@ -88,6 +92,7 @@ SIGNATURES = {
     "hns_dilate_leaf_masks": (_i, [_vp, _u64, _vp, _i, _vp, _vp, _u64, C.POINTER(C.c_uint64)]),
     "hns_union_leaves": (_i, [_vp, _u64, _vp, _u64, _vp, _u64, C.POINTER(C.c_uint64)]),
     "hns_add_leaves": (_i, [_vp, _u64, _vp, _vp, _vp, _u64, _vp, _vp, _i, _vp, _vp, _vp, _u64, C.POINTER(C.c_uint64)]),
+    "hns_deactivate_leaf_masks": (_i, [_u64, _vp, C.POINTER(hns_activity_field), C.POINTER(C.c_void_p), _i, _vp, C.POINTER(C.c_uint64)]),
     "hns_compute_sim": (_i, [_vp, C.POINTER(hns_field), _i, _i, _f, _f, C.POINTER(hns_combustion_params), _i, _vp]),
     "hns_compute_sim_resident": (_i, [_vp, C.POINTER(hns_field), _i, C.c_char_p, C.POINTER(C.c_int), _i, _f, _f, C.POINTER(hns_combustion_params), _i, _vp]),
     "hns_advect_index_grid": (_i, [_vp, C.POINTER(hns_field), _i, _f, _f, _vp]),
@@ -114,6 +119,7 @@ SIGNATURES = {
     "hns_sim_regrid": (_vp, [_vp, _i, _vp, _u64, _vp, _vp, _vp, _ip]),
     "hns_sim_regrid_times": (_i, [_vp, C.POINTER(C.c_float)]),
     "hns_sim_regrid_sourced": (_vp, [_vp, _i, C.POINTER(hns_leaf_source), _i, _vp, _u64, _vp, _vp, _vp, _ip]),
+    "hns_sim_deactivate": (_i, [_vp, C.POINTER(hns_activity_field), _i, C.POINTER(C.c_uint64), _vp]),
     "hns_dev_advect_vector": (_i, [_vp, _fp, _fp, _fp, _i, _f, _f, _vp]),
     "hns_dev_advect_scalar": (_i, [_vp, _fp, _fp, _fp, _fp, _i, _f, _f, _vp]),
     "hns_dev_advect_scalars": (_i, [_vp, _fp, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _i, _fp, _i, _f, _f, _vp]),

@@ -176,6 +176,7 @@ extern "C" void hns_sim_destroy(hns_sim* s) {
 	if (s->xfer) (void)hipStreamDestroy(s->xfer);
 	if (s->h_dig) (void)hipHostFree(s->h_dig);
 	if (s->d_masks) arena_put(Arena{s->d_masks, s->masks_bytes, s->device});
+	if (s->d_act) arena_put(Arena{s->d_act, s->act_bytes, s->device});
 	arena_put(Arena{s->arena, s->arena_bytes, s->device});
 	delete s;
 }

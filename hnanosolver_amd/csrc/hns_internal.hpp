@@ -186,6 +186,9 @@ struct hns_sim {
 	size_t masks_bytes = 0;
 	hipEvent_t rev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // phase boundaries of the last hns_sim_regrid (hns_sim_regrid_times: 0-4); 5: the origins' read-back
 	bool regrid_timed = false;
+	// hns_sim_deactivate's device table (its counts, then one row per listed field), made on first use from the arena pool, written by a kernel
+	void* d_act = nullptr;
+	size_t act_bytes = 0;
 	int device = -1;
 	int find(const char* name) const {
 		for (size_t i = 0; i < names.size(); ++i)
@@ -194,6 +197,9 @@ struct hns_sim {
 	}
 };
 
+// A field list of hns_sim_deactivate (s: its sim) or hns_deactivate_leaf_masks (s null), checked (hns_leafio.cpp): HNS_OK, or HNS_ERR_INVALID_ARGUMENT
+// with the message under `who`. field_of (or null) receives each entry's float field index in s, -1 for the velocity.
+namespace hns { int check_activity_fields(const hns_sim* s, const hns_activity_field* fields, int n_fields, const char* who, std::vector<int>* field_of); }
 
 // the sim's buffers over one arena (hns_api.hip): bytes an arena needs for n voxels, and the slices of `arena` for them (sets n, every buffer pointer, d_dig, p_result)
 size_t hns_sim_arena_need(const hns_sim* s, uint64_t n);

@@ -10,6 +10,7 @@
 // with zeros (:125-129,147-151); tile values of the sources are ignored (only leaves are probed, :105,122,144); output grids
 // receive all 512 values of every domain leaf (:198-211).
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <unordered_map>
 #include <unordered_set>
@@ -84,6 +85,60 @@ void hns::sort_leaf_origins(int32_t* xyz, size_t n) {
 	}
 	std::sort(v.begin(), v.end(), [](const Item& a, const Item& b) { return a.tile != b.tile ? a.tile < b.tile : a.node < b.node; });
 	for (size_t i = 0; i < n; ++i) xyz[3 * i] = v[i].x, xyz[3 * i + 1] = v[i].y, xyz[3 * i + 2] = v[i].z;
+}
+
+int hns::check_activity_fields(const hns_sim* s, const hns_activity_field* fields, int n_fields, const char* who, std::vector<int>* field_of) {
+	if (n_fields < 1 || !fields) {
+		set_error("%s: bad field list (%d fields%s)", who, n_fields, fields ? "" : ", NULL list");
+		return HNS_ERR_INVALID_ARGUMENT;
+	}
+	if (field_of) field_of->assign((size_t)n_fields, -1);
+	bool velocity = false;
+	for (int i = 0; i < n_fields; ++i) {
+		const hns_activity_field& q = fields[i];
+		const char* nm = q.name ? q.name : "(null)";
+		if (q.ncomp != 1 && q.ncomp != 3) {
+			set_error("%s: field %d ('%s'): ncomp %d (1 or 3)", who, i, nm, q.ncomp);
+			return HNS_ERR_INVALID_ARGUMENT;
+		}
+		if (q.name && !strcmp(q.name, "collision_sdf")) {
+			set_error("%s: field %d: 'collision_sdf' cannot be deactivated (its topology comes from the collision input)", who, i);
+			return HNS_ERR_INVALID_ARGUMENT;
+		}
+		if (s) {
+			const int f = q.name ? s->find(q.name) : -1;
+			if (q.ncomp == 1 && f < 0) {
+				set_error("%s: field %d: the sim has no float field '%s'", who, i, nm);
+				return HNS_ERR_INVALID_ARGUMENT;
+			}
+			if (q.ncomp == 3 && f >= 0) {
+				set_error("%s: field %d: ncomp 3 under the float field name '%s'", who, i, nm);
+				return HNS_ERR_INVALID_ARGUMENT;
+			}
+			if (field_of) (*field_of)[(size_t)i] = q.ncomp == 1 ? f : -1;
+		} else if (q.ncomp == 1 && !q.name) {
+			set_error("%s: field %d: a float field needs a name", who, i);
+			return HNS_ERR_INVALID_ARGUMENT;
+		}
+		if (q.ncomp == 3) {
+			if (velocity) {
+				set_error("%s: field %d: a second velocity entry", who, i);
+				return HNS_ERR_INVALID_ARGUMENT;
+			}
+			velocity = true;
+		} else {
+			for (int j = 0; j < i; ++j)
+				if (fields[j].ncomp == 1 && fields[j].name && !strcmp(fields[j].name, q.name)) {
+					set_error("%s: field %d: a second entry for '%s'", who, i, nm);
+					return HNS_ERR_INVALID_ARGUMENT;
+				}
+		}
+		if (!(q.tolerance >= 0.0f)) {
+			set_error("%s: field %d ('%s'): tolerance %g (>= 0, not NaN)", who, i, nm, (double)q.tolerance);
+			return HNS_ERR_INVALID_ARGUMENT;
+		}
+	}
+	return HNS_OK;
 }
 
 extern "C" {
@@ -277,6 +332,41 @@ int hns_union_leaves(const int32_t* a, uint64_t na, const int32_t* b, uint64_t n
 	for (uint64_t i = 0; i < nb; ++i) have.insert(Key{b[3 * i], b[3 * i + 1], b[3 * i + 2]});
 	std::vector<Key> keys(have.begin(), have.end());
 	return emit_sorted(keys, out_origins, capacity, n_out, "hns_union_leaves");
+}
+
+// hns_sim_deactivate on the host, voxel by voxel: the brute force the device's ballot kernel is checked against.
+int hns_deactivate_leaf_masks(uint64_t n_leaves, const unsigned char* masks_in, const hns_activity_field* fields, const float* const* values, int n_fields,
+                              unsigned char* masks_out, uint64_t* counts) {
+	const char* who = "hns_deactivate_leaf_masks";
+	if (int rc = check_activity_fields(nullptr, fields, n_fields, who, nullptr)) return rc;
+	if (n_leaves && (!masks_out || !values)) return fail(HNS_ERR_INVALID_ARGUMENT, "hns_deactivate_leaf_masks: masks_out or values NULL");
+	for (int i = 0; i < n_fields && n_leaves; ++i)
+		if (!values[i]) {
+			set_error("%s: field %d: values NULL", who, i);
+			return HNS_ERR_INVALID_ARGUMENT;
+		}
+	uint64_t voxels = 0, leaves = 0;
+	for (uint64_t l = 0; l < n_leaves; ++l) {
+		uint64_t in_leaf = 0;
+		for (int w = 0; w < 64; ++w) {  // mask byte w = x*8+y holds voxels 8w .. 8w+7 (bit z)
+			const unsigned char old = masks_in ? masks_in[64 * l + w] : 0xFF;
+			unsigned char keep = 0;
+			for (int z = 0; z < 8; ++z) {
+				if (!(old >> z & 1)) continue;
+				const uint64_t v = 512 * l + 8 * (uint64_t)w + (uint64_t)z;
+				bool quiet = true;
+				for (int i = 0; i < n_fields && quiet; ++i)
+					for (int c = 0; c < fields[i].ncomp && quiet; ++c) quiet = std::fabs(values[i][v * (uint64_t)fields[i].ncomp + (uint64_t)c]) <= fields[i].tolerance;
+				if (!quiet) keep |= (unsigned char)(1u << z);
+			}
+			masks_out[64 * l + w] = keep;
+			in_leaf += (uint64_t)__builtin_popcount(keep);
+		}
+		voxels += in_leaf;
+		leaves += in_leaf != 0;
+	}
+	if (counts) counts[0] = voxels, counts[1] = leaves;
+	return HNS_OK;
 }
 
 }  // extern "C"

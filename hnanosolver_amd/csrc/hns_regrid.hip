@@ -19,6 +19,9 @@
 //   4. fields      velocity and every float field, 16 bytes per load and store, from the old leaf or the fill (zeros; bytes 0x01 for collision_sdf),
 //                  into a fresh arena from the pool; a sourced field gets (old or +0) + (source or +0) instead. The old arena goes back to the pool
 //
+// hns_sim_deactivate, at the end of a frame, clears the mask bits of voxels whose listed fields are all within tolerance (the reference's commented-out
+// deactivate, GridBuilder.hpp:213-214), so that the next regrid can drop leaves no active voxel reaches: one wave per leaf, a ballot per 64 voxels.
+//
 // Everything that decides a result is order-free: hash slots hold the smallest thing that identifies a candidate (its thread id), the compacted
 // order is discarded by the sort, the mask OR is commutative and a source hash is only ever asked for an origin it holds once. Two runs give the
 // same bytes.
@@ -28,6 +31,12 @@
 
 #include "hns_device.hpp"
 #include "hns_dilate.hpp"
+
+// raw buffer loads through the LLVM intrinsics (hns_sim_deactivate's kernel; as in hns_advect.hip)
+typedef int v4i_act __attribute__((ext_vector_type(4)));
+typedef float v3f_act __attribute__((ext_vector_type(3)));
+__device__ float hns_act_load_f32(v4i_act rsrc, int voffset, int soffset, int aux) __asm("llvm.amdgcn.raw.buffer.load.f32");
+__device__ v3f_act hns_act_load_v3f32(v4i_act rsrc, int voffset, int soffset, int aux) __asm("llvm.amdgcn.raw.buffer.load.v3f32");
 
 #define HNS_TRY_RC(call)           \
 	do {                            \
@@ -698,6 +707,88 @@ int regrid(hns_sim* s, int p, const hns_leaf_source* src, int n_src, const int32
 	return HNS_OK;
 }
 
+// ---- hns_sim_deactivate: the end of a frame, one wave per leaf ----
+// Mask byte x*8+y, bit z is voxel x*64+y*8+z, so little-endian word k of a leaf's mask holds voxels 64k .. 64k+63: in round k lane L tests voxel
+// 64k+L and the wave's ballot is the new word. `pend[k]` (wave-uniform) holds the voxels of word k that are active and within every tolerance so
+// far; a round whose pend is 0 loads nothing. Per round a float field is 256 contiguous bytes, the velocity 768 (Vec3f AoS).
+
+struct ActField {  // one row of the device table
+	const float* p;
+	float tol;
+	int ncomp;
+};
+constexpr int kActRows = 16;  // rows per table-writing launch (their kernel argument)
+struct ActRows {
+	ActField f[kActRows];
+};
+
+// Writes rows of the table from the kernel argument (no host staging, so the call stays asynchronous); zeroes the packed count when asked.
+__global__ __launch_bounds__(64) void k_deactivate_table(ActRows rows, int n, ActField* dst, unsigned long long* count) {
+	if ((int)threadIdx.x < n) dst[threadIdx.x] = rows.f[threadIdx.x];
+	if (count && threadIdx.x == 0) *count = 0;
+}
+
+// Raw buffer loads over one leaf of a field (as in hns_advect.hip): a round to skip gets an offset past the descriptor's end, for which the hardware
+// returns 0 without touching memory. So the eight rounds' loads are issued back to back with no branch (a branch per round makes the compiler wait
+// for each load before the next).
+constexpr int kActSkip = 0x40000000;  // a byte offset past any leaf
+
+__device__ __forceinline__ v4i_act leaf_rsrc(const float* p, unsigned bytes) {
+	const unsigned long long a = (unsigned long long)p;
+	v4i_act r;
+	r.x = __builtin_amdgcn_readfirstlane((int)(unsigned)a);
+	r.y = __builtin_amdgcn_readfirstlane((int)((unsigned)(a >> 32) & 0xffffu));  // stride 0: raw buffer
+	r.z = (int)bytes;                                                            // num_records in bytes
+	r.w = 0x00020000;                                                            // 32-bit float data format
+	return r;
+}
+
+__device__ __forceinline__ uint64_t readlane64(uint64_t v, int lane) {
+	const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, lane), hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), lane);
+	return (uint64_t)hi << 32 | lo;
+}
+
+// masks_in null: every voxel active (it may equal masks_out). count: += active voxels | (leaves holding one) << 40, one atomic per such wave.
+__global__ __launch_bounds__(256) void k_deactivate(const ActField* __restrict__ tab, int n_tab, const uint64_t* masks_in, uint64_t* masks_out, uint64_t n_leaves,
+                                                    unsigned long long* count) {
+	const uint64_t leaf = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+	if (leaf >= n_leaves) return;  // (whole waves)
+	const int lane = (int)(threadIdx.x & 63);
+	const uint64_t word = masks_in && lane < 8 ? masks_in[8 * leaf + (uint64_t)lane] : ~0ull;
+	uint64_t old[8], pend[8];
+#pragma unroll
+	for (int k = 0; k < 8; ++k) pend[k] = old[k] = readlane64(word, k);
+	for (int f = 0; f < n_tab; ++f) {
+		const ActField e = tab[f];
+		if (e.ncomp == 1) {
+			const v4i_act r = leaf_rsrc(e.p + 512 * leaf, 2048u);
+			float x[8];
+#pragma unroll
+			for (int k = 0; k < 8; ++k) x[k] = hns_act_load_f32(r, pend[k] ? 4 * (64 * k + lane) : kActSkip, 0, 0);
+#pragma unroll
+			for (int k = 0; k < 8; ++k) pend[k] &= __ballot(fabsf(x[k]) <= e.tol);
+		} else {
+			const v4i_act r = leaf_rsrc(e.p + 1536 * leaf, 6144u);
+			v3f_act x[8];
+#pragma unroll
+			for (int k = 0; k < 8; ++k) x[k] = hns_act_load_v3f32(r, pend[k] ? 12 * (64 * k + lane) : kActSkip, 0, 0);
+#pragma unroll
+			for (int k = 0; k < 8; ++k) pend[k] &= __ballot(fabsf(x[k].x) <= e.tol && fabsf(x[k].y) <= e.tol && fabsf(x[k].z) <= e.tol);
+		}
+		if (!(pend[0] | pend[1] | pend[2] | pend[3] | pend[4] | pend[5] | pend[6] | pend[7])) break;  // every active voxel is kept already
+	}
+	uint64_t mine = 0;
+	unsigned pop = 0;
+#pragma unroll
+	for (int k = 0; k < 8; ++k) {
+		const uint64_t w = old[k] & ~pend[k];
+		pop += (unsigned)__popcll(w);
+		if (lane == k) mine = w;
+	}
+	if (lane < 8) masks_out[8 * leaf + (uint64_t)lane] = mine;
+	if (count && lane == 0 && pop) atomicAdd(count, (unsigned long long)pop | 1ull << 40);
+}
+
 }  // namespace
 }  // namespace hns
 
@@ -769,5 +860,64 @@ extern "C" int hns_sim_regrid_times(hns_sim* s, float* ms4) {
 	if (!s || !ms4) return fail(HNS_ERR_INVALID_ARGUMENT, "hns_sim_regrid_times: null argument");
 	if (!s->regrid_timed) return fail(HNS_ERR_RUNTIME, "hns_sim_regrid_times: no regrid has completed on this sim");
 	for (int i = 0; i < 4; ++i) HNS_HIP(hipEventElapsedTime(&ms4[i], s->rev[i], s->rev[i + 1]));
+	return HNS_OK;
+}
+
+// The end of a frame (include/hns.h): clears the active bits of voxels whose listed fields are all within tolerance. Fields are never touched.
+extern "C" int hns_sim_deactivate(hns_sim* s, const hns_activity_field* fields, int n_fields, uint64_t* counts, void* stream) {
+	const char* who = "hns_sim_deactivate";
+	if (!s || !s->grid) return fail(HNS_ERR_INVALID_ARGUMENT, "hns_sim_deactivate: null sim");
+	if (s->cached) return fail(HNS_ERR_INVALID_ARGUMENT, "hns_sim_deactivate: the sim belongs to a grid's cook cache");
+	std::vector<int> field_of;
+	HNS_TRY_RC(check_activity_fields(s, fields, n_fields, who, &field_of));
+	const uint64_t n_leaves = s->n / 512u;
+	if (!n_leaves) {
+		if (counts) counts[0] = counts[1] = 0;
+		return HNS_OK;
+	}
+	CurrentDevice on(s->device);
+	const hipStream_t st = (hipStream_t)stream;
+	if (!s->d_act) {  // the packed count, then a row per field the sim could list (its float fields and the velocity)
+		void* p = nullptr;
+		size_t got = 0;
+		HNS_TRY_RC(hns_arena_get(16 + sizeof(ActField) * (s->names.size() + 1), s->device, &p, &got));
+		s->d_act = p, s->act_bytes = got;
+	}
+	unsigned long long* d_count = (unsigned long long*)s->d_act;
+	ActField* d_tab = (ActField*)((char*)s->d_act + 16);
+	unsigned char* masks = s->d_masks;
+	size_t masks_bytes = s->masks_bytes;
+	if (!masks) {  // all active until now: the kernel reads no masks and writes the first ones
+		void* p = nullptr;
+		HNS_TRY_RC(hns_arena_get(64 * n_leaves, s->device, &p, &masks_bytes));
+		masks = (unsigned char*)p;
+	}
+	int rc = HNS_OK;
+	for (int i0 = 0; i0 < n_fields && rc == HNS_OK; i0 += kActRows) {
+		ActRows rows{};
+		const int n = std::min(kActRows, n_fields - i0);
+		for (int j = 0; j < n; ++j) {
+			const int f = field_of[(size_t)(i0 + j)];
+			rows.f[j] = ActField{f < 0 ? s->vel : s->cur[(size_t)f], fields[i0 + j].tolerance, fields[i0 + j].ncomp};
+		}
+		k_deactivate_table<<<1, 64, 0, st>>>(rows, n, d_tab + i0, counts && i0 == 0 ? d_count : nullptr);
+		if (hipGetLastError() != hipSuccess) rc = fail(HNS_ERR_HIP, "hns_sim_deactivate: table launch failed");
+	}
+	if (rc == HNS_OK) {
+		k_deactivate<<<(unsigned)((n_leaves + 3) / 4), 256, 0, st>>>(d_tab, n_fields, (const uint64_t*)s->d_masks, (uint64_t*)masks, n_leaves,
+		                                                            counts ? d_count : nullptr);
+		if (hipGetLastError() != hipSuccess) rc = fail(HNS_ERR_HIP, "hns_sim_deactivate: kernel launch failed");
+	}
+	if (rc != HNS_OK) {  // nothing ran: the masks are as they were
+		if (masks != s->d_masks) hns_arena_put(masks, masks_bytes, s->device);
+		return rc;
+	}
+	s->d_masks = masks, s->masks_bytes = masks_bytes;
+	if (counts) {
+		unsigned long long packed = 0;
+		HNS_HIP(hipMemcpyAsync(&packed, d_count, sizeof(packed), hipMemcpyDeviceToHost, st));
+		HNS_HIP(hipStreamSynchronize(st));
+		counts[0] = packed & ((1ull << 40) - 1), counts[1] = packed >> 40;
+	}
 	return HNS_OK;
 }

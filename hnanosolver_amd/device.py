@@ -11,7 +11,7 @@ from typing import List, Optional, Sequence
 
 import numpy as np
 
-from . import _lib
+from . import _lib, leafio
 from ._lib import hns_combustion_params, hns_field, lib
 from .api import CombustionParams, IndexGridHandle, _raise, create_grid_from_leaves  # noqa: F401
 
@@ -245,6 +245,16 @@ class Sim:
             _raise(err.value if err.value < 0 else _lib.HNS_ERR_RUNTIME)
         self.grid = IndexGridHandle(ptr)
         return self.grid
+
+    def deactivate(self, tolerances: dict, velocity: Optional[float] = None, counts: bool = False, stream: int = 0):
+        """The end of a frame (``hns_sim_deactivate``): clear the active bit of every voxel whose listed components are all within tolerance
+        (|x| <= tol; NaN never is). tolerances = {float field name: tolerance}; velocity = the velocity's tolerance, None = not tested. Field values
+        are untouched; the next regrid drops the leaves no active voxel reaches, with all their values. Asynchronous on `stream`, unless counts:
+        then synchronous, returning (active voxels, leaves holding one)."""
+        arr, n = leafio.activity_fields(tolerances, velocity)
+        out = (C.c_uint64 * 2)()
+        _raise(lib.hns_sim_deactivate(self._ptr, arr, n, out if counts else None, stream))
+        return (int(out[0]), int(out[1])) if counts else None
 
     def regrid_times(self):
         """hipEvent split of the last regrid in ms: {candidates, host (origins, sort, grid tables), masks, fields}"""

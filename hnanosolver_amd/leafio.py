@@ -85,6 +85,45 @@ def add_leaves(a, b, ncomp: int = 1):
     return out, out_m, out_v
 
 
+def activity_fields(tolerances: dict, velocity_tolerance=None):
+    """-> ctypes array of hns_activity_field: {float field name: tolerance} plus, unless velocity_tolerance is None, the velocity (name NULL)"""
+    entries = [(k.encode(), 1, float(t)) for k, t in tolerances.items()]
+    if velocity_tolerance is not None:
+        entries.append((None, 3, float(velocity_tolerance)))
+    arr = (_lib.hns_activity_field * max(1, len(entries)))()
+    for i, (name, nc, tol) in enumerate(entries):
+        arr[i].name, arr[i].ncomp, arr[i].tolerance = name, nc, tol
+    return arr, len(entries)
+
+
+def deactivate_masks(masks, fields: dict, velocity=None):
+    """The host mirror of ``Sim.deactivate`` (``hns_deactivate_leaf_masks``): masks (n x 64 uint8, or None = all active), fields = {name: (values:
+    512 floats per leaf, tolerance)}, velocity = (values: (n * 512, 3), tolerance) or None -> (masks, (active voxels, leaves holding one)). A voxel
+    stays active iff it was active and some listed component has |x| > tolerance (NaN counts as above)."""
+    vals, tols = [], {}
+    for name, (v, t) in fields.items():
+        vals.append(np.ascontiguousarray(v, dtype=np.float32).reshape(-1))
+        tols[name] = t
+    if velocity is not None:
+        vals.append(np.ascontiguousarray(velocity[0], dtype=np.float32).reshape(-1))
+    ncomps = [1] * len(fields) + ([3] if velocity is not None else [])
+    if masks is not None:
+        m = np.ascontiguousarray(masks, dtype=np.uint8).reshape(-1, 64)
+        n = len(m)
+    else:
+        m = None
+        n = vals[0].size // (512 * ncomps[0]) if vals else 0
+    for v, nc in zip(vals, ncomps):
+        if v.size != n * 512 * nc:
+            raise ValueError(f"deactivate_masks: need {n} x 512 x {nc} floats, got {v.size}")
+    arr, n_fields = activity_fields(tols, None if velocity is None else velocity[1])
+    ptrs = (C.c_void_p * max(1, len(vals)))(*[v.ctypes.data for v in vals])
+    out = np.zeros((n, 64), dtype=np.uint8)
+    counts = (C.c_uint64 * 2)()
+    _lib.check(lib.hns_deactivate_leaf_masks(n, None if m is None else m.ctypes.data, arr, ptrs, n_fields, out.ctypes.data, counts))
+    return out, (int(counts[0]), int(counts[1]))
+
+
 def union_leaves(a, b) -> np.ndarray:
     a, b = _o(a), _o(b)
     n = C.c_uint64(0)

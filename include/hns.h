@@ -175,6 +175,19 @@ int hns_union_leaves(const int32_t* a, uint64_t na, const int32_t* b, uint64_t n
 int hns_add_leaves(const int32_t* a_origins, uint64_t na, const unsigned char* a_masks, const float* a_values, const int32_t* b_origins, uint64_t nb,
                    const unsigned char* b_masks, const float* b_values, int ncomp, int32_t* out_origins, unsigned char* out_masks, float* out_values,
                    uint64_t capacity, uint64_t* n_out);
+/* One field whose values decide which voxels stay active (hns_sim_deactivate, hns_deactivate_leaf_masks). */
+typedef struct {
+	const char* name; /* a float field of the sim; with ncomp 3: the velocity (any name that is not a float field's) */
+	int ncomp;        /* 1 or 3 */
+	float tolerance;  /* >= 0, not NaN; +inf allowed */
+} hns_activity_field;
+/* Host mirror of hns_sim_deactivate over n_leaves leaves in the sim's (grid) order: masks_in n_leaves x 64 bytes or NULL = all active; values[i]
+ * = 512 * fields[i].ncomp floats per leaf (Vec3f AoS for ncomp 3); masks_out n_leaves x 64 bytes (may be masks_in). A voxel stays active iff it
+ * is active in masks_in and some component of some listed field has |x| > tolerance (NaN counts as above). counts (or NULL): {active voxels,
+ * leaves holding one} of masks_out. Refusals as hns_sim_deactivate's that need no sim (HNS_ERR_INVALID_ARGUMENT, masks_out untouched); a float
+ * entry needs a name, and two entries of one name are refused. */
+int hns_deactivate_leaf_masks(uint64_t n_leaves, const unsigned char* masks_in, const hns_activity_field* fields, const float* const* values, int n_fields,
+                              unsigned char* masks_out, uint64_t* counts);
 
 /* ------------------------------------------------------------------------------------------------------------ */
 /* Drop-in operators (host pointers in, results in place, synchronous)                                           */
@@ -267,7 +280,9 @@ float* hns_sim_pressure_ptr(hns_sim*);
 
 /* Each cook the reference rebuilds the domain (SOP_HNanoSolver.cpp:186-199): the velocity's active topology, dilateVoxels(padding,
  * NN_FACE_EDGE_VERTEX), united with the collision SDF's topology; padding has a hard minimum of 1 (:32-36) and the output grids keep the
- * dilated topology (GridBuilder.hpp:198-214 clones the domain's masks, prune commented out), so the domain grows by `padding` voxels a frame.
+ * dilated topology (GridBuilder.hpp:198-214 clones the domain's masks; the deactivate + pruneInactive after it, :213-214, is commented out), so
+ * the domain grows by `padding` voxels a frame. hns_sim_deactivate is that step, turned on: it clears the mask bits of quiet voxels, so the
+ * next regrid can drop the leaves no active voxel reaches.
  *
  * Active masks are sim state: leaf_count x 64 bytes, byte x*8+y, bit z (the hns_dilate_leaves layout). A new sim has every voxel active (NULL masks);
  * hns_sim_set_active_masks(sim, NULL, ...) returns to that. hns_sim_active_masks is synchronous. */
@@ -320,6 +335,26 @@ typedef struct {
  * unaligned or duplicated origins in a source (HNS_ERR_TOPOLOGY). hns_sim_regrid_times counts the source work in the phase it runs in. */
 hns_grid* hns_sim_regrid_sourced(hns_sim*, int padding_voxels, const hns_leaf_source* sources, int n_sources, const int32_t* sdf_origins, uint64_t n_sdf,
                                  const unsigned char* sdf_masks, const float* sdf_values, void* stream, int* err);
+/* The end of a frame, after its substeps and before the next regrid: clears the active-mask bit of every voxel whose listed fields are all
+ * quiet. The reference has this step commented out (GridBuilder.hpp:213-214: deactivate(grid, 0, 0) + pruneInactive on each output grid).
+ *   A voxel STAYS ACTIVE iff it is active now and at least one listed component is not within tolerance; x is within iff |x| <= tolerance.
+ *   The velocity's three components are tested one by one. So bits are only ever cleared, field values are never touched, -0.0f is within any
+ *   tolerance, NaN is never within (a blown-up voxel stays active), and +inf is a legal tolerance.
+ * The velocity alone at tolerance 0 clears exactly the voxels whose three components are all +-0: as we read OpenVDB's Activate.h, a zero
+ * tolerance compares value == zero, so this is the reference's commented-out deactivate(vel, 0, 0). That reading is UNVERIFIED (OpenVDB is absent
+ * from the build image), and no match is claimed for tolerances above 0. The sim holds one mask, the velocity's topology, the only one that shapes
+ * the domain (SOP_HNanoSolver.cpp:186-199); the reference's deactivate + prune of each float grid is not mirrored (there it would only turn the
+ * -0.0f of all-zero float leaves into +0.0f).
+ * Nothing else changes: substeps ignore the masks and the feedback signatures of hns_compute_sim_resident stay valid. The next hns_sim_regrid
+ * (_sourced) dilates what is still active (plus the velocity source masks), so a leaf no active voxel reaches within `padding` is dropped with
+ * ALL its values, listed fields or not, unless it is an SDF leaf: list every field whose values matter. With nothing active, no SDF leaf and no
+ * velocity source, that regrid refuses (HNS_ERR_RUNTIME, "No active voxels") and the sim stays as it is; a later sourced regrid works from there.
+ * A sim with NULL masks (all active) gets its masks from the pooled arena, as hns_sim_set_active_masks does.
+ * counts NULL: asynchronous on stream. Else counts[0] = active voxels, counts[1] = leaves holding one, and the call is synchronous.
+ * Refused, with the masks left exactly as they were (HNS_ERR_INVALID_ARGUMENT): n_fields < 1 or a NULL list, a name the sim lacks, collision_sdf
+ * (its topology comes from the collision input), two entries for one field or two velocity entries, ncomp other than 1 or 3 or ncomp 3 under a
+ * float field's name, a negative or NaN tolerance, a sim lent to a grid's cook cache. Host mirror: hns_deactivate_leaf_masks. */
+int hns_sim_deactivate(hns_sim*, const hns_activity_field* fields, int n_fields, uint64_t* counts, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------ */
 /* Kernel-level entry points on caller-owned DEVICE memory (asynchronous on `stream`).                           */
