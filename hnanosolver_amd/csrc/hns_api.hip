@@ -23,12 +23,6 @@ using namespace hns;
 		}                                                                                              \
 	} while (0)
 
-#define HNS_TRY(call)              \
-	do {                           \
-		int rc__ = (call);         \
-		if (rc__ != HNS_OK) return rc__; \
-	} while (0)
-
 // ---------------------------------------------------------------------------------------------------------------
 // grid: device tables
 // ---------------------------------------------------------------------------------------------------------------
@@ -74,18 +68,6 @@ struct Arena {
 	void* p;
 	size_t bytes;
 	int device;
-};
-// makes `device` current for the scope (allocations, frees and synchronisation of pooled memory belong to ITS device,
-// whatever the calling thread has current)
-struct DeviceScope {
-	int prev = -1;
-	bool switched = false;
-	explicit DeviceScope(int device) {
-		if (device >= 0 && hipGetDevice(&prev) == hipSuccess && prev != device) switched = hipSetDevice(device) == hipSuccess;
-	}
-	~DeviceScope() {
-		if (switched) (void)hipSetDevice(prev);
-	}
 };
 std::mutex g_pool_mutex;
 std::vector<Arena> g_pool;  // at most kPoolMax idle arenas

@@ -47,12 +47,6 @@
 #include "hns_device.hpp"
 #include "hns_flags.hpp"
 
-#define HNS_TRY(call)                    \
-	do {                                 \
-		int rc__ = (call);               \
-		if (rc__ != HNS_OK) return rc__; \
-	} while (0)
-
 // RCCL is bound at run time, the first time a multi-process transport is asked for: libhns.so then carries no load-time
 // dependency on the 500 MB library (single-GPU users never touch it), and a process that already holds an RCCL -- PyTorch
 // ships its own librccl.so.1 -- keeps exactly one copy instead of two interposing each other. (hns_dist_transport.hip)

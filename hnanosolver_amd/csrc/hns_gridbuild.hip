@@ -11,12 +11,6 @@
 
 #include "hns_device.hpp"
 
-#define HNS_TRY_RC(call)           \
-	do {                            \
-		int rc__ = (call);          \
-		if (rc__ != HNS_OK) return rc__; \
-	} while (0)
-
 namespace hns {
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -125,7 +119,7 @@ int hns_grid_upload(hns_grid* g) {
 	                      pad(4 * (2 * nl + 2))};    // scratch of the block-record build on first use (hns_grid_build_blocks: flag[n] | leaders[n] | total[2])
 	size_t total = 0;
 	for (size_t s : sz) total += s;
-	HNS_TRY_RC(hns_arena_get(total, g->device, &g->d_arena, &g->arena_bytes));
+	HNS_TRY(hns_arena_get(total, g->device, &g->d_arena, &g->arena_bytes));
 	char* q = (char*)g->d_arena;
 	void** slot[6] = {&g->d_origins, &g->d_nbr27, &g->d_hash, &g->d_sched_mem, &g->d_blk, &g->d_scratch};
 	for (int i = 0; i < 6; ++i) {

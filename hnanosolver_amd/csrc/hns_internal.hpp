@@ -22,6 +22,25 @@ inline int fail(int code, const char* msg) {
 	return code;
 }
 
+#define HNS_TRY(call)                    \
+	do {                                 \
+		int rc__ = (call);               \
+		if (rc__ != HNS_OK) return rc__; \
+	} while (0)
+
+// makes `device` current for the scope (allocations, frees and synchronisation of pooled memory belong to ITS device,
+// whatever the calling thread has current)
+struct DeviceScope {
+	int prev = -1;
+	bool switched = false;
+	explicit DeviceScope(int device) {
+		if (device >= 0 && hipGetDevice(&prev) == hipSuccess && prev != device) switched = hipSetDevice(device) == hipSuccess;
+	}
+	~DeviceScope() {
+		if (switched) (void)hipSetDevice(prev);
+	}
+};
+
 // ---- options (hns_set_option) -------------------------------------------------------------------------------------
 // Alternative kernel forms and data-movement strategies kept for A/B measurement and as cross-checks of the default one.
 // Every entry point reads the current value when it is called, so a test or benchmark can switch forms between calls.

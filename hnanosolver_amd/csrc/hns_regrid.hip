@@ -8,16 +8,23 @@
 // before the domain is built from the summed velocity). Only the source leaves cross PCIe; the sum is formed in the field phase, the velocity
 // source's leaves and masks join the domain through the candidate and mask phases (dilation distributes over the union, so nothing is pre-merged).
 //
+// The collision SDF is one more entry of the same source list (Source), of its own kind: its leaves join the domain undilated, its masks are ORed
+// in undilated and its values replace collision_sdf instead of being added. Every entry is validated, staged, uploaded and hashed by origin
+// (duplicates are refused) the same way, and all but the velocity's (the mask waves find its leaves) are indexed into the new grid by one kernel.
+//
 //   1. candidates  one thread per (old leaf, offset in the (2R+1)^3 leaf neighbourhood), R = ceil(p / 8), one per SDF leaf and one per (velocity source
 //                  leaf, offset): a hit (the leaf's active voxels reach the candidate's box, hns_dilate.hpp) goes into a fresh origin hash with
-//                  compare-and-swap, then the hash is compacted. Each source's leaves go into an origin hash of their own (duplicates are refused)
+//                  compare-and-swap, then the hash is compacted. Each source's leaves go into an origin hash of their own
 //   2. order       the origins come to the host, are sorted into OpenVDB leaf order and become a new hns_grid through the usual path (Topology::prepare,
 //                  hns_grid_upload: hash, nbr27, launch order); the source values are uploaded meanwhile
 //   3. masks       one wave per new leaf gathers the masks of the old leaves and velocity source leaves within reach (their origin hashes), dilates
 //                  each separably into its own box, ORs them across the wave and ORs in the SDF leaf's mask; the same wave records which old leaf and
-//                  which velocity source leaf (if any) has this origin. Each float source's leaves are indexed into the new grid
-//   4. fields      velocity and every float field, 16 bytes per load and store, from the old leaf or the fill (zeros; bytes 0x01 for collision_sdf),
-//                  into a fresh arena from the pool; a sourced field gets (old or +0) + (source or +0) instead. The old arena goes back to the pool
+//                  which velocity source leaf (if any) has this origin. Every other source's leaves are indexed into the new grid
+//   4. fields      velocity and every float field, 16 bytes per load and store, from the old leaf (collision_sdf: the SDF leaf, when an SDF is given)
+//                  or the fill (zeros; bytes 0x01 for collision_sdf), into a fresh arena from the pool; a field with a velocity or float source gets
+//                  (old or +0) + (source or +0) instead
+//   5. commit      the duplicate refusals the device raised; then the sim moves onto the new grid and the old arena goes back to the pool. Nothing
+//                  before this step touches the sim's state
 //
 // hns_sim_deactivate, at the end of a frame, clears the mask bits of voxels whose listed fields are all within tolerance (the reference's commented-out
 // deactivate, GridBuilder.hpp:213-214), so that the next regrid can drop leaves no active voxel reaches: one wave per leaf, a ballot per 64 voxels.
@@ -27,6 +34,8 @@
 // same bytes.
 #include <algorithm>
 #include <cstring>
+#include <memory>
+#include <type_traits>
 #include <vector>
 
 #include "hns_device.hpp"
@@ -38,18 +47,13 @@ typedef float v3f_act __attribute__((ext_vector_type(3)));
 __device__ float hns_act_load_f32(v4i_act rsrc, int voffset, int soffset, int aux) __asm("llvm.amdgcn.raw.buffer.load.f32");
 __device__ v3f_act hns_act_load_v3f32(v4i_act rsrc, int voffset, int soffset, int aux) __asm("llvm.amdgcn.raw.buffer.load.v3f32");
 
-#define HNS_TRY_RC(call)           \
-	do {                            \
-		int rc__ = (call);          \
-		if (rc__ != HNS_OK) return rc__; \
-	} while (0)
-
 namespace hns {
 namespace {
 
 constexpr unsigned long long kEmptySlot = ~0ull;
 constexpr uint64_t kMaxCandidates = uint64_t(1) << 23;  // distinct leaves the candidate hash may hold (the grid limit is 2^22: Topology::prepare)
-constexpr int kCopyFields = 16;                          // float fields per copy launch
+constexpr int kCopyFields = 16;                          // float fields per copy or add launch
+constexpr uint32_t kSdfFill = 0x01010101u;               // collision_sdf where no leaf has a value: memset(..., 1, ...) (GridBuilder.hpp:108)
 
 __device__ __forceinline__ void load_mask(const unsigned char* masks, int l, uint64_t (&m)[8]) {
 	const uint64_t* w = masks ? (const uint64_t*)(masks + 64 * (size_t)l) : nullptr;
@@ -174,13 +178,14 @@ __device__ __forceinline__ int d_find_src(const SrcHash& h, int x, int y, int z)
 	}
 }
 
-// sdf_idx[new leaf] = the SDF (or float source) leaf with its origin; two such leaves on one origin raise *dup. Leaves outside the new grid are skipped.
-__global__ __launch_bounds__(256) void k_regrid_sdf_index(GridDev ng, const int4* __restrict__ sdf, int n_sdf, int* __restrict__ sdf_idx, int* __restrict__ dup) {
+// idx[new leaf] = the source leaf with its origin; two such leaves on one origin raise *dup. Leaves outside the new grid are skipped (every SDF leaf
+// is a leaf of the new grid; a float source's may not be).
+__global__ __launch_bounds__(256) void k_regrid_src_index(GridDev ng, const int4* __restrict__ origins, int n, int* __restrict__ idx, int* __restrict__ dup) {
 	const int i = blockIdx.x * 256 + threadIdx.x;
-	if (i >= n_sdf) return;
-	const int4 o = sdf[i];
-	const int b = d_find_leaf(ng, o.x, o.y, o.z);  // (every SDF leaf is a leaf of the new grid; a float source's may not be)
-	if (b >= 0 && atomicCAS(&sdf_idx[b], -1, i) != -1) *dup = 1;
+	if (i >= n) return;
+	const int4 o = origins[i];
+	const int b = d_find_leaf(ng, o.x, o.y, o.z);
+	if (b >= 0 && atomicCAS(&idx[b], -1, i) != -1) *dup = 1;
 }
 
 // One wave per new leaf: its dilated mask (OR over the old leaves and velocity source leaves within reach, then the SDF leaf's mask), the old leaf with
@@ -237,22 +242,25 @@ __global__ __launch_bounds__(256) void k_regrid_masks(GridDev og, const unsigned
 	}
 }
 
-struct CopySet {
-	const float4* src[kCopyFields];
+// The fields of one copy or add launch, blockIdx.y = field.
+struct FieldSet {
+	const float4* a[kCopyFields];   // the old field (collision_sdf with an SDF: the SDF's leaves)
+	const int* map_a[kCopyFields];  // new leaf -> leaf of a, -1 = none
+	const float4* b[kCopyFields];   // add: the source's leaves
+	const int* map_b[kCopyFields];  // add: new leaf -> source leaf, -1 = none
 	float4* dst[kCopyFields];
-	const int* map[kCopyFields];  // new leaf -> source leaf, -1 = fill
-	uint32_t fill[kCopyFields];
+	uint32_t fill[kCopyFields];     // copy: the bytes of a new leaf that a lacks
 };
 
-// blockIdx.y = field; NC = floats per voxel (3: the velocity, AoS). Each thread moves four 16-byte pieces, all four loads in flight before the stores.
+// NC = floats per voxel (3: the velocity, AoS). Each thread moves four 16-byte pieces, all four loads in flight before the stores.
 template <int NC>
-__global__ __launch_bounds__(256) void k_regrid_copy(CopySet cs, uint32_t n_f4) {
+__global__ __launch_bounds__(256) void k_regrid_copy(FieldSet fs, uint32_t n_f4) {
 	constexpr uint32_t per_leaf = 128u * NC;
 	const int f = blockIdx.y;
-	const float4* __restrict__ src = cs.src[f];
-	float4* __restrict__ dst = cs.dst[f];
-	const int* __restrict__ map = cs.map[f];
-	const float fv = __uint_as_float(cs.fill[f]);
+	const float4* __restrict__ src = fs.a[f];
+	float4* __restrict__ dst = fs.dst[f];
+	const int* __restrict__ map = fs.map_a[f];
+	const float fv = __uint_as_float(fs.fill[f]);
 	const uint32_t base = blockIdx.x * 1024u + threadIdx.x;
 	float4 v[4];
 #pragma unroll
@@ -272,24 +280,16 @@ __global__ __launch_bounds__(256) void k_regrid_copy(CopySet cs, uint32_t n_f4) 
 	}
 }
 
-struct AddSet {
-	const float4* a[kCopyFields];  // the old field
-	const float4* b[kCopyFields];  // the source's leaves
-	float4* dst[kCopyFields];
-	const int* map_a[kCopyFields];  // new leaf -> old leaf, -1 = none
-	const int* map_b[kCopyFields];  // new leaf -> source leaf, -1 = none
-};
-
 // A sourced field (compSum, then the gather): (old or +0) + (source or +0) in f32, the k_regrid_copy layout. All eight loads in flight before the adds.
 template <int NC>
-__global__ __launch_bounds__(256) void k_regrid_add(AddSet as, uint32_t n_f4) {
+__global__ __launch_bounds__(256) void k_regrid_add(FieldSet fs, uint32_t n_f4) {
 	constexpr uint32_t per_leaf = 128u * NC;
 	const int f = blockIdx.y;
-	const float4* __restrict__ a = as.a[f];
-	const float4* __restrict__ b = as.b[f];
-	float4* __restrict__ dst = as.dst[f];
-	const int* __restrict__ map_a = as.map_a[f];
-	const int* __restrict__ map_b = as.map_b[f];
+	const float4* __restrict__ a = fs.a[f];
+	const float4* __restrict__ b = fs.b[f];
+	float4* __restrict__ dst = fs.dst[f];
+	const int* __restrict__ map_a = fs.map_a[f];
+	const int* __restrict__ map_b = fs.map_b[f];
 	const uint32_t base = blockIdx.x * 1024u + threadIdx.x;
 	float4 va[4], vb[4];
 #pragma unroll
@@ -310,6 +310,18 @@ __global__ __launch_bounds__(256) void k_regrid_add(AddSet as, uint32_t n_f4) {
 	}
 }
 
+// nf fields of nc floats per voxel: k_regrid_add where they have a source to add, else k_regrid_copy
+int launch_fields(const FieldSet& fs, int nf, int nc, bool add, uint64_t n_new, hipStream_t st) {
+	if (!nf) return HNS_OK;
+	const uint32_t n_f4 = (uint32_t)(n_new * 128u * (uint64_t)nc);
+	void (*k)(FieldSet, uint32_t) = nc == 3 ? (add ? k_regrid_add<3> : k_regrid_copy<3>) : (add ? k_regrid_add<1> : k_regrid_copy<1>);
+	k<<<dim3((n_f4 + 1023u) / 1024u, (unsigned)nf), 256, 0, st>>>(fs, n_f4);
+	HNS_HIP(hipGetLastError());
+	return HNS_OK;
+}
+
+size_t pad256(size_t b) { return (b + 255) & ~(size_t)255; }
+
 // device allocations of one regrid, returned to the pool however it ends (hns_arena_put waits for the device first)
 struct Scratch {
 	std::vector<std::pair<void*, size_t>> held;
@@ -321,390 +333,357 @@ struct Scratch {
 		if (rc == HNS_OK) held.emplace_back(*p, got);
 		return rc;
 	}
-	void keep(void* p) {  // ownership passes to the sim
+	// One allocation in 256-byte aligned slices: `slices(slice)` calls slice(pointer, bytes) once per slice, first to size the allocation, then
+	// to point every pointer at its slice, so the sizes and the carve come from the same list.
+	template <class F>
+	int carve(F slices) {
+		size_t total = 0;
+		slices([&](auto*&, size_t bytes) { total += pad256(bytes); });
+		void* p = nullptr;
+		HNS_TRY(get(total, &p));
+		char* q = (char*)p;
+		slices([&](auto*& ptr, size_t bytes) {
+			ptr = reinterpret_cast<std::remove_reference_t<decltype(ptr)>>(q);
+			q += pad256(bytes);
+		});
+		return HNS_OK;
+	}
+	size_t keep(void* p) {  // ownership passes to the sim: returns the allocation's size
+		size_t bytes = 0;
 		for (size_t i = 0; i < held.size(); ++i)
-			if (held[i].first == p) held.erase(held.begin() + (long)i);
+			if (held[i].first == p) bytes = held[i].second, held.erase(held.begin() + (long)i);
+		return bytes;
 	}
 	~Scratch() {
 		for (auto& h : held) hns_arena_put(h.first, h.second, device);
 	}
 };
 
-struct CurrentDevice {
-	int prev = -1;
-	explicit CurrentDevice(int device) {
-		if (hipGetDevice(&prev) != hipSuccess || prev == device || hipSetDevice(device) != hipSuccess) prev = -1;
-	}
-	~CurrentDevice() {
-		if (prev >= 0) (void)hipSetDevice(prev);
-	}
-};
-
-size_t pad256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-int copy_fields(const CopySet& cs, int nf, int nc, uint64_t n_new, hipStream_t st) {
-	if (!nf || !n_new) return HNS_OK;
-	const uint32_t n_f4 = (uint32_t)(n_new * 128u * (uint64_t)nc);
-	const dim3 grid((n_f4 + 1023u) / 1024u, (unsigned)nf);
-	if (nc == 3)
-		k_regrid_copy<3><<<grid, 256, 0, st>>>(cs, n_f4);
-	else
-		k_regrid_copy<1><<<grid, 256, 0, st>>>(cs, n_f4);
-	HNS_HIP(hipGetLastError());
-	return HNS_OK;
-}
-
-int add_fields(const AddSet& as, int nf, int nc, uint64_t n_new, hipStream_t st) {
-	if (!nf || !n_new) return HNS_OK;
-	const uint32_t n_f4 = (uint32_t)(n_new * 128u * (uint64_t)nc);
-	const dim3 grid((n_f4 + 1023u) / 1024u, (unsigned)nf);
-	if (nc == 3)
-		k_regrid_add<3><<<grid, 256, 0, st>>>(as, n_f4);
-	else
-		k_regrid_add<1><<<grid, 256, 0, st>>>(as, n_f4);
-	HNS_HIP(hipGetLastError());
-	return HNS_OK;
-}
-
-// One source of hns_sim_regrid_sourced, validated, and where its leaves live on the device.
+// One entry of the regrid's source list: the collision SDF or one source of hns_sim_regrid_sourced, validated, and where its leaves live on the
+// device. The kinds differ in three places only: the velocity's leaves are dilated candidates (phase 1) and its masks are dilated into the new
+// ones (phase 3), the SDF's leaves and masks join as they are; the SDF's values replace collision_sdf, with the 0x01 byte fill (phase 4), a
+// velocity or float source is added to its field. A float source's masks never enter the domain.
 struct Source {
-	const hns_leaf_source* s = nullptr;
-	int field = -1;  // float field index, -1 = the velocity
+	enum Kind { kVelocity, kFloat, kSdf } kind = kFloat;
+	hns_leaf_source l{};  // the caller's entry (the SDF's: its arguments of hns_sim_regrid)
+	int index = -1;       // in the caller's list (-1: the SDF)
+	int field = -1;       // float field index (the SDF's: collision_sdf), -1 = the velocity
 	std::vector<int32_t> o4;  // the origins as int4 (host staging of the upload)
 	int4* origins = nullptr;
 	int* table = nullptr;  // origin hash (SrcHash)
 	uint32_t mask = 0;
-	unsigned char* masks = nullptr;  // velocity only; null = every voxel active
+	unsigned char* masks = nullptr;  // where they enter the domain (velocity, SDF); null = every voxel active
 	float* values = nullptr;
 	int* idx = nullptr;  // new leaf -> source leaf, -1 = none (phase 3)
+	const char* name() const { return l.name ? l.name : "(null)"; }
 };
 
-int check_sources(const hns_sim* s, const hns_leaf_source* src, int n_src, const char* who, std::vector<Source>& out) {
-	if (n_src < 0 || (n_src > 0 && !src)) {
-		set_error("%s: bad source list", who);
-		return HNS_ERR_INVALID_ARGUMENT;
-	}
-	std::vector<char> taken(s->names.size() + 1, 0);  // [names.size()]: the velocity
-	out.resize((size_t)n_src);
-	for (int i = 0; i < n_src; ++i) {
-		const hns_leaf_source& q = src[i];
-		const char* nm = q.name ? q.name : "(null)";
-		if (q.ncomp != 1 && q.ncomp != 3) {
-			set_error("%s: source %d ('%s'): ncomp %d (1 or 3)", who, i, nm, q.ncomp);
-			return HNS_ERR_INVALID_ARGUMENT;
-		}
-		const int f = q.name ? s->find(q.name) : -1;
-		if (q.name && !strcmp(q.name, "collision_sdf")) {
-			set_error("%s: source %d: 'collision_sdf' cannot be a source (the SDF comes from the collision input, never from the feedback)", who, i);
-			return HNS_ERR_INVALID_ARGUMENT;
-		}
-		if (q.ncomp == 1 && f < 0) {
-			set_error("%s: source %d: the sim has no float field '%s'", who, i, nm);
-			return HNS_ERR_INVALID_ARGUMENT;
-		}
-		if (q.ncomp == 3 && f >= 0) {
-			set_error("%s: source %d: ncomp 3 under the float field name '%s'", who, i, nm);
-			return HNS_ERR_INVALID_ARGUMENT;
-		}
-		const size_t slot = q.ncomp == 3 ? s->names.size() : (size_t)f;
-		if (taken[slot]) {
-			if (q.ncomp == 3)
-				set_error("%s: source %d: a second velocity source", who, i);
+// 8-aligned origins, checked alike for the SDF and every source (the other checks of a source do not apply to the SDF: it has no leaf limit, and
+// regrid_entry refuses its NULL arrays)
+int check_origins(const Source& q, const char* who) {
+	for (uint64_t k = 0; k < 3 * q.l.n_leaves; ++k)
+		if (q.l.origins[k] & 7) {
+			if (q.kind == Source::kSdf)
+				set_error("%s: SDF leaf origin %llu is not 8-aligned", who, (unsigned long long)(k / 3));
 			else
-				set_error("%s: source %d: a second source for '%s'", who, i, nm);
-			return HNS_ERR_INVALID_ARGUMENT;
+				set_error("%s: source %d ('%s'): leaf origin %llu is not 8-aligned", who, q.index, q.name(), (unsigned long long)(k / 3));
+			return HNS_ERR_TOPOLOGY;
 		}
-		taken[slot] = 1;
-		if (q.n_leaves && (!q.origins || !q.values)) {
-			set_error("%s: source %d ('%s'): origins or values NULL with %llu leaves", who, i, nm, (unsigned long long)q.n_leaves);
-			return HNS_ERR_INVALID_ARGUMENT;
-		}
-		if (q.n_leaves > (uint64_t(1) << 22)) {
-			set_error("%s: source %d ('%s'): %llu leaves exceed the 2^22-leaf limit", who, i, nm, (unsigned long long)q.n_leaves);
-			return HNS_ERR_INVALID_ARGUMENT;
-		}
-		for (uint64_t k = 0; k < 3 * q.n_leaves; ++k)
-			if (q.origins[k] & 7) {
-				set_error("%s: source %d ('%s'): leaf origin %llu is not 8-aligned", who, i, nm, (unsigned long long)(k / 3));
-				return HNS_ERR_TOPOLOGY;
-			}
-		out[i].s = &q;
-		out[i].field = q.ncomp == 3 ? -1 : f;
-	}
 	return HNS_OK;
 }
 
-// The regrid proper; the sim is only touched at the very end, when everything has succeeded. `who` names the entry point in messages.
-int regrid(hns_sim* s, int p, const hns_leaf_source* src, int n_src, const int32_t* sdf_origins, uint64_t n_sdf, const unsigned char* sdf_masks, const float* sdf_values,
-           hipStream_t st, hns_grid** out, const char* who) {
-	hns_grid* og = s->grid;
-	const bool have_src = sdf_values != nullptr;
-	const int i_sdf = s->find("collision_sdf");
+// One regrid of s: its source list, its device scratch and what each phase hands the next. The sim is only touched by commit().
+struct Regrid {
+	hns_sim* s;
+	int p, R;
+	hipStream_t st;
+	const char* who;
+	std::vector<Source> srcs;  // the SDF first, when given, then the caller's sources (before the scratch: its staging outlives the device work)
+	Source* vsrc = nullptr;    // the velocity's source, if any
+	Source* sdf = nullptr;
+	Scratch scratch;
+	std::unique_ptr<hns_grid, void (*)(hns_grid*)> ng{nullptr, hns_grid_destroy};
+	Candidates c{};
+	int4* compact = nullptr;
+	int* dup = nullptr;  // one duplicate flag per source
+	uint64_t n_new = 0;
+	int* map = nullptr;  // new leaf -> old leaf, -1 = new
+	void* new_masks = nullptr;
+	void* new_fields = nullptr;
+
+	Regrid(hns_sim* sim, int padding, hipStream_t stream, const char* w) : s(sim), p(padding), R((padding + 7) / 8), st(stream), who(w), scratch(sim->device) {}
+
+	// ---- 0. the source list, checked; `sdf_src` is the SDF (given iff its values are) ----
+	int sources(const hns_leaf_source& sdf_src, const hns_leaf_source* src, int n_src) {
+		if (sdf_src.values) {
+			Source q;
+			q.kind = Source::kSdf, q.l = sdf_src, q.field = s->find("collision_sdf");
+			if (q.field < 0) {
+				set_error("%s: a collision SDF source was given but the sim has no field 'collision_sdf'", who);
+				return HNS_ERR_INVALID_ARGUMENT;
+			}
+			HNS_TRY(check_origins(q, who));
+			srcs.push_back(q);
+		}
+		if (n_src < 0 || (n_src > 0 && !src)) {
+			set_error("%s: bad source list", who);
+			return HNS_ERR_INVALID_ARGUMENT;
+		}
+		std::vector<char> taken(s->names.size() + 1, 0);  // [names.size()]: the velocity
+		for (int i = 0; i < n_src; ++i) {
+			const hns_leaf_source& l = src[i];
+			const char* nm = l.name ? l.name : "(null)";
+			if (l.ncomp != 1 && l.ncomp != 3) {
+				set_error("%s: source %d ('%s'): ncomp %d (1 or 3)", who, i, nm, l.ncomp);
+				return HNS_ERR_INVALID_ARGUMENT;
+			}
+			const int f = l.name ? s->find(l.name) : -1;
+			if (l.name && !strcmp(l.name, "collision_sdf")) {
+				set_error("%s: source %d: 'collision_sdf' cannot be a source (the SDF comes from the collision input, never from the feedback)", who, i);
+				return HNS_ERR_INVALID_ARGUMENT;
+			}
+			if (l.ncomp == 1 && f < 0) {
+				set_error("%s: source %d: the sim has no float field '%s'", who, i, nm);
+				return HNS_ERR_INVALID_ARGUMENT;
+			}
+			if (l.ncomp == 3 && f >= 0) {
+				set_error("%s: source %d: ncomp 3 under the float field name '%s'", who, i, nm);
+				return HNS_ERR_INVALID_ARGUMENT;
+			}
+			const size_t slot = l.ncomp == 3 ? s->names.size() : (size_t)f;
+			if (taken[slot]) {
+				if (l.ncomp == 3)
+					set_error("%s: source %d: a second velocity source", who, i);
+				else
+					set_error("%s: source %d: a second source for '%s'", who, i, nm);
+				return HNS_ERR_INVALID_ARGUMENT;
+			}
+			taken[slot] = 1;
+			if (l.n_leaves && (!l.origins || !l.values)) {
+				set_error("%s: source %d ('%s'): origins or values NULL with %llu leaves", who, i, nm, (unsigned long long)l.n_leaves);
+				return HNS_ERR_INVALID_ARGUMENT;
+			}
+			if (l.n_leaves > (uint64_t(1) << 22)) {
+				set_error("%s: source %d ('%s'): %llu leaves exceed the 2^22-leaf limit", who, i, nm, (unsigned long long)l.n_leaves);
+				return HNS_ERR_INVALID_ARGUMENT;
+			}
+			Source q;
+			q.kind = l.ncomp == 3 ? Source::kVelocity : Source::kFloat, q.l = l, q.index = i, q.field = l.ncomp == 3 ? -1 : f;
+			HNS_TRY(check_origins(q, who));
+			srcs.push_back(q);
+		}
+		for (Source& q : srcs) {
+			if (q.kind == Source::kVelocity) vsrc = &q;
+			if (q.kind == Source::kSdf) sdf = &q;
+		}
+		return HNS_OK;
+	}
+
+	// ---- 1. candidates: every source's origins (and masks where they enter the domain) go up and into its origin hash; the candidate hash ----
+	int candidates() {
+		const hns_grid* og = s->grid;
+		const uint64_t K = (uint64_t)(2 * R + 1) * (2 * R + 1) * (2 * R + 1);
+		c.old_origins = (const int4*)og->d_origins, c.old_masks = s->d_masks;
+		c.n_dil = (uint64_t)og->topo.n_leaves * K, c.n_sdf = sdf ? sdf->l.n_leaves : 0, c.n_vdil = vsrc ? vsrc->l.n_leaves * K : 0;
+		c.side = 2 * R + 1, c.R = R, c.p = p;
+		const uint64_t total = c.n_dil + c.n_sdf + c.n_vdil;
+		c.cap = std::min<uint64_t>(total, kMaxCandidates);
+		uint64_t T = 16;
+		while (T < 2 * c.cap) T <<= 1;
+		c.mask = (uint32_t)(T - 1);
+		for (Source& q : srcs) {
+			const uint64_t n = q.l.n_leaves;
+			uint64_t Ts = 16;
+			while (Ts < 2 * n) Ts <<= 1;
+			q.mask = (uint32_t)(Ts - 1);
+			q.o4.assign((size_t)n * 4, 0);
+			for (uint64_t i = 0; i < n; ++i)
+				for (int a = 0; a < 3; ++a) q.o4[4 * i + a] = q.l.origins[3 * i + a];
+		}
+		HNS_TRY(scratch.carve([&](auto&& slice) {
+			slice(c.table, 8 * T);
+			slice(compact, 16 * std::max<uint64_t>(c.cap, 1));
+			slice(c.count, 256);
+		}));
+		if (!srcs.empty())  // (an allocation of their own: the arena pool then serves a regrid with sources as it serves one without)
+			HNS_TRY(scratch.carve([&](auto&& slice) {
+				slice(dup, 4 * srcs.size());
+				for (Source& q : srcs) {
+					const uint64_t n1 = std::max<uint64_t>(q.l.n_leaves, 1);
+					slice(q.origins, 16 * n1);
+					slice(q.table, 4 * ((uint64_t)q.mask + 1));
+					if (q.kind != Source::kFloat && q.l.masks) slice(q.masks, 64 * n1);
+					slice(q.values, 2048 * (uint64_t)q.l.ncomp * n1);
+				}
+			}));
+		c.sdf = sdf ? sdf->origins : nullptr;
+		c.vsrc = vsrc ? vsrc->origins : nullptr, c.vsrc_masks = vsrc ? vsrc->masks : nullptr;
+		HNS_HIP(hipEventRecord(s->rev[0], st));
+		HNS_HIP(hipMemsetAsync(c.table, 0xFF, 8 * T, st));
+		HNS_HIP(hipMemsetAsync(c.count, 0, 256, st));
+		if (!srcs.empty()) HNS_HIP(hipMemsetAsync(dup, 0, 4 * srcs.size(), st));
+		for (size_t i = 0; i < srcs.size(); ++i) {
+			Source& q = srcs[i];
+			const uint64_t n = q.l.n_leaves;
+			HNS_HIP(hipMemsetAsync(q.table, 0xFF, 4 * ((size_t)q.mask + 1), st));
+			if (!n) continue;
+			HNS_HIP(hipMemcpyAsync(q.origins, q.o4.data(), 16 * n, hipMemcpyHostToDevice, st));
+			if (q.masks) HNS_HIP(hipMemcpyAsync(q.masks, q.l.masks, 64 * n, hipMemcpyHostToDevice, st));
+			k_regrid_src_hash<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(q.origins, (int)n, q.table, q.mask, dup + i);
+			HNS_HIP(hipGetLastError());
+		}
+		if (total) {
+			k_regrid_candidates<<<(unsigned)std::min<uint64_t>((total + 255) / 256, 1u << 20), 256, 0, st>>>(c);
+			HNS_HIP(hipGetLastError());
+			k_regrid_compact<<<(unsigned)(T / 256 ? T / 256 : 1), 256, 0, st>>>(c, compact);
+			HNS_HIP(hipGetLastError());
+		}
+		HNS_HIP(hipEventRecord(s->rev[1], st));
+		unsigned long long counts[3] = {0, 0, 0};
+		HNS_HIP(hipMemcpyAsync(counts, c.count, sizeof(counts), hipMemcpyDeviceToHost, st));
+		HNS_HIP(hipStreamSynchronize(st));
+		if (counts[1] || counts[2] > (uint64_t(1) << 22)) {
+			set_error("%s: the new domain exceeds the 2^22-leaf (2^31-voxel) limit of 32-bit voxel indices", who);
+			return HNS_ERR_TOPOLOGY;
+		}
+		n_new = counts[2];
+		if (n_new == 0) {  // SOP_HNanoSolver.cpp: "No active voxels"
+			set_error("%s: No active voxels in the new domain", who);
+			return HNS_ERR_RUNTIME;
+		}
+		return HNS_OK;
+	}
+
+	// ---- 2. order + grid: the origins to the host, OpenVDB leaf order, the new grid; the source values go up meanwhile ----
+	int order() {
+		std::vector<int32_t> c4((size_t)n_new * 4);
+		HNS_HIP(hipMemcpyAsync(c4.data(), compact, 16 * n_new, hipMemcpyDeviceToHost, st));
+		HNS_HIP(hipEventRecord(s->rev[5], st));
+		for (Source& q : srcs)  // issued before the sort, so that they can overlap it
+			if (q.l.n_leaves) HNS_HIP(hipMemcpyAsync(q.values, q.l.values, 2048 * (size_t)q.l.ncomp * q.l.n_leaves, hipMemcpyHostToDevice, st));
+		HNS_HIP(hipEventSynchronize(s->rev[5]));
+		std::vector<int32_t> xyz((size_t)n_new * 3);
+		for (uint64_t i = 0; i < n_new; ++i)
+			for (int a = 0; a < 3; ++a) xyz[3 * i + a] = c4[4 * i + a];
+		sort_leaf_origins(xyz.data(), (size_t)n_new);
+		ng.reset(new hns_grid);
+		ng->voxel_size = s->grid->voxel_size;
+		HNS_TRY(ng->topo.prepare(xyz.data(), (int64_t)n_new));
+		ng->n_active = n_new;
+		HNS_TRY(hns_grid_upload(ng.get()));
+		HNS_HIP(hipEventRecord(s->rev[2], st));
+		return HNS_OK;
+	}
+
+	// ---- 3. masks: one wave per new leaf; every source but the velocity's (whose leaves the waves find) indexed into the new grid ----
+	int masks() {
+		HNS_TRY(scratch.carve([&](auto&& slice) { slice(map, 4 * n_new); }));
+		HNS_TRY(scratch.get(64 * n_new, &new_masks));
+		if (!srcs.empty())
+			HNS_TRY(scratch.carve([&](auto&& slice) {
+				for (Source& q : srcs) slice(q.idx, 4 * n_new);
+			}));
+		for (size_t i = 0; i < srcs.size(); ++i) {
+			Source& q = srcs[i];
+			if (q.kind == Source::kVelocity) continue;
+			HNS_HIP(hipMemsetAsync(q.idx, 0xFF, 4 * n_new, st));  // (a source without leaves: every leaf is fill)
+			if (!q.l.n_leaves) continue;
+			k_regrid_src_index<<<(unsigned)((q.l.n_leaves + 255) / 256), 256, 0, st>>>(ng->dev(), q.origins, (int)q.l.n_leaves, q.idx, dup + i);
+			HNS_HIP(hipGetLastError());
+		}
+		const SrcHash vh{vsrc ? vsrc->origins : nullptr, vsrc ? vsrc->table : nullptr, vsrc ? vsrc->mask : 0u};
+		k_regrid_masks<<<(unsigned)((n_new + 3) / 4), 256, 0, st>>>(s->grid->dev(), s->d_masks, (const int4*)ng->d_origins, (int)n_new, p, R, sdf ? sdf->idx : nullptr,
+		                                                           sdf ? sdf->masks : nullptr, vh, vsrc ? vsrc->masks : nullptr, (uint64_t*)new_masks, map,
+		                                                           vsrc ? vsrc->idx : nullptr);
+		HNS_HIP(hipGetLastError());
+		HNS_HIP(hipEventRecord(s->rev[3], st));
+		return HNS_OK;
+	}
+
+	// entry j of a field launch: dst from `old` through map, or (q the SDF) from the SDF's leaves; with a velocity or float source q added
+	void field(FieldSet& fs, int j, const float* old, float* dst, const Source* q, uint32_t fill) const {
+		const bool from_sdf = q && q->kind == Source::kSdf, add = q && !from_sdf;
+		fs.a[j] = (const float4*)(from_sdf ? q->values : old), fs.map_a[j] = from_sdf ? q->idx : map;
+		fs.b[j] = add ? (const float4*)q->values : nullptr, fs.map_b[j] = add ? q->idx : nullptr;
+		fs.dst[j] = (float4*)dst, fs.fill[j] = fill;
+	}
+
+	// ---- 4. fields: into a fresh arena, the velocity, then the float fields copied and those with a source added, kCopyFields per launch ----
+	int fields() {
+		hns_sim shell;  // the new layout, built over the new arena (the sim itself keeps the old one until the end)
+		shell.names = s->names;
+		HNS_TRY(scratch.get(hns_sim_arena_need(s, n_new * 512u), &new_fields));
+		hns_sim_layout(&shell, new_fields, n_new * 512u);
+		std::vector<const Source*> src_of(s->names.size(), nullptr);
+		for (const Source& q : srcs)
+			if (q.field >= 0) src_of[(size_t)q.field] = &q;
+		const int i_sdf = s->find("collision_sdf");
+		FieldSet fs{};
+		field(fs, 0, s->vel, shell.vel, vsrc, 0u);
+		HNS_TRY(launch_fields(fs, 1, 3, vsrc != nullptr, n_new, st));
+		for (const bool add : {false, true}) {
+			int nf = 0;
+			for (size_t f = 0; f < s->names.size(); ++f) {
+				const Source* q = src_of[f];
+				if ((q && q->kind == Source::kFloat) != add) continue;
+				field(fs, nf++, s->cur[f], shell.cur[f], q, (int)f == i_sdf ? kSdfFill : 0u);
+				if (nf == kCopyFields) {
+					HNS_TRY(launch_fields(fs, nf, 1, add, n_new, st));
+					nf = 0;
+				}
+			}
+			HNS_TRY(launch_fields(fs, nf, 1, add, n_new, st));
+		}
+		HNS_HIP(hipEventRecord(s->rev[4], st));
+		return HNS_OK;
+	}
+
+	// ---- 5. commit: the duplicate origins the device found refuse the regrid; else the sim moves onto the new grid ----
+	int commit(hns_grid** out) {
+		std::vector<int> dups(srcs.size(), 0);
+		if (!srcs.empty()) HNS_HIP(hipMemcpyAsync(dups.data(), dup, 4 * srcs.size(), hipMemcpyDeviceToHost, st));
+		HNS_HIP(hipStreamSynchronize(st));
+		for (size_t i = 0; i < srcs.size(); ++i) {
+			if (!dups[i]) continue;
+			if (srcs[i].kind == Source::kSdf)
+				set_error("%s: duplicate SDF leaf origin", who);
+			else
+				set_error("%s: source %d ('%s'): duplicate leaf origin", who, srcs[i].index, srcs[i].name());
+			return HNS_ERR_TOPOLOGY;
+		}
+		scratch.held.emplace_back(s->arena, s->arena_bytes);  // the old state goes back to the pool with the scratch
+		if (s->d_masks) scratch.held.emplace_back(s->d_masks, s->masks_bytes);
+		s->arena = new_fields, s->arena_bytes = scratch.keep(new_fields);
+		hns_sim_layout(s, new_fields, n_new * 512u);
+		s->d_masks = (unsigned char*)new_masks, s->masks_bytes = scratch.keep(new_masks);
+		s->grid = ng.release();
+		s->sig_vel = s->dig_vel = 0;
+		std::fill(s->sig_cur.begin(), s->sig_cur.end(), 0);
+		std::fill(s->dig_cur.begin(), s->dig_cur.end(), 0);
+		s->regrid_timed = true;
+		*out = s->grid;
+		return HNS_OK;
+	}
+};
+
+// The regrid proper (include/hns.h); `who` names the entry point in messages.
+int regrid(hns_sim* s, int p, const hns_leaf_source* src, int n_src, const hns_leaf_source& sdf, hipStream_t st, hns_grid** out, const char* who) {
+	const hns_grid* og = s->grid;
 	if (og->first_active != 0 || og->n_active != (uint64_t)og->topo.n_leaves) {
 		set_error("%s: the grid's launch range is not the whole grid (a multi-GPU rank's grid cannot be regridded)", who);
 		return HNS_ERR_INVALID_ARGUMENT;
 	}
-	if (have_src && i_sdf < 0) {
-		set_error("%s: a collision SDF source was given but the sim has no field 'collision_sdf'", who);
-		return HNS_ERR_INVALID_ARGUMENT;
-	}
-	for (uint64_t i = 0; i < 3 * n_sdf; ++i)
-		if (sdf_origins[i] & 7) {
-			set_error("%s: SDF leaf origin %llu is not 8-aligned", who, (unsigned long long)(i / 3));
-			return HNS_ERR_TOPOLOGY;
-		}
-	std::vector<Source> srcs;  // (before the scratch: its staging outlives the device work)
-	HNS_TRY_RC(check_sources(s, src, n_src, who, srcs));
-	Source* vsrc = nullptr;
-	for (Source& q : srcs)
-		if (q.field < 0) vsrc = &q;
-	CurrentDevice on(s->device);
+	DeviceScope on(s->device);
+	Regrid r(s, p, st, who);
+	HNS_TRY(r.sources(sdf, src, n_src));
 	if (!s->rev[0])
 		for (hipEvent_t& e : s->rev) HNS_HIP(hipEventCreate(&e));
 	s->regrid_timed = false;
-	Scratch scratch(s->device);
-
-	// ---- 1. candidates ----
-	const uint64_t n_old = (uint64_t)og->topo.n_leaves;
-	const int R = (p + 7) / 8, side = 2 * R + 1;
-	const uint64_t n_dil = n_old * (uint64_t)side * side * side;
-	const uint64_t n_vdil = vsrc ? vsrc->s->n_leaves * (uint64_t)side * side * side : 0;
-	const uint64_t cap = std::min<uint64_t>(n_dil + n_sdf + n_vdil, kMaxCandidates);
-	uint64_t T = 16;
-	while (T < 2 * cap) T <<= 1;
-	std::vector<int32_t> sdf4((size_t)n_sdf * 4, 0);
-	for (uint64_t i = 0; i < n_sdf; ++i)
-		for (int a = 0; a < 3; ++a) sdf4[4 * i + a] = sdf_origins[3 * i + a];
-	const size_t sz1[4] = {pad256(8 * T), pad256(16 * (cap ? cap : 1)), pad256(16 * (n_sdf ? n_sdf : 1)), 256};
-	void* p1 = nullptr;
-	HNS_TRY_RC(scratch.get(sz1[0] + sz1[1] + sz1[2] + sz1[3], &p1));
-	char* q = (char*)p1;
-	Candidates c;
-	c.table = (unsigned long long*)q, q += sz1[0];
-	int4* compact = (int4*)q;
-	q += sz1[1];
-	int4* d_sdf = (int4*)q;
-	q += sz1[2];
-	c.count = (unsigned long long*)q;
-	// the sources: per source its origins, origin hash, masks (velocity) and values, and one duplicate flag each
-	int* src_dup = nullptr;
-	if (!srcs.empty()) {
-		size_t bytes = pad256(4 * srcs.size());
-		for (Source& sr : srcs) {
-			const uint64_t n = sr.s->n_leaves, n1 = n ? n : 1;
-			uint64_t Ts = 16;
-			while (Ts < 2 * n) Ts <<= 1;
-			sr.mask = (uint32_t)(Ts - 1);
-			bytes += pad256(16 * n1) + pad256(4 * Ts) + (sr.field < 0 && sr.s->masks ? pad256(64 * n1) : 0) + pad256(2048 * (uint64_t)sr.s->ncomp * n1);
-		}
-		void* ps = nullptr;
-		HNS_TRY_RC(scratch.get(bytes, &ps));
-		q = (char*)ps;
-		src_dup = (int*)q;
-		q += pad256(4 * srcs.size());
-		for (Source& sr : srcs) {
-			const uint64_t n = sr.s->n_leaves, n1 = n ? n : 1;
-			sr.origins = (int4*)q, q += pad256(16 * n1);
-			sr.table = (int*)q, q += pad256(4 * ((uint64_t)sr.mask + 1));
-			if (sr.field < 0 && sr.s->masks) sr.masks = (unsigned char*)q, q += pad256(64 * n1);
-			sr.values = (float*)q, q += pad256(2048 * (uint64_t)sr.s->ncomp * n1);
-			sr.o4.assign((size_t)n * 4, 0);
-			for (uint64_t i = 0; i < n; ++i)
-				for (int a = 0; a < 3; ++a) sr.o4[4 * i + a] = sr.s->origins[3 * i + a];
-		}
-	}
-	c.old_origins = (const int4*)og->d_origins, c.old_masks = s->d_masks, c.sdf = d_sdf;
-	c.vsrc = vsrc ? vsrc->origins : nullptr, c.vsrc_masks = vsrc ? vsrc->masks : nullptr;
-	c.n_dil = n_dil, c.n_sdf = n_sdf, c.n_vdil = n_vdil, c.side = side, c.R = R, c.p = p;
-	c.mask = (uint32_t)(T - 1), c.cap = cap;
-	HNS_HIP(hipEventRecord(s->rev[0], st));
-	HNS_HIP(hipMemsetAsync(c.table, 0xFF, 8 * T, st));
-	HNS_HIP(hipMemsetAsync(c.count, 0, 256, st));
-	if (n_sdf) HNS_HIP(hipMemcpyAsync(d_sdf, sdf4.data(), 16 * n_sdf, hipMemcpyHostToDevice, st));
-	if (!srcs.empty()) HNS_HIP(hipMemsetAsync(src_dup, 0, 4 * srcs.size(), st));
-	for (size_t i = 0; i < srcs.size(); ++i) {
-		Source& sr = srcs[i];
-		const uint64_t n = sr.s->n_leaves;
-		HNS_HIP(hipMemsetAsync(sr.table, 0xFF, 4 * ((size_t)sr.mask + 1), st));
-		if (!n) continue;
-		HNS_HIP(hipMemcpyAsync(sr.origins, sr.o4.data(), 16 * n, hipMemcpyHostToDevice, st));
-		if (sr.masks) HNS_HIP(hipMemcpyAsync(sr.masks, sr.s->masks, 64 * n, hipMemcpyHostToDevice, st));
-		k_regrid_src_hash<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(sr.origins, (int)n, sr.table, sr.mask, src_dup + i);
-		HNS_HIP(hipGetLastError());
-	}
-	if (n_dil + n_sdf + n_vdil) {
-		const uint64_t blocks = std::min<uint64_t>((n_dil + n_sdf + n_vdil + 255) / 256, 1u << 20);
-		k_regrid_candidates<<<(unsigned)blocks, 256, 0, st>>>(c);
-		HNS_HIP(hipGetLastError());
-		k_regrid_compact<<<(unsigned)(T / 256 ? T / 256 : 1), 256, 0, st>>>(c, compact);
-		HNS_HIP(hipGetLastError());
-	}
-	HNS_HIP(hipEventRecord(s->rev[1], st));
-	unsigned long long counts[3] = {0, 0, 0};
-	HNS_HIP(hipMemcpyAsync(counts, c.count, sizeof(counts), hipMemcpyDeviceToHost, st));
-	HNS_HIP(hipStreamSynchronize(st));
-	if (counts[1] || counts[2] > (uint64_t(1) << 22)) {
-		set_error("%s: the new domain exceeds the 2^22-leaf (2^31-voxel) limit of 32-bit voxel indices", who);
-		return HNS_ERR_TOPOLOGY;
-	}
-	const uint64_t n_new = counts[2];
-	if (n_new == 0) {  // SOP_HNanoSolver.cpp: "No active voxels"
-		set_error("%s: No active voxels in the new domain", who);
-		return HNS_ERR_RUNTIME;
-	}
-
-	// ---- 2. order + grid ----
-	std::vector<int32_t> c4((size_t)n_new * 4);
-	HNS_HIP(hipMemcpyAsync(c4.data(), compact, 16 * n_new, hipMemcpyDeviceToHost, st));
-	HNS_HIP(hipEventRecord(s->rev[5], st));
-	for (Source& sr : srcs)  // issued before the sort, so that they can overlap it
-		if (sr.s->n_leaves)
-			HNS_HIP(hipMemcpyAsync(sr.values, sr.s->values, 2048 * (size_t)sr.s->ncomp * sr.s->n_leaves, hipMemcpyHostToDevice, st));
-	HNS_HIP(hipEventSynchronize(s->rev[5]));
-	std::vector<int32_t> xyz((size_t)n_new * 3);
-	for (uint64_t i = 0; i < n_new; ++i)
-		for (int a = 0; a < 3; ++a) xyz[3 * i + a] = c4[4 * i + a];
-	sort_leaf_origins(xyz.data(), (size_t)n_new);
-	struct GridOwner {
-		hns_grid* g = new hns_grid;
-		~GridOwner() {
-			if (g) hns_grid_destroy(g);
-		}
-	} ng;
-	ng.g->voxel_size = og->voxel_size;
-	HNS_TRY_RC(ng.g->topo.prepare(xyz.data(), (int64_t)n_new));
-	ng.g->n_active = n_new;
-	HNS_TRY_RC(hns_grid_upload(ng.g));
-	HNS_HIP(hipEventRecord(s->rev[2], st));
-
-	// ---- 3. masks ----
-	const size_t sz2[5] = {pad256(4 * n_new), pad256(4 * n_new), pad256(64 * (n_sdf ? n_sdf : 1)), pad256(2048 * (have_src && n_sdf ? n_sdf : 1)), 256};
-	void *p2 = nullptr, *p_masks = nullptr;
-	HNS_TRY_RC(scratch.get(sz2[0] + sz2[1] + sz2[2] + sz2[3] + sz2[4], &p2));
-	HNS_TRY_RC(scratch.get(64 * n_new, &p_masks));
-	q = (char*)p2;
-	int* map = (int*)q;
-	q += sz2[0];
-	int* sdf_idx = (int*)q;
-	q += sz2[1];
-	unsigned char* d_sdf_masks = (unsigned char*)q;
-	q += sz2[2];
-	float* d_sdf_values = (float*)q;
-	q += sz2[3];
-	int* dup = (int*)q;
-	HNS_HIP(hipMemsetAsync(dup, 0, 4, st));
-	if (n_sdf || have_src) HNS_HIP(hipMemsetAsync(sdf_idx, 0xFF, 4 * n_new, st));  // (a source without leaves: every leaf is fill)
-	if (n_sdf) {
-		if (sdf_masks) HNS_HIP(hipMemcpyAsync(d_sdf_masks, sdf_masks, 64 * n_sdf, hipMemcpyHostToDevice, st));
-		if (have_src) HNS_HIP(hipMemcpyAsync(d_sdf_values, sdf_values, 2048 * n_sdf, hipMemcpyHostToDevice, st));
-		k_regrid_sdf_index<<<(unsigned)((n_sdf + 255) / 256), 256, 0, st>>>(ng.g->dev(), d_sdf, (int)n_sdf, sdf_idx, dup);
-		HNS_HIP(hipGetLastError());
-	}
-	if (!srcs.empty()) {  // new leaf -> source leaf: the velocity's from the mask waves, each float source's by its own leaves
-		void* pi = nullptr;
-		HNS_TRY_RC(scratch.get(pad256(4 * n_new) * srcs.size(), &pi));
-		for (size_t i = 0; i < srcs.size(); ++i) {
-			Source& sr = srcs[i];
-			sr.idx = (int*)((char*)pi + pad256(4 * n_new) * i);
-			if (sr.field < 0) continue;
-			HNS_HIP(hipMemsetAsync(sr.idx, 0xFF, 4 * n_new, st));
-			if (!sr.s->n_leaves) continue;
-			k_regrid_sdf_index<<<(unsigned)((sr.s->n_leaves + 255) / 256), 256, 0, st>>>(ng.g->dev(), sr.origins, (int)sr.s->n_leaves, sr.idx, src_dup + i);
-			HNS_HIP(hipGetLastError());
-		}
-	}
-	const SrcHash vh{vsrc ? vsrc->origins : nullptr, vsrc ? vsrc->table : nullptr, vsrc ? vsrc->mask : 0u};
-	k_regrid_masks<<<(unsigned)((n_new + 3) / 4), 256, 0, st>>>(og->dev(), s->d_masks, (const int4*)ng.g->d_origins, (int)n_new, p, R, n_sdf ? sdf_idx : nullptr,
-	                                                           sdf_masks ? d_sdf_masks : nullptr, vh, vsrc ? vsrc->masks : nullptr, (uint64_t*)p_masks, map,
-	                                                           vsrc ? vsrc->idx : nullptr);
-	HNS_HIP(hipGetLastError());
-	HNS_HIP(hipEventRecord(s->rev[3], st));
-
-	// ---- 4. fields ----
-	hns_sim shell;  // the new layout, built over the new arena (the sim itself keeps the old one until the end)
-	shell.names = s->names;
-	void* p_fields = nullptr;
-	HNS_TRY_RC(scratch.get(hns_sim_arena_need(s, n_new * 512u), &p_fields));
-	hns_sim_layout(&shell, p_fields, n_new * 512u);
-	const uint32_t sdf_fill = 0x01010101u;  // memset(..., 1, ...) (GridBuilder.hpp:108)
-	if (vsrc) {
-		AddSet as{};
-		as.a[0] = (const float4*)s->vel, as.map_a[0] = map;
-		as.b[0] = (const float4*)vsrc->values, as.map_b[0] = vsrc->idx;
-		as.dst[0] = (float4*)shell.vel;
-		HNS_TRY_RC(add_fields(as, 1, 3, n_new, st));
-	} else {
-		CopySet vs{};
-		vs.src[0] = (const float4*)s->vel, vs.dst[0] = (float4*)shell.vel, vs.map[0] = map, vs.fill[0] = 0;
-		HNS_TRY_RC(copy_fields(vs, 1, 3, n_new, st));
-	}
-	std::vector<const Source*> src_of(s->names.size(), nullptr);
-	for (const Source& sr : srcs)
-		if (sr.field >= 0) src_of[(size_t)sr.field] = &sr;
-	std::vector<size_t> plain, summed;  // fields carried as they are / with a source added
-	for (size_t f = 0; f < s->names.size(); ++f) (src_of[f] ? summed : plain).push_back(f);
-	for (size_t f0 = 0; f0 < plain.size(); f0 += kCopyFields) {
-		CopySet cs{};
-		int nf = 0;
-		for (size_t j = f0; j < plain.size() && nf < kCopyFields; ++j, ++nf) {
-			const size_t f = plain[j];
-			const bool sdf = (int)f == i_sdf;
-			const bool from_src = sdf && have_src;
-			cs.src[nf] = from_src ? (const float4*)d_sdf_values : (const float4*)s->cur[f];
-			cs.map[nf] = from_src ? sdf_idx : map;
-			cs.dst[nf] = (float4*)shell.cur[f];
-			cs.fill[nf] = sdf ? sdf_fill : 0u;
-		}
-		HNS_TRY_RC(copy_fields(cs, nf, 1, n_new, st));
-	}
-	for (size_t f0 = 0; f0 < summed.size(); f0 += kCopyFields) {
-		AddSet as{};
-		int nf = 0;
-		for (size_t j = f0; j < summed.size() && nf < kCopyFields; ++j, ++nf) {
-			const size_t f = summed[j];
-			as.a[nf] = (const float4*)s->cur[f], as.map_a[nf] = map;
-			as.b[nf] = (const float4*)src_of[f]->values, as.map_b[nf] = src_of[f]->idx;
-			as.dst[nf] = (float4*)shell.cur[f];
-		}
-		HNS_TRY_RC(add_fields(as, nf, 1, n_new, st));
-	}
-	HNS_HIP(hipEventRecord(s->rev[4], st));
-	int dup_h = 0;
-	std::vector<int> src_dup_h(srcs.size(), 0);
-	HNS_HIP(hipMemcpyAsync(&dup_h, dup, 4, hipMemcpyDeviceToHost, st));
-	if (!srcs.empty()) HNS_HIP(hipMemcpyAsync(src_dup_h.data(), src_dup, 4 * srcs.size(), hipMemcpyDeviceToHost, st));
-	HNS_HIP(hipStreamSynchronize(st));
-	if (dup_h) {
-		set_error("%s: duplicate SDF leaf origin", who);
-		return HNS_ERR_TOPOLOGY;
-	}
-	for (size_t i = 0; i < srcs.size(); ++i)
-		if (src_dup_h[i]) {
-			set_error("%s: source %zu ('%s'): duplicate leaf origin", who, i, srcs[i].s->name ? srcs[i].s->name : "(null)");
-			return HNS_ERR_TOPOLOGY;
-		}
-
-	// ---- the sim moves onto the new grid ----
-	size_t fields_bytes = 0, masks_bytes = 0;
-	for (const auto& h : scratch.held) {
-		if (h.first == p_fields) fields_bytes = h.second;
-		if (h.first == p_masks) masks_bytes = h.second;
-	}
-	scratch.keep(p_fields);
-	scratch.keep(p_masks);
-	scratch.held.emplace_back(s->arena, s->arena_bytes);  // the old state goes back to the pool with the scratch
-	if (s->d_masks) scratch.held.emplace_back(s->d_masks, s->masks_bytes);
-	s->arena = p_fields, s->arena_bytes = fields_bytes;
-	hns_sim_layout(s, p_fields, n_new * 512u);
-	s->d_masks = (unsigned char*)p_masks, s->masks_bytes = masks_bytes;
-	s->grid = ng.g;
-	ng.g = nullptr;
-	s->sig_vel = s->dig_vel = 0;
-	std::fill(s->sig_cur.begin(), s->sig_cur.end(), 0);
-	std::fill(s->dig_cur.begin(), s->dig_cur.end(), 0);
-	s->regrid_timed = true;
-	*out = s->grid;
-	return HNS_OK;
+	HNS_TRY(r.candidates());
+	HNS_TRY(r.order());
+	HNS_TRY(r.masks());
+	HNS_TRY(r.fields());
+	return r.commit(out);
 }
 
 // ---- hns_sim_deactivate: the end of a frame, one wave per leaf ----
@@ -806,7 +785,7 @@ extern "C" int hns_sim_set_active_masks(hns_sim* s, const unsigned char* masks, 
 	if (!s->d_masks) {
 		void* p = nullptr;
 		size_t got = 0;
-		HNS_TRY_RC(hns_arena_get(64 * n_leaves, s->device, &p, &got));
+		HNS_TRY(hns_arena_get(64 * n_leaves, s->device, &p, &got));
 		s->d_masks = (unsigned char*)p, s->masks_bytes = got;
 	}
 	HNS_HIP(hipMemcpyAsync(s->d_masks, masks, 64 * n_leaves, hipMemcpyHostToDevice, (hipStream_t)stream));
@@ -837,7 +816,8 @@ hns_grid* regrid_entry(hns_sim* s, int padding_voxels, const hns_leaf_source* so
 		set_error("%s: the sim belongs to a grid's cook cache", who);
 		rc = HNS_ERR_INVALID_ARGUMENT;
 	} else {
-		rc = regrid(s, padding_voxels, sources, n_sources, sdf_origins, n_sdf, sdf_masks, sdf_values, (hipStream_t)stream, &g, who);
+		const hns_leaf_source sdf{"collision_sdf", 1, sdf_origins, n_sdf, sdf_masks, sdf_values};
+		rc = regrid(s, padding_voxels, sources, n_sources, sdf, (hipStream_t)stream, &g, who);
 	}
 	if (err) *err = rc;
 	return rc == HNS_OK ? g : nullptr;
@@ -869,18 +849,18 @@ extern "C" int hns_sim_deactivate(hns_sim* s, const hns_activity_field* fields, 
 	if (!s || !s->grid) return fail(HNS_ERR_INVALID_ARGUMENT, "hns_sim_deactivate: null sim");
 	if (s->cached) return fail(HNS_ERR_INVALID_ARGUMENT, "hns_sim_deactivate: the sim belongs to a grid's cook cache");
 	std::vector<int> field_of;
-	HNS_TRY_RC(check_activity_fields(s, fields, n_fields, who, &field_of));
+	HNS_TRY(check_activity_fields(s, fields, n_fields, who, &field_of));
 	const uint64_t n_leaves = s->n / 512u;
 	if (!n_leaves) {
 		if (counts) counts[0] = counts[1] = 0;
 		return HNS_OK;
 	}
-	CurrentDevice on(s->device);
+	DeviceScope on(s->device);
 	const hipStream_t st = (hipStream_t)stream;
 	if (!s->d_act) {  // the packed count, then a row per field the sim could list (its float fields and the velocity)
 		void* p = nullptr;
 		size_t got = 0;
-		HNS_TRY_RC(hns_arena_get(16 + sizeof(ActField) * (s->names.size() + 1), s->device, &p, &got));
+		HNS_TRY(hns_arena_get(16 + sizeof(ActField) * (s->names.size() + 1), s->device, &p, &got));
 		s->d_act = p, s->act_bytes = got;
 	}
 	unsigned long long* d_count = (unsigned long long*)s->d_act;
@@ -889,7 +869,7 @@ extern "C" int hns_sim_deactivate(hns_sim* s, const hns_activity_field* fields, 
 	size_t masks_bytes = s->masks_bytes;
 	if (!masks) {  // all active until now: the kernel reads no masks and writes the first ones
 		void* p = nullptr;
-		HNS_TRY_RC(hns_arena_get(64 * n_leaves, s->device, &p, &masks_bytes));
+		HNS_TRY(hns_arena_get(64 * n_leaves, s->device, &p, &masks_bytes));
 		masks = (unsigned char*)p;
 	}
 	int rc = HNS_OK;

@@ -123,6 +123,25 @@ def unpack_leaves(packed, leaf_ids, field, ncomp: int = 1):
     return field
 
 
+def _leaf_source(entry, leaves, need, keep, ncomp: Optional[int] = None) -> None:
+    """Fills the hns_leaf_source `entry` (all but its name) from (origins, masks or None, values) of the collision SDF or a regrid source: the
+    arrays contiguous, their sizes checked against the origins, kept alive in `keep`. ncomp None: 3 for values of shape (n * 512, 3), else 1.
+    need: how the values and the masks refusals begin."""
+    so, sm, sv = leaves
+    o = np.ascontiguousarray(so, dtype=np.int32).reshape(-1, 3)
+    v = np.ascontiguousarray(sv, dtype=np.float32)
+    nc = ncomp or (3 if (v.ndim == 2 and v.shape[1] == 3) else 1)
+    if v.size != len(o) * 512 * nc:
+        per_leaf = "512" if ncomp else f"512 x {nc}"
+        raise ValueError(f"{need[0]} {len(o)} x {per_leaf} floats, got {v.size}")
+    m = None if sm is None else np.ascontiguousarray(sm, dtype=np.uint8).reshape(-1)
+    if m is not None and m.size != len(o) * 64:
+        raise ValueError(f"{need[1]} {len(o)} x 64 bytes, got {m.size}")
+    keep += [o, m, v]
+    entry.ncomp, entry.origins, entry.n_leaves, entry.values = nc, o.ctypes.data, len(o), v.ctypes.data
+    entry.masks = None if m is None else m.ctypes.data
+
+
 class Sim:
     """Device-resident simulation state (``hns_sim``): upload once, run many substeps."""
 
@@ -205,41 +224,19 @@ class Sim:
         sources = {name: (origins, masks or None, values)}: this frame's sources, added into the fields first (``hns_sim_regrid_sourced``); values
         of shape (n * 512, 3) make the source the velocity's, anything else holds 512 floats per leaf of a float field.
         Returns the new grid and makes it ``self.grid``; the old handle is untouched and still the caller's."""
-        o = m = v = None
-        n_sdf = 0
+        err, keep = C.c_int(0), []
+        sdf_e = _lib.hns_leaf_source()  # (NULL arrays, no leaves: no SDF)
         if sdf is not None:
-            so, sm, sv = sdf
-            o = np.ascontiguousarray(so, dtype=np.int32).reshape(-1, 3)
-            n_sdf = len(o)
-            v = np.ascontiguousarray(sv, dtype=np.float32).reshape(-1)
-            if v.size != n_sdf * 512:
-                raise ValueError(f"sdf values: need {n_sdf} x 512 floats, got {v.size}")
-            if sm is not None:
-                m = np.ascontiguousarray(sm, dtype=np.uint8).reshape(-1)
-                if m.size != n_sdf * 64:
-                    raise ValueError(f"sdf masks: need {n_sdf} x 64 bytes, got {m.size}")
-        err = C.c_int(0)
-        sdf_args = (None if o is None else o.ctypes.data, n_sdf, None if m is None else m.ctypes.data, None if v is None else v.ctypes.data)
+            _leaf_source(sdf_e, sdf, ("sdf values: need", "sdf masks: need"), keep, 1)
+        sdf_args = (sdf_e.origins, sdf_e.n_leaves, sdf_e.masks, sdf_e.values)
         if sources is None:
             ptr = lib.hns_sim_regrid(self._ptr, int(padding), *sdf_args, stream, C.byref(err))
         else:
             arr = (_lib.hns_leaf_source * max(1, len(sources)))()
-            keep = []
-            for i, (name, (so, sm, sv)) in enumerate(sources.items()):
-                so = np.ascontiguousarray(so, dtype=np.int32).reshape(-1, 3)
-                sv = np.ascontiguousarray(sv, dtype=np.float32)
-                nc = 3 if (sv.ndim == 2 and sv.shape[1] == 3) else 1
-                if sv.size != len(so) * 512 * nc:
-                    raise ValueError(f"source {name}: need {len(so)} x 512 x {nc} floats, got {sv.size}")
-                if sm is not None:
-                    sm = np.ascontiguousarray(sm, dtype=np.uint8).reshape(-1)
-                    if sm.size != len(so) * 64:
-                        raise ValueError(f"source {name}: masks need {len(so)} x 64 bytes, got {sm.size}")
-                b = name.encode()
-                keep += [b, so, sm, sv]
-                arr[i].name, arr[i].ncomp, arr[i].n_leaves = b, nc, len(so)
-                arr[i].origins, arr[i].values = so.ctypes.data, sv.ctypes.data
-                arr[i].masks = None if sm is None else sm.ctypes.data
+            for i, (name, leaves) in enumerate(sources.items()):
+                keep.append(name.encode())
+                arr[i].name = keep[-1]
+                _leaf_source(arr[i], leaves, (f"source {name}: need", f"source {name}: masks need"), keep)
             ptr = lib.hns_sim_regrid_sourced(self._ptr, int(padding), arr, len(sources), *sdf_args, stream, C.byref(err))
         if not ptr:
             _raise(err.value if err.value < 0 else _lib.HNS_ERR_RUNTIME)

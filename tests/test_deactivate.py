@@ -5,16 +5,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from frame_cases import pack, unpack
 from hnanosolver_amd import _lib, leafio
-
-
-def pack(bits: np.ndarray) -> np.ndarray:
-    """(n, 512) bool in x<<6|y<<3|z order -> (n, 64) bytes: byte x*8+y, bit z"""
-    return np.packbits(bits.reshape(len(bits), 64, 8), axis=2, bitorder="little").reshape(len(bits), 64)
-
-
-def unpack(masks: np.ndarray) -> np.ndarray:
-    return np.unpackbits(masks.reshape(len(masks), 64, 1), axis=2, bitorder="little").reshape(len(masks), 512).astype(bool)
 
 
 def brute_force(masks, n, fields, velocity):

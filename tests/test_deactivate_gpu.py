@@ -7,8 +7,8 @@ import numpy as np
 import pytest
 
 from hnanosolver_amd import _lib, api, fields, leafio
-from test_sources_gpu import (COMBUST, assert_same, download, emitter, host_chain, make_sim, make_sources, random_leaves, random_masks,
-                              sdf_source)
+from frame_cases import (COMBUST, assert_same, download, emitter, host_chain, make_sim, make_sources, random_leaves, random_masks,
+                         sdf_source)
 
 pytestmark = pytest.mark.gpu
 

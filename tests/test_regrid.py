@@ -3,18 +3,10 @@ dense brute force, the frame-to-frame growth it implies (SOP_HNanoSolver.cpp:186
 import numpy as np
 import pytest
 
+from frame_cases import pack, unpack
 from hnanosolver_amd import _lib, fields, leafio
 
 PADDINGS = [0, 1, 3, 7, 8, 9, 17]
-
-
-def pack(bits: np.ndarray) -> np.ndarray:
-    """(n, 512) bool in x<<6|y<<3|z order -> (n, 64) bytes: byte x*8+y, bit z"""
-    return np.packbits(bits.reshape(len(bits), 64, 8), axis=2, bitorder="little").reshape(len(bits), 64)
-
-
-def unpack(masks: np.ndarray) -> np.ndarray:
-    return np.unpackbits(masks.reshape(len(masks), 64, 1), axis=2, bitorder="little").reshape(len(masks), 512).astype(bool)
 
 
 def brute_force(origins: np.ndarray, masks: np.ndarray, p: int):

@@ -4,92 +4,10 @@ that follow."""
 import numpy as np
 import pytest
 
-from hnanosolver_amd import _lib, api, device, fields, leafio
+from frame_cases import COMBUST, assert_same, download, host_chain, make_sim, pack, random_leaves, random_masks, random_state, sdf_source
+from hnanosolver_amd import _lib, api, fields
 
 pytestmark = pytest.mark.gpu
-
-COMBUST = ["density", "fuel", "waste", "temperature", "flame"]
-
-
-def pack(bits):
-    return np.packbits(bits.reshape(len(bits), 64, 8), axis=2, bitorder="little").reshape(len(bits), 64)
-
-
-def random_leaves(seed, n=30, span=4):
-    rng = np.random.default_rng(seed)
-    o = np.unique(rng.integers(-span, span, size=(n, 3)), axis=0).astype(np.int32) * 8
-    o = np.concatenate([o, np.array([[8 * 3 * span, -8 * 2 * span, 8]], dtype=np.int32)])  # a lone leaf
-    return o[rng.permutation(len(o))]  # caller order, not OpenVDB order
-
-
-def random_masks(seed, n):
-    rng = np.random.default_rng(seed)
-    bits = rng.random((n, 512)) < rng.choice([0.003, 0.05, 0.5, 1.0], size=(n, 1))
-    bits[: max(1, n // 8)] = False  # leaves without active voxels
-    bits[-1, 200] = True
-    return pack(bits)
-
-
-def random_state(seed, n_leaves, names):
-    rng = np.random.default_rng(seed)
-    st = {"vel": rng.standard_normal((n_leaves * 512, 3)).astype(np.float32)}
-    for n in names:
-        st[n] = rng.standard_normal(n_leaves * 512).astype(np.float32)
-    return st
-
-
-def make_sim(origins, names, state, masks=None, vs=1.0 / 32):
-    g = api.create_grid_from_leaves(origins, vs)
-    s = device.Sim(g, names)
-    s.upload(state)
-    if masks is not None:
-        s.set_active_masks(masks)
-    return g, s
-
-
-def download(sim, names):
-    n = sim.grid.voxel_count()
-    out = {"vel": np.empty((n, 3), dtype=np.float32)}
-    for k in names:
-        out[k] = np.empty(n, dtype=np.float32)
-    sim.download(out)
-    return out
-
-
-def host_chain(origins, masks, state, names, p, sdf=None):
-    """What a host caller does between two frames, from leafio's functions: -> (origins, masks, state)"""
-    dom, dm = leafio.dilate_leaf_masks(origins, p, masks)
-    if sdf is not None:
-        so, sm, sv = sdf
-        dom2 = leafio.union_leaves(dom, so)
-        m2 = np.zeros((len(dom2), 64), dtype=np.uint8)
-        idx = {tuple(o): i for i, o in enumerate(dom2.tolist())}
-        for o, m in zip(dom.tolist(), dm):
-            m2[idx[tuple(o)]] |= m
-        for i, o in enumerate(np.asarray(so).tolist()):
-            m2[idx[tuple(o)]] |= 0xFF if sm is None else sm[i]
-        dom, dm = dom2, m2
-    out = {"vel": leafio.gather_leaves(dom, origins, state["vel"], 3, leafio.FILL_ZERO)}
-    for n in names:
-        if n == "collision_sdf" and sdf is not None:
-            out[n] = leafio.gather_leaves(dom, sdf[0], sdf[2], 1, leafio.FILL_SDF)
-        else:
-            out[n] = leafio.gather_leaves(dom, origins, state[n], 1, leafio.FILL_SDF if n == "collision_sdf" else leafio.FILL_ZERO)
-    return dom, dm, out
-
-
-def assert_same(a, b, what=""):
-    for k in a:
-        assert a[k].view(np.uint32).tobytes() == b[k].view(np.uint32).tobytes(), f"{what}: field {k} differs"
-
-
-def sdf_source(seed, origins, n=6):
-    rng = np.random.default_rng(seed)
-    so = np.unique(np.concatenate([origins[:2], rng.integers(-8, 8, size=(n, 3)).astype(np.int32) * 8]), axis=0).astype(np.int32)
-    so = so[rng.permutation(len(so))]
-    sm = pack(rng.random((len(so), 512)) < 0.1)
-    sv = rng.standard_normal(len(so) * 512).astype(np.float32)
-    return so, sm, sv
 
 
 CASES = [("s1", ["density"], False), ("s5", COMBUST, False), ("s5sdf", COMBUST + ["collision_sdf"], False), ("s5sdf_src", COMBUST + ["collision_sdf"], True)]
@@ -106,7 +24,7 @@ def test_regrid_matches_the_host_chain(case, p):
     g, s = make_sim(o, names, st, m)
     sdf = sdf_source(seed + 3, o) if with_src else None
     ng = s.regrid(p, sdf)
-    dom, dm, want = host_chain(o, m, st, names, p, sdf)
+    dom, dm, want = host_chain(o, m, st, names, p, sdf=sdf)
     assert s.grid is ng and ng.ptr != g.ptr and g.leaf_count() == len(o)
     assert np.array_equal(ng.coords()[::512], dom), "leaf set / OpenVDB order"
     assert np.array_equal(s.active_masks(), dm)

@@ -3,16 +3,8 @@ and the bindings of the sourced regrid ABI."""
 import numpy as np
 import pytest
 
+from frame_cases import pack, unpack
 from hnanosolver_amd import _lib, fields, leafio
-
-
-def pack(bits: np.ndarray) -> np.ndarray:
-    """(n, 512) bool in x<<6|y<<3|z order -> (n, 64) bytes: byte x*8+y, bit z"""
-    return np.packbits(bits.reshape(len(bits), 64, 8), axis=2, bitorder="little").reshape(len(bits), 64)
-
-
-def unpack(masks: np.ndarray) -> np.ndarray:
-    return np.unpackbits(masks.reshape(len(masks), 64, 1), axis=2, bitorder="little").reshape(len(masks), 512).astype(bool)
 
 
 def brute_force(a, b, ncomp):
