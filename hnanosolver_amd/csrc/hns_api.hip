@@ -1,7 +1,7 @@
-// hns_api.hip -- the device-resident simulation state and the drop-in operators of
-// include/hns.h. The launch orders follow the reference's host drivers (reference src/Cuda/HNanoSolver.cu:150-356,
+// hns_api.hip -- host code only: the device-resident simulation state (hns_sim_*), its substep (Substep: core and full), the cook cache (make_sim) and the drop-in
+// operators of include/hns.h with the resident-feedback cook (Cook). The launch orders follow the reference's host drivers (reference src/Cuda/HNanoSolver.cu:150-356,
 // src/Cuda/PressureProjection.cu:43-66, src/Cuda/Advection.cu:76-91,148-155); what differs is that fields can stay
-// resident across substeps and that nothing is allocated inside a substep.
+// resident across substeps and that nothing is allocated inside a substep. The pool the memory comes from: hns_arena.hip.
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -13,15 +13,6 @@
 #include "hns_digest.hpp"
 
 using namespace hns;
-
-#define HNS_HIP(call)                                                                                  \
-	do {                                                                                               \
-		hipError_t e__ = (call);                                                                       \
-		if (e__ != hipSuccess) {                                                                       \
-			set_error("%s failed: %s (%s:%d)", #call, hipGetErrorString(e__), __FILE__, __LINE__);     \
-			return HNS_ERR_HIP;                                                                        \
-		}                                                                                              \
-	} while (0)
 
 // ---------------------------------------------------------------------------------------------------------------
 // grid: device tables
@@ -57,109 +48,19 @@ extern "C" int hns_device_count(void) {
 
 // (struct hns_sim: hns_internal.hpp -- hns_regrid.hip moves a sim onto a new grid)
 
-// ---- arena pool ------------------------------------------------------------------------------------------------
-// A sim's fields are slices of ONE device allocation, and allocations that are no longer needed go to a small
-// process-wide pool instead of back to the driver. The reference pays cudaMallocAsync x 15+ and the matching frees every
-// cook (HNanoSolver.cu:87-133,361-369); with separate hipMallocs here a cold cook at 256^3 spent 4.2 ms in hipFree
-// alone. A sparse simulation changes its topology nearly every frame, so "cold" is its normal cook: with the pool the
-// new grid's fields land in the previous grid's memory whenever that is large enough. hns_trim_memory() empties it.
-namespace {
-struct Arena {
-	void* p;
-	size_t bytes;
-	int device;
-};
-std::mutex g_pool_mutex;
-std::vector<Arena> g_pool;  // at most kPoolMax idle arenas
-constexpr size_t kPoolMax = 6;  // simulation states (GBs) and grid tables (MBs) share it; the smallest goes first
-
-int arena_get(size_t need, int device, Arena& out) {
-	{
-		std::lock_guard<std::mutex> lock(g_pool_mutex);
-		int best = -1;
-		for (size_t i = 0; i < g_pool.size(); ++i)
-			if (g_pool[i].device == device && g_pool[i].bytes >= need && g_pool[i].bytes <= 2 * need + (64u << 20) &&
-			    (best < 0 || g_pool[i].bytes < g_pool[(size_t)best].bytes))
-				best = (int)i;
-		if (best >= 0) {
-			out = g_pool[(size_t)best];
-			g_pool.erase(g_pool.begin() + best);
-			return HNS_OK;
-		}
-	}
-	out.bytes = need + need / 8;  // headroom: the next, slightly larger topology still fits
-	out.device = device;
-	DeviceScope scope(device);
-	if (hipMalloc(&out.p, out.bytes) != hipSuccess) {
-		(void)hipGetLastError();
-		std::vector<Arena> drop;  // out of memory with idle arenas around: release them and retry at the exact size
-		{
-			std::lock_guard<std::mutex> lock(g_pool_mutex);
-			drop.swap(g_pool);
-		}
-		for (Arena& a : drop) (void)hipFree(a.p);
-		out.bytes = need;
-		HNS_HIP(hipMalloc(&out.p, out.bytes));
-	}
-	return HNS_OK;
-}
-
-// The hipFree this pool replaces waits for the device; so does this: whoever draws the memory next may use it on any
-// stream without ordering itself after the previous owner's queued kernels and copies. Cooks are synchronous, so the
-// device is normally idle here and the wait costs microseconds.
-void arena_put(const Arena& a) {
-	if (!a.p) return;
-	DeviceScope scope(a.device);
-	(void)hipDeviceSynchronize();
-	Arena evict{nullptr, 0, -1};
-	{
-		std::lock_guard<std::mutex> lock(g_pool_mutex);
-		g_pool.push_back(a);
-		if (g_pool.size() > kPoolMax) {  // drop the smallest
-			size_t k = 0;
-			for (size_t i = 1; i < g_pool.size(); ++i)
-				if (g_pool[i].bytes < g_pool[k].bytes) k = i;
-			evict = g_pool[k];
-			g_pool.erase(g_pool.begin() + (long)k);
-		}
-	}
-	if (evict.p) (void)hipFree(evict.p);
-}
-}  // namespace
-
-extern "C" int hns_arena_get(size_t need, int device, void** p, size_t* bytes) {
-	Arena a{nullptr, 0, -1};
-	const int rc = arena_get(need, device, a);
-	*p = a.p;
-	*bytes = a.bytes;
-	return rc;
-}
-extern "C" void hns_arena_put(void* p, size_t bytes, int device) { arena_put(Arena{p, bytes, device}); }
-
-// Returns the idle pooled device memory to the driver.
-extern "C" int hns_trim_memory(void) {
-	std::vector<Arena> drop;
-	{
-		std::lock_guard<std::mutex> lock(g_pool_mutex);
-		drop.swap(g_pool);
-	}
-	for (Arena& a : drop) HNS_HIP(hipFree(a.p));
-	return HNS_OK;
-}
-
 extern "C" void hns_sim_destroy(hns_sim* s) {
 	if (!s) return;
-	for (hipEvent_t e : s->ev) (void)hipEventDestroy(e);
-	for (hipEvent_t e : s->sev) (void)hipEventDestroy(e);
+	s->solve_ev.destroy();
+	s->stage_ev.destroy();
 	for (hipEvent_t e : s->xev)
 		if (e) (void)hipEventDestroy(e);
 	for (hipEvent_t e : s->rev)
 		if (e) (void)hipEventDestroy(e);
 	if (s->xfer) (void)hipStreamDestroy(s->xfer);
 	if (s->h_dig) (void)hipHostFree(s->h_dig);
-	if (s->d_masks) arena_put(Arena{s->d_masks, s->masks_bytes, s->device});
-	if (s->d_act) arena_put(Arena{s->d_act, s->act_bytes, s->device});
-	arena_put(Arena{s->arena, s->arena_bytes, s->device});
+	hns_arena_put(s->d_masks, s->masks_bytes, s->device);
+	hns_arena_put(s->d_act, s->act_bytes, s->device);
+	hns_arena_put(s->arena, s->arena_bytes, s->device);
 	delete s;
 }
 
@@ -186,7 +87,7 @@ extern "C" int hns_grid_release_cache(hns_grid* g) {
 }
 
 static size_t sim_unit(uint64_t n) { return (sizeof(float) * (size_t)(n ? n : 1) + 255) & ~(size_t)255; }  // one float field, 256-byte aligned
-static bool sim_combust(const hns_sim* s) { return s->find("fuel") >= 0 && s->find("waste") >= 0 && s->find("temperature") >= 0 && s->find("flame") >= 0; }
+static bool sim_combust(const hns_sim* s) { return std::all_of(kCombustionFields, kCombustionFields + 4, [s](const char* n) { return s->find(n) >= 0; }); }
 static size_t sim_units(const hns_sim* s) { return 3 * 3 + 3 + 2 * s->names.size() + (sim_combust(s) ? 4 : 0); }  // vel, adv, tmp | div, p_a, p_b | cur, nxt per field | q4
 
 size_t hns_sim_arena_need(const hns_sim* s, uint64_t n) { return sim_unit(n) * sim_units(s) + 256; }  // (+ the 16 digest accumulators of hns_compute_sim_resident, CHECKED fields)
@@ -229,14 +130,14 @@ static hns_sim* sim_create(hns_grid* g, const char* const* float_names, int n_fl
 			s->names.push_back(float_names[i]);
 		}
 	}
-	if (rc == HNS_OK) {
-		Arena a{nullptr, 0, -1};
-		rc = arena_get(hns_sim_arena_need(s, s->n), s->device, a);
-		if (rc == HNS_OK) {
-			s->arena = a.p, s->arena_bytes = a.bytes;
-			hns_sim_layout(s, a.p, s->n);
-			if (zero && hipMemsetAsync(a.p, 0, (char*)s->d_dig - (char*)a.p, (hipStream_t)stream) != hipSuccess) rc = fail(HNS_ERR_HIP, "hns_sim_create: clearing the field memory failed");
-		}
+	s->handed_cur.resize(s->names.size());
+	void* arena = nullptr;
+	size_t bytes = 0;
+	if (rc == HNS_OK) rc = hns_arena_get(hns_sim_arena_need(s, s->n), s->device, &arena, &bytes);
+	if (rc == HNS_OK) {  // (s->arena stays null otherwise: hns_sim_destroy below hands it to the pool)
+		s->arena = arena, s->arena_bytes = bytes;
+		hns_sim_layout(s, s->arena, s->n);
+		if (zero && hipMemsetAsync(s->arena, 0, (char*)s->d_dig - (char*)s->arena, (hipStream_t)stream) != hipSuccess) rc = fail(HNS_ERR_HIP, "hns_sim_create: clearing the field memory failed");
 	}
 	if (rc != HNS_OK) {
 		hns_sim_destroy(s);
@@ -268,54 +169,53 @@ extern "C" hns_sim* hns_sim_create(hns_grid* g, const char* const* float_names, 
 	return s;
 }
 
+// The device buffer behind a field of hns_sim_upload / hns_sim_download, and its index for hns_sim::forget: ncomp 3 is the velocity, 1 a float field looked up by name.
+static int sim_field(hns_sim* s, const hns_field& f, const char* who, int* k, float** buf) {
+	if (f.ncomp == 3) {
+		*k = hns_sim::kVelocity, *buf = s->vel;
+		return HNS_OK;
+	}
+	if (f.ncomp != 1) {
+		set_error("%s: ncomp must be 1 or 3", who);
+		return HNS_ERR_INVALID_ARGUMENT;
+	}
+	*k = f.name ? s->find(f.name) : -1;
+	if (*k < 0) {
+		set_error("%s: no float field named '%s' in this sim", who, f.name ? f.name : "?");
+		return HNS_ERR_RUNTIME;
+	}
+	*buf = s->cur[*k];
+	return HNS_OK;
+}
+
 extern "C" int hns_sim_upload(hns_sim* s, const hns_field* fields, int n_fields, void* stream) {
 	if (!s || (n_fields > 0 && !fields)) return fail(HNS_ERR_INVALID_ARGUMENT, "hns_sim_upload: null argument");
-	hipStream_t st = (hipStream_t)stream;
 	for (int i = 0; i < n_fields; ++i) {
 		const hns_field& f = fields[i];
 		if (!f.host) {
 			set_error("hns_sim_upload: host pointer is null for block: %s", f.name ? f.name : "?");
 			return HNS_ERR_RUNTIME;
 		}
-		if (f.ncomp == 3) {
-			s->sig_vel = s->dig_vel = 0;
-			HNS_HIP(hipMemcpyAsync(s->vel, f.host, sizeof(float) * 3 * (size_t)s->n, hipMemcpyHostToDevice, st));
-		} else if (f.ncomp == 1) {
-			const int k = f.name ? s->find(f.name) : -1;
-			if (k < 0) {
-				set_error("hns_sim_upload: no float field named '%s' in this sim", f.name ? f.name : "?");
-				return HNS_ERR_RUNTIME;
-			}
-			if ((size_t)k < s->sig_cur.size()) s->sig_cur[(size_t)k] = 0;
-			if ((size_t)k < s->dig_cur.size()) s->dig_cur[(size_t)k] = 0;
-			HNS_HIP(hipMemcpyAsync(s->cur[k], f.host, sizeof(float) * (size_t)s->n, hipMemcpyHostToDevice, st));
-		} else {
-			return fail(HNS_ERR_INVALID_ARGUMENT, "hns_sim_upload: ncomp must be 1 or 3");
-		}
+		int k;
+		float* buf;
+		HNS_TRY(sim_field(s, f, "hns_sim_upload", &k, &buf));
+		s->forget(k);
+		HNS_HIP(hipMemcpyAsync(buf, f.host, sizeof(float) * (size_t)f.ncomp * (size_t)s->n, hipMemcpyHostToDevice, (hipStream_t)stream));
 	}
 	return HNS_OK;
 }
 
 extern "C" int hns_sim_download(hns_sim* s, hns_field* fields, int n_fields, void* stream) {
 	if (!s || (n_fields > 0 && !fields)) return fail(HNS_ERR_INVALID_ARGUMENT, "hns_sim_download: null argument");
-	hipStream_t st = (hipStream_t)stream;
 	for (int i = 0; i < n_fields; ++i) {
 		hns_field& f = fields[i];
 		if (!f.host) return fail(HNS_ERR_RUNTIME, "hns_sim_download: null host pointer");
-		if (f.ncomp == 3) {
-			HNS_HIP(hipMemcpyAsync(f.host, s->vel, sizeof(float) * 3 * (size_t)s->n, hipMemcpyDeviceToHost, st));
-		} else if (f.ncomp == 1) {
-			const int k = f.name ? s->find(f.name) : -1;
-			if (k < 0) {
-				set_error("hns_sim_download: no float field named '%s' in this sim", f.name ? f.name : "?");
-				return HNS_ERR_RUNTIME;
-			}
-			HNS_HIP(hipMemcpyAsync(f.host, s->cur[k], sizeof(float) * (size_t)s->n, hipMemcpyDeviceToHost, st));
-		} else {
-			return fail(HNS_ERR_INVALID_ARGUMENT, "hns_sim_download: ncomp must be 1 or 3");
-		}
+		int k;
+		float* buf;
+		HNS_TRY(sim_field(s, f, "hns_sim_download", &k, &buf));
+		HNS_HIP(hipMemcpyAsync(f.host, buf, sizeof(float) * (size_t)f.ncomp * (size_t)s->n, hipMemcpyDeviceToHost, (hipStream_t)stream));
 	}
-	HNS_HIP(hipStreamSynchronize(st));
+	HNS_HIP(hipStreamSynchronize((hipStream_t)stream));
 	return HNS_OK;
 }
 
@@ -338,12 +238,12 @@ static int validate_step(float voxel_size, float dt, int64_t iterations, bool ne
 // the pressure hot loop: p = 0, `iterations` x (red, black); HNanoSolver.cu:256-272 / PressureProjection.cu:51-60
 static int sim_pressure(hns_sim* s, int iterations, float voxel_size, float omega, void* stream) {
 	int in_b = 0;  // never warm-started (HNanoSolver.cu:113): the solve starts from p = 0, which the first sweep knows without reading p_a
-	const bool timed = s->timing && s->ev_used + 2 <= s->ev.size();
-	if (timed) HNS_HIP(hipEventRecord(s->ev[s->ev_used], (hipStream_t)stream));
+	hipEvent_t* timed = s->solve_ev.current();
+	if (timed) HNS_HIP(hipEventRecord(timed[0], (hipStream_t)stream));
 	HNS_TRY(hns_rbgs_iterate(s->grid, s->div, s->p_a, s->p_b, voxel_size, omega, iterations, &in_b, stream, true));
 	if (timed) {
-		HNS_HIP(hipEventRecord(s->ev[s->ev_used + 1], (hipStream_t)stream));
-		s->ev_used += 2;
+		HNS_HIP(hipEventRecord(timed[1], (hipStream_t)stream));
+		s->solve_ev.advance();
 		s->timed_launches += iterations;
 	}
 	s->p_result = in_b ? s->p_b : s->p_a;
@@ -364,59 +264,33 @@ extern "C" int hns_sim_pressure_solve(hns_sim* s, int iterations, float voxel_si
 // Bracket every following pressure loop (up to max_solves of them) with a hipEvent pair on its launch stream.
 extern "C" int hns_sim_timing(hns_sim* s, int max_solves) {
 	if (!s || max_solves < 0) return fail(HNS_ERR_INVALID_ARGUMENT, "hns_sim_timing: bad arguments");
-	while (s->ev.size() < (size_t)max_solves * 2) {
-		hipEvent_t e;
-		HNS_HIP(hipEventCreate(&e));
-		s->ev.push_back(e);
-	}
-	s->timing = max_solves > 0;
-	s->ev_used = 0;
 	s->timed_launches = 0;
-	return HNS_OK;
+	return s->solve_ev.reset(max_solves);
 }
 
-// Bracket the five stages of the next max_substeps hns_sim_core_substep calls (six events per substep: a few microseconds
+// Bracket the five stages of the next max_substeps substeps (six events per substep: a few microseconds
 // each on the launch stream, which is why this is a switch of its own and not part of hns_sim_timing).
 extern "C" int hns_sim_stage_timing(hns_sim* s, int max_substeps) {
 	if (!s || max_substeps < 0) return fail(HNS_ERR_INVALID_ARGUMENT, "hns_sim_stage_timing: bad arguments");
-	while (s->sev.size() < (size_t)max_substeps * 6) {
-		hipEvent_t e;
-		HNS_HIP(hipEventCreate(&e));
-		s->sev.push_back(e);
-	}
-	s->stage_timing = max_substeps > 0;
-	s->sev_used = 0;
-	return HNS_OK;
+	return s->stage_ev.reset(max_substeps);
 }
 
-// Per-stage device time of the core substeps run since hns_sim_stage_timing(): ms5 = {advect_vector, divergence, pressure loop,
-// gradient subtraction, advect_scalars}, summed over `*substeps` substeps; events sit on the launch stream.
+// Per-stage device time of the substeps run since hns_sim_stage_timing(): ms5 = {advect_vector, divergence, pressure loop,
+// gradient subtraction, advect_scalars} (what the full substep adds to each: Substep), summed over `*substeps` substeps; events sit on the launch stream.
 extern "C" int hns_sim_stage_times(hns_sim* s, float* ms5, long long* substeps) {
 	if (!s || !ms5 || !substeps) return fail(HNS_ERR_INVALID_ARGUMENT, "hns_sim_stage_times: null argument");
-	double tot[5] = {0, 0, 0, 0, 0};
-	for (size_t i = 0; i + 5 < s->sev_used; i += 6) {
-		HNS_HIP(hipEventSynchronize(s->sev[i + 5]));
-		for (int k = 0; k < 5; ++k) {
-			float ms = 0.0f;
-			HNS_HIP(hipEventElapsedTime(&ms, s->sev[i + k], s->sev[i + k + 1]));
-			tot[k] += ms;
-		}
-	}
+	double tot[5];
+	HNS_TRY(s->stage_ev.elapsed(tot));
 	for (int k = 0; k < 5; ++k) ms5[k] = (float)tot[k];
-	*substeps = (long long)(s->sev_used / 6);
+	*substeps = (long long)s->stage_ev.used;
 	return HNS_OK;
 }
 
 // Sum of the bracketed pressure-loop times since hns_sim_timing() and the number of fused-iteration launches inside.
 extern "C" int hns_sim_pressure_time(hns_sim* s, float* total_ms, long long* launches) {
 	if (!s || !total_ms || !launches) return fail(HNS_ERR_INVALID_ARGUMENT, "hns_sim_pressure_time: null argument");
-	double tot = 0.0;
-	for (size_t i = 0; i + 1 < s->ev_used; i += 2) {
-		HNS_HIP(hipEventSynchronize(s->ev[i + 1]));
-		float ms = 0.0f;
-		HNS_HIP(hipEventElapsedTime(&ms, s->ev[i], s->ev[i + 1]));
-		tot += ms;
-	}
+	double tot;
+	HNS_TRY(s->solve_ev.elapsed(&tot));
 	*total_ms = (float)tot;
 	*launches = s->timed_launches;
 	return HNS_OK;
@@ -443,6 +317,8 @@ static int sim_advect_scalars(hns_sim* s, const float* sdf, bool coll, float dt,
 //   part A  needs velocity (+ collision_sdf)      collision, advect_vector, vorticity
 //   part B  needs fuel/waste/temperature/flame     divergence, combustion, buoyancy, pressure solve, gradient subtraction, collision
 //   part C  needs every advected float field       advect_scalars
+// The core substep (hns_sim_core_substep; `params` null) is the same sequence without its optional parts -- no collision, no vorticity, no combustion and buoyancy, never
+// fused -- as Step::full() tells the two apart in the partitioned substep (hns_dist_substep.hip). It asks nothing of the sim's float fields.
 // Round 6: without a collision field (and while a 16-byte-per-voxel array stays 32-bit addressable) part B opens with ONE launch for divergence + combustion +
 // buoyancy (hns_divergence_combust_buoyancy: 60 B/voxel instead of 16 + 40 + 28) that leaves the four combustion fields as one 16-byte element per voxel in s->q4, and
 // part C gathers those four from there (hns_advect_scalars_q4: a corner tap of the four is one gather, not four). Same expressions in the same order per voxel:
@@ -452,12 +328,13 @@ struct Substep {
 	hns_sim* s;
 	int iterations;
 	float dt, voxel_size, inv_dx;
-	const hns_combustion_params* params;
+	const hns_combustion_params* params;  // null: the core substep
 	int ci[4];
-	bool coll, fused;
-	const float* sdf;
+	bool coll = false, fused = false;
+	const float* sdf = nullptr;
 	void* stream;
 	hipEvent_t* stage_events = nullptr;  // six events of hns_sim_stage_timing, or null
+	bool full() const { return params != nullptr; }
 	int mark(int k) {
 		if (stage_events) HNS_HIP(hipEventRecord(stage_events[k], (hipStream_t)stream));
 		return HNS_OK;
@@ -471,12 +348,12 @@ struct Substep {
 		inv_dx = 1.0f / vs;
 		params = prm;
 		stream = st;
+		if (!full()) return HNS_OK;
 		if (s->names.empty()) return fail(HNS_ERR_RUNTIME, "No float blocks found in input data.");  // :61-63
-		const char* required[4] = {"fuel", "waste", "temperature", "flame"};                          // :193-201
-		for (int c = 0; c < 4; ++c) {
-			ci[c] = s->find(required[c]);
+		for (int c = 0; c < 4; ++c) {                                                                 // :193-201
+			ci[c] = s->find(kCombustionFields[c]);
 			if (ci[c] < 0) {
-				set_error("Missing required input field for combustion: %s", required[c]);
+				set_error("Missing required input field for combustion: %s", kCombustionFields[c]);
 				return HNS_ERR_RUNTIME;
 			}
 		}
@@ -495,7 +372,7 @@ struct Substep {
 		HNS_TRY(mark(0));
 		if (coll) HNS_TRY(hns_dev_enforce_collision_boundaries(g, s->vel, sdf, voxel_size, stream));  // :153-157
 		HNS_TRY(hns_dev_advect_vector(g, s->vel, s->adv, sdf, coll, dt, inv_dx, stream));  // :162-170
-		if ((int)params->factorScale != 0) {  // :172-176. With (int)factorScale == 0 every vorticity-magnitude tap collapses onto the centre, the
+		if (full() && (int)params->factorScale != 0) {  // :172-176. With (int)factorScale == 0 every vorticity-magnitude tap collapses onto the centre, the
 			// gradient is 0, N = 0/(0+1e-5) = 0 and the kernel writes u + dt*(scale*0) = u: a bit-exact copy, skipped.
 			HNS_TRY(hns_dev_vorticity_confinement(g, s->adv, s->tmp, dt, inv_dx,
 			                                      params->vorticityScale, params->factorScale, stream));
@@ -512,11 +389,13 @@ struct Substep {
 			std::swap(s->adv, s->tmp);
 		} else {
 			HNS_TRY(hns_dev_divergence(g, s->adv, s->div, inv_dx, stream));  // :181-188
-			HNS_TRY(hns_dev_combustion_oxygen(s->cur[ci[0]], s->cur[ci[1]], s->cur[ci[2]], s->div, s->cur[ci[3]], s->nxt[ci[0]], s->nxt[ci[1]],
-			                                  s->nxt[ci[2]], s->nxt[ci[3]], params->temperatureRelease, params->expansionRate, s->n, stream));  // :211-221
-			HNS_TRY(hns_dev_temperature_buoyancy(s->adv, s->nxt[ci[2]], s->adv, dt, params->ambientTemp, params->buoyancyStrength, s->n,
-			                                     stream));  // :226-234 (temperature AFTER combustion)
-			for (int c = 0; c < 4; ++c) std::swap(s->cur[ci[c]], s->nxt[ci[c]]);  // :239-246
+			if (full()) {
+				HNS_TRY(hns_dev_combustion_oxygen(s->cur[ci[0]], s->cur[ci[1]], s->cur[ci[2]], s->div, s->cur[ci[3]], s->nxt[ci[0]], s->nxt[ci[1]],
+				                                  s->nxt[ci[2]], s->nxt[ci[3]], params->temperatureRelease, params->expansionRate, s->n, stream));  // :211-221
+				HNS_TRY(hns_dev_temperature_buoyancy(s->adv, s->nxt[ci[2]], s->adv, dt, params->ambientTemp, params->buoyancyStrength, s->n,
+				                                     stream));  // :226-234 (temperature AFTER combustion)
+				for (int c = 0; c < 4; ++c) std::swap(s->cur[ci[c]], s->nxt[ci[c]]);  // :239-246
+			}
 		}
 		HNS_TRY(mark(2));
 		HNS_TRY(sim_pressure(s, iterations, voxel_size, omega_compute(voxel_size), stream));  // :256-272
@@ -543,54 +422,38 @@ struct Substep {
 			if (s->names[i] != "collision_sdf") std::swap(s->cur[i], s->nxt[i]);
 		return HNS_OK;
 	}
+	// The whole substep on one stream. hns_sim_stage_timing brackets five stages, the same for the core and the full substep -- {collision + advect_vector + vorticity,
+	// divergence + combustion + buoyancy (one launch when fused), pressure loop, gradient subtraction + collision, advect_scalars}: mark(0..4) open them, mark(5) closes the last.
+	int run() {
+		stage_events = s->stage_ev.current();
+		HNS_TRY(part_a());
+		HNS_TRY(part_b());
+		HNS_TRY(part_c());
+		HNS_TRY(mark(5));
+		if (stage_events) s->stage_ev.advance();
+		return HNS_OK;
+	}
 };
+
+// hns_sim_substep, and with `params` null hns_sim_core_substep
+int sim_substep(hns_sim* s, int iterations, float dt, float voxel_size, const hns_combustion_params* params, int has_collision, void* stream) {
+	HNS_TRY(validate_step(voxel_size, dt, iterations, true));
+	if (s->n == 0) return HNS_OK;  // HNanoSolver.cu:26-28
+	Substep step;
+	HNS_TRY(step.prepare(s, iterations, dt, voxel_size, params, has_collision, stream));
+	return step.run();
+}
 }  // namespace
 
 extern "C" int hns_sim_substep(hns_sim* s, int iterations, float dt, float voxel_size, const hns_combustion_params* params, int has_collision,
                                void* stream) {
 	if (!s || !params) return fail(HNS_ERR_INVALID_ARGUMENT, "hns_sim_substep: null argument");
-	HNS_TRY(validate_step(voxel_size, dt, iterations, true));
-	if (s->n == 0) return HNS_OK;  // HNanoSolver.cu:26-28
-	Substep step;
-	HNS_TRY(step.prepare(s, iterations, dt, voxel_size, params, has_collision, stream));
-	// hns_sim_stage_timing: the same five brackets as the core substep -- {collision + advect_vector + vorticity, divergence + combustion + buoyancy (one launch when
-	// fused), pressure loop, gradient subtraction + collision, advect_scalars}
-	const bool staged = s->stage_timing && s->sev_used + 6 <= s->sev.size();
-	step.stage_events = staged ? &s->sev[s->sev_used] : nullptr;
-	HNS_TRY(step.part_a());
-	HNS_TRY(step.part_b());
-	HNS_TRY(step.part_c());
-	if (staged) {
-		HNS_HIP(hipEventRecord(step.stage_events[5], (hipStream_t)stream));
-		s->sev_used += 6;
-	}
-	return HNS_OK;
+	return sim_substep(s, iterations, dt, voxel_size, params, has_collision, stream);
 }
 
 extern "C" int hns_sim_core_substep(hns_sim* s, int iterations, float dt, float voxel_size, void* stream) {
 	if (!s) return fail(HNS_ERR_INVALID_ARGUMENT, "hns_sim_core_substep: null sim");
-	HNS_TRY(validate_step(voxel_size, dt, iterations, true));
-	if (s->n == 0) return HNS_OK;
-	const float inv_dx = 1.0f / voxel_size;
-	hns_grid* g = s->grid;
-	const bool staged = s->stage_timing && s->sev_used + 6 <= s->sev.size();
-	hipEvent_t* se = staged ? &s->sev[s->sev_used] : nullptr;
-	if (staged) HNS_HIP(hipEventRecord(se[0], (hipStream_t)stream));
-	HNS_TRY(hns_dev_advect_vector(g, s->vel, s->adv, nullptr, 0, dt, inv_dx, stream));
-	if (staged) HNS_HIP(hipEventRecord(se[1], (hipStream_t)stream));
-	HNS_TRY(hns_dev_divergence(g, s->adv, s->div, inv_dx, stream));
-	if (staged) HNS_HIP(hipEventRecord(se[2], (hipStream_t)stream));
-	HNS_TRY(sim_pressure(s, iterations, voxel_size, omega_compute(voxel_size), stream));
-	if (staged) HNS_HIP(hipEventRecord(se[3], (hipStream_t)stream));
-	HNS_TRY(hns_dev_subtract_pressure_gradient(g, s->adv, s->p_result, s->vel, nullptr, 0,
-	                                           inv_dx, stream));
-	if (staged) HNS_HIP(hipEventRecord(se[4], (hipStream_t)stream));
-	HNS_TRY(sim_advect_scalars(s, nullptr, false, dt, inv_dx, stream));
-	if (staged) {
-		HNS_HIP(hipEventRecord(se[5], (hipStream_t)stream));
-		s->sev_used += 6;
-	}
-	return HNS_OK;
+	return sim_substep(s, iterations, dt, voxel_size, nullptr, 0, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -646,9 +509,9 @@ struct SimGuard {
 	}
 };
 
-int make_sim(hns_grid* g, const FieldSplit& fs, SimGuard& guard, void* stream) {
+int make_sim(hns_grid* g, const std::vector<hns_field*>& floats, SimGuard& guard, void* stream) {
 	std::vector<const char*> names;
-	for (hns_field* f : fs.floats) names.push_back(f->name);
+	for (hns_field* f : floats) names.push_back(f->name);
 	const bool use_cache = options().cook_cache.load() != 0;
 	if (use_cache) {
 		std::lock_guard<std::mutex> lock(g->host_mutex);
@@ -697,6 +560,29 @@ int make_sim(hns_grid* g, const FieldSplit& fs, SimGuard& guard, void* stream) {
 		g->sim_cache.push_back(guard.s);
 	}
 	return HNS_OK;
+}
+
+// How the four velocity-driven operators open: the grid, the field list, exactly one Vec3f block. What only one of them checks follows in that operator.
+int operator_fields(hns_grid* g, hns_field* fields, int n_fields, const char* who, FieldSplit& fs) {
+	if (!g) {
+		set_error("%s: null grid", who);
+		return HNS_ERR_INVALID_ARGUMENT;
+	}
+	HNS_TRY(split_fields(fields, n_fields, fs, who));
+	if (fs.n_vec3 != 1) return fail(HNS_ERR_RUNTIME, "Expected exactly one Vec3f block (velocity)");  // Advection.cu:19-21,119-121, PressureProjection.cu:14-17,85-88
+	return HNS_OK;
+}
+
+// ... and how they get to the device once their checks have passed: a sim borrowed for the float blocks `floats` (none: the velocity alone), with `up` uploaded. An empty
+// grid leaves guard.s null: the operator has nothing to do.
+int operator_sim(hns_grid* g, const char* who, const std::vector<hns_field*>& floats, const hns_field* up, int n_up, SimGuard& guard, void* stream) {
+	if (hns_grid_voxel_count(g) == 0) return HNS_OK;
+	if (!g->on_device) {
+		set_error("%s: grid has no device tables (there is no CPU fallback)", who);
+		return HNS_ERR_NO_DEVICE;
+	}
+	HNS_TRY(make_sim(g, floats, guard, stream));
+	return hns_sim_upload(guard.s, up, n_up, stream);
 }
 }  // namespace
 
@@ -770,47 +656,50 @@ static uint64_t host_digest(const float* a, size_t count) {  // hns_digest.hpp: 
 // `resident` (hns_compute_sim_resident): per field of `fields` (by position), non-zero = the caller vouches that the host array still
 // holds what the previous hns_compute_sim on this grid handed back for the block of that name. The field is then not uploaded -- if
 // the device state lent to this call is the one that produced it and the array's signature still matches; uploaded as usual otherwise.
-static int compute_sim_pipelined(hns_sim* s, FieldSplit& fs, int iterations, float dt, float voxel_size, const hns_combustion_params* params,
-                                 int has_collision, void* stream, const std::vector<std::pair<const hns_field*, int>>& resident, int* skipped) {
-	Substep step;
-	const size_t count = (size_t)s->n;
-	s->sig_cur.resize(s->names.size(), 0);
-	s->dig_cur.resize(s->names.size(), 0);
-	{  // (refused before anything is enqueued: the digest kernels have 16 accumulators)
-		int checked = 0;
-		for (auto& r : resident) checked += r.second >= 2 ? 1 : 0;
-		if (checked > 16) return fail(HNS_ERR_INVALID_ARGUMENT, "hns_compute_sim_resident: more than 16 CHECKED fields");
+namespace {
+struct Cook {
+	hns_sim* s;
+	const hns_field* fields;  // the caller's array: fs points into it, `resident` runs beside it
+	int n_fields;
+	FieldSplit& fs;
+	const unsigned char* resident;
+	int* skipped;
+	int iterations;
+	float dt, voxel_size;
+	const hns_combustion_params* params;
+	int has_collision;
+	hipStream_t st;
+	std::vector<std::pair<uint64_t*, size_t>> dig_slots = {};  // (where the digest goes, its element count), in the order of s->d_dig
+
+	size_t count() const { return (size_t)s->n; }
+	int level_of(const hns_field* f) const { return resident ? resident[f - fields] : 0; }
+	static bool is_sdf(const hns_field* f) { return !strcmp(f->name, "collision_sdf"); }
+	static bool is_combustion_field(const hns_field* f) {
+		return std::any_of(kCombustionFields, kCombustionFields + 4, [f](const char* n) { return !strcmp(f->name, n); });
 	}
-	auto level_of = [&](const hns_field* f) {
-		for (auto& r : resident)
-			if (r.first == f) return r.second;
-		return 0;
-	};
-	auto stays = [&](const hns_field* f) {
+
+	bool stays(const hns_field* f) {
 		const int level = level_of(f);
 		if (!level) return false;
-		uint64_t have = 0, have_full = 0;
-		size_t n = count;
-		if (f->ncomp == 3) have = s->sig_vel, have_full = s->dig_vel, n = 3 * count;
-		else {
-			const int k = s->find(f->name);
-			if (k >= 0) have = s->sig_cur[(size_t)k], have_full = s->dig_cur[(size_t)k];
-		}
-		if (!have || have != host_signature(f->host, n)) return false;
-		if (level >= 2 && (!have_full || have_full != host_digest(f->host, n))) return false;  // (no digest taken last cook: nothing to check against -> upload)
+		hns_sim::Handed have;
+		const size_t n = (size_t)f->ncomp * count();
+		if (f->ncomp == 3) have = s->handed_vel;
+		else if (const int k = s->find(f->name); k >= 0) have = s->handed_cur[(size_t)k];
+		if (!have.sig || have.sig != host_signature(f->host, n)) return false;
+		if (level >= 2 && (!have.dig || have.dig != host_digest(f->host, n))) return false;  // (no digest taken last cook: nothing to check against -> upload)
 		if (skipped) ++*skipped;
 		return true;
-	};
-	auto upload = [&](hns_field* f, void* on) { return stays(f) ? (int)HNS_OK : hns_sim_upload(s, f, 1, on); };
+	}
+	int upload(hns_field* f, hipStream_t on) { return stays(f) ? (int)HNS_OK : hns_sim_upload(s, f, 1, on); }
+
 	// the full digest of a CHECKED field is taken ON THE DEVICE, of the buffer the host array is downloaded from (the same bits), behind the last kernel of the
 	// substep and beside the downloads: one pass at memory speed instead of a second host pass over every array
-	std::vector<std::pair<uint64_t*, size_t>> dig_slots;  // (where the digest goes, its element count), in the order of s->d_dig
-	auto digest_on_device = [&](hipStream_t on) -> int {
+	int digest_on_device(hipStream_t on) {
 		std::vector<const float*> bufs;
-		if (level_of(fs.velocity) >= 2) bufs.push_back(s->vel), dig_slots.emplace_back(&s->dig_vel, 3 * count);
+		if (level_of(fs.velocity) >= 2) bufs.push_back(s->vel), dig_slots.emplace_back(&s->handed_vel.dig, 3 * count());
 		for (hns_field* f : fs.floats) {
 			const int k = s->find(f->name);
-			if (k >= 0 && strcmp(f->name, "collision_sdf") && level_of(f) >= 2) bufs.push_back(s->cur[(size_t)k]), dig_slots.emplace_back(&s->dig_cur[(size_t)k], count);
+			if (k >= 0 && !is_sdf(f) && level_of(f) >= 2) bufs.push_back(s->cur[(size_t)k]), dig_slots.emplace_back(&s->handed_cur[(size_t)k].dig, count());
 		}
 		if (bufs.empty()) return HNS_OK;
 		if (!s->h_dig) HNS_HIP(hipHostMalloc((void**)&s->h_dig, sizeof(unsigned long long) * 16, hipHostMallocDefault));  // (host memory: no device synchronisation)
@@ -818,74 +707,81 @@ static int compute_sim_pipelined(hns_sim* s, FieldSplit& fs, int iterations, flo
 		for (size_t i = 0; i < bufs.size(); ++i) HNS_TRY(hns_field_digest(bufs[i], dig_slots[i].second, s->d_dig + i, on));
 		HNS_HIP(hipMemcpyAsync(s->h_dig, s->d_dig, sizeof(unsigned long long) * 16, hipMemcpyDeviceToHost, on));  // (on the cook's own stream, in front of its final synchronise: ADVICE r5)
 		return HNS_OK;
-	};
-	auto sign = [&]() -> int {  // (the downloads and the digest kernels have completed: what the host arrays hold now is what vel / cur[] hold)
-		s->sig_vel = host_signature(fs.velocity->host, 3 * count);
-		s->dig_vel = 0;
+	}
+	int sign() {  // (the downloads and the digest kernels have completed: what the host arrays hold now is what vel / cur[] hold)
+		s->handed_vel = {host_signature(fs.velocity->host, 3 * count()), 0};
 		for (hns_field* f : fs.floats) {
 			const int k = s->find(f->name);
-			if (k < 0) continue;
-			const bool sdf = !strcmp(f->name, "collision_sdf");  // (the SDF comes back zeroed, the device keeps it)
-			s->sig_cur[(size_t)k] = sdf ? 0 : host_signature(f->host, count);
-			s->dig_cur[(size_t)k] = 0;
+			if (k >= 0) s->handed_cur[(size_t)k] = {is_sdf(f) ? 0 : host_signature(f->host, count()), 0};  // (the SDF comes back zeroed, the device keeps it)
 		}
-		if (!dig_slots.empty()) {
-			for (size_t i = 0; i < dig_slots.size(); ++i) *dig_slots[i].first = hns_digest_finish(s->h_dig[i], dig_slots[i].second);  // (the stream the copy ran on has been synchronised)
-		}
+		for (size_t i = 0; i < dig_slots.size(); ++i) *dig_slots[i].first = hns_digest_finish(s->h_dig[i], dig_slots[i].second);  // (the stream the copy ran on has been synchronised)
 		return HNS_OK;
-	};
-	if (!options().cook_pipeline.load()) {
+	}
+
+	// option "cook_pipeline" = 0: upload all / run / download all, on the caller's stream
+	int plain() {
 		std::vector<hns_field> all;
-		HNS_TRY(upload(fs.velocity, stream));
+		HNS_TRY(upload(fs.velocity, st));
 		all.push_back(*fs.velocity);
 		for (hns_field* f : fs.floats) {
-			HNS_TRY(upload(f, stream));
+			HNS_TRY(upload(f, st));
 			all.push_back(*f);
 		}
-		HNS_TRY(hns_sim_substep(s, iterations, dt, voxel_size, params, has_collision, stream));
-		HNS_TRY(digest_on_device((hipStream_t)stream));
-		HNS_TRY(hns_sim_download(s, all.data(), (int)all.size(), stream));
+		HNS_TRY(hns_sim_substep(s, iterations, dt, voxel_size, params, has_collision, st));
+		HNS_TRY(digest_on_device(st));
+		HNS_TRY(hns_sim_download(s, all.data(), (int)all.size(), st));
 		return sign();
 	}
-	if (!s->xfer) {
-		HNS_HIP(hipStreamCreateWithFlags(&s->xfer, hipStreamNonBlocking));
-		for (hipEvent_t& e : s->xev) HNS_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-	}
-	hipStream_t st = (hipStream_t)stream, xf = s->xfer;
-	HNS_TRY(step.prepare(s, iterations, dt, voxel_size, params, has_collision, stream));
-	auto is_combustion_field = [](const char* n) { return !strcmp(n, "fuel") || !strcmp(n, "waste") || !strcmp(n, "temperature") || !strcmp(n, "flame"); };
-	auto handoff = [&](hipEvent_t e, hipStream_t from, hipStream_t to) -> int {
+
+	static int handoff(hipEvent_t e, hipStream_t from, hipStream_t to) {
 		HNS_HIP(hipEventRecord(e, from));
 		HNS_HIP(hipStreamWaitEvent(to, e, 0));
 		return HNS_OK;
-	};
-	HNS_TRY(handoff(s->xev[0], st, xf));  // transfers start after whatever the caller's stream holds
-	if (step.coll)
+	}
+	int pipelined() {
+		if (!s->xfer) {
+			HNS_HIP(hipStreamCreateWithFlags(&s->xfer, hipStreamNonBlocking));
+			for (hipEvent_t& e : s->xev) HNS_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+		}
+		hipStream_t xf = s->xfer;
+		Substep step;
+		HNS_TRY(step.prepare(s, iterations, dt, voxel_size, params, has_collision, st));
+		HNS_TRY(handoff(s->xev[0], st, xf));  // transfers start after whatever the caller's stream holds
+		if (step.coll)
+			for (hns_field* f : fs.floats)
+				if (is_sdf(f)) HNS_TRY(hns_sim_upload(s, f, 1, xf));
+		HNS_TRY(upload(fs.velocity, xf));
+		HNS_TRY(handoff(s->xev[1], xf, st));
+		HNS_TRY(step.part_a());
 		for (hns_field* f : fs.floats)
-			if (!strcmp(f->name, "collision_sdf")) HNS_TRY(hns_sim_upload(s, f, 1, xf));
-	HNS_TRY(upload(fs.velocity, xf));
-	HNS_TRY(handoff(s->xev[1], xf, st));
-	HNS_TRY(step.part_a());
-	for (hns_field* f : fs.floats)
-		if (is_combustion_field(f->name)) HNS_TRY(upload(f, xf));
-	HNS_TRY(handoff(s->xev[2], xf, st));
-	HNS_TRY(step.part_b());  // the solve runs while every remaining field is still on its way
-	HNS_HIP(hipEventRecord(s->xev[3], st));  // s->vel is final here
-	for (hns_field* f : fs.floats)  // "collision_sdf" went up first if this call uses it; if not, nothing reads it and it returns zeroed
-		if (!is_combustion_field(f->name) && strcmp(f->name, "collision_sdf") != 0) HNS_TRY(upload(f, xf));
-	HNS_TRY(handoff(s->xev[4], xf, st));
-	HNS_TRY(step.part_c());
-	HNS_TRY(digest_on_device(st));  // (every field is final on the device here; the kernels run beside the downloads)
-	HNS_HIP(hipStreamWaitEvent(xf, s->xev[3], 0));
-	HNS_HIP(hipMemcpyAsync(fs.velocity->host, s->vel, sizeof(float) * 3 * (size_t)s->n, hipMemcpyDeviceToHost, xf));
-	HNS_TRY(handoff(s->xev[0], st, xf));
-	std::vector<hns_field> outs;
-	for (hns_field* f : fs.floats)
-		if (strcmp(f->name, "collision_sdf") != 0) outs.push_back(*f);  // the caller's SDF array comes back zeroed (hns_compute_sim): no bytes to fetch
-	HNS_TRY(hns_sim_download(s, outs.data(), (int)outs.size(), xf));  // synchronises xf
-	HNS_HIP(hipStreamSynchronize(st));
-	return sign();
-}
+			if (is_combustion_field(f)) HNS_TRY(upload(f, xf));
+		HNS_TRY(handoff(s->xev[2], xf, st));
+		HNS_TRY(step.part_b());  // the solve runs while every remaining field is still on its way
+		HNS_HIP(hipEventRecord(s->xev[3], st));  // s->vel is final here
+		for (hns_field* f : fs.floats)  // "collision_sdf" went up first if this call uses it; if not, nothing reads it and it returns zeroed
+			if (!is_combustion_field(f) && !is_sdf(f)) HNS_TRY(upload(f, xf));
+		HNS_TRY(handoff(s->xev[4], xf, st));
+		HNS_TRY(step.part_c());
+		HNS_TRY(digest_on_device(st));  // (every field is final on the device here; the kernels run beside the downloads)
+		HNS_HIP(hipStreamWaitEvent(xf, s->xev[3], 0));
+		HNS_HIP(hipMemcpyAsync(fs.velocity->host, s->vel, sizeof(float) * 3 * count(), hipMemcpyDeviceToHost, xf));
+		HNS_TRY(handoff(s->xev[0], st, xf));  // (xev[0] again: its first use is long past)
+		std::vector<hns_field> outs;
+		for (hns_field* f : fs.floats)
+			if (!is_sdf(f)) outs.push_back(*f);  // the caller's SDF array comes back zeroed (hns_compute_sim): no bytes to fetch
+		HNS_TRY(hns_sim_download(s, outs.data(), (int)outs.size(), xf));  // synchronises xf
+		HNS_HIP(hipStreamSynchronize(st));
+		return sign();
+	}
+
+	int run() {
+		int checked = 0;  // (refused before anything is enqueued: the digest kernels have 16 accumulators)
+		for (int i = 0; resident && i < n_fields; ++i) checked += resident[i] >= 2 ? 1 : 0;
+		if (checked > 16) return fail(HNS_ERR_INVALID_ARGUMENT, "hns_compute_sim_resident: more than 16 CHECKED fields");
+		return options().cook_pipeline.load() ? pipelined() : plain();
+	}
+};
+}  // namespace
 
 extern "C" int hns_compute_sim(hns_grid* g, hns_field* fields, int n_fields, int iterations, float dt, float voxel_size,
                                const hns_combustion_params* params, int has_collision, void* stream) {
@@ -913,16 +809,11 @@ extern "C" int hns_compute_sim_resident(hns_grid* g, hns_field* fields, int n_fi
 			return HNS_ERR_RUNTIME;
 		}
 	if (!g->on_device) return fail(HNS_ERR_NO_DEVICE, "hns_compute_sim: grid has no device tables (there is no CPU fallback)");
-	std::vector<std::pair<const hns_field*, int>> res;
-	if (resident)
-		for (int i = 0; i < n_fields; ++i)
-			if (resident[i]) res.emplace_back(&fields[i], (int)resident[i]);
 	SimGuard guard;
-	HNS_TRY(make_sim(g, fs, guard, stream));
-	if (int rc = compute_sim_pipelined(guard.s, fs, iterations, dt, voxel_size, params, has_collision, stream, res, uploads_skipped)) {
-		guard.s->sig_vel = guard.s->dig_vel = 0;  // whatever the buffers hold now, nobody was handed it
-		std::fill(guard.s->sig_cur.begin(), guard.s->sig_cur.end(), 0);
-		std::fill(guard.s->dig_cur.begin(), guard.s->dig_cur.end(), 0);
+	HNS_TRY(make_sim(g, fs.floats, guard, stream));
+	Cook cook{guard.s, fields, n_fields, fs, resident, uploads_skipped, iterations, dt, voxel_size, params, has_collision, (hipStream_t)stream};
+	if (int rc = cook.run()) {
+		guard.s->forget();  // whatever the buffers hold now, nobody was handed it
 		// copies on the transfer stream and kernels on the caller's may still be queued: let them finish before the
 		// guard hands the buffers on (and before the caller reuses its host arrays)
 		if (guard.s->xfer) (void)hipStreamSynchronize(guard.s->xfer);
@@ -937,23 +828,19 @@ extern "C" int hns_compute_sim_resident(hns_grid* g, hns_field* fields, int n_fi
 }
 
 extern "C" int hns_advect_index_grid(hns_grid* g, hns_field* fields, int n_fields, float dt, float voxel_size, void* stream) {
-	if (!g) return fail(HNS_ERR_INVALID_ARGUMENT, "hns_advect_index_grid: null grid");
 	FieldSplit fs;
-	HNS_TRY(split_fields(fields, n_fields, fs, "hns_advect_index_grid"));
-	if (fs.n_vec3 != 1) return fail(HNS_ERR_RUNTIME, "Expected exactly one Vec3f block (velocity)");  // Advection.cu:19-21
-	if (fs.floats.empty()) return fail(HNS_ERR_RUNTIME, "No float blocks found");                     // :27-29
+	HNS_TRY(operator_fields(g, fields, n_fields, "hns_advect_index_grid", fs));
+	if (fs.floats.empty()) return fail(HNS_ERR_RUNTIME, "No float blocks found");                     // Advection.cu:27-29
 	if (!fs.velocity->host) return fail(HNS_ERR_RUNTIME, "Velocity data not found");                  // :32-34
 	for (hns_field* f : fs.floats)
 		if (!f->host) {
 			set_error("Block '%s' not found or type mismatch", f->name);  // :46-48
 			return HNS_ERR_RUNTIME;
 		}
-	if (hns_grid_voxel_count(g) == 0) return HNS_OK;
-	if (!g->on_device) return fail(HNS_ERR_NO_DEVICE, "hns_advect_index_grid: grid has no device tables (there is no CPU fallback)");
 	SimGuard guard;
-	HNS_TRY(make_sim(g, fs, guard, stream));
+	HNS_TRY(operator_sim(g, "hns_advect_index_grid", fs.floats, fields, n_fields, guard, stream));
 	hns_sim* s = guard.s;
-	HNS_TRY(hns_sim_upload(s, fields, n_fields, stream));
+	if (!s) return HNS_OK;
 	const float inv_dx = 1.0f / voxel_size;
 	for (size_t i = 0; i < s->names.size(); ++i) {  // one advect_scalar per float block (Advection.cu:88-91)
 		HNS_TRY(hns_dev_advect_scalar(g, s->vel, s->cur[i], s->nxt[i], nullptr, 0, dt, inv_dx, stream));
@@ -965,44 +852,30 @@ extern "C" int hns_advect_index_grid(hns_grid* g, hns_field* fields, int n_field
 }
 
 extern "C" int hns_advect_index_grid_velocity(hns_grid* g, hns_field* fields, int n_fields, float dt, float voxel_size, void* stream) {
-	if (!g) return fail(HNS_ERR_INVALID_ARGUMENT, "hns_advect_index_grid_velocity: null grid");
 	FieldSplit fs;
-	HNS_TRY(split_fields(fields, n_fields, fs, "hns_advect_index_grid_velocity"));
-	if (fs.n_vec3 != 1) return fail(HNS_ERR_RUNTIME, "Expected exactly one Vec3f block (velocity)");  // Advection.cu:119-121
+	HNS_TRY(operator_fields(g, fields, n_fields, "hns_advect_index_grid_velocity", fs));
 	if (!fs.velocity->host) return fail(HNS_ERR_RUNTIME, "Velocity data not found");
-	if (hns_grid_voxel_count(g) == 0) return HNS_OK;
-	if (!g->on_device) return fail(HNS_ERR_NO_DEVICE, "hns_advect_index_grid_velocity: grid has no device tables (there is no CPU fallback)");
 	SimGuard guard;
-	FieldSplit only_vel;
-	only_vel.velocity = fs.velocity;
-	only_vel.n_vec3 = 1;
-	HNS_TRY(make_sim(g, only_vel, guard, stream));
+	HNS_TRY(operator_sim(g, "hns_advect_index_grid_velocity", {}, fs.velocity, 1, guard, stream));
 	hns_sim* s = guard.s;
-	HNS_TRY(hns_sim_upload(s, fs.velocity, 1, stream));
+	if (!s) return HNS_OK;
 	HNS_TRY(hns_dev_advect_vector(g, s->vel, s->adv, nullptr, 0, dt, 1.0f / voxel_size, stream));
 	std::swap(s->vel, s->adv);
 	return hns_sim_download(s, fs.velocity, 1, stream);
 }
 
 extern "C" int hns_project_non_divergent(hns_grid* g, hns_field* fields, int n_fields, uint64_t iterations, float voxel_size, void* stream) {
-	if (!g) return fail(HNS_ERR_INVALID_ARGUMENT, "hns_project_non_divergent: null grid");
 	FieldSplit fs;
-	HNS_TRY(split_fields(fields, n_fields, fs, "hns_project_non_divergent"));
-	if (fs.n_vec3 != 1) return fail(HNS_ERR_RUNTIME, "Expected exactly one Vec3f block (velocity)");  // PressureProjection.cu:14-17
+	HNS_TRY(operator_fields(g, fields, n_fields, "hns_project_non_divergent", fs));
 	if (!fs.velocity->host) return fail(HNS_ERR_RUNTIME, "Velocity data not found");
 	if (voxel_size <= 0.0f) return fail(HNS_ERR_INVALID_ARGUMENT, "voxelSize must be positive.");
 	if (iterations > 0x7fffffffull) return fail(HNS_ERR_INVALID_ARGUMENT, "hns_project_non_divergent: iteration count too large");
-	if (hns_grid_voxel_count(g) == 0) return HNS_OK;
-	if (!g->on_device) return fail(HNS_ERR_NO_DEVICE, "hns_project_non_divergent: grid has no device tables (there is no CPU fallback)");
 	SimGuard guard;
-	FieldSplit only_vel;
-	only_vel.velocity = fs.velocity;
-	only_vel.n_vec3 = 1;
-	HNS_TRY(make_sim(g, only_vel, guard, stream));
+	HNS_TRY(operator_sim(g, "hns_project_non_divergent", {}, fs.velocity, 1, guard, stream));
 	hns_sim* s = guard.s;
-	HNS_TRY(hns_sim_upload(s, fs.velocity, 1, stream));
+	if (!s) return HNS_OK;
 	const float inv_dx = 1.0f / voxel_size;
-	HNS_TRY(hns_dev_divergence(g, s->vel, s->div, inv_dx, stream));              // :48
+	HNS_TRY(hns_dev_divergence(g, s->vel, s->div, inv_dx, stream));              // PressureProjection.cu:48
 	HNS_TRY(sim_pressure(s, (int)iterations, voxel_size, omega_project(voxel_size), stream));            // :51-60 (0 iterations leaves p = 0)
 	HNS_TRY(hns_dev_subtract_pressure_gradient(g, s->vel, s->p_result, s->vel, nullptr, 0,
 	                                           inv_dx, stream));  // :64, in place
@@ -1010,25 +883,18 @@ extern "C" int hns_project_non_divergent(hns_grid* g, hns_field* fields, int n_f
 }
 
 extern "C" int hns_divergence(hns_grid* g, hns_field* fields, int n_fields, float voxel_size, void* stream) {
-	if (!g) return fail(HNS_ERR_INVALID_ARGUMENT, "hns_divergence: null grid");
 	FieldSplit fs;
-	HNS_TRY(split_fields(fields, n_fields, fs, "hns_divergence"));
-	if (fs.n_vec3 != 1) return fail(HNS_ERR_RUNTIME, "Expected exactly one Vec3f block (velocity)");  // PressureProjection.cu:85-88
+	HNS_TRY(operator_fields(g, fields, n_fields, "hns_divergence", fs));
 	if (!fs.velocity->host) return fail(HNS_ERR_RUNTIME, "Velocity data not found");
 	hns_field* out = nullptr;
 	for (hns_field* f : fs.floats)
-		if (strcmp(f->name, "divergence") == 0) out = f;  // :91
+		if (strcmp(f->name, "divergence") == 0) out = f;  // PressureProjection.cu:91
 	if (!out || !out->host) return fail(HNS_ERR_RUNTIME, "hns_divergence: no float block named 'divergence' to receive the result");
 	if (voxel_size <= 0.0f) return fail(HNS_ERR_INVALID_ARGUMENT, "voxelSize must be positive.");
-	if (hns_grid_voxel_count(g) == 0) return HNS_OK;
-	if (!g->on_device) return fail(HNS_ERR_NO_DEVICE, "hns_divergence: grid has no device tables (there is no CPU fallback)");
 	SimGuard guard;
-	FieldSplit only_vel;
-	only_vel.velocity = fs.velocity;
-	only_vel.n_vec3 = 1;
-	HNS_TRY(make_sim(g, only_vel, guard, stream));
+	HNS_TRY(operator_sim(g, "hns_divergence", {}, fs.velocity, 1, guard, stream));
 	hns_sim* s = guard.s;
-	HNS_TRY(hns_sim_upload(s, fs.velocity, 1, stream));
+	if (!s) return HNS_OK;
 	HNS_TRY(hns_dev_divergence(g, s->vel, s->div, 1.0f / voxel_size, stream));
 	HNS_HIP(hipMemcpyAsync(out->host, s->div, sizeof(float) * (size_t)s->n, hipMemcpyDeviceToHost, (hipStream_t)stream));
 	HNS_HIP(hipStreamSynchronize((hipStream_t)stream));

@@ -274,15 +274,6 @@ __device__ __forceinline__ float nbr_val3(const float* __restrict__ u, const int
 
 // ---- launcher plumbing shared by the kernel files ----
 
-#define HNS_HIP(call)                                                                  \
-	do {                                                                               \
-		hipError_t e__ = (call);                                                       \
-		if (e__ != hipSuccess) {                                                       \
-			hns::set_error("%s failed: %s (%s:%d)", #call, hipGetErrorString(e__), __FILE__, __LINE__); \
-			return HNS_ERR_HIP;                                                        \
-		}                                                                              \
-	} while (0)
-
 inline int check_grid(const hns_grid* g, const char* who) {
 	if (!g) {
 		hns::set_error("%s: null grid", who);

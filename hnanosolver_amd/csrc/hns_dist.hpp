@@ -225,9 +225,7 @@ struct hns_dist {
 	// statistics of the last substep
 	uint64_t bytes_sent[hnsd::X_COUNT] = {0, 0, 0, 0}, messages_sent = 0, exchanges = 0, packed_exchanges = 0;
 	// hipEvent bracketing of the pressure loop (communication included)
-	bool timing = false;
-	std::vector<hipEvent_t> tev;
-	size_t tev_used = 0;
+	hns::EventGroups solve_ev{2};
 	long long timed_sweeps = 0;
 };
 

@@ -248,7 +248,7 @@ void hns_dist_destroy(hns_dist* d) {
 	if (d->ipc_flags) (void)hipFree(d->ipc_flags);
 	if (d->ipc_status) (void)hipHostFree(d->ipc_status);
 	if (d->far_status) (void)hipHostFree(d->far_status);
-	for (hipEvent_t e : d->tev) (void)hipEventDestroy(e);
+	d->solve_ev.destroy();
 	if (d->ev_ready) (void)hipEventDestroy(d->ev_ready);
 	for (int i = 0; i < 2; ++i) {
 		if (d->ev_post[i]) (void)hipEventDestroy(d->ev_post[i]);

@@ -668,6 +668,12 @@ struct Step {
 		return post(d, X_ADV, f, st, nothing, nothing);  // advect_scalars reads their ghosts; hidden under the pressure solve
 	}
 
+	// hns_dist_timing: the pressure loop's bracket opens in its first block and closes in the gradient phase
+	int open_timed() {
+		if (hipEvent_t* timed = d->solve_ev.current()) HNS_HIP(hipEventRecord(timed[0], st));
+		return HNS_OK;
+	}
+
 	// one block of up to k sweeps with the halo of p exchanged behind it; all but the last sweep the ghost leaves too
 	int sor_block_exchanged(int b) {
 		hns_dist* D = d;
@@ -679,7 +685,7 @@ struct Step {
 		const bool unsplit = in_line_rank() && d->pack_ok[X_P] && d->pack_ok[X_D1] && hns_rbgs_block_packable(d->gO);
 		const int tail = unsplit ? std::min(n, 2) : ((n >= 2 && split_blocked()) ? 2 : 1);
 		if (b == 0 || n > tail || !complete_boundary_only(d, st)) HNS_TRY(complete(d, st));
-		if (b == 0 && d->timing && d->tev_used + 2 <= d->tev.size()) HNS_HIP(hipEventRecord(d->tev[d->tev_used], st));
+		if (b == 0) HNS_TRY(open_timed());
 		// Round 4: the sweeps of the block that the exchange follows are TWO iterations in one temporally blocked launch per range
 		// (hns_sorblock.hip over a launch range: the ghost leaves are tile sources, 2K = 4 voxels deep, and are not swept; the X_P region
 		// of a plan with k >= 2 reaches 2k >= 4 voxels, its div region 2k - 1 >= 3), where the library's plan for the ranges says so.
@@ -738,7 +744,7 @@ struct Step {
 	int mirror_block(int b) {
 		if (b == 0) {
 			it = 0, src = d->p_a, dst = d->p_b;  // never warm-started (reference HNanoSolver.cu:113): the first sweep reads no p
-			if (d->timing && d->tev_used + 2 <= d->tev.size()) HNS_HIP(hipEventRecord(d->tev[d->tev_used], st));
+			HNS_TRY(open_timed());
 		}
 		const int its = std::min(2, iterations - it);
 		const PhaseMirror m = phase_args(d, X_P, Outs{{dst, 1}});
@@ -759,9 +765,9 @@ struct Step {
 			m.seq = d->sweep_seq;
 			hipLaunchKernelGGL(k_sweep_wait, dim3(1), dim3(64), 0, st, m);
 		}
-		if (d->timing && d->tev_used + 2 <= d->tev.size()) {  // the timed region ends when the last refresh of p has landed (complete() in front of the phase)
-			HNS_HIP(hipEventRecord(d->tev[d->tev_used + 1], st));
-			d->tev_used += 2;
+		if (hipEvent_t* timed = d->solve_ev.current()) {  // the timed region ends when the last refresh of p has landed (complete() in front of the phase)
+			HNS_HIP(hipEventRecord(timed[1], st));
+			d->solve_ev.advance();
 			d->timed_sweeps += iterations;
 		}
 		hns_dist* D = d;
@@ -844,10 +850,9 @@ struct SimArgs { const hns_combustion_params* params; const int* field_index; in
 int sim_step_args(const hns_dist* d, const SimArgs& a, Step& s) {
 	const int* field_index = a.field_index;
 	if (!a.params || !field_index) return fail(HNS_ERR_INVALID_ARGUMENT, "hns_dist_sim_substep: null argument");
-	const char* required[4] = {"fuel", "waste", "temperature", "flame"};
 	for (int c = 0; c < 4; ++c) {
 		if (field_index[c] < 0 || field_index[c] >= d->n_scalars) {
-			set_error("Missing required input field for combustion: %s", required[c]);  // HNanoSolver.cu:193-201
+			set_error("Missing required input field for combustion: %s", kCombustionFields[c]);  // HNanoSolver.cu:193-201
 			return HNS_ERR_RUNTIME;
 		}
 		for (int e = 0; e < c; ++e)
@@ -945,26 +950,14 @@ int hns_dist_local_sim_substep(hns_dist* const* ranks, int world, int iterations
 
 int hns_dist_timing(hns_dist* d, int max_solves) {
 	if (!d || max_solves < 0) return fail(HNS_ERR_INVALID_ARGUMENT, "hns_dist_timing: bad arguments");
-	while (d->tev.size() < (size_t)max_solves * 2) {
-		hipEvent_t e;
-		HNS_HIP(hipEventCreate(&e));
-		d->tev.push_back(e);
-	}
-	d->timing = max_solves > 0;
-	d->tev_used = 0;
 	d->timed_sweeps = 0;
-	return HNS_OK;
+	return d->solve_ev.reset(max_solves);
 }
 
 int hns_dist_pressure_time(hns_dist* d, float* total_ms, long long* sweeps) {
 	if (!d || !total_ms || !sweeps) return fail(HNS_ERR_INVALID_ARGUMENT, "hns_dist_pressure_time: null argument");
-	double tot = 0.0;
-	for (size_t i = 0; i + 1 < d->tev_used; i += 2) {
-		HNS_HIP(hipEventSynchronize(d->tev[i + 1]));
-		float ms = 0.0f;
-		HNS_HIP(hipEventElapsedTime(&ms, d->tev[i], d->tev[i + 1]));
-		tot += ms;
-	}
+	double tot;
+	HNS_TRY(d->solve_ev.elapsed(&tot));
 	*total_ms = (float)tot;
 	*sweeps = d->timed_sweeps;
 	return HNS_OK;

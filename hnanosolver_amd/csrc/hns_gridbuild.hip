@@ -99,7 +99,7 @@ int hns_grid_upload_schedule(hns_grid* g) {
 }
 
 // Device tables from the host origin list (g->topo.origins / hash_mask prepared by Topology::prepare). One allocation
-// from the arena pool (hns_api.hip) holds all of them: a cook that rebuilds the grid reuses the previous grid's memory.
+// from the arena pool (hns_arena.hip) holds all of them: a cook that rebuilds the grid reuses the previous grid's memory.
 int hns_grid_upload(hns_grid* g) {
 	int ndev = 0;
 	if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {

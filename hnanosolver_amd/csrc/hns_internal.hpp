@@ -3,6 +3,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <atomic>
 #include <cstdarg>
 #include <cstdint>
@@ -27,6 +28,58 @@ inline int fail(int code, const char* msg) {
 		int rc__ = (call);               \
 		if (rc__ != HNS_OK) return rc__; \
 	} while (0)
+
+#define HNS_HIP(call)                                                                                   \
+	do {                                                                                                \
+		hipError_t e__ = (call);                                                                        \
+		if (e__ != hipSuccess) {                                                                        \
+			hns::set_error("%s failed: %s (%s:%d)", #call, hipGetErrorString(e__), __FILE__, __LINE__); \
+			return HNS_ERR_HIP;                                                                         \
+		}                                                                                               \
+	} while (0)
+
+// the four float fields combustion reads and writes, in the order the kernels take them (reference HNanoSolver.cu:193-201)
+constexpr const char* kCombustionFields[4] = {"fuel", "waste", "temperature", "flame"};
+
+// hipEvents that bracket stretches of a stream, in groups of `per`: 2 for a pressure loop (start, stop), 6 for the boundaries of a substep's five stages. Whoever is
+// timed records into current() -- null when timing is off or every group is used -- and calls advance() behind the group's last record; the group may be opened in
+// one function and closed in another (the partitioned pressure loop: its first block and its gradient phase).
+struct EventGroups {
+	size_t per;
+	std::vector<hipEvent_t> ev;
+	size_t used = 0;  // groups
+	bool on = false;
+	explicit EventGroups(size_t per_) : per(per_) {}
+	int reset(int groups) {  // room for `groups` groups (events are kept, never given back), none of them used; 0 = timing off
+		while (ev.size() < (size_t)groups * per) {
+			hipEvent_t e;
+			HNS_HIP(hipEventCreate(&e));
+			ev.push_back(e);
+		}
+		on = groups > 0;
+		used = 0;
+		return HNS_OK;
+	}
+	hipEvent_t* current() { return on && (used + 1) * per <= ev.size() ? &ev[used * per] : nullptr; }
+	void advance() { ++used; }
+	int elapsed(double* ms) {  // ms[per - 1]: the time from each event of a group to the next, summed over the used groups (waits for their last events)
+		std::fill(ms, ms + per - 1, 0.0);
+		for (size_t g = 0; g < used; ++g) {
+			const hipEvent_t* e = &ev[g * per];
+			HNS_HIP(hipEventSynchronize(e[per - 1]));
+			for (size_t k = 0; k + 1 < per; ++k) {
+				float t = 0.0f;
+				HNS_HIP(hipEventElapsedTime(&t, e[k], e[k + 1]));
+				ms[k] += t;
+			}
+		}
+		return HNS_OK;
+	}
+	void destroy() {
+		for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+		ev.clear();
+	}
+};
 
 // makes `device` current for the scope (allocations, frees and synchronisation of pooled memory belong to ITS device,
 // whatever the calling thread has current)
@@ -148,7 +201,7 @@ struct hns_grid {
 	uint64_t sched_prefix = 0;    // leaves at the head of the active range that the launch order deals out to all XCDs first (hns_dist: boundary leaves)
 	void* d_sched_mem = nullptr;  // storage of d_sched (d_sched itself is null under the linear schedule)
 	void* d_scratch = nullptr;    // scratch of the block-record build (hns_grid_build_blocks)
-	void* d_arena = nullptr;      // the one device allocation all of the above are slices of (arena pool, hns_api.hip)
+	void* d_arena = nullptr;      // the one device allocation all of the above are slices of (arena pool, hns_arena.hip)
 	size_t arena_bytes = 0;
 	// temporally blocked SOR kernel (hns_sorblock.hip): records of the 16^3-voxel blocks in launch order (64 leaves under each tile),
 	// built on first use into an arena allocation of their own
@@ -181,23 +234,26 @@ struct hns_sim {
 	float* p_b = nullptr;
 	float* p_result = nullptr;  // whichever of p_a/p_b holds the last solve
 	// optional hipEvent bracketing of the pressure hot loop (hns_sim_timing), on the stream the kernels run on
-	bool timing = false;
-	std::vector<hipEvent_t> ev;  // start/stop pairs
-	size_t ev_used = 0;
+	hns::EventGroups solve_ev{2};  // start/stop pairs
 	long long timed_launches = 0;
-	bool stage_timing = false;    // hns_sim_stage_timing: also bracket the five stages of hns_sim_core_substep
-	std::vector<hipEvent_t> sev;  // stage boundaries: six per substep
-	size_t sev_used = 0;
-	hipStream_t xfer = nullptr;  // transfer stream + hand-off events of the pipelined operator path (compute_sim_pipelined)
+	hns::EventGroups stage_ev{6};  // hns_sim_stage_timing: also bracket the five stages of hns_sim_substep / hns_sim_core_substep (six boundaries per substep)
+	hipStream_t xfer = nullptr;  // transfer stream + hand-off events of the pipelined operator path (hns_api.hip: Cook)
 	hipEvent_t xev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
 	bool cached = false, in_use = false;  // owned by the grid's cook cache / currently lent to an operator call
 	// Device-resident feedback across cooks (hns_compute_sim_resident): a signature of what the last hns_compute_sim on this state handed
 	// back for the velocity and for float field i -- those bytes are still in `vel` / cur[i]. 0 = nothing to vouch for (any upload clears it).
-	uint64_t sig_vel = 0, dig_vel = 0;  // (sig: sample signature; dig: full digest, 0 = not taken)
+	struct Handed { uint64_t sig = 0, dig = 0; };  // (sig: sample signature; dig: full digest, 0 = not taken)
+	Handed handed_vel;
+	std::vector<Handed> handed_cur;  // one per float field (sized where `names` is fixed: sim_create)
+	static constexpr int kVelocity = -1, kEverything = -2;
+	void forget(int k = kEverything) {  // float field k, the velocity or everything: the buffer no longer holds what the caller was handed
+		if (k == kEverything || k == kVelocity) handed_vel = Handed{};
+		for (size_t i = 0; i < handed_cur.size(); ++i)
+			if (k == kEverything || k == (int)i) handed_cur[i] = Handed{};
+	}
 	unsigned long long* d_dig = nullptr;  // 16 accumulators of the digest kernels (hns_digest.hpp): a slice of the arena
 	unsigned long long* h_dig = nullptr;  // pinned host copy of them (read asynchronously on the cook's own stream)
-	std::vector<uint64_t> sig_cur, dig_cur;
-	void* arena = nullptr;  // every field above is a slice of this one allocation (see the arena pool, hns_api.hip)
+	void* arena = nullptr;  // every field above is a slice of this one allocation (see the arena pool, hns_arena.hip)
 	size_t arena_bytes = 0;
 	// active voxel masks of the leaves (hns_sim_set_active_masks / hns_sim_regrid): leaf_count x 64 bytes, byte x*8+y, bit z; null = every voxel active.
 	// An allocation of their own from the arena pool, made on first use: nothing else reads them.
@@ -255,7 +311,7 @@ extern "C" __attribute__((visibility("hidden"))) int hns_combustion_fields(const
                                                                            float* out_fuel, float* out_waste, float* out_temperature, float* out_flame,
                                                                            float temp_gain, uint64_t n, void* stream);
 
-// implemented in hns_api.hip: process-wide pool of device allocations (simulation state and grid tables)
+// implemented in hns_arena.hip: process-wide pool of device allocations (simulation state and grid tables)
 extern "C" __attribute__((visibility("hidden"))) int hns_arena_get(size_t need, int device, void** p, size_t* bytes);
 extern "C" __attribute__((visibility("hidden"))) void hns_arena_put(void* p, size_t bytes, int device);
 

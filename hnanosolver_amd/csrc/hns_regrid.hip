@@ -657,9 +657,7 @@ struct Regrid {
 		hns_sim_layout(s, new_fields, n_new * 512u);
 		s->d_masks = (unsigned char*)new_masks, s->masks_bytes = scratch.keep(new_masks);
 		s->grid = ng.release();
-		s->sig_vel = s->dig_vel = 0;
-		std::fill(s->sig_cur.begin(), s->sig_cur.end(), 0);
-		std::fill(s->dig_cur.begin(), s->dig_cur.end(), 0);
+		s->forget();
 		s->regrid_timed = true;
 		*out = s->grid;
 		return HNS_OK;

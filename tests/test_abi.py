@@ -268,3 +268,116 @@ def test_cpp_host_mirror_matches_python_path_on_gpu(tmp_path):
     api.ProjectNonDivergent(d, 20, 1.0 / 32)
     api.AdvectIndexGrid(d, 1.0 / 24, 1.0 / 32)
     assert np.array_equal(vel, d.pValues("vel")) and np.array_equal(den, d.pValues("density"))
+
+
+def test_operator_refusals_keep_code_text_and_precedence():
+    """Every refusal of the six operators and of hns_sim_create that a host-only grid reaches, up to and including "no device tables": the
+    return code and the exact hns_last_error() text, one call with two faults per entry point for the precedence. The table was taken from the
+    library before the operators shared their opening checks (from its behaviour, not from the code under test)."""
+    lib = _lib.load_library()
+    g = api.create_grid_from_leaves(fields.dense_leaves(16), 1.0 / 16, _lib.HNS_GRID_HOST_ONLY)
+    n = int(lib.hns_grid_voxel_count(g.ptr))
+    vel, rho = np.zeros((n, 3), np.float32), np.zeros(n, np.float32)
+    prm = C.byref(_lib.hns_combustion_params())
+    BAD, RUN, NODEV = _lib.HNS_ERR_INVALID_ARGUMENT, _lib.HNS_ERR_RUNTIME, _lib.HNS_ERR_NO_DEVICE
+
+    def fl(*specs):  # (name, ncomp, host array or None) -> (hns_field array, count)
+        arr = (_lib.hns_field * max(1, len(specs)))()
+        for f, (name, ncomp, host) in zip(arr, specs):
+            f.name, f.ncomp = name, ncomp
+            if host is not None:
+                f.host = host.ctypes.data_as(C.POINTER(C.c_float))
+        return arr, len(specs)
+
+    V, V2, R, D = (b"vel", 3, vel), (b"vel2", 3, vel), (b"density", 1, rho), (b"divergence", 1, rho)
+    good, only_vel, with_div = fl(V, R), fl(V), fl(V, D)
+    no_tables = "%s: grid has no device tables (there is no CPU fallback)"
+    one_vec3 = "Expected exactly one Vec3f block (velocity)"
+    # what every operator says about a malformed field list, under its own name (the solver: as "hns_compute_sim" from both entry points)
+    field_list = [((None, 2), BAD, "%s: null field array"), ((None, -1), BAD, "%s: null field array"), (fl(V, (b"x", 2, rho)), BAD, "%s: field 1 has ncomp 2 (must be 1 or 3)"),
+                  (fl((None, 3, vel), R), BAD, "%s: field 0 has no name"), (fl(V, (None, 1, rho)), BAD, "%s: field 1 has no name")]
+
+    rows = []  # (label, call, code, text)
+
+    def solver(name, f=good, iters=5, dt=0.04, vs=1.0 / 16, grid=g.ptr, p=prm):
+        if name == "hns_compute_sim":
+            return lambda: lib.hns_compute_sim(grid, f[0], f[1], iters, dt, vs, p, 0, None)
+        return lambda: lib.hns_compute_sim_resident(grid, f[0], f[1], None, None, iters, dt, vs, p, 0, None)
+
+    for name in ("hns_compute_sim", "hns_compute_sim_resident"):
+        rows += [(name, solver(name, vs=0.0), BAD, "voxelSize must be positive."), (name, solver(name, dt=-1.0), BAD, "dt (time step) cannot be negative."),
+                 (name, solver(name, iters=0), BAD, "Number of pressure iterations must be positive."), (name, solver(name, grid=None), BAD, "Invalid grid handle provided (null grid)."),
+                 (name, solver(name, p=None), BAD, "hns_compute_sim: null combustion params")]
+        rows += [(name, solver(name, f), code, text % "hns_compute_sim") for f, code, text in field_list]
+        rows += [(name, solver(name, fl(R)), RUN, "Expected exactly one Vec3f block (velocity), found 0"), (name, solver(name, fl(V, V2, R)), RUN, "Expected exactly one Vec3f block (velocity), found 2"),
+                 (name, solver(name, (None, 0)), RUN, "Expected exactly one Vec3f block (velocity), found 0"), (name, solver(name, fl((b"vel", 3, None), R)), RUN, "Host velocity data pointer is null"),
+                 (name, solver(name, only_vel), RUN, "No float blocks found in input data."), (name, solver(name, fl(V, (b"density", 1, None))), RUN, "Host float data pointer is null for block: density"),
+                 (name, solver(name), NODEV, no_tables % "hns_compute_sim"),
+                 # two faults: the step's numbers are checked before the grid, the grid before the fields, the fields before the device tables
+                 (name, solver(name, (None, 2), vs=0.0), BAD, "voxelSize must be positive."), (name, solver(name, (None, 2), grid=None, dt=-1.0), BAD, "dt (time step) cannot be negative."),
+                 (name, solver(name, only_vel, p=None), BAD, "hns_compute_sim: null combustion params")]
+
+    def advect(f=good, grid=g.ptr):
+        return lambda: lib.hns_advect_index_grid(grid, f[0], f[1], 0.04, 1.0 / 16, None)
+
+    def advect_velocity(f=only_vel, grid=g.ptr):
+        return lambda: lib.hns_advect_index_grid_velocity(grid, f[0], f[1], 0.04, 1.0 / 16, None)
+
+    def project(f=only_vel, iters=5, vs=1.0 / 16, grid=g.ptr):
+        return lambda: lib.hns_project_non_divergent(grid, f[0], f[1], iters, vs, None)
+
+    def divergence(f=with_div, vs=1.0 / 16, grid=g.ptr):
+        return lambda: lib.hns_divergence(grid, f[0], f[1], vs, None)
+
+    for name, op in (("hns_advect_index_grid", advect), ("hns_advect_index_grid_velocity", advect_velocity), ("hns_project_non_divergent", project), ("hns_divergence", divergence)):
+        rows += [(name, op(grid=None), BAD, name + ": null grid"), (name, op((None, 2), grid=None), BAD, name + ": null grid")]
+        rows += [(name, op(f), code, text % name) for f, code, text in field_list]
+        rows += [(name, op(fl(R)), RUN, one_vec3), (name, op(fl(V, V2, R)), RUN, one_vec3), (name, op((None, 0)), RUN, one_vec3), (name, op(), NODEV, no_tables % name)]
+    rows += [("hns_advect_index_grid", advect(only_vel), RUN, "No float blocks found"), ("hns_advect_index_grid", advect(fl((b"vel", 3, None), R)), RUN, "Velocity data not found"),
+             ("hns_advect_index_grid", advect(fl(V, (b"density", 1, None))), RUN, "Block 'density' not found or type mismatch"),
+             ("hns_advect_index_grid", advect(fl((b"vel", 3, None))), RUN, "No float blocks found"),  # two faults: the float blocks are counted before the velocity's pointer is looked at
+             ("hns_advect_index_grid", advect(fl((b"vel", 3, None), (b"density", 1, None))), RUN, "Velocity data not found"),
+             ("hns_advect_index_grid_velocity", advect_velocity(fl((b"vel", 3, None))), RUN, "Velocity data not found"),
+             ("hns_advect_index_grid_velocity", advect_velocity(fl(V, (b"density", 1, None))), NODEV, no_tables % "hns_advect_index_grid_velocity"),  # (the float blocks are not looked at)
+             ("hns_advect_index_grid_velocity", advect_velocity(fl((b"vel", 3, None), (b"x", 2, rho))), BAD, "hns_advect_index_grid_velocity: field 1 has ncomp 2 (must be 1 or 3)"),
+             ("hns_project_non_divergent", project(fl((b"vel", 3, None))), RUN, "Velocity data not found"), ("hns_project_non_divergent", project(vs=0.0), BAD, "voxelSize must be positive."),
+             ("hns_project_non_divergent", project(vs=-1.0), BAD, "voxelSize must be positive."),
+             ("hns_project_non_divergent", project(iters=1 << 31), BAD, "hns_project_non_divergent: iteration count too large"),
+             ("hns_project_non_divergent", project(iters=0), NODEV, no_tables % "hns_project_non_divergent"),  # (0 iterations is a valid call: p = 0)
+             ("hns_project_non_divergent", project((None, 2), vs=0.0), BAD, "hns_project_non_divergent: null field array"),  # two faults: the fields before the voxel size,
+             ("hns_project_non_divergent", project(fl((b"vel", 3, None)), vs=0.0), RUN, "Velocity data not found"),
+             ("hns_project_non_divergent", project(vs=0.0, iters=1 << 31), BAD, "voxelSize must be positive."),  # the voxel size before the iteration count
+             ("hns_divergence", divergence(fl((b"vel", 3, None), D)), RUN, "Velocity data not found"),
+             ("hns_divergence", divergence(good), RUN, "hns_divergence: no float block named 'divergence' to receive the result"),
+             ("hns_divergence", divergence(only_vel), RUN, "hns_divergence: no float block named 'divergence' to receive the result"),
+             ("hns_divergence", divergence(fl(V, (b"divergence", 1, None))), RUN, "hns_divergence: no float block named 'divergence' to receive the result"),
+             ("hns_divergence", divergence(vs=0.0), BAD, "voxelSize must be positive."),
+             ("hns_divergence", divergence(good, vs=0.0), RUN, "hns_divergence: no float block named 'divergence' to receive the result"),  # two faults: the block before the voxel size,
+             ("hns_divergence", divergence(fl((b"vel", 3, None)), vs=0.0), RUN, "Velocity data not found")]  # the velocity before the block
+
+    def sim_create(grid, names, n_float):
+        def call():
+            err = C.c_int(0)
+            arr = (C.c_char_p * max(1, len(names)))(*names) if names is not None else None
+            s = lib.hns_sim_create(grid, arr, n_float, C.byref(err))
+            assert s is None, "hns_sim_create returned a sim for a refused call"
+            return err.value
+        return call
+
+    rows += [("hns_sim_create", sim_create(None, [b"density"], 1), BAD, "hns_sim_create: bad arguments"), ("hns_sim_create", sim_create(g.ptr, [b"density"], -1), BAD, "hns_sim_create: bad arguments"),
+             ("hns_sim_create", sim_create(g.ptr, None, 1), BAD, "hns_sim_create: bad arguments"), ("hns_sim_create", sim_create(g.ptr, [b"density"], 1), NODEV, no_tables % "hns_sim_create"),
+             ("hns_sim_create", sim_create(g.ptr, None, 0), NODEV, no_tables % "hns_sim_create"),
+             ("hns_sim_create", sim_create(g.ptr, [b"density", b"density"], 2), NODEV, no_tables % "hns_sim_create"),  # two faults: the device tables before the names
+             ("hns_sim_create", sim_create(None, None, -1), BAD, "hns_sim_create: bad arguments")]
+
+    assert len(rows) >= 100
+    wrong = []
+    for i, (label, call, code, text) in enumerate(rows):
+        lib.hns_set_option(b"rbgs", None)  # (a call that succeeds: whatever it leaves in hns_last_error(), the text read below is this row's)
+        got = call()
+        got_text = lib.hns_last_error().decode()
+        if (got, got_text) != (code, text):
+            wrong.append(f"row {i} {label}: want {code} {text!r}, got {got} {got_text!r}")
+    assert np.count_nonzero(vel) == 0 and np.count_nonzero(rho) == 0  # nothing was computed
+    assert not wrong, "\n".join(wrong)
+    g.reset()
