@@ -15,6 +15,42 @@
 #endif
 
 /* ------------------------------------------------------------------ */
+/* min / max / float -> int: the two operations whose result for zeros */
+/* of both signs, NaN and out-of-range values the C language leaves to */
+/* the target. The stock build uses the host's; ORC_DEVICE_SEMANTICS   */
+/* selects what the GPU's instructions do.       */
+/* ------------------------------------------------------------------ */
+#ifdef ORC_DEVICE_SEMANTICS
+/* V_MIN_F32 / V_MAX_F32: symmetric, -0 < +0, a NaN operand loses, NaN only if both are */
+static inline float orc_fminf(float a, float b) {
+	if (a != a) return b;
+	if (b != b) return a;
+	if (a == 0.0f && b == 0.0f) return signbit(a) ? a : b;
+	return a < b ? a : b;
+}
+static inline float orc_fmaxf(float a, float b) {
+	if (a != a) return b;
+	if (b != b) return a;
+	if (a == 0.0f && b == 0.0f) return signbit(a) ? b : a;
+	return a > b ? a : b;
+}
+/* V_FLOOR_F32 + V_CVT_I32_F32: saturating, NaN -> 0 */
+static inline int32_t orc_floor_to_int(float x) {
+	const float f = floorf(x);
+	if (f != f) return 0;
+	if (f >= 2147483648.0f) return INT32_MAX;
+	if (f <= -2147483648.0f) return INT32_MIN;
+	return (int32_t)f;
+}
+int orc_device_semantics(void) { return 1; }
+#else
+#define orc_fminf fminf
+#define orc_fmaxf fmaxf
+static inline int32_t orc_floor_to_int(float x) { return (int32_t)floorf(x); }
+int orc_device_semantics(void) { return 0; }
+#endif
+
+/* ------------------------------------------------------------------ */
 /* topology                                                            */
 /* ------------------------------------------------------------------ */
 
@@ -195,7 +231,7 @@ static inline vec3 nearest_v(acc_t* a, const float* d, int32_t i, int32_t j, int
 
 /* Floor (Stencils.hpp:25-43): __float2int_rd, then xyz -= float(ijk) */
 static inline int32_t floor_frac(float* x) {
-	const int32_t i = (int32_t)floorf(*x);
+	const int32_t i = orc_floor_to_int(*x);
 	*x -= (float)i;
 	return i;
 }
@@ -335,14 +371,14 @@ void orc_advect_vector(const orc_grid* g, const float* vel, float* out, const fl
 			nc[dim] += offset;
 			const vec3 nv = nearest_v(&acc, vel, nc[0], nc[1], nc[2]);
 			for (int c = 0; c < 3; ++c) {
-				minVel.v[c] = fminf(minVel.v[c], nv.v[c]);
-				maxVel.v[c] = fmaxf(maxVel.v[c], nv.v[c]);
+				minVel.v[c] = orc_fminf(minVel.v[c], nv.v[c]);
+				maxVel.v[c] = orc_fmaxf(maxVel.v[c], nv.v[c]);
 			}
 		}
 	for (int c = 0; c < 3; ++c) {
-		minVel.v[c] = fminf(minVel.v[c], velForward.v[c]);
-		maxVel.v[c] = fmaxf(maxVel.v[c], velForward.v[c]);
-		velCorr.v[c] = fmaxf(minVel.v[c], fminf(velCorr.v[c], maxVel.v[c]));
+		minVel.v[c] = orc_fminf(minVel.v[c], velForward.v[c]);
+		maxVel.v[c] = orc_fmaxf(maxVel.v[c], velForward.v[c]);
+		velCorr.v[c] = orc_fmaxf(minVel.v[c], orc_fminf(velCorr.v[c], maxVel.v[c]));
 	}
 	if (has_collision && sdf) { /* Kernel.cu:433-450 */
 		const float sdf_value = nearest_f(&acc, sdf, ci, cj, ck);
@@ -386,12 +422,12 @@ void orc_advect_scalar(const orc_grid* g, const float* vel, const float* in, flo
 			int32_t nc[3] = {ci, cj, ck};
 			nc[dim] += offset;
 			const float nv = nearest_f(&acc, in, nc[0], nc[1], nc[2]);
-			minVal = fminf(minVal, nv);
-			maxVal = fmaxf(maxVal, nv);
+			minVal = orc_fminf(minVal, nv);
+			maxVal = orc_fmaxf(maxVal, nv);
 		}
-	minVal = fminf(minVal, phiForward);
-	maxVal = fmaxf(maxVal, phiForward);
-	phiCorr = fmaxf(minVal, fminf(phiCorr, maxVal));
+	minVal = orc_fminf(minVal, phiForward);
+	maxVal = orc_fmaxf(maxVal, phiForward);
+	phiCorr = orc_fmaxf(minVal, orc_fminf(phiCorr, maxVal));
 	out[idx] = phiCorr;
 	END_FOR_EACH_VOXEL
 }
@@ -406,9 +442,9 @@ typedef struct {
 static inline interp_t setup_interp(acc_t* a, vec3 pos) {
 	interp_t d;
 	const float x = pos.v[0], y = pos.v[1], z = pos.v[2];
-	const int32_t i0 = (int32_t)floorf(x), i1 = i0 + 1;
-	const int32_t j0 = (int32_t)floorf(y), j1 = j0 + 1;
-	const int32_t k0 = (int32_t)floorf(z), k1 = k0 + 1;
+	const int32_t i0 = orc_floor_to_int(x), i1 = i0 + 1;
+	const int32_t j0 = orc_floor_to_int(y), j1 = j0 + 1;
+	const int32_t k0 = orc_floor_to_int(z), k1 = k0 + 1;
 	const float tx = x - (float)i0, ty = y - (float)j0, tz = z - (float)k0;
 	const float itx = 1.0f - tx, ity = 1.0f - ty, itz = 1.0f - tz;
 	const float w00 = itx * ity, w10 = tx * ity, w01 = itx * ty, w11 = tx * ty;
@@ -470,12 +506,12 @@ void orc_advect_scalars(const orc_grid* g, const float* vel, const float* const*
 		float minVal = phiOrig, maxVal = phiOrig;
 		for (int n = 0; n < 6; ++n) {
 			const float val = inData[nbrIdx[n]];
-			minVal = fminf(minVal, val);
-			maxVal = fmaxf(maxVal, val);
+			minVal = orc_fminf(minVal, val);
+			maxVal = orc_fmaxf(maxVal, val);
 		}
-		minVal = fminf(minVal, phiForward);
-		maxVal = fmaxf(maxVal, phiForward);
-		out[s][idx] = fmaxf(minVal, fminf(phiCorr, maxVal));
+		minVal = orc_fminf(minVal, phiForward);
+		maxVal = orc_fmaxf(maxVal, phiForward);
+		out[s][idx] = orc_fmaxf(minVal, orc_fminf(phiCorr, maxVal));
 	}
 	END_FOR_EACH_VOXEL
 }
@@ -561,12 +597,12 @@ void orc_combustion_oxygen(const float* fuelData, const float* wasteData, const 
 			outFlame[idx] = flame;
 			continue;
 		}
-		const float burn = fminf(oxygen, fuel);
+		const float burn = orc_fminf(oxygen, fuel);
 		outFuel[idx] = fuel - burn;
 		outWaste[idx] = waste + burn * 2.0f;
 		outTemperature[idx] = temperature + burn * temp_gain;
 		divergenceData[idx] += burn * expansion;
-		outFlame[idx] = fmaxf(flame, fminf(1.0f, burn * 10.0f));
+		outFlame[idx] = orc_fmaxf(flame, orc_fminf(1.0f, burn * 10.0f));
 	}
 }
 
@@ -581,7 +617,7 @@ void orc_temperature_buoyancy(const float* vel, const float* temp, float* out, f
 			continue;
 		}
 		const float tempDiff = t - ambient;
-		const vec3 force = v3(0.0f, fmaxf(0.0f, tempDiff * strength), 0.0f);
+		const vec3 force = v3(0.0f, orc_fmaxf(0.0f, tempDiff * strength), 0.0f);
 		v3_store(out, (uint64_t)idx, v3_add(v, v3_scale(force, dt)));
 	}
 }

@@ -64,6 +64,9 @@ void orc_coords(const orc_grid*, int32_t* out_xyz);                    /* N x 3,
 void orc_set_vec3_lerp_fma(int on);
 void orc_set_threads(int n); /* OpenMP threads used by every kernel below (0 = all cores) */
 int orc_get_threads(void);
+/* 1 if built with -DORC_DEVICE_SEMANTICS: fminf/fmaxf are the GPU's symmetric min/max (-0 < +0, a NaN operand loses) and
+ * the float -> cell index conversion saturates (NaN -> 0); 0 for the stock build (the host's libm and cast). */
+int orc_device_semantics(void);
 
 /* ---- samplers, batch form (Stencils.hpp:74-173) ---- */
 void orc_sample_nearest_f(const orc_grid*, const float* data, const int32_t* ijk, int64_t n, float* out);

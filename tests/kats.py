@@ -393,3 +393,220 @@ CASES = {
     "vorticity_rigid_rotation": kat_vorticity_rigid_rotation,
     "collision_inside_is_zero": kat_collision_inside_is_zero,
 }
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# special values: NaN, inf and zeros of both signs (closed forms; tests/test_special_values*.py run them)
+# ---------------------------------------------------------------------------------------------------------------
+# Signature: case(make, device) -- make(leaves) gives an engine with the OracleGrid call signatures; `device` says that the
+# engine's min/max follow the GPU's rule (-0 < +0; symmetric), which is the only thing a case may ask about the sign of a zero.
+# What both rules share, and what the cases pin: a NaN operand of fminf / fmaxf loses, and NaN comes out only if both are.
+
+
+def _corner_nan(phi: np.ndarray, d=(0, 0, 0)) -> np.ndarray:
+    """does any of the eight corners of the cell whose lower corner is (c - d) hold a NaN (outside: 0, no NaN)"""
+    n = np.isnan(phi)
+    out = np.zeros_like(n)
+    for di in (0, 1):
+        for dj in (0, 1):
+            for dk in (0, 1):
+                t = n
+                for ax, s in enumerate((di - d[0], dj - d[1], dk - d[2])):
+                    t = shift(t, ax, s, fill=False)
+                out |= t
+    return out
+
+
+def limiter_expected(phi: np.ndarray, d=(0, 0, 0)) -> np.ndarray:
+    """BFECC (Kernel.cu:300-351) for a uniform integer displacement d (voxels): phiForward = phi(c - d), phiBackward = phi(c),
+    each NaN if one of its cell's eight corners is (a weight of 0 does not silence a NaN: a + 0 * (NaN - a)); corr = forward
+    + 0.5 * (phi - backward); the clamp set {phi, six neighbours, forward} through fminf / fmaxf, which drop a NaN operand."""
+    fwd = phi
+    for ax in range(3):
+        fwd = shift(fwd, ax, -d[ax])
+    fwd = np.where(_corner_nan(phi, d), np.nan, fwd)
+    bwd = np.where(_corner_nan(phi), np.nan, phi)
+    corr = fwd + 0.5 * (phi - bwd)
+    mn, mx = phi.copy(), phi.copy()
+    for ax in range(3):
+        for s in (-1, 1):
+            nb = shift(phi, ax, s)
+            mn, mx = np.fmin(mn, nb), np.fmax(mx, nb)
+    mn, mx = np.fmin(mn, fwd), np.fmax(mx, fwd)
+    return np.fmax(mn, np.fmin(corr, mx))
+
+
+def _nan_field(box: Box, seed: int):
+    """positive integers (so that no comparison ties and the outside's +0 is never the maximum's rival in sign) with, well inside:
+    a lone NaN (cells with ONE NaN corner and seven known values), a 2 x 2 x 2 block (a cell with all eight corners NaN) and a
+    3 x 3 x 3 block (a voxel whose whole clamp set is NaN: the one place where NaN comes out)"""
+    rng = np.random.default_rng(seed)
+    phi = rng.integers(1, 200, size=(box.B,) * 3).astype(np.float64)
+    phi[5, 6, 7] = np.nan
+    phi[10:12, 5:7, 12:14] = np.nan
+    phi[14:17, 14:17, 7:10] = np.nan  # across the leaf faces at 16 and 8
+    return phi
+
+
+def _equal_with_nan(got, want) -> bool:
+    return np.array_equal(np.asarray(got, dtype=np.float64), want, equal_nan=True)
+
+
+def kat_limiter_nan_at_rest(make, device):
+    """zero velocity: every sample is the voxel itself; a NaN corner makes phiForward and corr NaN and the limiter answers with
+    the maximum of what is left of the clamp set (fminf(NaN, mx) = mx, fmaxf(mn, mx) = mx)"""
+    box = Box(24)
+    K = make(box.leaves)
+    phi = _nan_field(box, 31)
+    want = limiter_expected(phi)
+    assert np.isnan(want).sum() == 1 and np.isnan(want[15, 15, 8]) and (np.isfinite(want) & np.isnan(phi)).sum() == 1 + 8 + 26
+    vel = np.zeros((box.N, 3), F32)
+    got = box.to_dense(K.advect_scalar(vel, box.to_flat(phi), 0.25, 4.0))
+    assert _equal_with_nan(got, want)
+    flat = box.to_flat(phi)
+    assert flat[0] == phi[0, 0, 0] and np.isfinite(flat[0])
+    flat[0] = 0.0  # advect_scalars reads element 0 outside the domain (Kernel.cu:192,225): make it the 0 the other kernel reads
+    phi0 = box.to_dense(flat).astype(np.float64)
+    for S in (1, 5):
+        got = K.advect_scalars(vel, [flat] * S, 0.25, 4.0)
+        for g in got:
+            assert _equal_with_nan(box.to_dense(g), limiter_expected(phi0))
+
+
+def kat_limiter_nan_corr_between_finite_bounds(make, device):
+    """uniform velocity, one voxel of displacement along an axis: phiForward = phi(c - d) is finite where the voxel itself is NaN,
+    phiBackward and corr are NaN there: the answer is the maximum of forward and the neighbours (interior only: the velocity
+    sampled outside the domain is 0, which bends the trace at the border)"""
+    box = Box(24)
+    K = make(box.leaves)
+    phi = _nan_field(box, 32)
+    for d in ((1, 0, 0), (0, -1, 0), (0, 0, 2)):
+        vel = np.broadcast_to(np.array(d, dtype=F32), (box.N, 3)).copy()
+        want = limiter_expected(phi, d)
+        got = box.to_dense(K.advect_scalar(vel, box.to_flat(phi), 0.25, 4.0))
+        inner = (slice(4, -4),) * 3
+        assert np.isfinite(want[5, 6, 7]) and _equal_with_nan(got[inner], want[inner]), d
+
+
+def kat_limiter_zeros_of_both_signs(make, device):
+    """a field of +0 and -0 at rest: the result is a zero everywhere. Its sign under the GPU's rule (-0 < +0, symmetric): every lerp
+    a + 0 * (b - a) of zeros is +0 (b - a is -0 only for b = -0, a = +0, and then a + -0 = +0), so phiForward = +0 is in the clamp
+    set, mx = +0, corr = forward + 0.5 * (phi - phi) = +0, and fmaxf(mn, fminf(+0, +0)) = +0: +0 everywhere, whatever the signs
+    of the inputs. (The host's fminf / fmaxf return their second operand for a tie of zeros: the stock oracle and the reference's
+    kernels built for the host give -0 on part of these voxels.) The same for the velocity advected by itself."""
+    box = Box(16)
+    K = make(box.leaves)
+    rng = np.random.default_rng(33)
+    phi = np.where(rng.random((box.B,) * 3) < 0.8, -0.0, 0.0).astype(F32)
+    vel = np.where(rng.random((box.N, 3)) < 0.8, -0.0, 0.0).astype(F32)
+    outs = [K.advect_scalar(np.zeros((box.N, 3), F32), box.to_flat(phi), 0.25, 4.0), K.advect_scalar(vel, box.to_flat(phi), 0.25, 4.0),
+            K.advect_vector(vel, 0.25, 4.0)] + list(K.advect_scalars(vel, [box.to_flat(phi)] * 5, 0.25, 4.0))
+    for got in outs:
+        assert np.all(np.asarray(got) == 0)
+        if device:
+            assert not np.signbit(np.asarray(got)).any()
+
+
+def kat_divergence_one_inf(make, device):
+    """one inf in u.x: NaN (inf - inf) at the voxel itself, +inf / -inf at its two x neighbours, every other output finite and exact"""
+    box = Box(24)
+    K = make(box.leaves)
+    rng = np.random.default_rng(34)
+    u = rng.integers(-8, 9, size=(box.B,) * 3 + (3,)).astype(np.float64)
+    q = (8, 15, 16)  # on leaf faces in all three axes
+    u[q + (0,)] = np.inf
+    got = box.to_dense(K.divergence(box.to_flat(u), 32.0)).astype(np.float64)
+    with np.errstate(invalid="ignore"):
+        want = np.zeros((box.B,) * 3)
+        for ax in range(3):
+            comp = u[..., ax]
+            want = want + (comp + shift(comp, ax, +1)) * 0.5 - (comp + shift(comp, ax, -1)) * 0.5
+        want = want * 32.0
+    assert np.isnan(want).sum() == 1 and np.isnan(want[q]) and want[7, 15, 16] == np.inf and want[9, 15, 16] == -np.inf and np.isinf(want).sum() == 2
+    assert np.array_equal(got, want, equal_nan=True)
+
+
+def kat_gradient_inf(make, device):
+    """p = +inf at q and at q + 2 e_y: u.y becomes NaN between them (inf - inf), -inf / +inf on the outer sides, u.x and u.z -inf / +inf
+    beside each; the voxels q themselves read only their neighbours and stay finite"""
+    box = Box(24)
+    K = make(box.leaves)
+    rng = np.random.default_rng(35)
+    p = rng.integers(-8, 9, size=(box.B,) * 3).astype(np.float64)
+    u = rng.integers(-8, 9, size=(box.B,) * 3 + (3,)).astype(np.float64)
+    p[7, 7, 8] = p[7, 9, 8] = np.inf
+    got = box.to_dense(K.subtract_pressure_gradient(box.to_flat(u), box.to_flat(p), 16.0)).astype(np.float64)
+    want = u.copy()
+    with np.errstate(invalid="ignore"):
+        for ax in range(3):
+            want[..., ax] = u[..., ax] - ((shift(p, ax, +1) - shift(p, ax, -1)) * 0.5) * 16.0
+    assert np.isnan(want).sum() == 1 and np.isnan(want[7, 8, 8, 1]) and np.isfinite(want[7, 7, 8]).all() and np.isinf(want).sum() == 10
+    assert np.array_equal(got, want, equal_nan=True)
+
+
+def sor_nan_reach(present: np.ndarray, start: np.ndarray, iterations: int) -> np.ndarray:
+    """Which voxels are NaN after `iterations` red-black iterations (Kernel.cu:591-623, red = even i + j + k first) from a p that is
+    NaN on `start`: a voxel of the sweep's colour becomes NaN if it is, or one of its six neighbours is; a missing neighbour is a
+    finite zero. `present`: dense mask of the domain in a box whose corner has even coordinate sum."""
+    i, j, k = np.meshgrid(*[np.arange(n) for n in present.shape], indexing="ij")
+    nan = start & present
+    for _ in range(iterations):
+        for color in (0, 1):
+            near = nan.copy()
+            for ax in range(3):
+                for s in (-1, 1):
+                    near |= shift(nan, ax, s, fill=False)
+            nan = np.where((((i + j + k) & 1) == color) & present, near, nan)
+    return nan
+
+
+def _sor_nan_case(make, leaves, plant_at, iterations=(1, 2, 3, 4)):
+    leaves = np.ascontiguousarray(leaves[fields.nanovdb_order(leaves)], dtype=np.int32)
+    K = make(leaves)
+    c = fields.leaves_to_coords(leaves)
+    lo = c.min(axis=0) - 2  # even: leaf origins are multiples of 8
+    shape = tuple((c.max(axis=0) - lo + 3).tolist())
+    at = tuple((c - lo).T)
+    present = np.zeros(shape, dtype=bool)
+    present[at] = True
+    rng = np.random.default_rng(36)
+    div = rng.standard_normal(len(c)).astype(F32)
+    for q in plant_at:
+        q = np.asarray(q)
+        start = np.zeros(shape, dtype=bool)
+        start[tuple(q - lo)] = True
+        assert present[tuple(q - lo)]
+        p0 = rng.standard_normal(len(c)).astype(F32)
+        p0[np.flatnonzero((c == q).all(1))[0]] = np.nan
+        for it in iterations:
+            got = np.asarray(K.rbgs_iterations(div, 1.0 / 32.0, 1.7, it, p0))
+            want = sor_nan_reach(present, start, it)[at]
+            assert want.sum() > 1 and want.mean() <= 0.5
+            assert np.array_equal(np.isnan(got), want), (q.tolist(), it, int(np.isnan(got).sum()), int(want.sum()))
+            assert np.isfinite(got[~want]).all()
+
+
+def kat_sor_nan_cone_dense(make, device):
+    """dense 32^3: the cone crosses the 16^3-block borders (and the leaf faces) in every axis; once from a red voxel, once from a black"""
+    _sor_nan_case(make, fields.dense_leaves(32), [(15, 16, 17), (16, 15, 8), (15, 15, 15)])
+
+
+def kat_sor_nan_cone_ragged(make, device):
+    """a ragged leaf set: the cone stops at missing leaves (their zero is finite) and goes round them"""
+    rng = np.random.default_rng(37)
+    lat = np.stack(np.meshgrid(*[np.arange(-2, 2)] * 3, indexing="ij"), -1).reshape(-1, 3)
+    leaves = (lat[rng.random(len(lat)) < 0.5] * 8).astype(np.int32)
+    leaves = leaves[fields.nanovdb_order(leaves)]
+    o = leaves[len(leaves) // 2]
+    _sor_nan_case(make, leaves, [o + (0, 0, 0), o + (7, 7, 0), o + (3, 4, 4)])
+
+
+SPECIAL_CASES = {
+    "limiter_nan_at_rest": kat_limiter_nan_at_rest,
+    "limiter_nan_corr_between_finite_bounds": kat_limiter_nan_corr_between_finite_bounds,
+    "limiter_zeros_of_both_signs": kat_limiter_zeros_of_both_signs,
+    "divergence_one_inf": kat_divergence_one_inf,
+    "gradient_inf": kat_gradient_inf,
+    "sor_nan_cone_dense": kat_sor_nan_cone_dense,
+    "sor_nan_cone_ragged": kat_sor_nan_cone_ragged,
+}

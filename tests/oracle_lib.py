@@ -12,6 +12,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ORACLE_DIR = os.path.join(ROOT, "oracle")
 _ORC = None
+_ORC_DEV = None
 _REF = None
 
 _vp, _i, _i64, _f = C.c_void_p, C.c_int, C.c_int64, C.c_float
@@ -53,6 +54,7 @@ def _bind(L):
         "orc_set_vec3_lerp_fma": (None, [_i]),
         "orc_set_threads": (None, [_i]),
         "orc_get_threads": (_i, []),
+        "orc_device_semantics": (_i, []),
         "orc_sample_nearest_f": (None, [_vp, _vp, _vp, _i64, _vp]),
         "orc_sample_trilinear_f": (None, [_vp, _vp, _vp, _i64, _vp]),
         "orc_sample_trilinear_v": (None, [_vp, _vp, _vp, _i64, _vp]),
@@ -91,6 +93,21 @@ def oracle():
         subprocess.run(["make", "-C", ORACLE_DIR, "oracle"], check=True, capture_output=True)
     _ORC = _bind(C.CDLL(path))
     return _ORC
+
+
+def oracle_device():
+    """The same source built with -DORC_DEVICE_SEMANTICS (oracle/liboracle_dev.so): min/max and the float -> cell
+    conversion behave as the GPU's instructions do for zeros of both signs, NaN and out-of-range positions (DESIGN.md
+    section 2). The comparator of tests/test_special_values*.py; use as OracleGrid(origins, lib=oracle_device())."""
+    global _ORC_DEV
+    if _ORC_DEV is not None:
+        return _ORC_DEV
+    path = os.path.join(ORACLE_DIR, "liboracle_dev.so")
+    if not os.path.exists(path):
+        subprocess.run(["make", "-C", ORACLE_DIR, "oracle_dev"], check=True, capture_output=True)
+    _ORC_DEV = _bind(C.CDLL(path))
+    assert _ORC_DEV.orc_device_semantics() == 1 and oracle().orc_device_semantics() == 0
+    return _ORC_DEV
 
 
 def oracle_contracted():

@@ -12,10 +12,11 @@ from hnanosolver_amd import fields
 pytestmark = pytest.mark.gpu
 
 
-def single_grid(origins, R, names, iters, substeps, dt=1.0 / 24.0):
+def single_grid(origins, R, names, iters, substeps, dt=1.0 / 24.0, f=None):
+    """f: a dictionary of fields in place of fields.synthetic_fields (the special-value cases)"""
     from hnanosolver_amd import api, device as D
 
-    f = fields.synthetic_fields(origins, R)
+    f = f or fields.synthetic_fields(origins, R)
     grid = api.create_grid_from_leaves(origins, 1.0 / R)
     sim = D.Sim(grid, names)
     arrays = {"vel": f["vel"].copy(), **{n: f[n].copy() for n in names}}
@@ -26,10 +27,10 @@ def single_grid(origins, R, names, iters, substeps, dt=1.0 / 24.0):
     return f, arrays
 
 
-def run_local(origins, R, world, k, names, iters, substeps, dt=1.0 / 24.0):
+def run_local(origins, R, world, k, names, iters, substeps, dt=1.0 / 24.0, f=None):
     import torch
 
-    f = fields.synthetic_fields(origins, R)
+    f = f or fields.synthetic_fields(origins, R)
     ranks = [HD.DistRank(origins, world, r, 1.0 / R, n_scalars=len(names), sweeps_per_exchange=k) for r in range(world)]
     HD.DistRank.connect_local(ranks)
     b = None  # (which leaves a rank owns is the rank's own knowledge: DistRank.owned_ids / owned_voxels)
@@ -134,6 +135,39 @@ def test_chained_ranks_two_iterations_per_launch(name, world, iters):
     and writing the reach-4 region of p into the peers' ghost voxels themselves (k_rbgs_block_xy<., PhaseMirror>); an odd
     iteration left over is one more chained launch of the same kernel with two colour sweeps instead of four. Bit-identical to the single grid."""
     _local_ranks_match_single_grid(name, world, 2, iters)
+
+
+def special_fields(origins, R, cls):
+    """the synthetic state with an input class of tests/special_cases.py planted: `zeros` into the scalars and the velocity, `nonfinite` into the scalars (a NaN in
+    the velocity would fill the pressure solve's seven iterations with NaN)"""
+    import special_cases as sc
+
+    rng = np.random.default_rng(31)
+    f = fields.synthetic_fields(origins, R)
+    for n in ("density", "temperature") + (("vel",) if cls == "zeros" else ()):
+        f[n] = sc.plant(cls, f[n], rng)
+    return f
+
+
+@pytest.mark.parametrize("cls", ["nonfinite", "zeros"])
+@pytest.mark.parametrize("name,world,k,iters", [("scattered", 5, 2, 7), ("dense64", 2, 2, 7)])
+def test_ranks_match_single_grid_on_special_values(name, world, k, iters, cls):
+    """One exchanged case and one chained case with NaN / inf in the scalars, and with zeros of both signs in everything: owned voxels equal the single grid as raw
+    32-bit words, the ghost voxels hold their owners' bits. A NaN that a halo mask fails to carry, or a ghost voxel read before it was written, shows here."""
+    origins, R = {"scattered": (scattered_leaves(), 96), "dense64": (fields.dense_leaves(64), 64)}[name]
+    names, substeps = ["density", "temperature"], 2
+    f = special_fields(origins, R, cls)
+    _, want = single_grid(origins, R, names, iters, substeps, f=f)
+    for n in names:
+        assert np.isnan(want[n]).mean() <= 0.5 and (cls != "nonfinite" or np.isnan(f[n]).any())
+    ranks, b = run_local(origins, R, world, k, names, iters, substeps, f=f)
+    n_pairs, bad = HD.DistRank.ghost_check_local(ranks)
+    assert not bad and n_pairs > 0, (n_pairs, bad[:3])
+    for r, d in enumerate(ranks):
+        got = d.download()
+        assert np.array_equal(got["vel"].view(np.uint32), d.owned_voxels(want["vel"]).view(np.uint32)), f"rank {r} velocity"
+        for n, a in zip(names, got["scalars"]):
+            assert np.array_equal(a.view(np.uint32), d.owned_voxels(want[n]).view(np.uint32)), f"rank {r} {n}"
 
 
 @pytest.mark.parametrize("k", [0, 1, 2])

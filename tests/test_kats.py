@@ -22,6 +22,16 @@ def test_oracle_known_answers(case, box_name):
     kats.CASES[case](OracleGrid(box.leaves), box)
 
 
+@pytest.mark.parametrize("build", ["stock", "device"])
+@pytest.mark.parametrize("case", list(kats.SPECIAL_CASES))
+def test_oracle_special_value_known_answers(case, build):
+    """NaN, inf and zeros of both signs (kats.SPECIAL_CASES) through both builds of the oracle: the stock one (the host's fminf / fmaxf) and the
+    device-semantics one (the GPU's symmetric min/max)"""
+    from oracle_lib import OracleGrid, oracle_device
+
+    kats.SPECIAL_CASES[case](lambda leaves: OracleGrid(leaves, lib=oracle_device() if build == "device" else None), build == "device")
+
+
 from hip_kernels import HipKernels  # noqa: E402
 
 
@@ -57,5 +67,26 @@ def test_fused_sor_forms_known_sweep(form):
     H.set_option(*form)
     try:
         kats.kat_rbgs_known_sweep(FusedSorKernels(box.leaves), box)
+    finally:
+        H.set_option(form[0], None)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", list(kats.SPECIAL_CASES))
+def test_hip_special_value_known_answers(case):
+    kats.SPECIAL_CASES[case](lambda leaves: HipKernels(leaves), True)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("form", [("sor_block_lb", "1"), ("sor_block_lb", "2"), ("rbgs", "color")])
+@pytest.mark.parametrize("case", ["sor_nan_cone_dense", "sor_nan_cone_ragged"])
+def test_sor_forms_nan_cone(case, form):
+    """the NaN's reach after K iterations through every form of the solve: a temporally blocked form that read a halo voxel an iteration early or late
+    puts the cone's edge in the wrong place"""
+    import hnanosolver_amd as H
+
+    H.set_option(*form)
+    try:
+        kats.SPECIAL_CASES[case](lambda leaves: HipKernels(leaves), True)
     finally:
         H.set_option(form[0], None)

@@ -180,3 +180,73 @@ def test_blocked_sor_over_a_launch_range(name):
             assert bool((out[keep] == 7.0).all()), f"{name} range [{first}, +{count}) lb={lb}: a leaf outside the range was written"
             assert torch.equal(p_a, p0)
         H.set_option("sor_block_lb", None)
+
+
+def special_inputs(n_leaves, seed):
+    """div and p0 with zeros of both signs, subnormals and NaN / inf (tests/special_cases.py) planted into a third of the leaves each; the non-finite third gets a
+    stated number of plantings (every iteration widens a NaN's reach by two voxels)"""
+    import special_cases as sc
+
+    rng = np.random.default_rng(seed)
+    n = n_leaves * 512
+    div, p0 = rng.standard_normal(n).astype(np.float32), rng.standard_normal(n).astype(np.float32)
+    t = max(1, n_leaves // 3) * 512
+    for a in (div, p0):
+        a[:t] = sc.plant("zeros", a[:t], rng)
+        a[t:2 * t] = sc.plant("subnormal", a[t:2 * t], rng)
+    few = 1 if n < 65536 else 4
+    p0[2 * t:] = sc.plant_few(p0[2 * t:], rng, few) if n > 2 * t else p0[2 * t:]
+    div[2 * t:] = sc.plant_few(div[2 * t:], rng, few) if n > 2 * t else div[2 * t:]
+    return torch.from_numpy(div).cuda(), torch.from_numpy(p0).cuda()
+
+
+def same_words(a, b):
+    """equal as raw 32-bit words (torch.equal on floats calls a NaN unequal to itself), except that a NaN may differ from the other form's NaN in its sign bit:
+    special_cases.nan_sign_differences says why, and what was measured"""
+    import special_cases as sc
+
+    return sc.nan_sign_differences(a.cpu().numpy(), b.cpu().numpy())[0]
+
+
+@pytest.mark.parametrize("name", ["scatter", "dense40", "int32_edge"])
+def test_blocked_sor_on_special_values(name):
+    """zeros of both signs, subnormals, NaN and inf in div and p0: the blocked forms against the two-launch form, raw 32-bit words. A NaN is the sharpest tracer of the
+    halo's dependency cone: one that arrives an iteration early or late moves the edge of the NaN region."""
+    origins = leaf_sets()[name]
+    grid = api.create_grid_from_leaves(origins, 0.013)
+    div, p0 = special_inputs(len(origins), 21)
+    for iters in (1, 2, 3, 4, 7):
+        want = solve(grid, div, p0, iters, rbgs="color")
+        share = float(torch.isnan(want).float().mean())
+        assert 0 < share <= 0.5, (name, iters, share)
+        for lb in SHAPES:
+            got = solve(grid, div, p0, iters, sor_block_lb=lb)
+            assert same_words(want, got), (name, iters, lb, int((want.view(torch.int32) != got.view(torch.int32)).sum()))
+
+
+@pytest.mark.parametrize("name", ["dense40", "plume", "scatter", "node_borders"])
+def test_blocked_sor_over_a_launch_range_on_special_values(name):
+    """test_blocked_sor_over_a_launch_range with the special values in div and p0"""
+    origins = leaf_sets()[name]
+    n_leaves = len(origins)
+    n = n_leaves * 512
+    div, p0 = special_inputs(n_leaves, n_leaves)
+    whole = api.create_grid_from_leaves(origins, 0.013)
+    want = solve(whole, div, p0, 2, rbgs="color")
+    assert 0 < float(torch.isnan(want).float().mean()) <= 0.5
+    for first, count in ((0, n_leaves // 3), (n_leaves // 3, n_leaves // 2), (n_leaves - 5, 5), (7, 1), (0, n_leaves)):
+        count = max(1, min(count, n_leaves - first))
+        part = api.create_grid_from_leaves(origins, 0.013)
+        part.set_active_range(first, count)
+        for lb in (0, 1, 2):
+            H.set_option("sor_block_lb", str(lb))
+            p_a, p_b = p0.clone(), torch.full_like(p0, 7.0)
+            out = D.rbgs_iterate(part, div, p_a, p_b, 0.013, 1.93, 2)
+            assert out is p_b
+            sl = slice(first * 512, (first + count) * 512)
+            assert same_words(out[sl], want[sl]), f"{name} range [{first}, +{count}) lb={lb}: owned leaves differ"
+            keep = torch.ones(n, dtype=torch.bool, device="cuda")
+            keep[sl] = False
+            assert bool((out[keep] == 7.0).all()), f"{name} range [{first}, +{count}) lb={lb}: a leaf outside the range was written"
+            assert same_words(p_a, p0)
+        H.set_option("sor_block_lb", None)
