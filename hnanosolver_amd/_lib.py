@@ -110,6 +110,7 @@ SIGNATURES = {
     "hns_sim_pressure_time": (_i, [_vp, C.POINTER(C.c_float), C.POINTER(C.c_longlong)]),
     "hns_sim_stage_timing": (_i, [_vp, _i]),
     "hns_sim_stage_times": (_i, [_vp, C.POINTER(C.c_float), C.POINTER(C.c_longlong)]),
+    "hns_sim_lookahead_counts": (_i, [_vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     "hns_sim_velocity_ptr": (_vp, [_vp]),
     "hns_sim_field_ptr": (_vp, [_vp, C.c_char_p]),
     "hns_sim_divergence_ptr": (_vp, [_vp]),
@@ -123,6 +124,7 @@ SIGNATURES = {
     "hns_dev_advect_vector": (_i, [_vp, _fp, _fp, _fp, _i, _f, _f, _vp]),
     "hns_dev_advect_scalar": (_i, [_vp, _fp, _fp, _fp, _fp, _i, _f, _f, _vp]),
     "hns_dev_advect_scalars": (_i, [_vp, _fp, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _i, _fp, _i, _f, _f, _vp]),
+    "hns_dev_advect_scalars_ahead": (_i, [_vp, _fp, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _i, _fp, _f, _f, _vp]),
     "hns_dev_divergence": (_i, [_vp, _fp, _fp, _f, _vp]),
     "hns_dev_rbgs_color": (_i, [_vp, _fp, _fp, _f, _f, _i, _vp]),
     "hns_dev_rbgs_iterate": (_i, [_vp, _fp, _fp, _fp, _f, _f, _i, _ip, _vp]),

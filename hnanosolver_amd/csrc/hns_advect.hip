@@ -638,8 +638,16 @@ __device__ __forceinline__ void interp_from_taps(const Taps& T, int oob, int (&i
 // kernel is bound by L1 accesses per gather instruction (profiles/r05_advect_notes.txt 2), and a quad of lanes costs an access whatever its width -- sixteen
 // gathers for the four fields' two samples instead of thirty-two. Per field the arithmetic is the same chain of fused multiply-adds in the same order.
 // (at least four waves per SIMD = two workgroups per CU: the Q4 form sits at the 128-register line, and one register over it is ONE workgroup per CU -- 585 -> 838 us at 256^3, measured)
-template <bool Q4>
-__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(Q4 ? 6 : 4))) void k_advect_scalars_n(const GridDev g, const float* __restrict__ u, const ScalarPtrs P, const float scaled_dt) {
+// AHEAD (float-only form): the look-ahead launch of a substep's part C. The NEXT substep's advect_vector reads this same velocity with this same scaled_dt, so its own-velocity load,
+// its table staging, its back position, its eight tap offsets and its eight 12-byte gathers are the ones made here. The kernel writes advect_vector(u) of its voxels to adv_out as
+// well: both first samples are formed from the one set of taps (nested lerps for the vector, weight products for the fields: different bits); the vector's sample then waits in LDS
+// while the fields are advected, and BEHIND the per-field loop the vector half takes its second sample from a velocity box (rows kVY apart, as k_advect_vector_n), clamps and stores.
+// That order is the one that fits 80 registers without a spill (70; the vector half in front of the loop: 100, profiles/lookahead_ab.txt): three workgroups per CU, by registers and by
+// LDS (43 KB) alike. Same loads of the same values, same arithmetic in the same association as k_advect_vector_n and k_advect_scalars_n<false>: bit-identical to the two launches.
+template <bool Q4, bool AHEAD = false>
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(Q4 || AHEAD ? 6 : 4))) void k_advect_scalars_n(const GridDev g, const float* __restrict__ u, const ScalarPtrs P, const float scaled_dt,
+                                                                                                            float* __restrict__ adv_out) {
+	static_assert(!(Q4 && AHEAD), "the look-ahead form is float-only");
 	__shared__ int s_nbr[27];
 	__shared__ int s_base[27];
 	__shared__ unsigned s_b4[27];
@@ -687,41 +695,94 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(Q4 ? 6 : 4)
 	const unsigned sx_ = (unsigned)(bi - (L.org.x - 1)), sy_ = (unsigned)(bj - (L.org.y - 1)), sz_ = (unsigned)(bk - (L.org.z - 1));
 	const bool bboxed = FIRST && max(sx_, max(sy_, sz_)) <= 8u;
 	const int ba = bboxed ? (int)((sx_ * 10u + sy_) * 10u + sz_) : 0;  // box cell of the back cell's lower corner
-	{
-		float tx, ty, tz;
-		if (bboxed) {
-			tx = bx - (float)bi, ty = by - (float)bj, tz = bz - (float)bk;  // (make_taps_b's fractions)
-#pragma unroll
-			for (int q = 0; q < 8; ++q) bo[q] = 0u;
-		} else {
-			const TapsB T = make_taps_b(g, s_nbr, s_b4p, L.org, bx, by, bz);
-			tx = T.fx, ty = T.fy, tz = T.fz;
-#pragma unroll
-			for (int q = 0; q < 8; ++q) bo[q] = T.o[perm[q]] >= kOutside ? oob4 : T.o[perm[q]];
+	f3 vf = {0.0f, 0.0f, 0.0f};
+	// AHEAD: the velocity box of k_advect_vector_n (shell cells outside the domain read 0 there -- the descriptor's bounds check -- not element g.oob), this voxel's cell in
+	// it, and advect_vector's first sample
+	__shared__ float s_vbox[AHEAD ? 3 * kVP : 1];
+	__shared__ float s_wf[AHEAD ? 3 * 512 : 1];  // (advect_vector's first sample waits here, not in three registers, while the fields are advected)
+	if constexpr (AHEAD) {
+		const int obv = ((n >> 6) + 1) * kVX + (((n >> 3) & 7) + 1) * kVY + (n & 7) + 1;
+		s_vbox[obv] = vc.x, s_vbox[obv + kVP] = vc.y, s_vbox[obv + 2 * kVP] = vc.z;
+		f3 hv = {0.0f, 0.0f, 0.0f};
+		int vcell = 0;
+		if (n < kBoxShell) {
+			int slot, local;
+			box_shell_entry<kVX, kVY>(n, slot, local, vcell);
+			hv = ldv(ru, s_b4[slot] + ((unsigned)local << 2));
 		}
-		const float itx = 1.0f - tx, ity = 1.0f - ty, itz = 1.0f - tz;
-		const float w00 = itx * ity, w10 = tx * ity, w01 = itx * ty, w11 = tx * ty;
-		bw[0] = w00 * itz, bw[1] = w10 * itz, bw[2] = w01 * itz, bw[3] = w11 * itz, bw[4] = w00 * tz, bw[5] = w10 * tz, bw[6] = w01 * tz, bw[7] = w11 * tz;
-	}
-	f3 vt[8];
-	if (!bboxed) {
-#pragma unroll
-		for (int q = 0; q < 8; ++q) vt[q] = ldv(ru, bo[q]);
-	}
-	if constexpr (FIRST) __syncthreads();  // velocity box complete
-	if (bboxed) {
+		// the eight taps of the back cell, gathered ONCE with the unmapped offsets: 0 outside the domain, which is what advect_vector samples
+		const TapsB T = make_taps_b(g, s_nbr, s_b4p, L.org, bx, by, bz);
+		V3 c[8];  // (issued in the order the weight products consume them: the z lerp of a column follows as soon as its second tap has been added, and the pair's registers are free)
 #pragma unroll
 		for (int q = 0; q < 8; ++q) {
-			const int a = ba + (q & 1) * 100 + ((q >> 1) & 1) * 10 + (q >> 2);
-			vt[q] = f3{s_ubox[a], s_ubox[a + kBox], s_ubox[a + 2 * kBox]};
+			const v3f v = hns_buffer_load_v3f32(ru, (int)(T.o[perm[q]] + (T.o[perm[q]] << 1)), 0, 0);
+			c[perm[q]].xy = v2f32{v.x, v.y};
+			c[perm[q]].z = v.z;
 		}
-	}
-	f3 vf = {0.0f, 0.0f, 0.0f};
+		const float* __restrict__ uoob = u + 3 * (size_t)g.oob;
+		const f3 uo = {uoob[0], uoob[1], uoob[2]};  // what advect_scalars samples outside the domain: element g.oob (a uniform address: scalar registers)
+		if (n < kBoxShell) s_vbox[vcell] = hv.x, s_vbox[vcell + kVP] = hv.y, s_vbox[vcell + 2 * kVP] = hv.z;
+		{
+			const float tx = T.fx, ty = T.fy, tz = T.fz;
+			const float itx = 1.0f - tx, ity = 1.0f - ty, itz = 1.0f - tz;
+			const float w00 = itx * ity, w10 = tx * ity, w01 = itx * ty, w11 = tx * ty;
+			bw[0] = w00 * itz, bw[1] = w10 * itz, bw[2] = w01 * itz, bw[3] = w11 * itz, bw[4] = w00 * tz, bw[5] = w10 * tz, bw[6] = w01 * tz, bw[7] = w11 * tz;
+		}
+		// Two samples from the one set of taps. advect_scalars': the weight products, velF = velF + v * w (Kernel.cu:201-206), unfused, a tap outside the domain replaced by
+		// element g.oob. advect_vector's: nested lerps (tri_v_b) -- column z[t >> 1] = lerp(c[t - 1], c[t]) once the odd tap t has been added.
+		V3 z[4];
 #pragma unroll
-	for (int q = 0; q < 8; ++q) {  // velF = velF + v * w (Kernel.cu:201-206), unfused
-		vf.x = vf.x + bw[q] * vt[q].x;
-		vf.y = vf.y + bw[q] * vt[q].y;
-		vf.z = vf.z + bw[q] * vt[q].z;
+		for (int q = 0; q < 8; ++q) {
+			const int t = perm[q];
+			const bool outside = T.o[t] >= kOutside;
+			bo[q] = outside ? oob4 : T.o[t];
+			const float tx = outside ? uo.x : c[t].xy.x, ty = outside ? uo.y : c[t].xy.y, tz = outside ? uo.z : c[t].z;
+			vf.x = vf.x + bw[q] * tx;
+			vf.y = vf.y + bw[q] * ty;
+			vf.z = vf.z + bw[q] * tz;
+			if (t & 1) z[t >> 1] = lerp_v3(c[t - 1], c[t], T.fz);
+		}
+		{
+			const V3 y0 = lerp_v3(z[0], z[1], T.fy), y1 = lerp_v3(z[2], z[3], T.fy);
+			const V3 r = lerp_v3(y0, y1, T.fx);
+			s_wf[n] = r.xy.x, s_wf[n + 512] = r.xy.y, s_wf[n + 1024] = r.z;
+		}
+	} else {
+		{
+			float tx, ty, tz;
+			if (bboxed) {
+				tx = bx - (float)bi, ty = by - (float)bj, tz = bz - (float)bk;  // (make_taps_b's fractions)
+#pragma unroll
+				for (int q = 0; q < 8; ++q) bo[q] = 0u;
+			} else {
+				const TapsB T = make_taps_b(g, s_nbr, s_b4p, L.org, bx, by, bz);
+				tx = T.fx, ty = T.fy, tz = T.fz;
+#pragma unroll
+				for (int q = 0; q < 8; ++q) bo[q] = T.o[perm[q]] >= kOutside ? oob4 : T.o[perm[q]];
+			}
+			const float itx = 1.0f - tx, ity = 1.0f - ty, itz = 1.0f - tz;
+			const float w00 = itx * ity, w10 = tx * ity, w01 = itx * ty, w11 = tx * ty;
+			bw[0] = w00 * itz, bw[1] = w10 * itz, bw[2] = w01 * itz, bw[3] = w11 * itz, bw[4] = w00 * tz, bw[5] = w10 * tz, bw[6] = w01 * tz, bw[7] = w11 * tz;
+		}
+		f3 vt[8];
+		if (!bboxed) {
+#pragma unroll
+			for (int q = 0; q < 8; ++q) vt[q] = ldv(ru, bo[q]);
+		}
+		if constexpr (FIRST) __syncthreads();  // velocity box complete
+		if (bboxed) {
+#pragma unroll
+			for (int q = 0; q < 8; ++q) {
+				const int a = ba + (q & 1) * 100 + ((q >> 1) & 1) * 10 + (q >> 2);
+				vt[q] = f3{s_ubox[a], s_ubox[a + kBox], s_ubox[a + 2 * kBox]};
+			}
+		}
+#pragma unroll
+		for (int q = 0; q < 8; ++q) {  // velF = velF + v * w (Kernel.cu:201-206), unfused
+			vf.x = vf.x + bw[q] * vt[q].x;
+			vf.y = vf.y + bw[q] * vt[q].y;
+			vf.z = vf.z + bw[q] * vt[q].z;
+		}
 	}
 	// The second sample point is the voxel's own position up to s * (u(back) - u(own)): where it lands inside the leaf's 10^3 box (k_advect_vector_n, which see)
 	// the fields' forward taps are read from the LDS box that the clamp needs anyway, not gathered
@@ -833,6 +894,51 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(Q4 ? 6 : 4)
 		mn = fminf(mn, phiF);
 		mx = fmaxf(mx, phiF);
 		P.out[s][idx] = fmaxf(mn, fminf(phiCorr, mx));
+	}
+	if constexpr (AHEAD) {
+		// The rest of advect_vector (k_advect_vector_n from its second pass on) comes LAST and holds no register across the field loop, where the fields' two sets of tap
+		// offsets and weights held across the vector half cost sixteen. The voxel's own velocity and its back position are formed again from the box.
+		__syncthreads();  // velocity box complete (with no field the loop above held no barrier)
+		int m = n;
+		asm volatile("" : "+v"(m));  // (the voxel's position and box cell are formed again here, not kept in registers from the top of the kernel)
+		const int obv = ((m >> 6) + 1) * kVX + (((m >> 3) & 7) + 1) * kVY + (m & 7) + 1;
+		const float wx = (float)(L.org.x + (m >> 6)), wy = (float)(L.org.y + ((m >> 3) & 7)), wz = (float)(L.org.z + (m & 7));
+		const f3 vo = f3{s_vbox[obv], s_vbox[obv + kVP], s_vbox[obv + 2 * kVP]};
+		const f3 wf = f3{s_wf[m], s_wf[m + 512], s_wf[m + 1024]};
+		const float cx = wx - scaled_dt * vo.x, cy = wy - scaled_dt * vo.y, cz = wz - scaled_dt * vo.z;  // backPos (Kernel.cu:374)
+		const float sx = cx + scaled_dt * wf.x, sy = cy + scaled_dt * wf.y, sz = cz + scaled_dt * wf.z;  // Kernel.cu:387
+		const int i = __float2int_rd(sx), j = __float2int_rd(sy), k = __float2int_rd(sz);
+		const unsigned ux = (unsigned)(i - (L.org.x - 1)), uy = (unsigned)(j - (L.org.y - 1)), uz = (unsigned)(k - (L.org.z - 1));
+		f3 wb;
+		if (__all(max(ux, max(uy, uz)) <= 8u)) {
+			wb = tri_v_box(s_vbox, (int)(ux * (unsigned)kVX + uy * (unsigned)kVY + uz), sx - (float)i, sy - (float)j, sz - (float)k);
+		} else {
+			const TapsB T2 = make_taps_b(g, s_nbr, s_b4p, L.org, sx, sy, sz);
+			wb = tri_v_b(ru, T2);
+		}
+		f3 wc = {wf.x + 0.5f * (vo.x - wb.x), wf.y + 0.5f * (vo.y - wb.y), wf.z + 0.5f * (vo.z - wb.z)};
+		const int ev[6] = {obv - kVX, obv + kVX, obv - kVY, obv + kVY, obv - 1, obv + 1};
+		f3 vmn = vo, vmx = vo;
+#pragma unroll
+		for (int d = 0; d < 6; ++d) {
+			const V3 t = box_v3(s_vbox, ev[d]);
+			vmn.x = fminf(vmn.x, t.xy.x);
+			vmx.x = fmaxf(vmx.x, t.xy.x);
+			vmn.y = fminf(vmn.y, t.xy.y);
+			vmx.y = fmaxf(vmx.y, t.xy.y);
+			vmn.z = fminf(vmn.z, t.z);
+			vmx.z = fmaxf(vmx.z, t.z);
+		}
+		vmn.x = fminf(vmn.x, wf.x);
+		vmx.x = fmaxf(vmx.x, wf.x);
+		vmn.y = fminf(vmn.y, wf.y);
+		vmx.y = fmaxf(vmx.y, wf.y);
+		vmn.z = fminf(vmn.z, wf.z);
+		vmx.z = fmaxf(vmx.z, wf.z);
+		wc.x = fmaxf(vmn.x, fminf(wc.x, vmx.x));
+		wc.y = fmaxf(vmn.y, fminf(wc.y, vmx.y));
+		wc.z = fmaxf(vmn.z, fminf(wc.z, vmx.z));
+		st3(adv_out, idx, wc);
 	}
 }
 
@@ -976,12 +1082,41 @@ int hns_dev_advect_scalars(hns_grid* g, const float* vel3, const float* const* i
 			// backwards: the gradient kernel has just written the velocity front to back; starting on its cached tail also
 			// leaves the head cached for the next substep's advect_vector (256^3: -1 % here, -4 % there).
 			gd.rev = 1;
-			hipLaunchKernelGGL(k_advect_scalars_n<false>, grid, block, 0, (hipStream_t)stream, gd, vel3, P, scaled_dt);
+			hipLaunchKernelGGL(k_advect_scalars_n<false>, grid, block, 0, (hipStream_t)stream, gd, vel3, P, scaled_dt, (float*)nullptr);
 		}
 		else
 			hipLaunchKernelGGL(k_advect_scalars<false>, grid, block, 0, (hipStream_t)stream, g->dev(), vel3, P, sdf, scaled_dt);
 	}
 	return launch_status("hns_dev_advect_scalars");
+}
+
+// can this grid take the look-ahead launch (hns_dev_advect_scalars_ahead)?
+bool hns_advect_ahead_ok(const hns_grid* g) { return narrow_fields(g); }
+
+// advect_scalars over n float fields (at most HNS_MAX_SCALARS, no collision field) AND advect_vector of the same velocity into adv_out3, one launch (k_advect_scalars_n<false, true>).
+// Every output is bit-identical to hns_dev_advect_scalars followed by hns_dev_advect_vector with the same arguments. Applies where the 32-bit addressed kernels do.
+int hns_dev_advect_scalars_ahead(hns_grid* g, const float* vel3, const float* const* in, float* const* out, int n, float* adv_out3, float dt, float inv_dx, void* stream) {
+	if (int rc = check_grid(g, "hns_dev_advect_scalars_ahead")) return rc;
+	NULLCHK(!vel3 || !adv_out3 || (n > 0 && (!in || !out)), "hns_dev_advect_scalars_ahead");
+	if (vel3 == adv_out3) return fail(HNS_ERR_INVALID_ARGUMENT, "hns_dev_advect_scalars_ahead: adv_out3 must not alias vel3");
+	if (n < 0 || n > HNS_MAX_SCALARS) return fail(HNS_ERR_INVALID_ARGUMENT, "hns_dev_advect_scalars_ahead: between 0 and 8 fields");
+	if (!narrow_fields(g)) return fail(HNS_ERR_INVALID_ARGUMENT, "hns_dev_advect_scalars_ahead: grid too large for 32-bit offsets (or option advect = generic)");
+	if (g->n_active == 0) return HNS_OK;
+	ScalarPtrs P;
+	P.n = n;
+	P.q4 = nullptr, P.q4_out[0] = P.q4_out[1] = P.q4_out[2] = P.q4_out[3] = nullptr;
+	for (int s = 0; s < HNS_MAX_SCALARS; ++s) {
+		P.in[s] = s < n ? in[s] : nullptr;
+		P.out[s] = s < n ? out[s] : nullptr;
+		if (s < n && (!P.in[s] || !P.out[s])) {
+			set_error("hns_dev_advect_scalars_ahead: null device pointer for field %d", s);
+			return HNS_ERR_INVALID_ARGUMENT;
+		}
+	}
+	GridDev gd = g->dev();
+	gd.rev = 1;  // (as hns_dev_advect_scalars)
+	hipLaunchKernelGGL((k_advect_scalars_n<false, true>), dim3((unsigned)g->n_active), dim3(512), 0, (hipStream_t)stream, gd, vel3, P, dt * inv_dx, adv_out3);
+	return launch_status("hns_dev_advect_scalars_ahead");
 }
 
 // advect_scalars over the four fields of `q4` (one 16-byte element per voxel in, four float arrays out) and n more float fields, one launch (hns_sim_substep; no collision
@@ -1006,7 +1141,7 @@ int hns_advect_scalars_q4(hns_grid* g, const float* vel3, const float* q4, float
 	}
 	GridDev gd = g->dev();
 	gd.rev = 1;  // (as hns_dev_advect_scalars)
-	hipLaunchKernelGGL(k_advect_scalars_n<true>, dim3((unsigned)g->n_active), dim3(512), 0, (hipStream_t)stream, gd, vel3, P, dt * inv_dx);
+	hipLaunchKernelGGL(k_advect_scalars_n<true>, dim3((unsigned)g->n_active), dim3(512), 0, (hipStream_t)stream, gd, vel3, P, dt * inv_dx, (float*)nullptr);
 	return launch_status("hns_advect_scalars_q4");
 }
 

@@ -219,7 +219,18 @@ extern "C" int hns_sim_download(hns_sim* s, hns_field* fields, int n_fields, voi
 	return HNS_OK;
 }
 
-extern "C" float* hns_sim_velocity_ptr(hns_sim* s) { return s ? s->vel : nullptr; }
+extern "C" float* hns_sim_velocity_ptr(hns_sim* s) {
+	if (!s) return nullptr;
+	s->ahead_off = true;  // a writable pointer the library cannot watch: this sim never looks ahead again (include/hns.h)
+	s->drop_ahead();
+	return s->vel;
+}
+// How often a substep of this sim launched the look-ahead form of advect_scalars, and how often one skipped its advect_vector launch for it (tests, profiles).
+extern "C" int hns_sim_lookahead_counts(hns_sim* s, long long* produced, long long* consumed) {
+	if (!s || !produced || !consumed) return fail(HNS_ERR_INVALID_ARGUMENT, "hns_sim_lookahead_counts: null argument");
+	*produced = s->ahead_produced, *consumed = s->ahead_consumed;
+	return HNS_OK;
+}
 extern "C" float* hns_sim_field_ptr(hns_sim* s, const char* name) {
 	if (!s || !name) return nullptr;
 	const int k = s->find(name);
@@ -296,7 +307,8 @@ extern "C" int hns_sim_pressure_time(hns_sim* s, float* total_ms, long long* lau
 	return HNS_OK;
 }
 
-static int sim_advect_scalars(hns_sim* s, const float* sdf, bool coll, float dt, float inv_dx, void* stream) {
+// *ahead (in): also leave advect_vector(s->vel, dt) in s->adv, where one launch can (out: it was done)
+static int sim_advect_scalars(hns_sim* s, const float* sdf, bool coll, float dt, float inv_dx, void* stream, bool* ahead) {
 	std::vector<const float*> ins;
 	std::vector<float*> outs;
 	std::vector<int> which;
@@ -306,8 +318,11 @@ static int sim_advect_scalars(hns_sim* s, const float* sdf, bool coll, float dt,
 		outs.push_back(s->nxt[i]);
 		which.push_back((int)i);
 	}
-	HNS_TRY(hns_dev_advect_scalars(s->grid, s->vel, ins.data(), outs.data(), (int)ins.size(), sdf, coll, dt, inv_dx,
-	                               stream));
+	*ahead = *ahead && !coll && !ins.empty() && ins.size() <= 8 && hns_advect_ahead_ok(s->grid);
+	if (*ahead)
+		HNS_TRY(hns_dev_advect_scalars_ahead(s->grid, s->vel, ins.data(), outs.data(), (int)ins.size(), s->adv, dt, inv_dx, stream));
+	else
+		HNS_TRY(hns_dev_advect_scalars(s->grid, s->vel, ins.data(), outs.data(), (int)ins.size(), sdf, coll, dt, inv_dx, stream));
 	for (int i : which) std::swap(s->cur[i], s->nxt[i]);
 	return HNS_OK;
 }
@@ -323,7 +338,17 @@ static int sim_advect_scalars(hns_sim* s, const float* sdf, bool coll, float dt,
 // buoyancy (hns_divergence_combust_buoyancy: 60 B/voxel instead of 16 + 40 + 28) that leaves the four combustion fields as one 16-byte element per voxel in s->q4, and
 // part C gathers those four from there (hns_advect_scalars_q4: a corner tap of the four is one gather, not four). Same expressions in the same order per voxel:
 // bit-identical to the separate launches, which remain the path with a collision field and the hns_dev_* entry points.
+// Look-ahead (option "lookahead"): advect_scalars of substep n and advect_vector of substep n + 1 read the same velocity -- s->vel after the gradient subtraction -- with the same
+// dt, and make the same backtrace: own velocity, neighbour tables, back position, eight tap offsets, eight 12-byte gathers. Where part C runs the float-only 32-bit form in one
+// launch and there is no collision field it launches the look-ahead form (hns_dev_advect_scalars_ahead), which leaves advect_vector(s->vel, dt) in s->adv (dead since the
+// gradient kernel read it) and notes what that memo is valid for; the next part A, called with exactly these arguments, skips its advect_vector launch. Bit-identical, one
+// stream, 28 launches per core substep in steady state instead of 29. Every other writer of vel or adv drops the memo (hns_sim::drop_ahead).
 namespace {
+uint32_t float_bits(float x) {
+	uint32_t b;
+	memcpy(&b, &x, 4);
+	return b;
+}
 struct Substep {
 	hns_sim* s;
 	int iterations;
@@ -331,6 +356,7 @@ struct Substep {
 	const hns_combustion_params* params;  // null: the core substep
 	int ci[4];
 	bool coll = false, fused = false;
+	bool ahead_live = false;  // this substep may consume and produce the look-ahead memo
 	const float* sdf = nullptr;
 	void* stream;
 	hipEvent_t* stage_events = nullptr;  // six events of hns_sim_stage_timing, or null
@@ -348,6 +374,16 @@ struct Substep {
 		inv_dx = 1.0f / vs;
 		params = prm;
 		stream = st;
+		ahead_live = !s->ahead_off && options().lookahead.load() != kLookaheadOff;
+		if (ahead_live) {  // neither produce nor consume while the stream is captured: a replayed graph writes vel and adv unseen, so such a sim stops looking ahead for good
+			hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+			if (hipStreamIsCapturing((hipStream_t)stream, &cs) != hipSuccess) {
+				(void)hipGetLastError();
+				cs = hipStreamCaptureStatusActive;
+			}
+			if (cs != hipStreamCaptureStatusNone) ahead_live = false, s->ahead_off = true;
+		}
+		if (!ahead_live) s->drop_ahead();
 		if (!full()) return HNS_OK;
 		if (s->names.empty()) return fail(HNS_ERR_RUNTIME, "No float blocks found in input data.");  // :61-63
 		for (int c = 0; c < 4; ++c) {                                                                 // :193-201
@@ -370,8 +406,15 @@ struct Substep {
 	int part_a() {
 		hns_grid* g = s->grid;
 		HNS_TRY(mark(0));
+		const hns_sim::Ahead& m = s->ahead;
+		const bool memo = ahead_live && !coll && m.valid && m.grid == g && m.first == g->first_active && m.n_active == g->n_active && m.dt_bits == float_bits(dt) &&
+		                  m.vs_bits == float_bits(voxel_size);
+		s->drop_ahead();  // (from here on the substep overwrites adv, then vel)
 		if (coll) HNS_TRY(hns_dev_enforce_collision_boundaries(g, s->vel, sdf, voxel_size, stream));  // :153-157
-		HNS_TRY(hns_dev_advect_vector(g, s->vel, s->adv, sdf, coll, dt, inv_dx, stream));  // :162-170
+		if (memo)
+			++s->ahead_consumed;  // s->adv holds advect_vector(s->vel, dt) already: the previous substep's part C
+		else
+			HNS_TRY(hns_dev_advect_vector(g, s->vel, s->adv, sdf, coll, dt, inv_dx, stream));  // :162-170
 		if (full() && (int)params->factorScale != 0) {  // :172-176. With (int)factorScale == 0 every vorticity-magnitude tap collapses onto the centre, the
 			// gradient is 0, N = 0/(0+1e-5) = 0 and the kernel writes u + dt*(scale*0) = u: a bit-exact copy, skipped.
 			HNS_TRY(hns_dev_vorticity_confinement(g, s->adv, s->tmp, dt, inv_dx,
@@ -407,7 +450,18 @@ struct Substep {
 	}
 	int part_c() {  // :321-356
 		HNS_TRY(mark(4));
-		if (!fused) return sim_advect_scalars(s, sdf, coll, dt, inv_dx, stream);
+		// speculate? lookahead = 1: always; auto: when the previous substep call on this sim had this dt and voxel size (a lone substep, or a changing dt, pays nothing)
+		const uint32_t dtb = float_bits(dt), vsb = float_bits(voxel_size);
+		bool ahead = ahead_live && !fused && (options().lookahead.load() == kLookaheadOn || (s->have_last && s->last_dt_bits == dtb && s->last_vs_bits == vsb));
+		s->have_last = true, s->last_dt_bits = dtb, s->last_vs_bits = vsb;
+		if (!fused) {
+			HNS_TRY(sim_advect_scalars(s, sdf, coll, dt, inv_dx, stream, &ahead));
+			if (ahead) {
+				s->ahead = hns_sim::Ahead{true, s->grid, s->grid->first_active, s->grid->n_active, dtb, vsb};
+				++s->ahead_produced;
+			}
+			return HNS_OK;
+		}
 		std::vector<const float*> ins;
 		std::vector<float*> outs;
 		float* q4_out[4];
@@ -526,6 +580,7 @@ int make_sim(hns_grid* g, const std::vector<hns_field*>& floats, SimGuard& guard
 		}
 	}
 	if (guard.s) {
+		guard.s->ahead_off = true, guard.s->drop_ahead();  // (operator calls upload a velocity per call and write vel / adv themselves: nothing to look ahead for)
 		// A fresh sim starts zeroed and a substep only writes the active leaves; with an active prefix
 		// (hns_grid_set_active_leaves) restore that guarantee for everything a kernel may read across a leaf face.
 		if (g->n_active != (uint64_t)g->topo.n_leaves) {
@@ -544,6 +599,7 @@ int make_sim(hns_grid* g, const std::vector<hns_field*>& floats, SimGuard& guard
 	int err = HNS_OK;
 	// every operator writes each buffer before it reads it when all leaves are active, so the new memory is not cleared
 	guard.s = sim_create(g, names.data(), (int)names.size(), g->n_active != (uint64_t)g->topo.n_leaves, stream, &err);
+	if (guard.s) guard.s->ahead_off = true;
 	if (err != HNS_OK || !use_cache) return err;
 	std::lock_guard<std::mutex> lock(g->host_mutex);
 	if (g->sim_cache.size() >= 2) {  // evict the oldest entry that is not lent out

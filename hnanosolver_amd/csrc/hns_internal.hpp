@@ -99,6 +99,7 @@ struct DeviceScope {
 // Every entry point reads the current value when it is called, so a test or benchmark can switch forms between calls.
 enum { kRbgsAuto = 0, kRbgsColor = 1 };
 enum { kScheduleAuto = 0, kScheduleLinear = 1 };
+enum { kLookaheadAuto = 0, kLookaheadOff = 1, kLookaheadOn = 2 };
 struct Options {
 	std::atomic<int> rbgs{kRbgsAuto};          // "rbgs": auto | color (the reference's two launches per iteration: the independent cross-check)
 	std::atomic<int> advect_generic{0};        // "advect": auto | generic (64-bit addressed kernels)
@@ -108,6 +109,7 @@ struct Options {
 	std::atomic<int> cook_pipeline{1};         // "cook_pipeline": hns_compute_sim overlaps transfers with the substep
 	std::atomic<int> divergence_form{0};       // "divergence": 0 auto (by size) | 1 row | 2 coalesced (own leaf fetched in memory order, handed to the row owners through LDS) | 3 zpair (coalesced, two z-adjacent leaves per workgroup)
 	std::atomic<int> fuse_pointwise{1};        // "fuse": hns_sim_substep / hns_compute_sim without a collision field run divergence + combustion + buoyancy as one launch and advect the four combustion fields out of one 16-byte-per-voxel array
+	std::atomic<int> lookahead{kLookaheadAuto};  // "lookahead": auto | 0 | 1 -- a substep's advect_scalars also computes the NEXT substep's advect_vector (hns_api.hip: Substep); auto: only when the previous substep on the sim had the same dt and voxel size
 	std::atomic<int> sor_block_lb{0};          // "sor_block_lb": block edge of the temporally blocked SOR in leaves, 0 = by size | 1 | 2 (the tests' way to every kernel on every grid)
 	std::atomic<int> dist_wire_us{0};          // "dist_wire_us": loopback transport only, emulated time on the wire per exchange
 	std::atomic<int> dist_mirror{1};           // "dist_mirror": 1 | 0 | guarded -- over the ipc / local transports a rank of 16^3 blocks with sweeps_per_exchange = 2 runs the CHAINED substep (every kernel delivers its own halo); 0 = the exchanged substep (what RCCL ranks run)
@@ -246,7 +248,22 @@ struct hns_sim {
 	Handed handed_vel;
 	std::vector<Handed> handed_cur;  // one per float field (sized where `names` is fixed: sim_create)
 	static constexpr int kVelocity = -1, kEverything = -2;
+	// Look-ahead (hns_api.hip: Substep): `adv` as a memo of advect_vector(vel, dt), filled by a substep's advect_scalars launch and consumed by the next substep in place of
+	// its advect_vector launch. Valid for exactly one grid, dt and voxel size (compared by their bits), and only until something other than the substep writes vel or adv.
+	struct Ahead {
+		bool valid = false;
+		const hns_grid* grid = nullptr;
+		uint64_t first = 0, n_active = 0;  // the grid's launch range
+		uint32_t dt_bits = 0, vs_bits = 0;
+	};
+	Ahead ahead;
+	bool ahead_off = false;     // for good: the velocity pointer was handed out, the sim is lent to operator calls, or a substep was captured into a graph
+	bool have_last = false;     // option lookahead = auto: dt and voxel size of the previous substep call
+	uint32_t last_dt_bits = 0, last_vs_bits = 0;
+	long long ahead_produced = 0, ahead_consumed = 0;  // hns_sim_lookahead_counts
+	void drop_ahead() { ahead.valid = false; }
 	void forget(int k = kEverything) {  // float field k, the velocity or everything: the buffer no longer holds what the caller was handed
+		drop_ahead();
 		if (k == kEverything || k == kVelocity) handed_vel = Handed{};
 		for (size_t i = 0; i < handed_cur.size(); ++i)
 			if (k == kEverything || k == (int)i) handed_cur[i] = Handed{};
@@ -303,6 +320,7 @@ extern "C" __attribute__((visibility("hidden"))) int hns_divergence_combust_buoy
 extern "C" __attribute__((visibility("hidden"))) int hns_advect_scalars_q4(hns_grid* g, const float* vel3, const float* q4, float* const* q4_out, const float* const* in,
                                                                             float* const* out, int n, float dt, float inv_dx, void* stream);
 extern "C" __attribute__((visibility("hidden"))) bool hns_advect_q4_ok(const hns_grid* g);
+extern "C" __attribute__((visibility("hidden"))) bool hns_advect_ahead_ok(const hns_grid* g);  // hns_advect.hip: does hns_dev_advect_scalars_ahead apply to this grid?
 
 // implemented in hns_pointwise.hip: combustion_oxygen split into its divergence update (needs fuel, waste) and the rest (hns_dist_*.hip: the boundary leaves' divergence first)
 extern "C" __attribute__((visibility("hidden"))) int hns_combustion_div(const float* fuel, const float* waste, float* divergence, float expansion, uint64_t n,

@@ -891,6 +891,7 @@ extern "C" int hns_sim_deactivate(hns_sim* s, const hns_activity_field* fields, 
 		return rc;
 	}
 	s->d_masks = masks, s->masks_bytes = masks_bytes;
+	s->drop_ahead();  // (the end of a frame: the next substep belongs to another one)
 	if (counts) {
 		unsigned long long packed = 0;
 		HNS_HIP(hipMemcpyAsync(&packed, d_count, sizeof(packed), hipMemcpyDeviceToHost, st));

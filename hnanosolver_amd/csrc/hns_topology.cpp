@@ -140,6 +140,7 @@ const char* const kWordsBool[] = {"0", "1", nullptr};
 const char* const kWordsMirror[] = {"0", "1", "guarded", nullptr};
 const char* const kWordsUnsplit[] = {"0", "1", "always", nullptr};
 const char* const kWordsDivergence[] = {"auto", "row", "coalesced", "zpair", nullptr};
+const char* const kWordsLookahead[] = {"auto", "0", "1", nullptr};
 const OptionDesc kOptions[] = {
     {"rbgs", &Options::rbgs, kWordsRbgs},
     {"advect", &Options::advect_generic, kWordsAdvect},
@@ -149,6 +150,7 @@ const OptionDesc kOptions[] = {
     {"cook_pipeline", &Options::cook_pipeline, kWordsBool},
     {"divergence", &Options::divergence_form, kWordsDivergence},
     {"fuse", &Options::fuse_pointwise, kWordsBool},
+    {"lookahead", &Options::lookahead, kWordsLookahead},
     {"sor_block_lb", &Options::sor_block_lb, nullptr},
     {"dist_wire_us", &Options::dist_wire_us, nullptr},
     {"dist_mirror", &Options::dist_mirror, kWordsMirror},

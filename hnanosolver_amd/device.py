@@ -56,6 +56,15 @@ def advect_scalars(grid: IndexGridHandle, u, srcs: Sequence, dsts: Sequence, dt:
     return dsts
 
 
+def advect_scalars_ahead(grid: IndexGridHandle, u, srcs: Sequence, dsts: Sequence, adv_out, dt: float, inv_dx: float):
+    """advect_scalars over `srcs` and advect_vector(u) into `adv_out`, one launch (``hns_dev_advect_scalars_ahead``)."""
+    n = len(srcs)
+    ins = (C.c_void_p * max(1, n))(*[_ptr(t) for t in srcs])
+    outs = (C.c_void_p * max(1, n))(*[_ptr(t) for t in dsts])
+    _raise(lib.hns_dev_advect_scalars_ahead(grid.ptr, _ptr(u), ins, outs, n, _ptr(adv_out), dt, inv_dx, current_stream()))
+    return dsts, adv_out
+
+
 def divergence(grid: IndexGridHandle, u, div, inv_dx: float):
     _raise(lib.hns_dev_divergence(grid.ptr, _ptr(u), _ptr(div), inv_dx, current_stream()))
     return div
@@ -202,6 +211,16 @@ class Sim:
         ms, n = (C.c_float * 5)(), C.c_longlong(0)
         _raise(lib.hns_sim_stage_times(self._ptr, ms, C.byref(n)))
         return dict(zip(("advect_vector", "divergence", "pressure", "gradient", "advect_scalars"), [float(x) for x in ms])), int(n.value)
+
+    def lookahead_counts(self):
+        """(substeps that launched the look-ahead form of advect_scalars, substeps that skipped their advect_vector launch for it)"""
+        p, c = C.c_longlong(0), C.c_longlong(0)
+        _raise(lib.hns_sim_lookahead_counts(self._ptr, C.byref(p), C.byref(c)))
+        return int(p.value), int(c.value)
+
+    def velocity_ptr(self) -> int:
+        """Raw device pointer of the velocity (``hns_sim_velocity_ptr``): writable, so the sim stops looking ahead."""
+        return int(lib.hns_sim_velocity_ptr(self._ptr) or 0)
 
     def set_active_masks(self, masks: Optional[np.ndarray], stream: int = 0) -> None:
         """Active voxel masks of the grid's leaves (leaf_count x 64 uint8, byte x*8+y, bit z); None = every voxel active (a new sim's state)."""

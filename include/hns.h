@@ -265,10 +265,23 @@ int hns_sim_pressure_time(hns_sim*, float* total_ms, long long* launches);
 /* hns_sim_stage_timing(sim, n) brackets the five stages of the next n hns_sim_core_substep / hns_sim_substep calls (six events per substep;
  * a switch of its own because the events cost microseconds each on the launch stream); hns_sim_stage_times: ms5 receives the
  * summed milliseconds of {advect_vector, divergence, pressure loop, gradient subtraction, advect_scalars} over *substeps
- * (hns_sim_substep: {collision + advect_vector + vorticity, divergence + combustion + buoyancy, pressure loop, gradient + collision, advect_scalars}). */
+ * (hns_sim_substep: {collision + advect_vector + vorticity, divergence + combustion + buoyancy, pressure loop, gradient + collision, advect_scalars}).
+ * The brackets stay where they are under look-ahead (below): a substep that found its advect_vector done has a nearly empty first stage, and the last
+ * stage of the substep before it carried both advections. Per-stage fractions of those two stages say nothing then; their sum does. */
 int hns_sim_stage_timing(hns_sim*, int max_substeps);
 int hns_sim_stage_times(hns_sim*, float* ms5, long long* substeps);
-/* Raw device pointers of the sim's buffers (Vec3f AoS velocity, float fields, divergence, pressure). */
+/* Look-ahead (option "lookahead" = auto | 0 | 1). advect_scalars of one substep and advect_vector of the next read the same velocity with the same dt
+ * and make the same backtrace, so where a substep's advect_scalars is one launch of the 32-bit float-only form without a collision field, that launch
+ * can compute the next substep's advect_vector as well (hns_dev_advect_scalars_ahead) and the next hns_sim_substep / hns_sim_core_substep called with the
+ * same dt and voxel size on the same grid skips its own. Results are bit-identical to lookahead = 0. auto (default): only after a substep call with
+ * the same dt and voxel size as the one before, so a lone substep or a changing dt pays nothing and a frame of K substeps wastes at most its last
+ * look-ahead; 1: from the first substep; 0: never. What was looked ahead is dropped by everything else that writes the velocity: hns_sim_upload, the
+ * regrids, hns_sim_deactivate, a collision substep. hns_sim_download and the timing calls keep it. A sim whose substep was captured into a graph, one
+ * lent to the operator calls, and one whose hns_sim_velocity_ptr was taken never look ahead (again).
+ * hns_sim_lookahead_counts: substeps of this sim that launched the look-ahead form / that skipped their advect_vector launch for it. */
+int hns_sim_lookahead_counts(hns_sim*, long long* produced, long long* consumed);
+/* Raw device pointers of the sim's buffers (Vec3f AoS velocity, float fields, divergence, pressure). hns_sim_velocity_ptr hands out a WRITABLE pointer
+ * the library cannot watch: calling it switches look-ahead off for this sim for good. */
 float* hns_sim_velocity_ptr(hns_sim*);
 float* hns_sim_field_ptr(hns_sim*, const char* name);
 float* hns_sim_divergence_ptr(hns_sim*);
@@ -369,6 +382,11 @@ int hns_dev_advect_scalar(hns_grid*, const float* vel3, const float* in, float* 
 /* advect_scalars (Kernel.cu:118-266); in/out are HOST arrays of n device pointers */
 int hns_dev_advect_scalars(hns_grid*, const float* vel3, const float* const* in, float* const* out, int n, const float* sdf, int has_collision,
                            float dt, float inv_dx, void* stream);
+/* advect_scalars over n <= 8 fields without a collision field AND advect_vector(vel3) into adv_out3 (not aliasing vel3), one launch: every output is
+ * bit-identical to hns_dev_advect_scalars followed by hns_dev_advect_vector with these arguments. Applies where the 32-bit addressed kernels do
+ * (a Vec3f field below 4 GiB, option "advect" = auto); HNS_ERR_INVALID_ARGUMENT elsewhere. */
+int hns_dev_advect_scalars_ahead(hns_grid*, const float* vel3, const float* const* in, float* const* out, int n, float* adv_out3, float dt, float inv_dx,
+                                 void* stream);
 /* divergence / divergence_opt (Kernel.cu:455-519) */
 int hns_dev_divergence(hns_grid*, const float* vel3, float* div, float inv_dx, void* stream);
 /* One colour of redBlackGaussSeidelUpdate(_opt) in place (Kernel.cu:521-623): the two-launch form. */
