@@ -28,28 +28,10 @@ struct Taps {
 // takes a 32-bit byte offset, and the hardware returns 0 for offsets past the end. Taps are therefore carried as the
 // byte offset of the voxel in a float field (voxel * 4; a Vec3f tap is at three times that), and a tap outside the
 // domain is any offset >= kOutside: absent neighbour leaves get kOutside as their base, so no select is needed at all.
-typedef float v3f __attribute__((ext_vector_type(3)));
-typedef int v4i __attribute__((ext_vector_type(4)));
-// raw buffer loads through the LLVM intrinsics (this toolchain's __builtin_amdgcn_raw_buffer_load_b96 returns one dword)
-__device__ v3f hns_buffer_load_v3f32(v4i rsrc, int voffset, int soffset, int aux) __asm("llvm.amdgcn.raw.buffer.load.v3f32");
-__device__ float hns_buffer_load_f32(v4i rsrc, int voffset, int soffset, int aux) __asm("llvm.amdgcn.raw.buffer.load.f32");
-typedef float v2f32 __attribute__((ext_vector_type(2)));
-__device__ v2f32 hns_buffer_load_v2f32(v4i rsrc, int voffset, int soffset, int aux) __asm("llvm.amdgcn.raw.buffer.load.v2f32");
-typedef float v4f32 __attribute__((ext_vector_type(4)));
-__device__ v4f32 hns_buffer_load_v4f32(v4i rsrc, int voffset, int soffset, int aux) __asm("llvm.amdgcn.raw.buffer.load.v4f32");
-
+// (descriptor and loads: hns_device.hpp, "raw buffer access")
 constexpr unsigned kOutside = 0xFFFFE000u;        // float-field byte offsets at or above this read as 0 (and 3x it still lies past a Vec3f field)
 constexpr uint64_t kNarrowBytes = 0xFFFF0000ull;  // largest Vec3f field the 32-bit path accepts (and largest 16-byte-per-voxel field of the q4 path)
 
-__device__ __forceinline__ v4i field_rsrc(const float* p, unsigned bytes) {
-	const unsigned long long a = (unsigned long long)p;
-	v4i r;
-	r.x = __builtin_amdgcn_readfirstlane((int)(unsigned)a);
-	r.y = __builtin_amdgcn_readfirstlane((int)((unsigned)(a >> 32) & 0xffffu));  // stride 0: raw buffer
-	r.z = __builtin_amdgcn_readfirstlane((int)bytes);                            // num_records in bytes
-	r.w = 0x00020000;                                                            // 32-bit float data format
-	return r;
-}
 __device__ __forceinline__ f3 ldv(const v4i& r, unsigned o4) {  // Vec3f of the voxel at float-offset o4; 0 outside
 	const v3f v = hns_buffer_load_v3f32(r, (int)(o4 + (o4 << 1)), 0, 0);
 	return f3{v.x, v.y, v.z};
@@ -68,28 +50,98 @@ __device__ __forceinline__ void ld_zpair(const v4i& r, unsigned lo, unsigned hi,
 	if (hi != lo + 4u) b = lds1(r, hi);
 }
 
-// stage nbr27 (for the generic path), the neighbours' base indices leaf*512 (-1 = absent) and, for the 32-bit path, their
-// base byte offsets in a float field (kOutside = absent)
-// s_b4p (32-bit kernels): the same byte bases again in a table padded to 4 x 4 x 4, entry (ax*4 + ay)*4 + az for the neighbour leaf
+// The workgroup's leaf tables in LDS: nbr27 (for the far path) and, in the generic kernels, the neighbours' base indices leaf*512 (-1 = absent) ...
+struct GenericTabs {
+	int nbr[27], base[27];
+	__device__ __forceinline__ void set(int t, int nb) { nbr[t] = nb, base[t] = nb < 0 ? -1 : nb * 512; }
+};
+// ... in the 32-bit kernels their base byte offsets in a float field (kOutside = absent), twice:
+// b4p holds the same byte bases again in a table padded to 4 x 4 x 4, entry (ax*4 + ay)*4 + az for the neighbour leaf
 // (ax, ay, az) in 0..2 -- its byte index ax<<6 | ay<<4 | az<<2 is shifts and ORs of the tap's coordinates, where 9*ax + 3*ay + az cost
 // four quarter-rate multiplies per trilinear sample (make_taps_b).
 constexpr int kPadTab = 48;
-__device__ __forceinline__ LeafCtx stage_leaf_base(const GridDev& g, int* s_nbr, int* s_base, int block, unsigned* s_b4 = nullptr, unsigned* s_b4p = nullptr, int leaf = -1) {
-	LeafCtx c;
-	c.leaf = leaf >= 0 ? leaf : launch_leaf(g, (unsigned)block);
-	c.org = g.origins[c.leaf];
-	if (threadIdx.x < 27) {
-		const int nb = g.nbr27[c.leaf * 27 + threadIdx.x];
-		s_nbr[threadIdx.x] = nb;
-		s_base[threadIdx.x] = nb < 0 ? -1 : nb * 512;
-		if (s_b4) s_b4[threadIdx.x] = nb < 0 ? kOutside : (unsigned)nb * 2048u;
-		if (s_b4p) {
-			const int t = threadIdx.x, ax = t / 9, ay = (t - 9 * ax) / 3, az = t - 9 * ax - 3 * ay;
-			s_b4p[(ax * 4 + ay) * 4 + az] = nb < 0 ? kOutside : (unsigned)nb * 2048u;
-		}
+struct NarrowTabs {
+	int nbr[27];
+	unsigned b4[27], b4p[kPadTab];
+	__device__ __forceinline__ void set(int t, int nb) {
+		const int ax = t / 9, ay = (t - 9 * ax) / 3, az = t - 9 * ax - 3 * ay;
+		nbr[t] = nb, b4[t] = b4p[(ax * 4 + ay) * 4 + az] = nb < 0 ? kOutside : (unsigned)nb * 2048u;
 	}
-	__syncthreads();
-	return c;
+};
+
+// position of voxel n of the leaf at `org`
+__device__ __forceinline__ int3 voxel_ijk(const int4 org, int n) { return int3{org.x + (n >> 6), org.y + ((n >> 3) & 7), org.z + (n & 7)}; }
+
+// What a thread knows about its leaf and its voxel (thread n of the leaf's workgroup). The constructor sets what the voxel's own values need: their loads can be issued
+// before stage() fetches and stages the tables (k_advect_vector_n, which see).
+template <class Tabs>
+struct LeafVoxel {
+	Tabs& tabs;
+	const int n, leaf, idx;
+	int4 org;
+	int3 c;            // the voxel's coordinate
+	float px, py, pz;  // and as floats
+	__device__ __forceinline__ LeafVoxel(const GridDev& g, Tabs& t) : tabs(t), n(threadIdx.x), leaf(launch_leaf(g, blockIdx.x)), idx(leaf * 512 + n) {}
+	__device__ __forceinline__ void stage(const GridDev& g) {
+		org = g.origins[leaf];
+		if (threadIdx.x < 27) tabs.set(threadIdx.x, g.nbr27[leaf * 27 + threadIdx.x]);
+		__syncthreads();
+		c = voxel_ijk(org, n);
+		px = (float)c.x, py = (float)c.y, pz = (float)c.z;
+	}
+};
+typedef LeafVoxel<GenericTabs> GenericCtx;
+typedef LeafVoxel<NarrowTabs> NarrowCtx;
+
+// ---- the pieces every sampler is made of ------------------------------------------------------------------------------------
+// corner q of setupInterpolation's order 000,100,010,110,001,... of (x,y,z) (Kernel.cu:163-196) is tap tap_of(q) of the order (di,dj,dk) at t[di*4+dj*2+dk], and back
+__device__ __forceinline__ constexpr int tap_of(int q) { return ((q & 1) << 2) | (q & 2) | (q >> 2); }
+// its offset in a box with rows YS and slices XS apart
+template <int XS = 100, int YS = 10>
+__device__ __forceinline__ constexpr int box_corner(int q) { return (q & 1) * XS + ((q >> 1) & 1) * YS + (q >> 2); }
+// the eight weight products of setupInterpolation (Kernel.cu:163-196), in its order
+__device__ __forceinline__ void tri_weights(float tx, float ty, float tz, float (&w)[8]) {
+	const float itx = 1.0f - tx, ity = 1.0f - ty, itz = 1.0f - tz;
+	const float w00 = itx * ity, w10 = tx * ity, w01 = itx * ty, w11 = tx * ty;
+	w[0] = w00 * itz, w[1] = w10 * itz, w[2] = w01 * itz, w[3] = w11 * itz, w[4] = w00 * tz, w[5] = w10 * tz, w[6] = w01 * tz, w[7] = w11 * tz;
+}
+// TrilinearSampler's nest, z then y then x (Stencils.hpp:140-152), over the corners c[di*4+dj*2+dk] with one of the three lerps: lerp_f (IndexSampler<float,1>: unfused
+// a + w*(b-a)), lerp_c (IndexSampler<Vec3f,1> on the device branch: per component fmaf(w, b-a, a), Stencils.hpp:131-135) or lerp_v3 (the same on a register pair)
+template <class T, class Lerp>
+__device__ __forceinline__ T tri_nest_yx(const T (&z)[4], float fx, float fy, Lerp lerp) {  // (from the four z columns on: the look-ahead kernel forms those as its taps arrive)
+	const T y0 = lerp(z[0], z[1], fy), y1 = lerp(z[2], z[3], fy);
+	return lerp(y0, y1, fx);
+}
+template <class T, class Lerp>
+__device__ __forceinline__ T tri_nest(const T (&c)[8], float fx, float fy, float fz, Lerp lerp) {
+	const T z[4] = {lerp(c[0], c[1], fz), lerp(c[2], c[3], fz), lerp(c[4], c[5], fz), lerp(c[6], c[7], fz)};
+	return tri_nest_yx(z, fx, fy, lerp);
+}
+// BFECC's limiter (Kernel.cu:219-233, 334-352, 396-431 per component): the corrected value clamped to the range of the voxel, its six face neighbours and the first sample.
+// float or v4f32. The caller forms phiCorr: advect_scalar's is unfused, advect_scalars' is fmaf(0.5, error, phiForward), as in the reference.
+template <class T>
+__device__ __forceinline__ T bfecc_limit(T phiOrig, const T (&nbr)[6], T phiForward, T phiCorr) {
+	T mn = phiOrig, mx = phiOrig;
+#pragma unroll
+	for (int d = 0; d < 6; ++d) {
+		mn = __builtin_elementwise_min(mn, nbr[d]);
+		mx = __builtin_elementwise_max(mx, nbr[d]);
+	}
+	mn = __builtin_elementwise_min(mn, phiForward);
+	mx = __builtin_elementwise_max(mx, phiForward);
+	return __builtin_elementwise_max(mn, __builtin_elementwise_min(phiCorr, mx));
+}
+// advect_vector's (Kernel.cu:396-431): correction, then the limiter per component. nbr(d): the velocity at face neighbour d in the order -x,+x,-y,+y,-z,+z, 0 outside the domain
+template <class Fetch>
+__device__ __forceinline__ f3 bfecc_limit_v(const f3& vo, const f3& vf, const f3& vb, Fetch nbr) {
+	float nx[6], ny[6], nz[6];
+#pragma unroll
+	for (int d = 0; d < 6; ++d) {
+		const f3 t = nbr(d);
+		nx[d] = t.x, ny[d] = t.y, nz[d] = t.z;
+	}
+	return f3{bfecc_limit(vo.x, nx, vf.x, vf.x + 0.5f * (vo.x - vb.x)), bfecc_limit(vo.y, ny, vf.y, vf.y + 0.5f * (vo.y - vb.y)),
+	          bfecc_limit(vo.z, nz, vf.z, vf.z + 0.5f * (vo.z - vb.z))};
 }
 
 struct TapsB {
@@ -98,8 +150,9 @@ struct TapsB {
 };
 
 // Floor (Stencils.hpp:25-43) + the eight corner indices of TrilinearSampler::stencil (Stencils.hpp:104-114)
-__device__ __forceinline__ Taps make_taps(const GridDev& g, const int* s_nbr, const int* s_base, const int4 org, float x, float y, float z) {
+__device__ __forceinline__ Taps make_taps(const GridDev& g, const GenericCtx& C, float x, float y, float z) {
 	Taps T;
+	const int4 org = C.org;
 	const int i = __float2int_rd(x), j = __float2int_rd(y), k = __float2int_rd(z);
 	T.fx = x - (float)i;
 	T.fy = y - (float)j;
@@ -116,12 +169,12 @@ __device__ __forceinline__ Taps make_taps(const GridDev& g, const int* s_nbr, co
 #pragma unroll
 		for (int c = 0; c < 8; ++c) {
 			const int di = c >> 2, dj = (c >> 1) & 1, dk = c & 1;
-			const int b = s_base[sx[di] + sy[dj] + sz[dk]];
+			const int b = C.tabs.base[sx[di] + sy[dj] + sz[dk]];
 			T.t[c] = b < 0 ? -1 : b + (lx[di] | ly[dj] | lz[dk]);
 		}
 	} else {
 		int any = 0;
-		far_cell_taps(g, s_nbr, org, i, j, k, T.t);
+		far_cell_taps(g, C.tabs.nbr, org, i, j, k, T.t);
 #pragma unroll
 		for (int c = 0; c < 8; ++c) any |= T.t[c];
 		// a multi-GPU rank: a tap beyond the 27-leaf neighbourhood whose leaf is not HERE may exist on another rank (hns_dist reports
@@ -137,8 +190,9 @@ __device__ __forceinline__ Taps make_taps(const GridDev& g, const int* s_nbr, co
 // workgroup's leaf) per axis, "near" <=> every d in [0, 22] (cell and cell + 1 inside the 24 voxels: ONE max3 and ONE compare instead of
 // six range tests), neighbour slot and voxel-in-leaf are bit fields of d, the table is padded so that its index is ORs (s_b4p), and
 // the eight offsets are add3's of three precombined terms.
-__device__ __forceinline__ TapsB make_taps_b(const GridDev& g, const int* s_nbr, const unsigned* s_b4p, const int4 org, float x, float y, float z) {
+__device__ __forceinline__ TapsB make_taps_b(const GridDev& g, const NarrowCtx& C, float x, float y, float z) {
 	TapsB T;
+	const int4 org = C.org;
 	const int i = __float2int_rd(x), j = __float2int_rd(y), k = __float2int_rd(z);
 	T.fx = x - (float)i;
 	T.fy = y - (float)j;
@@ -151,7 +205,7 @@ __device__ __forceinline__ TapsB make_taps_b(const GridDev& g, const int* s_nbr,
 		const unsigned lx[2] = {(dx & 7u) << 8, (ex & 7u) << 8}, ly[2] = {(dy & 7u) << 5, (ey & 7u) << 5}, lz[2] = {(dz & 7u) << 2, (ez & 7u) << 2};
 		const unsigned XY[4] = {X[0] | Y[0], X[0] | Y[1], X[1] | Y[0], X[1] | Y[1]};
 		const unsigned lxy[4] = {lx[0] | ly[0], lx[0] | ly[1], lx[1] | ly[0], lx[1] | ly[1]};
-		const char* tab = reinterpret_cast<const char*>(s_b4p);
+		const char* tab = reinterpret_cast<const char*>(C.tabs.b4p);
 #pragma unroll
 		for (int c = 0; c < 8; ++c) {
 			const int dij = c >> 1, dk = c & 1;
@@ -159,7 +213,7 @@ __device__ __forceinline__ TapsB make_taps_b(const GridDev& g, const int* s_nbr,
 		}
 	} else {
 		int any = 0, ft[8];
-		far_cell_taps(g, s_nbr, org, i, j, k, ft);  // (round 6: through the neighbour tables up to two leaves away, the hash beyond)
+		far_cell_taps(g, C.tabs.nbr, org, i, j, k, ft);  // (round 6: through the neighbour tables up to two leaves away, the hash beyond)
 #pragma unroll
 		for (int c = 0; c < 8; ++c) {
 			any |= ft[c];
@@ -176,38 +230,23 @@ __device__ __forceinline__ float ldz(const float* __restrict__ f, int idx) {
 	return idx < 0 ? 0.0f : v;
 }
 
-// IndexSampler<float,1>: unfused a + w*(b-a), z then y then x (Stencils.hpp:140-152)
+// IndexSampler<float,1> (Stencils.hpp:140-152)
 __device__ __forceinline__ float tri_f_t(const float* __restrict__ f, const Taps& T) {
-	const float z0 = lerp_f(ldz(f, T.t[0]), ldz(f, T.t[1]), T.fz);
-	const float z1 = lerp_f(ldz(f, T.t[2]), ldz(f, T.t[3]), T.fz);
-	const float z2 = lerp_f(ldz(f, T.t[4]), ldz(f, T.t[5]), T.fz);
-	const float z3 = lerp_f(ldz(f, T.t[6]), ldz(f, T.t[7]), T.fz);
-	const float y0 = lerp_f(z0, z1, T.fy);
-	const float y1 = lerp_f(z2, z3, T.fy);
-	return lerp_f(y0, y1, T.fx);
-}
-
-// IndexSampler<Vec3f,1> on the device branch: per component fmaf(w, b-a, a) (Stencils.hpp:131-135); eight 12-byte taps
-template <class TapsT>
-__device__ __forceinline__ float tri_c8(float c0, float c1, float c2, float c3, float c4, float c5, float c6, float c7, const TapsT& T) {
-	const float z0 = lerp_c(c0, c1, T.fz);
-	const float z1 = lerp_c(c2, c3, T.fz);
-	const float z2 = lerp_c(c4, c5, T.fz);
-	const float z3 = lerp_c(c6, c7, T.fz);
-	const float y0 = lerp_c(z0, z1, T.fy);
-	const float y1 = lerp_c(z2, z3, T.fy);
-	return lerp_c(y0, y1, T.fx);
-}
-
-__device__ __forceinline__ f3 tri_v_t(const float* __restrict__ u, const Taps& T) {
-	f3 c[8];
+	float c[8];
 #pragma unroll
-	for (int q = 0; q < 8; ++q) c[q] = ld3z(u, T.t[q]);
-	f3 r;
-	r.x = tri_c8(c[0].x, c[1].x, c[2].x, c[3].x, c[4].x, c[5].x, c[6].x, c[7].x, T);
-	r.y = tri_c8(c[0].y, c[1].y, c[2].y, c[3].y, c[4].y, c[5].y, c[6].y, c[7].y, T);
-	r.z = tri_c8(c[0].z, c[1].z, c[2].z, c[3].z, c[4].z, c[5].z, c[6].z, c[7].z, T);
-	return r;
+	for (int q = 0; q < 8; ++q) c[q] = ldz(f, T.t[q]);
+	return tri_nest(c, T.fx, T.fy, T.fz, lerp_f);
+}
+
+// IndexSampler<Vec3f,1> on the device branch, per component (Stencils.hpp:131-135); eight 12-byte taps
+__device__ __forceinline__ f3 tri_v_t(const float* __restrict__ u, const Taps& T) {
+	float x[8], y[8], z[8];
+#pragma unroll
+	for (int q = 0; q < 8; ++q) {
+		const f3 c = ld3z(u, T.t[q]);
+		x[q] = c.x, y[q] = c.y, z[q] = c.z;
+	}
+	return f3{tri_nest(x, T.fx, T.fy, T.fz, lerp_c), tri_nest(y, T.fx, T.fy, T.fz, lerp_c), tri_nest(z, T.fx, T.fy, T.fz, lerp_c)};
 }
 
 // One Vec3f lerp of the device branch, fmaf(w, b - a, a) per component (Stencils.hpp:131-135), written on the (x, y) pair and on z: a
@@ -232,39 +271,15 @@ __device__ __forceinline__ f3 tri_v_b(const v4i& ru, const TapsB& T) {
 		c[q].xy = v2f32{v.x, v.y};
 		c[q].z = v.z;
 	}
-	const V3 z0 = lerp_v3(c[0], c[1], T.fz), z1 = lerp_v3(c[2], c[3], T.fz), z2 = lerp_v3(c[4], c[5], T.fz), z3 = lerp_v3(c[6], c[7], T.fz);
-	const V3 y0 = lerp_v3(z0, z1, T.fy), y1 = lerp_v3(z2, z3, T.fy);
-	const V3 r = lerp_v3(y0, y1, T.fx);
+	const V3 r = tri_nest(c, T.fx, T.fy, T.fz, lerp_v3);
 	return f3{r.xy.x, r.xy.y, r.z};
 }
 
 __device__ __forceinline__ float tri_f_b(const v4i& rf, const TapsB& T) {
-	const float z0 = lerp_f(lds1(rf, T.o[0]), lds1(rf, T.o[1]), T.fz);
-	const float z1 = lerp_f(lds1(rf, T.o[2]), lds1(rf, T.o[3]), T.fz);
-	const float z2 = lerp_f(lds1(rf, T.o[4]), lds1(rf, T.o[5]), T.fz);
-	const float z3 = lerp_f(lds1(rf, T.o[6]), lds1(rf, T.o[7]), T.fz);
-	const float y0 = lerp_f(z0, z1, T.fy);
-	const float y1 = lerp_f(z2, z3, T.fy);
-	return lerp_f(y0, y1, T.fx);
-}
-
-// float-field byte offset of the face neighbour of own voxel n along AXIS/DIR (>= kOutside where that leaf is absent)
-template <int AXIS, int DIR>
-__device__ __forceinline__ unsigned nbr_off(const unsigned* s_b4, unsigned own, int n) {
-	constexpr int shift = AXIS == 0 ? 6 : (AXIS == 1 ? 3 : 0);
-	constexpr int stride = 1 << shift;
-	constexpr int dslot = AXIS == 0 ? 9 : (AXIS == 1 ? 3 : 1);
-	const int c = (n >> shift) & 7;
-	const bool inside = DIR > 0 ? c != 7 : c != 0;
-	return inside ? own + (unsigned)(DIR * stride * 4) : s_b4[13 + DIR * dslot] + (unsigned)((n - DIR * 7 * stride) << 2);
-}
-__device__ __forceinline__ void nbr6_b(const unsigned* s_b4, unsigned own, int n, unsigned (&o)[6]) {
-	o[0] = nbr_off<0, -1>(s_b4, own, n);
-	o[1] = nbr_off<0, 1>(s_b4, own, n);
-	o[2] = nbr_off<1, -1>(s_b4, own, n);
-	o[3] = nbr_off<1, 1>(s_b4, own, n);
-	o[4] = nbr_off<2, -1>(s_b4, own, n);
-	o[5] = nbr_off<2, 1>(s_b4, own, n);
+	float c[8];
+#pragma unroll
+	for (int q = 0; q < 8; ++q) c[q] = lds1(rf, T.o[q]);
+	return tri_nest(c, T.fx, T.fy, T.fz, lerp_f);
 }
 
 // flat index of the face neighbour of voxel n of the workgroup's leaf along AXIS in direction DIR, -1 = outside
@@ -332,65 +347,87 @@ __device__ __forceinline__ void box_shell_entry(int h, int& slot, int& local, in
 	local = (((bx + 7) & 7) << 6) | (((by + 7) & 7) << 3) | ((bz + 7) & 7);
 	cell = bx * XS + by * YS + bz;
 }
+// the shell cell that thread h stages (the first 488 threads; 0 for the others) and the float-field byte offset of the voxel under it (>= kOutside where that leaf is absent)
+template <int XS = 100, int YS = 10>
+__device__ __forceinline__ unsigned box_shell_off(const unsigned* s_b4, int h, int& cell) {
+	unsigned off = 0u;
+	cell = 0;
+	if (h < kBoxShell) {
+		int slot, local;
+		box_shell_entry<XS, YS>(h, slot, local, cell);
+		off = s_b4[slot] + ((unsigned)local << 2);
+	}
+	return off;
+}
+// box cell of own voxel n, and the step from a cell to its face neighbour d in the reference's order -x,+x,-y,+y,-z,+z (Kernel.cu:219,334-342,410-421)
+template <int XS = 100, int YS = 10>
+__device__ __forceinline__ int box_own(int n) { return ((n >> 6) + 1) * XS + (((n >> 3) & 7) + 1) * YS + (n & 7) + 1; }
+template <int XS = 100, int YS = 10>
+__device__ __forceinline__ constexpr int box_nbr(int d) { return (d & 1 ? 1 : -1) * (d < 2 ? XS : (d < 4 ? YS : 1)); }
+
+// Stage the velocity box, three component planes PS apart: every thread its own voxel (value vo), the first 488 the shell cell `cell` with the voxel at `off` (box_shell_off).
+// What a shell cell outside the domain holds is the caller's choice of `off`: unmapped it reads 0 (advect_vector: the descriptor's bounds check), mapped to element g.oob that
+// element (advect_scalars, Kernel.cu:225). In two halves, load and store: the store waits for the load, and a kernel that has gathers to issue puts them in between
+// (k_advect_scalars_n<false, true>: with the store in front of them the kernel was 2.3 % slower, profiles/advect_refactor_ab.txt). The caller's barrier completes the box.
+template <int XS, int YS, int PS>
+__device__ __forceinline__ f3 velocity_box_load(float* s_box, const v4i& ru, int n, const f3& vo, unsigned off) {
+	const int ob = box_own<XS, YS>(n);
+	s_box[ob] = vo.x, s_box[ob + PS] = vo.y, s_box[ob + 2 * PS] = vo.z;
+	f3 h = {0.0f, 0.0f, 0.0f};
+	if (n < kBoxShell) h = ldv(ru, off);
+	return h;
+}
+template <int PS>
+__device__ __forceinline__ void velocity_box_store(float* s_box, int n, int cell, const f3& h) {
+	if (n < kBoxShell) s_box[cell] = h.x, s_box[cell + PS] = h.y, s_box[cell + 2 * PS] = h.z;
+}
 __device__ __forceinline__ V3 box_v3(const float* s_box, int a) {
 	V3 r;
 	r.xy = v2f32{s_box[a], s_box[a + kVP]};
 	r.z = s_box[a + 2 * kVP];
 	return r;
 }
-// TrilinearSampler over the box: a = cell of the lower corner
+__device__ __forceinline__ f3 box_f3(const float* s_box, int a) {
+	const V3 t = box_v3(s_box, a);
+	return f3{t.xy.x, t.xy.y, t.z};
+}
+// TrilinearSampler over the box (rows kVY apart): a = cell of the lower corner
 __device__ __forceinline__ f3 tri_v_box(const float* s_box, int a, float fx, float fy, float fz) {
 	V3 c[8];
 #pragma unroll
-	for (int q = 0; q < 8; ++q) c[q] = box_v3(s_box, a + (q >> 2) * kVX + ((q >> 1) & 1) * kVY + (q & 1));
-	const V3 z0 = lerp_v3(c[0], c[1], fz), z1 = lerp_v3(c[2], c[3], fz), z2 = lerp_v3(c[4], c[5], fz), z3 = lerp_v3(c[6], c[7], fz);
-	const V3 y0 = lerp_v3(z0, z1, fy), y1 = lerp_v3(z2, z3, fy);
-	const V3 r = lerp_v3(y0, y1, fx);
+	for (int q = 0; q < 8; ++q) c[q] = box_v3(s_box, a + box_corner<kVX, kVY>(tap_of(q)));
+	const V3 r = tri_nest(c, fx, fy, fz, lerp_v3);
 	return f3{r.xy.x, r.xy.y, r.z};
+}
+// The velocity at (sx, sy, sz), advect_vector's sample: out of the box where the whole wave's cells lie inside it, else gathered.
+// (either sample: the FIRST one too lands in the box where the flow moves less than a voxel per step -- then the wave gathers nothing at all. Per WAVE here: with a lane
+// outside, all of them gather -- measured 2.4 % faster through the plume's transient than a per-lane split; advect_scalars splits per lane)
+__device__ __forceinline__ f3 sample_velocity(const GridDev& g, const NarrowCtx& C, const v4i& ru, const float* s_box, float sx, float sy, float sz) {
+	const int i = __float2int_rd(sx), j = __float2int_rd(sy), k = __float2int_rd(sz);
+	const unsigned rx = (unsigned)(i - (C.org.x - 1)), ry = (unsigned)(j - (C.org.y - 1)), rz = (unsigned)(k - (C.org.z - 1));  // cell and cell + 1 inside the box <=> each in [0, 8]
+	if (__all(max(rx, max(ry, rz)) <= 8u)) return tri_v_box(s_box, (int)(rx * (unsigned)kVX + ry * (unsigned)kVY + rz), sx - (float)i, sy - (float)j, sz - (float)k);
+	return tri_v_b(ru, make_taps_b(g, C, sx, sy, sz));
 }
 
 // 32-bit addressed form (no collision field): same loads and arithmetic as the generic kernel below
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_advect_vector_n(const GridDev g, const float* __restrict__ u, float* __restrict__ out, const float scaled_dt) {
-	__shared__ int s_nbr[27];
-	__shared__ int s_base[27];
-	__shared__ unsigned s_b4[27];
-	__shared__ unsigned s_b4p[kPadTab];
+	__shared__ NarrowTabs tabs;
+	__shared__ float s_box[3 * kVP];
 	// the voxel's own velocity needs the leaf number only: its load is issued before the neighbour table is fetched and staged (one memory
 	// round trip less in front of the first gathers; the kernel is bound by the length of that chain)
-	const int n = threadIdx.x;
-	const int leaf = launch_leaf(g, blockIdx.x);
-	const int idx = leaf * 512 + n;
+	NarrowCtx C(g, tabs);
 	const v4i ru = field_rsrc(u, (unsigned)g.n_leaves * 6144u);
-	const unsigned own = (unsigned)idx << 2;
-	const f3 vo = ldv(ru, own);
-	const LeafCtx L = stage_leaf_base(g, s_nbr, s_base, blockIdx.x, s_b4, s_b4p, leaf);
-	const float px = (float)(L.org.x + (n >> 6)), py = (float)(L.org.y + ((n >> 3) & 7)), pz = (float)(L.org.z + (n & 7));
-
-	__shared__ float s_box[3 * kVP];
-	const int ob = ((n >> 6) + 1) * kVX + (((n >> 3) & 7) + 1) * kVY + (n & 7) + 1;
-	s_box[ob] = vo.x, s_box[ob + kVP] = vo.y, s_box[ob + 2 * kVP] = vo.z;
-	if (n < kBoxShell) {
-		int slot, local, cell;
-		box_shell_entry<kVX, kVY>(n, slot, local, cell);
-		const f3 h = ldv(ru, s_b4[slot] + ((unsigned)local << 2));
-		s_box[cell] = h.x, s_box[cell + kVP] = h.y, s_box[cell + 2 * kVP] = h.z;
-	}
-	float sx = px - scaled_dt * vo.x, sy = py - scaled_dt * vo.y, sz = pz - scaled_dt * vo.z;  // backPos (Kernel.cu:374)
+	const f3 vo = ldv(ru, (unsigned)C.idx << 2);
+	C.stage(g);
+	int cell;
+	const unsigned off = box_shell_off<kVX, kVY>(tabs.b4, C.n, cell);
+	velocity_box_store<kVP>(s_box, C.n, cell, velocity_box_load<kVX, kVY, kVP>(s_box, ru, C.n, vo, off));
+	float sx = C.px - scaled_dt * vo.x, sy = C.py - scaled_dt * vo.y, sz = C.pz - scaled_dt * vo.z;  // backPos (Kernel.cu:374)
 	f3 vf = {0.0f, 0.0f, 0.0f}, vb = {0.0f, 0.0f, 0.0f};
 	__syncthreads();  // box complete
 #pragma unroll 1
 	for (int pass = 0; pass < 2; ++pass) {
-		const int i = __float2int_rd(sx), j = __float2int_rd(sy), k = __float2int_rd(sz);
-		const unsigned rx = (unsigned)(i - (L.org.x - 1)), ry = (unsigned)(j - (L.org.y - 1)), rz = (unsigned)(k - (L.org.z - 1));  // cell and cell + 1 inside the box <=> each in [0, 8]
-		f3 v;
-		// (either sample: the FIRST one too lands in the box where the flow moves less than a voxel per step -- then the wave gathers nothing at all. Per WAVE here: with a lane
-		// outside, all of them gather -- measured 2.4 % faster through the plume's transient than a per-lane split; advect_scalars splits per lane)
-		if (__all(max(rx, max(ry, rz)) <= 8u)) {
-			v = tri_v_box(s_box, (int)(rx * (unsigned)kVX + ry * (unsigned)kVY + rz), sx - (float)i, sy - (float)j, sz - (float)k);
-		} else {
-			const TapsB T = make_taps_b(g, s_nbr, s_b4p, L.org, sx, sy, sz);
-			v = tri_v_b(ru, T);
-		}
+		const f3 v = sample_velocity(g, C, ru, s_box, sx, sy, sz);
 		if (pass == 0) {
 			vf = v;
 			sx = sx + scaled_dt * v.x, sy = sy + scaled_dt * v.y, sz = sz + scaled_dt * v.z;  // Kernel.cu:387
@@ -398,55 +435,31 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
 			vb = v;
 		}
 	}
-	f3 vc = {vf.x + 0.5f * (vo.x - vb.x), vf.y + 0.5f * (vo.y - vb.y), vf.z + 0.5f * (vo.z - vb.z)};
-	const int e[6] = {ob - kVX, ob + kVX, ob - kVY, ob + kVY, ob - 1, ob + 1};
-	f3 mn = vo, mx = vo;
-#pragma unroll
-	for (int d = 0; d < 6; ++d) {
-		const V3 t = box_v3(s_box, e[d]);
-		mn.x = fminf(mn.x, t.xy.x);
-		mx.x = fmaxf(mx.x, t.xy.x);
-		mn.y = fminf(mn.y, t.xy.y);
-		mx.y = fmaxf(mx.y, t.xy.y);
-		mn.z = fminf(mn.z, t.z);
-		mx.z = fmaxf(mx.z, t.z);
-	}
-	mn.x = fminf(mn.x, vf.x);
-	mx.x = fmaxf(mx.x, vf.x);
-	mn.y = fminf(mn.y, vf.y);
-	mx.y = fmaxf(mx.y, vf.y);
-	mn.z = fminf(mn.z, vf.z);
-	mx.z = fmaxf(mx.z, vf.z);
-	vc.x = fmaxf(mn.x, fminf(vc.x, mx.x));
-	vc.y = fmaxf(mn.y, fminf(vc.y, mx.y));
-	vc.z = fmaxf(mn.z, fminf(vc.z, mx.z));
-	st3(out, idx, vc);
+	const int ob = box_own<kVX, kVY>(C.n);
+	st3(out, C.idx, bfecc_limit_v(vo, vf, vb, [&](int d) { return box_f3(s_box, ob + box_nbr<kVX, kVY>(d)); }));
 }
 
 template <bool COLL>
 __global__ __launch_bounds__(512) void k_advect_vector(const GridDev g, const float* __restrict__ u, float* __restrict__ out,
                                                        const float* __restrict__ sdf, const float scaled_dt, const float inv_dx) {
-	__shared__ int s_nbr[27];
-	__shared__ int s_base[27];
-	const LeafCtx L = stage_leaf_base(g, s_nbr, s_base, blockIdx.x);
-	const int n = threadIdx.x;
-	const int idx = L.leaf * 512 + n;
-	const int ci = L.org.x + (n >> 6), cj = L.org.y + ((n >> 3) & 7), ck = L.org.z + (n & 7);
-	const float px = (float)ci, py = (float)cj, pz = (float)ck;
+	__shared__ GenericTabs tabs;
+	GenericCtx C(g, tabs);
+	C.stage(g);
+	const int idx = C.idx;
 
 	const f3 vo = ld3(u, idx);
 	// forward pass (backtrace) then backward check: the same sampling code twice, kept as a 2-trip loop so that the
 	// far-tap path is emitted once
-	float sx = px - scaled_dt * vo.x, sy = py - scaled_dt * vo.y, sz = pz - scaled_dt * vo.z;  // backPos (Kernel.cu:374)
-	float rx = px, ry = py, rz = pz;                                                            // where a collision sends the trace back to
+	float sx = C.px - scaled_dt * vo.x, sy = C.py - scaled_dt * vo.y, sz = C.pz - scaled_dt * vo.z;  // backPos (Kernel.cu:374)
+	float rx = C.px, ry = C.py, rz = C.pz;                                                            // where a collision sends the trace back to
 	f3 vf = {0.0f, 0.0f, 0.0f}, vb = {0.0f, 0.0f, 0.0f};
 #pragma unroll 1
 	for (int pass = 0; pass < 2; ++pass) {
-		Taps T = make_taps(g, s_nbr, s_base, L.org, sx, sy, sz);
+		Taps T = make_taps(g, C, sx, sy, sz);
 		if (COLL) {
 			if (tri_f_t(sdf, T) < 0.0f) {  // Kernel.cu:377-382 / :390-394
 				sx = rx, sy = ry, sz = rz;
-				T = make_taps(g, s_nbr, s_base, L.org, sx, sy, sz);
+				T = make_taps(g, C, sx, sy, sz);
 			}
 		}
 		const f3 v = tri_v_t(u, T);
@@ -458,37 +471,16 @@ __global__ __launch_bounds__(512) void k_advect_vector(const GridDev g, const fl
 			vb = v;
 		}
 	}
-	f3 vc = {vf.x + 0.5f * (vo.x - vb.x), vf.y + 0.5f * (vo.y - vb.y), vf.z + 0.5f * (vo.z - vb.z)};
-
 	int nb[6];
-	nbr6(s_base, L.leaf, n, nb);
-	f3 mn = vo, mx = vo;
-#pragma unroll
-	for (int d = 0; d < 6; ++d) {
-		const f3 nv = ld3z(u, nb[d]);
-		mn.x = fminf(mn.x, nv.x);
-		mx.x = fmaxf(mx.x, nv.x);
-		mn.y = fminf(mn.y, nv.y);
-		mx.y = fmaxf(mx.y, nv.y);
-		mn.z = fminf(mn.z, nv.z);
-		mx.z = fmaxf(mx.z, nv.z);
-	}
-	mn.x = fminf(mn.x, vf.x);
-	mx.x = fmaxf(mx.x, vf.x);
-	mn.y = fminf(mn.y, vf.y);
-	mx.y = fmaxf(mx.y, vf.y);
-	mn.z = fminf(mn.z, vf.z);
-	mx.z = fmaxf(mx.z, vf.z);
-	vc.x = fmaxf(mn.x, fminf(vc.x, mx.x));
-	vc.y = fmaxf(mn.y, fminf(vc.y, mx.y));
-	vc.z = fmaxf(mn.z, fminf(vc.z, mx.z));
+	nbr6(tabs.base, C.leaf, C.n, nb);
+	f3 vc = bfecc_limit_v(vo, vf, vb, [&](int d) { return ld3z(u, nb[d]); });
 
 	if (COLL) {  // Kernel.cu:433-450
 		const float sv = sdf[idx];
 		if (sv < 0.0f) {
 			vc.x = vc.y = vc.z = 0.0f;
 		} else if (sv < 0.1f) {
-			const f3 nrm = sdf_normal(g, s_nbr, L.org, sdf, ci, cj, ck, inv_dx);
+			const f3 nrm = sdf_normal(g, tabs.nbr, C.org, sdf, C.c.x, C.c.y, C.c.z, inv_dx);
 			vc = no_slip_blend(vc, nrm, 1.0f - (sv / 1.5f));
 		}
 	}
@@ -502,27 +494,23 @@ __global__ __launch_bounds__(512) void k_advect_vector(const GridDev g, const fl
 // 32-bit addressed form (no collision field)
 __global__ __launch_bounds__(512) void k_advect_scalar_n(const GridDev g, const float* __restrict__ u, const float* __restrict__ in, float* __restrict__ out,
                                                          const float scaled_dt) {
-	__shared__ int s_nbr[27];
-	__shared__ int s_base[27];
-	__shared__ unsigned s_b4[27];
-	__shared__ unsigned s_b4p[kPadTab];
-	const LeafCtx L = stage_leaf_base(g, s_nbr, s_base, blockIdx.x, s_b4, s_b4p);
-	const int n = threadIdx.x;
-	const int idx = L.leaf * 512 + n;
-	const float px = (float)(L.org.x + (n >> 6)), py = (float)(L.org.y + ((n >> 3) & 7)), pz = (float)(L.org.z + (n & 7));
-	const unsigned bytes1 = (unsigned)g.n_leaves * 2048u, own = (unsigned)idx << 2;
+	__shared__ NarrowTabs tabs;
+	NarrowCtx C(g, tabs);
+	C.stage(g);
+	const int n = C.n;
+	const unsigned bytes1 = (unsigned)g.n_leaves * 2048u, own = (unsigned)C.idx << 2;
 	const v4i ru = field_rsrc(u, bytes1 * 3u), rf = field_rsrc(in, bytes1);
 
 	__shared__ float s_tile[kTile];  // clamp neighbours through LDS (see k_advect_vector_n)
 	const float phiOrig = lds1(rf, own);
 	s_tile[n] = phiOrig;
-	if (n < 384) s_tile[512 + n] = lds1(rf, halo_off(s_b4, n));
+	if (n < 384) s_tile[512 + n] = lds1(rf, halo_off(tabs.b4, n));
 	const f3 vc = ldv(ru, own);
-	float sx = px - scaled_dt * vc.x, sy = py - scaled_dt * vc.y, sz = pz - scaled_dt * vc.z;
+	float sx = C.px - scaled_dt * vc.x, sy = C.py - scaled_dt * vc.y, sz = C.pz - scaled_dt * vc.z;
 	float phiForward = 0.0f, phiBackward = 0.0f;
 #pragma unroll 1
 	for (int pass = 0; pass < 2; ++pass) {
-		const TapsB T = make_taps_b(g, s_nbr, s_b4p, L.org, sx, sy, sz);
+		const TapsB T = make_taps_b(g, C, sx, sy, sz);
 		const float phi = tri_f_b(rf, T);
 		if (pass == 0) {
 			phiForward = phi;
@@ -533,44 +521,31 @@ __global__ __launch_bounds__(512) void k_advect_scalar_n(const GridDev g, const 
 		}
 	}
 	const float error = phiOrig - phiBackward;
-	const float phiCorr = phiForward + 0.5f * error;
 	__syncthreads();
-	const int e[6] = {tile_nbr<0, -1>(n), tile_nbr<0, 1>(n), tile_nbr<1, -1>(n), tile_nbr<1, 1>(n), tile_nbr<2, -1>(n), tile_nbr<2, 1>(n)};
-	float mn = phiOrig, mx = phiOrig;
-#pragma unroll
-	for (int d = 0; d < 6; ++d) {
-		const float nv = s_tile[e[d]];
-		mn = fminf(mn, nv);
-		mx = fmaxf(mx, nv);
-	}
-	mn = fminf(mn, phiForward);
-	mx = fmaxf(mx, phiForward);
-	out[idx] = fmaxf(mn, fminf(phiCorr, mx));
+	const float nv[6] = {s_tile[tile_nbr<0, -1>(n)], s_tile[tile_nbr<0, 1>(n)], s_tile[tile_nbr<1, -1>(n)], s_tile[tile_nbr<1, 1>(n)], s_tile[tile_nbr<2, -1>(n)], s_tile[tile_nbr<2, 1>(n)]};
+	out[C.idx] = bfecc_limit(phiOrig, nv, phiForward, phiForward + 0.5f * error);
 }
 
 template <bool COLL>
 __global__ __launch_bounds__(512) void k_advect_scalar(const GridDev g, const float* __restrict__ u, const float* __restrict__ in,
                                                        float* __restrict__ out, const float* __restrict__ sdf, const float scaled_dt) {
-	__shared__ int s_nbr[27];
-	__shared__ int s_base[27];
-	const LeafCtx L = stage_leaf_base(g, s_nbr, s_base, blockIdx.x);
-	const int n = threadIdx.x;
-	const int idx = L.leaf * 512 + n;
-	const int ci = L.org.x + (n >> 6), cj = L.org.y + ((n >> 3) & 7), ck = L.org.z + (n & 7);
-	const float px = (float)ci, py = (float)cj, pz = (float)ck;
+	__shared__ GenericTabs tabs;
+	GenericCtx C(g, tabs);
+	C.stage(g);
+	const int idx = C.idx;
 
 	const float phiOrig = in[idx];
 	const f3 vc = ld3(u, idx);
-	float sx = px - scaled_dt * vc.x, sy = py - scaled_dt * vc.y, sz = pz - scaled_dt * vc.z;
-	float rx = px, ry = py, rz = pz;
+	float sx = C.px - scaled_dt * vc.x, sy = C.py - scaled_dt * vc.y, sz = C.pz - scaled_dt * vc.z;
+	float rx = C.px, ry = C.py, rz = C.pz;
 	float phiForward = 0.0f, phiBackward = 0.0f;
 #pragma unroll 1
 	for (int pass = 0; pass < 2; ++pass) {
-		Taps T = make_taps(g, s_nbr, s_base, L.org, sx, sy, sz);
+		Taps T = make_taps(g, C, sx, sy, sz);
 		if (COLL) {
 			if (tri_f_t(sdf, T) < 0.0f) {
 				sx = rx, sy = ry, sz = rz;
-				T = make_taps(g, s_nbr, s_base, L.org, sx, sy, sz);
+				T = make_taps(g, C, sx, sy, sz);
 			}
 		}
 		const float phi = tri_f_t(in, T);
@@ -584,19 +559,12 @@ __global__ __launch_bounds__(512) void k_advect_scalar(const GridDev g, const fl
 		}
 	}
 	const float error = phiOrig - phiBackward;
-	const float phiCorr = phiForward + 0.5f * error;
 	int nb[6];
-	nbr6(s_base, L.leaf, n, nb);
-	float mn = phiOrig, mx = phiOrig;
+	nbr6(tabs.base, C.leaf, C.n, nb);
+	float nv[6];
 #pragma unroll
-	for (int d = 0; d < 6; ++d) {
-		const float nv = ldz(in, nb[d]);
-		mn = fminf(mn, nv);
-		mx = fmaxf(mx, nv);
-	}
-	mn = fminf(mn, phiForward);
-	mx = fmaxf(mx, phiForward);
-	out[idx] = fmaxf(mn, fminf(phiCorr, mx));
+	for (int d = 0; d < 6; ++d) nv[d] = ldz(in, nb[d]);
+	out[idx] = bfecc_limit(phiOrig, nv, phiForward, phiForward + 0.5f * error);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -617,20 +585,35 @@ struct ScalarPtrs {
 
 // setupInterpolation (Kernel.cu:163-196): indices and weights in the order 000,100,010,110,001,101,011,111 of (x,y,z)
 __device__ __forceinline__ void interp_from_taps(const Taps& T, int oob, int (&ix)[8], float (&w)[8]) {
-	const float tx = T.fx, ty = T.fy, tz = T.fz;
-	const float itx = 1.0f - tx, ity = 1.0f - ty, itz = 1.0f - tz;
-	const float w00 = itx * ity, w10 = tx * ity, w01 = itx * ty, w11 = tx * ty;
-	w[0] = w00 * itz;
-	w[1] = w10 * itz;
-	w[2] = w01 * itz;
-	w[3] = w11 * itz;
-	w[4] = w00 * tz;
-	w[5] = w10 * tz;
-	w[6] = w01 * tz;
-	w[7] = w11 * tz;
-	const int perm[8] = {0, 4, 2, 6, 1, 5, 3, 7};  // (di,dj,dk) at t[di*4+dj*2+dk]
+	tri_weights(T.fx, T.fy, T.fz, w);
 #pragma unroll
-	for (int q = 0; q < 8; ++q) ix[q] = T.t[perm[q]] < 0 ? oob : T.t[perm[q]];
+	for (int q = 0; q < 8; ++q) ix[q] = T.t[tap_of(q)] < 0 ? oob : T.t[tap_of(q)];
+}
+// velF = velF + v * w (Kernel.cu:201-206), unfused
+__device__ __forceinline__ void add_weighted(f3& a, const f3& v, float w) { a.x = a.x + w * v.x, a.y = a.y + w * v.y, a.z = a.z + w * v.z; }
+
+// One sample point of advect_scalars in the 32-bit kernels. Where BOX allows it and the point's cell and cell + 1 lie inside the leaf's 10^3 box (per lane): true, and the box
+// cell of the lower corner -- corner q of the interpolation order is box cell `cell + box_corner(q)`. Else the eight float-field byte offsets in interpolation order, a tap
+// outside the domain mapped to element oob4 / 4 (Kernel.cu:133,192,225). Either way the weights of setupInterpolation.
+template <bool BOX>
+__device__ __forceinline__ bool sample_setup(const GridDev& g, const NarrowCtx& C, float x, float y, float z, unsigned oob4, int& cell, unsigned (&o)[8], float (&w)[8]) {
+	const int i = __float2int_rd(x), j = __float2int_rd(y), k = __float2int_rd(z);
+	const unsigned rx = (unsigned)(i - (C.org.x - 1)), ry = (unsigned)(j - (C.org.y - 1)), rz = (unsigned)(k - (C.org.z - 1));
+	const bool boxed = BOX && max(rx, max(ry, rz)) <= 8u;
+	cell = boxed ? (int)((rx * 10u + ry) * 10u + rz) : 0;
+	float tx, ty, tz;
+	if (boxed) {
+		tx = x - (float)i, ty = y - (float)j, tz = z - (float)k;  // (make_taps_b's fractions)
+#pragma unroll
+		for (int q = 0; q < 8; ++q) o[q] = 0u;
+	} else {
+		const TapsB T = make_taps_b(g, C, x, y, z);
+		tx = T.fx, ty = T.fy, tz = T.fz;
+#pragma unroll
+		for (int q = 0; q < 8; ++q) o[q] = T.o[tap_of(q)] >= kOutside ? oob4 : T.o[tap_of(q)];
+	}
+	tri_weights(tx, ty, tz, w);
+	return boxed;
 }
 
 // 32-bit addressed form (no collision field). Out-of-domain taps read element g.oob, as in the generic kernel.
@@ -648,122 +631,70 @@ template <bool Q4, bool AHEAD = false>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(Q4 || AHEAD ? 6 : 4))) void k_advect_scalars_n(const GridDev g, const float* __restrict__ u, const ScalarPtrs P, const float scaled_dt,
                                                                                                             float* __restrict__ adv_out) {
 	static_assert(!(Q4 && AHEAD), "the look-ahead form is float-only");
-	__shared__ int s_nbr[27];
-	__shared__ int s_base[27];
-	__shared__ unsigned s_b4[27];
-	__shared__ unsigned s_b4p[kPadTab];
-	const int n = threadIdx.x;
-	const int leaf = launch_leaf(g, blockIdx.x);
-	const int idx = leaf * 512 + n;
+	__shared__ NarrowTabs tabs;
+	NarrowCtx C(g, tabs);
+	const int n = C.n, idx = C.idx;
 	const unsigned bytes1 = (unsigned)g.n_leaves * 2048u;
 	const v4i ru = field_rsrc(u, bytes1 * 3u);
 	const unsigned own = (unsigned)idx << 2, oob4 = (unsigned)g.oob << 2;
 	const f3 vc = ldv(ru, own);  // (issued before the neighbour table is staged: see k_advect_vector_n)
-	const LeafCtx L = stage_leaf_base(g, s_nbr, s_base, blockIdx.x, s_b4, s_b4p, leaf);
-	const float px = (float)(L.org.x + (n >> 6)), py = (float)(L.org.y + ((n >> 3) & 7)), pz = (float)(L.org.z + (n & 7));
+	C.stage(g);
 
 	// the leaf and one voxel around it through LDS (see k_advect_vector_n): the velocity once, then per field; shell cell of this thread (the first 488) and where its value lies
-	const int ob = (((n >> 6) + 1) * 10 + ((n >> 3) & 7) + 1) * 10 + (n & 7) + 1;
-	const int e[6] = {ob - 100, ob + 100, ob - 10, ob + 10, ob - 1, ob + 1};
-	unsigned ho = 0u;
-	int hcell = 0;
-	if (n < kBoxShell) {
-		int slot, local;
-		box_shell_entry(n, slot, local, hcell);
-		ho = s_b4[slot] + ((unsigned)local << 2);
-	}
+	const int ob = box_own(n);
+	int hcell;
+	unsigned ho = box_shell_off(tabs.b4, n, hcell);
 	ho = ho >= kOutside ? oob4 : ho;  // out-of-domain neighbours read element g.oob here (Kernel.cu:225)
 	// FIRST: the first sample's taps out of the boxes too (below). Measured (profiles/r06_advect_box_ab.txt): it pays in the q4 form, which then fits 80 registers = six waves per SIMD,
 	// and costs the float-only form a fifth (one more 12-byte gather per thread for the velocity shell, and a barrier in front of its first gathers)
 	constexpr bool FIRST = Q4;
 	__shared__ float s_ubox[FIRST ? 3 * kBox : 1];
-	if constexpr (FIRST) {
-		s_ubox[ob] = vc.x, s_ubox[ob + kBox] = vc.y, s_ubox[ob + 2 * kBox] = vc.z;
-		if (n < kBoxShell) {
-			const f3 h = ldv(ru, ho);
-			s_ubox[hcell] = h.x, s_ubox[hcell + kBox] = h.y, s_ubox[hcell + 2 * kBox] = h.z;
-		}
-	}
+	if constexpr (FIRST) velocity_box_store<kBox>(s_ubox, n, hcell, velocity_box_load<100, 10, kBox>(s_ubox, ru, n, vc, ho));
 
-	const float bx = px - scaled_dt * vc.x, by = py - scaled_dt * vc.y, bz = pz - scaled_dt * vc.z;
+	const float bx = C.px - scaled_dt * vc.x, by = C.py - scaled_dt * vc.y, bz = C.pz - scaled_dt * vc.z;
 	unsigned bo[8], fo[8];
 	float bw[8], fw[8];
-	const int perm[8] = {0, 4, 2, 6, 1, 5, 3, 7};  // setupInterpolation's order 000,100,010,110,001,... of (x,y,z) (Kernel.cu:163-196)
-	// Where the flow moves less than a voxel per step the FIRST sample point, too, lies among the voxel's 26 neighbours: its taps (velocity here, the fields' below) come out of
-	// the boxes, per lane. Corner q of the interpolation order (x fastest: perm) sits at box offset (q & 1) * 100 + ((q >> 1) & 1) * 10 + (q >> 2).
-	const int bi = __float2int_rd(bx), bj = __float2int_rd(by), bk = __float2int_rd(bz);
-	const unsigned sx_ = (unsigned)(bi - (L.org.x - 1)), sy_ = (unsigned)(bj - (L.org.y - 1)), sz_ = (unsigned)(bk - (L.org.z - 1));
-	const bool bboxed = FIRST && max(sx_, max(sy_, sz_)) <= 8u;
-	const int ba = bboxed ? (int)((sx_ * 10u + sy_) * 10u + sz_) : 0;  // box cell of the back cell's lower corner
+	bool bboxed = false;  // the back sample's taps come out of the boxes (FIRST only)
+	int ba = 0;           // box cell of the back cell's lower corner
 	f3 vf = {0.0f, 0.0f, 0.0f};
-	// AHEAD: the velocity box of k_advect_vector_n (shell cells outside the domain read 0 there -- the descriptor's bounds check -- not element g.oob), this voxel's cell in
-	// it, and advect_vector's first sample
+	// AHEAD: the velocity box of k_advect_vector_n (shell cells outside the domain read 0 there -- the descriptor's bounds check -- not element g.oob), and advect_vector's
+	// first sample
 	__shared__ float s_vbox[AHEAD ? 3 * kVP : 1];
 	__shared__ float s_wf[AHEAD ? 3 * 512 : 1];  // (advect_vector's first sample waits here, not in three registers, while the fields are advected)
 	if constexpr (AHEAD) {
-		const int obv = ((n >> 6) + 1) * kVX + (((n >> 3) & 7) + 1) * kVY + (n & 7) + 1;
-		s_vbox[obv] = vc.x, s_vbox[obv + kVP] = vc.y, s_vbox[obv + 2 * kVP] = vc.z;
-		f3 hv = {0.0f, 0.0f, 0.0f};
-		int vcell = 0;
-		if (n < kBoxShell) {
-			int slot, local;
-			box_shell_entry<kVX, kVY>(n, slot, local, vcell);
-			hv = ldv(ru, s_b4[slot] + ((unsigned)local << 2));
-		}
+		int vcell;
+		const unsigned voff = box_shell_off<kVX, kVY>(tabs.b4, n, vcell);
+		const f3 hv = velocity_box_load<kVX, kVY, kVP>(s_vbox, ru, n, vc, voff);
 		// the eight taps of the back cell, gathered ONCE with the unmapped offsets: 0 outside the domain, which is what advect_vector samples
-		const TapsB T = make_taps_b(g, s_nbr, s_b4p, L.org, bx, by, bz);
+		const TapsB T = make_taps_b(g, C, bx, by, bz);
 		V3 c[8];  // (issued in the order the weight products consume them: the z lerp of a column follows as soon as its second tap has been added, and the pair's registers are free)
 #pragma unroll
 		for (int q = 0; q < 8; ++q) {
-			const v3f v = hns_buffer_load_v3f32(ru, (int)(T.o[perm[q]] + (T.o[perm[q]] << 1)), 0, 0);
-			c[perm[q]].xy = v2f32{v.x, v.y};
-			c[perm[q]].z = v.z;
+			const v3f v = hns_buffer_load_v3f32(ru, (int)(T.o[tap_of(q)] + (T.o[tap_of(q)] << 1)), 0, 0);
+			c[tap_of(q)].xy = v2f32{v.x, v.y};
+			c[tap_of(q)].z = v.z;
 		}
 		const float* __restrict__ uoob = u + 3 * (size_t)g.oob;
 		const f3 uo = {uoob[0], uoob[1], uoob[2]};  // what advect_scalars samples outside the domain: element g.oob (a uniform address: scalar registers)
-		if (n < kBoxShell) s_vbox[vcell] = hv.x, s_vbox[vcell + kVP] = hv.y, s_vbox[vcell + 2 * kVP] = hv.z;
-		{
-			const float tx = T.fx, ty = T.fy, tz = T.fz;
-			const float itx = 1.0f - tx, ity = 1.0f - ty, itz = 1.0f - tz;
-			const float w00 = itx * ity, w10 = tx * ity, w01 = itx * ty, w11 = tx * ty;
-			bw[0] = w00 * itz, bw[1] = w10 * itz, bw[2] = w01 * itz, bw[3] = w11 * itz, bw[4] = w00 * tz, bw[5] = w10 * tz, bw[6] = w01 * tz, bw[7] = w11 * tz;
-		}
-		// Two samples from the one set of taps. advect_scalars': the weight products, velF = velF + v * w (Kernel.cu:201-206), unfused, a tap outside the domain replaced by
-		// element g.oob. advect_vector's: nested lerps (tri_v_b) -- column z[t >> 1] = lerp(c[t - 1], c[t]) once the odd tap t has been added.
+		velocity_box_store<kVP>(s_vbox, n, vcell, hv);
+		tri_weights(T.fx, T.fy, T.fz, bw);
+		// Two samples from the one set of taps. advect_scalars': the weight products, a tap outside the domain replaced by element g.oob. advect_vector's: nested lerps
+		// (tri_v_b) -- column z[t >> 1] = lerp(c[t - 1], c[t]) once the odd tap t has been added.
 		V3 z[4];
 #pragma unroll
 		for (int q = 0; q < 8; ++q) {
-			const int t = perm[q];
+			const int t = tap_of(q);
 			const bool outside = T.o[t] >= kOutside;
 			bo[q] = outside ? oob4 : T.o[t];
-			const float tx = outside ? uo.x : c[t].xy.x, ty = outside ? uo.y : c[t].xy.y, tz = outside ? uo.z : c[t].z;
-			vf.x = vf.x + bw[q] * tx;
-			vf.y = vf.y + bw[q] * ty;
-			vf.z = vf.z + bw[q] * tz;
+			add_weighted(vf, f3{outside ? uo.x : c[t].xy.x, outside ? uo.y : c[t].xy.y, outside ? uo.z : c[t].z}, bw[q]);
 			if (t & 1) z[t >> 1] = lerp_v3(c[t - 1], c[t], T.fz);
 		}
-		{
-			const V3 y0 = lerp_v3(z[0], z[1], T.fy), y1 = lerp_v3(z[2], z[3], T.fy);
-			const V3 r = lerp_v3(y0, y1, T.fx);
-			s_wf[n] = r.xy.x, s_wf[n + 512] = r.xy.y, s_wf[n + 1024] = r.z;
-		}
+		const V3 r = tri_nest_yx(z, T.fx, T.fy, lerp_v3);
+		s_wf[n] = r.xy.x, s_wf[n + 512] = r.xy.y, s_wf[n + 1024] = r.z;
 	} else {
-		{
-			float tx, ty, tz;
-			if (bboxed) {
-				tx = bx - (float)bi, ty = by - (float)bj, tz = bz - (float)bk;  // (make_taps_b's fractions)
-#pragma unroll
-				for (int q = 0; q < 8; ++q) bo[q] = 0u;
-			} else {
-				const TapsB T = make_taps_b(g, s_nbr, s_b4p, L.org, bx, by, bz);
-				tx = T.fx, ty = T.fy, tz = T.fz;
-#pragma unroll
-				for (int q = 0; q < 8; ++q) bo[q] = T.o[perm[q]] >= kOutside ? oob4 : T.o[perm[q]];
-			}
-			const float itx = 1.0f - tx, ity = 1.0f - ty, itz = 1.0f - tz;
-			const float w00 = itx * ity, w10 = tx * ity, w01 = itx * ty, w11 = tx * ty;
-			bw[0] = w00 * itz, bw[1] = w10 * itz, bw[2] = w01 * itz, bw[3] = w11 * itz, bw[4] = w00 * tz, bw[5] = w10 * tz, bw[6] = w01 * tz, bw[7] = w11 * tz;
-		}
+		// Where the flow moves less than a voxel per step the FIRST sample point, too, lies among the voxel's 26 neighbours: its taps (velocity here, the fields' below) come out of
+		// the boxes, per lane.
+		bboxed = sample_setup<FIRST>(g, C, bx, by, bz, oob4, ba, bo, bw);
 		f3 vt[8];
 		if (!bboxed) {
 #pragma unroll
@@ -773,40 +704,17 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(Q4 || AHEAD
 		if (bboxed) {
 #pragma unroll
 			for (int q = 0; q < 8; ++q) {
-				const int a = ba + (q & 1) * 100 + ((q >> 1) & 1) * 10 + (q >> 2);
+				const int a = ba + box_corner(q);
 				vt[q] = f3{s_ubox[a], s_ubox[a + kBox], s_ubox[a + 2 * kBox]};
 			}
 		}
 #pragma unroll
-		for (int q = 0; q < 8; ++q) {  // velF = velF + v * w (Kernel.cu:201-206), unfused
-			vf.x = vf.x + bw[q] * vt[q].x;
-			vf.y = vf.y + bw[q] * vt[q].y;
-			vf.z = vf.z + bw[q] * vt[q].z;
-		}
+		for (int q = 0; q < 8; ++q) add_weighted(vf, vt[q], bw[q]);
 	}
 	// The second sample point is the voxel's own position up to s * (u(back) - u(own)): where it lands inside the leaf's 10^3 box (k_advect_vector_n, which see)
 	// the fields' forward taps are read from the LDS box that the clamp needs anyway, not gathered
-	const float qx = bx + scaled_dt * vf.x, qy = by + scaled_dt * vf.y, qz = bz + scaled_dt * vf.z;
-	const int qi = __float2int_rd(qx), qj = __float2int_rd(qy), qk = __float2int_rd(qz);
-	const unsigned rx = (unsigned)(qi - (L.org.x - 1)), ry = (unsigned)(qj - (L.org.y - 1)), rz = (unsigned)(qk - (L.org.z - 1));
-	const bool boxed = max(rx, max(ry, rz)) <= 8u;  // (per lane)
-	const int fa = boxed ? (int)((rx * 10u + ry) * 10u + rz) : 0;  // box cell of the forward cell's lower corner
-	{
-		float tx, ty, tz;
-		if (boxed) {
-			tx = qx - (float)qi, ty = qy - (float)qj, tz = qz - (float)qk;  // (make_taps_b's fractions)
-#pragma unroll
-			for (int q = 0; q < 8; ++q) fo[q] = 0u;
-		} else {
-			const TapsB T = make_taps_b(g, s_nbr, s_b4p, L.org, qx, qy, qz);
-			tx = T.fx, ty = T.fy, tz = T.fz;
-#pragma unroll
-			for (int q = 0; q < 8; ++q) fo[q] = T.o[perm[q]] >= kOutside ? oob4 : T.o[perm[q]];
-		}
-		const float itx = 1.0f - tx, ity = 1.0f - ty, itz = 1.0f - tz;
-		const float w00 = itx * ity, w10 = tx * ity, w01 = itx * ty, w11 = tx * ty;
-		fw[0] = w00 * itz, fw[1] = w10 * itz, fw[2] = w01 * itz, fw[3] = w11 * itz, fw[4] = w00 * tz, fw[5] = w10 * tz, fw[6] = w01 * tz, fw[7] = w11 * tz;
-	}
+	int fa;  // box cell of the forward cell's lower corner
+	const bool boxed = sample_setup<true>(g, C, bx + scaled_dt * vf.x, by + scaled_dt * vf.y, bz + scaled_dt * vf.z, oob4, fa, fo, fw);
 	// per field one own value per thread and one shell value per thread of the first 488; two boxes alternate so that one barrier per field suffices
 	__shared__ float s_box[2][kBox];
 	if constexpr (Q4) {
@@ -833,24 +741,16 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(Q4 || AHEAD
 		__syncthreads();
 		if (bboxed) {
 #pragma unroll
-			for (int q = 0; q < 8; ++q) phiF = __builtin_elementwise_fma(s_box4[ba + (q & 1) * 100 + ((q >> 1) & 1) * 10 + (q >> 2)], v4f32{bw[q], bw[q], bw[q], bw[q]}, phiF);
+			for (int q = 0; q < 8; ++q) phiF = __builtin_elementwise_fma(s_box4[ba + box_corner(q)], v4f32{bw[q], bw[q], bw[q], bw[q]}, phiF);
 		}
 		if (boxed) {
 #pragma unroll
-			for (int q = 0; q < 8; ++q) phiB = __builtin_elementwise_fma(s_box4[fa + (q & 1) * 100 + ((q >> 1) & 1) * 10 + (q >> 2)], v4f32{fw[q], fw[q], fw[q], fw[q]}, phiB);
+			for (int q = 0; q < 8; ++q) phiB = __builtin_elementwise_fma(s_box4[fa + box_corner(q)], v4f32{fw[q], fw[q], fw[q], fw[q]}, phiB);
 		}
-		const v4f32 error = phiOrig - phiB;
-		const v4f32 phiCorr = __builtin_elementwise_fma(v4f32{0.5f, 0.5f, 0.5f, 0.5f}, error, phiF);
-		v4f32 mn = phiOrig, mx = phiOrig;
+		v4f32 nv[6];
 #pragma unroll
-		for (int d = 0; d < 6; ++d) {
-			const v4f32 v = s_box4[e[d]];
-			mn = __builtin_elementwise_min(mn, v);
-			mx = __builtin_elementwise_max(mx, v);
-		}
-		mn = __builtin_elementwise_min(mn, phiF);
-		mx = __builtin_elementwise_max(mx, phiF);
-		const v4f32 r = __builtin_elementwise_max(mn, __builtin_elementwise_min(phiCorr, mx));
+		for (int d = 0; d < 6; ++d) nv[d] = s_box4[ob + box_nbr(d)];
+		const v4f32 r = bfecc_limit(phiOrig, nv, phiF, __builtin_elementwise_fma(v4f32{0.5f, 0.5f, 0.5f, 0.5f}, phiOrig - phiB, phiF));
 		P.q4_out[0][idx] = r.x, P.q4_out[1][idx] = r.y, P.q4_out[2][idx] = r.z, P.q4_out[3][idx] = r.w;
 	}
 	for (int s = 0; s < P.n; ++s) {
@@ -872,28 +772,20 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(Q4 || AHEAD
 		__syncthreads();
 		if (bboxed) {
 #pragma unroll
-			for (int q = 0; q < 8; ++q) vb[q] = box[ba + (q & 1) * 100 + ((q >> 1) & 1) * 10 + (q >> 2)];
+			for (int q = 0; q < 8; ++q) vb[q] = box[ba + box_corner(q)];
 		}
 #pragma unroll
 		for (int q = 0; q < 8; ++q) phiF = __fmaf_rn(vb[q], bw[q], phiF);
 		if (boxed) {
 #pragma unroll
-			for (int q = 0; q < 8; ++q) vf8[q] = box[fa + (q & 1) * 100 + ((q >> 1) & 1) * 10 + (q >> 2)];
+			for (int q = 0; q < 8; ++q) vf8[q] = box[fa + box_corner(q)];
 		}
 #pragma unroll
 		for (int q = 0; q < 8; ++q) phiB = __fmaf_rn(vf8[q], fw[q], phiB);
-		const float error = phiOrig - phiB;
-		const float phiCorr = __fmaf_rn(0.5f, error, phiF);
-		float mn = phiOrig, mx = phiOrig;
+		float nv[6];
 #pragma unroll
-		for (int d = 0; d < 6; ++d) {
-			const float v = box[e[d]];
-			mn = fminf(mn, v);
-			mx = fmaxf(mx, v);
-		}
-		mn = fminf(mn, phiF);
-		mx = fmaxf(mx, phiF);
-		P.out[s][idx] = fmaxf(mn, fminf(phiCorr, mx));
+		for (int d = 0; d < 6; ++d) nv[d] = box[ob + box_nbr(d)];
+		P.out[s][idx] = bfecc_limit(phiOrig, nv, phiF, __fmaf_rn(0.5f, phiOrig - phiB, phiF));
 	}
 	if constexpr (AHEAD) {
 		// The rest of advect_vector (k_advect_vector_n from its second pass on) comes LAST and holds no register across the field loop, where the fields' two sets of tap
@@ -901,82 +793,43 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(Q4 || AHEAD
 		__syncthreads();  // velocity box complete (with no field the loop above held no barrier)
 		int m = n;
 		asm volatile("" : "+v"(m));  // (the voxel's position and box cell are formed again here, not kept in registers from the top of the kernel)
-		const int obv = ((m >> 6) + 1) * kVX + (((m >> 3) & 7) + 1) * kVY + (m & 7) + 1;
-		const float wx = (float)(L.org.x + (m >> 6)), wy = (float)(L.org.y + ((m >> 3) & 7)), wz = (float)(L.org.z + (m & 7));
-		const f3 vo = f3{s_vbox[obv], s_vbox[obv + kVP], s_vbox[obv + 2 * kVP]};
+		const int obv = box_own<kVX, kVY>(m);
+		const int3 w = voxel_ijk(C.org, m);
+		const f3 vo = box_f3(s_vbox, obv);
 		const f3 wf = f3{s_wf[m], s_wf[m + 512], s_wf[m + 1024]};
-		const float cx = wx - scaled_dt * vo.x, cy = wy - scaled_dt * vo.y, cz = wz - scaled_dt * vo.z;  // backPos (Kernel.cu:374)
-		const float sx = cx + scaled_dt * wf.x, sy = cy + scaled_dt * wf.y, sz = cz + scaled_dt * wf.z;  // Kernel.cu:387
-		const int i = __float2int_rd(sx), j = __float2int_rd(sy), k = __float2int_rd(sz);
-		const unsigned ux = (unsigned)(i - (L.org.x - 1)), uy = (unsigned)(j - (L.org.y - 1)), uz = (unsigned)(k - (L.org.z - 1));
-		f3 wb;
-		if (__all(max(ux, max(uy, uz)) <= 8u)) {
-			wb = tri_v_box(s_vbox, (int)(ux * (unsigned)kVX + uy * (unsigned)kVY + uz), sx - (float)i, sy - (float)j, sz - (float)k);
-		} else {
-			const TapsB T2 = make_taps_b(g, s_nbr, s_b4p, L.org, sx, sy, sz);
-			wb = tri_v_b(ru, T2);
-		}
-		f3 wc = {wf.x + 0.5f * (vo.x - wb.x), wf.y + 0.5f * (vo.y - wb.y), wf.z + 0.5f * (vo.z - wb.z)};
-		const int ev[6] = {obv - kVX, obv + kVX, obv - kVY, obv + kVY, obv - 1, obv + 1};
-		f3 vmn = vo, vmx = vo;
-#pragma unroll
-		for (int d = 0; d < 6; ++d) {
-			const V3 t = box_v3(s_vbox, ev[d]);
-			vmn.x = fminf(vmn.x, t.xy.x);
-			vmx.x = fmaxf(vmx.x, t.xy.x);
-			vmn.y = fminf(vmn.y, t.xy.y);
-			vmx.y = fmaxf(vmx.y, t.xy.y);
-			vmn.z = fminf(vmn.z, t.z);
-			vmx.z = fmaxf(vmx.z, t.z);
-		}
-		vmn.x = fminf(vmn.x, wf.x);
-		vmx.x = fmaxf(vmx.x, wf.x);
-		vmn.y = fminf(vmn.y, wf.y);
-		vmx.y = fmaxf(vmx.y, wf.y);
-		vmn.z = fminf(vmn.z, wf.z);
-		vmx.z = fmaxf(vmx.z, wf.z);
-		wc.x = fmaxf(vmn.x, fminf(wc.x, vmx.x));
-		wc.y = fmaxf(vmn.y, fminf(wc.y, vmx.y));
-		wc.z = fmaxf(vmn.z, fminf(wc.z, vmx.z));
-		st3(adv_out, idx, wc);
+		const float cx = (float)w.x - scaled_dt * vo.x, cy = (float)w.y - scaled_dt * vo.y, cz = (float)w.z - scaled_dt * vo.z;  // backPos (Kernel.cu:374)
+		const f3 wb = sample_velocity(g, C, ru, s_vbox, cx + scaled_dt * wf.x, cy + scaled_dt * wf.y, cz + scaled_dt * wf.z);  // Kernel.cu:387
+		st3(adv_out, idx, bfecc_limit_v(vo, wf, wb, [&](int d) { return box_f3(s_vbox, obv + box_nbr<kVX, kVY>(d)); }));
 	}
 }
 
 template <bool COLL>
 __global__ __launch_bounds__(512) void k_advect_scalars(const GridDev g, const float* __restrict__ u, const ScalarPtrs P,
                                                         const float* __restrict__ sdf, const float scaled_dt) {
-	__shared__ int s_nbr[27];
-	__shared__ int s_base[27];
-	const LeafCtx L = stage_leaf_base(g, s_nbr, s_base, blockIdx.x);
-	const int n = threadIdx.x;
-	const int idx = L.leaf * 512 + n;
-	const int ci = L.org.x + (n >> 6), cj = L.org.y + ((n >> 3) & 7), ck = L.org.z + (n & 7);
-	const float px = (float)ci, py = (float)cj, pz = (float)ck;
+	__shared__ GenericTabs tabs;
+	GenericCtx C(g, tabs);
+	C.stage(g);
+	const int idx = C.idx;
 
 	const f3 vc = ld3(u, idx);
-	float sx = px - scaled_dt * vc.x, sy = py - scaled_dt * vc.y, sz = pz - scaled_dt * vc.z;
-	float rx = px, ry = py, rz = pz;
+	float sx = C.px - scaled_dt * vc.x, sy = C.py - scaled_dt * vc.y, sz = C.pz - scaled_dt * vc.z;
+	float rx = C.px, ry = C.py, rz = C.pz;
 	int bi[8], fi[8];
 	float bw[8], fw[8];
 #pragma unroll 1
 	for (int pass = 0; pass < 2; ++pass) {
-		Taps T = make_taps(g, s_nbr, s_base, L.org, sx, sy, sz);
+		Taps T = make_taps(g, C, sx, sy, sz);
 		if (COLL) {  // the back-position test is made twice in the reference (Kernel.cu:142-155); the repeat cannot change the outcome
 			if (tri_f_t(sdf, T) < 0.0f) {
 				sx = rx, sy = ry, sz = rz;
-				T = make_taps(g, s_nbr, s_base, L.org, sx, sy, sz);
+				T = make_taps(g, C, sx, sy, sz);
 			}
 		}
 		if (pass == 0) {
 			interp_from_taps(T, g.oob, bi, bw);
 			f3 vf = {0.0f, 0.0f, 0.0f};
 #pragma unroll
-			for (int q = 0; q < 8; ++q) {  // velF = velF + v * w (Kernel.cu:201-206), unfused
-				const f3 v = ld3(u, bi[q]);
-				vf.x = vf.x + bw[q] * v.x;
-				vf.y = vf.y + bw[q] * v.y;
-				vf.z = vf.z + bw[q] * v.z;
-			}
+			for (int q = 0; q < 8; ++q) add_weighted(vf, ld3(u, bi[q]), bw[q]);
 			rx = sx, ry = sy, rz = sz;
 			sx = sx + scaled_dt * vf.x, sy = sy + scaled_dt * vf.y, sz = sz + scaled_dt * vf.z;
 		} else {
@@ -984,7 +837,7 @@ __global__ __launch_bounds__(512) void k_advect_scalars(const GridDev g, const f
 		}
 	}
 	int nb[6];
-	nbr6(s_base, L.leaf, n, nb);
+	nbr6(tabs.base, C.leaf, C.n, nb);
 #pragma unroll
 	for (int d = 0; d < 6; ++d) nb[d] = nb[d] < 0 ? g.oob : nb[d];
 	for (int s = 0; s < P.n; ++s) {
@@ -996,18 +849,10 @@ __global__ __launch_bounds__(512) void k_advect_scalars(const GridDev g, const f
 			phiF = __fmaf_rn(in[bi[q]], bw[q], phiF);
 			phiB = __fmaf_rn(in[fi[q]], fw[q], phiB);
 		}
-		const float error = phiOrig - phiB;
-		const float phiCorr = __fmaf_rn(0.5f, error, phiF);
-		float mn = phiOrig, mx = phiOrig;
+		float nv[6];
 #pragma unroll
-		for (int d = 0; d < 6; ++d) {
-			const float v = in[nb[d]];
-			mn = fminf(mn, v);
-			mx = fmaxf(mx, v);
-		}
-		mn = fminf(mn, phiF);
-		mx = fmaxf(mx, phiF);
-		P.out[s][idx] = fmaxf(mn, fminf(phiCorr, mx));
+		for (int d = 0; d < 6; ++d) nv[d] = in[nb[d]];
+		P.out[s][idx] = bfecc_limit(phiOrig, nv, phiF, __fmaf_rn(0.5f, phiOrig - phiB, phiF));
 	}
 }
 
@@ -1020,6 +865,33 @@ static bool narrow_fields(const hns_grid* g) {
 	return !options().advect_generic.load() && (uint64_t)g->topo.n_leaves * 6144u <= hns::kNarrowBytes;
 }
 
+// which of an operator's three kernels a call gets: the generic one with its collision branch, the 32-bit addressed one, or the generic one
+enum class AdvectForm { collision, narrow, generic };
+static AdvectForm advect_form(const hns_grid* g, const float* sdf, int has_collision) {
+	return has_collision && sdf ? AdvectForm::collision : (narrow_fields(g) ? AdvectForm::narrow : AdvectForm::generic);
+}
+
+// The launch tables of the advect_scalars kernels in the 32-bit form: leaves backwards. The gradient kernel has just written the velocity front to back; starting on its
+// cached tail also leaves the head cached for the next substep's advect_vector (256^3: -1 % here, -4 % there).
+static GridDev reversed(const hns_grid* g) {
+	GridDev gd = g->dev();
+	gd.rev = 1;
+	return gd;
+}
+
+// n float fields (at most HNS_MAX_SCALARS) and no q4 element; returns the first field with a null pointer, -1 if none
+static int fill_scalar_ptrs(ScalarPtrs& P, const float* const* in, float* const* out, int n) {
+	int bad = -1;
+	P.n = n;
+	P.q4 = nullptr, P.q4_out[0] = P.q4_out[1] = P.q4_out[2] = P.q4_out[3] = nullptr;
+	for (int s = 0; s < HNS_MAX_SCALARS; ++s) {
+		P.in[s] = s < n ? in[s] : nullptr;
+		P.out[s] = s < n ? out[s] : nullptr;
+		if (s < n && (!P.in[s] || !P.out[s]) && bad < 0) bad = s;
+	}
+	return bad;
+}
+
 extern "C" {
 
 int hns_dev_advect_vector(hns_grid* g, const float* vel3, float* out3, const float* sdf, int has_collision, float dt, float inv_dx, void* stream) {
@@ -1029,12 +901,11 @@ int hns_dev_advect_vector(hns_grid* g, const float* vel3, float* out3, const flo
 	if (g->n_active == 0) return HNS_OK;
 	const float scaled_dt = dt * inv_dx;  // Kernel.cu:361
 	const dim3 grid((unsigned)g->n_active), block(512);
-	if (has_collision && sdf)
-		hipLaunchKernelGGL(k_advect_vector<true>, grid, block, 0, (hipStream_t)stream, g->dev(), vel3, out3, sdf, scaled_dt, inv_dx);
-	else if (narrow_fields(g))
-		hipLaunchKernelGGL(k_advect_vector_n, grid, block, 0, (hipStream_t)stream, g->dev(), vel3, out3, scaled_dt);
-	else
-		hipLaunchKernelGGL(k_advect_vector<false>, grid, block, 0, (hipStream_t)stream, g->dev(), vel3, out3, sdf, scaled_dt, inv_dx);
+	switch (advect_form(g, sdf, has_collision)) {
+	case AdvectForm::collision: hipLaunchKernelGGL(k_advect_vector<true>, grid, block, 0, (hipStream_t)stream, g->dev(), vel3, out3, sdf, scaled_dt, inv_dx); break;
+	case AdvectForm::narrow: hipLaunchKernelGGL(k_advect_vector_n, grid, block, 0, (hipStream_t)stream, g->dev(), vel3, out3, scaled_dt); break;
+	case AdvectForm::generic: hipLaunchKernelGGL(k_advect_vector<false>, grid, block, 0, (hipStream_t)stream, g->dev(), vel3, out3, sdf, scaled_dt, inv_dx); break;
+	}
 	return launch_status("hns_dev_advect_vector");
 }
 
@@ -1045,12 +916,11 @@ int hns_dev_advect_scalar(hns_grid* g, const float* vel3, const float* in, float
 	if (g->n_active == 0) return HNS_OK;
 	const float scaled_dt = dt * inv_dx;
 	const dim3 grid((unsigned)g->n_active), block(512);
-	if (has_collision && sdf)
-		hipLaunchKernelGGL(k_advect_scalar<true>, grid, block, 0, (hipStream_t)stream, g->dev(), vel3, in, out, sdf, scaled_dt);
-	else if (narrow_fields(g))
-		hipLaunchKernelGGL(k_advect_scalar_n, grid, block, 0, (hipStream_t)stream, g->dev(), vel3, in, out, scaled_dt);
-	else
-		hipLaunchKernelGGL(k_advect_scalar<false>, grid, block, 0, (hipStream_t)stream, g->dev(), vel3, in, out, sdf, scaled_dt);
+	switch (advect_form(g, sdf, has_collision)) {
+	case AdvectForm::collision: hipLaunchKernelGGL(k_advect_scalar<true>, grid, block, 0, (hipStream_t)stream, g->dev(), vel3, in, out, sdf, scaled_dt); break;
+	case AdvectForm::narrow: hipLaunchKernelGGL(k_advect_scalar_n, grid, block, 0, (hipStream_t)stream, g->dev(), vel3, in, out, scaled_dt); break;
+	case AdvectForm::generic: hipLaunchKernelGGL(k_advect_scalar<false>, grid, block, 0, (hipStream_t)stream, g->dev(), vel3, in, out, sdf, scaled_dt); break;
+	}
 	return launch_status("hns_dev_advect_scalar");
 }
 
@@ -1064,28 +934,16 @@ int hns_dev_advect_scalars(hns_grid* g, const float* vel3, const float* const* i
 	// the backtrace does not depend on the fields, so splitting S fields over several launches changes nothing numerically
 	for (int base = 0; base < n; base += HNS_MAX_SCALARS) {
 		ScalarPtrs P;
-		P.n = n - base < HNS_MAX_SCALARS ? n - base : HNS_MAX_SCALARS;
-		for (int s = 0; s < HNS_MAX_SCALARS; ++s) {
-			P.q4 = nullptr, P.q4_out[0] = P.q4_out[1] = P.q4_out[2] = P.q4_out[3] = nullptr;
-			P.in[s] = s < P.n ? in[base + s] : nullptr;
-			P.out[s] = s < P.n ? out[base + s] : nullptr;
-			if (s < P.n && (!P.in[s] || !P.out[s])) {
-				set_error("hns_dev_advect_scalars: null device pointer for field %d", base + s);
-				return HNS_ERR_INVALID_ARGUMENT;
-			}
+		const int bad = fill_scalar_ptrs(P, in + base, out + base, n - base < HNS_MAX_SCALARS ? n - base : HNS_MAX_SCALARS);
+		if (bad >= 0) {
+			set_error("hns_dev_advect_scalars: null device pointer for field %d", base + bad);
+			return HNS_ERR_INVALID_ARGUMENT;
 		}
-		if (has_collision && sdf)
-			hipLaunchKernelGGL(k_advect_scalars<true>, grid, block, 0, (hipStream_t)stream, g->dev(), vel3, P, sdf, scaled_dt);
-		else if (narrow_fields(g))
-		{
-			GridDev gd = g->dev();
-			// backwards: the gradient kernel has just written the velocity front to back; starting on its cached tail also
-			// leaves the head cached for the next substep's advect_vector (256^3: -1 % here, -4 % there).
-			gd.rev = 1;
-			hipLaunchKernelGGL(k_advect_scalars_n<false>, grid, block, 0, (hipStream_t)stream, gd, vel3, P, scaled_dt, (float*)nullptr);
+		switch (advect_form(g, sdf, has_collision)) {
+		case AdvectForm::collision: hipLaunchKernelGGL(k_advect_scalars<true>, grid, block, 0, (hipStream_t)stream, g->dev(), vel3, P, sdf, scaled_dt); break;
+		case AdvectForm::narrow: hipLaunchKernelGGL(k_advect_scalars_n<false>, grid, block, 0, (hipStream_t)stream, reversed(g), vel3, P, scaled_dt, (float*)nullptr); break;
+		case AdvectForm::generic: hipLaunchKernelGGL(k_advect_scalars<false>, grid, block, 0, (hipStream_t)stream, g->dev(), vel3, P, sdf, scaled_dt); break;
 		}
-		else
-			hipLaunchKernelGGL(k_advect_scalars<false>, grid, block, 0, (hipStream_t)stream, g->dev(), vel3, P, sdf, scaled_dt);
 	}
 	return launch_status("hns_dev_advect_scalars");
 }
@@ -1103,19 +961,12 @@ int hns_dev_advect_scalars_ahead(hns_grid* g, const float* vel3, const float* co
 	if (!narrow_fields(g)) return fail(HNS_ERR_INVALID_ARGUMENT, "hns_dev_advect_scalars_ahead: grid too large for 32-bit offsets (or option advect = generic)");
 	if (g->n_active == 0) return HNS_OK;
 	ScalarPtrs P;
-	P.n = n;
-	P.q4 = nullptr, P.q4_out[0] = P.q4_out[1] = P.q4_out[2] = P.q4_out[3] = nullptr;
-	for (int s = 0; s < HNS_MAX_SCALARS; ++s) {
-		P.in[s] = s < n ? in[s] : nullptr;
-		P.out[s] = s < n ? out[s] : nullptr;
-		if (s < n && (!P.in[s] || !P.out[s])) {
-			set_error("hns_dev_advect_scalars_ahead: null device pointer for field %d", s);
-			return HNS_ERR_INVALID_ARGUMENT;
-		}
+	const int bad = fill_scalar_ptrs(P, in, out, n);
+	if (bad >= 0) {
+		set_error("hns_dev_advect_scalars_ahead: null device pointer for field %d", bad);
+		return HNS_ERR_INVALID_ARGUMENT;
 	}
-	GridDev gd = g->dev();
-	gd.rev = 1;  // (as hns_dev_advect_scalars)
-	hipLaunchKernelGGL((k_advect_scalars_n<false, true>), dim3((unsigned)g->n_active), dim3(512), 0, (hipStream_t)stream, gd, vel3, P, dt * inv_dx, adv_out3);
+	hipLaunchKernelGGL((k_advect_scalars_n<false, true>), dim3((unsigned)g->n_active), dim3(512), 0, (hipStream_t)stream, reversed(g), vel3, P, dt * inv_dx, adv_out3);
 	return launch_status("hns_dev_advect_scalars_ahead");
 }
 
@@ -1127,21 +978,12 @@ int hns_advect_scalars_q4(hns_grid* g, const float* vel3, const float* q4, float
 	NULLCHK(!vel3 || !q4 || !q4_out || (n > 0 && (!in || !out)), "hns_advect_scalars_q4");
 	if (!hns_advect_q4_ok(g) || n > HNS_MAX_SCALARS) return fail(HNS_ERR_INVALID_ARGUMENT, "hns_advect_scalars_q4: grid too large for 32-bit offsets, or too many fields");
 	if (g->n_active == 0) return HNS_OK;
+	for (int c = 0; c < 4; ++c) NULLCHK(!q4_out[c], "hns_advect_scalars_q4");
 	ScalarPtrs P;
-	P.n = n;
+	NULLCHK(fill_scalar_ptrs(P, in, out, n) >= 0, "hns_advect_scalars_q4");
 	P.q4 = q4;
-	for (int c = 0; c < 4; ++c) {
-		NULLCHK(!q4_out[c], "hns_advect_scalars_q4");
-		P.q4_out[c] = q4_out[c];
-	}
-	for (int s = 0; s < HNS_MAX_SCALARS; ++s) {
-		P.in[s] = s < n ? in[s] : nullptr;
-		P.out[s] = s < n ? out[s] : nullptr;
-		NULLCHK(s < n && (!P.in[s] || !P.out[s]), "hns_advect_scalars_q4");
-	}
-	GridDev gd = g->dev();
-	gd.rev = 1;  // (as hns_dev_advect_scalars)
-	hipLaunchKernelGGL(k_advect_scalars_n<true>, dim3((unsigned)g->n_active), dim3(512), 0, (hipStream_t)stream, gd, vel3, P, dt * inv_dx, (float*)nullptr);
+	for (int c = 0; c < 4; ++c) P.q4_out[c] = q4_out[c];
+	hipLaunchKernelGGL(k_advect_scalars_n<true>, dim3((unsigned)g->n_active), dim3(512), 0, (hipStream_t)stream, reversed(g), vel3, P, dt * inv_dx, (float*)nullptr);
 	return launch_status("hns_advect_scalars_q4");
 }
 

@@ -102,6 +102,31 @@ __device__ __forceinline__ float lerp_f(float a, float b, float w) { return a + 
 // Vec3f lerp on the device branch (Stencils.hpp:131-135): fmaf(w, b-a, a)
 __device__ __forceinline__ float lerp_c(float a, float b, float w) { return __fmaf_rn(w, b - a, a); }
 
+// ---- raw buffer access ---------------------------------------------------------------------------------------------
+// A buffer descriptor over a field takes a 32-bit byte offset, and the hardware bounds-checks it: a load at or past the
+// descriptor's end returns 0 without touching memory and a store there is dropped. hns_advect.hip (which see: "32-bit addressed
+// field access"), hns_sorblock.hip and hns_regrid.hip build on that.
+typedef float v2f32 __attribute__((ext_vector_type(2)));
+typedef float v3f __attribute__((ext_vector_type(3)));
+typedef float v4f32 __attribute__((ext_vector_type(4)));
+typedef int v4i __attribute__((ext_vector_type(4)));
+// through the LLVM intrinsics (this toolchain's __builtin_amdgcn_raw_buffer_load_b96 returns one dword)
+__device__ float hns_buffer_load_f32(v4i rsrc, int voffset, int soffset, int aux) __asm("llvm.amdgcn.raw.buffer.load.f32");
+__device__ v2f32 hns_buffer_load_v2f32(v4i rsrc, int voffset, int soffset, int aux) __asm("llvm.amdgcn.raw.buffer.load.v2f32");
+__device__ v3f hns_buffer_load_v3f32(v4i rsrc, int voffset, int soffset, int aux) __asm("llvm.amdgcn.raw.buffer.load.v3f32");
+__device__ v4f32 hns_buffer_load_v4f32(v4i rsrc, int voffset, int soffset, int aux) __asm("llvm.amdgcn.raw.buffer.load.v4f32");
+__device__ void hns_buffer_store_v4f32(v4f32 data, v4i rsrc, int voffset, int soffset, int aux) __asm("llvm.amdgcn.raw.buffer.store.v4f32");
+
+__device__ __forceinline__ v4i field_rsrc(const float* p, unsigned bytes) {
+	const unsigned long long a = (unsigned long long)p;
+	v4i r;
+	r.x = __builtin_amdgcn_readfirstlane((int)(unsigned)a);
+	r.y = __builtin_amdgcn_readfirstlane((int)((unsigned)(a >> 32) & 0xffffu));  // stride 0: raw buffer
+	r.z = __builtin_amdgcn_readfirstlane((int)bytes);                            // num_records in bytes: offsets at or past it read 0 / are not stored
+	r.w = 0x00020000;                                                            // 32-bit float data format
+	return r;
+}
+
 
 // ---- launch order ------------------------------------------------------------------------------------------------
 // Block -> leaf order. The dispatcher places workgroup b on XCD b % 8 (observed, not contractual), each XCD has a

@@ -41,12 +41,6 @@
 #include "hns_device.hpp"
 #include "hns_dilate.hpp"
 
-// raw buffer loads through the LLVM intrinsics (hns_sim_deactivate's kernel; as in hns_advect.hip)
-typedef int v4i_act __attribute__((ext_vector_type(4)));
-typedef float v3f_act __attribute__((ext_vector_type(3)));
-__device__ float hns_act_load_f32(v4i_act rsrc, int voffset, int soffset, int aux) __asm("llvm.amdgcn.raw.buffer.load.f32");
-__device__ v3f_act hns_act_load_v3f32(v4i_act rsrc, int voffset, int soffset, int aux) __asm("llvm.amdgcn.raw.buffer.load.v3f32");
-
 namespace hns {
 namespace {
 
@@ -710,16 +704,6 @@ __global__ __launch_bounds__(64) void k_deactivate_table(ActRows rows, int n, Ac
 // for each load before the next).
 constexpr int kActSkip = 0x40000000;  // a byte offset past any leaf
 
-__device__ __forceinline__ v4i_act leaf_rsrc(const float* p, unsigned bytes) {
-	const unsigned long long a = (unsigned long long)p;
-	v4i_act r;
-	r.x = __builtin_amdgcn_readfirstlane((int)(unsigned)a);
-	r.y = __builtin_amdgcn_readfirstlane((int)((unsigned)(a >> 32) & 0xffffu));  // stride 0: raw buffer
-	r.z = (int)bytes;                                                            // num_records in bytes
-	r.w = 0x00020000;                                                            // 32-bit float data format
-	return r;
-}
-
 __device__ __forceinline__ uint64_t readlane64(uint64_t v, int lane) {
 	const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, lane), hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), lane);
 	return (uint64_t)hi << 32 | lo;
@@ -738,17 +722,17 @@ __global__ __launch_bounds__(256) void k_deactivate(const ActField* __restrict__
 	for (int f = 0; f < n_tab; ++f) {
 		const ActField e = tab[f];
 		if (e.ncomp == 1) {
-			const v4i_act r = leaf_rsrc(e.p + 512 * leaf, 2048u);
+			const v4i r = field_rsrc(e.p + 512 * leaf, 2048u);
 			float x[8];
 #pragma unroll
-			for (int k = 0; k < 8; ++k) x[k] = hns_act_load_f32(r, pend[k] ? 4 * (64 * k + lane) : kActSkip, 0, 0);
+			for (int k = 0; k < 8; ++k) x[k] = hns_buffer_load_f32(r, pend[k] ? 4 * (64 * k + lane) : kActSkip, 0, 0);
 #pragma unroll
 			for (int k = 0; k < 8; ++k) pend[k] &= __ballot(fabsf(x[k]) <= e.tol);
 		} else {
-			const v4i_act r = leaf_rsrc(e.p + 1536 * leaf, 6144u);
-			v3f_act x[8];
+			const v4i r = field_rsrc(e.p + 1536 * leaf, 6144u);
+			v3f x[8];
 #pragma unroll
-			for (int k = 0; k < 8; ++k) x[k] = hns_act_load_v3f32(r, pend[k] ? 12 * (64 * k + lane) : kActSkip, 0, 0);
+			for (int k = 0; k < 8; ++k) x[k] = hns_buffer_load_v3f32(r, pend[k] ? 12 * (64 * k + lane) : kActSkip, 0, 0);
 #pragma unroll
 			for (int k = 0; k < 8; ++k) pend[k] &= __ballot(fabsf(x[k].x) <= e.tol && fabsf(x[k].y) <= e.tol && fabsf(x[k].z) <= e.tol);
 		}

@@ -34,20 +34,7 @@
 
 namespace hns {
 
-typedef float sb4f __attribute__((ext_vector_type(4)));
-typedef int sb4i __attribute__((ext_vector_type(4)));
-__device__ sb4f sb_load4(sb4i rsrc, int voffset, int soffset, int aux) __asm("llvm.amdgcn.raw.buffer.load.v4f32");
-__device__ void sb_store4(sb4f data, sb4i rsrc, int voffset, int soffset, int aux) __asm("llvm.amdgcn.raw.buffer.store.v4f32");
-
-__device__ __forceinline__ sb4i sb_rsrc(const float* p, unsigned bytes) {
-	const unsigned long long a = (unsigned long long)p;
-	sb4i r;
-	r.x = __builtin_amdgcn_readfirstlane((int)(unsigned)a);
-	r.y = __builtin_amdgcn_readfirstlane((int)((unsigned)(a >> 32) & 0xffffu));  // stride 0: raw buffer
-	r.z = __builtin_amdgcn_readfirstlane((int)bytes);                            // bytes covered: offsets at or past it read 0 / are not stored
-	r.w = 0x00020000;
-	return r;
-}
+// (tile loads and block stores: raw buffer access over a whole field, hns_device.hpp)
 
 template <int LB, int K>
 struct SbGeo {
@@ -193,15 +180,15 @@ __device__ __forceinline__ void sb_body(SbLds<LB, K>& L, const int t, const int*
 		r.ok[cz] = id >= 0 ? 0xFFFFFFFFu : 0u;
 		base[cz] = (unsigned)id * 2048u + row_bytes;
 	}
-	const sb4i rp = sb_rsrc(p_in, field_bytes), rd = sb_rsrc(div, field_bytes), ro = sb_rsrc(p_out, field_bytes);
-	sb4f pc[NCH], dc[NCH];
+	const v4i rp = field_rsrc(p_in, field_bytes), rd = field_rsrc(div, field_bytes), ro = field_rsrc(p_out, field_bytes);
+	v4f32 pc[NCH], dc[NCH];
 #pragma unroll
 	for (int j = 0; j < NCH; ++j) {
 		const int cz = (4 * j - H + 8) >> 3, zl = (4 * j - H) & 7;
 		const unsigned off = base[cz] + (unsigned)(zl * 4);
-		dc[j] = sb_load4(rd, (int)off, 0, 0);
-		if (ZERO) pc[j] = sb4f{0.0f, 0.0f, 0.0f, 0.0f};
-		else pc[j] = sb_load4(rp, (int)off, 0, 0);
+		dc[j] = hns_buffer_load_v4f32(rd, (int)off, 0, 0);
+		if (ZERO) pc[j] = v4f32{0.0f, 0.0f, 0.0f, 0.0f};
+		else pc[j] = hns_buffer_load_v4f32(rp, (int)off, 0, 0);
 	}
 	// Rim duty of the first RIM threads of the section: one rim row of this parity each -- p only, straight into LDS (nobody
 	// updates a rim row). Side 0: x = 0, 1: x = T-1, 2: y = 0, 3: y = T-1; the m-th row of the right parity along the side.
@@ -215,9 +202,9 @@ __device__ __forceinline__ void sb_body(SbLds<LB, K>& L, const int t, const int*
 		unsigned rbase[C];
 #pragma unroll
 		for (int cz = 0; cz < C; ++cz) rbase[cz] = (unsigned)rrec[cz] * 2048u + rrow;
-		sb4f rc[NCH];
+		v4f32 rc[NCH];
 #pragma unroll
-		for (int j = 0; j < NCH; ++j) rc[j] = ZERO ? sb4f{0.0f, 0.0f, 0.0f, 0.0f} : sb_load4(rp, (int)(rbase[(4 * j - H + 8) >> 3] + (unsigned)(((4 * j - H) & 7) * 4)), 0, 0);
+		for (int j = 0; j < NCH; ++j) rc[j] = ZERO ? v4f32{0.0f, 0.0f, 0.0f, 0.0f} : hns_buffer_load_v4f32(rp, (int)(rbase[(4 * j - H + 8) >> 3] + (unsigned)(((4 * j - H) & 7) * 4)), 0, 0);
 		float4* LR = L.arr(PAR ? 1 : 0, 0) + (rx * HALF + (ry >> 1)) * HS4;
 		float4* LK = L.arr(PAR ? 1 : 0, 1) + (rx * HALF + (ry >> 1)) * HS4;
 		float rr[HALF + 4], rb[HALF + 4];
@@ -264,10 +251,10 @@ __device__ __forceinline__ void sb_body(SbLds<LB, K>& L, const int t, const int*
 #pragma unroll
 		for (int j = H / 4; j < NCH - H / 4; ++j) {
 			const int cz = (4 * j - H + 8) >> 3, zl = (4 * j - H) & 7;
-			sb4f v;
+			v4f32 v;
 			v.x = PAR ? r.B[2 * j] : r.R[2 * j], v.y = PAR ? r.R[2 * j] : r.B[2 * j];
 			v.z = PAR ? r.B[2 * j + 1] : r.R[2 * j + 1], v.w = PAR ? r.R[2 * j + 1] : r.B[2 * j + 1];
-			sb_store4(v, ro, (int)(base[cz] + (unsigned)(zl * 4)), 0, 0);
+			hns_buffer_store_v4f32(v, ro, (int)(base[cz] + (unsigned)(zl * 4)), 0, 0);
 		}
 	}
 }
@@ -281,7 +268,7 @@ struct SbLeanRow {
 
 // 16 bytes (z = 4 * half .. 4 * half + 3 of z-row `row`) of boundary leaf `leaf` into the ghost copies the peers keep of it: the chained
 // blocked sweep of a multi-GPU rank (hns_flags.hpp). `mine` = this lane's piece belongs to `leaf`; the table walk is wave-uniform.
-__device__ __forceinline__ void chain_store_piece(const PhaseMirror& m, int leaf, bool mine, int row, int half, sb4f v) {
+__device__ __forceinline__ void chain_store_piece(const PhaseMirror& m, int leaf, bool mine, int row, int half, v4f32 v) {
 	const int e1 = m.first[leaf + 1];
 	for (int e = m.first[leaf]; e < e1; ++e) {
 		const int2 t = m.entry[e];
@@ -300,7 +287,7 @@ __device__ __forceinline__ void chain_store_piece(const PhaseMirror& m, int leaf
 }
 
 // the same piece into the peers' MESSAGES (PackMirror: the boundary sweep of an exchanged pressure loop packs what it stores)
-__device__ __forceinline__ void chain_store_piece(const PackMirror& m, int leaf, bool mine, int row, int half, sb4f v) {
+__device__ __forceinline__ void chain_store_piece(const PackMirror& m, int leaf, bool mine, int row, int half, v4f32 v) {
 	const int e1 = m.first[leaf + 1];
 	for (int e = m.first[leaf]; e < e1; ++e) {
 		const int2 t = m.entry[e];
@@ -359,22 +346,22 @@ __device__ __forceinline__ void sb_sweep_xy(Row& r, SbLdsXY& L, const int bi, co
 	if (dist >= S) {
 		// red sweep: own red at bi - TC (red array), own black at bi, lateral neighbours' black at bi +- TC, ypb, ymb.
 		// black sweep (dist >= 2: every neighbour is an interior row of planes 1 .. T-2): own black at bi, own red at bi - TC, neighbours' red at bi - TC +- TC, bi - TC +- 1.
-		sb4f* LXo4 = reinterpret_cast<sb4f*>((red ? L.red() + (bi - TC) * HS4 : L.black() + bi * HS4));
-		const sb4f* LYo4 = reinterpret_cast<const sb4f*>((red ? L.black() + bi * HS4 : L.red() + (bi - TC) * HS4));
+		v4f32* LXo4 = reinterpret_cast<v4f32*>((red ? L.red() + (bi - TC) * HS4 : L.black() + bi * HS4));
+		const v4f32* LYo4 = reinterpret_cast<const v4f32*>((red ? L.black() + bi * HS4 : L.red() + (bi - TC) * HS4));
 		const float4* LY = red ? L.black() : L.red() - TC * HS4;  // (indexed with BLACK entry numbers either way)
 		float Y[HALF];
 #pragma unroll
 		for (int q = 0; q < NQ; ++q) {
-			const sb4f y4 = LYo4[q];
+			const v4f32 y4 = LYo4[q];
 			Y[4 * q] = y4.x, Y[4 * q + 1] = y4.y, Y[4 * q + 2] = y4.z, Y[4 * q + 3] = y4.w;
 		}
-		const sb4f* pxp = reinterpret_cast<const sb4f*>(LY + (bi + TC) * HS4);
-		const sb4f* pxm = reinterpret_cast<const sb4f*>(LY + (bi - TC) * HS4);
-		const sb4f* pyp = reinterpret_cast<const sb4f*>(LY + (red ? ypb : bi + 1) * HS4);
-		const sb4f* pym = reinterpret_cast<const sb4f*>(LY + (red ? ymb : bi - 1) * HS4);
+		const v4f32* pxp = reinterpret_cast<const v4f32*>(LY + (bi + TC) * HS4);
+		const v4f32* pxm = reinterpret_cast<const v4f32*>(LY + (bi - TC) * HS4);
+		const v4f32* pyp = reinterpret_cast<const v4f32*>(LY + (red ? ypb : bi + 1) * HS4);
+		const v4f32* pym = reinterpret_cast<const v4f32*>(LY + (red ? ymb : bi - 1) * HS4);
 #pragma unroll
 		for (int q = qlo; q < qhi; ++q) {
-			sb4f x4 = LXo4[q], xp4 = pxp[q], xm4 = pxm[q], yp4 = pyp[q], ym4 = pym[q];
+			v4f32 x4 = LXo4[q], xp4 = pxp[q], xm4 = pxm[q], yp4 = pyp[q], ym4 = pym[q];
 			if (4 * q < jlo || 4 * q + 4 > jhi) {  // a piece only part of which is updated: keep its accesses whole (partial pieces make the compiler split the LDS accesses into narrower, conflicting ones)
 				asm volatile("" : "+v"(x4));
 				asm volatile("" : "+v"(xp4));
@@ -395,7 +382,7 @@ __device__ __forceinline__ void sb_sweep_xy(Row& r, SbLdsXY& L, const int bi, co
 				const int cz = (2 * j - H + 8) >> 3;
 				X[e] = MASKED ? __uint_as_float(__float_as_uint(cand) & r.ok[cz]) : cand;
 			}
-			sb4f o4 = sb4f{X[0], X[1], X[2], X[3]};
+			v4f32 o4 = v4f32{X[0], X[1], X[2], X[3]};
 			if (4 * q < jlo || 4 * q + 4 > jhi) asm volatile("" : "+v"(o4));
 			LXo4[q] = o4;
 			__builtin_amdgcn_sched_barrier(0);
@@ -487,14 +474,14 @@ __global__ __attribute__((amdgpu_waves_per_eu(6, 8))) __launch_bounds__((SbGeo<2
 		chain_begin(m, chain_leaf);
 		__syncthreads();
 	}
-	const sb4i rp = sb_rsrc(p_in, field_bytes), rd = sb_rsrc(div, field_bytes), ro = sb_rsrc(p_out, field_bytes);
-	sb4f pc[NCH], dc[NCH], rimv;
+	const v4i rp = field_rsrc(p_in, field_bytes), rd = field_rsrc(div, field_bytes), ro = field_rsrc(p_out, field_bytes);
+	v4f32 pc[NCH], dc[NCH], rimv;
 #pragma unroll
-	for (int j = 0; j < NCH; ++j) pc[j] = ZERO ? sb4f{0.0f, 0.0f, 0.0f, 0.0f} : sb_load4(rp, (int)(base[(4 * j - H + 8) >> 3] + (unsigned)(((4 * j - H) & 7) * 4)), 0, 0);
+	for (int j = 0; j < NCH; ++j) pc[j] = ZERO ? v4f32{0.0f, 0.0f, 0.0f, 0.0f} : hns_buffer_load_v4f32(rp, (int)(base[(4 * j - H + 8) >> 3] + (unsigned)(((4 * j - H) & 7) * 4)), 0, 0);
 	__builtin_amdgcn_sched_barrier(0);
-	rimv = ZERO ? sb4f{0.0f, 0.0f, 0.0f, 0.0f} : sb_load4(rp, (int)((unsigned)(rim_want ? rim_id : -1) * 2048u + rim_off), 0, 0);
+	rimv = ZERO ? v4f32{0.0f, 0.0f, 0.0f, 0.0f} : hns_buffer_load_v4f32(rp, (int)((unsigned)(rim_want ? rim_id : -1) * 2048u + rim_off), 0, 0);
 #pragma unroll
-	for (int j = 0; j < NCH; ++j) dc[j] = sb_load4(rd, (int)(dbase[(4 * j - H + 8) >> 3] + (unsigned)(((4 * j - H) & 7) * 4)), 0, 0);
+	for (int j = 0; j < NCH; ++j) dc[j] = hns_buffer_load_v4f32(rd, (int)(dbase[(4 * j - H + 8) >> 3] + (unsigned)(((4 * j - H) & 7) * 4)), 0, 0);
 	if (t < 64) s_rec[t] = rec_word;  // (the block record for the store phase; visible behind the staging barrier)
 	if (rim_on) {
 		float2* LK = reinterpret_cast<float2*>(L.black()) + rim_b2;  // (black only: even z of a row with odd x+y, odd z of one with even x+y)
@@ -507,7 +494,7 @@ __global__ __attribute__((amdgpu_waves_per_eu(6, 8))) __launch_bounds__((SbGeo<2
 		float4* LO = par ? L.red() + (bi - TC) * HS4 : L.black() + bi * HS4;
 #pragma unroll
 		for (int q = 0; q < G::NQ; ++q) {
-			const sb4f u = pc[2 * q], v = pc[2 * q + 1];
+			const v4f32 u = pc[2 * q], v = pc[2 * q + 1];
 			LE[q] = make_float4(u.x, u.z, v.x, v.z);
 			LO[q] = make_float4(u.y, u.w, v.y, v.w);
 		}
@@ -547,9 +534,9 @@ __global__ __attribute__((amdgpu_waves_per_eu(6, 8))) __launch_bounds__((SbGeo<2
 			const float2 rr = R2[(sb - TC) * HS4 * 2 + j], bb = B2[sb * HS4 * 2 + j];
 			const int cell = (((xx >> 3) << 1) | (yy >> 3)) << 1 | czb;
 			const int id = (meta >> (8 + cell)) & 1 ? s_rec[((1 + (xx >> 3)) * C + 1 + (yy >> 3)) * C + 1 + czb] : -1;  // (a leaf outside the launch range is a source only)
-			sb4f v;
+			v4f32 v;
 			v.x = sp ? bb.x : rr.x, v.y = sp ? rr.x : bb.x, v.z = sp ? bb.y : rr.y, v.w = sp ? rr.y : bb.y;
-			sb_store4(v, ro, (int)((unsigned)id * 2048u + (unsigned)((((xx & 7) << 3) | (yy & 7)) * 32 + jz * 16)), 0, 0);
+			hns_buffer_store_v4f32(v, ro, (int)((unsigned)id * 2048u + (unsigned)((((xx & 7) << 3) | (yy & 7)) * 32 + jz * 16)), 0, 0);
 			if constexpr (!std::is_same<M, NoMirror>::value) {
 				// (piece n of every thread lies in the block's x half n, the walk over that half's four leaves and over a leaf's table entries is wave-uniform)
 				if (meta & 2) {
