@@ -53,6 +53,23 @@ class hns_activity_field(C.Structure):
     _fields_ = [("name", C.c_char_p), ("ncomp", C.c_int), ("tolerance", C.c_float)]
 
 
+class hns_stats(C.Structure):
+    _fields_ = [("count", C.c_uint64), ("nan_count", C.c_uint64), ("min", C.c_float), ("max", C.c_float), ("max_abs", C.c_float), ("reserved", C.c_uint32),
+                ("sum", C.c_double), ("sum_sq", C.c_double)]
+
+
+class hns_stats_field(C.Structure):
+    _fields_ = [("name", C.c_char_p), ("ncomp", C.c_int)]
+
+
+class hns_solve_control(C.Structure):
+    _fields_ = [("rel_tol", C.c_float), ("abs_tol", C.c_float), ("check_every", C.c_int)]
+
+
+class hns_solve_report(C.Structure):
+    _fields_ = [("iterations", C.c_int), ("checks", C.c_int), ("converged", C.c_int), ("initial", hns_stats), ("final", hns_stats)]
+
+
 class hns_combustion_params(C.Structure):
     _fields_ = [(n, C.c_float) for n in ("expansionRate", "temperatureRelease", "buoyancyStrength", "ambientTemp", "vorticityScale", "factorScale")]
 
@@ -93,6 +110,7 @@ SIGNATURES = {
     "hns_union_leaves": (_i, [_vp, _u64, _vp, _u64, _vp, _u64, C.POINTER(C.c_uint64)]),
     "hns_add_leaves": (_i, [_vp, _u64, _vp, _vp, _vp, _u64, _vp, _vp, _i, _vp, _vp, _vp, _u64, C.POINTER(C.c_uint64)]),
     "hns_deactivate_leaf_masks": (_i, [_u64, _vp, C.POINTER(hns_activity_field), C.POINTER(C.c_void_p), _i, _vp, C.POINTER(C.c_uint64)]),
+    "hns_leaf_stats": (_i, [_u64, _vp, _vp, _i, _vp]),
     "hns_compute_sim": (_i, [_vp, C.POINTER(hns_field), _i, _i, _f, _f, C.POINTER(hns_combustion_params), _i, _vp]),
     "hns_compute_sim_resident": (_i, [_vp, C.POINTER(hns_field), _i, C.c_char_p, C.POINTER(C.c_int), _i, _f, _f, C.POINTER(hns_combustion_params), _i, _vp]),
     "hns_advect_index_grid": (_i, [_vp, C.POINTER(hns_field), _i, _f, _f, _vp]),
@@ -121,6 +139,10 @@ SIGNATURES = {
     "hns_sim_regrid_times": (_i, [_vp, C.POINTER(C.c_float)]),
     "hns_sim_regrid_sourced": (_vp, [_vp, _i, C.POINTER(hns_leaf_source), _i, _vp, _u64, _vp, _vp, _vp, _ip]),
     "hns_sim_deactivate": (_i, [_vp, C.POINTER(hns_activity_field), _i, C.POINTER(C.c_uint64), _vp]),
+    "hns_sim_stats": (_i, [_vp, C.POINTER(hns_stats_field), _i, _i, _vp, _vp]),
+    "hns_sim_residual": (_i, [_vp, _f, C.POINTER(hns_stats), _vp]),
+    "hns_sim_set_solve_control": (_i, [_vp, C.POINTER(hns_solve_control)]),
+    "hns_sim_solve_report": (_i, [_vp, C.POINTER(hns_solve_report), _vp, _i, _ip]),
     "hns_dev_advect_vector": (_i, [_vp, _fp, _fp, _fp, _i, _f, _f, _vp]),
     "hns_dev_advect_scalar": (_i, [_vp, _fp, _fp, _fp, _fp, _i, _f, _f, _vp]),
     "hns_dev_advect_scalars": (_i, [_vp, _fp, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _i, _fp, _i, _f, _f, _vp]),
@@ -135,6 +157,8 @@ SIGNATURES = {
     "hns_dev_enforce_collision_boundaries": (_i, [_vp, _fp, _fp, _f, _vp]),
     "hns_dev_pack_leaves": (_i, [_fp, _vp, _u64, _fp, _i, _vp]),
     "hns_dev_unpack_leaves": (_i, [_fp, _vp, _u64, _fp, _i, _vp]),
+    "hns_dev_field_stats": (_i, [_vp, _fp, _i, _vp, _vp, _vp]),
+    "hns_dev_residual": (_i, [_vp, _fp, _fp, _f, _fp, _vp, _vp]),
     "hns_dist_create": (_vp, [_vp, _u64, _i, _i, _f, _i, _i, C.c_uint, _ip]),
     "hns_dist_destroy": (None, [_vp]),
     "hns_dist_unique_id": (_i, [_vp]),

@@ -58,6 +58,7 @@ extern "C" void hns_sim_destroy(hns_sim* s) {
 		if (e) (void)hipEventDestroy(e);
 	if (s->xfer) (void)hipStreamDestroy(s->xfer);
 	if (s->h_dig) (void)hipHostFree(s->h_dig);
+	hns_sim_free_diagnostics(s);
 	hns_arena_put(s->d_masks, s->masks_bytes, s->device);
 	hns_arena_put(s->d_act, s->act_bytes, s->device);
 	hns_arena_put(s->arena, s->arena_bytes, s->device);
@@ -248,6 +249,7 @@ static int validate_step(float voxel_size, float dt, int64_t iterations, bool ne
 
 // the pressure hot loop: p = 0, `iterations` x (red, black); HNanoSolver.cu:256-272 / PressureProjection.cu:51-60
 static int sim_pressure(hns_sim* s, int iterations, float voxel_size, float omega, void* stream) {
+	if (s->control) return hns_sim_pressure_controlled(s, iterations, voxel_size, omega, stream);  // hns_sim_set_solve_control: `iterations` is the maximum
 	int in_b = 0;  // never warm-started (HNanoSolver.cu:113): the solve starts from p = 0, which the first sweep knows without reading p_a
 	hipEvent_t* timed = s->solve_ev.current();
 	if (timed) HNS_HIP(hipEventRecord(timed[0], (hipStream_t)stream));
@@ -258,6 +260,7 @@ static int sim_pressure(hns_sim* s, int iterations, float voxel_size, float omeg
 		s->timed_launches += iterations;
 	}
 	s->p_result = in_b ? s->p_b : s->p_a;
+	s->solved = true;
 	return HNS_OK;
 }
 
@@ -269,6 +272,7 @@ static float omega_project(float vs) { return (float)(2.0f / (1.0f + sin(3.14159
 extern "C" int hns_sim_pressure_solve(hns_sim* s, int iterations, float voxel_size, void* stream) {
 	if (!s) return fail(HNS_ERR_INVALID_ARGUMENT, "hns_sim_pressure_solve: null sim");
 	HNS_TRY(validate_step(voxel_size, 0.0f, iterations, true));
+	if (s->control) HNS_TRY(hns_refuse_capture(stream, "hns_sim_pressure_solve"));
 	return sim_pressure(s, iterations, voxel_size, omega_compute(voxel_size), stream);
 }
 
@@ -493,6 +497,7 @@ struct Substep {
 int sim_substep(hns_sim* s, int iterations, float dt, float voxel_size, const hns_combustion_params* params, int has_collision, void* stream) {
 	HNS_TRY(validate_step(voxel_size, dt, iterations, true));
 	if (s->n == 0) return HNS_OK;  // HNanoSolver.cu:26-28
+	if (s->control) HNS_TRY(hns_refuse_capture(stream, params ? "hns_sim_substep" : "hns_sim_core_substep"));  // (before anything is launched)
 	Substep step;
 	HNS_TRY(step.prepare(s, iterations, dt, voxel_size, params, has_collision, stream));
 	return step.run();

@@ -127,6 +127,16 @@ __device__ __forceinline__ v4i field_rsrc(const float* p, unsigned bytes) {
 	return r;
 }
 
+// One wave over one leaf of a field, voxel 64k + lane in round k (hns_regrid.hip: k_deactivate; hns_diagnostics.hip: k_field_stats). The descriptor covers the leaf alone
+// (as in hns_advect.hip): a round to skip gets an offset past the descriptor's end, for which the hardware returns 0 without touching memory. So the eight rounds'
+// loads are issued back to back with no branch (a branch per round makes the compiler wait for each load before the next). A leaf's 64 mask bytes are eight 64-bit
+// words, word k = voxels 64k .. 64k + 63, loaded by lanes 0..7 and handed to the wave through readlane.
+constexpr int kActSkip = 0x40000000;  // a byte offset past any leaf
+
+__device__ __forceinline__ uint64_t readlane64(uint64_t v, int lane) {
+	const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, lane), hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), lane);
+	return (uint64_t)hi << 32 | lo;
+}
 
 // ---- launch order ------------------------------------------------------------------------------------------------
 // Block -> leaf order. The dispatcher places workgroup b on XCD b % 8 (observed, not contractual), each XCD has a
@@ -190,6 +200,33 @@ __device__ __forceinline__ int tile_nbr(int n) {  // tile entry of the face neig
 	const int x = n >> 6, y = (n >> 3) & 7, z = n & 7;
 	const int ab = AXIS == 0 ? ((y << 3) | z) : (AXIS == 1 ? ((x << 3) | z) : ((x << 3) | y));
 	return inside ? n + DIR * (1 << shift) : 512 + 64 * f + ab;
+}
+
+// The Gauss-Seidel value of a voxel in the reference's association (Kernel.cu:621): what the sweep relaxes p towards (hns_pressure.hip: sor_update) and
+// what the residual measures p against (hns_diagnostics.hip: k_residual).
+__device__ __forceinline__ float gs_value(float pxp, float pxm, float pyp, float pym, float pzp, float pzm, float divVal, float dx2) {
+	constexpr float inv6 = 0.166666667f;
+	return ((pxp + pxm + pyp + pym + pzp + pzm) - divVal * dx2) * inv6;
+}
+
+// One wave stages a whole tile of float field p for the leaf of launch record `rec` ({leaf, nbr27[27]}: GridDev::blk): its own values as two 16-byte
+// loads per lane, each face layer as one value per lane, 0 where the neighbour leaf is absent. The caller synchronises before it reads P.
+// (k_subtract_gradient_s and k_residual)
+__device__ __forceinline__ void stage_tile_wave(float* P, const float* __restrict__ p, const int* __restrict__ rec, int leaf, int l) {
+	{
+		const float4* q = reinterpret_cast<const float4*>(p + (size_t)leaf * 512 + l * 8);
+		const float4 a = q[0], b = q[1];
+		*reinterpret_cast<float4*>(&P[l * 8]) = a;
+		*reinterpret_cast<float4*>(&P[l * 8 + 4]) = b;
+	}
+#pragma unroll
+	for (int f = 0; f < 6; ++f) {  // face f: -x,+x,-y,+y,-z,+z; its 64 entries are one per lane
+		int slot, local;
+		halo_entry(f * 64 + l, slot, local);
+		const int nb = __builtin_amdgcn_readfirstlane(rec[1 + slot]);
+		const float v = p[(size_t)(nb < 0 ? 0 : nb) * 512 + local];
+		P[512 + f * 64 + l] = nb < 0 ? 0.0f : v;
+	}
 }
 
 // Stage the workgroup's leaf id, origin and 27-neighbour table. Returns false for an out-of-range block.

@@ -174,6 +174,9 @@ void hns_grid_free_device(hns_grid* g) {
 	g->sb_bytes = 0;
 	g->n_sb = 0;
 	g->sb_built = false;
+	if (g->d_diag) hns_arena_put(g->d_diag, g->diag_bytes, g->device);
+	g->d_diag = nullptr;
+	g->diag_bytes = 0;
 	hns_arena_put(g->d_arena, g->arena_bytes, g->device);
 	g->d_arena = nullptr;
 	g->arena_bytes = 0;

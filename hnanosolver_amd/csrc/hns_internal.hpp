@@ -214,6 +214,9 @@ struct hns_grid {
 	int sb_seg = 0;
 	uint64_t sb_first = 0, sb_count = 0;                  // the launch range the records were built for
 	std::vector<std::pair<void*, size_t>> sb_retired;     // superseded tables: back to the pool when the grid goes, or -- beyond four of them -- behind a device synchronise
+	// hns_dev_field_stats / hns_dev_residual (hns_diagnostics.hip): the table of per-leaf partial records, an arena allocation of its own made on first use
+	void* d_diag = nullptr;
+	size_t diag_bytes = 0;
 	std::mutex build_mutex;              // guards the tables built on first use (block records): cooks from several host threads may share a grid
 	std::mutex host_mutex;               // guards the lazy host copy of the device-built tables and sim_cache
 	std::vector<hns_sim*> sim_cache;     // device-resident state kept between operator calls (hns_api.hip: make_sim)
@@ -281,6 +284,20 @@ struct hns_sim {
 	// hns_sim_deactivate's device table (its counts, then one row per listed field), made on first use from the arena pool, written by a kernel
 	void* d_act = nullptr;
 	size_t act_bytes = 0;
+	// Diagnostics (hns_diagnostics.hip). d_diag: the records a call leaves, then the table of per-leaf partial records -- an arena allocation of its own, made on first
+	// use; h_diag: pinned host memory the records are read into. solved: p_result holds a solve on the current grid (hns_sim_residual).
+	void* d_diag = nullptr;
+	size_t diag_bytes = 0;
+	hns_stats* h_diag = nullptr;
+	bool solved = false;
+	// hns_sim_set_solve_control: null = off, and then sim_pressure (hns_api.hip) is the uncontrolled loop after one pointer test
+	struct Control {
+		hns_solve_control c;
+		hns_solve_report report;
+		std::vector<hns_stats> history;
+		bool ran = false;
+	};
+	Control* control = nullptr;
 	int device = -1;
 	int find(const char* name) const {
 		for (size_t i = 0; i < names.size(); ++i)
@@ -292,6 +309,11 @@ struct hns_sim {
 // A field list of hns_sim_deactivate (s: its sim) or hns_deactivate_leaf_masks (s null), checked (hns_leafio.cpp): HNS_OK, or HNS_ERR_INVALID_ARGUMENT
 // with the message under `who`. field_of (or null) receives each entry's float field index in s, -1 for the velocity.
 namespace hns { int check_activity_fields(const hns_sim* s, const hns_activity_field* fields, int n_fields, const char* who, std::vector<int>* field_of); }
+
+// hns_diagnostics.hip: the controlled pressure loop of a sim with a control set (hns_api.hip: sim_pressure), and the refusal of a capturing stream in front of it
+int hns_sim_pressure_controlled(hns_sim* s, int max_iterations, float voxel_size, float omega, void* stream);
+int hns_refuse_capture(void* stream, const char* who);
+void hns_sim_free_diagnostics(hns_sim* s);  // (hns_sim_destroy)
 
 // the sim's buffers over one arena (hns_api.hip): bytes an arena needs for n voxels, and the slices of `arena` for them (sets n, every buffer pointer, d_dig, p_result)
 size_t hns_sim_arena_need(const hns_sim* s, uint64_t n);

@@ -17,6 +17,7 @@
 
 #include "hns_dilate.hpp"
 #include "hns_internal.hpp"
+#include "hns_stats.hpp"
 
 using namespace hns;
 
@@ -366,6 +367,45 @@ int hns_deactivate_leaf_masks(uint64_t n_leaves, const unsigned char* masks_in, 
 		leaves += in_leaf != 0;
 	}
 	if (counts) counts[0] = voxels, counts[1] = leaves;
+	return HNS_OK;
+}
+
+// hns_sim_stats / hns_dev_field_stats / the record of hns_dev_residual on the host, voxel by voxel, through the trees of hns_stats.hpp: what the device's records are
+// checked against, byte for byte.
+int hns_leaf_stats(uint64_t n_leaves, const unsigned char* masks, const float* values, int ncomp, hns_stats* out) {
+	if ((ncomp != 1 && ncomp != 3) || !out || (n_leaves && !values)) return fail(HNS_ERR_INVALID_ARGUMENT, "hns_leaf_stats: bad arguments");
+	std::vector<hns_stats> row((size_t)std::max<uint64_t>(n_leaves, 1));
+	for (int c = 0; c < ncomp; ++c) {
+		for (uint64_t l = 0; l < n_leaves; ++l) {
+			hns_stats lane[64];
+			for (int L = 0; L < 64; ++L) {  // lane L: voxels 64k + L, k ascending
+				hns_stats& a = lane[L];
+				a = stats_empty();
+				for (int k = 0; k < 8; ++k) {
+					const int v = 64 * k + L;
+					const bool on = !masks || (masks[64 * l + (uint64_t)(v >> 3)] >> (v & 7) & 1);
+					const float x = values[(512 * l + (uint64_t)v) * (uint64_t)ncomp + (uint64_t)c];
+					const bool use = on && !(x != x);
+					hns_stats t = stats_empty();  // the voxel's term
+					t.count = on, t.nan_count = on && x != x;
+					if (use) t.min = t.max = x, t.max_abs = std::fabs(x), t.sum = (double)x, t.sum_sq = (double)x * (double)x;
+					if (k == 0)
+						a = t;
+					else
+						stats_combine(a, t);
+				}
+			}
+			for (int m = 1; m < 64; m *= 2)  // the butterfly, as the tree it is
+				for (int L = 0; L < 64; L += 2 * m) stats_combine(lane[L], lane[L + m]);
+			row[(size_t)l] = lane[0];
+		}
+		if (n_leaves)
+			stats_fold(row.data(), n_leaves);
+		else
+			row[0] = stats_empty();
+		stats_finish(row[0]);
+		out[c] = row[0];
+	}
 	return HNS_OK;
 }
 

@@ -50,9 +50,8 @@ __global__ __launch_bounds__(512) void k_divergence(const GridDev g, const float
 
 __device__ __forceinline__ float sor_update(float pxp, float pxm, float pyp, float pym, float pzp, float pzm, float divVal, float pOld,
                                             float dx2, float omega) {
-	constexpr float inv6 = 0.166666667f;
-	const float pGS = ((pxp + pxm + pyp + pym + pzp + pzm) - divVal * dx2) * inv6;  // Kernel.cu:621
-	return pOld + omega * (pGS - pOld);                                              // Kernel.cu:622
+	const float pGS = gs_value(pxp, pxm, pyp, pym, pzp, pzm, divVal, dx2);  // Kernel.cu:621
+	return pOld + omega * (pGS - pOld);                                      // Kernel.cu:622
 }
 
 __global__ __launch_bounds__(256) void k_rbgs_color(const GridDev g, const float* __restrict__ div, float* p, const float dx2, const float omega,
@@ -114,20 +113,7 @@ __global__ __launch_bounds__(64) void k_subtract_gradient_s(const GridDev g, con
 	const int* __restrict__ rec = g.blk + (size_t)launch_pos(g, blockIdx.x) * 28;
 	const int leaf = __builtin_amdgcn_readfirstlane(rec[0]);
 	chain_begin(m, leaf);
-	{
-		const float4* q = reinterpret_cast<const float4*>(p + (size_t)leaf * 512 + l * 8);
-		const float4 a = q[0], b = q[1];
-		*reinterpret_cast<float4*>(&P[l * 8]) = a;
-		*reinterpret_cast<float4*>(&P[l * 8 + 4]) = b;
-	}
-#pragma unroll
-	for (int f = 0; f < 6; ++f) {  // face f: -x,+x,-y,+y,-z,+z; its 64 entries are one per lane
-		int slot, local;
-		halo_entry(f * 64 + l, slot, local);
-		const int nb = __builtin_amdgcn_readfirstlane(rec[1 + slot]);
-		const float v = p[(size_t)(nb < 0 ? 0 : nb) * 512 + local];
-		P[512 + f * 64 + l] = nb < 0 ? 0.0f : v;
-	}
+	stage_tile_wave(P, p, rec, leaf, l);
 	__syncthreads();
 	const float4* src = reinterpret_cast<const float4*>(u + (size_t)leaf * 1536);
 	float4* dst = reinterpret_cast<float4*>(out + (size_t)leaf * 1536);

@@ -652,6 +652,7 @@ struct Regrid {
 		s->d_masks = (unsigned char*)new_masks, s->masks_bytes = scratch.keep(new_masks);
 		s->grid = ng.release();
 		s->forget();
+		s->solved = false;  // (the divergence / pressure scratch holds no defined values: hns_sim_residual refuses until the next solve)
 		s->regrid_timed = true;
 		*out = s->grid;
 		return HNS_OK;
@@ -699,15 +700,7 @@ __global__ __launch_bounds__(64) void k_deactivate_table(ActRows rows, int n, Ac
 	if (count && threadIdx.x == 0) *count = 0;
 }
 
-// Raw buffer loads over one leaf of a field (as in hns_advect.hip): a round to skip gets an offset past the descriptor's end, for which the hardware
-// returns 0 without touching memory. So the eight rounds' loads are issued back to back with no branch (a branch per round makes the compiler wait
-// for each load before the next).
-constexpr int kActSkip = 0x40000000;  // a byte offset past any leaf
-
-__device__ __forceinline__ uint64_t readlane64(uint64_t v, int lane) {
-	const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, lane), hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), lane);
-	return (uint64_t)hi << 32 | lo;
-}
+// Raw buffer loads over one leaf of a field, a round to skip at kActSkip, and the mask words through readlane64: hns_device.hpp ("one wave over one leaf").
 
 // masks_in null: every voxel active (it may equal masks_out). count: += active voxels | (leaves holding one) << 40, one atomic per such wave.
 __global__ __launch_bounds__(256) void k_deactivate(const ActField* __restrict__ tab, int n_tab, const uint64_t* masks_in, uint64_t* masks_out, uint64_t n_leaves,

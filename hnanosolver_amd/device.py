@@ -132,6 +132,50 @@ def unpack_leaves(packed, leaf_ids, field, ncomp: int = 1):
     return field
 
 
+def _byte_ptr(t) -> int:
+    if t is None:
+        return 0
+    if not t.is_cuda or t.dtype != _torch().uint8 or not t.is_contiguous():
+        raise TypeError("expected a contiguous uint8 tensor on a HIP device")
+    return t.data_ptr()
+
+
+def stats_buffer(n_records: int = 1):
+    """Device memory for `n_records` hns_stats records (a uint8 tensor; ``read_stats`` brings it to the host)."""
+    return _torch().zeros(n_records * leafio.STATS_DTYPE.itemsize, dtype=_torch().uint8, device="cuda")
+
+
+def read_stats(buf) -> np.ndarray:
+    """The records of a ``stats_buffer`` on the host (waits for the current stream): an array of leafio.STATS_DTYPE"""
+    return buf.cpu().numpy().view(leafio.STATS_DTYPE).copy()
+
+
+def field_stats(grid: IndexGridHandle, values, masks=None, out=None):
+    """Statistics of a field in device memory over all leaves of `grid` (``hns_dev_field_stats``): values (N,) or (N, 3) float32, masks a uint8 tensor of
+    leaf_count x 64 bytes or None = every voxel. One record per component into `out` (``stats_buffer``), asynchronous on the current stream."""
+    ncomp = 3 if (values.dim() == 2 and values.shape[1] == 3) else 1
+    out = stats_buffer(ncomp) if out is None else out
+    _raise(lib.hns_dev_field_stats(grid.ptr, _ptr(values), ncomp, _byte_ptr(masks), _byte_ptr(out), current_stream()))
+    return out
+
+
+def residual(grid: IndexGridHandle, div, p, dx: float, c_out=None, out=None):
+    """The Gauss-Seidel correction c of pressure `p` against `div` over the grid's launch range (``hns_dev_residual``): its record into `out`
+    (``stats_buffer``), the field itself into c_out when given. Asynchronous on the current stream. ``residual_in_divergence_units`` rescales."""
+    out = stats_buffer(1) if out is None else out
+    _raise(lib.hns_dev_residual(grid.ptr, _ptr(div), _ptr(p), dx, _ptr(c_out), _byte_ptr(out), current_stream()))
+    return out
+
+
+def residual_in_divergence_units(c, dx: float):
+    """-6 c / dx^2: a correction (a value, or the min / max / max_abs of a record) as a residual of the discrete Poisson equation, in the divergence's units"""
+    return -6.0 * c / (dx * dx)
+
+
+def _record(r) -> np.ndarray:
+    return np.frombuffer(bytes(r), dtype=leafio.STATS_DTYPE).copy()
+
+
 def _leaf_source(entry, leaves, need, keep, ncomp: Optional[int] = None) -> None:
     """Fills the hns_leaf_source `entry` (all but its name) from (origins, masks or None, values) of the collision SDF or a regrid source: the
     arrays contiguous, their sizes checked against the origins, kept alive in `keep`. ncomp None: 3 for values of shape (n * 512, 3), else 1.
@@ -271,6 +315,43 @@ class Sim:
         out = (C.c_uint64 * 2)()
         _raise(lib.hns_sim_deactivate(self._ptr, arr, n, out if counts else None, stream))
         return (int(out[0]), int(out[1])) if counts else None
+
+    def stats(self, names: Sequence[str], velocity: bool = False, masks: bool = True, stream: int = 0) -> np.ndarray:
+        """Statistics of float fields `names` and, with velocity, of the velocity's three components behind them (``hns_sim_stats``): one record
+        (leafio.STATS_DTYPE) per component, over the active voxels (masks) or all of them. Synchronous; equal in every byte to ``leafio.leaf_stats`` of the
+        downloaded fields. dt * max(max_abs of the velocity's records) / dx is the longest back-trace in voxels."""
+        entries = [(n.encode(), 1) for n in names] + ([(None, 3)] if velocity else [])
+        arr = (_lib.hns_stats_field * max(1, len(entries)))()
+        for i, (name, nc) in enumerate(entries):
+            arr[i].name, arr[i].ncomp = name, nc
+        out = np.zeros(sum(nc for _, nc in entries), dtype=leafio.STATS_DTYPE)
+        _raise(lib.hns_sim_stats(self._ptr, arr, len(entries), int(masks), out.ctypes.data, stream))
+        return out
+
+    def residual(self, voxel_size: float, stream: int = 0) -> np.ndarray:
+        """The record of the Gauss-Seidel correction of the last pressure solve (``hns_sim_residual``); ``residual_in_divergence_units`` rescales it."""
+        r = _lib.hns_stats()
+        _raise(lib.hns_sim_residual(self._ptr, voxel_size, C.byref(r), stream))
+        return _record(r)
+
+    def solve_control(self, rel_tol: Optional[float] = 0.0, abs_tol: float = 0.0, check_every: int = 10) -> None:
+        """A stop rule for the pressure solve of pressure_solve / substep / core_substep (``hns_sim_set_solve_control``): their `iterations` becomes the
+        maximum and the loop ends at the first check, taken every check_every iterations, where the residual's max_abs <= max(abs_tol, rel_tol * the one
+        at p = 0). Both tolerances 0: monitor only. rel_tol None switches the control off."""
+        if rel_tol is None:
+            _raise(lib.hns_sim_set_solve_control(self._ptr, None))
+            return
+        c = _lib.hns_solve_control(float(rel_tol), float(abs_tol), int(check_every))
+        _raise(lib.hns_sim_set_solve_control(self._ptr, C.byref(c)))
+
+    def solve_report(self) -> dict:
+        """What the last controlled solve did (``hns_sim_solve_report``): iterations, checks, converged, initial, final and the history of the checks"""
+        r, n = _lib.hns_solve_report(), C.c_int(0)
+        _raise(lib.hns_sim_solve_report(self._ptr, C.byref(r), None, 0, C.byref(n)))
+        hist = np.zeros(n.value, dtype=leafio.STATS_DTYPE)
+        _raise(lib.hns_sim_solve_report(self._ptr, C.byref(r), hist.ctypes.data, n.value, C.byref(n)))
+        return {"iterations": r.iterations, "checks": r.checks, "converged": bool(r.converged), "initial": _record(r.initial)[0], "final": _record(r.final)[0],
+                "history": hist}
 
     def regrid_times(self):
         """hipEvent split of the last regrid in ms: {candidates, host (origins, sort, grid tables), masks, fields}"""

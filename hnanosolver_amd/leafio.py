@@ -124,6 +124,27 @@ def deactivate_masks(masks, fields: dict, velocity=None):
     return out, (int(counts[0]), int(counts[1]))
 
 
+# one hns_stats record (include/hns.h), 48 bytes; records compare byte for byte through .tobytes()
+STATS_DTYPE = np.dtype([("count", "<u8"), ("nan_count", "<u8"), ("min", "<f4"), ("max", "<f4"), ("max_abs", "<f4"), ("reserved", "<u4"), ("sum", "<f8"), ("sum_sq", "<f8")])
+assert STATS_DTYPE.itemsize == C.sizeof(_lib.hns_stats) == 48
+
+
+def leaf_stats(values, masks: Optional[np.ndarray] = None, ncomp: Optional[int] = None) -> np.ndarray:
+    """The host mirror of ``Sim.stats`` and of the residual's record (``hns_leaf_stats``): values = 512 floats per leaf, or shape (n * 512, 3) (or ncomp
+    = 3) for a Vec3f field; masks (n x 64 uint8) or None = every voxel -> ncomp records (STATS_DTYPE), summed in the fixed order include/hns.h states."""
+    v = np.ascontiguousarray(values, dtype=np.float32)
+    nc = ncomp or (3 if (v.ndim == 2 and v.shape[1] == 3) else 1)
+    if v.size % (512 * nc):
+        raise ValueError(f"leaf_stats: need whole leaves of 512 x {nc} floats, got {v.size}")
+    n = v.size // (512 * nc)
+    m = None if masks is None else np.ascontiguousarray(masks, dtype=np.uint8).reshape(-1)
+    if m is not None and m.size != n * 64:
+        raise ValueError(f"leaf_stats: masks need {n} x 64 bytes, got {m.size}")
+    out = np.zeros(nc, dtype=STATS_DTYPE)
+    _lib.check(lib.hns_leaf_stats(n, None if m is None else m.ctypes.data, v.ctypes.data if n else None, nc, out.ctypes.data))
+    return out
+
+
 def union_leaves(a, b) -> np.ndarray:
     a, b = _o(a), _o(b)
     n = C.c_uint64(0)

@@ -370,6 +370,75 @@ hns_grid* hns_sim_regrid_sourced(hns_sim*, int padding_voxels, const hns_leaf_so
 int hns_sim_deactivate(hns_sim*, const hns_activity_field* fields, int n_fields, uint64_t* counts, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------ */
+/* Diagnostics of a device-resident sim: field statistics, the pressure residual, a residual stop rule           */
+/* (new: the reference computes no norm of anything). Nothing here writes a field value.                         */
+/* ------------------------------------------------------------------------------------------------------------ */
+
+/* One record per component of a field. NaN voxels are counted and take part in nothing else; +-inf are values like any other.
+ * THE REDUCTION. sum and sum_sq are f64 sums of x and x*x (exact in f64 for an f32 x: only the additions round) in ONE fixed order, which is part
+ * of the interface -- the device and the host mirror hns_leaf_stats give the same bytes, and so do two calls, whatever the launch geometry:
+ *   inside a leaf  lane L (0..63) adds the terms of voxels 64k + L (voxel = x<<6|y<<3|z) for k = 0..7 ascending, ((t0 + t1) + t2) + ...; then the 64
+ *                  lane sums go through the balanced tree over lane index (an xor butterfly over lanes 1, 2, 4, 8, 16, 32);
+ *   over leaves    a balanced tree over leaf index padded with +0.0 up to the next power of two: at level s = 1, 2, 4, ... entry i + s is added
+ *                  to entry i for every i that is a multiple of 2s (+0.0 where i + s is past the last leaf).
+ * The term of an inactive voxel and of a NaN is +0.0. A sum that comes out NaN (+inf and -inf both present) is stored as 0x7FF8000000000000.
+ * No float or double atomics anywhere: the order does not depend on how the kernels were scheduled. */
+typedef struct {
+	uint64_t count;      /* voxels looked at (the active ones, or all) */
+	uint64_t nan_count;  /* of them NaN */
+	float min, max;      /* over the rest, ordered -0 < +0; none left: +inf, -inf */
+	float max_abs;       /* none left: +0 */
+	uint32_t reserved;   /* 0 */
+	double sum, sum_sq;  /* over the rest */
+} hns_stats;
+/* Host mirror, brute force and OpenVDB-free: n_leaves leaves of 512 x ncomp floats (Vec3f AoS for ncomp 3), masks n_leaves x 64 bytes (byte x*8+y,
+ * bit z) or NULL = every voxel; out receives ncomp records. n_leaves 0 gives the record of nothing (count 0, min +inf, max -inf, sums +0).
+ * HNS_ERR_INVALID_ARGUMENT, out untouched: ncomp other than 1 or 3, out NULL, values NULL with n_leaves > 0. */
+int hns_leaf_stats(uint64_t n_leaves, const unsigned char* masks, const float* values, int ncomp, hns_stats* out);
+/* One field of hns_sim_stats, addressed as in hns_activity_field. */
+typedef struct {
+	const char* name; /* a float field of the sim; with ncomp 3: the velocity (any name that is not a float field's) */
+	int ncomp;        /* 1 or 3 */
+} hns_stats_field;
+/* Statistics of the listed fields of a sim as the device holds them now, one record per component in list order (the velocity gives three, so a
+ * caller forms the back-trace length dt * max(max_abs) / dx itself). use_masks != 0: over the voxels of the sim's active masks (NULL masks = every
+ * voxel); 0: over every voxel. Synchronous. Equal in every byte to hns_leaf_stats of the downloaded fields (and masks). One wave per leaf reads the
+ * fields; its partial records go into a table from the arena pool (made on first use, kept with the sim) that a second small launch folds.
+ * Field values, masks, the feedback signatures of hns_compute_sim_resident and the look-ahead memo are untouched.
+ * Refused with out untouched (HNS_ERR_INVALID_ARGUMENT): n_fields < 1 or a NULL list, a name the sim lacks, two entries for one field or two
+ * velocity entries, ncomp other than 1 or 3 or ncomp 3 under a float field's name, a sim lent to a grid's cook cache. */
+int hns_sim_stats(hns_sim*, const hns_stats_field* names, int n_fields, int use_masks, hns_stats* out, void* stream);
+/* The Gauss-Seidel correction of the last pressure solve on this sim, per voxel (see hns_dev_residual), as one record over the leaves of the grid's
+ * launch range. voxel_size: the one the solve ran with. Synchronous. HNS_ERR_RUNTIME when no solve has run on this sim's grid since the sim was
+ * created or regridded (the pressure buffer holds no defined values then); HNS_ERR_INVALID_ARGUMENT for a sim lent to a grid's cook cache. */
+int hns_sim_residual(hns_sim*, float voxel_size, hns_stats* out, void* stream);
+/* A stop rule for the pressure solve of hns_sim_pressure_solve, hns_sim_substep and hns_sim_core_substep: with a control set, their `iterations` is
+ * the MAXIMUM. The residual (hns_dev_residual's record) is taken at p = 0 (`initial`), after every check_every iterations and at the maximum; the
+ * loop ends at the FIRST check where nan_count == 0 and max_abs <= max(abs_tol, rel_tol * initial.max_abs) -- the first crossing, not the last: the
+ * norm does not fall monotonically. A solve that carries NaN runs to the maximum and reports converged = 0. rel_tol = abs_tol = 0 only monitors:
+ * the loop never stops early and converged stays 0. Whatever number of iterations ran, pressure and every field equal, bit for bit, the
+ * uncontrolled call with that number.
+ * check_every >= 1; even values fit the kernels, which do two (small grids: four) iterations per launch -- an odd value costs an extra launch per
+ * check. The host waits once per check for a few bytes in pinned memory, so a controlled call is refused on a capturing stream
+ * (HNS_ERR_INVALID_ARGUMENT, nothing launched). hns_sim_timing counts the iterations that ran; the residual launches fall inside its brackets.
+ * NULL switches the control off (the default): bit for bit and launch for launch the calls above without one. The drop-in operators and the sims
+ * of a grid's cook cache never use a control; hns_dist_* has none (its residual would need an all-reduce over the ranks).
+ * HNS_ERR_INVALID_ARGUMENT: a negative or NaN tolerance, check_every < 1, a sim lent to a grid's cook cache. */
+typedef struct {
+	float rel_tol, abs_tol;
+	int check_every;
+} hns_solve_control;
+int hns_sim_set_solve_control(hns_sim*, const hns_solve_control*);
+/* What the last controlled solve of this sim did: iterations run, checks taken (the one at p = 0 not counted), converged, the residual at p = 0 and
+ * at the end; history (or NULL) receives the first min(checks, capacity) records of the checks in order, *n_history (or NULL) = checks.
+ * HNS_ERR_RUNTIME when no controlled solve has run on this sim. */
+typedef struct {
+	int iterations, checks, converged;
+	hns_stats initial, final;
+} hns_solve_report;
+int hns_sim_solve_report(hns_sim*, hns_solve_report*, hns_stats* history, int capacity, int* n_history);
+
+/* ------------------------------------------------------------------------------------------------------------ */
 /* Kernel-level entry points on caller-owned DEVICE memory (asynchronous on `stream`).                           */
 /* Velocity fields are Vec3f AoS on the device too (3 floats per voxel, `vel3`), exactly the host/reference layout.  */
 /* ------------------------------------------------------------------------------------------------------------ */
@@ -426,6 +495,19 @@ int hns_dev_enforce_collision_boundaries(hns_grid*, float* vel3, const float* sd
  * 3 = Vec3f field) between a field and a packed buffer. leaf_ids is a DEVICE array of n leaf indices. */
 int hns_dev_pack_leaves(const float* field, const int32_t* leaf_ids, uint64_t n, float* packed, int ncomp, void* stream);
 int hns_dev_unpack_leaves(const float* packed, const int32_t* leaf_ids, uint64_t n, float* field, int ncomp, void* stream);
+/* hns_sim_stats on caller-owned device memory: ncomp records over ALL leaves of the grid (values: leaf_count x 512 x ncomp floats; masks: leaf_count
+ * x 64 bytes in device memory, or NULL = every voxel) into d_out, DEVICE memory. The table of per-leaf partial records is kept with the grid (arena
+ * pool, made on first use) and shared with hns_dev_residual: calls on one grid must follow each other on one stream. */
+int hns_dev_field_stats(hns_grid*, const float* values, int ncomp, const unsigned char* masks, hns_stats* d_out, void* stream);
+/* The residual of the pressure solve as the quantity the reference's sweep itself defines: the Gauss-Seidel correction, in the reference's
+ * association (Kernel.cu:621),
+ *   c = ((pxp + pxm + pyp + pym + pzp + pzm) - div * dx*dx) * 0.166666667f - p
+ * all in f32, absent neighbours read as 0 -- omega * c is what the next sweep would add to p. Taken over the leaves of the grid's launch range, all
+ * 512 voxels each (the solve ignores active masks, so this does too). In divergence units the residual is -6 c / dx^2. d_out (DEVICE memory)
+ * receives ONE record: exactly hns_leaf_stats of the field c over those leaves, same tree. c_out (or NULL; leaf_count x 512 floats) receives c on
+ * the leaves of the range, so that tests can see the field. One wave per leaf: p and its six face layers staged in LDS as in the gradient
+ * subtraction, the divergence streamed in 16-byte pieces -- 8 B/voxel. The partial table is the grid's (hns_dev_field_stats). */
+int hns_dev_residual(hns_grid*, const float* div, const float* p, float dx, float* c_out, hns_stats* d_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------ */
 /* Leaf-partitioned multi-GPU core substep (new: the reference is single-GPU). One hns_dist per rank = per GPU.      */
