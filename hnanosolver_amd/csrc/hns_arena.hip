@@ -22,7 +22,20 @@ std::mutex g_pool_mutex;
 std::vector<Arena> g_pool;  // at most kPoolMax idle arenas
 constexpr size_t kPoolMax = 6;  // simulation states (GBs) and grid tables (MBs) share it; the smallest goes first
 
+// Option "arena_fill" (tests): the whole block, headroom included, holds the chosen byte when its new owner gets it. The wait is arena_put's promise
+// again: the owner may use the block on any stream. Called outside g_pool_mutex. A block that cannot be filled goes back to the driver: the caller gets none.
+int arena_fill(Arena& a, int fill) {
+	DeviceScope scope(a.device);
+	if (hipMemset(a.p, fill, a.bytes) == hipSuccess && hipDeviceSynchronize() == hipSuccess) return HNS_OK;
+	(void)hipGetLastError();
+	(void)hipFree(a.p);
+	a = Arena{nullptr, 0, -1};
+	return fail(HNS_ERR_HIP, "arena_fill: filling a pooled block failed");
+}
+
 int arena_get(size_t need, int device, Arena& out) {
+	const int fill = options().arena_fill.load(std::memory_order_relaxed);
+	bool pooled = false;
 	{
 		std::lock_guard<std::mutex> lock(g_pool_mutex);
 		int best = -1;
@@ -33,9 +46,10 @@ int arena_get(size_t need, int device, Arena& out) {
 		if (best >= 0) {
 			out = g_pool[(size_t)best];
 			g_pool.erase(g_pool.begin() + best);
-			return HNS_OK;
+			pooled = true;
 		}
 	}
+	if (pooled) return fill < 0 ? (int)HNS_OK : arena_fill(out, fill);
 	out.bytes = need + need / 8;  // headroom: the next, slightly larger topology still fits
 	out.device = device;
 	DeviceScope scope(device);
@@ -50,7 +64,7 @@ int arena_get(size_t need, int device, Arena& out) {
 		out.bytes = need;
 		HNS_HIP(hipMalloc(&out.p, out.bytes));
 	}
-	return HNS_OK;
+	return fill < 0 ? (int)HNS_OK : arena_fill(out, fill);
 }
 
 // The hipFree this pool replaces waits for the device; so does this: whoever draws the memory next may use it on any

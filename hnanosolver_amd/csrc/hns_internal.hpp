@@ -113,6 +113,7 @@ struct Options {
 	std::atomic<int> sor_block_lb{0};          // "sor_block_lb": block edge of the temporally blocked SOR in leaves, 0 = by size | 1 | 2 (the tests' way to every kernel on every grid)
 	std::atomic<int> dist_wire_us{0};          // "dist_wire_us": loopback transport only, emulated time on the wire per exchange
 	std::atomic<int> dist_mirror{1};           // "dist_mirror": 1 | 0 | guarded -- over the ipc / local transports a rank of 16^3 blocks with sweeps_per_exchange = 2 runs the CHAINED substep (every kernel delivers its own halo); 0 = the exchanged substep (what RCCL ranks run)
+	std::atomic<int> arena_fill{-1};           // "arena_fill": off | 0 .. 255 -- a TEST switch: every block the pool (hns_arena.hip) hands out is filled with that byte first, so that a result which depends on what pooled memory held shows up; a device-wide wait per block, never on while a stream captures
 	std::atomic<int> dist_unsplit{1};          // "dist_unsplit": small ranks of the exchanged substep run their short phases as ONE launch over the owned leaves with the exchange behind it on the compute stream; 0 = boundary / interior split on two streams at every size
 };
 Options& options();

@@ -131,6 +131,8 @@ struct OptionDesc {
 	const char* name;
 	std::atomic<int> Options::*field;
 	const char* const* words;  // value words, index = stored value; nullptr: a non-negative integer
+	int max = 1 << 20;         // the largest integer taken
+	const char* off = nullptr;  // an integer option's word for the stored value -1
 };
 const char* const kWordsRbgs[] = {"auto", "color", nullptr};
 const char* const kWordsAdvect[] = {"auto", "generic", nullptr};
@@ -155,6 +157,7 @@ const OptionDesc kOptions[] = {
     {"dist_wire_us", &Options::dist_wire_us, nullptr},
     {"dist_mirror", &Options::dist_mirror, kWordsMirror},
     {"dist_unsplit", &Options::dist_unsplit, kWordsUnsplit},
+    {"arena_fill", &Options::arena_fill, nullptr, 255, "off"},
 };
 const Options kDefaults;
 }  // namespace
@@ -168,9 +171,13 @@ int hns_set_option(const char* name, const char* value) {
 			return HNS_OK;
 		}
 		if (!d.words) {
+			if (d.off && strcmp(d.off, value) == 0) {
+				(options().*d.field).store(-1);
+				return HNS_OK;
+			}
 			char* end = nullptr;
 			const long v = strtol(value, &end, 10);
-			if (end == value || *end || v < 0 || v > 1 << 20) break;
+			if (end == value || *end || v < 0 || v > d.max) break;
 			(options().*d.field).store((int)v);
 			return HNS_OK;
 		}
@@ -192,6 +199,7 @@ const char* hns_get_option(const char* name) {
 		if (strcmp(d.name, name) != 0) continue;
 		const int v = (options().*d.field).load();
 		if (d.words) return d.words[v];
+		if (d.off && v < 0) return d.off;
 		snprintf(buf, sizeof(buf), "%d", v);
 		return buf;
 	}

@@ -59,8 +59,9 @@ int hns_device_count(void); /* 0 when no HIP device is visible; never initialise
  * topology, does not pay hipMalloc/hipFree again; this returns it to the driver. */
 int hns_trim_memory(void);
 /* Alternative kernel forms and data-movement strategies, kept as cross-checks of the default ones and for A/B measurement (all of them produce the same bits:
- * tests/test_kernel_variants_gpu.py). Process-wide, read by every entry point when it is called. value = NULL restores the default. Twelve names (round 6; the
- * twenty-four of round 5 -- five more SOR forms among them -- are history: DESIGN_HISTORY.md, profiles/micro/exp/):
+ * tests/test_kernel_variants_gpu.py). Process-wide, read by every entry point when it is called. value = NULL restores the default. Fourteen names: the
+ * twelve of round 6 below (the twenty-four of round 5 -- five more SOR forms among them -- are history: DESIGN_HISTORY.md, profiles/micro/exp/), "lookahead" (with
+ * hns_sim_substep) and the test switch "arena_fill":
  *   "rbgs"          auto | color. auto: temporally blocked red-black SOR (hns_sorblock.hip: two iterations per launch on 16^3-voxel blocks, two or four on one-leaf
  *                   blocks for grids of up to 600 leaves). color: the reference's own decomposition, two launches per iteration in place -- the independent cross-check
  *   "sor_block_lb"  0 = by size | 1 | 2: block edge of the temporally blocked form in leaves, whatever the size of the grid (how the tests reach both kernels on every leaf set)
@@ -82,7 +83,13 @@ int hns_trim_memory(void);
  *   "dist_unsplit"  1 | 0: a rank of the exchanged substep with up to 16,384 owned leaves runs the sweeps of its pressure loop, its divergence and its gradient subtraction
  *                   as ONE launch over all owned leaves with pack / transfer / unpack behind it on the compute stream; 0 = boundary leaves on a communication stream beside
  *                   the interior launch at every size (what larger ranks always do)
- *   "dist_wire_us"  N: the loopback transport of hns_dist holds every exchange N microseconds (emulated wire time) */
+ *   "dist_wire_us"  N: the loopback transport of hns_dist holds every exchange N microseconds (emulated wire time)
+ *   "arena_fill"    off | 0 .. 255 (a byte, in decimal): a TEST switch, no kernel form. Every block the pool of device memory (hns_trim_memory) hands out -- simulation states,
+ *                   grid and SOR tables, regrid scratch, masks, the deactivation and diagnostics tables; one taken from the pool or fresh from the driver -- is first filled
+ *                   with that byte over its whole size. No result may depend on it: 255 makes the block NaN as floats, -1 as ints and all-set as masks; 127 makes it
+ *                   3.39e38, for what lets a NaN lose (tests/test_pool_contents_gpu.py). The fill is a hipMemset followed by a wait for the WHOLE device on every draw:
+ *                   never leave it on in production, and never have it on while a stream is capturing (the wait would break the capture). Default off: one atomic load
+ *                   per draw. hns_get_option answers "off" or the byte in decimal */
 int hns_set_option(const char* name, const char* value);
 const char* hns_get_option(const char* name); /* current value as a word; NULL for an unknown name */
 

@@ -1,14 +1,19 @@
-"""TEST HELPER of the diagnostics tests (tests/test_diagnostics.py, tests/test_diagnostics_gpu.py): numpy restatements of the two things include/hns.h
-defines bit for bit -- the reduction behind an hns_stats record and the Gauss-Seidel correction c of the pressure residual -- written from the header's
-text, not from the library's code."""
+"""TEST HELPER of the diagnostics tests (tests/test_diagnostics.py, tests/test_diagnostics_gpu.py, tests/test_pool_contents_gpu.py): numpy restatements of the two
+things include/hns.h defines bit for bit -- the reduction behind an hns_stats record and the Gauss-Seidel correction c of the pressure residual -- written from the
+header's text, not from the library's code; and, for the GPU tests, the comparisons of the device diagnostics with them and with leafio.leaf_stats."""
 import math
 
 import numpy as np
 
-from hnanosolver_amd import _lib, api, leafio
+import special_cases as sc
+from frame_cases import assert_same, download
+from hnanosolver_amd import _lib, api, device as D, leafio
+from hnanosolver_amd._lib import lib
 
 F = np.float32
 INV6 = F(0.166666667)
+DX = 0.1
+REL, EVERY = 1e-3, 4  # the controlled solve of the GPU tests: relative tolerance, iterations between two checks
 QNAN64 = np.frombuffer(np.uint64(0x7FF8000000000000).tobytes(), np.float64)[0]
 
 
@@ -106,3 +111,116 @@ def residual_numpy(origins, div, p, dx):
     assert c.dtype == F
     return c.reshape(-1)
 
+
+# ---------------------------------------------------------------------------------------------------------------
+# on the GPU (torch is imported where it is used: this module also serves the tests that run without one)
+# ---------------------------------------------------------------------------------------------------------------
+
+
+def leaf_ids(n):
+    import torch
+
+    return torch.arange(n, dtype=torch.int32, device="cuda")
+
+
+def read_field(ptr, n_leaves):
+    """a float field at a raw device pointer of the library, through the library's own whole-leaf copy"""
+    import torch
+
+    out = torch.empty(n_leaves * 512, dtype=torch.float32, device="cuda")
+    D._raise(lib.hns_dev_pack_leaves(ptr, leaf_ids(n_leaves).data_ptr(), n_leaves, out.data_ptr(), 1, D.current_stream()))
+    torch.cuda.synchronize()
+    return out.cpu().numpy()
+
+
+def write_field(ptr, values):
+    import torch
+
+    v = torch.from_numpy(np.ascontiguousarray(values, dtype=F)).cuda()
+    n = v.numel() // 512
+    D._raise(lib.hns_dev_unpack_leaves(v.data_ptr(), leaf_ids(n).data_ptr(), n, ptr, 1, D.current_stream()))
+    torch.cuda.synchronize()
+
+
+def pressure_of(sim):
+    return read_field(lib.hns_sim_pressure_ptr(sim._ptr), sim.grid.leaf_count())
+
+
+def set_divergence(sim, div):
+    write_field(lib.hns_sim_divergence_ptr(sim._ptr), div)
+
+
+def words(a):
+    return np.ascontiguousarray(a).view(np.uint32).tobytes()
+
+
+def special_state(seed, n, names):
+    """normal values with a different special-value class planted in each field (NaN and +-inf, subnormals, signed zeros, 3e37, ...)"""
+    rng = np.random.default_rng(seed)
+    st = {"vel": sc.plant("nonfinite", rng.standard_normal((n * 512, 3)).astype(F), rng)}
+    for i, k in enumerate(names):
+        st[k] = sc.plant(sc.CLASSES[i % len(sc.CLASSES)], rng.standard_normal(n * 512).astype(F), rng)
+    return st
+
+
+def host_stats(sim, names, masked):
+    st = download(sim, names)
+    m = sim.active_masks() if masked else None
+    return np.concatenate([leafio.leaf_stats(st[k], m) for k in names] + [leafio.leaf_stats(st["vel"], m)]), st
+
+
+def assert_stats(sim, names, masked, what):
+    want, before = host_stats(sim, names, masked)
+    masks_before, ahead_before = sim.active_masks(), sim.lookahead_counts()
+    got = sim.stats(names, velocity=True, masks=masked)
+    assert got.tobytes() == want.tobytes(), f"{what}: {got} vs {want}"
+    assert sim.stats(names, velocity=True, masks=masked).tobytes() == got.tobytes(), f"{what}: two calls differ"
+    assert_same(download(sim, names), before, f"{what}: fields after stats")
+    assert np.array_equal(sim.active_masks(), masks_before) and sim.lookahead_counts() == ahead_before
+    return got
+
+
+def check_residual(grid, o, div, p, first, count, what):
+    import torch
+
+    c_out = torch.full((len(o) * 512,), 7.0, dtype=torch.float32, device="cuda")
+    rec = D.read_stats(D.residual(grid, div, p, DX, c_out))
+    want = residual_numpy(o, div.cpu().numpy(), p.cpu().numpy(), DX)
+    got = c_out.cpu().numpy()
+    lo, hi = first * 512, (first + count) * 512
+    assert sc.same_bits(got[lo:hi], want[lo:hi]), f"{what}: {sc.describe(got[lo:hi], want[lo:hi])}"
+    assert (got[:lo] == 7.0).all() and (got[hi:] == 7.0).all(), f"{what}: wrote outside the launch range"
+    assert rec.tobytes() == leafio.leaf_stats(got[lo:hi]).tobytes(), f"{what}: record {rec} vs {leafio.leaf_stats(got[lo:hi])}"
+    assert D.read_stats(D.residual(grid, div, p, DX)).tobytes() == rec.tobytes(), f"{what}: without c_out / second call"
+    return rec
+
+
+def crossed(rec, initial, rel=REL, abs_tol=0.0):
+    return rec["nan_count"] == 0 and rec["max_abs"] <= max(F(abs_tol), F(rel) * initial["max_abs"])
+
+
+def controlled_solve_against_plain_solves(a, b, o, div, dx, maxit):
+    """sims a and b on one grid with the divergence `div` set: the controlled pressure solve on a (REL, every EVERY iterations, at most maxit) against plain solves of
+    EVERY, 2 EVERY, ... iterations on b -- the initial record against the numpy restatement, the stop at the first crossing (or the maximum), every history entry, the
+    final record and the pressure bits. -> (report, iteration of the first crossing or None, the plain solves' records, the initial record)"""
+    initial = leafio.leaf_stats(residual_numpy(o, div, np.zeros_like(div), dx))[0]
+    a.solve_control(REL, 0.0, EVERY)
+    a.pressure_solve(maxit, dx)
+    rep = a.solve_report()
+    assert rep["initial"].tobytes() == initial.tobytes()
+    # the expected stop, derived from plain solves of 4, 8, ... iterations on the second sim
+    stop, plain = None, []
+    for j in range(EVERY, maxit + 1, EVERY):
+        b.pressure_solve(j, dx)
+        plain.append(b.residual(dx)[0])
+        if crossed(plain[-1], initial):
+            stop = j
+            break
+    ran = stop if stop is not None else EVERY * len(plain)
+    assert rep["iterations"] == ran and bool(rep["converged"]) == (stop is not None) and rep["checks"] == ran // EVERY == len(rep["history"])
+    for i, h in enumerate(rep["history"]):
+        assert h.tobytes() == plain[i].tobytes(), f"history[{i}] differs from the plain solve of {EVERY * (i + 1)} iterations"
+    assert rep["final"].tobytes() == plain[-1].tobytes()
+    assert words(pressure_of(a)) == words(pressure_of(b))
+    assert a.residual(dx)[0].tobytes() == rep["final"].tobytes()
+    return rep, stop, plain, initial

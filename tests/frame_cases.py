@@ -1,5 +1,5 @@
-"""The frame loop's test cases, shared by the regrid, source and deactivation tests: mask packing, random leaf sets, masks, fields and sources,
-device sims, and the host chain every device regrid must match byte for byte."""
+"""The frame loop's test cases, shared by the regrid, source, deactivation and pool-content tests: mask packing, random leaf sets, masks, fields and sources,
+device sims, the host chain every device regrid must match byte for byte, and a device-resident sim's frame loop against that chain continued on the host."""
 import numpy as np
 
 from hnanosolver_amd import api, device, leafio
@@ -109,6 +109,42 @@ def host_chain(origins, masks, state, names, p, sources=None, sdf=None):
         else:
             out[n] = leafio.gather_leaves(dom, cur[n][0], cur[n][1], 1, leafio.FILL_SDF if n == "collision_sdf" else leafio.FILL_ZERO)
     return dom, dm, out
+
+
+def host_deactivate(masks, st, tolerances, velocity):
+    return leafio.deactivate_masks(masks, {k: (st[k], t) for k, t in tolerances.items()}, None if velocity is None else (st["vel"], velocity))
+
+
+def frame_chain(s, names, start, frames, inputs, step, tolerances, vtol, vs, shadows=(), keep=None, probe=None):
+    """`frames` frames of the device-resident sim `s` -- a sourced regrid, two substeps, a deactivation -- each against the host chain continued on the host with the
+    downloaded substep results of a fresh sim: origins and masks after the regrid, deactivation counts, masks and every field after the frame.
+    start = (origins, masks or None, state) as uploaded to `s`; inputs(frame, origins) -> (padding, sdf or None, sources); step(sim, frame) runs one substep;
+    `shadows` are sims taken through the same regrids and substeps without deactivation; the grids go to `keep` (a list), so that none is freed mid-chain.
+    -> per frame (origins, masks after the regrid, masks after the deactivation, its counts, the downloaded fields, probe(s) taken behind the substeps)"""
+    ho, hm, hst = start
+    keep = [] if keep is None else keep
+    out = []
+    for frame in range(frames):
+        p, sdf, src = inputs(frame, ho)
+        keep.append(s.regrid(p, sdf, src))
+        for t in shadows:
+            keep.append(t.regrid(p, sdf, src))
+        ho, hm, hst = host_chain(ho, hm, hst, names, p, src, sdf)
+        assert np.array_equal(s.grid.coords()[::512], ho) and np.array_equal(s.active_masks(), hm), f"frame {frame} regrid"
+        hg, hs = make_sim(ho, names, hst, None, vs)
+        for _ in range(2):
+            for sim in (s, *shadows, hs):
+                step(sim, frame)
+        hst = download(hs, names)
+        hs.close()
+        probed, regrid_masks = probe(s) if probe else None, hm
+        counts = s.deactivate(tolerances, vtol, counts=True)
+        hm, hc = host_deactivate(hm, hst, tolerances, vtol)
+        assert counts == hc and np.array_equal(s.active_masks(), hm), f"frame {frame} deactivate"
+        got = download(s, names)
+        assert_same(got, hst, f"frame {frame}")
+        out.append((ho, regrid_masks, hm, counts, got, probed))
+    return out
 
 
 def source_leaves(rng, origins, where, n=10):

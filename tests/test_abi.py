@@ -381,3 +381,10 @@ def test_operator_refusals_keep_code_text_and_precedence():
     assert np.count_nonzero(vel) == 0 and np.count_nonzero(rho) == 0  # nothing was computed
     assert not wrong, "\n".join(wrong)
     g.reset()
+
+
+def test_arena_fill_option_round_trip():
+    """hns_set_option is host code: the pool's test switch (tests/test_pool_contents_gpu.py) round-trips without a device"""
+    from pool_cases import check_arena_fill_option
+
+    check_arena_fill_option()

@@ -6,9 +6,9 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from hnanosolver_amd import _lib, api, fields, leafio
-from frame_cases import (COMBUST, assert_same, download, emitter, host_chain, make_sim, make_sources, random_leaves, random_masks,
-                         sdf_source)
+from hnanosolver_amd import _lib, api, fields
+from frame_cases import (COMBUST, assert_same, download, emitter, frame_chain, host_chain, host_deactivate, make_sim, make_sources, random_leaves,
+                         random_masks, sdf_source)
 
 pytestmark = pytest.mark.gpu
 
@@ -37,10 +37,6 @@ def quiet_state(seed, n, names, tol, quiet_leaves=()):
         for i in quiet_leaves:
             v[i] = np.where(rng.random(v.shape[1]) < 0.5, np.float32(-0.0), np.float32(tol))
     return st
-
-
-def host_deactivate(masks, st, tolerances, velocity):
-    return leafio.deactivate_masks(masks, {k: (st[k], t) for k, t in tolerances.items()}, None if velocity is None else (st["vel"], velocity))
 
 
 CASES = {
@@ -138,28 +134,10 @@ def test_six_frame_chain_against_the_host_chain():
     names = COMBUST
     o, st = chain_state(R)
     params = api.CombustionParams()
-    tolerances, vtol = {"density": 1e-2}, 0.1
     g, s = make_sim(o, names, st, None, 1.0 / R)
     g0, s0 = make_sim(o, names, st, None, 1.0 / R)  # the same chain without deactivation
-    grids = [g, g0]
-    ho, hm, hst = o, None, st
-    for frame in range(6):
-        src = emitter(R, frame)
-        grids.append(s.regrid(1, None, src))
-        grids.append(s0.regrid(1, None, src))
-        ho, hm, hst = host_chain(ho, hm, hst, names, 1, src)
-        assert np.array_equal(s.grid.coords()[::512], ho) and np.array_equal(s.active_masks(), hm), f"frame {frame} regrid"
-        hg, hs = make_sim(ho, names, hst, None, 1.0 / R)
-        for _ in range(2):
-            s.substep(4, 1.0 / 24, 1.0 / R, params, False)
-            s0.substep(4, 1.0 / 24, 1.0 / R, params, False)
-            hs.substep(4, 1.0 / 24, 1.0 / R, params, False)
-        hst = download(hs, names)
-        hs.close()
-        counts = s.deactivate(tolerances, vtol, counts=True)
-        hm, hc = host_deactivate(hm, hst, tolerances, vtol)
-        assert counts == hc and np.array_equal(s.active_masks(), hm), f"frame {frame} deactivate"
-        assert_same(download(s, names), hst, f"frame {frame}")
+    frame_chain(s, names, (o, None, st), 6, lambda frame, origins: (1, None, emitter(R, frame)), lambda sim, frame: sim.substep(4, 1.0 / 24, 1.0 / R, params, False),
+                {"density": 1e-2}, 0.1, 1.0 / R, shadows=(s0,), keep=[g, g0])
     assert s.grid.leaf_count() < s0.grid.leaf_count(), (s.grid.leaf_count(), s0.grid.leaf_count())
     s.close(), s0.close()
 

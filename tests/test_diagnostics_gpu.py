@@ -8,6 +8,7 @@ import torch
 import diag_cases as dc
 import hnanosolver_amd as H
 import special_cases as sc
+from diag_cases import DX, EVERY, REL, assert_stats, check_residual, crossed, host_stats, pressure_of, set_divergence, special_state, words
 from frame_cases import COMBUST, assert_same, download, make_sim, make_sources, random_leaves, random_masks
 from hnanosolver_amd import _lib, api, device as D, fields, leafio
 from hnanosolver_amd._lib import lib
@@ -15,7 +16,6 @@ from hnanosolver_amd._lib import lib
 pytestmark = pytest.mark.gpu
 
 F = np.float32
-DX = 0.1
 
 
 @pytest.fixture(autouse=True)
@@ -25,66 +25,9 @@ def restore_options():
         H.set_option(k, None)
 
 
-def leaf_ids(n):
-    return torch.arange(n, dtype=torch.int32, device="cuda")
-
-
-def read_field(ptr, n_leaves):
-    """a float field at a raw device pointer of the library, through the library's own whole-leaf copy"""
-    out = torch.empty(n_leaves * 512, dtype=torch.float32, device="cuda")
-    D._raise(lib.hns_dev_pack_leaves(ptr, leaf_ids(n_leaves).data_ptr(), n_leaves, out.data_ptr(), 1, D.current_stream()))
-    torch.cuda.synchronize()
-    return out.cpu().numpy()
-
-
-def write_field(ptr, values):
-    v = torch.from_numpy(np.ascontiguousarray(values, dtype=F)).cuda()
-    n = v.numel() // 512
-    D._raise(lib.hns_dev_unpack_leaves(v.data_ptr(), leaf_ids(n).data_ptr(), n, ptr, 1, D.current_stream()))
-    torch.cuda.synchronize()
-
-
-def pressure_of(sim):
-    return read_field(lib.hns_sim_pressure_ptr(sim._ptr), sim.grid.leaf_count())
-
-
-def set_divergence(sim, div):
-    write_field(lib.hns_sim_divergence_ptr(sim._ptr), div)
-
-
-def words(a):
-    return np.ascontiguousarray(a).view(np.uint32).tobytes()
-
-
 # ---------------------------------------------------------------------------------------------------------------
 # field statistics
 # ---------------------------------------------------------------------------------------------------------------
-
-
-def special_state(seed, n, names):
-    """normal values with a different special-value class planted in each field (NaN and +-inf, subnormals, signed zeros, 3e37, ...)"""
-    rng = np.random.default_rng(seed)
-    st = {"vel": sc.plant("nonfinite", rng.standard_normal((n * 512, 3)).astype(F), rng)}
-    for i, k in enumerate(names):
-        st[k] = sc.plant(sc.CLASSES[i % len(sc.CLASSES)], rng.standard_normal(n * 512).astype(F), rng)
-    return st
-
-
-def host_stats(sim, names, masked):
-    st = download(sim, names)
-    m = sim.active_masks() if masked else None
-    return np.concatenate([leafio.leaf_stats(st[k], m) for k in names] + [leafio.leaf_stats(st["vel"], m)]), st
-
-
-def assert_stats(sim, names, masked, what):
-    want, before = host_stats(sim, names, masked)
-    masks_before, ahead_before = sim.active_masks(), sim.lookahead_counts()
-    got = sim.stats(names, velocity=True, masks=masked)
-    assert got.tobytes() == want.tobytes(), f"{what}: {got} vs {want}"
-    assert sim.stats(names, velocity=True, masks=masked).tobytes() == got.tobytes(), f"{what}: two calls differ"
-    assert_same(download(sim, names), before, f"{what}: fields after stats")
-    assert np.array_equal(sim.active_masks(), masks_before) and sim.lookahead_counts() == ahead_before
-    return got
 
 
 @pytest.mark.parametrize("masked", [False, True], ids=["all", "masks"])
@@ -150,19 +93,6 @@ def test_dev_field_stats_on_caller_memory():
 # ---------------------------------------------------------------------------------------------------------------
 
 
-def check_residual(grid, o, div, p, first, count, what):
-    c_out = torch.full((len(o) * 512,), 7.0, dtype=torch.float32, device="cuda")
-    rec = D.read_stats(D.residual(grid, div, p, DX, c_out))
-    want = dc.residual_numpy(o, div.cpu().numpy(), p.cpu().numpy(), DX)
-    got = c_out.cpu().numpy()
-    lo, hi = first * 512, (first + count) * 512
-    assert sc.same_bits(got[lo:hi], want[lo:hi]), f"{what}: {sc.describe(got[lo:hi], want[lo:hi])}"
-    assert (got[:lo] == 7.0).all() and (got[hi:] == 7.0).all(), f"{what}: wrote outside the launch range"
-    assert rec.tobytes() == leafio.leaf_stats(got[lo:hi]).tobytes(), f"{what}: record {rec} vs {leafio.leaf_stats(got[lo:hi])}"
-    assert D.read_stats(D.residual(grid, div, p, DX)).tobytes() == rec.tobytes(), f"{what}: without c_out / second call"
-    return rec
-
-
 @pytest.mark.parametrize("lb", [0, 1, 2])
 @pytest.mark.parametrize("leaf_set", ["ragged32", "dense32", "sparse_far", "one_leaf"])
 def test_residual_field_and_record_behind_both_sor_kernels(leaf_set, lb):
@@ -205,12 +135,8 @@ def test_residual_on_a_launch_range():
 # the controlled solve
 # ---------------------------------------------------------------------------------------------------------------
 
-REL, EVERY, MAXIT = 1e-3, 4, 100
+MAXIT = 100
 SETS = {"box16": lambda: fields.dense_leaves(16), "ragged32": sc.LEAF_SETS["ragged32"]}
-
-
-def crossed(rec, initial, rel=REL, abs_tol=0.0):
-    return rec["nan_count"] == 0 and rec["max_abs"] <= max(F(abs_tol), F(rel) * initial["max_abs"])
 
 
 def solve_sims(leaf_set, names=("density",), seed=20):
@@ -229,28 +155,11 @@ def solve_sims(leaf_set, names=("density",), seed=20):
 @pytest.mark.parametrize("leaf_set", list(SETS))
 def test_controlled_pressure_solve_stops_at_the_first_crossing(leaf_set):
     o, st, div, (a, b) = solve_sims(leaf_set)
-    initial = leafio.leaf_stats(dc.residual_numpy(o, div, np.zeros_like(div), DX))[0]
-    a.solve_control(REL, 0.0, EVERY)
     a.timing(4)
-    a.pressure_solve(MAXIT, DX)
-    rep = a.solve_report()
-    assert rep["initial"].tobytes() == initial.tobytes()
-    # the expected stop, derived from plain solves of 4, 8, ... iterations on the second sim
-    stop, plain = None, []
-    for j in range(EVERY, MAXIT + 1, EVERY):
-        b.pressure_solve(j, DX)
-        plain.append(b.residual(DX)[0])
-        if crossed(plain[-1], initial):
-            stop = j
-            break
+    rep, stop, plain, initial = dc.controlled_solve_against_plain_solves(a, b, o, div, DX, MAXIT)
     print(f"{leaf_set}: first crossing of {REL} at iteration {stop}; max_abs initial {initial['max_abs']:.3e}, history {[float(h['max_abs']) for h in rep['history']]}")
     assert stop is not None, "the plain solves never cross within the maximum"
     assert rep["iterations"] == stop and rep["converged"] and rep["checks"] == stop // EVERY == len(rep["history"])
-    for i, h in enumerate(rep["history"]):
-        assert h.tobytes() == plain[i].tobytes(), f"history[{i}] differs from the plain solve of {EVERY * (i + 1)} iterations"
-    assert rep["final"].tobytes() == plain[-1].tobytes()
-    assert words(pressure_of(a)) == words(pressure_of(b))
-    assert a.residual(DX)[0].tobytes() == rep["final"].tobytes()
     ms, iters = a.pressure_time()
     assert iters == stop  # hns_sim_timing counts the iterations that ran
     # control off after on: the parent's bits again

@@ -6,53 +6,11 @@ plume split into 8 leaf ranges."""
 import numpy as np
 import pytest
 
+from dist_cases import SIM_NAMES, check, partitioned_sim_substeps_match_single_grid, run_local, single_grid
 from hnanosolver_amd import dist as HD
 from hnanosolver_amd import fields
 
 pytestmark = pytest.mark.gpu
-
-
-def single_grid(origins, R, names, iters, substeps, dt=1.0 / 24.0, f=None):
-    """f: a dictionary of fields in place of fields.synthetic_fields (the special-value cases)"""
-    from hnanosolver_amd import api, device as D
-
-    f = f or fields.synthetic_fields(origins, R)
-    grid = api.create_grid_from_leaves(origins, 1.0 / R)
-    sim = D.Sim(grid, names)
-    arrays = {"vel": f["vel"].copy(), **{n: f[n].copy() for n in names}}
-    sim.upload(arrays)
-    for _ in range(substeps):
-        sim.core_substep(iters, dt, 1.0 / R, D.current_stream())
-    sim.download(arrays)
-    return f, arrays
-
-
-def run_local(origins, R, world, k, names, iters, substeps, dt=1.0 / 24.0, f=None):
-    import torch
-
-    f = f or fields.synthetic_fields(origins, R)
-    ranks = [HD.DistRank(origins, world, r, 1.0 / R, n_scalars=len(names), sweeps_per_exchange=k) for r in range(world)]
-    HD.DistRank.connect_local(ranks)
-    b = None  # (which leaves a rank owns is the rank's own knowledge: DistRank.owned_ids / owned_voxels)
-    for r, d in enumerate(ranks):
-        d.upload(d.owned_voxels(f["vel"]), [d.owned_voxels(f[n]) for n in names])
-    stream = int(torch.cuda.current_stream().cuda_stream)
-    for _ in range(substeps):
-        HD.DistRank.local_core_substep(ranks, iters, dt, stream)
-    for d in ranks:
-        d.synchronize(stream)
-    return ranks, b
-
-
-def check(ranks, b, want, names):
-    # the ghost voxels the next kernels read hold their owners' bits (velocity: whole leaves; p: reach 1), whatever the transport wrote them with
-    n_pairs, bad = HD.DistRank.ghost_check_local(ranks)
-    assert not bad and (n_pairs > 0 or len(ranks) == 1), (n_pairs, bad[:3])
-    for r, d in enumerate(ranks):
-        got = d.download()
-        assert np.array_equal(got["vel"], d.owned_voxels(want["vel"])), f"rank {r} velocity"
-        for n, a in zip(names, got["scalars"]):
-            assert np.array_equal(a, d.owned_voxels(want[n])), f"rank {r} {n}"
 
 
 def scattered_leaves():
@@ -91,8 +49,8 @@ def _local_ranks_match_single_grid(name, world, k, iters=7):
                   "dense64": (fields.dense_leaves(64), 64), "plume16": (fields.plume_leaves(16, 1.5, 0.3), 128), "scattered_big": (big_scattered_leaves(), 144)}[name]
     names, substeps = ["density", "temperature"], 2
     _, want = single_grid(origins, R, names, iters, substeps)
-    ranks, b = run_local(origins, R, world, k, names, iters, substeps)
-    check(ranks, b, want, names)
+    ranks = run_local(origins, R, world, k, names, iters, substeps)
+    check(ranks, want, names)
     info = [d.info() for d in ranks]
     assert all(i["sweeps_per_exchange"] == (k or 4) for i in info)
     assert sum(i["boundary_leaves"] + i["interior_leaves"] for i in info) == len(origins)
@@ -118,8 +76,8 @@ def test_exchanged_blocked_boundary_sweep_packs_its_own_messages():
     _, want = single_grid(origins, R, names, iters, 1)
     H.set_option("dist_mirror", "0")
     try:
-        ranks, b = run_local(origins, R, world, 2, names, iters, 1)
-        check(ranks, b, want, names)
+        ranks = run_local(origins, R, world, 2, names, iters, 1)
+        check(ranks, want, names)
         info = [d.info() for d in ranks]
     finally:
         H.set_option("dist_mirror", None)
@@ -160,7 +118,7 @@ def test_ranks_match_single_grid_on_special_values(name, world, k, iters, cls):
     _, want = single_grid(origins, R, names, iters, substeps, f=f)
     for n in names:
         assert np.isnan(want[n]).mean() <= 0.5 and (cls != "nonfinite" or np.isnan(f[n]).any())
-    ranks, b = run_local(origins, R, world, k, names, iters, substeps, f=f)
+    ranks = run_local(origins, R, world, k, names, iters, substeps, f=f)
     n_pairs, bad = HD.DistRank.ghost_check_local(ranks)
     assert not bad and n_pairs > 0, (n_pairs, bad[:3])
     for r, d in enumerate(ranks):
@@ -180,8 +138,8 @@ def test_plume1024_in_8_ranges_matches_single_grid(k):
     origins, R = fields.config_leaves("plume1024")
     names, iters = ["density"], 50
     _, want = single_grid(origins, R, names, iters, 1)
-    ranks, b = run_local(origins, R, 8, k, names, iters, 1)
-    check(ranks, b, want, names)
+    ranks = run_local(origins, R, 8, k, names, iters, 1)
+    check(ranks, want, names)
     info = [d.info() for d in ranks]
     assert max(i["peers"] for i in info) <= 7 and min(i["boundary_leaves"] for i in info) > 0
     for i in info:
@@ -202,7 +160,7 @@ def test_new_fields_between_substeps_and_many_substeps():
     origins, R = fields.plume_leaves(8, 1.5, 0.35), 64
     names, iters = ["density"], 5
     _, want = single_grid(origins, R, names, iters, 3)
-    ranks, b = run_local(origins, R, 3, 2, names, iters, 2)  # two substeps on fields that are then replaced
+    ranks = run_local(origins, R, 3, 2, names, iters, 2)  # two substeps on fields that are then replaced
     import torch
 
     f = fields.synthetic_fields(origins, R)
@@ -213,7 +171,7 @@ def test_new_fields_between_substeps_and_many_substeps():
         HD.DistRank.local_core_substep(ranks, iters, 1.0 / 24.0, stream)
     for d in ranks:
         d.synchronize(stream)
-    check(ranks, b, want, names)
+    check(ranks, want, names)
 
 
 def test_world_size_one_equals_sim():
@@ -555,18 +513,7 @@ def test_back_trace_beyond_the_ghost_layer_is_reported():
     for d in ranks:
         d.synchronize(stream)
     _, want = single_grid(origins, R, names, iters, 1)
-    check(ranks, None, want, names)
-
-
-SIM_NAMES = ["density", "temperature", "fuel", "waste", "flame", "collision_sdf"]
-
-
-def _sim_fields(origins, R):
-    f = fields.synthetic_fields(origins, R)
-    f["collision_sdf"] = fields.sphere_sdf(origins, R)
-    f["waste"] = (0.05 * f["density"]).astype(np.float32)  # burning state: every combustion branch is exercised (tests/kats.py has the table)
-    f["flame"] = (0.3 * f["fuel"]).astype(np.float32)
-    return f
+    check(ranks, want, names)
 
 
 @pytest.mark.parametrize("name,world,k,coll,factor_scale", [("plume", 8, 4, False, 0.5), ("plume", 8, 2, True, 1.0), ("dense32", 2, 4, True, 0.5), ("scattered", 5, 1, False, 2.0),
@@ -575,34 +522,13 @@ def test_partitioned_compute_sim_matches_single_grid(name, world, k, coll, facto
     """The WHOLE Compute_Sim substep (collision, advect_vector, vorticity confinement, divergence, combustion, buoyancy, solve, gradient,
     collision, advect_scalars; reference HNanoSolver.cu:150-356) on a domain split into leaf ranges: owned results of three chained
     substeps equal hns_sim_substep's on the one grid bit for bit."""
-    import torch
-    from hnanosolver_amd import api, device as D
+    from hnanosolver_amd import api
 
     origins, R = {"dense32": (fields.dense_leaves(32), 32), "plume": (fields.plume_leaves(16, 1.5, 0.3), 128), "scattered": (scattered_leaves(), 96)}[name]
     # (buoyancy and confinement kept gentle: at the SOP defaults the plume accelerates by ~10 voxels per step and step, and a back-trace that long leaves a
     # rank's ghost layer -- which test_back_trace_beyond_the_ghost_layer_is_reported covers)
     params = api.CombustionParams(factorScale=factor_scale, vorticityScale=0.01, buoyancyStrength=0.05)
-    iters, dt, substeps = 9, 1.0 / 24.0, 3
-    f = _sim_fields(origins, R)
-    grid = api.create_grid_from_leaves(origins, 1.0 / R)
-    sim = D.Sim(grid, SIM_NAMES)
-    want = {"vel": f["vel"].copy(), **{n: f[n].copy() for n in SIM_NAMES}}
-    sim.upload(want)
-    for _ in range(substeps):
-        sim.substep(iters, dt, 1.0 / R, params, coll, D.current_stream())
-    sim.download(want)
-
-    ranks = [HD.DistRank(origins, world, r, 1.0 / R, n_scalars=len(SIM_NAMES), sweeps_per_exchange=k) for r in range(world)]
-    HD.DistRank.connect_local(ranks)
-    b = None
-    for r, d in enumerate(ranks):
-        d.upload(d.owned_voxels(f["vel"]), [d.owned_voxels(f[n]) for n in SIM_NAMES])
-    stream = int(torch.cuda.current_stream().cuda_stream)
-    for _ in range(substeps):
-        HD.DistRank.local_sim_substep(ranks, SIM_NAMES, iters, dt, params, coll, stream)
-    for d in ranks:
-        d.synchronize(stream)
-    check(ranks, b, want, SIM_NAMES)
+    partitioned_sim_substeps_match_single_grid(origins, R, world, k, 9, 3, params, coll)
 
 
 def test_partitioned_compute_sim_refuses_what_the_reference_refuses():

@@ -7,6 +7,7 @@ import time
 import numpy as np
 import pytest
 
+from grid_cases import assert_device_tables_match_host_builder, expected_sched
 from hnanosolver_amd import _lib, api, fields
 
 pytestmark = pytest.mark.gpu
@@ -30,36 +31,9 @@ LEAF_SETS = {
 }
 
 
-def expected_sched(n):
-    base, rem = n // 8, n % 8
-    b = np.arange(n)
-    x, i = b % 8, b // 8
-    return (x * base + np.minimum(x, rem) + i).astype(np.int32)
-
-
 @pytest.mark.parametrize("name", list(LEAF_SETS))
 def test_device_tables_match_host_builder(name):
-    origins = LEAF_SETS[name]()
-    dev = api.create_grid_from_leaves(origins, 0.1)
-    host = api.create_grid_from_leaves(origins, 0.1, _lib.HNS_GRID_HOST_ONLY)
-    nbr_d, nbr_h = dev.neighbor_table(), host.neighbor_table()
-    assert np.array_equal(nbr_d, nbr_h)
-    # origin hash: same answers for voxels inside, next to and far from the domain
-    rng = np.random.default_rng(7)
-    c = fields.leaves_to_coords(origins)
-    probes = np.concatenate([c[rng.integers(0, len(c), 4000)], c[rng.integers(0, len(c), 4000)] + rng.integers(-20, 21, (4000, 3)),
-                             rng.integers(-2**31, 2**31 - 1, (2000, 3))]).astype(np.int64)
-    probes = np.clip(probes, -2**31, 2**31 - 1).astype(np.int32)
-    assert np.array_equal(dev.offsets(probes), host.offsets(probes))
-    inside = dev.offsets(c[::97])
-    assert np.array_equal(inside, np.arange(len(c), dtype=np.uint64)[::97] + 1)
-    # launch order
-    n = len(origins)
-    sched = dev.launch_order()
-    assert np.array_equal(np.sort(sched), np.arange(n))  # every leaf is worked on by exactly one workgroup
-    assert np.array_equal(sched, expected_sched(n))
-    dev.reset()
-    host.reset()
+    assert_device_tables_match_host_builder(LEAF_SETS[name]())
 
 
 def expected_sched_segments(n, seg):

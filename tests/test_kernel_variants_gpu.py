@@ -17,7 +17,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def run_workload():
     from hnanosolver_amd import api, fields
-    from test_operators_gpu import build_data, snapshot
+    from operator_cases import build_data, snapshot
 
     out = {}
     rng = np.random.default_rng(77)
@@ -143,6 +143,13 @@ def test_unknown_option_is_refused():
     with pytest.raises(H.HNSError):
         H.set_option("no-such-option", "1")
     assert H.get_option("no-such-option") is None
+
+
+def test_arena_fill_option_round_trip():
+    """the pool's test switch (tests/test_pool_contents_gpu.py): off | a byte in decimal"""
+    from pool_cases import check_arena_fill_option
+
+    check_arena_fill_option()
 
 
 BIG_CHILD = r"""

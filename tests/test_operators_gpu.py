@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 from hnanosolver_amd import api, fields
+from operator_cases import build_data, snapshot
 
 pytestmark = pytest.mark.gpu
 
@@ -15,31 +16,6 @@ def rel_linf(a, b):
     a = np.asarray(a, dtype=np.float64)
     b = np.asarray(b, dtype=np.float64)
     return np.abs(a - b).max() / max(np.abs(b).max(), 1e-30)
-
-
-def build_data(origins, R, with_sdf=False, amplitude=96.0, combustion=True):
-    f = fields.synthetic_fields(origins, R, amplitude_voxels=amplitude)
-    coords = fields.leaves_to_coords(origins)
-    d = api.GridIndexedData()
-    d.allocateCoords(len(coords))
-    d.pCoords()[:] = coords
-    # insertion order as the HNanoSolver SOP adds them: float grids first, then velocity (order of getBlocksOfType matters)
-    order = ["density", "temperature", "fuel", "waste", "flame"]
-    for name in order:
-        d.addValueBlock(name, d.FLOAT)
-        d.pValues(name)[:] = f[name] if (combustion or name in ("density", "temperature")) else 0.0
-    if with_sdf:
-        d.addValueBlock("collision_sdf", d.FLOAT)
-        sdf = fields.sphere_sdf(origins, R, center=(0.5, 0.3, 0.5), radius=0.15)
-        sdf[::11] = np.float32(0.04)
-        d.pValues("collision_sdf")[:] = sdf
-    d.addValueBlock("vel", d.VEC3F)
-    d.pValues("vel")[:] = f["vel"]
-    return d
-
-
-def snapshot(d):
-    return {n: d.pValues(n).copy() for n in d.getBlocksOfType(d.FLOAT) + d.getBlocksOfType(d.VEC3F)}
 
 
 GRIDS = {
