@@ -583,6 +583,56 @@ struct ScalarPtrs {
 	float* q4_out[4];
 };
 
+// advect_scalar (Kernel.cu:269-352) over up to HNS_MAX_SCALARS fields with ONE back-trace: k_advect_scalar_n's arithmetic per field (nested lerps, 0 outside the domain,
+// unfused correction), so every output is bit-identical to one k_advect_scalar_n launch per field (P.q4 unused). What does not depend on the field is done once per voxel --
+// own velocity, table staging, back position, both sets of eight tap offsets and the eight 12-byte velocity gathers (26 L1 tag lookups each, the unit these kernels are bound
+// by) -- where S launches of k_advect_scalar_n do it S times.
+// The two z-corners of a tap column come as one 8-byte load (ld_zpair): 9 + 8 S gathers per voxel against 25 S. The offsets are unmapped, so the pair of an absent leaf lies
+// wholly past the descriptor and reads 0, and hi == lo + 4 cannot hold across two leaves (leaf bases are multiples of 2048): the same values as eight 4-byte loads
+// (measured against those: profiles/advect_multi_ab.txt). Two tiles alternate so that one barrier per field suffices (as s_box[2] of k_advect_scalars_n).
+// Eight waves per SIMD: at 62 registers four workgroups share a CU; left to itself the compiler takes 67 = three, 7-10 % slower at S = 2 ... 8 (the same file, 2).
+__device__ __forceinline__ float tri_f_zpair(const v4i& rf, const TapsB& T) {  // tri_f_b with z-paired loads
+	float c[8];
+#pragma unroll
+	for (int m = 0; m < 4; ++m) ld_zpair(rf, T.o[2 * m], T.o[2 * m + 1], c[2 * m], c[2 * m + 1]);
+	return tri_nest(c, T.fx, T.fy, T.fz, lerp_f);
+}
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_advect_scalar_multi_n(const GridDev g, const float* __restrict__ u, const ScalarPtrs P, const float scaled_dt) {
+	__shared__ NarrowTabs tabs;
+	NarrowCtx C(g, tabs);
+	const int n = C.n;
+	const unsigned bytes1 = (unsigned)g.n_leaves * 2048u, own = (unsigned)C.idx << 2;
+	const v4i ru = field_rsrc(u, bytes1 * 3u);
+	const f3 vc = ldv(ru, own);  // (issued before the neighbour table is staged: see k_advect_vector_n)
+	C.stage(g);
+	// the back-trace, once: B = taps of the back position, F = taps of the forward position (a 2-trip loop so that the far-tap path is emitted once)
+	float sx = C.px - scaled_dt * vc.x, sy = C.py - scaled_dt * vc.y, sz = C.pz - scaled_dt * vc.z;
+	TapsB B, F;
+#pragma unroll 1
+	for (int pass = 0; pass < 2; ++pass) {
+		F = make_taps_b(g, C, sx, sy, sz);
+		if (pass == 0) {
+			B = F;
+			const f3 vf = tri_v_b(ru, B);
+			sx = sx + scaled_dt * vf.x, sy = sy + scaled_dt * vf.y, sz = sz + scaled_dt * vf.z;
+		}
+	}
+	const unsigned ho = n < 384 ? halo_off(tabs.b4, n) : 0u;
+	__shared__ float s_tile[2][kTile];  // clamp neighbours through LDS (see k_advect_vector_n)
+	for (int s = 0; s < P.n; ++s) {
+		const v4i rf = field_rsrc(P.in[s], bytes1);
+		float* tile = s_tile[s & 1];
+		const float phiOrig = lds1(rf, own);
+		tile[n] = phiOrig;
+		if (n < 384) tile[512 + n] = lds1(rf, ho);
+		const float phiForward = tri_f_zpair(rf, B), phiBackward = tri_f_zpair(rf, F);
+		const float error = phiOrig - phiBackward;
+		__syncthreads();
+		const float nv[6] = {tile[tile_nbr<0, -1>(n)], tile[tile_nbr<0, 1>(n)], tile[tile_nbr<1, -1>(n)], tile[tile_nbr<1, 1>(n)], tile[tile_nbr<2, -1>(n)], tile[tile_nbr<2, 1>(n)]};
+		P.out[s][C.idx] = bfecc_limit(phiOrig, nv, phiForward, phiForward + 0.5f * error);
+	}
+}
+
 // setupInterpolation (Kernel.cu:163-196): indices and weights in the order 000,100,010,110,001,101,011,111 of (x,y,z)
 __device__ __forceinline__ void interp_from_taps(const Taps& T, int oob, int (&ix)[8], float (&w)[8]) {
 	tri_weights(T.fx, T.fy, T.fz, w);
@@ -946,6 +996,62 @@ int hns_dev_advect_scalars(hns_grid* g, const float* vel3, const float* const* i
 		}
 	}
 	return launch_status("hns_dev_advect_scalars");
+}
+
+// advect_scalar over n fields with one back-trace per launch of up to HNS_MAX_SCALARS fields (k_advect_scalar_multi_n); with a collision field or 64-bit addressing one
+// k_advect_scalar launch per field. Either way output i is bit-identical to hns_dev_advect_scalar of field i.
+int hns_dev_advect_scalar_multi(hns_grid* g, const float* vel3, const float* const* in, float* const* out, int n, const float* sdf, int has_collision, float dt, float inv_dx,
+                                void* stream) {
+	if (int rc = check_grid(g, "hns_dev_advect_scalar_multi")) return rc;
+	NULLCHK(!vel3 || (n > 0 && (!in || !out)), "hns_dev_advect_scalar_multi");
+	// every refusal before the first launch: a field the kernel reads while a workgroup of the same call writes it has no defined result
+	for (int i = 0; i < n; ++i) {
+		if (!in[i] || !out[i]) {
+			set_error("hns_dev_advect_scalar_multi: null device pointer for field %d", i);
+			return HNS_ERR_INVALID_ARGUMENT;
+		}
+		if (out[i] == vel3) {
+			set_error("hns_dev_advect_scalar_multi: output of field %d aliases the velocity", i);
+			return HNS_ERR_INVALID_ARGUMENT;
+		}
+		for (int j = 0; j < n; ++j) {
+			if (out[i] == in[j]) {
+				set_error("hns_dev_advect_scalar_multi: output of field %d aliases the input of field %d", i, j);
+				return HNS_ERR_INVALID_ARGUMENT;
+			}
+			if (j < i && out[i] == out[j]) {
+				set_error("hns_dev_advect_scalar_multi: output of field %d is the output of field %d", i, j);
+				return HNS_ERR_INVALID_ARGUMENT;
+			}
+		}
+	}
+	if (g->n_active == 0 || n <= 0) return HNS_OK;
+	const float scaled_dt = dt * inv_dx;
+	const dim3 grid((unsigned)g->n_active), block(512);
+	const AdvectForm form = advect_form(g, sdf, has_collision);
+	if (form == AdvectForm::narrow) {
+		// the back-trace does not depend on the fields, so splitting them over several launches changes nothing numerically
+		// A lone field (n = 1, or the ninth of nine) has nothing to share and goes to k_advect_scalar_n, which interleaves the field's first sample with the velocity
+		// gathers: the multi-field kernel with one field measured 10-18 % slower than it at 256^3 (profiles/advect_multi_ab.txt, 1). The same bits either way.
+		for (int base = 0; base < n; base += HNS_MAX_SCALARS) {
+			const int m = n - base < HNS_MAX_SCALARS ? n - base : HNS_MAX_SCALARS;
+			if (m == 1) {
+				hipLaunchKernelGGL(k_advect_scalar_n, grid, block, 0, (hipStream_t)stream, g->dev(), vel3, in[base], out[base], scaled_dt);
+				continue;
+			}
+			ScalarPtrs P;
+			fill_scalar_ptrs(P, in + base, out + base, m);
+			hipLaunchKernelGGL(k_advect_scalar_multi_n, grid, block, 0, (hipStream_t)stream, g->dev(), vel3, P, scaled_dt);
+		}
+	} else {
+		for (int i = 0; i < n; ++i) {
+			if (form == AdvectForm::collision)
+				hipLaunchKernelGGL(k_advect_scalar<true>, grid, block, 0, (hipStream_t)stream, g->dev(), vel3, in[i], out[i], sdf, scaled_dt);
+			else
+				hipLaunchKernelGGL(k_advect_scalar<false>, grid, block, 0, (hipStream_t)stream, g->dev(), vel3, in[i], out[i], sdf, scaled_dt);
+		}
+	}
+	return launch_status("hns_dev_advect_scalar_multi");
 }
 
 // can this grid take the look-ahead launch (hns_dev_advect_scalars_ahead)?

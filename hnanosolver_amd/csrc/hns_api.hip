@@ -515,6 +515,50 @@ extern "C" int hns_sim_core_substep(hns_sim* s, int iterations, float dt, float 
 	return sim_substep(s, iterations, dt, voxel_size, nullptr, 0, stream);
 }
 
+// AdvectIndexGrid over the named float fields (n_names -1: all of them), then AdvectIndexGridVelocity, on the sim's buffers (Advection.cu:76-91,148-155): the fields read the
+// velocity before its self-advection. Every check comes before the first launch.
+extern "C" int hns_sim_advect(hns_sim* s, const char* const* names, int n_names, int advect_velocity, float dt, float voxel_size, void* stream) {
+	if (!s) {  // (without a device there is no sim to pass: hns_sim_create refused, and the caller learns why here too)
+		if (hns_device_count() == 0) return fail(HNS_ERR_NO_DEVICE, "hns_sim_advect: no HIP device (there is no CPU fallback)");
+		return fail(HNS_ERR_INVALID_ARGUMENT, "hns_sim_advect: null sim");
+	}
+	if (n_names < -1 || (n_names > 0 && !names)) return fail(HNS_ERR_INVALID_ARGUMENT, "hns_sim_advect: bad field list");
+	if (s->cached || s->in_use) return fail(HNS_ERR_INVALID_ARGUMENT, "hns_sim_advect: the sim belongs to a grid's cook cache");
+	HNS_TRY(validate_step(voxel_size, dt, 0, false));
+	std::vector<int> which;
+	if (n_names < 0) {
+		for (size_t i = 0; i < s->names.size(); ++i) which.push_back((int)i);
+	}
+	for (int i = 0; i < n_names; ++i) {
+		const int k = names[i] ? s->find(names[i]) : -1;
+		if (k < 0) {
+			set_error("hns_sim_advect: no float field named '%s' in this sim", names[i] ? names[i] : "?");
+			return HNS_ERR_INVALID_ARGUMENT;
+		}
+		if (std::find(which.begin(), which.end(), k) != which.end()) {
+			set_error("hns_sim_advect: field '%s' is listed twice", names[i]);
+			return HNS_ERR_INVALID_ARGUMENT;
+		}
+		which.push_back(k);
+	}
+	if (s->n == 0) return HNS_OK;
+	const float inv_dx = 1.0f / voxel_size;
+	std::vector<const float*> ins;
+	std::vector<float*> outs;
+	for (int k : which) ins.push_back(s->cur[k]), outs.push_back(s->nxt[k]);
+	HNS_TRY(hns_dev_advect_scalar_multi(s->grid, s->vel, ins.data(), outs.data(), (int)ins.size(), nullptr, 0, dt, inv_dx, stream));
+	for (int k : which) {
+		s->forget(k);
+		std::swap(s->cur[k], s->nxt[k]);
+	}
+	if (advect_velocity) {
+		s->forget(hns_sim::kVelocity);  // (drops the look-ahead memo: adv is overwritten, then becomes vel)
+		HNS_TRY(hns_dev_advect_vector(s->grid, s->vel, s->adv, nullptr, 0, dt, inv_dx, stream));
+		std::swap(s->vel, s->adv);
+	}
+	return HNS_OK;
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // drop-in operators (host pointers, synchronous, in place)
 // ---------------------------------------------------------------------------------------------------------------
@@ -903,10 +947,9 @@ extern "C" int hns_advect_index_grid(hns_grid* g, hns_field* fields, int n_field
 	hns_sim* s = guard.s;
 	if (!s) return HNS_OK;
 	const float inv_dx = 1.0f / voxel_size;
-	for (size_t i = 0; i < s->names.size(); ++i) {  // one advect_scalar per float block (Advection.cu:88-91)
-		HNS_TRY(hns_dev_advect_scalar(g, s->vel, s->cur[i], s->nxt[i], nullptr, 0, dt, inv_dx, stream));
-		std::swap(s->cur[i], s->nxt[i]);
-	}
+	// advect_scalar of every float block (Advection.cu:88-91: one launch per block), here with one back-trace for all of them: the same bits
+	HNS_TRY(hns_dev_advect_scalar_multi(g, s->vel, s->cur.data(), s->nxt.data(), (int)s->names.size(), nullptr, 0, dt, inv_dx, stream));
+	for (size_t i = 0; i < s->names.size(); ++i) std::swap(s->cur[i], s->nxt[i]);
 	std::vector<hns_field> outs;
 	for (hns_field* f : fs.floats) outs.push_back(*f);  // velocity is not copied back (Advection.cu:94-96)
 	return hns_sim_download(s, outs.data(), (int)outs.size(), stream);

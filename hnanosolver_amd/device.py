@@ -56,6 +56,15 @@ def advect_scalars(grid: IndexGridHandle, u, srcs: Sequence, dsts: Sequence, dt:
     return dsts
 
 
+def advect_scalar_multi(grid: IndexGridHandle, u, srcs: Sequence, dsts: Sequence, dt: float, inv_dx: float, sdf=None, has_collision: bool = False):
+    """advect_scalar of every field of `srcs` with one back-trace (``hns_dev_advect_scalar_multi``): dsts[i] is bit-identical to ``advect_scalar`` of srcs[i]."""
+    n = len(srcs)
+    ins = (C.c_void_p * max(1, n))(*[_ptr(t) for t in srcs])
+    outs = (C.c_void_p * max(1, n))(*[_ptr(t) for t in dsts])
+    _raise(lib.hns_dev_advect_scalar_multi(grid.ptr, _ptr(u), ins, outs, n, _ptr(sdf), int(has_collision), dt, inv_dx, current_stream()))
+    return dsts
+
+
 def advect_scalars_ahead(grid: IndexGridHandle, u, srcs: Sequence, dsts: Sequence, adv_out, dt: float, inv_dx: float):
     """advect_scalars over `srcs` and advect_vector(u) into `adv_out`, one launch (``hns_dev_advect_scalars_ahead``)."""
     n = len(srcs)
@@ -234,6 +243,15 @@ class Sim:
 
     def core_substep(self, iterations: int, dt: float, voxel_size: float, stream: int = 0) -> None:
         _raise(lib.hns_sim_core_substep(self._ptr, iterations, dt, voxel_size, stream))
+
+    def advect(self, names: Optional[Sequence[str]] = None, velocity: bool = False, *, dt: float, voxel_size: float, stream: int = 0) -> None:
+        """AdvectIndexGrid over the float fields `names` (None: all of them) with the current velocity, then, with `velocity`, AdvectIndexGridVelocity
+        (``hns_sim_advect``). Asynchronous on `stream`; an unknown or repeated name is refused with nothing changed."""
+        if names is None:
+            _raise(lib.hns_sim_advect(self._ptr, None, -1, int(velocity), dt, voxel_size, stream))
+            return
+        arr = (C.c_char_p * max(1, len(names)))(*[n.encode() for n in names])
+        _raise(lib.hns_sim_advect(self._ptr, arr, len(names), int(velocity), dt, voxel_size, stream))
 
     def pressure_solve(self, iterations: int, voxel_size: float, stream: int = 0) -> None:
         _raise(lib.hns_sim_pressure_solve(self._ptr, iterations, voxel_size, stream))

@@ -237,7 +237,8 @@ int hns_compute_sim(hns_grid*, hns_field* fields, int n_fields, int iterations, 
  * Results are bit-identical to hns_compute_sim whenever the promise holds. */
 int hns_compute_sim_resident(hns_grid*, hns_field* fields, int n_fields, const unsigned char* resident, int* uploads_skipped, int iterations, float dt,
                              float voxel_size, const hns_combustion_params* params, int has_collision, void* stream);
-/* AdvectIndexGrid: every float field through the single-field BFECC kernel (advect_scalar), no collision. */
+/* AdvectIndexGrid: every float field through the single-field BFECC arithmetic (advect_scalar), no collision; the fields share one back-trace
+ * (hns_dev_advect_scalar_multi), bit-identical to one advect_scalar launch per field. */
 int hns_advect_index_grid(hns_grid*, hns_field* fields, int n_fields, float dt, float voxel_size, void* stream);
 /* AdvectIndexGridVelocity: BFECC self-advection of the one Vec3f field. */
 int hns_advect_index_grid_velocity(hns_grid*, hns_field* fields, int n_fields, float dt, float voxel_size, void* stream);
@@ -262,6 +263,13 @@ int hns_sim_substep(hns_sim*, int iterations, float dt, float voxel_size, const 
 /* The metric's core substep: advect_vector -> divergence -> iterations x RB-SOR -> gradient subtraction ->
  * advect_scalars over every float field (SURVEY.md 8d "core substep"); asynchronous on `stream`. */
 int hns_sim_core_substep(hns_sim*, int iterations, float dt, float voxel_size, void* stream);
+/* AdvectIndexGrid and AdvectIndexGridVelocity on the device (Advection.cu:76-91,148-155; no collision): the named float fields (n_names = -1: every
+ * float field) through hns_dev_advect_scalar_multi with the sim's CURRENT velocity; then, with advect_velocity != 0, the velocity through
+ * hns_dev_advect_vector -- so the fields see the velocity before its self-advection, the order in which the two operators chain. Bit-identical to
+ * hns_advect_index_grid over those fields followed by hns_advect_index_grid_velocity. Asynchronous on `stream`, no device allocation. What a substep
+ * looked ahead (below) is dropped, as by every call that rewrites a field. Refused before anything is launched (HNS_ERR_INVALID_ARGUMENT): a name the sim lacks, a name listed
+ * twice, a null name or list, n_names < -1, a negative dt, a voxel size <= 0, a sim lent to a grid's cook cache. */
+int hns_sim_advect(hns_sim*, const char* const* names, int n_names, int advect_velocity, float dt, float voxel_size, void* stream);
 /* Only the pressure hot loop on the sim's divergence/pressure buffers (pressure zeroed first); asynchronous. */
 int hns_sim_pressure_solve(hns_sim*, int iterations, float voxel_size, void* stream);
 /* hipEvent timing of the pressure hot loop on its launch stream: after hns_sim_timing(sim, max_solves) every pressure
@@ -458,6 +466,13 @@ int hns_dev_advect_scalar(hns_grid*, const float* vel3, const float* in, float* 
 /* advect_scalars (Kernel.cu:118-266); in/out are HOST arrays of n device pointers */
 int hns_dev_advect_scalars(hns_grid*, const float* vel3, const float* const* in, float* const* out, int n, const float* sdf, int has_collision,
                            float dt, float inv_dx, void* stream);
+/* advect_scalar over n >= 0 fields with ONE back-trace (in/out: HOST arrays of n device pointers): output i is bit-identical to hns_dev_advect_scalar of
+ * field i with these arguments, whatever the options. Where the 32-bit addressed kernels apply (no collision field, a Vec3f field below 4 GiB, option
+ * "advect" = auto) eight fields share a launch and with it the own-velocity load, the neighbour tables, both sets of tap offsets and the velocity gathers;
+ * elsewhere one advect_scalar launch per field. Refused before anything is launched (HNS_ERR_INVALID_ARGUMENT, the first offending field's index in the
+ * message): a null pointer, an out[i] equal to any in[j] or to vel3, two equal out pointers. The same in listed twice is allowed. */
+int hns_dev_advect_scalar_multi(hns_grid*, const float* vel3, const float* const* in, float* const* out, int n, const float* sdf, int has_collision,
+                                float dt, float inv_dx, void* stream);
 /* advect_scalars over n <= 8 fields without a collision field AND advect_vector(vel3) into adv_out3 (not aliasing vel3), one launch: every output is
  * bit-identical to hns_dev_advect_scalars followed by hns_dev_advect_vector with these arguments. Applies where the 32-bit addressed kernels do
  * (a Vec3f field below 4 GiB, option "advect" = auto); HNS_ERR_INVALID_ARGUMENT elsewhere. */
