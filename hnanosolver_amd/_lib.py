@@ -130,6 +130,7 @@ SIGNATURES = {
     "hns_sim_stage_timing": (_i, [_vp, _i]),
     "hns_sim_stage_times": (_i, [_vp, C.POINTER(C.c_float), C.POINTER(C.c_longlong)]),
     "hns_sim_lookahead_counts": (_i, [_vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
+    "hns_sim_substep_plan": (_i, [_vp, C.POINTER(hns_combustion_params), _i, C.c_char_p, C.c_uint64]),
     "hns_sim_velocity_ptr": (_vp, [_vp]),
     "hns_sim_field_ptr": (_vp, [_vp, C.c_char_p]),
     "hns_sim_divergence_ptr": (_vp, [_vp]),

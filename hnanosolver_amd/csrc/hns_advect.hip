@@ -409,8 +409,49 @@ __device__ __forceinline__ f3 sample_velocity(const GridDev& g, const NarrowCtx&
 	return tri_v_b(ru, make_taps_b(g, C, sx, sy, sz));
 }
 
-// 32-bit addressed form (no collision field): same loads and arithmetic as the generic kernel below
-__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_advect_vector_n(const GridDev g, const float* __restrict__ u, float* __restrict__ out, const float scaled_dt) {
+// ---- the collision SDF of the leaf and one voxel around it, a fourth box (k_advect_vector_n<true>, k_advect_scalars_n<.., .., true>) -------------------------
+// With a collider every trial position is tested against the SDF first (its nested-lerp sample < 0: Kernel.cu:142-155, 211-214, 377-382, 390-394) and advect_vector blends
+// the result by the voxel's own SDF value and the gradient over its six face neighbours (:433-450). All of those lie in the box wherever the velocity sample itself does, so the
+// kernels stage the SDF as they stage the velocity: own value per thread, shell by the first 488 threads, through a descriptor of the float field with the UNMAPPED shell offsets --
+// a cell outside the domain holds 0, as IndexSampler<float, 1> (ldz in tri_f_t) and sdf_normal (ld0) read it. Same values, same arithmetic as the generic kernels: bit-identical.
+__device__ __forceinline__ float sdf_box_load(float* s_sdf, const v4i& rs, int n, int ob, float own, unsigned off) {
+	s_sdf[ob] = own;
+	float h = 0.0f;
+	if (n < kBoxShell) h = lds1(rs, off);
+	return h;
+}
+__device__ __forceinline__ void sdf_box_store(float* s_sdf, int n, int cell, float h) {
+	if (n < kBoxShell) s_sdf[cell] = h;
+}
+// IndexSampler<float,1> over a box (a = cell of the lower corner): tri_f_b's arithmetic
+template <int XS, int YS>
+__device__ __forceinline__ float tri_f_box(const float* s_f, int a, float fx, float fy, float fz) {
+	float c[8];
+#pragma unroll
+	for (int q = 0; q < 8; ++q) c[q] = s_f[a + box_corner<XS, YS>(tap_of(q))];
+	return tri_nest(c, fx, fy, fz, lerp_f);
+}
+// advect_vector's epilogue with a collider (Kernel.cu:433-450) for the voxel at box cell ob. (sv < 0 is false for -0 and NaN, sv < 0.1 false for NaN: in this order)
+template <int XS, int YS>
+__device__ __forceinline__ f3 collide_velocity(const float* s_sdf, int ob, f3 vc, float inv_dx) {
+	const float sv = s_sdf[ob];
+	if (sv < 0.0f) {
+		vc.x = vc.y = vc.z = 0.0f;
+	} else if (sv < 0.1f) {
+		float nb[6];
+#pragma unroll
+		for (int d = 0; d < 6; ++d) nb[d] = s_sdf[ob + box_nbr<XS, YS>(d)];
+		vc = no_slip_blend(vc, sdf_normal_of(nb, inv_dx), 1.0f - (sv / 1.5f));
+	}
+	return vc;
+}
+
+// 32-bit addressed form: same loads and arithmetic as the generic kernel below. COLL: with a collision SDF (rows of its box kVY apart, as the velocity's, so one cell number
+// serves both). The test is per lane; where it sends a lane back -- pass 0 to the voxel's own position, pass 1 to the (possibly reset) back position -- the wave samples again at
+// the positions it then has, a full eight-tap sample also where the weights are 0 (0 x inf = NaN, in the reference as here).
+template <bool COLL>
+__device__ __forceinline__ void advect_vector_n(const GridDev& g, const float* __restrict__ u, float* __restrict__ out, const float* __restrict__ sdf, float* s_sdf, const float scaled_dt,
+                                                const float inv_dx) {
 	__shared__ NarrowTabs tabs;
 	__shared__ float s_box[3 * kVP];
 	// the voxel's own velocity needs the leaf number only: its load is issued before the neighbour table is fetched and staged (one memory
@@ -418,25 +459,67 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
 	NarrowCtx C(g, tabs);
 	const v4i ru = field_rsrc(u, (unsigned)g.n_leaves * 6144u);
 	const f3 vo = ldv(ru, (unsigned)C.idx << 2);
+	v4i rs = {0, 0, 0, 0};
+	float so = 0.0f;
+	if constexpr (COLL) {
+		rs = field_rsrc(sdf, (unsigned)g.n_leaves * 2048u);
+		so = lds1(rs, (unsigned)C.idx << 2);
+	}
 	C.stage(g);
 	int cell;
 	const unsigned off = box_shell_off<kVX, kVY>(tabs.b4, C.n, cell);
-	velocity_box_store<kVP>(s_box, C.n, cell, velocity_box_load<kVX, kVY, kVP>(s_box, ru, C.n, vo, off));
+	const int ob = box_own<kVX, kVY>(C.n);
+	const f3 hv = velocity_box_load<kVX, kVY, kVP>(s_box, ru, C.n, vo, off);
+	if constexpr (COLL) sdf_box_store(s_sdf, C.n, cell, sdf_box_load(s_sdf, rs, C.n, ob, so, off));
+	velocity_box_store<kVP>(s_box, C.n, cell, hv);
 	float sx = C.px - scaled_dt * vo.x, sy = C.py - scaled_dt * vo.y, sz = C.pz - scaled_dt * vo.z;  // backPos (Kernel.cu:374)
+	float rx = C.px, ry = C.py, rz = C.pz;                                                            // COLL: where a collision sends the trace back to
 	f3 vf = {0.0f, 0.0f, 0.0f}, vb = {0.0f, 0.0f, 0.0f};
 	__syncthreads();  // box complete
 #pragma unroll 1
 	for (int pass = 0; pass < 2; ++pass) {
-		const f3 v = sample_velocity(g, C, ru, s_box, sx, sy, sz);
+		f3 v;
+		if constexpr (COLL) {  // Kernel.cu:377-382 / :390-394
+			const int i = __float2int_rd(sx), j = __float2int_rd(sy), k = __float2int_rd(sz);
+			const unsigned cx = (unsigned)(i - (C.org.x - 1)), cy = (unsigned)(j - (C.org.y - 1)), cz = (unsigned)(k - (C.org.z - 1));
+			const bool boxed = __all(max(cx, max(cy, cz)) <= 8u);  // per wave, as sample_velocity
+			const int a = (int)(cx * (unsigned)kVX + cy * (unsigned)kVY + cz);
+			float d;
+			if (boxed)
+				d = tri_f_box<kVX, kVY>(s_sdf, a, sx - (float)i, sy - (float)j, sz - (float)k);
+			else  // (sample_velocity builds these taps again for a lane that stays: held across the SDF gathers for it, their eight offsets take the kernel from 58 registers to 64 and three spills)
+				d = tri_f_b(rs, make_taps_b(g, C, sx, sy, sz));
+			if (d < 0.0f) sx = rx, sy = ry, sz = rz;
+			v = sample_velocity(g, C, ru, s_box, sx, sy, sz);
+		} else {
+			v = sample_velocity(g, C, ru, s_box, sx, sy, sz);
+		}
 		if (pass == 0) {
 			vf = v;
+			if constexpr (COLL) rx = sx, ry = sy, rz = sz;  // fwdPos2 falls back to backPos
 			sx = sx + scaled_dt * v.x, sy = sy + scaled_dt * v.y, sz = sz + scaled_dt * v.z;  // Kernel.cu:387
 		} else {
 			vb = v;
 		}
 	}
-	const int ob = box_own<kVX, kVY>(C.n);
-	st3(out, C.idx, bfecc_limit_v(vo, vf, vb, [&](int d) { return box_f3(s_box, ob + box_nbr<kVX, kVY>(d)); }));
+	f3 vc = bfecc_limit_v(vo, vf, vb, [&](int d) { return box_f3(s_box, ob + box_nbr<kVX, kVY>(d)); });
+	if constexpr (COLL) vc = collide_velocity<kVX, kVY>(s_sdf, ob, vc, inv_dx);
+	st3(out, C.idx, vc);
+}
+// Two kernels of ONE name: this one without a collision field, and below it the template that takes the SDF. The first keeps the symbol (and with it the registers and LDS that
+// tests/test_kernel_resources.py pins by symbol) it had before there was a second; a launch picks between them by its argument list.
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_advect_vector_n(const GridDev g, const float* __restrict__ u, float* __restrict__ out, const float scaled_dt) {
+	advect_vector_n<false>(g, u, out, nullptr, nullptr, scaled_dt, 0.0f);
+}
+// LDS: the velocity box, the SDF box and the tables. Four workgroups per CU (eight waves per SIMD) need a quarter of gfx950's 160 KB each.
+constexpr int kVectorCollLds = (3 * kVP + kVP) * 4 + (int)sizeof(NarrowTabs);
+static_assert(kVectorCollLds <= 160 * 1024 / 4, "k_advect_vector_n<true>: four workgroups per CU no longer fit the LDS");
+template <bool COLL>
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_advect_vector_n(const GridDev g, const float* __restrict__ u, float* __restrict__ out,
+                                                                                                const float* __restrict__ sdf, const float scaled_dt, const float inv_dx) {
+	static_assert(COLL, "without a collision field: the kernel of the same name that takes no SDF");
+	__shared__ float s_sdf[kVP];
+	advect_vector_n<true>(g, u, out, sdf, s_sdf, scaled_dt, inv_dx);
 }
 
 template <bool COLL>
@@ -677,10 +760,25 @@ __device__ __forceinline__ bool sample_setup(const GridDev& g, const NarrowCtx& 
 // while the fields are advected, and BEHIND the per-field loop the vector half takes its second sample from a velocity box (rows kVY apart, as k_advect_vector_n), clamps and stores.
 // That order is the one that fits 80 registers without a spill (70; the vector half in front of the loop: 100, profiles/lookahead_ab.txt): three workgroups per CU, by registers and by
 // LDS (43 KB) alike. Same loads of the same values, same arithmetic in the same association as k_advect_vector_n and k_advect_scalars_n<false>: bit-identical to the two launches.
-template <bool Q4, bool AHEAD = false>
-__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(Q4 || AHEAD ? 6 : 4))) void k_advect_scalars_n(const GridDev g, const float* __restrict__ u, const ScalarPtrs P, const float scaled_dt,
-                                                                                                            float* __restrict__ adv_out) {
+// COLL: with a collision SDF, staged as a fourth box (see sdf_box_load; 0 outside the domain, unlike the field boxes of this kernel). The back position is tested before its
+// sample is set up and falls back to the voxel's own position (Kernel.cu:142-155; the reference makes that test twice, and the repeat cannot change the outcome), the forward
+// position before the second set-up and falls back to the back position (:211-214). Per lane. The fields' arithmetic is untouched.
+// The SDF at (x, y, z) < 0 ? -- out of the leaf's SDF box (rows 10 apart) where the cell and cell + 1 lie inside it, else gathered
+__device__ __forceinline__ bool sdf_hit(const GridDev& g, const NarrowCtx& C, const v4i& rs, const float* s_sdf, float x, float y, float z) {
+	const int i = __float2int_rd(x), j = __float2int_rd(y), k = __float2int_rd(z);
+	const unsigned rx = (unsigned)(i - (C.org.x - 1)), ry = (unsigned)(j - (C.org.y - 1)), rz = (unsigned)(k - (C.org.z - 1));
+	float d;
+	if (max(rx, max(ry, rz)) <= 8u)
+		d = tri_f_box<100, 10>(s_sdf, (int)((rx * 10u + ry) * 10u + rz), x - (float)i, y - (float)j, z - (float)k);
+	else  // (sample_setup builds these taps again for a lane that stays: kept for it across the SDF gathers, they spill the q4 form at its 80 registers -- 132 bytes of scratch a lane -- and cost the float form eight)
+		d = tri_f_b(rs, make_taps_b(g, C, x, y, z));
+	return d < 0.0f;
+}
+template <bool Q4, bool AHEAD, bool COLL>
+__device__ __forceinline__ void advect_scalars_n(const GridDev& g, const float* __restrict__ u, const ScalarPtrs& P, const float scaled_dt, float* __restrict__ adv_out,
+                                                 const float* __restrict__ sdf) {
 	static_assert(!(Q4 && AHEAD), "the look-ahead form is float-only");
+	static_assert(!(AHEAD && COLL), "with a collider the next substep rewrites the velocity before it advects it: nothing to look ahead to");
 	__shared__ NarrowTabs tabs;
 	NarrowCtx C(g, tabs);
 	const int n = C.n, idx = C.idx;
@@ -688,12 +786,20 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(Q4 || AHEAD
 	const v4i ru = field_rsrc(u, bytes1 * 3u);
 	const unsigned own = (unsigned)idx << 2, oob4 = (unsigned)g.oob << 2;
 	const f3 vc = ldv(ru, own);  // (issued before the neighbour table is staged: see k_advect_vector_n)
+	v4i rs = {0, 0, 0, 0};
+	float so = 0.0f;
+	if constexpr (COLL) {
+		rs = field_rsrc(sdf, bytes1);
+		so = lds1(rs, own);
+	}
 	C.stage(g);
 
 	// the leaf and one voxel around it through LDS (see k_advect_vector_n): the velocity once, then per field; shell cell of this thread (the first 488) and where its value lies
 	const int ob = box_own(n);
 	int hcell;
 	unsigned ho = box_shell_off(tabs.b4, n, hcell);
+	__shared__ float s_sdf[COLL ? kBox : 1];
+	if constexpr (COLL) sdf_box_store(s_sdf, n, hcell, sdf_box_load(s_sdf, rs, n, ob, so, ho));  // (the unmapped offset: 0 outside the domain)
 	ho = ho >= kOutside ? oob4 : ho;  // out-of-domain neighbours read element g.oob here (Kernel.cu:225)
 	// FIRST: the first sample's taps out of the boxes too (below). Measured (profiles/r06_advect_box_ab.txt): it pays in the q4 form, which then fits 80 registers = six waves per SIMD,
 	// and costs the float-only form a fifth (one more 12-byte gather per thread for the velocity shell, and a barrier in front of its first gathers)
@@ -701,7 +807,14 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(Q4 || AHEAD
 	__shared__ float s_ubox[FIRST ? 3 * kBox : 1];
 	if constexpr (FIRST) velocity_box_store<kBox>(s_ubox, n, hcell, velocity_box_load<100, 10, kBox>(s_ubox, ru, n, vc, ho));
 
-	const float bx = C.px - scaled_dt * vc.x, by = C.py - scaled_dt * vc.y, bz = C.pz - scaled_dt * vc.z;
+	float bx = C.px - scaled_dt * vc.x, by = C.py - scaled_dt * vc.y, bz = C.pz - scaled_dt * vc.z;
+	__shared__ float s_back[COLL && FIRST ? 3 * 512 : 1];
+	if constexpr (COLL) {
+		__syncthreads();  // SDF box complete (and the velocity box, FIRST)
+		if (sdf_hit(g, C, rs, s_sdf, bx, by, bz)) bx = C.px, by = C.py, bz = C.pz;
+		if constexpr (FIRST) s_back[n] = bx, s_back[n + 512] = by, s_back[n + 1024] = bz;  // (read back by this thread alone)
+		asm volatile("" : "+v"(bx), "+v"(by), "+v"(bz));  // (the sample's set-up starts from the position, not from what the test kept of it)
+	}
 	unsigned bo[8], fo[8];
 	float bw[8], fw[8];
 	bool bboxed = false;  // the back sample's taps come out of the boxes (FIRST only)
@@ -750,7 +863,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(Q4 || AHEAD
 #pragma unroll
 			for (int q = 0; q < 8; ++q) vt[q] = ldv(ru, bo[q]);
 		}
-		if constexpr (FIRST) __syncthreads();  // velocity box complete
+		if constexpr (FIRST && !COLL) __syncthreads();  // velocity box complete
 		if (bboxed) {
 #pragma unroll
 			for (int q = 0; q < 8; ++q) {
@@ -764,7 +877,29 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(Q4 || AHEAD
 	// The second sample point is the voxel's own position up to s * (u(back) - u(own)): where it lands inside the leaf's 10^3 box (k_advect_vector_n, which see)
 	// the fields' forward taps are read from the LDS box that the clamp needs anyway, not gathered
 	int fa;  // box cell of the forward cell's lower corner
-	const bool boxed = sample_setup<true>(g, C, bx + scaled_dt * vf.x, by + scaled_dt * vf.y, bz + scaled_dt * vf.z, oob4, fa, fo, fw);
+	float fx = bx + scaled_dt * vf.x, fy = by + scaled_dt * vf.y, fz = bz + scaled_dt * vf.z;
+	if constexpr (COLL) {
+		if (sdf_hit(g, C, rs, s_sdf, fx, fy, fz)) {
+			if constexpr (FIRST) {
+				// (the back position waits in LDS, not in three registers across the velocity sample and this test: the q4 form sits on the 80-register line and spilled two with them)
+				int m = n;
+				asm volatile("" : "+v"(m));
+				fx = s_back[m], fy = s_back[m + 512], fz = s_back[m + 1024];
+			} else {
+				fx = bx, fy = by, fz = bz;
+			}
+		}
+	}
+	const bool boxed = sample_setup<true>(g, C, fx, fy, fz, oob4, fa, fo, fw);
+	// COLL and Q4: a sample has a box cell or tap offsets, never both, so from here on the cell rides in the first offset's register (the q4 form sits on the 80-register
+	// line, and with the tests in front of its set-ups it spilled the back cell)
+	constexpr bool SHARE = COLL && Q4;
+	if constexpr (SHARE) {
+		if (bboxed) bo[0] = (unsigned)ba;
+		if (boxed) fo[0] = (unsigned)fa;
+		asm volatile("" : "+v"(bo[0]), "+v"(fo[0]));
+	}
+	const int bcell = SHARE ? (int)bo[0] : ba, fcell = SHARE ? (int)fo[0] : fa;
 	// per field one own value per thread and one shell value per thread of the first 488; two boxes alternate so that one barrier per field suffices
 	__shared__ float s_box[2][kBox];
 	if constexpr (Q4) {
@@ -791,11 +926,11 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(Q4 || AHEAD
 		__syncthreads();
 		if (bboxed) {
 #pragma unroll
-			for (int q = 0; q < 8; ++q) phiF = __builtin_elementwise_fma(s_box4[ba + box_corner(q)], v4f32{bw[q], bw[q], bw[q], bw[q]}, phiF);
+			for (int q = 0; q < 8; ++q) phiF = __builtin_elementwise_fma(s_box4[bcell + box_corner(q)], v4f32{bw[q], bw[q], bw[q], bw[q]}, phiF);
 		}
 		if (boxed) {
 #pragma unroll
-			for (int q = 0; q < 8; ++q) phiB = __builtin_elementwise_fma(s_box4[fa + box_corner(q)], v4f32{fw[q], fw[q], fw[q], fw[q]}, phiB);
+			for (int q = 0; q < 8; ++q) phiB = __builtin_elementwise_fma(s_box4[fcell + box_corner(q)], v4f32{fw[q], fw[q], fw[q], fw[q]}, phiB);
 		}
 		v4f32 nv[6];
 #pragma unroll
@@ -822,13 +957,13 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(Q4 || AHEAD
 		__syncthreads();
 		if (bboxed) {
 #pragma unroll
-			for (int q = 0; q < 8; ++q) vb[q] = box[ba + box_corner(q)];
+			for (int q = 0; q < 8; ++q) vb[q] = box[bcell + box_corner(q)];
 		}
 #pragma unroll
 		for (int q = 0; q < 8; ++q) phiF = __fmaf_rn(vb[q], bw[q], phiF);
 		if (boxed) {
 #pragma unroll
-			for (int q = 0; q < 8; ++q) vf8[q] = box[fa + box_corner(q)];
+			for (int q = 0; q < 8; ++q) vf8[q] = box[fcell + box_corner(q)];
 		}
 #pragma unroll
 		for (int q = 0; q < 8; ++q) phiB = __fmaf_rn(vf8[q], fw[q], phiB);
@@ -851,6 +986,23 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(Q4 || AHEAD
 		const f3 wb = sample_velocity(g, C, ru, s_vbox, cx + scaled_dt * wf.x, cy + scaled_dt * wf.y, cz + scaled_dt * wf.z);  // Kernel.cu:387
 		st3(adv_out, idx, bfecc_limit_v(vo, wf, wb, [&](int d) { return box_f3(s_vbox, obv + box_nbr<kVX, kVY>(d)); }));
 	}
+}
+
+// Two templates of ONE name, as k_advect_vector_n: <Q4, AHEAD> without a collision field, under the symbols the resource tests pin, and <Q4, false, true> below, which takes the SDF.
+template <bool Q4, bool AHEAD = false>
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(Q4 || AHEAD ? 6 : 4))) void k_advect_scalars_n(const GridDev g, const float* __restrict__ u, const ScalarPtrs P, const float scaled_dt,
+                                                                                                            float* __restrict__ adv_out) {
+	advect_scalars_n<Q4, AHEAD, false>(g, u, P, scaled_dt, adv_out, nullptr);
+}
+// LDS of the q4 form with a collider: the tables, the velocity box, two float boxes, the 16-byte box, the SDF box and the back positions. Three workgroups per CU (six waves per SIMD) need a
+// third of gfx950's 160 KB each.
+constexpr int kScalarsQ4CollLds = (int)sizeof(NarrowTabs) + (3 * kBox + 2 * kBox + 4 * kBox + kBox + 3 * 512) * 4;
+static_assert(kScalarsQ4CollLds <= 160 * 1024 / 3, "k_advect_scalars_n<true, false, true>: three workgroups per CU no longer fit the LDS");
+template <bool Q4, bool AHEAD, bool COLL>
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(Q4 ? 6 : 4))) void k_advect_scalars_n(const GridDev g, const float* __restrict__ u, const ScalarPtrs P, const float* __restrict__ sdf,
+                                                                                                   const float scaled_dt) {
+	static_assert(COLL && !AHEAD, "without a collision field: the kernel of the same name that takes no SDF");
+	advect_scalars_n<Q4, false, true>(g, u, P, scaled_dt, nullptr, sdf);
 }
 
 template <bool COLL>
@@ -915,10 +1067,30 @@ static bool narrow_fields(const hns_grid* g) {
 	return !options().advect_generic.load() && (uint64_t)g->topo.n_leaves * 6144u <= hns::kNarrowBytes;
 }
 
-// which of an operator's three kernels a call gets: the generic one with its collision branch, the 32-bit addressed one, or the generic one
-enum class AdvectForm { collision, narrow, generic };
+// which of an operator's four kernels a call gets: the generic one with its collision branch, the 32-bit addressed one with its collision branch (advect_vector and
+// advect_scalars; option "collide" = generic sends those to the generic one, as before they existed), the 32-bit addressed one, or the generic one.
+// A null SDF is a call without a collider whatever has_collision says.
+enum class AdvectForm { collision, narrow_collision, narrow, generic };
 static AdvectForm advect_form(const hns_grid* g, const float* sdf, int has_collision) {
-	return has_collision && sdf ? AdvectForm::collision : (narrow_fields(g) ? AdvectForm::narrow : AdvectForm::generic);
+	if (has_collision && sdf) return narrow_fields(g) && !options().collide_generic.load() ? AdvectForm::narrow_collision : AdvectForm::collision;
+	return narrow_fields(g) ? AdvectForm::narrow : AdvectForm::generic;
+}
+// the source names of the kernels a form launches (hns_sim_substep_plan)
+static const char* advect_vector_kernel(AdvectForm f) {
+	switch (f) {
+	case AdvectForm::collision: return "k_advect_vector<true>";
+	case AdvectForm::narrow_collision: return "k_advect_vector_n<coll>";
+	case AdvectForm::narrow: return "k_advect_vector_n";
+	default: return "k_advect_vector<false>";
+	}
+}
+static const char* advect_scalars_kernel(AdvectForm f) {
+	switch (f) {
+	case AdvectForm::collision: return "k_advect_scalars<true>";
+	case AdvectForm::narrow_collision: return "k_advect_scalars_n<coll>";
+	case AdvectForm::narrow: return "k_advect_scalars_n";
+	default: return "k_advect_scalars<false>";
+	}
 }
 
 // The launch tables of the advect_scalars kernels in the 32-bit form: leaves backwards. The gradient kernel has just written the velocity front to back; starting on its
@@ -953,6 +1125,8 @@ int hns_dev_advect_vector(hns_grid* g, const float* vel3, float* out3, const flo
 	const dim3 grid((unsigned)g->n_active), block(512);
 	switch (advect_form(g, sdf, has_collision)) {
 	case AdvectForm::collision: hipLaunchKernelGGL(k_advect_vector<true>, grid, block, 0, (hipStream_t)stream, g->dev(), vel3, out3, sdf, scaled_dt, inv_dx); break;
+	// (k_advect_vector_n is overloaded: <true> names the template with the SDF, the bare name two lines on the kernel without -- see at their definitions)
+	case AdvectForm::narrow_collision: hipLaunchKernelGGL(k_advect_vector_n<true>, grid, block, 0, (hipStream_t)stream, g->dev(), vel3, out3, sdf, scaled_dt, inv_dx); break;
 	case AdvectForm::narrow: hipLaunchKernelGGL(k_advect_vector_n, grid, block, 0, (hipStream_t)stream, g->dev(), vel3, out3, scaled_dt); break;
 	case AdvectForm::generic: hipLaunchKernelGGL(k_advect_vector<false>, grid, block, 0, (hipStream_t)stream, g->dev(), vel3, out3, sdf, scaled_dt, inv_dx); break;
 	}
@@ -967,6 +1141,7 @@ int hns_dev_advect_scalar(hns_grid* g, const float* vel3, const float* in, float
 	const float scaled_dt = dt * inv_dx;
 	const dim3 grid((unsigned)g->n_active), block(512);
 	switch (advect_form(g, sdf, has_collision)) {
+	case AdvectForm::narrow_collision:  // (no operator of the reference hands this kernel a collider: it keeps the generic form)
 	case AdvectForm::collision: hipLaunchKernelGGL(k_advect_scalar<true>, grid, block, 0, (hipStream_t)stream, g->dev(), vel3, in, out, sdf, scaled_dt); break;
 	case AdvectForm::narrow: hipLaunchKernelGGL(k_advect_scalar_n, grid, block, 0, (hipStream_t)stream, g->dev(), vel3, in, out, scaled_dt); break;
 	case AdvectForm::generic: hipLaunchKernelGGL(k_advect_scalar<false>, grid, block, 0, (hipStream_t)stream, g->dev(), vel3, in, out, sdf, scaled_dt); break;
@@ -991,6 +1166,8 @@ int hns_dev_advect_scalars(hns_grid* g, const float* vel3, const float* const* i
 		}
 		switch (advect_form(g, sdf, has_collision)) {
 		case AdvectForm::collision: hipLaunchKernelGGL(k_advect_scalars<true>, grid, block, 0, (hipStream_t)stream, g->dev(), vel3, P, sdf, scaled_dt); break;
+		// (k_advect_scalars_n is overloaded by its template arity: three flags name the form with the SDF, one or two the form without -- see at their definitions)
+		case AdvectForm::narrow_collision: hipLaunchKernelGGL((k_advect_scalars_n<false, false, true>), grid, block, 0, (hipStream_t)stream, reversed(g), vel3, P, sdf, scaled_dt); break;
 		case AdvectForm::narrow: hipLaunchKernelGGL(k_advect_scalars_n<false>, grid, block, 0, (hipStream_t)stream, reversed(g), vel3, P, scaled_dt, (float*)nullptr); break;
 		case AdvectForm::generic: hipLaunchKernelGGL(k_advect_scalars<false>, grid, block, 0, (hipStream_t)stream, g->dev(), vel3, P, sdf, scaled_dt); break;
 		}
@@ -1045,7 +1222,7 @@ int hns_dev_advect_scalar_multi(hns_grid* g, const float* vel3, const float* con
 		}
 	} else {
 		for (int i = 0; i < n; ++i) {
-			if (form == AdvectForm::collision)
+			if (form == AdvectForm::collision || form == AdvectForm::narrow_collision)  // (as hns_dev_advect_scalar)
 				hipLaunchKernelGGL(k_advect_scalar<true>, grid, block, 0, (hipStream_t)stream, g->dev(), vel3, in[i], out[i], sdf, scaled_dt);
 			else
 				hipLaunchKernelGGL(k_advect_scalar<false>, grid, block, 0, (hipStream_t)stream, g->dev(), vel3, in[i], out[i], sdf, scaled_dt);
@@ -1076,10 +1253,10 @@ int hns_dev_advect_scalars_ahead(hns_grid* g, const float* vel3, const float* co
 	return launch_status("hns_dev_advect_scalars_ahead");
 }
 
-// advect_scalars over the four fields of `q4` (one 16-byte element per voxel in, four float arrays out) and n more float fields, one launch (hns_sim_substep; no collision
-// field). Applies where hns_advect_q4_ok(g).
-int hns_advect_scalars_q4(hns_grid* g, const float* vel3, const float* q4, float* const* q4_out, const float* const* in, float* const* out, int n, float dt, float inv_dx,
-                          void* stream) {
+// advect_scalars over the four fields of `q4` (one 16-byte element per voxel in, four float arrays out) and n more float fields, one launch (hns_sim_substep). sdf: the
+// collision field, null = none. Applies where hns_advect_q4_ok(g).
+int hns_advect_scalars_q4(hns_grid* g, const float* vel3, const float* q4, float* const* q4_out, const float* const* in, float* const* out, int n, const float* sdf, float dt,
+                          float inv_dx, void* stream) {
 	if (int rc = check_grid(g, "hns_advect_scalars_q4")) return rc;
 	NULLCHK(!vel3 || !q4 || !q4_out || (n > 0 && (!in || !out)), "hns_advect_scalars_q4");
 	if (!hns_advect_q4_ok(g) || n > HNS_MAX_SCALARS) return fail(HNS_ERR_INVALID_ARGUMENT, "hns_advect_scalars_q4: grid too large for 32-bit offsets, or too many fields");
@@ -1089,9 +1266,18 @@ int hns_advect_scalars_q4(hns_grid* g, const float* vel3, const float* q4, float
 	NULLCHK(fill_scalar_ptrs(P, in, out, n) >= 0, "hns_advect_scalars_q4");
 	P.q4 = q4;
 	for (int c = 0; c < 4; ++c) P.q4_out[c] = q4_out[c];
-	hipLaunchKernelGGL(k_advect_scalars_n<true>, dim3((unsigned)g->n_active), dim3(512), 0, (hipStream_t)stream, reversed(g), vel3, P, dt * inv_dx, (float*)nullptr);
+	if (sdf)
+		hipLaunchKernelGGL((k_advect_scalars_n<true, false, true>), dim3((unsigned)g->n_active), dim3(512), 0, (hipStream_t)stream, reversed(g), vel3, P, sdf, dt * inv_dx);
+	else
+		hipLaunchKernelGGL(k_advect_scalars_n<true>, dim3((unsigned)g->n_active), dim3(512), 0, (hipStream_t)stream, reversed(g), vel3, P, dt * inv_dx, (float*)nullptr);
 	return launch_status("hns_advect_scalars_q4");
 }
+const char* hns_advect_scalars_q4_kernel(const float* sdf) { return sdf ? "k_advect_scalars_n<q4,coll>" : "k_advect_scalars_n<q4>"; }
+
+// the kernels hns_dev_advect_vector / hns_dev_advect_scalars / hns_dev_advect_scalars_ahead launch for these arguments (hns_sim_substep_plan)
+const char* hns_advect_vector_kernel(const hns_grid* g, const float* sdf, int has_collision) { return advect_vector_kernel(advect_form(g, sdf, has_collision)); }
+const char* hns_advect_scalars_kernel(const hns_grid* g, const float* sdf, int has_collision) { return advect_scalars_kernel(advect_form(g, sdf, has_collision)); }
+const char* hns_advect_scalars_ahead_kernel(void) { return "k_advect_scalars_n<ahead>"; }
 
 // can this grid's fields take the q4 path (32-bit byte offsets into a 16-byte-per-voxel array)?
 bool hns_advect_q4_ok(const hns_grid* g) { return narrow_fields(g) && (uint64_t)g->topo.n_leaves * 8192u <= hns::kNarrowBytes; }

@@ -311,6 +311,9 @@ extern "C" int hns_sim_pressure_time(hns_sim* s, float* total_ms, long long* lau
 	return HNS_OK;
 }
 
+// can the advect_scalars launch of a substep over `fields` float fields also leave advect_vector in s->adv?
+static bool sim_ahead_applies(const hns_sim* s, bool coll, size_t fields) { return !coll && fields > 0 && fields <= 8 && hns_advect_ahead_ok(s->grid); }
+
 // *ahead (in): also leave advect_vector(s->vel, dt) in s->adv, where one launch can (out: it was done)
 static int sim_advect_scalars(hns_sim* s, const float* sdf, bool coll, float dt, float inv_dx, void* stream, bool* ahead) {
 	std::vector<const float*> ins;
@@ -322,7 +325,7 @@ static int sim_advect_scalars(hns_sim* s, const float* sdf, bool coll, float dt,
 		outs.push_back(s->nxt[i]);
 		which.push_back((int)i);
 	}
-	*ahead = *ahead && !coll && !ins.empty() && ins.size() <= 8 && hns_advect_ahead_ok(s->grid);
+	*ahead = *ahead && sim_ahead_applies(s, coll, ins.size());
 	if (*ahead)
 		HNS_TRY(hns_dev_advect_scalars_ahead(s->grid, s->vel, ins.data(), outs.data(), (int)ins.size(), s->adv, dt, inv_dx, stream));
 	else
@@ -341,7 +344,8 @@ static int sim_advect_scalars(hns_sim* s, const float* sdf, bool coll, float dt,
 // Round 6: without a collision field (and while a 16-byte-per-voxel array stays 32-bit addressable) part B opens with ONE launch for divergence + combustion +
 // buoyancy (hns_divergence_combust_buoyancy: 60 B/voxel instead of 16 + 40 + 28) that leaves the four combustion fields as one 16-byte element per voxel in s->q4, and
 // part C gathers those four from there (hns_advect_scalars_q4: a corner tap of the four is one gather, not four). Same expressions in the same order per voxel:
-// bit-identical to the separate launches, which remain the path with a collision field and the hns_dev_* entry points.
+// bit-identical to the separate launches, which remain the path of the hns_dev_* entry points. With a collision field the same (the fused launch reads no SDF; part C
+// launches the q4 form with its collision branch) unless option "collide" = generic, which keeps the separate launches and the 64-bit addressed advection kernels.
 // Look-ahead (option "lookahead"): advect_scalars of substep n and advect_vector of substep n + 1 read the same velocity -- s->vel after the gradient subtraction -- with the same
 // dt, and make the same backtrace: own velocity, neighbour tables, back position, eight tap offsets, eight 12-byte gathers. Where part C runs the float-only 32-bit form in one
 // launch and there is no collision field it launches the look-ahead form (hns_dev_advect_scalars_ahead), which leaves advect_vector(s->vel, dt) in s->adv (dead since the
@@ -370,7 +374,8 @@ struct Substep {
 		return HNS_OK;
 	}
 
-	int prepare(hns_sim* sim, int iters, float dt_, float vs, const hns_combustion_params* prm, int has_collision, void* st) {
+	// What a substep with these arguments does, decided from the sim as it stands; changes nothing (hns_sim_substep_plan stops here). `capturing`: its stream is being captured.
+	int decide(hns_sim* sim, int iters, float dt_, float vs, const hns_combustion_params* prm, int has_collision, void* st, bool capturing) {
 		s = sim;
 		iterations = iters;
 		dt = dt_;
@@ -378,16 +383,7 @@ struct Substep {
 		inv_dx = 1.0f / vs;
 		params = prm;
 		stream = st;
-		ahead_live = !s->ahead_off && options().lookahead.load() != kLookaheadOff;
-		if (ahead_live) {  // neither produce nor consume while the stream is captured: a replayed graph writes vel and adv unseen, so such a sim stops looking ahead for good
-			hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-			if (hipStreamIsCapturing((hipStream_t)stream, &cs) != hipSuccess) {
-				(void)hipGetLastError();
-				cs = hipStreamCaptureStatusActive;
-			}
-			if (cs != hipStreamCaptureStatusNone) ahead_live = false, s->ahead_off = true;
-		}
-		if (!ahead_live) s->drop_ahead();
+		ahead_live = !capturing && !s->ahead_off && options().lookahead.load() != kLookaheadOff;
 		if (!full()) return HNS_OK;
 		if (s->names.empty()) return fail(HNS_ERR_RUNTIME, "No float blocks found in input data.");  // :61-63
 		for (int c = 0; c < 4; ++c) {                                                                 // :193-201
@@ -403,23 +399,48 @@ struct Substep {
 		size_t advected = 0;
 		for (const std::string& n : s->names) advected += n != "collision_sdf";
 		// (every leaf active: the pointwise kernels of the separate path run over ALL voxels, read-only ghost leaves included, and advection taps read them there)
-		fused = !coll && s->q4 && s->grid->d_blk && s->grid->n_active == (uint64_t)s->grid->topo.n_leaves && !options().stencil_block.load() && hns_advect_q4_ok(s->grid) &&
+		fused = !(coll && options().collide_generic.load()) && s->q4 && s->grid->d_blk && s->grid->n_active == (uint64_t)s->grid->topo.n_leaves && !options().stencil_block.load() && hns_advect_q4_ok(s->grid) &&
 		        advected - 4 <= 8 && options().fuse_pointwise.load();
 		return HNS_OK;
+	}
+	// decide(), and what the decision does to the sim before the first launch
+	int prepare(hns_sim* sim, int iters, float dt_, float vs, const hns_combustion_params* prm, int has_collision, void* st) {
+		bool capturing = false;
+		if (!sim->ahead_off && options().lookahead.load() != kLookaheadOff) {  // neither produce nor consume while the stream is captured: a replayed graph writes vel and adv unseen, so such a sim stops looking ahead for good
+			hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+			if (hipStreamIsCapturing((hipStream_t)st, &cs) != hipSuccess) {
+				(void)hipGetLastError();
+				cs = hipStreamCaptureStatusActive;
+			}
+			if (cs != hipStreamCaptureStatusNone) capturing = true, sim->ahead_off = true;
+		}
+		const int rc = decide(sim, iters, dt_, vs, prm, has_collision, st, capturing);
+		if (!ahead_live) s->drop_ahead();
+		return rc;
+	}
+	// what part A, part C and hns_sim_substep_plan decide alike
+	bool memo() const {  // s->adv holds advect_vector(s->vel, dt) already (with a collider part A rewrites the velocity first: never)
+		const hns_grid* g = s->grid;
+		const hns_sim::Ahead& m = s->ahead;
+		return ahead_live && !coll && m.valid && m.grid == g && m.first == g->first_active && m.n_active == g->n_active && m.dt_bits == float_bits(dt) &&
+		       m.vs_bits == float_bits(voxel_size);
+	}
+	bool vorticity() const { return full() && (int)params->factorScale != 0; }
+	// speculate? lookahead = 1: always; auto: when the previous substep call on this sim had this dt and voxel size (a lone substep, or a changing dt, pays nothing)
+	bool speculate() const {
+		return ahead_live && !fused && (options().lookahead.load() == kLookaheadOn || (s->have_last && s->last_dt_bits == float_bits(dt) && s->last_vs_bits == float_bits(voxel_size)));
 	}
 	int part_a() {
 		hns_grid* g = s->grid;
 		HNS_TRY(mark(0));
-		const hns_sim::Ahead& m = s->ahead;
-		const bool memo = ahead_live && !coll && m.valid && m.grid == g && m.first == g->first_active && m.n_active == g->n_active && m.dt_bits == float_bits(dt) &&
-		                  m.vs_bits == float_bits(voxel_size);
+		const bool memo = this->memo();
 		s->drop_ahead();  // (from here on the substep overwrites adv, then vel)
 		if (coll) HNS_TRY(hns_dev_enforce_collision_boundaries(g, s->vel, sdf, voxel_size, stream));  // :153-157
 		if (memo)
 			++s->ahead_consumed;  // s->adv holds advect_vector(s->vel, dt) already: the previous substep's part C
 		else
 			HNS_TRY(hns_dev_advect_vector(g, s->vel, s->adv, sdf, coll, dt, inv_dx, stream));  // :162-170
-		if (full() && (int)params->factorScale != 0) {  // :172-176. With (int)factorScale == 0 every vorticity-magnitude tap collapses onto the centre, the
+		if (vorticity()) {  // :172-176. With (int)factorScale == 0 every vorticity-magnitude tap collapses onto the centre, the
 			// gradient is 0, N = 0/(0+1e-5) = 0 and the kernel writes u + dt*(scale*0) = u: a bit-exact copy, skipped.
 			HNS_TRY(hns_dev_vorticity_confinement(g, s->adv, s->tmp, dt, inv_dx,
 			                                      params->vorticityScale, params->factorScale, stream));
@@ -454,10 +475,9 @@ struct Substep {
 	}
 	int part_c() {  // :321-356
 		HNS_TRY(mark(4));
-		// speculate? lookahead = 1: always; auto: when the previous substep call on this sim had this dt and voxel size (a lone substep, or a changing dt, pays nothing)
 		const uint32_t dtb = float_bits(dt), vsb = float_bits(voxel_size);
-		bool ahead = ahead_live && !fused && (options().lookahead.load() == kLookaheadOn || (s->have_last && s->last_dt_bits == dtb && s->last_vs_bits == vsb));
-		s->have_last = true, s->last_dt_bits = dtb, s->last_vs_bits = vsb;
+		bool ahead = speculate();
+		s->have_last = true, s->last_dt_bits = dtb, s->last_vs_bits = vsb, s->last_iterations = iterations;
 		if (!fused) {
 			HNS_TRY(sim_advect_scalars(s, sdf, coll, dt, inv_dx, stream, &ahead));
 			if (ahead) {
@@ -475,13 +495,36 @@ struct Substep {
 			ins.push_back(s->cur[i]);
 			outs.push_back(s->nxt[i]);
 		}
-		HNS_TRY(hns_advect_scalars_q4(s->grid, s->vel, s->q4, q4_out, ins.data(), outs.data(), (int)ins.size(), dt, inv_dx, stream));
+		HNS_TRY(hns_advect_scalars_q4(s->grid, s->vel, s->q4, q4_out, ins.data(), outs.data(), (int)ins.size(), sdf, dt, inv_dx, stream));
 		for (size_t i = 0; i < s->names.size(); ++i)
 			if (s->names[i] != "collision_sdf") std::swap(s->cur[i], s->nxt[i]);
 		return HNS_OK;
 	}
 	// The whole substep on one stream. hns_sim_stage_timing brackets five stages, the same for the core and the full substep -- {collision + advect_vector + vorticity,
 	// divergence + combustion + buoyancy (one launch when fused), pressure loop, gradient subtraction + collision, advect_scalars}: mark(0..4) open them, mark(5) closes the last.
+	// hns_sim_substep_plan: the kernel each stage of run() launches, `stage=kernel` words; what decides is the code the parts run
+	std::string describe() const {
+		const hns_grid* g = s->grid;
+		size_t advected = 0;
+		for (const std::string& n : s->names) advected += n != "collision_sdf";
+		char sor[256];
+		if (hns_grid_rbgs_plan(s->grid, iterations, sor, sizeof(sor), nullptr, nullptr) != HNS_OK) sor[0] = 0;
+		std::string pressure(sor, strcspn(sor, ":"));
+		std::string out = std::string("collision=") + (coll ? "k_enforce_collision" : "-");
+		out += std::string(" advect_vector=") + (memo() ? "memo" : hns_advect_vector_kernel(g, sdf, coll));
+		out += std::string(" vorticity=") + (vorticity() ? "k_vorticity" : "-");
+		out += std::string(" divergence=") + hns_divergence_kernel(g, fused) + (!fused && full() ? "+k_combustion_oxygen+k_temperature_buoyancy" : "");
+		out += " pressure=" + (pressure.empty() ? std::string("-") : pressure);
+		out += std::string(" gradient=") + hns_subtract_gradient_kernel(g, sdf, coll);
+		out += " advect_scalars=";
+		if (fused)
+			out += hns_advect_scalars_q4_kernel(sdf);
+		else if (advected == 0)
+			out += "-";
+		else
+			out += speculate() && sim_ahead_applies(s, coll, advected) ? hns_advect_scalars_ahead_kernel() : hns_advect_scalars_kernel(g, sdf, coll);
+		return out;
+	}
 	int run() {
 		stage_events = s->stage_ev.current();
 		HNS_TRY(part_a());
@@ -508,6 +551,20 @@ extern "C" int hns_sim_substep(hns_sim* s, int iterations, float dt, float voxel
                                void* stream) {
 	if (!s || !params) return fail(HNS_ERR_INVALID_ARGUMENT, "hns_sim_substep: null argument");
 	return sim_substep(s, iterations, dt, voxel_size, params, has_collision, stream);
+}
+
+// Which kernel each stage of the next hns_sim_substep (params null: hns_sim_core_substep) with these arguments launches, as `stage=kernel` words; launches nothing and
+// leaves the sim as it is (Substep::decide, not prepare). The time step, the voxel size and the iteration count are taken to be those of the previous substep call on the sim
+// (the first two decide whether the look-ahead memo is consumed and produced; before the first call: one iteration, which a substep needs at the least), the stream to be
+// one that is not being captured (a captured substep neither consumes nor produces the memo).
+extern "C" int hns_sim_substep_plan(hns_sim* s, const hns_combustion_params* params, int has_collision, char* description, uint64_t description_bytes) {
+	if (!s) return fail(HNS_ERR_INVALID_ARGUMENT, "hns_sim_substep_plan: null sim");
+	float dt = 0.0f, vs = 0.0f;
+	if (s->have_last) memcpy(&dt, &s->last_dt_bits, 4), memcpy(&vs, &s->last_vs_bits, 4);
+	Substep step;
+	HNS_TRY(step.decide(s, s->have_last ? s->last_iterations : 1, dt, vs, params, params ? has_collision : 0, nullptr, false));
+	if (description && description_bytes) snprintf(description, description_bytes, "%s", s->n == 0 ? "" : step.describe().c_str());
+	return HNS_OK;
 }
 
 extern "C" int hns_sim_core_substep(hns_sim* s, int iterations, float dt, float voxel_size, void* stream) {

@@ -248,16 +248,10 @@ __device__ __forceinline__ LeafCtx stage_leaf(const GridDev& g, int* s_nbr, int 
 // collision helpers (reference Kernel.cu:8-74)
 // ---------------------------------------------------------------------------------------------------------------
 
-__device__ __forceinline__ f3 sdf_normal(const GridDev& g, const int* s_nbr, const int4 org, const float* __restrict__ sdf, int i, int j, int k,
-                                         float eps) {
-	const float right = ld0(sdf, tap_index(g, s_nbr, org, i + 1, j, k));
-	const float left = ld0(sdf, tap_index(g, s_nbr, org, i - 1, j, k));
-	const float top = ld0(sdf, tap_index(g, s_nbr, org, i, j + 1, k));
-	const float bottom = ld0(sdf, tap_index(g, s_nbr, org, i, j - 1, k));
-	const float front = ld0(sdf, tap_index(g, s_nbr, org, i, j, k + 1));
-	const float back = ld0(sdf, tap_index(g, s_nbr, org, i, j, k - 1));
+// the normalised central-difference gradient of the SDF from the six face neighbours' values nb[-x,+x,-y,+y,-z,+z] (0 outside the domain); eps = 1 / voxel size
+__device__ __forceinline__ f3 sdf_normal_of(const float (&nb)[6], float eps) {
 	const float s = 0.5f * eps;
-	f3 gr = {s * (right - left), s * (top - bottom), s * (front - back)};
+	f3 gr = {s * (nb[1] - nb[0]), s * (nb[3] - nb[2]), s * (nb[5] - nb[4])};
 	const float len = sqrtf(gr.x * gr.x + gr.y * gr.y + gr.z * gr.z);
 	if (len > 1e-6f) {
 		const float inv = 1.0f / len;
@@ -268,6 +262,18 @@ __device__ __forceinline__ f3 sdf_normal(const GridDev& g, const int* s_nbr, con
 		gr.x = gr.y = gr.z = 0.0f;
 	}
 	return gr;
+}
+
+__device__ __forceinline__ f3 sdf_normal(const GridDev& g, const int* s_nbr, const int4 org, const float* __restrict__ sdf, int i, int j, int k,
+                                         float eps) {
+	const float right = ld0(sdf, tap_index(g, s_nbr, org, i + 1, j, k));
+	const float left = ld0(sdf, tap_index(g, s_nbr, org, i - 1, j, k));
+	const float top = ld0(sdf, tap_index(g, s_nbr, org, i, j + 1, k));
+	const float bottom = ld0(sdf, tap_index(g, s_nbr, org, i, j - 1, k));
+	const float front = ld0(sdf, tap_index(g, s_nbr, org, i, j, k + 1));
+	const float back = ld0(sdf, tap_index(g, s_nbr, org, i, j, k - 1));
+	const float nb[6] = {left, right, bottom, top, back, front};
+	return sdf_normal_of(nb, eps);
 }
 
 __device__ __forceinline__ f3 no_slip_blend(f3 v, f3 n, float blend) {

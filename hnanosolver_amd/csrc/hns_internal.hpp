@@ -103,6 +103,7 @@ enum { kLookaheadAuto = 0, kLookaheadOff = 1, kLookaheadOn = 2 };
 struct Options {
 	std::atomic<int> rbgs{kRbgsAuto};          // "rbgs": auto | color (the reference's two launches per iteration: the independent cross-check)
 	std::atomic<int> advect_generic{0};        // "advect": auto | generic (64-bit addressed kernels)
+	std::atomic<int> collide_generic{0};       // "collide": auto | generic -- with a collision SDF advect_vector / advect_scalars run the 64-bit addressed kernels and hns_sim_substep does not fuse (the dispatch before the 32-bit collision forms: cross-check, A/B)
 	std::atomic<int> stencil_block{0};         // "stencil": auto | block (512-thread divergence / gradient)
 	std::atomic<int> schedule{kScheduleAuto};  // "schedule": auto | linear (read when launch tables are built)
 	std::atomic<int> cook_cache{1};            // "cook_cache": operator calls keep their device buffers with the grid
@@ -264,6 +265,7 @@ struct hns_sim {
 	bool ahead_off = false;     // for good: the velocity pointer was handed out, the sim is lent to operator calls, or a substep was captured into a graph
 	bool have_last = false;     // option lookahead = auto: dt and voxel size of the previous substep call
 	uint32_t last_dt_bits = 0, last_vs_bits = 0;
+	int last_iterations = 0;    // (hns_sim_substep_plan: the pressure stage of the previous call)
 	long long ahead_produced = 0, ahead_consumed = 0;  // hns_sim_lookahead_counts
 	void drop_ahead() { ahead.valid = false; }
 	void forget(int k = kEverything) {  // float field k, the velocity or everything: the buffer no longer holds what the caller was handed
@@ -341,7 +343,14 @@ extern "C" __attribute__((visibility("hidden"))) int hns_divergence_combust_buoy
                                                                                       const float* temperature, const float* flame, float* q4, float* vel3_out, float temp_gain,
                                                                                       float expansion, float dt, float ambient, float strength, void* stream);
 extern "C" __attribute__((visibility("hidden"))) int hns_advect_scalars_q4(hns_grid* g, const float* vel3, const float* q4, float* const* q4_out, const float* const* in,
-                                                                            float* const* out, int n, float dt, float inv_dx, void* stream);
+                                                                            float* const* out, int n, const float* sdf /* null: no collider */, float dt, float inv_dx, void* stream);
+// which kernel a launcher picks for these arguments, by the code that picks it for the launch (hns_sim_substep_plan)
+extern "C" __attribute__((visibility("hidden"))) const char* hns_advect_vector_kernel(const hns_grid* g, const float* sdf, int has_collision);
+extern "C" __attribute__((visibility("hidden"))) const char* hns_advect_scalars_kernel(const hns_grid* g, const float* sdf, int has_collision);
+extern "C" __attribute__((visibility("hidden"))) const char* hns_advect_scalars_q4_kernel(const float* sdf);
+extern "C" __attribute__((visibility("hidden"))) const char* hns_advect_scalars_ahead_kernel(void);
+extern "C" __attribute__((visibility("hidden"))) const char* hns_divergence_kernel(const hns_grid* g, bool fused);
+extern "C" __attribute__((visibility("hidden"))) const char* hns_subtract_gradient_kernel(const hns_grid* g, const float* sdf, int has_collision);
 extern "C" __attribute__((visibility("hidden"))) bool hns_advect_q4_ok(const hns_grid* g);
 extern "C" __attribute__((visibility("hidden"))) bool hns_advect_ahead_ok(const hns_grid* g);  // hns_advect.hip: does hns_dev_advect_scalars_ahead apply to this grid?
 

@@ -432,13 +432,51 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void k_
 
 using namespace hns;
 
+// which divergence kernel a grid gets, alone (hns_dev_divergence) or fused with combustion and buoyancy (hns_divergence_combust_buoyancy, which has no block form)
+enum class DivForm { block, zpair, coalesced, row };
+static DivForm divergence_form(const hns_grid* g, bool fused) {
+	if (!fused && (options().stencil_block.load() || !g->d_blk)) return DivForm::block;  // option "stencil" = block: A/B switch
+	// option "divergence" = auto | row | coalesced: by size (k_divergence_row's COAL form from 16k leaves; loses below, see the kernel)
+	const int form = options().divergence_form.load();
+	// auto, from 16,384 leaves (round 6): z-adjacent leaves in pairs, the coalesced form (256^3 63 -> 58 us, 512^3 467 -> 431, 66k-leaf plume 118 -> 112;
+	// below that size the pairing buys nothing and the coalesced form loses to the row form: profiles/r06_divergence_zpair_ab.txt). A range whose boundary leaves
+	// are dealt out first (a chained multi-GPU rank) keeps one leaf per workgroup.
+	if ((form == 3 || (form == 0 && g->n_active >= 16384)) && g->sched_pre == 0) return DivForm::zpair;
+	if (form == 2 || (form == 0 && g->n_active >= 16384)) return DivForm::coalesced;
+	return DivForm::row;
+}
+// which gradient kernel a call gets: the 512-thread one with its collision branch, the same without (option "stencil" = block: A/B switch), or the streaming one
+enum class GradForm { collision, block, stream };
+static GradForm gradient_form(const hns_grid* g, const float* sdf, int has_collision) {
+	if (has_collision && sdf) return GradForm::collision;
+	return options().stencil_block.load() != 0 || !g->d_blk ? GradForm::block : GradForm::stream;
+}
+
 extern "C" {
+
+// the source names of the kernels the launchers below pick for these arguments (hns_sim_substep_plan)
+const char* hns_divergence_kernel(const hns_grid* g, bool fused) {
+	switch (divergence_form(g, fused)) {
+	case DivForm::block: return "k_divergence";
+	case DivForm::zpair: return fused ? "k_divergence_combust_buoyancy_zpair" : "k_divergence_zpair<true>";
+	case DivForm::coalesced: return fused ? "k_divergence_combust_buoyancy<true>" : "k_divergence_row<NoMirror,true>";
+	default: return fused ? "k_divergence_combust_buoyancy<false>" : "k_divergence_row<NoMirror,false>";
+	}
+}
+const char* hns_subtract_gradient_kernel(const hns_grid* g, const float* sdf, int has_collision) {
+	switch (gradient_form(g, sdf, has_collision)) {
+	case GradForm::collision: return "k_subtract_gradient<true>";
+	case GradForm::block: return "k_subtract_gradient<false>";
+	default: return "k_subtract_gradient_s<NoMirror>";
+	}
+}
 
 int hns_dev_divergence(hns_grid* g, const float* vel3, float* div, float inv_dx, void* stream) {
 	if (int rc = check_grid(g, "hns_dev_divergence")) return rc;
 	NULLCHK(!vel3 || !div, "hns_dev_divergence");
 	if (g->n_active == 0) return HNS_OK;
-	if (options().stencil_block.load() || !g->d_blk)  // option "stencil" = block: A/B switch
+	const DivForm form = divergence_form(g, false);
+	if (form == DivForm::block)
 		hipLaunchKernelGGL(k_divergence, dim3((unsigned)g->n_active), dim3(512), 0, (hipStream_t)stream, g->dev(), vel3, div, inv_dx);
 	else
 	{
@@ -446,14 +484,9 @@ int hns_dev_divergence(hns_grid* g, const float* vel3, float* div, float inv_dx,
 		// backwards: advect_vector has just written the velocity front to back, so its tail is what the Infinity Cache holds
 		// (256^3: 74 -> 66 us).
 		gd.rev = 1;
-		// option "divergence" = auto | row | coalesced: by size (k_divergence_row's COAL form from 16k leaves; loses below, see the kernel)
-		const int form = options().divergence_form.load();
-		// auto, from 16,384 leaves (round 6): z-adjacent leaves in pairs, the coalesced form (256^3 63 -> 58 us, 512^3 467 -> 431, 66k-leaf plume 118 -> 112;
-		// below that size the pairing buys nothing and the coalesced form loses to the row form: profiles/r06_divergence_zpair_ab.txt). A range whose boundary leaves
-		// are dealt out first (a chained multi-GPU rank) keeps one leaf per workgroup.
-		if ((form == 3 || (form == 0 && g->n_active >= 16384)) && g->sched_pre == 0)
+		if (form == DivForm::zpair)
 			hipLaunchKernelGGL(k_divergence_zpair<true>, dim3((unsigned)((g->n_active + 1) / 2)), dim3(128), 0, (hipStream_t)stream, gd, vel3, div, inv_dx);
-		else if (form == 2 || (form == 0 && g->n_active >= 16384))
+		else if (form == DivForm::coalesced)
 			hipLaunchKernelGGL((k_divergence_row<NoMirror, true>), dim3((unsigned)g->n_active), dim3(64), 0, (hipStream_t)stream, gd, vel3, div, inv_dx, NoMirror{});
 		else
 			hipLaunchKernelGGL((k_divergence_row<NoMirror, false>), dim3((unsigned)g->n_active), dim3(64), 0, (hipStream_t)stream, gd, vel3, div, inv_dx, NoMirror{});
@@ -473,10 +506,10 @@ int hns_divergence_combust_buoyancy(hns_grid* g, const float* vel3, float* div, 
 	GridDev gd = g->dev();
 	gd.rev = 1;
 	const CombustFuse fz{fuel, waste, temperature, flame, reinterpret_cast<float4*>(q4), vel3_out, temp_gain, expansion, dt, ambient, strength};
-	const int form = options().divergence_form.load();
-	if ((form == 3 || (form == 0 && g->n_active >= 16384)) && g->sched_pre == 0)
+	const DivForm form = divergence_form(g, true);
+	if (form == DivForm::zpair)
 		hipLaunchKernelGGL(k_divergence_combust_buoyancy_zpair, dim3((unsigned)((g->n_active + 1) / 2)), dim3(128), 0, (hipStream_t)stream, gd, vel3, div, inv_dx, fz);
-	else if (form == 2 || (form == 0 && g->n_active >= 16384))
+	else if (form == DivForm::coalesced)
 		hipLaunchKernelGGL(k_divergence_combust_buoyancy<true>, dim3((unsigned)g->n_active), dim3(64), 0, (hipStream_t)stream, gd, vel3, div, inv_dx, fz);
 	else
 		hipLaunchKernelGGL(k_divergence_combust_buoyancy<false>, dim3((unsigned)g->n_active), dim3(64), 0, (hipStream_t)stream, gd, vel3, div, inv_dx, fz);
@@ -630,10 +663,11 @@ int hns_dev_subtract_pressure_gradient(hns_grid* g, const float* vel3, const flo
 	// (a wave-per-leaf row form like k_divergence_row was measured for this kernel too: 118 us vs 111 us at 256^3 -- not kept)
 	// (also measured and not kept for this kernel: the six taps through an LDS tile as in the advection kernels, 125 vs 116 us --
 	// at 470 MB per launch it streams from HBM and the extra barrier costs more than the loads it saves)
-	const bool block_form = options().stencil_block.load() != 0;  // option "stencil" = block: A/B switch
-	if (has_collision && sdf)
+	// (with a collision field the 512-thread form stays: the two forms measured within 6 % of each other, first line above)
+	const GradForm form = gradient_form(g, sdf, has_collision);
+	if (form == GradForm::collision)
 		hipLaunchKernelGGL(k_subtract_gradient<true>, grid, block, 0, (hipStream_t)stream, g->dev(), vel3, p, out3, sdf, inv_dx);
-	else if (block_form || !g->d_blk)
+	else if (form == GradForm::block)
 		hipLaunchKernelGGL(k_subtract_gradient<false>, grid, block, 0, (hipStream_t)stream, g->dev(), vel3, p, out3, sdf, inv_dx);
 	else
 		hipLaunchKernelGGL(k_subtract_gradient_s<NoMirror>, grid, dim3(64), 0, (hipStream_t)stream, g->dev(), vel3, p, out3, inv_dx, NoMirror{});

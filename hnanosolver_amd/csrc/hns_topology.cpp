@@ -146,6 +146,7 @@ const char* const kWordsLookahead[] = {"auto", "0", "1", nullptr};
 const OptionDesc kOptions[] = {
     {"rbgs", &Options::rbgs, kWordsRbgs},
     {"advect", &Options::advect_generic, kWordsAdvect},
+    {"collide", &Options::collide_generic, kWordsAdvect},
     {"stencil", &Options::stencil_block, kWordsStencil},
     {"schedule", &Options::schedule, kWordsSchedule},
     {"cook_cache", &Options::cook_cache, kWordsBool},

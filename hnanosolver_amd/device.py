@@ -280,6 +280,14 @@ class Sim:
         _raise(lib.hns_sim_lookahead_counts(self._ptr, C.byref(p), C.byref(c)))
         return int(p.value), int(c.value)
 
+    def substep_plan(self, params: Optional[CombustionParams] = None, has_collision: bool = False) -> dict:
+        """{stage: kernel form} of the next ``substep`` (params None: ``core_substep``) with these arguments (``hns_sim_substep_plan``); launches nothing.
+        Stages: collision advect_vector vorticity divergence pressure gradient advect_scalars; "-" = no launch, "memo" = already looked ahead."""
+        buf = C.create_string_buffer(1024)
+        p = None if params is None else params._c()
+        _raise(lib.hns_sim_substep_plan(self._ptr, None if p is None else C.byref(p), int(has_collision), buf, 1024))
+        return dict(w.split("=", 1) for w in buf.value.decode().split())
+
     def velocity_ptr(self) -> int:
         """Raw device pointer of the velocity (``hns_sim_velocity_ptr``): writable, so the sim stops looking ahead."""
         return int(lib.hns_sim_velocity_ptr(self._ptr) or 0)

@@ -59,19 +59,22 @@ int hns_device_count(void); /* 0 when no HIP device is visible; never initialise
  * topology, does not pay hipMalloc/hipFree again; this returns it to the driver. */
 int hns_trim_memory(void);
 /* Alternative kernel forms and data-movement strategies, kept as cross-checks of the default ones and for A/B measurement (all of them produce the same bits:
- * tests/test_kernel_variants_gpu.py). Process-wide, read by every entry point when it is called. value = NULL restores the default. Fourteen names: the
+ * tests/test_kernel_variants_gpu.py). Process-wide, read by every entry point when it is called. value = NULL restores the default. Fifteen names: the
  * twelve of round 6 below (the twenty-four of round 5 -- five more SOR forms among them -- are history: DESIGN_HISTORY.md, profiles/micro/exp/), "lookahead" (with
- * hns_sim_substep) and the test switch "arena_fill":
+ * hns_sim_substep), "collide" and the test switch "arena_fill":
  *   "rbgs"          auto | color. auto: temporally blocked red-black SOR (hns_sorblock.hip: two iterations per launch on 16^3-voxel blocks, two or four on one-leaf
  *                   blocks for grids of up to 600 leaves). color: the reference's own decomposition, two launches per iteration in place -- the independent cross-check
  *   "sor_block_lb"  0 = by size | 1 | 2: block edge of the temporally blocked form in leaves, whatever the size of the grid (how the tests reach both kernels on every leaf set)
  *   "advect"        auto | generic (64-bit addressed advection kernels)
+ *   "collide"       auto | generic. With a collision SDF, auto: advect_vector and advect_scalars run 32-bit addressed kernels that stage the SDF of the leaf and one
+ *                   voxel around it in LDS, and hns_sim_substep / hns_compute_sim fuse as without one ("fuse"). generic: the 64-bit addressed kernels and the
+ *                   reference's three launches -- the independent cross-check. hns_sim_substep_plan tells which a substep gets
  *   "stencil"       auto | block (512-thread divergence and gradient kernels)
  *   "divergence"    auto | row | coalesced | zpair: the divergence kernel fetches its own leaf row by row, or in memory order with a hand-over through LDS, or that with
  *                   two z-adjacent leaves per workgroup handing each other their common z face (auto: the last from 16,384 leaves, the first below)
  *   "schedule"      auto | linear (workgroup -> leaf order: one chunk of the leaf list per XCD, 128-leaf segments beyond 40,000 leaves | plain leaf order; takes
  *                   effect when a grid's launch tables are next built)
- *   "fuse"          1 | 0 (hns_sim_substep / hns_compute_sim without a collision field: divergence + combustion_oxygen + temperature_buoyancy as ONE launch that leaves
+ *   "fuse"          1 | 0 (hns_sim_substep / hns_compute_sim: divergence + combustion_oxygen + temperature_buoyancy as ONE launch that leaves
  *                   {fuel, waste, temperature, flame} as one 16-byte element per voxel, which advect_scalars then gathers its taps from; 0 = the reference's three
  *                   launches over five float arrays)
  *   "cook_cache"    1 | 0 (operator calls keep their device buffers with the grid)
@@ -295,6 +298,12 @@ int hns_sim_stage_times(hns_sim*, float* ms5, long long* substeps);
  * lent to the operator calls, and one whose hns_sim_velocity_ptr was taken never look ahead (again).
  * hns_sim_lookahead_counts: substeps of this sim that launched the look-ahead form / that skipped their advect_vector launch for it. */
 int hns_sim_lookahead_counts(hns_sim*, long long* produced, long long* consumed);
+/* Which kernel form each stage of the next hns_sim_substep (params NULL: hns_sim_core_substep) with these arguments would launch; launches nothing. The description is
+ * space-separated `stage=kernel` words for the stages collision advect_vector vorticity divergence pressure gradient advect_scalars, a kernel by its source name with its
+ * template flags (k_advect_scalars_n<q4,coll>; several launches of one stage joined by +). An absent stage reads `=-`, an advect_vector that the look-ahead has already
+ * computed `=memo`. dt, voxel size and iteration count are taken to be those of the previous substep call on the sim (dt and voxel size decide the look-ahead, the count
+ * what the pressure stage is planned for), the stream to be one that is not being captured. Decided by the code that launches; the query reads the sim and changes nothing in it. */
+int hns_sim_substep_plan(hns_sim*, const hns_combustion_params* params /* NULL: core */, int has_collision, char* description, uint64_t description_bytes);
 /* Raw device pointers of the sim's buffers (Vec3f AoS velocity, float fields, divergence, pressure). hns_sim_velocity_ptr hands out a WRITABLE pointer
  * the library cannot watch: calling it switches look-ahead off for this sim for good. */
 float* hns_sim_velocity_ptr(hns_sim*);
