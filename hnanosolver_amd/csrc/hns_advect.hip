@@ -105,18 +105,7 @@ __device__ __forceinline__ void tri_weights(float tx, float ty, float tz, float 
 	const float w00 = itx * ity, w10 = tx * ity, w01 = itx * ty, w11 = tx * ty;
 	w[0] = w00 * itz, w[1] = w10 * itz, w[2] = w01 * itz, w[3] = w11 * itz, w[4] = w00 * tz, w[5] = w10 * tz, w[6] = w01 * tz, w[7] = w11 * tz;
 }
-// TrilinearSampler's nest, z then y then x (Stencils.hpp:140-152), over the corners c[di*4+dj*2+dk] with one of the three lerps: lerp_f (IndexSampler<float,1>: unfused
-// a + w*(b-a)), lerp_c (IndexSampler<Vec3f,1> on the device branch: per component fmaf(w, b-a, a), Stencils.hpp:131-135) or lerp_v3 (the same on a register pair)
-template <class T, class Lerp>
-__device__ __forceinline__ T tri_nest_yx(const T (&z)[4], float fx, float fy, Lerp lerp) {  // (from the four z columns on: the look-ahead kernel forms those as its taps arrive)
-	const T y0 = lerp(z[0], z[1], fy), y1 = lerp(z[2], z[3], fy);
-	return lerp(y0, y1, fx);
-}
-template <class T, class Lerp>
-__device__ __forceinline__ T tri_nest(const T (&c)[8], float fx, float fy, float fz, Lerp lerp) {
-	const T z[4] = {lerp(c[0], c[1], fz), lerp(c[2], c[3], fz), lerp(c[4], c[5], fz), lerp(c[6], c[7], fz)};
-	return tri_nest_yx(z, fx, fy, lerp);
-}
+// (tri_nest / tri_nest_yx, TrilinearSampler's nest over eight corners with one of the three lerps: hns_device.hpp)
 // BFECC's limiter (Kernel.cu:219-233, 334-352, 396-431 per component): the corrected value clamped to the range of the voxel, its six face neighbours and the first sample.
 // float or v4f32. The caller forms phiCorr: advect_scalar's is unfused, advect_scalars' is fmaf(0.5, error, phiForward), as in the reference.
 template <class T>

@@ -102,6 +102,19 @@ __device__ __forceinline__ float lerp_f(float a, float b, float w) { return a + 
 // Vec3f lerp on the device branch (Stencils.hpp:131-135): fmaf(w, b-a, a)
 __device__ __forceinline__ float lerp_c(float a, float b, float w) { return __fmaf_rn(w, b - a, a); }
 
+// TrilinearSampler's nest, z then y then x (Stencils.hpp:140-152), over the corners c[di*4+dj*2+dk] with one of the three lerps: lerp_f (IndexSampler<float,1>: unfused
+// a + w*(b-a)), lerp_c (IndexSampler<Vec3f,1> on the device branch: per component fmaf(w, b-a, a), Stencils.hpp:131-135) or hns_advect.hip's lerp_v3 (the same on a register pair)
+template <class T, class Lerp>
+__device__ __forceinline__ T tri_nest_yx(const T (&z)[4], float fx, float fy, Lerp lerp) {  // (from the four z columns on: the look-ahead kernel forms those as its taps arrive)
+	const T y0 = lerp(z[0], z[1], fy), y1 = lerp(z[2], z[3], fy);
+	return lerp(y0, y1, fx);
+}
+template <class T, class Lerp>
+__device__ __forceinline__ T tri_nest(const T (&c)[8], float fx, float fy, float fz, Lerp lerp) {
+	const T z[4] = {lerp(c[0], c[1], fz), lerp(c[2], c[3], fz), lerp(c[4], c[5], fz), lerp(c[6], c[7], fz)};
+	return tri_nest_yx(z, fx, fy, lerp);
+}
+
 // ---- raw buffer access ---------------------------------------------------------------------------------------------
 // A buffer descriptor over a field takes a 32-bit byte offset, and the hardware bounds-checks it: a load at or past the
 // descriptor's end returns 0 without touching memory and a store there is dropped. hns_advect.hip (which see: "32-bit addressed

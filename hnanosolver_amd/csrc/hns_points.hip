@@ -1,0 +1,331 @@
+// hns_points.hip -- fields sampled at arbitrary positions and points traced through the velocity: the reference's samplers IndexSampler<float,1> /
+// IndexSampler<Vec3f,1> (src/Utils/Stencils.hpp:96-173) behind its Floor (Stencils.hpp:25-43), at positions that are no voxel centres. One thread per point, plain
+// 64-bit addressed loads (a point's taps may lie anywhere: the leaf-sized buffer descriptors of hns_advect.hip do not apply), no LDS. Positions are INDEX-SPACE
+// float triples, AoS n x 3, as the samplers and the advection kernels' back-traced `pos` have them. Arithmetic keeps the reference's association; -ffp-contract=off.
+#include "hns_device.hpp"
+
+#include <cmath>
+
+using namespace hns;
+
+namespace {
+
+constexpr int kMaxPointFields = 8;  // fields that share one launch of k_sample_points
+constexpr int kPointBlock = 256;
+
+struct PointFields {
+	const float* in[kMaxPointFields];
+	float* out[kMaxPointFields];
+	int n;
+	unsigned vec3;  // bit q: field q is Vec3f AoS
+};
+
+// the trilinear cell under a position: flat voxel index of corner (di,dj,dk) at t[di*4+dj*2+dk] (-1: its leaf is absent) and the fractions
+struct Cell {
+	int t[8];
+	float fx, fy, fz;
+};
+
+// The last leaf a thread of k_trace_points found and its origin (k_sample_points takes one sample per point and has none: CURSOR = false). The successive samples of one point (RK stages, steps) mostly land in that leaf or one of its 26 neighbours, whose
+// ids are one row of nbr27: one load in place of a walk through the origin hash (hash slot, then the candidate's origin, then perhaps the next slot: dependent
+// loads, one walk per distinct leaf under the cell). nbr27 is built from the same hash, so the answer is the hash's.
+struct Cursor {
+	int leaf, ox, oy, oz;  // leaf < 0: nothing found yet
+};
+
+__device__ __forceinline__ int plus8(int a) { return (int)((unsigned)a + 8u); }  // (wraps at the end of the int32 range, where no leaf lies beyond)
+
+// is leaf offset d (a multiple of 8 voxels; 64-bit: the difference of two int32 origins) one of {-8, 0, 8}, and with `crosses` (the cell reaches into the next leaf) one of {-8, 0}?
+__device__ __forceinline__ bool near_axis(long long d, bool crosses) { return (unsigned long long)(d + 8) <= (crosses ? 8ull : 16ull); }
+
+// leaf ids under the cell with lower corner (i, j, k), L[di*4+dj*2+dk]: one lookup per DISTINCT leaf (1, 2, 4 or 8: the lower corner on local index 7 along one, two
+// or three axes), as far_cell_taps (hns_device.hpp) takes its hash walks
+template <bool CURSOR>
+__device__ __forceinline__ void cell_leaves(const GridDev& g, Cursor& cur, int i, int j, int k, int (&L)[8]) {
+	const int i0 = i & ~7, j0 = j & ~7, k0 = k & ~7;
+	const bool cx = (i & 7) == 7, cy = (j & 7) == 7, cz = (k & 7) == 7;
+	bool near = false;
+	if (CURSOR && cur.leaf >= 0) near = near_axis((long long)i0 - cur.ox, cx) && near_axis((long long)j0 - cur.oy, cy) && near_axis((long long)k0 - cur.oz, cz);
+	// near: every leaf under the cell is the cursor's leaf or one of its 26 neighbours. Slot of the lower corner's leaf in the cursor's nbr27 row (13: the cursor's leaf itself)
+	const int slot = near ? (((i0 - cur.ox) >> 3) + 1) * 9 + (((j0 - cur.oy) >> 3) + 1) * 3 + ((k0 - cur.oz) >> 3) + 1 : 0;
+	const int* __restrict__ row = g.nbr27 + (near ? cur.leaf : 0) * 27;
+	// the leaf (a, b, c) leaves up from the lower corner's: the cursor's own id without a load, one load from its row, or a walk through the origin hash
+	auto leaf_at = [&](int a, int b, int c) -> int {
+		if (near) {
+			const int s = slot + a * 9 + b * 3 + c;
+			return s == 13 ? cur.leaf : row[s];
+		}
+		return d_find_leaf(g, a ? plus8(i0) : i0, b ? plus8(j0) : j0, c ? plus8(k0) : k0);
+	};
+	L[0] = leaf_at(0, 0, 0);
+	L[1] = cz ? leaf_at(0, 0, 1) : L[0];
+	L[2] = cy ? leaf_at(0, 1, 0) : L[0];
+	L[3] = cy ? (cz ? leaf_at(0, 1, 1) : L[2]) : L[1];
+	if (cx) {
+		L[4] = leaf_at(1, 0, 0);
+		L[5] = cz ? leaf_at(1, 0, 1) : L[4];
+		L[6] = cy ? leaf_at(1, 1, 0) : L[4];
+		L[7] = cy ? (cz ? leaf_at(1, 1, 1) : L[6]) : L[5];
+	} else {
+		L[4] = L[0], L[5] = L[1], L[6] = L[2], L[7] = L[3];
+	}
+	if (CURSOR && L[0] >= 0) cur = Cursor{L[0], i0, j0, k0};
+}
+
+// Floor (Stencils.hpp:25-43: __float2int_rd -- saturating, NaN -> 0 --, then xyz -= float(ijk)) and the eight corners of TrilinearSampler::stencil (Stencils.hpp:104-114)
+template <bool CURSOR>
+__device__ __forceinline__ Cell point_cell(const GridDev& g, Cursor& cur, float x, float y, float z) {
+	Cell C;
+	const int i = __float2int_rd(x), j = __float2int_rd(y), k = __float2int_rd(z);
+	C.fx = x - (float)i;
+	C.fy = y - (float)j;
+	C.fz = z - (float)k;
+	int L[8];
+	cell_leaves<CURSOR>(g, cur, i, j, k, L);
+	const unsigned lx[2] = {((unsigned)i & 7u) << 6, (((unsigned)i + 1u) & 7u) << 6}, ly[2] = {((unsigned)j & 7u) << 3, (((unsigned)j + 1u) & 7u) << 3},
+	               lz[2] = {(unsigned)k & 7u, ((unsigned)k + 1u) & 7u};
+#pragma unroll
+	for (int c = 0; c < 8; ++c) C.t[c] = L[c] < 0 ? -1 : L[c] * 512 + (int)(lx[c >> 2] | ly[(c >> 1) & 1] | lz[c & 1]);
+	return C;
+}
+
+// value or 0 outside the domain (IndexSampler<float,0>, Stencils.hpp:81-89) without a branch: the eight taps of a sample are issued together. (Reads element 0 for an
+// absent leaf: the launchers keep empty grids away from the kernels.)
+__device__ __forceinline__ float ldz(const float* __restrict__ f, int idx) {
+	const float v = f[idx < 0 ? 0 : idx];
+	return idx < 0 ? 0.0f : v;
+}
+
+// IndexSampler<float,1>: the nest z, y, x with the unfused lerp
+__device__ __forceinline__ float sample_f(const float* __restrict__ f, const Cell& C) {
+	float c[8];
+#pragma unroll
+	for (int q = 0; q < 8; ++q) c[q] = ldz(f, C.t[q]);
+	return tri_nest(c, C.fx, C.fy, C.fz, lerp_f);
+}
+
+// IndexSampler<Vec3f,1> on the device branch (Stencils.hpp:131-135): the same nest per component with fmaf(w, b - a, a); eight 12-byte taps
+__device__ __forceinline__ f3 sample_v(const float* __restrict__ u, const Cell& C) {
+	float x[8], y[8], z[8];
+#pragma unroll
+	for (int q = 0; q < 8; ++q) {
+		const f3 c = ld3z(u, C.t[q]);
+		x[q] = c.x, y[q] = c.y, z[q] = c.z;
+	}
+	return f3{tri_nest(x, C.fx, C.fy, C.fz, lerp_c), tri_nest(y, C.fx, C.fy, C.fz, lerp_c), tri_nest(z, C.fx, C.fy, C.fz, lerp_c)};
+}
+
+// Up to eight fields, float or Vec3f, at n positions: one Floor, one set of tap indices and fractions for all of them. Output q is what a launch with field q alone gives.
+__global__ __launch_bounds__(kPointBlock) void k_sample_points(const GridDev g, const PointFields P, const float* __restrict__ xyz, const unsigned n) {
+	const unsigned p = blockIdx.x * (unsigned)kPointBlock + threadIdx.x;
+	if (p >= n) return;
+	const f3 pos = ld3(xyz, (int)p);
+	Cursor none{-1, 0, 0, 0};
+	const Cell C = point_cell<false>(g, none, pos.x, pos.y, pos.z);
+#pragma unroll
+	for (int q = 0; q < kMaxPointFields; ++q) {
+		if (q >= P.n) break;
+		if ((P.vec3 >> q) & 1u)
+			st3(P.out[q], (int)p, sample_v(P.in[q], C));
+		else
+			P.out[q][p] = sample_f(P.in[q], C);
+	}
+}
+
+__device__ __forceinline__ bool finite_f(float a) { return (__float_as_uint(a) & 0x7fffffffu) < 0x7f800000u; }
+
+// `steps` steps of a point through the velocity u in registers, x' = x + s U(x) with U the Vec3f sampler above and s = dt / dx (negative: a back-trace); ORDER 1 forward
+// Euler, 2 the midpoint rule, 4 the classical Runge-Kutta step. Every a + c*b is a multiply, then an add. A point with no leaf under any tap samples U = 0 and
+// stays where it is. status (or null): 1 iff the final position is finite in all three components and the leaf of its cell exists.
+template <int ORDER, bool CURSOR>
+__global__ __launch_bounds__(kPointBlock) __attribute__((amdgpu_waves_per_eu(7, 8))) void k_trace_points(const GridDev g, const float* __restrict__ u, float* __restrict__ xyz, const unsigned n, const float s,
+                                                              const int steps, unsigned char* __restrict__ status) {
+	const unsigned p = blockIdx.x * (unsigned)kPointBlock + threadIdx.x;
+	if (p >= n) return;
+	f3 x = ld3(xyz, (int)p);
+	const float h = 0.5f * s, s6 = s * 0.16666667f;
+	Cursor cur{-1, 0, 0, 0};
+	auto U = [&](float a, float b, float c) { return sample_v(u, point_cell<CURSOR>(g, cur, a, b, c)); };
+	for (int step = 0; step < steps; ++step) {
+		const f3 k1 = U(x.x, x.y, x.z);
+		if (ORDER == 1) {
+			x = f3{x.x + s * k1.x, x.y + s * k1.y, x.z + s * k1.z};
+		} else if (ORDER == 2) {
+			const f3 k2 = U(x.x + h * k1.x, x.y + h * k1.y, x.z + h * k1.z);
+			x = f3{x.x + s * k2.x, x.y + s * k2.y, x.z + s * k2.z};
+		} else {
+			const f3 k2 = U(x.x + h * k1.x, x.y + h * k1.y, x.z + h * k1.z);
+			f3 sum = {k1.x + 2.0f * k2.x, k1.y + 2.0f * k2.y, k1.z + 2.0f * k2.z};
+			const f3 k3 = U(x.x + h * k2.x, x.y + h * k2.y, x.z + h * k2.z);
+			sum = f3{sum.x + 2.0f * k3.x, sum.y + 2.0f * k3.y, sum.z + 2.0f * k3.z};
+			const f3 k4 = U(x.x + s * k3.x, x.y + s * k3.y, x.z + s * k3.z);
+			sum = f3{sum.x + k4.x, sum.y + k4.y, sum.z + k4.z};
+			x = f3{x.x + s6 * sum.x, x.y + s6 * sum.y, x.z + s6 * sum.z};
+		}
+	}
+	st3(xyz, (int)p, x);
+	if (status) {
+		int L[8];
+		const int i = __float2int_rd(x.x), j = __float2int_rd(x.y), k = __float2int_rd(x.z);
+		bool in = finite_f(x.x) && finite_f(x.y) && finite_f(x.z);
+		if (in) {
+			cell_leaves<CURSOR>(g, cur, i & ~7, j & ~7, k & ~7, L);  // (the leaf's own corner: one lookup)
+			in = L[0] >= 0;
+		}
+		status[p] = in ? 1 : 0;
+	}
+}
+
+// ---- launchers ---------------------------------------------------------------------------------------------------------------------------------------------------------
+
+int refuse(const char* who, const char* what) {
+	set_error("%s: %s", who, what);
+	return HNS_ERR_INVALID_ARGUMENT;
+}
+
+constexpr uint64_t kMaxPoints = 0x7fffffffull;
+
+// fields / ncomp / out: HOST arrays of n_fields entries. Every refusal comes before the first launch.
+int sample_points(const char* who, hns_grid* g, const float* const* fields, const int* ncomp, int n_fields, const float* xyz, uint64_t n, float* const* out, void* stream) {
+	if (int rc = check_grid(g, who)) return rc;
+	if (n_fields < 1) return refuse(who, "n_fields must be at least 1");
+	if (!fields || !ncomp || !out) return refuse(who, "null list (fields, ncomp or out)");
+	for (int i = 0; i < n_fields; ++i)
+		if (ncomp[i] != 1 && ncomp[i] != 3) {
+			set_error("%s: ncomp[%d] is %d (must be 1 or 3)", who, i, ncomp[i]);
+			return HNS_ERR_INVALID_ARGUMENT;
+		}
+	if (n > kMaxPoints) return refuse(who, "n is above 2^31 - 1");
+	if (n == 0) return HNS_OK;  // (no point, no device pointer looked at: an empty array's may well be null)
+	if (!xyz) return refuse(who, "xyz is null");
+	for (int i = 0; i < n_fields; ++i) {
+		if (!fields[i] || !out[i]) {
+			set_error("%s: %s[%d] is null", who, fields[i] ? "out" : "fields", i);
+			return HNS_ERR_INVALID_ARGUMENT;
+		}
+		if (out[i] == xyz) {
+			set_error("%s: out[%d] is xyz", who, i);
+			return HNS_ERR_INVALID_ARGUMENT;
+		}
+		for (int j = 0; j < n_fields; ++j) {
+			if (out[i] == fields[j]) {
+				set_error("%s: out[%d] is fields[%d]", who, i, j);
+				return HNS_ERR_INVALID_ARGUMENT;
+			}
+			if (j < i && out[i] == out[j]) {
+				set_error("%s: out[%d] is out[%d]", who, i, j);
+				return HNS_ERR_INVALID_ARGUMENT;
+			}
+		}
+	}
+	if (g->topo.n_leaves == 0) {  // no leaf, no field element: every tap is outside and reads 0
+		for (int i = 0; i < n_fields; ++i) HNS_HIP(hipMemsetAsync(out[i], 0, sizeof(float) * ncomp[i] * n, (hipStream_t)stream));
+		return HNS_OK;
+	}
+	const dim3 grid((unsigned)((n + kPointBlock - 1) / kPointBlock)), block(kPointBlock);
+	for (int base = 0; base < n_fields; base += kMaxPointFields) {  // (the cell does not depend on the fields: more launches change nothing numerically)
+		PointFields P{};
+		P.n = n_fields - base < kMaxPointFields ? n_fields - base : kMaxPointFields;
+		for (int q = 0; q < P.n; ++q) {
+			P.in[q] = fields[base + q], P.out[q] = out[base + q];
+			P.vec3 |= (ncomp[base + q] == 3 ? 1u : 0u) << q;
+		}
+		hipLaunchKernelGGL(k_sample_points, grid, block, 0, (hipStream_t)stream, g->dev(), P, xyz, (unsigned)n);
+	}
+	return launch_status(who);
+}
+
+int trace_points(const char* who, const char* dx_name, hns_grid* g, const float* vel3, float* xyz, uint64_t n, float dt, float inv_dx, int order, int steps,
+                 unsigned char* status, void* stream) {
+	if (int rc = check_grid(g, who)) return rc;
+	if (order != 1 && order != 2 && order != 4) return refuse(who, "order must be 1, 2 or 4");
+	if (steps < 1) return refuse(who, "steps must be at least 1");
+	if (std::isnan(dt)) return refuse(who, "dt is NaN");
+	if (!(inv_dx > 0.0f) || std::isinf(inv_dx)) {
+		set_error("%s: %s must be a positive finite number", who, dx_name);
+		return HNS_ERR_INVALID_ARGUMENT;
+	}
+	if (n > kMaxPoints) return refuse(who, "n is above 2^31 - 1");
+	if (n == 0) return HNS_OK;  // (as above)
+	if (!xyz) return refuse(who, "xyz is null");
+	if (!vel3) return refuse(who, "vel3 is null");
+	if ((const void*)xyz == (const void*)vel3 || (status && ((const void*)status == (const void*)xyz || (const void*)status == (const void*)vel3)))
+		return refuse(who, "xyz, status and vel3 must be three different buffers");
+	if (g->topo.n_leaves == 0) {  // U = 0 everywhere: no point moves, none is inside
+		if (status) HNS_HIP(hipMemsetAsync(status, 0, n, (hipStream_t)stream));
+		return HNS_OK;
+	}
+	const float s = dt * inv_dx;
+	const dim3 grid((unsigned)((n + kPointBlock - 1) / kPointBlock)), block(kPointBlock);
+	// The leaf cursor (cell_leaves) stays on: at 256^3 it takes 0.61-0.70 of the hash form's time on points in leaf order at order 4 and 1.08 on randomly permuted ones
+	// (profiles/points_ab.txt; the hash form is profiles/micro/exp/points_hash_form.patch). The same words either way.
+	constexpr bool cursor = true;
+	switch (order) {
+	case 1: hipLaunchKernelGGL((k_trace_points<1, cursor>), grid, block, 0, (hipStream_t)stream, g->dev(), vel3, xyz, (unsigned)n, s, steps, status); break;
+	case 2: hipLaunchKernelGGL((k_trace_points<2, cursor>), grid, block, 0, (hipStream_t)stream, g->dev(), vel3, xyz, (unsigned)n, s, steps, status); break;
+	default: hipLaunchKernelGGL((k_trace_points<4, cursor>), grid, block, 0, (hipStream_t)stream, g->dev(), vel3, xyz, (unsigned)n, s, steps, status); break;
+	}
+	return launch_status(who);
+}
+
+// a sim the point calls may read: not null (without a device there is none to pass: hns_sim_create refused, and the caller learns why here too), not lent to a cook cache
+int check_sim(const hns_sim* s, const char* who) {
+	if (!s) {
+		if (hns_device_count() == 0) {
+			set_error("%s: no HIP device (there is no CPU fallback)", who);
+			return HNS_ERR_NO_DEVICE;
+		}
+		return refuse(who, "null sim");
+	}
+	if (s->cached || s->in_use) return refuse(who, "the sim belongs to a grid's cook cache");
+	return HNS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int hns_dev_sample_points(hns_grid* g, const float* const* fields, const int* ncomp, int n_fields, const float* xyz, uint64_t n, float* const* out, void* stream) {
+	return sample_points("hns_dev_sample_points", g, fields, ncomp, n_fields, xyz, n, out, stream);
+}
+
+int hns_dev_trace_points(hns_grid* g, const float* vel3, float* xyz, uint64_t n, float dt, float inv_dx, int order, int steps, unsigned char* status, void* stream) {
+	return trace_points("hns_dev_trace_points", "inv_dx", g, vel3, xyz, n, dt, inv_dx, order, steps, status, stream);
+}
+
+// Reads the sim's current buffers and nothing else of it: the look-ahead memo, the masks, the feedback signatures and the solve report stay as they are.
+int hns_sim_sample_points(hns_sim* s, const char* const* names, int n_names, int with_velocity, const float* xyz, uint64_t n, float* const* out, void* stream) {
+	const char* who = "hns_sim_sample_points";
+	if (int rc = check_sim(s, who)) return rc;
+	if (n_names < -1) return refuse(who, "n_names is below -1");
+	if (n_names > 0 && !names) return refuse(who, "names is null");
+	std::vector<const float*> fields;
+	std::vector<int> ncomp, which;
+	if (n_names < 0)
+		for (size_t i = 0; i < s->names.size(); ++i) which.push_back((int)i);
+	for (int i = 0; i < n_names; ++i) {
+		const int k = names[i] ? s->find(names[i]) : -1;
+		if (k < 0) {
+			set_error("%s: names[%d]: no float field named '%s' in this sim", who, i, names[i] ? names[i] : "?");
+			return HNS_ERR_INVALID_ARGUMENT;
+		}
+		if (std::find(which.begin(), which.end(), k) != which.end()) {
+			set_error("%s: names[%d]: field '%s' is listed twice", who, i, names[i]);
+			return HNS_ERR_INVALID_ARGUMENT;
+		}
+		which.push_back(k);
+	}
+	for (int k : which) fields.push_back(s->cur[k]), ncomp.push_back(1);
+	if (with_velocity) fields.push_back(s->vel), ncomp.push_back(3);
+	if (fields.empty()) return refuse(who, "no field to sample (no names and with_velocity = 0)");
+	return sample_points(who, s->grid, fields.data(), ncomp.data(), (int)fields.size(), xyz, n, out, stream);
+}
+
+int hns_sim_trace_points(hns_sim* s, float* xyz, uint64_t n, float dt, float voxel_size, int order, int steps, unsigned char* status, void* stream) {
+	const char* who = "hns_sim_trace_points";
+	if (int rc = check_sim(s, who)) return rc;
+	if (!(voxel_size > 0.0f) || std::isinf(voxel_size)) return refuse(who, "voxel_size must be a positive finite number");
+	return trace_points(who, "1 / voxel_size", s->grid, s->vel, xyz, n, dt, 1.0f / voxel_size, order, steps, status, stream);
+}
+
+}  // extern "C"

@@ -149,6 +149,32 @@ def _byte_ptr(t) -> int:
     return t.data_ptr()
 
 
+def _ncomp(t) -> int:
+    return 3 if (t.dim() == 2 and t.shape[1] == 3) else 1
+
+
+def sample_points(grid: IndexGridHandle, fields: Sequence, xyz, outs: Optional[Sequence] = None):
+    """Every field of `fields` -- (N,) float tensors and (N, 3) Vec3f tensors in any mix -- at the positions xyz, an (n, 3) float32 tensor in INDEX space
+    (``hns_dev_sample_points``): the advection kernels' trilinear samplers, 0 outside the domain. outs[i] is (n,) or (n, 3) like its field, made here when
+    outs is None; up to eight fields share a launch, and outs[i] is bit-identical to a call with fields[i] alone. Asynchronous on the current stream."""
+    n, k = xyz.shape[0], len(fields)
+    nc = [_ncomp(f) for f in fields]
+    if outs is None:
+        outs = [_torch().empty((n, 3) if c == 3 else (n,), dtype=_torch().float32, device=xyz.device) for c in nc]
+    ins = (C.c_void_p * max(1, k))(*[_ptr(t) for t in fields])
+    dst = (C.c_void_p * max(1, k))(*[_ptr(t) for t in outs])
+    _raise(lib.hns_dev_sample_points(grid.ptr, ins, (C.c_int * max(1, k))(*nc), k, _ptr(xyz), n, dst, current_stream()))
+    return outs
+
+
+def trace_points(grid: IndexGridHandle, vel, xyz, dt: float, inv_dx: float, order: int = 2, steps: int = 1, status=None):
+    """`steps` steps of the points xyz ((n, 3) float32, index space, moved IN PLACE) through the velocity `vel` (``hns_dev_trace_points``): order 1 Euler, 2 midpoint,
+    4 Runge-Kutta; a negative dt traces back. status: None or a uint8 tensor of n bytes, 1 where the final position is finite and inside a leaf. Asynchronous on
+    the current stream."""
+    _raise(lib.hns_dev_trace_points(grid.ptr, _ptr(vel), _ptr(xyz), xyz.shape[0], dt, inv_dx, int(order), int(steps), _byte_ptr(status), current_stream()))
+    return xyz
+
+
 def stats_buffer(n_records: int = 1):
     """Device memory for `n_records` hns_stats records (a uint8 tensor; ``read_stats`` brings it to the host)."""
     return _torch().zeros(n_records * leafio.STATS_DTYPE.itemsize, dtype=_torch().uint8, device="cuda")
@@ -252,6 +278,31 @@ class Sim:
             return
         arr = (C.c_char_p * max(1, len(names)))(*[n.encode() for n in names])
         _raise(lib.hns_sim_advect(self._ptr, arr, len(names), int(velocity), dt, voxel_size, stream))
+
+    def sample(self, names: Optional[Sequence[str]] = None, xyz=None, velocity: bool = False, stream: Optional[int] = None) -> dict:
+        """The sim's float fields `names` (None: all of them) and, with `velocity`, its velocity under the key "vel", at the positions xyz ((n, 3) float32 device
+        tensor, index space): {name: tensor} (``hns_sim_sample_points``). Asynchronous on `stream` (None: the current stream); the sim is only read."""
+        if xyz is None:
+            raise ValueError("Sim.sample: xyz is required")
+        names = list(self.names) if names is None else list(names)
+        n, t = xyz.shape[0], _torch()
+        out = {k: t.empty(n, dtype=t.float32, device=xyz.device) for k in names}
+        if len(out) != len(names):
+            raise ValueError("Sim.sample: a name is listed twice")
+        if velocity:
+            out["vel"] = t.empty((n, 3), dtype=t.float32, device=xyz.device)
+        arr = (C.c_char_p * max(1, len(names)))(*[k.encode() for k in names])
+        dst = (C.c_void_p * max(1, len(out)))(*[_ptr(v) for v in out.values()])
+        _raise(lib.hns_sim_sample_points(self._ptr, arr, len(names), int(velocity), _ptr(xyz), n, dst, current_stream() if stream is None else stream))
+        return out
+
+    def trace(self, xyz, *, dt: float, voxel_size: float, order: int = 2, steps: int = 1, status: bool = False, stream: Optional[int] = None):
+        """`steps` steps of the points xyz (moved in place) through the sim's current velocity (``hns_sim_trace_points``); with `status` returns the uint8 tensor
+        that is 1 where a point ended finite and inside a leaf. Asynchronous on `stream` (None: the current stream); the sim is only read."""
+        st = _torch().empty(xyz.shape[0], dtype=_torch().uint8, device=xyz.device) if status else None
+        _raise(lib.hns_sim_trace_points(self._ptr, _ptr(xyz), xyz.shape[0], dt, voxel_size, int(order), int(steps), _byte_ptr(st),
+                                        current_stream() if stream is None else stream))
+        return st
 
     def pressure_solve(self, iterations: int, voxel_size: float, stream: int = 0) -> None:
         _raise(lib.hns_sim_pressure_solve(self._ptr, iterations, voxel_size, stream))

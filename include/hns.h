@@ -273,6 +273,15 @@ int hns_sim_core_substep(hns_sim*, int iterations, float dt, float voxel_size, v
  * looked ahead (below) is dropped, as by every call that rewrites a field. Refused before anything is launched (HNS_ERR_INVALID_ARGUMENT): a name the sim lacks, a name listed
  * twice, a null name or list, n_names < -1, a negative dt, a voxel size <= 0, a sim lent to a grid's cook cache. */
 int hns_sim_advect(hns_sim*, const char* const* names, int n_names, int advect_velocity, float dt, float voxel_size, void* stream);
+/* Sample the sim's own fields at n points and trace points through its velocity (hns_dev_sample_points / hns_dev_trace_points below, which state the positions, the
+ * arithmetic and the refusals) without the fields leaving the device. names: float fields of the sim (n_names = -1: all of them, in insertion order; "collision_sdf"
+ * counts as any float field), then, with with_velocity != 0, the velocity as the LAST output; out: HOST array of device pointers in that order, n floats each (3n for the
+ * velocity). hns_sim_trace_points moves xyz in place through the sim's current velocity with inv_dx = 1.0f / voxel_size, as hns_sim_advect forms it. Both are
+ * asynchronous on `stream`, allocate nothing and write no field: the look-ahead memo, the active masks, the feedback signatures of hns_compute_sim_resident and the
+ * solve report stay as they are. Refused besides what the hns_dev_* calls refuse: n_names < -1, a name the sim lacks, a name listed twice, nothing to sample, a
+ * voxel_size that is not a positive finite number, a sim lent to a grid's cook cache. Not mirrored in hns_dist_*: a partitioned sim has no point calls. */
+int hns_sim_sample_points(hns_sim*, const char* const* names, int n_names, int with_velocity, const float* xyz, uint64_t n, float* const* out, void* stream);
+int hns_sim_trace_points(hns_sim*, float* xyz, uint64_t n, float dt, float voxel_size, int order, int steps, unsigned char* status, void* stream);
 /* Only the pressure hot loop on the sim's divergence/pressure buffers (pressure zeroed first); asynchronous. */
 int hns_sim_pressure_solve(hns_sim*, int iterations, float voxel_size, void* stream);
 /* hipEvent timing of the pressure hot loop on its launch stream: after hns_sim_timing(sim, max_solves) every pressure
@@ -487,6 +496,26 @@ int hns_dev_advect_scalar_multi(hns_grid*, const float* vel3, const float* const
  * (a Vec3f field below 4 GiB, option "advect" = auto); HNS_ERR_INVALID_ARGUMENT elsewhere. */
 int hns_dev_advect_scalars_ahead(hns_grid*, const float* vel3, const float* const* in, float* const* out, int n, float* adv_out3, float dt, float inv_dx,
                                  void* stream);
+/* Fields at points: the trilinear samplers of the advection kernels (IndexSampler<float,1> and, on its device branch, IndexSampler<Vec3f,1>: Stencils.hpp:96-173) at n
+ * arbitrary positions. xyz: n x 3 floats (AoS, device) in INDEX space -- voxel (i, j, k) has its sample at position (i, j, k), as the reference's samplers and the
+ * advection kernels' back-traced positions have it; a caller with world positions divides by the voxel size itself, so that positions round in one known place. The cell is
+ * Floor(xyz) (Stencils.hpp:25-43) with the GPU's float -> int conversion (saturating, NaN -> 0), a tap whose leaf is absent reads 0, and every leaf of the grid is readable
+ * whatever its launch range (ghost leaves included). fields[i]: device pointer, ncomp[i] 1 (float) or 3 (Vec3f AoS); out[i]: device, n x ncomp[i] floats; fields, ncomp and
+ * out are HOST arrays of n_fields entries. Up to eight fields share a launch and with it the cell, the tap indices and the fractions; output i is bit-identical to a call with
+ * field i alone, float results to the reference's sampler. Asynchronous on `stream`, no device allocation; n == 0 launches nothing and looks at no device pointer (an empty array's may be null). Refused before anything is launched
+ * (HNS_ERR_INVALID_ARGUMENT, the call and the argument in the message), outputs untouched: n_fields < 1, a null list or entry, a null xyz, an ncomp other than 1 or 3, an
+ * out[i] equal to another out[j], to xyz or to a field, n above 2^31 - 1. */
+int hns_dev_sample_points(hns_grid*, const float* const* fields, const int* ncomp, int n_fields, const float* xyz, uint64_t n, float* const* out, void* stream);
+/* Points through the velocity: `steps` steps of xyz (n x 3, index space, updated in place) in one launch, with U(x) the Vec3f sample above, s = dt * inv_dx, h = 0.5f * s,
+ * s6 = s * 0.16666667f, every operation one rounded float32 operation per component and every a + c*b a multiply, then an add:
+ *   order 1  x' = x + s*U(x)
+ *   order 2  k1 = U(x); x' = x + s*U(x + h*k1)
+ *   order 4  k1 = U(x); k2 = U(x + h*k1); k3 = U(x + h*k2); k4 = U(x + s*k3); x' = x + s6*(((k1 + 2.0f*k2) + 2.0f*k3) + k4)
+ * dt may be negative (a back-trace). A point with no leaf under any tap samples U = 0 and stays where it is. status: NULL, or n bytes (device): 1 iff the final position
+ * is finite in all three components and the leaf of its cell exists, else 0. Asynchronous on `stream`, no device allocation; n == 0 launches nothing. Refused before
+ * anything is launched (HNS_ERR_INVALID_ARGUMENT), positions and status untouched: a null xyz or vel3, an order not in {1, 2, 4}, steps < 1, a NaN dt, an inv_dx that is
+ * not a positive finite number, n above 2^31 - 1, xyz, status and vel3 not three different buffers. Neither call is mirrored in hns_dist_*. */
+int hns_dev_trace_points(hns_grid*, const float* vel3, float* xyz, uint64_t n, float dt, float inv_dx, int order, int steps, unsigned char* status, void* stream);
 /* divergence / divergence_opt (Kernel.cu:455-519) */
 int hns_dev_divergence(hns_grid*, const float* vel3, float* div, float inv_dx, void* stream);
 /* One colour of redBlackGaussSeidelUpdate(_opt) in place (Kernel.cu:521-623): the two-launch form. */

@@ -7,6 +7,7 @@
 #     build.sh halo4   sor_halo_exp.patch   -DHNS_EXP=4           # pair SOR kernel without its y-face halo (results wrong, timing only)
 #     build.sh trace   sorblock_trace.patch -DHNS_SB_TRACE=2048   # s_memtime stamps of workgroups 2048..2111 (profiles/micro/sb_trace.py)
 #     build.sh p4      advect_p4.patch      -DHNS_EXP_P4          # velocity gathered out of a float4-padded copy
+#     build.sh points_hash points_hash_form.patch               # k_trace_points without its leaf cursor (profiles/micro/points_time.py --ab)
 set -e
 here="$(cd "$(dirname "$0")" && pwd)"; src="$here/../../../hnanosolver_amd/csrc"
 name=$1; patch=$2; shift 2
@@ -14,7 +15,7 @@ tmp=$(mktemp -d); cp "$src"/*.hip "$src"/*.hpp "$src"/*.cpp "$tmp"/
 [ "$patch" != "-" ] && (cd "$tmp" && patch -s -p0 < "$here/$patch")
 cd "$tmp"
 objs=""
-for f in hns_topology.cpp hns_nanovdb.cpp hns_leafio.cpp hns_gridbuild.hip hns_advect.hip hns_pressure.hip hns_sorblock.hip hns_pointwise.hip hns_arena.hip hns_api.hip hns_dist_plan.hip hns_dist_transport.hip hns_dist_substep.hip hns_regrid.hip; do
+for f in hns_topology.cpp hns_nanovdb.cpp hns_leafio.cpp hns_gridbuild.hip hns_advect.hip hns_pressure.hip hns_sorblock.hip hns_pointwise.hip hns_arena.hip hns_api.hip hns_dist_plan.hip hns_dist_transport.hip hns_dist_substep.hip hns_regrid.hip hns_diagnostics.hip hns_points.hip; do
   extra=""; [ "$f" = hns_sorblock.hip ] && extra="${HNS_SORBLOCK_FLAGS--fno-slp-vectorize}"
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt -I"$src/../../include" $extra "$@" -x hip -c $f -o $f.o &
   objs="$objs $f.o"
