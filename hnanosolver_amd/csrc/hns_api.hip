@@ -251,14 +251,9 @@ static int validate_step(float voxel_size, float dt, int64_t iterations, bool ne
 static int sim_pressure(hns_sim* s, int iterations, float voxel_size, float omega, void* stream) {
 	if (s->control) return hns_sim_pressure_controlled(s, iterations, voxel_size, omega, stream);  // hns_sim_set_solve_control: `iterations` is the maximum
 	int in_b = 0;  // never warm-started (HNanoSolver.cu:113): the solve starts from p = 0, which the first sweep knows without reading p_a
-	hipEvent_t* timed = s->solve_ev.current();
-	if (timed) HNS_HIP(hipEventRecord(timed[0], (hipStream_t)stream));
+	HNS_TRY(s->solve_begin(stream));
 	HNS_TRY(hns_rbgs_iterate(s->grid, s->div, s->p_a, s->p_b, voxel_size, omega, iterations, &in_b, stream, true));
-	if (timed) {
-		HNS_HIP(hipEventRecord(timed[1], (hipStream_t)stream));
-		s->solve_ev.advance();
-		s->timed_launches += iterations;
-	}
+	HNS_TRY(s->solve_end(stream, iterations));
 	s->p_result = in_b ? s->p_b : s->p_a;
 	s->solved = true;
 	return HNS_OK;
@@ -407,12 +402,7 @@ struct Substep {
 	int prepare(hns_sim* sim, int iters, float dt_, float vs, const hns_combustion_params* prm, int has_collision, void* st) {
 		bool capturing = false;
 		if (!sim->ahead_off && options().lookahead.load() != kLookaheadOff) {  // neither produce nor consume while the stream is captured: a replayed graph writes vel and adv unseen, so such a sim stops looking ahead for good
-			hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-			if (hipStreamIsCapturing((hipStream_t)st, &cs) != hipSuccess) {
-				(void)hipGetLastError();
-				cs = hipStreamCaptureStatusActive;
-			}
-			if (cs != hipStreamCaptureStatusNone) capturing = true, sim->ahead_off = true;
+			if (stream_is_capturing(st)) capturing = true, sim->ahead_off = true;
 		}
 		const int rc = decide(sim, iters, dt_, vs, prm, has_collision, st, capturing);
 		if (!ahead_live) s->drop_ahead();

@@ -240,12 +240,7 @@ int fetch(hns_sim* s, const hns_stats* d_rec, int first, int n, hipStream_t st) 
 using namespace hns;
 
 int hns_refuse_capture(void* stream, const char* who) {
-	hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-	if (hipStreamIsCapturing((hipStream_t)stream, &cs) != hipSuccess) {
-		(void)hipGetLastError();
-		cs = hipStreamCaptureStatusActive;
-	}
-	if (cs == hipStreamCaptureStatusNone) return HNS_OK;
+	if (!stream_is_capturing(stream)) return HNS_OK;
 	set_error("%s: a solve control is set (the host reads the residual at every check) and the stream is capturing", who);
 	return HNS_ERR_INVALID_ARGUMENT;
 }
@@ -267,8 +262,7 @@ int hns_sim_pressure_controlled(hns_sim* s, int max_iterations, float voxel_size
 	DeviceScope on(s->device);
 	hns_stats *d_rec, *table;
 	HNS_TRY(sim_diag(s, 1, &d_rec, &table));
-	hipEvent_t* timed = s->solve_ev.current();
-	if (timed) HNS_HIP(hipEventRecord(timed[0], st));
+	HNS_TRY(s->solve_begin(stream));
 	ctl.ran = false;
 	ctl.history.clear();
 	ctl.report = hns_solve_report{};
@@ -294,11 +288,7 @@ int hns_sim_pressure_controlled(hns_sim* s, int max_iterations, float voxel_size
 			break;
 		}
 	}
-	if (timed) {
-		HNS_HIP(hipEventRecord(timed[1], st));
-		s->solve_ev.advance();
-		s->timed_launches += done;
-	}
+	HNS_TRY(s->solve_end(stream, done));
 	s->p_result = cur;
 	s->solved = true;
 	ctl.report.iterations = done, ctl.report.checks = (int)ctl.history.size();

@@ -528,8 +528,6 @@ struct Step {
 		return fail(HNS_ERR_RUNTIME, "hns_dist: unknown phase");
 	}
 
-	// Do both launch ranges of the split sweep take two iterations in ONE launch each (result in dst for both)? Asked of the library's own
-	// plan, so that whatever hns_rbgs_iterate does with `2` is what this loop assumes.
 	// Round 6: a SMALL rank (up to 16,384 owned leaves: BASELINE config 5 in 8 ranks has 8,243 each) runs its short phases -- the sweeps of the pressure loop, the divergence,
 	// the gradient subtraction -- as ONE launch over all owned leaves with the exchange behind it on the compute stream (post(..., in_line)): at that size the boundary chain
 	// (boundary kernel -> pack -> transfer -> unpack, each a latency-bound launch, plus two cross-stream event edges) is longer than the interior kernel it was meant to hide
@@ -539,12 +537,13 @@ struct Step {
 		return !d->single_stream && (d->comm || d->loopback || d->ipc) && u != 0 && (u == 2 || d->nB + d->nI <= 16384);
 	}
 
+	// Do both launch ranges of the split sweep take two iterations in ONE launch each (result in dst for both)? Asked of the schedule
+	// hns_rbgs_iterate walks, so that whatever it does with `2` is what this loop assumes.
 	bool split_blocked() const {
 		if (d->k < 2) return false;
 		for (hns_grid* g : {d->gB, d->gI}) {
 			if (!g->n_active) continue;
-			int launches = 0, per = 0;
-			if (hns_grid_rbgs_plan(g, 2, nullptr, 0, &launches, &per) != HNS_OK || launches != 1) return false;
+			if (!hns_rbgs_schedule(g, 2).one_blocked_launch()) return false;
 		}
 		return true;
 	}

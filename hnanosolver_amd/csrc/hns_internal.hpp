@@ -81,6 +81,45 @@ struct EventGroups {
 	}
 };
 
+// Is `stream` being captured into a graph? A query that fails counts as yes, and its error is cleared.
+inline bool stream_is_capturing(void* stream) {
+	hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+	if (hipStreamIsCapturing((hipStream_t)stream, &cs) != hipSuccess) {
+		(void)hipGetLastError();
+		return true;
+	}
+	return cs != hipStreamCaptureStatusNone;
+}
+
+// ---- the pressure loop's launch schedule ----------------------------------------------------------------------------
+// What one solve of `iterations` (red, black) iterations launches, as a value: hns_rbgs_iterate walks it, hns_grid_rbgs_plan describes it, the partitioned substep
+// queries it. lb = 0 is the colour form (copy, then one k_rbgs_color launch per colour, in place): every iteration is one ping-pong step and two kernel launches.
+// lb = 1 / 2 is the temporally blocked form on blocks of lb^3 leaves (hns_sorblock.hip): every step is one launch -- n4 of four iterations while k_max = 4 and four are
+// left, then n2 of two, then n1 = 1 for an odd iteration left over (the two-iteration kernel with two colour sweeps instead of four), in that order.
+struct SorSchedule {
+	int lb = 0, k_max = 0;
+	int n4 = 0, n2 = 0, n1 = 0;
+	int iterations() const { return 4 * n4 + 2 * n2 + n1; }
+	int steps() const { return n4 + n2 + n1; }                          // src -> dst ping-pong steps: their parity is result_in_b
+	int step(int i) const { return i < n4 ? 4 : (i < n4 + n2 ? 2 : 1); }  // iterations of step i
+	int launches() const { return lb ? steps() : 2 * steps(); }         // kernel launches
+	int iterations_per_launch() const { return lb && iterations() >= 2 ? k_max : 1; }
+	bool one_blocked_launch() const { return lb && steps() == 1; }
+};
+inline SorSchedule sor_schedule(int lb, int k_max, int iterations) {
+	SorSchedule s;
+	if (iterations < 1) return s;
+	if (!lb) {
+		s.n1 = iterations;
+		return s;
+	}
+	s.lb = lb, s.k_max = k_max;
+	s.n4 = k_max >= 4 ? iterations / 4 : 0;
+	s.n2 = (iterations - 4 * s.n4) / 2;
+	s.n1 = iterations & 1;
+	return s;
+}
+
 // makes `device` current for the scope (allocations, frees and synchronisation of pooled memory belong to ITS device,
 // whatever the calling thread has current)
 struct DeviceScope {
@@ -243,6 +282,18 @@ struct hns_sim {
 	// optional hipEvent bracketing of the pressure hot loop (hns_sim_timing), on the stream the kernels run on
 	hns::EventGroups solve_ev{2};  // start/stop pairs
 	long long timed_launches = 0;
+	int solve_begin(void* stream) {  // the bracket round one solve: sim_pressure (hns_api.hip) and the controlled loop (hns_diagnostics.hip)
+		if (hipEvent_t* timed = solve_ev.current()) HNS_HIP(hipEventRecord(timed[0], (hipStream_t)stream));
+		return HNS_OK;
+	}
+	int solve_end(void* stream, int iterations) {
+		if (hipEvent_t* timed = solve_ev.current()) {
+			HNS_HIP(hipEventRecord(timed[1], (hipStream_t)stream));
+			solve_ev.advance();
+			timed_launches += iterations;
+		}
+		return HNS_OK;
+	}
 	hns::EventGroups stage_ev{6};  // hns_sim_stage_timing: also bracket the five stages of hns_sim_substep / hns_sim_core_substep (six boundaries per substep)
 	hipStream_t xfer = nullptr;  // transfer stream + hand-off events of the pipelined operator path (hns_api.hip: Cook)
 	hipEvent_t xev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -372,7 +423,6 @@ int hns_grid_upload_schedule(hns_grid* g);  // launch-order tables for the curre
 // implemented in hns_sorblock.hip: the temporally blocked SOR form (k iterations per launch)
 int hns_grid_build_blocks(hns_grid* g);     // records of the 16^3-voxel blocks of the grid's launch range
 void hns_grid_retire_blocks(hns_grid* g);   // superseded records back to the pool (grid destruction / rebuild only)
-int hns_rbgs_block_shape(hns_grid* g, int* k_max);  // block edge in leaves this grid is swept with (0: not by this form) and the iterations per launch
-bool hns_rbgs_block_lean(hns_grid* g, int lb, int k);  // is that launch the lean form of the kernel (row state in LDS, three workgroups per CU)?
+hns::SorSchedule hns_rbgs_schedule(hns_grid* g, int iterations);  // what hns_rbgs_iterate launches for `iterations` over the grid's launch range under the current options (may build the block records)
 int hns_rbgs_block_launch(hns_grid* g, int lb, int k, bool src_is_zero, const float* div, const float* src, float* dst, float dx2, float omega, void* stream);
 int hns_grid_host_tables(const hns_grid* g);  // make topo.nbr27 / topo.hash valid on the host

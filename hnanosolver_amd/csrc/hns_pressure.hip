@@ -556,74 +556,53 @@ int hns_dev_rbgs_iterate(hns_grid* g, const float* div, float* p_a, float* p_b, 
 	return hns_rbgs_iterate(g, div, p_a, p_b, dx, omega, iterations, result_in_b, stream, false);
 }
 
-// from_zero: the solve starts from p = 0 (the reference never warm-starts, HNanoSolver.cu:113 / PressureProjection.cu:35) and
-// p_a's content is irrelevant: the first blocked launch does not read it, so the caller need not clear it either.
+// Walks the solve's schedule (hns_internal.hpp: SorSchedule; hns_grid_rbgs_plan below describes the same value), ping-ponging p_a / p_b once per step:
+// *result_in_b is the parity of the steps. Blocked (hns_sorblock.hip): one launch per step, p read and written once per launch. A launch range -- a multi-GPU rank's
+// boundary / interior leaves -- must never go through the colour form: its copy of the whole field would undo what the launch over the neighbouring range has stored.
+// from_zero: the solve starts from p = 0 (the reference never warm-starts, HNanoSolver.cu:113 / PressureProjection.cu:35) and p_a's content is irrelevant: the first
+// blocked launch does not read it (its ZERO kernel), the colour form is handed zeros, and a solve that launches nothing leaves p_a = 0.
 int hns_rbgs_iterate(hns_grid* g, const float* div, float* p_a, float* p_b, float dx, float omega, int iterations, int* result_in_b, void* stream,
                      bool from_zero) {
 	if (int rc = check_grid(g, "hns_dev_rbgs_iterate")) return rc;
 	NULLCHK(!div || !p_a || !p_b, "hns_dev_rbgs_iterate");
 	if (p_a == p_b) return fail(HNS_ERR_INVALID_ARGUMENT, "hns_dev_rbgs_iterate: p_a and p_b must be distinct buffers");
 	if (iterations < 0) return fail(HNS_ERR_INVALID_ARGUMENT, "hns_dev_rbgs_iterate: negative iteration count");
-	if (result_in_b) *result_in_b = iterations & 1;
+	const SorSchedule s = hns_rbgs_schedule(g, iterations);
+	if (result_in_b) *result_in_b = s.steps() & 1;
 	hipStream_t st = (hipStream_t)stream;
+	const size_t field_bytes = sizeof(float) * 512 * (size_t)g->topo.n_leaves;
 	if (g->n_active == 0 || iterations == 0) {
-		if (from_zero) HNS_HIP(hipMemsetAsync(p_a, 0, sizeof(float) * 512 * (size_t)g->topo.n_leaves, st));  // the result is p_a = 0
+		if (from_zero) HNS_HIP(hipMemsetAsync(p_a, 0, field_bytes, st));
 		return HNS_OK;
 	}
 	const float dx2 = dx * dx;  // Kernel.cu:608
-	const GridDev gd = g->dev();
-	// Temporally blocked (hns_sorblock.hip): k iterations per launch, p read and written once per launch -- 16^3 blocks two at a time, one-leaf blocks (small grids) two
-	// or four; an odd iteration left over is one more launch of the same kernel with two colour sweeps. (A launch range -- a multi-GPU rank's boundary / interior leaves --
-	// must never go through the two-launch form below: its copy of the whole field would undo what the launch over the neighbouring range has stored.)
-	int k_max = 0;
-	const int lb = options().rbgs.load() == kRbgsColor ? 0 : hns_rbgs_block_shape(g, &k_max);
 	float* src = p_a;
 	float* dst = p_b;
-	int left = iterations, launches = 0;
-	bool zero = from_zero;
-	while (lb && left >= 2) {
-		const int k = (k_max >= 4 && left >= 4) ? 4 : 2;
-		if (int rc = hns_rbgs_block_launch(g, lb, k, zero, div, src, dst, dx2, omega, stream)) return rc;
-		std::swap(src, dst);
-		left -= k, ++launches, zero = false;
+	if (s.lb) {
+		for (int i = 0; i < s.steps(); ++i, std::swap(src, dst))
+			if (int rc = hns_rbgs_block_launch(g, s.lb, s.step(i), from_zero && i == 0, div, src, dst, dx2, omega, stream)) return rc;
+	} else {
+		if (from_zero) HNS_HIP(hipMemsetAsync(src, 0, field_bytes, st));  // the colour form reads its input
+		const GridDev gd = g->dev();
+		for (int i = 0; i < s.steps(); ++i, std::swap(src, dst))
+			if (int rc = launch_color_iteration(g, gd, div, src, dst, dx2, omega, st)) return rc;
 	}
-	if (lb && left) {
-		if (int rc = hns_rbgs_block_launch(g, lb, 1, zero, div, src, dst, dx2, omega, stream)) return rc;
-		std::swap(src, dst);
-		--left, ++launches, zero = false;
-	}
-	if (left && zero) {  // the two-launch form reads its input: give it the zeros
-		HNS_HIP(hipMemsetAsync(src, 0, sizeof(float) * 512 * (size_t)g->topo.n_leaves, st));
-		zero = false;
-	}
-	for (; left; --left, ++launches) {
-		if (int rc = launch_color_iteration(g, gd, div, src, dst, dx2, omega, st)) return rc;
-		std::swap(src, dst);
-	}
-	if (result_in_b) *result_in_b = launches & 1;
 	return launch_status("hns_dev_rbgs_iterate");
 }
 
 int hns_grid_rbgs_plan(hns_grid* g, int iterations, char* description, uint64_t description_bytes, int* launches, int* iterations_per_launch) {
 	if (int rc = check_grid(g, "hns_grid_rbgs_plan")) return rc;
 	if (iterations < 0) return fail(HNS_ERR_INVALID_ARGUMENT, "hns_grid_rbgs_plan: negative iteration count");
-	int k_max = 0;
-	const int lb = (iterations >= 1 && options().rbgs.load() != kRbgsColor) ? hns_rbgs_block_shape(g, &k_max) : 0;
-	char buf[256];
-	int n = 0, k = 1, left = iterations;
-	if (lb) {
-		while (left >= 2) left -= (k_max >= 4 && left >= 4) ? 4 : 2, ++n;
-		if (left) --left, ++n;  // (an odd iteration left over: the same kernel, one iteration)
-		k = iterations >= 2 ? k_max : 1;
-		snprintf(buf, sizeof(buf), "k_rbgs_block%s<%d,%d>: %d red+black iterations per launch on %s blocks with a %d-voxel halo, p read and written once per launch%s", lb == 2 ? "_xy" : "", lb, k_max, k_max,
-		         lb == 1 ? "one-leaf (8^3-voxel)" : "16^3-voxel", 2 * k_max, lb == 2 ? " (rows in LDS, three workgroups per CU, the sweep threads fetch their own rows)" : "");
-	} else {
-		snprintf(buf, sizeof(buf), "k_rbgs_color: two launches per iteration, in place (the reference's decomposition)");
+	const SorSchedule s = hns_rbgs_schedule(g, iterations);
+	if (description && description_bytes) {
+		if (s.lb)
+			snprintf(description, description_bytes, "k_rbgs_block%s<%d,%d>: %d red+black iterations per launch on %s blocks with a %d-voxel halo, p read and written once per launch%s", s.lb == 2 ? "_xy" : "",
+			         s.lb, s.k_max, s.k_max, s.lb == 1 ? "one-leaf (8^3-voxel)" : "16^3-voxel", 2 * s.k_max, s.lb == 2 ? " (rows in LDS, three workgroups per CU, the sweep threads fetch their own rows)" : "");
+		else
+			snprintf(description, description_bytes, "k_rbgs_color: two launches per iteration, in place (the reference's decomposition)");
 	}
-	n += 2 * left;  // (what is left goes through the two-launch form)
-	if (description && description_bytes) snprintf(description, description_bytes, "%s", buf);
-	if (launches) *launches = n;
-	if (iterations_per_launch) *iterations_per_launch = k;
+	if (launches) *launches = s.launches();
+	if (iterations_per_launch) *iterations_per_launch = s.iterations_per_launch();
 	return HNS_OK;
 }
 

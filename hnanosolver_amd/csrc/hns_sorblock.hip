@@ -29,6 +29,10 @@
 // row fetches it; the block is stored in memory order; and only the part of the tile that can reach the block in 2K sweeps is fetched
 // and computed. How it got there (the 16^3 rows-in-registers form, the parity-sorted "lean" form and its LDS-DMA variant, each with its
 // measurements): DESIGN_HISTORY.md, profiles/r03_sorblock_notes.txt 10-12, profiles/r05_sorblock_notes.txt.
+//
+// Host part (at the end): the block records of the 16^3 form; hns_rbgs_schedule -- which form sweeps a grid's launch range and in which launches (hns_internal.hpp:
+// SorSchedule), the one caller of hns_rbgs_block_shape --; and one launcher per kernel, launch_leaf_blocks<K, NS> and launch_xy_blocks<M>, under the three entry points
+// hns_rbgs_block_launch (a step of hns_rbgs_iterate), hns_rbgs_block_pack_launch and hns_rbgs_block_mirror_launch (the sweeps of a multi-GPU rank).
 #include "hns_device.hpp"
 #include "hns_flags.hpp"
 
@@ -61,6 +65,15 @@ struct SbGeo {
 };
 
 constexpr float kInv6 = 0.166666667f;  // Kernel.cu:609
+
+// the update of one voxel in both blocked sweeps: X = its value, d = div * dx^2, ok = all ones if its leaf exists, else 0
+template <bool MASKED>
+__device__ __forceinline__ float sb_update(float xp, float xm, float yp, float ym, float zp, float zm, float d, float X, float omega, unsigned ok) {
+	const float pGS = ((xp + xm + yp + ym + zp + zm) - d) * kInv6;  // Kernel.cu:621 (d = div * dx^2)
+	const float cand = X + omega * (pGS - X);                      // Kernel.cu:622
+	// a voxel of an absent leaf stays +0 (as a bit mask, not a select: the compiler turns selects here into a branch per voxel)
+	return MASKED ? __uint_as_float(__float_as_uint(cand) & ok) : cand;
+}
 
 // a thread's z-row for the length of the launch, split by colour (static indexing only: the arrays live in registers)
 template <int HALF, int C>
@@ -126,11 +139,8 @@ __device__ __forceinline__ void sb_sweep(Row& r, SbLds<LB, K>& L, const int i, c
 				if (j < jlo || j >= jhi) continue;
 				const float below = j > 0 ? Y[j > 0 ? j - 1 : 0] : 0.0f, above = j + 1 < HALF ? Y[j + 1 < HALF ? j + 1 : 0] : 0.0f;
 				const float zm = up ? Y[j] : below, zp = up ? above : Y[j];
-				const float pGS = ((xp[e] + xm[e] + yp[e] + ym[e] + zp + zm) - dX[j]) * kInv6;  // Kernel.cu:621 (dX = div * dx^2)
-				const float cand = X[j] + omega * (pGS - X[j]);                                   // Kernel.cu:622
 				const int cz = (2 * j - H + 8) >> 3;  // leaf cell of this voxel along z: the same for both parities
-				// a voxel of an absent leaf stays +0 (as a bit mask, not a select: the compiler turns selects here into a branch per voxel)
-				X[j] = MASKED ? __uint_as_float(__float_as_uint(cand) & r.ok[cz]) : cand;
+				X[j] = sb_update<MASKED>(xp[e], xm[e], yp[e], ym[e], zp, zm, dX[j], X[j], omega, r.ok[cz]);
 			}
 			__builtin_amdgcn_sched_barrier(0);
 		}
@@ -377,10 +387,8 @@ __device__ __forceinline__ void sb_sweep_xy(Row& r, SbLdsXY& L, const int bi, co
 				if (j < jlo || j >= jhi) continue;
 				const float below = j > 0 ? Y[j > 0 ? j - 1 : 0] : 0.0f, above = j + 1 < HALF ? Y[j + 1 < HALF ? j + 1 : 0] : 0.0f;
 				const float zm = up ? Y[j] : below, zp = up ? above : Y[j];
-				const float pGS = ((xp[e] + xm[e] + yp[e] + ym[e] + zp + zm) - dX[j]) * kInv6;  // Kernel.cu:621 (dX = div * dx^2)
-				const float cand = X[e] + omega * (pGS - X[e]);                                   // Kernel.cu:622
 				const int cz = (2 * j - H + 8) >> 3;
-				X[e] = MASKED ? __uint_as_float(__float_as_uint(cand) & r.ok[cz]) : cand;
+				X[e] = sb_update<MASKED>(xp[e], xm[e], yp[e], ym[e], zp, zm, dX[j], X[e], omega, r.ok[cz]);
 			}
 			v4f32 o4 = v4f32{X[0], X[1], X[2], X[3]};
 			if (4 * q < jlo || 4 * q + 4 > jhi) asm volatile("" : "+v"(o4));
@@ -716,76 +724,89 @@ void hns_grid_retire_blocks(hns_grid* g) {  // (the grid is being destroyed or r
 	g->sb_retired.clear();
 }
 
-// Can this grid be swept by the blocked form, and with which block edge (in leaves)? 0 = no.
-int hns_rbgs_block_shape(hns_grid* g, int* k_max) {
+// Can this grid be swept by the blocked form, and with which block edge (in leaves)? 0 = no. *k_max: the most iterations one launch does.
+static int hns_rbgs_block_shape(hns_grid* g, int* k_max) {
 	*k_max = 0;
 	// fields addressable with 32-bit byte offsets. A launch range (a multi-GPU rank's boundary / interior / owned leaves) is swept like a
 	// whole grid: blocks that hold a leaf of the range, the other leaves of the grid as sources only (hns_grid_build_blocks). The CALLER
 	// vouches that p within 2K voxels of the range, and div within 2K - 1, are current in the leaves outside it (hns_dist_*.hip).
 	if (g->n_active == 0 || g->topo.n_leaves > 2000000) return 0;
-	int lb = options().sor_block_lb.load(), k = 0;
+	int lb = options().sor_block_lb.load();
 	// by size (profiles/r03_sor_forms.txt): one-leaf blocks while the grid cannot fill the chip with 16^3 blocks, four iterations per
 	// launch while even those leave most of it idle
 	if (lb == 0) lb = g->n_active <= 600 ? 1 : 2;  // (512 leaves: 2.97 against 3.36 us per iteration; 729: 3.65 against 3.49)
 	if (lb != 1 && lb != 2) return 0;
 	if (lb == 1 && !g->d_blk) return 0;
 	if (lb == 2 && (hns_grid_build_blocks(g) != HNS_OK || g->n_sb == 0)) return 0;
-	if (k == 0) k = (lb == 1 && g->n_active <= 300) ? 4 : 2;
-	if (k != 2 && !(k == 4 && lb == 1)) k = 2;
-	*k_max = k;
+	*k_max = (lb == 1 && g->n_active <= 300) ? 4 : 2;
 	return lb;
 }
 
-// 16^3 blocks are swept by the XY form (k_rbgs_block_xy: row state in LDS, three workgroups per CU, the thread that sweeps a row fetches it), one-leaf blocks by the
-// rows-in-registers form (k_rbgs_block<1, K>). The forms this replaced -- 16^3 blocks with the rows in registers, the parity-sorted lean form and its LDS-DMA variant -- are
-// history with their measurements: DESIGN_HISTORY.md, profiles/r03_sorblock_notes.txt, r05_sorblock_notes.txt.
-bool hns_rbgs_block_lean(hns_grid*, int lb, int k) { return lb == 2 && k == 2; }
+// The blocked form's schedule for the grid's launch range, whatever option "rbgs" says: the one place that asks for a block shape. A solve without an iteration
+// asks for none, and so builds no records.
+static SorSchedule blocked_schedule(hns_grid* g, int iterations) {
+	int k_max = 0;
+	const int lb = iterations >= 1 ? hns_rbgs_block_shape(g, &k_max) : 0;
+	return sor_schedule(lb, k_max, iterations);
+}
 
-// one launch: k iterations src -> dst
-int hns_rbgs_block_launch(hns_grid* g, int lb, int k, bool src_is_zero, const float* div, const float* src, float* dst, float dx2, float omega, void* stream) {
-	hipStream_t st = (hipStream_t)stream;
+// what hns_rbgs_iterate launches for `iterations` under the current options (hns_internal.hpp: SorSchedule)
+SorSchedule hns_rbgs_schedule(hns_grid* g, int iterations) {
+	return options().rbgs.load() == kRbgsColor ? sor_schedule(0, 0, iterations) : blocked_schedule(g, iterations);
+}
+
+// are two iterations over the grid's launch range ONE launch in 16^3 blocks (the XY form: the one form that can pack a rank's messages, or mirror, as it stores)? The packing
+// and the chained sweeps are blocked launches of their own and never go through hns_rbgs_iterate, so option "rbgs" has no say.
+static bool two_in_one_xy_launch(hns_grid* g) {
+	const SorSchedule s = blocked_schedule(g, 2);
+	return s.one_blocked_launch() && s.lb == 2;
+}
+
+// One launch of a one-leaf block kernel (k_rbgs_block<1, K>: rows in registers) over the grid's launch range: NS colour sweeps on the tile of K iterations.
+template <int K, int NS>
+static void launch_leaf_blocks(hns_grid* g, bool src_is_zero, const float* div, const float* src, float* dst, float dx2, float omega, hipStream_t st) {
 	const unsigned bytes = (unsigned)((size_t)g->topo.n_leaves * 2048u);
+	auto* kernel = src_is_zero ? k_rbgs_block<1, K, true, NS> : k_rbgs_block<1, K, false, NS>;
+	hipLaunchKernelGGL(kernel, dim3((unsigned)g->n_active), dim3(SbGeo<1, K>::NT), 0, st, (const int*)g->d_blk, div, src, dst, bytes, dx2, omega);
+}
+
+// One launch of the 16^3 form (k_rbgs_block_xy) over the grid's block records, two iterations (four colour sweeps) or one (two), with the mirror M: NoMirror, or what
+// a multi-GPU rank's sweep stores besides (hns_flags.hpp: PackMirror, PhaseMirror). The entry points below name what went wrong in their own words.
+enum class XYLaunch { done, no_records, bad_iterations };
+template <class M>
+static XYLaunch launch_xy_blocks(hns_grid* g, int iterations, bool src_is_zero, const float* div, const float* src, float* dst, float dx2, float omega, const M& m, hipStream_t st) {
 	// (the records' address and count as ONE snapshot: another host thread sharing the grid may be rebuilding them -- an option changed --,
 	// and a superseded table stays valid until the grid goes, but its count must be its own)
-	const int* sb_tab;
+	const int* tab;
 	uint64_t n_sb;
 	{
 		std::lock_guard<std::mutex> lock(g->build_mutex);
-		sb_tab = (const int*)g->d_sb_tab, n_sb = g->n_sb;
+		tab = (const int*)g->d_sb_tab, n_sb = g->n_sb;
 	}
-	if (lb == 2 && (!sb_tab || !n_sb)) return fail(HNS_ERR_RUNTIME, "hns_rbgs_block_launch: no block records");
-#define SB_LAUNCH(K_)                                                                                                                                                        \
-	do {                                                                                                                                                                      \
-		if (src_is_zero)                                                                                                                                                      \
-			hipLaunchKernelGGL((k_rbgs_block<1, K_, true>), dim3((unsigned)g->n_active), dim3(SbGeo<1, K_>::NT), 0, st, (const int*)g->d_blk, div, src, dst, bytes, dx2, omega);  \
-		else                                                                                                                                                                  \
-			hipLaunchKernelGGL((k_rbgs_block<1, K_, false>), dim3((unsigned)g->n_active), dim3(SbGeo<1, K_>::NT), 0, st, (const int*)g->d_blk, div, src, dst, bytes, dx2, omega); \
-	} while (0)
-	if (lb == 1 && k == 2) SB_LAUNCH(2);
-	else if (lb == 1 && k == 4) SB_LAUNCH(4);
-	else if (lb == 1 && k == 1) {  // an odd iteration left over: the tile of two iterations, two colour sweeps
-		if (src_is_zero)
-			hipLaunchKernelGGL((k_rbgs_block<1, 2, true, 2>), dim3((unsigned)g->n_active), dim3(SbGeo<1, 2>::NT), 0, st, (const int*)g->d_blk, div, src, dst, bytes, dx2, omega);
-		else
-			hipLaunchKernelGGL((k_rbgs_block<1, 2, false, 2>), dim3((unsigned)g->n_active), dim3(SbGeo<1, 2>::NT), 0, st, (const int*)g->d_blk, div, src, dst, bytes, dx2, omega);
+	if (!tab || !n_sb) return XYLaunch::no_records;
+	if (iterations != 1 && iterations != 2) return XYLaunch::bad_iterations;
+	const unsigned bytes = (unsigned)((size_t)g->topo.n_leaves * 2048u);
+	auto* kernel = iterations == 2 ? (src_is_zero ? k_rbgs_block_xy<true, M, 4> : k_rbgs_block_xy<false, M, 4>) : (src_is_zero ? k_rbgs_block_xy<true, M, 2> : k_rbgs_block_xy<false, M, 2>);
+	hipLaunchKernelGGL(kernel, dim3((unsigned)n_sb), dim3(SbGeo<2, 2>::NT), 0, st, tab, tab + (size_t)n_sb * 64, div, src, dst, bytes, dx2, omega, m);
+	return XYLaunch::done;
+}
+
+// one launch: k iterations src -> dst (k = 1: an odd iteration left over, two colour sweeps on the tile of two iterations)
+int hns_rbgs_block_launch(hns_grid* g, int lb, int k, bool src_is_zero, const float* div, const float* src, float* dst, float dx2, float omega, void* stream) {
+	hipStream_t st = (hipStream_t)stream;
+	if (lb == 1 && k == 2) launch_leaf_blocks<2, 4>(g, src_is_zero, div, src, dst, dx2, omega, st);
+	else if (lb == 1 && k == 4) launch_leaf_blocks<4, 8>(g, src_is_zero, div, src, dst, dx2, omega, st);
+	else if (lb == 1 && k == 1) launch_leaf_blocks<2, 2>(g, src_is_zero, div, src, dst, dx2, omega, st);
+	else {
+		const XYLaunch r = lb == 2 ? launch_xy_blocks(g, k, src_is_zero, div, src, dst, dx2, omega, NoMirror{}, st) : XYLaunch::bad_iterations;
+		if (r == XYLaunch::no_records) return fail(HNS_ERR_RUNTIME, "hns_rbgs_block_launch: no block records");
+		if (r != XYLaunch::done) return fail(HNS_ERR_INVALID_ARGUMENT, "hns_rbgs_block_launch: unsupported block shape");
 	}
-	else if (lb == 2 && (k == 2 || k == 1)) {
-#define XY_LAUNCH(ZERO_, NS_) hipLaunchKernelGGL((k_rbgs_block_xy<ZERO_, NoMirror, NS_>), dim3((unsigned)n_sb), dim3(SbGeo<2, 2>::NT), 0, st, sb_tab, sb_tab + (size_t)n_sb * 64, div, src, dst, bytes, dx2, omega, NoMirror{})
-		if (k == 2 && src_is_zero) XY_LAUNCH(true, 4);
-		else if (k == 2) XY_LAUNCH(false, 4);
-		else if (src_is_zero) XY_LAUNCH(true, 2);
-		else XY_LAUNCH(false, 2);
-#undef XY_LAUNCH
-	} else return fail(HNS_ERR_INVALID_ARGUMENT, "hns_rbgs_block_launch: unsupported block shape");
-#undef SB_LAUNCH
 	return HNS_OK;
 }
 
-// is the grid's launch range swept two iterations per launch in 16^3 blocks by the XY form (the one form that can pack a rank's messages as it stores)?
-extern "C" __attribute__((visibility("hidden"))) bool hns_rbgs_block_packable(hns_grid* g) {
-	int k = 0;
-	return g && g->n_active && hns_rbgs_block_shape(g, &k) == 2 && k == 2;
-}
+// would hns_rbgs_block_pack_launch launch on this grid's range?
+extern "C" __attribute__((visibility("hidden"))) bool hns_rbgs_block_packable(hns_grid* g) { return g && g->n_active && two_in_one_xy_launch(g); }
 
 // The sweep of an exchanged pressure loop that packs its own messages (hns_flags.hpp: PackMirror), two iterations per launch over the grid's launch range (the rank's
 // boundary leaves, or -- round 6 -- all of its owned leaves); *done = false and nothing launched where that range is not swept in 16^3 blocks by the XY form.
@@ -794,23 +815,9 @@ extern "C" __attribute__((visibility("hidden"))) int hns_rbgs_block_pack_launch(
 	*done = false;
 	if (!hns_rbgs_block_packable(g)) return HNS_OK;
 	if (int rc = hns_grid_build_blocks(g)) return rc;  // (the records of THIS launch range under the current options: ADVICE r5 -- not whatever table a previous launch left)
-	const unsigned bytes = (unsigned)((size_t)g->topo.n_leaves * 2048u);
-	const int* tab;
-	uint64_t n_sb;
-	{
-		std::lock_guard<std::mutex> lock(g->build_mutex);
-		tab = (const int*)g->d_sb_tab, n_sb = g->n_sb;
-	}
-	if (!tab || !n_sb) return HNS_OK;
-	const float dx2 = dx * dx;  // Kernel.cu:608
-#define XY_LAUNCH(ZERO_, NS_) hipLaunchKernelGGL((k_rbgs_block_xy<ZERO_, PackMirror, NS_>), dim3((unsigned)n_sb), dim3(SbGeo<2, 2>::NT), 0, (hipStream_t)stream, tab, tab + (size_t)n_sb * 64, div, src, dst, bytes, dx2, omega, *m)
-	if (iterations != 1 && iterations != 2) return fail(HNS_ERR_INVALID_ARGUMENT, "hns_rbgs_block_pack_launch: one or two iterations per launch");
-	if (iterations == 2 && src_is_zero) XY_LAUNCH(true, 4);
-	else if (iterations == 2) XY_LAUNCH(false, 4);
-	else if (src_is_zero) XY_LAUNCH(true, 2);
-	else XY_LAUNCH(false, 2);
-#undef XY_LAUNCH
-	*done = true;
+	const XYLaunch r = launch_xy_blocks(g, iterations, src_is_zero, div, src, dst, dx * dx /* Kernel.cu:608 */, omega, *m, (hipStream_t)stream);
+	if (r == XYLaunch::bad_iterations) return fail(HNS_ERR_INVALID_ARGUMENT, "hns_rbgs_block_pack_launch: one or two iterations per launch");
+	*done = r == XYLaunch::done;
 	return HNS_OK;
 }
 
@@ -818,24 +825,9 @@ extern "C" __attribute__((visibility("hidden"))) int hns_rbgs_block_pack_launch(
 // that waits for the peers where it reads their values and delivers its own boundary values into their ghost voxels. 16^3 blocks only.
 extern "C" __attribute__((visibility("hidden"))) int hns_rbgs_block_mirror_launch(hns_grid* g, const float* div, const float* src, float* dst, float dx, float omega, bool src_is_zero,
                                                                                    const hns::PhaseMirror* m, void* stream, int iterations) {
-	int k = 0;
-	if (hns_rbgs_block_shape(g, &k) != 2 || k != 2) return fail(HNS_ERR_RUNTIME, "hns_rbgs_block_mirror_launch: this launch range is not swept in 16^3 blocks");
-	const unsigned bytes = (unsigned)((size_t)g->topo.n_leaves * 2048u);
-	const int* tab;
-	uint64_t n_sb;
-	{
-		std::lock_guard<std::mutex> lock(g->build_mutex);
-		tab = (const int*)g->d_sb_tab, n_sb = g->n_sb;
-	}
-	if (!tab || !n_sb) return fail(HNS_ERR_RUNTIME, "hns_rbgs_block_mirror_launch: no block records");
-	const float dx2 = dx * dx;  // Kernel.cu:608
-#define XY_LAUNCH(ZERO_, NS_) hipLaunchKernelGGL((k_rbgs_block_xy<ZERO_, PhaseMirror, NS_>), dim3((unsigned)n_sb), dim3(SbGeo<2, 2>::NT), 0, (hipStream_t)stream, tab, tab + (size_t)n_sb * 64, div, src, dst, bytes, dx2, omega, *m)
-	if (iterations != 1 && iterations != 2) return fail(HNS_ERR_INVALID_ARGUMENT, "hns_rbgs_block_mirror_launch: one or two iterations per launch");
-	if (iterations == 2 && src_is_zero) XY_LAUNCH(true, 4);
-	else if (iterations == 2) XY_LAUNCH(false, 4);
-	else if (src_is_zero) XY_LAUNCH(true, 2);
-	else XY_LAUNCH(false, 2);
-#undef XY_LAUNCH
+	if (!two_in_one_xy_launch(g)) return fail(HNS_ERR_RUNTIME, "hns_rbgs_block_mirror_launch: this launch range is not swept in 16^3 blocks");
+	const XYLaunch r = launch_xy_blocks(g, iterations, src_is_zero, div, src, dst, dx * dx /* Kernel.cu:608 */, omega, *m, (hipStream_t)stream);
+	if (r == XYLaunch::no_records) return fail(HNS_ERR_RUNTIME, "hns_rbgs_block_mirror_launch: no block records");
+	if (r == XYLaunch::bad_iterations) return fail(HNS_ERR_INVALID_ARGUMENT, "hns_rbgs_block_mirror_launch: one or two iterations per launch");
 	return HNS_OK;
 }
-

@@ -149,6 +149,68 @@ def test_result_buffer_is_the_one_result_in_b_names(leaves):
         assert in_b.value == (launches & 1), f"iterations = {iters}: result_in_b = {in_b.value} but the plan says {launches} launches"
 
 
+def schedule_steps(lb, k_max, iterations):
+    """ping-pong steps of a solve, from the rule in include/hns.h (hns_dev_rbgs_iterate): blocked, launches of four iterations while four per launch is the form and at
+    least four remain, then of two, then one for an odd iteration left over; the colour form, one step per iteration"""
+    if lb == 0:
+        return iterations
+    steps, left = 0, iterations
+    while k_max == 4 and left >= 4:
+        steps, left = steps + 1, left - 4
+    return steps + left // 2 + left % 2
+
+
+# leaves -> edge of the dense box in voxels, and per option the form it selects there: (block edge in leaves, iterations per launch); (0, 1) = the colour form.
+# The smallest grids on which each form is the default: four per launch up to 300 leaves, one-leaf blocks up to 600, 16^3 blocks beyond. Forcing the block edge
+# leaves the iterations per launch by size.
+PLAN_FORMS = {
+    8: (16, {(): (1, 4), ("sor_block_lb", 1): (1, 4), ("sor_block_lb", 2): (2, 2), ("rbgs", "color"): (0, 1)}),
+    343: (56, {(): (1, 2), ("sor_block_lb", 1): (1, 2), ("sor_block_lb", 2): (2, 2), ("rbgs", "color"): (0, 1)}),
+    729: (72, {(): (2, 2), ("sor_block_lb", 1): (1, 2), ("sor_block_lb", 2): (2, 2), ("rbgs", "color"): (0, 1)}),
+}
+
+
+@pytest.mark.parametrize("leaves", list(PLAN_FORMS))
+def test_plan_and_solve_agree_for_every_form(leaves):
+    """hns_grid_rbgs_plan and hns_dev_rbgs_iterate read one schedule: for every form (by size, either block edge forced, the colour form) and 0 .. 9 iterations the buffer
+    *result_in_b names holds the colour form's bits, result_in_b is the parity of the steps, and the plan reports those steps as launches (two per iteration for the
+    colour form), the form's iterations per launch and its kernel. Through the raw C ABI."""
+    import ctypes as C
+
+    lib = H.load_library()
+    R, forms = PLAN_FORMS[leaves]
+    origins = fields.dense_leaves(R)
+    assert len(origins) == leaves
+    grid = api.create_grid_from_leaves(origins, 1.0 / R)
+    n = leaves * 512
+    g = torch.Generator(device="cpu").manual_seed(leaves)
+    div = torch.randn(n, generator=g).cuda()
+    p0 = torch.randn(n, generator=g).cuda()
+    want = [solve(grid, div, p0, iters, rbgs="color") for iters in range(10)]
+    assert torch.equal(want[0], p0)
+    for option, (lb, k_max) in forms.items():
+        if option:
+            H.set_option(option[0], str(option[1]))
+        for iters in range(10):
+            p_a, p_b = p0.clone(), torch.full_like(p0, 7.0)
+            in_b = C.c_int(-1)
+            rc = lib.hns_dev_rbgs_iterate(grid.ptr, div.data_ptr(), p_a.data_ptr(), p_b.data_ptr(), C.c_float(0.013), C.c_float(1.93), iters, C.byref(in_b), D.current_stream())
+            torch.cuda.synchronize()
+            what = f"{leaves} leaves, {option}, {iters} iterations"
+            steps = schedule_steps(lb, k_max, iters)
+            assert rc == 0 and in_b.value == (steps & 1), f"{what}: result_in_b = {in_b.value}, {steps} steps"
+            assert torch.equal(p_b if in_b.value else p_a, want[iters]), f"{what}: the buffer named by result_in_b does not hold the result"
+            if iters == 0:
+                assert in_b.value == 0 and torch.equal(p_a, p0), f"{what}: p_a touched"
+            desc, launches, per = D.rbgs_plan(grid, iters)
+            assert launches == (steps if lb else 2 * iters), f"{what}: the plan says {launches} launches"
+            assert per == (k_max if lb and iters >= 2 else 1), f"{what}: the plan says {per} iterations per launch"
+            kernel = {0: "k_rbgs_color", 1: "k_rbgs_block<1,", 2: "k_rbgs_block_xy<2,"}[lb if iters else 0]  # (a solve of no iteration names no blocked kernel)
+            assert desc.startswith(kernel), f"{what}: {desc}"
+        if option:
+            H.set_option(option[0], None)
+
+
 @pytest.mark.parametrize("name", ["dense40", "plume", "scatter", "node_borders"])
 def test_blocked_sor_over_a_launch_range(name):
     """Round 4: the blocked form over a LAUNCH RANGE [first, first + count) of the grid's leaves (what a multi-GPU rank's
