@@ -126,6 +126,7 @@ SIGNATURES = {
     "hns_sim_advect": (_i, [_vp, C.POINTER(C.c_char_p), _i, _i, _f, _f, _vp]),
     "hns_sim_sample_points": (_i, [_vp, C.POINTER(C.c_char_p), _i, _i, _fp, _u64, C.POINTER(C.c_void_p), _vp]),
     "hns_sim_trace_points": (_i, [_vp, _fp, _u64, _f, _f, _i, _i, _vp, _vp]),
+    "hns_sim_splat_points": (_i, [_vp, C.POINTER(C.c_char_p), _i, _fp, _fp, C.POINTER(C.c_void_p), _u64, _i, _i, _vp, _vp, _vp]),
     "hns_sim_pressure_solve": (_i, [_vp, _i, _f, _vp]),
     "hns_sim_timing": (_i, [_vp, _i]),
     "hns_sim_pressure_time": (_i, [_vp, C.POINTER(C.c_float), C.POINTER(C.c_longlong)]),
@@ -154,6 +155,8 @@ SIGNATURES = {
     "hns_dev_advect_scalars_ahead": (_i, [_vp, _fp, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _i, _fp, _f, _f, _vp]),
     "hns_dev_sample_points": (_i, [_vp, C.POINTER(C.c_void_p), _ip, _i, _fp, _u64, C.POINTER(C.c_void_p), _vp]),
     "hns_dev_trace_points": (_i, [_vp, _fp, _fp, _u64, _f, _f, _i, _i, _vp, _vp]),
+    "hns_dev_splat_points": (_i, [_vp, C.POINTER(C.c_void_p), _ip, _i, _fp, C.POINTER(C.c_void_p), _u64, _i, _vp, _vp, _vp]),
+    "hns_grid_splat_points": (_i, [_vp, C.POINTER(C.c_void_p), _ip, _i, _fp, C.POINTER(C.c_void_p), _u64, _i, _vp, _i, _vp, C.POINTER(C.c_uint64)]),
     "hns_dev_divergence": (_i, [_vp, _fp, _fp, _f, _vp]),
     "hns_dev_rbgs_color": (_i, [_vp, _fp, _fp, _f, _f, _i, _vp]),
     "hns_dev_rbgs_iterate": (_i, [_vp, _fp, _fp, _fp, _f, _f, _i, _ip, _vp]),

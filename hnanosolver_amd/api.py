@@ -319,3 +319,25 @@ def Divergence(data: GridIndexedData, voxelSize: float, stream=None, handle: Opt
     h = handle or _grid_for(data, voxelSize)
     fields, n, keep = data._fields()
     _raise(lib.hns_divergence(h.ptr, fields, n, float(voxelSize), _stream(stream)))
+
+
+def splat_points_host(grid: IndexGridHandle, fields, xyz, values, log2_quantum: int = -32, masks=None, activate: bool = True, status=None) -> int:
+    """Host mirror of ``device.splat_points`` / ``device.Sim.splat`` (``hns_grid_splat_points``): the point values `values` (one (n,) or (n, 3) float32 array per field)
+    at the index-space positions xyz ((n, 3) float32) added IN PLACE into `fields` ((N,) or (N, 3) C-contiguous float32 arrays), with the device's integer arithmetic;
+    works on host-only grids. masks: None, or leaf_count x 64 uint8, in which (with activate) the bit of every landed tap of positive weight is set; status: None, or n
+    uint8 receiving the landed taps of each point. Returns the number of (point, component, tap) terms that landed but were not accepted."""
+    xyz = np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
+    vals = [np.ascontiguousarray(v, dtype=np.float32) for v in values]
+    for a in list(fields) + ([] if masks is None else [masks]) + ([] if status is None else [status]):
+        if not a.flags["C_CONTIGUOUS"] or not a.flags["WRITEABLE"]:
+            raise TypeError("splat_points_host: fields, masks and status must be C-contiguous writable arrays")
+    k = len(fields)
+    nc = [3 if (f.ndim == 2 and f.shape[1] == 3) else 1 for f in fields]
+    dst = (C.c_void_p * max(1, k))(*[f.ctypes.data for f in fields])
+    src = (C.c_void_p * max(1, k))(*[v.ctypes.data for v in vals])
+    rejected = C.c_uint64(0)
+    _raise(lib.hns_grid_splat_points(grid.ptr, dst, (C.c_int * max(1, k))(*nc), k, xyz.ctypes.data, src, xyz.shape[0], int(log2_quantum),
+                                     None if masks is None else masks.ctypes.data, int(bool(activate)), None if status is None else status.ctypes.data,
+                                     C.byref(rejected)))
+    return int(rejected.value)
+

@@ -65,7 +65,7 @@ extern "C" void hns_sim_destroy(hns_sim* s) {
 	delete s;
 }
 
-// Frees the device-resident state operator calls left with the grid (see make_sim below).
+// Frees the device-resident state operator calls left with the grid (see make_sim below) and the accumulator of hns_dev_splat_points.
 extern "C" int hns_grid_release_cache(hns_grid* g) {
 	if (!g) return fail(HNS_ERR_INVALID_ARGUMENT, "hns_grid_release_cache: null grid");
 	std::vector<hns_sim*> drop;
@@ -84,6 +84,7 @@ extern "C" int hns_grid_release_cache(hns_grid* g) {
 		s->cached = false;
 		hns_sim_destroy(s);
 	}
+	hns_grid_free_splat(g);
 	return HNS_OK;
 }
 

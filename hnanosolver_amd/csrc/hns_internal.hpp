@@ -258,6 +258,12 @@ struct hns_grid {
 	// hns_dev_field_stats / hns_dev_residual (hns_diagnostics.hip): the table of per-leaf partial records, an arena allocation of its own made on first use
 	void* d_diag = nullptr;
 	size_t diag_bytes = 0;
+	// hns_dev_splat_points (hns_splat.hip): the fixed-point accumulator -- splat_channels int64 channels per voxel, then one touched word per leaf --, an arena allocation of
+	// its own made on first use and all zero between calls; splat_dirty: it must be cleared before its next use (fresh from the pool, or a call failed half way)
+	void* d_splat = nullptr;
+	size_t splat_bytes = 0;
+	int splat_channels = 0;
+	bool splat_dirty = false;
 	std::mutex build_mutex;              // guards the tables built on first use (block records): cooks from several host threads may share a grid
 	std::mutex host_mutex;               // guards the lazy host copy of the device-built tables and sim_cache
 	std::vector<hns_sim*> sim_cache;     // device-resident state kept between operator calls (hns_api.hip: make_sim)
@@ -368,6 +374,7 @@ namespace hns { int check_activity_fields(const hns_sim* s, const hns_activity_f
 int hns_sim_pressure_controlled(hns_sim* s, int max_iterations, float voxel_size, float omega, void* stream);
 int hns_refuse_capture(void* stream, const char* who);
 void hns_sim_free_diagnostics(hns_sim* s);  // (hns_sim_destroy)
+void hns_grid_free_splat(hns_grid* g);       // hns_splat.hip: the grid's accumulator back to the pool (hns_grid_release_cache, and through it hns_grid_destroy)
 
 // the sim's buffers over one arena (hns_api.hip): bytes an arena needs for n voxels, and the slices of `arena` for them (sets n, every buffer pointer, d_dig, p_result)
 size_t hns_sim_arena_need(const hns_sim* s, uint64_t n);

@@ -175,6 +175,28 @@ def trace_points(grid: IndexGridHandle, vel, xyz, dt: float, inv_dx: float, orde
     return xyz
 
 
+def _u64_ptr(t) -> int:
+    if t is None:
+        return 0
+    if not t.is_cuda or t.dtype != _torch().int64 or not t.is_contiguous() or t.numel() < 1:
+        raise TypeError("expected a contiguous int64 tensor of one element on a HIP device")
+    return t.data_ptr()
+
+
+def splat_points(grid: IndexGridHandle, fields: Sequence, xyz, values: Sequence, log2_quantum: int = -32, status=None, rejected=None):
+    """The transpose of ``sample_points`` (``hns_dev_splat_points``): every point adds weight * value to the eight voxels of its cell, IN PLACE into `fields` -- up to
+    eight (N,) float and (N, 3) Vec3f tensors in any mix -- from values[i], (n,) or (n, 3) like its field, at the positions xyz ((n, 3) float32, index space). Terms are
+    rounded once to multiples of 2^log2_quantum and summed as 64-bit integers, so the result does not depend on the order the atomics retire in and equals
+    ``api.splat_points_host`` in every byte. status: None or a uint8 tensor of n bytes, the taps of each point that landed in a leaf (0 .. 8); rejected: None or an int64
+    tensor of one element the call adds the number of landed but unaccepted terms to (NaN, inf, beyond 2^62 quanta). Asynchronous on the current stream."""
+    k = len(fields)
+    dst = (C.c_void_p * max(1, k))(*[_ptr(t) for t in fields])
+    src = (C.c_void_p * max(1, k))(*[_ptr(t) for t in values])
+    _raise(lib.hns_dev_splat_points(grid.ptr, dst, (C.c_int * max(1, k))(*[_ncomp(f) for f in fields]), k, _ptr(xyz), src, xyz.shape[0], int(log2_quantum),
+                                    _byte_ptr(status), _u64_ptr(rejected), current_stream()))
+    return fields
+
+
 def stats_buffer(n_records: int = 1):
     """Device memory for `n_records` hns_stats records (a uint8 tensor; ``read_stats`` brings it to the host)."""
     return _torch().zeros(n_records * leafio.STATS_DTYPE.itemsize, dtype=_torch().uint8, device="cuda")
@@ -302,6 +324,19 @@ class Sim:
         st = _torch().empty(xyz.shape[0], dtype=_torch().uint8, device=xyz.device) if status else None
         _raise(lib.hns_sim_trace_points(self._ptr, _ptr(xyz), xyz.shape[0], dt, voxel_size, int(order), int(steps), _byte_ptr(st),
                                         current_stream() if stream is None else stream))
+        return st
+
+    def splat(self, values: dict, xyz, velocity=None, log2_quantum: int = -32, activate: bool = True, status: bool = False, rejected=None, stream: Optional[int] = None):
+        """Point values added into the sim's own fields (``hns_sim_splat_points``, the arithmetic of ``splat_points``): values = {float field name: (n,) float32 device
+        tensor}, velocity = None or an (n, 3) tensor added into the velocity, xyz the (n, 3) index-space positions. activate: on a sim that holds active masks, set the bit
+        of every voxel a tap of positive weight landed on. Points outside the domain add no leaves: with `status` the uint8 tensor of landed taps per point (0 .. 8) is
+        returned. rejected: None or an int64 tensor of one element, as for ``splat_points``. Asynchronous on `stream` (None: the current stream)."""
+        names = list(values)
+        st = _torch().empty(xyz.shape[0], dtype=_torch().uint8, device=xyz.device) if status else None
+        arr = (C.c_char_p * max(1, len(names)))(*[k.encode() for k in names])
+        src = (C.c_void_p * max(1, len(names)))(*[_ptr(values[k]) for k in names])
+        _raise(lib.hns_sim_splat_points(self._ptr, arr, len(names), _ptr(velocity), _ptr(xyz), src, xyz.shape[0], int(log2_quantum), int(bool(activate)),
+                                        _byte_ptr(st), _u64_ptr(rejected), current_stream() if stream is None else stream))
         return st
 
     def pressure_solve(self, iterations: int, voxel_size: float, stream: int = 0) -> None:

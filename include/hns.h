@@ -139,7 +139,8 @@ int hns_grid_coords(const hns_grid*, int32_t* out_xyz);
  * serve the next cook), 0 if not, < 0 if the coordinates are not leaf-dense (same checks and flags as hns_grid_create). */
 int hns_grid_matches(const hns_grid*, const int32_t* coords_xyz, uint64_t n_voxels, unsigned flags);
 /* Operator calls (hns_compute_sim ... hns_divergence) keep their device buffers with the grid between calls, so a cook on
- * an unchanged topology allocates nothing; this frees them early (hns_grid_destroy does it too). */
+ * an unchanged topology allocates nothing; this frees them early (hns_grid_destroy does it too), and with them the accumulator
+ * hns_dev_splat_points keeps with the grid. */
 int hns_grid_release_cache(hns_grid*);
 /* Serialises the grid as a NanoVDB NanoGrid<ValueOnIndex> buffer (32.7.0 layout), the format the reference keeps its index
  * grid in (create_index_grid, HNanoSolver.cu:375-384 -> nanovdb voxelsToGrid): same header, tree, node and leaf contents,
@@ -282,6 +283,18 @@ int hns_sim_advect(hns_sim*, const char* const* names, int n_names, int advect_v
  * voxel_size that is not a positive finite number, a sim lent to a grid's cook cache. Not mirrored in hns_dist_*: a partitioned sim has no point calls. */
 int hns_sim_sample_points(hns_sim*, const char* const* names, int n_names, int with_velocity, const float* xyz, uint64_t n, float* const* out, void* stream);
 int hns_sim_trace_points(hns_sim*, float* xyz, uint64_t n, float dt, float voxel_size, int order, int steps, unsigned char* status, void* stream);
+/* Point values added into the sim's own fields (hns_dev_splat_points below, which states the positions, the arithmetic, status, d_rejected and the refusals) without
+ * anything leaving the device: the point emitter as an alternative to the leaf sources of hns_sim_regrid_sourced. names: n_names >= 0 float fields of the sim, field
+ * names[i] receives values[i] (HOST array of device pointers, n floats each); with velocity_values != NULL the velocity receives those 3n floats (Vec3f AoS). activate != 0 on
+ * a sim that holds active masks sets (an integer atomic OR) the mask bit of every tap that landed with a weight w > 0, whether or not its terms were accepted; a sim with
+ * NULL masks stays all-active; activate == 0 leaves the masks untouched. Asynchronous on `stream`. Writing the velocity drops the look-ahead memo, as every call that
+ * rewrites the velocity does, and the feedback signatures of hns_compute_sim_resident of the written fields are cleared; the solve report and the pressure of the last solve
+ * stay as they are. POINTS THAT LAND OUTSIDE THE DOMAIN CANNOT ADD LEAVES: their taps are dropped and `status` shows them (fewer than 8); a caller that wants them passes
+ * their leaves as an empty velocity source to hns_sim_regrid_sourced first. Refused before anything is launched (HNS_ERR_INVALID_ARGUMENT) besides what hns_dev_splat_points
+ * refuses: n_names < 0, a name the sim lacks or one listed twice, collision_sdf as a target (it comes from the collision input), nothing to write (no names and
+ * velocity_values NULL), a sim lent to a grid's cook cache. Not mirrored in hns_dist_*: a partitioned sim has no point calls. */
+int hns_sim_splat_points(hns_sim*, const char* const* names, int n_names, const float* velocity_values, const float* xyz, const float* const* values, uint64_t n,
+                         int log2_quantum, int activate, unsigned char* status, uint64_t* d_rejected, void* stream);
 /* Only the pressure hot loop on the sim's divergence/pressure buffers (pressure zeroed first); asynchronous. */
 int hns_sim_pressure_solve(hns_sim*, int iterations, float voxel_size, void* stream);
 /* hipEvent timing of the pressure hot loop on its launch stream: after hns_sim_timing(sim, max_solves) every pressure
@@ -516,6 +529,35 @@ int hns_dev_sample_points(hns_grid*, const float* const* fields, const int* ncom
  * anything is launched (HNS_ERR_INVALID_ARGUMENT), positions and status untouched: a null xyz or vel3, an order not in {1, 2, 4}, steps < 1, a NaN dt, an inv_dx that is
  * not a positive finite number, n above 2^31 - 1, xyz, status and vel3 not three different buffers. Neither call is mirrored in hns_dist_*. */
 int hns_dev_trace_points(hns_grid*, const float* vel3, float* xyz, uint64_t n, float dt, float inv_dx, int order, int steps, unsigned char* status, void* stream);
+/* Point values into fields: the transpose of hns_dev_sample_points -- every point adds w * v to the eight voxels of its cell -- with an accumulation that does not depend on
+ * the order the adds retire in. fields[i]: device pointer, ncomp[i] 1 (float) or 3 (Vec3f AoS), added into IN PLACE; values[i]: device, n x ncomp[i] floats, the value of
+ * each point for field i; fields, ncomp and values are HOST arrays of n_fields (1 .. 8) entries; xyz as for hns_dev_sample_points.
+ *   Cell     ijk = Floor(xyz) with the GPU's saturating float -> int conversion, f = xyz - float(ijk), taps = the eight corners of the trilinear sampler's stencil.
+ *   Weights  wx[0] = 1.0f - fx, wx[1] = fx, likewise y and z; w(di,dj,dk) = (wx[di] * wy[dj]) * wz[dk]; the term of a component with point value v is t = w * v. Each of
+ *            these is one rounded f32 operation, none contracted.
+ *   Landing  a point with a non-finite position component lands nowhere; otherwise a tap lands iff its leaf exists (any leaf of the grid, ghost leaves included).
+ *   Accepted a landed tap's term is accepted iff t is finite and |t| * 2^-Q < 2^62, Q = log2_quantum (-40 .. 0).
+ *   Sum      an accepted term adds the int64 k = rint((double)t * 2^-Q), ties to even, to the voxel's 64-bit accumulator of that component, modulo 2^64 -- on the device
+ *            an integer atomic add. Integer addition is associative: the result does not depend on scheduling. No float atomics.
+ *   Finish   every voxel whose accumulator a is non-zero gets field = field + (float)((double)(int64)a * 2^Q), an f32 add; every other voxel keeps its bytes (-0.0f stays).
+ * So a term is rounded once, to a multiple of 2^Q (the default of the Python layer, Q = -32, resolves 2.3e-10 and accepts |t| < 2^30), the sum of a voxel is exact, and the
+ * field sees one rounded add. status: NULL, or n bytes (device): the number of taps of each point that landed, 0 .. 8 -- positions only. d_rejected: NULL, or one uint64_t
+ * (device) the call ADDS the number of (point, component, tap) terms to that landed but were not accepted (NaN or inf values, terms beyond the bound). Up to eight fields
+ * share a call and with it the cell and the weights; output i is bit-identical to a call with field i alone. The host mirror hns_grid_splat_points gives the same bytes.
+ * The accumulator -- int64 channels over all voxels plus a touched word per leaf, sized for min(4, sum of ncomp) channels, 32 bytes a voxel at four -- is pooled device memory
+ * kept with the grid (made on first use, enlarged when a later call needs more channels, returned by hns_grid_release_cache and hns_grid_destroy). A call with more
+ * components runs several launches. It is all zero between calls: cleared when drawn from the pool, and zeroed again by the finish kernel, which visits only the leaves a
+ * tap landed in. Calls on one grid must follow each other on one stream. Asynchronous on `stream`; n == 0 launches nothing and looks at no device pointer. Refused before
+ * anything is launched (HNS_ERR_INVALID_ARGUMENT, the call and the argument in the message), everything untouched: a null list or entry, a null xyz, an ncomp other than 1
+ * or 3, n_fields outside 1 .. 8, n above 2^31 - 1, log2_quantum outside -40 .. 0, two equal field pointers, a field equal to xyz, to a values array, to status or to
+ * d_rejected. Not mirrored in hns_dist_*. */
+int hns_dev_splat_points(hns_grid*, float* const* fields, const int* ncomp, int n_fields, const float* xyz, const float* const* values, uint64_t n, int log2_quantum,
+                         unsigned char* status, uint64_t* d_rejected, void* stream);
+/* Host mirror of hns_dev_splat_points and hns_sim_splat_points: the same arguments over HOST arrays, brute force over hns_grid_offsets-style lookups, the same integer
+ * arithmetic (uint64 wrap-around) and the same conversions (saturating Floor); works on HNS_GRID_HOST_ONLY grids. masks: NULL, or leaf_count x 64 bytes (byte x*8+y, bit z)
+ * in which, with activate != 0, the bit of every landed tap with w > 0 is set. *rejected (or NULL) is ADDED to, as d_rejected is. Refusals as hns_dev_splat_points'. */
+int hns_grid_splat_points(const hns_grid*, float* const* fields, const int* ncomp, int n_fields, const float* xyz, const float* const* values, uint64_t n, int log2_quantum,
+                          unsigned char* masks, int activate, unsigned char* status, uint64_t* rejected);
 /* divergence / divergence_opt (Kernel.cu:455-519) */
 int hns_dev_divergence(hns_grid*, const float* vel3, float* div, float inv_dx, void* stream);
 /* One colour of redBlackGaussSeidelUpdate(_opt) in place (Kernel.cu:521-623): the two-launch form. */
