@@ -143,6 +143,7 @@ SIGNATURES = {
     "hns_sim_regrid": (_vp, [_vp, _i, _vp, _u64, _vp, _vp, _vp, _ip]),
     "hns_sim_regrid_times": (_i, [_vp, C.POINTER(C.c_float)]),
     "hns_sim_regrid_sourced": (_vp, [_vp, _i, C.POINTER(hns_leaf_source), _i, _vp, _u64, _vp, _vp, _vp, _ip]),
+    "hns_sim_regrid_seeded": (_vp, [_vp, _i, C.POINTER(hns_leaf_source), _i, _fp, _u64, C.POINTER(C.c_uint64), _vp, _u64, _vp, _vp, _vp, _ip]),
     "hns_sim_deactivate": (_i, [_vp, C.POINTER(hns_activity_field), _i, C.POINTER(C.c_uint64), _vp]),
     "hns_sim_stats": (_i, [_vp, C.POINTER(hns_stats_field), _i, _i, _vp, _vp]),
     "hns_sim_residual": (_i, [_vp, _f, C.POINTER(hns_stats), _vp]),
@@ -157,6 +158,8 @@ SIGNATURES = {
     "hns_dev_trace_points": (_i, [_vp, _fp, _fp, _u64, _f, _f, _i, _i, _vp, _vp]),
     "hns_dev_splat_points": (_i, [_vp, C.POINTER(C.c_void_p), _ip, _i, _fp, C.POINTER(C.c_void_p), _u64, _i, _vp, _vp, _vp]),
     "hns_grid_splat_points": (_i, [_vp, C.POINTER(C.c_void_p), _ip, _i, _fp, C.POINTER(C.c_void_p), _u64, _i, _vp, _i, _vp, C.POINTER(C.c_uint64)]),
+    "hns_point_leaves": (_i, [_fp, _u64, _vp, _vp, _u64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "hns_dev_point_leaves": (_i, [_i, _fp, _u64, _vp, _vp, _u64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), _vp]),
     "hns_dev_divergence": (_i, [_vp, _fp, _fp, _f, _vp]),
     "hns_dev_rbgs_color": (_i, [_vp, _fp, _fp, _f, _f, _i, _vp]),
     "hns_dev_rbgs_iterate": (_i, [_vp, _fp, _fp, _fp, _f, _f, _i, _ip, _vp]),

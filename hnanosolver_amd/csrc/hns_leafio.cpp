@@ -17,6 +17,7 @@
 
 #include "hns_dilate.hpp"
 #include "hns_internal.hpp"
+#include "hns_seed.hpp"
 #include "hns_stats.hpp"
 
 using namespace hns;
@@ -70,6 +71,14 @@ int check_aligned(const int32_t* o, uint64_t n, const char* who) {
 
 // OpenVDB leaf order of an origin list in place (hns_regrid.hip): the same order as leaf_less, by one precomputed key per leaf -- root tile (20 bits per
 // axis, biased), then the 15-bit child offset in the 4096^3 node and the 12-bit one in the 128^3 node.
+namespace {
+inline void leaf_sort_key(int32_t x, int32_t y, int32_t z, uint64_t& tile, uint32_t& node) {
+	tile = ((uint64_t)((x >> 12) + (1 << 19)) << 40) | ((uint64_t)((y >> 12) + (1 << 19)) << 20) | (uint64_t)((z >> 12) + (1 << 19));
+	node = ((uint32_t)(((x & 4095) >> 7) << 10 | ((y & 4095) >> 7) << 5 | ((z & 4095) >> 7)) << 12) |
+	       (uint32_t)(((x & 127) >> 3) << 8 | ((y & 127) >> 3) << 4 | ((z & 127) >> 3));
+}
+}  // namespace
+
 void hns::sort_leaf_origins(int32_t* xyz, size_t n) {
 	struct Item {
 		uint64_t tile;
@@ -79,13 +88,27 @@ void hns::sort_leaf_origins(int32_t* xyz, size_t n) {
 	std::vector<Item> v(n);
 	for (size_t i = 0; i < n; ++i) {
 		const int32_t x = xyz[3 * i], y = xyz[3 * i + 1], z = xyz[3 * i + 2];
-		const uint64_t tile = ((uint64_t)((x >> 12) + (1 << 19)) << 40) | ((uint64_t)((y >> 12) + (1 << 19)) << 20) | (uint64_t)((z >> 12) + (1 << 19));
-		const uint32_t node = ((uint32_t)(((x & 4095) >> 7) << 10 | ((y & 4095) >> 7) << 5 | ((z & 4095) >> 7)) << 12) |
-		                      (uint32_t)(((x & 127) >> 3) << 8 | ((y & 127) >> 3) << 4 | ((z & 127) >> 3));
-		v[i] = Item{tile, node, x, y, z};
+		v[i] = Item{0, 0, x, y, z};
+		leaf_sort_key(x, y, z, v[i].tile, v[i].node);
 	}
 	std::sort(v.begin(), v.end(), [](const Item& a, const Item& b) { return a.tile != b.tile ? a.tile < b.tile : a.node < b.node; });
 	for (size_t i = 0; i < n; ++i) xyz[3 * i] = v[i].x, xyz[3 * i + 1] = v[i].y, xyz[3 * i + 2] = v[i].z;
+}
+
+// The same order as a permutation, for whoever carries something with each leaf (distinct origins: the keys are distinct).
+void hns::leaf_order(const int32_t* xyz, size_t n, std::vector<uint32_t>* perm) {
+	struct Item {
+		uint64_t tile;
+		uint32_t node, at;
+	};
+	std::vector<Item> v(n);
+	for (size_t i = 0; i < n; ++i) {
+		v[i].at = (uint32_t)i;
+		leaf_sort_key(xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], v[i].tile, v[i].node);
+	}
+	std::sort(v.begin(), v.end(), [](const Item& a, const Item& b) { return a.tile != b.tile ? a.tile < b.tile : a.node < b.node; });
+	perm->resize(n);
+	for (size_t i = 0; i < n; ++i) (*perm)[i] = v[i].at;
 }
 
 int hns::check_activity_fields(const hns_sim* s, const hns_activity_field* fields, int n_fields, const char* who, std::vector<int>* field_of) {
@@ -319,6 +342,46 @@ int hns_add_leaves(const int32_t* a_origins, uint64_t na, const unsigned char* a
 			for (size_t k = 0; k < leaf_floats; ++k) dst[k] = (va ? va[k] : 0.0f) + (vb ? vb[k] : 0.0f);
 		}
 	}
+	return HNS_OK;
+}
+
+// The seeds of a point set (include/hns.h states the definition): brute force over the eight taps of every seeding point, the leaves in OpenVDB leaf order. What
+// hns_dev_point_leaves (hns_seed.hip) is checked against, byte for byte.
+int hns_point_leaves(const float* xyz, uint64_t n, int32_t* origins_out, unsigned char* masks_out, uint64_t cap, uint64_t* n_leaves, uint64_t* skipped) {
+	if (!n_leaves) return fail(HNS_ERR_INVALID_ARGUMENT, "hns_point_leaves: n_leaves is null");
+	*n_leaves = 0;
+	if (skipped) *skipped = 0;
+	if (n > kMaxSeedPoints) return fail(HNS_ERR_INVALID_ARGUMENT, "hns_point_leaves: n is above 2^31 - 1");
+	if (n && !xyz) return fail(HNS_ERR_INVALID_ARGUMENT, "hns_point_leaves: xyz is null");
+	struct Mask {
+		unsigned char b[64];
+	};
+	std::unordered_map<Key, Mask, KeyHash> have;
+	uint64_t skip = 0;
+	for (uint64_t p = 0; p < n; ++p) {
+		const float* q = xyz + 3 * p;
+		if (!(seeds_f(q[0]) && seeds_f(q[1]) && seeds_f(q[2]))) {
+			++skip;
+			continue;
+		}
+		const int32_t c[3] = {(int32_t)std::floor(q[0]), (int32_t)std::floor(q[1]), (int32_t)std::floor(q[2])};
+		for (int t = 0; t < 8; ++t) {
+			const int32_t x = c[0] + (t >> 2), y = c[1] + ((t >> 1) & 1), z = c[2] + (t & 1);
+			Mask& m = have.try_emplace(Key{x & ~7, y & ~7, z & ~7}, Mask{}).first->second;
+			m.b[(x & 7) * 8 + (y & 7)] |= (unsigned char)(1u << (z & 7));
+		}
+	}
+	if (skipped) *skipped = skip;
+	if (have.size() > kMaxSeedLeaves) return fail(HNS_ERR_TOPOLOGY, "hns_point_leaves: the points hold more than 2^23 distinct leaves");
+	*n_leaves = have.size();
+	if (!origins_out || have.size() > cap) return HNS_OK;  // (the query of the two-call idiom)
+	std::vector<int32_t> o;
+	o.reserve(have.size() * 3);
+	for (const auto& kv : have) o.insert(o.end(), {kv.first.x, kv.first.y, kv.first.z});
+	sort_leaf_origins(o.data(), have.size());
+	memcpy(origins_out, o.data(), o.size() * sizeof(int32_t));
+	if (masks_out)
+		for (size_t i = 0; i < have.size(); ++i) memcpy(masks_out + 64 * i, have[Key{o[3 * i], o[3 * i + 1], o[3 * i + 2]}].b, 64);
 	return HNS_OK;
 }
 

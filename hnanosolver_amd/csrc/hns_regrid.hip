@@ -8,6 +8,10 @@
 // before the domain is built from the summed velocity). Only the source leaves cross PCIe; the sum is formed in the field phase, the velocity
 // source's leaves and masks join the domain through the candidate and mask phases (dilation distributes over the union, so nothing is pre-merged).
 //
+// hns_sim_regrid_seeded unites the velocity's topology with the seeds of a device-resident point set (hns_seed.hip) before the dilation: one more entry of the source
+// list, of a kind that comes from the device and has no values. Its leaves and masks are dilation seeds exactly as the velocity source's are (phases 1 and 3) and take part
+// in nothing else; the two sets are never merged. Only the seeds' leaf count crosses PCIe.
+//
 // The collision SDF is one more entry of the same source list (Source), of its own kind: its leaves join the domain undilated, its masks are ORed
 // in undilated and its values replace collision_sdf instead of being added. Every entry is validated, staged, uploaded and hashed by origin
 // (duplicates are refused) the same way, and all but the velocity's (the mask waves find its leaves) are indexed into the new grid by one kernel.
@@ -40,6 +44,7 @@
 
 #include "hns_device.hpp"
 #include "hns_dilate.hpp"
+#include "hns_seed.hpp"
 
 namespace hns {
 namespace {
@@ -55,15 +60,23 @@ __device__ __forceinline__ void load_mask(const unsigned char* masks, int l, uin
 	for (int x = 0; x < 8; ++x) m[x] = w ? w[x] : ~0ull;
 }
 
-// The candidate a thread id stands for: ids [0, n_dil) are (old leaf, offset) pairs, ids [n_dil, n_dil + n_sdf) the SDF leaves, ids
-// [n_dil + n_sdf, n_dil + n_sdf + n_vdil) (velocity source leaf, offset) pairs.
+// A set of leaves whose masks are dilated into the domain besides the sim's own: [kVsrcSeeds] the velocity source's, [kPointSeeds] the seeds of a point set.
+constexpr int kVsrcSeeds = 0, kPointSeeds = 1, kSeedSets = 2;
+struct MaskedLeaves {
+	const int4* origins;
+	const unsigned char* masks;  // null: every voxel active
+	uint64_t n_dil;               // (leaf, offset) pairs
+};
+
+// The candidate a thread id stands for: ids [0, n_dil) are (old leaf, offset) pairs, ids [n_dil, n_dil + n_sdf) the SDF leaves, then the (leaf, offset)
+// pairs of seeds[0] and behind them those of seeds[1].
 struct Candidates {
 	const int4* old_origins;
 	const unsigned char* old_masks;  // null: every voxel active
 	const int4* sdf;
-	const int4* vsrc;                 // the velocity source's leaves
-	const unsigned char* vsrc_masks;  // null: every voxel active
-	uint64_t n_dil, n_sdf, n_vdil;
+	MaskedLeaves seeds[kSeedSets];
+	uint64_t n_dil, n_sdf;
+	__host__ __device__ uint64_t total() const { return n_dil + n_sdf + seeds[0].n_dil + seeds[1].n_dil; }
 	int side, R, p;
 	unsigned long long* table;
 	uint32_t mask;
@@ -71,7 +84,7 @@ struct Candidates {
 	unsigned long long* count;  // [0] slots reserved, [1] overflow, [2] compacted leaves
 };
 
-// l: the old or velocity source leaf whose active voxels (`masks`) must reach the candidate, -1 for an SDF leaf
+// l: the old or seed-set leaf whose active voxels (`masks`) must reach the candidate, -1 for an SDF leaf
 __device__ __forceinline__ bool cand_origin(const Candidates& c, uint64_t t, int& x, int& y, int& z, int& l, int (&d)[3], const unsigned char*& masks) {
 	const int4* origins = c.old_origins;
 	masks = c.old_masks;
@@ -82,7 +95,9 @@ __device__ __forceinline__ bool cand_origin(const Candidates& c, uint64_t t, int
 			return true;
 		}
 		t -= c.n_dil + c.n_sdf;
-		origins = c.vsrc, masks = c.vsrc_masks;
+		const int k = t < c.seeds[0].n_dil ? 0 : 1;
+		if (k) t -= c.seeds[0].n_dil;
+		origins = c.seeds[k].origins, masks = c.seeds[k].masks;
 	}
 	const uint64_t K = (uint64_t)c.side * c.side * c.side;
 	l = (int)(t / K);
@@ -96,7 +111,7 @@ __device__ __forceinline__ bool cand_origin(const Candidates& c, uint64_t t, int
 }
 
 __global__ __launch_bounds__(256) void k_regrid_candidates(Candidates c) {
-	const uint64_t total = c.n_dil + c.n_sdf + c.n_vdil;
+	const uint64_t total = c.total();
 	for (uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (uint64_t)gridDim.x * 256) {
 		int x, y, z, l, d[3] = {0, 0, 0};
 		const unsigned char* ms;
@@ -182,39 +197,62 @@ __global__ __launch_bounds__(256) void k_regrid_src_index(GridDev ng, const int4
 	if (b >= 0 && atomicCAS(&idx[b], -1, i) != -1) *dup = 1;
 }
 
-// One wave per new leaf: its dilated mask (OR over the old leaves and velocity source leaves within reach, then the SDF leaf's mask), the old leaf with
-// its origin (map, -1 = new) and, with a velocity source (vh.table != null), its leaf with that origin (vmap, -1 = none).
+// The seed sets of k_regrid_masks by origin (h.table null: none) with their masks (null: every voxel active)
+struct SeedHashes {
+	SrcHash h[kSeedSets];
+	const unsigned char* masks[kSeedSets];
+};
+
+// A float source's indices under point seeds: a leaf the unseeded regrid would not hold takes nothing from the source (k_regrid_masks: unseeded)
+__global__ __launch_bounds__(256) void k_regrid_src_unseeded(int* __restrict__ idx, const int* __restrict__ unseeded, int n_new) {
+	const int b = blockIdx.x * 256 + threadIdx.x;
+	if (b < n_new && !unseeded[b]) idx[b] = -1;
+}
+
+// One wave per new leaf: its dilated mask (OR over the old leaves and the leaves of either seed set within reach, then the SDF leaf's mask), the old leaf with
+// its origin (map, -1 = new) and, with a velocity source (sh.h[kVsrcSeeds].table != null), its leaf with that origin (vmap, -1 = none).
+// With point seeds a leaf may be in the domain through them alone: the unseeded regrid would not hold it, so it takes no value from anywhere -- map and vmap are -1
+// there and unseeded[leaf] (given with point seeds) is 0, for the float sources' indices. The leaf is in the unseeded domain iff an old or velocity source leaf
+// contributed to its mask (hns_dilate_leaf_masks' test) or it is an SDF leaf.
 __global__ __launch_bounds__(256) void k_regrid_masks(GridDev og, const unsigned char* __restrict__ old_masks, const int4* __restrict__ new_origins, int n_new, int p, int R,
-                                                      const int* __restrict__ sdf_idx, const unsigned char* __restrict__ sdf_masks, SrcHash vh,
-                                                      const unsigned char* __restrict__ vsrc_masks, uint64_t* __restrict__ new_masks, int* __restrict__ map,
-                                                      int* __restrict__ vmap) {
+                                                      const int* __restrict__ sdf_idx, const unsigned char* __restrict__ sdf_masks, SeedHashes sh,
+                                                      uint64_t* __restrict__ new_masks, int* __restrict__ map, int* __restrict__ vmap, int* __restrict__ unseeded) {
 	const int b = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
 	if (b >= n_new) return;
 	const int4 o = new_origins[b];
 	const int side = 2 * R + 1, K = side * side * side, centre = (K - 1) / 2;
 	uint64_t acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+	int own = -1, vown = -1;
+	bool reached = false;  // by an old or a velocity source leaf
 	for (int k = lane; k < K; k += 64) {
 		const int d[3] = {k / (side * side) - R, (k / side) % side - R, k % side - R};
 		const int64_t nx = (int64_t)o.x + 8 * d[0], ny = (int64_t)o.y + 8 * d[1], nz = (int64_t)o.z + 8 * d[2];
+		const bool in_range = nx >= INT32_MIN && nx <= INT32_MAX && ny >= INT32_MIN && ny <= INT32_MAX && nz >= INT32_MIN && nz <= INT32_MAX;
 		int l = -1;
-		if (og.n_leaves > 0 && nx >= INT32_MIN && nx <= INT32_MAX && ny >= INT32_MIN && ny <= INT32_MAX && nz >= INT32_MIN && nz <= INT32_MAX)
-			l = d_find_leaf(og, (int)nx, (int)ny, (int)nz);
-		int vl = -1;
-		if (vh.table && nx >= INT32_MIN && nx <= INT32_MAX && ny >= INT32_MIN && ny <= INT32_MAX && nz >= INT32_MIN && nz <= INT32_MAX)
-			vl = d_find_src(vh, (int)nx, (int)ny, (int)nz);
-		if (k == centre) {
-			map[b] = l;
-			if (vh.table) vmap[b] = vl;
-		}
+		if (og.n_leaves > 0 && in_range) l = d_find_leaf(og, (int)nx, (int)ny, (int)nz);
+		int sl[kSeedSets];
+#pragma unroll
+		for (int q = 0; q < kSeedSets; ++q) sl[q] = sh.h[q].table && in_range ? d_find_src(sh.h[q], (int)nx, (int)ny, (int)nz) : -1;
+		if (k == centre) own = l, vown = sl[kVsrcSeeds];
 		uint64_t m[8];
 		if (l >= 0) {
 			load_mask(old_masks, l, m);
-			dilate_into(m, 8 * d[0], 8 * d[1], 8 * d[2], p, acc);
+			reached |= dilate_into(m, 8 * d[0], 8 * d[1], 8 * d[2], p, acc);
 		}
-		if (vl >= 0) {
-			load_mask(vsrc_masks, vl, m);
-			dilate_into(m, 8 * d[0], 8 * d[1], 8 * d[2], p, acc);
-		}
+#pragma unroll
+		for (int q = 0; q < kSeedSets; ++q)
+			if (sl[q] >= 0) {
+				load_mask(sh.masks[q], sl[q], m);
+				const bool hit = dilate_into(m, 8 * d[0], 8 * d[1], 8 * d[2], p, acc);
+				if (q == kVsrcSeeds) reached |= hit;
+			}
+	}
+	const int si = sdf_idx ? sdf_idx[b] : -1;
+	const bool in_unseeded = !sh.h[kPointSeeds].table || __ballot(reached) != 0 || si >= 0;
+	if (lane == centre % 64) {  // (the lane that met the leaf's own origin)
+		map[b] = in_unseeded ? own : -1;
+		if (sh.h[kVsrcSeeds].table) vmap[b] = in_unseeded ? vown : -1;
+		if (unseeded) unseeded[b] = in_unseeded;
 	}
 #pragma unroll
 	for (int x = 0; x < 8; ++x) {
@@ -230,7 +268,6 @@ __global__ __launch_bounds__(256) void k_regrid_masks(GridDev og, const unsigned
 		uint64_t w = 0;
 #pragma unroll
 		for (int x = 0; x < 8; ++x) w = lane == x ? acc[x] : w;
-		const int si = sdf_idx ? sdf_idx[b] : -1;
 		if (si >= 0) w |= sdf_masks ? ((const uint64_t*)(sdf_masks + 64 * (size_t)si))[lane] : ~0ull;
 		new_masks[(size_t)b * 8 + lane] = w;
 	}
@@ -314,51 +351,16 @@ int launch_fields(const FieldSet& fs, int nf, int nc, bool add, uint64_t n_new, 
 	return HNS_OK;
 }
 
-size_t pad256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-// device allocations of one regrid, returned to the pool however it ends (hns_arena_put waits for the device first)
-struct Scratch {
-	std::vector<std::pair<void*, size_t>> held;
-	int device;
-	explicit Scratch(int dev) : device(dev) {}
-	int get(size_t bytes, void** p) {
-		size_t got = 0;
-		const int rc = hns_arena_get(bytes, device, p, &got);
-		if (rc == HNS_OK) held.emplace_back(*p, got);
-		return rc;
-	}
-	// One allocation in 256-byte aligned slices: `slices(slice)` calls slice(pointer, bytes) once per slice, first to size the allocation, then
-	// to point every pointer at its slice, so the sizes and the carve come from the same list.
-	template <class F>
-	int carve(F slices) {
-		size_t total = 0;
-		slices([&](auto*&, size_t bytes) { total += pad256(bytes); });
-		void* p = nullptr;
-		HNS_TRY(get(total, &p));
-		char* q = (char*)p;
-		slices([&](auto*& ptr, size_t bytes) {
-			ptr = reinterpret_cast<std::remove_reference_t<decltype(ptr)>>(q);
-			q += pad256(bytes);
-		});
-		return HNS_OK;
-	}
-	size_t keep(void* p) {  // ownership passes to the sim: returns the allocation's size
-		size_t bytes = 0;
-		for (size_t i = 0; i < held.size(); ++i)
-			if (held[i].first == p) bytes = held[i].second, held.erase(held.begin() + (long)i);
-		return bytes;
-	}
-	~Scratch() {
-		for (auto& h : held) hns_arena_put(h.first, h.second, device);
-	}
-};
+// (Scratch, the device allocations of one regrid: hns_seed.hpp)
 
 // One entry of the regrid's source list: the collision SDF or one source of hns_sim_regrid_sourced, validated, and where its leaves live on the
 // device. The kinds differ in three places only: the velocity's leaves are dilated candidates (phase 1) and its masks are dilated into the new
 // ones (phase 3), the SDF's leaves and masks join as they are; the SDF's values replace collision_sdf, with the 0x01 byte fill (phase 4), a
-// velocity or float source is added to its field. A float source's masks never enter the domain.
+// velocity or float source is added to its field. A float source's masks never enter the domain. The seeds of a point set (kPoints) come from the device
+// (hns_seed.hip: origins and masks point into the scratch, l holds the leaf count only) and have no values: they are treated like the velocity's in phases 1 and 3
+// and are in no field's sum; their origins are distinct by construction, so their duplicate flag never rises.
 struct Source {
-	enum Kind { kVelocity, kFloat, kSdf } kind = kFloat;
+	enum Kind { kVelocity, kFloat, kSdf, kPoints } kind = kFloat;
 	hns_leaf_source l{};  // the caller's entry (the SDF's: its arguments of hns_sim_regrid)
 	int index = -1;       // in the caller's list (-1: the SDF)
 	int field = -1;       // float field index (the SDF's: collision_sdf), -1 = the velocity
@@ -395,6 +397,7 @@ struct Regrid {
 	std::vector<Source> srcs;  // the SDF first, when given, then the caller's sources (before the scratch: its staging outlives the device work)
 	Source* vsrc = nullptr;    // the velocity's source, if any
 	Source* sdf = nullptr;
+	Source* points = nullptr;  // the seeds of the point set, if any
 	Scratch scratch;
 	std::unique_ptr<hns_grid, void (*)(hns_grid*)> ng{nullptr, hns_grid_destroy};
 	Candidates c{};
@@ -402,13 +405,14 @@ struct Regrid {
 	int* dup = nullptr;  // one duplicate flag per source
 	uint64_t n_new = 0;
 	int* map = nullptr;  // new leaf -> old leaf, -1 = new
+	int* unseeded = nullptr;  // with point seeds: is the new leaf one of the unseeded domain's?
 	void* new_masks = nullptr;
 	void* new_fields = nullptr;
 
 	Regrid(hns_sim* sim, int padding, hipStream_t stream, const char* w) : s(sim), p(padding), R((padding + 7) / 8), st(stream), who(w), scratch(sim->device) {}
 
-	// ---- 0. the source list, checked; `sdf_src` is the SDF (given iff its values are) ----
-	int sources(const hns_leaf_source& sdf_src, const hns_leaf_source* src, int n_src) {
+	// ---- 0. the source list, checked; `sdf_src` is the SDF (given iff its values are); with_points: an entry for the seeds of a point set, filled by seeds() ----
+	int sources(const hns_leaf_source& sdf_src, const hns_leaf_source* src, int n_src, bool with_points) {
 		if (sdf_src.values) {
 			Source q;
 			q.kind = Source::kSdf, q.l = sdf_src, q.field = s->find("collision_sdf");
@@ -466,10 +470,27 @@ struct Regrid {
 			HNS_TRY(check_origins(q, who));
 			srcs.push_back(q);
 		}
+		if (with_points) {
+			Source q;
+			q.kind = Source::kPoints, q.l.name = "(points)";
+			srcs.push_back(q);
+		}
 		for (Source& q : srcs) {
 			if (q.kind == Source::kVelocity) vsrc = &q;
 			if (q.kind == Source::kSdf) sdf = &q;
+			if (q.kind == Source::kPoints) points = &q;
 		}
+		return HNS_OK;
+	}
+
+	// ---- the seeds of the point set, on the device (hns_seed.hip); timed with the candidates ----
+	int seeds(const float* d_xyz, uint64_t n, uint64_t* skipped) {
+		if (!points) return HNS_OK;  // (candidates() opens the first phase where it always did)
+		HNS_HIP(hipEventRecord(s->rev[0], st));
+		SeedSet S;
+		HNS_TRY(seed_leaves(scratch, d_xyz, n, st, who, &S));
+		points->l.n_leaves = S.n_leaves, points->origins = S.origins, points->masks = S.masks;
+		if (skipped) *skipped = S.skipped;
 		return HNS_OK;
 	}
 
@@ -478,9 +499,10 @@ struct Regrid {
 		const hns_grid* og = s->grid;
 		const uint64_t K = (uint64_t)(2 * R + 1) * (2 * R + 1) * (2 * R + 1);
 		c.old_origins = (const int4*)og->d_origins, c.old_masks = s->d_masks;
-		c.n_dil = (uint64_t)og->topo.n_leaves * K, c.n_sdf = sdf ? sdf->l.n_leaves : 0, c.n_vdil = vsrc ? vsrc->l.n_leaves * K : 0;
+		c.n_dil = (uint64_t)og->topo.n_leaves * K, c.n_sdf = sdf ? sdf->l.n_leaves : 0;
+		c.seeds[kVsrcSeeds].n_dil = vsrc ? vsrc->l.n_leaves * K : 0, c.seeds[kPointSeeds].n_dil = points ? points->l.n_leaves * K : 0;
 		c.side = 2 * R + 1, c.R = R, c.p = p;
-		const uint64_t total = c.n_dil + c.n_sdf + c.n_vdil;
+		const uint64_t total = c.total();
 		c.cap = std::min<uint64_t>(total, kMaxCandidates);
 		uint64_t T = 16;
 		while (T < 2 * c.cap) T <<= 1;
@@ -490,6 +512,7 @@ struct Regrid {
 			uint64_t Ts = 16;
 			while (Ts < 2 * n) Ts <<= 1;
 			q.mask = (uint32_t)(Ts - 1);
+			if (q.kind == Source::kPoints) continue;  // (already on the device)
 			q.o4.assign((size_t)n * 4, 0);
 			for (uint64_t i = 0; i < n; ++i)
 				for (int a = 0; a < 3; ++a) q.o4[4 * i + a] = q.l.origins[3 * i + a];
@@ -504,15 +527,17 @@ struct Regrid {
 				slice(dup, 4 * srcs.size());
 				for (Source& q : srcs) {
 					const uint64_t n1 = std::max<uint64_t>(q.l.n_leaves, 1);
-					slice(q.origins, 16 * n1);
 					slice(q.table, 4 * ((uint64_t)q.mask + 1));
+					if (q.kind == Source::kPoints) continue;
+					slice(q.origins, 16 * n1);
 					if (q.kind != Source::kFloat && q.l.masks) slice(q.masks, 64 * n1);
 					slice(q.values, 2048 * (uint64_t)q.l.ncomp * n1);
 				}
 			}));
 		c.sdf = sdf ? sdf->origins : nullptr;
-		c.vsrc = vsrc ? vsrc->origins : nullptr, c.vsrc_masks = vsrc ? vsrc->masks : nullptr;
-		HNS_HIP(hipEventRecord(s->rev[0], st));
+		if (vsrc) c.seeds[kVsrcSeeds].origins = vsrc->origins, c.seeds[kVsrcSeeds].masks = vsrc->masks;
+		if (points) c.seeds[kPointSeeds].origins = points->origins, c.seeds[kPointSeeds].masks = points->masks;
+		if (!points) HNS_HIP(hipEventRecord(s->rev[0], st));
 		HNS_HIP(hipMemsetAsync(c.table, 0xFF, 8 * T, st));
 		HNS_HIP(hipMemsetAsync(c.count, 0, 256, st));
 		if (!srcs.empty()) HNS_HIP(hipMemsetAsync(dup, 0, 4 * srcs.size(), st));
@@ -521,8 +546,10 @@ struct Regrid {
 			const uint64_t n = q.l.n_leaves;
 			HNS_HIP(hipMemsetAsync(q.table, 0xFF, 4 * ((size_t)q.mask + 1), st));
 			if (!n) continue;
-			HNS_HIP(hipMemcpyAsync(q.origins, q.o4.data(), 16 * n, hipMemcpyHostToDevice, st));
-			if (q.masks) HNS_HIP(hipMemcpyAsync(q.masks, q.l.masks, 64 * n, hipMemcpyHostToDevice, st));
+			if (q.kind != Source::kPoints) {
+				HNS_HIP(hipMemcpyAsync(q.origins, q.o4.data(), 16 * n, hipMemcpyHostToDevice, st));
+				if (q.masks) HNS_HIP(hipMemcpyAsync(q.masks, q.l.masks, 64 * n, hipMemcpyHostToDevice, st));
+			}
 			k_regrid_src_hash<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(q.origins, (int)n, q.table, q.mask, dup + i);
 			HNS_HIP(hipGetLastError());
 		}
@@ -554,7 +581,7 @@ struct Regrid {
 		HNS_HIP(hipMemcpyAsync(c4.data(), compact, 16 * n_new, hipMemcpyDeviceToHost, st));
 		HNS_HIP(hipEventRecord(s->rev[5], st));
 		for (Source& q : srcs)  // issued before the sort, so that they can overlap it
-			if (q.l.n_leaves) HNS_HIP(hipMemcpyAsync(q.values, q.l.values, 2048 * (size_t)q.l.ncomp * q.l.n_leaves, hipMemcpyHostToDevice, st));
+			if (q.l.n_leaves && q.kind != Source::kPoints) HNS_HIP(hipMemcpyAsync(q.values, q.l.values, 2048 * (size_t)q.l.ncomp * q.l.n_leaves, hipMemcpyHostToDevice, st));
 		HNS_HIP(hipEventSynchronize(s->rev[5]));
 		std::vector<int32_t> xyz((size_t)n_new * 3);
 		for (uint64_t i = 0; i < n_new; ++i)
@@ -569,27 +596,37 @@ struct Regrid {
 		return HNS_OK;
 	}
 
-	// ---- 3. masks: one wave per new leaf; every source but the velocity's (whose leaves the waves find) indexed into the new grid ----
+	// ---- 3. masks: one wave per new leaf; every source but the velocity's and the points' (whose leaves the waves find) indexed into the new grid ----
 	int masks() {
-		HNS_TRY(scratch.carve([&](auto&& slice) { slice(map, 4 * n_new); }));
+		HNS_TRY(scratch.carve([&](auto&& slice) {
+			slice(map, 4 * n_new);
+			if (points) slice(unseeded, 4 * n_new);
+		}));
 		HNS_TRY(scratch.get(64 * n_new, &new_masks));
 		if (!srcs.empty())
 			HNS_TRY(scratch.carve([&](auto&& slice) {
-				for (Source& q : srcs) slice(q.idx, 4 * n_new);
+				for (Source& q : srcs)
+					if (q.kind != Source::kPoints) slice(q.idx, 4 * n_new);
 			}));
 		for (size_t i = 0; i < srcs.size(); ++i) {
 			Source& q = srcs[i];
-			if (q.kind == Source::kVelocity) continue;
+			if (q.kind == Source::kVelocity || q.kind == Source::kPoints) continue;
 			HNS_HIP(hipMemsetAsync(q.idx, 0xFF, 4 * n_new, st));  // (a source without leaves: every leaf is fill)
 			if (!q.l.n_leaves) continue;
 			k_regrid_src_index<<<(unsigned)((q.l.n_leaves + 255) / 256), 256, 0, st>>>(ng->dev(), q.origins, (int)q.l.n_leaves, q.idx, dup + i);
 			HNS_HIP(hipGetLastError());
 		}
-		const SrcHash vh{vsrc ? vsrc->origins : nullptr, vsrc ? vsrc->table : nullptr, vsrc ? vsrc->mask : 0u};
+		SeedHashes sh{};
+		if (vsrc) sh.h[kVsrcSeeds] = SrcHash{vsrc->origins, vsrc->table, vsrc->mask}, sh.masks[kVsrcSeeds] = vsrc->masks;
+		if (points) sh.h[kPointSeeds] = SrcHash{points->origins, points->table, points->mask}, sh.masks[kPointSeeds] = points->masks;
 		k_regrid_masks<<<(unsigned)((n_new + 3) / 4), 256, 0, st>>>(s->grid->dev(), s->d_masks, (const int4*)ng->d_origins, (int)n_new, p, R, sdf ? sdf->idx : nullptr,
-		                                                           sdf ? sdf->masks : nullptr, vh, vsrc ? vsrc->masks : nullptr, (uint64_t*)new_masks, map,
-		                                                           vsrc ? vsrc->idx : nullptr);
+		                                                           sdf ? sdf->masks : nullptr, sh, (uint64_t*)new_masks, map, vsrc ? vsrc->idx : nullptr, unseeded);
 		HNS_HIP(hipGetLastError());
+		for (Source& q : srcs) {
+			if (!points || q.kind != Source::kFloat) continue;
+			k_regrid_src_unseeded<<<(unsigned)((n_new + 255) / 256), 256, 0, st>>>(q.idx, unseeded, (int)n_new);
+			HNS_HIP(hipGetLastError());
+		}
 		HNS_HIP(hipEventRecord(s->rev[3], st));
 		return HNS_OK;
 	}
@@ -660,7 +697,14 @@ struct Regrid {
 };
 
 // The regrid proper (include/hns.h); `who` names the entry point in messages.
-int regrid(hns_sim* s, int p, const hns_leaf_source* src, int n_src, const hns_leaf_source& sdf, hipStream_t st, hns_grid** out, const char* who) {
+// The point set whose seeds join the velocity's topology (n == 0: none); *skipped (or null): the points that do not seed
+struct SeedPoints {
+	const float* d_xyz;
+	uint64_t n;
+	uint64_t* skipped;
+};
+
+int regrid(hns_sim* s, int p, const hns_leaf_source* src, int n_src, const hns_leaf_source& sdf, const SeedPoints& pts, hipStream_t st, hns_grid** out, const char* who) {
 	const hns_grid* og = s->grid;
 	if (og->first_active != 0 || og->n_active != (uint64_t)og->topo.n_leaves) {
 		set_error("%s: the grid's launch range is not the whole grid (a multi-GPU rank's grid cannot be regridded)", who);
@@ -668,10 +712,11 @@ int regrid(hns_sim* s, int p, const hns_leaf_source* src, int n_src, const hns_l
 	}
 	DeviceScope on(s->device);
 	Regrid r(s, p, st, who);
-	HNS_TRY(r.sources(sdf, src, n_src));
+	HNS_TRY(r.sources(sdf, src, n_src, pts.n > 0));
 	if (!s->rev[0])
 		for (hipEvent_t& e : s->rev) HNS_HIP(hipEventCreate(&e));
 	s->regrid_timed = false;
+	HNS_TRY(r.seeds(pts.d_xyz, pts.n, pts.skipped));
 	HNS_TRY(r.candidates());
 	HNS_TRY(r.order());
 	HNS_TRY(r.masks());
@@ -780,19 +825,26 @@ extern "C" int hns_sim_active_masks(hns_sim* s, unsigned char* out, void* stream
 }
 
 namespace {
-hns_grid* regrid_entry(hns_sim* s, int padding_voxels, const hns_leaf_source* sources, int n_sources, const int32_t* sdf_origins, uint64_t n_sdf,
+hns_grid* regrid_entry(hns_sim* s, int padding_voxels, const hns_leaf_source* sources, int n_sources, const SeedPoints& pts, const int32_t* sdf_origins, uint64_t n_sdf,
                        const unsigned char* sdf_masks, const float* sdf_values, void* stream, int* err, const char* who) {
 	int rc = HNS_OK;
 	hns_grid* g = nullptr;
+	if (pts.skipped) *pts.skipped = 0;
 	if (!s || !s->grid || padding_voxels < 0 || padding_voxels > 1024 || (n_sdf && (!sdf_origins || !sdf_values))) {
 		set_error("%s: bad arguments", who);
+		rc = HNS_ERR_INVALID_ARGUMENT;
+	} else if (pts.n && !pts.d_xyz) {
+		set_error("%s: d_seed_xyz is null with %llu seeds", who, (unsigned long long)pts.n);
+		rc = HNS_ERR_INVALID_ARGUMENT;
+	} else if (pts.n > kMaxSeedPoints) {
+		set_error("%s: n_seeds is above 2^31 - 1", who);
 		rc = HNS_ERR_INVALID_ARGUMENT;
 	} else if (s->cached) {
 		set_error("%s: the sim belongs to a grid's cook cache", who);
 		rc = HNS_ERR_INVALID_ARGUMENT;
 	} else {
 		const hns_leaf_source sdf{"collision_sdf", 1, sdf_origins, n_sdf, sdf_masks, sdf_values};
-		rc = regrid(s, padding_voxels, sources, n_sources, sdf, (hipStream_t)stream, &g, who);
+		rc = regrid(s, padding_voxels, sources, n_sources, sdf, pts, (hipStream_t)stream, &g, who);
 	}
 	if (err) *err = rc;
 	return rc == HNS_OK ? g : nullptr;
@@ -801,16 +853,25 @@ hns_grid* regrid_entry(hns_sim* s, int padding_voxels, const hns_leaf_source* so
 
 extern "C" hns_grid* hns_sim_regrid(hns_sim* s, int padding_voxels, const int32_t* sdf_origins, uint64_t n_sdf, const unsigned char* sdf_masks, const float* sdf_values,
                                     void* stream, int* err) {
-	return regrid_entry(s, padding_voxels, nullptr, 0, sdf_origins, n_sdf, sdf_masks, sdf_values, stream, err, "hns_sim_regrid");
+	return regrid_entry(s, padding_voxels, nullptr, 0, SeedPoints{nullptr, 0, nullptr}, sdf_origins, n_sdf, sdf_masks, sdf_values, stream, err, "hns_sim_regrid");
 }
 
 // hns_sim_regrid after adding a frame's sources into the fields (include/hns.h): the same four phases, the sources folded into them.
 extern "C" hns_grid* hns_sim_regrid_sourced(hns_sim* s, int padding_voxels, const hns_leaf_source* sources, int n_sources, const int32_t* sdf_origins, uint64_t n_sdf,
                                             const unsigned char* sdf_masks, const float* sdf_values, void* stream, int* err) {
-	return regrid_entry(s, padding_voxels, sources, n_sources, sdf_origins, n_sdf, sdf_masks, sdf_values, stream, err, "hns_sim_regrid_sourced");
+	return regrid_entry(s, padding_voxels, sources, n_sources, SeedPoints{nullptr, 0, nullptr}, sdf_origins, n_sdf, sdf_masks, sdf_values, stream, err,
+	                    "hns_sim_regrid_sourced");
 }
 
-// hipEvent split of the last hns_sim_regrid: {candidates, origins to the host + sort + grid tables, masks, field copy} in milliseconds
+// hns_sim_regrid_sourced with the seeds of a device-resident point set united into the velocity's topology before the dilation (include/hns.h)
+extern "C" hns_grid* hns_sim_regrid_seeded(hns_sim* s, int padding_voxels, const hns_leaf_source* sources, int n_sources, const float* d_seed_xyz, uint64_t n_seeds,
+                                           uint64_t* seeds_skipped, const int32_t* sdf_origins, uint64_t n_sdf, const unsigned char* sdf_masks, const float* sdf_values,
+                                           void* stream, int* err) {
+	return regrid_entry(s, padding_voxels, sources, n_sources, SeedPoints{d_seed_xyz, n_seeds, seeds_skipped}, sdf_origins, n_sdf, sdf_masks, sdf_values, stream, err,
+	                    "hns_sim_regrid_seeded");
+}
+
+// hipEvent split of the last hns_sim_regrid: {candidates (with the seeds of a point set, where given), origins to the host + sort + grid tables, masks, field copy} in milliseconds
 extern "C" int hns_sim_regrid_times(hns_sim* s, float* ms4) {
 	if (!s || !ms4) return fail(HNS_ERR_INVALID_ARGUMENT, "hns_sim_regrid_times: null argument");
 	if (!s->regrid_timed) return fail(HNS_ERR_RUNTIME, "hns_sim_regrid_times: no regrid has completed on this sim");

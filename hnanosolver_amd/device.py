@@ -197,6 +197,25 @@ def splat_points(grid: IndexGridHandle, fields: Sequence, xyz, values: Sequence,
     return fields
 
 
+def point_leaves(xyz):
+    """The seeds of the points xyz, an (n, 3) float32 device tensor in index space (``hns_dev_point_leaves``): the leaves under the eight taps of every point's cell and,
+    per leaf, exactly the tap bits -> (origins (m, 3) int32 in OpenVDB leaf order, masks (m, 64) uint8, the number of points that do not seed), numpy arrays equal in
+    every byte to ``leafio.point_leaves``. With ``create_grid_from_leaves`` the origins are a fresh grid around a particle set. Synchronous on the current stream."""
+    n = int(xyz.shape[0])
+    if xyz.dim() != 2 or xyz.shape[1] != 3:
+        raise ValueError("point_leaves: xyz must be an (n, 3) tensor")
+    ptr, dev, st = (_ptr(xyz) if n else 0), (xyz.device.index or 0), current_stream()
+    m, skipped = C.c_uint64(0), C.c_uint64(0)
+    cap = min(8 * n, 1 << 16)  # a guess that spares most point sets the second call: a call runs the kernels whether or not its arrays are large enough
+    while True:
+        out = np.zeros((cap, 3), dtype=np.int32)
+        out_m = np.zeros((cap, 64), dtype=np.uint8)
+        _raise(lib.hns_dev_point_leaves(dev, ptr, n, out.ctypes.data, out_m.ctypes.data, cap, C.byref(m), C.byref(skipped), st))
+        if m.value <= cap:
+            return np.ascontiguousarray(out[: m.value]), np.ascontiguousarray(out_m[: m.value]), int(skipped.value)
+        cap = int(m.value)
+
+
 def stats_buffer(n_records: int = 1):
     """Device memory for `n_records` hns_stats records (a uint8 tensor; ``read_stats`` brings it to the host)."""
     return _torch().zeros(n_records * leafio.STATS_DTYPE.itemsize, dtype=_torch().uint8, device="cuda")
@@ -393,30 +412,49 @@ class Sim:
         _raise(lib.hns_sim_active_masks(self._ptr, out.ctypes.data, stream))
         return out
 
-    def regrid(self, padding: int, sdf=None, sources=None, stream: int = 0) -> IndexGridHandle:
+    last_seeds_skipped = 0  # points of the last regrid(points=...) that did not seed
+
+    def regrid(self, padding: int, sdf=None, sources=None, points=None, stream: int = 0) -> IndexGridHandle:
         """The domain change between two cooks (``hns_sim_regrid``): dilate the active masks by `padding` voxels, unite with the collision SDF's
         leaves and carry every field into the new leaf set, on the device. sdf = (origins, masks or None, values: 512 floats per leaf) or None.
         sources = {name: (origins, masks or None, values)}: this frame's sources, added into the fields first (``hns_sim_regrid_sourced``); values
         of shape (n * 512, 3) make the source the velocity's, anything else holds 512 floats per leaf of a float field.
+        points = an (n, 3) float32 device tensor of index-space positions whose seeds (``point_leaves``) join the velocity's topology before the dilation, adding no value
+        to any field (``hns_sim_regrid_seeded``): afterwards every tap of every seeding point is inside the domain. ``last_seeds_skipped`` holds the points that did not seed.
         Returns the new grid and makes it ``self.grid``; the old handle is untouched and still the caller's."""
         err, keep = C.c_int(0), []
         sdf_e = _lib.hns_leaf_source()  # (NULL arrays, no leaves: no SDF)
         if sdf is not None:
             _leaf_source(sdf_e, sdf, ("sdf values: need", "sdf masks: need"), keep, 1)
         sdf_args = (sdf_e.origins, sdf_e.n_leaves, sdf_e.masks, sdf_e.values)
-        if sources is None:
+        if sources is None and points is None:
             ptr = lib.hns_sim_regrid(self._ptr, int(padding), *sdf_args, stream, C.byref(err))
         else:
+            sources = sources or {}
             arr = (_lib.hns_leaf_source * max(1, len(sources)))()
             for i, (name, leaves) in enumerate(sources.items()):
                 keep.append(name.encode())
                 arr[i].name = keep[-1]
                 _leaf_source(arr[i], leaves, (f"source {name}: need", f"source {name}: masks need"), keep)
-            ptr = lib.hns_sim_regrid_sourced(self._ptr, int(padding), arr, len(sources), *sdf_args, stream, C.byref(err))
+            if points is None:
+                ptr = lib.hns_sim_regrid_sourced(self._ptr, int(padding), arr, len(sources), *sdf_args, stream, C.byref(err))
+            else:
+                if points.dim() != 2 or points.shape[1] != 3:
+                    raise ValueError("regrid: points must be an (n, 3) tensor")
+                n, skipped = int(points.shape[0]), C.c_uint64(0)
+                ptr = lib.hns_sim_regrid_seeded(self._ptr, int(padding), arr, len(sources), _ptr(points) if n else 0, n, C.byref(skipped), *sdf_args, stream, C.byref(err))
+                self.last_seeds_skipped = int(skipped.value)
         if not ptr:
             _raise(err.value if err.value < 0 else _lib.HNS_ERR_RUNTIME)
         self.grid = IndexGridHandle(ptr)
         return self.grid
+
+    def emit(self, values: dict, xyz, velocity=None, *, padding: int = 1, sdf=None, sources=None, log2_quantum: int = -32, rejected=None, stream: int = 0):
+        """A point emitter's frame step without a host round trip: ``regrid(padding, sdf, sources, points=xyz)``, which makes room for every tap of every seeding point,
+        then ``splat(values, xyz, velocity, activate=True, status=True)`` on the new domain -> (the new grid, the uint8 status tensor: 8 for every seeding point)."""
+        grid = self.regrid(padding, sdf, sources, points=xyz, stream=stream)
+        status = self.splat(values, xyz, velocity, log2_quantum=log2_quantum, activate=True, status=True, rejected=rejected, stream=stream)
+        return grid, status
 
     def deactivate(self, tolerances: dict, velocity: Optional[float] = None, counts: bool = False, stream: int = 0):
         """The end of a frame (``hns_sim_deactivate``): clear the active bit of every voxel whose listed components are all within tolerance

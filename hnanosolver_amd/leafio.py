@@ -145,6 +145,19 @@ def leaf_stats(values, masks: Optional[np.ndarray] = None, ncomp: Optional[int] 
     return out
 
 
+def point_leaves(xyz):
+    """The seeds of a point set (``hns_point_leaves``; include/hns.h states the definition): xyz (n, 3) float32, index space -> (origins (m, 3) int32 in OpenVDB leaf
+    order, masks (m, 64) uint8 with exactly the bits of the eight taps of every seeding point, the number of points that do not seed). The host mirror of
+    ``device.point_leaves``."""
+    p = np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
+    n, skipped = C.c_uint64(0), C.c_uint64(0)
+    _lib.check(lib.hns_point_leaves(p.ctypes.data, len(p), None, None, 0, C.byref(n), C.byref(skipped)))
+    out = np.zeros((n.value, 3), dtype=np.int32)
+    out_m = np.zeros((n.value, 64), dtype=np.uint8)
+    _lib.check(lib.hns_point_leaves(p.ctypes.data, len(p), out.ctypes.data, out_m.ctypes.data, n.value, C.byref(n), C.byref(skipped)))
+    return out, out_m, int(skipped.value)
+
+
 def union_leaves(a, b) -> np.ndarray:
     a, b = _o(a), _o(b)
     n = C.c_uint64(0)

@@ -289,8 +289,9 @@ int hns_sim_trace_points(hns_sim*, float* xyz, uint64_t n, float dt, float voxel
  * a sim that holds active masks sets (an integer atomic OR) the mask bit of every tap that landed with a weight w > 0, whether or not its terms were accepted; a sim with
  * NULL masks stays all-active; activate == 0 leaves the masks untouched. Asynchronous on `stream`. Writing the velocity drops the look-ahead memo, as every call that
  * rewrites the velocity does, and the feedback signatures of hns_compute_sim_resident of the written fields are cleared; the solve report and the pressure of the last solve
- * stay as they are. POINTS THAT LAND OUTSIDE THE DOMAIN CANNOT ADD LEAVES: their taps are dropped and `status` shows them (fewer than 8); a caller that wants them passes
- * their leaves as an empty velocity source to hns_sim_regrid_sourced first. Refused before anything is launched (HNS_ERR_INVALID_ARGUMENT) besides what hns_dev_splat_points
+ * stay as they are. POINTS THAT LAND OUTSIDE THE DOMAIN CANNOT ADD LEAVES: their taps are dropped and `status` shows them (fewer than 8); a caller that wants them makes
+ * room first: hns_sim_regrid_seeded is the device-side way (the points seed the next domain without leaving the device); their leaves as an empty velocity source of
+ * hns_sim_regrid_sourced is the host-side one (it turns the velocity into a sum: every -0.0f becomes +0.0f). Refused before anything is launched (HNS_ERR_INVALID_ARGUMENT) besides what hns_dev_splat_points
  * refuses: n_names < 0, a name the sim lacks or one listed twice, collision_sdf as a target (it comes from the collision input), nothing to write (no names and
  * velocity_values NULL), a sim lent to a grid's cook cache. Not mirrored in hns_dist_*: a partitioned sim has no point calls. */
 int hns_sim_splat_points(hns_sim*, const char* const* names, int n_names, const float* velocity_values, const float* xyz, const float* const* values, uint64_t n,
@@ -394,6 +395,23 @@ typedef struct {
  * unaligned or duplicated origins in a source (HNS_ERR_TOPOLOGY). hns_sim_regrid_times counts the source work in the phase it runs in. */
 hns_grid* hns_sim_regrid_sourced(hns_sim*, int padding_voxels, const hns_leaf_source* sources, int n_sources, const int32_t* sdf_origins, uint64_t n_sdf,
                                  const unsigned char* sdf_masks, const float* sdf_values, void* stream, int* err);
+/* hns_sim_regrid_sourced that also makes room for a device-resident point set: before the dilation the velocity's topology -- the sim's leaves and active masks, united
+ * with the velocity source's where one is given -- is united with the seed set S of the n_seeds points at d_seed_xyz (DEVICE memory, n x 3 floats, index space; S is
+ * defined at hns_point_leaves below): leaves united, masks ORed. A sim with NULL masks counts as all-active on its own leaves only; on a leaf that S alone brings the
+ * mask is S's. S ADDS NO VALUE TO ANY FIELD: every field holds what the unseeded call would have produced on its smaller domain (a subset of the seeded one, since
+ * dilation distributes over the union), carried onto the larger one with the usual fills (zeros; bytes 0x01 for collision_sdf). In particular the velocity is a copy, not a
+ * sum, when there is no velocity leaf source: its -0.0f stay. So the result equals the host chain of hns_sim_regrid_sourced with a zero-valued velocity source over S
+ * merged in for the domain and the masks, and the fields of the unseeded chain gathered onto that domain. n_seeds == 0 IS hns_sim_regrid_sourced. Seeds are a dilation
+ * source of their own: a sim whose masks are all cleared, with no SDF and no sources, restarts from points alone instead of refusing with "No active voxels".
+ * Afterwards every tap of every seeding point lies inside the domain, so hns_sim_splat_points reports status 8 for it. S is built on the device (hns_seed.hip) and never
+ * crosses PCIe; only its leaf count does. *seeds_skipped (host, or NULL) is SET to the number of points that do not seed. hns_sim_regrid_times counts the seed work
+ * with the candidates.
+ * Refused, with the sim and its grid left exactly as they were: everything hns_sim_regrid_sourced refuses; d_seed_xyz NULL with n_seeds > 0 and n_seeds above 2^31 - 1
+ * (HNS_ERR_INVALID_ARGUMENT); more than 2^23 distinct seed leaves, and the 2^22-leaf limit of the new domain (HNS_ERR_TOPOLOGY). Not mirrored in hns_dist_*: a
+ * partitioned sim has no point calls. */
+hns_grid* hns_sim_regrid_seeded(hns_sim*, int padding_voxels, const hns_leaf_source* sources, int n_sources, const float* d_seed_xyz, uint64_t n_seeds,
+                                uint64_t* seeds_skipped /* host or NULL */, const int32_t* sdf_origins, uint64_t n_sdf, const unsigned char* sdf_masks,
+                                const float* sdf_values, void* stream, int* err);
 /* The end of a frame, after its substeps and before the next regrid: clears the active-mask bit of every voxel whose listed fields are all
  * quiet. The reference has this step commented out (GridBuilder.hpp:213-214: deactivate(grid, 0, 0) + pruneInactive on each output grid).
  *   A voxel STAYS ACTIVE iff it is active now and at least one listed component is not within tolerance; x is within iff |x| <= tolerance.
@@ -558,6 +576,26 @@ int hns_dev_splat_points(hns_grid*, float* const* fields, const int* ncomp, int 
  * in which, with activate != 0, the bit of every landed tap with w > 0 is set. *rejected (or NULL) is ADDED to, as d_rejected is. Refusals as hns_dev_splat_points'. */
 int hns_grid_splat_points(const hns_grid*, float* const* fields, const int* ncomp, int n_fields, const float* xyz, const float* const* values, uint64_t n, int log2_quantum,
                           unsigned char* masks, int activate, unsigned char* status, uint64_t* rejected);
+/* THE SEEDS OF A POINT SET: the leaves a point set needs in the domain so that every tap of every point lands (what hns_sim_regrid_seeded unites into the velocity's
+ * topology, and with hns_grid_create_from_leaves a fresh grid around a particle set). xyz: n x 3 floats, index space, as for hns_dev_sample_points.
+ *   Which points seed  a point seeds iff each coordinate c satisfies -8388608.0f <= c && c < 8388607.0f (NaN and +-inf fail): beyond 2^23 a float32 has no fraction, and
+ *                      inside the range a leaf coordinate fits 21 bits. Points that do not seed are counted in *skipped and seed nothing.
+ *   Cell and taps      (i, j, k) = Floor(xyz), exact in this range; the taps are the eight voxels (i+di, j+dj, k+dk). ALL EIGHT are seeds whatever their trilinear
+ *                      weights: a point at an integer position still finds its whole cell inside the domain (a later splat reports status 8).
+ *   The seed set S     the leaves (origin = coordinate & ~7) holding at least one tap, each with a 64-byte mask (byte x*8+y, bit z, local coordinates) in which exactly
+ *                      the tap bits are set; origins in OpenVDB leaf order. S depends on the SET of points only: not on their order or multiplicity.
+ * hns_point_leaves is the host mirror, plain C++ (the two-call idiom of hns_dilate_leaf_masks): *n_leaves is always set; origins_out (cap x 3) and masks_out (cap x 64, or
+ * NULL) are written only when origins_out is not NULL and *n_leaves <= cap; *skipped (or NULL) is set, not added to. HNS_ERR_INVALID_ARGUMENT: xyz NULL with n > 0,
+ * n_leaves NULL, n above 2^31 - 1; HNS_ERR_TOPOLOGY: more than 2^23 distinct leaves. */
+int hns_point_leaves(const float* xyz, uint64_t n, int32_t* origins_out, unsigned char* masks_out, uint64_t cap, uint64_t* n_leaves, uint64_t* skipped);
+/* The same for points in DEVICE memory of HIP device `device`: arguments and results are the host mirror's, byte for byte; d_xyz is device memory, every output is host
+ * memory. Synchronous; scratch comes from the pool of device memory. Two passes over the points, since the number of leaves is not known beforehand (hns_seed.hip): the
+ * leaves as keys into a hash -- equal keys merged within a wave before memory is touched, a compare-and-swap only on a slot a load shows empty --, then the tap bits as
+ * at most eight 64-bit integer ORs a point, each skipped when a load shows its bits set. The result does not depend on the order anything retires in. HNS_ERR_NO_DEVICE
+ * where there is no HIP device (no CPU fallback: hns_point_leaves is the host's); HNS_ERR_TOPOLOGY: more than 2^23 distinct leaves (the candidate-hash bound of the
+ * regrid). Not mirrored in hns_dist_*. */
+int hns_dev_point_leaves(int device, const float* d_xyz, uint64_t n, int32_t* origins_out, unsigned char* masks_out, uint64_t cap, uint64_t* n_leaves, uint64_t* skipped,
+                         void* stream);
 /* divergence / divergence_opt (Kernel.cu:455-519) */
 int hns_dev_divergence(hns_grid*, const float* vel3, float* div, float inv_dx, void* stream);
 /* One colour of redBlackGaussSeidelUpdate(_opt) in place (Kernel.cu:521-623): the two-launch form. */
