@@ -319,10 +319,11 @@ __device__ __forceinline__ void chain_store_piece(const PackMirror& m, int leaf,
 // Its predecessor sorted the rows by the parity of x+y into two sections of waves so that the parity was a template parameter of the sweep code; the price was that a wave's rows lay
 // 64 bytes apart in memory (every other z-row of a leaf) -- ~40 L1 accesses per load instruction. Round 5 measured that instructions are not what this kernel waits for, and that div
 // fetched at coalesced addresses WITHOUT a
-// hand-over would be worth 5.7 % at 256^3 (r05_sorblock_notes.txt 11). So here thread t owns the interior row (x, y) = (1 + t / 22, 1 + t % 22): consecutive lanes are consecutive z-rows
-// of a leaf (32 bytes apart: ~24 accesses per instruction for p AND div), the parity is a per-lane value (pointer selects at the staging, two selects per updated voxel for the z
-// neighbours), there is no fetch mapping, no hand-over and no section. LDS: the same 50,880 bytes, the rows of BOTH parities in one (x, y) order -- a wave's 64 rows are 64 consecutive
-// entries of either colour array, so the 16-byte accesses at the 48-byte row stride stay free of bank conflicts:
+// hand-over would be worth 5.7 % at 256^3 (r05_sorblock_notes.txt 11). So here a thread owns one interior row for the whole launch and consecutive lanes are consecutive z-rows
+// of a leaf (32 bytes apart, whole 128-byte lines per quad of lanes, for p AND div; which row: SbShells below -- the block's planes first, then the halo shell by shell, so that a
+// sweep runs on the waves whose rows it needs), the parity is a per-lane value (pointer selects at the staging, two selects per updated voxel for the z
+// neighbours), there is no fetch mapping, no hand-over and no section. LDS: the same 50,880 bytes, the rows of BOTH parities in one (x, y) order -- the entry numbers of a wave's rows are
+// distinct mod 16 within every group of lanes the LDS serves together (SbShells), so the 16-byte accesses at the 48-byte row stride stay free of bank conflicts:
 //   black array: planes x = 0 .. T-1, rows y = 1 .. T-2 (entry x * TC + y - 1), then the rim rows y = 0 / y = T-1 of every plane (entry T * TC + 2 x + (y != 0));
 //   red array:   planes x = 1 .. T-2 only (entry (x - 1) * TC + y - 1 = the row's black entry - TC): nobody reads a red value of plane 0 / T-1 or of a rim row.
 // A row's colour arrays hold its red / black values in ascending z (which z are red depends on the row's parity: even z if x+y is even); the four lateral neighbours of a voxel have the
@@ -341,9 +342,57 @@ struct SbLdsXY {
 };
 static_assert(sizeof(SbLdsXY) == 50880, "the XY form must fit three workgroups per CU (160 KB of LDS)");
 
+// Which row a thread of the XY form owns: the tile's rows SHELL BY SHELL. A voxel matters to the block at sweep S only if its L1 excess over the block's 16 voxels per axis is
+// <= NS - S, so a row with lateral excess e = ex + ey is swept while e <= NS - S and no longer: 460 / 388 / 320 / 256 of the 484 interior rows in the four sweeps of two iterations.
+// The rows are numbered so that a wave whose rows are all past that bound branches over the sweep to its barrier, and so that the lanes of a wave still fetch whole 128-byte lines:
+//   waves 0-3  the block's 256 rows (e = 0), 16-lane run r = plane x = H + r, along y                                                     swept in S = 1 .. 4
+//   wave  4    the strips x = 3, 20 (e = 1) and x = 2, 21 (e = 2), y = 4 .. 19, one run each                                              S = 1 .. 3 (NS = 2: S = 1)
+//   wave  5    the strips x = 1, 22 (e = 3); the 24 rows beside the block's corners: e = 2 (4 rows), e = 3 (8), e = 4 (12: fetched and
+//              staged, never swept -- their black values feed sweep 1 of the e = 3 rows); 8 lanes without a row                             S = 1, 2   (NS = 2: none)
+//   waves 6-7  the rows y = 1 .. 3 and y = 20 .. 22 of the planes x = 4 .. 19 (e = 3 .. 1), FOUR LANES PER PLANE AND SIDE, the first of them
+//              without a row: the three rows of a quad are one 128-byte line of a leaf                                                     S = 1 .. 3 (NS = 2: S = 1)
+// 27 wave-sweeps instead of 32 (NS = 2: 11 instead of 16). Sorting the y-side rows by shell as well (a strip along x per shell: 24 wave-sweeps) was measured first and LOST 4 % at
+// 256^3: the 16 lanes of such a strip fetch 16 different lines, every line three times from three waves, and the texture addresser's busy time rose by a quarter
+// (profiles/sor_shells_ab.txt). The 12 rows with e >= 5 have no thread: nothing that is ever swept reads them. Rim duty and the store phase number the threads their own way.
+// LDS: ds_read_b128 is served 16 lanes at a time (lanes {0-3, 12-15, 20-27} and {4-11, 16-19, 28-31} of each half wave), and two rows collide exactly when their entry
+// numbers are congruent mod 16 (48-byte stride). A run along y rotates its y by 6 x mod 16, so that entry = 22 x + y - 1 is congruent to lane + 11 in every plane (the set of
+// addresses a run fetches does not change); the quads of waves 6-7 take the even planes of their eight in the first lane group and the odd ones in the second (entries 22 apart
+// are 6 apart mod 16: four planes of one parity leave room for three rows each). Every access of a sweep but the rim rows' (y = 0 / T-1: sweep 1 of the rows y = 1 / T-2) is
+// then conflict-free, as it was with 64 consecutive entries.
+struct SbShells {
+	using G = SbGeo<2, 2>;
+	static constexpr int H = G::H, T = G::T;
+	static constexpr int STRIPS = 16 * (T - 2 * H) + 6 * 16, QUADS = 384;  // first thread behind the runs along y / of the quads
+	static_assert(H == 4 && T == 24 && STRIPS + 32 == QUADS && QUADS + 4 * 2 * 16 == G::NT, "16-lane runs, whole waves, 512 threads");
+	// closed form in t (no table: a lookup would be one more round trip in front of the id fetch). false: the thread has no row (x = y = 1, e beyond every sweep)
+	static __device__ __forceinline__ bool row(const int t, int& x, int& y, int& e) {
+		if (t < STRIPS) {  // runs 0-15: the block's planes; 16-21: the strips x = 3, 20, 2, 21, 1, 22
+			const int run = t >> 4, s = (run - 16) >> 1;
+			x = run < 16 ? H + run : (run & 1 ? T - H + s : H - 1 - s);
+			y = H + (((t & 15) - 6 * x + 8) & 15);
+			e = run < 16 ? 0 : s + 1;
+			return true;
+		}
+		if (t < QUADS) {  // corners: c >> 2 picks (ex, ey) = (1,1) (1,2) (2,1) (1,3) (3,1) (2,2), bit 0 / 1 of c the high side in x / y
+			const int c = t - STRIPS;
+			const int ex = (0x231211 >> (4 * (c >> 2) & 31)) & 15, ey = (0x213121 >> (4 * (c >> 2) & 31)) & 15;
+			const bool v = c < 24;
+			x = v ? (c & 1 ? T - 1 - H + ex : H - ex) : 1, y = v ? (c & 2 ? T - 1 - H + ey : H - ey) : 1, e = v ? ex + ey : 2 * H;
+			return v;
+		}
+		// quads: half wave h = (side in y) * 2 + (planes 4 .. 11 / 12 .. 19); quad q of it takes plane 0, 1, 3, 2, 5, 4, 6, 7 of the eight; lane i of the quad the row y = i / T-1-H + i
+		const int u = t - QUADS, i = u & 3, q = (u >> 2) & 7, h = u >> 5;
+		const bool v = i != 0;
+		x = H + 8 * (h & 1) + ((0x76452310 >> (4 * q)) & 7);
+		y = v ? (h & 2 ? T - 1 - H + i : i) : 1;
+		e = v ? (h & 2 ? i : H - i) : 2 * H;
+		return v;
+	}
+};
+
 // one colour sweep S of the row this thread owns: entry `bi` in the black array, bi - TC in the red one; par = (x + y) & 1; yp / ym = black entries of the rows (x, y +- 1)
 template <int S, int NS, bool MASKED, class Row>
-__device__ __forceinline__ void sb_sweep_xy(Row& r, SbLdsXY& L, const int bi, const int ypb, const int ymb, const int par, const int dist, const float omega) {
+__device__ __forceinline__ void sb_sweep_xy(Row& r, SbLdsXY& L, const int bi, const int ypb, const int ymb, const int par, const int e, const float omega) {
 	using G = SbGeo<2, 2>;
 	constexpr int H = G::H, HALF = G::HALF, HS4 = G::HS4, NQ = G::NQ, TC = G::TC;
 	constexpr bool red = (S & 1) != 0;
@@ -353,9 +402,9 @@ __device__ __forceinline__ void sb_sweep_xy(Row& r, SbLdsXY& L, const int bi, co
 	// updated: S <= z' <= T-1-S; union over zo = 0 / 1 (see above)
 	constexpr int jlo = S / 2, jhi = (G::T - 1 - S) / 2 + 1;
 	constexpr int qlo = jlo / 4, qhi = (jhi + 3) / 4;
-	if (dist >= S) {
+	if (e <= NS - S) {
 		// red sweep: own red at bi - TC (red array), own black at bi, lateral neighbours' black at bi +- TC, ypb, ymb.
-		// black sweep (dist >= 2: every neighbour is an interior row of planes 1 .. T-2): own black at bi, own red at bi - TC, neighbours' red at bi - TC +- TC, bi - TC +- 1.
+		// black sweep (e <= H - 2: every neighbour is an interior row of planes 1 .. T-2): own black at bi, own red at bi - TC, neighbours' red at bi - TC +- TC, bi - TC +- 1.
 		v4f32* LXo4 = reinterpret_cast<v4f32*>((red ? L.red() + (bi - TC) * HS4 : L.black() + bi * HS4));
 		const v4f32* LYo4 = reinterpret_cast<const v4f32*>((red ? L.black() + bi * HS4 : L.red() + (bi - TC) * HS4));
 		const float4* LY = red ? L.black() : L.red() - TC * HS4;  // (indexed with BLACK entry numbers either way)
@@ -405,9 +454,9 @@ __device__ __forceinline__ void sb_sweep_xy(Row& r, SbLdsXY& L, const int bi, co
 template <int S, int NS, bool MASKED>
 struct SbSweepsXY {
 	template <class Row>
-	static __device__ __forceinline__ void run(Row& r, SbLdsXY& L, const int bi, const int ypb, const int ymb, const int par, const int dist, const float omega) {
-		sb_sweep_xy<S, NS, MASKED>(r, L, bi, ypb, ymb, par, dist, omega);
-		if constexpr (S < NS) SbSweepsXY<S + 1, NS, MASKED>::run(r, L, bi, ypb, ymb, par, dist, omega);
+	static __device__ __forceinline__ void run(Row& r, SbLdsXY& L, const int bi, const int ypb, const int ymb, const int par, const int e, const float omega) {
+		sb_sweep_xy<S, NS, MASKED>(r, L, bi, ypb, ymb, par, e, omega);
+		if constexpr (S < NS) SbSweepsXY<S + 1, NS, MASKED>::run(r, L, bi, ypb, ymb, par, e, omega);
 	}
 };
 
@@ -421,13 +470,12 @@ __global__ __attribute__((amdgpu_waves_per_eu(6, 8))) __launch_bounds__((SbGeo<2
 	__shared__ SbLdsXY L;
 	__shared__ int s_rec[64];
 	const int t = threadIdx.x;
-	const bool valid = t < TC * TC;
-	const int xq = valid ? t / TC : 0;
-	const int x = 1 + xq, y = valid ? 1 + t - xq * TC : 1;
+	// thread -> row, shell by shell (see above): the row (x, y), its lateral excess e over the block, valid = the thread has one
+	int x, y, e;
+	const bool valid = SbShells::row(t, x, y, e);
 	const int par = (x + y) & 1;
 	const int bi = SbLdsXY::brow(x, y);
 	const int ypb = y == T - 2 ? SbLdsXY::brim(x, T - 1) : bi + 1, ymb = y == 1 ? SbLdsXY::brim(x, 0) : bi - 1;
-	const int dist = valid ? min(min(x, T - 1 - x), min(y, T - 1 - y)) : -1;
 	const int cx = (x - H + 8) >> 3, cy = (y - H + 8) >> 3;
 	const unsigned row_bytes = (unsigned)(((((x - H) & 7) << 3) | ((y - H) & 7)) * 32);
 	const int* brec = recs + (size_t)blockIdx.x * G::REC;
@@ -464,7 +512,6 @@ __global__ __attribute__((amdgpu_waves_per_eu(6, 8))) __launch_bounds__((SbGeo<2
 	constexpr unsigned kBeyond = 0xFFFFF000u;
 	{
 		const int ids[C] = {valid ? q4.x : -1, valid ? q4.y : -1, valid ? q4.z : -1, valid ? q4.w : -1};
-		const int e = max(0, max(H - x, x - (T - 1 - H))) + max(0, max(H - y, y - (T - 1 - H)));
 #pragma unroll
 		for (int cz = 0; cz < C; ++cz) {
 			r.ok[cz] = ids[cz] >= 0 ? 0xFFFFFFFFu : 0u;
@@ -516,9 +563,9 @@ __global__ __attribute__((amdgpu_waves_per_eu(6, 8))) __launch_bounds__((SbGeo<2
 	}
 	__syncthreads();
 	if ((meta & 1) == 0)
-		SbSweepsXY<1, NS, false>::run(r, L, bi, ypb, ymb, par, dist, omega);
+		SbSweepsXY<1, NS, false>::run(r, L, bi, ypb, ymb, par, e, omega);
 	else
-		SbSweepsXY<1, NS, true>::run(r, L, bi, ypb, ymb, par, dist, omega);
+		SbSweepsXY<1, NS, true>::run(r, L, bi, ypb, ymb, par, e, omega);
 	// store phase: the block's 16 x 16 rows x four 16-byte pieces in memory order, values out of the rows' LDS entries, leaf ids out of the record's LDS copy
 	__syncthreads();
 	{
