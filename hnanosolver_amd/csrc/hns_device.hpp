@@ -3,7 +3,7 @@
 // reference src/Cuda/Kernel.cu:8-74. Arithmetic keeps the reference's association; build with -ffp-contract=off.
 #pragma once
 
-#include "hns_internal.hpp"
+#include "hns_originhash.hpp"
 
 namespace hns {
 
@@ -11,26 +11,8 @@ namespace hns {
 // topology access on the device
 // ---------------------------------------------------------------------------------------------------------------
 
-__device__ __forceinline__ uint32_t d_hash_origin(int x, int y, int z) {
-	uint32_t h = (uint32_t)(x >> 3) * 0x9E3779B1u;
-	h ^= (uint32_t)(y >> 3) * 0x85EBCA77u;
-	h ^= (uint32_t)(z >> 3) * 0xC2B2AE3Du;
-	h ^= h >> 15;
-	h *= 0x2C1B3C6Du;
-	h ^= h >> 12;
-	return h;
-}
-
-__device__ __forceinline__ int d_find_leaf(const GridDev& g, int ox, int oy, int oz) {
-	uint32_t s = d_hash_origin(ox, oy, oz) & g.hash_mask;
-	for (;;) {
-		const int l = g.hash[s];
-		if (l < 0) return -1;
-		const int4 o = g.origins[l];
-		if (o.x == ox && o.y == oy && o.z == oz) return l;
-		s = (s + 1) & g.hash_mask;
-	}
-}
+// the leaf with origin (ox, oy, oz), -1 = none (hns_originhash.hpp)
+__device__ __forceinline__ int d_find_leaf(const GridDev& g, int ox, int oy, int oz) { return find_origin(OriginIndex{g.origins, g.hash, g.hash_mask}, ox, oy, oz); }
 
 // Flat index of global voxel (i,j,k), or -1 when its leaf is absent. `org` is the workgroup's leaf origin and s_nbr its
 // 27-neighbour table (LDS). Replaces IndexOffsetSampler<0>::offset (reference Stencils.hpp:59-61), minus the +1.
@@ -148,6 +130,17 @@ constexpr int kActSkip = 0x40000000;  // a byte offset past any leaf
 
 __device__ __forceinline__ uint64_t readlane64(uint64_t v, int lane) {
 	const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, lane), hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), lane);
+	return (uint64_t)hi << 32 | lo;
+}
+
+// OR of `bits` over the lanes for which `take` holds, in every lane (two 32-bit butterflies)
+__device__ __forceinline__ uint64_t wave_or64(uint64_t bits, bool take) {
+	uint32_t lo = take ? (uint32_t)bits : 0u, hi = take ? (uint32_t)(bits >> 32) : 0u;
+#pragma unroll
+	for (int w = 32; w >= 1; w >>= 1) {
+		lo |= (uint32_t)__shfl_xor((int)lo, w);
+		hi |= (uint32_t)__shfl_xor((int)hi, w);
+	}
 	return (uint64_t)hi << 32 | lo;
 }
 

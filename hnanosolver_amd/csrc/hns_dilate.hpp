@@ -5,13 +5,9 @@
 // eight 64-bit words: word x holds bytes y = 0..7 (byte x*8+y of the hns_leafio layout, little endian), bit z of each byte.
 #pragma once
 
-#include <hip/hip_runtime.h>
-
-#include <cstdint>
+#include "hns_internal.hpp"
 
 namespace hns {
-
-#define HNS_HD __host__ __device__ __forceinline__
 
 // bits [lo, hi] of a byte (clamped to 0..7), 0 when empty
 HNS_HD uint32_t dil_bits(int lo, int hi) {
@@ -61,7 +57,5 @@ HNS_HD bool dilate_into(const uint64_t (&m)[8], int ox, int oy, int oz, int p, u
 	}
 	return any != 0;
 }
-
-#undef HNS_HD
 
 }  // namespace hns

@@ -17,27 +17,12 @@ namespace hns {
 // origin hash + neighbour table
 // ---------------------------------------------------------------------------------------------------------------
 
-// One thread per leaf: linear-probe insert with compare-and-swap. Entries are never removed, so a probe that meets
-// an occupied slot can compare origins safely. status[0] receives the smallest leaf index that found its origin
-// already present (INT_MAX when none).
+// One thread per leaf (insert_origin, hns_originhash.hpp). status[0] receives the smallest leaf index that found its origin already present (INT_MAX when none).
 __global__ __launch_bounds__(256) void k_hash_insert(const int4* __restrict__ origins, int n, int* __restrict__ hash, uint32_t mask, int* __restrict__ status) {
 	const int l = blockIdx.x * 256 + threadIdx.x;
 	if (l >= n) return;
-	const int4 o = origins[l];
-	uint32_t s = d_hash_origin(o.x, o.y, o.z) & mask;
-	for (;;) {
-		int cur = hash[s];
-		if (cur < 0) {
-			cur = atomicCAS(&hash[s], -1, l);
-			if (cur < 0) return;  // slot was empty and is now ours
-		}
-		const int4 q = origins[cur];
-		if (q.x == o.x && q.y == o.y && q.z == o.z) {
-			atomicMin(status, l > cur ? l : cur);
-			return;
-		}
-		s = (s + 1) & mask;
-	}
+	const int cur = insert_origin(origins, hash, mask, l);
+	if (cur >= 0) atomicMin(status, l > cur ? l : cur);
 }
 
 // One thread per (leaf, neighbour slot). 64-bit arithmetic so that origins at the int32 edge cannot wrap into a

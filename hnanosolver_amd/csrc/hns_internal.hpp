@@ -14,6 +14,9 @@
 
 #include "hns.h"
 
+// a function the host and the device both compile (hns_originhash.hpp, hns_dilate.hpp)
+#define HNS_HD __host__ __device__ __forceinline__
+
 namespace hns {
 
 // ---- error plumbing -------------------------------------------------------------------------------------------
@@ -178,7 +181,6 @@ struct Topology {
 	uint64_t offset(int32_t i, int32_t j, int32_t k) const;  // 1-based, 0 = outside
 };
 
-uint32_t hash_origin(int32_t x, int32_t y, int32_t z);
 void sort_leaf_origins(int32_t* xyz, size_t n);  // OpenVDB leaf order, in place (hns_leafio.cpp)
 
 // Device view handed to every kernel by value.
@@ -339,7 +341,7 @@ struct hns_sim {
 	// An allocation of their own from the arena pool, made on first use: nothing else reads them.
 	unsigned char* d_masks = nullptr;
 	size_t masks_bytes = 0;
-	hipEvent_t rev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // phase boundaries of the last hns_sim_regrid (hns_sim_regrid_times: 0-4); 5: the origins' read-back
+	hipEvent_t rev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // phase boundaries of the last hns_sim_regrid (hns_sim_regrid_times)
 	bool regrid_timed = false;
 	// hns_sim_deactivate's device table (its counts, then one row per listed field), made on first use from the arena pool, written by a kernel
 	void* d_act = nullptr;

@@ -16,7 +16,7 @@
 #include <unordered_set>
 
 #include "hns_dilate.hpp"
-#include "hns_internal.hpp"
+#include "hns_originhash.hpp"
 #include "hns_seed.hpp"
 #include "hns_stats.hpp"
 

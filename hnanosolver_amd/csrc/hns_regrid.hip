@@ -17,8 +17,8 @@
 // (duplicates are refused) the same way, and all but the velocity's (the mask waves find its leaves) are indexed into the new grid by one kernel.
 //
 //   1. candidates  one thread per (old leaf, offset in the (2R+1)^3 leaf neighbourhood), R = ceil(p / 8), one per SDF leaf and one per (velocity source
-//                  leaf, offset): a hit (the leaf's active voxels reach the candidate's box, hns_dilate.hpp) goes into a fresh origin hash with
-//                  compare-and-swap, then the hash is compacted. Each source's leaves go into an origin hash of their own
+//                  leaf, offset): a hit (the leaf's active voxels reach the candidate's box, hns_dilate.hpp) claims a slot of a fresh claim table
+//                  (hns_originhash.hpp), which is then compacted. Each source's leaves go into an index table of their own
 //   2. order       the origins come to the host, are sorted into OpenVDB leaf order and become a new hns_grid through the usual path (Topology::prepare,
 //                  hns_grid_upload: hash, nbr27, launch order); the source values are uploaded meanwhile
 //   3. masks       one wave per new leaf gathers the masks of the old leaves and velocity source leaves within reach (their origin hashes), dilates
@@ -49,7 +49,6 @@
 namespace hns {
 namespace {
 
-constexpr unsigned long long kEmptySlot = ~0ull;
 constexpr uint64_t kMaxCandidates = uint64_t(1) << 23;  // distinct leaves the candidate hash may hold (the grid limit is 2^22: Topology::prepare)
 constexpr int kCopyFields = 16;                          // float fields per copy or add launch
 constexpr uint32_t kSdfFill = 0x01010101u;               // collision_sdf where no leaf has a value: memset(..., 1, ...) (GridBuilder.hpp:108)
@@ -81,7 +80,7 @@ struct Candidates {
 	unsigned long long* table;
 	uint32_t mask;
 	unsigned long long cap;
-	unsigned long long* count;  // [0] slots reserved, [1] overflow, [2] compacted leaves
+	unsigned long long* count;  // (claim_slot states it)
 };
 
 // l: the old or seed-set leaf whose active voxels (`masks`) must reach the candidate, -1 for an SDF leaf
@@ -121,70 +120,31 @@ __global__ __launch_bounds__(256) void k_regrid_candidates(Candidates c) {
 			load_mask(ms, l, m);
 			if (!dilate_into(m, -8 * d[0], -8 * d[1], -8 * d[2], c.p, out)) continue;
 		}
-		uint32_t s = d_hash_origin(x, y, z) & c.mask;
-		bool reserved = false;
-		for (;;) {
-			unsigned long long cur = c.table[s];
-			if (cur == kEmptySlot) {
-				if (!reserved) {  // at most `cap` slots are ever taken: the table (>= 2 cap) always has an empty slot ahead
-					if (atomicAdd(&c.count[0], 1ull) >= c.cap) {
-						c.count[1] = 1;
-						break;
-					}
-					reserved = true;
-				}
-				cur = atomicCAS(&c.table[s], kEmptySlot, (unsigned long long)t);
-				if (cur == kEmptySlot) break;
-			}
+		claim_slot(c.table, c.mask, c.cap, c.count, hash_origin(x, y, z) & c.mask, (unsigned long long)t, [&](unsigned long long cur) {
 			int qx, qy, qz, ql, qd[3];
 			const unsigned char* qm;
 			cand_origin(c, cur, qx, qy, qz, ql, qd, qm);  // (an id in the table always stands for a valid origin)
-			if (qx == x && qy == y && qz == z) break;
-			s = (s + 1) & c.mask;
-		}
+			return qx == x && qy == y && qz == z;
+		});
 	}
 }
 
+// one thread per slot, whole waves
 __global__ __launch_bounds__(256) void k_regrid_compact(Candidates c, int4* __restrict__ out) {
 	const uint64_t s = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-	if (s > c.mask) return;
-	const unsigned long long t = c.table[s];
+	const unsigned long long t = s <= c.mask ? c.table[s] : kEmptySlot;
+	const uint32_t i = wave_compact(t != kEmptySlot, &c.count[2]);
 	if (t == kEmptySlot) return;
 	int x, y, z, l, d[3];
 	const unsigned char* m;
 	cand_origin(c, t, x, y, z, l, d, m);
-	out[atomicAdd(&c.count[2], 1ull)] = make_int4(x, y, z, 0);
+	out[i] = make_int4(x, y, z, 0);
 }
 
-// A source's leaves by origin: open addressing over `mask + 1` (>= 2 n) slots holding the leaf index, -1 = empty. Two leaves on one origin raise *dup.
-struct SrcHash {
-	const int4* origins;
-	const int* table;
-	uint32_t mask;
-};
-
+// A source's leaves into its index table of `mask + 1` (>= 2 n) slots. Two leaves on one origin raise *dup.
 __global__ __launch_bounds__(256) void k_regrid_src_hash(const int4* __restrict__ origins, int n, int* __restrict__ table, uint32_t mask, int* __restrict__ dup) {
 	const int i = blockIdx.x * 256 + threadIdx.x;
-	if (i >= n) return;
-	const int4 o = origins[i];
-	for (uint32_t s = d_hash_origin(o.x, o.y, o.z) & mask;; s = (s + 1) & mask) {
-		const int cur = atomicCAS(&table[s], -1, i);
-		if (cur == -1) return;
-		const int4 q = origins[cur];
-		if (q.x == o.x && q.y == o.y && q.z == o.z) {
-			*dup = 1;
-			return;
-		}
-	}
-}
-
-__device__ __forceinline__ int d_find_src(const SrcHash& h, int x, int y, int z) {
-	for (uint32_t s = d_hash_origin(x, y, z) & h.mask;; s = (s + 1) & h.mask) {
-		const int i = h.table[s];
-		if (i < 0) return -1;
-		const int4 q = h.origins[i];
-		if (q.x == x && q.y == y && q.z == z) return i;
-	}
+	if (i < n && insert_origin(origins, table, mask, i) >= 0) *dup = 1;
 }
 
 // idx[new leaf] = the source leaf with its origin; two such leaves on one origin raise *dup. Leaves outside the new grid are skipped (every SDF leaf
@@ -199,7 +159,7 @@ __global__ __launch_bounds__(256) void k_regrid_src_index(GridDev ng, const int4
 
 // The seed sets of k_regrid_masks by origin (h.table null: none) with their masks (null: every voxel active)
 struct SeedHashes {
-	SrcHash h[kSeedSets];
+	OriginIndex h[kSeedSets];
 	const unsigned char* masks[kSeedSets];
 };
 
@@ -232,7 +192,7 @@ __global__ __launch_bounds__(256) void k_regrid_masks(GridDev og, const unsigned
 		if (og.n_leaves > 0 && in_range) l = d_find_leaf(og, (int)nx, (int)ny, (int)nz);
 		int sl[kSeedSets];
 #pragma unroll
-		for (int q = 0; q < kSeedSets; ++q) sl[q] = sh.h[q].table && in_range ? d_find_src(sh.h[q], (int)nx, (int)ny, (int)nz) : -1;
+		for (int q = 0; q < kSeedSets; ++q) sl[q] = sh.h[q].table && in_range ? find_origin(sh.h[q], (int)nx, (int)ny, (int)nz) : -1;
 		if (k == centre) own = l, vown = sl[kVsrcSeeds];
 		uint64_t m[8];
 		if (l >= 0) {
@@ -255,15 +215,7 @@ __global__ __launch_bounds__(256) void k_regrid_masks(GridDev og, const unsigned
 		if (unseeded) unseeded[b] = in_unseeded;
 	}
 #pragma unroll
-	for (int x = 0; x < 8; ++x) {
-		uint32_t lo = (uint32_t)acc[x], hi = (uint32_t)(acc[x] >> 32);
-#pragma unroll
-		for (int w = 32; w >= 1; w >>= 1) {
-			lo |= __shfl_xor(lo, w);
-			hi |= __shfl_xor(hi, w);
-		}
-		acc[x] = (uint64_t)hi << 32 | lo;
-	}
+	for (int x = 0; x < 8; ++x) acc[x] = wave_or64(acc[x], true);
 	if (lane < 8) {
 		uint64_t w = 0;
 #pragma unroll
@@ -366,7 +318,7 @@ struct Source {
 	int field = -1;       // float field index (the SDF's: collision_sdf), -1 = the velocity
 	std::vector<int32_t> o4;  // the origins as int4 (host staging of the upload)
 	int4* origins = nullptr;
-	int* table = nullptr;  // origin hash (SrcHash)
+	int* table = nullptr;  // its index table (OriginIndex)
 	uint32_t mask = 0;
 	unsigned char* masks = nullptr;  // where they enter the domain (velocity, SDF); null = every voxel active
 	float* values = nullptr;
@@ -504,14 +456,11 @@ struct Regrid {
 		c.side = 2 * R + 1, c.R = R, c.p = p;
 		const uint64_t total = c.total();
 		c.cap = std::min<uint64_t>(total, kMaxCandidates);
-		uint64_t T = 16;
-		while (T < 2 * c.cap) T <<= 1;
+		const uint64_t T = hash_slots(2 * c.cap);
 		c.mask = (uint32_t)(T - 1);
 		for (Source& q : srcs) {
 			const uint64_t n = q.l.n_leaves;
-			uint64_t Ts = 16;
-			while (Ts < 2 * n) Ts <<= 1;
-			q.mask = (uint32_t)(Ts - 1);
+			q.mask = (uint32_t)(hash_slots(2 * n) - 1);
 			if (q.kind == Source::kPoints) continue;  // (already on the device)
 			q.o4.assign((size_t)n * 4, 0);
 			for (uint64_t i = 0; i < n; ++i)
@@ -577,15 +526,10 @@ struct Regrid {
 
 	// ---- 2. order + grid: the origins to the host, OpenVDB leaf order, the new grid; the source values go up meanwhile ----
 	int order() {
-		std::vector<int32_t> c4((size_t)n_new * 4);
-		HNS_HIP(hipMemcpyAsync(c4.data(), compact, 16 * n_new, hipMemcpyDeviceToHost, st));
-		HNS_HIP(hipEventRecord(s->rev[5], st));
+		std::vector<int32_t> xyz;
+		HNS_TRY(download_origins(compact, (size_t)n_new, st, &xyz));
 		for (Source& q : srcs)  // issued before the sort, so that they can overlap it
 			if (q.l.n_leaves && q.kind != Source::kPoints) HNS_HIP(hipMemcpyAsync(q.values, q.l.values, 2048 * (size_t)q.l.ncomp * q.l.n_leaves, hipMemcpyHostToDevice, st));
-		HNS_HIP(hipEventSynchronize(s->rev[5]));
-		std::vector<int32_t> xyz((size_t)n_new * 3);
-		for (uint64_t i = 0; i < n_new; ++i)
-			for (int a = 0; a < 3; ++a) xyz[3 * i + a] = c4[4 * i + a];
 		sort_leaf_origins(xyz.data(), (size_t)n_new);
 		ng.reset(new hns_grid);
 		ng->voxel_size = s->grid->voxel_size;
@@ -617,8 +561,8 @@ struct Regrid {
 			HNS_HIP(hipGetLastError());
 		}
 		SeedHashes sh{};
-		if (vsrc) sh.h[kVsrcSeeds] = SrcHash{vsrc->origins, vsrc->table, vsrc->mask}, sh.masks[kVsrcSeeds] = vsrc->masks;
-		if (points) sh.h[kPointSeeds] = SrcHash{points->origins, points->table, points->mask}, sh.masks[kPointSeeds] = points->masks;
+		if (vsrc) sh.h[kVsrcSeeds] = OriginIndex{vsrc->origins, vsrc->table, vsrc->mask}, sh.masks[kVsrcSeeds] = vsrc->masks;
+		if (points) sh.h[kPointSeeds] = OriginIndex{points->origins, points->table, points->mask}, sh.masks[kPointSeeds] = points->masks;
 		k_regrid_masks<<<(unsigned)((n_new + 3) / 4), 256, 0, st>>>(s->grid->dev(), s->d_masks, (const int4*)ng->d_origins, (int)n_new, p, R, sdf ? sdf->idx : nullptr,
 		                                                           sdf ? sdf->masks : nullptr, sh, (uint64_t*)new_masks, map, vsrc ? vsrc->idx : nullptr, unseeded);
 		HNS_HIP(hipGetLastError());

@@ -3,12 +3,12 @@
 // next domain without it crossing PCIe; hns_dev_point_leaves brings it to the host in OpenVDB leaf order.
 //
 // Two passes over the points, because the number of leaves is not known beforehand, both shaped to issue almost no atomic where points are coherent (an emitter):
-//   k_seed_keys     one thread per point: its 1, 2, 4 or 8 leaves as 63-bit keys into an open-addressing hash. Equal keys are merged within the wave BEFORE memory is touched,
-//                   and a probe reads the slot with a load first: the compare-and-swap is issued only on an empty slot
-//   k_seed_compact  every occupied slot gets a leaf index (one atomic per wave) and writes its origin
+//   k_seed_keys     one thread per point: its 1, 2, 4 or 8 leaves as 63-bit keys into a claim table (hns_originhash.hpp: claim_slot). Equal keys are merged within the wave
+//                   BEFORE memory is touched
+//   k_seed_compact  every occupied slot gets a leaf index (wave_compact) and writes its origin
 //   k_seed_masks    one thread per point: the leaf index of each of its leaves by loads alone, then the tap bits as at most eight 64-bit ORs (two when the cell lies inside
 //                   one leaf), merged within the wave like the keys and each skipped when a load shows its bits already set
-// Keys never leave the table and bits are only ever set, so a stale load can only cause an atomic that was not needed. Everything that decides the result is order-free: a
+// Bits are only ever set, so a stale load can only cause an OR that was not needed (as for the keys: claim_slot). Everything that decides the result is order-free: a
 // set of keys, ORs of bits; the compacted order is discarded by whoever sorts. Integer atomics only, no LDS.
 #include <cstring>
 
@@ -18,10 +18,9 @@
 namespace hns {
 namespace {
 
-constexpr unsigned long long kEmptyKey = ~0ull;
 constexpr int kMergeRounds = 8;  // distinct keys (mask words) a wave merges per slot before its lanes insert (OR) on their own
 
-// The key hash: open addressing over mask + 1 >= 2 min(8n, 2^23) slots. count: [0] slots reserved, [1] overflow, [2] leaves, [3] points that do not seed.
+// The key table: a claim table of mask + 1 >= 2 min(8n, 2^23) slots. count: [0..2] as claim_slot states them ([2]: leaves), [3] points that do not seed.
 struct SeedTable {
 	unsigned long long* keys;
 	int* leaf;  // slot -> leaf index, written by k_seed_compact for occupied slots only
@@ -30,7 +29,7 @@ struct SeedTable {
 	unsigned long long* count;
 };
 
-// three leaf coordinates (cell >> 3, in [-2^20, 2^20)) biased by 2^20, 21 bits each: never all ones in 64 bits
+// three leaf coordinates (cell >> 3, in [-2^20, 2^20)) biased by 2^20, 21 bits each: never kEmptySlot
 __device__ __forceinline__ unsigned long long leaf_key(int lx, int ly, int lz) {
 	return (unsigned long long)(unsigned)(lx + (1 << 20)) << 42 | (unsigned long long)(unsigned)(ly + (1 << 20)) << 21 | (unsigned long long)(unsigned)(lz + (1 << 20));
 }
@@ -39,11 +38,8 @@ __device__ __forceinline__ int4 key_origin(unsigned long long k) {
 }
 __device__ __forceinline__ uint32_t key_slot(unsigned long long k, uint32_t mask) {
 	const int4 o = key_origin(k);
-	return d_hash_origin(o.x, o.y, o.z) & mask;
+	return hash_origin(o.x, o.y, o.z) & mask;
 }
-
-// a load that another CU's atomic is visible to (the per-CU cache is passed by): what "read before you swap / OR" reads
-__device__ __forceinline__ unsigned long long load_fresh(const unsigned long long* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 // The cell of a seeding point: lower corner (i, j, k), which axes cross into the next leaf, the lower leaf's coordinates.
 struct SeedCell {
@@ -62,28 +58,6 @@ __device__ __forceinline__ bool seed_cell(const float* __restrict__ xyz, unsigne
 	return true;
 }
 
-__device__ __forceinline__ void insert_key(const SeedTable& t, unsigned long long key) {
-	bool reserved = false;
-	for (uint32_t s = key_slot(key, t.mask);; s = (s + 1) & t.mask) {
-		unsigned long long cur = load_fresh(t.keys + s);
-		if (cur == kEmptyKey) {
-			if (!reserved) {
-				if (atomicAdd(&t.count[0], 1ull) >= t.reserve) {
-					t.count[1] = 1;
-					return;
-				}
-				reserved = true;
-			}
-			cur = atomicCAS(t.keys + s, kEmptyKey, key);
-			if (cur == kEmptyKey) return;
-		}
-		if (cur == key) {  // a key that was seen is a key that is present
-			if (reserved) atomicAdd(&t.count[0], ~0ull);  // (given back: count[0] never exceeds the occupied slots plus one per thread in flight)
-			return;
-		}
-	}
-}
-
 __global__ __launch_bounds__(256) void k_seed_keys(const float* __restrict__ xyz, const unsigned n, const SeedTable t) {
 	const unsigned p = blockIdx.x * 256u + threadIdx.x;
 	const int lane = (int)(threadIdx.x & 63u);
@@ -93,7 +67,7 @@ __global__ __launch_bounds__(256) void k_seed_keys(const float* __restrict__ xyz
 	for (int c = 0; c < 8; ++c) {
 		bool pending = seeds && C.has(c);
 		if (!__ballot(pending)) continue;
-		const unsigned long long key = pending ? C.key(c) : kEmptyKey;
+		const unsigned long long key = pending ? C.key(c) : kEmptySlot;
 		bool mine = false;  // this lane inserts for every lane of the wave that held its key
 		for (int r = 0; r < kMergeRounds; ++r) {
 			const unsigned long long left = __ballot(pending);
@@ -104,7 +78,7 @@ __global__ __launch_bounds__(256) void k_seed_keys(const float* __restrict__ xyz
 				mine = lane == first;
 			}
 		}
-		if (mine || pending) insert_key(t, key);
+		if (mine || pending) claim_slot(t.keys, t.mask, t.reserve, t.count, key_slot(key, t.mask), key, [key](unsigned long long cur) { return cur == key; });
 	}
 	unsigned skip = p < n && !seeds ? 1u : 0u;
 #pragma unroll
@@ -112,19 +86,12 @@ __global__ __launch_bounds__(256) void k_seed_keys(const float* __restrict__ xyz
 	if (lane == 0 && skip) atomicAdd(&t.count[3], (unsigned long long)skip);
 }
 
-// One thread per slot; a wave takes its leaf indices with one atomic. Leaves beyond `cap` (the refusal's case) are counted and not written.
+// One thread per slot. Leaves beyond `cap` (the refusal's case) are counted and not written.
 __global__ __launch_bounds__(256) void k_seed_compact(const SeedTable t, int4* __restrict__ origins, const unsigned long long cap) {
 	const uint64_t s = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-	const int lane = (int)(threadIdx.x & 63u);
-	const unsigned long long key = s <= t.mask ? t.keys[s] : kEmptyKey;
-	const unsigned long long full = __ballot(key != kEmptyKey);
-	if (!full) return;
-	unsigned long long base = 0;
-	if (lane == 0) base = atomicAdd(&t.count[2], (unsigned long long)__popcll(full));
-	base = readlane64(base, 0);
-	if (key == kEmptyKey) return;
-	const unsigned long long l = base + (unsigned long long)__popcll(full & ((1ull << lane) - 1ull));
-	if (l >= cap) return;
+	const unsigned long long key = s <= t.mask ? t.keys[s] : kEmptySlot;
+	const uint32_t l = wave_compact(key != kEmptySlot, &t.count[2]);
+	if (key == kEmptySlot || l >= cap) return;
 	origins[l] = key_origin(key);
 	t.leaf[s] = (int)l;
 }
@@ -132,17 +99,6 @@ __global__ __launch_bounds__(256) void k_seed_compact(const SeedTable t, int4* _
 __device__ __forceinline__ int find_key(const SeedTable& t, unsigned long long key) {
 	for (uint32_t s = key_slot(key, t.mask);; s = (s + 1) & t.mask)
 		if (t.keys[s] == key) return t.leaf[s];  // (every key asked for was inserted by k_seed_keys)
-}
-
-// OR of `bits` over the lanes for which `take` holds, in every lane (two 32-bit butterflies)
-__device__ __forceinline__ unsigned long long wave_or(unsigned long long bits, bool take) {
-	uint32_t lo = take ? (uint32_t)bits : 0u, hi = take ? (uint32_t)(bits >> 32) : 0u;
-#pragma unroll
-	for (int w = 32; w >= 1; w >>= 1) {
-		lo |= (uint32_t)__shfl_xor((int)lo, w);
-		hi |= (uint32_t)__shfl_xor((int)hi, w);
-	}
-	return (unsigned long long)hi << 32 | lo;
 }
 
 // masks: leaf x 8 words; word x holds the bytes y = 0 .. 7 of layer x, bit z of each. The two z-taps of a row share a byte, the two y-rows of a layer a word: a point has
@@ -178,7 +134,7 @@ __global__ __launch_bounds__(256) void k_seed_masks(const float* __restrict__ xy
 					if (!left) break;
 					const int first = __ffsll((long long)left) - 1;
 					const bool same = pending && word == (unsigned)__builtin_amdgcn_readlane((int)word, first);
-					const unsigned long long all = wave_or(bits, same);
+					const unsigned long long all = wave_or64(bits, same);
 					if (same) pending = false;
 					if (lane == first) mine = true, bits = all;
 				}
@@ -197,8 +153,7 @@ int seed_leaves(Scratch& scratch, const float* d_xyz, uint64_t n, hipStream_t st
 	*out = SeedSet{};
 	if (n == 0) return HNS_OK;
 	const uint64_t cap = std::min<uint64_t>(8 * n, kMaxSeedLeaves);
-	uint64_t T = 16;
-	while (T < 2 * cap) T <<= 1;
+	const uint64_t T = hash_slots(2 * cap);
 	SeedTable t{};
 	t.mask = (uint32_t)(T - 1);
 	// A thread holds at most one reservation it may still give back, and fewer than 2^22 threads are in flight: with 2^23 or fewer distinct leaves count[0] stays below
@@ -262,14 +217,10 @@ extern "C" int hns_dev_point_leaves(int device, const float* d_xyz, uint64_t n, 
 		HNS_HIP(hipStreamSynchronize(st));
 		return HNS_OK;
 	}
-	std::vector<int32_t> o4((size_t)S.n_leaves * 4);
 	std::vector<unsigned char> m(masks_out ? (size_t)S.n_leaves * 64 : 0);
-	HNS_HIP(hipMemcpyAsync(o4.data(), S.origins, 16 * S.n_leaves, hipMemcpyDeviceToHost, st));
 	if (masks_out) HNS_HIP(hipMemcpyAsync(m.data(), S.masks, 64 * S.n_leaves, hipMemcpyDeviceToHost, st));
-	HNS_HIP(hipStreamSynchronize(st));
-	std::vector<int32_t> xyz((size_t)S.n_leaves * 3);
-	for (uint64_t i = 0; i < S.n_leaves; ++i)
-		for (int a = 0; a < 3; ++a) xyz[3 * i + a] = o4[4 * i + a];
+	std::vector<int32_t> xyz;
+	HNS_TRY(download_origins(S.origins, (size_t)S.n_leaves, st, &xyz));
 	std::vector<uint32_t> perm;
 	leaf_order(xyz.data(), (size_t)S.n_leaves, &perm);
 	for (uint64_t r = 0; r < S.n_leaves; ++r) {

@@ -73,4 +73,15 @@ int seed_leaves(Scratch& scratch, const float* d_xyz, uint64_t n, hipStream_t st
 // hns_leafio.cpp: perm[r] = the position in xyz of the leaf that comes r-th in OpenVDB leaf order (sort_leaf_origins' order)
 void leaf_order(const int32_t* xyz, size_t n, std::vector<uint32_t>* perm);
 
+// n int4 origins on the device, as xyz on the host: what sort_leaf_origins and leaf_order take. Waits for `st`.
+inline int download_origins(const int4* d_origins, size_t n, hipStream_t st, std::vector<int32_t>* xyz) {
+	std::vector<int32_t> o4(n * 4);
+	HNS_HIP(hipMemcpyAsync(o4.data(), d_origins, 16 * n, hipMemcpyDeviceToHost, st));
+	HNS_HIP(hipStreamSynchronize(st));
+	xyz->resize(n * 3);
+	for (size_t i = 0; i < n; ++i)
+		for (int a = 0; a < 3; ++a) (*xyz)[3 * i + a] = o4[4 * i + a];
+	return HNS_OK;
+}
+
 }  // namespace hns

@@ -10,7 +10,7 @@
 #include <cstring>
 #include <thread>
 
-#include "hns_internal.hpp"
+#include "hns_originhash.hpp"
 
 namespace hns {
 
@@ -28,17 +28,6 @@ void set_error(const char* fmt, ...) {
 Options& options() {
 	static Options o;
 	return o;
-}
-
-uint32_t hash_origin(int32_t x, int32_t y, int32_t z) {
-	// leaf coordinates (origin >> 3) mixed with three odd 32-bit constants; the same function runs on the device
-	uint32_t h = (uint32_t)(x >> 3) * 0x9E3779B1u;
-	h ^= (uint32_t)(y >> 3) * 0x85EBCA77u;
-	h ^= (uint32_t)(z >> 3) * 0xC2B2AE3Du;
-	h ^= h >> 15;
-	h *= 0x2C1B3C6Du;
-	h ^= h >> 12;
-	return h;
 }
 
 int64_t Topology::find_leaf(int32_t ox, int32_t oy, int32_t oz) const {
@@ -67,9 +56,7 @@ int Topology::prepare(const int32_t* leaf_origins_xyz, int64_t n) {
 	n_leaves = n;
 	have_tables = false;
 	origins.assign((size_t)n * 4, 0);
-	uint32_t size = 16;
-	while ((int64_t)size < 2 * n + 2) size <<= 1;
-	hash_mask = size - 1;
+	hash_mask = (uint32_t)(hash_slots(2 * (uint64_t)n + 2) - 1);
 	for (int64_t l = 0; l < n; ++l) {
 		const int32_t ox = leaf_origins_xyz[3 * l], oy = leaf_origins_xyz[3 * l + 1], oz = leaf_origins_xyz[3 * l + 2];
 		if ((ox & 7) || (oy & 7) || (oz & 7)) {
