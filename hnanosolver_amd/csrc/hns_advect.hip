@@ -317,6 +317,11 @@ constexpr int kBox = 1000, kBoxShell = kBox - 512;
 // k_advect_vector_n pads its rows from 10 to 24 floats (kVY; a plane = kVP floats): a wave's taps are an 8 (y) x 8 (z) window of one x-slice, and with rows 24 apart the four rows of
 // a 32-lane group fall on banks c, c + 24, c + 16, c + 8 (+ 0..7): every bank once. With rows 10 apart six lanes of every group collide (46 % of the kernel's LDS cycles were conflicts).
 constexpr int kVY = 24, kVX = 10 * kVY, kVP = 10 * kVX;
+// Only 10 of a row's 24 floats are used, so a second component's rows lie in the gaps: x rows at 24 r and y rows at 24 r + 12 share one plane, z has a plane of its own --
+// two planes (19,200 B), not three. A load reads ONE component for all lanes, so every component keeps the bank pattern above, shifted uniformly (y by 12 banks).
+// Component offsets from a cell: x 0, y kVCy, z kVCz; the box is kVBox floats.
+constexpr int kVCy = kVY / 2, kVCz = kVP, kVBox = 2 * kVP;
+static_assert(kVCy + 10 <= kVY, "velocity box: the y rows (10 floats from kVCy) run into the next x row");
 // shell cell h in [0, 488): the two full x-slabs (2 x 100), the y = -1 / 8 rows of the inner x (2 x 80), the z = -1 / 8 ends of the inner rows (2 x 64):
 // slot of its leaf in the 27-table, voxel inside that leaf, box cell
 template <int XS = 100, int YS = 10>  // strides of the box the cell number is for
@@ -354,26 +359,26 @@ __device__ __forceinline__ int box_own(int n) { return ((n >> 6) + 1) * XS + (((
 template <int XS = 100, int YS = 10>
 __device__ __forceinline__ constexpr int box_nbr(int d) { return (d & 1 ? 1 : -1) * (d < 2 ? XS : (d < 4 ? YS : 1)); }
 
-// Stage the velocity box, three component planes PS apart: every thread its own voxel (value vo), the first 488 the shell cell `cell` with the voxel at `off` (box_shell_off).
+// Stage the velocity box, components y and z at CY and CZ floats from x (three planes, or kVCy / kVCz): every thread its own voxel (value vo), the first 488 the shell cell `cell` with the voxel at `off` (box_shell_off).
 // What a shell cell outside the domain holds is the caller's choice of `off`: unmapped it reads 0 (advect_vector: the descriptor's bounds check), mapped to element g.oob that
 // element (advect_scalars, Kernel.cu:225). In two halves, load and store: the store waits for the load, and a kernel that has gathers to issue puts them in between
 // (k_advect_scalars_n<false, true>: with the store in front of them the kernel was 2.3 % slower, profiles/advect_refactor_ab.txt). The caller's barrier completes the box.
-template <int XS, int YS, int PS>
+template <int XS, int YS, int CY, int CZ>
 __device__ __forceinline__ f3 velocity_box_load(float* s_box, const v4i& ru, int n, const f3& vo, unsigned off) {
 	const int ob = box_own<XS, YS>(n);
-	s_box[ob] = vo.x, s_box[ob + PS] = vo.y, s_box[ob + 2 * PS] = vo.z;
+	s_box[ob] = vo.x, s_box[ob + CY] = vo.y, s_box[ob + CZ] = vo.z;
 	f3 h = {0.0f, 0.0f, 0.0f};
 	if (n < kBoxShell) h = ldv(ru, off);
 	return h;
 }
-template <int PS>
+template <int CY, int CZ>
 __device__ __forceinline__ void velocity_box_store(float* s_box, int n, int cell, const f3& h) {
-	if (n < kBoxShell) s_box[cell] = h.x, s_box[cell + PS] = h.y, s_box[cell + 2 * PS] = h.z;
+	if (n < kBoxShell) s_box[cell] = h.x, s_box[cell + CY] = h.y, s_box[cell + CZ] = h.z;
 }
 __device__ __forceinline__ V3 box_v3(const float* s_box, int a) {
 	V3 r;
-	r.xy = v2f32{s_box[a], s_box[a + kVP]};
-	r.z = s_box[a + 2 * kVP];
+	r.xy = v2f32{s_box[a], s_box[a + kVCy]};
+	r.z = s_box[a + kVCz];
 	return r;
 }
 __device__ __forceinline__ f3 box_f3(const float* s_box, int a) {
@@ -442,7 +447,7 @@ template <bool COLL>
 __device__ __forceinline__ void advect_vector_n(const GridDev& g, const float* __restrict__ u, float* __restrict__ out, const float* __restrict__ sdf, float* s_sdf, const float scaled_dt,
                                                 const float inv_dx) {
 	__shared__ NarrowTabs tabs;
-	__shared__ float s_box[3 * kVP];
+	__shared__ float s_box[kVBox];
 	// the voxel's own velocity needs the leaf number only: its load is issued before the neighbour table is fetched and staged (one memory
 	// round trip less in front of the first gathers; the kernel is bound by the length of that chain)
 	NarrowCtx C(g, tabs);
@@ -458,9 +463,9 @@ __device__ __forceinline__ void advect_vector_n(const GridDev& g, const float* _
 	int cell;
 	const unsigned off = box_shell_off<kVX, kVY>(tabs.b4, C.n, cell);
 	const int ob = box_own<kVX, kVY>(C.n);
-	const f3 hv = velocity_box_load<kVX, kVY, kVP>(s_box, ru, C.n, vo, off);
+	const f3 hv = velocity_box_load<kVX, kVY, kVCy, kVCz>(s_box, ru, C.n, vo, off);
 	if constexpr (COLL) sdf_box_store(s_sdf, C.n, cell, sdf_box_load(s_sdf, rs, C.n, ob, so, off));
-	velocity_box_store<kVP>(s_box, C.n, cell, hv);
+	velocity_box_store<kVCy, kVCz>(s_box, C.n, cell, hv);
 	float sx = C.px - scaled_dt * vo.x, sy = C.py - scaled_dt * vo.y, sz = C.pz - scaled_dt * vo.z;  // backPos (Kernel.cu:374)
 	float rx = C.px, ry = C.py, rz = C.pz;                                                            // COLL: where a collision sends the trace back to
 	f3 vf = {0.0f, 0.0f, 0.0f}, vb = {0.0f, 0.0f, 0.0f};
@@ -501,7 +506,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
 	advect_vector_n<false>(g, u, out, nullptr, nullptr, scaled_dt, 0.0f);
 }
 // LDS: the velocity box, the SDF box and the tables. Four workgroups per CU (eight waves per SIMD) need a quarter of gfx950's 160 KB each.
-constexpr int kVectorCollLds = (3 * kVP + kVP) * 4 + (int)sizeof(NarrowTabs);
+constexpr int kVectorCollLds = (kVBox + kVP) * 4 + (int)sizeof(NarrowTabs);
 static_assert(kVectorCollLds <= 160 * 1024 / 4, "k_advect_vector_n<true>: four workgroups per CU no longer fit the LDS");
 template <bool COLL>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_advect_vector_n(const GridDev g, const float* __restrict__ u, float* __restrict__ out,
@@ -747,8 +752,9 @@ __device__ __forceinline__ bool sample_setup(const GridDev& g, const NarrowCtx& 
 // its table staging, its back position, its eight tap offsets and its eight 12-byte gathers are the ones made here. The kernel writes advect_vector(u) of its voxels to adv_out as
 // well: both first samples are formed from the one set of taps (nested lerps for the vector, weight products for the fields: different bits); the vector's sample then waits in LDS
 // while the fields are advected, and BEHIND the per-field loop the vector half takes its second sample from a velocity box (rows kVY apart, as k_advect_vector_n), clamps and stores.
-// That order is the one that fits 80 registers without a spill (70; the vector half in front of the loop: 100, profiles/lookahead_ab.txt): three workgroups per CU, by registers and by
-// LDS (43 KB) alike. Same loads of the same values, same arithmetic in the same association as k_advect_vector_n and k_advect_scalars_n<false>: bit-identical to the two launches.
+// That order is the one that fits without a spill (the vector half in front of the loop: 100 registers, profiles/lookahead_ab.txt); with the two-plane velocity box and the far-tap
+// path's grid fields read where that path runs (gk below) it is 64 registers and 33.8 KB of LDS: four workgroups per CU, eight waves per SIMD (profiles/lookahead_occupancy_ab.txt).
+// Same loads of the same values, same arithmetic in the same association as k_advect_vector_n and k_advect_scalars_n<false>: bit-identical to the two launches.
 // COLL: with a collision SDF, staged as a fourth box (see sdf_box_load; 0 outside the domain, unlike the field boxes of this kernel). The back position is tested before its
 // sample is set up and falls back to the voxel's own position (Kernel.cu:142-155; the reference makes that test twice, and the repeat cannot change the outcome), the forward
 // position before the second set-up and falls back to the back position (:211-214). Per lane. The fields' arithmetic is untouched.
@@ -763,11 +769,19 @@ __device__ __forceinline__ bool sdf_hit(const GridDev& g, const NarrowCtx& C, co
 		d = tri_f_b(rs, make_taps_b(g, C, x, y, z));
 	return d < 0.0f;
 }
+// The kernel's GridDev where it lies in the kernel-argument segment. ONLY in kernels whose FIRST parameter is the GridDev (by value: offset 0 of the segment): a field read through
+// this reference is a scalar load at the point of use, where the same field of the by-value parameter is loaded at the kernel's entry and held.
+__device__ __forceinline__ const GridDev& kernarg_grid() { return *reinterpret_cast<const GridDev*>((const void*)__builtin_amdgcn_kernarg_segment_ptr()); }
+
 template <bool Q4, bool AHEAD, bool COLL>
 __device__ __forceinline__ void advect_scalars_n(const GridDev& g, const float* __restrict__ u, const ScalarPtrs& P, const float scaled_dt, float* __restrict__ adv_out,
                                                  const float* __restrict__ sdf) {
 	static_assert(!(Q4 && AHEAD), "the look-ahead form is float-only");
 	static_assert(!(AHEAD && COLL), "with a collider the next substep rewrites the velocity before it advects it: nothing to look ahead to");
+	// AHEAD: what the far-tap path needs of the grid (origins, nbr27, hash, hash_mask, far_flag) is read where that path runs, not held from the kernel's entry in nine scalar
+	// registers across three inlined copies of it: at eight waves per SIMD 80 scalar registers are addressable, and with them held the kernel spilled four into a VGPR's lanes
+	// -- the 65th register (profiles/lookahead_occupancy_ab.txt).
+	const GridDev& gk = AHEAD ? kernarg_grid() : g;
 	__shared__ NarrowTabs tabs;
 	NarrowCtx C(g, tabs);
 	const int n = C.n, idx = C.idx;
@@ -794,7 +808,7 @@ __device__ __forceinline__ void advect_scalars_n(const GridDev& g, const float* 
 	// and costs the float-only form a fifth (one more 12-byte gather per thread for the velocity shell, and a barrier in front of its first gathers)
 	constexpr bool FIRST = Q4;
 	__shared__ float s_ubox[FIRST ? 3 * kBox : 1];
-	if constexpr (FIRST) velocity_box_store<kBox>(s_ubox, n, hcell, velocity_box_load<100, 10, kBox>(s_ubox, ru, n, vc, ho));
+	if constexpr (FIRST) velocity_box_store<kBox, 2 * kBox>(s_ubox, n, hcell, velocity_box_load<100, 10, kBox, 2 * kBox>(s_ubox, ru, n, vc, ho));
 
 	float bx = C.px - scaled_dt * vc.x, by = C.py - scaled_dt * vc.y, bz = C.pz - scaled_dt * vc.z;
 	__shared__ float s_back[COLL && FIRST ? 3 * 512 : 1];
@@ -811,14 +825,14 @@ __device__ __forceinline__ void advect_scalars_n(const GridDev& g, const float* 
 	f3 vf = {0.0f, 0.0f, 0.0f};
 	// AHEAD: the velocity box of k_advect_vector_n (shell cells outside the domain read 0 there -- the descriptor's bounds check -- not element g.oob), and advect_vector's
 	// first sample
-	__shared__ float s_vbox[AHEAD ? 3 * kVP : 1];
+	__shared__ float s_vbox[AHEAD ? kVBox : 1];
 	__shared__ float s_wf[AHEAD ? 3 * 512 : 1];  // (advect_vector's first sample waits here, not in three registers, while the fields are advected)
 	if constexpr (AHEAD) {
 		int vcell;
 		const unsigned voff = box_shell_off<kVX, kVY>(tabs.b4, n, vcell);
-		const f3 hv = velocity_box_load<kVX, kVY, kVP>(s_vbox, ru, n, vc, voff);
+		const f3 hv = velocity_box_load<kVX, kVY, kVCy, kVCz>(s_vbox, ru, n, vc, voff);
 		// the eight taps of the back cell, gathered ONCE with the unmapped offsets: 0 outside the domain, which is what advect_vector samples
-		const TapsB T = make_taps_b(g, C, bx, by, bz);
+		const TapsB T = make_taps_b(gk, C, bx, by, bz);
 		V3 c[8];  // (issued in the order the weight products consume them: the z lerp of a column follows as soon as its second tap has been added, and the pair's registers are free)
 #pragma unroll
 		for (int q = 0; q < 8; ++q) {
@@ -828,7 +842,7 @@ __device__ __forceinline__ void advect_scalars_n(const GridDev& g, const float* 
 		}
 		const float* __restrict__ uoob = u + 3 * (size_t)g.oob;
 		const f3 uo = {uoob[0], uoob[1], uoob[2]};  // what advect_scalars samples outside the domain: element g.oob (a uniform address: scalar registers)
-		velocity_box_store<kVP>(s_vbox, n, vcell, hv);
+		velocity_box_store<kVCy, kVCz>(s_vbox, n, vcell, hv);
 		tri_weights(T.fx, T.fy, T.fz, bw);
 		// Two samples from the one set of taps. advect_scalars': the weight products, a tap outside the domain replaced by element g.oob. advect_vector's: nested lerps
 		// (tri_v_b) -- column z[t >> 1] = lerp(c[t - 1], c[t]) once the odd tap t has been added.
@@ -846,7 +860,7 @@ __device__ __forceinline__ void advect_scalars_n(const GridDev& g, const float* 
 	} else {
 		// Where the flow moves less than a voxel per step the FIRST sample point, too, lies among the voxel's 26 neighbours: its taps (velocity here, the fields' below) come out of
 		// the boxes, per lane.
-		bboxed = sample_setup<FIRST>(g, C, bx, by, bz, oob4, ba, bo, bw);
+		bboxed = sample_setup<FIRST>(gk, C, bx, by, bz, oob4, ba, bo, bw);
 		f3 vt[8];
 		if (!bboxed) {
 #pragma unroll
@@ -879,7 +893,7 @@ __device__ __forceinline__ void advect_scalars_n(const GridDev& g, const float* 
 			}
 		}
 	}
-	const bool boxed = sample_setup<true>(g, C, fx, fy, fz, oob4, fa, fo, fw);
+	const bool boxed = sample_setup<true>(gk, C, fx, fy, fz, oob4, fa, fo, fw);
 	// COLL and Q4: a sample has a box cell or tap offsets, never both, so from here on the cell rides in the first offset's register (the q4 form sits on the 80-register
 	// line, and with the tests in front of its set-ups it spilled the back cell)
 	constexpr bool SHARE = COLL && Q4;
@@ -972,14 +986,18 @@ __device__ __forceinline__ void advect_scalars_n(const GridDev& g, const float* 
 		const f3 vo = box_f3(s_vbox, obv);
 		const f3 wf = f3{s_wf[m], s_wf[m + 512], s_wf[m + 1024]};
 		const float cx = (float)w.x - scaled_dt * vo.x, cy = (float)w.y - scaled_dt * vo.y, cz = (float)w.z - scaled_dt * vo.z;  // backPos (Kernel.cu:374)
-		const f3 wb = sample_velocity(g, C, ru, s_vbox, cx + scaled_dt * wf.x, cy + scaled_dt * wf.y, cz + scaled_dt * wf.z);  // Kernel.cu:387
+		const f3 wb = sample_velocity(gk, C, ru, s_vbox, cx + scaled_dt * wf.x, cy + scaled_dt * wf.y, cz + scaled_dt * wf.z);  // Kernel.cu:387
 		st3(adv_out, idx, bfecc_limit_v(vo, wf, wb, [&](int d) { return box_f3(s_vbox, obv + box_nbr<kVX, kVY>(d)); }));
 	}
 }
 
 // Two templates of ONE name, as k_advect_vector_n: <Q4, AHEAD> without a collision field, under the symbols the resource tests pin, and <Q4, false, true> below, which takes the SDF.
+// LDS of the look-ahead form: the tables, the velocity box, advect_vector's first sample and two float boxes. Four workgroups per CU (eight waves per SIMD, at 64 registers) need a
+// quarter of gfx950's 160 KB each. (the q4 form: at least six waves, the float-only form at least four, as before)
+constexpr int kLookaheadLds = (int)sizeof(NarrowTabs) + (kVBox + 3 * 512 + 2 * kBox) * 4;
+static_assert(kLookaheadLds <= 160 * 1024 / 4, "k_advect_scalars_n<false, true>: four workgroups per CU no longer fit the LDS");
 template <bool Q4, bool AHEAD = false>
-__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(Q4 || AHEAD ? 6 : 4))) void k_advect_scalars_n(const GridDev g, const float* __restrict__ u, const ScalarPtrs P, const float scaled_dt,
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(AHEAD ? 8 : (Q4 ? 6 : 4), 8))) void k_advect_scalars_n(const GridDev g, const float* __restrict__ u, const ScalarPtrs P, const float scaled_dt,
                                                                                                             float* __restrict__ adv_out) {
 	advect_scalars_n<Q4, AHEAD, false>(g, u, P, scaled_dt, adv_out, nullptr);
 }
