@@ -285,3 +285,44 @@ def test_pack_unpack_leaves(case):
     refv = np.zeros((nl, 1536), np.float32)
     refv[ids_h] = case.f["vel"].reshape(nl, 1536)[ids_h]
     assert np.array_equal(dv.cpu().numpy().reshape(-1), refv.reshape(-1))
+
+
+def test_kernel_by_kernel_guard_banded(case):
+    """The kernel-by-kernel comparisons above once more through tests/hip_kernels.py with slab=True: every output and in-place operand carved from a patterned
+    slab with two leaves of pattern around it. Same oracle, same bar; besides, no kernel may store outside its outputs or write an operand it only reads."""
+    from hip_kernels import HipKernels
+    from oracle_lib import oracle
+
+    K, O, f = HipKernels(case.origins, case.vs, slab=True), case.oracle, case.f
+    dt, inv_dx, vs = case.dt, case.inv_dx, case.vs
+    sdf = fields.sphere_sdf(case.origins, case.R, center=(0.5, 0.3, 0.5), radius=0.2)
+    sdf[::7] = np.float32(0.05)
+    omega = float(oracle().orc_omega_compute(vs))
+    div = O.divergence(f["vel"], inv_dx)
+    rng = np.random.default_rng(11)
+    p = rng.standard_normal(case.N).astype(np.float32)
+    p0 = (0.01 * rng.standard_normal(case.N)).astype(np.float32)
+    waste = (0.5 * np.abs(rng.standard_normal(case.N))).astype(np.float32)
+    phis = [f[n] for n in ("density", "temperature", "fuel", "waste", "flame")]
+    for coll in (False, True):
+        s = sdf if coll else None
+        assert_close(K.advect_vector(f["vel"], dt, inv_dx, s, coll), O.advect_vector(f["vel"], dt, inv_dx, s, coll), f"advect_vector coll={coll}")
+        assert_close(K.advect_scalar(f["vel"], f["density"], dt, inv_dx, s, coll), O.advect_scalar(f["vel"], f["density"], dt, inv_dx, s, coll), f"advect_scalar coll={coll}")
+        for i, (got, want) in enumerate(zip(K.advect_scalars(f["vel"], phis, dt, inv_dx, s, coll), O.advect_scalars(f["vel"], phis, dt, inv_dx, s, coll))):
+            assert_close(got, want, f"advect_scalars[{i}] coll={coll}")
+        assert_close(K.subtract_pressure_gradient(f["vel"], p, inv_dx, s, coll), O.subtract_pressure_gradient(f["vel"], p, inv_dx, s, coll), f"gradient coll={coll}")
+    assert_close(K.divergence(f["vel"], inv_dx), div, "divergence")
+    want, got = p0.copy(), p0
+    for color in (0, 1):
+        O.rbgs(div, want, vs, color, omega)
+        got = K.rbgs(div, got, vs, color, omega)
+        assert_close(got, want, f"rbgs_color {color}")
+    for iters in (1, 2, 7):
+        assert_close(K.rbgs_iterations(div, vs, omega, iters, p0), O.rbgs_iterations(div, vs, omega, iters, p0), f"rbgs_fused x{iters}")
+    for got, w, name in zip(K.combustion_oxygen(f["fuel"], waste, f["temperature"], div, f["flame"], 0.5, 0.1),
+                            O.combustion_oxygen(f["fuel"], waste, f["temperature"], div, f["flame"], 0.5, 0.1), ["fuel", "waste", "temperature", "flame", "divergence"]):
+        assert_close(got, w, f"combustion {name}")
+    assert_close(K.temperature_buoyancy(f["vel"], f["temperature"], dt, 23.0, 1.0), O.temperature_buoyancy(f["vel"], f["temperature"], dt, 23.0, 1.0), "buoyancy")
+    for fs in (0.5, 1.0, 2.0):
+        assert_close(K.vorticity_confinement(f["vel"], dt, inv_dx, 1.0, fs), O.vorticity_confinement(f["vel"], dt, inv_dx, 1.0, fs), f"vorticity fs={fs}")
+    assert_close(K.enforce_collision_boundaries(f["vel"], sdf, vs), O.enforce_collision_boundaries(f["vel"], sdf, vs), "enforce_collision")
