@@ -70,6 +70,10 @@ class hns_solve_report(C.Structure):
     _fields_ = [("iterations", C.c_int), ("checks", C.c_int), ("converged", C.c_int), ("initial", hns_stats), ("final", hns_stats)]
 
 
+class hns_solve_method(C.Structure):
+    _fields_ = [("method", C.c_int), ("pre", C.c_int), ("post", C.c_int), ("coarse_iterations", C.c_int), ("max_levels", C.c_int), ("omega", C.c_float)]
+
+
 class hns_combustion_params(C.Structure):
     _fields_ = [(n, C.c_float) for n in ("expansionRate", "temperatureRelease", "buoyancyStrength", "ambientTemp", "vorticityScale", "factorScale")]
 
@@ -149,6 +153,8 @@ SIGNATURES = {
     "hns_sim_residual": (_i, [_vp, _f, C.POINTER(hns_stats), _vp]),
     "hns_sim_set_solve_control": (_i, [_vp, C.POINTER(hns_solve_control)]),
     "hns_sim_solve_report": (_i, [_vp, C.POINTER(hns_solve_report), _vp, _i, _ip]),
+    "hns_sim_set_solve_method": (_i, [_vp, C.POINTER(hns_solve_method)]),
+    "hns_sim_solve_levels": (_i, [_vp, _ip, C.POINTER(C.c_uint64), _i]),
     "hns_dev_advect_vector": (_i, [_vp, _fp, _fp, _fp, _i, _f, _f, _vp]),
     "hns_dev_advect_scalar": (_i, [_vp, _fp, _fp, _fp, _fp, _i, _f, _f, _vp]),
     "hns_dev_advect_scalars": (_i, [_vp, _fp, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _i, _fp, _i, _f, _f, _vp]),

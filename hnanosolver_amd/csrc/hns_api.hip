@@ -59,6 +59,7 @@ extern "C" void hns_sim_destroy(hns_sim* s) {
 	if (s->xfer) (void)hipStreamDestroy(s->xfer);
 	if (s->h_dig) (void)hipHostFree(s->h_dig);
 	hns_sim_free_diagnostics(s);
+	hns_sim_free_multigrid(s);
 	hns_arena_put(s->d_masks, s->masks_bytes, s->device);
 	hns_arena_put(s->d_act, s->act_bytes, s->device);
 	hns_arena_put(s->arena, s->arena_bytes, s->device);
@@ -251,6 +252,7 @@ static int validate_step(float voxel_size, float dt, int64_t iterations, bool ne
 // the pressure hot loop: p = 0, `iterations` x (red, black); HNanoSolver.cu:256-272 / PressureProjection.cu:51-60
 static int sim_pressure(hns_sim* s, int iterations, float voxel_size, float omega, void* stream) {
 	if (s->control) return hns_sim_pressure_controlled(s, iterations, voxel_size, omega, stream);  // hns_sim_set_solve_control: `iterations` is the maximum
+	if (s->mg) return hns_sim_pressure_multigrid(s, iterations, voxel_size, stream);                // hns_sim_set_solve_method: `iterations` V-cycles, the method's own omega
 	int in_b = 0;  // never warm-started (HNanoSolver.cu:113): the solve starts from p = 0, which the first sweep knows without reading p_a
 	HNS_TRY(s->solve_begin(stream));
 	HNS_TRY(hns_rbgs_iterate(s->grid, s->div, s->p_a, s->p_b, voxel_size, omega, iterations, &in_b, stream, true));
@@ -269,6 +271,7 @@ extern "C" int hns_sim_pressure_solve(hns_sim* s, int iterations, float voxel_si
 	if (!s) return fail(HNS_ERR_INVALID_ARGUMENT, "hns_sim_pressure_solve: null sim");
 	HNS_TRY(validate_step(voxel_size, 0.0f, iterations, true));
 	if (s->control) HNS_TRY(hns_refuse_capture(stream, "hns_sim_pressure_solve"));
+	if (s->mg) HNS_TRY(hns_mg_ready(s, stream, "hns_sim_pressure_solve"));
 	return sim_pressure(s, iterations, voxel_size, omega_compute(voxel_size), stream);
 }
 
@@ -500,7 +503,7 @@ struct Substep {
 		for (const std::string& n : s->names) advected += n != "collision_sdf";
 		char sor[256];
 		if (hns_grid_rbgs_plan(s->grid, iterations, sor, sizeof(sor), nullptr, nullptr) != HNS_OK) sor[0] = 0;
-		std::string pressure(sor, strcspn(sor, ":"));
+		std::string pressure = s->mg ? hns_mg_plan(s) : std::string(sor, strcspn(sor, ":"));
 		std::string out = std::string("collision=") + (coll ? "k_enforce_collision" : "-");
 		out += std::string(" advect_vector=") + (memo() ? "memo" : hns_advect_vector_kernel(g, sdf, coll));
 		out += std::string(" vorticity=") + (vorticity() ? "k_vorticity" : "-");
@@ -532,6 +535,7 @@ int sim_substep(hns_sim* s, int iterations, float dt, float voxel_size, const hn
 	HNS_TRY(validate_step(voxel_size, dt, iterations, true));
 	if (s->n == 0) return HNS_OK;  // HNanoSolver.cu:26-28
 	if (s->control) HNS_TRY(hns_refuse_capture(stream, params ? "hns_sim_substep" : "hns_sim_core_substep"));  // (before anything is launched)
+	if (s->mg) HNS_TRY(hns_mg_ready(s, stream, params ? "hns_sim_substep" : "hns_sim_core_substep"));           // (a hierarchy that a regrid dropped is built here, not on a capturing stream)
 	Substep step;
 	HNS_TRY(step.prepare(s, iterations, dt, voxel_size, params, has_collision, stream));
 	return step.run();

@@ -208,11 +208,17 @@ __device__ __forceinline__ int tile_nbr(int n) {  // tile entry of the face neig
 	return inside ? n + DIR * (1 << shift) : 512 + 64 * f + ab;
 }
 
-// The Gauss-Seidel value of a voxel in the reference's association (Kernel.cu:621): what the sweep relaxes p towards (hns_pressure.hip: sor_update) and
+// The Gauss-Seidel value of a voxel in the reference's association (Kernel.cu:621): what the sweep relaxes p towards (sor_update below) and
 // what the residual measures p against (hns_diagnostics.hip: k_residual).
 __device__ __forceinline__ float gs_value(float pxp, float pxm, float pyp, float pym, float pzp, float pzm, float divVal, float dx2) {
 	constexpr float inv6 = 0.166666667f;
 	return ((pxp + pxm + pyp + pym + pzp + pzm) - divVal * dx2) * inv6;
+}
+
+// One relaxed Gauss-Seidel update (Kernel.cu:621-622): every sweep of hns_pressure.hip and hns_multigrid.hip
+__device__ __forceinline__ float sor_update(float pxp, float pxm, float pyp, float pym, float pzp, float pzm, float divVal, float pOld, float dx2, float omega) {
+	const float pGS = gs_value(pxp, pxm, pyp, pym, pzp, pzm, divVal, dx2);  // Kernel.cu:621
+	return pOld + omega * (pGS - pOld);                                      // Kernel.cu:622
 }
 
 // One wave stages a whole tile of float field p for the leaf of launch record `rec` ({leaf, nbr27[27]}: GridDev::blk): its own values as two 16-byte

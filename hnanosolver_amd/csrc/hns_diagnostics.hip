@@ -252,7 +252,8 @@ void hns_sim_free_diagnostics(hns_sim* s) {
 	s->h_diag = nullptr, s->d_diag = nullptr, s->diag_bytes = 0, s->control = nullptr;
 }
 
-// The pressure loop under a control (include/hns.h: hns_solve_control): the loop of sim_pressure (hns_api.hip) cut into pieces of check_every iterations, the residual behind each.
+// The pressure loop under a control (include/hns.h: hns_solve_control): the loop of sim_pressure (hns_api.hip) cut into pieces of check_every iterations (V-cycles under
+// hns_sim_set_solve_method), the residual behind each.
 // A piece is the same sequence of launches the uncontrolled loop makes for those iterations, so the pressure after j iterations is the uncontrolled solve's, bit for bit.
 int hns_sim_pressure_controlled(hns_sim* s, int max_iterations, float voxel_size, float omega, void* stream) {
 	const char* who = "hns_sim_pressure_solve (controlled)";
@@ -270,13 +271,19 @@ int hns_sim_pressure_controlled(hns_sim* s, int max_iterations, float voxel_size
 	HNS_HIP(hipMemsetAsync(s->p_a, 0, sizeof(float) * 512 * (size_t)g->topo.n_leaves, st));
 	HNS_TRY(launch_residual(g, s->div, s->p_a, voxel_size, nullptr, table, d_rec, st, who));
 	float *cur = s->p_a, *other = s->p_b;
+	// one step of k iterations -- V-cycles under hns_sim_set_solve_method -- further: the launches the uncontrolled solve makes for them
+	auto step = [&](int k, bool first) {
+		if (s->mg) return hns_mg_cycles(s, &cur, &other, voxel_size, k, first, stream);
+		int in_b = 0;
+		HNS_TRY(hns_rbgs_iterate(g, s->div, cur, other, voxel_size, omega, k, &in_b, stream, first));
+		if (in_b) std::swap(cur, other);
+		return (int)HNS_OK;
+	};
 	const bool monitor_only = ctl.c.rel_tol == 0.0f && ctl.c.abs_tol == 0.0f;
 	int done = 0;
 	while (done < max_iterations) {
 		const int k = std::min(ctl.c.check_every, max_iterations - done);
-		int in_b = 0;
-		HNS_TRY(hns_rbgs_iterate(g, s->div, cur, other, voxel_size, omega, k, &in_b, stream, done == 0));
-		if (in_b) std::swap(cur, other);
+		HNS_TRY(step(k, done == 0));
 		done += k;
 		HNS_TRY(launch_residual(g, s->div, cur, voxel_size, nullptr, table, d_rec + 1, st, who));
 		HNS_TRY(fetch(s, d_rec, ctl.history.empty() ? 0 : 1, ctl.history.empty() ? 2 : 1, st));  // the one wait of this check

@@ -360,6 +360,10 @@ struct hns_sim {
 		bool ran = false;
 	};
 	Control* control = nullptr;
+	// hns_sim_set_solve_method: null = SOR, and then sim_pressure (hns_api.hip) is the plain loop after one more pointer test; else the V-cycle's parameters and its
+	// hierarchy of coarse grids, masks, tables and buffers (hns_multigrid.hip)
+	struct Multigrid;
+	Multigrid* mg = nullptr;
 	int device = -1;
 	int find(const char* name) const {
 		for (size_t i = 0; i < names.size(); ++i)
@@ -376,6 +380,14 @@ namespace hns { int check_activity_fields(const hns_sim* s, const hns_activity_f
 int hns_sim_pressure_controlled(hns_sim* s, int max_iterations, float voxel_size, float omega, void* stream);
 int hns_refuse_capture(void* stream, const char* who);
 void hns_sim_free_diagnostics(hns_sim* s);  // (hns_sim_destroy)
+
+// hns_multigrid.hip: the V-cycle solve of a sim with a method set (include/hns.h: hns_solve_method)
+int hns_mg_ready(hns_sim* s, void* stream, const char* who);  // the hierarchy of the sim's current grid is there afterwards: built here when a regrid dropped it (refused on a capturing stream), before anything is launched
+int hns_mg_cycles(hns_sim* s, float** cur, float** other, float dx, int cycles, bool first, void* stream);  // `cycles` V-cycles on *cur (first: from p = 0, whatever *cur holds); *cur / *other are swapped as the fine sweeps ping-pong
+int hns_sim_pressure_multigrid(hns_sim* s, int cycles, float voxel_size, void* stream);  // the uncontrolled solve (hns_api.hip: sim_pressure)
+std::string hns_mg_plan(hns_sim* s);  // the pressure stage's word of hns_sim_substep_plan
+void hns_sim_drop_hierarchy(hns_sim* s);   // the sim has moved onto another grid (hns_regrid.hip): the next solve builds the hierarchy again
+void hns_sim_free_multigrid(hns_sim* s);   // (hns_sim_destroy)
 void hns_grid_free_splat(hns_grid* g);       // hns_splat.hip: the grid's accumulator back to the pool (hns_grid_release_cache, and through it hns_grid_destroy)
 
 // the sim's buffers over one arena (hns_api.hip): bytes an arena needs for n voxels, and the slices of `arena` for them (sets n, every buffer pointer, d_dig, p_result)

@@ -48,11 +48,7 @@ __global__ __launch_bounds__(512) void k_divergence(const GridDev g, const float
 // red-black SOR, two-launch form: one colour in place (reference Kernel.cu:591-623 / :521-588)
 // ---------------------------------------------------------------------------------------------------------------
 
-__device__ __forceinline__ float sor_update(float pxp, float pxm, float pyp, float pym, float pzp, float pzm, float divVal, float pOld,
-                                            float dx2, float omega) {
-	const float pGS = gs_value(pxp, pxm, pyp, pym, pzp, pzm, divVal, dx2);  // Kernel.cu:621
-	return pOld + omega * (pGS - pOld);                                      // Kernel.cu:622
-}
+// (sor_update: hns_device.hpp)
 
 __global__ __launch_bounds__(256) void k_rbgs_color(const GridDev g, const float* __restrict__ div, float* p, const float dx2, const float omega,
                                                     const int color) {

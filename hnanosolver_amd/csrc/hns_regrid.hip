@@ -633,6 +633,7 @@ struct Regrid {
 		s->d_masks = (unsigned char*)new_masks, s->masks_bytes = scratch.keep(new_masks);
 		s->grid = ng.release();
 		s->forget();
+		hns_sim_drop_hierarchy(s);  // (hns_sim_set_solve_method: the next solve builds the new grid's)
 		s->solved = false;  // (the divergence / pressure scratch holds no defined values: hns_sim_residual refuses until the next solve)
 		s->regrid_timed = true;
 		*out = s->grid;

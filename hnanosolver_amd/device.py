@@ -503,6 +503,24 @@ class Sim:
         return {"iterations": r.iterations, "checks": r.checks, "converged": bool(r.converged), "initial": _record(r.initial)[0], "final": _record(r.final)[0],
                 "history": hist}
 
+    def solve_method(self, method: Optional[int] = 1, pre: int = 2, post: int = 2, coarse_iterations: int = 8, max_levels: int = 0, omega: float = 1.0) -> None:
+        """The solve method of pressure_solve / substep / core_substep (``hns_sim_set_solve_method``). method 1: geometric multigrid V(pre, post) cycles on the
+        leaf-sparse grid with exact coarse-level masks -- `iterations` of those calls then counts CYCLES, also under a ``solve_control`` --, `coarse_iterations` sweeps on the
+        coarsest level, at most `max_levels` levels (0: as deep as the leaf set goes), every sweep relaxed by `omega`. method 0 or None: back to SOR, the default."""
+        if method is None:
+            _raise(lib.hns_sim_set_solve_method(self._ptr, None))
+            return
+        m = _lib.hns_solve_method(int(method), int(pre), int(post), int(coarse_iterations), int(max_levels), float(omega))
+        _raise(lib.hns_sim_set_solve_method(self._ptr, C.byref(m)))
+
+    def solve_levels(self) -> List[int]:
+        """Leaves per level of the V-cycle's hierarchy, level 0 first (``hns_sim_solve_levels``)"""
+        n = C.c_int(0)
+        _raise(lib.hns_sim_solve_levels(self._ptr, C.byref(n), None, 0))
+        out = (C.c_uint64 * max(1, n.value))()
+        _raise(lib.hns_sim_solve_levels(self._ptr, C.byref(n), out, n.value))
+        return [int(x) for x in out[: n.value]]
+
     def regrid_times(self):
         """hipEvent split of the last regrid in ms: {candidates, host (origins, sort, grid tables), masks, fields}"""
         ms = (C.c_float * 4)()

@@ -88,7 +88,7 @@ int hns_trim_memory(void);
  *                   the interior launch at every size (what larger ranks always do)
  *   "dist_wire_us"  N: the loopback transport of hns_dist holds every exchange N microseconds (emulated wire time)
  *   "arena_fill"    off | 0 .. 255 (a byte, in decimal): a TEST switch, no kernel form. Every block the pool of device memory (hns_trim_memory) hands out -- simulation states,
- *                   grid and SOR tables, regrid scratch, masks, the deactivation and diagnostics tables; one taken from the pool or fresh from the driver -- is first filled
+ *                   grid and SOR tables, regrid scratch, masks, the deactivation and diagnostics tables, the V-cycle's hierarchy; one taken from the pool or fresh from the driver -- is first filled
  *                   with that byte over its whole size. No result may depend on it: 255 makes the block NaN as floats, -1 as ints and all-set as masks; 127 makes it
  *                   3.39e38, for what lets a NaN lose (tests/test_pool_contents_gpu.py). The fill is a hipMemset followed by a wait for the WHOLE device on every draw:
  *                   never leave it on in production, and never have it on while a stream is capturing (the wait would break the capture). Default off: one atomic load
@@ -501,6 +501,52 @@ typedef struct {
 	hns_stats initial, final;
 } hns_solve_report;
 int hns_sim_solve_report(hns_sim*, hns_solve_report*, hns_stats* history, int capacity, int* n_history);
+
+/* ------------------------------------------------------------------------------------------------------------ */
+/* A second solve method: geometric multigrid V-cycles on the leaf-sparse grid (new: the reference has SOR only)  */
+/* ------------------------------------------------------------------------------------------------------------ */
+
+/* Selected per sim, off by default: a sim that never sets a method runs the SOR loop bit for bit and launch for launch as before (one more pointer test). With method 1 set,
+ * the `iterations` argument of hns_sim_pressure_solve, hns_sim_substep and hns_sim_core_substep is the number of V-CYCLES; under a solve control it is their maximum,
+ * check_every counts cycles and hns_solve_report.iterations reports cycles. hns_sim_timing counts cycles, hns_sim_residual works after a V-cycle solve, and
+ * hns_sim_substep_plan words the pressure stage `vcycle<pre,post,coarse_iterations>/L<levels>:<fine kernel>+k_mg_restrict+k_mg_color+k_mg_prolong`. omega is explicit: the
+ * reference's 2 / (1 + sin(pi * voxel_size)) means nothing on a level with a doubled voxel size. The setter does its device work (the hierarchy) on a private stream it waits
+ * for; the solves stay asynchronous on their own streams and allocate nothing. NULL, or method 0 (its other members are not looked at): back to SOR.
+ *
+ * THE HIERARCHY, per grid topology; a regrid drops it and the next solve (or hns_sim_solve_levels) builds it again -- which is refused on a capturing stream
+ * (HNS_ERR_INVALID_ARGUMENT, nothing launched), as a controlled solve is.
+ *   Level 0       the sim's grid; every voxel of every leaf is an unknown, as in the SOR.
+ *   Level l + 1   voxel size doubled; coarse voxel I = i >> 1 per axis on global coordinates (a floor: negative coordinates work). Its leaves are the distinct
+ *                 floor(origin / 16) * 8 of the level below. A coarse voxel is an UNKNOWN iff at least one of its eight children is an unknown of the level below (exact
+ *                 masks, 64 bytes per leaf, byte x*8+y, bit z); every other voxel of a coarse leaf holds +0 and is never updated. Without the masks the cycle diverges on
+ *                 ragged leaf sets (DESIGN_HISTORY.md).
+ *   Depth         levels end at one leaf, at max_levels, or where the next level would have no fewer leaves than this one (leaves either side of coordinate 0 never merge:
+ *                 floor keeps origins -8 and 0 apart; isolated far tiles do not merge either). A hierarchy of one level is `coarse_iterations` plain sweeps per cycle.
+ *
+ * THE ARITHMETIC: single rounded f32 operations, unfused; dx of level l + 1 is 2.0f * dx of level l, dx2 = dx * dx.
+ *   Sweep         the red-black update of Kernel.cu:621-622 with the method's omega, on unknowns only; level 0 through hns_dev_rbgs_iterate's kernels.
+ *   Residual      c = hns_dev_residual's correction of the level's p against its right-hand side (level 0: the divergence); +0 at a voxel that is not an unknown.
+ *   Restriction   rhs_c[I] = (((c000 + c001) + (c010 + c011)) + ((c100 + c101) + (c110 + c111))) * k, children indexed dx dy dz, a child in an absent leaf reads +0,
+ *                 k = -0.75f / dx2 of the FINE level: the mean of the children's residual in divergence units, -6 c / dx^2.
+ *   Coarse solve  from e = 0, the sweep above with rhs_c and the coarse dx2.
+ *   Prolongation  cell-centred trilinear: per axis the second coarse voxel is I + ((i & 1) ? 1 : -1); v = 0.75f * a + 0.25f * b (two multiplies, then an add) with a the value
+ *                 at I's side, nested z, then y, then x; a coarse voxel that is absent or masked reads 0. Then p[i] = p[i] + v on unknowns only.
+ *   One cycle on level l: `pre` sweeps; residual and restriction; the cycle on level l + 1 -- on the coarsest level `coarse_iterations` sweeps instead of all this --;
+ *                 prolongation and add; `post` sweeps. The first cycle of a solve starts from p = 0.
+ * The drop-in operators and the sims of a grid's cook cache never use a method; hns_dist_* has none.
+ * HNS_ERR_INVALID_ARGUMENT, sim unchanged: a method other than 0 or 1, pre or post < 0 or both 0, coarse_iterations < 1, max_levels < 0, an omega that is not a finite
+ * number strictly between 0 and 2, a grid whose launch range is not the whole grid, a sim lent to a grid's cook cache. */
+typedef struct {
+	int method;            /* 0 = SOR (default), 1 = V-cycle */
+	int pre, post;         /* red-black iterations before / after the coarse correction on every level, >= 0, pre + post >= 1 */
+	int coarse_iterations; /* iterations on the coarsest level, >= 1 */
+	int max_levels;        /* 0 = as deep as the rule above goes; else at most this many levels, level 0 included */
+	float omega;           /* relaxation factor of every sweep, 0 < omega < 2 */
+} hns_solve_method;
+int hns_sim_set_solve_method(hns_sim*, const hns_solve_method*);
+/* The hierarchy's depth and (leaves_per_level != NULL) the leaf count of its first min(capacity, *n_levels) levels, level 0 first. Builds the hierarchy when a regrid
+ * dropped it (synchronous then). HNS_ERR_RUNTIME when no method is set. */
+int hns_sim_solve_levels(hns_sim*, int* n_levels, uint64_t* leaves_per_level, int capacity);
 
 /* ------------------------------------------------------------------------------------------------------------ */
 /* Kernel-level entry points on caller-owned DEVICE memory (asynchronous on `stream`).                           */
