@@ -249,19 +249,6 @@ static int validate_step(float voxel_size, float dt, int64_t iterations, bool ne
 	return HNS_OK;
 }
 
-// the pressure hot loop: p = 0, `iterations` x (red, black); HNanoSolver.cu:256-272 / PressureProjection.cu:51-60
-static int sim_pressure(hns_sim* s, int iterations, float voxel_size, float omega, void* stream) {
-	if (s->control) return hns_sim_pressure_controlled(s, iterations, voxel_size, omega, stream);  // hns_sim_set_solve_control: `iterations` is the maximum
-	if (s->mg) return hns_sim_pressure_multigrid(s, iterations, voxel_size, stream);                // hns_sim_set_solve_method: `iterations` V-cycles, the method's own omega
-	int in_b = 0;  // never warm-started (HNanoSolver.cu:113): the solve starts from p = 0, which the first sweep knows without reading p_a
-	HNS_TRY(s->solve_begin(stream));
-	HNS_TRY(hns_rbgs_iterate(s->grid, s->div, s->p_a, s->p_b, voxel_size, omega, iterations, &in_b, stream, true));
-	HNS_TRY(s->solve_end(stream, iterations));
-	s->p_result = in_b ? s->p_b : s->p_a;
-	s->solved = true;
-	return HNS_OK;
-}
-
 namespace hns {  // (declared in hns_dist.hpp: the partitioned substep uses the same omega)
 float omega_compute(float vs) { return 2.0f / (1.0f + sinf(static_cast<float>(3.14159) * vs)); }          // HNanoSolver.cu:257
 }  // namespace hns
@@ -270,9 +257,8 @@ static float omega_project(float vs) { return (float)(2.0f / (1.0f + sin(3.14159
 extern "C" int hns_sim_pressure_solve(hns_sim* s, int iterations, float voxel_size, void* stream) {
 	if (!s) return fail(HNS_ERR_INVALID_ARGUMENT, "hns_sim_pressure_solve: null sim");
 	HNS_TRY(validate_step(voxel_size, 0.0f, iterations, true));
-	if (s->control) HNS_TRY(hns_refuse_capture(stream, "hns_sim_pressure_solve"));
-	if (s->mg) HNS_TRY(hns_mg_ready(s, stream, "hns_sim_pressure_solve"));
-	return sim_pressure(s, iterations, voxel_size, omega_compute(voxel_size), stream);
+	HNS_TRY(hns_solve_preflight(s, stream, "hns_sim_pressure_solve"));
+	return hns_sim_solve(s, iterations, voxel_size, omega_compute(voxel_size), stream);
 }
 
 // Bracket every following pressure loop (up to max_solves of them) with a hipEvent pair on its launch stream.
@@ -460,7 +446,7 @@ struct Substep {
 			}
 		}
 		HNS_TRY(mark(2));
-		HNS_TRY(sim_pressure(s, iterations, voxel_size, omega_compute(voxel_size), stream));  // :256-272
+		HNS_TRY(hns_sim_solve(s, iterations, voxel_size, omega_compute(voxel_size), stream));  // :256-272
 		HNS_TRY(mark(3));
 		HNS_TRY(hns_dev_subtract_pressure_gradient(g, s->adv, s->p_result, s->vel, sdf, coll,
 		                                           inv_dx, stream));  // :278-289
@@ -534,8 +520,7 @@ struct Substep {
 int sim_substep(hns_sim* s, int iterations, float dt, float voxel_size, const hns_combustion_params* params, int has_collision, void* stream) {
 	HNS_TRY(validate_step(voxel_size, dt, iterations, true));
 	if (s->n == 0) return HNS_OK;  // HNanoSolver.cu:26-28
-	if (s->control) HNS_TRY(hns_refuse_capture(stream, params ? "hns_sim_substep" : "hns_sim_core_substep"));  // (before anything is launched)
-	if (s->mg) HNS_TRY(hns_mg_ready(s, stream, params ? "hns_sim_substep" : "hns_sim_core_substep"));           // (a hierarchy that a regrid dropped is built here, not on a capturing stream)
+	HNS_TRY(hns_solve_preflight(s, stream, params ? "hns_sim_substep" : "hns_sim_core_substep"));  // (before anything is launched)
 	Substep step;
 	HNS_TRY(step.prepare(s, iterations, dt, voxel_size, params, has_collision, stream));
 	return step.run();
@@ -1032,7 +1017,7 @@ extern "C" int hns_project_non_divergent(hns_grid* g, hns_field* fields, int n_f
 	if (!s) return HNS_OK;
 	const float inv_dx = 1.0f / voxel_size;
 	HNS_TRY(hns_dev_divergence(g, s->vel, s->div, inv_dx, stream));              // PressureProjection.cu:48
-	HNS_TRY(sim_pressure(s, (int)iterations, voxel_size, omega_project(voxel_size), stream));            // :51-60 (0 iterations leaves p = 0)
+	HNS_TRY(hns_sim_solve(s, (int)iterations, voxel_size, omega_project(voxel_size), stream));            // :51-60 (0 iterations leaves p = 0)
 	HNS_TRY(hns_dev_subtract_pressure_gradient(g, s->vel, s->p_result, s->vel, nullptr, 0,
 	                                           inv_dx, stream));  // :64, in place
 	return hns_sim_download(s, fs.velocity, 1, stream);

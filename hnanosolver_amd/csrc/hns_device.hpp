@@ -208,12 +208,15 @@ __device__ __forceinline__ int tile_nbr(int n) {  // tile entry of the face neig
 	return inside ? n + DIR * (1 << shift) : 512 + 64 * f + ab;
 }
 
-// The Gauss-Seidel value of a voxel in the reference's association (Kernel.cu:621): what the sweep relaxes p towards (sor_update below) and
-// what the residual measures p against (hns_diagnostics.hip: k_residual).
-__device__ __forceinline__ float gs_value(float pxp, float pxm, float pyp, float pym, float pzp, float pzm, float divVal, float dx2) {
-	constexpr float inv6 = 0.166666667f;
-	return ((pxp + pxm + pyp + pym + pzp + pzm) - divVal * dx2) * inv6;
+// The Gauss-Seidel value of a voxel in the reference's association (Kernel.cu:621) with the product divVal * dx2 passed in: the temporally blocked sweeps carry
+// it already multiplied (hns_sorblock.hip: sb_update)
+__device__ __forceinline__ float gs_value_of(float pxp, float pxm, float pyp, float pym, float pzp, float pzm, float div_dx2) {
+	constexpr float inv6 = 0.166666667f;  // Kernel.cu:609
+	return ((pxp + pxm + pyp + pym + pzp + pzm) - div_dx2) * inv6;
 }
+// The same from divVal and dx2: what the sweep relaxes p towards (sor_update below), what the residual measures p against (hns_diagnostics.hip: k_residual) and
+// what the V-cycle restricts (hns_multigrid.hip: k_mg_restrict)
+__device__ __forceinline__ float gs_value(float pxp, float pxm, float pyp, float pym, float pzp, float pzm, float divVal, float dx2) { return gs_value_of(pxp, pxm, pyp, pym, pzp, pzm, divVal * dx2); }
 
 // One relaxed Gauss-Seidel update (Kernel.cu:621-622): every sweep of hns_pressure.hip and hns_multigrid.hip
 __device__ __forceinline__ float sor_update(float pxp, float pxm, float pyp, float pym, float pzp, float pzm, float divVal, float pOld, float dx2, float omega) {
@@ -348,6 +351,71 @@ __device__ __forceinline__ float nbr_val3(const float* __restrict__ u, const int
 		const int nl = s_nbr[13 - (AXIS == 0 ? 9 : (AXIS == 1 ? 3 : 1))];
 		return nl < 0 ? 0.0f : u[3 * (size_t)(nl * 512 + n + 7 * stride) + COMP];
 	}
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// the projection's reference expressions, each stated once (hns_pressure.hip, hns_pointwise.hip, hns_multigrid.hip)
+// ---------------------------------------------------------------------------------------------------------------
+
+// LDS written by this wave is visible to this wave
+__device__ __forceinline__ void wave_sync() {
+	__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+	__builtin_amdgcn_wave_barrier();
+	__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// divergence of one voxel (Kernel.cu:499-519) from its centre velocity c and the six face values: u.x at +-x, u.y at +-y, u.z at +-z (0 outside the domain)
+__device__ __forceinline__ float divergence_of(f3 c, float uxp, float uxm, float uyp, float uym, float uzp, float uzm, float inv_dx) {
+	const float xp = (c.x + uxp) * 0.5f, xm = (c.x + uxm) * 0.5f;
+	const float yp = (c.y + uyp) * 0.5f, ym = (c.y + uym) * 0.5f;
+	const float zp = (c.z + uzp) * 0.5f, zm = (c.z + uzm) * 0.5f;
+	return (xp - xm + yp - ym + zp - zm) * inv_dx;
+}
+
+// one component of the central pressure gradient (Kernel.cu:795-801)
+__device__ __forceinline__ float central_gradient(float p_plus, float p_minus, float inv_dx) { return ((p_plus - p_minus) * 0.5f) * inv_dx; }
+
+// combustion_oxygen of one voxel (Kernel.cu:923-966): the four new fields, the burn amount and whether the voxel burns at all (no oxygen left: it passes through, and
+// `burn` is not to be used). Branch-free -- selects between bit-exact alternatives -- as the fused divergence launch needs it (hns_pressure.hip: fused_epilogue).
+struct Burnt { float fuel, waste, temperature, flame, burn; bool burns; };
+__device__ __forceinline__ Burnt combust_voxel(float fuel, float waste, float temperature, float flame, float temp_gain) {
+	const float fu = fuel < 0.001f ? 0.0f : fuel;  // :936-938
+	const float oxy = 1.0f - fu - waste;           // :941
+	const bool burns = !(oxy < 0.0f);              // :942-949
+	const float burn = fminf(oxy, fu);             // :952
+	const float te = burns ? temperature + burn * temp_gain : temperature;
+	return {burns ? fu - burn : fu, burns ? waste + burn * 2.0f : waste, te, burns ? fmaxf(flame, fminf(1.0f, burn * 10.0f)) : flame, burn, burns};
+}
+// what combustion leaves of a divergence d (Kernel.cu:964)
+__device__ __forceinline__ float combust_divergence(const Burnt& b, float d, float expansion) { return b.burns ? d + b.burn * expansion : d; }
+
+// temperature_buoyancy of one voxel (Kernel.cu:831-847): vel + (0, max(0, (T - Tamb) * k), 0) * dt where T > Tamb. The x and z results are vel + 0 * dt; they go
+// through the same add so that the stored bits equal the reference's (-0 + 0 = +0). Branch-free, as combust_voxel.
+__device__ __forceinline__ f3 buoyancy_voxel(f3 v, float t, float dt, float ambient, float strength) {
+	const bool hot = !(t <= ambient);
+	const float tempDiff = t - ambient;
+	const float bx = v.x + dt * 0.0f, by = v.y + dt * fmaxf(0.0f, tempDiff * strength), bz = v.z + dt * 0.0f;
+	return {hot ? bx : v.x, hot ? by : v.y, hot ? bz : v.z};
+}
+
+// is voxel v of leaf `leaf` an unknown? masks: 64 bytes per leaf, byte x*8+y, bit z; null = every voxel (hns_multigrid.hip)
+__device__ __forceinline__ bool is_unknown(const unsigned char* __restrict__ masks, int leaf, int v) { return !masks || ((masks[(size_t)leaf * 64 + (v >> 3)] >> (v & 7)) & 1); }
+
+// One colour of one red-black iteration in place (Kernel.cu:591-623 / :521-588), a 256-thread workgroup per leaf, one thread per voxel of the colour.
+// MASKED: on unknowns only -- a voxel whose mask bit is clear keeps its 0 (k_mg_color); else every voxel (k_rbgs_color).
+template <bool MASKED>
+__device__ __forceinline__ void color_sweep(const GridDev& g, int* s_nbr, const unsigned char* __restrict__ masks, const float* __restrict__ div, float* p, float dx2,
+                                            float omega, int color) {
+	const LeafCtx L = stage_leaf(g, s_nbr, blockIdx.x);
+	const int t = threadIdx.x, x = t >> 5, y = (t >> 2) & 7;
+	const int z = 2 * (t & 3) + ((x + y + color) & 1);  // origins are 8-aligned, so global parity == local parity
+	const int n = (x << 6) | (y << 3) | z;
+	if (MASKED && !is_unknown(masks, L.leaf, n)) return;
+	const int idx = L.leaf * 512 + n;
+	const float pxp = nbr_val<0, 1>(p, s_nbr, L.leaf, n), pxm = nbr_val<0, -1>(p, s_nbr, L.leaf, n);
+	const float pyp = nbr_val<1, 1>(p, s_nbr, L.leaf, n), pym = nbr_val<1, -1>(p, s_nbr, L.leaf, n);
+	const float pzp = nbr_val<2, 1>(p, s_nbr, L.leaf, n), pzm = nbr_val<2, -1>(p, s_nbr, L.leaf, n);
+	p[idx] = sor_update(pxp, pxm, pyp, pym, pzp, pzm, div[idx], p[idx], dx2, omega);
 }
 
 }  // namespace hns

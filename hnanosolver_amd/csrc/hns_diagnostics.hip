@@ -1,5 +1,5 @@
 // hns_diagnostics.hip -- what a device-resident sim can say about itself without a download (include/hns.h: "Diagnostics"): statistics of its fields, the residual
-// of its pressure solve, and the solve that stops on that residual. Hand-written HIP for gfx950 / CDNA4, wave64.
+// of its pressure solve, and what a solve control adds to the solve's driver so that it stops on that residual (hns_pressure.hip: hns_sim_solve). Hand-written HIP for gfx950 / CDNA4, wave64.
 //
 // Everything ends in hns_stats records, and every record comes out of ONE reduction (hns_stats.hpp; the host mirror hns_leaf_stats walks the same trees):
 //   a wave turns one leaf of one component into a partial record (leaf_record: per-lane sums over voxels 64k + lane, then an xor butterfly) and writes it into a table,
@@ -239,12 +239,6 @@ int fetch(hns_sim* s, const hns_stats* d_rec, int first, int n, hipStream_t st) 
 
 using namespace hns;
 
-int hns_refuse_capture(void* stream, const char* who) {
-	if (!stream_is_capturing(stream)) return HNS_OK;
-	set_error("%s: a solve control is set (the host reads the residual at every check) and the stream is capturing", who);
-	return HNS_ERR_INVALID_ARGUMENT;
-}
-
 void hns_sim_free_diagnostics(hns_sim* s) {
 	if (s->h_diag) (void)hipHostFree(s->h_diag);
 	hns_arena_put(s->d_diag, s->diag_bytes, s->device);
@@ -252,54 +246,36 @@ void hns_sim_free_diagnostics(hns_sim* s) {
 	s->h_diag = nullptr, s->d_diag = nullptr, s->diag_bytes = 0, s->control = nullptr;
 }
 
-// The pressure loop under a control (include/hns.h: hns_solve_control): the loop of sim_pressure (hns_api.hip) cut into pieces of check_every iterations (V-cycles under
-// hns_sim_set_solve_method), the residual behind each.
-// A piece is the same sequence of launches the uncontrolled loop makes for those iterations, so the pressure after j iterations is the uncontrolled solve's, bit for bit.
-int hns_sim_pressure_controlled(hns_sim* s, int max_iterations, float voxel_size, float omega, void* stream) {
-	const char* who = "hns_sim_pressure_solve (controlled)";
-	hns_sim::Control& ctl = *s->control;
-	hns_grid* g = s->grid;
-	const hipStream_t st = (hipStream_t)stream;
-	DeviceScope on(s->device);
+// The control's part of a solve (include/hns.h: hns_solve_control). The driver, hns_sim_solve (hns_pressure.hip), cuts the loop into pieces of check_every iterations
+// (V-cycles under hns_sim_set_solve_method) with hns_control_check behind each.
+// before the solve's bracket opens: the diagnostics memory, an empty report
+int hns_control_begin(hns_sim* s) {
 	hns_stats *d_rec, *table;
 	HNS_TRY(sim_diag(s, 1, &d_rec, &table));
-	HNS_TRY(s->solve_begin(stream));
-	ctl.ran = false;
-	ctl.history.clear();
-	ctl.report = hns_solve_report{};
-	// `initial`: the residual at p = 0 (the solve never warm-starts)
-	HNS_HIP(hipMemsetAsync(s->p_a, 0, sizeof(float) * 512 * (size_t)g->topo.n_leaves, st));
-	HNS_TRY(launch_residual(g, s->div, s->p_a, voxel_size, nullptr, table, d_rec, st, who));
-	float *cur = s->p_a, *other = s->p_b;
-	// one step of k iterations -- V-cycles under hns_sim_set_solve_method -- further: the launches the uncontrolled solve makes for them
-	auto step = [&](int k, bool first) {
-		if (s->mg) return hns_mg_cycles(s, &cur, &other, voxel_size, k, first, stream);
-		int in_b = 0;
-		HNS_TRY(hns_rbgs_iterate(g, s->div, cur, other, voxel_size, omega, k, &in_b, stream, first));
-		if (in_b) std::swap(cur, other);
-		return (int)HNS_OK;
-	};
-	const bool monitor_only = ctl.c.rel_tol == 0.0f && ctl.c.abs_tol == 0.0f;
-	int done = 0;
-	while (done < max_iterations) {
-		const int k = std::min(ctl.c.check_every, max_iterations - done);
-		HNS_TRY(step(k, done == 0));
-		done += k;
-		HNS_TRY(launch_residual(g, s->div, cur, voxel_size, nullptr, table, d_rec + 1, st, who));
-		HNS_TRY(fetch(s, d_rec, ctl.history.empty() ? 0 : 1, ctl.history.empty() ? 2 : 1, st));  // the one wait of this check
-		const hns_stats& r = s->h_diag[1];
-		ctl.history.push_back(r);
-		const float bound = std::max(ctl.c.abs_tol, ctl.c.rel_tol * s->h_diag[0].max_abs);
-		if (!monitor_only && r.nan_count == 0 && r.max_abs <= bound) {
-			ctl.report.converged = 1;
-			break;
-		}
+	*s->control = hns_sim::Control{s->control->c, hns_solve_report{}, {}, false};
+	return HNS_OK;
+}
+// p null: `initial`, the residual at p = 0 (the solve never warm-starts: p_a is zeroed for it), into record 0. Else, behind a piece that brought the solve to `done`
+// iterations: the residual of p into record 1, the history and the report; *met: the stop rule holds. The one wait of a check is the fetch.
+int hns_control_check(hns_sim* s, const float* p, int done, float voxel_size, void* stream, bool* met) {
+	const char* who = "hns_sim_pressure_solve (controlled)";
+	hns_sim::Control& ctl = *s->control;
+	const hipStream_t st = (hipStream_t)stream;
+	hns_stats *d_rec, *table;
+	HNS_TRY(sim_diag(s, 1, &d_rec, &table));
+	if (!p) {
+		HNS_HIP(hipMemsetAsync(s->p_a, 0, sizeof(float) * 512 * (size_t)s->grid->topo.n_leaves, st));
+		return launch_residual(s->grid, s->div, s->p_a, voxel_size, nullptr, table, d_rec, st, who);
 	}
-	HNS_TRY(s->solve_end(stream, done));
-	s->p_result = cur;
-	s->solved = true;
-	ctl.report.iterations = done, ctl.report.checks = (int)ctl.history.size();
-	ctl.report.initial = s->h_diag[0], ctl.report.final = s->h_diag[1];
+	HNS_TRY(launch_residual(s->grid, s->div, p, voxel_size, nullptr, table, d_rec + 1, st, who));
+	HNS_TRY(fetch(s, d_rec, ctl.history.empty() ? 0 : 1, ctl.history.empty() ? 2 : 1, st));
+	const hns_stats& r = s->h_diag[1];
+	ctl.history.push_back(r);
+	const bool monitor_only = ctl.c.rel_tol == 0.0f && ctl.c.abs_tol == 0.0f;
+	*met = !monitor_only && r.nan_count == 0 && r.max_abs <= std::max(ctl.c.abs_tol, ctl.c.rel_tol * s->h_diag[0].max_abs);
+	ctl.report = hns_solve_report{};
+	ctl.report.converged = *met, ctl.report.iterations = done, ctl.report.checks = (int)ctl.history.size();
+	ctl.report.initial = s->h_diag[0], ctl.report.final = r;
 	ctl.ran = true;
 	return HNS_OK;
 }

@@ -290,7 +290,7 @@ struct hns_sim {
 	// optional hipEvent bracketing of the pressure hot loop (hns_sim_timing), on the stream the kernels run on
 	hns::EventGroups solve_ev{2};  // start/stop pairs
 	long long timed_launches = 0;
-	int solve_begin(void* stream) {  // the bracket round one solve: sim_pressure (hns_api.hip) and the controlled loop (hns_diagnostics.hip)
+	int solve_begin(void* stream) {  // the bracket round one solve (hns_pressure.hip: hns_sim_solve)
 		if (hipEvent_t* timed = solve_ev.current()) HNS_HIP(hipEventRecord(timed[0], (hipStream_t)stream));
 		return HNS_OK;
 	}
@@ -352,7 +352,7 @@ struct hns_sim {
 	size_t diag_bytes = 0;
 	hns_stats* h_diag = nullptr;
 	bool solved = false;
-	// hns_sim_set_solve_control: null = off, and then sim_pressure (hns_api.hip) is the uncontrolled loop after one pointer test
+	// hns_sim_set_solve_control: null = off, and then hns_sim_solve (hns_pressure.hip) is the uncontrolled loop after one pointer test
 	struct Control {
 		hns_solve_control c;
 		hns_solve_report report;
@@ -360,7 +360,7 @@ struct hns_sim {
 		bool ran = false;
 	};
 	Control* control = nullptr;
-	// hns_sim_set_solve_method: null = SOR, and then sim_pressure (hns_api.hip) is the plain loop after one more pointer test; else the V-cycle's parameters and its
+	// hns_sim_set_solve_method: null = SOR, and then hns_sim_solve (hns_pressure.hip) is the plain loop after one more pointer test; else the V-cycle's parameters and its
 	// hierarchy of coarse grids, masks, tables and buffers (hns_multigrid.hip)
 	struct Multigrid;
 	Multigrid* mg = nullptr;
@@ -376,15 +376,17 @@ struct hns_sim {
 // with the message under `who`. field_of (or null) receives each entry's float field index in s, -1 for the velocity.
 namespace hns { int check_activity_fields(const hns_sim* s, const hns_activity_field* fields, int n_fields, const char* who, std::vector<int>* field_of); }
 
-// hns_diagnostics.hip: the controlled pressure loop of a sim with a control set (hns_api.hip: sim_pressure), and the refusal of a capturing stream in front of it
-int hns_sim_pressure_controlled(hns_sim* s, int max_iterations, float voxel_size, float omega, void* stream);
-int hns_refuse_capture(void* stream, const char* who);
+// hns_pressure.hip: the one driver of a sim's pressure solve -- SOR sweeps or V-cycles, whole or in a control's pieces -- and the checks in front of its first launch
+int hns_sim_solve(hns_sim* s, int iterations, float voxel_size, float omega, void* stream);
+int hns_solve_preflight(hns_sim* s, void* stream, const char* who);
+// hns_diagnostics.hip: what a control adds to hns_sim_solve -- before its bracket opens; the residual at p = 0 (p null) and behind each piece
+int hns_control_begin(hns_sim* s);
+int hns_control_check(hns_sim* s, const float* p, int done, float voxel_size, void* stream, bool* met);
 void hns_sim_free_diagnostics(hns_sim* s);  // (hns_sim_destroy)
 
 // hns_multigrid.hip: the V-cycle solve of a sim with a method set (include/hns.h: hns_solve_method)
 int hns_mg_ready(hns_sim* s, void* stream, const char* who);  // the hierarchy of the sim's current grid is there afterwards: built here when a regrid dropped it (refused on a capturing stream), before anything is launched
 int hns_mg_cycles(hns_sim* s, float** cur, float** other, float dx, int cycles, bool first, void* stream);  // `cycles` V-cycles on *cur (first: from p = 0, whatever *cur holds); *cur / *other are swapped as the fine sweeps ping-pong
-int hns_sim_pressure_multigrid(hns_sim* s, int cycles, float voxel_size, void* stream);  // the uncontrolled solve (hns_api.hip: sim_pressure)
 std::string hns_mg_plan(hns_sim* s);  // the pressure stage's word of hns_sim_substep_plan
 void hns_sim_drop_hierarchy(hns_sim* s);   // the sim has moved onto another grid (hns_regrid.hip): the next solve builds the hierarchy again
 void hns_sim_free_multigrid(hns_sim* s);   // (hns_sim_destroy)

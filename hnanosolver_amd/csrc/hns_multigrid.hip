@@ -18,17 +18,6 @@
 namespace hns {
 namespace {
 
-__device__ __forceinline__ void wave_sync() {  // LDS written by this wave is visible to this wave
-	__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-	__builtin_amdgcn_wave_barrier();
-	__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// is voxel v of leaf `leaf` an unknown? masks: 64 bytes per leaf, byte x*8+y, bit z; null = every voxel (level 0)
-__device__ __forceinline__ bool is_unknown(const unsigned char* __restrict__ masks, int leaf, int v) {
-	return !masks || ((masks[(size_t)leaf * 64 + (v >> 3)] >> (v & 7)) & 1);
-}
-
 // One wave per coarse leaf, lane = mask byte x*8+y. child: the <= 8 child leaves of each coarse leaf (octant ox*4+oy*2+oz, -1 = absent); the children of coarse voxel
 // (x, y, z) are the voxels (2(x&3)+dx, 2(y&3)+dy, 2(z&3)+dz) of the child leaf in octant (x>>2, y>>2, z>>2): four bytes of its mask, two bits of each.
 __global__ __launch_bounds__(64) void k_mg_masks(const int* __restrict__ child, const unsigned char* __restrict__ fine_masks, unsigned char* __restrict__ coarse_masks) {
@@ -51,21 +40,11 @@ __global__ __launch_bounds__(64) void k_mg_masks(const int* __restrict__ child, 
 	coarse_masks[(size_t)leaf * 64 + l] = (unsigned char)out;
 }
 
-// One colour of one iteration in place (k_rbgs_color, hns_pressure.hip) on unknowns only: a voxel whose mask bit is clear keeps its 0.
+// One colour of one iteration in place on unknowns only: the masked instance of the sweep k_rbgs_color is the other instance of (hns_device.hpp: color_sweep)
 __global__ __launch_bounds__(256) void k_mg_color(const GridDev g, const unsigned char* __restrict__ masks, const float* __restrict__ rhs, float* p, const float dx2,
                                                   const float omega, const int color) {
 	__shared__ int s_nbr[27];
-	const LeafCtx L = stage_leaf(g, s_nbr, blockIdx.x);
-	const int t = threadIdx.x;
-	const int x = t >> 5, y = (t >> 2) & 7;
-	const int z = 2 * (t & 3) + ((x + y + color) & 1);
-	const int n = (x << 6) | (y << 3) | z;
-	if (!is_unknown(masks, L.leaf, n)) return;
-	const int idx = L.leaf * 512 + n;
-	const float pxp = nbr_val<0, 1>(p, s_nbr, L.leaf, n), pxm = nbr_val<0, -1>(p, s_nbr, L.leaf, n);
-	const float pyp = nbr_val<1, 1>(p, s_nbr, L.leaf, n), pym = nbr_val<1, -1>(p, s_nbr, L.leaf, n);
-	const float pzp = nbr_val<2, 1>(p, s_nbr, L.leaf, n), pzm = nbr_val<2, -1>(p, s_nbr, L.leaf, n);
-	p[idx] = sor_update(pxp, pxm, pyp, pym, pzp, pzm, rhs[idx], p[idx], dx2, omega);
+	color_sweep<true>(g, s_nbr, masks, rhs, p, dx2, omega, color);
 }
 
 // Residual + restriction (include/hns.h: "Restriction"). One workgroup per coarse leaf; wave w has the child leaf of octant w and stages its tile of p as k_residual
@@ -342,18 +321,6 @@ int hns_mg_cycles(hns_sim* s, float** cur, float** other, float dx, int cycles, 
 	Cycle c{s, *s->mg, cur, other, (hipStream_t)stream, stream};
 	for (int i = 0; i < cycles; ++i) HNS_TRY(c.run(0, dx, first && i == 0));
 	return launch_status("hns_sim_pressure_solve (V-cycle)");
-}
-
-int hns_sim_pressure_multigrid(hns_sim* s, int cycles, float voxel_size, void* stream) {
-	DeviceScope on(s->device);
-	HNS_TRY(hns_mg_ready(s, stream, "hns_sim_pressure_solve"));
-	float *cur = s->p_a, *other = s->p_b;
-	HNS_TRY(s->solve_begin(stream));
-	HNS_TRY(hns_mg_cycles(s, &cur, &other, voxel_size, cycles, true, stream));
-	HNS_TRY(s->solve_end(stream, cycles));
-	s->p_result = cur;
-	s->solved = true;
-	return HNS_OK;
 }
 
 // `pressure=` of hns_sim_substep_plan under method 1: vcycle<pre,post,coarse_iterations>/L<levels>: the fine sweeps' kernel + the three coarse-level kernels

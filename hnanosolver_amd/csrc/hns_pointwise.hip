@@ -18,20 +18,9 @@ __global__ __launch_bounds__(256) void k_combustion_oxygen(const float* __restri
                                                            float* __restrict__ waste_out, float* __restrict__ temp_out, float* __restrict__ flame_out,
                                                            const float temp_gain, const float expansion, const uint64_t n, const int update_div) {
 	for (uint64_t v = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; v < n; v += (uint64_t)gridDim.x * blockDim.x) {
-		float f = fuel_in[v];
-		const float w = waste_in[v], tmp = temp_in[v], fl = flame_in[v];
-		if (f < 0.001f) f = 0.0f;       // Kernel.cu:936-938
-		const float oxy = 1.0f - f - w;  // :941
-		if (oxy < 0.0f) {                // :942-949: no oxygen left, the voxel passes through
-			fuel_out[v] = f, waste_out[v] = w, temp_out[v] = tmp, flame_out[v] = fl;
-			continue;
-		}
-		const float burn = fminf(oxy, f);  // :952
-		fuel_out[v] = f - burn;
-		waste_out[v] = w + burn * 2.0f;
-		temp_out[v] = tmp + burn * temp_gain;
-		if (update_div) div[v] += burn * expansion;
-		flame_out[v] = fmaxf(fl, fminf(1.0f, burn * 10.0f));
+		const Burnt b = combust_voxel(fuel_in[v], waste_in[v], temp_in[v], flame_in[v], temp_gain);
+		fuel_out[v] = b.fuel, waste_out[v] = b.waste, temp_out[v] = b.temperature, flame_out[v] = b.flame;
+		if (update_div && b.burns) div[v] = combust_divergence(b, div[v], expansion);
 	}
 }
 
@@ -41,31 +30,16 @@ __global__ __launch_bounds__(256) void k_combustion_oxygen(const float* __restri
 __global__ __launch_bounds__(256) void k_combustion_div(const float* __restrict__ fuelData, const float* __restrict__ wasteData,
                                                         float* __restrict__ divergenceData, const float expansion, const uint64_t n) {
 	for (uint64_t idx = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < n; idx += (uint64_t)gridDim.x * blockDim.x) {
-		float fuel = fuelData[idx];
-		const float waste = wasteData[idx];
-		if (fuel < 0.001f) fuel = 0.0f;
-		const float oxygen = 1.0f - fuel - waste;
-		if (oxygen < 0.0f) continue;
-		const float burn = fminf(oxygen, fuel);
-		divergenceData[idx] += burn * expansion;
+		const Burnt b = combust_voxel(fuelData[idx], wasteData[idx], 0.0f, 0.0f, 0.0f);  // (temperature and flame play no part in burn)
+		if (b.burns) divergenceData[idx] = combust_divergence(b, divergenceData[idx], expansion);
 	}
 }
 
-// temperature_buoyancy (reference Kernel.cu:831-847): vel + (0, max(0,(T-Tamb)*k), 0) * dt. The x and z results are
-// vel + 0*dt; they are passed through the same add so that the stored bits equal the reference's (-0 + 0 = +0).
+// temperature_buoyancy (reference Kernel.cu:831-847; hns_device.hpp: buoyancy_voxel)
 __global__ __launch_bounds__(256) void k_temperature_buoyancy(const float* u, const float* __restrict__ temp, float* out, const float dt,
                                                               const float ambient, const float strength, const uint64_t n) {
-	for (uint64_t idx = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < n; idx += (uint64_t)gridDim.x * blockDim.x) {
-		const f3 v = ld3(u, (int)idx);
-		const float t = temp[idx];
-		if (t <= ambient) {
-			st3(out, (int)idx, v);
-			continue;
-		}
-		const float tempDiff = t - ambient;
-		const f3 r = {v.x + dt * 0.0f, v.y + dt * fmaxf(0.0f, tempDiff * strength), v.z + dt * 0.0f};
-		st3(out, (int)idx, r);
-	}
+	for (uint64_t idx = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < n; idx += (uint64_t)gridDim.x * blockDim.x)
+		st3(out, (int)idx, buoyancy_voxel(ld3(u, (int)idx), temp[idx], dt, ambient, strength));
 }
 
 // whole-leaf gather/scatter for the halo exchange: a leaf payload is 512*ncomp floats (ncomp 1 = float field, 3 = Vec3f
@@ -154,8 +128,6 @@ __global__ __launch_bounds__(512) void k_enforce_collision(const GridDev g, floa
 using namespace hns;
 
 extern "C" {
-
-
 
 int hns_dev_combustion_oxygen(const float* fuel, const float* waste, const float* temperature, float* divergence, const float* flame,
                               float* out_fuel, float* out_waste, float* out_temperature, float* out_flame, float temp_gain, float expansion,

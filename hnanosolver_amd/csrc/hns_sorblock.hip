@@ -64,12 +64,10 @@ struct SbGeo {
 	static_assert(NQ <= HS4 && NT <= 1024 && RIM <= CROWS, "tile too large");
 };
 
-constexpr float kInv6 = 0.166666667f;  // Kernel.cu:609
-
 // the update of one voxel in both blocked sweeps: X = its value, d = div * dx^2, ok = all ones if its leaf exists, else 0
 template <bool MASKED>
 __device__ __forceinline__ float sb_update(float xp, float xm, float yp, float ym, float zp, float zm, float d, float X, float omega, unsigned ok) {
-	const float pGS = ((xp + xm + yp + ym + zp + zm) - d) * kInv6;  // Kernel.cu:621 (d = div * dx^2)
+	const float pGS = gs_value_of(xp, xm, yp, ym, zp, zm, d);  // Kernel.cu:621 (d = div * dx^2)
 	const float cand = X + omega * (pGS - X);                      // Kernel.cu:622
 	// a voxel of an absent leaf stays +0 (as a bit mask, not a select: the compiler turns selects here into a branch per voxel)
 	return MASKED ? __uint_as_float(__float_as_uint(cand) & ok) : cand;

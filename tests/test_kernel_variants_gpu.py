@@ -137,6 +137,84 @@ def test_variant_is_bit_identical(name, default_outputs, options):
         assert np.array_equal(got[k], default_outputs[k]), (name, k)
 
 
+# ---- the pieces of the row divergence kernels on the smallest leaf set on which the z-pair ones can go wrong --------------------------------------------------------
+# In NanoVDB order: leaves 0, 1 are a z-adjacent pair (they hand each other their common z face through LDS); 2, 3 are a pair that is not adjacent (both gather, and
+# both lack most neighbours); 4 is alone: the range is odd and the second wave of the last workgroup shadows the first and must store nothing.
+ZPAIR_LEAVES = np.array([[0, 0, 0], [0, 0, 8], [0, 8, 0], [16, 0, 0], [16, 8, 8]], dtype=np.int32)
+ZPAIR_FORMS = [(div, fuse) for div in ("row", "coalesced", "zpair") for fuse in (None, "0")]
+
+
+def zpair_data():
+    """smooth fields in which some voxels burn, some have no oxygen left (fuel + waste > 1) and some fuel lies below the 0.001 threshold"""
+    from hnanosolver_amd import api, fields
+
+    assert np.array_equal(ZPAIR_LEAVES[fields.nanovdb_order(ZPAIR_LEAVES)], ZPAIR_LEAVES)
+    c = fields.leaves_to_coords(ZPAIR_LEAVES).astype(np.float64)
+    x, y, z = c[:, 0] / 24.0, c[:, 1] / 16.0, c[:, 2] / 16.0
+    f = {"density": 0.5 + 0.4 * np.sin(3.0 * x + y), "temperature": 0.2 + 0.6 * np.cos(2.0 * y - z) ** 2, "fuel": 0.45 * (1.0 + np.sin(5.0 * x + 2.0 * z)) * y,
+         "waste": 0.7 * (1.0 + np.cos(4.0 * y + x)) * z, "flame": 0.3 * np.sin(2.0 * x * y + z) ** 2}
+    vel = 0.5 * np.stack([np.sin(4.0 * y) * np.cos(3.0 * z), np.cos(5.0 * x) + np.sin(2.0 * z), np.sin(3.0 * x + 4.0 * y)], -1)
+    fuel, oxygen = f["fuel"].astype(np.float32), 1.0 - f["fuel"] - f["waste"]
+    assert ((fuel >= 0.001) & (oxygen > 0.05)).sum() > 200 and (oxygen < -0.05).sum() > 100 and ((fuel > 0) & (fuel < 0.001)).sum() > 20
+    d = api.GridIndexedData()
+    d.allocateCoords(len(c))
+    d.pCoords()[:] = fields.leaves_to_coords(ZPAIR_LEAVES)
+    for n in ("density", "temperature", "fuel", "waste", "flame"):
+        d.addValueBlock(n, d.FLOAT)
+        d.pValues(n)[:] = f[n].astype(np.float32)
+    d.addValueBlock("vel", d.VEC3F)
+    d.pValues("vel")[:] = vel.astype(np.float32)
+    return d
+
+
+@pytest.fixture(scope="module")
+def zpair_oracle():
+    from hnanosolver_amd import api
+    from oracle_lib import OracleGrid
+    from operator_cases import snapshot
+
+    want = snapshot(zpair_data())
+    names = [n for n in want if n != "vel"]
+    assert OracleGrid(ZPAIR_LEAVES).compute_sim(want["vel"], {n: want[n] for n in names}, 3, 1.0 / 24.0, 1.0 / 16.0, api.CombustionParams(factorScale=1.0), False) == 0
+    return want
+
+
+@pytest.fixture(scope="module")
+def zpair_unfused_row(zpair_oracle):
+    return run_zpair_case("row", "0")
+
+
+def run_zpair_case(div, fuse):
+    from hnanosolver_amd import api
+    from operator_cases import snapshot
+
+    try:
+        H.set_option("divergence", div)
+        H.set_option("fuse", fuse)
+        d = zpair_data()
+        h = api.IndexGridHandle()
+        api.CreateIndexGrid(d, h, 1.0 / 16.0)
+        api.Compute_Sim(d, h, 3, 1.0 / 24.0, 1.0 / 16.0, api.CombustionParams(factorScale=1.0), False)
+        h.reset()
+        return snapshot(d)
+    finally:
+        H.set_option("divergence", None)
+        H.set_option("fuse", None)
+
+
+def test_unfused_row_form_on_the_zpair_leaves_is_the_oracle(zpair_unfused_row, zpair_oracle):
+    for n, want in zpair_oracle.items():
+        assert np.array_equal(zpair_unfused_row[n], want), n
+
+
+@pytest.mark.parametrize("div,fuse", ZPAIR_FORMS)
+def test_row_kernel_pieces_on_the_zpair_leaves(div, fuse, zpair_unfused_row):
+    got = run_zpair_case(div, fuse)
+    assert got.keys() == zpair_unfused_row.keys()
+    for n, want in zpair_unfused_row.items():
+        assert np.array_equal(got[n].view(np.uint32), want.view(np.uint32)), (div, fuse, n)
+
+
 def test_unknown_option_is_refused():
     with pytest.raises(H.HNSError):
         H.set_option("rbgs", "no-such-form")
