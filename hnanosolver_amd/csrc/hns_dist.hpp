@@ -31,7 +31,7 @@
 // Round 6: three translation units around this header --
 //   hns_dist_plan.hip       which leaves a rank owns, its halo regions and tables; create / destroy, plan queries, upload / download
 //   hns_dist_transport.hip  RCCL (bound at run time), the loopback stand-ins, hipIpc-mapped peers, locally connected ranks; the flags and tables of the chained substep
-//   hns_dist_substep.hip    the exchange (post / complete), its kernels, and the core / full substep as a sequence of phases
+//   hns_dist_substep.hip    the exchange (post / one transfer per transport / complete), its kernels, and the core / full substep as a sequence of phases
 #pragma once
 #include <dlfcn.h>
 #include <unistd.h>
@@ -83,7 +83,7 @@ float omega_compute(float vs);
 
 namespace hnsd {
 
-constexpr int kMaxBatchPeers = 16;  // peers whose regions one pack / unpack launch serves (k_halo_copy_all)
+constexpr int kMaxBatchPeers = 16;  // peers whose regions one pack / unpack launch serves (k_halo_copy's PeerMsgs)
 constexpr int kIpcMaxSegs = 32, kIpcMaxPeers = hns::kMirrorMaxPeers;  // one-sided transport: segments per put launch, peers a rank can map
 
 enum { X_ADV = 0, X_D1 = 1, X_DIV = 2, X_P = 3, X_COUNT = 4 };  // halo region types (see the file header)
@@ -138,12 +138,21 @@ struct Peer {
 	size_t sbuf_floats = 0, rbuf_floats = 0;
 };
 
+// One field of an exchange. A peer's message is the exchange's fields in order: this one starts `before` * (the region's voxels) floats in.
+struct MsgField {
+	float* field;
+	int ncomp;
+	int before = 0;  // components of the fields ahead of it in the message: filled in where the exchange is posted, read everywhere else
+	MsgField(float* f, int n) : field(f), ncomp(n) {}
+};
+
 struct Pending {  // an exchange that has been posted and not yet consumed
 	bool active = false;
 	bool prepacked = false;  // the boundary kernel wrote the messages itself (PackMirror): no pack launch
 	int type = 0, parity = 0;
 	hipStream_t stream = nullptr;  // where its boundary kernel, packing, transfer and unpacking run
-	std::vector<std::pair<float*, int>> fields;  // (device field, ncomp) in message order
+	std::vector<MsgField> fields;  // in message order
+	int comps = 0;                 // components per voxel of a whole message
 };
 
 }  // namespace hnsd
@@ -240,6 +249,17 @@ inline int far_check(const hns_dist* d) {
 
 inline size_t pad256(size_t b) { return (b + 255) & ~(size_t)255; }
 
+// How a rank's messages travel, derived here and nowhere else. A rank with several connections uses the first of: mapped peer memory, an RCCL communicator (the loopback
+// variant's is a one-rank communicator to itself: hns_dist::loopback says so), the copy-based loopback, the locally connected ranks.
+enum class Transport { None, Local, Loopback, Rccl, Ipc };
+inline Transport transport(const hns_dist* d) {
+	if (d->ipc) return Transport::Ipc;
+	if (d->comm) return Transport::Rccl;
+	if (d->loopback) return Transport::Loopback;
+	return d->local_ranks.empty() ? Transport::None : Transport::Local;
+}
+// Does the boundary side of an exchange run on the communication stream, under the interior kernel? (Locally connected ranks keep everything on the caller's stream.)
+inline bool two_stream_transport(const hns_dist* d) { return !d->single_stream && transport(d) > Transport::Local; }
 
 // Round 4: sweeps_per_exchange = 2 mirrors as well -- its sweeps are the temporally blocked form, two iterations per chained launch
 // (hns_sorblock.hip: k_rbgs_block<2, 2, ., true, PhaseMirror>), whose mirror region is the plan's reach-4 region of p. All ranks must

@@ -499,9 +499,6 @@ hns_dist* hns_dist_create(const int32_t* global_leaf_origins_xyz, uint64_t n_lea
 	return d;
 }
 
-// The communication stream exists only where a second stream is used: RCCL and loopback transports. It outranks the compute
-// stream: its short kernels (boundary leaves, pack, unpack) must not queue behind the thousands of waves of the interior
-
 // ---- plan queries (also on HNS_DIST_PLAN_ONLY handles) ----
 int hns_dist_local_leaves(const hns_dist* d, int64_t* out_global_ids) {
 	if (!d || !out_global_ids) return fail(HNS_ERR_INVALID_ARGUMENT, "hns_dist_local_leaves: null argument");

@@ -1,4 +1,6 @@
-// hns_dist_substep.hip -- multi-GPU: the exchange (post / complete) and its kernels, and the core / full substep of a rank as a sequence of phases (see hns_dist.hpp)
+// hns_dist_substep.hip -- multi-GPU: the exchange (post / complete) and its kernels, and the core / full substep of a rank as a sequence of phases (see hns_dist.hpp).
+// Three things are stated once here: how an exchange's fields lie in a message (lay_out; one pack / unpack kernel, k_halo_copy, launched by launch_halo_copy), how the
+// messages travel (one transfer_* per hnsd::Transport, picked by transfer()), and which form a stencil phase takes (Step::stencil).
 #include "hns_dist.hpp"
 
 namespace hns {
@@ -24,43 +26,19 @@ __global__ void k_wire_delay(long long ticks) {
 	while (wall_clock64() - t0 < ticks) __builtin_amdgcn_s_sleep(32);
 }
 
-template <int NCOMP, bool PACK>
-__global__ __launch_bounds__(64) void k_halo_copy(float* __restrict__ field, const int* __restrict__ leaf, const unsigned char* __restrict__ mask,
-                                                  const int* __restrict__ off, float* __restrict__ msg) {
-	const int i = blockIdx.x, l = threadIdx.x;
-	const unsigned m = mask[(size_t)i * 64 + l];
-	const int base = off[i] + wave_exclusive_scan(__popc(m));
-	float* f = field + ((size_t)leaf[i] * 512 + l * 8) * NCOMP;
-	float* q = msg + (size_t)base * NCOMP;
-	int c = 0;
-#pragma unroll
-	for (int z = 0; z < 8; ++z) {
-		if (m >> z & 1) {
-#pragma unroll
-			for (int k = 0; k < NCOMP; ++k) {
-				if (PACK)
-					q[c * NCOMP + k] = f[z * NCOMP + k];
-				else
-					f[z * NCOMP + k] = q[c * NCOMP + k];
-			}
-			++c;
-		}
-	}
-}
-
-// The same for ALL peers of a rank in one launch (a rank of a 3-d decomposition talks to several: 7 in the 8-range plume):
-// entry i carries its peer, whose message base and region size come by value.
+// One launch serves ALL peers of a rank (a rank of a 3-d decomposition talks to several: 7 in the 8-range plume): entry i carries its peer, whose message
+// base and region size come by value. A null `peer` table: every entry is peer 0 (the tables of one peer's region).
 struct PeerMsgs {
 	float* base[kMaxBatchPeers];
 	int voxels[kMaxBatchPeers];
 };
 
 template <int NCOMP, bool PACK>
-__global__ __launch_bounds__(64) void k_halo_copy_all(float* __restrict__ field, const int* __restrict__ leaf, const unsigned char* __restrict__ mask,
-                                                      const int* __restrict__ off, const int* __restrict__ peer, const PeerMsgs msgs, const int comps_before) {
+__global__ __launch_bounds__(64) void k_halo_copy(float* __restrict__ field, const int* __restrict__ leaf, const unsigned char* __restrict__ mask,
+                                                  const int* __restrict__ off, const int* __restrict__ peer, const PeerMsgs msgs, const int comps_before) {
 	const int i = blockIdx.x, l = threadIdx.x;
 	const unsigned m = mask[(size_t)i * 64 + l];
-	const int p = peer[i];
+	const int p = peer ? peer[i] : 0;
 	const int base = off[i] + wave_exclusive_scan(__popc(m));
 	float* f = field + ((size_t)leaf[i] * 512 + l * 8) * NCOMP;
 	float* q = msgs.base[p] + (size_t)comps_before * (size_t)msgs.voxels[p] + (size_t)base * NCOMP;
@@ -200,32 +178,61 @@ using namespace hnsd;
 
 namespace {
 
+typedef std::vector<MsgField> Fields;
+
+// statistics: `comps` floats per voxel of every peer's send region of type `t` leave this rank; returns how many peers get any
+int count_sent(hns_dist* d, int t, int comps) {
+	int messages = 0;
+	for (const Peer& p : d->peers) {
+		const size_t fl = (size_t)comps * (size_t)p.send[t].voxels;
+		d->bytes_sent[t] += sizeof(float) * fl, messages += fl != 0;
+	}
+	return messages;
+}
+
 // the arguments of one chained launch: region type `t`, output arrays `outs` (device fields of this rank, components per voxel)
-PhaseMirror phase_args(hns_dist* d, int t, const std::vector<std::pair<const float*, int>>& outs) {
+PhaseMirror phase_args(hns_dist* d, int t, const Fields& outs) {
 	PhaseMirror m = d->mir;
 	m.first = d->mir_type[t].first, m.entry = d->mir_type[t].entry, m.mask = d->mir_type[t].mask;
 	int k = 0, comps = 0;
-	for (auto& f : outs) m.out_unit[k++] = (int)((size_t)((const char*)f.first - (const char*)d->arena) / d->unit_bytes), comps += f.second;
+	for (const MsgField& f : outs) m.out_unit[k++] = (int)((size_t)((const char*)f.field - (const char*)d->arena) / d->unit_bytes), comps += f.ncomp;
 	m.seq = ++d->sweep_seq;
-	for (Peer& p : d->peers) d->bytes_sent[t] += sizeof(float) * (size_t)p.send[t].voxels * (size_t)comps;
+	count_sent(d, t, comps);
 	return m;
 }
 
+// THE layout of a message, stated here once: the exchange's fields in order, field f starting f.before * region.voxels floats into every peer's message.
+// Whoever reads or writes a message -- pack / unpack, the transfers, message_floats -- goes by f.before (and segment()).
+void lay_out(Pending& x) {
+	int before = 0;
+	for (MsgField& f : x.fields) f.before = before, before += f.ncomp;
+	x.comps = before;
+}
+
+// The one place the pack / unpack kernel is launched: `n` table entries of `field`, whose messages are `msgs` (`peer`: see k_halo_copy).
+void launch_halo_copy(bool pack, float* field, int ncomp, size_t n, const int* leaf, const unsigned char* mask, const int* off, const int* peer, const PeerMsgs& msgs,
+                      int comps_before, hipStream_t st) {
+	const dim3 grid((unsigned)n), block(64);
+	if (ncomp == 3) {
+		if (pack)
+			hipLaunchKernelGGL((k_halo_copy<3, true>), grid, block, 0, st, field, leaf, mask, off, peer, msgs, comps_before);
+		else
+			hipLaunchKernelGGL((k_halo_copy<3, false>), grid, block, 0, st, field, leaf, mask, off, peer, msgs, comps_before);
+	} else {
+		if (pack)
+			hipLaunchKernelGGL((k_halo_copy<1, true>), grid, block, 0, st, field, leaf, mask, off, peer, msgs, comps_before);
+		else
+			hipLaunchKernelGGL((k_halo_copy<1, false>), grid, block, 0, st, field, leaf, mask, off, peer, msgs, comps_before);
+	}
+}
+
+// one field of one peer's region; `msg`: where that field starts in the peer's message
 int halo_copy(bool pack, float* field, int ncomp, const Region& r, float* msg, hipStream_t st) {
 	if (r.leaf.empty()) return HNS_OK;
 	if (r.whole) return pack ? hns_dev_pack_leaves(field, r.d_leaf, r.leaf.size(), msg, ncomp, st) : hns_dev_unpack_leaves(msg, r.d_leaf, r.leaf.size(), field, ncomp, st);
-	const dim3 grid((unsigned)r.leaf.size()), block(64);
-	if (ncomp == 3) {
-		if (pack)
-			hipLaunchKernelGGL((k_halo_copy<3, true>), grid, block, 0, st, field, r.d_leaf, r.d_mask, r.d_off, msg);
-		else
-			hipLaunchKernelGGL((k_halo_copy<3, false>), grid, block, 0, st, field, r.d_leaf, r.d_mask, r.d_off, msg);
-	} else {
-		if (pack)
-			hipLaunchKernelGGL((k_halo_copy<1, true>), grid, block, 0, st, field, r.d_leaf, r.d_mask, r.d_off, msg);
-		else
-			hipLaunchKernelGGL((k_halo_copy<1, false>), grid, block, 0, st, field, r.d_leaf, r.d_mask, r.d_off, msg);
-	}
+	PeerMsgs one{};
+	one.base[0] = msg, one.voxels[0] = r.voxels;
+	launch_halo_copy(pack, field, ncomp, r.leaf.size(), r.d_leaf, r.d_mask, r.d_off, nullptr, one, 0, st);
 	return launch_status("hns_dist: halo pack/unpack");
 }
 
@@ -239,73 +246,132 @@ int halo_copy_exchange(hns_dist* d, bool pack, const Pending& x, hipStream_t st)
 			msgs.base[pi] = pack ? d->peers[pi].sbuf[x.parity] : d->peers[pi].rbuf[x.parity];
 			msgs.voxels[pi] = (pack ? d->peers[pi].send[x.type] : d->peers[pi].recv[x.type]).voxels;
 		}
-		int before = 0;
-		const dim3 grid((unsigned)a.n), block(64);
-		for (auto& f : x.fields) {
-			if (f.second == 3) {
-				if (pack)
-					hipLaunchKernelGGL((k_halo_copy_all<3, true>), grid, block, 0, st, f.first, a.d_leaf, a.d_mask, a.d_off, a.d_peer, msgs, before);
-				else
-					hipLaunchKernelGGL((k_halo_copy_all<3, false>), grid, block, 0, st, f.first, a.d_leaf, a.d_mask, a.d_off, a.d_peer, msgs, before);
-			} else {
-				if (pack)
-					hipLaunchKernelGGL((k_halo_copy_all<1, true>), grid, block, 0, st, f.first, a.d_leaf, a.d_mask, a.d_off, a.d_peer, msgs, before);
-				else
-					hipLaunchKernelGGL((k_halo_copy_all<1, false>), grid, block, 0, st, f.first, a.d_leaf, a.d_mask, a.d_off, a.d_peer, msgs, before);
-			}
-			before += f.second;
-		}
+		for (const MsgField& f : x.fields) launch_halo_copy(pack, f.field, f.ncomp, (size_t)a.n, a.d_leaf, a.d_mask, a.d_off, a.d_peer, msgs, f.before, st);
 		return launch_status("hns_dist: halo pack/unpack");
 	}
 	for (Peer& p : d->peers) {
 		float* msg = pack ? p.sbuf[x.parity] : p.rbuf[x.parity];
 		const Region& r = pack ? p.send[x.type] : p.recv[x.type];
 		if (r.direct >= 0) continue;
-		for (auto& f : x.fields) {
-			HNS_TRY(halo_copy(pack, f.first, f.second, r, msg, st));
-			msg += (size_t)f.second * (size_t)r.voxels;
+		for (const MsgField& f : x.fields) HNS_TRY(halo_copy(pack, f.field, f.ncomp, r, msg + (size_t)f.before * (size_t)r.voxels, st));
+	}
+	return HNS_OK;
+}
+
+// where field `f` of a message lives: in the field itself when the region is a run of whole consecutive leaves, in the message buffer `buf` otherwise
+// (`field`: the array of that field on the rank whose region `r` is -- f.field on this rank)
+float* segment(const Region& r, const MsgField& f, float* field, float* buf) {
+	return r.direct >= 0 ? field + (size_t)r.direct * 512 * (size_t)f.ncomp : buf + (size_t)f.before * (size_t)r.voxels;
+}
+
+size_t message_floats(const Pending& x, const Region& r) { return (size_t)x.comps * (size_t)r.voxels; }
+
+// All messages of exchange `x` as k_ipc_put launches of up to kIpcMaxSegs segments on its stream, one segment per peer and field: `voxels(i)` voxels of peer i's send
+// region travel, and field `f` of that message lands at `dst(i, f)`.
+template <bool FENCE, class VoxelsFn, class DstFn>
+void put_messages(hns_dist* d, const Pending& x, VoxelsFn voxels, DstFn dst) {
+	IpcSegs sg;
+	sg.n = 0, sg.wg0[0] = 0;
+	auto flush = [&]() {
+		if (sg.n) hipLaunchKernelGGL(k_ipc_put<FENCE>, dim3(sg.wg0[sg.n]), dim3(256), 0, x.stream, sg);
+		sg.n = 0;
+	};
+	for (size_t i = 0; i < d->peers.size(); ++i) {
+		const Peer& p = d->peers[i];
+		for (const MsgField& f : x.fields) {
+			const size_t fl = voxels(i) * (size_t)f.ncomp;
+			if (!fl) continue;
+			if (sg.n == kIpcMaxSegs) flush();
+			sg.dst[sg.n] = dst(i, f), sg.src[sg.n] = segment(p.send[x.type], f, f.field, p.sbuf[x.parity]), sg.floats[sg.n] = (unsigned)fl;
+			sg.wg0[sg.n + 1] = sg.wg0[sg.n] + (unsigned)((fl + 4095) / 4096);
+			++sg.n;
+		}
+	}
+	flush();
+}
+
+// ---- the transfer of a posted (packed) exchange, one function per transport, all on the exchange's stream ----
+
+// ipc: "ready to receive" both ways, the puts into the peers' memory, "landed" both ways
+int transfer_ipc(hns_dist* d, const Pending& x) {
+	const uint32_t seq = ++d->ipc_seq;
+	IpcPeers ip;
+	ip.n = (int)d->peers.size();
+	for (int i = 0; i < ip.n; ++i) {
+		ip.theirs_ready[i] = d->ipc_peers[(size_t)i].flags + d->rank;
+		ip.theirs_landed[i] = d->ipc_peers[(size_t)i].flags + kFlagLanded + d->rank;
+		ip.rank[i] = d->peers[(size_t)i].rank;
+	}
+	hipLaunchKernelGGL(k_ipc_ready, dim3(1), dim3(64), 0, x.stream, ip, (const uint32_t*)d->ipc_flags, seq, d->ipc_status);
+	put_messages<true>(d, x, [&](size_t i) { return (size_t)d->peers[i].send[x.type].voxels; }, [&](size_t i, const MsgField& f) {
+		// the same field in the peer's memory: fields sit at the same multiples of the (peer's) unit
+		const hns_dist::IpcPeer& q = d->ipc_peers[i];
+		const size_t unit_index = (size_t)((char*)f.field - (char*)d->arena) / d->unit_bytes;
+		return (float*)(q.recv_direct[x.type] >= 0 ? q.arena + unit_index * q.unit_bytes + sizeof(float) * 512 * (size_t)q.recv_direct[x.type] * (size_t)f.ncomp
+		                                           : q.tables + q.rbuf_off[x.parity] + sizeof(float) * (size_t)f.before * (size_t)q.recv_voxels[x.type]);
+	});
+	hipLaunchKernelGGL(k_ipc_landed, dim3(1), dim3(64), 0, x.stream, ip, (const uint32_t*)d->ipc_flags, seq, d->ipc_status);
+	return launch_status("hns_dist: one-sided exchange");
+}
+
+// RCCL: sends and receives of all peers are one group
+int transfer_rccl(hns_dist* d, const Pending& x) {
+	HNS_NCCL(rccl().GroupStart());
+	for (Peer& p : d->peers) {
+		const Region &rs = p.send[x.type], &rr = p.recv[x.type];
+		// (loopback over RCCL: the peer is this rank, the answer to a message is the message, cut to the smaller region)
+		const int to = d->loopback ? 0 : p.rank;
+		const size_t vs = d->loopback ? (size_t)std::min(rs.voxels, rr.voxels) : (size_t)rs.voxels, vr = d->loopback ? vs : (size_t)rr.voxels;
+		for (const MsgField& f : x.fields) {  // one send and one receive per field: either end may use the field itself or its buffer
+			if (vs) HNS_NCCL(rccl().Send(segment(rs, f, f.field, p.sbuf[x.parity]), vs * f.ncomp, ncclFloat, to, d->comm, x.stream));
+			if (vr) HNS_NCCL(rccl().Recv(segment(rr, f, f.field, p.rbuf[x.parity]), vr * f.ncomp, ncclFloat, to, d->comm, x.stream));
+		}
+	}
+	HNS_NCCL(rccl().GroupEnd());
+	return HNS_OK;
+}
+
+// loopback: same streams, events and copy sizes as a real exchange, but the payload is this rank's own
+int transfer_loopback(hns_dist* d, const Pending& x) {
+	if (const int us = options().dist_wire_us.load()) hipLaunchKernelGGL(k_wire_delay, dim3(1), dim3(1), 0, x.stream, (long long)us * 100);
+	// all messages of the exchange as ONE copy launch (round 6; a hipMemcpyAsync per peer and field cost the host 5-8 us each, two to fourteen of them per exchange):
+	// what stands in for the one send / receive group of the RCCL path
+	put_messages<false>(d, x, [&](size_t i) { return (size_t)std::min(d->peers[i].send[x.type].voxels, d->peers[i].recv[x.type].voxels); },
+	                    [&](size_t i, const MsgField& f) { return segment(d->peers[i].recv[x.type], f, f.field, d->peers[i].rbuf[x.parity]); });
+	return launch_status("hns_dist: loopback exchange");
+}
+
+// local: nothing travels at post(); at complete() this rank pulls every peer's message out of its send buffer, once the peer has packed it
+int transfer_local(hns_dist* d, const Pending& x) {
+	for (Peer& p : d->peers) {
+		// the peer packed this message into its buffer of the same parity when it posted the same exchange; it may already
+		// have posted the NEXT one (other parity) -- never the one after, which its own complete() of this one precedes
+		hns_dist* q = d->local_ranks[(size_t)p.rank];
+		const Peer* back = nullptr;
+		for (const Peer& c : q->peers)
+			if (c.rank == d->rank) back = &c;
+		const size_t nr = message_floats(x, p.recv[x.type]);
+		if (!nr) continue;
+		if (!back || message_floats(x, back->send[x.type]) != nr) return fail(HNS_ERR_RUNTIME, "hns_dist: send/receive plans of two ranks disagree");
+		const Pending& y = q->pending;  // the peer's record of the same exchange (its fields are ITS device arrays)
+		if (y.type != x.type || y.parity != x.parity || y.fields.size() != x.fields.size()) return fail(HNS_ERR_RUNTIME, "hns_dist: locally connected ranks are out of step");
+		if (!d->single_stream) HNS_HIP(hipStreamWaitEvent(x.stream, q->ev_post[x.parity], 0));
+		for (size_t fi = 0; fi < x.fields.size(); ++fi) {
+			const MsgField& f = x.fields[fi];
+			HNS_HIP(hipMemcpyAsync(segment(p.recv[x.type], f, f.field, p.rbuf[x.parity]), segment(back->send[x.type], f, y.fields[fi].field, back->sbuf[x.parity]),
+			                       sizeof(float) * (size_t)p.recv[x.type].voxels * f.ncomp, hipMemcpyDeviceToDevice, x.stream));
 		}
 	}
 	return HNS_OK;
 }
 
-// where field `f` (ncomp components, `before` components of earlier fields ahead of it) of a message lives: in the field itself
-// when the region is a run of whole consecutive leaves, in the message buffer otherwise
-float* segment(const Region& r, float* field, int ncomp, float* buf, int before) {
-	return r.direct >= 0 ? field + (size_t)r.direct * 512 * (size_t)ncomp : buf + (size_t)before * (size_t)r.voxels;
-}
-
-size_t message_floats(const Pending& x, const Region& r) {
-	size_t c = 0;
-	for (auto& f : x.fields) c += (size_t)f.second;
-	return c * (size_t)r.voxels;
-}
-
-// All messages of exchange `x` as k_ipc_put launches of up to kIpcMaxSegs segments, one segment per peer and field: `voxels(i)` voxels of peer i's send region travel,
-// and field `f` of that message lands at `dst(i, f, before)` (`before`: the components of the fields ahead of it in the message).
-template <bool FENCE, class VoxelsFn, class DstFn>
-void put_messages(hns_dist* d, const Pending& x, hipStream_t cs, VoxelsFn voxels, DstFn dst) {
-	IpcSegs sg;
-	sg.n = 0, sg.wg0[0] = 0;
-	auto flush = [&]() {
-		if (sg.n) hipLaunchKernelGGL(k_ipc_put<FENCE>, dim3(sg.wg0[sg.n]), dim3(256), 0, cs, sg);
-		sg.n = 0;
-	};
-	for (size_t i = 0; i < d->peers.size(); ++i) {
-		const Peer& p = d->peers[i];
-		int before = 0;
-		for (auto& f : x.fields) {
-			const size_t fl = voxels(i) * (size_t)f.second;
-			if (fl) {
-				if (sg.n == kIpcMaxSegs) flush();
-				sg.dst[sg.n] = dst(i, f, before), sg.src[sg.n] = segment(p.send[x.type], f.first, f.second, p.sbuf[x.parity], before), sg.floats[sg.n] = (unsigned)fl;
-				sg.wg0[sg.n + 1] = sg.wg0[sg.n] + (unsigned)((fl + 4095) / 4096);
-				++sg.n;
-			}
-			before += f.second;
-		}
+int transfer(hns_dist* d, const Pending& x, Transport via) {
+	switch (via) {
+		case Transport::Ipc: return transfer_ipc(d, x);
+		case Transport::Rccl: return transfer_rccl(d, x);
+		case Transport::Loopback: return transfer_loopback(d, x);
+		default: return HNS_OK;  // (local: transfer_local, from complete())
 	}
-	flush();
 }
 
 // received regions -> ghost voxels, on the communication stream; ev_done marks the end of the exchange
@@ -316,29 +382,31 @@ int unpack(hns_dist* d, Pending& x) {
 }
 
 const auto nothing = [](hipStream_t) { return (int)HNS_OK; };  // a boundary or interior launch that has nothing to launch
+const auto no_chain = [](const PhaseMirror&) { return fail(HNS_ERR_RUNTIME, "hns_dist: this phase has no chained form"); };  // (a phase of the full substep only)
 
 // One exchange. post(): the compute stream `st` marks "everything the boundary kernel reads is ready", and the rank's
 // communication stream takes over the whole boundary side of the step: `boundary(cs)` runs the kernel on the boundary leaves,
 // the regions the peers read are packed, the messages travel, the received regions are unpacked into the ghost voxels. The
 // caller then launches the interior kernel on `st`, which runs concurrently with all of that (an interior leaf touches no
 // ghost and no ghost-facing leaf writes what it reads). complete(): `st` waits for the end of that chain.
-// RCCL: sends and receives are one group on the communication stream. Local: the peers pull at complete().
+// The messages travel by transfer(): one function per transport (local: the peers pull at complete()).
 // Round 6: `interior(st)` -- the same kernel over the interior leaves -- is handed in and enqueued HERE, right behind the boundary kernel and in front of the pack / transfer /
 // unpack calls. Enqueued after them (rounds 2-5) it reached the device only once the host had issued the whole boundary chain, and by then that chain had run: the two
 // streams never overlapped (profiles/r06_dist_exchanged_timeline_before.txt; the loop is bound by the HOST's ~10 runtime calls per exchange).
 // in_line: the whole exchange -- `boundary(st)`, pack, transfer, unpack -- on the compute stream itself, in order, no events, complete on return (round 6: the pressure loop
 // whose one launch over all owned leaves packs its own messages; also what locally connected ranks do).
 template <class BoundaryFn, class InteriorFn>
-int post(hns_dist* d, int type, std::vector<std::pair<float*, int>> fields, hipStream_t st, BoundaryFn boundary, InteriorFn interior, bool in_line = false) {
+int post(hns_dist* d, int type, Fields fields, hipStream_t st, BoundaryFn boundary, InteriorFn interior, bool in_line = false) {
 	if (d->pending.active) return fail(HNS_ERR_RUNTIME, "hns_dist: an exchange is already in flight");
 	if (d->world == 1) {  // nobody to talk to: the boundary range is empty, keep everything on one stream
 		HNS_TRY(boundary(st));
 		return interior(st);
 	}
-	if (!d->comm && !d->loopback && !d->ipc && d->local_ranks.empty())
-		return fail(HNS_ERR_RUNTIME, "hns_dist: not connected (call hns_dist_connect_rccl, hns_dist_connect_ipc or hns_dist_connect_local first)");
+	const Transport via = transport(d);
+	if (via == Transport::None) return fail(HNS_ERR_RUNTIME, "hns_dist: not connected (call hns_dist_connect_rccl, hns_dist_connect_ipc or hns_dist_connect_local first)");
 	Pending& x = d->pending;
 	x.active = true, x.type = type, x.parity = d->parity, x.fields = std::move(fields);
+	lay_out(x);
 	d->parity ^= 1;
 	const bool one_stream = d->single_stream || in_line;
 	const hipStream_t cs = one_stream ? st : d->cs;
@@ -353,56 +421,13 @@ int post(hns_dist* d, int type, std::vector<std::pair<float*, int>> fields, hipS
 	HNS_TRY(interior(st));
 	if (!x.prepacked) HNS_TRY(halo_copy_exchange(d, true, x, cs));
 	else ++d->packed_exchanges;
-	for (Peer& p : d->peers) {
-		const size_t fl = message_floats(x, p.send[type]);
-		if (fl) d->bytes_sent[type] += sizeof(float) * fl, ++d->messages_sent;
-	}
+	d->messages_sent += (uint64_t)count_sent(d, type, x.comps);
 	++d->exchanges;
-	if (d->ipc) {
-		const uint32_t seq = ++d->ipc_seq;
-		IpcPeers ip;
-		ip.n = (int)d->peers.size();
-		for (int i = 0; i < ip.n; ++i) {
-			ip.theirs_ready[i] = d->ipc_peers[(size_t)i].flags + d->rank;
-			ip.theirs_landed[i] = d->ipc_peers[(size_t)i].flags + kFlagLanded + d->rank;
-			ip.rank[i] = d->peers[(size_t)i].rank;
-		}
-		hipLaunchKernelGGL(k_ipc_ready, dim3(1), dim3(64), 0, cs, ip, (const uint32_t*)d->ipc_flags, seq, d->ipc_status);
-		put_messages<true>(d, x, cs, [&](size_t i) { return (size_t)d->peers[i].send[type].voxels; }, [&](size_t i, const std::pair<float*, int>& f, int before) {
-			// the same field in the peer's memory: fields sit at the same multiples of the (peer's) unit
-			const hns_dist::IpcPeer& q = d->ipc_peers[i];
-			const size_t unit_index = (size_t)((char*)f.first - (char*)d->arena) / d->unit_bytes;
-			return (float*)(q.recv_direct[type] >= 0 ? q.arena + unit_index * q.unit_bytes + sizeof(float) * 512 * (size_t)q.recv_direct[type] * (size_t)f.second
-			                                         : q.tables + q.rbuf_off[x.parity] + sizeof(float) * (size_t)before * (size_t)q.recv_voxels[type]);
-		});
-		hipLaunchKernelGGL(k_ipc_landed, dim3(1), dim3(64), 0, cs, ip, (const uint32_t*)d->ipc_flags, seq, d->ipc_status);
-		HNS_TRY(launch_status("hns_dist: one-sided exchange"));
-	} else if (d->comm) {
-		HNS_NCCL(rccl().GroupStart());
-		for (Peer& p : d->peers) {
-			const Region &rs = p.send[type], &rr = p.recv[type];
-			// (loopback over RCCL: the peer is this rank, the answer to a message is the message, cut to the smaller region)
-			const int to = d->loopback ? 0 : p.rank;
-			const size_t vs = d->loopback ? (size_t)std::min(rs.voxels, rr.voxels) : (size_t)rs.voxels, vr = d->loopback ? vs : (size_t)rr.voxels;
-			int before = 0;
-			for (auto& f : x.fields) {  // one send and one receive per field: either end may use the field itself or its buffer
-				if (vs) HNS_NCCL(rccl().Send(segment(rs, f.first, f.second, p.sbuf[x.parity], before), vs * f.second, ncclFloat, to, d->comm, cs));
-				if (vr) HNS_NCCL(rccl().Recv(segment(rr, f.first, f.second, p.rbuf[x.parity], before), vr * f.second, ncclFloat, to, d->comm, cs));
-				before += f.second;
-			}
-		}
-		HNS_NCCL(rccl().GroupEnd());
-	} else if (d->loopback) {  // same streams, events and copy sizes as a real exchange, but the payload is this rank's own
-		if (const int us = options().dist_wire_us.load()) hipLaunchKernelGGL(k_wire_delay, dim3(1), dim3(1), 0, cs, (long long)us * 100);
-		// all messages of the exchange as ONE copy launch (round 6; a hipMemcpyAsync per peer and field cost the host 5-8 us each, two to fourteen of them per exchange):
-		// what stands in for the one send / receive group of the RCCL path
-		put_messages<false>(d, x, cs, [&](size_t i) { return (size_t)std::min(d->peers[i].send[type].voxels, d->peers[i].recv[type].voxels); },
-		                    [&](size_t i, const std::pair<float*, int>& f, int before) { return segment(d->peers[i].recv[type], f.first, f.second, d->peers[i].rbuf[x.parity], before); });
-		HNS_TRY(launch_status("hns_dist: loopback exchange"));
-	} else {
+	if (via == Transport::Local) {
 		if (!d->single_stream) HNS_HIP(hipEventRecord(d->ev_post[x.parity], cs));  // packed: the peers may pull
 		return HNS_OK;
 	}
+	HNS_TRY(transfer(d, x, via));
 	if (in_line && !d->single_stream) {  // received regions -> ghost voxels behind the transfer on the same stream: nothing left to wait for
 		HNS_TRY(halo_copy_exchange(d, false, x, cs));
 		x.active = false;
@@ -415,29 +440,8 @@ int post(hns_dist* d, int type, std::vector<std::pair<float*, int>> fields, hipS
 int complete(hns_dist* d, hipStream_t st) {
 	Pending& x = d->pending;
 	if (!x.active) return HNS_OK;
-	if (!d->comm && !d->loopback && !d->ipc) {  // local transport: pull every peer's message out of its send buffer, once the peer has packed it
-		for (Peer& p : d->peers) {
-			// the peer packed this message into its buffer of the same parity when it posted the same exchange; it may already
-			// have posted the NEXT one (other parity) -- never the one after, which its own complete() of this one precedes
-			hns_dist* q = d->local_ranks[(size_t)p.rank];
-			const Peer* back = nullptr;
-			for (const Peer& c : q->peers)
-				if (c.rank == d->rank) back = &c;
-			const size_t nr = message_floats(x, p.recv[x.type]);
-			if (!nr) continue;
-			if (!back || message_floats(x, back->send[x.type]) != nr) return fail(HNS_ERR_RUNTIME, "hns_dist: send/receive plans of two ranks disagree");
-			const Pending& y = q->pending;  // the peer's record of the same exchange (its fields are ITS device arrays)
-			if (y.type != x.type || y.parity != x.parity || y.fields.size() != x.fields.size()) return fail(HNS_ERR_RUNTIME, "hns_dist: locally connected ranks are out of step");
-			if (!d->single_stream) HNS_HIP(hipStreamWaitEvent(x.stream, q->ev_post[x.parity], 0));
-			int before = 0;
-			for (size_t fi = 0; fi < x.fields.size(); ++fi) {
-				const int nc = x.fields[fi].second;
-				HNS_HIP(hipMemcpyAsync(segment(p.recv[x.type], x.fields[fi].first, nc, p.rbuf[x.parity], before),
-				                       segment(back->send[x.type], y.fields[fi].first, nc, back->sbuf[x.parity], before), sizeof(float) * (size_t)p.recv[x.type].voxels * nc,
-				                       hipMemcpyDeviceToDevice, x.stream));
-				before += nc;
-			}
-		}
+	if (transport(d) == Transport::Local) {
+		HNS_TRY(transfer_local(d, x));
 		HNS_TRY(unpack(d, x));
 	}
 	if (!d->single_stream) HNS_HIP(hipStreamWaitEvent(st, d->ev_done[x.parity], 0));
@@ -455,7 +459,7 @@ int complete(hns_dist* d, hipStream_t st) {
 bool complete_boundary_only(hns_dist* d, hipStream_t st) {
 	Pending& x = d->pending;
 	if (!x.active) return true;
-	if (d->single_stream || !(d->comm || d->loopback || d->ipc)) return false;
+	if (!two_stream_transport(d)) return false;
 	if (hipStreamWaitEvent(st, d->ev_bdone[x.parity], 0) != hipSuccess) return false;
 	x.active = false;
 	return true;
@@ -471,9 +475,6 @@ struct Phase {
 	int block;  // SorBlock: which block of up to k sweeps of the pressure loop (0 otherwise)
 	bool operator==(const Phase& o) const { return kind == o.kind && block == o.block; }
 };
-
-typedef std::vector<std::pair<float*, int>> Fields;
-typedef std::vector<std::pair<const float*, int>> Outs;
 
 struct Step {
 	hns_dist* d;
@@ -534,7 +535,7 @@ struct Step {
 	// under. Large ranks (a 256^3 slab: 32,768 leaves) keep the boundary / interior split on two streams. A rank decides for itself: the messages are the same either way.
 	bool in_line_rank() const {
 		const int u = options().dist_unsplit.load();  // 0 never | 1 by size | 2 always
-		return !d->single_stream && (d->comm || d->loopback || d->ipc) && u != 0 && (u == 2 || d->nB + d->nI <= 16384);
+		return two_stream_transport(d) && u != 0 && (u == 2 || d->nB + d->nI <= 16384);
 	}
 
 	// Do both launch ranges of the split sweep take two iterations in ONE launch each (result in dst for both)? Asked of the schedule
@@ -571,6 +572,41 @@ struct Step {
 		return launch_status("hns_dist: chained launch");
 	}
 
+	// chained form of the two advection phases: behind the kernel as it is, the boundary leaves' new values go into the peers' ghost voxels (k_chain_mirror)
+	template <int NC>
+	int chain_mirror(const PhaseMirror& m, float* const* outs, int n_out) {
+		const float* f[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+		for (int s = 0; s < n_out && s < 8; ++s) f[s] = outs[s];
+		if (d->nB && m.n_peers) hipLaunchKernelGGL(k_chain_mirror<NC>, dim3((unsigned)d->nB), dim3(64), 0, st, m, n_out, f[0], f[1], f[2], f[3], f[4], f[5], f[6], f[7]);
+		return HNS_OK;
+	}
+
+	// THE form of a stencil phase, chosen here for all of them. A phase states its kernel -- `kernel(g, s)`: over launch range g on stream s, an empty range being a no-op --,
+	// the fields it writes that the peers read, and their region type; and `chain(m)`, its one launch over the owned leaves in the chained form (arguments m).
+	//   chained   one launch over gO that delivers its own halo (the two advection kernels: behind a gate, with chain_mirror behind them)
+	//   in line   one launch over gO, the exchange behind it on the compute stream: the SHORT phases of a small rank (in_line_rank), core substep only
+	//   split     gB on the communication stream, gI handed to post(), which enqueues it in front of the pack / transfer / unpack calls
+	//   the same with gI launched here, BEHIND post(): the full substep's divergence, gradient and scalar advection
+	template <class Kernel, class Chain>
+	int stencil(PhaseKind kind, int type, Fields fields, Kernel kernel, Chain chain) {
+		const bool advection = kind == PhaseKind::AdvectVector || kind == PhaseKind::AdvectScalars;
+		const bool short_phase = kind == PhaseKind::Divergence || kind == PhaseKind::Gradient;
+		if (chained_form()) {
+			const PhaseMirror m = phase_args(d, type, fields);
+			return chained(m, [&] { return chain(m); }, advection);
+		}
+		auto over = [&kernel](hns_grid* g) { return [&kernel, g](hipStream_t s) { return kernel(g, s); }; };
+		if (!full() && short_phase && in_line_rank()) return post(d, type, std::move(fields), st, over(d->gO), nothing, true);
+		// The full substep's interior launch of these phases stays BEHIND post(). Moving it in front, as round 6 did for the core substep (see post()), changes the order
+		// in which work reaches the device and so its timing: a performance change that needs its own measurement, not a refactor.
+		const bool interior_behind_post = full() && (short_phase || kind == PhaseKind::AdvectScalars);
+		if (interior_behind_post) {
+			HNS_TRY(post(d, type, std::move(fields), st, over(d->gB), nothing));
+			return kernel(d->gI, st);
+		}
+		return post(d, type, std::move(fields), st, over(d->gB), over(d->gI));
+	}
+
 	// the advection inputs: phi unless the previous substep already posted it, and u
 	int open() {
 		Fields f;
@@ -598,57 +634,31 @@ struct Step {
 
 	// advect_vector (:162-170); vorticity confinement reads it up to factor_scale + 1 voxels away: whole leaves travel then
 	int advect_vector() {
-		const float ix = inv_dx(), dtv = dt;
-		if (chained_form()) {
-			const PhaseMirror m = phase_args(d, X_D1, Outs{{d->adv, 3}});
-			return chained(m, [&] {  // gate | the kernel as it is | copy of the boundary leaves' reach-1 voxels into the peers' ghosts
-				HNS_TRY(hns_dev_advect_vector(d->gO, d->u, d->adv, nullptr, 0, dt, ix, st));
-				if (d->nB && m.n_peers)
-					hipLaunchKernelGGL(k_chain_mirror<3>, dim3((unsigned)d->nB), dim3(64), 0, st, m, 1, (const float*)d->adv, (const float*)nullptr, (const float*)nullptr,
-					                   (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr);
-				return HNS_OK;
-			}, true);
-		}
-		hns_dist* D = d;
-		const float* sd = sdf();
-		const int c = coll ? 1 : 0;
-		return post(d, vort ? X_ADV : X_D1, Fields{{d->adv, 3}}, st, [=](hipStream_t s) { return hns_dev_advect_vector(D->gB, D->u, D->adv, sd, c, dtv, ix, s); },
-		            [=](hipStream_t s) { return hns_dev_advect_vector(D->gI, D->u, D->adv, sd, c, dtv, ix, s); });
+		const float ix = inv_dx();
+		auto kernel = [&](hns_grid* g, hipStream_t s) { return hns_dev_advect_vector(g, d->u, d->adv, sdf(), coll ? 1 : 0, dt, ix, s); };
+		return stencil(PhaseKind::AdvectVector, vort ? X_ADV : X_D1, Fields{{d->adv, 3}}, kernel, [&](const PhaseMirror& m) -> int {
+			HNS_TRY(kernel(d->gO, st));
+			return chain_mirror<3>(m, &d->adv, 1);
+		});
 	}
 
 	// :172-176, out of place (the reference's in-place launch races)
 	int vorticity() {
-		hns_dist* D = d;
-		const float ix = inv_dx(), dtv = dt, scale = prm->vorticityScale, fs = prm->factorScale;
-		HNS_TRY(post(d, X_D1, Fields{{d->tmp, 3}}, st, [=](hipStream_t s) { return hns_dev_vorticity_confinement(D->gB, D->adv, D->tmp, dtv, ix, scale, fs, s); },
-		             [=](hipStream_t s) { return hns_dev_vorticity_confinement(D->gI, D->adv, D->tmp, dtv, ix, scale, fs, s); }));
+		const float ix = inv_dx();
+		HNS_TRY(stencil(PhaseKind::Vorticity, X_D1, Fields{{d->tmp, 3}},
+		                [&](hns_grid* g, hipStream_t s) { return hns_dev_vorticity_confinement(g, d->adv, d->tmp, dt, ix, prm->vorticityScale, prm->factorScale, s); }, no_chain));
 		std::swap(d->adv, d->tmp);
 		return HNS_OK;
 	}
 
-	// divergence (:181-188)
+	// divergence (:181-188); full: + what combustion adds to it over the same leaves (:211-221, k_combustion_div: fuel and waste only)
 	int divergence() {
-		hns_dist* D = d;
 		const float ix = inv_dx();
-		if (!full()) {
-			if (d->chain) {
-				const PhaseMirror m = phase_args(d, X_DIV, Outs{{d->div, 1}});
-				return chained(m, [&] { return hns_chain_divergence(d->gO, d->adv, d->div, ix, &m, st); });
-			}
-			if (in_line_rank()) return post(d, X_DIV, Fields{{d->div, 1}}, st, [=](hipStream_t s) { return hns_dev_divergence(D->gO, D->adv, D->div, ix, s); }, nothing, true);
-			return post(d, X_DIV, Fields{{d->div, 1}}, st, [=](hipStream_t s) { return hns_dev_divergence(D->gB, D->adv, D->div, ix, s); },
-			            [=](hipStream_t s) { return hns_dev_divergence(D->gI, D->adv, D->div, ix, s); });
-		}
-		// full: + what combustion adds to it (:211-221, k_combustion_div: fuel and waste only); its interior launches follow post() instead of being handed to it
-		const float ex = prm->expansionRate;
-		const float *fuel = d->phi[(size_t)fi[0]], *waste = d->phi[(size_t)fi[1]];
-		const uint64_t nb = (uint64_t)d->nB * 512u, ni = (uint64_t)d->nI * 512u;
-		HNS_TRY(post(d, X_DIV, Fields{{d->div, 1}}, st, [=](hipStream_t s) {
-			HNS_TRY(hns_dev_divergence(D->gB, D->adv, D->div, ix, s));
-			return nb ? hns_combustion_div(fuel, waste, D->div, ex, nb, s) : HNS_OK;
-		}, nothing));
-		HNS_TRY(hns_dev_divergence(d->gI, d->adv, d->div, ix, st));
-		return ni ? hns_combustion_div(fuel + nb, waste + nb, d->div + nb, ex, ni, st) : HNS_OK;
+		return stencil(PhaseKind::Divergence, X_DIV, Fields{{d->div, 1}}, [&](hns_grid* g, hipStream_t s) -> int {
+			HNS_TRY(hns_dev_divergence(g, d->adv, d->div, ix, s));
+			const uint64_t first = g->first_active * 512u, n = g->n_active * 512u;
+			return full() && n ? hns_combustion_div(d->phi[(size_t)fi[0]] + first, d->phi[(size_t)fi[1]] + first, d->div + first, prm->expansionRate, n, s) : (int)HNS_OK;
+		}, [&](const PhaseMirror& m) { return hns_chain_divergence(d->gO, d->adv, d->div, ix, &m, st); });
 	}
 
 	// the rest of combustion, buoyancy with the NEW temperature (:226-234), outputs become inputs (:239-246): pointwise, owned voxels
@@ -746,7 +756,7 @@ struct Step {
 			HNS_TRY(open_timed());
 		}
 		const int its = std::min(2, iterations - it);
-		const PhaseMirror m = phase_args(d, X_P, Outs{{dst, 1}});
+		const PhaseMirror m = phase_args(d, X_P, Fields{{dst, 1}});
 		const bool zero = it == 0;
 		HNS_TRY(chained(m, [&] { return hns_rbgs_block_mirror_launch(d->gO, d->div, src, dst, d->voxel_size, omega_compute(d->voxel_size), zero, &m, st, its); }));
 		std::swap(src, dst);
@@ -769,53 +779,19 @@ struct Step {
 			d->solve_ev.advance();
 			d->timed_sweeps += iterations;
 		}
-		hns_dist* D = d;
 		const float ix = inv_dx();
-		if (!full()) {
-			if (d->chain) {  // (its boundary workgroups wait for the peers' last sweep themselves)
-				const PhaseMirror m = phase_args(d, X_ADV, Outs{{d->u, 3}});
-				return chained(m, [&] { return hns_chain_subtract_pressure_gradient(d->gO, d->adv, d->p_result, d->u, ix, &m, st); });
-			}
-			if (in_line_rank())
-				return post(d, X_ADV, Fields{{d->u, 3}}, st, [=](hipStream_t s) { return hns_dev_subtract_pressure_gradient(D->gO, D->adv, D->p_result, D->u, nullptr, 0, ix, s); }, nothing, true);
-			return post(d, X_ADV, Fields{{d->u, 3}}, st, [=](hipStream_t s) { return hns_dev_subtract_pressure_gradient(D->gB, D->adv, D->p_result, D->u, nullptr, 0, ix, s); },
-			            [=](hipStream_t s) { return hns_dev_subtract_pressure_gradient(D->gI, D->adv, D->p_result, D->u, nullptr, 0, ix, s); });
-		}
-		// full: with collision; its interior launches follow post() instead of being handed to it
-		const float* sd = sdf();
-		const int c = coll ? 1 : 0;
-		const float vs = d->voxel_size;
-		HNS_TRY(post(d, X_ADV, Fields{{d->u, 3}}, st, [=](hipStream_t s) {
-			HNS_TRY(hns_dev_subtract_pressure_gradient(D->gB, D->adv, D->p_result, D->u, sd, c, ix, s));
-			return c ? hns_dev_enforce_collision_boundaries(D->gB, D->u, sd, vs, s) : HNS_OK;
-		}, nothing));
-		HNS_TRY(hns_dev_subtract_pressure_gradient(d->gI, d->adv, d->p_result, d->u, sd, c, ix, st));
-		return c ? hns_dev_enforce_collision_boundaries(d->gI, d->u, sd, vs, st) : HNS_OK;
+		return stencil(PhaseKind::Gradient, X_ADV, Fields{{d->u, 3}}, [&](hns_grid* g, hipStream_t s) -> int {
+			HNS_TRY(hns_dev_subtract_pressure_gradient(g, d->adv, d->p_result, d->u, sdf(), coll ? 1 : 0, ix, s));
+			return coll ? hns_dev_enforce_collision_boundaries(g, d->u, sdf(), d->voxel_size, s) : (int)HNS_OK;
+		}, [&](const PhaseMirror& m) {  // (its boundary workgroups wait for the peers' last sweep themselves)
+			return hns_chain_subtract_pressure_gradient(d->gO, d->adv, d->p_result, d->u, ix, &m, st);
+		});
 	}
 
 	// advect every float field except collision_sdf with the projected velocity (:321-356), and already post them for the advection that opens the next substep
 	int advect_scalars() {
 		d->u_ghosts_fresh = !coll;  // (with collision the next substep rewrites u before it advects)
 		const float ix = inv_dx();
-		if (chained_form()) {
-			if (d->n_scalars) {
-				Outs outs;
-				for (float* p : d->phi_next) outs.emplace_back(p, 1);
-				const PhaseMirror m = phase_args(d, X_ADV, outs);
-				std::vector<const float*> in(d->phi.begin(), d->phi.end());
-				HNS_TRY(chained(m, [&] {
-					HNS_TRY(hns_dev_advect_scalars(d->gO, d->u, in.data(), d->phi_next.data(), d->n_scalars, nullptr, 0, dt, ix, st));
-					const float* f[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-					for (int s = 0; s < d->n_scalars && s < 8; ++s) f[s] = d->phi_next[(size_t)s];
-					if (d->nB && m.n_peers)
-						hipLaunchKernelGGL(k_chain_mirror<1>, dim3((unsigned)d->nB), dim3(64), 0, st, m, d->n_scalars, f[0], f[1], f[2], f[3], f[4], f[5], f[6], f[7]);
-					return HNS_OK;
-				}, true));
-				std::swap(d->phi, d->phi_next);
-			}
-			d->phi_in_flight = true;  // (here: the peers' ghost copies of phi are already being written, nothing to open the next substep with)
-			return HNS_OK;
-		}
 		std::vector<const float*> in;
 		std::vector<float*> out;
 		std::vector<int> which;
@@ -825,18 +801,17 @@ struct Step {
 		if (ns) {
 			Fields f;
 			for (float* p : out) f.emplace_back(p, 1);  // the boundary leaves' new values travel while the interior is advected
-			const float* sd = sdf();
-			const int c = coll ? 1 : 0;
-			auto part = [&](hns_grid* g, hipStream_t s) { return g->n_active ? hns_dev_advect_scalars(g, d->u, in.data(), out.data(), ns, sd, c, dt, ix, s) : (int)HNS_OK; };
-			if (full()) {  // (its interior launch follows post() instead of being handed to it)
-				HNS_TRY(post(d, X_ADV, f, st, [&](hipStream_t s) { return part(d->gB, s); }, nothing));
-				HNS_TRY(part(d->gI, st));
-			} else {
-				HNS_TRY(post(d, X_ADV, f, st, [&](hipStream_t s) { return part(d->gB, s); }, [&](hipStream_t s) { return part(d->gI, s); }));
-			}
+			auto kernel = [&](hns_grid* g, hipStream_t s) {
+				return g->n_active ? hns_dev_advect_scalars(g, d->u, in.data(), out.data(), ns, sdf(), coll ? 1 : 0, dt, ix, s) : (int)HNS_OK;
+			};
+			HNS_TRY(stencil(PhaseKind::AdvectScalars, X_ADV, std::move(f), kernel, [&](const PhaseMirror& m) -> int {
+				HNS_TRY(kernel(d->gO, st));
+				return chain_mirror<1>(m, out.data(), ns);
+			}));
 		}
 		for (int s : which) std::swap(d->phi[(size_t)s], d->phi_next[(size_t)s]);
-		d->phi_in_flight = ns > 0 && d->world > 1;
+		// (chained: the peers' ghost copies of phi are already being written, nothing to open the next substep with -- whether or not the rank has scalars)
+		d->phi_in_flight = chained_form() || (ns > 0 && d->world > 1);
 		return HNS_OK;
 	}
 };

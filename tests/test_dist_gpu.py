@@ -6,7 +6,7 @@ plume split into 8 leaf ranges."""
 import numpy as np
 import pytest
 
-from dist_cases import SIM_NAMES, check, partitioned_sim_substeps_match_single_grid, run_local, single_grid
+from dist_cases import EXCHANGE_FORMS, SIM_NAMES, check, exchange_counts, partitioned_sim_substeps_match_single_grid, run_local, single_grid
 from hnanosolver_amd import dist as HD
 from hnanosolver_amd import fields
 
@@ -310,6 +310,27 @@ def test_one_process_per_rank_over_mapped_peer_memory(case, world, k, iters, tmp
         for n in names:
             assert np.array_equal(g[n], HD.take_leaves(want[n], ids)), f"rank {r} {n}"
         assert int(g["messages"]) > 0
+    if (case, world, k, iters) == ("plume", 3, 2, 7):  # the one-sided transport issues the exchanges it issued before the halo exchange was stated once
+        assert [{"exchanges": int(g["exchanges"]), "messages_sent": int(g["messages"])} for g in got] == _golden_exchange_counts()["ipc_plume_3_k2"]
+
+
+def _golden_exchange_counts():
+    import json
+    import os
+
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "dist_exchange_counts.json")) as f:
+        return json.load(f)
+
+
+@pytest.mark.parametrize("form", sorted(EXCHANGE_FORMS))
+def test_every_form_issues_the_exchanges_it_issued_before(form):
+    """One pack kernel, one walk over a message, one transfer per transport and one statement of a phase's form (hns_dist_substep.hip) replaced several copies of each:
+    every form of the substep -- per-peer and combined pack tables, chained, split and in line on two streams -- still reports, rank by rank, the exchanges, messages,
+    self-packed exchanges and bytes per region type that the commit before reported (tests/golden/dist_exchange_counts.json, profiles/micro/dist_exchange_counts.py),
+    after one core substep and after one whole Compute_Sim substep. The values themselves are the other tests' business: bit for bit against the single grid."""
+    got, want = exchange_counts(form), _golden_exchange_counts()[form]
+    assert form != "local_chained" or all(r["chained"] for r in got["core"])
+    assert got == want
 
 
 @pytest.mark.parametrize("extra", [[], ["--config", "plume", "--partition"]])
