@@ -74,6 +74,10 @@ class hns_solve_method(C.Structure):
     _fields_ = [("method", C.c_int), ("pre", C.c_int), ("post", C.c_int), ("coarse_iterations", C.c_int), ("max_levels", C.c_int), ("omega", C.c_float)]
 
 
+class hns_splat_spec(C.Structure):
+    _fields_ = [("kernel", C.c_int), ("mode", C.c_int), ("radius", C.c_float), ("d_radius", C.c_void_p), ("min_weight", C.c_float)]
+
+
 class hns_combustion_params(C.Structure):
     _fields_ = [(n, C.c_float) for n in ("expansionRate", "temperatureRelease", "buoyancyStrength", "ambientTemp", "vorticityScale", "factorScale")]
 
@@ -164,6 +168,12 @@ SIGNATURES = {
     "hns_dev_trace_points": (_i, [_vp, _fp, _fp, _u64, _f, _f, _i, _i, _vp, _vp]),
     "hns_dev_splat_points": (_i, [_vp, C.POINTER(C.c_void_p), _ip, _i, _fp, C.POINTER(C.c_void_p), _u64, _i, _vp, _vp, _vp]),
     "hns_grid_splat_points": (_i, [_vp, C.POINTER(C.c_void_p), _ip, _i, _fp, C.POINTER(C.c_void_p), _u64, _i, _vp, _i, _vp, C.POINTER(C.c_uint64)]),
+    "hns_grid_set_splat_spec": (_i, [_vp, C.POINTER(hns_splat_spec)]),
+    "hns_sim_set_splat_spec": (_i, [_vp, C.POINTER(hns_splat_spec)]),
+    "hns_grid_get_splat_spec": (_i, [_vp, C.POINTER(hns_splat_spec)]),
+    "hns_sim_get_splat_spec": (_i, [_vp, C.POINTER(hns_splat_spec)]),
+    "hns_grid_splat_points_spec": (_i, [_vp, C.POINTER(hns_splat_spec), C.POINTER(C.c_void_p), _ip, _i, _fp, C.POINTER(C.c_void_p), _u64, _i, _vp, _i, _vp,
+                                        C.POINTER(C.c_uint64)]),
     "hns_point_leaves": (_i, [_fp, _u64, _vp, _vp, _u64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "hns_dev_point_leaves": (_i, [_i, _fp, _u64, _vp, _vp, _u64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), _vp]),
     "hns_dev_divergence": (_i, [_vp, _fp, _fp, _f, _vp]),

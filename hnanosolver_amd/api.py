@@ -321,23 +321,65 @@ def Divergence(data: GridIndexedData, voxelSize: float, stream=None, handle: Opt
     _raise(lib.hns_divergence(h.ptr, fields, n, float(voxelSize), _stream(stream)))
 
 
-def splat_points_host(grid: IndexGridHandle, fields, xyz, values, log2_quantum: int = -32, masks=None, activate: bool = True, status=None) -> int:
-    """Host mirror of ``device.splat_points`` / ``device.Sim.splat`` (``hns_grid_splat_points``): the point values `values` (one (n,) or (n, 3) float32 array per field)
+SPLAT_KERNELS = {"trilinear": 0, "radial": 1}
+SPLAT_MODES = {"add": 0, "average": 1}
+
+
+def splat_spec(kernel: str = "trilinear", mode: str = "add", radius=None, max_radius: Optional[float] = None, min_weight: float = 0.0, pointer=None) -> _lib.hns_splat_spec:
+    """The ``hns_splat_spec`` of the splat calls' keywords. radius: None, a number, or one radius per point -- an array whose address is ``pointer(radius)`` (device memory for
+    the device calls, host memory for the mirror), with its upper bound in `max_radius`. What the numbers may be is the library's to refuse."""
+    if kernel not in SPLAT_KERNELS or mode not in SPLAT_MODES:
+        raise ValueError(f"splat: kernel must be one of {sorted(SPLAT_KERNELS)} and mode one of {sorted(SPLAT_MODES)}")
+    spec = _lib.hns_splat_spec(SPLAT_KERNELS[kernel], SPLAT_MODES[mode], 0.0, None, float(min_weight))
+    if radius is None:
+        if kernel == "radial":
+            raise ValueError("splat: kernel='radial' needs a radius")
+    elif isinstance(radius, (int, float, np.floating, np.integer)):
+        spec.radius = float(radius)
+    else:
+        if max_radius is None:
+            raise ValueError("splat: one radius per point needs its upper bound in max_radius")
+        spec.radius, spec.d_radius = float(max_radius), pointer(radius)
+    return spec
+
+
+class stored_splat_spec:
+    """``with stored_splat_spec(setter, getter, handle, spec):`` -- the spec stored with a grid or a sim for the block, the previous one back afterwards"""
+
+    def __init__(self, setter, getter, handle, spec):
+        self.setter, self.handle, self.spec, self.previous = setter, handle, spec, _lib.hns_splat_spec()
+        _raise(getter(handle, C.byref(self.previous)))
+
+    def __enter__(self):
+        _raise(self.setter(self.handle, C.byref(self.spec)))
+
+    def __exit__(self, *exc):
+        _raise(self.setter(self.handle, C.byref(self.previous)))
+
+
+def splat_points_host(grid: IndexGridHandle, fields, xyz, values, log2_quantum: int = -32, masks=None, activate: bool = True, status=None, *, kernel: str = "trilinear",
+                      mode: str = "add", radius=None, max_radius: Optional[float] = None, min_weight: float = 0.0) -> int:
+    """Host mirror of ``device.splat_points`` / ``device.Sim.splat`` (``hns_grid_splat_points_spec``): the point values `values` (one (n,) or (n, 3) float32 array per field)
     at the index-space positions xyz ((n, 3) float32) added IN PLACE into `fields` ((N,) or (N, 3) C-contiguous float32 arrays), with the device's integer arithmetic;
     works on host-only grids. masks: None, or leaf_count x 64 uint8, in which (with activate) the bit of every landed tap of positive weight is set; status: None, or n
-    uint8 receiving the landed taps of each point. Returns the number of (point, component, tap) terms that landed but were not accepted."""
+    uint8 receiving the landed taps of each point (radial: 2 the whole footprint landed, 1 a part, 0 nothing). kernel, mode, radius (a number, or a float32 array of n with
+    max_radius its bound) and min_weight as for ``device.splat_points``. Returns the number of (point, component, tap) terms that landed but were not accepted."""
     xyz = np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
     vals = [np.ascontiguousarray(v, dtype=np.float32) for v in values]
     for a in list(fields) + ([] if masks is None else [masks]) + ([] if status is None else [status]):
         if not a.flags["C_CONTIGUOUS"] or not a.flags["WRITEABLE"]:
             raise TypeError("splat_points_host: fields, masks and status must be C-contiguous writable arrays")
+    if radius is not None and not isinstance(radius, (int, float, np.floating, np.integer)):
+        radius = np.ascontiguousarray(radius, dtype=np.float32)
+        if radius.shape != (xyz.shape[0],):
+            raise ValueError("splat_points_host: radius must be a number or one float per point")
+    spec = splat_spec(kernel, mode, radius, max_radius, min_weight, pointer=lambda a: a.ctypes.data)
     k = len(fields)
     nc = [3 if (f.ndim == 2 and f.shape[1] == 3) else 1 for f in fields]
     dst = (C.c_void_p * max(1, k))(*[f.ctypes.data for f in fields])
     src = (C.c_void_p * max(1, k))(*[v.ctypes.data for v in vals])
     rejected = C.c_uint64(0)
-    _raise(lib.hns_grid_splat_points(grid.ptr, dst, (C.c_int * max(1, k))(*nc), k, xyz.ctypes.data, src, xyz.shape[0], int(log2_quantum),
-                                     None if masks is None else masks.ctypes.data, int(bool(activate)), None if status is None else status.ctypes.data,
-                                     C.byref(rejected)))
+    _raise(lib.hns_grid_splat_points_spec(grid.ptr, C.byref(spec), dst, (C.c_int * max(1, k))(*nc), k, xyz.ctypes.data, src, xyz.shape[0], int(log2_quantum),
+                                          None if masks is None else masks.ctypes.data, int(bool(activate)), None if status is None else status.ctypes.data,
+                                          C.byref(rejected)))
     return int(rejected.value)
-

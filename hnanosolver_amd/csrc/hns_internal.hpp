@@ -266,6 +266,7 @@ struct hns_grid {
 	size_t splat_bytes = 0;
 	int splat_channels = 0;
 	bool splat_dirty = false;
+	hns_splat_spec splat_spec = {0, 0, 0.0f, nullptr, 0.0f};  // hns_grid_set_splat_spec: what hns_dev_splat_points on this grid reads (the default: today's cell, a sum)
 	std::mutex build_mutex;              // guards the tables built on first use (block records): cooks from several host threads may share a grid
 	std::mutex host_mutex;               // guards the lazy host copy of the device-built tables and sim_cache
 	std::vector<hns_sim*> sim_cache;     // device-resident state kept between operator calls (hns_api.hip: make_sim)
@@ -364,6 +365,7 @@ struct hns_sim {
 	// hierarchy of coarse grids, masks, tables and buffers (hns_multigrid.hip)
 	struct Multigrid;
 	Multigrid* mg = nullptr;
+	hns_splat_spec splat_spec = {0, 0, 0.0f, nullptr, 0.0f};  // hns_sim_set_splat_spec: what hns_sim_splat_points reads; the sim's own, so a regrid's new grid changes nothing
 	int device = -1;
 	int find(const char* name) const {
 		for (size_t i = 0; i < names.size(); ++i)

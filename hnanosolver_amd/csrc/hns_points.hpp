@@ -1,8 +1,12 @@
 // hns_points.hpp -- the trilinear cell under an index-space position, shared by the kernel files that work at points: hns_points.hip (fields read at points, points
-// traced through the velocity) and hns_splat.hip (point values added into fields). One statement of Floor, the tap indices and the fractions for both directions.
+// traced through the velocity), hns_splat.hip (point values added into fields) and hns_rasterize.hip (the same with a radius). One statement of Floor, the tap indices and
+// the fractions for both directions, and one of the splat's arithmetic -- weights, footprint, term, total, average -- for the kernels and the host mirror.
 #pragma once
 
+#include <cmath>
+
 #include "hns_device.hpp"
+#include "hns_seed.hpp"
 
 namespace hns {
 
@@ -76,6 +80,87 @@ __device__ __forceinline__ Cell point_cell(const GridDev& g, Cursor& cur, float 
 }
 
 __device__ __forceinline__ bool finite_f(float a) { return (__float_as_uint(a) & 0x7fffffffu) < 0x7f800000u; }
+
+// ---- point values into fields: what hns_splat.hip and hns_rasterize.hip share ----------------------------------------------------------------------------------------
+
+constexpr int kSplatChannels = 4;   // channels one launch accumulates: the channels of a voxel's piece of the accumulator (32 bytes: one L2 sector pair)
+constexpr int kSplatBlock = 256;
+
+// one component of a field and of its point values: element e of either is at [e * stride + off] (a float field: 1, 0; component c of a Vec3f AoS field: 3, c).
+// val null: the weight channel W of an average (every point's value is 1.0f, no field)
+struct SplatChannel {
+	const float* val;
+	float* field;
+	int stride, off;
+	int wide;  // finish: the field is a 16-byte aligned float array, four voxels per access
+};
+// the channels of one pass. average: channel 0 is W and the finish divides channels 1 .. n - 1 by it
+struct SplatChannels {
+	SplatChannel c[kSplatChannels];
+	int n;
+	int average;
+	float min_weight;
+};
+
+// The arithmetic, stated once for the kernels and the host mirror (-ffp-contract=off: every line is one rounded operation; include/hns.h states it in words).
+
+// trilinear: w[di*4+dj*2+dk] = (wx[di] * wy[dj]) * wz[dk]
+__host__ __device__ inline void splat_weights(float fx, float fy, float fz, float (&w)[8]) {
+	const float wx[2] = {1.0f - fx, fx}, wy[2] = {1.0f - fy, fy}, wz[2] = {1.0f - fz, fz};
+	for (int c = 0; c < 8; ++c) w[c] = (wx[c >> 2] * wy[(c >> 1) & 1]) * wz[c & 1];
+}
+
+// radial: does a point with radius r rasterise under the spec's bound? (a NaN fails every comparison)
+__host__ __device__ inline bool radial_point(float x, float y, float z, float r, float bound) { return seeds_f(x) && seeds_f(y) && seeds_f(z) && 0.0f < r && r <= bound; }
+// the box of candidates along one axis: lo .. lo + E - 1 (a rasterising point: the floor is exact and fits an int; r <= 4: E <= 8)
+__host__ __device__ inline int radial_extent(float r) { return (int)ceilf(2.0f * r); }
+__host__ __device__ inline int radial_lo(float c, float r) {
+	const float low = c - r;
+	return (int)floorf(low) + 1;
+}
+__host__ __device__ inline float radial_inv(float r) {
+	const float r2 = r * r;
+	return 1.0f / r2;
+}
+// the weight of the candidate (dx, dy, dz) away from the point; false: it is not in the footprint
+__host__ __device__ inline bool radial_weight(float dx, float dy, float dz, float inv, float* w) {
+	const float xx = dx * dx, yy = dy * dy, zz = dz * dz;
+	const float xy = xx + yy;
+	const float d2 = xy + zz;
+	const float q = d2 * inv;
+	if (!(q < 1.0f)) return false;
+	const float a = 1.0f - q;
+	*w = a * a;
+	return true;
+}
+
+// Is the term t accepted, and as which multiple of the quantum? scale = 2^-Q: the product is exact in f64 (a power of two, |t| < 2^128, scale <= 2^40), so the test is the
+// header's "t finite and |t| * 2^-Q < 2^62" (a NaN and an inf fail the comparison), and k = rint of it, ties to even.
+__host__ __device__ inline bool splat_term(float t, double scale, long long* k) {
+	const double x = (double)t * scale;
+	if (!(fabs(x) < 0x1p62)) return false;
+#ifdef __HIP_DEVICE_COMPILE__
+	*k = __double2ll_rn(x);
+#else
+	*k = (long long)std::nearbyint(x);  // (the default rounding mode: to nearest, ties to even)
+#endif
+	return true;
+}
+
+// what a non-zero accumulator adds to its voxel: quantum = 2^Q
+__host__ __device__ inline float splat_total(unsigned long long a, double quantum) { return (float)((double)(long long)a * quantum); }
+
+// average: what a voxel with the non-zero weight accumulator a_w becomes
+__host__ __device__ inline float splat_average(unsigned long long a_v, unsigned long long a_w, double quantum, float min_weight) {
+	const float wsum = splat_total(a_w, quantum), vsum = splat_total(a_v, quantum);
+	const float den = fmaxf(wsum, min_weight);
+	return vsum / den;
+}
+
+// hns_rasterize.hip: lanes of a group that share one point (1, 4, 16 or 64, from the spec's radius), and the radial kernel's launch in place of k_splat_points'
+int splat_radial_group(float radius);
+void launch_splat_radial(hipStream_t st, const GridDev& g, const SplatChannels& ch, const float* xyz, const float* radii, float bound, unsigned n, double scale,
+                         unsigned long long* acc, int S, int* touched, unsigned* masks, unsigned char* status, unsigned long long* rejected);
 
 // ---- launcher plumbing of the point calls ----
 

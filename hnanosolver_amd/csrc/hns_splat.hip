@@ -2,7 +2,8 @@
 // nest, and an accumulation whose result does not depend on the order the adds retire in: every term is rounded ONCE to a multiple of the quantum 2^Q and added as a 64-bit
 // integer (include/hns.h: hns_dev_splat_points states the arithmetic). Integer addition modulo 2^64 is associative, so two runs, and the host mirror below, give the same
 // bytes. No float atomics. One thread per point adds into an accumulator kept with the grid; a second launch, one wave per touched leaf, adds the accumulator into the
-// fields and leaves it zero for the next call.
+// fields and leaves it zero for the next call. Under a spec (include/hns.h: hns_splat_spec) the first launch is the radial kernel of hns_rasterize.hip, and a pass carries
+// a weight channel W that the second launch divides by in place of adding (the average).
 #include "hns_points.hpp"
 
 #include <cmath>
@@ -12,45 +13,7 @@ using namespace hns;
 
 namespace {
 
-constexpr int kSplatChannels = 4;   // components one launch accumulates: the channels of a voxel's piece of the accumulator (32 bytes: one L2 sector pair)
 constexpr int kMaxSplatFields = 8;  // fields of one call
-constexpr int kSplatBlock = 256;
-
-// one component of a field and of its point values: element e of either is at [e * stride + off] (a float field: 1, 0; component c of a Vec3f AoS field: 3, c)
-struct SplatChannel {
-	const float* val;
-	float* field;
-	int stride, off;
-	int wide;  // finish: the field is a 16-byte aligned float array, four voxels per access
-};
-struct SplatChannels {
-	SplatChannel c[kSplatChannels];
-	int n;
-};
-
-// ---- the arithmetic, stated once for the kernel and the host mirror (-ffp-contract=off: every line is one rounded operation) ---------------------------------------
-
-// w[di*4+dj*2+dk] = (wx[di] * wy[dj]) * wz[dk]
-__host__ __device__ inline void splat_weights(float fx, float fy, float fz, float (&w)[8]) {
-	const float wx[2] = {1.0f - fx, fx}, wy[2] = {1.0f - fy, fy}, wz[2] = {1.0f - fz, fz};
-	for (int c = 0; c < 8; ++c) w[c] = (wx[c >> 2] * wy[(c >> 1) & 1]) * wz[c & 1];
-}
-
-// Is the term t accepted, and as which multiple of the quantum? scale = 2^-Q: the product is exact in f64 (a power of two, |t| < 2^128, scale <= 2^40), so the test is the
-// header's "t finite and |t| * 2^-Q < 2^62" (a NaN and an inf fail the comparison), and k = rint of it, ties to even.
-__host__ __device__ inline bool splat_term(float t, double scale, long long* k) {
-	const double x = (double)t * scale;
-	if (!(fabs(x) < 0x1p62)) return false;
-#ifdef __HIP_DEVICE_COMPILE__
-	*k = __double2ll_rn(x);
-#else
-	*k = (long long)std::nearbyint(x);  // (the default rounding mode: to nearest, ties to even)
-#endif
-	return true;
-}
-
-// what a non-zero accumulator adds to its voxel: quantum = 2^Q
-__host__ __device__ inline float splat_total(unsigned long long a, double quantum) { return (float)((double)(long long)a * quantum); }
 
 // ---- kernels -----------------------------------------------------------------------------------------------------------------------------------------------------------
 
@@ -77,7 +40,8 @@ __global__ __launch_bounds__(kSplatBlock) void k_splat_points(const GridDev g, c
 		}
 		float v[kSplatChannels];
 #pragma unroll
-		for (int q = 0; q < kSplatChannels; ++q) v[q] = q < ch.n ? ch.c[q].val[(size_t)p * (unsigned)ch.c[q].stride + (unsigned)ch.c[q].off] : 0.0f;
+		for (int q = 0; q < kSplatChannels; ++q)  // (a channel without point values is the weight channel of an average: every point's value is 1.0f)
+			v[q] = q < ch.n ? (ch.c[q].val ? ch.c[q].val[(size_t)p * (unsigned)ch.c[q].stride + (unsigned)ch.c[q].off] : 1.0f) : 0.0f;
 		float w[8];
 		splat_weights(C.fx, C.fy, C.fz, w);
 		int landed = 0;
@@ -109,7 +73,8 @@ __global__ __launch_bounds__(kSplatBlock) void k_splat_points(const GridDev g, c
 
 // One wave per leaf, four leaves per workgroup. An untouched leaf costs its flag load. Lane l takes voxels 4l .. 4l + 3 of each half of the leaf: their S channels are 32 S
 // contiguous bytes of the accumulator, read and zeroed in 16-byte pieces; a float field takes its four values as one 16-byte access, a Vec3f component one by one. Only
-// voxels with a non-zero accumulator change (a 16-byte store rewrites the others of its four with the bits it read).
+// voxels with a non-zero accumulator change (a 16-byte store rewrites the others of its four with the bits it read). ch.average: channel 0 is the weight channel W, which
+// has no field; the voxels whose W accumulator is non-zero change, and they become Vsum / max(Wsum, min_weight) (splat_average) in place of field + Vsum.
 template <int S>
 __global__ __launch_bounds__(256) void k_splat_finish(const SplatChannels ch, unsigned long long* __restrict__ acc, int* __restrict__ touched, const unsigned n_leaves,
                                                       const double quantum) {
@@ -132,22 +97,27 @@ __global__ __launch_bounds__(256) void k_splat_finish(const SplatChannels ch, un
 #pragma unroll
 		for (int q = 0; q < S; ++q) {
 			if (q >= ch.n) break;
+			if (ch.average && q == 0) continue;
 			const SplatChannel e = ch.c[q];
-			if (!(x[q] | x[S + q] | x[2 * S + q] | x[3 * S + q])) continue;
+			unsigned long long gate[4];  // the accumulator that says whether voxel v0 + j changes: the channel's own, or W
+#pragma unroll
+			for (int j = 0; j < 4; ++j) gate[j] = ch.average ? x[j * S] : x[j * S + q];
+			if (!(gate[0] | gate[1] | gate[2] | gate[3])) continue;
+			auto value = [&](float old, int j) { return ch.average ? splat_average(x[j * S + q], x[j * S], quantum, ch.min_weight) : old + splat_total(x[j * S + q], quantum); };
 			if (e.wide) {
 				float4* f = reinterpret_cast<float4*>(e.field + v0);
 				float4 y = *f;
-				if (x[q]) y.x = y.x + splat_total(x[q], quantum);
-				if (x[S + q]) y.y = y.y + splat_total(x[S + q], quantum);
-				if (x[2 * S + q]) y.z = y.z + splat_total(x[2 * S + q], quantum);
-				if (x[3 * S + q]) y.w = y.w + splat_total(x[3 * S + q], quantum);
+				if (gate[0]) y.x = value(y.x, 0);
+				if (gate[1]) y.y = value(y.y, 1);
+				if (gate[2]) y.z = value(y.z, 2);
+				if (gate[3]) y.w = value(y.w, 3);
 				*f = y;
 			} else {
 #pragma unroll
 				for (int j = 0; j < 4; ++j)
-					if (x[j * S + q]) {
+					if (gate[j]) {
 						float* f = e.field + (v0 + (unsigned)j) * (unsigned)e.stride + (unsigned)e.off;
-						*f = *f + splat_total(x[j * S + q], quantum);
+						*f = value(*f, j);
 					}
 			}
 		}
@@ -195,6 +165,32 @@ int check_splat_lists(const char* who, const void* fields, const int* ncomp, int
 	return HNS_OK;
 }
 
+const hns_splat_spec kDefaultSpec = {0, 0, 0.0f, nullptr, 0.0f};
+
+// what the setters and the host mirror refuse in a spec
+int check_splat_spec(const char* who, const hns_splat_spec& sp) {
+	if (sp.kernel != 0 && sp.kernel != 1) return invalid("%s: spec.kernel is %d (must be 0 trilinear or 1 radial)", who, sp.kernel);
+	if (sp.mode != 0 && sp.mode != 1) return invalid("%s: spec.mode is %d (must be 0 add or 1 average)", who, sp.mode);
+	if (sp.kernel == 1 && !(0.0f < sp.radius && sp.radius <= 4.0f)) return refuse(who, "spec.radius of a radial spec must lie in (0, 4]");
+	if (sp.kernel == 0 && sp.d_radius) return refuse(who, "spec.d_radius is given but spec.kernel is 0 (trilinear)");
+	if (!(sp.min_weight >= 0.0f && sp.min_weight < INFINITY)) return refuse(who, "spec.min_weight must be finite and >= 0");
+	return HNS_OK;
+}
+
+// The passes of a call: add -- up to four value channels each; average -- the weight channel W first, then up to three value channels
+std::vector<SplatChannels> splat_passes(const std::vector<SplatChannel>& all, const hns_splat_spec& sp) {
+	std::vector<SplatChannels> passes;
+	const size_t per = sp.mode ? kSplatChannels - 1 : kSplatChannels;
+	for (size_t base = 0; base < all.size(); base += per) {
+		SplatChannels ch{};
+		ch.average = sp.mode, ch.min_weight = sp.min_weight;
+		if (sp.mode) ch.c[ch.n++] = SplatChannel{nullptr, nullptr, 0, 0, 0};
+		for (size_t q = base; q < std::min(all.size(), base + per); ++q) ch.c[ch.n++] = all[q];
+		passes.push_back(ch);
+	}
+	return passes;
+}
+
 // the pointers of a call with n > 0
 int check_splat_pointers(const char* who, float* const* fields, int n_fields, const float* xyz, const float* const* values, const void* status, const void* rejected) {
 	if (!xyz) return refuse(who, "xyz is null");
@@ -217,8 +213,8 @@ int check_splat_pointers(const char* who, float* const* fields, int n_fields, co
 // ---- launcher --------------------------------------------------------------------------------------------------------------------------------------------------------------
 
 // fields / ncomp / values: HOST arrays of n_fields entries; masks: null, or the active masks of a sim on this grid. Every refusal comes before the first launch.
-int splat_points(const char* who, hns_grid* g, float* const* fields, const int* ncomp, int n_fields, const float* xyz, const float* const* values, uint64_t n,
-                 int log2_quantum, unsigned char* masks, unsigned char* status, uint64_t* d_rejected, void* stream) {
+int splat_points(const char* who, hns_grid* g, const hns_splat_spec& sp, float* const* fields, const int* ncomp, int n_fields, const float* xyz,
+                 const float* const* values, uint64_t n, int log2_quantum, unsigned char* masks, unsigned char* status, uint64_t* d_rejected, void* stream) {
 	if (int rc = check_grid(g, who)) return rc;
 	HNS_TRY(check_splat_lists(who, fields, ncomp, n_fields, values, n, log2_quantum));
 	if (n == 0) return HNS_OK;  // (no point, no device pointer looked at: an empty array's may well be null)
@@ -231,20 +227,22 @@ int splat_points(const char* who, hns_grid* g, float* const* fields, const int* 
 	std::vector<SplatChannel> all;
 	for (int i = 0; i < n_fields; ++i)
 		for (int c = 0; c < ncomp[i]; ++c) all.push_back(SplatChannel{values[i], fields[i], ncomp[i], c, ncomp[i] == 1 && ((uintptr_t)fields[i] & 15u) == 0});
-	HNS_TRY(splat_accumulator(g, std::min<int>(kSplatChannels, (int)all.size()), st));
+	HNS_TRY(splat_accumulator(g, std::min<int>(kSplatChannels, (int)all.size() + (sp.mode ? 1 : 0)), st));
 	const int S = g->splat_channels;
 	unsigned long long* acc = (unsigned long long*)g->d_splat;
 	int* touched = (int*)((char*)g->d_splat + splat_acc_bytes(g, S));
 	const double scale = std::ldexp(1.0, -log2_quantum), quantum = std::ldexp(1.0, log2_quantum);
 	const unsigned n_leaves = (unsigned)g->topo.n_leaves;
 	const dim3 pgrid((unsigned)((n + kSplatBlock - 1) / kSplatBlock)), lgrid((n_leaves + 3u) / 4u);
-	for (size_t base = 0; base < all.size(); base += kSplatChannels) {  // (a channel's sum does not depend on the others: more launches change nothing numerically)
-		SplatChannels ch{};
-		ch.n = (int)std::min<size_t>(kSplatChannels, all.size() - base);
-		for (int q = 0; q < ch.n; ++q) ch.c[q] = all[base + (size_t)q];
-		const bool first = base == 0;
-		hipLaunchKernelGGL(k_splat_points<false>, pgrid, dim3(kSplatBlock), 0, st, g->dev(), ch, xyz, (unsigned)n, scale, acc, S, touched,
-		                   first ? (unsigned*)masks : nullptr, first ? status : nullptr, (unsigned long long*)d_rejected);
+	bool first = true;
+	for (const SplatChannels& ch : splat_passes(all, sp)) {  // (a channel's sum does not depend on the others: more launches change nothing numerically)
+		if (sp.kernel)
+			launch_splat_radial(st, g->dev(), ch, xyz, sp.d_radius, sp.radius, (unsigned)n, scale, acc, S, touched, first ? (unsigned*)masks : nullptr, first ? status : nullptr,
+			                    (unsigned long long*)d_rejected);
+		else
+			hipLaunchKernelGGL(k_splat_points<false>, pgrid, dim3(kSplatBlock), 0, st, g->dev(), ch, xyz, (unsigned)n, scale, acc, S, touched,
+			                   first ? (unsigned*)masks : nullptr, first ? status : nullptr, (unsigned long long*)d_rejected);
+		first = false;
 		switch (S) {
 		case 1: hipLaunchKernelGGL(k_splat_finish<1>, lgrid, dim3(256), 0, st, ch, acc, touched, n_leaves, quantum); break;
 		case 2: hipLaunchKernelGGL(k_splat_finish<2>, lgrid, dim3(256), 0, st, ch, acc, touched, n_leaves, quantum); break;
@@ -279,7 +277,7 @@ extern "C" {
 
 int hns_dev_splat_points(hns_grid* g, float* const* fields, const int* ncomp, int n_fields, const float* xyz, const float* const* values, uint64_t n, int log2_quantum,
                          unsigned char* status, uint64_t* d_rejected, void* stream) {
-	return splat_points("hns_dev_splat_points", g, fields, ncomp, n_fields, xyz, values, n, log2_quantum, nullptr, status, d_rejected, stream);
+	return splat_points("hns_dev_splat_points", g, g ? g->splat_spec : kDefaultSpec, fields, ncomp, n_fields, xyz, values, n, log2_quantum, nullptr, status, d_rejected, stream);
 }
 
 int hns_sim_splat_points(hns_sim* s, const char* const* names, int n_names, const float* velocity_values, const float* xyz, const float* const* values, uint64_t n,
@@ -308,8 +306,8 @@ int hns_sim_splat_points(hns_sim* s, const char* const* names, int n_names, cons
 	for (size_t i = 0; i < which.size(); ++i) fields.push_back(s->cur[(size_t)which[i]]), vals.push_back(values[i]), ncomp.push_back(1);
 	if (velocity_values) fields.push_back(s->vel), vals.push_back(velocity_values), ncomp.push_back(3);
 	if (fields.empty()) return refuse(who, "nothing to write (no names and velocity_values is null)");
-	HNS_TRY(splat_points(who, s->grid, fields.data(), ncomp.data(), (int)fields.size(), xyz, vals.data(), n, log2_quantum, activate ? s->d_masks : nullptr, status,
-	                     d_rejected, stream));
+	HNS_TRY(splat_points(who, s->grid, s->splat_spec, fields.data(), ncomp.data(), (int)fields.size(), xyz, vals.data(), n, log2_quantum, activate ? s->d_masks : nullptr,
+	                     status, d_rejected, stream));
 	if (n) {  // the written buffers no longer hold what a cook handed back; a rewritten velocity is not the one a substep looked ahead from
 		for (int k : which) s->handed_cur[(size_t)k] = hns_sim::Handed{};
 		if (velocity_values) s->forget(hns_sim::kVelocity);
@@ -317,61 +315,139 @@ int hns_sim_splat_points(hns_sim* s, const char* const* names, int n_names, cons
 	return HNS_OK;
 }
 
-// Host mirror: brute force, the same integers. One accumulator of n_voxels words, one component after the other.
-int hns_grid_splat_points(const hns_grid* g, float* const* fields, const int* ncomp, int n_fields, const float* xyz, const float* const* values, uint64_t n,
-                          int log2_quantum, unsigned char* masks, int activate, unsigned char* status, uint64_t* rejected) {
-	const char* who = "hns_grid_splat_points";
+int hns_grid_set_splat_spec(hns_grid* g, const hns_splat_spec* spec) {
+	const char* who = "hns_grid_set_splat_spec";
 	if (!g) return refuse(who, "null grid");
+	if (spec) HNS_TRY(check_splat_spec(who, *spec));
+	g->splat_spec = spec ? *spec : kDefaultSpec;
+	return HNS_OK;
+}
+
+int hns_sim_set_splat_spec(hns_sim* s, const hns_splat_spec* spec) {
+	const char* who = "hns_sim_set_splat_spec";
+	if (!s) return refuse(who, "null sim");
+	if (spec) HNS_TRY(check_splat_spec(who, *spec));
+	s->splat_spec = spec ? *spec : kDefaultSpec;
+	return HNS_OK;
+}
+
+int hns_grid_get_splat_spec(const hns_grid* g, hns_splat_spec* spec) {
+	if (!g || !spec) return refuse("hns_grid_get_splat_spec", "null grid or spec");
+	*spec = g->splat_spec;
+	return HNS_OK;
+}
+
+int hns_sim_get_splat_spec(const hns_sim* s, hns_splat_spec* spec) {
+	if (!s || !spec) return refuse("hns_sim_get_splat_spec", "null sim or spec");
+	*spec = s->splat_spec;
+	return HNS_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// Host mirror: brute force, the same integers. Every point's footprint as a list of (flat voxel or -1: did not land, weight), then one accumulator of n_voxels words, one
+// component after the other; average: the weight accumulator once (it is the same in every pass: a weight's term is always accepted).
+int splat_points_host(const char* who, const hns_grid* g, const hns_splat_spec* spec, float* const* fields, const int* ncomp, int n_fields, const float* xyz,
+                      const float* const* values, uint64_t n, int log2_quantum, unsigned char* masks, int activate, unsigned char* status, uint64_t* rejected) {
+	if (!g) return refuse(who, "null grid");
+	const hns_splat_spec sp = spec ? *spec : kDefaultSpec;
+	HNS_TRY(check_splat_spec(who, sp));
 	HNS_TRY(check_splat_lists(who, fields, ncomp, n_fields, values, n, log2_quantum));
 	if (n == 0) return HNS_OK;
 	HNS_TRY(check_splat_pointers(who, fields, n_fields, xyz, values, status, rejected));
 	HNS_TRY(hns_grid_host_tables(g));
 	const Topology& T = g->topo;
-	std::vector<int64_t> tap((size_t)n * 8);  // flat voxel index, -1: did not land
-	std::vector<float> weight((size_t)n * 8);
+	std::vector<size_t> first((size_t)n + 1, 0);  // point p's footprint: tap / weight [first[p], first[p + 1])
+	std::vector<int64_t> tap;
+	std::vector<float> weight;
 	for (uint64_t p = 0; p < n; ++p) {
 		const float* x = xyz + 3 * p;
-		const bool finite = std::isfinite(x[0]) && std::isfinite(x[1]) && std::isfinite(x[2]);
-		const int i = floor_sat(x[0]), j = floor_sat(x[1]), k = floor_sat(x[2]);
-		float w[8];
-		splat_weights(x[0] - (float)i, x[1] - (float)j, x[2] - (float)k, w);
-		int landed = 0;
-		for (int c = 0; c < 8; ++c) {  // (corner coordinates wrap at the end of the int32 range, as point_cell's do)
-			const int32_t ci = (int32_t)((uint32_t)i + (uint32_t)(c >> 2)), cj = (int32_t)((uint32_t)j + (uint32_t)((c >> 1) & 1)), ck = (int32_t)((uint32_t)k + (uint32_t)(c & 1));
-			const uint64_t off = finite ? T.offset(ci, cj, ck) : 0;
-			tap[8 * p + c] = (int64_t)off - 1;
-			weight[8 * p + c] = w[c];
-			if (!off) continue;
+		int in_footprint = 0, landed = 0;
+		auto candidate = [&](uint64_t off, float w) {
+			tap.push_back((int64_t)off - 1), weight.push_back(w);
+			++in_footprint;
+			if (!off) return;
 			++landed;
-			if (masks && activate && w[c] > 0.0f) masks[(off - 1) >> 3] |= (unsigned char)(1u << ((off - 1) & 7u));
+			if (masks && activate && w > 0.0f) masks[(off - 1) >> 3] |= (unsigned char)(1u << ((off - 1) & 7u));
+		};
+		if (sp.kernel) {
+			const float r = sp.d_radius ? sp.d_radius[p] : sp.radius;
+			if (radial_point(x[0], x[1], x[2], r, sp.radius)) {
+				const int E = radial_extent(r), i0 = radial_lo(x[0], r), j0 = radial_lo(x[1], r), k0 = radial_lo(x[2], r);
+				const float inv = radial_inv(r);
+				for (int i = i0; i < i0 + E; ++i)
+					for (int j = j0; j < j0 + E; ++j)
+						for (int k = k0; k < k0 + E; ++k) {
+							float w;
+							if (radial_weight((float)i - x[0], (float)j - x[1], (float)k - x[2], inv, &w)) candidate(T.offset(i, j, k), w);
+						}
+			}
+			if (status) status[p] = (unsigned char)(in_footprint > 0 && landed == in_footprint ? 2 : landed > 0 ? 1 : 0);
+		} else {
+			const bool finite = std::isfinite(x[0]) && std::isfinite(x[1]) && std::isfinite(x[2]);
+			const int i = floor_sat(x[0]), j = floor_sat(x[1]), k = floor_sat(x[2]);
+			float w[8];
+			splat_weights(x[0] - (float)i, x[1] - (float)j, x[2] - (float)k, w);
+			for (int c = 0; c < 8; ++c) {  // (corner coordinates wrap at the end of the int32 range, as point_cell's do)
+				const int32_t ci = (int32_t)((uint32_t)i + (uint32_t)(c >> 2)), cj = (int32_t)((uint32_t)j + (uint32_t)((c >> 1) & 1)), ck = (int32_t)((uint32_t)k + (uint32_t)(c & 1));
+				candidate(finite ? T.offset(ci, cj, ck) : 0, w[c]);
+			}
+			if (status) status[p] = (unsigned char)landed;
 		}
-		if (status) status[p] = (unsigned char)landed;
+		first[(size_t)p + 1] = tap.size();
 	}
 	const double scale = std::ldexp(1.0, -log2_quantum), quantum = std::ldexp(1.0, log2_quantum);
-	std::vector<uint64_t> acc((size_t)T.n_leaves * 512u);
+	std::vector<uint64_t> acc((size_t)T.n_leaves * 512u), acc_w;
 	uint64_t rej = 0;
+	// the sum of the accepted terms of one channel; val null: the weight channel (value 1.0f)
+	auto accumulate = [&](std::vector<uint64_t>& a, const float* val, uint64_t stride, uint64_t off) {
+		std::fill(a.begin(), a.end(), 0);
+		for (uint64_t p = 0; p < n; ++p) {
+			const float v = val ? val[p * stride + off] : 1.0f;
+			for (size_t e = first[(size_t)p]; e < first[(size_t)p + 1]; ++e) {
+				if (tap[e] < 0) continue;
+				long long k;
+				if (!splat_term(weight[e] * v, scale, &k))
+					++rej;
+				else
+					a[(size_t)tap[e]] += (uint64_t)k;
+			}
+		}
+	};
+	if (sp.mode) {
+		acc_w.resize(acc.size());
+		accumulate(acc_w, nullptr, 0, 0);
+	}
 	for (int f = 0; f < n_fields; ++f)
 		for (int comp = 0; comp < ncomp[f]; ++comp) {
-			std::fill(acc.begin(), acc.end(), 0);
-			for (uint64_t p = 0; p < n; ++p) {
-				const float v = values[f][p * (uint64_t)ncomp[f] + (uint64_t)comp];
-				for (int c = 0; c < 8; ++c) {
-					if (tap[8 * p + c] < 0) continue;
-					long long k;
-					if (!splat_term(weight[8 * p + c] * v, scale, &k))
-						++rej;
-					else
-						acc[(size_t)tap[8 * p + c]] += (uint64_t)k;
-				}
-			}
-			for (size_t e = 0; e < acc.size(); ++e)
-				if (acc[e]) {
-					float* dst = fields[f] + e * (size_t)ncomp[f] + (size_t)comp;
+			accumulate(acc, values[f], (uint64_t)ncomp[f], (uint64_t)comp);
+			for (size_t e = 0; e < acc.size(); ++e) {
+				float* dst = fields[f] + e * (size_t)ncomp[f] + (size_t)comp;
+				if (sp.mode) {
+					if (acc_w[e]) *dst = splat_average(acc[e], acc_w[e], quantum, sp.min_weight);
+				} else if (acc[e]) {
 					*dst = *dst + splat_total(acc[e], quantum);
 				}
+			}
 		}
 	if (rejected) *rejected += rej;
 	return HNS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int hns_grid_splat_points(const hns_grid* g, float* const* fields, const int* ncomp, int n_fields, const float* xyz, const float* const* values, uint64_t n,
+                          int log2_quantum, unsigned char* masks, int activate, unsigned char* status, uint64_t* rejected) {
+	return splat_points_host("hns_grid_splat_points", g, nullptr, fields, ncomp, n_fields, xyz, values, n, log2_quantum, masks, activate, status, rejected);
+}
+
+int hns_grid_splat_points_spec(const hns_grid* g, const hns_splat_spec* spec, float* const* fields, const int* ncomp, int n_fields, const float* xyz,
+                               const float* const* values, uint64_t n, int log2_quantum, unsigned char* masks, int activate, unsigned char* status, uint64_t* rejected) {
+	return splat_points_host("hns_grid_splat_points_spec", g, spec, fields, ncomp, n_fields, xyz, values, n, log2_quantum, masks, activate, status, rejected);
 }
 
 }  // extern "C"

@@ -13,7 +13,7 @@ import numpy as np
 
 from . import _lib, leafio
 from ._lib import hns_combustion_params, hns_field, lib
-from .api import CombustionParams, IndexGridHandle, _raise, create_grid_from_leaves  # noqa: F401
+from .api import CombustionParams, IndexGridHandle, _raise, create_grid_from_leaves, splat_spec, stored_splat_spec  # noqa: F401
 
 
 def _torch():
@@ -183,17 +183,30 @@ def _u64_ptr(t) -> int:
     return t.data_ptr()
 
 
-def splat_points(grid: IndexGridHandle, fields: Sequence, xyz, values: Sequence, log2_quantum: int = -32, status=None, rejected=None):
+def _radius_ptr(t, n) -> int:
+    if not t.is_cuda or t.dtype != _torch().float32 or not t.is_contiguous() or tuple(t.shape) != (n,):
+        raise TypeError("radius: expected a number or a contiguous float32 tensor of one radius per point on a HIP device")
+    return t.data_ptr()
+
+
+def splat_points(grid: IndexGridHandle, fields: Sequence, xyz, values: Sequence, log2_quantum: int = -32, status=None, rejected=None, *, kernel: str = "trilinear",
+                 mode: str = "add", radius=None, max_radius: Optional[float] = None, min_weight: float = 0.0):
     """The transpose of ``sample_points`` (``hns_dev_splat_points``): every point adds weight * value to the eight voxels of its cell, IN PLACE into `fields` -- up to
     eight (N,) float and (N, 3) Vec3f tensors in any mix -- from values[i], (n,) or (n, 3) like its field, at the positions xyz ((n, 3) float32, index space). Terms are
     rounded once to multiples of 2^log2_quantum and summed as 64-bit integers, so the result does not depend on the order the atomics retire in and equals
     ``api.splat_points_host`` in every byte. status: None or a uint8 tensor of n bytes, the taps of each point that landed in a leaf (0 .. 8); rejected: None or an int64
-    tensor of one element the call adds the number of landed but unaccepted terms to (NaN, inf, beyond 2^62 quanta). Asynchronous on the current stream."""
+    tensor of one element the call adds the number of landed but unaccepted terms to (NaN, inf, beyond 2^62 quanta). Asynchronous on the current stream.
+    kernel="radial": every point rasterises the footprint of `radius` voxels (0 < radius <= 4; a number, or a float32 device tensor of one radius per point with its
+    upper bound in `max_radius`) with the weights (1 - d^2/r^2)^2 (``hns_splat_spec`` in include/hns.h), and status is 2 (the whole footprint landed), 1 (a part) or 0.
+    mode="average": the fields are REPLACED by the weighted mean sum(w v) / max(sum(w), min_weight) wherever a weight arrived. The spec is stored with the grid for the call
+    and the previous one put back; a radius tensor must stay alive until the call has run."""
+    spec = splat_spec(kernel, mode, radius, max_radius, min_weight, pointer=lambda t: _radius_ptr(t, xyz.shape[0]))
     k = len(fields)
     dst = (C.c_void_p * max(1, k))(*[_ptr(t) for t in fields])
     src = (C.c_void_p * max(1, k))(*[_ptr(t) for t in values])
-    _raise(lib.hns_dev_splat_points(grid.ptr, dst, (C.c_int * max(1, k))(*[_ncomp(f) for f in fields]), k, _ptr(xyz), src, xyz.shape[0], int(log2_quantum),
-                                    _byte_ptr(status), _u64_ptr(rejected), current_stream()))
+    with stored_splat_spec(lib.hns_grid_set_splat_spec, lib.hns_grid_get_splat_spec, grid.ptr, spec):
+        _raise(lib.hns_dev_splat_points(grid.ptr, dst, (C.c_int * max(1, k))(*[_ncomp(f) for f in fields]), k, _ptr(xyz), src, xyz.shape[0], int(log2_quantum),
+                                        _byte_ptr(status), _u64_ptr(rejected), current_stream()))
     return fields
 
 
@@ -345,17 +358,21 @@ class Sim:
                                         current_stream() if stream is None else stream))
         return st
 
-    def splat(self, values: dict, xyz, velocity=None, log2_quantum: int = -32, activate: bool = True, status: bool = False, rejected=None, stream: Optional[int] = None):
+    def splat(self, values: dict, xyz, velocity=None, log2_quantum: int = -32, activate: bool = True, status: bool = False, rejected=None, stream: Optional[int] = None, *,
+              kernel: str = "trilinear", mode: str = "add", radius=None, max_radius: Optional[float] = None, min_weight: float = 0.0):
         """Point values added into the sim's own fields (``hns_sim_splat_points``, the arithmetic of ``splat_points``): values = {float field name: (n,) float32 device
         tensor}, velocity = None or an (n, 3) tensor added into the velocity, xyz the (n, 3) index-space positions. activate: on a sim that holds active masks, set the bit
         of every voxel a tap of positive weight landed on. Points outside the domain add no leaves: with `status` the uint8 tensor of landed taps per point (0 .. 8) is
-        returned. rejected: None or an int64 tensor of one element, as for ``splat_points``. Asynchronous on `stream` (None: the current stream)."""
+        returned. rejected: None or an int64 tensor of one element, as for ``splat_points``. kernel, mode, radius, max_radius, min_weight: as for ``splat_points`` (the
+        spec is stored with the sim for the call). Asynchronous on `stream` (None: the current stream)."""
+        spec = splat_spec(kernel, mode, radius, max_radius, min_weight, pointer=lambda t: _radius_ptr(t, xyz.shape[0]))
         names = list(values)
         st = _torch().empty(xyz.shape[0], dtype=_torch().uint8, device=xyz.device) if status else None
         arr = (C.c_char_p * max(1, len(names)))(*[k.encode() for k in names])
         src = (C.c_void_p * max(1, len(names)))(*[_ptr(values[k]) for k in names])
-        _raise(lib.hns_sim_splat_points(self._ptr, arr, len(names), _ptr(velocity), _ptr(xyz), src, xyz.shape[0], int(log2_quantum), int(bool(activate)),
-                                        _byte_ptr(st), _u64_ptr(rejected), current_stream() if stream is None else stream))
+        with stored_splat_spec(lib.hns_sim_set_splat_spec, lib.hns_sim_get_splat_spec, self._ptr, spec):
+            _raise(lib.hns_sim_splat_points(self._ptr, arr, len(names), _ptr(velocity), _ptr(xyz), src, xyz.shape[0], int(log2_quantum), int(bool(activate)),
+                                            _byte_ptr(st), _u64_ptr(rejected), current_stream() if stream is None else stream))
         return st
 
     def pressure_solve(self, iterations: int, voxel_size: float, stream: int = 0) -> None:
@@ -449,11 +466,22 @@ class Sim:
         self.grid = IndexGridHandle(ptr)
         return self.grid
 
-    def emit(self, values: dict, xyz, velocity=None, *, padding: int = 1, sdf=None, sources=None, log2_quantum: int = -32, rejected=None, stream: int = 0):
+    def emit(self, values: dict, xyz, velocity=None, *, padding: int = 1, sdf=None, sources=None, log2_quantum: int = -32, rejected=None, stream: int = 0,
+             kernel: Optional[str] = None, mode: str = "add", radius=None, max_radius: Optional[float] = None, min_weight: float = 0.0):
         """A point emitter's frame step without a host round trip: ``regrid(padding, sdf, sources, points=xyz)``, which makes room for every tap of every seeding point,
-        then ``splat(values, xyz, velocity, activate=True, status=True)`` on the new domain -> (the new grid, the uint8 status tensor: 8 for every seeding point)."""
+        then ``splat(values, xyz, velocity, activate=True, status=True)`` on the new domain -> (the new grid, the uint8 status tensor: 8 for every seeding point).
+        With a `radius` the splat is radial (kernel, mode, radius, max_radius, min_weight: as for ``splat``) and the status of every seeding point is 2; the seeds are still
+        the eight taps of each point's cell, and a footprint voxel lies within ceil(radius) voxels of that cell along every axis, so `padding` must be at least
+        ceil(the largest radius): the regrid's dilation by `padding` then covers the footprint. Anything less raises ValueError before anything runs."""
+        if kernel is None:
+            kernel = "trilinear" if radius is None else "radial"
+        if kernel == "radial":
+            bound = radius if isinstance(radius, (int, float, np.floating, np.integer)) else max_radius
+            if bound is None or not int(padding) >= int(np.ceil(float(bound))):
+                raise ValueError(f"emit: a radial splat needs padding >= ceil(the largest radius): padding {padding}, radius bound {bound}")
         grid = self.regrid(padding, sdf, sources, points=xyz, stream=stream)
-        status = self.splat(values, xyz, velocity, log2_quantum=log2_quantum, activate=True, status=True, rejected=rejected, stream=stream)
+        status = self.splat(values, xyz, velocity, log2_quantum=log2_quantum, activate=True, status=True, rejected=rejected, stream=stream, kernel=kernel, mode=mode,
+                            radius=radius, max_radius=max_radius, min_weight=min_weight)
         return grid, status
 
     def deactivate(self, tolerances: dict, velocity: Optional[float] = None, counts: bool = False, stream: int = 0):

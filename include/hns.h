@@ -622,6 +622,46 @@ int hns_dev_splat_points(hns_grid*, float* const* fields, const int* ncomp, int 
  * in which, with activate != 0, the bit of every landed tap with w > 0 is set. *rejected (or NULL) is ADDED to, as d_rejected is. Refusals as hns_dev_splat_points'. */
 int hns_grid_splat_points(const hns_grid*, float* const* fields, const int* ncomp, int n_fields, const float* xyz, const float* const* values, uint64_t n, int log2_quantum,
                           unsigned char* masks, int activate, unsigned char* status, uint64_t* rejected);
+/* POINTS RASTERISED INTO FIELDS: a radius footprint in place of the cell, and a weighted average in place of the sum. A spec stored with a grid is read by every later
+ * hns_dev_splat_points on that grid, one stored with a sim by every later hns_sim_splat_points (the sim keeps it across regrids); the calls themselves are unchanged, and
+ * with the default spec {0, 0, ..} they give the bytes, the launches and the accumulator they gave before there was a spec. Everything not restated here -- positions,
+ * landing, acceptance, the int64 sum, d_rejected, log2_quantum, the refusals -- is hns_dev_splat_points'. Every line below is one rounded f32 operation, none contracted;
+ * the divisions are correctly rounded.
+ *   Radial footprint (kernel 1) of a point x with radius r (r = d_radius[p] where d_radius is given, else spec.radius):
+ *     Which points rasterise  a point rasterises iff each coordinate satisfies the seeds' condition (hns_point_leaves: "Which points seed") AND 0 < r && r <= spec.radius
+ *                             (a NaN fails both). Any other point lands nowhere: status 0.
+ *     Box      per axis lo = Floor(x - r) + 1 and E = (int)ceilf(2.0f * r) <= 8; the candidates are lo .. lo + E - 1: at most two leaves per axis lie under them.
+ *     Weight   of candidate (i, j, k): dx = (float)i - x.x, likewise dy, dz; d2 = (dx*dx + dy*dy) + dz*dz; r2 = r*r; inv = 1.0f / r2; q = d2 * inv; the voxel is in the
+ *              footprint iff q < 1.0f, and then a = 1.0f - q, w = a * a. THE BOX IS PART OF THE DEFINITION: a voxel outside it is not in the footprint whatever its q.
+ *              Some 280 of the 512 candidates at r = 4; r = 1 at an integer position is that one voxel with w = 1.0f.
+ *     status   (radial calls) 2 iff the footprint is non-empty and every voxel of it landed, 1 iff some but not all landed, else 0. The trilinear 0 .. 8 is unchanged.
+ *     activate the mask bit of every landed footprint voxel with w > 0 is set, whether or not its terms were accepted (the trilinear rule).
+ *   Average (mode 1), with either kernel: every pass carries one more channel W whose term is w itself (t = w * 1.0f), put through the same acceptance and sum; a pass
+ *   holds up to three value channels and W, a call with more components runs more passes, each with its own W, so that output i still equals a call with field i alone.
+ *     Finish   every voxel whose W accumulator a_w is non-zero: Wsum = (float)((double)(int64)a_w * 2^Q), Vsum likewise from a_v, den = fmaxf(Wsum, min_weight),
+ *              field = Vsum / den, REPLACING the old value. A voxel with a_w == 0 keeps its bytes, even where an a_v is non-zero. All accumulators end zero either way.
+ *   So point values all equal to 1.0f average to exactly 1.0f wherever Wsum >= min_weight (the two accumulators are the same integer), and doubling every point leaves an
+ *   average unchanged bit for bit while no accumulator wraps (2 a_v / 2 a_w). The accumulator is sized for min(4, components + 1) channels in average mode.
+ *   On the device the radial kernel (hns_rasterize.hip) gives a group of 1, 4, 16 or 64 lanes to each point -- the square of ceil(2 * spec.radius) rounded up to a power of
+ *   two --, so that the adds of one wave instruction go to the contiguous accumulator pieces of z-runs; a spec.radius far above the radii in d_radius leaves lanes idle.
+ * The setters do no device work and refuse (HNS_ERR_INVALID_ARGUMENT, the stored spec unchanged): a null grid or sim, kernel or mode outside {0, 1}, radial with a radius
+ * that is NaN or outside (0, 4], d_radius with kernel 0, a min_weight that is negative or not finite. spec NULL stores the default. radius is ignored by
+ * kernel 0, min_weight by mode 0. d_radius is read by every later splat call, asynchronously: the caller keeps it alive. Not mirrored in hns_dist_*. */
+typedef struct hns_splat_spec {
+    int kernel;             /* 0 trilinear (the cell of hns_dev_splat_points), 1 radial */
+    int mode;               /* 0 add, 1 average */
+    float radius;           /* radial: the radius in voxels (index space), 0 < radius <= 4.0f; with d_radius: the caller's upper bound of it */
+    const float* d_radius;  /* radial: NULL, or n floats in device memory, one radius per point */
+    float min_weight;       /* average: finite, >= 0 */
+} hns_splat_spec;
+int hns_grid_set_splat_spec(hns_grid*, const hns_splat_spec* spec);
+int hns_sim_set_splat_spec(hns_sim*, const hns_splat_spec* spec);
+int hns_grid_get_splat_spec(const hns_grid*, hns_splat_spec* spec);
+int hns_sim_get_splat_spec(const hns_sim*, hns_splat_spec* spec);
+/* Host mirror of both splat calls under a spec (NULL: the default, and then this is hns_grid_splat_points): the arguments of hns_grid_splat_points behind the spec, whose
+ * d_radius is a HOST pointer here. The same integers, the same bytes. */
+int hns_grid_splat_points_spec(const hns_grid*, const hns_splat_spec* spec, float* const* fields, const int* ncomp, int n_fields, const float* xyz,
+                               const float* const* values, uint64_t n, int log2_quantum, unsigned char* masks, int activate, unsigned char* status, uint64_t* rejected);
 /* THE SEEDS OF A POINT SET: the leaves a point set needs in the domain so that every tap of every point lands (what hns_sim_regrid_seeded unites into the velocity's
  * topology, and with hns_grid_create_from_leaves a fresh grid around a particle set). xyz: n x 3 floats, index space, as for hns_dev_sample_points.
  *   Which points seed  a point seeds iff each coordinate c satisfies -8388608.0f <= c && c < 8388607.0f (NaN and +-inf fail): beyond 2^23 a float32 has no fraction, and
