@@ -78,6 +78,11 @@ class hns_splat_spec(C.Structure):
     _fields_ = [("kernel", C.c_int), ("mode", C.c_int), ("radius", C.c_float), ("d_radius", C.c_void_p), ("min_weight", C.c_float)]
 
 
+class hns_point_order_info(C.Structure):
+    _fields_ = [("perm", C.c_void_p), ("keys", C.c_void_p), ("leaf_start", C.c_void_p), ("n", C.c_uint64), ("n_leaves", C.c_uint64), ("capacity", C.c_uint64),
+                ("level", C.c_int)]
+
+
 class hns_combustion_params(C.Structure):
     _fields_ = [(n, C.c_float) for n in ("expansionRate", "temperatureRelease", "buoyancyStrength", "ambientTemp", "vorticityScale", "factorScale")]
 
@@ -176,6 +181,14 @@ SIGNATURES = {
                                         C.POINTER(C.c_uint64)]),
     "hns_point_leaves": (_i, [_fp, _u64, _vp, _vp, _u64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "hns_dev_point_leaves": (_i, [_i, _fp, _u64, _vp, _vp, _u64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), _vp]),
+    "hns_point_order_create": (_vp, [_vp, _u64, _ip]),
+    "hns_point_order_destroy": (None, [_vp]),
+    "hns_point_order_set_stream": (_i, [_vp, _vp]),
+    "hns_point_order_sort": (_i, [_vp, _fp, _u64, _i]),
+    "hns_point_order_get": (_i, [_vp, C.POINTER(hns_point_order_info)]),
+    "hns_point_order_gather": (_i, [_vp, _vp, _vp, _i]),
+    "hns_point_order_scatter": (_i, [_vp, _vp, _vp, _i]),
+    "hns_grid_sort_points": (_i, [_vp, _fp, _u64, _i, _vp, _vp, _vp]),
     "hns_dev_divergence": (_i, [_vp, _fp, _fp, _f, _vp]),
     "hns_dev_rbgs_color": (_i, [_vp, _fp, _fp, _f, _f, _i, _vp]),
     "hns_dev_rbgs_iterate": (_i, [_vp, _fp, _fp, _fp, _f, _f, _i, _ip, _vp]),

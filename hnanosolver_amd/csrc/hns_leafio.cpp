@@ -385,6 +385,44 @@ int hns_point_leaves(const float* xyz, uint64_t n, int32_t* origins_out, unsigne
 	return HNS_OK;
 }
 
+// The leaf order of a point set (include/hns.h states the definition): the keys by brute force over the topology's offsets, std::stable_sort, the ranges by counting.
+// What hns_point_order_sort (hns_pointorder.hip) is checked against, byte for byte.
+int hns_grid_sort_points(const hns_grid* g, const float* xyz, uint64_t n, int level, uint32_t* perm, uint32_t* keys, uint32_t* leaf_start) {
+	const char* who = "hns_grid_sort_points";
+	if (!g) return fail(HNS_ERR_INVALID_ARGUMENT, "hns_grid_sort_points: null grid");
+	if (n > kMaxSeedPoints) return fail(HNS_ERR_INVALID_ARGUMENT, "hns_grid_sort_points: n is above 2^31 - 1");
+	if (n && !xyz) return fail(HNS_ERR_INVALID_ARGUMENT, "hns_grid_sort_points: xyz is null");
+	if (n && !perm) return fail(HNS_ERR_INVALID_ARGUMENT, "hns_grid_sort_points: perm is null");
+	if (level != 0 && level != 1) {
+		set_error("%s: level %d (0: by leaf, 1: by voxel)", who, level);
+		return HNS_ERR_INVALID_ARGUMENT;
+	}
+	const uint64_t L = (uint64_t)g->topo.n_leaves;
+	if ((L + 2) * 512 > (uint64_t(1) << 32)) return fail(HNS_ERR_INVALID_ARGUMENT, "hns_grid_sort_points: the grid's voxel keys do not fit 32 bits ((leaves + 2) * 512 > 2^32)");
+	if (int rc = hns_grid_host_tables(g)) return rc;
+	std::vector<uint32_t> key((size_t)n);
+	std::vector<uint32_t> count((size_t)L + 3, 0);  // [q + 1]: points with leaf-level key q, then their running sum
+	for (uint64_t p = 0; p < n; ++p) {
+		const float* q = xyz + 3 * p;
+		uint32_t k = (uint32_t)(512 * (L + 1));
+		if (seeds_f(q[0]) && seeds_f(q[1]) && seeds_f(q[2])) {
+			const uint64_t off = g->topo.offset((int32_t)std::floor(q[0]), (int32_t)std::floor(q[1]), (int32_t)std::floor(q[2]));
+			k = off ? (uint32_t)(off - 1) : (uint32_t)(512 * L);
+		}
+		++count[(size_t)(k >> 9) + 1];
+		key[(size_t)p] = level ? k : k >> 9;
+	}
+	for (uint64_t p = 0; p < n; ++p) perm[p] = (uint32_t)p;
+	std::stable_sort(perm, perm + n, [&](uint32_t a, uint32_t b) { return key[a] < key[b]; });
+	if (keys)
+		for (uint64_t r = 0; r < n; ++r) keys[r] = key[perm[r]];
+	if (leaf_start) {
+		leaf_start[0] = 0;
+		for (uint64_t q = 1; q < L + 3; ++q) leaf_start[q] = leaf_start[q - 1] + count[(size_t)q];
+	}
+	return HNS_OK;
+}
+
 // topologyUnion of two leaf sets (SOP_HNanoSolver.cpp:189,195-197), in OpenVDB leaf order, duplicates removed.
 int hns_union_leaves(const int32_t* a, uint64_t na, const int32_t* b, uint64_t nb, int32_t* out_origins, uint64_t capacity, uint64_t* n_out) {
 	if ((na && !a) || (nb && !b)) return fail(HNS_ERR_INVALID_ARGUMENT, "hns_union_leaves: bad arguments");

@@ -229,6 +229,127 @@ def point_leaves(xyz):
         cap = int(m.value)
 
 
+POINT_ORDER_TILE = 2048        # points of one tile of the radix sort (hns_pointorder.hip: kOrderTile)
+POINT_ORDER_SCAN_TILES = 1024  # tiles one round of a scan workgroup covers (kScanChunk): beyond POINT_ORDER_TILE * POINT_ORDER_SCAN_TILES points the scan carries
+
+
+class _DeviceWords:
+    """`n` 32-bit words of device memory at `ptr` for ``torch.as_tensor``: a view, no copy; `owner` is kept alive with it"""
+
+    def __init__(self, ptr: int, n: int, owner):
+        self.owner = owner
+        self.__cuda_array_interface__ = {"shape": (int(n),), "typestr": "<i4", "data": (int(ptr), False), "strides": None, "version": 2}
+
+
+class PointOrder:
+    """The leaf order of a point set on the device (``hns_point_order``; include/hns.h states the definition): a stable sort of up to `capacity` points by the voxel -- or
+    the leaf -- of their cell on `grid`, the per-leaf ranges, and the moves that carry per-point rows through the permutation and back. The point kernels run some five
+    times faster on points in this order. Buffers come from the pool of device memory once, here; ``sort``, ``gather`` and ``scatter`` allocate nothing in the library
+    and are asynchronous on the stream of the last ``sort``. Holds the grid handle: the grid outlives the object."""
+
+    def __init__(self, grid: IndexGridHandle, capacity: int, _sim=None):
+        capacity = int(capacity)
+        if capacity < 0:
+            raise ValueError(f"PointOrder: capacity {capacity} is negative")
+        self.grid, self.capacity, self._sim, self._ptr = grid, capacity, _sim, 0
+        err = C.c_int(0)
+        self._ptr = lib.hns_point_order_create(grid.ptr, capacity, C.byref(err))
+        if not self._ptr:
+            _raise(err.value if err.value < 0 else _lib.HNS_ERR_RUNTIME)
+        self.n, self.level = 0, None
+
+    def _live(self) -> int:
+        if not self._ptr:
+            raise RuntimeError("PointOrder: the object is closed")
+        if self._sim is not None and self._sim.grid is not self.grid:
+            raise RuntimeError("PointOrder: the sim has moved onto another grid (regrid) since Sim.point_order made this object; make a new one on the sim's current grid")
+        return self._ptr
+
+    def sort(self, xyz, level="voxel", stream: Optional[int] = None):
+        """Sort the points xyz ((n, 3) float32 device tensor, index space, only read; n <= capacity) by "voxel" or by "leaf". stream: a hipStream_t as an integer, None = torch's
+        current stream; this call and every later ``gather`` / ``scatter`` are ordered on it and on nothing else. Returns self; ``perm``, ``keys`` and
+        ``leaf_start`` are the results."""
+        ptr, lv = self._live(), leafio.sort_level(level)
+        if xyz.dim() != 2 or xyz.shape[1] != 3 or xyz.dtype != _torch().float32:
+            raise ValueError("PointOrder.sort: xyz must be an (n, 3) float32 tensor")
+        n = int(xyz.shape[0])
+        if n > self.capacity:
+            raise ValueError(f"PointOrder.sort: {n} points are above the capacity {self.capacity}")
+        _raise(lib.hns_point_order_set_stream(ptr, current_stream() if stream is None else int(stream)))
+        _raise(lib.hns_point_order_sort(ptr, _ptr(xyz) if n else 0, n, lv))
+        self.n, self.level = n, ("voxel" if lv else "leaf")
+        return self
+
+    def _info(self):
+        info = _lib.hns_point_order_info()
+        _raise(lib.hns_point_order_get(self._live(), C.byref(info)))
+        return info
+
+    def _words(self, ptr, n):
+        if n == 0:
+            return _torch().empty(0, dtype=_torch().int32, device="cuda")
+        return _torch().as_tensor(_DeviceWords(ptr, n, self), device="cuda")
+
+    @property
+    def perm(self):
+        """perm[r]: the index in xyz of the point of rank r -- an int32 view of the object's buffer (n entries), valid until the next sort; no wait"""
+        info = self._info()
+        return self._words(info.perm, info.n)
+
+    @property
+    def keys(self):
+        """keys[r]: the key of point perm[r] at the sort's level -- a view of the uint32 words as int32, valid until the next sort; no wait"""
+        info = self._info()
+        return self._words(info.keys, info.n)
+
+    @property
+    def leaf_start(self):
+        """leaves + 3 entries: leaf q owns ranks leaf_start[q] .. leaf_start[q + 1]; [leaves] starts the outside points, [leaves + 1] the points that do not sort,
+        [leaves + 2] = n -- an int32 view, valid until the next sort; no wait"""
+        info = self._info()
+        return self._words(info.leaf_start, info.n_leaves + 3)
+
+    def _move(self, call, what, src, dst):
+        ptr, torch = self._live(), _torch()
+        if self.level is None:
+            raise RuntimeError(f"PointOrder.{what}: no sort has run on this object")
+        for name, t in (("src", src), ("dst", dst)):
+            if t is not None and (not t.is_cuda or not t.is_contiguous() or t.dim() < 1):
+                raise TypeError(f"PointOrder.{what}: {name} must be a contiguous tensor of at least one dimension on a HIP device")
+        row_bytes = src.element_size() * int(np.prod(src.shape[1:], dtype=np.int64))
+        if row_bytes % 4 or not 4 <= row_bytes <= 64:
+            raise ValueError(f"PointOrder.{what}: a row of src has {row_bytes} bytes (a multiple of 4 in 4 .. 64)")
+        if dst is None:
+            dst = torch.empty((self.n,) + tuple(src.shape[1:]), dtype=src.dtype, device=src.device)
+        if dst.dtype != src.dtype or tuple(dst.shape[1:]) != tuple(src.shape[1:]):
+            raise ValueError(f"PointOrder.{what}: dst rows are not src rows ({tuple(dst.shape[1:])} {dst.dtype} against {tuple(src.shape[1:])} {src.dtype})")
+        if src.shape[0] < self.n or dst.shape[0] < self.n:
+            raise ValueError(f"PointOrder.{what}: src has {src.shape[0]} rows and dst {dst.shape[0]}, the last sort {self.n}")
+        if self.n:
+            _raise(call(ptr, src.data_ptr(), dst.data_ptr(), row_bytes))
+        return dst
+
+    def gather(self, src, dst=None):
+        """dst row r = src row perm[r] for the n rows of the last sort -> dst (made here when None; rows of a longer dst beyond n keep their bytes). Rows are
+        src.shape[1:], 4 .. 64 bytes in whole 32-bit words. On the stream of the last sort."""
+        return self._move(lib.hns_point_order_gather, "gather", src, dst)
+
+    def scatter(self, src, dst=None):
+        """dst row perm[r] = src row r: the way back, ``scatter(gather(x)) == x``"""
+        return self._move(lib.hns_point_order_scatter, "scatter", src, dst)
+
+    def close(self) -> None:
+        if self._ptr:
+            lib.hns_point_order_destroy(self._ptr)
+            self._ptr = 0
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def stats_buffer(n_records: int = 1):
     """Device memory for `n_records` hns_stats records (a uint8 tensor; ``read_stats`` brings it to the host)."""
     return _torch().zeros(n_records * leafio.STATS_DTYPE.itemsize, dtype=_torch().uint8, device="cuda")
@@ -548,6 +669,11 @@ class Sim:
         out = (C.c_uint64 * max(1, n.value))()
         _raise(lib.hns_sim_solve_levels(self._ptr, C.byref(n), out, n.value))
         return [int(x) for x in out[: n.value]]
+
+    def point_order(self, capacity: int) -> PointOrder:
+        """A ``PointOrder`` for up to `capacity` points on the sim's CURRENT grid. After a ``regrid`` the sim is on another grid and the object refuses every call
+        (RuntimeError): make a new one."""
+        return PointOrder(self.grid, capacity, _sim=self)
 
     def regrid_times(self):
         """hipEvent split of the last regrid in ms: {candidates, host (origins, sort, grid tables), masks, fields}"""

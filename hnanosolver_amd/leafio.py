@@ -158,6 +158,33 @@ def point_leaves(xyz):
     return out, out_m, int(skipped.value)
 
 
+LEVELS = {"leaf": 0, "voxel": 1}  # what a point order sorts by (include/hns.h: "Level")
+
+
+def sort_level(level) -> int:
+    """"leaf" / "voxel" (or the ABI's 0 / 1) -> the ABI's level"""
+    if level in LEVELS:
+        return LEVELS[level]
+    if isinstance(level, (int, np.integer)) and not isinstance(level, bool) and int(level) in (0, 1):
+        return int(level)
+    raise ValueError(f'level must be "leaf" or "voxel" (0 or 1), got {level!r}')
+
+
+def sort_points(grid, xyz, level="voxel"):
+    """The leaf order of a point set (``hns_grid_sort_points``; include/hns.h states the definition): xyz (n, 3) float32, index space, on `grid` (a host-only grid will do)
+    -> (perm (n,) uint32: the stable order by voxel key, or by leaf with level="leaf"; keys (n,) uint32: the key of point perm[r]; leaf_start (leaves + 3,) uint32: the
+    ranks each leaf owns, then the outside points, then the points that do not sort, then n). The host mirror of ``device.PointOrder.sort``."""
+    lv = sort_level(level)
+    p = np.ascontiguousarray(xyz, dtype=np.float32)
+    if p.ndim != 2 or p.shape[1] != 3:
+        raise ValueError("sort_points: xyz must be an (n, 3) array")
+    n = len(p)
+    perm, keys = np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint32)
+    leaf_start = np.zeros(grid.leaf_count() + 3, dtype=np.uint32)
+    _lib.check(lib.hns_grid_sort_points(grid.ptr, p.ctypes.data if n else None, n, lv, perm.ctypes.data, keys.ctypes.data, leaf_start.ctypes.data))
+    return perm, keys, leaf_start
+
+
 def union_leaves(a, b) -> np.ndarray:
     a, b = _o(a), _o(b)
     n = C.c_uint64(0)
