@@ -188,6 +188,8 @@ SIGNATURES = {
     "hns_point_order_get": (_i, [_vp, C.POINTER(hns_point_order_info)]),
     "hns_point_order_gather": (_i, [_vp, _vp, _vp, _i]),
     "hns_point_order_scatter": (_i, [_vp, _vp, _vp, _i]),
+    "hns_point_order_splat": (_i, [_vp, C.POINTER(C.c_void_p), _ip, _i, _fp, C.POINTER(C.c_void_p), _i, _i, _vp, _vp]),
+    "hns_point_order_splat_sim": (_i, [_vp, _vp, C.POINTER(C.c_char_p), _i, _fp, _fp, C.POINTER(C.c_void_p), _i, _i, _i, _vp, _vp]),
     "hns_grid_sort_points": (_i, [_vp, _fp, _u64, _i, _vp, _vp, _vp]),
     "hns_dev_divergence": (_i, [_vp, _fp, _fp, _f, _vp]),
     "hns_dev_rbgs_color": (_i, [_vp, _fp, _fp, _f, _f, _i, _vp]),

@@ -293,27 +293,7 @@ inline unsigned order_tiles(uint64_t n) { return (unsigned)((n + kOrderTile - 1)
 
 using namespace hns;
 
-struct hns_point_order {
-	hns_grid* grid = nullptr;
-	int device = -1;
-	uint64_t capacity = 0, n_leaves = 0;
-	hipStream_t stream = nullptr;
-	// one pooled allocation: the results, the (key, index) ping-pong -- the keys of k_order_keys lie in kb: by the time a pass writes kb they are spent --, and the tables
-	void* arena = nullptr;
-	size_t arena_bytes = 0;
-	uint32_t *perm = nullptr, *keys = nullptr, *ka = nullptr, *ia = nullptr, *kb = nullptr, *ib = nullptr, *leaf_start = nullptr;
-	uint32_t *hist = nullptr, *total = nullptr;  // of the running pass: the [digit][tile] table and its row sums
-	uint64_t n = 0;
-	int level = -1;
-	bool sorted = false;
-};
-
-namespace {
-
-int check_order(const hns_point_order* o, const char* who) {
-	if (!o) return refuse(who, "null point order");
-	return check_grid(o->grid, who);
-}
+namespace {  // (struct hns_point_order and check_order: hns_points.hpp, shared with hns_splat_binned.hip)
 
 template <bool SCATTER>
 int move_rows(const hns_point_order* o, const void* d_src, void* d_dst, int row_bytes, const char* who) {

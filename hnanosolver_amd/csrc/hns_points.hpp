@@ -1,5 +1,5 @@
 // hns_points.hpp -- the trilinear cell under an index-space position, shared by the kernel files that work at points: hns_points.hip (fields read at points, points
-// traced through the velocity), hns_splat.hip (point values added into fields) and hns_rasterize.hip (the same with a radius). One statement of Floor, the tap indices and
+// traced through the velocity), hns_splat.hip (point values added into fields), hns_rasterize.hip (the same with a radius) and hns_splat_binned.hip (the same through a leaf order). One statement of Floor, the tap indices and
 // the fractions for both directions, and one of the splat's arithmetic -- weights, footprint, term, total, average -- for the kernels and the host mirror.
 #pragma once
 
@@ -157,10 +157,33 @@ __host__ __device__ inline float splat_average(unsigned long long a_v, unsigned 
 	return vsum / den;
 }
 
+// The finish rule, stated once for k_splat_finish, the leaf kernel of hns_splat_binned.hip and the host mirror. a_v: the channel's accumulator of a voxel; a_w: the weight
+// channel's (read in average mode only). The gate says whether the voxel changes at all: the channel's own accumulator, or W.
+__host__ __device__ inline unsigned long long splat_gate(int average, unsigned long long a_v, unsigned long long a_w) { return average ? a_w : a_v; }
+// what a voxel whose gate is non-zero becomes, `old` being what it holds
+__host__ __device__ inline float splat_finished(int average, float old, unsigned long long a_v, unsigned long long a_w, double quantum, float min_weight) {
+	return average ? splat_average(a_v, a_w, quantum, min_weight) : old + splat_total(a_v, quantum);
+}
+// one voxel of one channel: *f changes iff the gate is non-zero (every other voxel keeps its bytes: -0.0f stays)
+__host__ __device__ inline void splat_finish(int average, unsigned long long a_v, unsigned long long a_w, double quantum, float min_weight, float* f) {
+	if (splat_gate(average, a_v, a_w)) *f = splat_finished(average, *f, a_v, a_w, quantum, min_weight);
+}
+
 // hns_rasterize.hip: lanes of a group that share one point (1, 4, 16 or 64, from the spec's radius), and the radial kernel's launch in place of k_splat_points'
 int splat_radial_group(float radius);
 void launch_splat_radial(hipStream_t st, const GridDev& g, const SplatChannels& ch, const float* xyz, const float* radii, float bound, unsigned n, double scale,
                          unsigned long long* acc, int S, int* touched, unsigned* masks, unsigned char* status, unsigned long long* rejected);
+
+// hns_splat.hip: what its launcher shares with the ordered one of hns_splat_binned.hip -- the grid's pooled accumulator (int64 channels over all voxels, then a touched
+// word per leaf: all zero between calls), the refusals, the passes of a call and the field lists of a sim call
+size_t splat_acc_bytes(const hns_grid* g, int channels);
+int splat_accumulator(hns_grid* g, int channels, hipStream_t st);
+int check_splat_lists(const char* who, const void* fields, const int* ncomp, int n_fields, const void* values, uint64_t n, int log2_quantum);
+int check_splat_pointers(const char* who, float* const* fields, int n_fields, const float* xyz, const float* const* values, const void* status, const void* rejected);
+std::vector<SplatChannels> splat_passes(const std::vector<SplatChannel>& all, const hns_splat_spec& sp);
+int sim_splat_fields(const char* who, const hns_sim* s, const char* const* names, int n_names, const float* velocity_values, const float* const* values,
+                     std::vector<float*>& fields, std::vector<const float*>& vals, std::vector<int>& ncomp, std::vector<int>& which);
+void sim_splat_wrote(hns_sim* s, const std::vector<int>& which, bool velocity);
 
 // ---- launcher plumbing of the point calls ----
 
@@ -182,6 +205,31 @@ inline int check_sim(const hns_sim* s, const char* who) {
 	}
 	if (s->cached || s->in_use) return refuse(who, "the sim belongs to a grid's cook cache");
 	return HNS_OK;
+}
+
+}  // namespace hns
+
+// The leaf order of a point set (hns_pointorder.hip makes it; hns_splat_binned.hip reads perm, keys and leaf_start)
+struct hns_point_order {
+	hns_grid* grid = nullptr;
+	int device = -1;
+	uint64_t capacity = 0, n_leaves = 0;
+	hipStream_t stream = nullptr;
+	// one pooled allocation: the results, the (key, index) ping-pong -- the keys of k_order_keys lie in kb: by the time a pass writes kb they are spent --, and the tables
+	void* arena = nullptr;
+	size_t arena_bytes = 0;
+	uint32_t *perm = nullptr, *keys = nullptr, *ka = nullptr, *ia = nullptr, *kb = nullptr, *ib = nullptr, *leaf_start = nullptr;
+	uint32_t *hist = nullptr, *total = nullptr;  // of the running pass: the [digit][tile] table and its row sums
+	uint64_t n = 0;
+	int level = -1;
+	bool sorted = false;
+};
+
+namespace hns {
+
+inline int check_order(const hns_point_order* o, const char* who) {
+	if (!o) return refuse(who, "null point order");
+	return check_grid(o->grid, who);
 }
 
 }  // namespace hns

@@ -101,9 +101,9 @@ __global__ __launch_bounds__(256) void k_splat_finish(const SplatChannels ch, un
 			const SplatChannel e = ch.c[q];
 			unsigned long long gate[4];  // the accumulator that says whether voxel v0 + j changes: the channel's own, or W
 #pragma unroll
-			for (int j = 0; j < 4; ++j) gate[j] = ch.average ? x[j * S] : x[j * S + q];
+			for (int j = 0; j < 4; ++j) gate[j] = splat_gate(ch.average, x[j * S + q], x[j * S]);
 			if (!(gate[0] | gate[1] | gate[2] | gate[3])) continue;
-			auto value = [&](float old, int j) { return ch.average ? splat_average(x[j * S + q], x[j * S], quantum, ch.min_weight) : old + splat_total(x[j * S + q], quantum); };
+			auto value = [&](float old, int j) { return splat_finished(ch.average, old, x[j * S + q], x[j * S], quantum, ch.min_weight); };
 			if (e.wide) {
 				float4* f = reinterpret_cast<float4*>(e.field + v0);
 				float4 y = *f;
@@ -124,6 +124,10 @@ __global__ __launch_bounds__(256) void k_splat_finish(const SplatChannels ch, un
 	}
 	if (lane == 0) touched[leaf] = 0;
 }
+
+}  // namespace
+
+namespace hns {  // (hns_points.hpp declares what hns_splat_binned.hip shares: the accumulator, the checks, the passes, the sim's field lists)
 
 // ---- the accumulator -----------------------------------------------------------------------------------------------------------------------------------------------------
 
@@ -149,7 +153,7 @@ int splat_accumulator(hns_grid* g, int channels, hipStream_t st) {
 
 // ---- argument checks shared by the device call and the host mirror -------------------------------------------------------------------------------------------------------
 
-int invalid(const char* fmt, const char* who, int i = 0, int j = 0) {
+static int invalid(const char* fmt, const char* who, int i = 0, int j = 0) {
 	set_error(fmt, who, i, j);
 	return HNS_ERR_INVALID_ARGUMENT;
 }
@@ -168,7 +172,7 @@ int check_splat_lists(const char* who, const void* fields, const int* ncomp, int
 const hns_splat_spec kDefaultSpec = {0, 0, 0.0f, nullptr, 0.0f};
 
 // what the setters and the host mirror refuse in a spec
-int check_splat_spec(const char* who, const hns_splat_spec& sp) {
+static int check_splat_spec(const char* who, const hns_splat_spec& sp) {
 	if (sp.kernel != 0 && sp.kernel != 1) return invalid("%s: spec.kernel is %d (must be 0 trilinear or 1 radial)", who, sp.kernel);
 	if (sp.mode != 0 && sp.mode != 1) return invalid("%s: spec.mode is %d (must be 0 add or 1 average)", who, sp.mode);
 	if (sp.kernel == 1 && !(0.0f < sp.radius && sp.radius <= 4.0f)) return refuse(who, "spec.radius of a radial spec must lie in (0, 4]");
@@ -209,6 +213,41 @@ int check_splat_pointers(const char* who, float* const* fields, int n_fields, co
 	}
 	return HNS_OK;
 }
+
+// The field, value and component lists of a sim call (hns_sim_splat_points, hns_point_order_splat_sim) from its names: every refusal that is about the names. which: the
+// float fields the call writes
+int sim_splat_fields(const char* who, const hns_sim* s, const char* const* names, int n_names, const float* velocity_values, const float* const* values,
+                     std::vector<float*>& fields, std::vector<const float*>& vals, std::vector<int>& ncomp, std::vector<int>& which) {
+	if (n_names < 0) return refuse(who, "n_names is negative");
+	if (n_names > 0 && (!names || !values)) return refuse(who, "null list (names or values)");
+	for (int i = 0; i < n_names; ++i) {
+		const int k = names[i] ? s->find(names[i]) : -1;
+		if (k < 0) {
+			set_error("%s: names[%d]: no float field named '%s' in this sim", who, i, names[i] ? names[i] : "?");
+			return HNS_ERR_INVALID_ARGUMENT;
+		}
+		if (s->names[(size_t)k] == "collision_sdf") return invalid("%s: names[%d]: collision_sdf takes no point values (it comes from the collision input)", who, i);
+		if (std::find(which.begin(), which.end(), k) != which.end()) {
+			set_error("%s: names[%d]: field '%s' is listed twice", who, i, names[i]);
+			return HNS_ERR_INVALID_ARGUMENT;
+		}
+		which.push_back(k);
+	}
+	for (size_t i = 0; i < which.size(); ++i) fields.push_back(s->cur[(size_t)which[i]]), vals.push_back(values[i]), ncomp.push_back(1);
+	if (velocity_values) fields.push_back(s->vel), vals.push_back(velocity_values), ncomp.push_back(3);
+	if (fields.empty()) return refuse(who, "nothing to write (no names and velocity_values is null)");
+	return HNS_OK;
+}
+
+// a sim call with n > 0 has run: the written buffers no longer hold what a cook handed back; a rewritten velocity is not the one a substep looked ahead from
+void sim_splat_wrote(hns_sim* s, const std::vector<int>& which, bool velocity) {
+	for (int k : which) s->handed_cur[(size_t)k] = hns_sim::Handed{};
+	if (velocity) s->forget(hns_sim::kVelocity);
+}
+
+}  // namespace hns
+
+namespace {
 
 // ---- launcher --------------------------------------------------------------------------------------------------------------------------------------------------------------
 
@@ -284,34 +323,13 @@ int hns_sim_splat_points(hns_sim* s, const char* const* names, int n_names, cons
                          int log2_quantum, int activate, unsigned char* status, uint64_t* d_rejected, void* stream) {
 	const char* who = "hns_sim_splat_points";
 	if (int rc = check_sim(s, who)) return rc;
-	if (n_names < 0) return refuse(who, "n_names is negative");
-	if (n_names > 0 && (!names || !values)) return refuse(who, "null list (names or values)");
-	std::vector<int> which;
-	for (int i = 0; i < n_names; ++i) {
-		const int k = names[i] ? s->find(names[i]) : -1;
-		if (k < 0) {
-			set_error("%s: names[%d]: no float field named '%s' in this sim", who, i, names[i] ? names[i] : "?");
-			return HNS_ERR_INVALID_ARGUMENT;
-		}
-		if (s->names[(size_t)k] == "collision_sdf") return invalid("%s: names[%d]: collision_sdf takes no point values (it comes from the collision input)", who, i);
-		if (std::find(which.begin(), which.end(), k) != which.end()) {
-			set_error("%s: names[%d]: field '%s' is listed twice", who, i, names[i]);
-			return HNS_ERR_INVALID_ARGUMENT;
-		}
-		which.push_back(k);
-	}
 	std::vector<float*> fields;
 	std::vector<const float*> vals;
-	std::vector<int> ncomp;
-	for (size_t i = 0; i < which.size(); ++i) fields.push_back(s->cur[(size_t)which[i]]), vals.push_back(values[i]), ncomp.push_back(1);
-	if (velocity_values) fields.push_back(s->vel), vals.push_back(velocity_values), ncomp.push_back(3);
-	if (fields.empty()) return refuse(who, "nothing to write (no names and velocity_values is null)");
+	std::vector<int> ncomp, which;
+	HNS_TRY(sim_splat_fields(who, s, names, n_names, velocity_values, values, fields, vals, ncomp, which));
 	HNS_TRY(splat_points(who, s->grid, s->splat_spec, fields.data(), ncomp.data(), (int)fields.size(), xyz, vals.data(), n, log2_quantum, activate ? s->d_masks : nullptr,
 	                     status, d_rejected, stream));
-	if (n) {  // the written buffers no longer hold what a cook handed back; a rewritten velocity is not the one a substep looked ahead from
-		for (int k : which) s->handed_cur[(size_t)k] = hns_sim::Handed{};
-		if (velocity_values) s->forget(hns_sim::kVelocity);
-	}
+	if (n) sim_splat_wrote(s, which, velocity_values != nullptr);
 	return HNS_OK;
 }
 
@@ -423,14 +441,8 @@ int splat_points_host(const char* who, const hns_grid* g, const hns_splat_spec* 
 	for (int f = 0; f < n_fields; ++f)
 		for (int comp = 0; comp < ncomp[f]; ++comp) {
 			accumulate(acc, values[f], (uint64_t)ncomp[f], (uint64_t)comp);
-			for (size_t e = 0; e < acc.size(); ++e) {
-				float* dst = fields[f] + e * (size_t)ncomp[f] + (size_t)comp;
-				if (sp.mode) {
-					if (acc_w[e]) *dst = splat_average(acc[e], acc_w[e], quantum, sp.min_weight);
-				} else if (acc[e]) {
-					*dst = *dst + splat_total(acc[e], quantum);
-				}
-			}
+			for (size_t e = 0; e < acc.size(); ++e)
+				splat_finish(sp.mode, acc[e], sp.mode ? acc_w[e] : 0, quantum, sp.min_weight, fields[f] + e * (size_t)ncomp[f] + (size_t)comp);
 		}
 	if (rejected) *rejected += rej;
 	return HNS_OK;

@@ -231,6 +231,7 @@ def point_leaves(xyz):
 
 POINT_ORDER_TILE = 2048        # points of one tile of the radix sort (hns_pointorder.hip: kOrderTile)
 POINT_ORDER_SCAN_TILES = 1024  # tiles one round of a scan workgroup covers (kScanChunk): beyond POINT_ORDER_TILE * POINT_ORDER_SCAN_TILES points the scan carries
+SPLAT_ROWS = {"original": 0, "ranked": 1}  # the per-point arrays of an ordered splat: those the sort saw, or their gather (include/hns.h: hns_point_order_splat)
 
 
 class _DeviceWords:
@@ -337,6 +338,36 @@ class PointOrder:
     def scatter(self, src, dst=None):
         """dst row perm[r] = src row r: the way back, ``scatter(gather(x)) == x``"""
         return self._move(lib.hns_point_order_scatter, "scatter", src, dst)
+
+    def _splat_rows(self, what, rows, xyz, per_point) -> int:
+        """the ABI's `rows` of an ordered splat, after the checks that need no device: a sort has run, and every per-point array has the n rows of that sort"""
+        if rows not in SPLAT_ROWS:
+            raise ValueError(f'{what}: rows must be "original" (the arrays the sort saw) or "ranked" (their gather), got {rows!r}')
+        if self.level is None:
+            raise RuntimeError(f"{what}: no sort has run on this object")
+        if xyz.dim() != 2 or xyz.shape[1] != 3 or xyz.dtype != _torch().float32:
+            raise ValueError(f"{what}: xyz must be an (n, 3) float32 tensor")
+        for name, t in [("xyz", xyz), *per_point]:
+            if t is not None and t.shape[0] != self.n:
+                raise ValueError(f"{what}: {name} has {t.shape[0]} rows, the last sort {self.n}")
+        return SPLAT_ROWS[rows]
+
+    def splat(self, fields: Sequence, xyz, values: Sequence, log2_quantum: int = -32, status=None, rejected=None, *, rows: str = "original", kernel: str = "trilinear",
+              mode: str = "add", radius=None, max_radius: Optional[float] = None, min_weight: float = 0.0):
+        """``splat_points`` for the points of the last sort, through the order (``hns_point_order_splat``): each leaf's voxels are summed on chip by one workgroup and the
+        fields written with plain stores. The same bytes, status and rejected count as ``splat_points(self.grid, ...)`` of the same points. rows="original": xyz,
+        values, status and a radius tensor are the arrays the sort saw; rows="ranked": they are in sorted order (``gather``). xyz must hold the positions of the last
+        sort. Asynchronous on the stream of the last sort. A point set concentrated in a few leaves is summed by a few workgroups: ``splat_points`` is then faster."""
+        r = self._splat_rows("PointOrder.splat", rows, xyz, [(f"values[{i}]", v) for i, v in enumerate(values)] + [("status", status)])
+        ptr = self._live()
+        spec = splat_spec(kernel, mode, radius, max_radius, min_weight, pointer=lambda t: _radius_ptr(t, self.n))
+        k = len(fields)
+        dst = (C.c_void_p * max(1, k))(*[_ptr(t) for t in fields])
+        src = (C.c_void_p * max(1, k))(*[_ptr(t) for t in values])
+        with stored_splat_spec(lib.hns_grid_set_splat_spec, lib.hns_grid_get_splat_spec, self.grid.ptr, spec):
+            _raise(lib.hns_point_order_splat(ptr, dst, (C.c_int * max(1, k))(*[_ncomp(f) for f in fields]), k, _ptr(xyz) if self.n else 0, src, r, int(log2_quantum),
+                                             _byte_ptr(status), _u64_ptr(rejected)))
+        return fields
 
     def close(self) -> None:
         if self._ptr:
@@ -480,17 +511,34 @@ class Sim:
         return st
 
     def splat(self, values: dict, xyz, velocity=None, log2_quantum: int = -32, activate: bool = True, status: bool = False, rejected=None, stream: Optional[int] = None, *,
-              kernel: str = "trilinear", mode: str = "add", radius=None, max_radius: Optional[float] = None, min_weight: float = 0.0):
+              kernel: str = "trilinear", mode: str = "add", radius=None, max_radius: Optional[float] = None, min_weight: float = 0.0, order: Optional[PointOrder] = None,
+              rows: str = "original"):
         """Point values added into the sim's own fields (``hns_sim_splat_points``, the arithmetic of ``splat_points``): values = {float field name: (n,) float32 device
         tensor}, velocity = None or an (n, 3) tensor added into the velocity, xyz the (n, 3) index-space positions. activate: on a sim that holds active masks, set the bit
         of every voxel a tap of positive weight landed on. Points outside the domain add no leaves: with `status` the uint8 tensor of landed taps per point (0 .. 8) is
         returned. rejected: None or an int64 tensor of one element, as for ``splat_points``. kernel, mode, radius, max_radius, min_weight: as for ``splat_points`` (the
-        spec is stored with the sim for the call). Asynchronous on `stream` (None: the current stream)."""
-        spec = splat_spec(kernel, mode, radius, max_radius, min_weight, pointer=lambda t: _radius_ptr(t, xyz.shape[0]))
+        spec is stored with the sim for the call). Asynchronous on `stream` (None: the current stream).
+        order: a ``PointOrder`` on the sim's grid whose last sort saw these points: the call goes through it (``hns_point_order_splat_sim``: leaves summed on chip, the
+        same bytes, masks and status) on the stream of that sort -- `stream` must then be None --; rows as for ``PointOrder.splat``."""
         names = list(values)
+        if order is None:
+            if rows != "original":
+                raise ValueError("Sim.splat: rows is about an order; without one the arrays are what they are")
+        else:
+            if stream is not None:
+                raise ValueError("Sim.splat: an order runs on the stream of its last sort; pass no stream with it")
+            if order.grid is not self.grid:
+                raise ValueError("Sim.splat: the order was made on another grid than the sim's current one")
+            r = order._splat_rows("Sim.splat", rows, xyz, [(k, values[k]) for k in names] + [("velocity", velocity)])
+        spec = splat_spec(kernel, mode, radius, max_radius, min_weight, pointer=lambda t: _radius_ptr(t, xyz.shape[0]))
         st = _torch().empty(xyz.shape[0], dtype=_torch().uint8, device=xyz.device) if status else None
         arr = (C.c_char_p * max(1, len(names)))(*[k.encode() for k in names])
         src = (C.c_void_p * max(1, len(names)))(*[_ptr(values[k]) for k in names])
+        if order is not None:
+            with stored_splat_spec(lib.hns_sim_set_splat_spec, lib.hns_sim_get_splat_spec, self._ptr, spec):
+                _raise(lib.hns_point_order_splat_sim(order._live(), self._ptr, arr, len(names), _ptr(velocity), _ptr(xyz) if order.n else 0, src, r, int(log2_quantum),
+                                                     int(bool(activate)), _byte_ptr(st), _u64_ptr(rejected)))
+            return st
         with stored_splat_spec(lib.hns_sim_set_splat_spec, lib.hns_sim_get_splat_spec, self._ptr, spec):
             _raise(lib.hns_sim_splat_points(self._ptr, arr, len(names), _ptr(velocity), _ptr(xyz), src, xyz.shape[0], int(log2_quantum), int(bool(activate)),
                                             _byte_ptr(st), _u64_ptr(rejected), current_stream() if stream is None else stream))

@@ -725,6 +725,33 @@ typedef struct hns_point_order_info {
 int hns_point_order_get(const hns_point_order*, hns_point_order_info*);
 int hns_point_order_gather(const hns_point_order*, const void* d_src, void* d_dst, int row_bytes);
 int hns_point_order_scatter(const hns_point_order*, const void* d_src, void* d_dst, int row_bytes);
+/* POINT VALUES INTO FIELDS THROUGH A LEAF ORDER: hns_dev_splat_points / hns_sim_splat_points for the n points of the object's last sort, with each leaf's voxels summed in
+ * LDS by one workgroup and the fields written with plain stores, in place of one global atomic per term. The new path is selected by calling it: the plain calls are
+ * unchanged. fields, ncomp, n_fields, values, log2_quantum, status and d_rejected are those of hns_dev_splat_points; names, n_names, velocity_values and activate those of
+ * hns_sim_splat_points; n is the n of the last sort. The device form reads the spec stored with the object's grid, the sim form the sim's: the radial kernel and the
+ * average mode run under the same specs. No stream argument: like sort, gather and scatter the calls run on the stream bound to the object.
+ *   rows      how the per-point arrays -- d_xyz, every values[i], spec.d_radius, status -- are laid out. 0 (original): row perm[r] belongs to rank r; these are the arrays
+ *             the sort saw. 1 (ranked): row r belongs to rank r; the caller has gathered them with hns_point_order_gather and keeps its attributes in sorted order.
+ *   Contract  the positions are, bit for bit, those of the last sort (rows = 1: its gather). Then every field holds exactly the bytes hns_dev_splat_points
+ *             (hns_sim_splat_points) leaves for the same points in their original order, with either kernel and either mode; the increment of *d_rejected is the same;
+ *             status is the same under the row mapping; with activate the sim's masks are the same. With other positions WHICH terms are added is unspecified; every
+ *             access still stays inside the caller's n rows and the grid's voxels.
+ *   Tail      the ranks from leaf_start[L] on -- points whose cell's leaf is absent, points that do not sort -- can still land (a cell in an absent leaf next to an
+ *             existing one; a finite trilinear point beyond 2^23). A per-point kernel adds their terms into the grid's accumulator with integer atomics, as the plain calls
+ *             do, BEFORE the leaf kernel, which adds a touched leaf's piece of the accumulator into its sums: a voxel reached by a tail point and a binned point gets one
+ *             sum and one rounded add. The host never waits for the length of the tail. status, where asked for, comes from the same kernel walking every rank.
+ *   Leaves    one workgroup per leaf Q walks the ranks of the leaves whose points can reach Q (trilinear: the eight leaves Q - {0,1}^3; radial: all 27 neighbours, since
+ *             with r <= 4 a box lies under its point's leaf and that leaf's neighbours), recomputes each point's candidates and keeps those inside Q. Every
+ *             (point, tap, channel) term is evaluated by exactly one workgroup, rejected terms are counted there. Both sort levels give the same bytes.
+ * Asynchronous on the object's stream. Allocates nothing beyond the grid's pooled splat accumulator (which the plain calls draw too) and leaves it and the touched words all
+ * zero: plain and ordered calls may alternate on one grid, on one stream. n == 0 launches nothing. One workgroup per destination leaf: a point set concentrated in a few
+ * leaves is summed by a few workgroups, and the plain calls are then the faster ones. Refused before anything is launched (HNS_ERR_INVALID_ARGUMENT, the call and the
+ * argument in the message), everything untouched: whatever the corresponding plain call refuses; a null object; a call before any sort; rows outside {0, 1}; a sim whose grid
+ * is not the object's grid. Not mirrored in hns_dist_*. */
+int hns_point_order_splat(const hns_point_order*, float* const* fields, const int* ncomp, int n_fields, const float* d_xyz, const float* const* values, int rows,
+                          int log2_quantum, unsigned char* status, uint64_t* d_rejected);
+int hns_point_order_splat_sim(const hns_point_order*, hns_sim*, const char* const* names, int n_names, const float* velocity_values, const float* d_xyz,
+                              const float* const* values, int rows, int log2_quantum, int activate, unsigned char* status, uint64_t* d_rejected);
 /* Host mirror of hns_point_order_sort: xyz and the outputs are HOST arrays -- perm n entries, keys (or NULL) n entries, leaf_start (or NULL) L + 3 entries --, plain C++
  * around std::stable_sort over hns_grid_offsets-style lookups; works on HNS_GRID_HOST_ONLY grids. The same bytes as the device's. Refusals as above, and a null perm
  * with n > 0. */
