@@ -83,6 +83,14 @@ class hns_point_order_info(C.Structure):
                 ("level", C.c_int)]
 
 
+class hns_birth_spec(C.Structure):
+    _fields_ = [("threshold", C.c_float), ("rate", C.c_float), ("max_per_voxel", C.c_uint32), ("seed", C.c_uint32), ("fill", C.c_int)]
+
+
+class hns_point_population_info(C.Structure):
+    _fields_ = [("slot", C.c_void_p), ("counters", C.c_void_p), ("n", C.c_uint64), ("capacity", C.c_uint64)]
+
+
 class hns_combustion_params(C.Structure):
     _fields_ = [(n, C.c_float) for n in ("expansionRate", "temperatureRelease", "buoyancyStrength", "ambientTemp", "vorticityScale", "factorScale")]
 
@@ -191,6 +199,17 @@ SIGNATURES = {
     "hns_point_order_splat": (_i, [_vp, C.POINTER(C.c_void_p), _ip, _i, _fp, C.POINTER(C.c_void_p), _i, _i, _vp, _vp]),
     "hns_point_order_splat_sim": (_i, [_vp, _vp, C.POINTER(C.c_char_p), _i, _fp, _fp, C.POINTER(C.c_void_p), _i, _i, _i, _vp, _vp]),
     "hns_grid_sort_points": (_i, [_vp, _fp, _u64, _i, _vp, _vp, _vp]),
+    "hns_point_population_create": (_vp, [_vp, _u64, _ip]),
+    "hns_point_population_destroy": (None, [_vp]),
+    "hns_point_population_set_stream": (_i, [_vp, _vp]),
+    "hns_point_population_set_live": (_i, [_vp, _u64]),
+    "hns_point_population_select": (_i, [_vp, _vp, _u64, _i]),
+    "hns_point_population_compact": (_i, [_vp, _vp, _vp, _i, C.POINTER(C.c_uint32)]),
+    "hns_point_population_birth": (_i, [_vp, _fp, _vp, C.POINTER(hns_birth_spec), _fp, _vp, _u64, _i]),
+    "hns_point_population_birth_sim": (_i, [_vp, _vp, C.c_char_p, _i, C.POINTER(hns_birth_spec), _fp, _vp, _u64, _i]),
+    "hns_point_population_get": (_i, [_vp, C.POINTER(hns_point_population_info)]),
+    "hns_point_population_counts": (_i, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "hns_grid_birth_points": (_i, [_vp, _fp, _vp, C.POINTER(hns_birth_spec), _u64, _fp, _vp, _u64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "hns_dev_divergence": (_i, [_vp, _fp, _fp, _f, _vp]),
     "hns_dev_rbgs_color": (_i, [_vp, _fp, _fp, _f, _f, _i, _vp]),
     "hns_dev_rbgs_iterate": (_i, [_vp, _fp, _fp, _fp, _f, _f, _i, _ip, _vp]),

@@ -15,6 +15,7 @@
 #include <unordered_map>
 #include <unordered_set>
 
+#include "hns_birth.hpp"
 #include "hns_dilate.hpp"
 #include "hns_originhash.hpp"
 #include "hns_seed.hpp"
@@ -420,6 +421,51 @@ int hns_grid_sort_points(const hns_grid* g, const float* xyz, uint64_t n, int le
 		leaf_start[0] = 0;
 		for (uint64_t q = 1; q < L + 3; ++q) leaf_start[q] = leaf_start[q - 1] + count[(size_t)q];
 	}
+	return HNS_OK;
+}
+
+// Points born from a field (include/hns.h: "BIRTH AND DEATH OF POINTS"): voxel by voxel in index order, the count and the positions of hns_birth.hpp. What
+// hns_point_population_birth (hns_population.hip) is checked against, byte for byte.
+int hns_grid_birth_points(const hns_grid* g, const float* field, const unsigned char* masks, const hns_birth_spec* sp, uint64_t start, float* xyz, uint32_t* voxel,
+                          uint64_t capacity_rows, uint64_t* live, uint64_t* wanted) {
+	const char* who = "hns_grid_birth_points";
+	auto refused = [&](const char* what) {
+		set_error("%s: %s", who, what);
+		return HNS_ERR_INVALID_ARGUMENT;
+	};
+	if (!g) return refused("null grid");
+	if (const char* what = birth_spec_refusal(sp)) return refused(what);
+	if (capacity_rows > kMaxSeedPoints) return refused("capacity_rows is above 2^31 - 1");
+	if (start > kMaxSeedPoints) return refused("start is above 2^31 - 1");
+	const uint64_t L = (uint64_t)g->topo.n_leaves;
+	if (L * 512 > (uint64_t(1) << 32)) return refused("the grid's voxel indices do not fit 32 bits (leaves * 512 > 2^32)");
+	if (L && !field) return refused("null field");
+	if (capacity_rows && !xyz) return refused("null xyz");
+	if (xyz && ((const void*)xyz == (const void*)field || (const void*)xyz == (const void*)voxel)) return refused("xyz is field or voxel");
+	uint64_t row = start;
+	for (uint64_t l = 0; l < L; ++l) {
+		const int32_t* o = &g->topo.origins[4 * (size_t)l];
+		for (uint32_t v = 0; v < 512; ++v) {
+			const int i = o[0] + (int)(v >> 6), j = o[1] + (int)((v >> 3) & 7), k = o[2] + (int)(v & 7);
+			const uint64_t e = 512 * l + v;
+			uint32_t h = 0;
+			const uint32_t c = birth_count(field[e], !masks || (masks[64 * l + (v >> 3)] >> (v & 7) & 1), i, j, k, *sp, &h);
+			for (uint32_t q = 0; q < c; ++q, ++row) {
+				if (row >= capacity_rows) continue;
+				xyz[3 * row] = birth_position(i, h, q, 0), xyz[3 * row + 1] = birth_position(j, h, q, 1), xyz[3 * row + 2] = birth_position(k, h, q, 2);
+				if (voxel) voxel[row] = (uint32_t)e;
+			}
+		}
+	}
+	const uint64_t alive = std::min(row, capacity_rows);
+	if (sp->fill)
+		for (uint64_t r = alive; r < capacity_rows; ++r) {
+			const uint32_t nan = kBirthNaN;
+			for (int a = 0; a < 3; ++a) memcpy(&xyz[3 * r + a], &nan, 4);
+			if (voxel) voxel[r] = kBirthNoVoxel;
+		}
+	if (live) *live = alive;
+	if (wanted) *wanted = row;
 	return HNS_OK;
 }
 

@@ -14,6 +14,7 @@
 //   k_order_rows     gather / scatter of rows of 1 .. 16 words through perm: adjacent lanes take adjacent words of a row
 // No kernel waits on another workgroup: every dependence is a launch boundary. The only atomics are integer adds in LDS (a tile's histogram counts: sums of integers, unique
 // whatever the order); no float atomics, no scratch. Every index below is bounded by n < 2^31 and by the tile: the histograms count exactly the points the scatter places.
+#include "hns_blockscan.hpp"
 #include "hns_points.hpp"
 
 namespace hns {
@@ -27,6 +28,7 @@ constexpr int kRadix = 256;                               // 8-bit digits; one d
 constexpr int kScanItems = 4;                             // table entries per thread and round of k_order_scan
 constexpr int kScanChunk = kOrderBlock * kScanItems;      // 1024 tiles per round: device.POINT_ORDER_SCAN_TILES
 static_assert(kRadix == kOrderBlock, "k_order_scan and k_order_scatter give every digit one thread");
+static_assert(kOrderBlock == kBlockScanThreads && kOrderWaves == kBlockScanWaves, "block_scan (hns_blockscan.hpp) scans a workgroup of this size");
 
 // LDS per kernel, stated and held
 constexpr int kLdsKeys = kRadix * 4;                                                                        // k_order_keys, k_order_hist: the tile's histogram
@@ -96,29 +98,6 @@ __global__ __launch_bounds__(kOrderBlock) void k_order_hist(const unsigned* __re
 	}
 	__syncthreads();
 	hist_store(s_hist, hist, n_tiles);
-}
-
-// exclusive prefix of v over the workgroup's 256 threads and, in every thread, the sum; s_wave: kOrderWaves words nobody else uses between the call's two barriers
-__device__ __forceinline__ unsigned block_scan(unsigned v, unsigned* s_wave, unsigned& sum) {
-	const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-	unsigned incl = v;
-#pragma unroll
-	for (int d = 1; d < 64; d <<= 1) {
-		const unsigned up = (unsigned)__shfl_up((int)incl, d);
-		if (lane >= d) incl += up;
-	}
-	__syncthreads();  // (the previous call's reads of s_wave are over)
-	if (lane == 63) s_wave[w] = incl;
-	__syncthreads();
-	unsigned before = 0;
-	sum = 0;
-#pragma unroll
-	for (int k = 0; k < kOrderWaves; ++k) {
-		const unsigned c = s_wave[k];
-		before += k < w ? c : 0u;
-		sum += c;
-	}
-	return before + incl - v;
 }
 
 // total[d] = the sum of row d of the table: how many points hold digit d. One workgroup per digit, a plain store (512 k atomic adds of the tiles into 256 words took

@@ -381,6 +381,134 @@ class PointOrder:
             pass
 
 
+POINT_POPULATION_TILE = 2048        # items -- points of a select, voxels of a birth -- of one tile (hns_population.hip: kPopTile)
+POINT_POPULATION_SCAN_TILES = 1024  # tiles one round of the scan workgroup covers (kPopScanChunk): beyond POINT_POPULATION_TILE * POINT_POPULATION_SCAN_TILES items the scan carries
+
+
+class PointPopulation:
+    """Birth and death of points on the device (``hns_point_population``; include/hns.h states the rules): ``select`` turns a flag byte per point into a slot per kept
+    point, ``compact`` moves the rows of any attribute array through the slots, ``birth`` makes points from a field -- 0 .. max_per_voxel per voxel --, and the live count
+    stays on the device: nothing here waits for the host but ``counts``. A frame loop keeps calling every point kernel with n = capacity; the rows beyond the live count
+    hold NaN positions, which those kernels treat as nothing. Buffers come from the pool of device memory once, here. ``select``, ``birth`` and ``set_live`` bind the
+    stream they are given (None: torch's current stream); ``compact`` runs on the stream bound last. Holds the grid handle: the grid outlives the object."""
+
+    def __init__(self, grid: IndexGridHandle, capacity: int, _sim=None):
+        capacity = int(capacity)
+        if capacity < 0:
+            raise ValueError(f"PointPopulation: capacity {capacity} is negative")
+        self.grid, self.capacity, self._sim, self._ptr = grid, capacity, _sim, 0
+        err = C.c_int(0)
+        self._ptr = lib.hns_point_population_create(grid.ptr, capacity, C.byref(err))
+        if not self._ptr:
+            _raise(err.value if err.value < 0 else _lib.HNS_ERR_RUNTIME)
+        self.n = None  # of the last select
+
+    def _live(self) -> int:
+        if not self._ptr:
+            raise RuntimeError("PointPopulation: the object is closed")
+        if self._sim is not None and self._sim.grid is not self.grid:
+            raise RuntimeError("PointPopulation: the sim has moved onto another grid (regrid) since Sim.point_population made this object; make a new one on the sim's current grid")
+        return self._ptr
+
+    def _bind(self, stream) -> int:
+        ptr = self._live()
+        _raise(lib.hns_point_population_set_stream(ptr, current_stream() if stream is None else int(stream)))
+        return ptr
+
+    def set_live(self, n: int, stream: Optional[int] = None):
+        """live = wanted = n, on the stream: for a caller that already holds n rows"""
+        _raise(lib.hns_point_population_set_live(self._bind(stream), int(n)))
+        return self
+
+    def select(self, flags, at_least: int = 1, stream: Optional[int] = None):
+        """Point i of the n = len(flags) points (a uint8 device tensor, only read; n <= capacity) is kept iff flags[i] >= at_least: the status of ``trace_points`` or of a
+        splat is such a flag. Afterwards ``slot`` holds, per point, its row among the kept ones or -1, and live = the number kept. Returns self."""
+        n = int(flags.shape[0])
+        if flags.dim() != 1:
+            raise ValueError("PointPopulation.select: flags must be a one-dimensional uint8 tensor")
+        if n > self.capacity:
+            raise ValueError(f"PointPopulation.select: {n} points are above the capacity {self.capacity}")
+        _raise(lib.hns_point_population_select(self._bind(stream), _byte_ptr(flags) if n else 0, n, int(at_least)))
+        self.n = n
+        return self
+
+    @property
+    def slot(self):
+        """slot[i]: the row of point i among the kept ones, -1 for a dropped point -- an int32 view of the object's buffer (the n of the last select), valid until the
+        next select; no wait"""
+        info = _lib.hns_point_population_info()
+        _raise(lib.hns_point_population_get(self._live(), C.byref(info)))
+        if info.n == 0:
+            return _torch().empty(0, dtype=_torch().int32, device="cuda")
+        return _torch().as_tensor(_DeviceWords(info.slot, info.n, self), device="cuda")
+
+    def compact(self, src, dst=None, fill=None):
+        """dst row slot[i] = src row i for every point the last select kept -> dst (made here, n rows, when None). Rows are src.shape[1:], 4 .. 64 bytes in whole 32-bit
+        words. fill: None -- the rows of dst from the live count on keep their bytes --, or a float (its float32 bits) or an int (a 32-bit word) that every word of the rows
+        live .. n - 1 becomes: ``fill=float("nan")`` for positions. Rows of a longer dst beyond n are never touched. On the stream bound last."""
+        ptr, torch = self._live(), _torch()
+        if self.n is None:
+            raise RuntimeError("PointPopulation.compact: no select has run on this object")
+        for name, t in (("src", src), ("dst", dst)):
+            if t is not None and (not t.is_cuda or not t.is_contiguous() or t.dim() < 1):
+                raise TypeError(f"PointPopulation.compact: {name} must be a contiguous tensor of at least one dimension on a HIP device")
+        row_bytes = src.element_size() * int(np.prod(src.shape[1:], dtype=np.int64))
+        if row_bytes % 4 or not 4 <= row_bytes <= 64:
+            raise ValueError(f"PointPopulation.compact: a row of src has {row_bytes} bytes (a multiple of 4 in 4 .. 64)")
+        if dst is None:
+            dst = torch.empty((self.n,) + tuple(src.shape[1:]), dtype=src.dtype, device=src.device)
+        if dst.dtype != src.dtype or tuple(dst.shape[1:]) != tuple(src.shape[1:]):
+            raise ValueError(f"PointPopulation.compact: dst rows are not src rows ({tuple(dst.shape[1:])} {dst.dtype} against {tuple(src.shape[1:])} {src.dtype})")
+        if src.shape[0] < self.n or dst.shape[0] < self.n:
+            raise ValueError(f"PointPopulation.compact: src has {src.shape[0]} rows and dst {dst.shape[0]}, the last select {self.n}")
+        word = None
+        if fill is not None:
+            bits = int(np.float32(fill).view(np.uint32)) if isinstance(fill, (float, np.floating)) else int(fill) & 0xFFFFFFFF
+            word = C.byref(C.c_uint32(bits))
+        if self.n:
+            _raise(lib.hns_point_population_compact(ptr, src.data_ptr(), dst.data_ptr(), row_bytes, word))
+        return dst
+
+    @staticmethod
+    def _birth_rows(what, xyz, voxel):
+        torch = _torch()
+        if xyz.dim() != 2 or xyz.shape[1] != 3 or xyz.dtype != torch.float32:
+            raise ValueError(f"{what}: xyz must be a (rows, 3) float32 tensor")
+        rows = int(xyz.shape[0])
+        if voxel is not None and (voxel.dtype != torch.int32 or tuple(voxel.shape) != (rows,)):
+            raise ValueError(f"{what}: voxel must be an int32 tensor of one word per row of xyz")
+        return rows, (_ptr(xyz) if rows else 0), (_ptr(voxel) if voxel is not None and rows else 0)
+
+    def birth(self, field, xyz, masks=None, voxel=None, *, threshold: float, rate: float, max_per_voxel: int, seed: int, append: bool = False, fill: bool = True,
+              stream: Optional[int] = None):
+        """Points from a field: every voxel of `field` ((voxels,) float32 on the object's grid) above `threshold` -- and, with masks ((leaves, 64) uint8 device tensor), active
+        -- bears min(value * rate, max_per_voxel) points, the fraction rounded up with that probability by a hash of the voxel's coordinates and `seed`, at hashed positions
+        inside the voxel, in voxel order, into the rows of xyz ((rows, 3) float32) from the live count on (append) or from 0; voxel (None or (rows,) int32) receives each
+        birth's flat voxel index. Rows at or beyond len(xyz) are dropped; ``counts`` tells (live, wanted). fill: the rows from the live count on become NaN / -1. Equal in
+        every byte to ``leafio.birth_points``. Returns self."""
+        rows, px, pv = self._birth_rows("PointPopulation.birth", xyz, voxel)
+        spec = leafio.birth_spec(threshold, rate, max_per_voxel, seed, fill)
+        _raise(lib.hns_point_population_birth(self._bind(stream), _ptr(field), _byte_ptr(masks), C.byref(spec), px, pv, rows, int(bool(append))))
+        return self
+
+    def counts(self):
+        """(live, wanted): waits for the bound stream. wanted above live: the last birth did not fit its rows"""
+        live, wanted = C.c_uint64(0), C.c_uint64(0)
+        _raise(lib.hns_point_population_counts(self._live(), C.byref(live), C.byref(wanted)))
+        return int(live.value), int(wanted.value)
+
+    def close(self) -> None:
+        if self._ptr:
+            lib.hns_point_population_destroy(self._ptr)
+            self._ptr = 0
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def stats_buffer(n_records: int = 1):
     """Device memory for `n_records` hns_stats records (a uint8 tensor; ``read_stats`` brings it to the host)."""
     return _torch().zeros(n_records * leafio.STATS_DTYPE.itemsize, dtype=_torch().uint8, device="cuda")
@@ -722,6 +850,22 @@ class Sim:
         """A ``PointOrder`` for up to `capacity` points on the sim's CURRENT grid. After a ``regrid`` the sim is on another grid and the object refuses every call
         (RuntimeError): make a new one."""
         return PointOrder(self.grid, capacity, _sim=self)
+
+    def point_population(self, capacity: int) -> PointPopulation:
+        """A ``PointPopulation`` for up to `capacity` points on the sim's CURRENT grid. After a ``regrid`` the sim is on another grid and the object refuses every call
+        (RuntimeError): make a new one."""
+        return PointPopulation(self.grid, capacity, _sim=self)
+
+    def birth(self, population: PointPopulation, name: str, xyz, voxel=None, *, threshold: float, rate: float, max_per_voxel: int, seed: int, append: bool = False,
+              fill: bool = True, use_masks: bool = True, stream: Optional[int] = None):
+        """``PointPopulation.birth`` from the sim's own float field `name` and, with use_masks, its active masks (``hns_point_population_birth_sim``): embers where
+        "flame" is high, markers where "fuel" is. The population must be on the sim's current grid. Asynchronous on `stream` (None: the current stream)."""
+        if population.grid is not self.grid:
+            raise ValueError("Sim.birth: the population was made on another grid than the sim's current one")
+        rows, px, pv = population._birth_rows("Sim.birth", xyz, voxel)
+        spec = leafio.birth_spec(threshold, rate, max_per_voxel, seed, fill)
+        _raise(lib.hns_point_population_birth_sim(population._bind(stream), self._ptr, name.encode(), int(bool(use_masks)), C.byref(spec), px, pv, rows, int(bool(append))))
+        return population
 
     def regrid_times(self):
         """hipEvent split of the last regrid in ms: {candidates, host (origins, sort, grid tables), masks, fields}"""

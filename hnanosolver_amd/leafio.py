@@ -185,6 +185,35 @@ def sort_points(grid, xyz, level="voxel"):
     return perm, keys, leaf_start
 
 
+def birth_spec(threshold, rate, max_per_voxel, seed, fill=True) -> _lib.hns_birth_spec:
+    """the ABI's hns_birth_spec (include/hns.h: "BIRTH AND DEATH OF POINTS"); the library refuses what is outside the rule"""
+    return _lib.hns_birth_spec(float(threshold), float(rate), int(max_per_voxel), int(seed) & 0xFFFFFFFF, int(bool(fill)))
+
+
+def birth_points(grid, field, masks=None, *, threshold, rate, max_per_voxel, seed, fill=True, start=0, capacity_rows, xyz=None, voxel=None):
+    """Points born from a field (``hns_grid_birth_points``; include/hns.h states the rule): field (voxels,) float32 on `grid` (a host-only grid will do), masks None or
+    (leaves, 64) uint8. Every eligible voxel bears 0 .. max_per_voxel points, in voxel order, into rows start .. of xyz ((capacity_rows, 3) float32) and voxel
+    ((capacity_rows,) uint32), made here (zeroed) when None -> (xyz, voxel, live, wanted): wanted = start + the births, live = min(wanted, capacity_rows); with fill the
+    rows live .. capacity_rows - 1 are NaN / 0xFFFFFFFF. The host mirror of ``device.PointPopulation.birth``."""
+    f = np.ascontiguousarray(field, dtype=np.float32).reshape(-1)
+    if f.size != grid.leaf_count() * 512:
+        raise ValueError(f"birth_points: the field has {f.size} values, the grid {grid.leaf_count() * 512} voxels")
+    m = None if masks is None else np.ascontiguousarray(masks, dtype=np.uint8).reshape(-1)
+    if m is not None and m.size != grid.leaf_count() * 64:
+        raise ValueError(f"birth_points: masks need {grid.leaf_count()} x 64 bytes, got {m.size}")
+    rows = int(capacity_rows)
+    xyz = np.zeros((rows, 3), dtype=np.float32) if xyz is None else xyz
+    voxel = np.zeros(rows, dtype=np.uint32) if voxel is None else voxel
+    for name, a, shape, dt in (("xyz", xyz, (rows, 3), np.float32), ("voxel", voxel, (rows,), np.uint32)):
+        if a.dtype != dt or tuple(a.shape) != shape or not a.flags["C_CONTIGUOUS"]:
+            raise ValueError(f"birth_points: {name} must be a C-contiguous {np.dtype(dt).name} array of shape {shape}")
+    spec = birth_spec(threshold, rate, max_per_voxel, seed, fill)
+    live, wanted = C.c_uint64(0), C.c_uint64(0)
+    _lib.check(lib.hns_grid_birth_points(grid.ptr, f.ctypes.data, None if m is None else m.ctypes.data, C.byref(spec), int(start), xyz.ctypes.data if rows else None,
+                                         voxel.ctypes.data if rows else None, rows, C.byref(live), C.byref(wanted)))
+    return xyz, voxel, int(live.value), int(wanted.value)
+
+
 def union_leaves(a, b) -> np.ndarray:
     a, b = _o(a), _o(b)
     n = C.c_uint64(0)

@@ -756,6 +756,73 @@ int hns_point_order_splat_sim(const hns_point_order*, hns_sim*, const char* cons
  * around std::stable_sort over hns_grid_offsets-style lookups; works on HNS_GRID_HOST_ONLY grids. The same bytes as the device's. Refusals as above, and a null perm
  * with n > 0. */
 int hns_grid_sort_points(const hns_grid*, const float* xyz, uint64_t n, int level, uint32_t* perm, uint32_t* keys, uint32_t* leaf_start);
+/* BIRTH AND DEATH OF POINTS: a stream of items, each with a small count c, expanded into sum(c) rows in item order, with the counts kept on the device. Death is c in
+ * {0, 1} per point (select, then compact of every attribute array); birth is c in {0 .. K} per voxel of a field. A frame loop -- trace, drop the dead, append the newborn,
+ * splat -- then runs without a host wait: the host keeps calling every point kernel with n = capacity, and the rows beyond the live count hold NaN positions, which the
+ * point calls above treat as nothing (they land nowhere, they do not sort, their status is 0).
+ *   Object    hns_point_population is modelled on hns_point_order: create draws every buffer from the pool of device memory -- slot, `capacity` uint32 words; one count word
+ *             per tile of 2048 items for max(capacity, voxels of the grid) items; the two uint64 counters {live, wanted} --, destroy returns them. It refers to its grid,
+ *             which must outlive it. live = wanted = 0 after create. set_stream binds the stream (the null stream before); set_live, select, compact, birth and birth_sim are
+ *             asynchronous on that stream and on nothing else, allocate nothing, and launch nothing whose length depends on data: the host never learns a count unless it
+ *             asks. counts waits for the stream and returns the two counters (either pointer may be NULL). set_live(n) sets live = wanted = n on the stream, for a caller
+ *             that already holds n rows. get fills the info with DEVICE pointers -- slot, and counters[0] = live, counters[1] = wanted -- and the n of the last select; no wait.
+ *   Select    point i < n is kept iff d_flags[i] >= at_least, at_least in 1 .. 255 (the status bytes of hns_dev_trace_points and of the splat calls are such flags).
+ *             slot[i] = the number of kept points below i, or 0xFFFFFFFF for a dropped point. live = wanted = the number kept. n == 0 sets both to 0 and launches no kernel.
+ *   Compact   for the n and the slot of the last select: dst row slot[i] = src row i for every kept i, rows of row_bytes bytes, a multiple of 4 in 4 .. 64 as for
+ *             hns_point_order_gather. The move is stable, so the result is unique. With fill_word != NULL every 32-bit word of rows live .. n - 1 of dst becomes *fill_word,
+ *             which the host reads at the call; with fill_word == NULL those rows keep their bytes. Rows of dst from n on are never touched. d_src != d_dst. One select
+ *             serves any number of compacts: one per attribute array.
+ *   Birth     the device form visits every leaf of the object's grid, whatever its launch range. A voxel has the flat index e = leaf * 512 + (x<<6 | y<<3 | z) and the
+ *             global coordinates (i, j, k) = origin + (x, y, z). d_field: one float per voxel; d_masks: NULL, or leaf_count x 64 bytes.
+ *     Eligible  all of: d_masks == NULL or the voxel's bit is set (byte x*8+y, bit z: the layout of hns_sim_active_masks); v = field[e] satisfies v > threshold (a NaN
+ *               fails); each coordinate c satisfies -8388608 <= c && c <= 8388606, so that every birth meets the seeds' condition of hns_point_leaves.
+ *     Hash      H(x): x ^= x>>16; x *= 0x7feb352d; x ^= x>>15; x *= 0x846ca68b; x ^= x>>16, on uint32. h = H(H(H(H(seed ^ 0x9E3779B9) ^ (uint32)i) ^ (uint32)j) ^ (uint32)k).
+ *               Draw d is r(d) = H(h + d), and U(d) = (float)(r(d) >> 8) * 2^-24, exact. The draws depend on the voxel's coordinates and the seed only, never on the leaf
+ *               numbering: the same voxel bears the same points on any grid that holds it.
+ *     Count     m = fmaxf(0.0f, fminf(v * rate, (float)K)) with one rounded multiply, K = max_per_voxel in 1 .. 16; b = (uint32)m; f = m - (float)b;
+ *               c = b + (U(0) < f ? 1 : 0). A voxel that is not eligible has c = 0.
+ *     Position  of point q < c, per axis a in {0, 1, 2} with the voxel's coordinate i along it: p = (float)i + U(1 + 3q + a), one rounded add; if !(p < (float)(i + 1))
+ *               then p = nextafterf((float)(i + 1), -inf). So Floor(p) == i always.
+ *     Order     start = append ? live : 0. Point q of voxel e takes row start + sum of c(e') over e' < e + q. Rows at or beyond capacity_rows are not written: a prefix
+ *               survives, so the result is unique. d_xyz row = p; d_voxel row (d_voxel may be NULL) = e. Afterwards wanted = start + sum(c) and
+ *               live = min(wanted, capacity_rows). With spec.fill != 0, rows live .. capacity_rows - 1 of d_xyz are NaN (0x7FC00000 in every word) and those of d_voxel are
+ *               0xFFFFFFFF. Rows below start are untouched.
+ *   birth_sim reads the sim's float field `name` and, with use_masks != 0, the sim's own masks (a sim without masks: every voxel). The sim's grid must be the object's grid.
+ *   hns_grid_birth_points is the host mirror, plain C++ over HOST arrays with `start` given by the caller; works on HNS_GRID_HOST_ONLY grids and gives the same bytes;
+ *   *live and *wanted (either may be NULL) are set.
+ * On the device (hns_population.hip) both are count, scan, place over tiles of 2048 items: a count kernel writes one word per tile, one workgroup scans the tile table and
+ * writes the counters, a place kernel recomputes its tile's counts, ranks them in index order and writes slot, or the rows; a row kernel moves and fills. No kernel waits on
+ * another workgroup, and there is no atomic at all.
+ * Refused with HNS_ERR_INVALID_ARGUMENT (the call and the argument in the message) before anything is launched, nothing touched: a null object, a null grid, a null array
+ * with n > 0 (flags, src, dst; the field, the spec; d_xyz with capacity_rows > 0); n > capacity; a capacity, n or capacity_rows above 2^31 - 1; an at_least outside
+ * 1 .. 255; a row_bytes outside the rule; d_src == d_dst; compact before any select; a K outside 1 .. 16; a rate or a threshold that is not finite, or a rate <= 0; d_xyz
+ * equal to d_field or to d_voxel; a sim of another grid, or an unknown field name; an HNS_GRID_HOST_ONLY grid at create; a grid of more than 2^32 voxels.
+ * HNS_ERR_NO_DEVICE where there is no HIP device. Not mirrored in hns_dist_*. */
+typedef struct hns_point_population hns_point_population;
+hns_point_population* hns_point_population_create(hns_grid*, uint64_t capacity, int* err);
+void hns_point_population_destroy(hns_point_population*);
+int hns_point_population_set_stream(hns_point_population*, void* hip_stream);
+int hns_point_population_set_live(hns_point_population*, uint64_t n);
+int hns_point_population_select(hns_point_population*, const unsigned char* d_flags, uint64_t n, int at_least);
+int hns_point_population_compact(const hns_point_population*, const void* d_src, void* d_dst, int row_bytes, const uint32_t* fill_word);
+typedef struct hns_birth_spec {
+    float threshold, rate;         /* both finite, rate > 0 */
+    uint32_t max_per_voxel, seed;  /* K in 1 .. 16 */
+    int fill;                      /* != 0: the rows live .. capacity_rows - 1 become NaN / 0xFFFFFFFF */
+} hns_birth_spec;
+int hns_point_population_birth(hns_point_population*, const float* d_field, const unsigned char* d_masks, const hns_birth_spec*, float* d_xyz, uint32_t* d_voxel,
+                               uint64_t capacity_rows, int append);
+int hns_point_population_birth_sim(hns_point_population*, hns_sim*, const char* name, int use_masks, const hns_birth_spec*, float* d_xyz, uint32_t* d_voxel,
+                                   uint64_t capacity_rows, int append);
+typedef struct hns_point_population_info {
+    const uint32_t* slot;      /* n entries (device) */
+    const uint64_t* counters;  /* {live, wanted} (device) */
+    uint64_t n, capacity;
+} hns_point_population_info;
+int hns_point_population_get(const hns_point_population*, hns_point_population_info*);
+int hns_point_population_counts(hns_point_population*, uint64_t* live, uint64_t* wanted);
+int hns_grid_birth_points(const hns_grid*, const float* field, const unsigned char* masks, const hns_birth_spec*, uint64_t start, float* xyz, uint32_t* voxel,
+                          uint64_t capacity_rows, uint64_t* live, uint64_t* wanted);
 /* divergence / divergence_opt (Kernel.cu:455-519) */
 int hns_dev_divergence(hns_grid*, const float* vel3, float* div, float inv_dx, void* stream);
 /* One colour of redBlackGaussSeidelUpdate(_opt) in place (Kernel.cu:521-623): the two-launch form. */
