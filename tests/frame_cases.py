@@ -1,5 +1,7 @@
 """The frame loop's test cases, shared by the regrid, source, deactivation and pool-content tests: mask packing, random leaf sets, masks, fields and sources,
 device sims, the host chain every device regrid must match byte for byte, and a device-resident sim's frame loop against that chain continued on the host."""
+import contextlib
+
 import numpy as np
 
 from hnanosolver_amd import api, device, leafio
@@ -174,6 +176,28 @@ def make_sources(seed, origins, kind, where):
             m = random_masks(seed + 7, len(o)) if name == "density" else None  # (masks of a float source do not enter the domain)
             out[name] = (o, m, with_negative_zeros(rng, rng.standard_normal(len(o) * 512).astype(np.float32)))
     return out
+
+
+LAUNCH_RANGES = ("inner", "half")
+
+
+@contextlib.contextmanager
+def launch_range(grid, kind):
+    """the grid's launch range narrowed for the block, the whole range back afterwards (also after a failure) -- "inner": set_active_range on a strict inner range,
+    leaves left out at either end; "half": set_active_leaves(n // 2). The point calls count every leaf whatever the range (include/hns.h): ghost leaves included."""
+    n = grid.leaf_count()
+    edge = max(1, n // 5)
+    assert n >= 4 and 0 < edge and edge + (n - 2 * edge) < n
+    if kind == "inner":
+        grid.set_active_range(edge, n - 2 * edge)
+    else:
+        assert kind == "half"
+        grid.set_active_leaves(n // 2)
+    assert grid.active_leaves() == (n - 2 * edge if kind == "inner" else n // 2)
+    try:
+        yield
+    finally:
+        grid.set_active_range(0, n)
 
 
 def emitter(R, frame):

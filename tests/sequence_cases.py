@@ -1,0 +1,1106 @@
+"""TEST HELPER of tests/test_sequence_cases.py (CPU) and tests/test_sequences_gpu.py: mixed call sequences on ONE device-resident sim against a twin with no hidden state.
+
+A sim and the point objects that hang off it carry state between calls. Some of it is semantic -- include/hns.h documents it as the sim's or the object's state -- and
+the rest is memo: the look-ahead, the feedback signatures, `solved` and p_result, the multigrid hierarchy, the lazily made tables, the buffer roles that swap under
+every call, the grid's pooled splat accumulator, an order's permutation and a population's slots. A stale memo gives plausible numbers and no fault.
+
+  OPS       the vocabulary: one entry per call that changes or reads that state, a function (world, rng) -> outputs with the resources it reads and writes, the
+            library symbols it goes through, what it needs from the script before it, and what it does to the look-ahead memo.
+  World     the device side of a script: the sim, the points, one PointOrder and one PointPopulation.
+  resident  ONE World from the first step to the last (the order and the population made anew only after a step that moves the sim onto another grid).
+  twin      a NEW World for every step, built from nothing but the semantic state (`World.capture`), run with lookahead = 0 and the pool filled with a non-zero byte.
+  SCRIPTS   the committed scripts: explicit lists of (operation, seed). `draw_scripts` is the seeded generator they were drawn with; a red script is rerun and cut
+            down by hand with `compare(script, mode, upto=...)`.
+
+Every comparison is equality of bytes: every path involved is documented as bit-identical to its stateless form. Where a memo may rightly live or die without moving a
+byte -- hns_sim_deactivate drops the look-ahead although the velocity stays -- the table's memo column predicts hns_sim_lookahead_counts under lookahead = 1
+(`expected_lookahead`), and the resident pass is held to it step by step. Everything runs on the null stream."""
+from __future__ import annotations
+
+import ctypes as C
+import functools
+from typing import NamedTuple
+
+import numpy as np
+
+import frame_cases as fc
+
+F = np.float32
+DT = float(F(1.0 / 24.0))  # of every substep, advect and trace of every script: "two substeps of equal dt and voxel size" is then any two substeps
+VS = 1.0 / 32
+ITERS = 3
+N_POINTS = 1500
+TWIN_FILLS = (0x7F, 0xFF)  # the pool's fill byte during the twin's pass, by the parity of the step: a finite 3.39e38 and a NaN
+PROFILES = {"combust": list(fc.COMBUST), "collide": list(fc.COMBUST) + ["collision_sdf"], "one": ["density"]}
+
+# ---- resources ---------------------------------------------------------------------------------------------------------------------------------------------------
+
+ALL_FIELDS = tuple("f:" + n for n in PROFILES["collide"])
+ADVECTED = tuple("f:" + n for n in fc.COMBUST)
+RESOURCES = ("vel", "masks", "grid", "scratch", "splat_spec", "solve_method", "solve_control", "points", "order", "live") + ALL_FIELDS
+SOLVE = ("solve_method", "solve_control", "grid")  # what every pressure solve reads besides its right-hand side (the hierarchy is a memo of grid and method)
+
+
+class Op(NamedTuple):
+    kind: str
+    fn: object
+    reads: frozenset
+    writes: frozenset
+    symbols: tuple
+    needs: frozenset     # float fields the sim must hold
+    requires: frozenset  # "order": a sort since the last change of grid; "fresh_order": and no write of the positions since
+    grid: bool           # moves the sim onto another grid
+    memo: str            # what the call does to the look-ahead memo under lookahead = 1: "produce" (consumes a live one, leaves one), "consume" (consumes a live one,
+                         # leaves none), "drop", or "keep"
+    same_points: bool    # writes the point arrays with the bytes they held (scatter of gather)
+
+    @property
+    def breaks(self):
+        out = set()
+        if self.grid:
+            out |= {"order", "fresh_order"}
+        if "points" in self.writes and not self.same_points:
+            out.add("fresh_order")
+        return frozenset(out)
+
+
+OPS = {}
+
+
+def op(kind, reads=(), writes=(), symbols=(), needs=(), requires=(), grid=False, memo="keep", same_points=False):
+    def register(fn):
+        w = set(writes) | ({"grid", "scratch"} if grid else set())
+        OPS[fn.__name__] = Op(kind, fn, frozenset(reads), frozenset(w), tuple(symbols), frozenset(needs), frozenset(requires), grid, memo, same_points)
+        return fn
+
+    return register
+
+
+# the symbols the two runners and World go through themselves, whatever the script
+RUNNER_SYMBOLS = ("hns_sim_create", "hns_sim_destroy", "hns_sim_upload", "hns_sim_download", "hns_sim_set_active_masks", "hns_sim_active_masks", "hns_sim_get_splat_spec",
+                  "hns_sim_set_splat_spec", "hns_sim_set_solve_method", "hns_sim_set_solve_control", "hns_sim_lookahead_counts", "hns_sim_timing", "hns_sim_pressure_time",
+                  "hns_sim_stage_timing", "hns_sim_stage_times", "hns_point_order_create", "hns_point_order_destroy", "hns_point_order_set_stream", "hns_point_order_get",
+                  "hns_point_order_sort", "hns_point_population_create", "hns_point_population_destroy", "hns_point_population_set_stream", "hns_point_population_set_live",
+                  "hns_point_population_get", "hns_point_population_counts")
+
+EXEMPT = {
+    "hns_sim_velocity_ptr": "switches the look-ahead off for good by contract, so no memo is left to go stale behind it; test_lookahead_gpu holds that contract",
+    "hns_sim_substep_plan": "its text names the memo by design (advect_vector=memo), so a resident sim and a twin differ in it rightly; test_kernel_variants_gpu reads it",
+    "hns_point_order_splat": "writes caller-owned tensors and no sim buffer: there is no sim state for it to leave stale; the sim's form hns_point_order_splat_sim is an operation",
+    "hns_point_population_birth": "reads a caller-owned tensor and no sim: the sim's form hns_point_population_birth_sim is an operation and shares its kernels",
+}
+
+
+# ---- the device side ---------------------------------------------------------------------------------------------------------------------------------------------
+
+
+def _torch():
+    import torch
+
+    return torch
+
+
+def device_floats(owner, ptr, n):
+    """`n` floats of device memory at `ptr` as a torch view (no copy)"""
+    from hnanosolver_amd import device
+
+    torch = _torch()
+    return torch.as_tensor(device._DeviceWords(ptr, n, owner), device="cuda").view(torch.float32)
+
+
+DEFAULT_SPEC = (0, 0, 0.0, 0.0)
+
+
+class World:
+    """The sim of a script with its points, its order and its population, opened from the semantic state alone: what `capture` returns, plus the solve method, the solve
+    control, the order's last (xyz, level) and the switches of the script, which the library has no getter for and the ops record here."""
+
+    def __init__(self, state):
+        from hnanosolver_amd import api, device
+
+        torch = _torch()
+        self.names = list(state["names"])
+        self.timing = state["timing"]
+        self.grid = api.create_grid_from_leaves(state["origins"], VS)
+        self.grids = [self.grid]  # every grid the sim has been on: none is freed mid-script
+        self.sim = device.Sim(self.grid, self.names)
+        self.sim.upload({k: np.ascontiguousarray(state[k]) for k in ["vel"] + self.names})
+        if state["masks"] is not None:
+            self.sim.set_active_masks(state["masks"])
+        self.set_spec(state["splat_spec"])
+        self.method = self.control = None
+        self.set_method(state["method"])
+        self.set_control(state["control"])
+        if self.timing:
+            self.sim.timing(64)
+            self.sim.stage_timing(64)
+        self.xyz = torch.from_numpy(np.array(state["xyz"])).cuda()
+        self.attr = torch.from_numpy(np.array(state["attr"])).cuda()
+        self.order_key = state["order_key"]
+        self.live = state["live"]
+        self._order = self._population = None
+
+    # -- the state the library has no getter for
+    def set_spec(self, spec):
+        from hnanosolver_amd import _lib, api
+
+        kernel, mode, radius, min_weight = spec
+        api._raise(_lib.lib.hns_sim_set_splat_spec(self.sim._ptr, C.byref(_lib.hns_splat_spec(kernel, mode, radius, None, min_weight))))
+
+    def get_spec(self):
+        from hnanosolver_amd import _lib, api
+
+        s = _lib.hns_splat_spec()
+        api._raise(_lib.lib.hns_sim_get_splat_spec(self.sim._ptr, C.byref(s)))
+        assert not s.d_radius
+        return (int(s.kernel), int(s.mode), float(s.radius), float(s.min_weight))
+
+    def set_method(self, method):
+        self.method = method
+        self.sim.solve_method(None) if method is None else self.sim.solve_method(1, *method)
+
+    def set_control(self, control):
+        self.control = control
+        self.sim.solve_control(None) if control is None else self.sim.solve_control(*control)
+
+    # -- the point objects
+    def order(self):
+        """the PointOrder on the sim's current grid; a new one sorts the order's last (xyz, level) again"""
+        if self._order is None:
+            self._order = self.sim.point_order(N_POINTS)
+            if self.order_key is not None:
+                self._order.sort(_torch().from_numpy(self.order_key[0]).cuda(), self.order_key[1])
+        return self._order
+
+    def population(self):
+        """the PointPopulation on the sim's current grid; a new one is told the live count"""
+        if self._population is None:
+            self._population = self.sim.point_population(N_POINTS)
+            if self.live is not None:
+                self._population.set_live(self.live)
+        return self._population
+
+    def drop_point_objects(self):
+        for o in (self._order, self._population):
+            if o is not None:
+                o.close()
+        self._order = self._population = None
+
+    def after(self, operation: Op):
+        if operation.grid:  # the objects of the old grid refuse every call from here on
+            self.grids.append(self.sim.grid)
+            self.drop_point_objects()
+            self.order_key = None
+
+    def vel3(self):
+        """an (n, 3) value per point from the attribute"""
+        a = self.attr
+        return _torch().stack([a, -0.5 * a, 0.25 * a], dim=1).contiguous()
+
+    def capture(self):
+        """the full downloaded state: everything include/hns.h documents as the sim's and the objects' state, and nothing else"""
+        sim = self.sim
+        st = fc.download(sim, self.names)
+        st.update(origins=np.ascontiguousarray(sim.grid.coords()[::512]), masks=sim.active_masks(), xyz=self.xyz.cpu().numpy(), attr=self.attr.cpu().numpy(),
+                  splat_spec=self.get_spec(), live=self.live)
+        return st
+
+    def carry(self, captured):
+        """the state a new World is opened from"""
+        return dict(captured, names=self.names, timing=self.timing, method=self.method, control=self.control, order_key=self.order_key)
+
+    def close(self):
+        if self.timing:  # (times are never compared)
+            self.sim.pressure_time(), self.sim.stage_times()
+        self.drop_point_objects()
+        self.sim.close()
+
+
+# ---- the vocabulary ----------------------------------------------------------------------------------------------------------------------------------------------
+
+
+def _seed(rng):
+    return int(rng.integers(1 << 30))
+
+
+def _solve_outputs(w):
+    """what a pressure solve leaves behind it for the host: the control's report and history, the hierarchy's levels"""
+    out = {}
+    if w.control is not None:
+        r = w.sim.solve_report()
+        out["solve_report"] = (r["iterations"], r["checks"], r["converged"], r["initial"].tobytes(), r["final"].tobytes())
+        out["solve_history"] = r["history"]
+    if w.method is not None:
+        out["solve_levels"] = np.array(w.sim.solve_levels(), dtype=np.int64)
+    return out
+
+
+def _vel(rng, n):
+    return fc.with_negative_zeros(rng, (0.6 * rng.standard_normal((n, 3))).astype(F))
+
+
+@op("upload", writes=("vel",), symbols=("hns_sim_upload",), memo="drop")
+def upload_vel(w, rng):
+    w.sim.upload({"vel": _vel(rng, w.sim.grid.voxel_count())})
+    return {}
+
+
+@op("upload", writes=("f:density",), symbols=("hns_sim_upload",), memo="drop")
+def upload_field(w, rng):
+    w.sim.upload({"density": rng.standard_normal(w.sim.grid.voxel_count()).astype(F)})
+    return {}
+
+
+@op("upload", writes=("vel",) + ALL_FIELDS, symbols=("hns_sim_upload",), memo="drop")
+def upload_all(w, rng):
+    n = w.sim.grid.voxel_count()
+    st = {"vel": _vel(rng, n)}
+    for k in w.names:
+        st[k] = fc.with_negative_zeros(rng, rng.standard_normal(n).astype(F))
+    w.sim.upload(st)
+    return {}
+
+
+@op("core_substep", reads=("vel",) + ADVECTED + SOLVE, writes=("vel", "scratch") + ADVECTED, symbols=("hns_sim_core_substep",), memo="produce")
+def core_substep(w, rng):
+    w.sim.core_substep(ITERS, DT, VS)
+    return _solve_outputs(w)
+
+
+def _substep(w, params, collision, fuse=None):
+    import hnanosolver_amd as H
+
+    if fuse is not None:
+        H.set_option("fuse", fuse)
+    try:
+        w.sim.substep(ITERS, DT, VS, params, collision)
+    finally:
+        H.set_option("fuse", None)
+    return _solve_outputs(w)
+
+
+@op("substep", reads=("vel",) + ADVECTED + SOLVE, writes=("vel", "scratch") + ADVECTED, symbols=("hns_sim_substep",), needs=fc.COMBUST, memo="consume")
+def substep_fused(w, rng):
+    from hnanosolver_amd import api
+
+    return _substep(w, api.CombustionParams(), False)
+
+
+@op("substep", reads=("vel",) + ADVECTED + SOLVE, writes=("vel", "scratch") + ADVECTED, symbols=("hns_sim_substep",), needs=fc.COMBUST, memo="produce")
+def substep_unfused(w, rng):
+    from hnanosolver_amd import api
+
+    return _substep(w, api.CombustionParams(), False, fuse="0")
+
+
+@op("substep", reads=("vel",) + ADVECTED + SOLVE, writes=("vel", "scratch") + ADVECTED, symbols=("hns_sim_substep",), needs=fc.COMBUST, memo="consume")
+def substep_vorticity(w, rng):
+    from hnanosolver_amd import api
+
+    return _substep(w, api.CombustionParams(factorScale=1.0, vorticityScale=0.4), False)
+
+
+@op("substep", reads=("vel",) + ALL_FIELDS + SOLVE, writes=("vel", "scratch") + ADVECTED, symbols=("hns_sim_substep",), needs=PROFILES["collide"], memo="drop")
+def substep_collision(w, rng):
+    from hnanosolver_amd import api
+
+    return _substep(w, api.CombustionParams(), True)
+
+
+@op("advect", reads=("vel", "f:density", "grid"), writes=("f:density",), symbols=("hns_sim_advect",), memo="drop")
+def advect_names(w, rng):
+    w.sim.advect(["density"], velocity=False, dt=DT, voxel_size=VS)
+    return {}
+
+
+@op("advect", reads=("vel", "grid") + ADVECTED, writes=("vel",) + ADVECTED, symbols=("hns_sim_advect",), memo="drop")
+def advect_velocity(w, rng):
+    w.sim.advect(None, velocity=True, dt=DT, voxel_size=VS)
+    return {}
+
+
+@op("pressure", reads=SOLVE, writes=("scratch",), symbols=("hns_sim_divergence_ptr", "hns_sim_pressure_solve", "hns_sim_residual", "hns_sim_pressure_ptr", "hns_sim_solve_report",
+                                                           "hns_sim_solve_levels"))
+def pressure_residual(w, rng):
+    """ONE compound step, because div and p are scratch (include/hns.h): write div, solve, take the residual of that solve, read p"""
+    from hnanosolver_amd._lib import lib
+
+    n = w.sim.grid.voxel_count()
+    div = device_floats(w.sim, lib.hns_sim_divergence_ptr(w.sim._ptr), n)
+    div.copy_(_torch().from_numpy(rng.standard_normal(n).astype(F)))
+    w.sim.pressure_solve(ITERS, VS)
+    out = {"residual": w.sim.residual(VS)}
+    out["p"] = device_floats(w.sim, lib.hns_sim_pressure_ptr(w.sim._ptr), n).clone().cpu().numpy()
+    out.update(_solve_outputs(w))
+    return out
+
+
+def sparse_masks(rng, moving):
+    """masks that shrink the next regrid's domain without emptying the sim: of the voxels that hold a velocity (`moving`, (leaves, 512) bool) a share per leaf, a third
+    of those leaves none, and a dozen voxels anywhere"""
+    n = len(moving)
+    bits = moving & (rng.random((n, 512)) < rng.choice([0.05, 0.5, 1.0], size=(n, 1)))
+    bits[rng.permutation(n)[: n // 3]] = False
+    bits[rng.integers(n, size=12), rng.integers(512, size=12)] = True
+    return fc.pack(bits)
+
+
+@op("set_active_masks", reads=("grid",), writes=("masks",), symbols=("hns_sim_set_active_masks",))
+def masks_array(w, rng):
+    """(the harness looks at the downloaded velocity to choose the masks; the call itself reads no field)"""
+    n = w.sim.grid.voxel_count()
+    vel = np.empty((n, 3), dtype=F)
+    w.sim.download({"vel": vel})
+    w.sim.set_active_masks(sparse_masks(rng, (vel != 0).any(1).reshape(-1, 512)))
+    return {}
+
+
+@op("set_active_masks", writes=("masks",), symbols=("hns_sim_set_active_masks",))
+def masks_none(w, rng):
+    w.sim.set_active_masks(None)
+    return {}
+
+
+def _regrid(w, padding, **kw):
+    before = w.sim.grid.leaf_count()
+    w.sim.regrid(padding, **kw)
+    if w.timing:
+        w.sim.regrid_times()
+    out = {"leaves": (before, w.sim.grid.leaf_count())}
+    if w.method is not None:
+        out["solve_levels"] = np.array(w.sim.solve_levels(), dtype=np.int64)
+    return out
+
+
+CARRIED = ("vel", "masks", "grid", "solve_method") + ALL_FIELDS  # what a regrid reads: everything it carries, and the method whose hierarchy it drops
+
+
+@op("regrid", reads=CARRIED, writes=("vel", "masks") + ALL_FIELDS, symbols=("hns_sim_regrid", "hns_sim_regrid_times", "hns_sim_solve_levels"), grid=True, memo="drop")
+def regrid_plain(w, rng):
+    return _regrid(w, 1)
+
+
+@op("regrid", reads=CARRIED, writes=("vel", "masks") + ALL_FIELDS, symbols=("hns_sim_regrid_sourced",), grid=True, memo="drop")
+def regrid_sourced(w, rng):
+    src = fc.make_sources(_seed(rng), w.sim.grid.coords()[::512], "mixed", "edge")
+    return _regrid(w, 2, sources={k: v for k, v in src.items() if k == "vel" or k in w.names})
+
+
+@op("regrid", reads=CARRIED + ("points",), writes=("vel", "masks") + ALL_FIELDS, symbols=("hns_sim_regrid_seeded",), grid=True, memo="drop")
+def regrid_seeded(w, rng):
+    out = _regrid(w, 0, points=w.xyz)
+    out["seeds_skipped"] = w.sim.last_seeds_skipped
+    return out
+
+
+@op("regrid", reads=CARRIED, writes=("vel", "masks") + ALL_FIELDS, symbols=("hns_sim_regrid",), needs=("collision_sdf",), grid=True, memo="drop")
+def regrid_sdf(w, rng):
+    return _regrid(w, 1, sdf=fc.sdf_source(_seed(rng), w.sim.grid.coords()[::512]))
+
+
+def _emit(w, **kw):
+    before = w.sim.grid.leaf_count()
+    rejected = _torch().zeros(1, dtype=_torch().int64, device="cuda")
+    _, status = w.sim.emit({"density": w.attr}, w.xyz, rejected=rejected, **kw)
+    return {"leaves": (before, w.sim.grid.leaf_count()), "status": status.cpu().numpy(), "rejected": int(rejected.item()), "seeds_skipped": w.sim.last_seeds_skipped}
+
+
+EMIT_SYMBOLS = ("hns_sim_regrid_seeded", "hns_sim_splat_points")
+
+
+@op("emit", reads=CARRIED + ("points",), writes=("vel", "masks") + ALL_FIELDS, symbols=EMIT_SYMBOLS, grid=True, memo="drop")
+def emit_trilinear(w, rng):
+    return _emit(w, padding=1)
+
+
+@op("emit", reads=CARRIED + ("points",), writes=("vel", "masks") + ALL_FIELDS, symbols=EMIT_SYMBOLS, grid=True, memo="drop")
+def emit_radial(w, rng):
+    return _emit(w, velocity=w.vel3(), padding=2, radius=1.5)
+
+
+QUIET = dict(tolerances={"density": 0.7}, velocity=1.0)
+
+
+@op("deactivate", reads=("vel", "f:density", "masks", "grid"), writes=("masks",), symbols=("hns_sim_deactivate",), memo="drop")
+def deactivate(w, rng):
+    w.sim.deactivate(**QUIET)
+    return {}
+
+
+@op("deactivate", reads=("vel", "f:density", "masks", "grid"), writes=("masks",), symbols=("hns_sim_deactivate",), memo="drop")
+def deactivate_counts(w, rng):
+    return {"counts": w.sim.deactivate(counts=True, **QUIET)}
+
+
+@op("stats", reads=("vel", "masks", "grid") + ALL_FIELDS, symbols=("hns_sim_stats",))
+def stats(w, rng):
+    return {"records": w.sim.stats(w.names, velocity=True, masks=True)}
+
+
+@op("sample", reads=("vel", "grid", "points") + ALL_FIELDS, symbols=("hns_sim_sample_points", "hns_sim_field_ptr"))
+def sample(w, rng):
+    from hnanosolver_amd._lib import lib
+
+    out = {k: v.cpu().numpy() for k, v in w.sim.sample(None, w.xyz, velocity=True).items()}
+    out["density_in_place"] = device_floats(w.sim, lib.hns_sim_field_ptr(w.sim._ptr, b"density"), w.sim.grid.voxel_count()).cpu().numpy()
+    return out
+
+
+@op("trace", reads=("vel", "grid", "points"), writes=("points",), symbols=("hns_sim_trace_points",))
+def trace(w, rng):
+    return {"status": w.sim.trace(w.xyz, dt=DT, voxel_size=VS, order=2, steps=2, status=True).cpu().numpy()}
+
+
+def _splat(w, values, velocity, **kw):
+    rejected = _torch().zeros(1, dtype=_torch().int64, device="cuda")
+    status = w.sim.splat(values, w.xyz, velocity, status=True, rejected=rejected, **kw)
+    return {"status": status.cpu().numpy(), "rejected": int(rejected.item())}
+
+
+SPLAT = ("hns_sim_splat_points",)
+
+
+@op("splat", reads=("f:density", "masks", "grid", "points"), writes=("f:density", "masks"), symbols=SPLAT)
+def splat_floats(w, rng):
+    return _splat(w, {"density": w.attr}, None, activate=True)
+
+
+@op("splat", reads=("vel", "grid", "points"), writes=("vel",), symbols=SPLAT, memo="drop")
+def splat_velocity(w, rng):
+    return _splat(w, {}, w.vel3(), activate=False)
+
+
+@op("splat", reads=("vel", "f:density", "masks", "grid", "points"), writes=("vel", "f:density", "masks"), symbols=SPLAT, memo="drop")
+def splat_both(w, rng):
+    return _splat(w, {"density": w.attr}, w.vel3(), activate=True, kernel="radial", radius=1.25)
+
+
+@op("splat", reads=("vel", "f:density", "masks", "grid", "points", "splat_spec"), writes=("vel", "f:density", "masks"), symbols=SPLAT, memo="drop")
+def splat_stored(w, rng):
+    """through the spec stored with the sim: the library call itself, which reads it (Sim.splat stores its keywords' spec for the call)"""
+    from hnanosolver_amd import api
+    from hnanosolver_amd._lib import lib
+
+    torch = _torch()
+    n = w.xyz.shape[0]
+    status, rejected, vel = torch.empty(n, dtype=torch.uint8, device="cuda"), torch.zeros(1, dtype=torch.int64, device="cuda"), w.vel3()
+    api._raise(lib.hns_sim_splat_points(w.sim._ptr, (C.c_char_p * 1)(b"density"), 1, vel.data_ptr(), w.xyz.data_ptr(), (C.c_void_p * 1)(w.attr.data_ptr()), n, -32, 1,
+                                        status.data_ptr(), rejected.data_ptr(), 0))
+    return {"status": status.cpu().numpy(), "rejected": int(rejected.item())}
+
+
+def _sort(w, level):
+    o = w.order()
+    o.sort(w.xyz, level)
+    w.order_key = (w.xyz.cpu().numpy(), level)
+    return {"perm": o.perm.cpu().numpy(), "keys": o.keys.cpu().numpy(), "leaf_start": o.leaf_start.cpu().numpy()}
+
+
+@op("sort", reads=("grid", "points"), writes=("order",), symbols=("hns_point_order_sort", "hns_point_order_get"))
+def sort_voxel(w, rng):
+    return _sort(w, "voxel")
+
+
+@op("sort", reads=("grid", "points"), writes=("order",), symbols=("hns_point_order_sort", "hns_point_order_get"))
+def sort_leaf(w, rng):
+    return _sort(w, "leaf")
+
+
+@op("gather_scatter", reads=("order", "points"), writes=("points",), symbols=("hns_point_order_gather", "hns_point_order_scatter"), requires=("order",), same_points=True)
+def gather_scatter(w, rng):
+    o = w.order()
+    gx, ga = o.gather(w.xyz), o.gather(w.attr)
+    w.xyz, w.attr = o.scatter(gx), o.scatter(ga)
+    return {"ranked_xyz": gx.cpu().numpy(), "ranked_attr": ga.cpu().numpy()}
+
+
+ORDER_SPLAT = ("hns_point_order_splat_sim",)
+
+
+@op("order_splat", reads=("vel", "f:density", "masks", "grid", "points", "order"), writes=("vel", "f:density", "masks"), symbols=ORDER_SPLAT, requires=("order", "fresh_order"),
+    memo="drop")
+def order_splat_original(w, rng):
+    return _splat(w, {"density": w.attr}, w.vel3(), activate=True, order=w.order(), rows="original")
+
+
+@op("order_splat", reads=("f:density", "grid", "points", "order"), writes=("f:density",), symbols=ORDER_SPLAT + ("hns_point_order_gather",), requires=("order", "fresh_order"))
+def order_splat_ranked(w, rng):
+    """the per-point arrays in sorted order; float fields only, so the look-ahead memo stays"""
+    o = w.order()
+    torch = _torch()
+    gx, ga = o.gather(w.xyz), o.gather(w.attr)
+    rejected = torch.zeros(1, dtype=torch.int64, device="cuda")
+    status = w.sim.splat({"density": ga}, gx, None, activate=False, status=True, rejected=rejected, order=o, rows="ranked", kernel="radial", mode="average", radius=1.5,
+                         min_weight=0.125)
+    return {"status": status.cpu().numpy(), "rejected": int(rejected.item())}
+
+
+def _select_compact(w, fill):
+    """ONE compound step, because the slots are not state: trace with status, select from it, compact both point arrays"""
+    status = w.sim.trace(w.xyz, dt=DT, voxel_size=VS, order=1, steps=1, status=True)
+    p = w.population()
+    p.select(status)
+    slot = p.slot.cpu().numpy()
+    w.xyz = p.compact(w.xyz, w.xyz.clone(), fill=float("nan") if fill else None)
+    w.attr = p.compact(w.attr, w.attr.clone(), fill=0 if fill else None)
+    counts = p.counts()
+    w.live = counts[0]
+    return {"status": status.cpu().numpy(), "slot": slot, "counts": counts}
+
+
+POPULATION = ("hns_sim_trace_points", "hns_point_population_select", "hns_point_population_compact", "hns_point_population_get", "hns_point_population_counts")
+
+
+@op("select_compact", reads=("vel", "grid", "points"), writes=("points", "live"), symbols=POPULATION)
+def select_compact_fill(w, rng):
+    return _select_compact(w, True)
+
+
+@op("select_compact", reads=("vel", "grid", "points"), writes=("points", "live"), symbols=POPULATION)
+def select_compact_keep(w, rng):
+    return _select_compact(w, False)
+
+
+@op("set_live", writes=("live",), symbols=("hns_point_population_set_live", "hns_point_population_counts"))
+def set_live(w, rng):
+    p = w.population()
+    p.set_live(int(rng.integers(N_POINTS // 4, N_POINTS // 2)))
+    counts = p.counts()
+    w.live = counts[0]
+    return {"counts": counts}
+
+
+def _birth(w, rng, append, fill, **spec):
+    torch = _torch()
+    p = w.population()
+    voxel = torch.full((N_POINTS,), -7, dtype=torch.int32, device="cuda")
+    w.sim.birth(p, "density", w.xyz, voxel, seed=_seed(rng) & 0xFFFF, append=append, fill=fill, use_masks=True, **spec)
+    counts = p.counts()
+    before, w.live = w.live, counts[0]
+    return {"voxel": voxel.cpu().numpy(), "counts": counts, "live_before": before if append else 0}
+
+
+BIRTH = ("hns_point_population_birth_sim", "hns_point_population_counts")
+FEW = dict(threshold=1.5, rate=0.6, max_per_voxel=2)
+MANY = dict(threshold=0.0, rate=3.0, max_per_voxel=4)  # thousands of births: more than the rows
+
+
+@op("birth", reads=("f:density", "masks", "grid", "points"), writes=("points", "live"), symbols=BIRTH)
+def birth(w, rng):
+    """from row 0; the rows behind the births keep their positions (fill off), so the script's point set does not die with a quiet field"""
+    return _birth(w, rng, False, False, **FEW)
+
+
+@op("birth", reads=("f:density", "masks", "grid", "live", "points"), writes=("points", "live"), symbols=BIRTH)
+def birth_append(w, rng):
+    return _birth(w, rng, True, False, **FEW)
+
+
+@op("birth", reads=("f:density", "masks", "grid", "live", "points"), writes=("points", "live"), symbols=BIRTH)
+def birth_overflow(w, rng):
+    """appended, filled, and more births than rows: wanted > live"""
+    return _birth(w, rng, True, True, **MANY)
+
+
+@op("solve_method", writes=("solve_method",), symbols=("hns_sim_set_solve_method",))
+def method_sor(w, rng):
+    w.set_method(None)
+    return {}
+
+
+@op("solve_method", reads=("grid",), writes=("solve_method",), symbols=("hns_sim_set_solve_method", "hns_sim_solve_levels"))
+def method_vcycle_a(w, rng):
+    w.set_method((2, 2, 8, 0, 1.0))
+    return {"solve_levels": np.array(w.sim.solve_levels(), dtype=np.int64)}
+
+
+@op("solve_method", reads=("grid",), writes=("solve_method",), symbols=("hns_sim_set_solve_method", "hns_sim_solve_levels"))
+def method_vcycle_b(w, rng):
+    w.set_method((1, 1, 4, 2, 1.2))
+    return {"solve_levels": np.array(w.sim.solve_levels(), dtype=np.int64)}
+
+
+@op("solve_control", writes=("solve_control",), symbols=("hns_sim_set_solve_control",))
+def control_off(w, rng):
+    w.set_control(None)
+    return {}
+
+
+@op("solve_control", writes=("solve_control",), symbols=("hns_sim_set_solve_control", "hns_sim_solve_report"))
+def control_on(w, rng):
+    """the report itself comes out of the next solve's step (a report needs a controlled solve on the same sim)"""
+    w.set_control((0.5, 0.0, 2))
+    return {}
+
+
+@op("set_splat_spec", writes=("splat_spec",), symbols=("hns_sim_set_splat_spec", "hns_sim_get_splat_spec"))
+def spec_radial_average(w, rng):
+    w.set_spec((1, 1, 1.5, 0.25))
+    return {}
+
+
+@op("set_splat_spec", writes=("splat_spec",), symbols=("hns_sim_set_splat_spec", "hns_sim_get_splat_spec"))
+def spec_default(w, rng):
+    w.set_spec(DEFAULT_SPEC)
+    return {}
+
+
+KINDS = tuple(dict.fromkeys(o.kind for o in OPS.values()))
+PRODUCERS = frozenset(k for k, o in OPS.items() if o.memo == "produce")
+
+# ---- conditions on scripts, from the table alone (no device) ---------------------------------------------------------------------------------------------------------
+
+
+class Script(NamedTuple):
+    name: str
+    profile: str
+    seed: int
+    timing: bool
+    steps: tuple  # of (operation name, seed)
+
+    @property
+    def ops(self):
+        return [OPS[k] for k, _ in self.steps]
+
+
+def profile_allows(profile, operation: Op):
+    return operation.needs <= set(PROFILES[profile])
+
+
+def depends(a: Op, b: Op):
+    """what `a` writes that `b` reads, or that a memo `b` consumes depends on"""
+    return a.writes & b.reads
+
+
+def feasible(a: Op, b: Op):
+    """can `b` directly follow `a` in some script? not when `a` breaks what `b` requires of the steps before it"""
+    return not (a.breaks & b.requires) and any(profile_allows(p, a) and profile_allows(p, b) for p in PROFILES)
+
+
+def needed_pairs():
+    """{(kind A, kind B): [(a, b) operation names that would cover it]}"""
+    out = {}
+    for ka, a in OPS.items():
+        for kb, b in OPS.items():
+            if depends(a, b) and feasible(a, b):
+                out.setdefault((a.kind, b.kind), []).append((ka, kb))
+    return out
+
+
+def covered_pairs(scripts):
+    out = {}
+    for s in scripts:
+        for i in range(1, len(s.steps)):
+            a, b = OPS[s.steps[i - 1][0]], OPS[s.steps[i][0]]
+            if depends(a, b):
+                out.setdefault((a.kind, b.kind), []).append((s.name, i))
+    return out
+
+
+def placed_writers():
+    """the operations that must sit between two look-ahead substeps in some script: every writer of the velocity, every change of grid and everything else that drops
+    the memo -- but the substeps that leave a memo themselves"""
+    return [k for k, o in OPS.items() if k not in PRODUCERS and ("vel" in o.writes or o.grid or o.memo == "drop")]
+
+
+def placements(scripts):
+    out = {}
+    for s in scripts:
+        names = [k for k, _ in s.steps]
+        for i in range(1, len(names) - 1):
+            if names[i - 1] in PRODUCERS and names[i + 1] in PRODUCERS:
+                out.setdefault(names[i], []).append((s.name, i))
+    return out
+
+
+class Tracker:
+    """what a script has established so far, as far as the table can tell: is there an order on the current grid, and does it match the positions?"""
+
+    def __init__(self):
+        self.have = set()
+
+    def refusal(self, profile, name):
+        o = OPS[name]
+        if not profile_allows(profile, o):
+            return f"{name} needs the fields {sorted(o.needs)}, the profile {profile} holds {PROFILES[profile]}"
+        if not o.requires <= self.have:
+            return f"{name} requires {sorted(o.requires - self.have)}: a sort since the last change of grid (fresh_order: and since the last write of the positions)"
+        return None
+
+    def step(self, name):
+        o = OPS[name]
+        self.have -= o.breaks
+        if o.kind == "sort":
+            self.have |= {"order", "fresh_order"}
+
+
+def refusals(script: Script):
+    """the steps of a script the library (or its Python objects) would refuse, by the table"""
+    t, out = Tracker(), []
+    for i, (name, _) in enumerate(script.steps):
+        if name not in OPS:
+            out.append((i, f"{name} is no operation"))
+            continue
+        why = t.refusal(script.profile, name)
+        if why:
+            out.append((i, why))
+        t.step(name)
+    return out
+
+
+def expected_lookahead(script: Script, upto=None):
+    """(produced, consumed) after every step under lookahead = 1, by the table's memo column"""
+    live, produced, consumed, out = False, 0, 0, []
+    for o in script.ops[:upto]:
+        if o.memo in ("produce", "consume"):
+            consumed += live
+            live = o.memo == "produce"
+            produced += live
+        elif o.memo == "drop":
+            live = False
+        out.append((produced, consumed))
+    return out
+
+
+def has_two_equal_substeps(script: Script):
+    names = [k for k, _ in script.steps]
+    return any(a in PRODUCERS and b in PRODUCERS for a, b in zip(names, names[1:]))
+
+
+# ---- the generator the committed scripts were drawn with ---------------------------------------------------------------------------------------------------------------
+
+
+def draw_scripts(seed=2026, max_steps=24, max_scripts=16):
+    """Placement scripts first (substep, writer, substep, writer, ...), then greedy walks that take the step covering the most uncovered pairs. Prints nothing; returns the
+    scripts, whose text (`format_scripts`) is pasted below. The CPU test holds the conditions on the committed text, not on this function."""
+    rng = np.random.default_rng(seed)
+    ways_of = needed_pairs()
+    need = set(ways_of)
+    scripts, counter = [], [100]
+
+    def next_seed():
+        counter[0] += 1
+        return counter[0]
+
+    def finish(name, profile, names, timing=False):
+        s = Script(name, profile, next_seed(), timing, tuple((k, next_seed()) for k in names))
+        assert not refusals(s), (name, refusals(s))
+        scripts.append(s)
+        need.difference_update(covered_pairs([s]))
+
+    # placement: S S w S w S ..., a sort in front of a producer where the writer needs an order
+    writers = placed_writers()
+    groups = {"collide": [k for k in writers if "collision_sdf" in OPS[k].needs], "one": [], "combust": []}
+    rest = [k for k in writers if k not in groups["collide"]]
+    for i, k in enumerate(rest):
+        groups["one" if (not OPS[k].needs and i % 2) else "combust"].append(k)
+    groups["collide"] += groups["combust"][-3:]
+    del groups["combust"][-3:]
+    for profile, ws in groups.items():
+        cycle = ["core_substep"] if profile == "one" else ["core_substep", "substep_unfused"]
+        names, t = [cycle[0]], Tracker()
+        for j, k in enumerate(ws):
+            if t.refusal(profile, k):
+                names += ["sort_voxel" if j % 2 else "sort_leaf", cycle[j % len(cycle)]]
+                t.step(names[-2])
+            names += [k, cycle[(j + 1) % len(cycle)]]
+            t.step(k)
+        finish(f"placement_{profile}", profile, [cycle[-1]] + names, timing=profile == "combust")
+
+    # greedy walks
+    profiles = ["combust", "collide", "one", "combust"]
+    while need and len(scripts) < max_scripts:
+        profile = profiles[len(scripts) % len(profiles)]
+        names, t, idle = [], Tracker(), 0
+
+        def gain(a, b):
+            return 1.0 if (OPS[a].kind, OPS[b].kind) in need and depends(OPS[a], OPS[b]) else 0.0
+
+        while len(names) < max_steps:
+            best, best_score = None, 0.0
+            for k in rng.permutation(list(OPS)):
+                k, o = str(k), OPS[str(k)]
+                if t.refusal(profile, k):
+                    continue
+                t2 = Tracker()
+                t2.have = set(t.have)
+                t2.step(k)
+                onward = max([gain(k, c) for c in OPS if c != k and not t2.refusal(profile, c)
+                              and not (names and OPS[c].kind == OPS[names[-1]].kind and o.kind == OPS[c].kind)] or [0.0])
+                after = sum(1 for (a, b), ways in ways_of.items() if (a, b) in need and a == o.kind and any(x == k and profile_allows(profile, OPS[y]) for x, y in ways))
+                score = (gain(names[-1], k) if names else 0.0) + 0.9 * onward + 0.01 * after
+                if o.grid and sum(OPS[x].grid for x in names) >= 4:
+                    score *= 0.1  # (keeps a script's domain from growing without end)
+                if score > best_score:
+                    best, best_score = k, score
+            if best is None:
+                break
+            names.append(best)
+            t.step(best)
+            won = len(names) > 1 and gain(names[-2], best) > 0
+            if won:
+                need.discard((OPS[names[-2]].kind, OPS[best].kind))
+            idle = 0 if won else idle + 1
+            if idle >= 3:
+                del names[-3:]
+                break
+        if len(names) < 6:
+            break  # (the walk finds too little: the rest is picked up pair by pair)
+        finish(f"walk_{len(scripts)}", profile, names, timing=len(scripts) % 5 == 0)
+
+    # what the walks left: pair by pair, each with the sort it requires in front
+    while need and len(scripts) < max_scripts:
+        profile = "combust" if all(any(profile_allows("combust", OPS[a]) and profile_allows("combust", OPS[b]) for a, b in ways_of[p]) for p in need) else "collide"
+        names, t = [], Tracker()
+        for p in sorted(need):
+            a, b = next((a, b) for a, b in ways_of[p] if profile_allows(profile, OPS[a]) and profile_allows(profile, OPS[b]))
+            seg, t2 = [], Tracker()
+            t2.have = set(t.have)
+            if names and names[-1] == a and not t2.refusal(profile, b):
+                seg = [b]
+            else:
+                if (OPS[a].requires | (OPS[b].requires - OPS[a].breaks)) - t2.have:
+                    seg.append("sort_voxel")
+                seg += [a, b]
+            if len(names) + len(seg) > max_steps:
+                break
+            for k in seg:
+                names.append(k)
+                t.step(k)
+        finish(f"pairs_{len(scripts)}", profile, names)
+    return scripts, need
+
+
+def format_scripts(scripts):
+    lines = ["SCRIPTS = ("]
+    for s in scripts:
+        lines.append(f'    Script("{s.name}", "{s.profile}", {s.seed}, {s.timing}, (')
+        row = "        "
+        for k, sd in s.steps:
+            item = f'("{k}", {sd}), '
+            if len(row) + len(item) > 168:
+                lines.append(row.rstrip())
+                row = "        "
+            row += item
+        lines.append(row.rstrip())
+        lines.append("    )),")
+    lines.append(")")
+    return "\n".join(lines)
+
+
+# ---- the committed scripts -----------------------------------------------------------------------------------------------------------------------------------------------
+
+# all but the last were drawn by draw_scripts (its closing three-step script folded into the last one); frame_vcycle is written by hand: a V-cycle method and a
+# control on a sim, then a seeded regrid, an ordered splat of the velocity, substeps, a deactivate, statistics, a birth from a field, a regrid onto another leaf count,
+# a stored spec set and put back, and the way back to SOR -- and the operations no drawn script holds
+SCRIPTS = (
+    Script("placement_collide", "collide", 101, False, (
+        ("substep_unfused", 102), ("core_substep", 103), ("substep_collision", 104), ("substep_unfused", 105), ("regrid_sdf", 106), ("core_substep", 107),
+        ("deactivate", 108), ("substep_unfused", 109), ("splat_velocity", 110), ("core_substep", 111), ("splat_stored", 112), ("substep_unfused", 113),
+    )),
+    Script("placement_one", "one", 114, False, (
+        ("core_substep", 115), ("core_substep", 116), ("upload_field", 117), ("core_substep", 118), ("advect_names", 119), ("core_substep", 120),
+        ("regrid_plain", 121), ("core_substep", 122), ("regrid_seeded", 123), ("core_substep", 124), ("emit_radial", 125), ("core_substep", 126),
+        ("deactivate_counts", 127), ("core_substep", 128), ("splat_both", 129), ("core_substep", 130), ("sort_voxel", 131), ("core_substep", 132),
+        ("order_splat_original", 133), ("core_substep", 134),
+    )),
+    Script("placement_combust", "combust", 135, True, (
+        ("substep_unfused", 136), ("core_substep", 137), ("upload_vel", 138), ("substep_unfused", 139), ("upload_all", 140), ("core_substep", 141),
+        ("substep_fused", 142), ("substep_unfused", 143), ("substep_vorticity", 144), ("core_substep", 145), ("advect_velocity", 146), ("substep_unfused", 147),
+        ("regrid_sourced", 148), ("core_substep", 149), ("emit_trilinear", 150), ("substep_unfused", 151),
+    )),
+    Script("walk_3", "combust", 152, False, (
+        ("regrid_plain", 153), ("regrid_seeded", 154), ("emit_radial", 155), ("emit_trilinear", 156), ("advect_velocity", 157), ("splat_stored", 158),
+        ("splat_both", 159), ("advect_velocity", 160), ("advect_velocity", 161), ("select_compact_fill", 162), ("splat_stored", 163), ("birth", 164), ("trace", 165),
+        ("trace", 166), ("splat_velocity", 167), ("select_compact_keep", 168), ("select_compact_keep", 169), ("birth_overflow", 170), ("birth_append", 171),
+        ("splat_velocity", 172), ("deactivate_counts", 173), ("deactivate_counts", 174), ("splat_both", 175), ("trace", 176),
+    )),
+    Script("walk_4", "combust", 177, False, (
+        ("regrid_plain", 178), ("substep_fused", 179), ("emit_radial", 180), ("regrid_seeded", 181), ("advect_velocity", 182), ("regrid_seeded", 183),
+        ("masks_array", 184), ("birth_append", 185), ("select_compact_fill", 186), ("trace", 187), ("birth_append", 188), ("sort_voxel", 189),
+        ("order_splat_original", 190), ("order_splat_original", 191), ("substep_fused", 192), ("order_splat_original", 193), ("advect_velocity", 194),
+        ("order_splat_original", 195), ("trace", 196), ("gather_scatter", 197), ("gather_scatter", 198), ("splat_floats", 199), ("upload_all", 200),
+        ("advect_velocity", 201),
+    )),
+    Script("walk_5", "collide", 202, True, (
+        ("emit_trilinear", 203), ("masks_array", 204), ("regrid_seeded", 205), ("select_compact_keep", 206), ("emit_radial", 207), ("splat_velocity", 208),
+        ("emit_radial", 209), ("deactivate", 210), ("birth_append", 211), ("upload_all", 212), ("trace", 213), ("select_compact_keep", 214), ("sort_voxel", 215),
+        ("gather_scatter", 216), ("order_splat_original", 217), ("birth_overflow", 218), ("gather_scatter", 219), ("trace", 220), ("sort_voxel", 221),
+        ("upload_all", 222), ("order_splat_original", 223), ("splat_floats", 224), ("order_splat_original", 225), ("deactivate_counts", 226),
+    )),
+    Script("walk_6", "one", 227, False, (
+        ("regrid_plain", 228), ("deactivate_counts", 229), ("emit_trilinear", 230), ("method_vcycle_b", 231), ("regrid_plain", 232), ("splat_stored", 233),
+        ("regrid_sourced", 234), ("method_vcycle_b", 235), ("core_substep", 236), ("birth_append", 237), ("sample", 238), ("upload_all", 239),
+        ("select_compact_fill", 240), ("sample", 241), ("upload_field", 242), ("deactivate", 243), ("stats", 244), ("upload_all", 245), ("birth_overflow", 246),
+        ("advect_velocity", 247), ("trace", 248), ("sample", 249), ("advect_names", 250), ("deactivate", 251),
+    )),
+    Script("walk_7", "combust", 252, False, (
+        ("emit_radial", 253), ("trace", 254), ("emit_trilinear", 255), ("select_compact_fill", 256), ("regrid_seeded", 257), ("birth", 258), ("regrid_seeded", 259),
+        ("trace", 260), ("substep_fused", 261), ("advect_names", 262), ("birth_overflow", 263), ("substep_unfused", 264), ("deactivate_counts", 265),
+        ("masks_array", 266), ("splat_floats", 267), ("sample", 268), ("upload_all", 269), ("splat_both", 270), ("stats", 271), ("substep_vorticity", 272),
+        ("trace", 273), ("substep_fused", 274), ("birth", 275), ("upload_field", 276),
+    )),
+    Script("walk_8", "combust", 277, False, (
+        ("emit_trilinear", 278), ("birth_overflow", 279), ("emit_trilinear", 280), ("sort_leaf", 281), ("gather_scatter", 282), ("regrid_seeded", 283),
+        ("sort_voxel", 284), ("gather_scatter", 285), ("emit_trilinear", 286), ("sample", 287), ("masks_none", 288), ("deactivate", 289), ("upload_all", 290),
+        ("stats", 291), ("core_substep", 292), ("trace", 293), ("advect_names", 294), ("sample", 295), ("upload_field", 296), ("sample", 297), ("masks_array", 298),
+        ("stats", 299), ("substep_unfused", 300), ("select_compact_fill", 301),
+    )),
+    Script("walk_9", "collide", 302, False, (
+        ("core_substep", 303), ("select_compact_keep", 304), ("regrid_sourced", 305), ("sample", 306), ("control_on", 307), ("substep_vorticity", 308), ("stats", 309),
+        ("method_vcycle_a", 310), ("emit_radial", 311), ("stats", 312), ("deactivate_counts", 313), ("regrid_plain", 314), ("pressure_residual", 315),
+        ("control_off", 316), ("core_substep", 317), ("sample", 318), ("upload_all", 319), ("regrid_sourced", 320), ("stats", 321), ("method_sor", 322),
+        ("substep_vorticity", 323), ("sample", 324), ("masks_array", 325), ("advect_velocity", 326),
+    )),
+    Script("walk_10", "one", 327, True, (
+        ("advect_names", 328), ("emit_trilinear", 329), ("pressure_residual", 330), ("masks_array", 331), ("emit_trilinear", 332), ("method_vcycle_a", 333),
+        ("pressure_residual", 334), ("control_on", 335), ("pressure_residual", 336), ("upload_vel", 337), ("emit_trilinear", 338), ("trace", 339),
+        ("regrid_seeded", 340), ("advect_names", 341), ("stats", 342), ("core_substep", 343), ("stats", 344), ("spec_radial_average", 345), ("splat_stored", 346),
+        ("set_live", 347), ("birth_append", 348),
+    )),
+    Script("pairs_11", "combust", 349, False, (
+        ("sort_voxel", 350), ("deactivate", 351), ("order_splat_original", 352), ("gather_scatter", 353), ("birth_append", 354), ("gather_scatter", 355),
+        ("sample", 356), ("gather_scatter", 357), ("select_compact_fill", 358), ("gather_scatter", 359), ("sort_voxel", 360), ("order_splat_original", 361),
+        ("emit_trilinear", 362), ("sort_voxel", 363), ("order_splat_original", 364), ("regrid_plain", 365), ("sort_voxel", 366), ("order_splat_original", 367),
+        ("sample", 368), ("order_splat_original", 369), ("select_compact_fill", 370), ("sort_voxel", 371), ("order_splat_original", 372), ("stats", 373),
+    )),
+    Script("frame_vcycle", "combust", 374, True, (
+        ("method_vcycle_a", 375), ("control_on", 376), ("regrid_seeded", 377), ("sort_voxel", 378), ("masks_array", 379), ("order_splat_original", 380),
+        ("core_substep", 381), ("core_substep", 382), ("deactivate", 383), ("stats", 384), ("birth", 385), ("substep_unfused", 386), ("substep_unfused", 387),
+        ("regrid_plain", 388), ("pressure_residual", 389), ("method_vcycle_b", 390), ("spec_radial_average", 391), ("splat_stored", 392), ("spec_default", 393),
+        ("splat_stored", 394), ("control_off", 395), ("method_sor", 396), ("core_substep", 397), ("sort_leaf", 398), ("order_splat_ranked", 399), ("core_substep", 400),
+    )),
+)
+
+BY_NAME = {s.name: s for s in SCRIPTS}
+
+
+# ---- the two runners -----------------------------------------------------------------------------------------------------------------------------------------------------
+
+
+def points_of(origins, seed):
+    """N_POINTS positions from points_cases' classes (inside, crossing, rim, outside, far, integer, below, large) with non-finite rows, and one attribute per point with
+    non-finite values"""
+    import points_cases as pc
+
+    rng = np.random.default_rng([seed, 77])
+    xyz = pc.make_points(origins, seed, n=N_POINTS).copy()
+    rows = rng.choice(N_POINTS, size=12, replace=False)
+    xyz[rows[:4], 0] = np.nan
+    xyz[rows[4:8], 1] = np.inf
+    xyz[rows[8:], 2] = -np.inf
+    attr = rng.standard_normal(N_POINTS).astype(F)
+    attr[rng.choice(N_POINTS, size=9, replace=False)] = np.array([np.nan, np.inf, -np.inf] * 3, dtype=F)
+    return xyz, attr
+
+
+@functools.lru_cache(maxsize=None)
+def initial_state(name):
+    s = BY_NAME[name]
+    names = PROFILES[s.profile]
+    o = np.ascontiguousarray(fc.random_leaves(s.seed), dtype=np.int32)
+    st = fc.random_state(s.seed + 1, len(o), names)
+    st["vel"] *= F(0.6)
+    xyz, attr = points_of(o, s.seed)
+    st.update(origins=o, masks=None, xyz=xyz, attr=attr, splat_spec=DEFAULT_SPEC, live=N_POINTS, names=names, timing=s.timing, method=None, control=None, order_key=None)
+    return st
+
+
+def _step(world, script, i):
+    name, seed = script.steps[i]
+    out = OPS[name].fn(world, np.random.default_rng(seed))
+    world.after(OPS[name])
+    return out
+
+
+def run_twin(script: Script, upto=None):
+    """-> per step (outputs, captured state): every step on a World of its own, opened from the state the step before left, under lookahead = 0 and a filled pool"""
+    import hnanosolver_amd as H
+    from pool_cases import arena_fill
+
+    state, out = initial_state(script.name), []
+    H.set_option("lookahead", "0")
+    try:
+        for i in range(len(script.steps) if upto is None else upto):
+            with arena_fill(TWIN_FILLS[i % 2]):
+                w = World(state)
+                try:
+                    outputs = _step(w, script, i)
+                    captured = w.capture()
+                    state = w.carry(captured)
+                finally:
+                    w.close()
+            out.append((outputs, captured))
+    finally:
+        H.set_option("lookahead", None)
+    return out
+
+
+def run_resident(script: Script, mode, upto=None, against=None):
+    """ONE World from the first step to the last, options at their defaults but lookahead = mode -> (per step (outputs, captured state, lookahead_counts), difference).
+    against: the twin's records; every step is then compared as soon as it has run, the pass ends at the first difference, and the captured states are not kept"""
+    import hnanosolver_amd as H
+
+    out, difference = [], None
+    H.set_option("lookahead", mode)
+    try:
+        w = World(initial_state(script.name))
+        try:
+            for i in range(len(script.steps) if upto is None else upto):
+                outputs = _step(w, script, i)
+                record = (outputs, w.capture(), w.sim.lookahead_counts())
+                if against is not None:
+                    difference = step_difference(script, mode, i, against[i], record)
+                    record = (outputs, None, record[2])
+                out.append(record)
+                if difference:
+                    break
+        finally:
+            w.close()
+    finally:
+        H.set_option("lookahead", None)
+    return out, difference
+
+
+def as_words(v):
+    """an output as 32-bit words where it is an array of them (so that NaN payloads and signed zeros count), else as the bytes pool_cases.as_bytes compares"""
+    from pool_cases import as_bytes
+
+    b = as_bytes(v)
+    return np.frombuffer(b, dtype=np.uint32) if len(b) % 4 == 0 else np.frombuffer(b, dtype=np.uint8)
+
+
+def step_difference(script: Script, mode, i, t, r):
+    """None, or how step i of the resident pass (r) differs from the twin's (t) in anything the step returned or in the downloaded state"""
+    for part, a, b in (("returned", r[0], t[0]), ("state", r[1], t[1])):
+        where = f"script {script.name}, lookahead = {mode}, step {i} ({script.steps[i][0]}, after {script.steps[i - 1][0] if i else 'the upload'})"
+        if a.keys() != b.keys():
+            return f"{where}: the {part} names differ: {sorted(a.keys() ^ b.keys())}"
+        for k in a:
+            x, y = as_words(a[k]), as_words(b[k])
+            if x.shape != y.shape:
+                return f"{where}: {part} {k} has {x.size} words on the resident sim and {y.size} on the twin"
+            d = np.flatnonzero(x != y)
+            if len(d):
+                return f"{where}: {part} {k} differs in {len(d)} of {x.size} words, first at word {int(d[0])} ({int(x[d[0]]):#x} resident, {int(y[d[0]]):#x} twin)"
+    return None
+
+
+def first_difference(script: Script, mode, twin, resident):
+    """None, or the message of the first step at which the resident and the twin differ"""
+    for i, (t, r) in enumerate(zip(twin, resident)):
+        d = step_difference(script, mode, i, t, r)
+        if d:
+            return d
+    return None
+
+
+@functools.lru_cache(maxsize=1)
+def twin_record(name):
+    """the twin's pass of a script: run before any resident pass and shared by the modes (one script's record is kept at a time: it holds every step's full state)"""
+    return run_twin(BY_NAME[name])
+
+
+def compare(script: Script, mode, upto=None):
+    """rerun any prefix of a script both ways -> the first difference or None"""
+    return run_resident(script, mode, upto, against=run_twin(script, upto))[1]

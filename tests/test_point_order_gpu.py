@@ -12,7 +12,7 @@ import order_cases as oc
 import pool_cases
 import seed_cases as sd
 import stream_cases as sc
-from frame_cases import make_sim, random_state
+from frame_cases import LAUNCH_RANGES, launch_range, make_sim, random_state
 from hnanosolver_amd import _lib, api, device, fields, leafio
 from hnanosolver_amd._lib import lib
 
@@ -77,6 +77,31 @@ def test_grids_levels_and_counts(name, level):
         what = f"{name} level {level} count {count}"
         first = sort_and_check(po, grid, xyz, level, what)
         oc.same(sort_and_check(po, grid, xyz, level, what + " (again)"), first, what + ": the second sort of the same object")
+    po.close()
+
+
+@pytest.mark.parametrize("kind", LAUNCH_RANGES)
+def test_every_leaf_is_a_bin_whatever_the_launch_range(kind):
+    """include/hns.h: the order counts every leaf whatever the grid's launch range, ghost leaves included -- an object made before the range was narrowed and one made
+    under it give the whole range's permutation, keys and leaf ranges (which equal the host mirror) under set_active_range on a strict inner range and under
+    set_active_leaves(n // 2)"""
+    name = "ragged32"
+    grid, xyz = dev_grid(name), oc.full_set(name)
+    po = device.PointOrder(grid, len(xyz))
+    for level in oc.LEVELS:
+        whole = sort_and_check(po, grid, xyz, level, f"whole range, level {level}")
+        with launch_range(grid, kind):
+            x = to_dev(xyz)
+            po.sort(x, oc.LEVEL_NAMES[level])
+            got = results(po)
+            fresh = device.PointOrder(grid, len(xyz))
+            fresh.sort(x, oc.LEVEL_NAMES[level])
+            got_fresh, ranked = results(fresh), u32(fresh.gather(x))
+            fresh.close()
+        assert grid.active_leaves() == grid.leaf_count()
+        oc.same(got, whole, f"{kind}, level {level}")
+        oc.same(got_fresh, whole, f"{kind}, level {level}, an object made under the range")
+        assert np.array_equal(ranked, np.ascontiguousarray(xyz).view(np.uint32)[whole[0]]), f"{kind}, level {level}: gather"
     po.close()
 
 

@@ -13,7 +13,7 @@ import pytest
 
 import points_cases as pc
 import special_cases as sc
-from frame_cases import download, make_sim, random_state
+from frame_cases import LAUNCH_RANGES, download, launch_range, make_sim, random_state
 from oracle_lib import OracleGrid, oracle_device, reference_samplers
 
 pytestmark = pytest.mark.gpu
@@ -164,6 +164,29 @@ def test_many_field_calls_equal_one_field_calls(name):
         assert len(got) == S
         for i in range(S):
             assert_words(got[i], alone[which[i]], f"{name} S={S}: output {i}")
+
+
+@pytest.mark.parametrize("kind", LAUNCH_RANGES)
+def test_samples_and_traces_count_every_leaf_whatever_the_launch_range(kind):
+    """include/hns.h: a leaf counts as inside whatever the grid's launch range, ghost leaves included -- the bytes of the whole range (which the tests around this one hold
+    to the oracle and the mirror) under set_active_range on a strict inner range and under set_active_leaves(n // 2)"""
+    name = "ragged32"
+    R, (want_f, want_v) = rig(name), expected(name)
+    o, vel, _, xyz = pc.case(name)
+    fields, which = mixed_fields(R)
+    u = R.dev(pc.scaled_velocity(vel, 4.0, F(pc.DT) * F(pc.INV_DX)))
+    whole = R.sample(fields, xyz, "whole range")
+    whole_xyz, whole_status = R.trace(u, xyz, pc.DT, pc.INV_DX, 2, 3, "whole range")
+    assert 0 < whole_status.sum() < len(xyz)
+    with launch_range(R.grid, kind):
+        got = R.sample(fields, xyz, kind)
+        got_xyz, got_status = R.trace(u, xyz, pc.DT, pc.INV_DX, 2, 3, kind)
+    assert R.grid.active_leaves() == len(o)
+    for i, k in enumerate(which):
+        assert_words(got[i], whole[i], f"{kind}: output {i} (field {k}) against the whole range")
+        assert_words(got[i], want_v if k < 0 else want_f[k], f"{kind}: output {i} (field {k}) against the oracle")
+    assert_words(got_xyz, whole_xyz, f"{kind}: traced positions")
+    assert np.array_equal(got_status, whole_status), f"{kind}: status"
 
 
 # ---------------------------------------------------------------------------------------------------------------

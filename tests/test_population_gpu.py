@@ -12,7 +12,7 @@ import order_cases as oc
 import pool_cases
 import population_cases as P
 import stream_cases as sc
-from frame_cases import download, make_sim, random_masks, random_state
+from frame_cases import LAUNCH_RANGES, download, launch_range, make_sim, random_masks, random_state
 from hnanosolver_amd import _lib, api, device, fields, leafio
 from hnanosolver_amd._lib import lib
 
@@ -187,6 +187,34 @@ def test_birth_matches_the_mirror(grid_name, kind):
         got = device_birth(pop, lambda x, vox, **k: pop.birth(f, x, masks, vox, **k), rows, 0, True, spec, voxel=False)
         assert got[0].view(U32).tobytes() == want[0].view(U32).tobytes() and got[2:] == want[2:] and (got[1] == P.VOXEL_SENTINEL).all()
     assert u32(field).tobytes() == np.asarray(v).view(U32).tobytes(), "the field was written"
+    pop.close(), sim_pop.close(), sim.close()
+
+
+@pytest.mark.parametrize("kind", LAUNCH_RANGES)
+def test_every_leaf_bears_whatever_the_launch_range(kind):
+    """include/hns.h: every leaf bears whatever the grid's launch range, ghost leaves included -- the device form and the sim's form under set_active_range on a strict
+    inner range and under set_active_leaves(n // 2) give the rows, voxels and counts of the whole range, which equal the mirror"""
+    o, grid, host = P.origins("ragged32"), dev_grid("ragged32"), P.host_grid("ragged32")
+    rng = np.random.default_rng(32)
+    v = rng.uniform(-0.5, 2.0, len(o) * 512).astype(F)
+    m = np.packbits((rng.random((len(o), 512)) < 0.5).reshape(len(o), 64, 8), axis=2, bitorder="little").reshape(len(o), 64)
+    spec = dict(P.SPEC)
+    rows = leafio.birth_points(host, v, m, **spec, capacity_rows=0)[3] + 5
+    want = leafio.birth_points(host, v, m, **spec, fill=True, start=0, capacity_rows=rows, xyz=P.sentinels(rows)[0], voxel=P.sentinels(rows)[1])
+    field, masks = to_dev(v), to_dev(m)
+    pop = device.PointPopulation(grid, 16)
+    sim_grid, sim = make_sim(o, ["flame"], {"vel": np.zeros((len(o) * 512, 3), dtype=F), "flame": v}, m, VS)
+    sim_pop = sim.point_population(0)
+    forms = {"device form": (pop, lambda x, vox, **k: pop.birth(field, x, masks, vox, **k)), "sim": (sim_pop, lambda x, vox, **k: sim.birth(sim_pop, "flame", x, vox, use_masks=True, **k))}
+    for form, (p, call) in forms.items():
+        whole = device_birth(p, call, rows, 0, True, spec)
+        P.same_birth(whole, want, f"whole range ({form})")
+        with launch_range(p.grid, kind):
+            got = device_birth(p, call, rows, 0, True, spec)
+        assert p.grid.active_leaves() == len(o)
+        P.same_birth(got, whole, f"{kind} ({form})")
+        leaves = set((got[1][: got[2]] // 512).tolist())
+        assert {0, len(o) - 1} <= leaves and len(leaves) == len(o)  # (the leaves outside either range bore too)
     pop.close(), sim_pop.close(), sim.close()
 
 

@@ -14,7 +14,7 @@ import rasterize_cases as rc
 import seed_cases as sd
 import splat_cases as sp
 import stream_cases as stc
-from frame_cases import assert_same, download, make_sim, random_masks, random_state
+from frame_cases import LAUNCH_RANGES, assert_same, download, launch_range, make_sim, random_masks, random_state
 
 pytestmark = pytest.mark.gpu
 
@@ -121,6 +121,22 @@ def test_one_radius_per_point_with_the_special_values(bound):
         with np.errstate(invalid="ignore"):
             refused = ~((radii > 0) & (radii <= F(bound)))
         assert refused.sum() >= 20 and (status[refused] == 0).all() and (status[~refused] == 2).any()
+
+
+@pytest.mark.parametrize("kind", LAUNCH_RANGES)
+def test_footprints_land_in_every_leaf_whatever_the_launch_range(kind):
+    """include/hns.h: a footprint voxel lands in a leaf whatever the grid's launch range, ghost leaves included -- a radial sum and a radial average give the bytes of the
+    whole range, which equal the mirror, under set_active_range on a strict inner range and under set_active_leaves(n // 2)"""
+    R, (_, vel, phi, xyz, vals, vvals, _, _) = rig("ragged32"), rc.case("ragged32")
+    for mode in MODES:
+        kw = dict(kernel="radial", mode=mode, radius=2.5, min_weight=0.125 if mode == "average" else 0.0)
+        whole, whole_status = assert_equal_the_mirror(R, [phi[0], vel], xyz, [vals[0], vvals], -32, f"whole range, {mode}", **kw)
+        _, _, whole_rejected = R.splat([phi[0], vel], xyz, [vals[0], vvals], -32, f"whole range, {mode}", **kw)
+        with launch_range(R.grid, kind):
+            got, status, rejected = R.splat([phi[0], vel], xyz, [vals[0], vvals], -32, f"{kind}, {mode}", **kw)
+        assert R.grid.active_leaves() == R.grid.leaf_count()
+        assert sp.same_bytes(got[0], whole[0]) and sp.same_bytes(got[1], whole[1]), f"{kind}, {mode}: a field differs from the whole range's"
+        assert sp.same_bytes(status, whole_status) and rejected == whole_rejected, f"{kind}, {mode}: status or rejected"
 
 
 # ---------------------------------------------------------------------------------------------------------------

@@ -1,0 +1,133 @@
+"""The vocabulary and the scripts of tests/test_sequences_gpu.py, checked without a GPU from the declared read / write table and the script lists alone: every entry point
+of a sim, a point order and a point population is an operation or a stated exemption; every pair of operation kinds where the first writes what the second reads is
+adjacent in some script; every writer of the velocity and every change of grid sits between two look-ahead substeps; no script holds a step the library would refuse."""
+import numpy as np
+import pytest
+
+import sequence_cases as sq
+from hnanosolver_amd import _lib
+
+PREFIXES = ("hns_sim_", "hns_point_order_", "hns_point_population_")
+
+
+def bound_symbols():
+    return [n for n in _lib.SIGNATURES if n.startswith(PREFIXES)]
+
+
+def undecided_symbols(ops):
+    used = set(sq.RUNNER_SYMBOLS) | {s for o in ops.values() for s in o.symbols}
+    return [n for n in bound_symbols() if n not in used and n not in sq.EXEMPT]
+
+
+def uncovered_pairs(ops, scripts):
+    """the needed pairs of the operations `ops` that no script of `scripts` holds adjacent (a script that names a missing operation holds nothing)"""
+    scripts = [s for s in scripts if all(k in ops for k, _ in s.steps)]
+    need = {p for p, ways in sq.needed_pairs().items() if any(a in ops and b in ops for a, b in ways)}
+    return sorted(need - set(sq.covered_pairs(scripts)))
+
+
+def test_every_entry_point_is_an_operation_or_exempt():
+    """a new hns_sim_* / hns_point_order_* / hns_point_population_* entry point fails here until it joins the vocabulary or states why it needs no place in it"""
+    assert len(bound_symbols()) >= 50
+    assert not undecided_symbols(sq.OPS), f"entry points that are neither used by an operation of sequence_cases.OPS nor in EXEMPT: {undecided_symbols(sq.OPS)}"
+    named = set(sq.RUNNER_SYMBOLS) | set(sq.EXEMPT) | {s for o in sq.OPS.values() for s in o.symbols}
+    assert not named - set(_lib.SIGNATURES), f"symbols _lib.py does not bind: {sorted(named - set(_lib.SIGNATURES))}"
+    used = set(sq.RUNNER_SYMBOLS) | {s for o in sq.OPS.values() for s in o.symbols}
+    assert not used & set(sq.EXEMPT), "an exemption for a symbol that is used"
+    assert all(isinstance(r, str) and len(r) > 40 and "\n" not in r for r in sq.EXEMPT.values())
+
+
+def test_the_table_is_well_formed():
+    for name, o in sq.OPS.items():
+        assert o.reads <= set(sq.RESOURCES) and o.writes <= set(sq.RESOURCES), name
+        assert o.symbols and o.memo in ("produce", "consume", "drop", "keep") and o.requires <= {"order", "fresh_order"}, name
+        assert o.needs <= set(sq.PROFILES["collide"]), name
+        if "vel" in o.writes or o.grid:  # include/hns.h: what was looked ahead is dropped by everything else that writes the velocity
+            assert o.memo != "keep", name
+        if o.memo in ("produce", "consume"):
+            assert o.kind in ("substep", "core_substep"), name
+    assert len(sq.KINDS) >= 20 and sq.PRODUCERS == {"core_substep", "substep_unfused"}
+
+
+def test_every_operation_is_in_a_script_and_every_script_is_of_operations():
+    used = {k for s in sq.SCRIPTS for k, _ in s.steps}
+    assert not used - set(sq.OPS), f"scripts name operations the vocabulary lacks: {sorted(used - set(sq.OPS))}"
+    assert not set(sq.OPS) - used, f"operations no script holds: {sorted(set(sq.OPS) - used)}"
+    assert len({s.name for s in sq.SCRIPTS}) == len(sq.SCRIPTS) <= 14
+    seeds = [sd for s in sq.SCRIPTS for _, sd in s.steps] + [s.seed for s in sq.SCRIPTS]
+    assert len(seeds) == len(set(seeds))
+    for s in sq.SCRIPTS:
+        assert 2 <= len(s.steps) <= 26 and s.profile in sq.PROFILES, s.name
+    assert any(s.timing for s in sq.SCRIPTS) and not all(s.timing for s in sq.SCRIPTS)
+    assert {s.profile for s in sq.SCRIPTS} == set(sq.PROFILES)
+    assert any("birth_overflow" in [k for k, _ in s.steps] for s in sq.SCRIPTS)
+
+
+def test_every_dependent_pair_of_kinds_is_adjacent_in_a_script():
+    """(A, B) with A writing what B reads, B followed by the full download both runners take after every step"""
+    need = sq.needed_pairs()
+    assert len(need) >= 150 and ("splat", "core_substep") in need and ("regrid", "pressure") in need and ("deactivate", "regrid") in need
+    assert ("trace", "order_splat") not in need  # (an ordered splat requires a sort since the last write of the positions: never adjacent, by the table's `breaks`)
+    missing = uncovered_pairs(sq.OPS, sq.SCRIPTS)
+    assert not missing, f"pairs of operation kinds no script holds adjacent: {missing}"
+
+
+def test_writers_of_the_velocity_sit_between_two_lookahead_substeps():
+    """every substep, advect and trace of every script runs with sequence_cases.DT and VS, so two look-ahead substeps either side of a step are substeps of equal dt and
+    voxel size: the memo is live when the writer comes"""
+    writers = sq.placed_writers()
+    assert {"upload_vel", "upload_field", "advect_velocity", "regrid_plain", "regrid_sourced", "regrid_seeded", "regrid_sdf", "emit_trilinear", "emit_radial", "deactivate",
+            "splat_velocity", "splat_both", "splat_stored", "order_splat_original", "substep_collision", "substep_fused"} <= set(writers)
+    assert "splat_floats" not in writers and "order_splat_ranked" not in writers  # (float fields only: the memo is of the velocity)
+    placed = sq.placements(sq.SCRIPTS)
+    assert not [k for k in writers if k not in placed], f"never between two look-ahead substeps: {[k for k in writers if k not in placed]}"
+
+
+def test_no_script_holds_a_step_that_would_be_refused():
+    for s in sq.SCRIPTS:
+        assert not sq.refusals(s), f"script {s.name}: {sq.refusals(s)}"
+    bad = sq.Script("bad", "one", 1, False, (("sort_voxel", 2), ("trace", 3), ("order_splat_original", 4), ("regrid_plain", 5), ("gather_scatter", 6), ("substep_fused", 7)))
+    assert [i for i, _ in sq.refusals(bad)] == [2, 4, 5]  # positions moved since the sort; no order on the new grid; a field the profile lacks
+
+
+@pytest.mark.parametrize("gone", [("deactivate", "deactivate_counts"), ("pressure_residual",), ("order_splat_original", "order_splat_ranked"), ("birth", "birth_append", "birth_overflow")])
+def test_a_deleted_operation_is_noticed(gone):
+    """the conditions name what goes uncovered when an operation leaves the vocabulary"""
+    ops = {k: o for k, o in sq.OPS.items() if k not in gone}
+    lost = {s for k in gone for s in sq.OPS[k].symbols} - set(sq.RUNNER_SYMBOLS) - {s for o in ops.values() for s in o.symbols}
+    assert lost and set(undecided_symbols(ops)) == lost
+    assert uncovered_pairs(ops, sq.SCRIPTS)  # (the scripts that named it no longer count)
+
+
+def test_expected_lookahead_counts():
+    s = sq.Script("x", "combust", 1, False, tuple((k, i) for i, k in enumerate(
+        ["core_substep", "substep_unfused", "splat_floats", "core_substep", "deactivate", "core_substep", "substep_fused", "core_substep", "substep_collision", "core_substep"])))
+    #                                 produce  consume+produce  keep    consume+produce  drop    produce  consume  produce  drop    produce
+    assert sq.expected_lookahead(s) == [(1, 0), (2, 1), (2, 1), (3, 2), (3, 2), (4, 2), (4, 3), (5, 3), (5, 3), (6, 3)]
+    assert sq.has_two_equal_substeps(s) and not sq.has_two_equal_substeps(sq.Script("y", "one", 1, False, (("core_substep", 1), ("stats", 2), ("core_substep", 3))))
+    assert sum(sq.has_two_equal_substeps(s) for s in sq.SCRIPTS) >= 3
+
+
+def test_first_difference_names_script_mode_step_operations_array_and_words():
+    s = sq.SCRIPTS[0]
+    a = np.arange(12, dtype=np.float32)
+    twin = [({"status": np.zeros(5, dtype=np.uint8)}, {"vel": a.copy(), "live": None}) for _ in range(3)]
+    same = [({"status": np.zeros(5, dtype=np.uint8)}, {"vel": a.copy(), "live": None}, (0, 0)) for _ in range(3)]
+    assert sq.first_difference(s, "1", twin, same) is None
+    same[2][1]["vel"][7] = -a[7]
+    same[2][1]["vel"][9] = np.nan
+    msg = sq.first_difference(s, "1", twin, same)
+    assert msg.startswith(f"script {s.name}, lookahead = 1, step 2 ({s.steps[2][0]}, after {s.steps[1][0]}): state vel differs in 2 of 12 words, first at word 7"), msg
+    same[1][0]["status"][4] = 1  # an earlier step, in what it returned; a byte array compares byte by byte
+    assert "step 1" in sq.first_difference(s, "1", twin, same) and "returned status differs in 1 of 5" in sq.first_difference(s, "1", twin, same)
+    zero = [({}, {"vel": np.zeros(2, dtype=np.float32)})]
+    assert "differs in 1 of 2 words" in sq.first_difference(s, "auto", zero, [({}, {"vel": np.array([0.0, -0.0], dtype=np.float32)}, (0, 0))])  # a zero's sign counts
+
+
+def test_the_generator_still_draws_scripts_that_meet_the_conditions():
+    """the committed lists are what is tested; the generator is kept to draw new ones when the table grows, so it must keep working on the table as it stands"""
+    drawn, left = sq.draw_scripts()
+    assert not left and not uncovered_pairs(sq.OPS, drawn) and len(drawn) <= 14
+    assert not [k for k in sq.placed_writers() if k not in sq.placements(drawn)]
+    assert all(not sq.refusals(s) and len(s.steps) <= 24 for s in drawn)
+    assert "Script(" in sq.format_scripts(drawn)

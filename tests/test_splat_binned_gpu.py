@@ -17,7 +17,7 @@ import rasterize_cases as rc
 import seed_cases as sd
 import splat_cases as sp
 import stream_cases as sc
-from frame_cases import download, make_sim, random_state
+from frame_cases import LAUNCH_RANGES, download, launch_range, make_sim, random_state
 from pool_cases import arena_fill
 
 pytestmark = pytest.mark.gpu
@@ -143,6 +143,24 @@ def test_ordered_splat_equals_the_mirror(name, n):
         for level in LEVELS:
             for rows in bc.ROWS:
                 assert_equal_the_mirror(R, fields, c["xyz"][:n], [v[:n] for v in values], f"{name} n={n} {label} {level} {rows}", level=level, rows=rows)
+
+
+@pytest.mark.parametrize("kind", LAUNCH_RANGES)
+def test_every_leaf_is_summed_whatever_the_launch_range(kind):
+    """include/hns.h: the order and the splat landing count every leaf whatever the grid's launch range, ghost leaves included -- sort and ordered splat under
+    set_active_range on a strict inner range and under set_active_leaves(n // 2) give the bytes of the whole range, which equal the mirror"""
+    R, c = rig("ragged32"), bc.case("ragged32")
+    fields, values = bc.channel_sets("ragged32")["float+vec3"]
+    for level in LEVELS:
+        for rows in bc.ROWS:
+            whole = assert_equal_the_mirror(R, fields, c["xyz"], values, f"whole range {level} {rows}", level=level, rows=rows)
+            _, whole_status, whole_rejected = R.ordered(fields, c["xyz"], values, -32, level, rows, f"whole range {level} {rows}")
+            with launch_range(R.grid, kind):
+                got, status, rejected = R.ordered(fields, c["xyz"], values, -32, level, rows, f"{kind} {level} {rows}")
+            assert R.grid.active_leaves() == R.grid.leaf_count()
+            for i in range(len(fields)):
+                assert sp.same_bytes(got[i], whole[i]), f"{kind} {level} {rows}: field {i} differs from the whole range's"
+            assert np.array_equal(status, whole_status) and rejected == whole_rejected, f"{kind} {level} {rows}: status or rejected"
 
 
 @pytest.mark.parametrize("radius", rc.RADII)

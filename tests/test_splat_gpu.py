@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 import splat_cases as sp
-from frame_cases import download, make_sim, random_state
+from frame_cases import LAUNCH_RANGES, download, launch_range, make_sim, random_state
 from pool_cases import arena_fill
 
 pytestmark = pytest.mark.gpu
@@ -98,6 +98,22 @@ def test_device_equals_the_mirror_at_every_quantum(name, q):
     R, xyz = rig(name), sp.case(name)[3]
     fields, values = sp.channel_sets(name)["float+vec3"]
     assert_equal_the_mirror(R, fields, xyz, values, q, f"{name} Q={q}")
+
+
+@pytest.mark.parametrize("kind", LAUNCH_RANGES)
+def test_taps_land_in_every_leaf_whatever_the_launch_range(kind):
+    """include/hns.h: a tap lands in a leaf whatever the grid's launch range, ghost leaves included -- the bytes of the whole range, which equal the mirror, under
+    set_active_range on a strict inner range and under set_active_leaves(n // 2)"""
+    R, xyz = rig("ragged32"), sp.case("ragged32")[3]
+    fields, values = sp.channel_sets("ragged32")["float+vec3"]
+    whole = assert_equal_the_mirror(R, fields, xyz, values, -32, "whole range")
+    _, whole_status, whole_rejected = R.splat(fields, xyz, values, -32, "whole range")
+    with launch_range(R.grid, kind):
+        got, status, rejected = R.splat(fields, xyz, values, -32, kind)
+    assert R.grid.active_leaves() == R.grid.leaf_count()
+    for i in range(len(fields)):
+        assert sp.same_bytes(got[i], whole[i]), f"{kind}: field {i} differs from the whole range's"
+    assert sp.same_bytes(status, whole_status) and rejected == whole_rejected, f"{kind}: status or rejected"
 
 
 def test_special_values_equal_the_mirror():
