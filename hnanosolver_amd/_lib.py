@@ -78,6 +78,13 @@ class hns_splat_spec(C.Structure):
     _fields_ = [("kernel", C.c_int), ("mode", C.c_int), ("radius", C.c_float), ("d_radius", C.c_void_p), ("min_weight", C.c_float)]
 
 
+class hns_point_collision(C.Structure):
+    _fields_ = [("mode", C.c_int), ("threshold", C.c_float), ("skin", C.c_float), ("iterations", C.c_int)]
+
+
+HNS_COLLIDE_STOP, HNS_COLLIDE_PUSH, HNS_COLLIDE_KILL = 1, 2, 3
+
+
 class hns_point_order_info(C.Structure):
     _fields_ = [("perm", C.c_void_p), ("keys", C.c_void_p), ("leaf_start", C.c_void_p), ("n", C.c_uint64), ("n_leaves", C.c_uint64), ("capacity", C.c_uint64),
                 ("level", C.c_int)]
@@ -179,6 +186,8 @@ SIGNATURES = {
     "hns_dev_advect_scalars_ahead": (_i, [_vp, _fp, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _i, _fp, _f, _f, _vp]),
     "hns_dev_sample_points": (_i, [_vp, C.POINTER(C.c_void_p), _ip, _i, _fp, _u64, C.POINTER(C.c_void_p), _vp]),
     "hns_dev_trace_points": (_i, [_vp, _fp, _fp, _u64, _f, _f, _i, _i, _vp, _vp]),
+    "hns_dev_trace_points_collide": (_i, [_vp, _fp, _fp, _fp, _u64, _f, _f, _i, _i, C.POINTER(hns_point_collision), _vp, _vp, _vp]),
+    "hns_sim_trace_points_collide": (_i, [_vp, _fp, _u64, _f, _f, _i, _i, C.POINTER(hns_point_collision), _vp, _vp, _vp]),
     "hns_dev_splat_points": (_i, [_vp, C.POINTER(C.c_void_p), _ip, _i, _fp, C.POINTER(C.c_void_p), _u64, _i, _vp, _vp, _vp]),
     "hns_grid_splat_points": (_i, [_vp, C.POINTER(C.c_void_p), _ip, _i, _fp, C.POINTER(C.c_void_p), _u64, _i, _vp, _i, _vp, C.POINTER(C.c_uint64)]),
     "hns_grid_set_splat_spec": (_i, [_vp, C.POINTER(hns_splat_spec)]),

@@ -22,31 +22,7 @@ struct PointFields {
 
 // the cell under a position, its tap indices and fractions (Cell, Cursor, point_cell): hns_points.hpp, shared with hns_splat.hip
 
-// value or 0 outside the domain (IndexSampler<float,0>, Stencils.hpp:81-89) without a branch: the eight taps of a sample are issued together. (Reads element 0 for an
-// absent leaf: the launchers keep empty grids away from the kernels.)
-__device__ __forceinline__ float ldz(const float* __restrict__ f, int idx) {
-	const float v = f[idx < 0 ? 0 : idx];
-	return idx < 0 ? 0.0f : v;
-}
-
-// IndexSampler<float,1>: the nest z, y, x with the unfused lerp
-__device__ __forceinline__ float sample_f(const float* __restrict__ f, const Cell& C) {
-	float c[8];
-#pragma unroll
-	for (int q = 0; q < 8; ++q) c[q] = ldz(f, C.t[q]);
-	return tri_nest(c, C.fx, C.fy, C.fz, lerp_f);
-}
-
-// IndexSampler<Vec3f,1> on the device branch (Stencils.hpp:131-135): the same nest per component with fmaf(w, b - a, a); eight 12-byte taps
-__device__ __forceinline__ f3 sample_v(const float* __restrict__ u, const Cell& C) {
-	float x[8], y[8], z[8];
-#pragma unroll
-	for (int q = 0; q < 8; ++q) {
-		const f3 c = ld3z(u, C.t[q]);
-		x[q] = c.x, y[q] = c.y, z[q] = c.z;
-	}
-	return f3{tri_nest(x, C.fx, C.fy, C.fz, lerp_c), tri_nest(y, C.fx, C.fy, C.fz, lerp_c), tri_nest(z, C.fx, C.fy, C.fz, lerp_c)};
-}
+// (ldz, sample_f, sample_v -- the two samplers over a Cell: hns_points.hpp, shared with hns_points_collide.hip)
 
 // Up to eight fields, float or Vec3f, at n positions: one Floor, one set of tap indices and fractions for all of them. Output q is what a launch with field q alone gives.
 __global__ __launch_bounds__(kPointBlock) void k_sample_points(const GridDev g, const PointFields P, const float* __restrict__ xyz, const unsigned n) {

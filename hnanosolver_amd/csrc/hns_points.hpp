@@ -1,5 +1,5 @@
 // hns_points.hpp -- the trilinear cell under an index-space position, shared by the kernel files that work at points: hns_points.hip (fields read at points, points
-// traced through the velocity), hns_splat.hip (point values added into fields), hns_rasterize.hip (the same with a radius) and hns_splat_binned.hip (the same through a leaf order). One statement of Floor, the tap indices and
+// traced through the velocity), hns_points_collide.hip (the same against a collision SDF), hns_splat.hip (point values added into fields), hns_rasterize.hip (the same with a radius) and hns_splat_binned.hip (the same through a leaf order). One statement of Floor, the tap indices and
 // the fractions for both directions, and one of the splat's arithmetic -- weights, footprint, term, total, average -- for the kernels and the host mirror.
 #pragma once
 
@@ -80,6 +80,34 @@ __device__ __forceinline__ Cell point_cell(const GridDev& g, Cursor& cur, float 
 }
 
 __device__ __forceinline__ bool finite_f(float a) { return (__float_as_uint(a) & 0x7fffffffu) < 0x7f800000u; }
+
+// ---- the samplers over a Cell: what hns_points.hip and hns_points_collide.hip share ------------------------------------------------------------------------------------
+
+// value or 0 outside the domain (IndexSampler<float,0>, Stencils.hpp:81-89) without a branch: the eight taps of a sample are issued together. (Reads element 0 for an
+// absent leaf: the launchers keep empty grids away from the kernels.)
+__device__ __forceinline__ float ldz(const float* __restrict__ f, int idx) {
+	const float v = f[idx < 0 ? 0 : idx];
+	return idx < 0 ? 0.0f : v;
+}
+
+// IndexSampler<float,1>: the nest z, y, x with the unfused lerp
+__device__ __forceinline__ float sample_f(const float* __restrict__ f, const Cell& C) {
+	float c[8];
+#pragma unroll
+	for (int q = 0; q < 8; ++q) c[q] = ldz(f, C.t[q]);
+	return tri_nest(c, C.fx, C.fy, C.fz, lerp_f);
+}
+
+// IndexSampler<Vec3f,1> on the device branch (Stencils.hpp:131-135): the same nest per component with fmaf(w, b - a, a); eight 12-byte taps
+__device__ __forceinline__ f3 sample_v(const float* __restrict__ u, const Cell& C) {
+	float x[8], y[8], z[8];
+#pragma unroll
+	for (int q = 0; q < 8; ++q) {
+		const f3 c = ld3z(u, C.t[q]);
+		x[q] = c.x, y[q] = c.y, z[q] = c.z;
+	}
+	return f3{tri_nest(x, C.fx, C.fy, C.fz, lerp_c), tri_nest(y, C.fx, C.fy, C.fz, lerp_c), tri_nest(z, C.fx, C.fy, C.fz, lerp_c)};
+}
 
 // ---- point values into fields: what hns_splat.hip and hns_rasterize.hip share ----------------------------------------------------------------------------------------
 

@@ -175,6 +175,27 @@ def trace_points(grid: IndexGridHandle, vel, xyz, dt: float, inv_dx: float, orde
     return xyz
 
 
+COLLIDE_MODES = {"stop": _lib.HNS_COLLIDE_STOP, "push": _lib.HNS_COLLIDE_PUSH, "kill": _lib.HNS_COLLIDE_KILL}
+
+
+def _collision(who: str, mode, threshold: float, skin: float, iterations: int):
+    if mode not in COLLIDE_MODES:
+        raise ValueError(f"{who}: mode must be one of {sorted(COLLIDE_MODES)}, not {mode!r}")
+    return _lib.hns_point_collision(COLLIDE_MODES[mode], float(threshold), float(skin), int(iterations))
+
+
+def trace_points_collide(grid: IndexGridHandle, vel, sdf, xyz, dt: float, inv_dx: float, order: int = 2, steps: int = 1, *, mode: str, threshold: float = 0.0,
+                         skin: float = 1 / 16, iterations: int = 2, status=None, hit=None):
+    """``trace_points`` against the collision SDF `sdf` (a float field of the grid), tested after every step inside the launch (``hns_dev_trace_points_collide``). A point
+    whose step ends where the SDF's sample is below `threshold` is, by `mode`, put back ("stop"), pushed out along the SDF's normal by its depth plus `skin` voxels, up to
+    `iterations` times, and put back if still inside ("push"), or frozen and marked dead ("kill"). status: None or a uint8 tensor of n bytes, 1 where the point is alive,
+    finite and inside a leaf. hit: None or a uint8 tensor of n bytes: 1 pushed, 2 put back, 4 killed, 8 started inside, ORed. Asynchronous on the current stream."""
+    spec = _collision("trace_points_collide", mode, threshold, skin, iterations)
+    _raise(lib.hns_dev_trace_points_collide(grid.ptr, _ptr(vel), _ptr(sdf), _ptr(xyz), xyz.shape[0], dt, inv_dx, int(order), int(steps), C.byref(spec), _byte_ptr(status),
+                                            _byte_ptr(hit), current_stream()))
+    return xyz
+
+
 def _u64_ptr(t) -> int:
     if t is None:
         return 0
@@ -630,13 +651,25 @@ class Sim:
         _raise(lib.hns_sim_sample_points(self._ptr, arr, len(names), int(velocity), _ptr(xyz), n, dst, current_stream() if stream is None else stream))
         return out
 
-    def trace(self, xyz, *, dt: float, voxel_size: float, order: int = 2, steps: int = 1, status: bool = False, stream: Optional[int] = None):
+    def trace(self, xyz, *, dt: float, voxel_size: float, order: int = 2, steps: int = 1, status: bool = False, stream: Optional[int] = None, collide: Optional[str] = None,
+              threshold: float = 0.0, skin: float = 1 / 16, iterations: int = 2, hit: bool = False):
         """`steps` steps of the points xyz (moved in place) through the sim's current velocity (``hns_sim_trace_points``); with `status` returns the uint8 tensor
-        that is 1 where a point ended finite and inside a leaf. Asynchronous on `stream` (None: the current stream); the sim is only read."""
-        st = _torch().empty(xyz.shape[0], dtype=_torch().uint8, device=xyz.device) if status else None
-        _raise(lib.hns_sim_trace_points(self._ptr, _ptr(xyz), xyz.shape[0], dt, voxel_size, int(order), int(steps), _byte_ptr(st),
-                                        current_stream() if stream is None else stream))
-        return st
+        that is 1 where a point ended finite and inside a leaf. Asynchronous on `stream` (None: the current stream); the sim is only read.
+        collide: None, or "stop", "push" or "kill": the sim's field collision_sdf is tested after every step (``hns_sim_trace_points_collide``, ``trace_points_collide``
+        for threshold, skin and iterations); with `hit` the return value is (status or None, the uint8 tensor of hit bits)."""
+        spec = None if collide is None else _collision("Sim.trace", collide, threshold, skin, iterations)
+        t = _torch()
+        st = t.empty(xyz.shape[0], dtype=t.uint8, device=xyz.device) if status else None
+        stream = current_stream() if stream is None else stream
+        if spec is None:
+            if hit:
+                raise ValueError("Sim.trace: hit needs collide")
+            _raise(lib.hns_sim_trace_points(self._ptr, _ptr(xyz), xyz.shape[0], dt, voxel_size, int(order), int(steps), _byte_ptr(st), stream))
+            return st
+        ht = t.empty(xyz.shape[0], dtype=t.uint8, device=xyz.device) if hit else None
+        _raise(lib.hns_sim_trace_points_collide(self._ptr, _ptr(xyz), xyz.shape[0], dt, voxel_size, int(order), int(steps), C.byref(spec), _byte_ptr(st), _byte_ptr(ht),
+                                                stream))
+        return (st, ht) if hit else st
 
     def splat(self, values: dict, xyz, velocity=None, log2_quantum: int = -32, activate: bool = True, status: bool = False, rejected=None, stream: Optional[int] = None, *,
               kernel: str = "trilinear", mode: str = "add", radius=None, max_radius: Optional[float] = None, min_weight: float = 0.0, order: Optional[PointOrder] = None,

@@ -593,6 +593,47 @@ int hns_dev_sample_points(hns_grid*, const float* const* fields, const int* ncom
  * anything is launched (HNS_ERR_INVALID_ARGUMENT), positions and status untouched: a null xyz or vel3, an order not in {1, 2, 4}, steps < 1, a NaN dt, an inv_dx that is
  * not a positive finite number, n above 2^31 - 1, xyz, status and vel3 not three different buffers. Neither call is mirrored in hns_dist_*. */
 int hns_dev_trace_points(hns_grid*, const float* vel3, float* xyz, uint64_t n, float dt, float inv_dx, int order, int steps, unsigned char* status, void* stream);
+/* Points through the velocity against a collision SDF: hns_dev_trace_points with the SDF tested after every step, inside the same launch. sdf: a float field of the grid
+ * (device), only read. Every line below is one rounded float32 operation per component, none contracted.
+ *   Samplers S(x) is the float sample of hns_dev_sample_points on sdf (IndexSampler<float,1>, the unfused lerp, an absent tap reads 0); U the Vec3f sample; RK(x) one step
+ *            of hns_dev_trace_points at `order`, with exactly its operations. A position x is IN COLLISION iff S(x) < threshold (0.0f: the reference's
+ *            isInCollision(.., 0.0f)); a NaN sample is no collision.
+ *   Start    bit 3 (value 8) of hit is set iff S(x_start) < threshold.
+ *   Step     for a point that is not dead: x0 = x; x1 = RK(x0); d = S(x1). If !(d < threshold), x = x1. Otherwise by mode:
+ *   STOP     x = x0; hit |= 2 (the reference's rule for a back-trace that lands in the collider, Kernel.cu:144-147).
+ *   KILL     x = x1; the point is dead and takes no further step; hit |= 4.
+ *   PUSH     hit |= 1; then up to `iterations` times while d < threshold:
+ *              nb = S(x1 -+ e_axis) in the order -x, +x, -y, +y, -z, +z, each position formed as x1.c - 1.0f or x1.c + 1.0f, each a full sample with its own Floor;
+ *              n  = the normalised central difference of hns_dev_enforce_collision_boundaries: g.c = (0.5f * inv_dx) * (nb[+c] - nb[-c]),
+ *                   len = sqrtf((g.x*g.x + g.y*g.y) + g.z*g.z), n.c = (1.0f / len) * g.c if len > 1e-6f, else n = 0;
+ *              a  = (threshold - d) * inv_dx; a = a + skin;
+ *              x1.c = x1.c + a * n.c (a multiply, then an add); d = S(x1).
+ *            After the loop: if still d < threshold, x = x0 and hit |= 2; otherwise x = x1.
+ *   Outputs  status: NULL, or n bytes: 1 iff the point is not dead, its final position is finite in all three components and the leaf of its cell exists (the rule of
+ *            hns_dev_trace_points, a dead point counting as outside: hns_point_population_select with at_least = 1 drops it). hit: NULL, or n bytes: the OR of the bits
+ *            above over all steps; 0 for a point that never touched anything.
+ * skin is an index-space distance added to every push; iterations (1 .. 8) is read by PUSH only but must be in range in every mode. Caveat: a leaf that the source of an
+ * SDF lacks holds 2.4e-38f in reference-style data, and a tap outside the domain reads 0, so only threshold <= 0 is meaningful there; a positive threshold is allowed and
+ * flags such places. Asynchronous on `stream`, no device allocation; n == 0 launches nothing and looks at no device pointer (the numbers and the spec, a host struct, are checked whatever n); on a grid with no leaves status and hit are set to 0
+ * and nothing moves. Refused before anything is launched (HNS_ERR_INVALID_ARGUMENT, the call and the argument in the message), positions, status and hit untouched:
+ * everything hns_dev_trace_points refuses, a null spec, a mode outside 1 .. 3, a threshold that is NaN or infinite, a skin that is NaN, infinite or negative, iterations
+ * outside 1 .. 8, a null sdf, any two of xyz, vel3, sdf, status and hit being the same buffer. Not mirrored in hns_dist_*. */
+#define HNS_COLLIDE_STOP 1
+#define HNS_COLLIDE_PUSH 2
+#define HNS_COLLIDE_KILL 3
+typedef struct hns_point_collision {
+	int mode;        /* HNS_COLLIDE_*: 1 .. 3 */
+	float threshold; /* finite; a position is in collision iff S(x) < threshold */
+	float skin;      /* finite, >= 0; index-space distance added to every push */
+	int iterations;  /* 1 .. 8 pushes per step (PUSH only; the other modes ignore it but it must still be in range) */
+} hns_point_collision;
+int hns_dev_trace_points_collide(hns_grid*, const float* vel3, const float* sdf, float* xyz, uint64_t n, float dt, float inv_dx, int order, int steps,
+                                 const hns_point_collision*, unsigned char* status, unsigned char* hit, void* stream);
+/* The same on a sim's own buffers: its current velocity and its float field "collision_sdf", with inv_dx = 1.0f / voxel_size as hns_sim_trace_points forms it. The sim is
+ * only read: the look-ahead memo, the active masks, the feedback signatures and the solve report stay as they are. Refused besides the above: a sim without a float field
+ * "collision_sdf", a voxel_size that is not a positive finite number, a sim lent to a grid's cook cache. Not mirrored in hns_dist_*. */
+int hns_sim_trace_points_collide(hns_sim*, float* xyz, uint64_t n, float dt, float voxel_size, int order, int steps,
+                                 const hns_point_collision*, unsigned char* status, unsigned char* hit, void* stream);
 /* Point values into fields: the transpose of hns_dev_sample_points -- every point adds w * v to the eight voxels of its cell -- with an accumulation that does not depend on
  * the order the adds retire in. fields[i]: device pointer, ncomp[i] 1 (float) or 3 (Vec3f AoS), added into IN PLACE; values[i]: device, n x ncomp[i] floats, the value of
  * each point for field i; fields, ncomp and values are HOST arrays of n_fields (1 .. 8) entries; xyz as for hns_dev_sample_points.
