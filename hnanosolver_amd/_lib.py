@@ -208,6 +208,9 @@ SIGNATURES = {
     "hns_point_order_splat": (_i, [_vp, C.POINTER(C.c_void_p), _ip, _i, _fp, C.POINTER(C.c_void_p), _i, _i, _vp, _vp]),
     "hns_point_order_splat_sim": (_i, [_vp, _vp, C.POINTER(C.c_char_p), _i, _fp, _fp, C.POINTER(C.c_void_p), _i, _i, _i, _vp, _vp]),
     "hns_grid_sort_points": (_i, [_vp, _fp, _u64, _i, _vp, _vp, _vp]),
+    "hns_point_order_cells": (_i, [_vp, C.POINTER(C.c_void_p)]),
+    "hns_point_order_neighbours": (_i, [_vp, _fp, _i, _f, _vp, _fp, _fp]),
+    "hns_grid_point_neighbours": (_i, [_vp, _fp, _u64, _f, _vp, _fp, _fp]),
     "hns_point_population_create": (_vp, [_vp, _u64, _ip]),
     "hns_point_population_destroy": (None, [_vp]),
     "hns_point_population_set_stream": (_i, [_vp, _vp]),

@@ -17,6 +17,7 @@
 
 #include "hns_birth.hpp"
 #include "hns_dilate.hpp"
+#include "hns_neighbours.hpp"
 #include "hns_originhash.hpp"
 #include "hns_seed.hpp"
 #include "hns_stats.hpp"
@@ -420,6 +421,72 @@ int hns_grid_sort_points(const hns_grid* g, const float* xyz, uint64_t n, int le
 	if (leaf_start) {
 		leaf_start[0] = 0;
 		for (uint64_t q = 1; q < L + 3; ++q) leaf_start[q] = leaf_start[q - 1] + count[(size_t)q];
+	}
+	return HNS_OK;
+}
+
+// Point neighbourhoods (include/hns.h: "POINT NEIGHBOURHOODS THROUGH A LEAF ORDER"): the voxel keys of hns_grid_sort_points, a cell list by counting, and for every point
+// that takes part a walk over the cells of its box with the pair arithmetic of hns_neighbours.hpp. What hns_point_order_neighbours (hns_neighbours.hip) is checked
+// against, byte for byte; rows in the original order.
+int hns_grid_point_neighbours(const hns_grid* g, const float* xyz, uint64_t n, float radius, uint32_t* count, float* density, float* push) {
+	const char* who = "hns_grid_point_neighbours";
+	auto refused = [&](const char* what) {
+		set_error("%s: %s", who, what);
+		return HNS_ERR_INVALID_ARGUMENT;
+	};
+	if (!g) return refused("null grid");
+	if (n > kMaxSeedPoints) return refused("n is above 2^31 - 1");
+	if (!neighbour_radius(radius)) {
+		set_error("%s: radius %g (0 < radius <= 2)", who, (double)radius);
+		return HNS_ERR_INVALID_ARGUMENT;
+	}
+	if (n && !xyz) return refused("xyz is null");
+	if (!count && !density && !push) return refused("count, density and push are all null");
+	if ((count && (const void*)count == (const void*)xyz) || (density && density == xyz) || (push && push == xyz)) return refused("an output is xyz");
+	if ((count && (const void*)count == (const void*)density) || (count && (const void*)count == (const void*)push) || (density && density == push))
+		return refused("two outputs are the same buffer");
+	const uint64_t L = (uint64_t)g->topo.n_leaves;
+	if ((L + 2) * 512 > (uint64_t(1) << 32)) return refused("the grid's voxel keys do not fit 32 bits ((leaves + 2) * 512 > 2^32)");
+	if (!n) return HNS_OK;
+	if (int rc = hns_grid_host_tables(g)) return rc;
+	// cell list: start[v] .. start[v + 1] of `order` are the points of voxel v, in index order; a point in no cell takes no part
+	const uint32_t none = 0xFFFFFFFFu;
+	std::vector<uint32_t> cell((size_t)n, none), start((size_t)(512 * L + 1), 0);
+	for (uint64_t p = 0; p < n; ++p) {
+		const float* q = xyz + 3 * p;
+		if (!(seeds_f(q[0]) && seeds_f(q[1]) && seeds_f(q[2]))) continue;
+		const uint64_t off = g->topo.offset((int32_t)std::floor(q[0]), (int32_t)std::floor(q[1]), (int32_t)std::floor(q[2]));
+		if (!off) continue;
+		cell[(size_t)p] = (uint32_t)(off - 1);
+		++start[(size_t)off];
+	}
+	for (size_t v = 1; v < start.size(); ++v) start[v] += start[v - 1];
+	std::vector<uint32_t> order((size_t)start.back()), fill(start.begin(), start.end() - 1);
+	for (uint64_t p = 0; p < n; ++p)
+		if (cell[(size_t)p] != none) order[fill[cell[(size_t)p]]++] = (uint32_t)p;
+	const float inv = radial_inv(radius);
+	for (uint64_t p = 0; p < n; ++p) {
+		NeighbourSums s;
+		if (cell[(size_t)p] != none) {
+			const float* x = xyz + 3 * p;
+			int lo[3], hi[3];
+			for (int c = 0; c < 3; ++c) neighbour_box(x[c], radius, &lo[c], &hi[c]);
+			for (int i = lo[0]; i <= hi[0]; ++i)
+				for (int j = lo[1]; j <= hi[1]; ++j)
+					for (int k = lo[2]; k <= hi[2]; ++k) {
+						const uint64_t off = g->topo.offset(i, j, k);
+						if (!off) continue;
+						for (uint32_t at = start[(size_t)off - 1]; at < start[(size_t)off]; ++at) {
+							const uint32_t o = order[at];
+							if (o == p) continue;
+							const float* y = xyz + 3 * (size_t)o;
+							neighbour_pair(x[0], x[1], x[2], y[0], y[1], y[2], inv, s);
+						}
+					}
+		}
+		if (count) count[p] = s.count;
+		if (density) density[p] = neighbour_total(s.w);
+		if (push) push[3 * p] = neighbour_total(s.px), push[3 * p + 1] = neighbour_total(s.py), push[3 * p + 2] = neighbour_total(s.pz);
 	}
 	return HNS_OK;
 }

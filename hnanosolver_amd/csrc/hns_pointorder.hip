@@ -328,6 +328,7 @@ hns_point_order* hns_point_order_create(hns_grid* g, uint64_t capacity, int* err
 void hns_point_order_destroy(hns_point_order* o) {
 	if (!o) return;
 	if (o->arena) hns_arena_put(o->arena, o->arena_bytes, o->device);  // (waits for the device first)
+	if (o->cell_start) hns_arena_put(o->cell_start, o->cells_bytes, o->device);
 	delete o;
 }
 
@@ -352,7 +353,7 @@ int hns_point_order_sort(hns_point_order* o, const float* d_xyz, uint64_t n, int
 	if (n && !d_xyz) return refuse(who, "xyz is null");
 	const hipStream_t st = o->stream;
 	const unsigned L = (unsigned)o->n_leaves;
-	o->n = n, o->level = level, o->sorted = true;
+	o->n = n, o->level = level, o->sorted = true, o->cells_fresh = false;
 	if (!n) {
 		HNS_HIP(hipMemsetAsync(o->leaf_start, 0, 4 * (size_t)(L + 3), st));
 		return HNS_OK;

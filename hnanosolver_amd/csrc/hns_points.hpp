@@ -6,6 +6,7 @@
 #include <cmath>
 
 #include "hns_device.hpp"
+#include "hns_radial.hpp"
 #include "hns_seed.hpp"
 
 namespace hns {
@@ -146,21 +147,7 @@ __host__ __device__ inline int radial_lo(float c, float r) {
 	const float low = c - r;
 	return (int)floorf(low) + 1;
 }
-__host__ __device__ inline float radial_inv(float r) {
-	const float r2 = r * r;
-	return 1.0f / r2;
-}
-// the weight of the candidate (dx, dy, dz) away from the point; false: it is not in the footprint
-__host__ __device__ inline bool radial_weight(float dx, float dy, float dz, float inv, float* w) {
-	const float xx = dx * dx, yy = dy * dy, zz = dz * dz;
-	const float xy = xx + yy;
-	const float d2 = xy + zz;
-	const float q = d2 * inv;
-	if (!(q < 1.0f)) return false;
-	const float a = 1.0f - q;
-	*w = a * a;
-	return true;
-}
+// (radial_inv and radial_weight, the footprint's weight: hns_radial.hpp)
 
 // Is the term t accepted, and as which multiple of the quantum? scale = 2^-Q: the product is exact in f64 (a power of two, |t| < 2^128, scale <= 2^40), so the test is the
 // header's "t finite and |t| * 2^-Q < 2^62" (a NaN and an inf fail the comparison), and k = rint of it, ties to even.
@@ -175,8 +162,7 @@ __host__ __device__ inline bool splat_term(float t, double scale, long long* k) 
 	return true;
 }
 
-// what a non-zero accumulator adds to its voxel: quantum = 2^Q
-__host__ __device__ inline float splat_total(unsigned long long a, double quantum) { return (float)((double)(long long)a * quantum); }
+// (splat_total, what a non-zero accumulator adds to its voxel: hns_radial.hpp)
 
 // average: what a voxel with the non-zero weight accumulator a_w becomes
 __host__ __device__ inline float splat_average(unsigned long long a_v, unsigned long long a_w, double quantum, float min_weight) {
@@ -237,7 +223,7 @@ inline int check_sim(const hns_sim* s, const char* who) {
 
 }  // namespace hns
 
-// The leaf order of a point set (hns_pointorder.hip makes it; hns_splat_binned.hip reads perm, keys and leaf_start)
+// The leaf order of a point set (hns_pointorder.hip makes it; hns_splat_binned.hip and hns_neighbours.hip read perm, keys and leaf_start)
 struct hns_point_order {
 	hns_grid* grid = nullptr;
 	int device = -1;
@@ -251,6 +237,10 @@ struct hns_point_order {
 	uint64_t n = 0;
 	int level = -1;
 	bool sorted = false;
+	// the cell table of a voxel-level sort (hns_neighbours.hip): a pooled allocation of its own, drawn by the first call that needs it; stale after every sort
+	uint32_t* cell_start = nullptr;
+	size_t cells_bytes = 0;
+	bool cells_fresh = false;
 };
 
 namespace hns {

@@ -390,6 +390,39 @@ class PointOrder:
                                              _byte_ptr(status), _u64_ptr(rejected)))
         return fields
 
+    @property
+    def cell_start(self):
+        """512 * leaves + 1 entries: voxel v owns ranks cell_start[v] .. cell_start[v + 1] of the last sort, which must be by "voxel" (``hns_point_order_cells``) -- an
+        int32 view of the object's table, built on the stream of the last sort by the first call behind it, valid until the next sort; no wait"""
+        if self.level is None:
+            raise RuntimeError("PointOrder.cell_start: no sort has run on this object")
+        table = C.c_void_p(0)
+        _raise(lib.hns_point_order_cells(self._live(), C.byref(table)))
+        return self._words(table.value, 512 * self.grid.leaf_count() + 1)
+
+    def neighbours(self, xyz, radius: float, *, rows: str = "original", count=True, density=True, push=True):
+        """The points around each point of the last sort, which must be by "voxel" (``hns_point_order_neighbours``; include/hns.h states the definition): within `radius`
+        (0 < radius <= 2 voxels) of every point the number of other points, the sum of their weights (1 - d^2 / radius^2)^2 and the weighted sum of the unit vectors away
+        from them, each sum exact in multiples of 2^-32: the bytes of ``leafio.point_neighbours``. rows="original": xyz and the outputs are in the order the sort saw;
+        rows="ranked": in sorted order (``gather``). xyz must hold the positions of the last sort. count, density, push: True (made here), False (left out) or a tensor to
+        write -- (n,) int32 holding the uint32 words, (n,) float32, (n, 3) float32. -> a dict of the outputs asked for. Asynchronous on the stream of the last sort."""
+        r = self._splat_rows("PointOrder.neighbours", rows, xyz, [])
+        ptr, torch = self._live(), _torch()
+        out = {}
+        for name, want, shape, dtype in (("count", count, (self.n,), torch.int32), ("density", density, (self.n,), torch.float32), ("push", push, (self.n, 3), torch.float32)):
+            if want is False or want is None:
+                continue
+            t = torch.empty(shape, dtype=dtype, device=xyz.device) if want is True else want
+            if not t.is_cuda or not t.is_contiguous() or t.dtype != dtype or tuple(t.shape) != shape:
+                raise ValueError(f"PointOrder.neighbours: {name} must be a contiguous {dtype} tensor of shape {shape} on a HIP device")
+            out[name] = t
+        if not out:
+            raise ValueError("PointOrder.neighbours: none of count, density and push is asked for")
+        addr = lambda name: out[name].data_ptr() if name in out else 0
+        if self.n:  # (the outputs of no points are empty tensors, which have no address)
+            _raise(lib.hns_point_order_neighbours(ptr, _ptr(xyz), r, float(radius), addr("count"), addr("density"), addr("push")))
+        return out
+
     def close(self) -> None:
         if self._ptr:
             lib.hns_point_order_destroy(self._ptr)

@@ -185,6 +185,19 @@ def sort_points(grid, xyz, level="voxel"):
     return perm, keys, leaf_start
 
 
+def point_neighbours(grid, xyz, radius):
+    """Point neighbourhoods (``hns_grid_point_neighbours``; include/hns.h states the definition): xyz (n, 3) float32, index space, on `grid` (a host-only grid will do),
+    0 < radius <= 2 -> (count (n,) uint32: the points around each point; density (n,) float32: the sum of their weights; push (n, 3) float32: the weighted sum of the unit
+    vectors away from them), rows in the order of xyz. The host mirror of ``device.PointOrder.neighbours``."""
+    p = np.ascontiguousarray(xyz, dtype=np.float32)
+    if p.ndim != 2 or p.shape[1] != 3:
+        raise ValueError("point_neighbours: xyz must be an (n, 3) array")
+    n = len(p)
+    count, density, push = np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.float32), np.zeros((n, 3), dtype=np.float32)
+    _lib.check(lib.hns_grid_point_neighbours(grid.ptr, p.ctypes.data if n else None, n, float(radius), count.ctypes.data, density.ctypes.data, push.ctypes.data))
+    return count, density, push
+
+
 def birth_spec(threshold, rate, max_per_voxel, seed, fill=True) -> _lib.hns_birth_spec:
     """the ABI's hns_birth_spec (include/hns.h: "BIRTH AND DEATH OF POINTS"); the library refuses what is outside the rule"""
     return _lib.hns_birth_spec(float(threshold), float(rate), int(max_per_voxel), int(seed) & 0xFFFFFFFF, int(bool(fill)))

@@ -797,6 +797,44 @@ int hns_point_order_splat_sim(const hns_point_order*, hns_sim*, const char* cons
  * around std::stable_sort over hns_grid_offsets-style lookups; works on HNS_GRID_HOST_ONLY grids. The same bytes as the device's. Refusals as above, and a null perm
  * with n > 0. */
 int hns_grid_sort_points(const hns_grid*, const float* xyz, uint64_t n, int level, uint32_t* perm, uint32_t* keys, uint32_t* leaf_start);
+/* POINT NEIGHBOURHOODS THROUGH A LEAF ORDER: what relates a point to other points -- for every point the number of points around it, a density and a push away from
+ * them --, read off the order of a voxel-level sort. L is the grid's leaf count and inside = leaf_start[L]: the ranks below it are the points that sort and whose cell's
+ * leaf exists.
+ *   Cell table  cell_start has 512 * L + 1 uint32 entries: cell_start[v] = the number of ranks r < inside with keys[r] < v. Voxel v (a flat field index) owns the ranks
+ *               cell_start[v] .. cell_start[v + 1]; cell_start[512 * L] = inside. Defined by the sort alone, so unique. It needs the sort at level 1: after a sort at level 0,
+ *               or before any sort, hns_point_order_cells and hns_point_order_neighbours are refused. The table lives in the object: 4 * (512 * L + 1) bytes drawn from the
+ *               pool of device memory by the first call that needs it (what hns_point_order_create draws is unchanged) and returned by destroy. It is rebuilt on the
+ *               object's stream by the first call behind every sort that needs it, so a stale table is never read. hns_point_order_cells returns a DEVICE pointer, valid
+ *               until the next sort or the destroy; no host wait. With n == 0 the table is all zero. hns_point_order_info keeps its layout.
+ *   rows        as for hns_point_order_splat. 0 (original): row perm[r] of d_xyz and of every output belongs to rank r. 1 (ranked): row r belongs to rank r.
+ *   Contract    the positions are, bit for bit, those of the last sort (rows = 1: its gather). With other positions WHICH pairs are found is unspecified; every access
+ *               still stays inside the caller's n rows, the object's buffers and the grid's tables (leaves are looked up by coordinates, never taken from a key).
+ *   Outputs     d_count n uint32, d_density n floats, d_push n x 3 floats; any may be NULL, not all three. Every row of a non-NULL output is written.
+ *   Takes part  a point takes part iff its rank is < inside. Every other point gets count 0, density +0.0f and push (+0, +0, +0), and is no one's neighbour.
+ *   Box         h = radius, 0 < h <= 2. Along axis c the box of point i is the cells lo_c = (int)floorf(x_i.c - h) .. hi_c = (int)floorf(x_i.c + h), the subtraction and
+ *               the addition being f32 operations: at most 5 cells an axis (6 where x + h rounds up to an integer) under at most two leaves an axis.
+ *   Pair        j is a neighbour of i iff j != i, j takes part, Floor(x_j) lies in i's box on all three axes, and with dx = x_i.x - x_j.x (f32), likewise dy, dz,
+ *               the radial footprint's weight holds (hns_splat_spec: "Weight"): d2 = (dx*dx + dy*dy) + dz*dz; inv = 1.0f / (h*h); q = d2 * inv; q < 1.0f; and then
+ *               a = 1.0f - q, w = a * a. THE BOX IS PART OF THE DEFINITION: a point whose cell is outside it is no neighbour whatever its q.
+ *   Terms       count_i = the number of neighbours. density_i sums the int64 k = rint((double)w * 2^32), ties to even. push_i.c is taken from the pairs with d2 > 0 only:
+ *               d = sqrtf(d2); s = w / d; t_c = d_c * s; the sum of rint((double)t_c * 2^32). Every line is one rounded f32 operation, none contracted; the division and
+ *               the root are correctly rounded. A coincident pair (d2 == 0) counts, has w = 1.0f and adds nothing to the push. No term is refused: |t| is about 1 at
+ *               most, and 2^31 - 1 of them fit an int64.
+ *   Finish      each sum a becomes (float)((double)(int64)a * 2^-32): the sums are exact, so a result depends neither on the order the pairs are met in nor on how
+ *               they are split over lanes. The push points away from the neighbours: x_i + c * push_i thins a clump.
+ * On the device (hns_neighbours.hip) the table is one workgroup per leaf -- a histogram of the leaf's ranks in LDS, a scan on top of leaf_start[leaf] --, and the query
+ * goes by rank, so that neighbouring lanes hold points of the same or of adjacent voxels: 4, 16 or 32 lanes share a point and split the (x, y) columns of its box; a
+ * column's z-run is one contiguous range of ranks per leaf under it, read from two entries of the table; the lanes' int64 sums are added across lanes. No kernel waits on
+ * another workgroup. The query is asynchronous on the object's stream (no stream argument, like sort, gather and the ordered splat) and allocates nothing beyond the table;
+ * n == 0 launches nothing and looks at no pointer. Refused before anything is launched (HNS_ERR_INVALID_ARGUMENT, the call and the argument in the message), nothing
+ * touched: a null object; no sort yet; a sort at level 0; rows outside {0, 1}; a radius that is NaN, <= 0 or > 2; a null d_xyz (with n > 0); a null d_cell_start; all three
+ * outputs NULL; an output equal to d_xyz or to another output. Not mirrored in hns_dist_*. */
+int hns_point_order_cells(hns_point_order*, const uint32_t** d_cell_start);
+int hns_point_order_neighbours(hns_point_order*, const float* d_xyz, int rows, float radius, uint32_t* d_count, float* d_density, float* d_push);
+/* Host mirror of hns_point_order_neighbours: xyz and the outputs are HOST arrays with rows in the ORIGINAL order (no sort is needed: the cells come from the positions), plain
+ * C++ with a cell list over hns_grid_offsets-style lookups; works on HNS_GRID_HOST_ONLY grids. The same bytes as the device's. Refusals as above, a null grid, and an n
+ * above 2^31 - 1. */
+int hns_grid_point_neighbours(const hns_grid*, const float* xyz, uint64_t n, float radius, uint32_t* count, float* density, float* push);
 /* BIRTH AND DEATH OF POINTS: a stream of items, each with a small count c, expanded into sum(c) rows in item order, with the counts kept on the device. Death is c in
  * {0, 1} per point (select, then compact of every attribute array); birth is c in {0 .. K} per voxel of a field. A frame loop -- trace, drop the dead, append the newborn,
  * splat -- then runs without a host wait: the host keeps calling every point kernel with n = capacity, and the rows beyond the live count hold NaN positions, which the
