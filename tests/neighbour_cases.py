@@ -8,9 +8,8 @@ with d = x_i - x_j per axis (f32), d2 = (dx*dx + dy*dy) + dz*dz, inv = 1.0f / (h
 neighbours; density sums rint((double)w * 2^32); push sums rint((double)(d_c * (w / sqrtf(d2))) * 2^32) over the pairs with d2 > 0; each sum a becomes
 (float)((double)a * 2^-32). A point that takes no part gets count 0, density +0.0f and push +0.0f. float32 arrays: every operation below rounds once; float64 for the rint.
 
-On import the two new point-order entry points join tests/sequence_cases.EXEMPT (as tests/points_collide_stream_cases.py does for its calls): tests/test_sequence_cases.py
-asks about every hns_point_order_* symbol, and is collected after the files that import this module. Neither call has a `void* stream` parameter, so
-tests/stream_cases.py needs nothing."""
+The two point-order entry points are operations of tests/sequence_cases.py (neighbours_original, neighbours_ranked, cell_table), whose GPU test holds one query of a
+script to `restate` below. Neither call has a `void* stream` parameter, so tests/stream_cases.py needs nothing."""
 from __future__ import annotations
 
 import functools
@@ -20,7 +19,6 @@ import numpy as np
 
 import order_cases as oc
 import points_cases as pc
-import sequence_cases as sq
 
 F = np.float32
 GRIDS = pc.GRIDS
@@ -30,20 +28,6 @@ N_POINTS = pc.N_POINTS
 LATTICE_GRID = "dense32"
 LATTICE_RADII = (0.5, 187.0 / 256.0, 1.0, 1.5, 2.0)  # multiples of 2^-8
 N_LATTICE = 1500
-
-EXEMPT_FROM_SEQUENCES = {
-    "hns_point_order_cells": "writes the object's own cell table and no sim buffer: there is no sim state for it to leave stale; test_neighbours_gpu holds the table to searchsorted",
-    "hns_point_order_neighbours": "writes caller-owned tensors and the object's own cell table, and no sim buffer: there is no sim state for it to leave stale",
-}
-
-
-def register():
-    """idempotent: the entries join sequence_cases.EXEMPT"""
-    for name, reason in EXEMPT_FROM_SEQUENCES.items():
-        sq.EXEMPT.setdefault(name, reason)
-
-
-register()
 
 Result = namedtuple("Result", "count density push pairs d2")  # pairs: (m, 2) original indices (i, j) of the neighbour pairs; d2: their squared distances
 

@@ -2,15 +2,16 @@
 
 A sim and the point objects that hang off it carry state between calls. Some of it is semantic -- include/hns.h documents it as the sim's or the object's state -- and
 the rest is memo: the look-ahead, the feedback signatures, `solved` and p_result, the multigrid hierarchy, the lazily made tables, the buffer roles that swap under
-every call, the grid's pooled splat accumulator, an order's permutation and a population's slots. A stale memo gives plausible numbers and no fault.
+every call, the grid's pooled splat accumulator, an order's permutation and its cell table, and a population's slots. A stale memo gives plausible numbers and no fault.
 
   OPS       the vocabulary: one entry per call that changes or reads that state, a function (world, rng) -> outputs with the resources it reads and writes, the
             library symbols it goes through, what it needs from the script before it, and what it does to the look-ahead memo.
   World     the device side of a script: the sim, the points, one PointOrder and one PointPopulation.
   resident  ONE World from the first step to the last (the order and the population made anew only after a step that moves the sim onto another grid).
   twin      a NEW World for every step, built from nothing but the semantic state (`World.capture`), run with lookahead = 0 and the pool filled with a non-zero byte.
-  SCRIPTS   the committed scripts: explicit lists of (operation, seed). `draw_scripts` is the seeded generator they were drawn with; a red script is rerun and cut
-            down by hand with `compare(script, mode, upto=...)`.
+  SCRIPTS   the committed scripts: explicit lists of (operation, seed). `draw_scripts` is the seeded generator the first twelve were drawn with, the rest are written by
+            hand (POINT_SCRIPTS: collision tracing, the order's cell table, the frame loop of points); a red script is rerun and cut down by hand with
+            `compare(script, mode, upto=...)`.
 
 Every comparison is equality of bytes: every path involved is documented as bit-identical to its stateless form. Where a memo may rightly live or die without moving a
 byte -- hns_sim_deactivate drops the look-ahead although the velocity stays -- the table's memo column predicts hns_sim_lookahead_counts under lookahead = 1
@@ -37,7 +38,7 @@ PROFILES = {"combust": list(fc.COMBUST), "collide": list(fc.COMBUST) + ["collisi
 
 ALL_FIELDS = tuple("f:" + n for n in PROFILES["collide"])
 ADVECTED = tuple("f:" + n for n in fc.COMBUST)
-RESOURCES = ("vel", "masks", "grid", "scratch", "splat_spec", "solve_method", "solve_control", "points", "order", "live") + ALL_FIELDS
+RESOURCES = ("vel", "masks", "grid", "scratch", "splat_spec", "solve_method", "solve_control", "points", "order", "cells", "live") + ALL_FIELDS  # cells: the order's cell table, a memo of "order"
 SOLVE = ("solve_method", "solve_control", "grid")  # what every pressure solve reads besides its right-hand side (the hierarchy is a memo of grid and method)
 
 
@@ -48,17 +49,19 @@ class Op(NamedTuple):
     writes: frozenset
     symbols: tuple
     needs: frozenset     # float fields the sim must hold
-    requires: frozenset  # "order": a sort since the last change of grid; "fresh_order": and no write of the positions since
+    requires: frozenset  # "order": a sort since the last change of grid; "fresh_order": and no write of the positions since; "voxel_order": and the last sort by voxel
     grid: bool           # moves the sim onto another grid
     memo: str            # what the call does to the look-ahead memo under lookahead = 1: "produce" (consumes a live one, leaves one), "consume" (consumes a live one,
                          # leaves none), "drop", or "keep"
     same_points: bool    # writes the point arrays with the bytes they held (scatter of gather)
+    sets: frozenset      # what the call establishes of `requires` for the steps behind it (the sorts)
+    clears: frozenset    # ... and what it takes away besides what `breaks` works out (a sort by leaf: "voxel_order")
 
     @property
     def breaks(self):
-        out = set()
+        out = set(self.clears)
         if self.grid:
-            out |= {"order", "fresh_order"}
+            out |= {"order", "fresh_order", "voxel_order"}
         if "points" in self.writes and not self.same_points:
             out.add("fresh_order")
         return frozenset(out)
@@ -67,13 +70,14 @@ class Op(NamedTuple):
 OPS = {}
 
 
-def op(kind, reads=(), writes=(), symbols=(), needs=(), requires=(), grid=False, memo="keep", same_points=False):
-    def register(fn):
+def op(kind, reads=(), writes=(), symbols=(), needs=(), requires=(), grid=False, memo="keep", same_points=False, sets=(), clears=()):
+    def add(fn):
         w = set(writes) | ({"grid", "scratch"} if grid else set())
-        OPS[fn.__name__] = Op(kind, fn, frozenset(reads), frozenset(w), tuple(symbols), frozenset(needs), frozenset(requires), grid, memo, same_points)
+        OPS[fn.__name__] = Op(kind, fn, frozenset(reads), frozenset(w), tuple(symbols), frozenset(needs), frozenset(requires), grid, memo, same_points, frozenset(sets),
+                              frozenset(clears))
         return fn
 
-    return register
+    return add
 
 
 # the symbols the two runners and World go through themselves, whatever the script
@@ -496,12 +500,12 @@ def _sort(w, level):
     return {"perm": o.perm.cpu().numpy(), "keys": o.keys.cpu().numpy(), "leaf_start": o.leaf_start.cpu().numpy()}
 
 
-@op("sort", reads=("grid", "points"), writes=("order",), symbols=("hns_point_order_sort", "hns_point_order_get"))
+@op("sort", reads=("grid", "points"), writes=("order", "cells"), symbols=("hns_point_order_sort", "hns_point_order_get"), sets=("order", "fresh_order", "voxel_order"))
 def sort_voxel(w, rng):
     return _sort(w, "voxel")
 
 
-@op("sort", reads=("grid", "points"), writes=("order",), symbols=("hns_point_order_sort", "hns_point_order_get"))
+@op("sort", reads=("grid", "points"), writes=("order", "cells"), symbols=("hns_point_order_sort", "hns_point_order_get"), sets=("order", "fresh_order"), clears=("voxel_order",))
 def sort_leaf(w, rng):
     return _sort(w, "leaf")
 
@@ -559,6 +563,70 @@ def select_compact_fill(w, rng):
 @op("select_compact", reads=("vel", "grid", "points"), writes=("points", "live"), symbols=POPULATION)
 def select_compact_keep(w, rng):
     return _select_compact(w, False)
+
+
+def _trace_collide(w, mode, order, steps, **spec):
+    """the sim is only read (include/hns.h): the current velocity buffer, whichever role it plays after the calls before, and collision_sdf as it stands; a pending
+    look-ahead memo is neither read nor disturbed"""
+    status, hit = w.sim.trace(w.xyz, dt=DT, voxel_size=VS, order=order, steps=steps, status=True, collide=mode, hit=True, **spec)
+    return status, {"status": status.cpu().numpy(), "hit": hit.cpu().numpy()}
+
+
+COLLIDE_READS = ("vel", "grid", "points", "f:collision_sdf")
+COLLIDE = ("hns_sim_trace_points_collide",)
+COLLIDE_SPECS = {"trace_collide_stop": ("stop", 2, 2, {}), "trace_collide_push": ("push", 4, 3, dict(iterations=2, skin=1 / 16)), "trace_collide_kill_compact": ("kill", 1, 1, {})}
+
+
+@op("trace_collide", reads=COLLIDE_READS, writes=("points",), symbols=COLLIDE, needs=("collision_sdf",))
+def trace_collide_stop(w, rng):
+    return _trace_collide(w, *COLLIDE_SPECS["trace_collide_stop"][:3])[1]
+
+
+@op("trace_collide", reads=COLLIDE_READS, writes=("points",), symbols=COLLIDE, needs=("collision_sdf",))
+def trace_collide_push(w, rng):
+    mode, order, steps, spec = COLLIDE_SPECS["trace_collide_push"]
+    return _trace_collide(w, mode, order, steps, **spec)[1]
+
+
+@op("trace_collide", reads=COLLIDE_READS, writes=("points", "live"), symbols=COLLIDE + POPULATION[1:], needs=("collision_sdf",))
+def trace_collide_kill_compact(w, rng):
+    """ONE compound step, as _select_compact is (the slots are not state): a kill trace, select from its status, compact both point arrays with select_compact_fill's fills"""
+    status, out = _trace_collide(w, *COLLIDE_SPECS["trace_collide_kill_compact"][:3])
+    p = w.population()
+    p.select(status, 1)
+    out["slot"] = p.slot.cpu().numpy()
+    w.xyz = p.compact(w.xyz, w.xyz.clone(), fill=float("nan"))
+    w.attr = p.compact(w.attr, w.attr.clone(), fill=0)
+    out["counts"] = p.counts()
+    w.live = out["counts"][0]
+    return out
+
+
+CELL_READS = ("grid", "order", "cells")
+VOXEL_ORDER = ("order", "fresh_order", "voxel_order")
+
+
+def _neighbours(w, xyz, **kw):
+    return {k: v.cpu().numpy() for k, v in w.order().neighbours(xyz, **kw).items()}
+
+
+@op("neighbours", reads=("grid", "points", "order", "cells"), writes=("cells",), symbols=("hns_point_order_neighbours",), requires=VOXEL_ORDER)
+def neighbours_original(w, rng):
+    """radius 2: five cells an axis, the 32-lane group; the first query behind a sort builds the cell table, every later one reads it"""
+    return _neighbours(w, w.xyz, radius=2.0, rows="original")
+
+
+@op("neighbours", reads=("grid", "points", "order", "cells"), writes=("cells",), symbols=("hns_point_order_neighbours", "hns_point_order_gather"), requires=VOXEL_ORDER)
+def neighbours_ranked(w, rng):
+    """radius 0.5: two cells an axis, the 4-lane group, on the gathered positions; no density"""
+    return _neighbours(w, w.order().gather(w.xyz), radius=0.5, rows="ranked", density=False)
+
+
+@op("cells", reads=CELL_READS, writes=("cells",), symbols=("hns_point_order_cells",), requires=VOXEL_ORDER)
+def cell_table(w, rng):
+    """the whole table, and `inside` next to it (leaf_start[leaves]: the table's last entry by definition)"""
+    o = w.order()
+    return {"cell_start": o.cell_start.cpu().numpy(), "inside": int(o.leaf_start[w.sim.grid.leaf_count()].item())}
 
 
 @op("set_live", writes=("live",), symbols=("hns_point_population_set_live", "hns_point_population_counts"))
@@ -714,7 +782,7 @@ def placements(scripts):
 
 
 class Tracker:
-    """what a script has established so far, as far as the table can tell: is there an order on the current grid, and does it match the positions?"""
+    """what a script has established so far, as far as the table can tell: is there an order on the current grid, does it match the positions, and is it by voxel?"""
 
     def __init__(self):
         self.have = set()
@@ -724,14 +792,14 @@ class Tracker:
         if not profile_allows(profile, o):
             return f"{name} needs the fields {sorted(o.needs)}, the profile {profile} holds {PROFILES[profile]}"
         if not o.requires <= self.have:
-            return f"{name} requires {sorted(o.requires - self.have)}: a sort since the last change of grid (fresh_order: and since the last write of the positions)"
+            return (f"{name} requires {sorted(o.requires - self.have)}: a sort since the last change of grid (fresh_order: and since the last write of the positions; "
+                    f"voxel_order: and the last sort by voxel)")
         return None
 
     def step(self, name):
         o = OPS[name]
         self.have -= o.breaks
-        if o.kind == "sort":
-            self.have |= {"order", "fresh_order"}
+        self.have |= o.sets
 
 
 def refusals(script: Script):
@@ -890,9 +958,10 @@ def format_scripts(scripts):
 
 # ---- the committed scripts -----------------------------------------------------------------------------------------------------------------------------------------------
 
-# all but the last were drawn by draw_scripts (its closing three-step script folded into the last one); frame_vcycle is written by hand: a V-cycle method and a
-# control on a sim, then a seeded regrid, an ordered splat of the velocity, substeps, a deactivate, statistics, a birth from a field, a regrid onto another leaf count,
-# a stored spec set and put back, and the way back to SOR -- and the operations no drawn script holds
+# the first twelve were drawn by draw_scripts on the table as it stood before collision tracing and the neighbourhoods joined it (its closing three-step script folded
+# into frame_vcycle); they and their seeds stay as they are. frame_vcycle is written by hand: a V-cycle method and a control on a sim, then a seeded regrid, an ordered
+# splat of the velocity, substeps, a deactivate, statistics, a birth from a field, a regrid onto another leaf count, a stored spec set and put back, and the way back to
+# SOR -- and the operations no drawn script of that table holds. The last three are written by hand too, for the pairs the two features add (POINT_SCRIPTS below).
 SCRIPTS = (
     Script("placement_collide", "collide", 101, False, (
         ("substep_unfused", 102), ("core_substep", 103), ("substep_collision", 104), ("substep_unfused", 105), ("regrid_sdf", 106), ("core_substep", 107),
@@ -971,6 +1040,45 @@ SCRIPTS = (
         ("splat_stored", 394), ("control_off", 395), ("method_sor", 396), ("core_substep", 397), ("sort_leaf", 398), ("order_splat_ranked", 399), ("core_substep", 400),
     )),
 )
+
+# Written by hand, all three on a sim that holds collision_sdf.
+#   collide_points  every call kind that writes what the collision trace reads (the velocity, the fields, the grid, the positions) directly in front of one, and every
+#                   kind that reads the positions directly behind one: upload, regrid, emit, splat, select, birth, trace, advect, and a trace behind a trace.
+#   cells_memo      the order's cell table through its transitions on ONE order object: built by a query behind a sort, read again by the table's download, twice, by
+#                   a query at another radius (another k_neighbours<G>), behind a gather / scatter; a sort by voxel, by leaf and by voxel again in front of a query;
+#                   a query behind an ordered splat's trace and gather / scatter; the table built by its download instead of by a query; a kill in front of a sort.
+#   frame_points    the frame loop the two features were built for: a push under a pending look-ahead memo that the next substep consumes, a kill that drops rows, the
+#                   sort, the queries at both radii around an ordered splat, a regrid (a new order object), a sort by leaf then by voxel, the table, a collision substep
+#                   and a stop.
+# What the twin showed on the MI355X (check_liveness of tests/test_sequences_gpu.py prints it) stands above each script.
+POINT_SCRIPTS = (
+    # twin: rows (hit == 0, hit != 0) of the nine traces (793, 707) (756, 744) (1427, 73) (1312, 188) (1422, 78) (1419, 81) (1458, 42) (1489, 11) (1397, 103); rows with
+    # the mode's bit: stop put back 789, push pushed 1062 and put back 58, kill killed 76; the kill kept 1424 of 1500; 1220 leaves at the end
+    Script("collide_points", "collide", 401, False, (
+        ("upload_all", 402), ("trace_collide_stop", 403), ("regrid_seeded", 404), ("trace_collide_push", 405), ("emit_trilinear", 406), ("trace_collide_stop", 407),
+        ("splat_both", 408), ("trace_collide_push", 409), ("select_compact_keep", 410), ("trace_collide_stop", 411), ("birth_append", 412),
+        ("trace_collide_kill_compact", 413), ("trace", 414), ("trace_collide_push", 415), ("trace_collide_stop", 416), ("sample", 417), ("advect_velocity", 418),
+        ("trace_collide_push", 419),
+    )),
+    # twin: traces (827, 673) (775, 725) (1438, 62); stop put back 595, push pushed 707 and put back 17, kill killed 61, kept 297 of 1500; rows (count == 0, count != 0)
+    # of the six queries (874, 626) (1451, 49) (874, 626) (1451, 49) (1308, 192) (1459, 41); table entries strictly between 0 and inside, and inside: (15839, 878) twice,
+    # (15798, 363); 31 leaves throughout
+    Script("cells_memo", "collide", 420, True, (
+        ("birth_overflow", 421), ("sort_voxel", 422), ("neighbours_original", 423), ("cell_table", 424), ("cell_table", 425), ("neighbours_ranked", 426),
+        ("gather_scatter", 427), ("neighbours_original", 428), ("sort_voxel", 429), ("sort_leaf", 430), ("sort_voxel", 431), ("neighbours_ranked", 432),
+        ("order_splat_original", 433), ("trace_collide_stop", 434), ("gather_scatter", 435), ("trace_collide_push", 436), ("sort_voxel", 437), ("cell_table", 438),
+        ("neighbours_original", 439), ("trace_collide_kill_compact", 440), ("sort_voxel", 441), ("neighbours_ranked", 442),
+    )),
+    # twin: traces (826, 674) (1450, 50) (1478, 22); push pushed 631 and put back 16, kill killed 50, kept 410 of 1500, stop put back 21; queries (1299, 201)
+    # (1457, 43) (1299, 201) (1457, 43); table (236450, 410); look-ahead counts (3, 2) under lookahead = 1; 498 leaves at the end. Against the mirrors: the push moved 1048
+    # rows, no word differs; the first query finds 350 pairs among the 410 points that take part
+    Script("frame_points", "collide", 443, False, (
+        ("core_substep", 444), ("core_substep", 445), ("trace_collide_push", 446), ("core_substep", 447), ("trace_collide_kill_compact", 448), ("sort_voxel", 449),
+        ("neighbours_original", 450), ("neighbours_ranked", 451), ("order_splat_original", 452), ("neighbours_original", 453), ("regrid_sdf", 454), ("sort_leaf", 455),
+        ("sort_voxel", 456), ("cell_table", 457), ("neighbours_ranked", 458), ("substep_collision", 459), ("trace_collide_stop", 460),
+    )),
+)
+SCRIPTS += POINT_SCRIPTS
 
 BY_NAME = {s.name: s for s in SCRIPTS}
 

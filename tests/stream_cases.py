@@ -647,6 +647,32 @@ def k_trace_points(x):
     return Call({"vel": x.f["vel"], "xyz": x.xyz}, {"status": ((N_POINTS,), np.uint8)}, run, expect, inplace=("xyz",))
 
 
+# the collision trace of both levels: PUSH at order 4 with 3 steps and 2 iterations on the harness's 1,031 points, with a threshold above the 0.05 band planted in Ctx.sdf, so
+# that hundreds of the points are pushed, put back or left alone (counted on the mirror, never on the library under test)
+COLLIDE_THRESHOLD = 0.06
+COLLIDE_SPEC = dict(threshold=COLLIDE_THRESHOLD, skin=0.0625, iterations=2)
+COLLIDE_ORDER, COLLIDE_STEPS, COLLIDE_MODE = 4, 3, "push"
+COLLIDE_VARIANT = "push_order4_steps3"
+
+
+def _collide_mirror(x, vel, sdf, xyz):
+    from points_collide_cases import collide_mirror
+
+    got, status, hit, _ = collide_mirror(x.oracle, vel, sdf, xyz, x.dt, x.inv_dx, COLLIDE_ORDER, COLLIDE_STEPS, COLLIDE_MODE, **COLLIDE_SPEC)
+    assert ((hit & 1) != 0).sum() >= 100 and ((hit & 2) != 0).sum() >= 50 and (hit == 0).sum() >= 100, "the case's points meet too little of the collider"
+    return got, status, hit
+
+
+def k_trace_points_collide(x):
+    def expect(h):
+        got, status, hit = _collide_mirror(x, h.vel, h.sdf, h.xyz)
+        return {"xyz": got, "status": status, "hit": hit}
+
+    run = lambda t: _D().trace_points_collide(x.grid, t.vel, t.sdf, t.xyz, x.dt, x.inv_dx, order=COLLIDE_ORDER, steps=COLLIDE_STEPS, mode=COLLIDE_MODE, status=t.status, hit=t.hit,
+                                              **COLLIDE_SPEC)
+    return Call({"vel": x.f["vel"], "sdf": x.sdf, "xyz": x.xyz}, {"status": ((N_POINTS,), np.uint8), "hit": ((N_POINTS,), np.uint8)}, run, expect, inplace=("xyz",))
+
+
 def k_splat_points(x):
     """into a float and a Vec3f field at once; the host mirror hns_grid_splat_points gives the expected bytes"""
     def run(t):
@@ -908,6 +934,19 @@ def s_trace(x):
     return SimCall(lambda sim, st, t: {"status": sim.trace(t.xyz, dt=x.dt, voxel_size=x.vs, order=4, steps=3, status=True, stream=st)}, _points, inplace=("xyz",), expect=expect)
 
 
+def s_trace_collide(x):
+    def expect(x, r):
+        got, status, hit = _collide_mirror(x, x.state["vel"], x.state["collision_sdf"], x.xyz)
+        assert same_words(r["xyz"], got) and same_words(r["status"], status) and same_words(r["hit"], hit), \
+            "hns_sim_trace_points_collide on the null stream differs from points_collide_cases.collide_mirror"
+
+    def run(sim, st, t):
+        status, hit = sim.trace(t.xyz, dt=x.dt, voxel_size=x.vs, order=COLLIDE_ORDER, steps=COLLIDE_STEPS, status=True, stream=st, collide=COLLIDE_MODE, hit=True, **COLLIDE_SPEC)
+        return {"status": status, "hit": hit}
+
+    return SimCall(run, _points, inplace=("xyz",), expect=expect)
+
+
 def s_splat(x):
     def run(sim, st, t):
         sim.set_active_masks(x.masks, st)
@@ -1104,6 +1143,7 @@ CASES = {
     "hns_dev_unpack_leaves": Entry("kernel", "numpy indexing and the null stream", SCATTERED, {"float": k_unpack(1), "vec3": k_unpack(3)}),
     "hns_dev_sample_points": Entry("kernel", ORACLE + " (sample_trilinear_f / _v)", SCATTERED, {"float_vec3_float": k_sample_points}),
     "hns_dev_trace_points": Entry("kernel", MIRROR + " (points_cases.trace_mirror)", SCATTERED, {"order4_steps3": k_trace_points}),
+    "hns_dev_trace_points_collide": Entry("kernel", MIRROR + " (points_collide_cases.collide_mirror)", SCATTERED, {COLLIDE_VARIANT: k_trace_points_collide}),
     "hns_dev_splat_points": Entry("kernel", MIRROR + " (hns_grid_splat_points)", SCATTERED, {"float_and_vec3": k_splat_points}),
     "hns_dev_point_leaves": Entry("kernel", MIRROR + " (hns_point_leaves)", SCATTERED, {"plain": k_point_leaves}),
     "hns_dev_field_stats": Entry("kernel", MIRROR + " (hns_leaf_stats)", BOTH, {"masked_float_and_vec3": k_field_stats}),
@@ -1118,6 +1158,7 @@ CASES = {
                                                         "solve_control": s_pressure_solve_controlled}),
     "hns_sim_sample_points": Entry("sim", ORACLE + " (sample_trilinear_f / _v)", SCATTERED, {"all_fields_and_velocity": s_sample}),
     "hns_sim_trace_points": Entry("sim", MIRROR + " (points_cases.trace_mirror)", SCATTERED, {"order4_steps3": s_trace}),
+    "hns_sim_trace_points_collide": Entry("sim", MIRROR + " (points_collide_cases.collide_mirror)", SCATTERED, {COLLIDE_VARIANT: s_trace_collide}),
     "hns_sim_splat_points": Entry("sim", MIRROR + " (hns_grid_splat_points)", SCATTERED, {"two_floats_and_velocity": s_splat}),
     "hns_sim_set_active_masks": Entry("sim", "the masks set and the null stream", SCATTERED, {"plain": s_set_masks}),
     "hns_sim_active_masks": Entry("sim", "the masks set and the null stream", SCATTERED, {"plain": s_get_masks}),

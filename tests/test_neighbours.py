@@ -154,13 +154,15 @@ def test_object_refusals_that_need_no_device():
     assert table.value is None
 
 
-def test_the_symbols_are_bound_exported_and_exempt():
+def test_the_symbols_are_bound_exported_and_operations_of_the_sequences():
     header = open(os.path.join(ROOT, "include", "hns.h")).read()
     for name in SYMBOLS:
         assert name in _lib.SIGNATURES and callable(getattr(lib, name)) and f" {name}(" in header, name
     assert lib.hns_version() == 100
-    for name in SYMBOLS[:2]:
-        assert name in sq.EXEMPT and len(sq.EXEMPT[name]) > 40
+    for name in SYMBOLS[:2]:  # the object's calls: operations of the call-sequence vocabulary that some committed script holds, and no exemption
+        ops = [k for k, o in sq.OPS.items() if name in o.symbols]
+        assert ops and name not in sq.EXEMPT, name
+        assert [s.name for s in sq.SCRIPTS if set(ops) & {k for k, _ in s.steps}], f"no committed script holds an operation of {name}"
     assert hasattr(device.PointOrder, "neighbours") and isinstance(device.PointOrder.cell_start, property) and callable(leafio.point_neighbours)
 
 

@@ -8,7 +8,6 @@ import re
 import numpy as np
 import pytest
 
-import points_collide_stream_cases as pcs
 from hnanosolver_amd import _lib, api, device, fields
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -115,17 +114,23 @@ def test_python_mirrors_exist_and_refuse_an_unknown_mode():
 
 
 def test_both_calls_are_stream_cases_and_the_sim_form_is_decided_for_the_sequences():
-    """the feature's entries of the late-stream harness and of the call-sequence vocabulary (tests/points_collide_stream_cases.py) are in both tables"""
+    """the feature's entries stand in the tables themselves: both calls are cases of the late-stream harness (tests/stream_cases.py), and the sim's form is an operation
+    of the call-sequence vocabulary (tests/sequence_cases.py) in every mode, held by a committed script, and no exemption"""
     import sequence_cases
     import stream_cases
 
     declared = stream_cases.stream_entry_points(header())
     for name in SYMBOLS:
-        assert name in declared and stream_cases.CASES[name] is pcs.CASES[name] and "null stream" in stream_cases.CASES[name].source
-        assert (name, pcs.VARIANT, "scattered") in stream_cases.variants(stream_cases.CASES[name].level)
-    reason = sequence_cases.EXEMPT["hns_sim_trace_points_collide"]
-    assert len(reason) > 40 and "hns_sim_trace_points" in reason
-    assert not any("hns_sim_trace_points_collide" in o.symbols for o in sequence_cases.OPS.values())
+        assert name in declared and "null stream" in stream_cases.CASES[name].source and "collide_mirror" in stream_cases.CASES[name].source
+        assert (name, stream_cases.COLLIDE_VARIANT, "scattered") in stream_cases.variants(stream_cases.CASES[name].level)
+        assert name not in stream_cases.EXEMPT
+    name = "hns_sim_trace_points_collide"
+    assert name not in sequence_cases.EXEMPT
+    ops = {k for k, o in sequence_cases.OPS.items() if name in o.symbols}
+    assert ops == {"trace_collide_stop", "trace_collide_push", "trace_collide_kill_compact"}
+    assert {sequence_cases.COLLIDE_SPECS[k][0] for k in ops} == set(device.COLLIDE_MODES)
+    for k in ops:
+        assert [s.name for s in sequence_cases.SCRIPTS if k in [n for n, _ in s.steps]], f"no committed script holds {k}"
 
 
 @pytest.mark.gpu

@@ -4,8 +4,8 @@ their Python mirrors, against the numpy mirror of tests/points_collide_cases.py,
 Every comparison is equality of 32-bit words for positions and of bytes for status and hit; a NaN counts as equal to any NaN only in the special-value test, as in
 tests/test_points_gpu.py. Every output is made one row (one byte) longer than asked and the element behind the last is watched. The conditions the point sets meet -- how
 many points start inside, are put back, killed, pushed out by the first or a later push -- are held without a GPU by tests/test_points_collide_cases.py. The two entry
-points run late on a non-blocking stream inside guard bands at the end of this file, with the harness of tests/stream_cases.py and the cases of
-tests/points_collide_stream_cases.py."""
+points run late on a non-blocking stream inside guard bands at the end of this file, with the harness and the cases of tests/stream_cases.py (tests/test_streams_gpu.py runs
+the same two entries of its table; here they stand next to the feature's other tests)."""
 import functools
 
 import numpy as np
@@ -13,7 +13,6 @@ import pytest
 
 import points_cases as pc
 import points_collide_cases as cc
-import points_collide_stream_cases as pcs
 import special_cases as sc
 from frame_cases import download, make_sim, random_masks, random_state
 from oracle_lib import OracleGrid, oracle_device
@@ -234,17 +233,17 @@ def stream_ctx(grid):
     return stream_cases.Ctx(grid)
 
 
-@pytest.mark.parametrize("name", sorted(pcs.CASES))
+@pytest.mark.parametrize("name", ["hns_dev_trace_points_collide", "hns_sim_trace_points_collide"])
 def test_entry_point_late_on_a_non_blocking_stream(name):
     import stream_cases
     import torch
 
-    entry = pcs.CASES[name]
+    entry = stream_cases.CASES[name]
     delay = stream_cases.Delay(torch)
     for grid in entry.grids:
         x = stream_ctx(grid)
-        case = entry.variants[pcs.VARIANT](x)
-        what = f"{name}[{pcs.VARIANT}-{grid}]"
+        case = entry.variants[stream_cases.COLLIDE_VARIANT](x)
+        what = f"{name}[{stream_cases.COLLIDE_VARIANT}-{grid}]"
         if entry.level == "kernel":
             stream_cases.check_call(torch, case, delay, what)
         else:

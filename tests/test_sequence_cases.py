@@ -1,6 +1,8 @@
 """The vocabulary and the scripts of tests/test_sequences_gpu.py, checked without a GPU from the declared read / write table and the script lists alone: every entry point
 of a sim, a point order and a point population is an operation or a stated exemption; every pair of operation kinds where the first writes what the second reads is
-adjacent in some script; every writer of the velocity and every change of grid sits between two look-ahead substeps; no script holds a step the library would refuse."""
+adjacent in some script; every writer of the velocity and every change of grid sits between two look-ahead substeps; the order's cell table goes through its transitions on
+one object; no script holds a step the library would refuse. OPS and EXEMPT are whole in tests/sequence_cases.py -- no other module adds to them --, so this file gives the
+same answer run alone as in the suite."""
 import numpy as np
 import pytest
 
@@ -8,6 +10,11 @@ import sequence_cases as sq
 from hnanosolver_amd import _lib
 
 PREFIXES = ("hns_sim_", "hns_point_order_", "hns_point_population_")
+REQUIREMENTS = {"order", "fresh_order", "voxel_order"}
+
+
+FRAME_POINTS = ["core_substep", "core_substep", "trace_collide_push", "core_substep", "trace_collide_kill_compact", "sort_voxel", "neighbours_original", "neighbours_ranked",
+                "order_splat_original", "neighbours_original", "regrid_sdf", "sort_leaf", "sort_voxel", "cell_table", "neighbours_ranked", "substep_collision", "trace_collide_stop"]
 
 
 def bound_symbols():
@@ -40,20 +47,36 @@ def test_every_entry_point_is_an_operation_or_exempt():
 def test_the_table_is_well_formed():
     for name, o in sq.OPS.items():
         assert o.reads <= set(sq.RESOURCES) and o.writes <= set(sq.RESOURCES), name
-        assert o.symbols and o.memo in ("produce", "consume", "drop", "keep") and o.requires <= {"order", "fresh_order"}, name
+        assert o.symbols and o.memo in ("produce", "consume", "drop", "keep"), name
+        assert o.requires <= REQUIREMENTS and o.sets <= REQUIREMENTS and o.clears <= REQUIREMENTS and not o.sets & o.breaks, name
+        assert bool(o.sets) == (o.kind == "sort"), name
+        if "order" in o.writes:  # the cell table is a memo of the order: whatever makes another order leaves the table behind
+            assert "cells" in o.writes, name
+        if "voxel_order" in o.requires:  # (hns_point_order_cells and _neighbours refuse a sort by leaf; Python's xyz must be the positions of that sort)
+            assert {"order", "fresh_order"} <= o.requires, name
         assert o.needs <= set(sq.PROFILES["collide"]), name
         if "vel" in o.writes or o.grid:  # include/hns.h: what was looked ahead is dropped by everything else that writes the velocity
             assert o.memo != "keep", name
         if o.memo in ("produce", "consume"):
             assert o.kind in ("substep", "core_substep"), name
-    assert len(sq.KINDS) >= 20 and sq.PRODUCERS == {"core_substep", "substep_unfused"}
+    assert len(sq.KINDS) >= 23 and sq.PRODUCERS == {"core_substep", "substep_unfused"}
+    assert "cells" in sq.RESOURCES and sq.OPS["sort_voxel"].sets == REQUIREMENTS and sq.OPS["sort_leaf"].breaks == {"voxel_order"}
+    assert sq.OPS["regrid_plain"].breaks == REQUIREMENTS and sq.OPS["trace_collide_push"].breaks == {"fresh_order"} and not sq.OPS["gather_scatter"].breaks
+    for name in ("trace_collide_stop", "trace_collide_push", "trace_collide_kill_compact"):  # include/hns.h: the sim is only read, and what was looked ahead stays
+        o = sq.OPS[name]
+        assert o.kind == "trace_collide" and o.memo == "keep" and o.needs == {"collision_sdf"} and "hns_sim_trace_points_collide" in o.symbols, name
+        assert {"vel", "grid", "points", "f:collision_sdf"} == o.reads and "points" in o.writes and not o.writes & set(sq.ALL_FIELDS + ("vel", "masks")), name
+        assert [p for p in sq.PROFILES if sq.profile_allows(p, o)] == ["collide"], name
+    assert "live" in sq.OPS["trace_collide_kill_compact"].writes and "hns_point_population_select" in sq.OPS["trace_collide_kill_compact"].symbols
+    for name in ("neighbours_original", "neighbours_ranked", "cell_table"):
+        assert sq.OPS[name].requires == REQUIREMENTS and sq.OPS[name].writes == {"cells"} and {"grid", "order", "cells"} <= sq.OPS[name].reads, name
 
 
 def test_every_operation_is_in_a_script_and_every_script_is_of_operations():
     used = {k for s in sq.SCRIPTS for k, _ in s.steps}
     assert not used - set(sq.OPS), f"scripts name operations the vocabulary lacks: {sorted(used - set(sq.OPS))}"
     assert not set(sq.OPS) - used, f"operations no script holds: {sorted(set(sq.OPS) - used)}"
-    assert len({s.name for s in sq.SCRIPTS}) == len(sq.SCRIPTS) <= 14
+    assert len({s.name for s in sq.SCRIPTS}) == len(sq.SCRIPTS) <= 16  # (a budget of run time: draw_scripts' own max_scripts)
     seeds = [sd for s in sq.SCRIPTS for _, sd in s.steps] + [s.seed for s in sq.SCRIPTS]
     assert len(seeds) == len(set(seeds))
     for s in sq.SCRIPTS:
@@ -61,6 +84,8 @@ def test_every_operation_is_in_a_script_and_every_script_is_of_operations():
     assert any(s.timing for s in sq.SCRIPTS) and not all(s.timing for s in sq.SCRIPTS)
     assert {s.profile for s in sq.SCRIPTS} == set(sq.PROFILES)
     assert any("birth_overflow" in [k for k, _ in s.steps] for s in sq.SCRIPTS)
+    assert [s.name for s in sq.SCRIPTS[:13]] == ["placement_collide", "placement_one", "placement_combust"] + [f"walk_{i}" for i in range(3, 11)] + ["pairs_11", "frame_vcycle"]
+    assert sorted(sd for s in sq.SCRIPTS[:13] for sd in [s.seed] + [x for _, x in s.steps]) == list(range(101, 401))  # the regression base keeps its seeds
 
 
 def test_every_dependent_pair_of_kinds_is_adjacent_in_a_script():
@@ -68,8 +93,40 @@ def test_every_dependent_pair_of_kinds_is_adjacent_in_a_script():
     need = sq.needed_pairs()
     assert len(need) >= 150 and ("splat", "core_substep") in need and ("regrid", "pressure") in need and ("deactivate", "regrid") in need
     assert ("trace", "order_splat") not in need  # (an ordered splat requires a sort since the last write of the positions: never adjacent, by the table's `breaks`)
+    for pair in (("sort", "neighbours"), ("neighbours", "neighbours"), ("cells", "neighbours"), ("neighbours", "cells"), ("gather_scatter", "neighbours"), ("trace_collide", "sort"),
+                 ("core_substep", "trace_collide"), ("upload", "trace_collide"), ("regrid", "trace_collide"), ("trace_collide", "trace_collide")):
+        assert pair in need, pair
+    # never adjacent, by `breaks`: the positions moved since the sort; the last sort is by leaf; no order on the new grid
+    assert not {("trace_collide", "neighbours"), ("trace", "neighbours"), ("regrid", "neighbours"), ("regrid", "cells"), ("trace_collide", "order_splat")} & set(need)
+    assert ("sort_leaf", "neighbours_original") not in need[("sort", "neighbours")] and ("sort_leaf", "cell_table") not in need[("sort", "cells")]
     missing = uncovered_pairs(sq.OPS, sq.SCRIPTS)
     assert not missing, f"pairs of operation kinds no script holds adjacent: {missing}"
+
+
+def runs_of(names, wanted):
+    """the positions at which the consecutive steps `names` match `wanted`, a list of sets of operation names"""
+    return [i for i in range(len(names) - len(wanted) + 1) if all(names[i + j] in w for j, w in enumerate(wanted))]
+
+
+def test_the_cell_table_goes_through_its_transitions_in_some_script():
+    """what the kinds' pairs alone do not say about the memo of the order object (cell_start behind cells_fresh): each of these is a run of steps on ONE order object
+    -- no step of a run changes the grid, by the table's `requires`"""
+    query = {"neighbours_original", "neighbours_ranked"}
+    runs = {
+        "a sort by voxel, by leaf and by voxel again in front of a query": [{"sort_voxel"}, {"sort_leaf"}, {"sort_voxel"}, query],
+        "two queries at two radii on one fresh table, the wide group first": [{"neighbours_original"}, {"neighbours_ranked"}],
+        "... and the narrow group first, a gather and a scatter between them": [{"neighbours_ranked"}, {"gather_scatter"}, {"neighbours_original"}],
+        "a query behind an ordered splat through the same object": [query, {"order_splat_original", "order_splat_ranked"}, query],
+        "a query behind a gather and a scatter through the same object": [query, {"gather_scatter"}, query],
+        "the table built by its download, then queried": [{"sort_voxel"}, {"cell_table"}, query],
+        "the table built by a query, then downloaded twice": [{"sort_voxel"}, query, {"cell_table"}, {"cell_table"}],
+        "a query through a new order object behind a regrid": [{"regrid_sdf", "regrid_plain", "regrid_sourced", "regrid_seeded"}, {"sort_leaf"}, {"sort_voxel"}, {"cell_table"}, query],
+        "a kill in front of the sort in front of a query": [{"trace_collide_kill_compact"}, {"sort_voxel"}, query],
+    }
+    for what, wanted in runs.items():
+        found = [(s.name, i) for s in sq.SCRIPTS for i in runs_of([k for k, _ in s.steps], wanted)]
+        assert found, f"no script holds {what}: {wanted}"
+    assert sq.OPS["neighbours_original"].fn is not sq.OPS["neighbours_ranked"].fn
 
 
 def test_writers_of_the_velocity_sit_between_two_lookahead_substeps():
@@ -88,9 +145,15 @@ def test_no_script_holds_a_step_that_would_be_refused():
         assert not sq.refusals(s), f"script {s.name}: {sq.refusals(s)}"
     bad = sq.Script("bad", "one", 1, False, (("sort_voxel", 2), ("trace", 3), ("order_splat_original", 4), ("regrid_plain", 5), ("gather_scatter", 6), ("substep_fused", 7)))
     assert [i for i, _ in sq.refusals(bad)] == [2, 4, 5]  # positions moved since the sort; no order on the new grid; a field the profile lacks
+    bad = sq.Script("bad", "collide", 1, False, tuple((k, i) for i, k in enumerate(
+        ["neighbours_original", "sort_leaf", "cell_table", "sort_voxel", "neighbours_ranked", "trace_collide_stop", "neighbours_ranked", "gather_scatter", "sort_voxel", "sort_leaf",
+         "neighbours_original", "sort_voxel", "regrid_sdf", "cell_table"])))
+    assert [i for i, _ in sq.refusals(bad)] == [0, 2, 6, 10, 13]  # no sort yet; a sort by leaf; positions moved; by leaf again; no order on the new grid
+    assert [i for i, _ in sq.refusals(sq.Script("bad", "combust", 1, False, (("trace_collide_push", 1), ("trace", 2))))] == [0]  # no collision_sdf in the profile
 
 
-@pytest.mark.parametrize("gone", [("deactivate", "deactivate_counts"), ("pressure_residual",), ("order_splat_original", "order_splat_ranked"), ("birth", "birth_append", "birth_overflow")])
+@pytest.mark.parametrize("gone", [("deactivate", "deactivate_counts"), ("pressure_residual",), ("order_splat_original", "order_splat_ranked"), ("birth", "birth_append", "birth_overflow"),
+                                  ("trace_collide_stop", "trace_collide_push", "trace_collide_kill_compact"), ("neighbours_original", "neighbours_ranked", "cell_table")])
 def test_a_deleted_operation_is_noticed(gone):
     """the conditions name what goes uncovered when an operation leaves the vocabulary"""
     ops = {k: o for k, o in sq.OPS.items() if k not in gone}
@@ -104,6 +167,12 @@ def test_expected_lookahead_counts():
         ["core_substep", "substep_unfused", "splat_floats", "core_substep", "deactivate", "core_substep", "substep_fused", "core_substep", "substep_collision", "core_substep"])))
     #                                 produce  consume+produce  keep    consume+produce  drop    produce  consume  produce  drop    produce
     assert sq.expected_lookahead(s) == [(1, 0), (2, 1), (2, 1), (3, 2), (3, 2), (4, 2), (4, 3), (5, 3), (5, 3), (6, 3)]
+    # a collision trace of every mode keeps a live memo, and the substep behind it consumes it: what frame_points opens with
+    t = sq.Script("t", "collide", 1, False, tuple((k, i) for i, k in enumerate(
+        ["core_substep", "core_substep", "trace_collide_push", "core_substep", "trace_collide_kill_compact", "trace_collide_stop", "core_substep"])))
+    assert sq.expected_lookahead(t) == [(1, 0), (2, 1), (2, 1), (3, 2), (3, 2), (3, 2), (4, 3)]
+    assert [k for k, _ in sq.BY_NAME["frame_points"].steps] == FRAME_POINTS and sq.BY_NAME["frame_points"].profile == "collide"
+    assert sq.expected_lookahead(sq.BY_NAME["frame_points"])[:5] == [(1, 0), (2, 1), (2, 1), (3, 2), (3, 2)]
     assert sq.has_two_equal_substeps(s) and not sq.has_two_equal_substeps(sq.Script("y", "one", 1, False, (("core_substep", 1), ("stats", 2), ("core_substep", 3))))
     assert sum(sq.has_two_equal_substeps(s) for s in sq.SCRIPTS) >= 3
 
