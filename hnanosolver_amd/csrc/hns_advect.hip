@@ -1126,7 +1126,8 @@ extern "C" {
 int hns_dev_advect_vector(hns_grid* g, const float* vel3, float* out3, const float* sdf, int has_collision, float dt, float inv_dx, void* stream) {
 	if (int rc = check_grid(g, "hns_dev_advect_vector")) return rc;
 	NULLCHK(!vel3 || !out3, "hns_dev_advect_vector");
-	if (vel3 == out3) return fail(HNS_ERR_INVALID_ARGUMENT, "hns_dev_advect_vector: output must not alias input");
+	const size_t vec_bytes = sizeof(float) * 1536 * (size_t)g->topo.n_leaves;
+	if (ranges_overlap(vel3, vec_bytes, out3, vec_bytes)) return fail(HNS_ERR_INVALID_ARGUMENT, "hns_dev_advect_vector: output must not alias input (out3 overlaps vel3)");
 	if (g->n_active == 0) return HNS_OK;
 	const float scaled_dt = dt * inv_dx;  // Kernel.cu:361
 	const dim3 grid((unsigned)g->n_active), block(512);
@@ -1189,21 +1190,22 @@ int hns_dev_advect_scalar_multi(hns_grid* g, const float* vel3, const float* con
 	if (int rc = check_grid(g, "hns_dev_advect_scalar_multi")) return rc;
 	NULLCHK(!vel3 || (n > 0 && (!in || !out)), "hns_dev_advect_scalar_multi");
 	// every refusal before the first launch: a field the kernel reads while a workgroup of the same call writes it has no defined result
+	const size_t field_bytes = sizeof(float) * 512 * (size_t)g->topo.n_leaves;
 	for (int i = 0; i < n; ++i) {
 		if (!in[i] || !out[i]) {
 			set_error("hns_dev_advect_scalar_multi: null device pointer for field %d", i);
 			return HNS_ERR_INVALID_ARGUMENT;
 		}
-		if (out[i] == vel3) {
+		if (ranges_overlap(out[i], field_bytes, vel3, 3 * field_bytes)) {
 			set_error("hns_dev_advect_scalar_multi: output of field %d aliases the velocity", i);
 			return HNS_ERR_INVALID_ARGUMENT;
 		}
 		for (int j = 0; j < n; ++j) {
-			if (out[i] == in[j]) {
+			if (ranges_overlap(out[i], field_bytes, in[j], field_bytes)) {
 				set_error("hns_dev_advect_scalar_multi: output of field %d aliases the input of field %d", i, j);
 				return HNS_ERR_INVALID_ARGUMENT;
 			}
-			if (j < i && out[i] == out[j]) {
+			if (j < i && ranges_overlap(out[i], field_bytes, out[j], field_bytes)) {
 				set_error("hns_dev_advect_scalar_multi: output of field %d is the output of field %d", i, j);
 				return HNS_ERR_INVALID_ARGUMENT;
 			}
@@ -1246,7 +1248,8 @@ bool hns_advect_ahead_ok(const hns_grid* g) { return narrow_fields(g); }
 int hns_dev_advect_scalars_ahead(hns_grid* g, const float* vel3, const float* const* in, float* const* out, int n, float* adv_out3, float dt, float inv_dx, void* stream) {
 	if (int rc = check_grid(g, "hns_dev_advect_scalars_ahead")) return rc;
 	NULLCHK(!vel3 || !adv_out3 || (n > 0 && (!in || !out)), "hns_dev_advect_scalars_ahead");
-	if (vel3 == adv_out3) return fail(HNS_ERR_INVALID_ARGUMENT, "hns_dev_advect_scalars_ahead: adv_out3 must not alias vel3");
+	const size_t vec_bytes = sizeof(float) * 1536 * (size_t)g->topo.n_leaves;
+	if (ranges_overlap(vel3, vec_bytes, adv_out3, vec_bytes)) return fail(HNS_ERR_INVALID_ARGUMENT, "hns_dev_advect_scalars_ahead: adv_out3 must not alias vel3");
 	if (n < 0 || n > HNS_MAX_SCALARS) return fail(HNS_ERR_INVALID_ARGUMENT, "hns_dev_advect_scalars_ahead: between 0 and 8 fields");
 	if (!narrow_fields(g)) return fail(HNS_ERR_INVALID_ARGUMENT, "hns_dev_advect_scalars_ahead: grid too large for 32-bit offsets (or option advect = generic)");
 	if (g->n_active == 0) return HNS_OK;

@@ -73,11 +73,24 @@ struct StatRows {
 };
 
 // masks null: every voxel. Reads only: eight raw buffer loads in flight per field, a round without an active voxel loads nothing.
-__global__ __launch_bounds__(256) void k_field_stats(const StatRows rows, const uint64_t* __restrict__ masks, const uint64_t n_leaves, hns_stats* __restrict__ table) {
+// WORDS: the masks are 8-byte aligned (the library's own always are) and lane k < 8 loads the 64-bit word of round k. Else they are a caller's byte array, which may start at
+// any byte (include/hns.h: an unsigned char* needs no alignment): lane k puts the word together from its eight bytes, lowest first -- the same value.
+template <bool WORDS>
+__device__ __forceinline__ void field_stats(const StatRows& rows, const unsigned char* __restrict__ masks, const uint64_t n_leaves, hns_stats* __restrict__ table) {
 	const uint64_t leaf = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
 	if (leaf >= n_leaves) return;  // (whole waves)
 	const int lane = (int)(threadIdx.x & 63);
-	const uint64_t word = masks && lane < 8 ? masks[8 * leaf + (uint64_t)lane] : ~0ull;
+	uint64_t word = ~0ull;
+	if (masks && lane < 8) {
+		const unsigned char* b = masks + 64 * leaf + 8 * (uint64_t)lane;
+		if (WORDS) {
+			word = *reinterpret_cast<const uint64_t*>(b);
+		} else {
+			word = 0;
+#pragma unroll
+			for (int k = 0; k < 8; ++k) word |= (uint64_t)b[k] << (8 * k);
+		}
+	}
 	uint64_t act[8];
 #pragma unroll
 	for (int k = 0; k < 8; ++k) act[k] = readlane64(word, k);
@@ -109,6 +122,13 @@ __global__ __launch_bounds__(256) void k_field_stats(const StatRows rows, const 
 			if (lane == 0) out[0] = r0, out[n_leaves] = r1, out[2 * n_leaves] = r2;
 		}
 	}
+}
+
+__global__ __launch_bounds__(256) void k_field_stats(const StatRows rows, const unsigned char* __restrict__ masks, const uint64_t n_leaves, hns_stats* __restrict__ table) {
+	field_stats<true>(rows, masks, n_leaves, table);
+}
+__global__ __launch_bounds__(256) void k_field_stats_bytes(const StatRows rows, const unsigned char* __restrict__ masks, const uint64_t n_leaves, hns_stats* __restrict__ table) {
+	field_stats<false>(rows, masks, n_leaves, table);
 }
 
 // The tree over leaves (hns_stats.hpp: stats_fold), in place: workgroup b folds row b of the table (n records) and writes out[b]. n = 0: the record of nothing.
@@ -192,7 +212,10 @@ int launch_stats(const std::vector<StatRow>& rows, int n_records, const unsigned
 		StatRows a{};
 		a.n = (int)std::min<size_t>(kStatRows, rows.size() - i0);
 		for (int j = 0; j < a.n; ++j) a.f[j] = rows[i0 + (size_t)j];
-		k_field_stats<<<(unsigned)((n_leaves + 3) / 4), 256, 0, st>>>(a, (const uint64_t*)masks, n_leaves, table);
+		if (((uintptr_t)masks & 7) == 0)
+			k_field_stats<<<(unsigned)((n_leaves + 3) / 4), 256, 0, st>>>(a, masks, n_leaves, table);
+		else
+			k_field_stats_bytes<<<(unsigned)((n_leaves + 3) / 4), 256, 0, st>>>(a, masks, n_leaves, table);
 	}
 	k_stats_fold<<<(unsigned)n_records, 1024, 0, st>>>(table, n_leaves, d_out);
 	return launch_status(who);

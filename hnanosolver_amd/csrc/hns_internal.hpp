@@ -25,6 +25,12 @@ inline int fail(int code, const char* msg) {
 	set_error("%s", msg);
 	return code;
 }
+// The test behind every "must not alias" of include/hns.h, stated once: the byte ranges [a, a + a_bytes) and [b, b + b_bytes) share a byte, or the pointers are equal (so
+// that two empty ranges at one address still count). A partial overlap -- an output that starts one leaf into its input -- is refused like identical pointers.
+inline bool ranges_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
+	const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+	return x == y || (x < y + b_bytes && y < x + a_bytes);
+}
 
 #define HNS_TRY(call)                    \
 	do {                                 \

@@ -195,7 +195,8 @@ int hns_dev_vorticity_confinement(hns_grid* g, const float* vel3, float* out3, f
                                   void* stream) {
 	if (int rc = check_grid(g, "hns_dev_vorticity_confinement")) return rc;
 	NULLCHK(!vel3 || !out3, "hns_dev_vorticity_confinement");
-	if (vel3 == out3) return fail(HNS_ERR_INVALID_ARGUMENT, "hns_dev_vorticity_confinement: output must not alias input");
+	const size_t vec_bytes = sizeof(float) * 1536 * (size_t)g->topo.n_leaves;
+	if (ranges_overlap(vel3, vec_bytes, out3, vec_bytes)) return fail(HNS_ERR_INVALID_ARGUMENT, "hns_dev_vorticity_confinement: output must not alias input (out3 overlaps vel3)");
 	if (g->n_active == 0) return HNS_OK;
 	const int fs = (int)factor_scale;  // nanovdb::Coord(factorScale,0,0) truncates (Kernel.cu:998)
 	hipLaunchKernelGGL(k_vorticity, dim3((unsigned)g->n_active), dim3(512), 0, (hipStream_t)stream, g->dev(), vel3, out3, dt, inv_dx, confinement_scale,

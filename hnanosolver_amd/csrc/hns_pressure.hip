@@ -547,12 +547,14 @@ int hns_rbgs_iterate(hns_grid* g, const float* div, float* p_a, float* p_b, floa
                      bool from_zero) {
 	if (int rc = check_grid(g, "hns_dev_rbgs_iterate")) return rc;
 	NULLCHK(!div || !p_a || !p_b, "hns_dev_rbgs_iterate");
-	if (p_a == p_b) return fail(HNS_ERR_INVALID_ARGUMENT, "hns_dev_rbgs_iterate: p_a and p_b must be distinct buffers");
+	const size_t field_bytes = sizeof(float) * 512 * (size_t)g->topo.n_leaves;
+	if (ranges_overlap(p_a, field_bytes, p_b, field_bytes)) return fail(HNS_ERR_INVALID_ARGUMENT, "hns_dev_rbgs_iterate: p_a and p_b must be distinct buffers (they overlap)");
+	if (ranges_overlap(div, field_bytes, p_a, field_bytes) || ranges_overlap(div, field_bytes, p_b, field_bytes))
+		return fail(HNS_ERR_INVALID_ARGUMENT, "hns_dev_rbgs_iterate: div overlaps p_a or p_b");
 	if (iterations < 0) return fail(HNS_ERR_INVALID_ARGUMENT, "hns_dev_rbgs_iterate: negative iteration count");
 	const SorSchedule s = hns_rbgs_schedule(g, iterations);
 	if (result_in_b) *result_in_b = s.steps() & 1;
 	hipStream_t st = (hipStream_t)stream;
-	const size_t field_bytes = sizeof(float) * 512 * (size_t)g->topo.n_leaves;
 	if (g->n_active == 0 || iterations == 0) {
 		if (from_zero) HNS_HIP(hipMemsetAsync(p_a, 0, field_bytes, st));
 		return HNS_OK;

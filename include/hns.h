@@ -30,6 +30,15 @@
  * read by every entry point when it is called -- switch them while no call is in flight) and the pool of idle device
  * allocations (hns_trim_memory; internally locked).
  *
+ * Device operands: every DEVICE pointer a caller passes -- directly, or inside a `float* const*` list -- needs the alignment of its element type and no more: 4 bytes for
+ * float / int32_t / uint32_t, 8 for hns_stats, int64_t and uint64_t, 1 for unsigned char (masks, status, hit, flags), and 4 for the `void*` rows of hns_point_order_gather /
+ * _scatter and hns_point_population_compact whatever row_bytes is. So `xyz + 3` of an (n, 3) float array, `field + 1` and a status array sliced out of a larger one at any
+ * byte are all legal operands, and RESULTS DO NOT DEPEND ON THE ALIGNMENT: a call gives the same bytes at a 4-, 8- or 12-byte start as at a 16-byte one (where a kernel has
+ * a wider path for 16-byte aligned operands it picks it per pointer, from that pointer's own bits; tests/test_operand_layout_gpu.py). A pointer misaligned for its own
+ * element type has no defined result. Unless a function says otherwise ("may alias", "in place"), no output may overlap an input or another output of the same call, in
+ * whole or in part; where a function says "must not alias" the overlap is refused with HNS_ERR_INVALID_ARGUMENT before anything is launched, identical pointers and an
+ * output that starts inside its input alike.
+ *
  * There is no CPU fallback: without a usable HIP device every compute entry point fails with HNS_ERR_NO_DEVICE.
  */
 #ifndef HNS_H
@@ -553,7 +562,7 @@ int hns_sim_solve_levels(hns_sim*, int* n_levels, uint64_t* leaves_per_level, in
 /* Velocity fields are Vec3f AoS on the device too (3 floats per voxel, `vel3`), exactly the host/reference layout.  */
 /* ------------------------------------------------------------------------------------------------------------ */
 
-/* advect_vector (Kernel.cu:354-453); out3 must not alias vel3 */
+/* advect_vector (Kernel.cu:354-453); out3 must not alias vel3: any overlap of the two fields is refused (HNS_ERR_INVALID_ARGUMENT, nothing launched) */
 int hns_dev_advect_vector(hns_grid*, const float* vel3, float* out3, const float* sdf, int has_collision, float dt, float inv_dx, void* stream);
 /* advect_scalar (Kernel.cu:269-352) */
 int hns_dev_advect_scalar(hns_grid*, const float* vel3, const float* in, float* out, const float* sdf, int has_collision, float dt, float inv_dx,
@@ -565,10 +574,10 @@ int hns_dev_advect_scalars(hns_grid*, const float* vel3, const float* const* in,
  * field i with these arguments, whatever the options. Where the 32-bit addressed kernels apply (no collision field, a Vec3f field below 4 GiB, option
  * "advect" = auto) eight fields share a launch and with it the own-velocity load, the neighbour tables, both sets of tap offsets and the velocity gathers;
  * elsewhere one advect_scalar launch per field. Refused before anything is launched (HNS_ERR_INVALID_ARGUMENT, the first offending field's index in the
- * message): a null pointer, an out[i] equal to any in[j] or to vel3, two equal out pointers. The same in listed twice is allowed. */
+ * message): a null pointer, an out[i] that overlaps any in[j] or vel3, two out fields that overlap. The same in listed twice is allowed. */
 int hns_dev_advect_scalar_multi(hns_grid*, const float* vel3, const float* const* in, float* const* out, int n, const float* sdf, int has_collision,
                                 float dt, float inv_dx, void* stream);
-/* advect_scalars over n <= 8 fields without a collision field AND advect_vector(vel3) into adv_out3 (not aliasing vel3), one launch: every output is
+/* advect_scalars over n <= 8 fields without a collision field AND advect_vector(vel3) into adv_out3 (not aliasing vel3: any overlap of the two is refused with HNS_ERR_INVALID_ARGUMENT), one launch: every output is
  * bit-identical to hns_dev_advect_scalars followed by hns_dev_advect_vector with these arguments. Applies where the 32-bit addressed kernels do
  * (a Vec3f field below 4 GiB, option "advect" = auto); HNS_ERR_INVALID_ARGUMENT elsewhere. */
 int hns_dev_advect_scalars_ahead(hns_grid*, const float* vel3, const float* const* in, float* const* out, int n, float* adv_out3, float dt, float inv_dx,
@@ -912,7 +921,7 @@ int hns_dev_rbgs_color(hns_grid*, const float* div, float* p, float dx, float om
  * WHICH BUFFER HOLDS THE RESULT IS NOT A FUNCTION OF `iterations`: *result_in_b is 1 when it is p_b, 0 when it is p_a
  * (e.g. blocked form: iterations = 2 -> p_b, 4 -> p_b or p_a, 6 -> p_b or p_a). A caller that wants the result must pass
  * result_in_b and read it (NULL is accepted from callers that only time the solve). The other buffer holds an intermediate
- * iterate. p_a and p_b must not alias.
+ * iterate. p_a and p_b must not alias, and neither may overlap div: any overlap among the three fields is refused (HNS_ERR_INVALID_ARGUMENT, nothing launched).
  * On a grid with a LAUNCH RANGE (hns_grid_set_active_range / _leaves: a multi-GPU rank's boundary / interior / owned leaves) only the leaves
  * of the range are written, and the statement above holds for ONE launch: a temporally blocked launch advances the leaves outside the range
  * inside its tiles instead of reading them as fixed, so its result on the range equals what a WHOLE-grid sweep leaves there -- provided p within
@@ -921,17 +930,18 @@ int hns_dev_rbgs_color(hns_grid*, const float* div, float* p, float dx, float om
  * launches (hns_dist does: an exchange, or its peers' mirror stores, after every launch). With nothing refreshing them, use one launch per call. */
 int hns_dev_rbgs_iterate(hns_grid*, const float* div, float* p_a, float* p_b, float dx, float omega, int iterations, int* result_in_b,
                          void* stream);
-/* subtractPressureGradient(_opt) (Kernel.cu:694-829); out3 may alias vel3 (each voxel reads only its own velocity) */
+/* subtractPressureGradient(_opt) (Kernel.cu:694-829); out3 may alias vel3 -- be the same pointer: the call is then in place -- since each voxel reads only its own velocity */
 int hns_dev_subtract_pressure_gradient(hns_grid*, const float* vel3, const float* p, float* out3, const float* sdf, int has_collision, float inv_dx,
                                        void* stream);
 /* combustion_oxygen (Kernel.cu:923-966) */
 int hns_dev_combustion_oxygen(const float* fuel, const float* waste, const float* temperature, float* divergence, const float* flame,
                               float* out_fuel, float* out_waste, float* out_temperature, float* out_flame, float temp_gain, float expansion,
                               uint64_t n, void* stream);
-/* temperature_buoyancy (Kernel.cu:831-847); out3 may alias vel3 */
+/* temperature_buoyancy (Kernel.cu:831-847); out3 may alias vel3 (be the same pointer: in place) */
 int hns_dev_temperature_buoyancy(const float* vel3, const float* temperature, float* out3, float dt, float ambient, float strength, uint64_t n,
                                  void* stream);
-/* vorticityConfinement (Kernel.cu:970-1024), out-of-place (the reference's in-place launch races when factor_scale >= 1) */
+/* vorticityConfinement (Kernel.cu:970-1024), out-of-place (the reference's in-place launch races when factor_scale >= 1): out3 must not alias vel3, any overlap of the
+ * two fields is refused (HNS_ERR_INVALID_ARGUMENT, nothing launched) */
 int hns_dev_vorticity_confinement(hns_grid*, const float* vel3, float* out3, float dt, float inv_dx, float confinement_scale, float factor_scale,
                                   void* stream);
 /* enforceCollisionBoundaries (Kernel.cu:77-116), in place */

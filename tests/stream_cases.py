@@ -8,7 +8,8 @@ against everything, and allocates each output on its own. Here
               valid but different value, so nothing can address out of range) and the outputs a sentinel. Whatever part of the call is not ordered behind S -- a
               launch, memset or copy on another stream, a forgotten event -- reads the poison or is overwritten by the sentinel, and the bytes come out wrong.
   Slab        carves the outputs out of one patterned buffer with two leaves of the widest field (2 x 512 x 3 x 4 B) between and around them; check() finds any store
-              outside an output. Every view is 256-byte aligned (smaller alignments are out of scope: include/hns.h states no minimum).
+              outside an output. Every view is 256-byte aligned unless it is given a skew: tests/layout_cases.py starts views 1 .. 12 bytes behind that, the least
+              alignment include/hns.h asks of a device operand.
               Guard bands cover the KERNEL level (hns_dev_*), where the caller owns every output. At sim level the fields belong to the library and the point
               outputs (sampled values, status, moved positions) are allocated by device.Sim; they are compared, not guard-banded.
   CASES       entry point -> (level, source of the expected bytes, variants). The coverage test in tests/test_stream_cases.py fails for an entry point with a stream
@@ -98,12 +99,16 @@ def _torch_dtype(torch, dtype):
 
 
 class Slab:
-    """One uint32 tensor filled with GUARD_WORD from which buffers are carved as views, each with at least GUARD_BYTES of pattern on both sides and 256-byte aligned."""
+    """One uint32 tensor filled with GUARD_WORD from which buffers are carved as views, each with at least GUARD_BYTES of pattern on both sides and 256-byte aligned --
+    or, with a skew, starting that many bytes behind a multiple of 256: the skipped bytes are guard like the rest."""
 
-    def __init__(self, torch, specs, device="cpu"):
-        """specs: {name: (shape, numpy dtype)} -> self.views[name]"""
+    def __init__(self, torch, specs, device="cpu", skew=None):
+        """specs: {name: (shape, numpy dtype)} -> self.views[name]; skew: None, or {name: bytes in 0 .. 255, a multiple of the element size} (a name left out: 0)"""
         self.torch = torch
-        total = GUARD_BYTES + sum(self._padded(self._nbytes(s, d)) + GUARD_BYTES for s, d in specs.values())
+        assert not set(skew or {}) - set(specs), "a skew for a view that is not in specs"
+        skew = {k: int((skew or {}).get(k, 0)) for k in specs}
+        assert all(0 <= b < ALIGN and b % np.dtype(specs[k][1]).itemsize == 0 for k, b in skew.items()), skew
+        total = GUARD_BYTES + sum(self._padded(skew[k] + self._nbytes(s, d)) + GUARD_BYTES for k, (s, d) in specs.items())
         self._store = torch.empty(total // 4, dtype=torch.int32, device=device)
         self._store.fill_(_signed(GUARD_WORD))
         self.words = self._store.view(torch.uint32) if hasattr(torch, "uint32") else self._store
@@ -112,10 +117,10 @@ class Slab:
             assert self._store.data_ptr() % ALIGN == 0
         self.extents, self.views, cursor = [], NS(), GUARD_BYTES
         for name, (shape, dtype) in specs.items():
-            n = self._nbytes(shape, dtype)
-            self.views[name] = self.bytes[cursor:cursor + n].view(_torch_dtype(torch, dtype)).reshape(shape)
-            self.extents.append((name, cursor, n))
-            cursor += self._padded(n) + GUARD_BYTES
+            n, start = self._nbytes(shape, dtype), cursor + skew[name]
+            self.views[name] = self.bytes[start:start + n].view(_torch_dtype(torch, dtype)).reshape(shape)
+            self.extents.append((name, start, n))
+            cursor += self._padded(skew[name] + n) + GUARD_BYTES
         assert cursor == total
 
     @staticmethod
