@@ -60,10 +60,7 @@ extern "C" void hns_sim_destroy(hns_sim* s) {
 	if (s->h_dig) (void)hipHostFree(s->h_dig);
 	hns_sim_free_diagnostics(s);
 	hns_sim_free_multigrid(s);
-	hns_arena_put(s->d_masks, s->masks_bytes, s->device);
-	hns_arena_put(s->d_act, s->act_bytes, s->device);
-	hns_arena_put(s->arena, s->arena_bytes, s->device);
-	delete s;
+	delete s;  // (its pooled blocks go back with their owners)
 }
 
 // Frees the device-resident state operator calls left with the grid (see make_sim below) and the accumulator of hns_dev_splat_points.
@@ -89,32 +86,7 @@ extern "C" int hns_grid_release_cache(hns_grid* g) {
 	return HNS_OK;
 }
 
-static size_t sim_unit(uint64_t n) { return (sizeof(float) * (size_t)(n ? n : 1) + 255) & ~(size_t)255; }  // one float field, 256-byte aligned
-static bool sim_combust(const hns_sim* s) { return std::all_of(kCombustionFields, kCombustionFields + 4, [s](const char* n) { return s->find(n) >= 0; }); }
-static size_t sim_units(const hns_sim* s) { return 3 * 3 + 3 + 2 * s->names.size() + (sim_combust(s) ? 4 : 0); }  // vel, adv, tmp | div, p_a, p_b | cur, nxt per field | q4
-
-size_t hns_sim_arena_need(const hns_sim* s, uint64_t n) { return sim_unit(n) * sim_units(s) + 256; }  // (+ the 16 digest accumulators of hns_compute_sim_resident, CHECKED fields)
-
-void hns_sim_layout(hns_sim* s, void* arena, uint64_t n) {
-	const size_t unit = sim_unit(n);
-	char* q = (char*)arena;
-	auto take = [&](size_t k) {
-		float* r = (float*)q;
-		q += k * unit;
-		return r;
-	};
-	s->n = n;
-	s->vel = take(3), s->adv = take(3), s->tmp = take(3);
-	s->div = take(1), s->p_a = take(1), s->p_b = take(1);
-	s->cur.clear(), s->nxt.clear();
-	for (size_t i = 0; i < s->names.size(); ++i) {
-		s->cur.push_back(take(1));
-		s->nxt.push_back(take(1));
-	}
-	s->q4 = sim_combust(s) ? take(4) : nullptr;
-	s->d_dig = (unsigned long long*)q;
-	s->p_result = s->p_a;
-}
+// (the sim's buffers over its arena: hns_sim_arena_need / hns_sim_layout, hns_internal.hpp)
 
 // zero: clear the arena (what hns_sim_create promises); the operator path skips it when every buffer is written before it is read
 static hns_sim* sim_create(hns_grid* g, const char* const* float_names, int n_float, bool zero, void* stream, int* rc_out) {
@@ -134,13 +106,10 @@ static hns_sim* sim_create(hns_grid* g, const char* const* float_names, int n_fl
 		}
 	}
 	s->handed_cur.resize(s->names.size());
-	void* arena = nullptr;
-	size_t bytes = 0;
-	if (rc == HNS_OK) rc = hns_arena_get(hns_sim_arena_need(s, s->n), s->device, &arena, &bytes);
-	if (rc == HNS_OK) {  // (s->arena stays null otherwise: hns_sim_destroy below hands it to the pool)
-		s->arena = arena, s->arena_bytes = bytes;
-		hns_sim_layout(s, s->arena, s->n);
-		if (zero && hipMemsetAsync(s->arena, 0, (char*)s->d_dig - (char*)s->arena, (hipStream_t)stream) != hipSuccess) rc = fail(HNS_ERR_HIP, "hns_sim_create: clearing the field memory failed");
+	if (rc == HNS_OK) rc = s->arena.get(hns_sim_arena_need(s, s->n), s->device);
+	if (rc == HNS_OK) {
+		hns_sim_layout(s, s->arena.p, s->n);
+		if (zero && hipMemsetAsync(s->arena.p, 0, (char*)s->d_dig - s->arena.as<char>(), (hipStream_t)stream) != hipSuccess) rc = fail(HNS_ERR_HIP, "hns_sim_create: clearing the field memory failed");
 	}
 	if (rc != HNS_OK) {
 		hns_sim_destroy(s);

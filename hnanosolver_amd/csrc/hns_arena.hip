@@ -1,5 +1,8 @@
-// hns_arena.hip -- the process-wide pool of device allocations that simulation states (hns_api.hip, hns_regrid.hip), grid tables (hns_gridbuild.hip,
-// hns_sorblock.hip) and the partitioned ranks (hns_dist_plan.hip) draw from.
+// hns_arena.hip -- the process-wide pool of device allocations. Nobody calls it directly: a block is held by an hns::Pooled (hns_pool.hpp), which draws it here and gives
+// it back when it goes. Its users: a sim's fields, masks, deactivation table (hns_api.hip, hns_regrid.hip), diagnostics (hns_diagnostics.hip) and multigrid levels
+// (hns_multigrid.hip); a grid's tables (hns_gridbuild.hip), block records (hns_sorblock.hip), statistics table and splat accumulator (hns_splat.hip); a point order with its
+// cell table (hns_pointorder.hip, hns_neighbours.hip) and a point population (hns_population.hip); a partitioned rank's fields (hns_dist_plan.hip); and the scratch of a
+// regrid or a seed call (hns::Scratch).
 // A sim's fields are slices of ONE device allocation, and allocations that are no longer needed go to a small
 // process-wide pool instead of back to the driver. The reference pays cudaMallocAsync x 15+ and the matching frees every
 // cook (HNanoSolver.cu:87-133,361-369); with separate hipMallocs here a cold cook at 256^3 spent 4.2 ms in hipFree

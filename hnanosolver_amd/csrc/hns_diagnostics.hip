@@ -197,14 +197,6 @@ __global__ __launch_bounds__(64) void k_residual(const GridDev g, const float* _
 constexpr size_t kRecordBytes = 4096;  // head of a sim's diagnostics allocation: the records its calls leave (85 of them)
 constexpr size_t kRecordsMax = kRecordBytes / sizeof(hns_stats);
 
-// *slot holds at least `need` bytes of pooled device memory afterwards (what it held is not kept)
-int ensure(void** slot, size_t* bytes, size_t need, int device) {
-	if (*slot && *bytes >= need) return HNS_OK;
-	if (*slot) hns_arena_put(*slot, *bytes, device);  // (waits for the device: nothing still reads it)
-	*slot = nullptr, *bytes = 0;
-	return hns_arena_get(need, device, slot, bytes);
-}
-
 // rows of fields over n_leaves leaves -> n_records records at d_out; table: n_records x n_leaves partial records
 int launch_stats(const std::vector<StatRow>& rows, int n_records, const unsigned char* masks, uint64_t n_leaves, hns_stats* table, hns_stats* d_out, hipStream_t st,
                  const char* who) {
@@ -236,18 +228,18 @@ int launch_residual(hns_grid* g, const float* div, const float* p, float dx, flo
 
 int grid_table(hns_grid* g, size_t records, hns_stats** table) {
 	std::lock_guard<std::mutex> lock(g->build_mutex);
-	HNS_TRY(ensure(&g->d_diag, &g->diag_bytes, sizeof(hns_stats) * std::max<size_t>(records, 1), g->device));
-	*table = (hns_stats*)g->d_diag;
+	HNS_TRY(g->d_diag.reserve(sizeof(hns_stats) * std::max<size_t>(records, 1), g->device));  // (a put waits for the device: nothing still reads the old table)
+	*table = g->d_diag.as<hns_stats>();
 	return HNS_OK;
 }
 
 // a sim's diagnostics memory: device records | partial table for `rows` table rows; pinned host records
 int sim_diag(hns_sim* s, size_t rows, hns_stats** d_rec, hns_stats** table) {
 	const uint64_t n_leaves = s->n / 512u;
-	HNS_TRY(ensure(&s->d_diag, &s->diag_bytes, kRecordBytes + sizeof(hns_stats) * std::max<uint64_t>(rows * n_leaves, 1), s->device));
+	HNS_TRY(s->d_diag.reserve(kRecordBytes + sizeof(hns_stats) * std::max<uint64_t>(rows * n_leaves, 1), s->device));
 	if (!s->h_diag) HNS_HIP(hipHostMalloc((void**)&s->h_diag, kRecordBytes, hipHostMallocDefault));
-	*d_rec = (hns_stats*)s->d_diag;
-	*table = (hns_stats*)((char*)s->d_diag + kRecordBytes);
+	*d_rec = s->d_diag.as<hns_stats>();
+	*table = (hns_stats*)(s->d_diag.as<char>() + kRecordBytes);
 	return HNS_OK;
 }
 
@@ -264,9 +256,9 @@ using namespace hns;
 
 void hns_sim_free_diagnostics(hns_sim* s) {
 	if (s->h_diag) (void)hipHostFree(s->h_diag);
-	hns_arena_put(s->d_diag, s->diag_bytes, s->device);
+	s->d_diag.release();
 	delete s->control;
-	s->h_diag = nullptr, s->d_diag = nullptr, s->diag_bytes = 0, s->control = nullptr;
+	s->h_diag = nullptr, s->control = nullptr;
 }
 
 // The control's part of a solve (include/hns.h: hns_solve_control). The driver, hns_sim_solve (hns_pressure.hip), cuts the loop into pieces of check_every iterations
@@ -374,7 +366,7 @@ int hns_sim_stats(hns_sim* s, const hns_stats_field* names, int n_fields, int us
 	const hipStream_t st = (hipStream_t)stream;
 	hns_stats *d_rec, *table;
 	HNS_TRY(sim_diag(s, (size_t)n_records, &d_rec, &table));
-	HNS_TRY(launch_stats(rows, n_records, use_masks ? s->d_masks : nullptr, s->n / 512u, table, d_rec, st, who));
+	HNS_TRY(launch_stats(rows, n_records, use_masks ? s->d_masks.as<unsigned char>() : nullptr, s->n / 512u, table, d_rec, st, who));
 	HNS_TRY(fetch(s, d_rec, 0, n_records, st));
 	memcpy(out, s->h_diag, sizeof(hns_stats) * (size_t)n_records);
 	return HNS_OK;

@@ -170,8 +170,7 @@ struct hns_dist {
 	std::vector<hnsd::Peer> peers;
 	hns_grid *gB = nullptr, *gI = nullptr, *gO = nullptr, *gA = nullptr;
 	// device state over the local leaves
-	void* arena = nullptr;
-	size_t arena_bytes = 0;
+	hns::Pooled arena;
 	int device = -1;
 	float *u = nullptr, *adv = nullptr, *tmp = nullptr, *div = nullptr, *p_a = nullptr, *p_b = nullptr, *p_result = nullptr, *stage = nullptr;
 	std::vector<float*> phi, phi_next;
@@ -246,8 +245,6 @@ inline int far_check(const hns_dist* d) {
 		                             "boundary): the owned result can differ from the single-domain run. Use a smaller time step (or fewer ranks); upload the fields again to clear this.");
 	return HNS_OK;
 }
-
-inline size_t pad256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 // How a rank's messages travel, derived here and nowhere else. A rank with several connections uses the first of: mapped peer memory, an RCCL communicator (the loopback
 // variant's is a one-rank communicator to itself: hns_dist::loopback says so), the copy-based loopback, the locally connected ranks.

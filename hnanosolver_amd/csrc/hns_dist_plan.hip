@@ -258,7 +258,7 @@ void hns_dist_destroy(hns_dist* d) {
 	d->cs_owner.reset();  // destroys the stream with its last user
 	for (hns_grid* g : {d->gB, d->gI, d->gO, d->gA})
 		if (g) hns_grid_destroy(g);
-	if (d->arena) hns_arena_put(d->arena, d->arena_bytes, d->device);
+	d->arena.release();
 	if (d->tables) (void)hipFree(d->tables);
 	if (d->pack_tables) (void)hipFree(d->pack_tables);
 	delete d;
@@ -275,7 +275,6 @@ static int build_pack_tables(hns_dist* d) {
 		std::vector<unsigned char> mask;
 		std::vector<unsigned short> pre;
 	} h[4];
-	size_t bytes = 0;
 	for (int t : {X_D1, X_P}) {
 		std::vector<std::vector<std::pair<int, int>>> of((size_t)d->nB);  // per boundary leaf: (peer index, index in that peer's region)
 		bool fits = true;
@@ -305,28 +304,31 @@ static int build_pack_tables(hns_dist* d) {
 			}
 		}
 		o.first[(size_t)d->nB] = (int)o.entry.size();
-		bytes += pad256(sizeof(int) * o.first.size()) + pad256(sizeof(int2) * o.entry.size()) + pad256(o.mask.size()) + pad256(sizeof(unsigned short) * o.pre.size());
 		d->pack_ok[t] = true;
 	}
+	// per packed region type first | entry | mask | row_pre, each uploaded where it is placed
+	int rc = HNS_OK;
+	auto tables = [&](const Slice& slice) {
+		auto put = [&](auto*& ptr, const void* src, size_t n) {
+			if (slice(ptr, n) && n && hipMemcpy((void*)ptr, src, n, hipMemcpyHostToDevice) != hipSuccess) rc = fail(HNS_ERR_HIP, "hns_dist_create: uploading the pack tables failed");
+		};
+		for (int t : {X_D1, X_P}) {
+			if (!d->pack_ok[t]) continue;
+			PackMirror& m = d->pack_type[t];
+			put(m.first, h[t].first.data(), sizeof(int) * h[t].first.size());
+			put(m.entry, h[t].entry.data(), sizeof(int2) * h[t].entry.size());
+			put(m.mask, h[t].mask.data(), h[t].mask.size());
+			put(m.row_pre, h[t].pre.data(), sizeof(unsigned short) * h[t].pre.size());
+		}
+	};
+	const size_t bytes = carve(nullptr, tables);
 	if (!bytes) return HNS_OK;
 	if (hipMalloc(&d->pack_tables, bytes) != hipSuccess) return fail(HNS_ERR_HIP, "hns_dist_create: allocating the pack tables failed");
-	char* q = (char*)d->pack_tables;
-	int rc = HNS_OK;
-	auto put = [&](const void* src, size_t n) -> void* {
-		void* r = q;
-		if (n && hipMemcpy(q, src, n, hipMemcpyHostToDevice) != hipSuccess) rc = fail(HNS_ERR_HIP, "hns_dist_create: uploading the pack tables failed");
-		q += pad256(n);
-		return r;
-	};
+	carve(d->pack_tables, tables);
 	for (int t : {X_D1, X_P}) {
 		if (!d->pack_ok[t]) continue;
-		PackMirror& m = d->pack_type[t];
-		m.n_boundary = d->nB;
-		m.first = (const int*)put(h[t].first.data(), sizeof(int) * h[t].first.size());
-		m.entry = (const int2*)put(h[t].entry.data(), sizeof(int2) * h[t].entry.size());
-		m.mask = (const unsigned char*)put(h[t].mask.data(), h[t].mask.size());
-		m.row_pre = (const unsigned short*)put(h[t].pre.data(), sizeof(unsigned short) * h[t].pre.size());
-		for (int i = 0; i < kMirrorMaxPeers; ++i) m.msg[i] = nullptr;
+		d->pack_type[t].n_boundary = d->nB;
+		for (int i = 0; i < kMirrorMaxPeers; ++i) d->pack_type[t].msg[i] = nullptr;
 	}
 	return rc;
 }
@@ -409,84 +411,67 @@ hns_dist* hns_dist_create(const int32_t* global_leaf_origins_xyz, uint64_t n_lea
 	{
 		const size_t unit = pad256(sizeof(float) * 512 * (size_t)std::max(n_local, 1));
 		d->unit_bytes = unit;
-		const size_t units = 3 + 3 + 3 + 3 + 2 * (size_t)n_scalars + 3;
-		if ((rc = hns_arena_get(unit * units, d->device, &d->arena, &d->arena_bytes)) != HNS_OK) return bail(rc);
-		if (hipMemset(d->arena, 0, unit * units) != hipSuccess) return bail(fail(HNS_ERR_HIP, "hns_dist_create: clearing the field memory failed"));
-		char* q = (char*)d->arena;
-		auto take = [&](size_t k) {
-			float* r = (float*)q;
-			q += k * unit;
-			return r;
+		d->phi.assign((size_t)n_scalars, nullptr), d->phi_next.assign((size_t)n_scalars, nullptr);
+		auto fields = [&](const Slice& slice) {
+			slice(d->u, 3, unit), slice(d->adv, 3, unit), slice(d->tmp, 3, unit), slice(d->div, 1, unit), slice(d->p_a, 1, unit), slice(d->p_b, 1, unit);
+			for (int s = 0; s < n_scalars; ++s) slice(d->phi[(size_t)s], 1, unit), slice(d->phi_next[(size_t)s], 1, unit);
+			slice(d->stage, 3, unit);
 		};
-		d->u = take(3), d->adv = take(3), d->tmp = take(3), d->div = take(1), d->p_a = take(1), d->p_b = take(1);
-		for (int s = 0; s < n_scalars; ++s) d->phi.push_back(take(1)), d->phi_next.push_back(take(1));
-		d->stage = take(3);
+		if ((rc = carve(d->arena, d->device, fields)) != HNS_OK) return bail(rc);
+		if (hipMemset(d->arena.p, 0, carve(nullptr, fields)) != hipSuccess) return bail(fail(HNS_ERR_HIP, "hns_dist_create: clearing the field memory failed"));
 		d->p_result = d->p_a;
 	}
 	// region tables and message buffers
 	{
-		size_t bytes = pad256(sizeof(int) * (size_t)std::max(nO, 1));
 		for (Peer& p : d->peers) {
-			for (int t = 0; t < X_COUNT; ++t)
-				for (Region* r : {&p.send[t], &p.recv[t]}) bytes += pad256(sizeof(int) * r->leaf.size()) + pad256(r->mask.size()) + pad256(sizeof(int) * r->off.size());
 			p.sbuf_floats = (size_t)p.send[X_ADV].voxels * (size_t)(3 + n_scalars);
 			p.rbuf_floats = (size_t)p.recv[X_ADV].voxels * (size_t)(3 + n_scalars);
 			for (int t = 1; t < X_COUNT; ++t) {  // every other message is one Vec3f or one float per voxel of a smaller region
 				p.sbuf_floats = std::max(p.sbuf_floats, (size_t)p.send[t].voxels * 3);
 				p.rbuf_floats = std::max(p.rbuf_floats, (size_t)p.recv[t].voxels * 3);
 			}
-			bytes += 2 * pad256(sizeof(float) * p.sbuf_floats) + 2 * pad256(sizeof(float) * p.rbuf_floats);
 		}
+		// the regions of all peers concatenated, per type and direction (regions that travel straight out of / into the field are left out)
+		struct Batch {
+			std::vector<int> leaf, off, peer;
+			std::vector<unsigned char> mask;
+		} all[X_COUNT][2];
 		const bool batch = d->peers.size() > 1 && d->peers.size() <= (size_t)kMaxBatchPeers;
 		if (batch)
 			for (int t = 0; t < X_COUNT; ++t)
-				for (int dir = 0; dir < 2; ++dir) {
-					size_t n = 0;
-					for (Peer& p : d->peers) n += (dir ? p.recv[t] : p.send[t]).leaf.size();  // (direct regions are left out below)
-					bytes += 3 * pad256(sizeof(int) * n) + pad256(64 * n);
-				}
-		if (hipMalloc(&d->tables, bytes) != hipSuccess) return bail(fail(HNS_ERR_HIP, "hns_dist_create: allocating the halo tables failed"));
-		char* q = (char*)d->tables;
-		auto put = [&](const void* src, size_t n) -> void* {
-			void* r = q;
-			if (n && hipMemcpy(q, src, n, hipMemcpyHostToDevice) != hipSuccess) rc = fail(HNS_ERR_HIP, "hns_dist_create: uploading the halo tables failed");
-			q += pad256(n);
-			return r;
-		};
-		d->d_perm = (int*)put(d->owned_perm.data(), sizeof(int) * d->owned_perm.size());
-		if (d->owned_perm.empty()) q += 256;
-		for (Peer& p : d->peers) {
-			for (int t = 0; t < X_COUNT; ++t)
-				for (Region* r : {&p.send[t], &p.recv[t]}) {
-					r->d_leaf = (int*)put(r->leaf.data(), sizeof(int) * r->leaf.size());
-					r->d_mask = (unsigned char*)put(r->mask.data(), r->mask.size());
-					r->d_off = (int*)put(r->off.data(), sizeof(int) * r->off.size());
-				}
-			for (int i = 0; i < 2; ++i) {
-				p.sbuf[i] = (float*)q, q += pad256(sizeof(float) * p.sbuf_floats);
-				p.rbuf[i] = (float*)q, q += pad256(sizeof(float) * p.rbuf_floats);
-			}
-		}
-		if (batch)
-			for (int t = 0; t < X_COUNT; ++t)
-				for (int dir = 0; dir < 2; ++dir) {
-					std::vector<int> leaf, off, peer;
-					std::vector<unsigned char> mask;
+				for (int dir = 0; dir < 2; ++dir)
 					for (size_t pi = 0; pi < d->peers.size(); ++pi) {
 						const Region& r = dir ? d->peers[pi].recv[t] : d->peers[pi].send[t];
-						if (r.direct >= 0) continue;  // travels straight out of / into the field
-						leaf.insert(leaf.end(), r.leaf.begin(), r.leaf.end());
-						off.insert(off.end(), r.off.begin(), r.off.end());
-						mask.insert(mask.end(), r.mask.begin(), r.mask.end());
-						peer.insert(peer.end(), r.leaf.size(), (int)pi);
+						if (r.direct >= 0) continue;
+						Batch& b = all[t][dir];
+						b.leaf.insert(b.leaf.end(), r.leaf.begin(), r.leaf.end());
+						b.off.insert(b.off.end(), r.off.begin(), r.off.end());
+						b.mask.insert(b.mask.end(), r.mask.begin(), r.mask.end());
+						b.peer.insert(b.peer.end(), r.leaf.size(), (int)pi);
 					}
-					hns_dist::AllPeers& a = dir ? d->all_recv[t] : d->all_send[t];
-					a.n = (int)leaf.size();
-					a.d_leaf = (int*)put(leaf.data(), sizeof(int) * leaf.size());
-					a.d_mask = (unsigned char*)put(mask.data(), mask.size());
-					a.d_off = (int*)put(off.data(), sizeof(int) * off.size());
-					a.d_peer = (int*)put(peer.data(), sizeof(int) * peer.size());
-				}
+		// one allocation: the owned permutation | per peer its region tables, then its message buffers | the concatenated tables; each table uploaded where it is placed
+		auto tables = [&](const Slice& slice) {
+			auto put = [&](auto*& ptr, const void* src, size_t n, size_t room) {
+				if (slice(ptr, room) && n && hipMemcpy((void*)ptr, src, n, hipMemcpyHostToDevice) != hipSuccess) rc = fail(HNS_ERR_HIP, "hns_dist_create: uploading the halo tables failed");
+			};
+			auto table = [&](auto*& ptr, const auto& v) { put(ptr, v.data(), sizeof(v[0]) * v.size(), sizeof(v[0]) * v.size()); };
+			put(d->d_perm, d->owned_perm.data(), sizeof(int) * d->owned_perm.size(), sizeof(int) * (size_t)std::max(nO, 1));
+			for (Peer& p : d->peers) {
+				for (int t = 0; t < X_COUNT; ++t)
+					for (Region* r : {&p.send[t], &p.recv[t]}) table(r->d_leaf, r->leaf), table(r->d_mask, r->mask), table(r->d_off, r->off);
+				for (int i = 0; i < 2; ++i) slice(p.sbuf[i], sizeof(float) * p.sbuf_floats), slice(p.rbuf[i], sizeof(float) * p.rbuf_floats);
+			}
+			if (batch)
+				for (int t = 0; t < X_COUNT; ++t)
+					for (int dir = 0; dir < 2; ++dir) {
+						hns_dist::AllPeers& a = dir ? d->all_recv[t] : d->all_send[t];
+						const Batch& b = all[t][dir];
+						a.n = (int)b.leaf.size();
+						table(a.d_leaf, b.leaf), table(a.d_mask, b.mask), table(a.d_off, b.off), table(a.d_peer, b.peer);
+					}
+		};
+		if (hipMalloc(&d->tables, carve(nullptr, tables)) != hipSuccess) return bail(fail(HNS_ERR_HIP, "hns_dist_create: allocating the halo tables failed"));
+		carve(d->tables, tables);
 		if (rc != HNS_OK) return bail(rc);
 	}
 	if ((rc = build_pack_tables(d)) != HNS_OK) return bail(rc);

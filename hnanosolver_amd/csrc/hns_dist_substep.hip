@@ -195,7 +195,7 @@ PhaseMirror phase_args(hns_dist* d, int t, const Fields& outs) {
 	PhaseMirror m = d->mir;
 	m.first = d->mir_type[t].first, m.entry = d->mir_type[t].entry, m.mask = d->mir_type[t].mask;
 	int k = 0, comps = 0;
-	for (const MsgField& f : outs) m.out_unit[k++] = (int)((size_t)((const char*)f.field - (const char*)d->arena) / d->unit_bytes), comps += f.ncomp;
+	for (const MsgField& f : outs) m.out_unit[k++] = (int)((size_t)((const char*)f.field - d->arena.as<const char>()) / d->unit_bytes), comps += f.ncomp;
 	m.seq = ++d->sweep_seq;
 	count_sent(d, t, comps);
 	return m;
@@ -306,7 +306,7 @@ int transfer_ipc(hns_dist* d, const Pending& x) {
 	put_messages<true>(d, x, [&](size_t i) { return (size_t)d->peers[i].send[x.type].voxels; }, [&](size_t i, const MsgField& f) {
 		// the same field in the peer's memory: fields sit at the same multiples of the (peer's) unit
 		const hns_dist::IpcPeer& q = d->ipc_peers[i];
-		const size_t unit_index = (size_t)((char*)f.field - (char*)d->arena) / d->unit_bytes;
+		const size_t unit_index = (size_t)((char*)f.field - d->arena.as<char>()) / d->unit_bytes;
 		return (float*)(q.recv_direct[x.type] >= 0 ? q.arena + unit_index * q.unit_bytes + sizeof(float) * 512 * (size_t)q.recv_direct[x.type] * (size_t)f.ncomp
 		                                           : q.tables + q.rbuf_off[x.parity] + sizeof(float) * (size_t)f.before * (size_t)q.recv_voxels[x.type]);
 	});

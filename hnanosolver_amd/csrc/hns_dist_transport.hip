@@ -63,7 +63,6 @@ int setup_mirror(hns_dist* d, const std::vector<std::vector<int>> (&remote_leaf)
 	std::vector<int> first[X_COUNT];
 	std::vector<int2> entry[X_COUNT];
 	std::vector<unsigned char> mask[X_COUNT];
-	size_t bytes = 256;
 	for (int t = 0; t < X_COUNT; ++t) {
 		std::vector<std::vector<std::pair<int2, const unsigned char*>>> per_leaf((size_t)nB);
 		bool whole = true;
@@ -85,22 +84,24 @@ int setup_mirror(hns_dist* d, const std::vector<std::vector<int>> (&remote_leaf)
 			}
 		}
 		first[t][(size_t)nB] = (int)entry[t].size();
-		bytes += pad256(sizeof(int) * first[t].size()) + pad256(sizeof(int2) * entry[t].size()) + pad256(mask[t].size());
 	}
-	if (hipMalloc(&d->mir_tables, bytes) != hipSuccess) return fail(HNS_ERR_HIP, "hns_dist: allocating the mirror tables failed");
-	char* q = (char*)d->mir_tables;
-	auto put = [&](const void* src, size_t n) -> char* {
-		char* r = q;
-		if (n && hipMemcpy(q, src, n, hipMemcpyHostToDevice) != hipSuccess) r = nullptr;
-		q += pad256(n);
-		return r;
+	// per region type first | entry | mask (and 256 bytes to spare behind them), each uploaded where it is placed
+	bool uploaded = true;
+	auto tables = [&](const Slice& slice) {
+		auto put = [&](auto*& ptr, const void* src, size_t n) {
+			if (slice(ptr, n) && n && hipMemcpy((void*)ptr, src, n, hipMemcpyHostToDevice) != hipSuccess) uploaded = false;
+		};
+		for (int t = 0; t < X_COUNT; ++t) {
+			put(d->mir_type[t].first, first[t].data(), sizeof(int) * first[t].size());
+			put(d->mir_type[t].entry, entry[t].data(), sizeof(int2) * entry[t].size());
+			put(d->mir_type[t].mask, mask[t].data(), mask[t].size());
+		}
 	};
-	for (int t = 0; t < X_COUNT; ++t) {
-		d->mir_type[t].first = (const int*)put(first[t].data(), sizeof(int) * first[t].size());
-		d->mir_type[t].entry = (const int2*)put(entry[t].data(), sizeof(int2) * entry[t].size());
-		d->mir_type[t].mask = mask[t].empty() ? nullptr : (const unsigned char*)put(mask[t].data(), mask[t].size());
-		if (!d->mir_type[t].first || !d->mir_type[t].entry) return fail(HNS_ERR_HIP, "hns_dist: uploading the mirror tables failed");
-	}
+	if (hipMalloc(&d->mir_tables, 256 + carve(nullptr, tables)) != hipSuccess) return fail(HNS_ERR_HIP, "hns_dist: allocating the mirror tables failed");
+	carve(d->mir_tables, tables);
+	if (!uploaded) return fail(HNS_ERR_HIP, "hns_dist: uploading the mirror tables failed");
+	for (int t = 0; t < X_COUNT; ++t)
+		if (mask[t].empty()) d->mir_type[t].mask = nullptr;  // (whole leaves)
 	PhaseMirror& m = d->mir;
 	memset(&m, 0, sizeof(m));
 	m.n_boundary = nB, m.n_peers = (int)d->peers.size();
@@ -183,7 +184,7 @@ int hns_dist_connect_loopback(hns_dist* d) {
 			for (int t = 0; t < X_COUNT; ++t)
 				for (size_t j = 0; j < p.send[t].leaf.size(); ++j)
 					remote[t][i].push_back(p.recv[t].leaf.empty() ? d->nB + d->nI : p.recv[t].leaf[j % p.recv[t].leaf.size()]);
-			arenas.push_back((char*)d->arena), units.push_back((uint64_t)d->unit_bytes);
+			arenas.push_back(d->arena.as<char>()), units.push_back((uint64_t)d->unit_bytes);
 			fl.push_back(d->ipc_flags + (p.rank - d->rank));  // (so that the flag this rank raises "on the peer" is the one it waits for)
 		}
 		if (d->nG > 0) HNS_TRY(setup_mirror(d, remote, arenas, units, fl));
@@ -234,7 +235,7 @@ int hns_dist_ipc_export(hns_dist* d, void* out_blob) {
 	memset(&b, 0, sizeof(b));
 	b.magic = kIpcMagic, b.world = (uint32_t)d->world, b.rank = (uint32_t)d->rank, b.n_peers = (uint32_t)d->peers.size();
 	b.unit_bytes = d->unit_bytes, b.pid = (uint64_t)getpid();
-	HNS_HIP(hipIpcGetMemHandle(&b.arena, d->arena));
+	HNS_HIP(hipIpcGetMemHandle(&b.arena, d->arena.p));
 	HNS_HIP(hipIpcGetMemHandle(&b.tables, d->tables));
 	HNS_HIP(hipIpcGetMemHandle(&b.flags, d->ipc_flags));
 	for (size_t i = 0; i < d->peers.size(); ++i) {
@@ -329,7 +330,7 @@ int hns_dist_connect_local(hns_dist* const* ranks, int world) {
 				for (const Peer& c : q->peers)
 					if (c.rank == d->rank)
 						for (int t = 0; t < X_COUNT; ++t) remote[t][i] = c.recv[t].leaf;
-				arenas.push_back((char*)q->arena), units.push_back((uint64_t)q->unit_bytes), fl.push_back(q->ipc_flags);
+				arenas.push_back(q->arena.as<char>()), units.push_back((uint64_t)q->unit_bytes), fl.push_back(q->ipc_flags);
 			}
 			HNS_TRY(setup_mirror(d, remote, arenas, units, fl));
 		}

@@ -84,7 +84,7 @@ int hns_grid_upload_schedule(hns_grid* g) {
 }
 
 // Device tables from the host origin list (g->topo.origins / hash_mask prepared by Topology::prepare). One allocation
-// from the arena pool (hns_arena.hip) holds all of them: a cook that rebuilds the grid reuses the previous grid's memory.
+// from the arena pool (hns_arena.hip) holds all of them (hns_internal.hpp: grid_slices): a cook that rebuilds the grid reuses the previous grid's memory.
 int hns_grid_upload(hns_grid* g) {
 	int ndev = 0;
 	if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
@@ -95,22 +95,7 @@ int hns_grid_upload(hns_grid* g) {
 	Topology& t = g->topo;
 	const size_t nl = (size_t)(t.n_leaves > 0 ? t.n_leaves : 1);
 	const size_t hash_size = (size_t)t.hash_mask + 1;
-	auto pad = [](size_t bytes) { return (bytes + 255) & ~(size_t)255; };
-	const size_t sz[6] = {pad(16 * nl),              // origins (int4)
-	                      pad(4 * 27 * nl),          // nbr27
-	                      pad(4 * (hash_size + 1)),  // hash + the duplicate-origin status word
-	                      pad(4 * nl),               // sched
-	                      pad(4 * 28 * nl),          // blk records
-	                      pad(4 * (2 * nl + 2))};    // scratch of the block-record build on first use (hns_grid_build_blocks: flag[n] | leaders[n] | total[2])
-	size_t total = 0;
-	for (size_t s : sz) total += s;
-	HNS_TRY(hns_arena_get(total, g->device, &g->d_arena, &g->arena_bytes));
-	char* q = (char*)g->d_arena;
-	void** slot[6] = {&g->d_origins, &g->d_nbr27, &g->d_hash, &g->d_sched_mem, &g->d_blk, &g->d_scratch};
-	for (int i = 0; i < 6; ++i) {
-		*slot[i] = q;
-		q += sz[i];
-	}
+	HNS_TRY(carve(g->d_arena, g->device, [&](const Slice& slice) { grid_slices(*g, slice); }));
 	int* status = (int*)g->d_hash + hash_size;
 	g->on_device = true;
 	HNS_HIP(hipMemsetAsync(g->d_hash, 0xFF, sizeof(int32_t) * hash_size, 0));
@@ -153,18 +138,12 @@ int hns_grid_host_tables(const hns_grid* cg) {
 void hns_grid_free_device(hns_grid* g) {
 	if (!g) return;
 	(void)hns_grid_release_cache(g);
-	if (g->d_sb_tab) hns_arena_put(g->d_sb_tab, g->sb_bytes, g->device);
+	g->d_sb_tab.release();
 	hns_grid_retire_blocks(g);
-	g->d_sb_tab = nullptr;
-	g->sb_bytes = 0;
 	g->n_sb = 0;
 	g->sb_built = false;
-	if (g->d_diag) hns_arena_put(g->d_diag, g->diag_bytes, g->device);
-	g->d_diag = nullptr;
-	g->diag_bytes = 0;
-	hns_arena_put(g->d_arena, g->arena_bytes, g->device);
-	g->d_arena = nullptr;
-	g->arena_bytes = 0;
+	g->d_diag.release();
+	g->d_arena.release();
 	g->d_origins = g->d_nbr27 = g->d_hash = g->d_sched = g->d_sched_mem = g->d_blk = g->d_scratch = nullptr;
 	g->on_device = false;
 }

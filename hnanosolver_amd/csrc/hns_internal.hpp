@@ -230,6 +230,8 @@ __device__ __forceinline__ int launch_leaf(const GridDev& g, unsigned b) {
 
 }  // namespace hns
 
+#include "hns_pool.hpp"  // hns::Pooled, hns::carve, hns::Scratch: every block of pooled device memory below has one owner
+
 struct hns_sim;
 
 struct hns_grid {
@@ -252,24 +254,20 @@ struct hns_grid {
 	uint64_t sched_prefix = 0;    // leaves at the head of the active range that the launch order deals out to all XCDs first (hns_dist: boundary leaves)
 	void* d_sched_mem = nullptr;  // storage of d_sched (d_sched itself is null under the linear schedule)
 	void* d_scratch = nullptr;    // scratch of the block-record build (hns_grid_build_blocks)
-	void* d_arena = nullptr;      // the one device allocation all of the above are slices of (arena pool, hns_arena.hip)
-	size_t arena_bytes = 0;
+	hns::Pooled d_arena;          // the one device allocation all of the above are slices of (hns::grid_slices below)
 	// temporally blocked SOR kernel (hns_sorblock.hip): records of the 16^3-voxel blocks in launch order (64 leaves under each tile),
 	// built on first use into an arena allocation of their own
-	void* d_sb_tab = nullptr;
-	size_t sb_bytes = 0;
+	hns::Pooled d_sb_tab;
 	uint64_t n_sb = 0;
 	bool sb_built = false;
 	int sb_seg = 0;
 	uint64_t sb_first = 0, sb_count = 0;                  // the launch range the records were built for
-	std::vector<std::pair<void*, size_t>> sb_retired;     // superseded tables: back to the pool when the grid goes, or -- beyond four of them -- behind a device synchronise
+	std::vector<hns::Pooled> sb_retired;                  // superseded tables: back to the pool when the grid goes, or -- beyond four of them -- behind a device synchronise
 	// hns_dev_field_stats / hns_dev_residual (hns_diagnostics.hip): the table of per-leaf partial records, an arena allocation of its own made on first use
-	void* d_diag = nullptr;
-	size_t diag_bytes = 0;
+	hns::Pooled d_diag;
 	// hns_dev_splat_points (hns_splat.hip): the fixed-point accumulator -- splat_channels int64 channels per voxel, then one touched word per leaf --, an arena allocation of
 	// its own made on first use and all zero between calls; splat_dirty: it must be cleared before its next use (fresh from the pool, or a call failed half way)
-	void* d_splat = nullptr;
-	size_t splat_bytes = 0;
+	hns::Pooled d_splat;
 	int splat_channels = 0;
 	bool splat_dirty = false;
 	hns_splat_spec splat_spec = {0, 0, 0.0f, nullptr, 0.0f};  // hns_grid_set_splat_spec: what hns_dev_splat_points on this grid reads (the default: today's cell, a sum)
@@ -342,21 +340,17 @@ struct hns_sim {
 	}
 	unsigned long long* d_dig = nullptr;  // 16 accumulators of the digest kernels (hns_digest.hpp): a slice of the arena
 	unsigned long long* h_dig = nullptr;  // pinned host copy of them (read asynchronously on the cook's own stream)
-	void* arena = nullptr;  // every field above is a slice of this one allocation (see the arena pool, hns_arena.hip)
-	size_t arena_bytes = 0;
+	hns::Pooled arena;  // every field above is a slice of this one allocation (hns::sim_slices below)
 	// active voxel masks of the leaves (hns_sim_set_active_masks / hns_sim_regrid): leaf_count x 64 bytes, byte x*8+y, bit z; null = every voxel active.
 	// An allocation of their own from the arena pool, made on first use: nothing else reads them.
-	unsigned char* d_masks = nullptr;
-	size_t masks_bytes = 0;
+	hns::Pooled d_masks;
 	hipEvent_t rev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // phase boundaries of the last hns_sim_regrid (hns_sim_regrid_times)
 	bool regrid_timed = false;
 	// hns_sim_deactivate's device table (its counts, then one row per listed field), made on first use from the arena pool, written by a kernel
-	void* d_act = nullptr;
-	size_t act_bytes = 0;
+	hns::Pooled d_act;
 	// Diagnostics (hns_diagnostics.hip). d_diag: the records a call leaves, then the table of per-leaf partial records -- an arena allocation of its own, made on first
 	// use; h_diag: pinned host memory the records are read into. solved: p_result holds a solve on the current grid (hns_sim_residual).
-	void* d_diag = nullptr;
-	size_t diag_bytes = 0;
+	hns::Pooled d_diag;
 	hns_stats* h_diag = nullptr;
 	bool solved = false;
 	// hns_sim_set_solve_control: null = off, and then hns_sim_solve (hns_pressure.hip) is the uncontrolled loop after one pointer test
@@ -400,9 +394,46 @@ void hns_sim_drop_hierarchy(hns_sim* s);   // the sim has moved onto another gri
 void hns_sim_free_multigrid(hns_sim* s);   // (hns_sim_destroy)
 void hns_grid_free_splat(hns_grid* g);       // hns_splat.hip: the grid's accumulator back to the pool (hns_grid_release_cache, and through it hns_grid_destroy)
 
-// the sim's buffers over one arena (hns_api.hip): bytes an arena needs for n voxels, and the slices of `arena` for them (sets n, every buffer pointer, d_dig, p_result)
-size_t hns_sim_arena_need(const hns_sim* s, uint64_t n);
-void hns_sim_layout(hns_sim* s, void* arena, uint64_t n);
+// The two layouts that lie under every kernel, each stated once as a list for hns::carve (plain host arithmetic: tests/cpp/pool_owner.cpp pins their offsets).
+namespace hns {
+// A sim's buffers for n voxels over one arena, in units of one 256-byte aligned float field: vel, adv, tmp | div, p_a, p_b | cur, nxt per field | q4 (sims that hold the four
+// combustion fields) | the 16 digest accumulators of hns_compute_sim_resident. s.cur / s.nxt hold one entry per name.
+inline size_t sim_unit(uint64_t n) { return pad256(sizeof(float) * (size_t)(n ? n : 1)); }
+inline bool sim_combust(const hns_sim& s) { return std::all_of(kCombustionFields, kCombustionFields + 4, [&s](const char* n) { return s.find(n) >= 0; }); }
+inline void sim_slices(hns_sim& s, uint64_t n, const Slice& slice) {
+	const size_t unit = sim_unit(n);
+	slice(s.vel, 3, unit), slice(s.adv, 3, unit), slice(s.tmp, 3, unit);
+	slice(s.div, 1, unit), slice(s.p_a, 1, unit), slice(s.p_b, 1, unit);
+	for (size_t i = 0; i < s.names.size(); ++i) slice(s.cur[i], 1, unit), slice(s.nxt[i], 1, unit);
+	if (sim_combust(s)) slice(s.q4, 4, unit);
+	slice(s.d_dig, 16 * sizeof(unsigned long long));
+}
+// A grid's device tables over one allocation (hns_grid_upload), sized for n_active = n_leaves.
+inline void grid_slices(hns_grid& g, const Slice& slice) {
+	const size_t nl = (size_t)(g.topo.n_leaves > 0 ? g.topo.n_leaves : 1), hash_size = (size_t)g.topo.hash_mask + 1;
+	slice(g.d_origins, 16 * nl);             // int4
+	slice(g.d_nbr27, 4 * 27 * nl);
+	slice(g.d_hash, 4 * (hash_size + 1));    // + the duplicate-origin status word
+	slice(g.d_sched_mem, 4 * nl);
+	slice(g.d_blk, 4 * 28 * nl);             // block records
+	slice(g.d_scratch, 4 * (2 * nl + 2));    // of the block-record build on first use (hns_grid_build_blocks: flag[n] | leaders[n] | total[2])
+}
+}  // namespace hns
+// bytes an arena needs for n voxels of s's fields, and the slices of `arena` for them (sets n, every buffer pointer, d_dig, p_result). Neither owns anything: a sim whose
+// `arena` owner is empty may be laid over any memory (hns_regrid.hip: the new layout before the sim moves onto it).
+inline void hns_sim_layout(hns_sim* s, void* arena, uint64_t n) {
+	s->n = n;
+	s->cur.assign(s->names.size(), nullptr), s->nxt.assign(s->names.size(), nullptr);
+	s->q4 = nullptr;
+	hns::carve(arena, [&](const hns::Slice& slice) { hns::sim_slices(*s, n, slice); });
+	s->p_result = s->p_a;
+}
+inline size_t hns_sim_arena_need(const hns_sim* s, uint64_t n) {
+	hns_sim shell;  // (the list wants somewhere to point: a layout-only object with the same names)
+	shell.names = s->names;
+	shell.cur.resize(s->names.size()), shell.nxt.resize(s->names.size());
+	return hns::carve(nullptr, [&](const hns::Slice& slice) { hns::sim_slices(shell, n, slice); });
+}
 
 // implemented in hns_pressure.hip: hns_dev_rbgs_iterate with the option of starting from p = 0 without reading (or clearing) p_a
 extern "C" __attribute__((visibility("hidden"))) int hns_rbgs_iterate(hns_grid* g, const float* div, float* p_a, float* p_b, float dx, float omega, int iterations, int* result_in_b,
@@ -442,10 +473,6 @@ extern "C" __attribute__((visibility("hidden"))) int hns_combustion_div(const fl
 extern "C" __attribute__((visibility("hidden"))) int hns_combustion_fields(const float* fuel, const float* waste, const float* temperature, const float* flame,
                                                                            float* out_fuel, float* out_waste, float* out_temperature, float* out_flame,
                                                                            float temp_gain, uint64_t n, void* stream);
-
-// implemented in hns_arena.hip: process-wide pool of device allocations (simulation state and grid tables)
-extern "C" __attribute__((visibility("hidden"))) int hns_arena_get(size_t need, int device, void** p, size_t* bytes);
-extern "C" __attribute__((visibility("hidden"))) void hns_arena_put(void* p, size_t bytes, int device);
 
 // implemented in hns_gridbuild.hip
 int hns_grid_upload(hns_grid* g);           // device build of every table from topo.origins

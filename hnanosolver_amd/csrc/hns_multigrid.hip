@@ -138,7 +138,6 @@ struct Level {  // level >= 1
 	int2* parent = nullptr;          // per leaf of the level BELOW: {leaf of this level, octant}
 	float *p = nullptr, *rhs = nullptr;
 };
-size_t pad256(size_t b) { return (b + 255) & ~(size_t)255; }
 }  // namespace
 
 struct hns_sim::Multigrid {
@@ -146,8 +145,7 @@ struct hns_sim::Multigrid {
 	bool built = false;
 	std::vector<Level> levels;       // levels[i] is level i + 1
 	std::vector<uint64_t> leaves;    // per level, level 0 included
-	void* mem = nullptr;             // masks, tables and buffers of every level: one pooled allocation kept with the sim
-	size_t mem_bytes = 0;
+	Pooled mem;                      // masks, tables and buffers of every level: one pooled allocation kept with the sim
 	void drop_grids() {
 		for (Level& L : levels) hns_grid_destroy(L.grid);
 		levels.clear();
@@ -214,35 +212,25 @@ static int build_hierarchy(hns_sim* s, const char* who) {
 		host.push_back(std::move(h));
 		below = L.grid;
 	}
-	// one allocation: per level p | rhs | masks | child | parent
-	size_t need = 256;
-	for (size_t i = 0; i < mg.levels.size(); ++i) need += 2 * pad256(2048 * mg.levels[i].n) + pad256(64 * mg.levels[i].n) + pad256(32 * mg.levels[i].n) + pad256(8 * mg.leaves[i]);
-	if (!mg.mem || mg.mem_bytes < need) {
-		if (mg.mem) hns_arena_put(mg.mem, mg.mem_bytes, s->device);  // (waits for the device: nothing still reads it)
-		mg.mem = nullptr, mg.mem_bytes = 0;
-		if (int rc = hns_arena_get(need, s->device, &mg.mem, &mg.mem_bytes)) {
-			mg.drop_grids();
-			return rc;
+	// one allocation: per level p | rhs | masks | child | parent (and 256 bytes to spare behind them)
+	auto slices = [&](const Slice& slice) {
+		for (size_t i = 0; i < mg.levels.size(); ++i) {
+			Level& L = mg.levels[i];
+			slice(L.p, 2048 * L.n), slice(L.rhs, 2048 * L.n), slice(L.masks, 64 * L.n), slice(L.child, 32 * L.n), slice(L.parent, 8 * mg.leaves[i]);
 		}
-	}
-	hipStream_t st = nullptr;
-	HNS_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-	struct Closer {
-		hipStream_t st;
-		~Closer() { (void)hipStreamDestroy(st); }
-	} closer{st};
-	HNS_HIP(hipMemsetAsync(mg.mem, 0, need, st));  // (zeroed when drawn; every cycle writes what it reads all the same: tests/test_multigrid_pool_gpu.py)
-	char* q = (char*)mg.mem;
-	auto take = [&](size_t bytes) {
-		void* r = q;
-		q += pad256(bytes);
-		return r;
 	};
+	const size_t need = 256 + carve(nullptr, slices);
+	if (int rc = mg.mem.reserve(need, s->device)) {  // (a put waits for the device: nothing still reads the old block)
+		mg.drop_grids();
+		return rc;
+	}
+	PrivateStream own;
+	HNS_TRY(own.create());
+	const hipStream_t st = own.st;
+	HNS_HIP(hipMemsetAsync(mg.mem.p, 0, need, st));  // (zeroed when drawn; every cycle writes what it reads all the same: tests/test_multigrid_pool_gpu.py)
+	carve(mg.mem.p, slices);
 	for (size_t i = 0; i < mg.levels.size(); ++i) {
 		Level& L = mg.levels[i];
-		L.p = (float*)take(2048 * L.n), L.rhs = (float*)take(2048 * L.n);
-		L.masks = (unsigned char*)take(64 * L.n);
-		L.child = (int*)take(32 * L.n), L.parent = (int2*)take(8 * mg.leaves[i]);
 		HNS_HIP(hipMemcpyAsync(L.child, host[i].child.data(), 32 * L.n, hipMemcpyHostToDevice, st));
 		HNS_HIP(hipMemcpyAsync(L.parent, host[i].parent.data(), 8 * mg.leaves[i], hipMemcpyHostToDevice, st));
 		k_mg_masks<<<(unsigned)L.n, 64, 0, st>>>(L.child, i ? mg.levels[i - 1].masks : nullptr, L.masks);
@@ -269,8 +257,7 @@ void hns_sim_drop_hierarchy(hns_sim* s) {
 void hns_sim_free_multigrid(hns_sim* s) {
 	if (!s->mg) return;
 	s->mg->drop_grids();
-	hns_arena_put(s->mg->mem, s->mg->mem_bytes, s->device);
-	delete s->mg;
+	delete s->mg;  // (mem goes back to the pool with it)
 	s->mg = nullptr;
 }
 

@@ -140,10 +140,10 @@ void launch_neighbours(const hns_point_order* o, const float* xyz, int rows, flo
 	const dim3 grid((n + per_block - 1u) / per_block), block(kNbrBlock);
 	if (rows)
 		hipLaunchKernelGGL((k_neighbours<G, true>), grid, block, 0, o->stream, o->grid->dev(), (const unsigned*)o->perm, (const unsigned*)o->leaf_start,
-		                   (const unsigned*)o->cell_start, xyz, n, h, count, density, push);
+		                   o->cell_start.as<const unsigned>(), xyz, n, h, count, density, push);
 	else
 		hipLaunchKernelGGL((k_neighbours<G, false>), grid, block, 0, o->stream, o->grid->dev(), (const unsigned*)o->perm, (const unsigned*)o->leaf_start,
-		                   (const unsigned*)o->cell_start, xyz, n, h, count, density, push);
+		                   o->cell_start.as<const unsigned>(), xyz, n, h, count, density, push);
 }
 
 // what the cell calls refuse about the object's sort
@@ -156,18 +156,13 @@ int check_voxel_sort(const hns_point_order* o, const char* who) {
 // the table of the last sort, on the object's stream: drawn from the pool once, rebuilt by the first call behind every sort
 int ensure_cells(hns_point_order* o, const char* who) {
 	const size_t L = (size_t)o->n_leaves, bytes = 4 * (512 * L + 1);
-	if (!o->cell_start) {
-		void* p = nullptr;
-		size_t got = 0;
-		HNS_TRY(hns_arena_get(bytes, o->device, &p, &got));
-		o->cell_start = (uint32_t*)p, o->cells_bytes = got;
-	}
+	HNS_TRY(o->cell_start.reserve(bytes, o->device));
 	if (o->cells_fresh) return HNS_OK;
 	if (!o->n || !L) {
-		HNS_HIP(hipMemsetAsync(o->cell_start, 0, bytes, o->stream));
+		HNS_HIP(hipMemsetAsync(o->cell_start.p, 0, bytes, o->stream));
 	} else {
 		hipLaunchKernelGGL(k_cell_table, dim3((unsigned)L), dim3(kCellBlock), 0, o->stream, (const unsigned*)o->keys, (const unsigned*)o->leaf_start, (unsigned)L,
-		                   o->cell_start);
+		                   o->cell_start.as<unsigned>());
 		HNS_TRY(launch_status(who));
 	}
 	o->cells_fresh = true;
@@ -187,7 +182,7 @@ int hns_point_order_cells(hns_point_order* o, const uint32_t** d_cell_start) {
 	HNS_TRY(check_voxel_sort(o, who));
 	if (!d_cell_start) return refuse(who, "null d_cell_start");
 	HNS_TRY(ensure_cells(o, who));
-	*d_cell_start = o->cell_start;
+	*d_cell_start = o->cell_start.as<uint32_t>();
 	return HNS_OK;
 }
 

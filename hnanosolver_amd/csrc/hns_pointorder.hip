@@ -309,9 +309,8 @@ hns_point_order* hns_point_order_create(hns_grid* g, uint64_t capacity, int* err
 	DeviceScope on(g->device);
 	hns_point_order* o = new hns_point_order;
 	o->grid = g, o->device = g->device, o->capacity = capacity, o->n_leaves = L;
-	Scratch scratch(g->device);
 	const size_t cap = (size_t)std::max<uint64_t>(capacity, 1), tiles = order_tiles(cap);
-	const int rc = scratch.carve([&](auto slice) {
+	const int rc = carve(o->arena, g->device, [&](const Slice& slice) {
 		slice(o->perm, 4 * cap), slice(o->keys, 4 * cap), slice(o->ka, 4 * cap), slice(o->ia, 4 * cap), slice(o->kb, 4 * cap), slice(o->ib, 4 * cap);
 		slice(o->leaf_start, 4 * (size_t)(L + 3)), slice(o->hist, 4 * (size_t)kRadix * tiles), slice(o->total, 4 * (size_t)kRadix);
 	});
@@ -319,17 +318,13 @@ hns_point_order* hns_point_order_create(hns_grid* g, uint64_t capacity, int* err
 		delete o;
 		return out(rc);
 	}
-	o->arena = o->perm;
-	o->arena_bytes = scratch.keep(o->arena);
 	if (err) *err = HNS_OK;
 	return o;
 }
 
 void hns_point_order_destroy(hns_point_order* o) {
 	if (!o) return;
-	if (o->arena) hns_arena_put(o->arena, o->arena_bytes, o->device);  // (waits for the device first)
-	if (o->cell_start) hns_arena_put(o->cell_start, o->cells_bytes, o->device);
-	delete o;
+	delete o;  // (its two blocks go back to the pool, which waits for the device first)
 }
 
 int hns_point_order_set_stream(hns_point_order* o, void* hip_stream) {

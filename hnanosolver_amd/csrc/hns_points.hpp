@@ -230,16 +230,14 @@ struct hns_point_order {
 	uint64_t capacity = 0, n_leaves = 0;
 	hipStream_t stream = nullptr;
 	// one pooled allocation: the results, the (key, index) ping-pong -- the keys of k_order_keys lie in kb: by the time a pass writes kb they are spent --, and the tables
-	void* arena = nullptr;
-	size_t arena_bytes = 0;
+	hns::Pooled arena;
 	uint32_t *perm = nullptr, *keys = nullptr, *ka = nullptr, *ia = nullptr, *kb = nullptr, *ib = nullptr, *leaf_start = nullptr;
 	uint32_t *hist = nullptr, *total = nullptr;  // of the running pass: the [digit][tile] table and its row sums
 	uint64_t n = 0;
 	int level = -1;
 	bool sorted = false;
 	// the cell table of a voxel-level sort (hns_neighbours.hip): a pooled allocation of its own, drawn by the first call that needs it; stale after every sort
-	uint32_t* cell_start = nullptr;
-	size_t cells_bytes = 0;
+	hns::Pooled cell_start;
 	bool cells_fresh = false;
 };
 

@@ -242,8 +242,7 @@ struct hns_point_population {
 	uint64_t capacity = 0, n_leaves = 0;
 	hipStream_t stream = nullptr;
 	// one pooled allocation: the slots, the tile table, the counters {live, wanted}
-	void* arena = nullptr;
-	size_t arena_bytes = 0;
+	Pooled arena;
 	uint32_t *slot = nullptr, *table = nullptr;
 	unsigned long long* counters = nullptr;
 	uint64_t n = 0;  // of the last select
@@ -304,25 +303,21 @@ hns_point_population* hns_point_population_create(hns_grid* g, uint64_t capacity
 	DeviceScope on(g->device);
 	hns_point_population* o = new hns_point_population;
 	o->grid = g, o->device = g->device, o->capacity = capacity, o->n_leaves = L;
-	Scratch scratch(g->device);
 	const size_t cap = (size_t)std::max<uint64_t>(capacity, 1), tiles = std::max<size_t>(pop_tiles(std::max<uint64_t>(capacity, L * 512)), 1);
-	int rc = scratch.carve([&](auto slice) { slice(o->slot, 4 * cap), slice(o->table, 4 * tiles), slice(o->counters, 16); });
+	int rc = carve(o->arena, g->device, [&](const Slice& slice) { slice(o->slot, 4 * cap), slice(o->table, 4 * tiles), slice(o->counters, 16); });
 	if (rc == HNS_OK && (hipMemsetAsync(o->counters, 0, 16, nullptr) != hipSuccess || hipStreamSynchronize(nullptr) != hipSuccess))
 		rc = fail(HNS_ERR_HIP, "hns_point_population_create: clearing the counters failed");
 	if (rc != HNS_OK) {
 		delete o;
 		return out(rc);
 	}
-	o->arena = o->slot;
-	o->arena_bytes = scratch.keep(o->arena);
 	if (err) *err = HNS_OK;
 	return o;
 }
 
 void hns_point_population_destroy(hns_point_population* o) {
 	if (!o) return;
-	if (o->arena) hns_arena_put(o->arena, o->arena_bytes, o->device);  // (waits for the device first)
-	delete o;
+	delete o;  // (its block goes back to the pool, which waits for the device first)
 }
 
 int hns_point_population_set_stream(hns_point_population* o, void* hip_stream) {
@@ -406,7 +401,7 @@ int hns_point_population_birth_sim(hns_point_population* o, hns_sim* s, const ch
 		set_error("%s: the sim has no float field '%s'", who, name ? name : "(null)");
 		return HNS_ERR_INVALID_ARGUMENT;
 	}
-	return birth(who, o, s->cur[(size_t)f], use_masks ? s->d_masks : nullptr, sp, d_xyz, d_voxel, capacity_rows, append);
+	return birth(who, o, s->cur[(size_t)f], use_masks ? s->d_masks.as<unsigned char>() : nullptr, sp, d_xyz, d_voxel, capacity_rows, append);
 }
 
 int hns_point_population_get(const hns_point_population* o, hns_point_population_info* info) {

@@ -303,7 +303,7 @@ int launch_fields(const FieldSet& fs, int nf, int nc, bool add, uint64_t n_new, 
 	return HNS_OK;
 }
 
-// (Scratch, the device allocations of one regrid: hns_seed.hpp)
+// (Scratch, the device allocations of one regrid: hns_pool.hpp)
 
 // One entry of the regrid's source list: the collision SDF or one source of hns_sim_regrid_sourced, validated, and where its leaves live on the
 // device. The kinds differ in three places only: the velocity's leaves are dilated candidates (phase 1) and its masks are dilated into the new
@@ -360,6 +360,7 @@ struct Regrid {
 	int* unseeded = nullptr;  // with point seeds: is the new leaf one of the unseeded domain's?
 	void* new_masks = nullptr;
 	void* new_fields = nullptr;
+	size_t i_masks = 0, i_fields = 0;  // their blocks in scratch.held
 
 	Regrid(hns_sim* sim, int padding, hipStream_t stream, const char* w) : s(sim), p(padding), R((padding + 7) / 8), st(stream), who(w), scratch(sim->device) {}
 
@@ -450,7 +451,7 @@ struct Regrid {
 	int candidates() {
 		const hns_grid* og = s->grid;
 		const uint64_t K = (uint64_t)(2 * R + 1) * (2 * R + 1) * (2 * R + 1);
-		c.old_origins = (const int4*)og->d_origins, c.old_masks = s->d_masks;
+		c.old_origins = (const int4*)og->d_origins, c.old_masks = s->d_masks.as<unsigned char>();
 		c.n_dil = (uint64_t)og->topo.n_leaves * K, c.n_sdf = sdf ? sdf->l.n_leaves : 0;
 		c.seeds[kVsrcSeeds].n_dil = vsrc ? vsrc->l.n_leaves * K : 0, c.seeds[kPointSeeds].n_dil = points ? points->l.n_leaves * K : 0;
 		c.side = 2 * R + 1, c.R = R, c.p = p;
@@ -547,6 +548,7 @@ struct Regrid {
 			if (points) slice(unseeded, 4 * n_new);
 		}));
 		HNS_TRY(scratch.get(64 * n_new, &new_masks));
+		i_masks = scratch.held.size() - 1;
 		if (!srcs.empty())
 			HNS_TRY(scratch.carve([&](auto&& slice) {
 				for (Source& q : srcs)
@@ -563,7 +565,7 @@ struct Regrid {
 		SeedHashes sh{};
 		if (vsrc) sh.h[kVsrcSeeds] = OriginIndex{vsrc->origins, vsrc->table, vsrc->mask}, sh.masks[kVsrcSeeds] = vsrc->masks;
 		if (points) sh.h[kPointSeeds] = OriginIndex{points->origins, points->table, points->mask}, sh.masks[kPointSeeds] = points->masks;
-		k_regrid_masks<<<(unsigned)((n_new + 3) / 4), 256, 0, st>>>(s->grid->dev(), s->d_masks, (const int4*)ng->d_origins, (int)n_new, p, R, sdf ? sdf->idx : nullptr,
+		k_regrid_masks<<<(unsigned)((n_new + 3) / 4), 256, 0, st>>>(s->grid->dev(), s->d_masks.as<unsigned char>(), (const int4*)ng->d_origins, (int)n_new, p, R, sdf ? sdf->idx : nullptr,
 		                                                           sdf ? sdf->masks : nullptr, sh, (uint64_t*)new_masks, map, vsrc ? vsrc->idx : nullptr, unseeded);
 		HNS_HIP(hipGetLastError());
 		for (Source& q : srcs) {
@@ -588,6 +590,7 @@ struct Regrid {
 		hns_sim shell;  // the new layout, built over the new arena (the sim itself keeps the old one until the end)
 		shell.names = s->names;
 		HNS_TRY(scratch.get(hns_sim_arena_need(s, n_new * 512u), &new_fields));
+		i_fields = scratch.held.size() - 1;
 		hns_sim_layout(&shell, new_fields, n_new * 512u);
 		std::vector<const Source*> src_of(s->names.size(), nullptr);
 		for (const Source& q : srcs)
@@ -626,11 +629,9 @@ struct Regrid {
 				set_error("%s: source %d ('%s'): duplicate leaf origin", who, srcs[i].index, srcs[i].name());
 			return HNS_ERR_TOPOLOGY;
 		}
-		scratch.held.emplace_back(s->arena, s->arena_bytes);  // the old state goes back to the pool with the scratch
-		if (s->d_masks) scratch.held.emplace_back(s->d_masks, s->masks_bytes);
-		s->arena = new_fields, s->arena_bytes = scratch.keep(new_fields);
+		std::swap(s->arena, scratch.held[i_fields]);  // the old state goes back to the pool with the scratch
+		std::swap(s->d_masks, scratch.held[i_masks]);
 		hns_sim_layout(s, new_fields, n_new * 512u);
-		s->d_masks = (unsigned char*)new_masks, s->masks_bytes = scratch.keep(new_masks);
 		s->grid = ng.release();
 		s->forget();
 		hns_sim_drop_hierarchy(s);  // (hns_sim_set_solve_method: the next solve builds the new grid's)
@@ -742,18 +743,12 @@ extern "C" int hns_sim_set_active_masks(hns_sim* s, const unsigned char* masks, 
 	if (!s) return fail(HNS_ERR_INVALID_ARGUMENT, "hns_sim_set_active_masks: null sim");
 	const uint64_t n_leaves = s->n / 512u;
 	if (!masks) {  // every voxel active: the state a sim starts in
-		if (s->d_masks) hns_arena_put(s->d_masks, s->masks_bytes, s->device);
-		s->d_masks = nullptr, s->masks_bytes = 0;
+		s->d_masks.release();
 		return HNS_OK;
 	}
 	if (!n_leaves) return HNS_OK;
-	if (!s->d_masks) {
-		void* p = nullptr;
-		size_t got = 0;
-		HNS_TRY(hns_arena_get(64 * n_leaves, s->device, &p, &got));
-		s->d_masks = (unsigned char*)p, s->masks_bytes = got;
-	}
-	HNS_HIP(hipMemcpyAsync(s->d_masks, masks, 64 * n_leaves, hipMemcpyHostToDevice, (hipStream_t)stream));
+	HNS_TRY(s->d_masks.reserve(64 * n_leaves, s->device));
+	HNS_HIP(hipMemcpyAsync(s->d_masks.p, masks, 64 * n_leaves, hipMemcpyHostToDevice, (hipStream_t)stream));
 	return HNS_OK;
 }
 
@@ -764,7 +759,7 @@ extern "C" int hns_sim_active_masks(hns_sim* s, unsigned char* out, void* stream
 		memset(out, 0xFF, 64 * n_leaves);
 		return HNS_OK;
 	}
-	HNS_HIP(hipMemcpyAsync(out, s->d_masks, 64 * n_leaves, hipMemcpyDeviceToHost, (hipStream_t)stream));
+	HNS_HIP(hipMemcpyAsync(out, s->d_masks.p, 64 * n_leaves, hipMemcpyDeviceToHost, (hipStream_t)stream));
 	HNS_HIP(hipStreamSynchronize((hipStream_t)stream));
 	return HNS_OK;
 }
@@ -838,21 +833,12 @@ extern "C" int hns_sim_deactivate(hns_sim* s, const hns_activity_field* fields, 
 	}
 	DeviceScope on(s->device);
 	const hipStream_t st = (hipStream_t)stream;
-	if (!s->d_act) {  // the packed count, then a row per field the sim could list (its float fields and the velocity)
-		void* p = nullptr;
-		size_t got = 0;
-		HNS_TRY(hns_arena_get(16 + sizeof(ActField) * (s->names.size() + 1), s->device, &p, &got));
-		s->d_act = p, s->act_bytes = got;
-	}
-	unsigned long long* d_count = (unsigned long long*)s->d_act;
-	ActField* d_tab = (ActField*)((char*)s->d_act + 16);
-	unsigned char* masks = s->d_masks;
-	size_t masks_bytes = s->masks_bytes;
-	if (!masks) {  // all active until now: the kernel reads no masks and writes the first ones
-		void* p = nullptr;
-		HNS_TRY(hns_arena_get(64 * n_leaves, s->device, &p, &masks_bytes));
-		masks = (unsigned char*)p;
-	}
+	HNS_TRY(s->d_act.reserve(16 + sizeof(ActField) * (s->names.size() + 1), s->device));  // the packed count, then a row per field the sim could list (its float fields and the velocity)
+	unsigned long long* d_count = s->d_act.as<unsigned long long>();
+	ActField* d_tab = (ActField*)(s->d_act.as<char>() + 16);
+	Pooled first_masks;  // all active until now: the kernel reads no masks and writes the first ones, which the sim takes once the launches went out
+	if (!s->d_masks) HNS_TRY(first_masks.get(64 * n_leaves, s->device));
+	unsigned char* masks = s->d_masks ? s->d_masks.as<unsigned char>() : first_masks.as<unsigned char>();
 	int rc = HNS_OK;
 	for (int i0 = 0; i0 < n_fields && rc == HNS_OK; i0 += kActRows) {
 		ActRows rows{};
@@ -865,15 +851,12 @@ extern "C" int hns_sim_deactivate(hns_sim* s, const hns_activity_field* fields, 
 		if (hipGetLastError() != hipSuccess) rc = fail(HNS_ERR_HIP, "hns_sim_deactivate: table launch failed");
 	}
 	if (rc == HNS_OK) {
-		k_deactivate<<<(unsigned)((n_leaves + 3) / 4), 256, 0, st>>>(d_tab, n_fields, (const uint64_t*)s->d_masks, (uint64_t*)masks, n_leaves,
+		k_deactivate<<<(unsigned)((n_leaves + 3) / 4), 256, 0, st>>>(d_tab, n_fields, s->d_masks.as<const uint64_t>(), (uint64_t*)masks, n_leaves,
 		                                                            counts ? d_count : nullptr);
 		if (hipGetLastError() != hipSuccess) rc = fail(HNS_ERR_HIP, "hns_sim_deactivate: kernel launch failed");
 	}
-	if (rc != HNS_OK) {  // nothing ran: the masks are as they were
-		if (masks != s->d_masks) hns_arena_put(masks, masks_bytes, s->device);
-		return rc;
-	}
-	s->d_masks = masks, s->masks_bytes = masks_bytes;
+	if (rc != HNS_OK) return rc;  // nothing ran: the masks are as they were
+	if (first_masks) s->d_masks = std::move(first_masks);
 	s->drop_ahead();  // (the end of a frame: the next substep belongs to another one)
 	if (counts) {
 		unsigned long long packed = 0;

@@ -723,10 +723,8 @@ int hns_grid_build_blocks(hns_grid* g) {
 			HNS_HIP(hipDeviceSynchronize());
 			hns_grid_retire_blocks(g);
 		}
-		g->sb_retired.emplace_back(g->d_sb_tab, g->sb_bytes);
+		g->sb_retired.push_back(std::move(g->d_sb_tab));
 	}
-	g->d_sb_tab = nullptr;
-	g->sb_bytes = 0;
 	g->n_sb = 0;
 	g->sb_built = true;
 	g->sb_seg = seg;
@@ -741,12 +739,9 @@ int hns_grid_build_blocks(hns_grid* g) {
 	// (chain_boundary: the leading leaves of the range that are a multi-GPU rank's boundary leaves -- hns_dist_*.hip sets it on the range its
 	// chained sweeps run over; 0 everywhere else. sched_prefix != 0: deal the blocks they lead out to all XCDs first)
 	const int n_boundary = g->chain_boundary ? first + (int)std::min<uint64_t>(g->chain_boundary, g->n_active) : 0;
-	hipStream_t st = nullptr;
-	HNS_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-	struct Drop {
-		hipStream_t s;
-		~Drop() { (void)hipStreamDestroy(s); }
-	} drop{st};
+	PrivateStream own;
+	HNS_TRY(own.create());
+	const hipStream_t st = own.st;
 	hipLaunchKernelGGL(k_sb_leader, dim3((n + 255) / 256), dim3(256), 0, st, gd, first, count, flag);
 	hipLaunchKernelGGL(k_sb_compact, dim3(1), dim3(1024), 0, st, (const int*)flag, n, leaders, total, n_boundary);
 	int tot[2] = {0, 0};
@@ -754,18 +749,17 @@ int hns_grid_build_blocks(hns_grid* g) {
 	HNS_HIP(hipStreamSynchronize(st));
 	const int nb = tot[0];
 	if (nb <= 0) return fail(HNS_ERR_RUNTIME, "hns_grid_build_blocks: no block leader found");
-	if (int rc = hns_arena_get(sizeof(int) * 65 * (size_t)nb, g->device, &g->d_sb_tab, &g->sb_bytes)) return rc;
-	HNS_HIP(hipMemsetAsync((int*)g->d_sb_tab + (size_t)nb * 64, 0, sizeof(int) * (size_t)nb, st));
+	HNS_TRY(g->d_sb_tab.get(sizeof(int) * 65 * (size_t)nb, g->device));
+	HNS_HIP(hipMemsetAsync(g->d_sb_tab.as<int>() + (size_t)nb * 64, 0, sizeof(int) * (size_t)nb, st));
 	// the blocks led by a boundary leaf are dealt out to all XCDs first (as hns_grid_upload_schedule does with the boundary leaves themselves)
 	const int pre = (n_boundary && g->sched_prefix) ? (std::min(tot[1], nb) & ~7) : 0;
-	hipLaunchKernelGGL(k_sb_table, dim3((unsigned)(((int64_t)nb * 64 + 255) / 256)), dim3(256), 0, st, gd, (const int*)leaders, nb, seg, pre, first, count, n_boundary, (int*)g->d_sb_tab);
+	hipLaunchKernelGGL(k_sb_table, dim3((unsigned)(((int64_t)nb * 64 + 255) / 256)), dim3(256), 0, st, gd, (const int*)leaders, nb, seg, pre, first, count, n_boundary, g->d_sb_tab.as<int>());
 	HNS_HIP(hipStreamSynchronize(st));
 	g->n_sb = (uint64_t)nb;
 	return HNS_OK;
 }
 
 void hns_grid_retire_blocks(hns_grid* g) {  // (the grid is being destroyed or rebuilt: the device is idle for it)
-	for (auto& t : g->sb_retired) hns_arena_put(t.first, t.second, g->device);
 	g->sb_retired.clear();
 }
 
@@ -826,7 +820,7 @@ static XYLaunch launch_xy_blocks(hns_grid* g, int iterations, bool src_is_zero, 
 	uint64_t n_sb;
 	{
 		std::lock_guard<std::mutex> lock(g->build_mutex);
-		tab = (const int*)g->d_sb_tab, n_sb = g->n_sb;
+		tab = g->d_sb_tab.as<const int>(), n_sb = g->n_sb;
 	}
 	if (!tab || !n_sb) return XYLaunch::no_records;
 	if (iterations != 1 && iterations != 2) return XYLaunch::bad_iterations;

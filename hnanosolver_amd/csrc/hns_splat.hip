@@ -138,14 +138,13 @@ size_t splat_acc_bytes(const hns_grid* g, int channels) { return sizeof(unsigned
 int splat_accumulator(hns_grid* g, int channels, hipStream_t st) {
 	std::lock_guard<std::mutex> lock(g->build_mutex);
 	if (!g->d_splat || g->splat_channels < channels) {
-		if (g->d_splat) hns_arena_put(g->d_splat, g->splat_bytes, g->device);  // (waits for the device: nothing still adds into it)
-		g->d_splat = nullptr, g->splat_bytes = 0, g->splat_channels = 0;
-		HNS_TRY(hns_arena_get(splat_acc_bytes(g, channels) + sizeof(int) * (size_t)g->topo.n_leaves, g->device, &g->d_splat, &g->splat_bytes));
+		g->splat_channels = 0;  // (a narrower block goes back first, behind a wait for the device: nothing still adds into it)
+		HNS_TRY(g->d_splat.get(splat_acc_bytes(g, channels) + sizeof(int) * (size_t)g->topo.n_leaves, g->device));
 		g->splat_channels = channels;
 		g->splat_dirty = true;
 	}
 	if (g->splat_dirty) {
-		HNS_HIP(hipMemsetAsync(g->d_splat, 0, splat_acc_bytes(g, g->splat_channels) + sizeof(int) * (size_t)g->topo.n_leaves, st));
+		HNS_HIP(hipMemsetAsync(g->d_splat.p, 0, splat_acc_bytes(g, g->splat_channels) + sizeof(int) * (size_t)g->topo.n_leaves, st));
 		g->splat_dirty = false;
 	}
 	return HNS_OK;
@@ -268,8 +267,8 @@ int splat_points(const char* who, hns_grid* g, const hns_splat_spec& sp, float* 
 		for (int c = 0; c < ncomp[i]; ++c) all.push_back(SplatChannel{values[i], fields[i], ncomp[i], c, ncomp[i] == 1 && ((uintptr_t)fields[i] & 15u) == 0});
 	HNS_TRY(splat_accumulator(g, std::min<int>(kSplatChannels, (int)all.size() + (sp.mode ? 1 : 0)), st));
 	const int S = g->splat_channels;
-	unsigned long long* acc = (unsigned long long*)g->d_splat;
-	int* touched = (int*)((char*)g->d_splat + splat_acc_bytes(g, S));
+	unsigned long long* acc = g->d_splat.as<unsigned long long>();
+	int* touched = (int*)(g->d_splat.as<char>() + splat_acc_bytes(g, S));
 	const double scale = std::ldexp(1.0, -log2_quantum), quantum = std::ldexp(1.0, log2_quantum);
 	const unsigned n_leaves = (unsigned)g->topo.n_leaves;
 	const dim3 pgrid((unsigned)((n + kSplatBlock - 1) / kSplatBlock)), lgrid((n_leaves + 3u) / 4u);
@@ -308,8 +307,8 @@ int floor_sat(float x) {
 
 void hns_grid_free_splat(hns_grid* g) {
 	std::lock_guard<std::mutex> lock(g->build_mutex);
-	if (g->d_splat) hns_arena_put(g->d_splat, g->splat_bytes, g->device);
-	g->d_splat = nullptr, g->splat_bytes = 0, g->splat_channels = 0, g->splat_dirty = false;
+	g->d_splat.release();
+	g->splat_channels = 0, g->splat_dirty = false;
 }
 
 extern "C" {
@@ -327,7 +326,7 @@ int hns_sim_splat_points(hns_sim* s, const char* const* names, int n_names, cons
 	std::vector<const float*> vals;
 	std::vector<int> ncomp, which;
 	HNS_TRY(sim_splat_fields(who, s, names, n_names, velocity_values, values, fields, vals, ncomp, which));
-	HNS_TRY(splat_points(who, s->grid, s->splat_spec, fields.data(), ncomp.data(), (int)fields.size(), xyz, vals.data(), n, log2_quantum, activate ? s->d_masks : nullptr,
+	HNS_TRY(splat_points(who, s->grid, s->splat_spec, fields.data(), ncomp.data(), (int)fields.size(), xyz, vals.data(), n, log2_quantum, activate ? s->d_masks.as<unsigned char>() : nullptr,
 	                     status, d_rejected, stream));
 	if (n) sim_splat_wrote(s, which, velocity_values != nullptr);
 	return HNS_OK;

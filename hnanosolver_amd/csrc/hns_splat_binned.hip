@@ -285,8 +285,8 @@ int splat_ordered(const char* who, const hns_point_order* o, const hns_splat_spe
 		for (int c = 0; c < ncomp[i]; ++c) all.push_back(SplatChannel{values[i], fields[i], ncomp[i], c, 0});
 	HNS_TRY(splat_accumulator(g, std::min<int>(kSplatChannels, (int)all.size() + (sp.mode ? 1 : 0)), st));
 	const int S = g->splat_channels;
-	unsigned long long* acc = (unsigned long long*)g->d_splat;
-	int* touched = (int*)((char*)g->d_splat + splat_acc_bytes(g, S));
+	unsigned long long* acc = g->d_splat.as<unsigned long long>();
+	int* touched = (int*)(g->d_splat.as<char>() + splat_acc_bytes(g, S));
 	const double scale = std::ldexp(1.0, -log2_quantum), quantum = std::ldexp(1.0, log2_quantum);
 	const unsigned n_leaves = (unsigned)g->topo.n_leaves;
 	const OrderDev od{o->perm, o->leaf_start, (unsigned)n, rows};
@@ -338,7 +338,7 @@ int hns_point_order_splat_sim(const hns_point_order* o, hns_sim* s, const char* 
 	std::vector<const float*> vals;
 	std::vector<int> ncomp, which;
 	HNS_TRY(sim_splat_fields(who, s, names, n_names, velocity_values, values, fields, vals, ncomp, which));
-	HNS_TRY(splat_ordered(who, o, s->splat_spec, fields.data(), ncomp.data(), (int)fields.size(), d_xyz, vals.data(), rows, log2_quantum, activate ? s->d_masks : nullptr, status,
+	HNS_TRY(splat_ordered(who, o, s->splat_spec, fields.data(), ncomp.data(), (int)fields.size(), d_xyz, vals.data(), rows, log2_quantum, activate ? s->d_masks.as<unsigned char>() : nullptr, status,
 	                      d_rejected));
 	if (o->n) sim_splat_wrote(s, which, velocity_values != nullptr);
 	return HNS_OK;
