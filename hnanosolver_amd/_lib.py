@@ -85,6 +85,18 @@ class hns_point_collision(C.Structure):
 HNS_COLLIDE_STOP, HNS_COLLIDE_PUSH, HNS_COLLIDE_KILL = 1, 2, 3
 
 
+class hns_point_motion_info(C.Structure):
+    _fields_ = [("capacity", C.c_uint64), ("xyz", C.c_void_p), ("vel", C.c_void_p), ("age", C.c_void_p), ("status", C.c_void_p), ("hit", C.c_void_p)]
+
+
+class hns_point_motion_spec(C.Structure):
+    _fields_ = [("mode", C.c_int), ("gravity", C.c_float * 3), ("drag", C.c_float), ("restitution", C.c_float), ("friction", C.c_float), ("max_age", C.c_float),
+                ("threshold", C.c_float), ("skin", C.c_float), ("iterations", C.c_int)]
+
+
+HNS_MOTION_FREE, HNS_MOTION_STICK, HNS_MOTION_BOUNCE, HNS_MOTION_KILL = 0, 1, 2, 3
+
+
 class hns_point_order_info(C.Structure):
     _fields_ = [("perm", C.c_void_p), ("keys", C.c_void_p), ("leaf_start", C.c_void_p), ("n", C.c_uint64), ("n_leaves", C.c_uint64), ("capacity", C.c_uint64),
                 ("level", C.c_int)]
@@ -188,6 +200,11 @@ SIGNATURES = {
     "hns_dev_trace_points": (_i, [_vp, _fp, _fp, _u64, _f, _f, _i, _i, _vp, _vp]),
     "hns_dev_trace_points_collide": (_i, [_vp, _fp, _fp, _fp, _u64, _f, _f, _i, _i, C.POINTER(hns_point_collision), _vp, _vp, _vp]),
     "hns_sim_trace_points_collide": (_i, [_vp, _fp, _u64, _f, _f, _i, _i, C.POINTER(hns_point_collision), _vp, _vp, _vp]),
+    "hns_point_motion_create": (_vp, [_u64, _ip]),
+    "hns_point_motion_destroy": (None, [_vp]),
+    "hns_point_motion_set_stream": (_i, [_vp, _vp]),
+    "hns_point_motion_get": (_i, [_vp, C.POINTER(hns_point_motion_info)]),
+    "hns_point_motion_step": (_i, [_vp, _vp, _u64, _f, _f, _i, C.POINTER(hns_point_motion_spec)]),
     "hns_dev_splat_points": (_i, [_vp, C.POINTER(C.c_void_p), _ip, _i, _fp, C.POINTER(C.c_void_p), _u64, _i, _vp, _vp, _vp]),
     "hns_grid_splat_points": (_i, [_vp, C.POINTER(C.c_void_p), _ip, _i, _fp, C.POINTER(C.c_void_p), _u64, _i, _vp, _i, _vp, C.POINTER(C.c_uint64)]),
     "hns_grid_set_splat_spec": (_i, [_vp, C.POINTER(hns_splat_spec)]),

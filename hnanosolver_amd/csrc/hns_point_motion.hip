@@ -1,0 +1,232 @@
+// hns_point_motion.hip -- points with a velocity of their own: an object that owns the per-point state (position, velocity, age, status, hit; one block of the pool) and
+// the kernel that steps it through a sim's fluid: drag towards the gas (implicit Euler), gravity, the move, and the collision SDF's answer to a step that lands in the
+// collider -- stick, bounce (reflect the velocity about the SDF's normal, then the collision trace's push) or kill. The samplers, the leaf cursor and the normal are those of
+// hns_points.hpp and hns_device.hpp, as k_trace_points_collide (hns_points_collide.hip) uses them; include/hns.h states the arithmetic line by line. One thread per point,
+// no LDS, no atomics. -ffp-contract=off.
+#include "hns_points.hpp"
+
+#include <cmath>
+
+using namespace hns;
+
+namespace {
+
+constexpr int kMotionBlock = 256;
+
+// what hit holds (include/hns.h)
+constexpr unsigned kHitBounced = 1, kHitReverted = 2, kHitKilled = 4, kHitStartInside = 8, kHitReflected = 16;
+
+// the host's constants of one call (include/hns.h: "Host constants"), by value: wave-uniform, so the branches on mode and empty cost no divergence
+struct MotionDev {
+	int mode, iterations;
+	int empty;  // the grid has no leaves: U = 0 and S = 0 everywhere, no leaf exists
+	float inv_dx, s, k, r, dt, gdx, gdy, gdz, restitution, ft, max_age, threshold, skin;
+};
+
+// `steps` steps of a point. COLLIDE = false is mode FREE: S is not in the kernel at all. The bounce holds one float sample at a time (the rolled sampler body of
+// k_trace_points_collide); x, v and age are written once, behind the last step. A killed point leaves the loop.
+template <bool COLLIDE>
+__global__ __launch_bounds__(kMotionBlock) void k_move_points(const GridDev g, const float* __restrict__ u, const float* __restrict__ sdf, float* __restrict__ xyz,
+                                                               float* __restrict__ vel, float* __restrict__ age, const unsigned n, const int steps, const MotionDev c,
+                                                               unsigned char* __restrict__ status, unsigned char* __restrict__ hit) {
+	const unsigned p = blockIdx.x * (unsigned)kMotionBlock + threadIdx.x;
+	if (p >= n) return;
+	f3 x = ld3(xyz, (int)p);
+	if (!(finite_f(x.x) && finite_f(x.y) && finite_f(x.z))) {  // a row that holds no point (PointPopulation's rows beyond the live count): every bit stays
+		status[p] = 0;
+		hit[p] = 0;
+		return;
+	}
+	f3 v = ld3(vel, (int)p);
+	float a = age[p];
+	Cursor cur{-1, 0, 0, 0};
+	auto U = [&](float q, float b, float e) { return c.empty ? f3{0.0f, 0.0f, 0.0f} : sample_v(u, point_cell<true>(g, cur, q, b, e)); };
+	auto S = [&](float q, float b, float e) { return c.empty ? 0.0f : sample_f(sdf, point_cell<true>(g, cur, q, b, e)); };
+	unsigned flags = 0;
+	if (COLLIDE) flags = S(x.x, x.y, x.z) < c.threshold ? kHitStartInside : 0u;
+	bool dead = false;
+	for (int step = 0; step < steps; ++step) {
+		const f3 w = U(x.x, x.y, x.z);
+		f3 t = {c.k * w.x, c.k * w.y, c.k * w.z};  // drag, implicit Euler
+		t = f3{v.x + t.x, v.y + t.y, v.z + t.z};
+		v = f3{t.x * c.r, t.y * c.r, t.z * c.r};
+		v = f3{v.x + c.gdx, v.y + c.gdy, v.z + c.gdz};  // gravity
+		const f3 m = {c.s * v.x, c.s * v.y, c.s * v.z};  // the move
+		f3 x1 = {x.x + m.x, x.y + m.y, x.z + m.z};
+		a = a + c.dt;
+		if (COLLIDE) {
+			float d = S(x1.x, x1.y, x1.z);
+			if (d < c.threshold) {
+				if (c.mode == HNS_MOTION_KILL) {
+					flags |= kHitKilled;
+					dead = true;
+					x = x1;
+					break;
+				}
+				if (c.mode == HNS_MOTION_STICK) {
+					flags |= kHitReverted;
+					v = f3{0.0f, 0.0f, 0.0f};
+					x1 = x;
+				} else {
+					flags |= kHitBounced;
+#pragma unroll 1
+					for (int it = 0; it < c.iterations && d < c.threshold; ++it) {
+						float nb[6] = {};
+#pragma unroll 1
+						for (int q = 0; q < 6; ++q) {  // -x, +x, -y, +y, -z, +z: ONE sampler body in the code, one sample's taps in flight (x + -1.0f is x - 1.0f)
+							const float off = (q & 1) ? 1.0f : -1.0f;
+							const int axis = q >> 1;
+							const float val = S(axis == 0 ? x1.x + off : x1.x, axis == 1 ? x1.y + off : x1.y, axis == 2 ? x1.z + off : x1.z);
+#pragma unroll
+							for (int e = 0; e < 6; ++e) nb[e] = q == e ? val : nb[e];  // (selects: nb stays in registers)
+						}
+						const f3 nrm = sdf_normal_of(nb, c.inv_dx);
+						if (it == 0) {  // reflect the velocity, once a step
+							const float vn = (v.x * nrm.x + v.y * nrm.y) + v.z * nrm.z;
+							if (vn < 0.0f) {
+								const f3 wn = {vn * nrm.x, vn * nrm.y, vn * nrm.z};
+								const f3 vt = {v.x - wn.x, v.y - wn.y, v.z - wn.z};
+								const float b = c.restitution * vn;
+								const f3 pt = {c.ft * vt.x, c.ft * vt.y, c.ft * vt.z};
+								const f3 qn = {b * nrm.x, b * nrm.y, b * nrm.z};
+								v = f3{pt.x - qn.x, pt.y - qn.y, pt.z - qn.z};
+								flags |= kHitReflected;
+							}
+						}
+						float b = (c.threshold - d) * c.inv_dx;
+						b = b + c.skin;
+						x1 = f3{x1.x + b * nrm.x, x1.y + b * nrm.y, x1.z + b * nrm.z};
+						d = S(x1.x, x1.y, x1.z);
+					}
+					if (d < c.threshold) {  // a push that did not get out: the reflected velocity stays
+						flags |= kHitReverted;
+						x1 = x;
+					}
+				}
+			}
+		}
+		x = x1;
+	}
+	st3(xyz, (int)p, x);
+	st3(vel, (int)p, v);
+	age[p] = a;
+	hit[p] = (unsigned char)flags;
+	bool in = !dead && finite_f(x.x) && finite_f(x.y) && finite_f(x.z) && a < c.max_age && !c.empty;
+	if (in) {
+		int L[8];
+		const int i = __float2int_rd(x.x), j = __float2int_rd(x.y), k = __float2int_rd(x.z);
+		cell_leaves<true>(g, cur, i & ~7, j & ~7, k & ~7, L);  // (the leaf's own corner: one lookup)
+		in = L[0] >= 0;
+	}
+	status[p] = in ? 1 : 0;
+}
+
+}  // namespace
+
+struct hns_point_motion {
+	int device = -1;
+	uint64_t capacity = 0;
+	hipStream_t stream = nullptr;
+	// one pooled allocation: the five per-point arrays
+	Pooled arena;
+	float *xyz = nullptr, *vel = nullptr, *age = nullptr;
+	unsigned char *status = nullptr, *hit = nullptr;
+};
+
+extern "C" {
+
+hns_point_motion* hns_point_motion_create(uint64_t capacity, int* err) {
+	const char* who = "hns_point_motion_create";
+	auto out = [&](int rc) {
+		if (err) *err = rc;
+		return (hns_point_motion*)nullptr;
+	};
+	if (capacity > kMaxPoints) return out(refuse(who, "capacity is above 2^31 - 1"));
+	if (hns_device_count() == 0) return out(fail(HNS_ERR_NO_DEVICE, "hns_point_motion_create: no HIP device (there is no CPU fallback)"));
+	int dev = -1;
+	if (hipGetDevice(&dev) != hipSuccess) return out(fail(HNS_ERR_HIP, "hns_point_motion_create: no current HIP device"));
+	hns_point_motion* o = new hns_point_motion;
+	o->device = dev, o->capacity = capacity;
+	const size_t cap = (size_t)std::max<uint64_t>(capacity, 1);
+	const int rc = carve(o->arena, dev, [&](const Slice& slice) {
+		slice(o->xyz, 12 * cap), slice(o->vel, 12 * cap), slice(o->age, 4 * cap), slice(o->status, cap), slice(o->hit, cap);
+	});
+	if (rc != HNS_OK) {
+		delete o;
+		return out(rc);
+	}
+	if (err) *err = HNS_OK;
+	return o;
+}
+
+void hns_point_motion_destroy(hns_point_motion* o) {
+	if (!o) return;
+	delete o;  // (its block goes back to the pool, which waits for the device first)
+}
+
+int hns_point_motion_set_stream(hns_point_motion* o, void* hip_stream) {
+	if (!o) return refuse("hns_point_motion_set_stream", "null point motion");
+	o->stream = (hipStream_t)hip_stream;
+	return HNS_OK;
+}
+
+int hns_point_motion_get(hns_point_motion* o, hns_point_motion_info* info) {
+	if (!o) return refuse("hns_point_motion_get", "null point motion");
+	if (!info) return refuse("hns_point_motion_get", "null info");
+	*info = hns_point_motion_info{o->capacity, o->xyz, o->vel, o->age, o->status, o->hit};
+	return HNS_OK;
+}
+
+// Reads the sim's current velocity and collision_sdf and nothing else of it: the look-ahead memo, the masks, the feedback signatures and the solve report stay as they are.
+int hns_point_motion_step(hns_point_motion* o, hns_sim* s, uint64_t n, float dt, float voxel_size, int steps, const hns_point_motion_spec* sp) {
+	const char* who = "hns_point_motion_step";
+	// the numbers and the spec, a host struct, first: they are refused whatever the objects are, a machine without a device included
+	if (!sp) return refuse(who, "the spec is null");
+	if (n > kMaxPoints) return refuse(who, "n is above 2^31 - 1");
+	if (steps < 1) return refuse(who, "steps must be at least 1");
+	if (std::isnan(dt)) return refuse(who, "dt is NaN");
+	if (!(voxel_size > 0.0f) || std::isinf(voxel_size)) return refuse(who, "voxel_size must be a positive finite number");
+	if (sp->mode < HNS_MOTION_FREE || sp->mode > HNS_MOTION_KILL) return refuse(who, "mode must be 0 (free), 1 (stick), 2 (bounce) or 3 (kill)");
+	for (int a = 0; a < 3; ++a)
+		if (!std::isfinite(sp->gravity[a])) return refuse(who, "gravity must be finite");
+	if (!std::isfinite(sp->drag) || sp->drag < 0.0f) return refuse(who, "drag must be finite and not negative");
+	if (!(sp->restitution >= 0.0f && sp->restitution <= 1.0f)) return refuse(who, "restitution must be in [0, 1]");
+	if (!(sp->friction >= 0.0f && sp->friction <= 1.0f)) return refuse(who, "friction must be in [0, 1]");
+	if (!(sp->max_age > 0.0f)) return refuse(who, "max_age must be positive (+inf: no point expires)");
+	if (!std::isfinite(sp->threshold)) return refuse(who, "threshold must be finite");
+	if (!std::isfinite(sp->skin) || sp->skin < 0.0f) return refuse(who, "skin must be finite and not negative");
+	if (sp->iterations < 1 || sp->iterations > 8) return refuse(who, "iterations must be 1 .. 8");
+	if (!o) return refuse(who, "null point motion");
+	if (n > o->capacity) {
+		set_error("%s: n %llu is above the capacity %llu", who, (unsigned long long)n, (unsigned long long)o->capacity);
+		return HNS_ERR_INVALID_ARGUMENT;
+	}
+	if (int rc = check_sim(s, who)) return rc;
+	const int f = sp->mode == HNS_MOTION_FREE ? -1 : s->find("collision_sdf");
+	if (sp->mode != HNS_MOTION_FREE && f < 0) return refuse(who, "no float field named 'collision_sdf' in this sim (mode free needs none)");
+	if (n == 0) return HNS_OK;
+	hns_grid* g = s->grid;
+	if (int rc = check_grid(g, who)) return rc;
+	if (g->device != o->device) return refuse(who, "the sim's grid and the point motion live on different HIP devices");
+	MotionDev d;
+	d.mode = sp->mode, d.iterations = sp->iterations, d.empty = g->topo.n_leaves == 0;
+	d.inv_dx = 1.0f / voxel_size;
+	d.s = dt * d.inv_dx;
+	d.k = sp->drag * dt;
+	d.r = 1.0f / (1.0f + d.k);
+	d.dt = dt;
+	d.gdx = dt * sp->gravity[0], d.gdy = dt * sp->gravity[1], d.gdz = dt * sp->gravity[2];
+	d.restitution = sp->restitution;
+	d.ft = 1.0f - sp->friction;
+	d.max_age = sp->max_age, d.threshold = sp->threshold, d.skin = sp->skin;
+	const dim3 grid((unsigned)((n + kMotionBlock - 1) / kMotionBlock)), block(kMotionBlock);
+	if (sp->mode == HNS_MOTION_FREE)
+		hipLaunchKernelGGL(k_move_points<false>, grid, block, 0, o->stream, g->dev(), (const float*)s->vel, (const float*)nullptr, o->xyz, o->vel, o->age, (unsigned)n, steps, d,
+		                   o->status, o->hit);
+	else
+		hipLaunchKernelGGL(k_move_points<true>, grid, block, 0, o->stream, g->dev(), (const float*)s->vel, (const float*)s->cur[(size_t)f], o->xyz, o->vel, o->age, (unsigned)n,
+		                   steps, d, o->status, o->hit);
+	return launch_status(who);
+}
+
+}  // extern "C"

@@ -256,11 +256,13 @@ SPLAT_ROWS = {"original": 0, "ranked": 1}  # the per-point arrays of an ordered 
 
 
 class _DeviceWords:
-    """`n` 32-bit words of device memory at `ptr` for ``torch.as_tensor``: a view, no copy; `owner` is kept alive with it"""
+    """`n` 32-bit words of device memory at `ptr` for ``torch.as_tensor``: a view, no copy; `owner` is kept alive with it. shape, typestr: another shape and element
+    type ("<f4", "|u1") over the same memory"""
 
-    def __init__(self, ptr: int, n: int, owner):
+    def __init__(self, ptr: int, n: int, owner, shape=None, typestr: str = "<i4"):
         self.owner = owner
-        self.__cuda_array_interface__ = {"shape": (int(n),), "typestr": "<i4", "data": (int(ptr), False), "strides": None, "version": 2}
+        self.__cuda_array_interface__ = {"shape": tuple(shape) if shape is not None else (int(n),), "typestr": typestr, "data": (int(ptr), False), "strides": None,
+                                         "version": 2}
 
 
 class PointOrder:
@@ -555,6 +557,105 @@ class PointPopulation:
         if self._ptr:
             lib.hns_point_population_destroy(self._ptr)
             self._ptr = 0
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+MOTION_MODES = {"free": _lib.HNS_MOTION_FREE, "stick": _lib.HNS_MOTION_STICK, "bounce": _lib.HNS_MOTION_BOUNCE, "kill": _lib.HNS_MOTION_KILL}
+MOTION_HIT = {"bounced": 1, "reverted": 2, "killed": 4, "started_inside": 8, "reflected": 16}  # the bits of PointMotion.hit
+
+
+class PointMotion:
+    """Points with a velocity of their own on the device (``hns_point_motion``; include/hns.h states the arithmetic line by line): embers, sparks, soot, debris. The object
+    OWNS the per-point state -- ``xyz`` [capacity, 3] (index space), ``vel`` [capacity, 3] (the units of the sim's velocity), ``age``, ``status`` and ``hit`` [capacity] --
+    in one block of the pool of device memory; the attributes are torch views of the library's arrays, valid until ``close``: fill xyz, vel and age through them.
+    ``step`` drags every point towards a sim's gas, lets it fall, moves it, and answers a step that lands in the sim's "collision_sdf" by `mode`. Bound to no grid: a
+    step uses the grid the sim has at that call, so the object survives regrids. A row with a non-finite xyz (``PointPopulation``'s rows beyond the live count) is not
+    stepped."""
+
+    def __init__(self, capacity: int):
+        capacity = int(capacity)
+        if capacity < 0:
+            raise ValueError(f"PointMotion: capacity {capacity} is negative")
+        self.capacity, self._ptr = capacity, 0
+        err = C.c_int(0)
+        self._ptr = lib.hns_point_motion_create(capacity, C.byref(err))
+        if not self._ptr:
+            _raise(err.value if err.value < 0 else _lib.HNS_ERR_RUNTIME)
+
+    def _live(self) -> int:
+        if not self._ptr:
+            raise RuntimeError("PointMotion: the object is closed")
+        return self._ptr
+
+    def _view(self, which: str, shape, typestr: str):
+        info = _lib.hns_point_motion_info()
+        _raise(lib.hns_point_motion_get(self._live(), C.byref(info)))
+        torch = _torch()
+        if self.capacity == 0:
+            return torch.empty(shape, dtype=torch.float32 if typestr == "<f4" else torch.uint8, device="cuda")
+        return torch.as_tensor(_DeviceWords(getattr(info, which), 0, self, shape, typestr), device="cuda")
+
+    @property
+    def xyz(self):
+        """positions, [capacity, 3] float32 in index space -- a view of the object's array, valid until ``close``; no wait"""
+        return self._view("xyz", (self.capacity, 3), "<f4")
+
+    @property
+    def vel(self):
+        """the points' own velocities, [capacity, 3] float32 in the units of the sim's velocity -- a view, valid until ``close``; no wait"""
+        return self._view("vel", (self.capacity, 3), "<f4")
+
+    @property
+    def age(self):
+        """[capacity] float32 -- a view, valid until ``close``; no wait"""
+        return self._view("age", (self.capacity,), "<f4")
+
+    @property
+    def status(self):
+        """[capacity] uint8, what the last ``step`` left: 1 alive, finite, inside a leaf and younger than max_age -- a view, valid until ``close``; no wait"""
+        return self._view("status", (self.capacity,), "|u1")
+
+    @property
+    def hit(self):
+        """[capacity] uint8, what the last ``step`` left: MOTION_HIT's bits ORed over its steps -- a view, valid until ``close``; no wait"""
+        return self._view("hit", (self.capacity,), "|u1")
+
+    def step(self, sim, n: int, dt: float, voxel_size: float, steps: int = 1, mode: str = "bounce", gravity=(0.0, 0.0, 0.0), drag: float = 0.0, restitution: float = 0.5,
+             friction: float = 0.0, max_age: float = float("inf"), threshold: float = 0.0, skin: float = 1 / 16, iterations: int = 3, stream: Optional[int] = None):
+        """`steps` steps of rows 0 .. n - 1 in one launch (``hns_point_motion_step``): v = (v + drag*dt*U(x)) / (1 + drag*dt) (implicit Euler towards the gas's velocity
+        U), v += dt*gravity, x += (dt / voxel_size)*v, age += dt; then, unless mode is "free", a step that ends where the SDF's sample is below `threshold` puts the point
+        back with zero velocity ("stick"), reflects the velocity about the SDF's normal -- `restitution` of the normal speed back, `friction` of the tangential velocity
+        lost -- and pushes the point out as ``trace_points_collide`` does, up to `iterations` times ("bounce"), or marks it dead ("kill"). Afterwards ``status`` is 1 where
+        the point is alive, finite, inside a leaf and younger than `max_age` -- ``PointPopulation.select(motion.status, 1)`` drops the rest -- and ``hit`` ORs MOTION_HIT.
+        The sim is only read. stream: a hipStream_t as an integer, None = torch's current stream; the step is asynchronous on it. Returns self."""
+        ptr = self._live()
+        if mode not in MOTION_MODES:
+            raise ValueError(f"PointMotion.step: mode must be one of {sorted(MOTION_MODES)}, not {mode!r}")
+        g = tuple(float(c) for c in gravity)
+        if len(g) != 3:
+            raise ValueError("PointMotion.step: gravity has three components")
+        spec = _lib.hns_point_motion_spec(MOTION_MODES[mode], (C.c_float * 3)(*g), float(drag), float(restitution), float(friction), float(max_age), float(threshold),
+                                          float(skin), int(iterations))
+        _raise(lib.hns_point_motion_set_stream(ptr, current_stream() if stream is None else int(stream)))
+        _raise(lib.hns_point_motion_step(ptr, sim._ptr, int(n), float(dt), float(voxel_size), int(steps), C.byref(spec)))
+        return self
+
+    def close(self) -> None:
+        """the block goes back to the pool (which waits for the device first); the views must not be used afterwards"""
+        if self._ptr:
+            lib.hns_point_motion_destroy(self._ptr)
+            self._ptr = 0
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
     def __del__(self):
         try:
@@ -921,6 +1022,10 @@ class Sim:
         """A ``PointPopulation`` for up to `capacity` points on the sim's CURRENT grid. After a ``regrid`` the sim is on another grid and the object refuses every call
         (RuntimeError): make a new one."""
         return PointPopulation(self.grid, capacity, _sim=self)
+
+    def point_motion(self, capacity: int) -> PointMotion:
+        """A ``PointMotion`` of `capacity` rows. It is bound to no grid: ``motion.step(sim, ...)`` reads the grid the sim has at that call, after a ``regrid`` too."""
+        return PointMotion(capacity)
 
     def birth(self, population: PointPopulation, name: str, xyz, voxel=None, *, threshold: float, rate: float, max_per_voxel: int, seed: int, append: bool = False,
               fill: bool = True, use_masks: bool = True, stream: Optional[int] = None):

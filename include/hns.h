@@ -643,6 +643,84 @@ int hns_dev_trace_points_collide(hns_grid*, const float* vel3, const float* sdf,
  * "collision_sdf", a voxel_size that is not a positive finite number, a sim lent to a grid's cook cache. Not mirrored in hns_dist_*. */
 int hns_sim_trace_points_collide(hns_sim*, float* xyz, uint64_t n, float dt, float voxel_size, int order, int steps,
                                  const hns_point_collision*, unsigned char* status, unsigned char* hit, void* stream);
+/* POINTS WITH A VELOCITY OF THEIR OWN: embers, sparks, soot, debris. Where the traces above move a massless tracer (x' = U(x)), a point here carries a velocity and an
+ * age: it is dragged towards the gas, falls, moves with its own velocity, and a step that lands in the collider sticks, bounces or kills it. hns_point_motion is an
+ * object that OWNS the per-point arrays and hands device pointers out, as hns_point_order_get does; it reads the fluid from a hns_sim. No call here takes a caller's
+ * data pointer: the arrays are carved from the library's pool and have the pool's alignment.
+ *   Object   create draws ONE block of the pool of device memory on the current HIP device and carves five disjoint arrays of `capacity` rows from it: xyz (12 bytes a
+ *            row), vel (12), age (4), status (1), hit (1); destroy returns the block. The object is bound to no grid: step uses the grid the sim has at that call, so the
+ *            object survives regrids. hns_point_motion_get fills the info with the DEVICE pointers; it waits for nothing, and the pointers are valid until destroy. The
+ *            caller fills xyz, vel and age through them (hns_point_population_birth may write xyz directly, hns_point_order_sort may read it). Before the first step
+ *            status and hit hold whatever the pool held; nothing reads them. step allocates nothing and is asynchronous on the object's stream: the null stream until
+ *            hns_point_motion_set_stream binds another.
+ *   Units    positions are in index space (as for hns_dev_sample_points); vel is in the units of the sim's velocity.
+ * The arithmetic of hns_point_motion_step. Every line below is one rounded float32 operation per component, none contracted.
+ *   Host constants, formed in float32 on the host once per call: inv_dx = 1.0f / voxel_size; s = dt * inv_dx; k = drag * dt; r = 1.0f / (1.0f + k);
+ *            gd.c = dt * gravity.c; ft = 1.0f - friction.
+ *   Samplers U is the Vec3f sample of the sim's current velocity and S the float sample of its float field "collision_sdf": exactly the samplers of
+ *            hns_dev_trace_points_collide. S is not evaluated at all in mode FREE.
+ *   Rows     only rows 0 .. n - 1 are read or written.
+ *   Skip     a row with a non-finite component of xyz is not stepped: its xyz, vel and age keep every bit, its status is 0 and its hit is 0 (the convention of
+ *            hns_point_population_birth for the rows beyond the live count).
+ *   Start    bit 3 (value 8) of hit is set iff S(x_start) < threshold; it is never set in mode FREE.
+ *   Step     `steps` times, for a row that is not dead:
+ *              1. x0 = x; u = U(x0).
+ *              2. drag, implicit Euler: t.c = k * u.c; t.c = v.c + t.c; v.c = t.c * r.
+ *              3. gravity: v.c = v.c + gd.c.
+ *              4. move: m.c = s * v.c; x1.c = x0.c + m.c.
+ *              5. age = age + dt.
+ *              6. in mode FREE, x = x1 and the step ends here.
+ *              7. otherwise d = S(x1). If !(d < threshold), a NaN included, then x = x1. Else the mode decides:
+ *   STICK    x = x0; v = +0.0f in every component; hit |= 2.
+ *   KILL     x = x1; the row is dead and takes no further step; hit |= 4.
+ *   BOUNCE   hit |= 1; then up to `iterations` times while d < threshold:
+ *              nb and n exactly as PUSH of hns_dev_trace_points_collide takes them: six samples at x1 -+ e_axis in the order -x, +x, -y, +y, -z, +z, and the normalised
+ *                   central difference of hns_dev_enforce_collision_boundaries; n = 0 when len <= 1e-6f;
+ *              on the first iteration only, reflect the velocity: vn = (v.x*n.x + v.y*n.y) + v.z*n.z; if vn < 0: w.c = vn * n.c; vt.c = v.c - w.c; a = restitution * vn;
+ *                   p.c = ft * vt.c; q.c = a * n.c; v.c = p.c - q.c; hit |= 16;
+ *              then PUSH's move: a = (threshold - d) * inv_dx; a = a + skin; x1.c = x1.c + a * n.c (a multiply, then an add); d = S(x1).
+ *            After the loop: if still d < threshold, x = x0 and hit |= 2 -- the reflected velocity stays --; otherwise x = x1.
+ *   Outputs  status is 1 iff the row is not dead, x is finite in all three components, the leaf of its cell exists, and age < max_age (a NaN age gives 0); hit is the
+ *            OR of the bits above over all steps. hns_point_population_select(status, at_least = 1) therefore drops the dead, the escaped and the expired. x, v and age
+ *            are written once, after the last step.
+ *   No leaves  on a grid with no leaves U = 0 and S = 0, and no leaf exists: rows still fall under gravity, and every status is 0.
+ * Refused before anything is launched and with nothing touched (HNS_ERR_INVALID_ARGUMENT, the call and the argument in the message) -- the numbers and the spec, a host
+ * struct, first and whatever n, then the objects --: a null spec, n above 2^31 - 1, steps < 1, a NaN dt, a voxel_size that is not a positive finite number, a mode
+ * outside 0 .. 3, a non-finite gravity component, a drag that is NaN, infinite or negative, a restitution or friction outside [0, 1] or NaN, a max_age that is NaN or
+ * <= 0 (+inf is allowed: no point expires), a threshold that is not finite, a skin that is NaN, infinite or negative, iterations outside 1 .. 8 (read by BOUNCE only but
+ * checked in every mode); a null object, n > capacity, a null sim (HNS_ERR_NO_DEVICE where there is no device), a sim lent to a grid's cook cache, a mode other than
+ * FREE on a sim without a float field "collision_sdf"; create: a capacity above 2^31 - 1, and HNS_ERR_NO_DEVICE without a HIP device; get: a null object or info.
+ * n == 0 launches nothing. The sim is only read: the look-ahead memo, the active masks, the feedback signatures and the solve report stay as they are. Not mirrored in
+ * hns_dist_*, and there is no host mirror: the Python tests restate the text above in numpy. */
+typedef struct hns_point_motion hns_point_motion;
+hns_point_motion* hns_point_motion_create(uint64_t capacity, int* err);
+void hns_point_motion_destroy(hns_point_motion*);
+int hns_point_motion_set_stream(hns_point_motion*, void* hip_stream);
+typedef struct hns_point_motion_info {
+	uint64_t capacity;
+	float* xyz;            /* DEVICE pointers handed out: capacity x 3 floats */
+	float* vel;            /* capacity x 3 floats */
+	float* age;            /* capacity floats */
+	unsigned char* status; /* capacity bytes */
+	unsigned char* hit;    /* capacity bytes */
+} hns_point_motion_info;
+int hns_point_motion_get(hns_point_motion*, hns_point_motion_info*);
+#define HNS_MOTION_FREE 0 /* no collider looked at; the sim needs no collision_sdf */
+#define HNS_MOTION_STICK 1
+#define HNS_MOTION_BOUNCE 2
+#define HNS_MOTION_KILL 3
+typedef struct hns_point_motion_spec {
+	int mode;         /* HNS_MOTION_*: 0 .. 3 */
+	float gravity[3]; /* finite; units of the sim's velocity per unit of time */
+	float drag;       /* finite, >= 0; 1 / the time in which a point takes up the gas's velocity */
+	float restitution; /* 0 .. 1: the share of the normal speed a bounce gives back */
+	float friction;   /* 0 .. 1: the share of the tangential velocity a bounce takes */
+	float max_age;    /* > 0, +inf allowed: status is 0 from this age on */
+	float threshold;  /* finite; a position is in collision iff S(x) < threshold */
+	float skin;       /* finite, >= 0; index-space distance added to every push */
+	int iterations;   /* 1 .. 8 pushes per bounced step */
+} hns_point_motion_spec;
+int hns_point_motion_step(hns_point_motion*, hns_sim*, uint64_t n, float dt, float voxel_size, int steps, const hns_point_motion_spec*);
 /* Point values into fields: the transpose of hns_dev_sample_points -- every point adds w * v to the eight voxels of its cell -- with an accumulation that does not depend on
  * the order the adds retire in. fields[i]: device pointer, ncomp[i] 1 (float) or 3 (Vec3f AoS), added into IN PLACE; values[i]: device, n x ncomp[i] floats, the value of
  * each point for field i; fields, ncomp and values are HOST arrays of n_fields (1 .. 8) entries; xyz as for hns_dev_sample_points.
