@@ -1,20 +1,16 @@
 // hns_point_motion.hip -- points with a velocity of their own: an object that owns the per-point state (position, velocity, age, status, hit; one block of the pool) and
 // the kernel that steps it through a sim's fluid: drag towards the gas (implicit Euler), gravity, the move, and the collision SDF's answer to a step that lands in the
-// collider -- stick, bounce (reflect the velocity about the SDF's normal, then the collision trace's push) or kill. The samplers, the leaf cursor and the normal are those of
-// hns_points.hpp and hns_device.hpp, as k_trace_points_collide (hns_points_collide.hip) uses them; include/hns.h states the arithmetic line by line. One thread per point,
-// no LDS, no atomics. -ffp-contract=off.
-#include "hns_points.hpp"
-
-#include <cmath>
+// collider -- stick, bounce (reflect the velocity about the SDF's normal, then the collision trace's push) or kill. The samplers and the leaf cursor are those of
+// hns_points.hpp; the push (push_out, which hands the reflection its normal), the status rule and the hit bits those of hns_pointstep.hpp, as k_trace_points_collide
+// (hns_points_collide.hip) uses them; include/hns.h states the arithmetic line by line. One thread per point, no LDS, no atomics. -ffp-contract=off.
+#include "hns_pointstep.hpp"
 
 using namespace hns;
 
 namespace {
 
-constexpr int kMotionBlock = 256;
-
-// what hit holds (include/hns.h)
-constexpr unsigned kHitBounced = 1, kHitReverted = 2, kHitKilled = 4, kHitStartInside = 8, kHitReflected = 16;
+// what hit holds beside the bits of hns_pointstep.hpp (include/hns.h)
+constexpr unsigned kHitBounced = kHitPushed, kHitReflected = 16;
 
 // the host's constants of one call (include/hns.h: "Host constants"), by value: wave-uniform, so the branches on mode and empty cost no divergence
 struct MotionDev {
@@ -24,12 +20,12 @@ struct MotionDev {
 };
 
 // `steps` steps of a point. COLLIDE = false is mode FREE: S is not in the kernel at all. The bounce holds one float sample at a time (the rolled sampler body of
-// k_trace_points_collide); x, v and age are written once, behind the last step. A killed point leaves the loop.
+// push_out); x, v and age are written once, behind the last step. A killed point leaves the loop.
 template <bool COLLIDE>
-__global__ __launch_bounds__(kMotionBlock) void k_move_points(const GridDev g, const float* __restrict__ u, const float* __restrict__ sdf, float* __restrict__ xyz,
+__global__ __launch_bounds__(kPointBlock) void k_move_points(const GridDev g, const float* __restrict__ u, const float* __restrict__ sdf, float* __restrict__ xyz,
                                                                float* __restrict__ vel, float* __restrict__ age, const unsigned n, const int steps, const MotionDev c,
                                                                unsigned char* __restrict__ status, unsigned char* __restrict__ hit) {
-	const unsigned p = blockIdx.x * (unsigned)kMotionBlock + threadIdx.x;
+	const unsigned p = blockIdx.x * (unsigned)kPointBlock + threadIdx.x;
 	if (p >= n) return;
 	f3 x = ld3(xyz, (int)p);
 	if (!(finite_f(x.x) && finite_f(x.y) && finite_f(x.z))) {  // a row that holds no point (PointPopulation's rows beyond the live count): every bit stays
@@ -69,35 +65,18 @@ __global__ __launch_bounds__(kMotionBlock) void k_move_points(const GridDev g, c
 					x1 = x;
 				} else {
 					flags |= kHitBounced;
-#pragma unroll 1
-					for (int it = 0; it < c.iterations && d < c.threshold; ++it) {
-						float nb[6] = {};
-#pragma unroll 1
-						for (int q = 0; q < 6; ++q) {  // -x, +x, -y, +y, -z, +z: ONE sampler body in the code, one sample's taps in flight (x + -1.0f is x - 1.0f)
-							const float off = (q & 1) ? 1.0f : -1.0f;
-							const int axis = q >> 1;
-							const float val = S(axis == 0 ? x1.x + off : x1.x, axis == 1 ? x1.y + off : x1.y, axis == 2 ? x1.z + off : x1.z);
-#pragma unroll
-							for (int e = 0; e < 6; ++e) nb[e] = q == e ? val : nb[e];  // (selects: nb stays in registers)
+					push_out(S, x1, d, c.threshold, c.skin, c.inv_dx, c.iterations, [&](const f3& nrm) {  // reflect the velocity, once a step
+						const float vn = (v.x * nrm.x + v.y * nrm.y) + v.z * nrm.z;
+						if (vn < 0.0f) {
+							const f3 wn = {vn * nrm.x, vn * nrm.y, vn * nrm.z};
+							const f3 vt = {v.x - wn.x, v.y - wn.y, v.z - wn.z};
+							const float b = c.restitution * vn;
+							const f3 pt = {c.ft * vt.x, c.ft * vt.y, c.ft * vt.z};
+							const f3 qn = {b * nrm.x, b * nrm.y, b * nrm.z};
+							v = f3{pt.x - qn.x, pt.y - qn.y, pt.z - qn.z};
+							flags |= kHitReflected;
 						}
-						const f3 nrm = sdf_normal_of(nb, c.inv_dx);
-						if (it == 0) {  // reflect the velocity, once a step
-							const float vn = (v.x * nrm.x + v.y * nrm.y) + v.z * nrm.z;
-							if (vn < 0.0f) {
-								const f3 wn = {vn * nrm.x, vn * nrm.y, vn * nrm.z};
-								const f3 vt = {v.x - wn.x, v.y - wn.y, v.z - wn.z};
-								const float b = c.restitution * vn;
-								const f3 pt = {c.ft * vt.x, c.ft * vt.y, c.ft * vt.z};
-								const f3 qn = {b * nrm.x, b * nrm.y, b * nrm.z};
-								v = f3{pt.x - qn.x, pt.y - qn.y, pt.z - qn.z};
-								flags |= kHitReflected;
-							}
-						}
-						float b = (c.threshold - d) * c.inv_dx;
-						b = b + c.skin;
-						x1 = f3{x1.x + b * nrm.x, x1.y + b * nrm.y, x1.z + b * nrm.z};
-						d = S(x1.x, x1.y, x1.z);
-					}
+					});
 					if (d < c.threshold) {  // a push that did not get out: the reflected velocity stays
 						flags |= kHitReverted;
 						x1 = x;
@@ -111,14 +90,7 @@ __global__ __launch_bounds__(kMotionBlock) void k_move_points(const GridDev g, c
 	st3(vel, (int)p, v);
 	age[p] = a;
 	hit[p] = (unsigned char)flags;
-	bool in = !dead && finite_f(x.x) && finite_f(x.y) && finite_f(x.z) && a < c.max_age && !c.empty;
-	if (in) {
-		int L[8];
-		const int i = __float2int_rd(x.x), j = __float2int_rd(x.y), k = __float2int_rd(x.z);
-		cell_leaves<true>(g, cur, i & ~7, j & ~7, k & ~7, L);  // (the leaf's own corner: one lookup)
-		in = L[0] >= 0;
-	}
-	status[p] = in ? 1 : 0;
+	status[p] = in_a_leaf<true>(g, cur, x, !dead && a < c.max_age && !c.empty) ? 1 : 0;
 }
 
 }  // namespace
@@ -185,7 +157,8 @@ int hns_point_motion_step(hns_point_motion* o, hns_sim* s, uint64_t n, float dt,
 	if (n > kMaxPoints) return refuse(who, "n is above 2^31 - 1");
 	if (steps < 1) return refuse(who, "steps must be at least 1");
 	if (std::isnan(dt)) return refuse(who, "dt is NaN");
-	if (!(voxel_size > 0.0f) || std::isinf(voxel_size)) return refuse(who, "voxel_size must be a positive finite number");
+	float inv_dx;
+	if (int rc = inv_voxel_size(who, voxel_size, &inv_dx)) return rc;
 	if (sp->mode < HNS_MOTION_FREE || sp->mode > HNS_MOTION_KILL) return refuse(who, "mode must be 0 (free), 1 (stick), 2 (bounce) or 3 (kill)");
 	for (int a = 0; a < 3; ++a)
 		if (!std::isfinite(sp->gravity[a])) return refuse(who, "gravity must be finite");
@@ -193,9 +166,7 @@ int hns_point_motion_step(hns_point_motion* o, hns_sim* s, uint64_t n, float dt,
 	if (!(sp->restitution >= 0.0f && sp->restitution <= 1.0f)) return refuse(who, "restitution must be in [0, 1]");
 	if (!(sp->friction >= 0.0f && sp->friction <= 1.0f)) return refuse(who, "friction must be in [0, 1]");
 	if (!(sp->max_age > 0.0f)) return refuse(who, "max_age must be positive (+inf: no point expires)");
-	if (!std::isfinite(sp->threshold)) return refuse(who, "threshold must be finite");
-	if (!std::isfinite(sp->skin) || sp->skin < 0.0f) return refuse(who, "skin must be finite and not negative");
-	if (sp->iterations < 1 || sp->iterations > 8) return refuse(who, "iterations must be 1 .. 8");
+	if (int rc = check_push_numbers(who, sp->threshold, sp->skin, sp->iterations)) return rc;
 	if (!o) return refuse(who, "null point motion");
 	if (n > o->capacity) {
 		set_error("%s: n %llu is above the capacity %llu", who, (unsigned long long)n, (unsigned long long)o->capacity);
@@ -210,7 +181,7 @@ int hns_point_motion_step(hns_point_motion* o, hns_sim* s, uint64_t n, float dt,
 	if (g->device != o->device) return refuse(who, "the sim's grid and the point motion live on different HIP devices");
 	MotionDev d;
 	d.mode = sp->mode, d.iterations = sp->iterations, d.empty = g->topo.n_leaves == 0;
-	d.inv_dx = 1.0f / voxel_size;
+	d.inv_dx = inv_dx;
 	d.s = dt * d.inv_dx;
 	d.k = sp->drag * dt;
 	d.r = 1.0f / (1.0f + d.k);
@@ -219,7 +190,7 @@ int hns_point_motion_step(hns_point_motion* o, hns_sim* s, uint64_t n, float dt,
 	d.restitution = sp->restitution;
 	d.ft = 1.0f - sp->friction;
 	d.max_age = sp->max_age, d.threshold = sp->threshold, d.skin = sp->skin;
-	const dim3 grid((unsigned)((n + kMotionBlock - 1) / kMotionBlock)), block(kMotionBlock);
+	const dim3 grid = point_blocks(n), block(kPointBlock);
 	if (sp->mode == HNS_MOTION_FREE)
 		hipLaunchKernelGGL(k_move_points<false>, grid, block, 0, o->stream, g->dev(), (const float*)s->vel, (const float*)nullptr, o->xyz, o->vel, o->age, (unsigned)n, steps, d,
 		                   o->status, o->hit);

@@ -2,16 +2,14 @@
 // IndexSampler<Vec3f,1> (src/Utils/Stencils.hpp:96-173) behind its Floor (Stencils.hpp:25-43), at positions that are no voxel centres. One thread per point, plain
 // 64-bit addressed loads (a point's taps may lie anywhere: the leaf-sized buffer descriptors of hns_advect.hip do not apply), no LDS. Positions are INDEX-SPACE
 // float triples, AoS n x 3, as the samplers and the advection kernels' back-traced `pos` have them. Arithmetic keeps the reference's association; -ffp-contract=off.
-#include "hns_points.hpp"
-
-#include <cmath>
+// The trace's RK step, its status rule, the block size and the refusals of its numbers: hns_pointstep.hpp, shared with hns_points_collide.hip and hns_point_motion.hip.
+#include "hns_pointstep.hpp"
 
 using namespace hns;
 
 namespace {
 
 constexpr int kMaxPointFields = 8;  // fields that share one launch of k_sample_points
-constexpr int kPointBlock = 256;
 
 struct PointFields {
 	const float* in[kMaxPointFields];
@@ -41,9 +39,9 @@ __global__ __launch_bounds__(kPointBlock) void k_sample_points(const GridDev g, 
 	}
 }
 
-// `steps` steps of a point through the velocity u in registers, x' = x + s U(x) with U the Vec3f sampler above and s = dt / dx (negative: a back-trace); ORDER 1 forward
-// Euler, 2 the midpoint rule, 4 the classical Runge-Kutta step. Every a + c*b is a multiply, then an add. A point with no leaf under any tap samples U = 0 and
-// stays where it is. status (or null): 1 iff the final position is finite in all three components and the leaf of its cell exists.
+// `steps` steps of a point through the velocity u in registers, x' = x + s U(x) with U the Vec3f sampler above and s = dt / dx (negative: a back-trace), each step
+// rk_step<ORDER>. A point with no leaf under any tap samples U = 0 and stays where it is. status (or null): 1 iff the final position is finite in all three components
+// and the leaf of its cell exists.
 template <int ORDER, bool CURSOR>
 __global__ __launch_bounds__(kPointBlock) __attribute__((amdgpu_waves_per_eu(7, 8))) void k_trace_points(const GridDev g, const float* __restrict__ u, float* __restrict__ xyz, const unsigned n, const float s,
                                                               const int steps, unsigned char* __restrict__ status) {
@@ -53,34 +51,9 @@ __global__ __launch_bounds__(kPointBlock) __attribute__((amdgpu_waves_per_eu(7, 
 	const float h = 0.5f * s, s6 = s * 0.16666667f;
 	Cursor cur{-1, 0, 0, 0};
 	auto U = [&](float a, float b, float c) { return sample_v(u, point_cell<CURSOR>(g, cur, a, b, c)); };
-	for (int step = 0; step < steps; ++step) {
-		const f3 k1 = U(x.x, x.y, x.z);
-		if (ORDER == 1) {
-			x = f3{x.x + s * k1.x, x.y + s * k1.y, x.z + s * k1.z};
-		} else if (ORDER == 2) {
-			const f3 k2 = U(x.x + h * k1.x, x.y + h * k1.y, x.z + h * k1.z);
-			x = f3{x.x + s * k2.x, x.y + s * k2.y, x.z + s * k2.z};
-		} else {
-			const f3 k2 = U(x.x + h * k1.x, x.y + h * k1.y, x.z + h * k1.z);
-			f3 sum = {k1.x + 2.0f * k2.x, k1.y + 2.0f * k2.y, k1.z + 2.0f * k2.z};
-			const f3 k3 = U(x.x + h * k2.x, x.y + h * k2.y, x.z + h * k2.z);
-			sum = f3{sum.x + 2.0f * k3.x, sum.y + 2.0f * k3.y, sum.z + 2.0f * k3.z};
-			const f3 k4 = U(x.x + s * k3.x, x.y + s * k3.y, x.z + s * k3.z);
-			sum = f3{sum.x + k4.x, sum.y + k4.y, sum.z + k4.z};
-			x = f3{x.x + s6 * sum.x, x.y + s6 * sum.y, x.z + s6 * sum.z};
-		}
-	}
+	for (int step = 0; step < steps; ++step) x = rk_step<ORDER>(U, x, s, h, s6);
 	st3(xyz, (int)p, x);
-	if (status) {
-		int L[8];
-		const int i = __float2int_rd(x.x), j = __float2int_rd(x.y), k = __float2int_rd(x.z);
-		bool in = finite_f(x.x) && finite_f(x.y) && finite_f(x.z);
-		if (in) {
-			cell_leaves<CURSOR>(g, cur, i & ~7, j & ~7, k & ~7, L);  // (the leaf's own corner: one lookup)
-			in = L[0] >= 0;
-		}
-		status[p] = in ? 1 : 0;
-	}
+	if (status) status[p] = in_a_leaf<CURSOR>(g, cur, x, true) ? 1 : 0;
 }
 
 // ---- launchers ---------------------------------------------------------------------------------------------------------------------------------------------------------
@@ -140,13 +113,7 @@ int sample_points(const char* who, hns_grid* g, const float* const* fields, cons
 int trace_points(const char* who, const char* dx_name, hns_grid* g, const float* vel3, float* xyz, uint64_t n, float dt, float inv_dx, int order, int steps,
                  unsigned char* status, void* stream) {
 	if (int rc = check_grid(g, who)) return rc;
-	if (order != 1 && order != 2 && order != 4) return refuse(who, "order must be 1, 2 or 4");
-	if (steps < 1) return refuse(who, "steps must be at least 1");
-	if (std::isnan(dt)) return refuse(who, "dt is NaN");
-	if (!(inv_dx > 0.0f) || std::isinf(inv_dx)) {
-		set_error("%s: %s must be a positive finite number", who, dx_name);
-		return HNS_ERR_INVALID_ARGUMENT;
-	}
+	if (int rc = check_step_numbers(who, dx_name, order, steps, dt, inv_dx)) return rc;
 	if (n > kMaxPoints) return refuse(who, "n is above 2^31 - 1");
 	if (n == 0) return HNS_OK;  // (as above)
 	if (!xyz) return refuse(who, "xyz is null");
@@ -158,15 +125,12 @@ int trace_points(const char* who, const char* dx_name, hns_grid* g, const float*
 		return HNS_OK;
 	}
 	const float s = dt * inv_dx;
-	const dim3 grid((unsigned)((n + kPointBlock - 1) / kPointBlock)), block(kPointBlock);
 	// The leaf cursor (cell_leaves) stays on: at 256^3 it takes 0.61-0.70 of the hash form's time on points in leaf order at order 4 and 1.08 on randomly permuted ones
 	// (profiles/points_ab.txt; the hash form is profiles/micro/exp/points_hash_form.patch). The same words either way.
 	constexpr bool cursor = true;
-	switch (order) {
-	case 1: hipLaunchKernelGGL((k_trace_points<1, cursor>), grid, block, 0, (hipStream_t)stream, g->dev(), vel3, xyz, (unsigned)n, s, steps, status); break;
-	case 2: hipLaunchKernelGGL((k_trace_points<2, cursor>), grid, block, 0, (hipStream_t)stream, g->dev(), vel3, xyz, (unsigned)n, s, steps, status); break;
-	default: hipLaunchKernelGGL((k_trace_points<4, cursor>), grid, block, 0, (hipStream_t)stream, g->dev(), vel3, xyz, (unsigned)n, s, steps, status); break;
-	}
+	with_order(order, [&](auto o) {
+		hipLaunchKernelGGL((k_trace_points<decltype(o)::value, cursor>), point_blocks(n), dim3(kPointBlock), 0, (hipStream_t)stream, g->dev(), vel3, xyz, (unsigned)n, s, steps, status);
+	});
 	return launch_status(who);
 }
 
@@ -213,8 +177,9 @@ int hns_sim_sample_points(hns_sim* s, const char* const* names, int n_names, int
 int hns_sim_trace_points(hns_sim* s, float* xyz, uint64_t n, float dt, float voxel_size, int order, int steps, unsigned char* status, void* stream) {
 	const char* who = "hns_sim_trace_points";
 	if (int rc = check_sim(s, who)) return rc;
-	if (!(voxel_size > 0.0f) || std::isinf(voxel_size)) return refuse(who, "voxel_size must be a positive finite number");
-	return trace_points(who, "1 / voxel_size", s->grid, s->vel, xyz, n, dt, 1.0f / voxel_size, order, steps, status, stream);
+	float inv_dx;
+	if (int rc = inv_voxel_size(who, voxel_size, &inv_dx)) return rc;
+	return trace_points(who, "1 / voxel_size", s->grid, s->vel, xyz, n, dt, inv_dx, order, steps, status, stream);
 }
 
 }  // extern "C"

@@ -1,7 +1,7 @@
 """TEST HELPER of tests/test_point_motion_cases.py (CPU) and tests/test_point_motion_gpu.py: the inputs that points with a velocity of their own are stepped on, and the
 mirror of k_move_points (hns_point_motion.hip) restated from the text of include/hns.h alone: numpy float32, one rounded operation per line, with S(x) the oracle's
-sample_trilinear_f, U(x) its sample_trilinear_v on the fmaf branch of the Vec3f lerp, the cell and leaf rules of points_cases and the normal of
-points_collide_cases.normal. Nothing here calls the library under test: the mirror is the oracle of every comparison, and the classes the conditions count are its own.
+sample_trilinear_f, U(x) its sample_trilinear_v on the fmaf branch of the Vec3f lerp, the cell and leaf rules of points_cases and the push of
+points_collide_cases.push_out. Nothing here calls the library under test: the mirror is the oracle of every comparison, and the classes the conditions count are its own.
 
 Inputs per grid of points_cases.GRIDS: the grid's velocity and its 4,099 points (points_cases.case), the lattice SDF (points_collide_cases.sdf_of), point velocities
 3 * standard_normal and ages uniform(0, 1) from default_rng([7, GRIDS.index(name)])."""
@@ -102,46 +102,31 @@ def motion_mirror(G, vel, sdf, xyz, v, age, dt, inv_dx, steps, mode, spec):
                 else:
                     hit[act[coll]] |= HIT_BOUNCED
                     cls["bounced"][act[coll]] += 1
-                    for it in range(iterations):
-                        idx = np.flatnonzero(coll & (d < thr))
-                        if not len(idx):
-                            break
-                        p, nb = x1[idx], []
-                        for axis in range(3):
-                            for sign in (-1, 1):
-                                q = p.copy()
-                                q[:, axis] = p[:, axis] - one if sign < 0 else p[:, axis] + one
-                                nb.append(S(q))
-                        nrm = cc.normal(nb, inv)
-                        if it == 0:  # reflect the velocity
-                            vv = v1[idx]
-                            vn = vv[:, 0] * nrm[:, 0]
-                            t2 = vv[:, 1] * nrm[:, 1]
-                            vn = vn + t2
-                            t2 = vv[:, 2] * nrm[:, 2]
-                            vn = vn + t2
-                            neg = vn < F(0.0)
-                            w = vn[:, None] * nrm
-                            vt = vv - w
-                            a = rest * vn
-                            pt = ft * vt
-                            qn = a[:, None] * nrm
-                            new = pt - qn
-                            v1[idx[neg]] = new[neg]
-                            hit[act[idx[neg]]] |= HIT_REFLECTED
-                            cls["reflected"][act[idx[neg]]] += 1
-                        a = thr - d[idx]
-                        a = a * inv
-                        a = a + skin
-                        move = a[:, None] * nrm
-                        p = p + move
-                        x1[idx] = p
-                        d[idx] = S(p)
-                        out = idx[~(d[idx] < thr)]
-                        cls["first_push" if it == 0 else "later_push"][act[out]] += 1
-                    rev = coll & (d < thr)
+
+                    def reflect(idx, nrm):  # the velocity, once a step
+                        vv = v1[idx]
+                        vn = vv[:, 0] * nrm[:, 0]
+                        t2 = vv[:, 1] * nrm[:, 1]
+                        vn = vn + t2
+                        t2 = vv[:, 2] * nrm[:, 2]
+                        vn = vn + t2
+                        neg = vn < F(0.0)
+                        w = vn[:, None] * nrm
+                        vt = vv - w
+                        a = rest * vn
+                        pt = ft * vt
+                        qn = a[:, None] * nrm
+                        new = pt - qn
+                        v1[idx[neg]] = new[neg]
+                        hit[act[idx[neg]]] |= HIT_REFLECTED
+                        cls["reflected"][act[idx[neg]]] += 1
+
+                    first, later, inside = cc.push_out(S, x1, d, coll, thr, skin, inv, iterations, on_first=reflect)
+                    cls["first_push"][act] += first
+                    cls["later_push"][act] += later
+                    cls["reverted"][act] += inside
+                    rev = inside > 0
                     hit[act[rev]] |= HIT_REVERTED
-                    cls["reverted"][act[rev]] += 1
                     x1[rev] = x0[rev]
             x[act], v[act], age[act] = x1, v1, a1
             dead[act[killed]] = True

@@ -59,12 +59,43 @@ def normal(nb, inv_dx):
     return np.stack([np.where(ok, inv * c, F(0.0)) for c in g], axis=1).astype(F)
 
 
+def push_out(S, x1, d, coll, thr, skin, inv, iterations, on_first=None):
+    """push_out (hns_pointstep.hpp) restated, in place on x1 [m, 3] and d = S(x1): the rows of `coll` are pushed while d < thr, at most `iterations` times.
+    on_first(idx, nrm): what the caller does with the first iteration's rows and normals. -> per-row counts (first_push, later_push, inside): steps the first / a later
+    push resolved, and steps still inside after the last"""
+    one = F(1.0)
+    first_push, later_push, inside = (np.zeros(len(x1), np.int64) for _ in range(3))
+    for it in range(iterations):
+        idx = np.flatnonzero(coll & (d < thr))
+        if not len(idx):
+            break
+        p, nb = x1[idx], []
+        for axis in range(3):
+            for sign in (-1, 1):
+                q = p.copy()
+                q[:, axis] = p[:, axis] - one if sign < 0 else p[:, axis] + one
+                nb.append(S(q))
+        nrm = normal(nb, inv)
+        if it == 0 and on_first is not None:
+            on_first(idx, nrm)
+        a = thr - d[idx]
+        a = a * inv
+        a = a + skin
+        move = a[:, None] * nrm
+        p = p + move
+        x1[idx] = p
+        d[idx] = S(p)
+        out = idx[~(d[idx] < thr)]
+        (first_push if it == 0 else later_push)[out] += 1
+    inside[coll & (d < thr)] += 1
+    return first_push, later_push, inside
+
+
 def collide_mirror(G: OracleGrid, vel, sdf, xyz, dt, inv_dx, order, steps, mode, threshold=THRESHOLD, skin=SKIN, iterations=ITERATIONS):
     """-> (final positions [n, 3], status bytes, hit bytes, classes): classes is a dict of per-point counts of STEPS -- first_push / later_push: steps the first / a
     later push resolved; push_reverted: steps put back after the last push"""
     assert mode in MODES
     thr, skin, inv = F(threshold), F(skin), F(inv_dx)
-    one = F(1.0)
     x = np.array(xyz, dtype=F)
     n = len(x)
     S = lambda q: G.sample_trilinear_f(sdf, np.ascontiguousarray(q, dtype=F)) if len(q) else np.zeros(0, F)
@@ -85,29 +116,12 @@ def collide_mirror(G: OracleGrid, vel, sdf, xyz, dt, inv_dx, order, steps, mode,
                 hit[coll] |= HIT_KILLED
             else:
                 hit[coll] |= HIT_PUSHED
-                for it in range(iterations):
-                    idx = np.flatnonzero(coll & (d < thr))
-                    if not len(idx):
-                        break
-                    p, nb = x1[idx], []
-                    for axis in range(3):
-                        for sign in (-1, 1):
-                            q = p.copy()
-                            q[:, axis] = p[:, axis] - one if sign < 0 else p[:, axis] + one
-                            nb.append(S(q))
-                    nrm = normal(nb, inv)
-                    a = thr - d[idx]
-                    a = a * inv
-                    a = a + skin
-                    move = a[:, None] * nrm
-                    p = p + move
-                    x1[idx] = p
-                    d[idx] = S(p)
-                    out = idx[~(d[idx] < thr)]
-                    (first_push if it == 0 else later_push)[out] += 1
-                rev = coll & (d < thr)
+                first, later, inside = push_out(S, x1, d, coll, thr, skin, inv, iterations)
+                first_push += first
+                later_push += later
+                push_reverted += inside
+                rev = inside > 0
                 hit[rev] |= HIT_REVERTED
-                push_reverted[rev] += 1
                 x1[rev] = x0[rev]
             x = np.where(dead[:, None], x0, x1).astype(F)  # (a dead point takes no further step)
             if mode == "kill":
