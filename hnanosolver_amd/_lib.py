@@ -97,6 +97,19 @@ class hns_point_motion_spec(C.Structure):
 HNS_MOTION_FREE, HNS_MOTION_STICK, HNS_MOTION_BOUNCE, HNS_MOTION_KILL = 0, 1, 2, 3
 
 
+class hns_turbulence_spec(C.Structure):
+    _fields_ = [("amplitude", C.c_float), ("frequency", C.c_float), ("offset", C.c_float * 3), ("octaves", C.c_int), ("lacunarity", C.c_float), ("gain", C.c_float),
+                ("seed", C.c_uint), ("control", C.c_char_p), ("control_lo", C.c_float), ("control_hi", C.c_float)]
+
+
+class hns_decay_spec(C.Structure):
+    _fields_ = [("name", C.c_char_p), ("rate", C.c_float), ("target", C.c_float)]
+
+
+class hns_shaping_curl(C.Structure):
+    _fields_ = [("c", C.c_float * 3)]
+
+
 class hns_point_order_info(C.Structure):
     _fields_ = [("perm", C.c_void_p), ("keys", C.c_void_p), ("leaf_start", C.c_void_p), ("n", C.c_uint64), ("n_leaves", C.c_uint64), ("capacity", C.c_uint64),
                 ("level", C.c_int)]
@@ -205,6 +218,11 @@ SIGNATURES = {
     "hns_point_motion_set_stream": (_i, [_vp, _vp]),
     "hns_point_motion_get": (_i, [_vp, C.POINTER(hns_point_motion_info)]),
     "hns_point_motion_step": (_i, [_vp, _vp, _u64, _f, _f, _i, C.POINTER(hns_point_motion_spec)]),
+    "hns_shaping_create": (_vp, [_ip]),
+    "hns_shaping_destroy": (None, [_vp]),
+    "hns_shaping_set_stream": (_i, [_vp, _vp]),
+    "hns_shaping_apply": (_i, [_vp, _vp, _f, C.POINTER(hns_turbulence_spec), C.POINTER(hns_decay_spec), _i]),
+    "hns_shaping_curl_host": (_i, [C.POINTER(hns_turbulence_spec), _i, _i, _i, C.POINTER(hns_shaping_curl)]),
     "hns_dev_splat_points": (_i, [_vp, C.POINTER(C.c_void_p), _ip, _i, _fp, C.POINTER(C.c_void_p), _u64, _i, _vp, _vp, _vp]),
     "hns_grid_splat_points": (_i, [_vp, C.POINTER(C.c_void_p), _ip, _i, _fp, C.POINTER(C.c_void_p), _u64, _i, _vp, _i, _vp, C.POINTER(C.c_uint64)]),
     "hns_grid_set_splat_spec": (_i, [_vp, C.POINTER(hns_splat_spec)]),

@@ -338,6 +338,7 @@ struct hns_sim {
 		for (size_t i = 0; i < handed_cur.size(); ++i)
 			if (k == kEverything || k == (int)i) handed_cur[i] = Handed{};
 	}
+	void wrote_field(int k) { handed_cur[(size_t)k] = Handed{}; }  // float field k was written in place by a call that left the velocity alone: its signature goes, the look-ahead memo (a function of the velocity and collision_sdf) stays
 	unsigned long long* d_dig = nullptr;  // 16 accumulators of the digest kernels (hns_digest.hpp): a slice of the arena
 	unsigned long long* h_dig = nullptr;  // pinned host copy of them (read asynchronously on the cook's own stream)
 	hns::Pooled arena;  // every field above is a slice of this one allocation (hns::sim_slices below)

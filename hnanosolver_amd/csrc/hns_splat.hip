@@ -240,7 +240,7 @@ int sim_splat_fields(const char* who, const hns_sim* s, const char* const* names
 
 // a sim call with n > 0 has run: the written buffers no longer hold what a cook handed back; a rewritten velocity is not the one a substep looked ahead from
 void sim_splat_wrote(hns_sim* s, const std::vector<int>& which, bool velocity) {
-	for (int k : which) s->handed_cur[(size_t)k] = hns_sim::Handed{};
+	for (int k : which) s->wrote_field(k);
 	if (velocity) s->forget(hns_sim::kVelocity);
 }
 

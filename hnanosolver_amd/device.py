@@ -664,6 +664,83 @@ class PointMotion:
             pass
 
 
+class Shaping:
+    """Shaping a device-resident sim in place (``hns_shaping``; include/hns.h states the arithmetic line by line): divergence-free curl-noise turbulence on the velocity,
+    optionally weighted by a control field, and implicit decay of float fields towards a target, in one launch over the sim's leaves. The object holds no device memory
+    and is bound to no sim: ``apply`` takes the sim."""
+
+    TURBULENCE = dict(amplitude=0.0, frequency=1.0 / 16, offset=(0.0, 0.0, 0.0), octaves=1, lacunarity=2.0, gain=0.5, seed=0, control=None, control_lo=0.0, control_hi=1.0)
+
+    def __init__(self):
+        self._ptr = 0
+        err = C.c_int(0)
+        self._ptr = lib.hns_shaping_create(C.byref(err))
+        if not self._ptr:
+            _raise(err.value if err.value < 0 else _lib.HNS_ERR_RUNTIME)
+
+    @classmethod
+    def turbulence_spec(cls, turbulence: dict):
+        """the ``hns_turbulence_spec`` of a dict with the keys of ``Shaping.TURBULENCE`` (missing ones take its values)"""
+        unknown = set(turbulence) - set(cls.TURBULENCE)
+        if unknown:
+            raise ValueError(f"Shaping: unknown turbulence keys {sorted(unknown)} (known: {sorted(cls.TURBULENCE)})")
+        t = {**cls.TURBULENCE, **turbulence}
+        off = tuple(float(c) for c in t["offset"])
+        if len(off) != 3:
+            raise ValueError("Shaping: offset has three components")
+        return _lib.hns_turbulence_spec(float(t["amplitude"]), float(t["frequency"]), (C.c_float * 3)(*off), int(t["octaves"]), float(t["lacunarity"]), float(t["gain"]),
+                                        int(t["seed"]) & 0xFFFFFFFF, None if t["control"] is None else str(t["control"]).encode(), float(t["control_lo"]),
+                                        float(t["control_hi"]))
+
+    def apply(self, sim, dt: float, turbulence: Optional[dict] = None, decay: Optional[dict] = None, stream: Optional[int] = None):
+        """One launch on `sim` (``hns_shaping_apply``). turbulence: None, or a dict with the keys of ``Shaping.TURBULENCE`` -- v += amplitude * dt * w * C, C the summed
+        curl of `octaves` octaves of gradient noise at `frequency` lattice cells per voxel (each octave `lacunarity` times finer and `gain` times weaker; one octave has
+        |C| about 0.8 on average), w = 1 or, with `control` the name of a float field, clamp((field - control_lo) / (control_hi - control_lo), 0, 1) of its value before
+        this call's decay; scroll `offset` to animate. decay: None, or {name: (rate, target)} of up to eight float fields -- f = target + (f - target) / (1 + rate * dt).
+        stream: a hipStream_t as an integer, None = torch's current stream; the call is asynchronous on it. Returns self."""
+        if not self._ptr:
+            raise RuntimeError("Shaping: the object is closed")
+        spec = None if turbulence is None else self.turbulence_spec(turbulence)
+        rows = list((decay or {}).items())
+        arr = (_lib.hns_decay_spec * max(1, len(rows)))()
+        for d, (name, (rate, target)) in zip(arr, rows):
+            d.name, d.rate, d.target = str(name).encode(), float(rate), float(target)
+        _raise(lib.hns_shaping_set_stream(self._ptr, current_stream() if stream is None else int(stream)))
+        _raise(lib.hns_shaping_apply(self._ptr, sim._ptr, float(dt), None if spec is None else C.byref(spec), arr if rows else None, len(rows)))
+        return self
+
+    def close(self) -> None:
+        if self._ptr:
+            lib.hns_shaping_destroy(self._ptr)
+            self._ptr = 0
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def shaping_curl_host(turbulence: dict, ijk) -> np.ndarray:
+    """C of the voxels `ijk` ([n, 3] int32 global coordinates), [n, 3] float32, evaluated on the host by ``hns_shaping_curl_host`` -- the summed curl before amplitude,
+    control and dt, from the header the kernel includes. Needs no device."""
+    spec = Shaping.turbulence_spec(turbulence)
+    ijk = np.ascontiguousarray(ijk, dtype=np.int32).reshape(-1, 3)
+    out = np.empty((len(ijk), 3), np.float32)
+    one = _lib.hns_shaping_curl()
+    fn, ref = lib.hns_shaping_curl_host, C.byref(one)
+    for r, (i, j, k) in enumerate(ijk.tolist()):
+        _raise(fn(C.byref(spec), i, j, k, ref))
+        out[r] = one.c[0], one.c[1], one.c[2]
+    return out
+
+
 def stats_buffer(n_records: int = 1):
     """Device memory for `n_records` hns_stats records (a uint8 tensor; ``read_stats`` brings it to the host)."""
     return _torch().zeros(n_records * leafio.STATS_DTYPE.itemsize, dtype=_torch().uint8, device="cuda")
@@ -725,6 +802,7 @@ class Sim:
     def __init__(self, grid: IndexGridHandle, float_names: Sequence[str]):
         self.grid = grid
         self.names = list(float_names)
+        self._shaping = None  # the Shaping that ``shape`` makes on first use
         arr = (C.c_char_p * max(1, len(self.names)))(*[n.encode() for n in self.names])
         err = C.c_int(0)
         self._ptr = lib.hns_sim_create(grid.ptr, arr, len(self.names), C.byref(err))
@@ -1027,6 +1105,14 @@ class Sim:
         """A ``PointMotion`` of `capacity` rows. It is bound to no grid: ``motion.step(sim, ...)`` reads the grid the sim has at that call, after a ``regrid`` too."""
         return PointMotion(capacity)
 
+    def shape(self, dt: float, turbulence: Optional[dict] = None, decay: Optional[dict] = None, stream: Optional[int] = None):
+        """``Shaping.apply`` on this sim through a ``Shaping`` the sim owns (made on first use, closed with the sim): curl-noise turbulence on the velocity and decay of
+        float fields, in place, in one launch. Returns self."""
+        if self._shaping is None:
+            self._shaping = Shaping()
+        self._shaping.apply(self, dt, turbulence, decay, stream)
+        return self
+
     def birth(self, population: PointPopulation, name: str, xyz, voxel=None, *, threshold: float, rate: float, max_per_voxel: int, seed: int, append: bool = False,
               fill: bool = True, use_masks: bool = True, stream: Optional[int] = None):
         """``PointPopulation.birth`` from the sim's own float field `name` and, with use_masks, its active masks (``hns_point_population_birth_sim``): embers where
@@ -1045,6 +1131,9 @@ class Sim:
         return dict(zip(("candidates", "host", "masks", "fields"), [float(x) for x in ms]))
 
     def close(self) -> None:
+        if self._shaping is not None:
+            self._shaping.close()
+            self._shaping = None
         if self._ptr:
             lib.hns_sim_destroy(self._ptr)
             self._ptr = 0

@@ -721,6 +721,82 @@ typedef struct hns_point_motion_spec {
 	int iterations;   /* 1 .. 8 pushes per bounced step */
 } hns_point_motion_spec;
 int hns_point_motion_step(hns_point_motion*, hns_sim*, uint64_t n, float dt, float voxel_size, int steps, const hns_point_motion_spec*);
+/* SHAPING A SIM: curl-noise turbulence and field decay, the two operators a device-resident sim needs to be shaped without leaving the GPU. Turbulence adds a
+ * divergence-free force to the velocity -- the curl of a three-channel gradient-noise potential, summed over octaves, optionally weighted by a control field --, which the
+ * projection does not remove; decay relaxes float fields implicitly towards a target (smoke thins out, temperature cools to ambient). Both run in ONE launch over the
+ * sim's leaves, in place. hns_shaping is an object that only holds the stream the launch goes to; the sim is an argument. No call here takes a caller's data pointer.
+ *   Object   create allocates no device memory (HNS_ERR_NO_DEVICE without a HIP device); the null stream until hns_shaping_set_stream binds another.
+ *   apply    asynchronous on the object's stream; allocates nothing. It updates all 512 voxels of the leaves in the grid's launch range [first, first + n_active), as
+ *            the substep's pointwise stages do, whatever the active masks say, and writes nothing else: no other leaf, no other field, not the advected velocity, the
+ *            pressure or the divergence, not the masks. When the velocity is written the sim forgets what it knew of it (the look-ahead memo and the velocity's feedback
+ *            signature are dropped, as by hns_sim_splat_points); of a decayed field its signature alone -- the memo is a function of the velocity and of collision_sdf, which
+ *            is why that field may not be decayed, so a call that only decays leaves the memo in place. Nothing else about the sim changes. A call
+ *            with no turbulence (NULL, or amplitude == 0) and n_decays == 0 launches nothing and forgets nothing; with amplitude == 0 the velocity is neither read nor
+ *            written; a grid with no leaves launches nothing.
+ * The arithmetic. Every line below is one rounded float32 operation, none contracted; integers are uint32 and wrap. H is the hash of BIRTH AND DEATH OF POINTS.
+ *   Host constants, formed in float32 on the host once per call: f_0 = frequency, f_o = f_(o-1) * lacunarity; a_0 = 1.0f, a_o = a_(o-1) * gain; kA = amplitude * dt;
+ *            inv = 1.0f / (control_hi - control_lo); s_o = H(H(seed ^ 0x9E3779B9u) + o); per decay r = 1.0f / (1.0f + rate * dt).
+ *   Lattice  the voxel has global coordinates x = (i, j, k). Per octave o and component c: q.c = f_o * (float)x.c; q.c = q.c + offset.c. If any component of q is not
+ *            finite or has |q.c| >= 4194304.0f the octave's curl is c_o = (+0, +0, +0): that far out the fraction has no bits left. Otherwise the cell is
+ *            I.c = Floor(q.c) and the fraction t.c = q.c - (float)I.c (0 <= t.c <= 1; 1 where the subtraction rounds up).
+ *   Corners  h(I + (a,b,e)) = H(H(H(s_o ^ (uint32)(I.x+a)) ^ (uint32)(I.y+b)) ^ (uint32)(I.z+e)) for a, b, e in {0, 1}: one hash per lattice corner and octave. Channel m
+ *            in {0, 1, 2} reads nibble (h >> 4m) & 15, which selects a gradient g from the 16 of improved Perlin noise, in this order:
+ *            (1,1,0), (-1,1,0), (1,-1,0), (-1,-1,0), (1,0,1), (-1,0,1), (1,0,-1), (-1,0,-1), (0,1,1), (0,-1,1), (0,1,-1), (0,-1,-1), (1,1,0), (-1,1,0), (0,-1,1), (0,-1,-1),
+ *            its components the floats +0.0f, 1.0f and -1.0f.
+ *   Value    p = (t.x - a, t.y - b, t.z - e), where a component with a, b or e = 0 is t's itself and the others are t.c - 1.0f;
+ *            d_abe = (g.x * p.x + g.y * p.y) + g.z * p.z: three multiplies (a zero component gives a signed zero), then the two adds in this order.
+ *   Fades    u(t) = (((((6.0f * t - 15.0f) * t + 10.0f) * t) * t) * t, seven operations from the left; u'(t): b = t - 2.0f; b = b * t; b = b + 1.0f; e = 30.0f * t;
+ *            e = e * t; u' = e * b.
+ *   Lerp     lerp(v0, v1, w): d = v1 - v0; d = w * d; v0 + d.
+ *   Nests    L(v) over eight corner values v_abe: first along z, v_ab = lerp(v_ab0, v_ab1, u(t.z)); then along y, v_a = lerp(v_a0, v_a1, u(t.y)); then along x,
+ *            lerp(v_0, v_1, u(t.x)). A nest over four values runs the same order with the missing axis left out.
+ *   Partials dN_m/dx = u'(t.x) * L_yz(d_1be - d_0be) + L(g_abe.x): the four differences, their nest z then y, the multiply, the nest of the gradients' x components,
+ *            the add. dN_m/dy likewise with d_a1e - d_a0e, the nest z then x, u'(t.y) and g_abe.y; dN_m/dz with d_ab1 - d_ab0, the nest y then x, u'(t.z) and g_abe.z.
+ *            N itself is not formed. Derivatives are taken in lattice units.
+ *   Curl     of the potential (N_0, N_1, N_2): c_o.x = dN_2/dy - dN_1/dz; c_o.y = dN_0/dz - dN_2/dx; c_o.z = dN_1/dx - dN_0/dy -- six of the nine partials. Each
+ *            octave is divergence-free on its own, so the sum is. C.c = sum over o = 0 .. octaves - 1 in ascending order of a_o * c_o.c: C.c = +0; then per octave
+ *            e = a_o * c_o.c; C.c = C.c + e. A component of one octave's c_o has a magnitude of 0.81 on average and 3.9 at the peak of 4,000 samples (tests/test_shaping_cases.py prints both): choose the amplitude by that.
+ *   Control  without a control w is not formed and k = kA. With one, c is the control field's value at the voxel BEFORE this call's decay: w = c - control_lo;
+ *            w = w * inv; w = fminf(fmaxf(w, 0.0f), 1.0f) with the GPU's min / max, which a NaN operand loses, formed as w = w > 0.0f ? w : +0.0f;
+ *            w = w < 1.0f ? w : 1.0f -- so a NaN c gives w = 0, and so does -0 --; k = kA * w.
+ *   Velocity e = k * C.c; v.c = v.c + e. NaN and inf in v pass through by the arithmetic.
+ *   Decay    of each listed field, after the control was read: t = f - target; t = t * r; f = target + t.
+ * hns_shaping_curl_host evaluates C of the voxel (i, j, k) -- before amplitude, control and dt -- ON THE HOST, from the header the kernel includes (hns_noise.hpp); it
+ * ignores control, control_lo and control_hi, and needs no device. There is no host mirror over whole arrays (it would take data pointers): the Python tests restate the
+ * text above in numpy and compare every byte.
+ * Refused before anything is launched and with nothing touched (HNS_ERR_INVALID_ARGUMENT, the call and the argument in the message) -- the numbers and the specs, host
+ * structs, first, then the objects --: a NaN, infinite or negative dt; an amplitude or offset component that is not finite, a frequency that is not finite and > 0,
+ * octaves outside 1 .. 4, a lacunarity that is not finite and >= 1, a gain outside 0 .. 1 or NaN, with a control a control_lo or control_hi that is not finite or
+ * control_lo >= control_hi; n_decays outside 0 .. 8, a null decays with n_decays > 0, a null decay name, a rate that is NaN, infinite or negative, a target that is not
+ * finite; then a null object, a null sim (HNS_ERR_NO_DEVICE where there is no device), a sim lent to a grid's cook cache, a control or decay name that is not a float
+ * field of the sim, "collision_sdf" as a decay name (it may be the control), a decay name given twice. curl_host: a null spec or out, and the spec's numbers as above.
+ * Not mirrored in hns_dist_*. */
+typedef struct hns_shaping hns_shaping;
+hns_shaping* hns_shaping_create(int* err);
+void hns_shaping_destroy(hns_shaping*);
+int hns_shaping_set_stream(hns_shaping*, void* hip_stream);
+typedef struct hns_turbulence_spec {
+	float amplitude;     /* finite; velocity units per unit of time; 0 = read and write no velocity */
+	float frequency;     /* finite, > 0; lattice cells per voxel of octave 0 */
+	float offset[3];     /* finite; lattice units; the caller scrolls it to animate */
+	int octaves;         /* 1 .. 4 */
+	float lacunarity;    /* finite, >= 1 */
+	float gain;          /* finite, 0 .. 1 */
+	unsigned int seed;
+	const char* control; /* NULL, or the name of a float field of the sim */
+	float control_lo;    /* finite, control_lo < control_hi; read only with a control */
+	float control_hi;
+} hns_turbulence_spec;
+typedef struct hns_decay_spec {
+	const char* name; /* a float field of the sim, not "collision_sdf" */
+	float rate;       /* finite, >= 0; in the limit of small dt the e-folding rate of the distance to the target */
+	float target;     /* finite */
+} hns_decay_spec;
+int hns_shaping_apply(hns_shaping*, hns_sim*, float dt, const hns_turbulence_spec* turbulence, const hns_decay_spec* decays, int n_decays);
+typedef struct hns_shaping_curl {
+	float c[3];
+} hns_shaping_curl;
+int hns_shaping_curl_host(const hns_turbulence_spec*, int i, int j, int k, hns_shaping_curl* out);
 /* Point values into fields: the transpose of hns_dev_sample_points -- every point adds w * v to the eight voxels of its cell -- with an accumulation that does not depend on
  * the order the adds retire in. fields[i]: device pointer, ncomp[i] 1 (float) or 3 (Vec3f AoS), added into IN PLACE; values[i]: device, n x ncomp[i] floats, the value of
  * each point for field i; fields, ncomp and values are HOST arrays of n_fields (1 .. 8) entries; xyz as for hns_dev_sample_points.
