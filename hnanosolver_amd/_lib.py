@@ -110,6 +110,21 @@ class hns_shaping_curl(C.Structure):
     _fields_ = [("c", C.c_float * 3)]
 
 
+class hns_diffusion_term(C.Structure):
+    _fields_ = [("name", C.c_char_p), ("coefficient", C.c_float)]
+
+
+class hns_diffusion_spec(C.Structure):
+    _fields_ = [("iterations", C.c_int), ("method", C.c_int), ("viscosity", C.c_float), ("collide", C.c_int), ("threshold", C.c_float)]
+
+
+class hns_diffusion_schedule(C.Structure):
+    _fields_ = [("a", C.c_float), ("r", C.c_float * 7), ("rho", C.c_float), ("omega", C.c_float * 256)]
+
+
+HNS_DIFFUSION_JACOBI, HNS_DIFFUSION_CHEBYSHEV = 0, 1
+
+
 class hns_point_order_info(C.Structure):
     _fields_ = [("perm", C.c_void_p), ("keys", C.c_void_p), ("leaf_start", C.c_void_p), ("n", C.c_uint64), ("n_leaves", C.c_uint64), ("capacity", C.c_uint64),
                 ("level", C.c_int)]
@@ -223,6 +238,11 @@ SIGNATURES = {
     "hns_shaping_set_stream": (_i, [_vp, _vp]),
     "hns_shaping_apply": (_i, [_vp, _vp, _f, C.POINTER(hns_turbulence_spec), C.POINTER(hns_decay_spec), _i]),
     "hns_shaping_curl_host": (_i, [C.POINTER(hns_turbulence_spec), _i, _i, _i, C.POINTER(hns_shaping_curl)]),
+    "hns_diffusion_create": (_vp, [_ip]),
+    "hns_diffusion_destroy": (None, [_vp]),
+    "hns_diffusion_set_stream": (_i, [_vp, _vp]),
+    "hns_diffusion_apply": (_i, [_vp, _vp, _f, _f, C.POINTER(hns_diffusion_spec), C.POINTER(hns_diffusion_term), _i]),
+    "hns_diffusion_schedule_host": (_i, [_f, _f, _f, _i, C.POINTER(hns_diffusion_schedule)]),
     "hns_dev_splat_points": (_i, [_vp, C.POINTER(C.c_void_p), _ip, _i, _fp, C.POINTER(C.c_void_p), _u64, _i, _vp, _vp, _vp]),
     "hns_grid_splat_points": (_i, [_vp, C.POINTER(C.c_void_p), _ip, _i, _fp, C.POINTER(C.c_void_p), _u64, _i, _vp, _i, _vp, C.POINTER(C.c_uint64)]),
     "hns_grid_set_splat_spec": (_i, [_vp, C.POINTER(hns_splat_spec)]),

@@ -741,6 +741,73 @@ def shaping_curl_host(turbulence: dict, ijk) -> np.ndarray:
     return out
 
 
+class Diffusion:
+    """Implicit diffusion of float fields and viscosity of the velocity on a device-resident sim (``hns_diffusion``; include/hns.h states the arithmetic line by line):
+    per field (I - a L) x = b over the sim's unknowns, a = coefficient * dt / voxel_size**2, by a fixed number of Jacobi or Chebyshev iterations, one launch each. The
+    object holds its stream and the pooled scratch of its calls and is bound to no sim: ``apply`` takes the sim."""
+
+    METHODS = {"jacobi": _lib.HNS_DIFFUSION_JACOBI, "chebyshev": _lib.HNS_DIFFUSION_CHEBYSHEV}
+
+    def __init__(self):
+        self._ptr = 0
+        err = C.c_int(0)
+        self._ptr = lib.hns_diffusion_create(C.byref(err))
+        if not self._ptr:
+            _raise(err.value if err.value < 0 else _lib.HNS_ERR_RUNTIME)
+
+    @classmethod
+    def spec(cls, viscosity: float = 0.0, iterations: int = 8, method: str = "jacobi", collide: bool = False, threshold: float = 0.0):
+        """the ``hns_diffusion_spec`` of these arguments"""
+        if method not in cls.METHODS:
+            raise ValueError(f"Diffusion: unknown method {method!r} (known: {sorted(cls.METHODS)})")
+        return _lib.hns_diffusion_spec(int(iterations), cls.METHODS[method], float(viscosity), 1 if collide else 0, float(threshold))
+
+    def apply(self, sim, dt: float, voxel_size: float, fields: Optional[dict] = None, viscosity: float = 0.0, iterations: int = 8, method: str = "jacobi",
+              collide: bool = False, threshold: float = 0.0, stream: Optional[int] = None):
+        """``hns_diffusion_apply`` on `sim`. fields: None, or {name: coefficient} of up to eight float fields; viscosity: the velocity's coefficient (0: the velocity
+        is neither read nor written); iterations 1 .. 256 of method "jacobi" or "chebyshev"; collide: voxels whose ``collision_sdf`` lies below `threshold` are solid --
+        zero-flux for a float field, a no-slip wall at rest for the velocity. Only the sim's unknowns (active, not solid) are written. stream: a hipStream_t as an integer,
+        None = torch's current stream; the call is asynchronous on it. Returns self."""
+        if not self._ptr:
+            raise RuntimeError("Diffusion: the object is closed")
+        spec = self.spec(viscosity, iterations, method, collide, threshold)
+        rows = list((fields or {}).items())
+        unknown = [str(k) for k, _ in rows if str(k) not in sim.names]
+        if unknown:
+            raise ValueError(f"Diffusion: unknown fields {sorted(unknown)} (the sim's float fields: {sorted(sim.names)})")
+        arr = (_lib.hns_diffusion_term * max(1, len(rows)))()
+        for t, (name, coefficient) in zip(arr, rows):
+            t.name, t.coefficient = str(name).encode(), float(coefficient)
+        _raise(lib.hns_diffusion_set_stream(self._ptr, current_stream() if stream is None else int(stream)))
+        _raise(lib.hns_diffusion_apply(self._ptr, sim._ptr, float(dt), float(voxel_size), C.byref(spec), arr if rows else None, len(rows)))
+        return self
+
+    def close(self) -> None:
+        if self._ptr:
+            lib.hns_diffusion_destroy(self._ptr)
+            self._ptr = 0
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def diffusion_schedule_host(coefficient: float, dt: float, voxel_size: float, iterations: int) -> dict:
+    """The host constants of one coefficient (``hns_diffusion_schedule_host``; needs no device): {"a": float32, "r": float32[7], "rho": float32,
+    "omega": float32[256]}, omega[k - 1] = w_k for k <= iterations and 0 behind them."""
+    out = _lib.hns_diffusion_schedule()
+    _raise(lib.hns_diffusion_schedule_host(float(coefficient), float(dt), float(voxel_size), int(iterations), C.byref(out)))
+    return {"a": np.float32(out.a), "r": np.array(out.r[:], np.float32), "rho": np.float32(out.rho), "omega": np.array(out.omega[:], np.float32)}
+
+
 def stats_buffer(n_records: int = 1):
     """Device memory for `n_records` hns_stats records (a uint8 tensor; ``read_stats`` brings it to the host)."""
     return _torch().zeros(n_records * leafio.STATS_DTYPE.itemsize, dtype=_torch().uint8, device="cuda")
@@ -803,6 +870,7 @@ class Sim:
         self.grid = grid
         self.names = list(float_names)
         self._shaping = None  # the Shaping that ``shape`` makes on first use
+        self._diffusion = None  # the Diffusion that ``diffuse`` makes on first use
         arr = (C.c_char_p * max(1, len(self.names)))(*[n.encode() for n in self.names])
         err = C.c_int(0)
         self._ptr = lib.hns_sim_create(grid.ptr, arr, len(self.names), C.byref(err))
@@ -1113,6 +1181,15 @@ class Sim:
         self._shaping.apply(self, dt, turbulence, decay, stream)
         return self
 
+    def diffuse(self, dt: float, voxel_size: float, fields: Optional[dict] = None, viscosity: float = 0.0, iterations: int = 8, method: str = "jacobi",
+                collide: bool = False, threshold: float = 0.0, stream: Optional[int] = None):
+        """``Diffusion.apply`` on this sim through a ``Diffusion`` the sim owns (made on first use, closed with the sim; it keeps its pooled scratch between calls):
+        implicit diffusion of float fields and viscosity of the velocity over the sim's unknowns. Returns self."""
+        if self._diffusion is None:
+            self._diffusion = Diffusion()
+        self._diffusion.apply(self, dt, voxel_size, fields, viscosity, iterations, method, collide, threshold, stream)
+        return self
+
     def birth(self, population: PointPopulation, name: str, xyz, voxel=None, *, threshold: float, rate: float, max_per_voxel: int, seed: int, append: bool = False,
               fill: bool = True, use_masks: bool = True, stream: Optional[int] = None):
         """``PointPopulation.birth`` from the sim's own float field `name` and, with use_masks, its active masks (``hns_point_population_birth_sim``): embers where
@@ -1134,6 +1211,9 @@ class Sim:
         if self._shaping is not None:
             self._shaping.close()
             self._shaping = None
+        if self._diffusion is not None:
+            self._diffusion.close()
+            self._diffusion = None
         if self._ptr:
             lib.hns_sim_destroy(self._ptr)
             self._ptr = 0

@@ -797,6 +797,79 @@ typedef struct hns_shaping_curl {
 	float c[3];
 } hns_shaping_curl;
 int hns_shaping_curl_host(const hns_turbulence_spec*, int i, int j, int k, hns_shaping_curl* out);
+/* DIFFUSING A SIM: implicit diffusion of float fields (heat conduction, smoke diffusion) and viscosity of the velocity, the operator that spreads a field of a
+ * device-resident sim without leaving the GPU. For each listed field solve (I - a L) x = b: b is the field as it stands at the call,
+ * a = coefficient * dt / voxel_size^2, L the 7-point Laplacian over the UNKNOWNS of the sim. It is implicit, so it is stable at any a; the solve is a fixed number of
+ * Jacobi or Chebyshev-accelerated Jacobi iterations, one launch each over all listed fields. hns_diffusion is an object that holds the stream the launches go to and
+ * the pooled scratch of its calls; the sim is an argument. No call here takes a caller's data pointer.
+ *   Object   create allocates no device memory (HNS_ERR_NO_DEVICE without a HIP device); the null stream until hns_diffusion_set_stream binds another.
+ *   apply    asynchronous on the object's stream. It updates only the unknowns of the listed fields, and of the velocity when viscosity gives a non-zero a, and writes
+ *            nothing else the caller can observe: no other field, not the divergence, not the pressure, not the masks. Device pointers the sim has handed out stay valid,
+ *            and the result lies behind them. When the velocity is written the sim forgets what it knew of it (the look-ahead memo and the velocity's feedback signature
+ *            are dropped, as by hns_shaping_apply); of a written float field its signature alone. A call that leaves every term at a == 0, or a grid without leaves,
+ *            launches nothing and forgets nothing. Otherwise: one launch that classifies the faces, `iterations` launches, and with iterations == 1 one copy.
+ *   Scratch  each written field needs two iterates beside b. Of the velocity they are the sim's advected-velocity and vorticity buffers (the memo in the first goes
+ *            with the forget); of a float field the sim's own next-value buffer of that field and one array from the pool. The object draws ONE block from the pool on the
+ *            first apply that launches -- two code bytes per voxel and one float per voxel and written float field --, draws a larger one when a later call needs more
+ *            (which waits for the device), keeps it between calls and gives it back in destroy. The iterations write every word of the scratch before they read it
+ *            for a result: no result depends on what that memory held. The first iteration reads the field itself and the last writes into it (a thread of the last
+ *            launch reads b and x^(k-2) of its own voxel only, its neighbours from the scratch), so there is no copy, except with iterations == 1.
+ * The mathematics.
+ *   Voxel classes  a voxel is SOLID iff collide != 0, its leaf exists and collision_sdf < threshold there (a NaN is not solid: the rule of the collision trace). A voxel
+ *            is an UNKNOWN iff its leaf exists, its bit in the sim's active masks is set (no masks = every voxel) and it is not solid. Every voxel that is not an
+ *            unknown keeps its bytes: it is never written.
+ *   Faces    of an unknown, in the fixed order +x, -x, +y, -y, +z, -z. OPEN: the neighbour is an unknown. WALL: the neighbour is solid. Closed: everything else (an
+ *            absent leaf, an inactive voxel). For a float field open faces exchange; wall and closed faces are zero-flux. For the velocity (all three components, the
+ *            same faces) a wall face is a no-slip wall at rest: it counts in m and adds nothing to the sum. m = open faces for a float field; m = open + wall faces
+ *            for the velocity.
+ *   Host constants, in float32 on the host, one rounded operation per step, once per field and call: h2 = voxel_size * voxel_size; a = coefficient * dt; a = a / h2;
+ *            for m = 0..6: e = a * (float)m; den = 1.0f + e; r_m = 1.0f / den; s = 6.0f * a; den = 1.0f + s; rho = s / den; q = rho * rho;
+ *            w_1 = 1.0f; w_2 = 1.0f / (1.0f - q * 0.5f) as h = q * 0.5f; d = 1.0f - h; w_2 = 1.0f / d;
+ *            w_(k+1) = 1.0f / (1.0f - (q * 0.25f) * w_k) as c = q * 0.25f; e = c * w_k; d = 1.0f - e; w_(k+1) = 1.0f / d. There is no division on the device.
+ *   Iteration k = 1..iterations, per unknown and component, one rounded float32 operation per line, none contracted: x^0 = b; S = +0.0f;
+ *            for each OPEN face in the order above: S = S + x^(k-1)[neighbour]; t = a * S; t = b + t; j = t * r_m.
+ *            Jacobi (method 0): x^k = j. Chebyshev (method 1): x^1 = j; for k >= 2: d = j - x^(k-2); d = w_k * d; x^k = x^(k-2) + d.
+ *            Chebyshev reads only its own voxel of x^(k-2), so x^k may be written over x^(k-2). NaN and inf pass through by the arithmetic.
+ *   Result   a Jacobi sweep reads only the previous iterate: the result is unique, whatever order workgroups retire in. There are no atomics.
+ *   Convergence, to choose the iteration count by: Jacobi contracts the max-norm error by rho per iteration and keeps every iterate of a float field inside
+ *            [min b, max b]. Chebyshev reaches 2 sigma^k / (1 + sigma^(2k)) with sigma = rho / (1 + sqrt(1 - rho^2)); it loses that monotonicity and is worse for the first
+ *            few iterations at large a. Measured on the numpy mirror (tests/test_diffusion_cases.py prints them): at a = 4 after 40 iterations the error is 3e-2 for Jacobi
+ *            and 1e-4 for Chebyshev (max|b| = 8); at a = 0.05 both are converged to float32 in 8 iterations.
+ *   Exact solution  of a float field conserves the sum of x over the unknowns. The velocity's does not: the wall takes momentum.
+ *   Skipped  a term whose a is +0 (coefficient 0 or dt 0) is skipped: neither read nor written, and the sim forgets nothing of it. The same holds for viscosity.
+ * hns_diffusion_schedule_host forms the host constants of one coefficient ON THE HOST, with no device: a, r[m] = r_m, rho, omega[k-1] = w_k for k = 1 .. iterations
+ * (omega[0] = 1.0f) and +0.0f behind them. There is no host mirror over whole arrays (it would take data pointers): the Python tests restate the text above in numpy
+ * and compare every byte.
+ * Refused before anything is launched and with nothing touched (HNS_ERR_INVALID_ARGUMENT, the call and the argument in the message) -- the numbers and the host
+ * structs first, then the objects --: a null spec; a NaN, infinite or negative dt; a voxel_size that is not finite and > 0; iterations outside 1 .. 256; method outside
+ * 0 .. 1; a viscosity or a coefficient that is NaN, infinite or negative; any a or 6 a that is not finite; with collide a threshold that is not finite; n_terms outside
+ * 0 .. 8; null terms with n_terms > 0; a null name; then a null object, a null sim (HNS_ERR_NO_DEVICE where there is no device), a sim lent to a grid's cook cache, a
+ * name that is not a float field of the sim, "collision_sdf" as a term, a name listed twice, collide on a sim without a collision_sdf field; then, of a call that has
+ * something to launch, a sim and an object on different devices and a grid whose launch range is not the whole grid (as the multigrid solve refuses it: a face of a
+ * leaf outside the range would be neither open nor closed). schedule_host: a null out and the same numbers. Not mirrored in hns_dist_*. */
+typedef struct hns_diffusion hns_diffusion;
+hns_diffusion* hns_diffusion_create(int* err);
+void hns_diffusion_destroy(hns_diffusion*);
+int hns_diffusion_set_stream(hns_diffusion*, void* hip_stream);
+typedef struct hns_diffusion_term {
+	const char* name;  /* a float field of the sim, not "collision_sdf" */
+	float coefficient; /* finite, >= 0; the diffusivity, in voxel_size^2 per unit of dt */
+} hns_diffusion_term;
+typedef struct hns_diffusion_spec {
+	int iterations;  /* 1 .. 256 */
+	int method;      /* 0 Jacobi, 1 Chebyshev */
+	float viscosity; /* finite, >= 0; the velocity's coefficient, 0 = the velocity is neither read nor written */
+	int collide;     /* 0: no voxel is solid; 1: the sim's collision_sdf decides */
+	float threshold; /* finite; read only with collide */
+} hns_diffusion_spec;
+int hns_diffusion_apply(hns_diffusion*, hns_sim*, float dt, float voxel_size, const hns_diffusion_spec*, const hns_diffusion_term* terms, int n_terms);
+typedef struct hns_diffusion_schedule {
+	float a;
+	float r[7];
+	float rho;
+	float omega[256]; /* omega[k-1] = w_k; omega[0] = 1.0f */
+} hns_diffusion_schedule;
+int hns_diffusion_schedule_host(float coefficient, float dt, float voxel_size, int iterations, hns_diffusion_schedule* out);
 /* Point values into fields: the transpose of hns_dev_sample_points -- every point adds w * v to the eight voxels of its cell -- with an accumulation that does not depend on
  * the order the adds retire in. fields[i]: device pointer, ncomp[i] 1 (float) or 3 (Vec3f AoS), added into IN PLACE; values[i]: device, n x ncomp[i] floats, the value of
  * each point for field i; fields, ncomp and values are HOST arrays of n_fields (1 .. 8) entries; xyz as for hns_dev_sample_points.
