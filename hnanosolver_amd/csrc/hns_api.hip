@@ -11,6 +11,8 @@
 
 #include "hns_internal.hpp"
 #include "hns_digest.hpp"
+#include "hns_device.hpp"  // check_grid, which hns_simcall.hpp builds on
+#include "hns_simcall.hpp"
 
 using namespace hns;
 
@@ -524,29 +526,11 @@ extern "C" int hns_sim_core_substep(hns_sim* s, int iterations, float dt, float 
 // AdvectIndexGrid over the named float fields (n_names -1: all of them), then AdvectIndexGridVelocity, on the sim's buffers (Advection.cu:76-91,148-155): the fields read the
 // velocity before its self-advection. Every check comes before the first launch.
 extern "C" int hns_sim_advect(hns_sim* s, const char* const* names, int n_names, int advect_velocity, float dt, float voxel_size, void* stream) {
-	if (!s) {  // (without a device there is no sim to pass: hns_sim_create refused, and the caller learns why here too)
-		if (hns_device_count() == 0) return fail(HNS_ERR_NO_DEVICE, "hns_sim_advect: no HIP device (there is no CPU fallback)");
-		return fail(HNS_ERR_INVALID_ARGUMENT, "hns_sim_advect: null sim");
-	}
-	if (n_names < -1 || (n_names > 0 && !names)) return fail(HNS_ERR_INVALID_ARGUMENT, "hns_sim_advect: bad field list");
-	if (s->cached || s->in_use) return fail(HNS_ERR_INVALID_ARGUMENT, "hns_sim_advect: the sim belongs to a grid's cook cache");
+	const char* who = "hns_sim_advect";
+	HNS_TRY(check_sim(s, who));
 	HNS_TRY(validate_step(voxel_size, dt, 0, false));
 	std::vector<int> which;
-	if (n_names < 0) {
-		for (size_t i = 0; i < s->names.size(); ++i) which.push_back((int)i);
-	}
-	for (int i = 0; i < n_names; ++i) {
-		const int k = names[i] ? s->find(names[i]) : -1;
-		if (k < 0) {
-			set_error("hns_sim_advect: no float field named '%s' in this sim", names[i] ? names[i] : "?");
-			return HNS_ERR_INVALID_ARGUMENT;
-		}
-		if (std::find(which.begin(), which.end(), k) != which.end()) {
-			set_error("hns_sim_advect: field '%s' is listed twice", names[i]);
-			return HNS_ERR_INVALID_ARGUMENT;
-		}
-		which.push_back(k);
-	}
+	HNS_TRY(sim_fields(who, "names", s, n_names, names_at(names), nullptr, true, which));
 	if (s->n == 0) return HNS_OK;
 	const float inv_dx = 1.0f / voxel_size;
 	std::vector<const float*> ins;

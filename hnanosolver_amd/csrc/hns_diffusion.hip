@@ -234,26 +234,12 @@ struct hns_diffusion {
 extern "C" {
 
 hns_diffusion* hns_diffusion_create(int* err) {
-	auto out = [&](int rc) {
-		if (err) *err = rc;
-		return (hns_diffusion*)nullptr;
-	};
-	if (hns_device_count() == 0) return out(fail(HNS_ERR_NO_DEVICE, "hns_diffusion_create: no HIP device (there is no CPU fallback)"));
-	int dev = -1;
-	if (hipGetDevice(&dev) != hipSuccess) return out(fail(HNS_ERR_HIP, "hns_diffusion_create: no current HIP device"));
-	hns_diffusion* o = new hns_diffusion;
-	o->device = dev;
-	if (err) *err = HNS_OK;
-	return o;
+	return make_object<hns_diffusion>("hns_diffusion_create", err, false, nullptr, 0, "", [](hns_diffusion*) { return (int)HNS_OK; });
 }
 
 void hns_diffusion_destroy(hns_diffusion* o) { delete o; }
 
-int hns_diffusion_set_stream(hns_diffusion* o, void* hip_stream) {
-	if (!o) return refuse("hns_diffusion_set_stream", "null diffusion");
-	o->stream = (hipStream_t)hip_stream;
-	return HNS_OK;
-}
+int hns_diffusion_set_stream(hns_diffusion* o, void* hip_stream) { return set_object_stream(o, hip_stream, "hns_diffusion_set_stream", "null diffusion"); }
 
 int hns_diffusion_schedule_host(float coefficient, float dt, float voxel_size, int iterations, hns_diffusion_schedule* out) {
 	const char* who = "hns_diffusion_schedule_host";
@@ -271,19 +257,8 @@ int hns_diffusion_apply(hns_diffusion* o, hns_sim* s, float dt, float voxel_size
 	if (int rc = check_diffusion_numbers(who, dt, voxel_size, sp, terms, n_terms)) return rc;
 	if (!o) return refuse(who, "null diffusion");
 	if (int rc = check_sim(s, who)) return rc;
-	int field[kDiffMaxTerms];
-	for (int k = 0; k < n_terms; ++k) {
-		field[k] = s->find(terms[k].name);
-		if (field[k] < 0 || !strcmp(terms[k].name, "collision_sdf")) {
-			set_error(field[k] < 0 ? "%s: terms: no float field named '%s' in this sim" : "%s: terms: '%s' decides what is solid and is not diffused", who, terms[k].name);
-			return HNS_ERR_INVALID_ARGUMENT;
-		}
-		for (int j = 0; j < k; ++j)
-			if (field[j] == field[k]) {
-				set_error("%s: terms: '%s' is listed twice", who, terms[k].name);
-				return HNS_ERR_INVALID_ARGUMENT;
-			}
-	}
+	std::vector<int> field;
+	HNS_TRY(sim_fields(who, "terms", s, n_terms, [&](int k) { return terms[k].name; }, "decides what is solid and is not diffused", false, field));
 	const int i_sdf = sp->collide ? s->find("collision_sdf") : -1;
 	if (sp->collide && i_sdf < 0) return refuse(who, "collide: no float field named 'collision_sdf' in this sim");
 	// the terms that run: a == +0 (coefficient 0 or dt 0) is skipped, neither read nor written
@@ -298,12 +273,10 @@ int hns_diffusion_apply(hns_diffusion* o, hns_sim* s, float dt, float voxel_size
 	const bool has_vel = !which.empty();
 	for (int k = 0; k < n_terms; ++k) add(terms[k].coefficient, field[k]);
 	if (which.empty()) return HNS_OK;
-	hns_grid* g = s->grid;
-	if (int rc = check_grid(g, who)) return rc;
-	if (g->device != o->device) return refuse(who, "the sim's grid and the diffusion object live on different HIP devices");
+	hns_grid* g;
+	HNS_TRY(sim_grid(who, s, o->device, "diffusion object", true, &g));
 	if (g->first_active != 0 || g->n_active != (uint64_t)g->topo.n_leaves) return refuse(who, "the grid's launch range is not the whole grid");
 	if (g->n_active == 0) return HNS_OK;
-	if (s->n != 512 * (uint64_t)g->topo.n_leaves) return fail(HNS_ERR_RUNTIME, "hns_diffusion_apply: the sim's buffers are not its grid's size");
 	// scratch: of the velocity adv and tmp (the look-ahead memo in adv goes with the forget below), of a float field its own nxt and one pooled array
 	const size_t n_float = which.size() - (has_vel ? 1 : 0), unit = sim_unit(s->n);
 	unsigned char *lo = nullptr, *hi = nullptr;

@@ -108,27 +108,13 @@ struct hns_point_motion {
 extern "C" {
 
 hns_point_motion* hns_point_motion_create(uint64_t capacity, int* err) {
-	const char* who = "hns_point_motion_create";
-	auto out = [&](int rc) {
-		if (err) *err = rc;
-		return (hns_point_motion*)nullptr;
-	};
-	if (capacity > kMaxPoints) return out(refuse(who, "capacity is above 2^31 - 1"));
-	if (hns_device_count() == 0) return out(fail(HNS_ERR_NO_DEVICE, "hns_point_motion_create: no HIP device (there is no CPU fallback)"));
-	int dev = -1;
-	if (hipGetDevice(&dev) != hipSuccess) return out(fail(HNS_ERR_HIP, "hns_point_motion_create: no current HIP device"));
-	hns_point_motion* o = new hns_point_motion;
-	o->device = dev, o->capacity = capacity;
-	const size_t cap = (size_t)std::max<uint64_t>(capacity, 1);
-	const int rc = carve(o->arena, dev, [&](const Slice& slice) {
-		slice(o->xyz, 12 * cap), slice(o->vel, 12 * cap), slice(o->age, 4 * cap), slice(o->status, cap), slice(o->hit, cap);
+	return make_object<hns_point_motion>("hns_point_motion_create", err, false, nullptr, capacity, "", [&](hns_point_motion* o) {
+		o->capacity = capacity;
+		const size_t cap = (size_t)std::max<uint64_t>(capacity, 1);
+		return carve(o->arena, o->device, [&](const Slice& slice) {
+			slice(o->xyz, 12 * cap), slice(o->vel, 12 * cap), slice(o->age, 4 * cap), slice(o->status, cap), slice(o->hit, cap);
+		});
 	});
-	if (rc != HNS_OK) {
-		delete o;
-		return out(rc);
-	}
-	if (err) *err = HNS_OK;
-	return o;
 }
 
 void hns_point_motion_destroy(hns_point_motion* o) {
@@ -136,11 +122,7 @@ void hns_point_motion_destroy(hns_point_motion* o) {
 	delete o;  // (its block goes back to the pool, which waits for the device first)
 }
 
-int hns_point_motion_set_stream(hns_point_motion* o, void* hip_stream) {
-	if (!o) return refuse("hns_point_motion_set_stream", "null point motion");
-	o->stream = (hipStream_t)hip_stream;
-	return HNS_OK;
-}
+int hns_point_motion_set_stream(hns_point_motion* o, void* hip_stream) { return set_object_stream(o, hip_stream, "hns_point_motion_set_stream", "null point motion"); }
 
 int hns_point_motion_get(hns_point_motion* o, hns_point_motion_info* info) {
 	if (!o) return refuse("hns_point_motion_get", "null point motion");
@@ -168,17 +150,13 @@ int hns_point_motion_step(hns_point_motion* o, hns_sim* s, uint64_t n, float dt,
 	if (!(sp->max_age > 0.0f)) return refuse(who, "max_age must be positive (+inf: no point expires)");
 	if (int rc = check_push_numbers(who, sp->threshold, sp->skin, sp->iterations)) return rc;
 	if (!o) return refuse(who, "null point motion");
-	if (n > o->capacity) {
-		set_error("%s: n %llu is above the capacity %llu", who, (unsigned long long)n, (unsigned long long)o->capacity);
-		return HNS_ERR_INVALID_ARGUMENT;
-	}
+	HNS_TRY(check_capacity(who, n, o->capacity));
 	if (int rc = check_sim(s, who)) return rc;
 	const int f = sp->mode == HNS_MOTION_FREE ? -1 : s->find("collision_sdf");
 	if (sp->mode != HNS_MOTION_FREE && f < 0) return refuse(who, "no float field named 'collision_sdf' in this sim (mode free needs none)");
 	if (n == 0) return HNS_OK;
-	hns_grid* g = s->grid;
-	if (int rc = check_grid(g, who)) return rc;
-	if (g->device != o->device) return refuse(who, "the sim's grid and the point motion live on different HIP devices");
+	hns_grid* g;
+	HNS_TRY(sim_grid(who, s, o->device, "point motion", false, &g));  // (not sized: the kernel addresses the sim's buffers through the grid's tables, point by point)
 	MotionDev d;
 	d.mode = sp->mode, d.iterations = sp->iterations, d.empty = g->topo.n_leaves == 0;
 	d.inv_dx = inv_dx;

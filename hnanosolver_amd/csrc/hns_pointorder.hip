@@ -277,13 +277,7 @@ namespace {  // (struct hns_point_order and check_order: hns_points.hpp, shared 
 template <bool SCATTER>
 int move_rows(const hns_point_order* o, const void* d_src, void* d_dst, int row_bytes, const char* who) {
 	HNS_TRY(check_order(o, who));
-	if (!o->sorted) return refuse(who, "no sort has run on this object");
-	if (row_bytes < 4 || row_bytes > 64 || row_bytes % 4) {
-		set_error("%s: row_bytes %d (a multiple of 4 in 4 .. 64)", who, row_bytes);
-		return HNS_ERR_INVALID_ARGUMENT;
-	}
-	if (o->n && (!d_src || !d_dst)) return refuse(who, "null d_src or d_dst");
-	if (o->n && d_src == d_dst) return refuse(who, "d_src and d_dst are the same buffer");
+	HNS_TRY(check_rows(who, o->sorted, "sort", o->n, d_src, d_dst, row_bytes));
 	if (!o->n) return HNS_OK;
 	hipLaunchKernelGGL((k_order_rows<SCATTER>), dim3((unsigned)((o->n + kOrderBlock - 1) / kOrderBlock)), dim3(kOrderBlock), 0, o->stream, o->perm, (const unsigned*)d_src,
 	                   (unsigned*)d_dst, (unsigned)o->n, (unsigned)(row_bytes / 4));
@@ -296,30 +290,16 @@ extern "C" {
 
 hns_point_order* hns_point_order_create(hns_grid* g, uint64_t capacity, int* err) {
 	const char* who = "hns_point_order_create";
-	auto out = [&](int rc) {
-		if (err) *err = rc;
-		return (hns_point_order*)nullptr;
-	};
-	if (!g) return out(refuse(who, "null grid"));
-	if (capacity > kMaxPoints) return out(refuse(who, "capacity is above 2^31 - 1"));
-	if (hns_device_count() == 0) return out(fail(HNS_ERR_NO_DEVICE, "hns_point_order_create: no HIP device (there is no CPU fallback; hns_grid_sort_points is the host's)"));
-	if (!g->on_device) return out(refuse(who, "the grid is HNS_GRID_HOST_ONLY: it has no device tables"));
-	const uint64_t L = (uint64_t)g->topo.n_leaves;
-	if ((L + 2) * 512 > (uint64_t(1) << 32)) return out(refuse(who, "the grid's voxel keys do not fit 32 bits ((leaves + 2) * 512 > 2^32)"));
-	DeviceScope on(g->device);
-	hns_point_order* o = new hns_point_order;
-	o->grid = g, o->device = g->device, o->capacity = capacity, o->n_leaves = L;
-	const size_t cap = (size_t)std::max<uint64_t>(capacity, 1), tiles = order_tiles(cap);
-	const int rc = carve(o->arena, g->device, [&](const Slice& slice) {
-		slice(o->perm, 4 * cap), slice(o->keys, 4 * cap), slice(o->ka, 4 * cap), slice(o->ia, 4 * cap), slice(o->kb, 4 * cap), slice(o->ib, 4 * cap);
-		slice(o->leaf_start, 4 * (size_t)(L + 3)), slice(o->hist, 4 * (size_t)kRadix * tiles), slice(o->total, 4 * (size_t)kRadix);
+	return make_object<hns_point_order>(who, err, true, g, capacity, "; hns_grid_sort_points is the host's", [&](hns_point_order* o) {
+		const uint64_t L = (uint64_t)g->topo.n_leaves;
+		if ((L + 2) * 512 > (uint64_t(1) << 32)) return refuse(who, "the grid's voxel keys do not fit 32 bits ((leaves + 2) * 512 > 2^32)");
+		o->grid = g, o->capacity = capacity, o->n_leaves = L;
+		const size_t cap = (size_t)std::max<uint64_t>(capacity, 1), tiles = order_tiles(cap);
+		return carve(o->arena, g->device, [&](const Slice& slice) {
+			slice(o->perm, 4 * cap), slice(o->keys, 4 * cap), slice(o->ka, 4 * cap), slice(o->ia, 4 * cap), slice(o->kb, 4 * cap), slice(o->ib, 4 * cap);
+			slice(o->leaf_start, 4 * (size_t)(L + 3)), slice(o->hist, 4 * (size_t)kRadix * tiles), slice(o->total, 4 * (size_t)kRadix);
+		});
 	});
-	if (rc != HNS_OK) {
-		delete o;
-		return out(rc);
-	}
-	if (err) *err = HNS_OK;
-	return o;
 }
 
 void hns_point_order_destroy(hns_point_order* o) {
@@ -327,20 +307,13 @@ void hns_point_order_destroy(hns_point_order* o) {
 	delete o;  // (its two blocks go back to the pool, which waits for the device first)
 }
 
-int hns_point_order_set_stream(hns_point_order* o, void* hip_stream) {
-	if (!o) return refuse("hns_point_order_set_stream", "null point order");
-	o->stream = (hipStream_t)hip_stream;
-	return HNS_OK;
-}
+int hns_point_order_set_stream(hns_point_order* o, void* hip_stream) { return set_object_stream(o, hip_stream, "hns_point_order_set_stream", "null point order"); }
 
 int hns_point_order_sort(hns_point_order* o, const float* d_xyz, uint64_t n, int level) {
 	const char* who = "hns_point_order_sort";
 	HNS_TRY(check_order(o, who));
 	if (n > kMaxPoints) return refuse(who, "n is above 2^31 - 1");
-	if (n > o->capacity) {
-		set_error("%s: n %llu is above the capacity %llu", who, (unsigned long long)n, (unsigned long long)o->capacity);
-		return HNS_ERR_INVALID_ARGUMENT;
-	}
+	HNS_TRY(check_capacity(who, n, o->capacity));
 	if (level != 0 && level != 1) {
 		set_error("%s: level %d (0: by leaf, 1: by voxel)", who, level);
 		return HNS_ERR_INVALID_ARGUMENT;

@@ -150,24 +150,9 @@ int hns_dev_trace_points(hns_grid* g, const float* vel3, float* xyz, uint64_t n,
 int hns_sim_sample_points(hns_sim* s, const char* const* names, int n_names, int with_velocity, const float* xyz, uint64_t n, float* const* out, void* stream) {
 	const char* who = "hns_sim_sample_points";
 	if (int rc = check_sim(s, who)) return rc;
-	if (n_names < -1) return refuse(who, "n_names is below -1");
-	if (n_names > 0 && !names) return refuse(who, "names is null");
 	std::vector<const float*> fields;
 	std::vector<int> ncomp, which;
-	if (n_names < 0)
-		for (size_t i = 0; i < s->names.size(); ++i) which.push_back((int)i);
-	for (int i = 0; i < n_names; ++i) {
-		const int k = names[i] ? s->find(names[i]) : -1;
-		if (k < 0) {
-			set_error("%s: names[%d]: no float field named '%s' in this sim", who, i, names[i] ? names[i] : "?");
-			return HNS_ERR_INVALID_ARGUMENT;
-		}
-		if (std::find(which.begin(), which.end(), k) != which.end()) {
-			set_error("%s: names[%d]: field '%s' is listed twice", who, i, names[i]);
-			return HNS_ERR_INVALID_ARGUMENT;
-		}
-		which.push_back(k);
-	}
+	HNS_TRY(sim_fields(who, "names", s, n_names, names_at(names), nullptr, true, which));
 	for (int k : which) fields.push_back(s->cur[k]), ncomp.push_back(1);
 	if (with_velocity) fields.push_back(s->vel), ncomp.push_back(3);
 	if (fields.empty()) return refuse(who, "no field to sample (no names and with_velocity = 0)");

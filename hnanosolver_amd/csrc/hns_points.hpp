@@ -8,6 +8,7 @@
 #include "hns_device.hpp"
 #include "hns_radial.hpp"
 #include "hns_seed.hpp"
+#include "hns_simcall.hpp"  // refuse, check_sim, kMaxPoints and the rest of a call's host preamble
 
 namespace hns {
 
@@ -198,28 +199,6 @@ std::vector<SplatChannels> splat_passes(const std::vector<SplatChannel>& all, co
 int sim_splat_fields(const char* who, const hns_sim* s, const char* const* names, int n_names, const float* velocity_values, const float* const* values,
                      std::vector<float*>& fields, std::vector<const float*>& vals, std::vector<int>& ncomp, std::vector<int>& which);
 void sim_splat_wrote(hns_sim* s, const std::vector<int>& which, bool velocity);
-
-// ---- launcher plumbing of the point calls ----
-
-inline int refuse(const char* who, const char* what) {
-	set_error("%s: %s", who, what);
-	return HNS_ERR_INVALID_ARGUMENT;
-}
-
-constexpr uint64_t kMaxPoints = 0x7fffffffull;
-
-// a sim the point calls may use: not null (without a device there is none to pass: hns_sim_create refused, and the caller learns why here too), not lent to a cook cache
-inline int check_sim(const hns_sim* s, const char* who) {
-	if (!s) {
-		if (hns_device_count() == 0) {
-			set_error("%s: no HIP device (there is no CPU fallback)", who);
-			return HNS_ERR_NO_DEVICE;
-		}
-		return refuse(who, "null sim");
-	}
-	if (s->cached || s->in_use) return refuse(who, "the sim belongs to a grid's cook cache");
-	return HNS_OK;
-}
 
 }  // namespace hns
 

@@ -290,29 +290,16 @@ extern "C" {
 
 hns_point_population* hns_point_population_create(hns_grid* g, uint64_t capacity, int* err) {
 	const char* who = "hns_point_population_create";
-	auto out = [&](int rc) {
-		if (err) *err = rc;
-		return (hns_point_population*)nullptr;
-	};
-	if (!g) return out(refuse(who, "null grid"));
-	if (capacity > kMaxPoints) return out(refuse(who, "capacity is above 2^31 - 1"));
-	if (hns_device_count() == 0) return out(fail(HNS_ERR_NO_DEVICE, "hns_point_population_create: no HIP device (there is no CPU fallback; hns_grid_birth_points is the host's)"));
-	if (!g->on_device) return out(refuse(who, "the grid is HNS_GRID_HOST_ONLY: it has no device tables"));
-	const uint64_t L = (uint64_t)g->topo.n_leaves;
-	if (L * 512 > (uint64_t(1) << 32)) return out(refuse(who, "the grid's voxel indices do not fit 32 bits (leaves * 512 > 2^32)"));
-	DeviceScope on(g->device);
-	hns_point_population* o = new hns_point_population;
-	o->grid = g, o->device = g->device, o->capacity = capacity, o->n_leaves = L;
-	const size_t cap = (size_t)std::max<uint64_t>(capacity, 1), tiles = std::max<size_t>(pop_tiles(std::max<uint64_t>(capacity, L * 512)), 1);
-	int rc = carve(o->arena, g->device, [&](const Slice& slice) { slice(o->slot, 4 * cap), slice(o->table, 4 * tiles), slice(o->counters, 16); });
-	if (rc == HNS_OK && (hipMemsetAsync(o->counters, 0, 16, nullptr) != hipSuccess || hipStreamSynchronize(nullptr) != hipSuccess))
-		rc = fail(HNS_ERR_HIP, "hns_point_population_create: clearing the counters failed");
-	if (rc != HNS_OK) {
-		delete o;
-		return out(rc);
-	}
-	if (err) *err = HNS_OK;
-	return o;
+	return make_object<hns_point_population>(who, err, true, g, capacity, "; hns_grid_birth_points is the host's", [&](hns_point_population* o) {
+		const uint64_t L = (uint64_t)g->topo.n_leaves;
+		if (L * 512 > (uint64_t(1) << 32)) return refuse(who, "the grid's voxel indices do not fit 32 bits (leaves * 512 > 2^32)");
+		o->grid = g, o->capacity = capacity, o->n_leaves = L;
+		const size_t cap = (size_t)std::max<uint64_t>(capacity, 1), tiles = std::max<size_t>(pop_tiles(std::max<uint64_t>(capacity, L * 512)), 1);
+		HNS_TRY(carve(o->arena, g->device, [&](const Slice& slice) { slice(o->slot, 4 * cap), slice(o->table, 4 * tiles), slice(o->counters, 16); }));
+		if (hipMemsetAsync(o->counters, 0, 16, nullptr) != hipSuccess || hipStreamSynchronize(nullptr) != hipSuccess)
+			return fail(HNS_ERR_HIP, "hns_point_population_create: clearing the counters failed");
+		return (int)HNS_OK;
+	});
 }
 
 void hns_point_population_destroy(hns_point_population* o) {
@@ -321,9 +308,7 @@ void hns_point_population_destroy(hns_point_population* o) {
 }
 
 int hns_point_population_set_stream(hns_point_population* o, void* hip_stream) {
-	if (!o) return refuse("hns_point_population_set_stream", "null point population");
-	o->stream = (hipStream_t)hip_stream;
-	return HNS_OK;
+	return set_object_stream(o, hip_stream, "hns_point_population_set_stream", "null point population");
 }
 
 int hns_point_population_set_live(hns_point_population* o, uint64_t n) {
@@ -338,10 +323,7 @@ int hns_point_population_select(hns_point_population* o, const unsigned char* d_
 	const char* who = "hns_point_population_select";
 	HNS_TRY(check_population(o, who));
 	if (n > kMaxPoints) return refuse(who, "n is above 2^31 - 1");
-	if (n > o->capacity) {
-		set_error("%s: n %llu is above the capacity %llu", who, (unsigned long long)n, (unsigned long long)o->capacity);
-		return HNS_ERR_INVALID_ARGUMENT;
-	}
+	HNS_TRY(check_capacity(who, n, o->capacity));
 	if (at_least < 1 || at_least > 255) {
 		set_error("%s: at_least %d (1 .. 255)", who, at_least);
 		return HNS_ERR_INVALID_ARGUMENT;
@@ -364,13 +346,7 @@ int hns_point_population_select(hns_point_population* o, const unsigned char* d_
 int hns_point_population_compact(const hns_point_population* o, const void* d_src, void* d_dst, int row_bytes, const uint32_t* fill_word) {
 	const char* who = "hns_point_population_compact";
 	HNS_TRY(check_population(o, who));
-	if (!o->selected) return refuse(who, "no select has run on this object");
-	if (row_bytes < 4 || row_bytes > 64 || row_bytes % 4) {
-		set_error("%s: row_bytes %d (a multiple of 4 in 4 .. 64)", who, row_bytes);
-		return HNS_ERR_INVALID_ARGUMENT;
-	}
-	if (o->n && (!d_src || !d_dst)) return refuse(who, "null d_src or d_dst");
-	if (o->n && d_src == d_dst) return refuse(who, "d_src and d_dst are the same buffer");
+	HNS_TRY(check_rows(who, o->selected, "select", o->n, d_src, d_dst, row_bytes));
 	if (!o->n) return HNS_OK;
 	const dim3 grid((unsigned)((o->n + kPopBlock - 1) / kPopBlock)), block(kPopBlock);
 	const unsigned W = (unsigned)(row_bytes / 4);

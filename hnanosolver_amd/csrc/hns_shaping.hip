@@ -91,26 +91,12 @@ struct hns_shaping {
 extern "C" {
 
 hns_shaping* hns_shaping_create(int* err) {
-	auto out = [&](int rc) {
-		if (err) *err = rc;
-		return (hns_shaping*)nullptr;
-	};
-	if (hns_device_count() == 0) return out(fail(HNS_ERR_NO_DEVICE, "hns_shaping_create: no HIP device (there is no CPU fallback)"));
-	int dev = -1;
-	if (hipGetDevice(&dev) != hipSuccess) return out(fail(HNS_ERR_HIP, "hns_shaping_create: no current HIP device"));
-	hns_shaping* o = new hns_shaping;
-	o->device = dev;
-	if (err) *err = HNS_OK;
-	return o;
+	return make_object<hns_shaping>("hns_shaping_create", err, false, nullptr, 0, "", [](hns_shaping*) { return (int)HNS_OK; });
 }
 
 void hns_shaping_destroy(hns_shaping* o) { delete o; }
 
-int hns_shaping_set_stream(hns_shaping* o, void* hip_stream) {
-	if (!o) return refuse("hns_shaping_set_stream", "null shaping");
-	o->stream = (hipStream_t)hip_stream;
-	return HNS_OK;
-}
+int hns_shaping_set_stream(hns_shaping* o, void* hip_stream) { return set_object_stream(o, hip_stream, "hns_shaping_set_stream", "null shaping"); }
 
 int hns_shaping_apply(hns_shaping* o, hns_sim* s, float dt, const hns_turbulence_spec* tb, const hns_decay_spec* decays, int n_decays) {
 	const char* who = "hns_shaping_apply";
@@ -127,26 +113,13 @@ int hns_shaping_apply(hns_shaping* o, hns_sim* s, float dt, const hns_turbulence
 			return HNS_ERR_INVALID_ARGUMENT;
 		}
 	}
-	int field[kShapeMaxDecays];
-	for (int k = 0; k < n_decays; ++k) {
-		field[k] = s->find(decays[k].name);
-		if (field[k] < 0 || !strcmp(decays[k].name, "collision_sdf")) {
-			set_error(field[k] < 0 ? "%s: decays: no float field named '%s' in this sim" : "%s: decays: '%s' may be the control, not a decayed field", who, decays[k].name);
-			return HNS_ERR_INVALID_ARGUMENT;
-		}
-		for (int j = 0; j < k; ++j)
-			if (field[j] == field[k]) {
-				set_error("%s: decays: '%s' is listed twice", who, decays[k].name);
-				return HNS_ERR_INVALID_ARGUMENT;
-			}
-	}
+	std::vector<int> field;
+	HNS_TRY(sim_fields(who, "decays", s, n_decays, [&](int k) { return decays[k].name; }, "may be the control, not a decayed field", false, field));
 	const bool turbulent = tb && tb->amplitude != 0.0f;
 	if (!turbulent && n_decays == 0) return HNS_OK;
-	hns_grid* g = s->grid;
-	if (int rc = check_grid(g, who)) return rc;
-	if (g->device != o->device) return refuse(who, "the sim's grid and the shaping object live on different HIP devices");
+	hns_grid* g;
+	HNS_TRY(sim_grid(who, s, o->device, "shaping object", true, &g));
 	if (g->n_active == 0) return HNS_OK;
-	if (s->n != 512 * (uint64_t)g->topo.n_leaves) return fail(HNS_ERR_RUNTIME, "hns_shaping_apply: the sim's buffers are not its grid's size");
 	if (turbulent) {
 		noise_octaves(*tb, d.oct);
 		d.octaves = tb->octaves;

@@ -217,21 +217,8 @@ int check_splat_pointers(const char* who, float* const* fields, int n_fields, co
 // float fields the call writes
 int sim_splat_fields(const char* who, const hns_sim* s, const char* const* names, int n_names, const float* velocity_values, const float* const* values,
                      std::vector<float*>& fields, std::vector<const float*>& vals, std::vector<int>& ncomp, std::vector<int>& which) {
-	if (n_names < 0) return refuse(who, "n_names is negative");
-	if (n_names > 0 && (!names || !values)) return refuse(who, "null list (names or values)");
-	for (int i = 0; i < n_names; ++i) {
-		const int k = names[i] ? s->find(names[i]) : -1;
-		if (k < 0) {
-			set_error("%s: names[%d]: no float field named '%s' in this sim", who, i, names[i] ? names[i] : "?");
-			return HNS_ERR_INVALID_ARGUMENT;
-		}
-		if (s->names[(size_t)k] == "collision_sdf") return invalid("%s: names[%d]: collision_sdf takes no point values (it comes from the collision input)", who, i);
-		if (std::find(which.begin(), which.end(), k) != which.end()) {
-			set_error("%s: names[%d]: field '%s' is listed twice", who, i, names[i]);
-			return HNS_ERR_INVALID_ARGUMENT;
-		}
-		which.push_back(k);
-	}
+	if (n_names > 0 && !values) return refuse(who, "null list (values)");
+	HNS_TRY(sim_fields(who, "names", s, n_names, names_at(names), "takes no point values (it comes from the collision input)", false, which));
 	for (size_t i = 0; i < which.size(); ++i) fields.push_back(s->cur[(size_t)which[i]]), vals.push_back(values[i]), ncomp.push_back(1);
 	if (velocity_values) fields.push_back(s->vel), vals.push_back(velocity_values), ncomp.push_back(3);
 	if (fields.empty()) return refuse(who, "nothing to write (no names and velocity_values is null)");

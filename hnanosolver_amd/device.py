@@ -38,6 +38,86 @@ def current_stream() -> int:
     return int(_torch().cuda.current_stream().cuda_stream)
 
 
+def _stream(stream: Optional[int]) -> int:
+    """a hipStream_t as an integer; None: torch's current stream"""
+    return current_stream() if stream is None else int(stream)
+
+
+def _ptrs(tensors):
+    """the device addresses of `tensors` as a void* array (one entry at the least: there is no empty ctypes array to pass)"""
+    p = [_ptr(t) for t in tensors]
+    return (C.c_void_p * max(1, len(p)))(*p)
+
+
+def _names(names):
+    """`names` as a char* array, likewise"""
+    b = [n.encode() for n in names]
+    return (C.c_char_p * max(1, len(b)))(*b)
+
+
+def _xyz3(what: str, xyz, shape: str = "an (n, 3)") -> None:
+    if xyz.dim() != 2 or xyz.shape[1] != 3 or xyz.dtype != _torch().float32:
+        raise ValueError(f"{what}: xyz must be {shape} float32 tensor")
+
+
+class _Handle:
+    """An object of libhns.so behind ``_ptr``: made by a create call whose last argument is the status, gone with ``close`` -- at the end of a ``with`` block and with the
+    Python object too. _destroy: the name of the library's destroy function. _sim, _made_by: the Sim whose grid the object was made on and the method that made it."""
+
+    _destroy = ""
+    _ptr = 0
+    _sim = None
+    _made_by = ""
+
+    def _create(self, create, *args) -> None:
+        err = C.c_int(0)
+        self._ptr = create(*args, C.byref(err))
+        if not self._ptr:
+            _raise(err.value if err.value < 0 else _lib.HNS_ERR_RUNTIME)
+
+    def _live(self) -> int:
+        name = type(self).__name__
+        if not self._ptr:
+            raise RuntimeError(f"{name}: the object is closed")
+        if self._sim is not None and self._sim.grid is not self.grid:
+            raise RuntimeError(f"{name}: the sim has moved onto another grid (regrid) since {self._made_by} made this object; make a new one on the sim's current grid")
+        return self._ptr
+
+    def close(self) -> None:
+        if self._ptr:
+            getattr(lib, self._destroy)(self._ptr)
+            self._ptr = 0
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _row_move(what: str, n: int, ran: str, src, dst):
+    """The checks of a move of the first `n` rows of src into dst (made here when None) behind the object's last `ran` -> (dst, bytes of a row)"""
+    for name, t in (("src", src), ("dst", dst)):
+        if t is not None and (not t.is_cuda or not t.is_contiguous() or t.dim() < 1):
+            raise TypeError(f"{what}: {name} must be a contiguous tensor of at least one dimension on a HIP device")
+    row_bytes = src.element_size() * int(np.prod(src.shape[1:], dtype=np.int64))
+    if row_bytes % 4 or not 4 <= row_bytes <= 64:
+        raise ValueError(f"{what}: a row of src has {row_bytes} bytes (a multiple of 4 in 4 .. 64)")
+    if dst is None:
+        dst = _torch().empty((n,) + tuple(src.shape[1:]), dtype=src.dtype, device=src.device)
+    if dst.dtype != src.dtype or tuple(dst.shape[1:]) != tuple(src.shape[1:]):
+        raise ValueError(f"{what}: dst rows are not src rows ({tuple(dst.shape[1:])} {dst.dtype} against {tuple(src.shape[1:])} {src.dtype})")
+    if src.shape[0] < n or dst.shape[0] < n:
+        raise ValueError(f"{what}: src has {src.shape[0]} rows and dst {dst.shape[0]}, the last {ran} {n}")
+    return dst, row_bytes
+
+
 def advect_vector(grid: IndexGridHandle, u, out, dt: float, inv_dx: float, sdf=None, has_collision: bool = False):
     _raise(lib.hns_dev_advect_vector(grid.ptr, _ptr(u), _ptr(out), _ptr(sdf), int(has_collision), dt, inv_dx, current_stream()))
     return out
@@ -48,29 +128,23 @@ def advect_scalar(grid: IndexGridHandle, u, src, dst, dt: float, inv_dx: float, 
     return dst
 
 
-def advect_scalars(grid: IndexGridHandle, u, srcs: Sequence, dsts: Sequence, dt: float, inv_dx: float, sdf=None, has_collision: bool = False):
-    n = len(srcs)
-    ins = (C.c_void_p * max(1, n))(*[_ptr(t) for t in srcs])
-    outs = (C.c_void_p * max(1, n))(*[_ptr(t) for t in dsts])
-    _raise(lib.hns_dev_advect_scalars(grid.ptr, _ptr(u), ins, outs, n, _ptr(sdf), int(has_collision), dt, inv_dx, current_stream()))
+def _advect_many(call, grid, u, srcs, dsts, dt, inv_dx, sdf, has_collision):
+    _raise(call(grid.ptr, _ptr(u), _ptrs(srcs), _ptrs(dsts), len(srcs), _ptr(sdf), int(has_collision), dt, inv_dx, current_stream()))
     return dsts
+
+
+def advect_scalars(grid: IndexGridHandle, u, srcs: Sequence, dsts: Sequence, dt: float, inv_dx: float, sdf=None, has_collision: bool = False):
+    return _advect_many(lib.hns_dev_advect_scalars, grid, u, srcs, dsts, dt, inv_dx, sdf, has_collision)
 
 
 def advect_scalar_multi(grid: IndexGridHandle, u, srcs: Sequence, dsts: Sequence, dt: float, inv_dx: float, sdf=None, has_collision: bool = False):
     """advect_scalar of every field of `srcs` with one back-trace (``hns_dev_advect_scalar_multi``): dsts[i] is bit-identical to ``advect_scalar`` of srcs[i]."""
-    n = len(srcs)
-    ins = (C.c_void_p * max(1, n))(*[_ptr(t) for t in srcs])
-    outs = (C.c_void_p * max(1, n))(*[_ptr(t) for t in dsts])
-    _raise(lib.hns_dev_advect_scalar_multi(grid.ptr, _ptr(u), ins, outs, n, _ptr(sdf), int(has_collision), dt, inv_dx, current_stream()))
-    return dsts
+    return _advect_many(lib.hns_dev_advect_scalar_multi, grid, u, srcs, dsts, dt, inv_dx, sdf, has_collision)
 
 
 def advect_scalars_ahead(grid: IndexGridHandle, u, srcs: Sequence, dsts: Sequence, adv_out, dt: float, inv_dx: float):
     """advect_scalars over `srcs` and advect_vector(u) into `adv_out`, one launch (``hns_dev_advect_scalars_ahead``)."""
-    n = len(srcs)
-    ins = (C.c_void_p * max(1, n))(*[_ptr(t) for t in srcs])
-    outs = (C.c_void_p * max(1, n))(*[_ptr(t) for t in dsts])
-    _raise(lib.hns_dev_advect_scalars_ahead(grid.ptr, _ptr(u), ins, outs, n, _ptr(adv_out), dt, inv_dx, current_stream()))
+    _raise(lib.hns_dev_advect_scalars_ahead(grid.ptr, _ptr(u), _ptrs(srcs), _ptrs(dsts), len(srcs), _ptr(adv_out), dt, inv_dx, current_stream()))
     return dsts, adv_out
 
 
@@ -161,9 +235,7 @@ def sample_points(grid: IndexGridHandle, fields: Sequence, xyz, outs: Optional[S
     nc = [_ncomp(f) for f in fields]
     if outs is None:
         outs = [_torch().empty((n, 3) if c == 3 else (n,), dtype=_torch().float32, device=xyz.device) for c in nc]
-    ins = (C.c_void_p * max(1, k))(*[_ptr(t) for t in fields])
-    dst = (C.c_void_p * max(1, k))(*[_ptr(t) for t in outs])
-    _raise(lib.hns_dev_sample_points(grid.ptr, ins, (C.c_int * max(1, k))(*nc), k, _ptr(xyz), n, dst, current_stream()))
+    _raise(lib.hns_dev_sample_points(grid.ptr, _ptrs(fields), (C.c_int * max(1, k))(*nc), k, _ptr(xyz), n, _ptrs(outs), current_stream()))
     return outs
 
 
@@ -223,10 +295,8 @@ def splat_points(grid: IndexGridHandle, fields: Sequence, xyz, values: Sequence,
     and the previous one put back; a radius tensor must stay alive until the call has run."""
     spec = splat_spec(kernel, mode, radius, max_radius, min_weight, pointer=lambda t: _radius_ptr(t, xyz.shape[0]))
     k = len(fields)
-    dst = (C.c_void_p * max(1, k))(*[_ptr(t) for t in fields])
-    src = (C.c_void_p * max(1, k))(*[_ptr(t) for t in values])
     with stored_splat_spec(lib.hns_grid_set_splat_spec, lib.hns_grid_get_splat_spec, grid.ptr, spec):
-        _raise(lib.hns_dev_splat_points(grid.ptr, dst, (C.c_int * max(1, k))(*[_ncomp(f) for f in fields]), k, _ptr(xyz), src, xyz.shape[0], int(log2_quantum),
+        _raise(lib.hns_dev_splat_points(grid.ptr, _ptrs(fields), (C.c_int * max(1, k))(*[_ncomp(f) for f in fields]), k, _ptr(xyz), _ptrs(values), xyz.shape[0], int(log2_quantum),
                                         _byte_ptr(status), _u64_ptr(rejected), current_stream()))
     return fields
 
@@ -265,41 +335,32 @@ class _DeviceWords:
                                          "version": 2}
 
 
-class PointOrder:
+class PointOrder(_Handle):
     """The leaf order of a point set on the device (``hns_point_order``; include/hns.h states the definition): a stable sort of up to `capacity` points by the voxel -- or
     the leaf -- of their cell on `grid`, the per-leaf ranges, and the moves that carry per-point rows through the permutation and back. The point kernels run some five
     times faster on points in this order. Buffers come from the pool of device memory once, here; ``sort``, ``gather`` and ``scatter`` allocate nothing in the library
     and are asynchronous on the stream of the last ``sort``. Holds the grid handle: the grid outlives the object."""
 
+    _destroy, _made_by = "hns_point_order_destroy", "Sim.point_order"
+
     def __init__(self, grid: IndexGridHandle, capacity: int, _sim=None):
         capacity = int(capacity)
         if capacity < 0:
             raise ValueError(f"PointOrder: capacity {capacity} is negative")
-        self.grid, self.capacity, self._sim, self._ptr = grid, capacity, _sim, 0
-        err = C.c_int(0)
-        self._ptr = lib.hns_point_order_create(grid.ptr, capacity, C.byref(err))
-        if not self._ptr:
-            _raise(err.value if err.value < 0 else _lib.HNS_ERR_RUNTIME)
+        self.grid, self.capacity, self._sim = grid, capacity, _sim
+        self._create(lib.hns_point_order_create, grid.ptr, capacity)
         self.n, self.level = 0, None
-
-    def _live(self) -> int:
-        if not self._ptr:
-            raise RuntimeError("PointOrder: the object is closed")
-        if self._sim is not None and self._sim.grid is not self.grid:
-            raise RuntimeError("PointOrder: the sim has moved onto another grid (regrid) since Sim.point_order made this object; make a new one on the sim's current grid")
-        return self._ptr
 
     def sort(self, xyz, level="voxel", stream: Optional[int] = None):
         """Sort the points xyz ((n, 3) float32 device tensor, index space, only read; n <= capacity) by "voxel" or by "leaf". stream: a hipStream_t as an integer, None = torch's
         current stream; this call and every later ``gather`` / ``scatter`` are ordered on it and on nothing else. Returns self; ``perm``, ``keys`` and
         ``leaf_start`` are the results."""
         ptr, lv = self._live(), leafio.sort_level(level)
-        if xyz.dim() != 2 or xyz.shape[1] != 3 or xyz.dtype != _torch().float32:
-            raise ValueError("PointOrder.sort: xyz must be an (n, 3) float32 tensor")
+        _xyz3("PointOrder.sort", xyz)
         n = int(xyz.shape[0])
         if n > self.capacity:
             raise ValueError(f"PointOrder.sort: {n} points are above the capacity {self.capacity}")
-        _raise(lib.hns_point_order_set_stream(ptr, current_stream() if stream is None else int(stream)))
+        _raise(lib.hns_point_order_set_stream(ptr, _stream(stream)))
         _raise(lib.hns_point_order_sort(ptr, _ptr(xyz) if n else 0, n, lv))
         self.n, self.level = n, ("voxel" if lv else "leaf")
         return self
@@ -334,21 +395,10 @@ class PointOrder:
         return self._words(info.leaf_start, info.n_leaves + 3)
 
     def _move(self, call, what, src, dst):
-        ptr, torch = self._live(), _torch()
+        ptr = self._live()
         if self.level is None:
             raise RuntimeError(f"PointOrder.{what}: no sort has run on this object")
-        for name, t in (("src", src), ("dst", dst)):
-            if t is not None and (not t.is_cuda or not t.is_contiguous() or t.dim() < 1):
-                raise TypeError(f"PointOrder.{what}: {name} must be a contiguous tensor of at least one dimension on a HIP device")
-        row_bytes = src.element_size() * int(np.prod(src.shape[1:], dtype=np.int64))
-        if row_bytes % 4 or not 4 <= row_bytes <= 64:
-            raise ValueError(f"PointOrder.{what}: a row of src has {row_bytes} bytes (a multiple of 4 in 4 .. 64)")
-        if dst is None:
-            dst = torch.empty((self.n,) + tuple(src.shape[1:]), dtype=src.dtype, device=src.device)
-        if dst.dtype != src.dtype or tuple(dst.shape[1:]) != tuple(src.shape[1:]):
-            raise ValueError(f"PointOrder.{what}: dst rows are not src rows ({tuple(dst.shape[1:])} {dst.dtype} against {tuple(src.shape[1:])} {src.dtype})")
-        if src.shape[0] < self.n or dst.shape[0] < self.n:
-            raise ValueError(f"PointOrder.{what}: src has {src.shape[0]} rows and dst {dst.shape[0]}, the last sort {self.n}")
+        dst, row_bytes = _row_move(f"PointOrder.{what}", self.n, "sort", src, dst)
         if self.n:
             _raise(call(ptr, src.data_ptr(), dst.data_ptr(), row_bytes))
         return dst
@@ -368,8 +418,7 @@ class PointOrder:
             raise ValueError(f'{what}: rows must be "original" (the arrays the sort saw) or "ranked" (their gather), got {rows!r}')
         if self.level is None:
             raise RuntimeError(f"{what}: no sort has run on this object")
-        if xyz.dim() != 2 or xyz.shape[1] != 3 or xyz.dtype != _torch().float32:
-            raise ValueError(f"{what}: xyz must be an (n, 3) float32 tensor")
+        _xyz3(what, xyz)
         for name, t in [("xyz", xyz), *per_point]:
             if t is not None and t.shape[0] != self.n:
                 raise ValueError(f"{what}: {name} has {t.shape[0]} rows, the last sort {self.n}")
@@ -385,10 +434,8 @@ class PointOrder:
         ptr = self._live()
         spec = splat_spec(kernel, mode, radius, max_radius, min_weight, pointer=lambda t: _radius_ptr(t, self.n))
         k = len(fields)
-        dst = (C.c_void_p * max(1, k))(*[_ptr(t) for t in fields])
-        src = (C.c_void_p * max(1, k))(*[_ptr(t) for t in values])
         with stored_splat_spec(lib.hns_grid_set_splat_spec, lib.hns_grid_get_splat_spec, self.grid.ptr, spec):
-            _raise(lib.hns_point_order_splat(ptr, dst, (C.c_int * max(1, k))(*[_ncomp(f) for f in fields]), k, _ptr(xyz) if self.n else 0, src, r, int(log2_quantum),
+            _raise(lib.hns_point_order_splat(ptr, _ptrs(fields), (C.c_int * max(1, k))(*[_ncomp(f) for f in fields]), k, _ptr(xyz) if self.n else 0, _ptrs(values), r, int(log2_quantum),
                                              _byte_ptr(status), _u64_ptr(rejected)))
         return fields
 
@@ -425,50 +472,31 @@ class PointOrder:
             _raise(lib.hns_point_order_neighbours(ptr, _ptr(xyz), r, float(radius), addr("count"), addr("density"), addr("push")))
         return out
 
-    def close(self) -> None:
-        if self._ptr:
-            lib.hns_point_order_destroy(self._ptr)
-            self._ptr = 0
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 POINT_POPULATION_TILE = 2048        # items -- points of a select, voxels of a birth -- of one tile (hns_population.hip: kPopTile)
 POINT_POPULATION_SCAN_TILES = 1024  # tiles one round of the scan workgroup covers (kPopScanChunk): beyond POINT_POPULATION_TILE * POINT_POPULATION_SCAN_TILES items the scan carries
 
 
-class PointPopulation:
+class PointPopulation(_Handle):
     """Birth and death of points on the device (``hns_point_population``; include/hns.h states the rules): ``select`` turns a flag byte per point into a slot per kept
     point, ``compact`` moves the rows of any attribute array through the slots, ``birth`` makes points from a field -- 0 .. max_per_voxel per voxel --, and the live count
     stays on the device: nothing here waits for the host but ``counts``. A frame loop keeps calling every point kernel with n = capacity; the rows beyond the live count
     hold NaN positions, which those kernels treat as nothing. Buffers come from the pool of device memory once, here. ``select``, ``birth`` and ``set_live`` bind the
     stream they are given (None: torch's current stream); ``compact`` runs on the stream bound last. Holds the grid handle: the grid outlives the object."""
 
+    _destroy, _made_by = "hns_point_population_destroy", "Sim.point_population"
+
     def __init__(self, grid: IndexGridHandle, capacity: int, _sim=None):
         capacity = int(capacity)
         if capacity < 0:
             raise ValueError(f"PointPopulation: capacity {capacity} is negative")
-        self.grid, self.capacity, self._sim, self._ptr = grid, capacity, _sim, 0
-        err = C.c_int(0)
-        self._ptr = lib.hns_point_population_create(grid.ptr, capacity, C.byref(err))
-        if not self._ptr:
-            _raise(err.value if err.value < 0 else _lib.HNS_ERR_RUNTIME)
+        self.grid, self.capacity, self._sim = grid, capacity, _sim
+        self._create(lib.hns_point_population_create, grid.ptr, capacity)
         self.n = None  # of the last select
-
-    def _live(self) -> int:
-        if not self._ptr:
-            raise RuntimeError("PointPopulation: the object is closed")
-        if self._sim is not None and self._sim.grid is not self.grid:
-            raise RuntimeError("PointPopulation: the sim has moved onto another grid (regrid) since Sim.point_population made this object; make a new one on the sim's current grid")
-        return self._ptr
 
     def _bind(self, stream) -> int:
         ptr = self._live()
-        _raise(lib.hns_point_population_set_stream(ptr, current_stream() if stream is None else int(stream)))
+        _raise(lib.hns_point_population_set_stream(ptr, _stream(stream)))
         return ptr
 
     def set_live(self, n: int, stream: Optional[int] = None):
@@ -502,21 +530,10 @@ class PointPopulation:
         """dst row slot[i] = src row i for every point the last select kept -> dst (made here, n rows, when None). Rows are src.shape[1:], 4 .. 64 bytes in whole 32-bit
         words. fill: None -- the rows of dst from the live count on keep their bytes --, or a float (its float32 bits) or an int (a 32-bit word) that every word of the rows
         live .. n - 1 becomes: ``fill=float("nan")`` for positions. Rows of a longer dst beyond n are never touched. On the stream bound last."""
-        ptr, torch = self._live(), _torch()
+        ptr = self._live()
         if self.n is None:
             raise RuntimeError("PointPopulation.compact: no select has run on this object")
-        for name, t in (("src", src), ("dst", dst)):
-            if t is not None and (not t.is_cuda or not t.is_contiguous() or t.dim() < 1):
-                raise TypeError(f"PointPopulation.compact: {name} must be a contiguous tensor of at least one dimension on a HIP device")
-        row_bytes = src.element_size() * int(np.prod(src.shape[1:], dtype=np.int64))
-        if row_bytes % 4 or not 4 <= row_bytes <= 64:
-            raise ValueError(f"PointPopulation.compact: a row of src has {row_bytes} bytes (a multiple of 4 in 4 .. 64)")
-        if dst is None:
-            dst = torch.empty((self.n,) + tuple(src.shape[1:]), dtype=src.dtype, device=src.device)
-        if dst.dtype != src.dtype or tuple(dst.shape[1:]) != tuple(src.shape[1:]):
-            raise ValueError(f"PointPopulation.compact: dst rows are not src rows ({tuple(dst.shape[1:])} {dst.dtype} against {tuple(src.shape[1:])} {src.dtype})")
-        if src.shape[0] < self.n or dst.shape[0] < self.n:
-            raise ValueError(f"PointPopulation.compact: src has {src.shape[0]} rows and dst {dst.shape[0]}, the last select {self.n}")
+        dst, row_bytes = _row_move("PointPopulation.compact", self.n, "select", src, dst)
         word = None
         if fill is not None:
             bits = int(np.float32(fill).view(np.uint32)) if isinstance(fill, (float, np.floating)) else int(fill) & 0xFFFFFFFF
@@ -527,11 +544,9 @@ class PointPopulation:
 
     @staticmethod
     def _birth_rows(what, xyz, voxel):
-        torch = _torch()
-        if xyz.dim() != 2 or xyz.shape[1] != 3 or xyz.dtype != torch.float32:
-            raise ValueError(f"{what}: xyz must be a (rows, 3) float32 tensor")
+        _xyz3(what, xyz, "a (rows, 3)")
         rows = int(xyz.shape[0])
-        if voxel is not None and (voxel.dtype != torch.int32 or tuple(voxel.shape) != (rows,)):
+        if voxel is not None and (voxel.dtype != _torch().int32 or tuple(voxel.shape) != (rows,)):
             raise ValueError(f"{what}: voxel must be an int32 tensor of one word per row of xyz")
         return rows, (_ptr(xyz) if rows else 0), (_ptr(voxel) if voxel is not None and rows else 0)
 
@@ -553,23 +568,12 @@ class PointPopulation:
         _raise(lib.hns_point_population_counts(self._live(), C.byref(live), C.byref(wanted)))
         return int(live.value), int(wanted.value)
 
-    def close(self) -> None:
-        if self._ptr:
-            lib.hns_point_population_destroy(self._ptr)
-            self._ptr = 0
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 MOTION_MODES = {"free": _lib.HNS_MOTION_FREE, "stick": _lib.HNS_MOTION_STICK, "bounce": _lib.HNS_MOTION_BOUNCE, "kill": _lib.HNS_MOTION_KILL}
 MOTION_HIT = {"bounced": 1, "reverted": 2, "killed": 4, "started_inside": 8, "reflected": 16}  # the bits of PointMotion.hit
 
 
-class PointMotion:
+class PointMotion(_Handle):
     """Points with a velocity of their own on the device (``hns_point_motion``; include/hns.h states the arithmetic line by line): embers, sparks, soot, debris. The object
     OWNS the per-point state -- ``xyz`` [capacity, 3] (index space), ``vel`` [capacity, 3] (the units of the sim's velocity), ``age``, ``status`` and ``hit`` [capacity] --
     in one block of the pool of device memory; the attributes are torch views of the library's arrays, valid until ``close``: fill xyz, vel and age through them.
@@ -577,20 +581,14 @@ class PointMotion:
     step uses the grid the sim has at that call, so the object survives regrids. A row with a non-finite xyz (``PointPopulation``'s rows beyond the live count) is not
     stepped."""
 
+    _destroy = "hns_point_motion_destroy"
+
     def __init__(self, capacity: int):
         capacity = int(capacity)
         if capacity < 0:
             raise ValueError(f"PointMotion: capacity {capacity} is negative")
-        self.capacity, self._ptr = capacity, 0
-        err = C.c_int(0)
-        self._ptr = lib.hns_point_motion_create(capacity, C.byref(err))
-        if not self._ptr:
-            _raise(err.value if err.value < 0 else _lib.HNS_ERR_RUNTIME)
-
-    def _live(self) -> int:
-        if not self._ptr:
-            raise RuntimeError("PointMotion: the object is closed")
-        return self._ptr
+        self.capacity = capacity
+        self._create(lib.hns_point_motion_create, capacity)
 
     def _view(self, which: str, shape, typestr: str):
         info = _lib.hns_point_motion_info()
@@ -641,42 +639,26 @@ class PointMotion:
             raise ValueError("PointMotion.step: gravity has three components")
         spec = _lib.hns_point_motion_spec(MOTION_MODES[mode], (C.c_float * 3)(*g), float(drag), float(restitution), float(friction), float(max_age), float(threshold),
                                           float(skin), int(iterations))
-        _raise(lib.hns_point_motion_set_stream(ptr, current_stream() if stream is None else int(stream)))
+        _raise(lib.hns_point_motion_set_stream(ptr, _stream(stream)))
         _raise(lib.hns_point_motion_step(ptr, sim._ptr, int(n), float(dt), float(voxel_size), int(steps), C.byref(spec)))
         return self
 
     def close(self) -> None:
         """the block goes back to the pool (which waits for the device first); the views must not be used afterwards"""
-        if self._ptr:
-            lib.hns_point_motion_destroy(self._ptr)
-            self._ptr = 0
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        super().close()
 
 
-class Shaping:
+class Shaping(_Handle):
     """Shaping a device-resident sim in place (``hns_shaping``; include/hns.h states the arithmetic line by line): divergence-free curl-noise turbulence on the velocity,
     optionally weighted by a control field, and implicit decay of float fields towards a target, in one launch over the sim's leaves. The object holds no device memory
     and is bound to no sim: ``apply`` takes the sim."""
 
     TURBULENCE = dict(amplitude=0.0, frequency=1.0 / 16, offset=(0.0, 0.0, 0.0), octaves=1, lacunarity=2.0, gain=0.5, seed=0, control=None, control_lo=0.0, control_hi=1.0)
 
+    _destroy = "hns_shaping_destroy"
+
     def __init__(self):
-        self._ptr = 0
-        err = C.c_int(0)
-        self._ptr = lib.hns_shaping_create(C.byref(err))
-        if not self._ptr:
-            _raise(err.value if err.value < 0 else _lib.HNS_ERR_RUNTIME)
+        self._create(lib.hns_shaping_create)
 
     @classmethod
     def turbulence_spec(cls, turbulence: dict):
@@ -698,33 +680,15 @@ class Shaping:
         |C| about 0.8 on average), w = 1 or, with `control` the name of a float field, clamp((field - control_lo) / (control_hi - control_lo), 0, 1) of its value before
         this call's decay; scroll `offset` to animate. decay: None, or {name: (rate, target)} of up to eight float fields -- f = target + (f - target) / (1 + rate * dt).
         stream: a hipStream_t as an integer, None = torch's current stream; the call is asynchronous on it. Returns self."""
-        if not self._ptr:
-            raise RuntimeError("Shaping: the object is closed")
+        ptr = self._live()
         spec = None if turbulence is None else self.turbulence_spec(turbulence)
         rows = list((decay or {}).items())
         arr = (_lib.hns_decay_spec * max(1, len(rows)))()
         for d, (name, (rate, target)) in zip(arr, rows):
             d.name, d.rate, d.target = str(name).encode(), float(rate), float(target)
-        _raise(lib.hns_shaping_set_stream(self._ptr, current_stream() if stream is None else int(stream)))
-        _raise(lib.hns_shaping_apply(self._ptr, sim._ptr, float(dt), None if spec is None else C.byref(spec), arr if rows else None, len(rows)))
+        _raise(lib.hns_shaping_set_stream(ptr, _stream(stream)))
+        _raise(lib.hns_shaping_apply(ptr, sim._ptr, float(dt), None if spec is None else C.byref(spec), arr if rows else None, len(rows)))
         return self
-
-    def close(self) -> None:
-        if self._ptr:
-            lib.hns_shaping_destroy(self._ptr)
-            self._ptr = 0
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def shaping_curl_host(turbulence: dict, ijk) -> np.ndarray:
@@ -741,19 +705,17 @@ def shaping_curl_host(turbulence: dict, ijk) -> np.ndarray:
     return out
 
 
-class Diffusion:
+class Diffusion(_Handle):
     """Implicit diffusion of float fields and viscosity of the velocity on a device-resident sim (``hns_diffusion``; include/hns.h states the arithmetic line by line):
     per field (I - a L) x = b over the sim's unknowns, a = coefficient * dt / voxel_size**2, by a fixed number of Jacobi or Chebyshev iterations, one launch each. The
     object holds its stream and the pooled scratch of its calls and is bound to no sim: ``apply`` takes the sim."""
 
     METHODS = {"jacobi": _lib.HNS_DIFFUSION_JACOBI, "chebyshev": _lib.HNS_DIFFUSION_CHEBYSHEV}
 
+    _destroy = "hns_diffusion_destroy"
+
     def __init__(self):
-        self._ptr = 0
-        err = C.c_int(0)
-        self._ptr = lib.hns_diffusion_create(C.byref(err))
-        if not self._ptr:
-            _raise(err.value if err.value < 0 else _lib.HNS_ERR_RUNTIME)
+        self._create(lib.hns_diffusion_create)
 
     @classmethod
     def spec(cls, viscosity: float = 0.0, iterations: int = 8, method: str = "jacobi", collide: bool = False, threshold: float = 0.0):
@@ -768,8 +730,7 @@ class Diffusion:
         is neither read nor written); iterations 1 .. 256 of method "jacobi" or "chebyshev"; collide: voxels whose ``collision_sdf`` lies below `threshold` are solid --
         zero-flux for a float field, a no-slip wall at rest for the velocity. Only the sim's unknowns (active, not solid) are written. stream: a hipStream_t as an integer,
         None = torch's current stream; the call is asynchronous on it. Returns self."""
-        if not self._ptr:
-            raise RuntimeError("Diffusion: the object is closed")
+        ptr = self._live()
         spec = self.spec(viscosity, iterations, method, collide, threshold)
         rows = list((fields or {}).items())
         unknown = [str(k) for k, _ in rows if str(k) not in sim.names]
@@ -778,26 +739,9 @@ class Diffusion:
         arr = (_lib.hns_diffusion_term * max(1, len(rows)))()
         for t, (name, coefficient) in zip(arr, rows):
             t.name, t.coefficient = str(name).encode(), float(coefficient)
-        _raise(lib.hns_diffusion_set_stream(self._ptr, current_stream() if stream is None else int(stream)))
-        _raise(lib.hns_diffusion_apply(self._ptr, sim._ptr, float(dt), float(voxel_size), C.byref(spec), arr if rows else None, len(rows)))
+        _raise(lib.hns_diffusion_set_stream(ptr, _stream(stream)))
+        _raise(lib.hns_diffusion_apply(ptr, sim._ptr, float(dt), float(voxel_size), C.byref(spec), arr if rows else None, len(rows)))
         return self
-
-    def close(self) -> None:
-        if self._ptr:
-            lib.hns_diffusion_destroy(self._ptr)
-            self._ptr = 0
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def diffusion_schedule_host(coefficient: float, dt: float, voxel_size: float, iterations: int) -> dict:
@@ -863,19 +807,17 @@ def _leaf_source(entry, leaves, need, keep, ncomp: Optional[int] = None) -> None
     entry.masks = None if m is None else m.ctypes.data
 
 
-class Sim:
+class Sim(_Handle):
     """Device-resident simulation state (``hns_sim``): upload once, run many substeps."""
+
+    _destroy = "hns_sim_destroy"
 
     def __init__(self, grid: IndexGridHandle, float_names: Sequence[str]):
         self.grid = grid
         self.names = list(float_names)
         self._shaping = None  # the Shaping that ``shape`` makes on first use
         self._diffusion = None  # the Diffusion that ``diffuse`` makes on first use
-        arr = (C.c_char_p * max(1, len(self.names)))(*[n.encode() for n in self.names])
-        err = C.c_int(0)
-        self._ptr = lib.hns_sim_create(grid.ptr, arr, len(self.names), C.byref(err))
-        if not self._ptr:
-            _raise(err.value if err.value < 0 else _lib.HNS_ERR_RUNTIME)
+        self._create(lib.hns_sim_create, grid.ptr, _names(self.names), len(self.names))
 
     def _fields(self, arrays: dict):
         arr = (hns_field * max(1, len(arrays)))()
@@ -911,8 +853,7 @@ class Sim:
         if names is None:
             _raise(lib.hns_sim_advect(self._ptr, None, -1, int(velocity), dt, voxel_size, stream))
             return
-        arr = (C.c_char_p * max(1, len(names)))(*[n.encode() for n in names])
-        _raise(lib.hns_sim_advect(self._ptr, arr, len(names), int(velocity), dt, voxel_size, stream))
+        _raise(lib.hns_sim_advect(self._ptr, _names(names), len(names), int(velocity), dt, voxel_size, stream))
 
     def sample(self, names: Optional[Sequence[str]] = None, xyz=None, velocity: bool = False, stream: Optional[int] = None) -> dict:
         """The sim's float fields `names` (None: all of them) and, with `velocity`, its velocity under the key "vel", at the positions xyz ((n, 3) float32 device
@@ -926,9 +867,7 @@ class Sim:
             raise ValueError("Sim.sample: a name is listed twice")
         if velocity:
             out["vel"] = t.empty((n, 3), dtype=t.float32, device=xyz.device)
-        arr = (C.c_char_p * max(1, len(names)))(*[k.encode() for k in names])
-        dst = (C.c_void_p * max(1, len(out)))(*[_ptr(v) for v in out.values()])
-        _raise(lib.hns_sim_sample_points(self._ptr, arr, len(names), int(velocity), _ptr(xyz), n, dst, current_stream() if stream is None else stream))
+        _raise(lib.hns_sim_sample_points(self._ptr, _names(names), len(names), int(velocity), _ptr(xyz), n, _ptrs(out.values()), _stream(stream)))
         return out
 
     def trace(self, xyz, *, dt: float, voxel_size: float, order: int = 2, steps: int = 1, status: bool = False, stream: Optional[int] = None, collide: Optional[str] = None,
@@ -940,7 +879,7 @@ class Sim:
         spec = None if collide is None else _collision("Sim.trace", collide, threshold, skin, iterations)
         t = _torch()
         st = t.empty(xyz.shape[0], dtype=t.uint8, device=xyz.device) if status else None
-        stream = current_stream() if stream is None else stream
+        stream = _stream(stream)
         if spec is None:
             if hit:
                 raise ValueError("Sim.trace: hit needs collide")
@@ -973,8 +912,7 @@ class Sim:
             r = order._splat_rows("Sim.splat", rows, xyz, [(k, values[k]) for k in names] + [("velocity", velocity)])
         spec = splat_spec(kernel, mode, radius, max_radius, min_weight, pointer=lambda t: _radius_ptr(t, xyz.shape[0]))
         st = _torch().empty(xyz.shape[0], dtype=_torch().uint8, device=xyz.device) if status else None
-        arr = (C.c_char_p * max(1, len(names)))(*[k.encode() for k in names])
-        src = (C.c_void_p * max(1, len(names)))(*[_ptr(values[k]) for k in names])
+        arr, src = _names(names), _ptrs(values[k] for k in names)
         if order is not None:
             with stored_splat_spec(lib.hns_sim_set_splat_spec, lib.hns_sim_get_splat_spec, self._ptr, spec):
                 _raise(lib.hns_point_order_splat_sim(order._live(), self._ptr, arr, len(names), _ptr(velocity), _ptr(xyz) if order.n else 0, src, r, int(log2_quantum),
@@ -982,7 +920,7 @@ class Sim:
             return st
         with stored_splat_spec(lib.hns_sim_set_splat_spec, lib.hns_sim_get_splat_spec, self._ptr, spec):
             _raise(lib.hns_sim_splat_points(self._ptr, arr, len(names), _ptr(velocity), _ptr(xyz), src, xyz.shape[0], int(log2_quantum), int(bool(activate)),
-                                            _byte_ptr(st), _u64_ptr(rejected), current_stream() if stream is None else stream))
+                                            _byte_ptr(st), _u64_ptr(rejected), _stream(stream)))
         return st
 
     def pressure_solve(self, iterations: int, voxel_size: float, stream: int = 0) -> None:
@@ -1214,12 +1152,4 @@ class Sim:
         if self._diffusion is not None:
             self._diffusion.close()
             self._diffusion = None
-        if self._ptr:
-            lib.hns_sim_destroy(self._ptr)
-            self._ptr = 0
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        super().close()
