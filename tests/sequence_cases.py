@@ -6,15 +6,16 @@ every call, the grid's pooled splat accumulator, an order's permutation and its 
 
   OPS       the vocabulary: one entry per call that changes or reads that state, a function (world, rng) -> outputs with the resources it reads and writes, the
             library symbols it goes through, what it needs from the script before it, and what it does to the look-ahead memo.
-  World     the device side of a script: the sim, the points, one PointOrder and one PointPopulation.
-  resident  ONE World from the first step to the last (the order and the population made anew only after a step that moves the sim onto another grid).
+  World     the device side of a script: the sim, the points, one PointOrder and one PointPopulation, and one PointMotion of N_POINTS rows, one Shaping and one Diffusion.
+  resident  ONE World from the first step to the last (the order and the population made anew only after a step that moves the sim onto another grid; the motion, the
+            shaping and the diffusion are bound to no grid and stay through every change of grid: the Diffusion with its pooled block, the motion with its rows).
   twin      a NEW World for every step, built from nothing but the semantic state (`World.capture`), run with lookahead = 0 and the pool filled with a non-zero byte.
   SCRIPTS   the committed scripts: explicit lists of (operation, seed). `draw_scripts` is the seeded generator the first twelve were drawn with, the rest are written by
-            hand (POINT_SCRIPTS: collision tracing, the order's cell table, the frame loop of points); a red script is rerun and cut down by hand with
-            `compare(script, mode, upto=...)`.
+            hand (POINT_SCRIPTS: collision tracing, the order's cell table, the frame loop of points) or drawn by `draw_scripts(only=...)` for the pairs a grown table
+            adds (FEATURE_SCRIPTS: points with a velocity of their own, shaping, diffusion); a red script is rerun and cut down by hand with `compare(script, mode, upto=...)`.
 
 Every comparison is equality of bytes: every path involved is documented as bit-identical to its stateless form. Where a memo may rightly live or die without moving a
-byte -- hns_sim_deactivate drops the look-ahead although the velocity stays -- the table's memo column predicts hns_sim_lookahead_counts under lookahead = 1
+byte -- hns_sim_deactivate drops the look-ahead although the velocity stays; a decay or a diffuse of float fields alone must keep it -- the table's memo column predicts hns_sim_lookahead_counts under lookahead = 1
 (`expected_lookahead`), and the resident pass is held to it step by step. Everything runs on the null stream."""
 from __future__ import annotations
 
@@ -38,7 +39,8 @@ PROFILES = {"combust": list(fc.COMBUST), "collide": list(fc.COMBUST) + ["collisi
 
 ALL_FIELDS = tuple("f:" + n for n in PROFILES["collide"])
 ADVECTED = tuple("f:" + n for n in fc.COMBUST)
-RESOURCES = ("vel", "masks", "grid", "scratch", "splat_spec", "solve_method", "solve_control", "points", "order", "cells", "live") + ALL_FIELDS  # cells: the order's cell table, a memo of "order"
+RESOURCES = ("vel", "masks", "grid", "scratch", "splat_spec", "solve_method", "solve_control", "points", "order", "cells", "live", "motion") + ALL_FIELDS
+# cells: the order's cell table, a memo of "order"; motion: rows 0 .. N_POINTS - 1 of the PointMotion's xyz, vel and age (status and hit are outputs of a step)
 SOLVE = ("solve_method", "solve_control", "grid")  # what every pressure solve reads besides its right-hand side (the hierarchy is a memo of grid and method)
 
 
@@ -85,13 +87,17 @@ RUNNER_SYMBOLS = ("hns_sim_create", "hns_sim_destroy", "hns_sim_upload", "hns_si
                   "hns_sim_set_splat_spec", "hns_sim_set_solve_method", "hns_sim_set_solve_control", "hns_sim_lookahead_counts", "hns_sim_timing", "hns_sim_pressure_time",
                   "hns_sim_stage_timing", "hns_sim_stage_times", "hns_point_order_create", "hns_point_order_destroy", "hns_point_order_set_stream", "hns_point_order_get",
                   "hns_point_order_sort", "hns_point_population_create", "hns_point_population_destroy", "hns_point_population_set_stream", "hns_point_population_set_live",
-                  "hns_point_population_get", "hns_point_population_counts")
+                  "hns_point_population_get", "hns_point_population_counts", "hns_point_motion_create", "hns_point_motion_destroy", "hns_point_motion_set_stream",
+                  "hns_point_motion_get", "hns_shaping_create", "hns_shaping_destroy", "hns_shaping_set_stream", "hns_diffusion_create", "hns_diffusion_destroy",
+                  "hns_diffusion_set_stream")
 
 EXEMPT = {
     "hns_sim_velocity_ptr": "switches the look-ahead off for good by contract, so no memo is left to go stale behind it; test_lookahead_gpu holds that contract",
     "hns_sim_substep_plan": "its text names the memo by design (advect_vector=memo), so a resident sim and a twin differ in it rightly; test_kernel_variants_gpu reads it",
     "hns_point_order_splat": "writes caller-owned tensors and no sim buffer: there is no sim state for it to leave stale; the sim's form hns_point_order_splat_sim is an operation",
     "hns_point_population_birth": "reads a caller-owned tensor and no sim: the sim's form hns_point_population_birth_sim is an operation and shares its kernels",
+    "hns_shaping_curl_host": "host-only: it evaluates one voxel's curl from a host struct and touches no sim, no object and no device; test_shaping_cases holds it to the mirror",
+    "hns_diffusion_schedule_host": "host-only: it forms one coefficient's constants from numbers and touches no sim, no object and no device; test_diffusion_cases holds it",
 }
 
 
@@ -113,10 +119,12 @@ def device_floats(owner, ptr, n):
 
 
 DEFAULT_SPEC = (0, 0, 0.0, 0.0)
+MOTION_STATE = ("xyz", "vel", "age")  # the PointMotion's arrays that are state; the state's keys are "motion_xyz", ...
 
 
 class World:
-    """The sim of a script with its points, its order and its population, opened from the semantic state alone: what `capture` returns, plus the solve method, the solve
+    """The sim of a script with its points, its order, its population, its motion, its shaping and its diffusion, opened from the semantic state alone: what `capture`
+    returns (the motion's xyz, vel and age with it; its status and hit are outputs of a step and hold pool contents before the first), plus the solve method, the solve
     control, the order's last (xyz, level) and the switches of the script, which the library has no getter for and the ops record here."""
 
     def __init__(self, state):
@@ -143,6 +151,11 @@ class World:
         self.order_key = state["order_key"]
         self.live = state["live"]
         self._order = self._population = None
+        # bound to no grid (include/hns.h): these three stay from the first step to the last, through every change of grid -- `after` does not drop them
+        self.motion = device.PointMotion(N_POINTS)
+        self.shaping, self.diffusion = device.Shaping(), device.Diffusion()
+        for k in MOTION_STATE:
+            getattr(self.motion, k).copy_(torch.from_numpy(np.array(state["motion_" + k])).cuda())
 
     # -- the state the library has no getter for
     def set_spec(self, spec):
@@ -207,6 +220,7 @@ class World:
         st = fc.download(sim, self.names)
         st.update(origins=np.ascontiguousarray(sim.grid.coords()[::512]), masks=sim.active_masks(), xyz=self.xyz.cpu().numpy(), attr=self.attr.cpu().numpy(),
                   splat_spec=self.get_spec(), live=self.live)
+        st.update({"motion_" + k: getattr(self.motion, k).cpu().numpy() for k in MOTION_STATE})
         return st
 
     def carry(self, captured):
@@ -217,6 +231,8 @@ class World:
         if self.timing:  # (times are never compared)
             self.sim.pressure_time(), self.sim.stage_times()
         self.drop_point_objects()
+        for o in (self.motion, self.shaping, self.diffusion):
+            o.close()
         self.sim.close()
 
 
@@ -713,6 +729,155 @@ def spec_default(w, rng):
     return {}
 
 
+# -- shaping (include/hns.h, SHAPING A SIM): one launch over the leaves whatever the masks say; the memo goes when the amplitude is non-zero and stays behind a decay alone
+
+
+def _turbulence(rng, **control):
+    return dict(amplitude=2.0, frequency=1.0 / 8, offset=tuple(float(F(c)) for c in rng.uniform(-64.0, 64.0, 3)), octaves=int(rng.integers(2, 4)), lacunarity=2.0, gain=0.5,
+                seed=_seed(rng), **control)
+
+
+CONTROL = dict(control="density", control_lo=-0.25, control_hi=0.75)  # the fields of these scripts are of order 1: values fall below, inside and above
+DECAY = {"density": (2.0, 0.125)}
+SHAPE = ("hns_shaping_apply",)
+
+
+@op("shape", reads=("vel", "grid"), writes=("vel",), symbols=SHAPE, memo="drop")
+def shape_turbulence(w, rng):
+    w.shaping.apply(w.sim, DT, _turbulence(rng))
+    return {}
+
+
+@op("shape", reads=("vel", "grid", "f:density"), writes=("vel", "f:density"), symbols=SHAPE, needs=("density",), memo="drop")
+def shape_controlled(w, rng):
+    """the weight comes from density before this call's decay of it"""
+    w.shaping.apply(w.sim, DT, _turbulence(rng, **CONTROL), DECAY)
+    return {}
+
+
+@op("shape", reads=("grid", "f:density"), writes=("f:density",), symbols=SHAPE, needs=("density",))
+def shape_decay(w, rng):
+    """amplitude 0: the velocity is neither read nor written, and what was looked ahead stays"""
+    w.shaping.apply(w.sim, DT, dict(_turbulence(rng), amplitude=0.0), DECAY)
+    return {}
+
+
+# -- diffusion (DIFFUSING A SIM): the iterates ping-pong in the sim's adv, tmp and nxt buffers and in ONE block the object keeps between calls; only the unknowns are written
+
+
+def coefficient_of(a):
+    """the coefficient that gives a = coefficient * DT / VS^2"""
+    return a * VS * VS / DT
+
+
+# name -> ({field: a}, the velocity's a, iterations, method, collide): 1, 5, 0 and 1 written float fields, so the object's block is carved anew from call to call
+DIFFUSE_SPECS = {
+    "diffuse_copy": ({"density": 0.5}, 0.0, 1, "jacobi", False),
+    "diffuse_fields": (dict(zip(fc.COMBUST, (0.05, 0.3, 1.0, 2.0, 4.0))), 0.0, 3, "chebyshev", False),
+    "diffuse_viscosity": ({}, 1.5, 2, "jacobi", False),
+    "diffuse_walls": ({"density": 4.0}, 0.75, 4, "chebyshev", True),
+}
+DIFFUSE = ("hns_diffusion_apply",)
+
+
+def diffuse_arguments(name):
+    """the keywords of Diffusion.apply (and of diffusion_cases.apply_mirror) of a diffuse operation"""
+    fields, viscosity, iterations, method, collide = DIFFUSE_SPECS[name]
+    return dict(fields={k: coefficient_of(a) for k, a in fields.items()}, viscosity=coefficient_of(viscosity), iterations=iterations, method=method, collide=collide, threshold=0.0)
+
+
+def _diffuse(w, name):
+    w.diffusion.apply(w.sim, DT, VS, **diffuse_arguments(name))
+    return {}
+
+
+@op("diffuse", reads=("grid", "masks", "f:density"), writes=("f:density",), symbols=DIFFUSE, needs=("density",))
+def diffuse_copy(w, rng):
+    """iterations == 1: the one iterate lies in the scratch and a copy brings it into the field"""
+    return _diffuse(w, "diffuse_copy")
+
+
+@op("diffuse", reads=("grid", "masks") + ADVECTED, writes=ADVECTED, symbols=DIFFUSE, needs=fc.COMBUST)
+def diffuse_fields(w, rng):
+    return _diffuse(w, "diffuse_fields")
+
+
+@op("diffuse", reads=("grid", "masks", "vel"), writes=("vel",), symbols=DIFFUSE, memo="drop")
+def diffuse_viscosity(w, rng):
+    return _diffuse(w, "diffuse_viscosity")
+
+
+@op("diffuse", reads=("grid", "masks", "vel", "f:density", "f:collision_sdf"), writes=("vel", "f:density"), symbols=DIFFUSE, needs=("density", "collision_sdf"), memo="drop")
+def diffuse_walls(w, rng):
+    return _diffuse(w, "diffuse_walls")
+
+
+# -- points with a velocity of their own (POINTS WITH A VELOCITY OF THEIR OWN): the sim is only read, the object is bound to no grid
+
+GRAVITY = (0.0, -9.8, 0.0)
+# name -> (mode, steps or None = 1 .. 3 from the step's rng, the keywords of PointMotion.step); the ages are drawn in [0, 1), so a finite max_age below 1 expires rows
+MOTION_SPECS = {
+    "motion_free": ("free", 1, dict(gravity=GRAVITY, drag=2.0)),
+    "motion_stick": ("stick", None, dict(gravity=GRAVITY, drag=1.0, max_age=0.9)),
+    "motion_bounce": ("bounce", None, dict(gravity=GRAVITY, drag=2.0, restitution=0.5, friction=0.25, max_age=0.95, skin=1 / 16, iterations=3)),
+    "motion_kill_compact": ("kill", 1, dict(gravity=GRAVITY, drag=2.0, max_age=0.9)),
+}
+MOTION = ("hns_point_motion_step", "hns_point_motion_get")
+MOTION_READS = ("vel", "grid", "motion")
+
+
+@op("motion_load", reads=("points",), writes=("motion",), symbols=("hns_point_motion_get",))
+def motion_load(w, rng):
+    """points -> motion: through the device pointers the object hands out"""
+    w.motion.xyz.copy_(w.xyz)
+    w.motion.vel.copy_(w.vel3())
+    w.motion.age.copy_(_torch().from_numpy(rng.random(N_POINTS).astype(F)).cuda())
+    return {}
+
+
+@op("motion_store", reads=("motion",), writes=("points",), symbols=("hns_point_motion_get",))
+def motion_store(w, rng):
+    """motion -> points: the sorts, splats, traces and queries behind it read the moved positions"""
+    w.xyz = w.motion.xyz.clone()
+    return {}
+
+
+def _motion(w, rng, name):
+    mode, steps, spec = MOTION_SPECS[name]
+    steps = int(rng.integers(1, 4)) if steps is None else steps
+    w.motion.step(w.sim, N_POINTS, DT, VS, steps, mode, **spec)
+    return {"status": w.motion.status.cpu().numpy(), "hit": w.motion.hit.cpu().numpy(), "steps": steps}
+
+
+@op("motion", reads=MOTION_READS, writes=("motion",), symbols=MOTION)
+def motion_free(w, rng):
+    return _motion(w, rng, "motion_free")
+
+
+@op("motion", reads=MOTION_READS + ("f:collision_sdf",), writes=("motion",), symbols=MOTION, needs=("collision_sdf",))
+def motion_stick(w, rng):
+    return _motion(w, rng, "motion_stick")
+
+
+@op("motion", reads=MOTION_READS + ("f:collision_sdf",), writes=("motion",), symbols=MOTION, needs=("collision_sdf",))
+def motion_bounce(w, rng):
+    return _motion(w, rng, "motion_bounce")
+
+
+@op("motion", reads=MOTION_READS + ("f:collision_sdf",), writes=("motion", "live"), symbols=MOTION + POPULATION[1:], needs=("collision_sdf",))
+def motion_kill_compact(w, rng):
+    """ONE compound step, as trace_collide_kill_compact is (the slots are not state): a kill step, select from its status, compact xyz, vel and age into the motion's arrays"""
+    out = _motion(w, rng, "motion_kill_compact")
+    m, p = w.motion, w.population()
+    p.select(m.status, 1)
+    out["slot"] = p.slot.cpu().numpy()
+    for a, fill in ((m.xyz, float("nan")), (m.vel, 0.0), (m.age, 0.0)):
+        p.compact(a.clone(), a, fill=fill)
+    out["counts"] = p.counts()
+    w.live = out["counts"][0]
+    return out
+
+
 KINDS = tuple(dict.fromkeys(o.kind for o in OPS.values()))
 PRODUCERS = frozenset(k for k, o in OPS.items() if o.memo == "produce")
 
@@ -838,13 +1003,14 @@ def has_two_equal_substeps(script: Script):
 # ---- the generator the committed scripts were drawn with ---------------------------------------------------------------------------------------------------------------
 
 
-def draw_scripts(seed=2026, max_steps=24, max_scripts=16):
+def draw_scripts(seed=2026, max_steps=24, max_scripts=16, only=None, first_seed=101):
     """Placement scripts first (substep, writer, substep, writer, ...), then greedy walks that take the step covering the most uncovered pairs. Prints nothing; returns the
-    scripts, whose text (`format_scripts`) is pasted below. The CPU test holds the conditions on the committed text, not on this function."""
+    scripts, whose text (`format_scripts`) is pasted below. The CPU test holds the conditions on the committed text, not on this function.
+    only: a set of pairs of kinds -- no placement scripts, and the walks go for these pairs alone (what a grown table adds to the committed scripts)"""
     rng = np.random.default_rng(seed)
     ways_of = needed_pairs()
-    need = set(ways_of)
-    scripts, counter = [], [100]
+    need = set(ways_of) if only is None else set(only) & set(ways_of)
+    scripts, counter = [], [first_seed - 1]
 
     def next_seed():
         counter[0] += 1
@@ -864,7 +1030,7 @@ def draw_scripts(seed=2026, max_steps=24, max_scripts=16):
         groups["one" if (not OPS[k].needs and i % 2) else "combust"].append(k)
     groups["collide"] += groups["combust"][-3:]
     del groups["combust"][-3:]
-    for profile, ws in groups.items():
+    for profile, ws in groups.items() if only is None else ():
         cycle = ["core_substep"] if profile == "one" else ["core_substep", "substep_unfused"]
         names, t = [cycle[0]], Tracker()
         for j, k in enumerate(ws):
@@ -1080,6 +1246,82 @@ POINT_SCRIPTS = (
 )
 SCRIPTS += POINT_SCRIPTS
 
+# The three features merged since: points with a velocity of their own, shaping, diffusion. The first three are written by hand, the last four drawn by draw_scripts(only=
+# the pairs the three left uncovered) and touched up by hand (a masks_array or a deactivate in front, so that no diffuse runs with every voxel an unknown of random values).
+#   frame_shaped   the frame loop the features were built for: a controlled shape and a diffuse with walls between two substeps, points loaded into the motion, bounced,
+#                  killed and compacted, stored back, sorted and splatted through the order; a regrid; and the same again on the new grid, through the SAME PointMotion,
+#                  Shaping and Diffusion.
+#   memo_kept      every shape and diffuse directly between two look-ahead substeps: shape_decay, diffuse_copy and diffuse_fields must leave the memo for the next substep
+#                  to consume, the four that write the velocity must drop it. On the one Diffusion the written float fields go 1, 5, (1), 0, 1 and, behind a regrid onto
+#                  a larger grid, 0 and 5: its block is carved anew and drawn anew. A diffuse of the velocity (adv, tmp) in front of the vorticity stage.
+#   motion_regrid  motion steps either side of a regrid and of an emit with no load between them: the one object follows the sim onto its new grids; a store in front of
+#                  a collision trace, a kill in front of a store and a birth; deactivate in front of a diffuse; a collision substep in front of a stick.
+# What the twin showed on the MI355X (check_liveness of tests/test_sequences_gpu.py prints it) stands above each script.
+FEATURE_SCRIPTS = (
+    # twin: 31 leaves, 525 behind the regrid. Control (below, inside, above) of the two shapes (6174, 7249, 1425) (4691, 263983, 126); the diffuses changed 30752 of 59392
+    # words with 7119 solid voxels and 7729 unknowns, then 111419 of 1075200 with 240161 of 268800 voxels inactive, 2038 solid, 27902 unknowns. Bounces: status (0, 1)
+    # (1118, 382) and (1344, 156), rows per hit bit 1, 8, 16: 438, 529, 203 and 5, 3, 4; the kills killed 200 and 2, kept 171 and 134 of 1500; 414 rows expired by age.
+    # look-ahead counts (4, 0) under lookahead = 1. Against the mirrors (3 octaves; 1 bounce step): no word differs in any of the three
+    Script("frame_shaped", "collide", 461, False, (
+        ("core_substep", 462), ("shape_controlled", 463), ("diffuse_walls", 464), ("core_substep", 465), ("motion_load", 466), ("motion_bounce", 467),
+        ("motion_kill_compact", 468), ("motion_store", 469), ("sort_voxel", 470), ("order_splat_original", 471), ("regrid_sdf", 472), ("core_substep", 473),
+        ("shape_controlled", 474), ("diffuse_walls", 475), ("core_substep", 476), ("motion_load", 477), ("motion_bounce", 478), ("motion_kill_compact", 479),
+        ("motion_store", 480), ("sort_voxel", 481), ("order_splat_original", 482),
+    )),
+    # twin: 9282 of 14848 voxels inactive from the first step on, 160868 of 177152 behind the regrid (31 -> 346 leaves). Words changed: copy 5384 of 14848, fields 26828 of
+    # 74240, viscosity 16152 of 44544, walls 11219 of 59392 (6994 solid, 2888 unknowns); on the larger grid viscosity 48642 of 531456, fields 70067 of 885760. The decay
+    # moved no velocity word and all 14848 of density; control (890, 13836, 122). look-ahead counts (10, 4) under lookahead = 1: the three keeps were each consumed behind
+    Script("memo_kept", "collide", 483, True, (
+        ("masks_array", 484), ("core_substep", 485), ("substep_unfused", 486), ("shape_decay", 487), ("core_substep", 488), ("diffuse_copy", 489),
+        ("substep_unfused", 490), ("diffuse_fields", 491), ("core_substep", 492), ("shape_turbulence", 493), ("substep_unfused", 494), ("shape_controlled", 495),
+        ("core_substep", 496), ("diffuse_viscosity", 497), ("substep_unfused", 498), ("diffuse_walls", 499), ("core_substep", 500), ("regrid_plain", 501),
+        ("diffuse_viscosity", 502), ("substep_vorticity", 503), ("diffuse_fields", 504), ("core_substep", 505),
+    )),
+    # twin: sticks of 3, 3 and 1 steps, status (0, 1) (1084, 416) (1009, 491) (323, 1177), stuck 608, 613, 407, started inside 467, 195, 457; bounces of 2 and 3 steps
+    # (1175, 325) (1185, 315), bounced 609 and 149, reflected 453 and 91, put back 1; the kill killed 38 and kept 563 of 1500; 2906 rows expired by age over the script.
+    # diffuse_copy behind the deactivate: 462841 of 472064 voxels inactive, 9024 words changed; walls 86601 of 1046528 (7388 solid, 22518 unknowns). 511 leaves at the end
+    Script("motion_regrid", "collide", 506, False, (
+        ("motion_load", 507), ("motion_free", 508), ("motion_stick", 509), ("regrid_seeded", 510), ("motion_stick", 511), ("motion_bounce", 512),
+        ("emit_trilinear", 513), ("motion_bounce", 514), ("motion_store", 515), ("trace_collide_stop", 516), ("motion_load", 517), ("motion_kill_compact", 518),
+        ("motion_store", 519), ("birth_append", 520), ("motion_load", 521), ("motion_free", 522), ("deactivate", 523), ("diffuse_copy", 524), ("regrid_plain", 525),
+        ("diffuse_walls", 526), ("deactivate_counts", 527), ("shape_decay", 528), ("substep_collision", 529), ("motion_stick", 530),
+    )),
+    # twin: seven controlled shapes, the control (5820, 6113, 3427) at first and (4403, 844093, 1424) on the last grid; four viscosity diffuses under masks with 7610 of
+    # 15360 and then 397614 of 451072 voxels inactive, 23082 of 46080 and 94646 of 1353216 words changed. 1660 leaves at the end
+    Script("walk_19", "combust", 531, True, (
+        ("masks_array", 532), ("shape_controlled", 533), ("shape_controlled", 534), ("splat_stored", 535), ("diffuse_viscosity", 536), ("diffuse_viscosity", 537),
+        ("shape_controlled", 538), ("advect_velocity", 539), ("diffuse_viscosity", 540), ("splat_stored", 541), ("shape_controlled", 542), ("emit_trilinear", 543),
+        ("diffuse_viscosity", 544), ("advect_velocity", 545), ("shape_controlled", 546), ("regrid_seeded", 547), ("shape_controlled", 548), ("trace", 549),
+        ("motion_load", 550), ("motion_store", 551), ("emit_radial", 552), ("shape_controlled", 553), ("select_compact_fill", 554), ("motion_load", 555),
+    )),
+    # twin: five diffuses with walls, 7519 solid voxels throughout, 8353 unknowns on the first grid and 88636 of 483328 voxels behind the emit; kills killed 435 and 126 (489
+    # rows started inside), kept 329 and 192 of 1500, 158 rows expired; control (3361, 478294, 1673) and (2891, 478878, 1559). 944 leaves at the end
+    Script("walk_20", "collide", 556, False, (
+        ("diffuse_walls", 557), ("motion_kill_compact", 558), ("birth_append", 559), ("diffuse_walls", 560), ("emit_radial", 561), ("motion_store", 562),
+        ("splat_both", 563), ("motion_kill_compact", 564), ("diffuse_walls", 565), ("select_compact_keep", 566), ("shape_controlled", 567),
+        ("trace_collide_stop", 568), ("motion_store", 569), ("sample", 570), ("diffuse_walls", 571), ("sample", 572), ("motion_store", 573),
+        ("select_compact_fill", 574), ("shape_controlled", 575), ("birth_append", 576), ("diffuse_walls", 577), ("birth_append", 578), ("motion_store", 579),
+        ("motion_load", 580),
+    )),
+    # twin: no collision_sdf in this profile: motion_free alone, status (0, 1) (778, 722) (92, 1408) (168, 1332) (273, 1227), no hit bit. Viscosity under the deactivate's masks
+    # (6849 of 15872 voxels inactive): 26672 and 26698 of 47616 words changed; the copy behind masks_none, every voxel an unknown: 33576 of 263168. 514 leaves at the end
+    Script("walk_21", "one", 581, False, (
+        ("shape_controlled", 582), ("deactivate", 583), ("upload_vel", 584), ("shape_controlled", 585), ("motion_free", 586), ("motion_store", 587), ("trace", 588),
+        ("diffuse_viscosity", 589), ("stats", 590), ("upload_all", 591), ("diffuse_viscosity", 592), ("trace", 593), ("shape_controlled", 594), ("sample", 595),
+        ("motion_store", 596), ("regrid_seeded", 597), ("core_substep", 598), ("motion_free", 599), ("masks_none", 600), ("diffuse_copy", 601), ("upload_vel", 602),
+        ("motion_free", 603), ("advect_velocity", 604), ("motion_free", 605),
+    )),
+    # twin: copies under the deactivate's masks and the ordered splats' activations: 9365 and 11756 of 15872 words changed (6408, then 4084 voxels inactive), viscosity 34338
+    # of 47616; motion_free status (0, 1) (809, 691); the stop put back 582; control (4617, 10238, 1017). 31 leaves throughout
+    Script("pairs_22", "collide", 606, False, (
+        ("deactivate", 607), ("sort_voxel", 608), ("diffuse_copy", 609), ("order_splat_original", 610), ("diffuse_viscosity", 611), ("trace_collide_stop", 612),
+        ("gather_scatter", 613), ("motion_load", 614), ("motion_store", 615), ("gather_scatter", 616), ("sort_voxel", 617), ("order_splat_original", 618),
+        ("diffuse_copy", 619), ("order_splat_original", 620), ("motion_free", 621), ("order_splat_original", 622), ("shape_turbulence", 623),
+        ("order_splat_original", 624), ("shape_controlled", 625), ("stats", 626),
+    )),
+)
+SCRIPTS += FEATURE_SCRIPTS
+
 BY_NAME = {s.name: s for s in SCRIPTS}
 
 
@@ -1111,6 +1353,8 @@ def initial_state(name):
     st["vel"] *= F(0.6)
     xyz, attr = points_of(o, s.seed)
     st.update(origins=o, masks=None, xyz=xyz, attr=attr, splat_spec=DEFAULT_SPEC, live=N_POINTS, names=names, timing=s.timing, method=None, control=None, order_key=None)
+    # the motion's rows: the points' positions (their non-finite rows with them), velocities from the attribute as World.vel3 forms them, ages in [0, 1)
+    st.update(motion_xyz=xyz.copy(), motion_vel=np.stack([attr, F(-0.5) * attr, F(0.25) * attr], axis=1), motion_age=np.random.default_rng([s.seed, 78]).random(N_POINTS).astype(F))
     return st
 
 

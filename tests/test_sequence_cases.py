@@ -1,7 +1,8 @@
 """The vocabulary and the scripts of tests/test_sequences_gpu.py, checked without a GPU from the declared read / write table and the script lists alone: every entry point
-of a sim, a point order and a point population is an operation or a stated exemption; every pair of operation kinds where the first writes what the second reads is
+of a sim, a point order, a point population, a point motion, a shaping and a diffusion is an operation or a stated exemption; every pair of operation kinds where the first writes what the second reads is
 adjacent in some script; every writer of the velocity and every change of grid sits between two look-ahead substeps; the order's cell table goes through its transitions on
-one object; no script holds a step the library would refuse. OPS and EXEMPT are whole in tests/sequence_cases.py -- no other module adds to them --, so this file gives the
+one object; every call that must keep the look-ahead memo sits between two look-ahead substeps too; one Diffusion meets a call with more written fields and a larger grid;
+one PointMotion steps either side of a change of grid; no script holds a step the library would refuse. OPS and EXEMPT are whole in tests/sequence_cases.py -- no other module adds to them --, so this file gives the
 same answer run alone as in the suite."""
 import numpy as np
 import pytest
@@ -9,7 +10,7 @@ import pytest
 import sequence_cases as sq
 from hnanosolver_amd import _lib
 
-PREFIXES = ("hns_sim_", "hns_point_order_", "hns_point_population_")
+PREFIXES = ("hns_sim_", "hns_point_order_", "hns_point_population_", "hns_point_motion_", "hns_shaping_", "hns_diffusion_")
 REQUIREMENTS = {"order", "fresh_order", "voxel_order"}
 
 
@@ -34,8 +35,12 @@ def uncovered_pairs(ops, scripts):
 
 
 def test_every_entry_point_is_an_operation_or_exempt():
-    """a new hns_sim_* / hns_point_order_* / hns_point_population_* entry point fails here until it joins the vocabulary or states why it needs no place in it"""
-    assert len(bound_symbols()) >= 50
+    """a new hns_sim_* / hns_point_order_* / hns_point_population_* / hns_point_motion_* / hns_shaping_* / hns_diffusion_* entry point fails here until it joins the
+    vocabulary or states why it needs no place in it"""
+    assert len(bound_symbols()) >= 65  # (50 and the fifteen entry points of the three later prefixes)
+    assert {"hns_point_motion_create", "hns_point_motion_destroy", "hns_point_motion_set_stream", "hns_point_motion_get", "hns_shaping_create", "hns_shaping_destroy",
+            "hns_shaping_set_stream", "hns_diffusion_create", "hns_diffusion_destroy", "hns_diffusion_set_stream"} <= set(sq.RUNNER_SYMBOLS)
+    assert {"hns_point_motion_step", "hns_shaping_apply", "hns_diffusion_apply"} <= {s for o in sq.OPS.values() for s in o.symbols}
     assert not undecided_symbols(sq.OPS), f"entry points that are neither used by an operation of sequence_cases.OPS nor in EXEMPT: {undecided_symbols(sq.OPS)}"
     named = set(sq.RUNNER_SYMBOLS) | set(sq.EXEMPT) | {s for o in sq.OPS.values() for s in o.symbols}
     assert not named - set(_lib.SIGNATURES), f"symbols _lib.py does not bind: {sorted(named - set(_lib.SIGNATURES))}"
@@ -70,13 +75,41 @@ def test_the_table_is_well_formed():
     assert "live" in sq.OPS["trace_collide_kill_compact"].writes and "hns_point_population_select" in sq.OPS["trace_collide_kill_compact"].symbols
     for name in ("neighbours_original", "neighbours_ranked", "cell_table"):
         assert sq.OPS[name].requires == REQUIREMENTS and sq.OPS[name].writes == {"cells"} and {"grid", "order", "cells"} <= sq.OPS[name].reads, name
+    # include/hns.h: a shape reads no masks; the memo goes with a non-zero amplitude and stays behind a decay alone
+    for name, writes, memo in (("shape_turbulence", {"vel"}, "drop"), ("shape_controlled", {"vel", "f:density"}, "drop"), ("shape_decay", {"f:density"}, "keep")):
+        o = sq.OPS[name]
+        assert o.kind == "shape" and o.writes == writes and o.memo == memo and writes | {"grid"} == o.reads and o.symbols == ("hns_shaping_apply",) and not o.breaks, name
+    # a diffuse reads the grid, the masks and what it writes; with collide collision_sdf; the memo goes when the velocity is written
+    fields = set(sq.ADVECTED)
+    for name, writes, memo, count in (("diffuse_copy", {"f:density"}, "keep", 1), ("diffuse_fields", fields, "keep", 5), ("diffuse_viscosity", {"vel"}, "drop", 0),
+                                      ("diffuse_walls", {"vel", "f:density"}, "drop", 1)):
+        o = sq.OPS[name]
+        collide = sq.DIFFUSE_SPECS[name][4]
+        assert o.kind == "diffuse" and o.writes == writes and o.memo == memo and o.reads == writes | {"grid", "masks"} | ({"f:collision_sdf"} if collide else set()), name
+        assert len(sq.DIFFUSE_SPECS[name][0]) == count == len(writes - {"vel"}) and ("vel" in writes) == (sq.DIFFUSE_SPECS[name][1] != 0) and not o.breaks, name
+        assert all(0.05 <= a <= 4.0 for a in list(sq.DIFFUSE_SPECS[name][0].values()) + [sq.DIFFUSE_SPECS[name][1] or 1.0]), name
+        assert ("collision_sdf" in o.needs) == collide and "collision_sdf" not in sq.DIFFUSE_SPECS[name][0], name
+    assert sq.DIFFUSE_SPECS["diffuse_copy"][2] == 1 and all(sq.DIFFUSE_SPECS[k][2] >= 2 for k in sq.DIFFUSE_SPECS if k != "diffuse_copy")
+    assert {sq.DIFFUSE_SPECS[k][3] for k in sq.DIFFUSE_SPECS} == {"jacobi", "chebyshev"}
+    # a motion step only reads the sim and keeps the memo; its object is state of its own, and only a store moves the points
+    for name, (mode, steps, spec) in sq.MOTION_SPECS.items():
+        o = sq.OPS[name]
+        assert o.kind == "motion" and o.memo == "keep" and "motion" in o.writes and {"vel", "grid", "motion"} <= o.reads and "hns_point_motion_step" in o.symbols, name
+        assert not o.writes & set(sq.ALL_FIELDS + ("vel", "masks", "points")) and not o.breaks and ("f:collision_sdf" in o.reads) == (mode != "free") == bool(o.needs), name
+        if mode != "free":
+            assert np.isfinite(spec["max_age"]) and 0 < spec["max_age"] < 1, name  # (the ages are drawn in [0, 1): rows expire)
+    assert 0 < sq.MOTION_SPECS["motion_bounce"][2]["restitution"] < 1 and 0 < sq.MOTION_SPECS["motion_bounce"][2]["friction"] < 1
+    assert sq.OPS["motion_kill_compact"].writes == {"motion", "live"} and "hns_point_population_select" in sq.OPS["motion_kill_compact"].symbols
+    assert sq.OPS["motion_load"].reads == {"points"} and sq.OPS["motion_load"].writes == {"motion"} and sq.OPS["motion_store"].reads == {"motion"}
+    assert sq.OPS["motion_store"].writes == {"points"} and sq.OPS["motion_store"].breaks == {"fresh_order"} and "motion" in sq.RESOURCES
 
 
 def test_every_operation_is_in_a_script_and_every_script_is_of_operations():
     used = {k for s in sq.SCRIPTS for k, _ in s.steps}
     assert not used - set(sq.OPS), f"scripts name operations the vocabulary lacks: {sorted(used - set(sq.OPS))}"
     assert not set(sq.OPS) - used, f"operations no script holds: {sorted(set(sq.OPS) - used)}"
-    assert len({s.name for s in sq.SCRIPTS}) == len(sq.SCRIPTS) <= 16  # (a budget of run time: draw_scripts' own max_scripts)
+    assert len({s.name for s in sq.SCRIPTS}) == len(sq.SCRIPTS) <= 23  # (a budget of run time: the sixteen of the table before the three features, and their seven)
+    assert sq.SCRIPTS[16:] == sq.FEATURE_SCRIPTS and all(len(s.steps) <= 24 for s in sq.FEATURE_SCRIPTS)
     seeds = [sd for s in sq.SCRIPTS for _, sd in s.steps] + [s.seed for s in sq.SCRIPTS]
     assert len(seeds) == len(set(seeds))
     for s in sq.SCRIPTS:
@@ -91,13 +124,17 @@ def test_every_operation_is_in_a_script_and_every_script_is_of_operations():
 def test_every_dependent_pair_of_kinds_is_adjacent_in_a_script():
     """(A, B) with A writing what B reads, B followed by the full download both runners take after every step"""
     need = sq.needed_pairs()
-    assert len(need) >= 150 and ("splat", "core_substep") in need and ("regrid", "pressure") in need and ("deactivate", "regrid") in need
+    assert len(need) >= 283 and ("splat", "core_substep") in need and ("regrid", "pressure") in need and ("deactivate", "regrid") in need
     assert ("trace", "order_splat") not in need  # (an ordered splat requires a sort since the last write of the positions: never adjacent, by the table's `breaks`)
     for pair in (("sort", "neighbours"), ("neighbours", "neighbours"), ("cells", "neighbours"), ("neighbours", "cells"), ("gather_scatter", "neighbours"), ("trace_collide", "sort"),
-                 ("core_substep", "trace_collide"), ("upload", "trace_collide"), ("regrid", "trace_collide"), ("trace_collide", "trace_collide")):
+                 ("core_substep", "trace_collide"), ("upload", "trace_collide"), ("regrid", "trace_collide"), ("trace_collide", "trace_collide"), ("diffuse", "regrid"),
+                 ("deactivate", "diffuse"), ("set_active_masks", "diffuse"), ("diffuse", "substep"), ("shape", "core_substep"), ("regrid", "motion"), ("motion", "motion"),
+                 ("motion_store", "sort"), ("motion_store", "trace_collide"), ("motion_load", "motion"), ("diffuse", "motion"), ("shape", "motion"), ("motion", "birth")):
         assert pair in need, pair
     # never adjacent, by `breaks`: the positions moved since the sort; the last sort is by leaf; no order on the new grid
-    assert not {("trace_collide", "neighbours"), ("trace", "neighbours"), ("regrid", "neighbours"), ("regrid", "cells"), ("trace_collide", "order_splat")} & set(need)
+    assert not {("trace_collide", "neighbours"), ("trace", "neighbours"), ("regrid", "neighbours"), ("regrid", "cells"), ("trace_collide", "order_splat"),
+                ("motion_store", "neighbours"), ("motion_store", "order_splat")} & set(need)
+    assert not [p for p in need if p[0] == "motion" and p[1] not in ("motion", "motion_store", "birth")]  # a motion step writes nothing of the sim
     assert ("sort_leaf", "neighbours_original") not in need[("sort", "neighbours")] and ("sort_leaf", "cell_table") not in need[("sort", "cells")]
     missing = uncovered_pairs(sq.OPS, sq.SCRIPTS)
     assert not missing, f"pairs of operation kinds no script holds adjacent: {missing}"
@@ -134,10 +171,74 @@ def test_writers_of_the_velocity_sit_between_two_lookahead_substeps():
     voxel size: the memo is live when the writer comes"""
     writers = sq.placed_writers()
     assert {"upload_vel", "upload_field", "advect_velocity", "regrid_plain", "regrid_sourced", "regrid_seeded", "regrid_sdf", "emit_trilinear", "emit_radial", "deactivate",
-            "splat_velocity", "splat_both", "splat_stored", "order_splat_original", "substep_collision", "substep_fused"} <= set(writers)
+            "splat_velocity", "splat_both", "splat_stored", "order_splat_original", "substep_collision", "substep_fused", "shape_turbulence", "shape_controlled",
+            "diffuse_viscosity", "diffuse_walls"} <= set(writers)
     assert "splat_floats" not in writers and "order_splat_ranked" not in writers  # (float fields only: the memo is of the velocity)
     placed = sq.placements(sq.SCRIPTS)
     assert not [k for k in writers if k not in placed], f"never between two look-ahead substeps: {[k for k in writers if k not in placed]}"
+
+
+KEEPERS = ("shape_decay", "diffuse_copy", "diffuse_fields")
+
+
+def test_the_calls_that_must_keep_the_memo_sit_between_two_lookahead_substeps():
+    """the one prediction a "keep" can fail: with a producer directly on either side, expected_lookahead demands under lookahead = 1 that the substep behind the call
+    consumed the memo the substep in front of it left"""
+    assert not set(KEEPERS) & set(sq.placed_writers()) and all(sq.OPS[k].memo == "keep" for k in KEEPERS)
+    placed = sq.placements(sq.SCRIPTS)
+    for k in KEEPERS:
+        assert placed.get(k), f"{k} is never directly between two look-ahead substeps"
+        name, i = placed[k][0]
+        want = sq.expected_lookahead(sq.BY_NAME[name])
+        assert want[i] == want[i - 1] and want[i + 1] == (want[i][0] + 1, want[i][1] + 1), (k, name, i)
+    for k in ("shape_turbulence", "shape_controlled", "diffuse_viscosity", "diffuse_walls"):  # ... and what a "drop" predicts: nothing is consumed behind it
+        name, i = placed[k][0]
+        want = sq.expected_lookahead(sq.BY_NAME[name])
+        assert want[i + 1] == (want[i][0] + 1, want[i][1]), (k, name, i)
+
+
+def written_fields(name):
+    return len(sq.DIFFUSE_SPECS[name][0])
+
+
+def test_one_diffusion_meets_more_fields_and_a_larger_grid_in_one_script():
+    """the resident World's one Diffusion keeps its pooled block between calls: in ONE script a diffuse with more written float fields comes behind one with fewer (the block
+    is carved anew and drawn larger), and a diffuse comes behind a change of grid"""
+    found = []
+    for s in sq.SCRIPTS:
+        names = [k for k, _ in s.steps]
+        at = [i for i, k in enumerate(names) if k in sq.DIFFUSE_SPECS]
+        more = any(written_fields(names[j]) > written_fields(names[i]) for n, i in enumerate(at) for j in at[n + 1:])
+        regridded = any(sq.OPS[names[g]].grid for i in at[:1] for g in range(i + 1, at[-1]))  # a change of grid between the script's first diffuse and its last
+        if more and regridded:
+            found.append(s.name)
+    assert "memo_kept" in found, found
+    assert sorted(written_fields(k) for k in sq.DIFFUSE_SPECS) == [0, 1, 1, 5]
+
+
+def test_one_motion_steps_either_side_of_a_change_of_grid():
+    """the PointMotion is documented to survive regrids: in some script a motion step, a change of grid and a motion step, with no motion_load between them (World.after
+    drops the order and the population there, and must not drop the motion)"""
+    found = []
+    for s in sq.SCRIPTS:
+        ops = s.ops
+        for i, o in enumerate(ops):
+            if o.grid and i and ops[i - 1].kind == "motion":
+                j = next((j for j in range(i + 1, len(ops)) if ops[j].kind in ("motion", "motion_load")), None)
+                if j is not None and ops[j].kind == "motion" and not any(x.grid for x in ops[i + 1:j]):
+                    found.append((s.name, i))
+    assert ("motion_regrid", 3) in found and ("motion_regrid", 6) in found, found
+
+
+FRAME_HALF = ["core_substep", "shape_controlled", "diffuse_walls", "core_substep", "motion_load", "motion_bounce", "motion_kill_compact", "motion_store", "sort_voxel",
+              "order_splat_original"]
+
+
+def test_frame_shaped_is_the_frame_loop_on_two_grids():
+    s = sq.BY_NAME["frame_shaped"]
+    assert [k for k, _ in s.steps] == FRAME_HALF + ["regrid_sdf"] + FRAME_HALF and s.profile == "collide"
+    # shape_controlled and diffuse_walls both drop the memo; the motion steps, the sort and the store keep it, the ordered splat of the velocity drops it
+    assert sq.expected_lookahead(s)[:11] == [(1, 0), (1, 0), (1, 0), (2, 0), (2, 0), (2, 0), (2, 0), (2, 0), (2, 0), (2, 0), (2, 0)]
 
 
 def test_no_script_holds_a_step_that_would_be_refused():
@@ -153,7 +254,9 @@ def test_no_script_holds_a_step_that_would_be_refused():
 
 
 @pytest.mark.parametrize("gone", [("deactivate", "deactivate_counts"), ("pressure_residual",), ("order_splat_original", "order_splat_ranked"), ("birth", "birth_append", "birth_overflow"),
-                                  ("trace_collide_stop", "trace_collide_push", "trace_collide_kill_compact"), ("neighbours_original", "neighbours_ranked", "cell_table")])
+                                  ("trace_collide_stop", "trace_collide_push", "trace_collide_kill_compact"), ("neighbours_original", "neighbours_ranked", "cell_table"),
+                                  ("shape_turbulence", "shape_controlled", "shape_decay"), ("diffuse_copy", "diffuse_fields", "diffuse_viscosity", "diffuse_walls"),
+                                  ("motion_free", "motion_stick", "motion_bounce", "motion_kill_compact")])
 def test_a_deleted_operation_is_noticed(gone):
     """the conditions name what goes uncovered when an operation leaves the vocabulary"""
     ops = {k: o for k, o in sq.OPS.items() if k not in gone}
@@ -195,8 +298,15 @@ def test_first_difference_names_script_mode_step_operations_array_and_words():
 
 def test_the_generator_still_draws_scripts_that_meet_the_conditions():
     """the committed lists are what is tested; the generator is kept to draw new ones when the table grows, so it must keep working on the table as it stands"""
-    drawn, left = sq.draw_scripts()
-    assert not left and not uncovered_pairs(sq.OPS, drawn) and len(drawn) <= 14
+    drawn, left = sq.draw_scripts(max_scripts=24)
+    assert not left and not uncovered_pairs(sq.OPS, drawn) and len(drawn) <= 20
     assert not [k for k in sq.placed_writers() if k not in sq.placements(drawn)]
     assert all(not sq.refusals(s) and len(s.steps) <= 24 for s in drawn)
     assert "Script(" in sq.format_scripts(drawn)
+    placed = sq.placements(drawn)  # (the placement scripts put every writer between two producers; the keepers are placed by hand in memo_kept)
+    assert {"shape_turbulence", "shape_controlled", "diffuse_viscosity", "diffuse_walls"} <= set(placed)
+    # restricted to the pairs a grown table adds: what FEATURE_SCRIPTS' walks were drawn with
+    added = {p for p in sq.needed_pairs() if {"shape", "diffuse", "motion", "motion_load", "motion_store"} & set(p)}
+    more, left = sq.draw_scripts(seed=2027, only=added, first_seed=1001, max_scripts=10)
+    assert len(added) == 81 and not left and added <= set(sq.covered_pairs(more)) and all(not sq.refusals(s) and len(s.steps) <= 24 for s in more)
+    assert min(sd for s in more for _, sd in s.steps) > 1001 and not any(s.name.startswith("placement") for s in more)

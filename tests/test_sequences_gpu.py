@@ -5,11 +5,18 @@ The twin's pass of a script runs first, every step on a sim, an order and a popu
 the pool of device memory filled with a non-zero byte. Then ONE sim runs the script from its first step to its last, once with lookahead = auto and once with
 lookahead = 1, and after every step everything the step returned and the full downloaded state must be the twin's, byte for byte. Nothing here is a tolerance.
 
-Byte equality with the twin compares the library with itself, so one collision trace and one neighbourhood query of the twin's pass of frame_points are held once to
-the numpy mirrors of the per-call tests (test_the_twin_equals_the_mirrors): a twin that is wrong in the way the resident sim is wrong cannot pass."""
+The resident World keeps its PointMotion, its Shaping and its Diffusion through every change of grid (they are bound to no grid); the twin makes them anew for every step.
+check_liveness counts, on the twin's record and the state captured in front of each step, what the shape, diffuse and motion steps met -- velocity words moved, the
+control below, inside and above its range, inactive and solid voxels, words changed and kept, status 0 and 1, the hit bits, rows expired by age, rows a kill kept --
+and prints each count before it asserts.
+
+Byte equality with the twin compares the library with itself, so one collision trace and one neighbourhood query of the twin's pass of frame_points, and one controlled
+shape, one diffuse with walls and one bounce of its pass of frame_shaped, are held once to the numpy mirrors of the per-call tests (test_the_twin_equals_the_mirrors):
+a twin that is wrong in the way the resident sim is wrong cannot pass."""
 import numpy as np
 import pytest
 
+import frame_cases as fc
 import sequence_cases as sq
 
 pytestmark = pytest.mark.gpu
@@ -41,10 +48,105 @@ def collide_bits(script, out):
     return seen
 
 
+HIT_BITS = (1, 2, 4, 8, 16)  # of a motion step: bounced, put back (or stuck), killed, started inside, reflected
+FEATURE_SEEN = {}  # script name -> counts over the twin's shape, diffuse and motion steps; filled by check_liveness
+
+
+def words(a):
+    return np.ascontiguousarray(a).view(np.uint32).reshape(-1)
+
+
+def state_before(script, twin, i):
+    """the state the twin's step i was opened from"""
+    return twin[i - 1][1] if i else sq.initial_state(script.name)
+
+
+def active_of(state):
+    n = 512 * len(state["origins"])
+    return np.ones(n, bool) if state["masks"] is None else fc.unpack(state["masks"]).reshape(-1)
+
+
+def feature_counts(script, twin):
+    """what the twin's shape, diffuse and motion steps of a script met, from its record and the state captured in front of each step; asserts what EVERY such step must
+    show and returns the counts that only the suite as a whole must show"""
+    names = [k for k, _ in script.steps]
+    out = [t[0] for t in twin]
+    seen = {}
+
+    def add(key, n):
+        seen[key] = seen.get(key, 0) + int(n)
+
+    for i in steps_of(script, ("shape",)):
+        before, after = state_before(script, twin, i), twin[i][1]
+        moved = int((words(after["vel"]) != words(before["vel"])).sum())
+        faded = int((words(after["density"]) != words(before["density"])).sum())
+        line = f"{script.name} step {i} ({names[i]}): {moved} velocity words and {faded} density words changed"
+        if names[i] == "shape_decay":
+            assert moved == 0 and faded > 0, line
+        else:
+            assert moved > 0 and (faded > 0) == (names[i] == "shape_controlled"), line
+        if names[i] == "shape_controlled":
+            c, lo, hi = before["density"], np.float32(sq.CONTROL["control_lo"]), np.float32(sq.CONTROL["control_hi"])
+            split = (int((c < lo).sum()), int(((c >= lo) & (c <= hi)).sum()), int((c > hi).sum()))
+            line += f"; control (below, inside, above): {split}"
+            assert all(split), line
+        print(line)
+    for i in steps_of(script, ("diffuse",)):
+        before, after = state_before(script, twin, i), twin[i][1]
+        fields, viscosity, _, _, collide = sq.DIFFUSE_SPECS[names[i]]
+        written = list(fields) + (["vel"] if viscosity else [])
+        changed = sum(int((words(after[k]) != words(before[k])).sum()) for k in written)
+        total = sum(words(before[k]).size for k in written)
+        active = active_of(before)
+        line = f"{script.name} step {i} ({names[i]}): {changed} of {total} words of {written} changed; {int((~active).sum())} of {active.size} voxels inactive"
+        add("diffuse steps with inactive voxels", not active.all())
+        if collide:
+            solid = before["collision_sdf"] < np.float32(0.0)
+            line += f", {int(solid.sum())} solid, {int((active & ~solid).sum())} unknowns"
+            add("diffuse_walls steps with solid voxels and unknowns", solid.any() and (active & ~solid).any())
+        print(line)
+        assert 0 < changed < total, line
+        for k in after:  # what the call does not list keeps every byte (masks=None in the initial state is every bit set)
+            if k not in written and not (k == "masks" and before[k] is None):
+                assert np.array_equal(sq.as_words(after[k]), sq.as_words(before[k])), (line, k)
+    motions = steps_of(script, ("motion",))
+    for i in motions:
+        mode, _, spec = sq.MOTION_SPECS[names[i]]
+        before, status, hit = state_before(script, twin, i), out[i]["status"], out[i]["hit"]
+        for bit in HIT_BITS:
+            add((mode, bit), ((hit & bit) != 0).sum())
+        age = before["motion_age"].copy()
+        for _ in range(out[i]["steps"]):
+            age = age + np.float32(sq.DT)
+        with np.errstate(invalid="ignore"):  # rows that took their steps, were not killed, and end at or beyond max_age: the mirror of the status rule's last clause
+            expired = np.isfinite(before["motion_xyz"]).all(1) & ((hit & 4) == 0) & ~(age < np.float32(spec.get("max_age", np.inf)))
+        assert not status[expired].any(), f"{script.name} step {i} ({names[i]}): rows at or beyond max_age with status 1: {np.flatnonzero(expired & (status != 0))[:8].tolist()}"
+        add("expired", expired.sum())
+        print(f"{script.name} step {i} ({names[i]}, {out[i]['steps']} steps): status (0, 1) ({int((status == 0).sum())}, {int((status == 1).sum())}), expired {int(expired.sum())}, "
+              f"rows per hit bit {[int(((hit & b) != 0).sum()) for b in HIT_BITS]}")
+    if motions:
+        both = [(int((out[i]["status"] == 0).sum()), int((out[i]["status"] == 1).sum())) for i in motions]
+        assert any(a > 0 and b > 0 for a, b in both), f"{script.name}: no motion step left both status 0 and status 1: {both}"
+        assert all(set(np.unique(out[i]["status"])) <= {0, 1} for i in motions)
+    kills = [i for i in motions if names[i] == "motion_kill_compact"]
+    if kills:
+        kept = [(int((out[i]["slot"] >= 0).sum()), len(out[i]["slot"])) for i in kills]
+        print(f"{script.name}: motion kills (kept, rows): {kept}")
+        assert any(0 < k < n for k, n in kept), f"{script.name}: no motion kill both dropped and kept a row: {kept}"
+        for i in kills:
+            assert out[i]["counts"][0] == int((out[i]["slot"] >= 0).sum()) == int((out[i]["status"] >= 1).sum()) == twin[i][1]["live"]
+            live = out[i]["counts"][0]  # the compacted rows: positions behind the live count are the fill, in front of it finite
+            assert np.isnan(twin[i][1]["motion_xyz"][live:]).all() and np.isfinite(twin[i][1]["motion_xyz"][:live]).all()
+    return seen
+
+
 def check_liveness(script, twin):
     """the script did exercise the state it is about -- counted from the twin's recorded outputs, so that a script which never reaches the hidden state cannot pass empty"""
     names = [k for k, _ in script.steps]
     out = [t[0] for t in twin]
+    if steps_of(script, ("shape", "diffuse", "motion")):
+        FEATURE_SEEN[script.name] = feature_counts(script, twin)
+        print(f"{script.name}: {FEATURE_SEEN[script.name]}")
     changes = steps_of(script, ("regrid", "emit"))
     if changes:
         moved = [out[i]["leaves"] for i in changes]
@@ -132,9 +234,95 @@ def test_every_collision_mode_sets_its_own_bit_somewhere():
     assert set(total) == {(m, b) for m, bits in MODE_BIT.items() for b in bits} and all(v > 0 for v in total.values()), total
 
 
+def test_every_motion_mode_and_every_class_of_voxel_occurs_somewhere():
+    """over the twin's passes of the scripts that shape, diffuse or step points (counted by check_liveness where the comparison above has run; a script it has not seen
+    runs its twin's pass here): bit 1 and bit 16 under bounce, bit 2 under stick, bit 4 under kill, bit 8 somewhere, a row that expires by age; a diffuse with inactive
+    voxels, and a diffuse_walls with solid voxels and unknowns"""
+    total = {}
+    for script in sq.SCRIPTS:
+        if steps_of(script, ("shape", "diffuse", "motion")):
+            seen = FEATURE_SEEN.get(script.name)
+            if seen is None:
+                seen = feature_counts(script, sq.twin_record(script.name))
+            for k, v in seen.items():
+                total[k] = total.get(k, 0) + v
+    print(f"counts over the suite: {total}")
+    for key in (("bounce", 1), ("bounce", 16), ("stick", 2), ("kill", 4), "expired", "diffuse steps with inactive voxels", "diffuse_walls steps with solid voxels and unknowns"):
+        assert total.get(key, 0) > 0, (key, total)
+    assert sum(v for k, v in total.items() if isinstance(k, tuple) and k[1] == 8) > 0, total
+    assert not any(v for k, v in total.items() if isinstance(k, tuple) and k[0] == "free"), total  # (mode free looks at no collider)
+
+
+def frame_shaped_against_the_mirrors():
+    """one shape_controlled, one diffuse_walls and one motion_bounce of the twin's pass of frame_shaped, each on the state the twin captured in front of the step, every word"""
+    import diffusion_cases as dc
+    import point_motion_cases as mc
+    import shaping_cases as shc
+    from oracle_lib import OracleGrid, oracle_device
+    from test_points_gpu import assert_same_bits, assert_words
+
+    script = sq.BY_NAME["frame_shaped"]
+    names = [k for k, _ in script.steps]
+    twin = sq.twin_record(script.name)
+    fields = sq.PROFILES[script.profile]
+
+    def unlisted_kept(i, written):
+        before, after = state_before(script, twin, i), twin[i][1]
+        for k in after:
+            if k not in written and not (k == "masks" and before[k] is None):
+                assert np.array_equal(sq.as_words(after[k]), sq.as_words(before[k])), f"frame_shaped step {i} ({names[i]}) changed {k}"
+
+    # the shape: the turbulence of the step's own rng, the weight from density before its decay
+    i = names.index("shape_controlled")
+    before, after = state_before(script, twin, i), twin[i][1]
+    turbulence = sq._turbulence(np.random.default_rng(script.steps[i][1]), **sq.CONTROL)
+    vel, out = shc.apply_mirror(dc.coords(before["origins"]), before["vel"], {"density": before["density"]}, sq.DT, turbulence, sq.DECAY)
+    w = (before["density"] - np.float32(sq.CONTROL["control_lo"])) / np.float32(sq.CONTROL["control_hi"] - sq.CONTROL["control_lo"])
+    print(f"frame_shaped step {i}: {turbulence['octaves']} octaves; weights (0, between, 1): {int((w <= 0).sum())}, {int(((w > 0) & (w < 1)).sum())}, {int((w >= 1).sum())}; "
+          f"{int((words(vel) != words(before['vel'])).sum())} of {vel.size} velocity words move in the mirror")
+    assert (w <= 0).any() and ((w > 0) & (w < 1)).any() and (w >= 1).any() and (words(vel) != words(before["vel"])).mean() > 0.25
+    assert_words(after["vel"], vel, "frame_shaped's shape_controlled against shaping_cases.apply_mirror: vel")
+    assert_words(after["density"], out["density"], "frame_shaped's shape_controlled against shaping_cases.apply_mirror: density")
+    unlisted_kept(i, ("vel", "density"))
+    # the diffuse: the captured masks and collision_sdf decide the unknowns, the walls and the faces
+    i = names.index("diffuse_walls")
+    before, after = state_before(script, twin, i), twin[i][1]
+    active = active_of(before)
+    want = dc.apply_mirror(before["origins"], {k: before[k] for k in ["vel"] + fields}, sq.DT, sq.VS, active=active, **sq.diffuse_arguments("diffuse_walls"))
+    unknown, solid = dc.classes(len(active), active, before["collision_sdf"], True, 0.0)
+    print(f"frame_shaped step {i}: {int(unknown.sum())} unknowns, {int(solid.sum())} solid voxels of {len(active)}; the mirror changes "
+          f"{int((words(want['vel']) != words(before['vel'])).sum())} velocity words and {int((words(want['density']) != words(before['density'])).sum())} density words")
+    assert unknown.any() and solid.any() and (words(want["density"]) != words(before["density"])).any() and (words(want["vel"]) != words(before["vel"])).any()
+    for k in ["vel"] + fields:
+        assert_words(after[k], want[k], f"frame_shaped's diffuse_walls against diffusion_cases.apply_mirror: {k}")
+    unlisted_kept(i, ("vel", "density"))
+    # the motion step (the device-semantics build of the oracle: the rows hold NaN and infinite positions and velocities; a NaN is equal to any NaN, as in
+    # tests/test_point_motion_gpu.py's special values)
+    i = names.index("motion_bounce")
+    before, after = state_before(script, twin, i), twin[i]
+    mode, _, spec = sq.MOTION_SPECS["motion_bounce"]
+    steps = after[0]["steps"]
+    assert names[i - 1] == "motion_load" and mode == "bounce" and not np.isfinite(before["motion_xyz"]).all() and not np.isfinite(before["motion_vel"]).all()
+    G = OracleGrid(before["origins"], lib=oracle_device())
+    inv_dx = float(np.float32(1.0) / np.float32(sq.VS))
+    x, v, age, status, hit, _ = mc.motion_mirror(G, before["vel"], before["collision_sdf"], before["motion_xyz"], before["motion_vel"], before["motion_age"], sq.DT, inv_dx, steps,
+                                                 mode, dict(spec, threshold=0.0))
+    print(f"frame_shaped step {i}: {steps} steps; the mirror's status (0, 1) ({int((status == 0).sum())}, {int((status == 1).sum())}), rows per hit bit "
+          f"{[int(((hit & b) != 0).sum()) for b in HIT_BITS]}, {int((words(x).reshape(-1, 3) != words(before['motion_xyz']).reshape(-1, 3)).any(1).sum())} rows moved")
+    assert (hit & 1).any() and (hit & 16).any() and (hit == 0).any() and status.any() and not status.all()
+    assert np.array_equal(after[0]["status"], status), f"status differs at rows {np.flatnonzero(after[0]['status'] != status)[:8].tolist()}"
+    assert np.array_equal(after[0]["hit"], hit), f"hit differs at rows {np.flatnonzero(after[0]['hit'] != hit)[:8].tolist()}"
+    for k, a in (("xyz", x), ("vel", v), ("age", age)):
+        assert_same_bits(after[1]["motion_" + k], a, f"frame_shaped's motion_bounce against point_motion_cases.motion_mirror: {k}")
+    unlisted_kept(i, ("motion_xyz", "motion_vel", "motion_age"))
+
+
 def test_the_twin_equals_the_mirrors():
     """frame_points' trace_collide_push against points_collide_cases.collide_mirror, and its first neighbours_original against neighbour_cases.restate, each on the state
-    the twin captured in front of the step: words for the positions, bytes for status and hit; bytes of count, density and push for the 1,500 points"""
+    the twin captured in front of the step: words for the positions, bytes for status and hit; bytes of count, density and push for the 1,500 points. Then frame_shaped's
+    first shape_controlled against shaping_cases.apply_mirror, its first diffuse_walls against diffusion_cases.apply_mirror on the captured masks and collision_sdf, and its
+    first motion_bounce against point_motion_cases.motion_mirror on the oracle's device-semantics build: every word of everything the step may write, and everything else
+    of the captured state unchanged"""
     import neighbour_cases as nc
     import points_collide_cases as cc
     from hnanosolver_amd import _lib, api
@@ -169,6 +357,7 @@ def test_the_twin_equals_the_mirrors():
     print(f"frame_points step {j}: {int((r.count != 0).sum())} of {len(r.count)} points have neighbours, {len(r.pairs)} pairs, {int(nc.takes_part(grid, len(before['origins']), before['xyz']).sum())} take part")
     assert len(r.count) == sq.N_POINTS and (r.count != 0).any() and (r.count == 0).any() and np.count_nonzero(r.push)
     nc.same((after["count"], after["density"], after["push"]), r, "frame_points' first neighbours_original against the restatement")
+    frame_shaped_against_the_mirrors()
 
 
 def test_the_twin_is_deterministic():
